@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- EnSRF cov+update throughput on MI355X (driver contract).
 
-    python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W [--scaling strong --workload cfg4]
 
@@ -82,7 +82,15 @@ def parse_args():
     ap.add_argument("--cpu-obs", type=int, default=8, help="timed observations of the CPU baseline (BASELINE.md 3)")
     ap.add_argument("--cpu-warm", type=int, default=2, help="warm-up observations of the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=25.0, help="time budget of the CPU baseline")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed to DIR/<name>.npy (float64): the posterior "
+                         "members of a fixed, seeded sample of the global state rows and the per-ob diagnostics")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 # ----------------------------------------------------------------------------------------------
@@ -262,7 +270,45 @@ def measure(args, wl, strong, world, rank, eng, dist, torch, seed, balance=True)
     return dict(sh=sh, X=X, post=post, pick=pick, glat=glat, glon=glon, lat2=lat2, lon2=lon2, n_lead=n_lead, ncol_g=ncol_g,
                 rows_g=rows_g, rows=rows, ncol_l=ncol_l, elapsed=elapsed, my_elapsed=my_elapsed, state_ms=state_ms, obs_ms=obs_ms,
                 launches=launches, path_taken=path_taken, n_active=int(d["assimilated"].sum()), pairs=pairs,
-                kind=ctx.get_option("phase_a_kind"))
+                kind=ctx.get_option("phase_a_kind"), diag=d)
+
+
+DUMP_POST_BYTES = 32 << 20     # --dump-outputs: the posterior sample stays under 32 MiB ...
+DUMP_MAX_OBS = 1 << 16         # ... and the per-ob diagnostics under 2.6 MB
+
+
+def dump_outputs(out_dir, r, seed, world, rank, dist, torch):
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files in `out_dir`.
+    posterior_members.npy: (S, M) posterior members of S global state rows, all of them when they fit in DUMP_POST_BYTES,
+    otherwise a seeded sample (sorted row order) that depends only on the workload, so two builds, or two rank counts,
+    write the same rows; every rank contributes the rows it owns.  ob_<field>.npy: the per-ob diagnostics of the cycle
+    (prior_mean, prior_var, post_mean, post_var, assimilated as 0/1), every ob up to DUMP_MAX_OBS, else a seeded sample."""
+    sh, post, M = r["sh"], r["post"], r["sh"].M
+    rows_g, ncol_g = r["rows_g"], r["ncol_g"]
+    n_rows = min(rows_g, DUMP_POST_BYTES // (8 * M))
+    grow = np.arange(rows_g) if n_rows == rows_g else np.sort(np.random.default_rng(5000 + seed).choice(rows_g, n_rows, replace=False))
+    lead, col = grow // ncol_g, grow % ncol_g
+    mine = (col >= sh.lo) & (col < sh.hi)
+    lrow = lead[mine] * (sh.hi - sh.lo) + (col[mine] - sh.lo)     # local rows of one lead are one contiguous run
+    vals = post[torch.as_tensor(lrow, device=post.device)].cpu().numpy()
+    parts = [(np.flatnonzero(mine), vals)]
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, (np.flatnonzero(mine), vals))
+    if rank != 0:
+        return
+    sample = np.full((n_rows, M), np.nan)
+    for pos, v in parts:
+        sample[pos] = v
+    d = r["diag"]
+    P = len(d["post_mean"])
+    oi = np.arange(P) if P <= DUMP_MAX_OBS else np.sort(np.random.default_rng(6000 + seed).choice(P, DUMP_MAX_OBS, replace=False))
+    arrays = {"posterior_members": sample}
+    for k in ("prior_mean", "prior_var", "post_mean", "post_var", "assimilated"):
+        arrays["ob_" + k] = np.asarray(d[k], dtype=np.float64)[oi]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def init_library_comm(eng, rank, world, dist, torch, timeout_s=120.0):
@@ -364,6 +410,8 @@ def main():
 
     seed = 1000 + sorted(WORKLOADS).index(args.workload)
     r = measure(args, wl, strong, world, rank, eng, dist, torch, seed, balance=not args.no_balance)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r, seed, world, rank, dist, torch)
     sh, X, post, pick = r["sh"], r["X"], r["post"], r["pick"]
     glat, glon, lat2, lon2 = r["glat"], r["glon"], r["lat2"], r["lon2"]
     n_lead, ncol_g, rows_g, rows, ncol_l = r["n_lead"], r["ncol_g"], r["rows_g"], r["rows"], r["ncol_l"]

@@ -1,6 +1,7 @@
 """Run by tests/test_cpu_host.py in a child process with the clang ASan runtime LD_PRELOADed: loads the host-sanitised build of the
 C-ABI library (make -C efa_xray_amd/csrc asan) and walks every entry point's argument checks -- null context, null out-pointers,
-unknown options -- with no GPU call behind them.  Any AddressSanitizer / UBSan report aborts the process (halt_on_error)."""
+unknown options -- with no GPU call behind them: the test hides every GPU from this process, and the walk insists on seeing none.
+Any AddressSanitizer / UBSan report aborts the process (halt_on_error)."""
 import ctypes
 import importlib.util
 import os
@@ -24,13 +25,11 @@ assert lib.efa_abi_version() == 1
 n = ctypes.c_int(-1)
 assert lib.efa_device_count(ctypes.byref(n)) == 0 and n.value >= 0
 assert lib.efa_device_count(None) < 0
+assert n.value == 0, "every GPU must be hidden from the sanitised process (ROCR_VISIBLE_DEVICES=-1), saw %d" % n.value
 ctx = ctypes.c_void_p()
 rc = lib.efa_ctx_create(0, ctypes.byref(ctx))
-if n.value == 0:
-    assert rc == ns["EFA_ERR_NO_DEVICE"] and not ctx.value, rc
-    assert b"no CPU fallback" in lib.efa_last_error()
-elif rc == 0:
-    lib.efa_ctx_destroy(ctx)
+assert rc == ns["EFA_ERR_NO_DEVICE"] and not ctx.value, rc
+assert b"no CPU fallback" in lib.efa_last_error()
 assert lib.efa_ctx_create(0, None) < 0
 assert lib.efa_ctx_destroy(None) == 0
 

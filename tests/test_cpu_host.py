@@ -97,7 +97,8 @@ def test_no_cpu_fallback_without_gpu():
 def test_host_side_of_the_c_abi_under_address_and_ub_sanitizers():
     """SURVEY.md section 5's sanitizer row, on the CPU build only (no GPU sanitizers on this pool): the host side of the C ABI compiled
     with -fsanitize=address,undefined (make asan; device code as in the product), every entry point's argument checks walked in a
-    child process under the preloaded clang ASan runtime.  A sanitizer report aborts the child."""
+    child process under the preloaded clang ASan runtime.  A sanitizer report aborts the child.  Every GPU is hidden from the
+    child, so it walks the same host-only path on a GPU box as on a CPU box (the GPU runtime never starts under the sanitizer)."""
     import glob
     csrc = os.path.join(ROOT, "efa_xray_amd", "csrc")
     lib = os.path.join(ROOT, "efa_xray_amd", "libefa_hip_asan.so")
@@ -108,7 +109,7 @@ def test_host_side_of_the_c_abi_under_address_and_ub_sanitizers():
     if not rt:
         pytest.skip("clang ASan runtime not found")
     env = dict(os.environ, LD_PRELOAD=rt[0], ASAN_OPTIONS="detect_leaks=0:halt_on_error=1:abort_on_error=0:protect_shadow_gap=0",
-               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", ROCR_VISIBLE_DEVICES="-1", HIP_VISIBLE_DEVICES="-1")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_asan_abi_driver.py"), lib], env=env,
                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
     text = out.stdout.decode("utf-8", "replace")
