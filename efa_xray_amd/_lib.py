@@ -25,6 +25,10 @@ PATH_AUTO = 0
 PATH_SWEEP = 1
 PATH_TRANSFORM = 2
 
+RELAX_NONE = 0
+RELAX_RTPP = 1
+RELAX_RTPS = 2
+
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_uint8_p = ctypes.POINTER(ctypes.c_uint8)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
@@ -41,6 +45,7 @@ SIGNATURES = {
     "efa_ctx_set_stream": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "efa_ctx_set_option": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_long]),
     "efa_ctx_get_option": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_long)]),
+    "efa_ctx_set_relaxation": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double]),
     "efa_ctx_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
     "efa_malloc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, c_void_pp]),
     "efa_free": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
@@ -278,6 +283,10 @@ class Context(object):
         v = ctypes.c_long(0)
         _check(self.lib, self.lib.efa_ctx_get_option(self.handle, key.encode(), ctypes.byref(v)))
         return v.value
+
+    def set_relaxation(self, kind, alpha=0.0):
+        """Posterior relaxation of every later state phase on this context (RELAX_NONE / RELAX_RTPP / RELAX_RTPS)."""
+        _check(self.lib, self.lib.efa_ctx_set_relaxation(self.handle, int(kind), float(alpha)))
 
     def set_stream(self, hip_stream):
         _check(self.lib, self.lib.efa_ctx_set_stream(self.handle, ctypes.c_void_p(hip_stream or 0)))

@@ -18,18 +18,41 @@ from efa_xray_amd import _lib
 from efa_xray_amd.assimilation.assimilation import Assimilation
 
 
+def relaxation_setting(rtps=None, rtpp=None):
+    """(kind, alpha) for efa_ctx_set_relaxation from the `rtps` / `rtpp` keywords; ValueError on a bad pair."""
+    if rtps is not None and rtpp is not None:
+        raise ValueError("rtps and rtpp are exclusive: set at most one of them")
+    for name, val, top in (("rtps", rtps, None), ("rtpp", rtpp, 1.0)):
+        if val is None:
+            continue
+        try:
+            a = float(val)
+        except (TypeError, ValueError):
+            raise ValueError("%s=%r: expected a number" % (name, val))
+        if not np.isfinite(a) or a < 0.0 or (top is not None and a > top):
+            raise ValueError("%s=%r: expected a finite number in [0, %s]" % (name, val, "inf)" if top is None else "1]"))
+        return (_lib.RELAX_RTPS if name == "rtps" else _lib.RELAX_RTPP), a
+    return _lib.RELAX_NONE, 0.0
+
+
 class EnSRF(Assimilation):
     def __init__(self, state, obs, nproc=1, inflation=None, verbose=True, loc=False, **kw):
         """Extra keyword-only options (all default to reference behaviour):
         device   -- HIP device ordinal (default 0)
         obs_batch-- observations fused per sweep launch (1..64)
         path     -- 'auto' | 'sweep' | 'transform' (how the state sweep runs)
+        rtps     -- posterior relaxation to prior spread, factor >= 0 (Whitaker & Hamill 2012)
+        rtpp     -- posterior relaxation to prior perturbations, factor in [0, 1]
+                    (at most one of the two; None: no relaxation)
         """
         device = kw.pop("device", 0)
         self.obs_batch = kw.pop("obs_batch", None)
         self.path = kw.pop("path", None)
+        rtps = kw.pop("rtps", None)
+        rtpp = kw.pop("rtpp", None)
         if kw:
             raise TypeError("unexpected keyword arguments %r" % sorted(kw))
+        self.relaxation = relaxation_setting(rtps, rtpp)
         Assimilation.__init__(self, state, obs, nproc, inflation, verbose, device=device)
         self.loc = loc
         self.last_timing = None
@@ -73,6 +96,7 @@ class EnSRF(Assimilation):
         path = {None: _lib.PATH_AUTO, "auto": _lib.PATH_AUTO, "sweep": _lib.PATH_SWEEP,
                 "transform": _lib.PATH_TRANSFORM}[self.path]
         ctx.set_option("path", path)
+        ctx.set_relaxation(*self.relaxation)   # every call: the context is shared per device
 
     # ------------------------------------------------------------------
     def update(self):

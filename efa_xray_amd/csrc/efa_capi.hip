@@ -178,6 +178,12 @@ struct efa_ctx {
   bool grid_ready = false;   // efa_ensrf_cycle_dev brought the grid up to date ahead of Phase A: the state phase must not again
   DevBuf glat, glon;  // grid lat/lon [ncol]
   DevBuf xm_ws;       // means for efa_state_cycle_dev
+  // --- posterior relaxation (efa_ctx_set_relaxation) ------------------------------------------------------
+  int relax_kind = EFA_RELAX_NONE;
+  double relax_alpha = 0.0;
+  DevBuf relax_T;      // RTPP: (1-alpha) T + alpha I [M][M]
+  DevBuf relax_ss;     // standalone passes: sum of squared prior deviations per row [rows]
+  DevBuf relax_prior;  // standalone RTPP with the posterior written over the prior: a copy of the prior [rows][M]
   // --- f1: interpolation stencils -------------------------------------------------
   DevBuf fs_idx, fs_wts;  // efa_forward_stencil_dev staging
   DevBuf f_glat, f_glon, f_sl, f_cl, f_valids, f_var, f_time, f_lat, f_lon, f_near, f_idx, f_wts, f_status;
@@ -203,6 +209,7 @@ struct efa_ctx {
     double* post = nullptr;
     long rows = 0;
     int pair = 0;  // event pair of the launched transform
+    long launches = 0;  // state-phase launches it took (the transform, and the relaxation's)
     bool obs_out = true;
   } spec;
   double state_ms_sum = 0.0, obs_ms_sum = 0.0;  // timing 2: sums since the previous efa_last_timing
@@ -288,6 +295,76 @@ int check_common(int M, long P) {
 }
 
 bool auto_transform(int M, long n_active, bool member_form);  // (with Phase B's path choice, below)
+
+// ---- posterior relaxation (RTPP / RTPS, efa_relax.hip) ----------------------------------------------------------
+// Applied only where a state phase writes the caller's state rows, and only when an ob was assimilated (otherwise the posterior
+// is returned exactly as without it).
+bool relax_on(const efa_ctx* c) {
+  return c->relax_kind != EFA_RELAX_NONE && c->relax_alpha != 0.0 && c->P > 0 && c->n_active > 0;
+}
+// standalone passes, before the state phase: what the relaxation needs of the prior rows Xin (members or perturbations) -- RTPS
+// their spread, RTPP the rows themselves (copied when the state phase writes over them)
+int relax_prepare(efa_ctx* c, long rows, int M, const double* Xin, const double* Xout, const double** prior, long* nl) {
+  *prior = nullptr;
+  if (c->relax_kind == EFA_RELAX_RTPS) {
+    EFA_TRY(c->relax_ss.reserve((size_t)rows * sizeof(double)));
+    EFA_HIP(launch_row_spread(rows, M, Xin, c->relax_ss.as<double>(), c->stream));
+    ++*nl;
+    return EFA_OK;
+  }
+  const size_t bytes = (size_t)rows * M * sizeof(double);
+  const char *a = reinterpret_cast<const char*>(Xin), *b = reinterpret_cast<const char*>(Xout);
+  if (a + bytes <= b || b + bytes <= a) {
+    *prior = Xin;
+  } else {
+    EFA_TRY(c->relax_prior.reserve(bytes));
+    EFA_HIP(hipMemcpyAsync(c->relax_prior.p, Xin, bytes, hipMemcpyDeviceToDevice, c->stream));
+    *prior = c->relax_prior.as<double>();
+  }
+  return EFA_OK;
+}
+// ... and after it, in place on the posterior rows
+int relax_apply(efa_ctx* c, long rows, int M, double* Xout, const double* prior, long* nl) {
+  EFA_HIP(launch_relax_rows(rows, M, c->relax_kind == EFA_RELAX_RTPP ? 1 : 0, c->relax_alpha, Xout, c->relax_ss.as<double>(), prior,
+                            c->stream));
+  ++*nl;
+  return EFA_OK;
+}
+// The member-form state transform, prior members X -> posterior members post through [T | w], with the relaxation: RTPP folded
+// into T (Xb' ((1-alpha) T + alpha I)), RTPS fused into the transform up to 136 members, the standalone passes above that.
+int member_transform(efa_ctx* c, long rows, int M, const double* X, double* post, const double* T, const double* w, long* nl) {
+  hipStream_t s = c->stream;
+  TransformArgs t{};
+  t.Xin = X;
+  t.Xout = post;
+  t.nrows = rows;
+  t.M = M;
+  t.T = T;
+  t.w = w;
+  t.fused_members = 1;
+  *nl = 1;
+  if (!relax_on(c)) {
+    EFA_HIP(launch_transform(t, s));
+    return EFA_OK;
+  }
+  if (c->relax_kind == EFA_RELAX_RTPP) {
+    EFA_TRY(c->relax_T.reserve((size_t)M * M * sizeof(double)));
+    EFA_HIP(launch_relax_fold(M, c->relax_alpha, T, c->relax_T.as<double>(), s));
+    t.T = c->relax_T.as<double>();
+    EFA_HIP(launch_transform(t, s));
+    *nl = 2;
+    return EFA_OK;
+  }
+  if (transform_rtps_supported(M)) {
+    EFA_HIP(launch_transform_rtps(t, c->relax_alpha, s));
+    return EFA_OK;
+  }
+  const double* prior = nullptr;
+  EFA_TRY(relax_prepare(c, rows, M, X, post, &prior, nl));
+  EFA_HIP(launch_transform(t, s));
+  EFA_TRY(relax_apply(c, rows, M, post, prior, nl));
+  return EFA_OK;
+}
 
 // ---- Phase A ---------------------------------------------------------------
 int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const double* ob_value,
@@ -611,15 +688,7 @@ int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const d
           // the host -- what the host waits for below --, the obs interval ends and the state interval of this pair begins
           EFA_HIP(hipEventRecord(c->ev[2 + 2 * pr], s));
           c->obs_end_ev = 2 + 2 * pr;
-          TransformArgs t{};
-          t.Xin = c->spec.X;
-          t.Xout = c->spec.post;
-          t.nrows = c->spec.rows;
-          t.M = M;
-          t.T = Yw + (size_t)P * M;
-          t.w = ymw + P;
-          t.fused_members = 1;
-          EFA_HIP(launch_transform(t, s));
+          EFA_TRY(member_transform(c, c->spec.rows, M, c->spec.X, c->spec.post, Yw + (size_t)P * M, ymw + P, &c->spec.launches));
           if (c->timing) EFA_HIP(hipEventRecord(c->ev[3 + 2 * pr], s));
           c->spec.pair = pr;
           spec_now = true;
@@ -956,6 +1025,8 @@ int state_phase(efa_ctx* c, long rows, int M, const double* xm_in, const double*
   EFA_TRY(prepare_grid(c, grid_lat, grid_lon, ncol, n_lead, rows));
   hipStream_t s = c->stream;
   if (c->timing) EFA_HIP(hipEventRecord(c->ev[2], s));
+  const bool relax = relax_on(c);
+  const double* prior = nullptr;
   if (c->P > 0 && c->n_active > 0 && want_transform(c, false)) {
     TransformArgs t{};
     t.Xin = Xp_in;
@@ -967,11 +1038,22 @@ int state_phase(efa_ctx* c, long rows, int M, const double* xm_in, const double*
     t.T = c->Yw.as<double>() + (size_t)c->P * M;
     t.w = c->ymw.as<double>() + c->P;
     t.fused_members = 0;
-    EFA_HIP(launch_transform(t, s));
     c->state_launches = 1;
+    if (relax && c->relax_kind == EFA_RELAX_RTPP) {  // Xap = Xbp ((1-alpha) T + alpha I); xam as without it
+      EFA_TRY(c->relax_T.reserve((size_t)M * M * sizeof(double)));
+      EFA_HIP(launch_relax_fold(M, c->relax_alpha, t.T, c->relax_T.as<double>(), s));
+      t.T = c->relax_T.as<double>();
+      c->state_launches++;
+    } else if (relax) {  // RTPS in perturbation form: the standalone passes
+      EFA_TRY(relax_prepare(c, rows, M, Xp_in, Xp_out, &prior, &c->state_launches));
+    }
+    EFA_HIP(launch_transform(t, s));
+    if (relax && c->relax_kind == EFA_RELAX_RTPS) EFA_TRY(relax_apply(c, rows, M, Xp_out, prior, &c->state_launches));
     c->path_taken = EFA_PATH_TRANSFORM;
   } else {
+    if (relax) EFA_TRY(relax_prepare(c, rows, M, Xp_in, Xp_out, &prior, &c->state_launches));
     EFA_TRY(state_sweeps(c, rows, xm_in, Xp_in, xm_out, Xp_out, ncol));
+    if (relax) EFA_TRY(relax_apply(c, rows, M, Xp_out, prior, &c->state_launches));
   }
   EFA_TRY(finish_state_timing(c, s));
   return EFA_OK;
@@ -1159,6 +1241,20 @@ int efa_ctx_set_option(efa_ctx* c, const char* key, long value) {
   } else {
     return fail(EFA_ERR_INVALID, "unknown option '%s'", key);
   }
+  return EFA_OK;
+}
+
+int efa_ctx_set_relaxation(efa_ctx* c, int kind, double alpha) {
+  EFA_TRY(use(c));
+  if (kind != EFA_RELAX_NONE && kind != EFA_RELAX_RTPP && kind != EFA_RELAX_RTPS)
+    return fail(EFA_ERR_INVALID, "relaxation kind %d: expected EFA_RELAX_NONE (0), EFA_RELAX_RTPP (1) or EFA_RELAX_RTPS (2)", kind);
+  if (kind != EFA_RELAX_NONE) {
+    if (!std::isfinite(alpha)) return fail(EFA_ERR_INVALID, "relaxation factor must be a finite number");
+    if (alpha < 0.0) return fail(EFA_ERR_INVALID, "relaxation factor %g must be >= 0", alpha);
+    if (kind == EFA_RELAX_RTPP && alpha > 1.0) return fail(EFA_ERR_INVALID, "RTPP factor %g must be <= 1", alpha);
+  }
+  c->relax_kind = kind;
+  c->relax_alpha = kind == EFA_RELAX_NONE ? 0.0 : alpha;
   return EFA_OK;
 }
 
@@ -1387,27 +1483,25 @@ int efa_state_cycle_dev(efa_ctx* c, long rows, int M, const double* X_dev, doubl
   EFA_TRY(prepare_grid(c, grid_lat, grid_lon, ncol, n_lead, rows));
   hipStream_t s = c->stream;
   if (c->timing) EFA_HIP(hipEventRecord(c->ev[2], s));
+  const bool relax = relax_on(c);
+  const double* prior = nullptr;
   if (c->P > 0 && c->n_active > 0 && want_transform(c, true)) {
-    efa::TransformArgs t{};
-    t.Xin = X_dev;
-    t.Xout = post_dev;
-    t.nrows = rows;
-    t.M = M;
-    t.T = c->Yw.as<double>() + (size_t)c->P * M;
-    t.w = c->ymw.as<double>() + c->P;
-    t.fused_members = 1;
-    EFA_HIP(efa::launch_transform(t, s));
-    c->state_launches = 1;
+    EFA_TRY(member_transform(c, rows, M, X_dev, post_dev, c->Yw.as<double>() + (size_t)c->P * M, c->ymw.as<double>() + c->P,
+                             &c->state_launches));
     c->path_taken = EFA_PATH_TRANSFORM;
   } else if (c->loc_mode == EFA_LOC_GC && c->gc_onepass && c->n_active > 0) {
     // localised: prior members -> posterior members in one read + one write of the state
+    if (relax) EFA_TRY(relax_prepare(c, rows, M, X_dev, post_dev, &prior, &c->state_launches));
     EFA_TRY(state_gc_onepass(c, rows, nullptr, X_dev, nullptr, post_dev, ncol, n_lead, 1));
+    if (relax) EFA_TRY(relax_apply(c, rows, M, post_dev, prior, &c->state_launches));
   } else {
+    if (relax) EFA_TRY(relax_prepare(c, rows, M, X_dev, post_dev, &prior, &c->state_launches));
     EFA_TRY(c->xm_ws.reserve((size_t)rows * sizeof(double)));
     double* xm = c->xm_ws.as<double>();
     EFA_HIP(efa::launch_form_perts(rows, M, X_dev, 1.0, xm, post_dev, s));
     EFA_TRY(state_sweeps(c, rows, xm, post_dev, xm, post_dev, ncol));
     EFA_HIP(efa::launch_posterior(rows, M, xm, post_dev, post_dev, s));
+    if (relax) EFA_TRY(relax_apply(c, rows, M, post_dev, prior, &c->state_launches));
   }
   EFA_TRY(finish_state_timing(c, s));
   return EFA_OK;
@@ -1457,6 +1551,7 @@ int efa_ensrf_cycle_dev(efa_ctx* c, long rows, int M, long P, const double* X_de
                            prior_mean, prior_var, post_mean, post_var, assimilated);
   const bool launched = c->spec.launched;
   const int pair = c->spec.pair;
+  const long spec_launches = c->spec.launches;
   c->spec = efa_ctx::Spec{};
   if (rc != EFA_OK) {
     c->grid_ready = false;
@@ -1464,8 +1559,8 @@ int efa_ensrf_cycle_dev(efa_ctx* c, long rows, int M, long P, const double* X_de
   }
   if (launched) {  // Phase B is in the stream already, behind the launch that turned out fine
     c->state_ms = 0.0;
-    c->state_launches = 1;
-    c->state_launches_sum += 1;
+    c->state_launches = spec_launches;
+    c->state_launches_sum += spec_launches;
     c->path_taken = EFA_PATH_TRANSFORM;
     if (c->timing) {
       (pair ? c->state_ms_pending2 : c->state_ms_pending) = true;

@@ -175,6 +175,15 @@ hipError_t launch_sweep(const SweepArgs& a, hipStream_t s);
 hipError_t launch_diag(const DiagArgs& a, hipStream_t s);
 hipError_t launch_transform(const TransformArgs& a, hipStream_t s);
 bool transform_supported(int M);
+// RTPS fused into the member-form transform (k_transform_rtps): M <= 136, one launch with [T | w] in LDS
+hipError_t launch_transform_rtps(const TransformArgs& a, double alpha, hipStream_t s);
+bool transform_rtps_supported(int M);
+// posterior relaxation (efa_relax.hip): Tout = (1-alpha) T + alpha I; per-row sum of squared deviations; in-place relaxation of
+// rows (rtpp 0: RTPS from ss, 1: RTPP against the prior rows)
+hipError_t launch_relax_fold(int M, double alpha, const double* T, double* Tout, hipStream_t s);
+hipError_t launch_row_spread(long rows, int M, const double* X, double* ss, hipStream_t s);
+hipError_t launch_relax_rows(long rows, int M, int rtpp, double alpha, double* X, const double* ss, const double* prior,
+                             hipStream_t s);
 
 hipError_t launch_form_perts(long rows, int M, const double* X, double scale, double* xm,
                              double* Xp, hipStream_t s);

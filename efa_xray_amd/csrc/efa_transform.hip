@@ -304,6 +304,233 @@ hipError_t transform_nu(const TransformArgs& a, hipStream_t s) {
 }
 
 
+// ---- RTPS fused into the member-form transform (M <= 136) -------------------------------------------------
+// k_transform's member form with the relaxation to prior spread (Whitaker & Hamill 2012) applied before the stores:
+//   post_ij <- mean_j(post_i) + (post_ij - mean_j(post_i)) ((1 - alpha) + alpha sigma_b / sigma_a)
+// Once the row mean is removed, a[] holds the prior perturbations of row n (lane (g, n): members {8u+2g, 8u+2g+1}), so
+// sum_m b^2 reduces over g exactly as rmean does.  The posterior member columns of rows 4v+g are acc[t][v] (w folded in)
+// plus, at M % 16 in 1..4, the narrow tile's accn: their row mean and sum of squared deviations reduce over the 16 lanes n
+// of a row group (the narrow tile's over its 4 columns first).  The scale is applied in registers: no extra HBM traffic.
+// Rows with sigma_a == 0 are stored as k_transform stores them.  A kernel of its own -- not a flag of k_transform -- so
+// the shipped transform's code stays as it is.
+template <int NU, bool HALF, bool AL>
+__global__ __launch_bounds__(kThreadsT) void k_transform_rtps(const TransformArgs p, const double alpha) {
+  using Sh = TShape<NU, true, HALF>;
+  constexpr int NT = Sh::NT;
+  constexpr bool NARROW = Sh::NARROW;
+  extern __shared__ __align__(16) double Bs[];  // as k_transform (member form: T + w 1^T)
+  const int M = p.M;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < (int)Sh::lds_doubles; i += kThreadsT) {
+    const int l = i & 63;
+    const int g = l >> 4, n = l & 15;
+    int s, j;
+    if (i < (int)Sh::wide_doubles) {
+      const int st = i >> 6;
+      s = st / Sh::NTA;
+      j = 16 * (st % Sh::NTA) + n;
+    } else {
+      s = (i - (int)Sh::wide_doubles) >> 6;
+      j = 16 * NT + (l & 3);
+    }
+    const int u = s >> 1, h = s & 1;
+    const int m = (HALF && u == NU - 1) ? (h == 0 ? 8 * u + g : M) : 8 * u + 2 * g + h;
+    double v = 0.0;
+    if (m < M && j < M) v = p.T[(size_t)m * M + j] + p.w[m];
+    Bs[i] = v;
+  }
+  __syncthreads();
+
+  const int lane = tid & 63;
+  const int g = lane >> 4, n = lane & 15;
+  const long ntiles = (p.nrows + 15) / 16;
+  const long wave = (long)blockIdx.x * (kThreadsT / 64) + (tid >> 6);
+  const long nwaves = (long)gridDim.x * (kThreadsT / 64);
+  const long last_row = p.nrows - 1;
+  const bool last_ok = (HALF ? (8 * (NU - 1) + g) : (8 * (NU - 1) + 2 * g)) < M;
+  const bool last_ok1 = !HALF && (8 * (NU - 1) + 2 * g + 1) < M;
+  const int nv = (lane >> 2) & 3;            // the narrow tile: this lane's row is 4 nv + g ...
+  const int nrow = 4 * nv + g;
+  const int ncol = 16 * NT + (lane & 3);     // ... and its column
+
+  double a[2 * NU], an[2 * NU];
+  long tile = wave;
+  if (tile < ntiles) {
+    const long r = tile * 16 + n;
+    load_tile<NU, HALF, AL>(p.Xin, r < last_row ? r : last_row, M, g, a);
+  }
+  if (kPrefetchT) {
+#pragma unroll
+    for (int c = 0; c < 2 * NU; ++c) asm volatile("" : "+v"(a[c]));
+  }
+
+  while (tile < ntiles) {
+    const long next = tile + nwaves;
+    const long r0 = tile * 16;
+    if (kPrefetchT) {
+      const long r = (next < ntiles ? next : tile) * 16 + n;
+      load_tile<NU, HALF, AL>(p.Xin, r < last_row ? r : last_row, M, g, an);
+    }
+    if (!last_ok) a[2 * NU - 2] = 0.0;
+    if (!last_ok1) a[2 * NU - 1] = 0.0;
+
+    double rmean, sb;  // prior mean of row n and sum of its squared perturbations
+    {
+      double s4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int c = 0; c < 2 * NU; ++c) s4[c & 3] += a[c];
+      double s = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+      s += __shfl_xor(s, 16, 64);
+      s += __shfl_xor(s, 32, 64);
+      rmean = s / (double)M;
+#pragma unroll
+      for (int c = 0; c < 2 * NU - 2; ++c) a[c] -= rmean;
+      a[2 * NU - 2] = last_ok ? a[2 * NU - 2] - rmean : 0.0;
+      a[2 * NU - 1] = last_ok1 ? a[2 * NU - 1] - rmean : 0.0;
+      double q4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int c = 0; c < 2 * NU; ++c) q4[c & 3] = fma(a[c], a[c], q4[c & 3]);
+      sb = (q4[0] + q4[1]) + (q4[2] + q4[3]);
+      sb += __shfl_xor(sb, 16, 64);
+      sb += __shfl_xor(sb, 32, 64);
+    }
+
+    v4f64 acc[Sh::NTA];
+    double accn = 0.0;
+#pragma unroll
+    for (int t = 0; t < Sh::NTA; ++t) acc[t] = (v4f64){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < (HALF ? 2 * NU - 1 : 2 * NU); ++s) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const double b = Bs[((size_t)s * NT + t) * 64 + lane];
+        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], b, acc[t], 0, 0, 0);
+      }
+      if (NARROW) accn = __builtin_amdgcn_mfma_f64_4x4x4f64(a[s], Bs[Sh::wide_doubles + (size_t)s * 64 + lane], accn, 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (kPrefetchT) {
+#pragma unroll
+      for (int c = 0; c < 2 * NU; ++c) a[c] = an[c];
+#pragma unroll
+      for (int c = 0; c < 2 * NU; ++c) asm volatile("" : "+v"(a[c]));
+    }
+
+    // posterior row mean (of the product part) and sum of squared deviations of rows 4v+g
+    const bool nok = NARROW && ncol < M;
+    double nsum = nok ? accn : 0.0;
+    if (NARROW) {
+      nsum += __shfl_xor(nsum, 1, 64);
+      nsum += __shfl_xor(nsum, 2, 64);
+    }
+    double mv[4], base[4], sc[4];  // a row with sigma_a == 0 gets mv 0, sc 1: (base + 0) + 1 (acc - 0) == base + acc exactly
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      double rs = 0.0;
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+        if (16 * t + n < M) rs += acc[t][v];
+      rs += __shfl_xor(rs, 1, 64);
+      rs += __shfl_xor(rs, 2, 64);
+      rs += __shfl_xor(rs, 4, 64);
+      rs += __shfl_xor(rs, 8, 64);
+      if (NARROW) rs += __shfl(nsum, (lane & 48) | (4 * v), 64);
+      mv[v] = rs / (double)M;
+    }
+    double ndev = 0.0;
+    if (NARROW) {
+      const double mn = nv == 0 ? mv[0] : nv == 1 ? mv[1] : nv == 2 ? mv[2] : mv[3];
+      const double d = nok ? accn - mn : 0.0;
+      ndev = d * d;
+      ndev += __shfl_xor(ndev, 1, 64);
+      ndev += __shfl_xor(ndev, 2, 64);
+    }
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      double q = 0.0;
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const double d = (16 * t + n < M) ? acc[t][v] - mv[v] : 0.0;
+        q = fma(d, d, q);
+      }
+      q += __shfl_xor(q, 1, 64);
+      q += __shfl_xor(q, 2, 64);
+      q += __shfl_xor(q, 4, 64);
+      q += __shfl_xor(q, 8, 64);
+      if (NARROW) q += __shfl(ndev, (lane & 48) | (4 * v), 64);
+      const double sbv = __shfl(sb, 4 * v + g, 64);
+      const bool keep = !(q > 0.0);
+      sc[v] = keep ? 1.0 : (1.0 - alpha) + alpha * sqrt(sbv / q);
+      if (keep) mv[v] = 0.0;
+      base[v] = __shfl(rmean, 4 * v + g, 64) + mv[v];
+    }
+    double nval = 0.0;
+    if (NARROW) {
+      const double nb = nv == 0 ? base[0] : nv == 1 ? base[1] : nv == 2 ? base[2] : base[3];
+      const double mn = nv == 0 ? mv[0] : nv == 1 ? mv[1] : nv == 2 ? mv[2] : mv[3];
+      const double sn = nv == 0 ? sc[0] : nv == 1 ? sc[1] : nv == 2 ? sc[2] : sc[3];
+      nval = nb + sn * (accn - mn);
+    }
+    if (r0 + 16 <= p.nrows) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int col = 16 * t + n;
+        if (col < M) {
+#pragma unroll
+          for (int v = 0; v < 4; ++v)
+            p.Xout[(size_t)(r0 + 4 * v + g) * M + col] = base[v] + sc[v] * (acc[t][v] - mv[v]);
+        }
+      }
+      if (nok) p.Xout[(size_t)(r0 + nrow) * M + ncol] = nval;
+    } else {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int col = 16 * t + n;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const long row = r0 + 4 * v + g;
+          if (col < M && row < p.nrows)
+            p.Xout[(size_t)row * M + col] = base[v] + sc[v] * (acc[t][v] - mv[v]);
+        }
+      }
+      if (nok && r0 + nrow < p.nrows) p.Xout[(size_t)(r0 + nrow) * M + ncol] = nval;
+    }
+
+    if (!kPrefetchT && next < ntiles) {
+      const long r = next * 16 + n;
+      load_tile<NU, HALF, AL>(p.Xin, r < last_row ? r : last_row, M, g, a);
+    }
+    tile = next;
+  }
+}
+
+template <int NU, bool HALF, bool AL>
+hipError_t transform_rtps_launch(const TransformArgs& a, double alpha, hipStream_t s) {
+  using Sh = TShape<NU, true, HALF>;
+  const size_t lds = (Sh::lds_doubles ? Sh::lds_doubles : 64) * sizeof(double);
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_transform_rtps<NU, HALF, AL>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  const long ntiles = (a.nrows + 15) / 16;
+  const int per_cu = (lds <= 80 * 1024) ? 2 : 1;
+  long grid = (ntiles + EFA_T_WAVES - 1) / EFA_T_WAVES;
+  if (grid > 256L * per_cu) grid = 256L * per_cu;
+  if (grid < 1) grid = 1;
+  hipLaunchKernelGGL((k_transform_rtps<NU, HALF, AL>), dim3((unsigned)grid), dim3(kThreadsT), lds, s, a, alpha);
+  return hipGetLastError();
+}
+
+template <int NU>
+hipError_t transform_rtps_nu(const TransformArgs& a, double alpha, hipStream_t s) {
+  const int rem = a.M % 8;
+  const bool half = rem != 0 && rem <= 4;
+  const bool al = (a.M % 2 == 0) && (reinterpret_cast<uintptr_t>(a.Xin) & 15u) == 0;
+  if (al) return half ? transform_rtps_launch<NU, true, true>(a, alpha, s) : transform_rtps_launch<NU, false, true>(a, alpha, s);
+  return half ? transform_rtps_launch<NU, true, false>(a, alpha, s) : transform_rtps_launch<NU, false, false>(a, alpha, s);
+}
+
 // ---- ensembles of 137 .. 256 members ----------------------------------------------------------------------
 // The LDS image of [T | w] no longer fits one CU (M^2 x 8 B > 160 KB), so the product is cut into column groups of
 // kWideTiles 16-wide tiles: blockIdx.y takes one group, stages only that part of the image and re-reads the
@@ -441,6 +668,35 @@ hipError_t transform_wide_nu(const TransformArgs& a, hipStream_t s) {
 
 // one launch with the whole [T | w] image in LDS up to M = 136; column groups above (k_transform_wide) up to 256
 bool transform_supported(int M) { return M >= 2 && M <= 256; }
+
+bool transform_rtps_supported(int M) { return M >= 2 && M <= 136; }
+
+// member form only (Xin prior members, Xout posterior members)
+hipError_t launch_transform_rtps(const TransformArgs& a, double alpha, hipStream_t s) {
+  if (!transform_rtps_supported(a.M) || !a.fused_members) return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(a.Xin) & 7u) != 0) return hipErrorInvalidValue;
+  if (a.nrows <= 0) return hipSuccess;
+  switch ((a.M + 7) / 8) {
+    case 1: return transform_rtps_nu<1>(a, alpha, s);
+    case 2: return transform_rtps_nu<2>(a, alpha, s);
+    case 3: return transform_rtps_nu<3>(a, alpha, s);
+    case 4: return transform_rtps_nu<4>(a, alpha, s);
+    case 5: return transform_rtps_nu<5>(a, alpha, s);
+    case 6: return transform_rtps_nu<6>(a, alpha, s);
+    case 7: return transform_rtps_nu<7>(a, alpha, s);
+    case 8: return transform_rtps_nu<8>(a, alpha, s);
+    case 9: return transform_rtps_nu<9>(a, alpha, s);
+    case 10: return transform_rtps_nu<10>(a, alpha, s);
+    case 11: return transform_rtps_nu<11>(a, alpha, s);
+    case 12: return transform_rtps_nu<12>(a, alpha, s);
+    case 13: return transform_rtps_nu<13>(a, alpha, s);
+    case 14: return transform_rtps_nu<14>(a, alpha, s);
+    case 15: return transform_rtps_nu<15>(a, alpha, s);
+    case 16: return transform_rtps_nu<16>(a, alpha, s);
+    case 17: return transform_rtps_nu<17>(a, alpha, s);
+    default: return hipErrorInvalidValue;
+  }
+}
 
 hipError_t launch_transform(const TransformArgs& a, hipStream_t s) {
   if (!transform_supported(a.M)) return hipErrorInvalidValue;

@@ -31,6 +31,7 @@ logic on CPU ranks with gloo by passing their own engine.)
 import numpy as np
 
 from efa_xray_amd import _lib
+from efa_xray_amd.assimilation.ensrf import relaxation_setting
 
 
 def column_bounds(ncol, world_size):
@@ -139,6 +140,10 @@ class HipEngine(object):
         self.ctx.form_perts(rows, M, X.data_ptr(), xm.data_ptr(), X.data_ptr(), scale=factor)
         self.ctx.posterior(rows, M, xm.data_ptr(), X.data_ptr(), X.data_ptr())
 
+    def set_relaxation(self, kind, alpha):
+        """Posterior relaxation (RTPP / RTPS) of the state phases that follow on this engine's context."""
+        self.ctx.set_relaxation(kind, alpha)
+
     def obs_phase(self, M, P, ym, Yp, ob):
         return self.ctx.obs_phase(M, P, ym.data_ptr(), Yp.data_ptr(), ob["value"], ob["error"], ob["assim"],
                                   _lib.LOC_GC if ob.get("loc") == "GC" else _lib.LOC_NONE,
@@ -223,10 +228,16 @@ class ShardedEnSRF(object):
         eng.forward_stencil(self.rows_local, M, X_local, lidx, lwts, HX)
         return HX
 
-    def assimilate(self, X_local, post_local, HX, ob, grid_lat=None, grid_lon=None):
+    def assimilate(self, X_local, post_local, HX, ob, grid_lat=None, grid_lon=None, rtps=None, rtpp=None):
         """Stage 2, after HX has been summed over the shards: obs-space priors, Phase A
-        (replicated: identical on every rank) and the sweep of this shard's rows."""
+        (replicated: identical on every rank) and the sweep of this shard's rows.  `rtps` / `rtpp`:
+        posterior relaxation of the shard's rows as in `EnSRF` (row-local: no communication)."""
         eng, M = self.engine, self.M
+        relax = relaxation_setting(rtps, rtpp)
+        if hasattr(eng, "set_relaxation"):
+            eng.set_relaxation(*relax)                                     # every call: "none" included
+        elif relax[0] != _lib.RELAX_NONE:
+            raise ValueError("this engine does not support posterior relaxation")
         P = int(HX.shape[0])
         ym = eng.empty((max(P, 1),))
         eng.form_perts(P, M, HX, ym, HX)                                   # assimilation.py:46-48
@@ -240,7 +251,8 @@ class ShardedEnSRF(object):
         eng.state_cycle(self.rows_local, M, X_local, post_local, glat, glon, self.n_lead)
         return diag
 
-    def update(self, X_local, post_local, sten_idx, sten_wts, ob, grid_lat=None, grid_lon=None, inflation=None):
+    def update(self, X_local, post_local, sten_idx, sten_wts, ob, grid_lat=None, grid_lon=None, inflation=None,
+               rtps=None, rtpp=None):
         HX = self.partial_estimates(X_local, sten_idx, sten_wts, inflation)
         self.all_reduce_sum(HX)                                            # the one exchange step
-        return self.assimilate(X_local, post_local, HX, ob, grid_lat, grid_lon)
+        return self.assimilate(X_local, post_local, HX, ob, grid_lat, grid_lon, rtps=rtps, rtpp=rtpp)

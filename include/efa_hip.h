@@ -92,6 +92,30 @@ int efa_ctx_set_stream(efa_ctx *ctx, void *hip_stream);
  *          ((column, ob) pairs with a non-zero taper in the last one-pass sweep) */
 int efa_ctx_set_option(efa_ctx *ctx, const char *key, long value);
 int efa_ctx_get_option(efa_ctx *ctx, const char *key, long *value);
+
+/* ---- posterior inflation by relaxation (Whitaker & Hamill 2012) ----------
+ * Context state like "path": every later state phase that writes the caller's
+ * state rows (efa_state_phase_dev, efa_state_cycle_dev, efa_ensrf_cycle_dev,
+ * efa_ensrf_update_dev, efa_ensrf_update) relaxes each row i of M members,
+ * with prior perturbations b_i and posterior perturbations a_i (deviations
+ * from the row's member mean):
+ *   EFA_RELAX_RTPP: xa_i <- mean(xa_i) + (1-alpha) a_i + alpha b_i, 0 <= alpha <= 1
+ *   EFA_RELAX_RTPS: xa_i <- mean(xa_i) + a_i ((1-alpha) + alpha sigma_b/sigma_a),
+ *                   alpha >= 0; a row with sigma_a == 0 is left as it is.
+ * The prior is the ensemble the call is given.  The obs block and the
+ * per-ob diagnostics are not relaxed; alpha == 0, EFA_RELAX_NONE and a cycle
+ * with no assimilated ob leave the results bit for bit as without it.
+ * Cost: on the unlocalised transform path RTPP is folded into T and RTPS
+ * (up to 136 members, member form) is fused into the transform; every other
+ * path adds a row-spread pass over the prior and a relaxation pass over the
+ * posterior.  RTPP on those paths with the posterior written over the prior
+ * keeps a copy of the prior in a context workspace: rows*M*8 bytes more
+ * device memory.  Bad kind, NaN or infinite alpha, alpha < 0 or (RTPP)
+ * alpha > 1 return EFA_ERR_INVALID. */
+#define EFA_RELAX_NONE 0
+#define EFA_RELAX_RTPP 1
+#define EFA_RELAX_RTPS 2
+int efa_ctx_set_relaxation(efa_ctx *ctx, int kind, double alpha);
 int efa_ctx_synchronize(efa_ctx *ctx);
 
 /* ---- device memory for callers without their own allocator -------------*/
