@@ -93,6 +93,26 @@ def localize_obs(all_lat, all_lon, ob_lat, ob_lon, halfwidth):
     return gaspari_cohn(d, halfwidth)
 
 
+def localize_obs_vec(all_lat, all_lon, ob_lat, ob_lon, halfwidth):
+    """`localize_obs` with the P `haversine` calls done as one array
+    expression: the same operations in the same order as `haversine`
+    (radians of the lon DIFFERENCE, observation.py:141), with `loc2` an
+    array.  Not bit-identical to the loop -- vectorised sin/cos may differ
+    from the scalar ones in the last bit (a few 1e-16 km) -- so it is
+    opt-in (`obs_taper="vector"`); it turns the oracle's O(P^2) Python
+    loop into O(P) array work for thousands of obs.
+    """
+    all_lat = np.asarray(all_lat, dtype=np.float64)
+    all_lon = np.asarray(all_lon, dtype=np.float64)
+    p1 = np.radians(ob_lat)
+    p2 = np.radians(all_lat)
+    dp = p2 - p1
+    dl = np.radians(all_lon - ob_lon)
+    a = np.sin(dp / 2) ** 2 + np.cos(p1) * np.cos(p2) * np.sin(dl / 2) ** 2
+    c = 2 * np.arctan2(np.sqrt(a), np.sqrt(1 - a))
+    return gaspari_cohn(EARTH_RADIUS_KM * c, halfwidth)
+
+
 # ---------------------------------------------------------------------------
 # formation of the augmented mean / perturbation arrays
 # ---------------------------------------------------------------------------
@@ -145,7 +165,7 @@ def inflate_constant(X, factor):
 def ensrf_update(xbm, Xbp, nstate, ob_value, ob_error, ob_assim,
                  loc=None, ob_lat=None, ob_lon=None, ob_halfwidth=None,
                  grid_lat=None, grid_lon=None, state_shape=None,
-                 faithful_cost=False):
+                 faithful_cost=False, obs_taper="loop", step_hook=None):
     """Serial EnSRF loop on the augmented state.
 
     Follows efa_xray/assimilation/ensrf.py:50-149 statement for statement.
@@ -161,6 +181,12 @@ def ensrf_update(xbm, Xbp, nstate, ob_value, ob_error, ob_assim,
         row picks (ensrf.py:61-64,144-145) instead of a direct row read --
         same bits, but the reference's memory traffic; used when this loop is
         timed as the CPU baseline.
+    obs_taper: "loop" (default: the reference's one `haversine` call per ob
+        pair, bit-identical) or "vector" (`localize_obs_vec`: the same
+        arithmetic as one array expression, for large P).
+    step_hook: optional callable(k, xam, Xap), called before ob k is
+        processed with the current augmented arrays (read only; test
+        instrumentation, e.g. variances at Phase-A block starts).
 
     Returns xam (A,), Xap (A, M) and a dict of the per-ob diagnostics the
     reference writes onto each Observation (ensrf.py:66,70,75,146-149):
@@ -173,6 +199,7 @@ def ensrf_update(xbm, Xbp, nstate, ob_value, ob_error, ob_assim,
     P = len(ob_value)
     assert A == nstate + P
     use_loc = loc not in (None, False)
+    loc_obs = {"loop": localize_obs, "vector": localize_obs_vec}[obs_taper]
     if use_loc:
         grid_lat = np.asarray(grid_lat, dtype=np.float64)
         grid_lon = np.asarray(grid_lon, dtype=np.float64)
@@ -185,6 +212,8 @@ def ensrf_update(xbm, Xbp, nstate, ob_value, ob_error, ob_assim,
     assimilated = np.zeros(P, dtype=bool)
 
     for k in range(P):
+        if step_hook is not None:
+            step_hook(k, xam, Xap)
         xb = xam
         Xb = Xap
         row = nstate + k
@@ -211,7 +240,7 @@ def ensrf_update(xbm, Xbp, nstate, ob_value, ob_error, ob_assim,
                 sl = (sl[None, None, :, :] * dum_localize).flatten()
             else:
                 sl = (sl[None, None, None, :] * dum_localize).flatten()
-            ol = localize_obs(ob_lat, ob_lon, ob_lat[k], ob_lon[k], ob_halfwidth[k])
+            ol = loc_obs(ob_lat, ob_lon, ob_lat[k], ob_lon[k], ob_halfwidth[k])
             kcov = np.multiply(np.hstack((sl, ol)), kcov)
         kmat = np.divide(kcov, kdenom)
         xam = xb + np.multiply(kmat, innov)

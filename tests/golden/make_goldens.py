@@ -4,7 +4,8 @@
 Runs ONLY in the build container (needs /root/reference); nothing here is
 imported by tests, the product or the bench.  Usage:
 
-    python3 -B tests/golden/make_goldens.py            # writes G1..G8 + KAT
+    python3 -B tests/golden/make_goldens.py            # writes G1..G12 + KAT
+    python3 -B tests/golden/make_goldens.py --only G12 # writes G12 alone
 
 What executes verbatim from the reference:
   efa_xray/assimilation/ensrf.py:33-151        EnSRF.update
@@ -35,6 +36,8 @@ estimate IS the weight vector.  The 2-D branch's "< 1 km" exact-match case
 raises IndexError in the reference (ensemble.py:194-196 writes a 2-D index
 into a 1-D array) and is therefore kept out of G9; the 1-D branch's
 spaceweights are (1, 4), so the same statement works there and G10 holds one.
+
+G12 (`main_g12`) is EnSRF.update() with GC as in G1..G8, 2 500 obs deep (see its docstring).
 
 A fixture is data only: inputs and the reference's outputs.
 """
@@ -174,7 +177,10 @@ def pack_stencils(stencils):
 
 
 def make_case(name, shape, lat, lon, rng, P, loc, radii=None, errors=1.0, assim=None,
-              stencil="pick", pick=None, keep=("xbm", "Xbp", "xam", "Xap"), sigma=3.0):
+              stencil="pick", pick=None, keep=("xbm", "Xbp", "xam", "Xap"), sigma=3.0, relocate=None,
+              drop=(), compress=False):
+    """relocate(ob_lat, ob_lon): edits the (jittered) ob locations in place before the run.
+    drop: outputs left out of the file (e.g. HX, which the loader re-derives).  compress: np.savez_compressed."""
     nvar, nt, ny, nx, M = shape
     N = nvar * nt * ny * nx
     mu = rng.standard_normal((nvar, nt, ny, nx, 1))
@@ -204,6 +210,8 @@ def make_case(name, shape, lat, lon, rng, P, loc, radii=None, errors=1.0, assim=
     # jitter so obs are off-grid
     ob_lat = ob_lat + 0.3 * rng.standard_normal(P)
     ob_lon = ob_lon + 0.3 * rng.standard_normal(P)
+    if relocate is not None:
+        relocate(ob_lat, ob_lon)
     errors = np.broadcast_to(np.asarray(errors, dtype=np.float64), (P,)).copy()
     vect = arr.reshape(N, M)
     truth = np.array([(s[1][:, None] * vect[s[0]]).sum(axis=0).mean() for s in stencils])
@@ -225,8 +233,10 @@ def make_case(name, shape, lat, lon, rng, P, loc, radii=None, errors=1.0, assim=
     )
     for k in keep:
         fix[k] = out[k]
+    for k in drop:
+        del fix[k]
     path = os.path.join(OUT, name + ".npz")
-    np.savez(path, **fix)
+    (np.savez_compressed if compress else np.savez)(path, **fix)
     print("%-4s N=%d M=%d P=%d loc=%r assimilated=%d -> %s (%.1f KB)" % (
         name, N, M, P, loc, int(out["assimilated"].sum()), os.path.basename(path),
         os.path.getsize(path) / 1024))
@@ -446,7 +456,48 @@ def main_f1():
         shape, P, int(fix["assimilated"].sum()), os.path.basename(path), os.path.getsize(path) / 1024))
 
 
+def main_g12():
+    """G12: Gaspari-Cohn a few thousand obs deep -- 2 500 obs x 100 members, ~40 hand-overs of a 64-ob Phase-A
+    block.  The file must stay small, so the state is a small 2 x 8 x 10 grid (N = 160 rows) and the obs pick its
+    rows WITH replacement: every row is observed ~16 times, by obs a few tens of km apart (taper ~1), some of them
+    within one 64-ob block.  Radii 300..1500 km on a ~600..900 km grid, so many ob pairs interact and many have zero
+    taper; a few co-located obs (three observing the same row at the same place as the ob before, one pair across a
+    block boundary), one ob whose taper is zero everywhere but at itself (as in G5), ~5 % not assimilated.  The
+    rows are independent draws, so an ob's variance falls within a block only through earlier obs of its own row,
+    by far less than the Phase-A leaders' cancellation guard needs (the tests check that margin).
+    Kept: xam, post and the diagnostics, not Xap (the obs rows alone would be 2 MB); HX is left out too (= X's
+    picked rows, LinOb.estimate's rows[0].copy()) and rebuilt by the loader."""
+    rng = np.random.default_rng(31)
+    shape = (2, 1, 8, 10, 100)
+    nvar, nt, ny, nx, M = shape
+    N, P = nvar * nt * ny * nx, 2500
+    lat, lon = np.meshgrid(np.linspace(20, 60, ny), np.linspace(200, 290, nx), indexing="ij")
+    pick = np.random.default_rng(32).choice(N, P, replace=True)
+    dup = [(63, 64), (200, 201), (1500, 1501)]         # (ob, later ob observing the same row at the same place)
+    for a, b in dup:
+        pick[b] = pick[a]
+    radii = np.random.default_rng(33).uniform(300, 1500, P)
+    radii[777] = 1e-3                                   # zero taper everywhere but at its own location
+    assim = np.random.default_rng(34).random(P) > 0.05
+    assim[[63, 64, 200, 201, 1500, 1501, 777]] = True
+    errors = np.random.default_rng(35).uniform(0.5, 2.0, P)
+
+    def relocate(ob_lat, ob_lon):
+        for a, b in dup + [(10, 11), (300, 900), (2400, 2499)]:     # co-located (the last three: different rows)
+            ob_lat[b] = ob_lat[a]
+            ob_lon[b] = ob_lon[a]
+
+    make_case("G12", shape, lat, lon, rng, P, "GC", radii=radii, errors=errors, assim=assim, pick=pick,
+              keep=("xam",), relocate=relocate, drop=("HX",), compress=True)
+
+
 if __name__ == "__main__":
+    if "--only" in sys.argv:
+        only = sys.argv[sys.argv.index("--only") + 1]
+        {"G12": main_g12}[only]()
+        sys.exit(0)
     if "--f1-only" not in sys.argv:
         main()
     main_f1()
+    if "--f1-only" not in sys.argv:
+        main_g12()

@@ -12,7 +12,9 @@ tests/test_distributed_gloo.py and the logical-shard tests in tests/test_gpu_sha
 An oracle run at these sizes would take hours, so each test
 combines (i) the oracle on the obs block alone (Phase A is independent of the
 state rows: DESIGN.md F1), (ii) the oracle on a slice of state rows carried with
-the full obs block, and (iii) size-independent properties.
+the full obs block, and (iii) size-independent properties.  With localisation
+the oracle uses its vector obs-obs taper (`obs_taper="vector"`), so it follows
+all P obs.
 Tolerance: float64 1e-10 relative (BASELINE.json north_star); fp32 contraction
 |C - ref| <= 1e-4 |ref| + 2e-6 sum|a||b| against a float64 evaluation.
 """
@@ -99,7 +101,13 @@ def test_3d_atmosphere_gaspari_cohn_full_size(cfg, M, P):
       - configs[2]: the one-pass active-list sweep against the per-batch taper-table sweep on sampled column slabs;
       - rows whose taper is zero for every assimilated ob come back as the prior;
       - the last ob's row reproduces its post_mean / post_var;
+      - ALL P obs against the oracle (vector obs-obs taper), carrying a slab of 48 columns x 8 of the 148 variable x level
+        slabs -- state rows are independent of one another, so a few slabs cost the oracle little beside the obs block --:
+        all four diagnostics of every ob and the slab's posterior of the same full run; the oracle runs on a host thread
+        while the GPU works;
       - a 300-ob prefix against the oracle on a slab of columns (all 148 variable x level slabs of them)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from _phase_a_guard import GuardProbe, expected_kind
     ctx = _ctx()
     ny, nx, lat2, lon2 = _cfg2_grid()
     ncol, n_lead = ny * nx, 148
@@ -118,6 +126,24 @@ def test_3d_atmosphere_gaspari_cohn_full_size(cfg, M, P):
     err = np.ones(P)
     asm = np.ones(P, dtype=bool)
     ob_lat, ob_lon, hw = glat[ocol], glon[ocol], np.full(P, 1000.0)
+    # the full-length slab: the 48 columns around the column that the most footprints (of all P obs) cover, of 200
+    # candidate ob columns; the first, the last and six more of the variable x level slabs
+    cand = ocol[::P // 200]
+    cover = [int((orc.localize_obs_vec(ob_lat, ob_lon, glat[cc], glon[cc], hw) > 0).sum()) for cc in cand]
+    cf = int(cand[int(np.argmax(cover))])
+    cf = min(max(cf - 24, 0), ncol - 48)
+    leads_f = [0, 21, 42, 63, 84, 105, 126, n_lead - 1]
+    Xf = np.concatenate([X.download_rows(l * ncol + cf, l * ncol + cf + 48) for l in leads_f])
+
+    def full_oracle():
+        probe = GuardProbe(len(Xf), asm)
+        post_f, _, _, rdf = orc.ensrf_cycle(Xf, hx, val, err, asm, loc="GC", ob_lat=ob_lat, ob_lon=ob_lon, ob_halfwidth=hw,
+                                            grid_lat=glat[cf:cf + 48].reshape(1, 48), grid_lon=glon[cf:cf + 48].reshape(1, 48),
+                                            state_shape=(len(leads_f), 1, 1, 48), obs_taper="vector", step_hook=probe)
+        return post_f, rdf, probe.min_ratio()
+
+    pool = ThreadPoolExecutor(1)
+    fut = pool.submit(full_oracle)
 
     def run(n_obs, onepass, post):
         ctx.set_option("gc_onepass", onepass)
@@ -158,6 +184,7 @@ def test_3d_atmosphere_gaspari_cohn_full_size(cfg, M, P):
         for c0 in (0, 3 * nx, ncol - 5 * nx):
             pr, po = slab(X, c0, c0 + 64), slab(post, c0, c0 + 64)
             assert np.abs(po - pr).max() <= 4e-15 * np.abs(pr).max(), "zero-taper rows changed (cols %d..)" % c0
+        got_f = {"one-pass": np.concatenate([post.download_rows(l * ncol + cf, l * ncol + cf + 48) for l in leads_f])}
         # sampled slabs, kept for the comparison with the per-batch taper-table path
         samples = [int(c) for c in rng.choice(ncol - 48, 5, replace=False)] + [int(ocol[-1]) - int(ocol[-1]) % 16]
         onepass = [slab(post, c0, c0 + 48) for c0 in samples]
@@ -171,6 +198,7 @@ def test_3d_atmosphere_gaspari_cohn_full_size(cfg, M, P):
             for s, c0 in zip(onepass, samples):
                 t = slab(post, c0, c0 + 48)
                 assert np.abs(t - s).max() <= 1e-10 * np.abs(s).max(), "one-pass vs table path, cols %d.." % c0
+            got_f["table"] = np.concatenate([post.download_rows(l * ncol + cf, l * ncol + cf + 48) for l in leads_f])
         # ---- 300-ob prefix vs the oracle on a slab of 48 columns x 148 slabs --------------------
         n_p = 300
         dp = run(n_p, 1, post)
@@ -185,10 +213,23 @@ def test_3d_atmosphere_gaspari_cohn_full_size(cfg, M, P):
         assert float(np.abs(ref_post - Xs).max()) > 1e-3, "the oracle slab saw no update: test is vacuous"
         for key in ("prior_mean", "prior_var", "post_mean", "post_var"):
             assert_parity(dp[key], rd[key], cfg + " prefix " + key)
+        # ---- all P obs vs the oracle: every ob's diagnostics and the slab's posterior -------------------------
+        post_f, rdf, ratio = fut.result()
+        print("%s: oracle over all %d obs, slab columns %d..%d, guard min ratio %.3e" % (cfg, P, cf, cf + 47, ratio))
+        assert expected_kind(ratio, M) == 4
+        for key in ("prior_mean", "prior_var", "post_mean", "post_var"):
+            rel = assert_parity(d[key], rdf[key], "%s Phase A %s, all %d obs" % (cfg, key, P))
+            print("%s all %d obs vs oracle, %s: max rel err %.3e" % (cfg, P, key, rel))
+        assert np.array_equal(d["assimilated"], rdf["assimilated"])
+        for how, got in got_f.items():
+            rel = assert_parity(got, post_f, "%s all %d obs, %s sweep: slab vs oracle" % (cfg, P, how))
+            print("%s all %d obs vs oracle, slab posterior (%s sweep): max rel err %.3e" % (cfg, P, how, rel))
+        assert float(np.abs(post_f - Xf).max()) > 1e-3, "the full-length oracle slab saw no update: test is vacuous"
     finally:
         ctx.set_option("gc_onepass", 1)
         post.free()
         X.free()
+        pool.shutdown(wait=True)
 
 
 def test_config4_dense_contraction_1e6_x_128_x_4096_fp32_full_size():
