@@ -7,6 +7,7 @@
 
 #include <dlfcn.h>
 
+#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -141,7 +142,7 @@ struct efa_ctx {
   DevBuf traj, tw_mat, status, dbg;  // pipeline: trajectory records, GC obs-obs taper, status words, stamps
   const double* ye_ptr = nullptr;  // where Phase B reads the recorded ye rows
   long ye_stride = 0;
-  int phase_a_kind = 0;          // 1 pipeline, 2 per-batch kernels
+  int phase_a_kind = 0;          // 1 vector-chain pipeline, 2 per-batch kernels, 3 Gram leader, 4 band leader
   DevBuf ob_pack, out_pack;  // the per-ob inputs / diagnostics below are carved out of these two allocations
   PinBuf pin_in, pin_out;    // their pinned host images: one H2D and one D2H per call
   PinBuf pin_fs;             // pinned image of the forward-operator stencil
@@ -263,6 +264,14 @@ int finish_state_timing(efa_ctx* c, hipStream_t s) {
   return EFA_OK;
 }
 
+// start of a state-phase call, once its arguments are checked: the previous interval is read, the counters cleared
+void reset_state_phase(efa_ctx* c) {
+  harvest_state_ms(c);
+  c->state_ms = 0.0;
+  c->state_launches = 0;
+  c->path_taken = EFA_PATH_SWEEP;
+}
+
 int use(efa_ctx* c) {
   if (!c) return fail(EFA_ERR_INVALID, "null context");
   EFA_HIP(hipSetDevice(c->device));
@@ -330,66 +339,90 @@ int relax_apply(efa_ctx* c, long rows, int M, double* Xout, const double* prior,
   ++*nl;
   return EFA_OK;
 }
-// The member-form state transform, prior members X -> posterior members post through [T | w], with the relaxation: RTPP folded
-// into T (Xb' ((1-alpha) T + alpha I)), RTPS fused into the transform up to 136 members, the standalone passes above that.
-int member_transform(efa_ctx* c, long rows, int M, const double* X, double* post, const double* T, const double* w, long* nl) {
+// core(), the state phase's pass(es) from prior rows Xin to posterior rows Xout, between the standalone relaxation passes
+template <class Core>
+int with_relaxation(efa_ctx* c, long rows, int M, const double* Xin, double* Xout, long* nl, Core&& core) {
+  const bool relax = relax_on(c);
+  const double* prior = nullptr;
+  if (relax) EFA_TRY(relax_prepare(c, rows, M, Xin, Xout, &prior, nl));
+  EFA_TRY(core());
+  if (relax) EFA_TRY(relax_apply(c, rows, M, Xout, prior, nl));
+  return EFA_OK;
+}
+// The state transform through [T | w] (member or perturbation form, t.fused_members) with the relaxation: RTPP folded into T
+// (Xb' ((1-alpha) T + alpha I); xam as without it), RTPS fused into the member-form transform up to 136 members, the standalone
+// passes otherwise.  *nl = the launches it took.
+int transform_with_relaxation(efa_ctx* c, TransformArgs t, long* nl) {
   hipStream_t s = c->stream;
-  TransformArgs t{};
-  t.Xin = X;
-  t.Xout = post;
-  t.nrows = rows;
-  t.M = M;
-  t.T = T;
-  t.w = w;
-  t.fused_members = 1;
+  const bool relax = relax_on(c);
   *nl = 1;
-  if (!relax_on(c)) {
-    EFA_HIP(launch_transform(t, s));
-    return EFA_OK;
-  }
-  if (c->relax_kind == EFA_RELAX_RTPP) {
-    EFA_TRY(c->relax_T.reserve((size_t)M * M * sizeof(double)));
-    EFA_HIP(launch_relax_fold(M, c->relax_alpha, T, c->relax_T.as<double>(), s));
+  if (relax && c->relax_kind == EFA_RELAX_RTPP) {
+    EFA_TRY(c->relax_T.reserve((size_t)t.M * t.M * sizeof(double)));
+    EFA_HIP(launch_relax_fold(t.M, c->relax_alpha, t.T, c->relax_T.as<double>(), s));
     t.T = c->relax_T.as<double>();
-    EFA_HIP(launch_transform(t, s));
     *nl = 2;
-    return EFA_OK;
-  }
-  if (transform_rtps_supported(M)) {
+  } else if (relax && t.fused_members && transform_rtps_supported(t.M)) {
     EFA_HIP(launch_transform_rtps(t, c->relax_alpha, s));
     return EFA_OK;
+  } else if (relax) {
+    return with_relaxation(c, t.nrows, t.M, t.Xin, t.Xout, nl, [&]() -> int {
+      EFA_HIP(launch_transform(t, s));
+      return EFA_OK;
+    });
   }
-  const double* prior = nullptr;
-  EFA_TRY(relax_prepare(c, rows, M, X, post, &prior, nl));
   EFA_HIP(launch_transform(t, s));
-  EFA_TRY(relax_apply(c, rows, M, post, prior, nl));
   return EFA_OK;
+}
+// [T | w] as Phase A left them: the carried identity rows behind the P obs rows of the working block
+TransformArgs carried_transform(const efa_ctx* c, const double* Xin, const double* xin, double* Xout, double* xout, long rows,
+                                int fused_members) {
+  return TransformArgs{Xin, xin, Xout, xout, rows, c->M, c->Yw.as<double>() + (size_t)c->P * c->M, c->ymw.as<double>() + c->P,
+                       fused_members};
 }
 
 // ---- Phase A ---------------------------------------------------------------
-int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const double* ob_value,
-              const double* ob_error, const uint8_t* ob_assim, int loc_mode, const double* ob_lat,
-              const double* ob_lon, const double* ob_hw, double* prior_mean, double* prior_var,
-              double* post_mean, double* post_var, uint8_t* assimilated) {
-  EFA_TRY(check_common(M, P));
-  if (loc_mode != EFA_LOC_NONE && loc_mode != EFA_LOC_GC) return fail(EFA_ERR_INVALID, "loc_mode %d", loc_mode);
-  c->have_traj = false;
-  c->M = M;
-  c->P = P;
-  c->loc_mode = loc_mode;
-  c->n_active = 0;
-  c->have_transform = false;
-  c->spec.launched = false;
-  harvest_obs_ms(c);
-  c->obs_ms = 0.0;
-  if (P == 0) {
-    c->have_traj = true;
-    c->h_assim.clear();
-    return EFA_OK;
-  }
-  if (!ym_dev || !Yp_dev || !ob_value || !ob_error || !ob_assim)
+// One obs_phase call: its arguments and the workspace layout that the steps below share.
+struct ObsCall {
+  int M = 0, loc_mode = EFA_LOC_NONE;
+  long P = 0;
+  double *ym_dev = nullptr, *Yp_dev = nullptr;  // the caller's obs block
+  const uint8_t* ob_assim = nullptr;            // host
+  bool carry_T = false;  // M identity rows ride along behind the obs rows: Phase A leaves the transform [T | w] in them
+  long extra = 0, R = 0;  // those rows (M or 0); rows of the working block, P + extra
+  double *Yw = nullptr, *ymw = nullptr;  // the working block [R][M], [R]
+  size_t oslot = 0;      // bytes of one diagnostics array in out_pack / pin_out
+  size_t pack_bytes = 0; // of the input pack, which goes to the device inside the prep launch
+  long B = 0;            // obs per pass of the per-batch kernels
+  bool pipe_ok = false;  // the persistent kernels apply
+  long Wmax = 0, nwin = 1;  // obs per window, windows
+  long TS_std = 0, TS_band = 0, TS = 0;  // record strides of the two layouts, and the larger (the allocation's)
+};
+// The layout of the records Phase B reads.  All windows of a call leave ONE layout: Phase B reads them with one stride.
+enum class Records { kNone /* dense ye rows in Ye_rec: the per-batch kernels */, kStandard /* k_pipe, k_pipe_gram */, kBand /* k_pipe_band */ };
+long record_stride(const ObsCall& a, Records r) { return r == Records::kBand ? a.TS_band : a.TS_std; }
+
+// Obs [w0, w1) and the rows their persistent launch works on: the block itself when one window covers it (direct), else a
+// workspace [window rows | transform rows].
+struct Window {
+  long w, w0, w1, Pw, Rw;
+  bool direct;
+  double *Wy, *Wm;
+};
+Window make_window(const ObsCall& a, long w) {
+  const long w0 = a.pipe_ok ? w * a.Wmax : 0, w1 = a.pipe_ok ? ((w0 + a.Wmax < a.P) ? w0 + a.Wmax : a.P) : a.P;
+  return Window{w, w0, w1, w1 - w0, w1 - w0 + ((a.nwin == 1) ? a.extra : 2 * a.extra), a.nwin == 1, a.Yw, a.ymw};
+}
+
+// Argument and radius checks, the host copies of the assimilate flags and the geometry, the per-ob inputs in one pinned pack,
+// the diagnostics pack and the workspaces.  ob_hw comes back sanitised.
+int stage_obs_inputs(efa_ctx* c, ObsCall& a, const double* ob_value, const double* ob_error, const double* ob_lat,
+                     const double* ob_lon, const double*& ob_hw) {
+  const int M = a.M;
+  const long P = a.P;
+  const uint8_t* ob_assim = a.ob_assim;
+  if (!a.ym_dev || !a.Yp_dev || !ob_value || !ob_error || !ob_assim)
     return fail(EFA_ERR_INVALID, "null observation array");
-  if (loc_mode == EFA_LOC_GC) {
+  if (a.loc_mode == EFA_LOC_GC) {
     if (!ob_lat || !ob_lon || !ob_hw) return fail(EFA_ERR_INVALID, "GC localisation needs ob_lat/ob_lon/ob_halfwidth_km");
     // the reference reads localize_radius only for obs it assimilates (ensrf.py:74-76 comes before :101):
     // an unassimilated ob may carry any radius; it is replaced by a harmless one before it goes to the device
@@ -407,7 +440,7 @@ int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const d
   }
   c->h_assim.assign(ob_assim, ob_assim + P);
   for (long k = 0; k < P; ++k) c->n_active += ob_assim[k] ? 1 : 0;
-  if (loc_mode == EFA_LOC_GC) {
+  if (a.loc_mode == EFA_LOC_GC) {
     const size_t nb8 = (size_t)P * sizeof(double);
     const bool same = (long)c->geo_lat.size() == P && std::memcmp(c->geo_lat.data(), ob_lat, nb8) == 0 &&
                       std::memcmp(c->geo_lon.data(), ob_lon, nb8) == 0 && std::memcmp(c->geo_hw.data(), ob_hw, nb8) == 0 &&
@@ -421,17 +454,16 @@ int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const d
     }
   }
 
-  const bool carry_T = (loc_mode == EFA_LOC_NONE) && transform_supported(M) && (c->path != EFA_PATH_SWEEP);
-  const long extra = carry_T ? M : 0;
-  const long R = P + extra;
+  a.carry_T = (a.loc_mode == EFA_LOC_NONE) && transform_supported(M) && (c->path != EFA_PATH_SWEEP);
+  a.extra = a.carry_T ? M : 0;
+  a.R = P + a.extra;
   const size_t dP = (size_t)P * sizeof(double);
 
-  size_t pack_bytes = 0;
   // per-ob inputs: [value | error | assim bytes | {error, sqrt(error), assimilate (1.0 / 0.0), 0} x P | lat | lon | halfwidth] in one
   // allocation, ONE H2D from pinned memory (the last three slots only with localisation); the four-double records are the band
   // leader's per-ob constants, fetched with wave-uniform loads
   {
-    const bool gc = loc_mode == EFA_LOC_GC;
+    const bool gc = a.loc_mode == EFA_LOC_GC;
     const size_t slot = ((size_t)P * sizeof(double) + 255) & ~(size_t)255;
     const size_t total = 10 * slot;
     EFA_TRY(c->ob_pack.reserve(total));
@@ -462,360 +494,447 @@ int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const d
     c->ob_lat.carve(db + 7 * slot, slot);
     c->ob_lon.carve(db + 8 * slot, slot);
     c->ob_hw.carve(db + 9 * slot, slot);
-    pack_bytes = gc ? total : 7 * slot;  // goes to the device inside the prep launch below (read from the mapped pinned buffer)
+    a.pack_bytes = gc ? total : 7 * slot;  // goes to the device inside the prep launch (read from the mapped pinned buffer)
   }
   EFA_TRY(c->Ye_rec.reserve((size_t)P * M * sizeof(double)));
   EFA_TRY(c->coef.reserve((size_t)P * kCoefStride * sizeof(double)));
   // per-ob diagnostics: [prior_mean | prior_var | post_mean | post_var | assimilated bytes], one D2H at the end
-  const size_t oslot = ((size_t)P * sizeof(double) + 255) & ~(size_t)255;
+  a.oslot = ((size_t)P * sizeof(double) + 255) & ~(size_t)255;
   {
-    EFA_TRY(c->out_pack.reserve(5 * oslot));
-    EFA_TRY(c->pin_out.reserve(5 * oslot));
+    EFA_TRY(c->out_pack.reserve(5 * a.oslot));
+    EFA_TRY(c->pin_out.reserve(5 * a.oslot));
     char* db = static_cast<char*>(c->out_pack.p);
-    c->d_prior_mean.carve(db, oslot);
-    c->d_prior_var.carve(db + oslot, oslot);
-    c->d_post_mean.carve(db + 2 * oslot, oslot);
-    c->d_post_var.carve(db + 3 * oslot, oslot);
-    c->d_assimilated.carve(db + 4 * oslot, oslot);
+    c->d_prior_mean.carve(db, a.oslot);
+    c->d_prior_var.carve(db + a.oslot, a.oslot);
+    c->d_post_mean.carve(db + 2 * a.oslot, a.oslot);
+    c->d_post_var.carve(db + 3 * a.oslot, a.oslot);
+    c->d_assimilated.carve(db + 4 * a.oslot, a.oslot);
   }
-  EFA_TRY(c->Yw.reserve((size_t)R * M * sizeof(double)));
-  EFA_TRY(c->ymw.reserve((size_t)R * sizeof(double)));
+  EFA_TRY(c->Yw.reserve((size_t)a.R * M * sizeof(double)));
+  EFA_TRY(c->ymw.reserve((size_t)a.R * sizeof(double)));
+  a.Yw = c->Yw.as<double>();
+  a.ymw = c->ymw.as<double>();
+  return EFA_OK;
+}
 
+// ---- Phase A in WINDOWS of observations -----------------------------------------------------------------
+// A persistent launch keeps 64 obs rows per workgroup and needs its whole grid resident: at most kPipeMaxWGs * 64
+// rows (the window's obs + the M carried transform rows).  More observations are taken window by window: the
+// window's rows and the transform rows go through one persistent launch (in a workspace when the window is not the
+// whole block), and the rows of all OTHER observations -- earlier windows' (the reference keeps updating them,
+// ensrf.py:141 acts on every augmented row) and later ones' -- take the window's trajectory through the per-batch
+// sweep kernel, 64 obs per pass.  A window whose launch gives up (bounded spin, cancellation guard twice) is redone,
+// for its own observations only, by the per-batch kernels.
+// Without localisation a window that is not the whole block carries a SECOND set of identity rows: they come out as the
+// window's own transform (T_w, w_w), which then updates all other rows of the block in one k_transform pass instead of
+// one sweep pass per 64 obs.
+//
+// The window plan, and ONE launch that copies the caller's block into the working rows, writes the identity rows, fills the
+// records with the sentinel and clears the status words.
+int start_phase_a(efa_ctx* c, ObsCall& a) {
+  const int M = a.M;
+  const long P = a.P;
   hipStream_t s = c->stream;
   if (c->timing) EFA_HIP(hipEventRecord(c->ev[0], s));
-  double* Yw = c->Yw.as<double>();
-  double* ymw = c->ymw.as<double>();
-  // (the copies of the caller's block into the working rows, the identity rows, the sentinel fill of the records and the
-  //  clearing of the status words are ONE launch: launch_phase_a_prep below, once the record stride is known)
-
-  // ---- Phase A in WINDOWS of observations -----------------------------------------------------------------
-  // A persistent launch keeps 64 obs rows per workgroup and needs its whole grid resident: at most kPipeMaxWGs * 64
-  // rows (the window's obs + the M carried transform rows).  More observations are taken window by window: the
-  // window's rows and the transform rows go through one persistent launch (in a workspace when the window is not the
-  // whole block), and the rows of all OTHER observations -- earlier windows' (the reference keeps updating them,
-  // ensrf.py:141 acts on every augmented row) and later ones' -- take the window's trajectory through the per-batch
-  // sweep kernel, 64 obs per pass.  A window whose launch gives up (bounded spin, cancellation guard twice) is redone,
-  // for its own observations only, by the per-batch kernels.
-  // Without localisation a window that is not the whole block carries a SECOND set of identity rows: they come out as the
-  // window's own transform (T_w, w_w), which then updates all other rows of the block in one k_transform pass instead of
-  // one sweep pass per 64 obs.
-  const long Wone = (long)kPipeMaxWGs * kPipeRowsPerWG - extra;            // one window covers the block up to here
-  const long Wmax = (P <= Wone) ? Wone : Wone - extra;                       // else: two sets of extra rows per window
-  const bool pipe_ok = c->use_pipeline && Wmax > 0 && pipeline_supported(M, (P <= Wone ? P + extra : Wmax + 2 * extra));
-  const long TS_std = traj_stride(M), TS_band = band_traj_stride(M);
-  const long TS = TS_std > TS_band ? TS_std : TS_band;
-  const long B = effective_batch(c, M);
-  bool traj_kind_band = false, any_pipeline = false, any_batch = false;
-  bool diag_on_host = false;  // the diagnostics are already in pin_out (copied with the status words of the one launch that did it all)
-  if (pipe_ok) {
-    EFA_TRY(c->traj.reserve((size_t)P * TS * sizeof(unsigned long long)));
+  const long Wone = (long)kPipeMaxWGs * kPipeRowsPerWG - a.extra;           // one window covers the block up to here
+  a.Wmax = (P <= Wone) ? Wone : Wone - a.extra;                              // else: two sets of extra rows per window
+  a.pipe_ok = c->use_pipeline && a.Wmax > 0 && pipeline_supported(M, (P <= Wone ? P + a.extra : a.Wmax + 2 * a.extra));
+  a.TS_std = traj_stride(M);
+  a.TS_band = band_traj_stride(M);
+  a.TS = a.TS_std > a.TS_band ? a.TS_std : a.TS_band;
+  a.B = effective_batch(c, M);
+  if (a.pipe_ok) {
+    EFA_TRY(c->traj.reserve((size_t)P * a.TS * sizeof(unsigned long long)));
     EFA_TRY(c->status.reserve(3 * sizeof(int)));
   }
-  EFA_HIP(launch_phase_a_prep(P, M, Yp_dev, ym_dev, Yw, ymw, carry_T ? 1 : 0, pipe_ok ? c->traj.as<unsigned long long>() : nullptr,
-                              pipe_ok ? (size_t)P * TS : 0, kTrajSentinel, pipe_ok ? c->status.as<int>() : nullptr,
-                              c->pin_in.p, c->ob_pack.p, pack_bytes, s));
-  bool status_clear = pipe_ok;  // (cleared by the prep launch: the first window's launch needs no memset of its own)
-  // rows [lo, hi) of the obs block take obs [b0, b0 + nb) from (Ye, ye_stride): the per-batch sweep
-  auto sweep_rows = [&](long b0, int nb, const double* Ye, long ye_stride, long skip_lo, long skip_hi, long nrows) -> int {
-    SweepArgs a{};
-    a.Xin = Yw;
-    a.xin = ymw;
-    a.Xout = Yw;
-    a.xout = ymw;
-    a.nrows = nrows;
-    a.M = M;
-    a.Ye = Ye;
-    a.ye_stride = ye_stride;
-    a.coef = c->coef.as<double>() + (size_t)b0 * kCoefStride;
-    a.nb = nb;
-    a.taper_mode = (loc_mode == EFA_LOC_GC) ? kTaperObs : kTaperNone;
-    a.row_lat = c->ob_lat.as<double>();
-    a.row_lon = c->ob_lon.as<double>();
-    a.ob_lat = c->ob_lat.as<double>() + b0;
-    a.ob_lon = c->ob_lon.as<double>() + b0;
-    a.ob_hw = c->ob_hw.as<double>() + b0;
-    a.skip_lo = skip_lo;
-    a.skip_hi = skip_hi;
-    a.taper_rows = P;
-    EFA_HIP(launch_sweep(a, s));
-    return EFA_OK;
-  };
-  // obs [w0, w1) by the per-batch kernels (k_diag on the batch's own rows, k_sweep on every other row of the block)
-  auto batch_window = [&](long w0, long w1) -> int {
-    for (long b0 = w0; b0 < w1; b0 += B) {
-      const int nb = (int)((w1 - b0 < B) ? (w1 - b0) : B);
-      DiagArgs d{};
-      d.Yp = Yw;
-      d.ym = ymw;
-      d.M = M;
-      d.b0 = b0;
-      d.nb = nb;
-      d.ob_value = c->ob_val.as<double>();
-      d.ob_error = c->ob_err.as<double>();
-      d.ob_assim = c->ob_asm.as<uint8_t>();
-      d.loc_mode = loc_mode;
-      d.ob_lat = c->ob_lat.as<double>();
-      d.ob_lon = c->ob_lon.as<double>();
-      d.ob_hw = c->ob_hw.as<double>();
-      d.Ye_rec = c->Ye_rec.as<double>();
-      d.coef = c->coef.as<double>();
-      d.prior_mean = c->d_prior_mean.as<double>();
-      d.prior_var = c->d_prior_var.as<double>();
-      d.post_mean = c->d_post_mean.as<double>();
-      d.post_var = c->d_post_var.as<double>();
-      d.assimilated = c->d_assimilated.as<uint8_t>();
-      EFA_HIP(launch_diag(d, s));
-      long act = 0;
-      for (int k = 0; k < nb; ++k) act += ob_assim[b0 + k] ? 1 : 0;
-      if (act == 0 || R == nb) continue;
-      EFA_TRY(sweep_rows(b0, nb, c->Ye_rec.as<double>() + (size_t)b0 * M, M, b0, b0 + nb, R));
+  EFA_HIP(launch_phase_a_prep(P, M, a.Yp_dev, a.ym_dev, a.Yw, a.ymw, a.carry_T ? 1 : 0,
+                              a.pipe_ok ? c->traj.as<unsigned long long>() : nullptr, a.pipe_ok ? (size_t)P * a.TS : 0, kTrajSentinel,
+                              a.pipe_ok ? c->status.as<int>() : nullptr, c->pin_in.p, c->ob_pack.p, a.pack_bytes, s));
+  a.nwin = a.pipe_ok ? (P + a.Wmax - 1) / a.Wmax : 1;
+  return EFA_OK;
+}
+
+// rows [0, nrows) of the working block but [skip_lo, skip_hi) take obs [b0, b0 + nb) from (Ye, ye_stride): the per-batch sweep
+int sweep_rows(efa_ctx* c, const ObsCall& a, long b0, int nb, const double* Ye, long ye_stride, long skip_lo, long skip_hi,
+               long nrows) {
+  SweepArgs sw{};
+  sw.Xin = a.Yw;
+  sw.xin = a.ymw;
+  sw.Xout = a.Yw;
+  sw.xout = a.ymw;
+  sw.nrows = nrows;
+  sw.M = a.M;
+  sw.Ye = Ye;
+  sw.ye_stride = ye_stride;
+  sw.coef = c->coef.as<double>() + (size_t)b0 * kCoefStride;
+  sw.nb = nb;
+  sw.taper_mode = (a.loc_mode == EFA_LOC_GC) ? kTaperObs : kTaperNone;
+  sw.row_lat = c->ob_lat.as<double>();
+  sw.row_lon = c->ob_lon.as<double>();
+  sw.ob_lat = c->ob_lat.as<double>() + b0;
+  sw.ob_lon = c->ob_lon.as<double>() + b0;
+  sw.ob_hw = c->ob_hw.as<double>() + b0;
+  sw.skip_lo = skip_lo;
+  sw.skip_hi = skip_hi;
+  sw.taper_rows = a.P;
+  EFA_HIP(launch_sweep(sw, c->stream));
+  return EFA_OK;
+}
+
+long active_in(const ObsCall& a, long b0, int nb) {
+  long act = 0;
+  for (int k = 0; k < nb; ++k) act += a.ob_assim[b0 + k] ? 1 : 0;
+  return act;
+}
+
+// obs [w0, w1) by the per-batch kernels (k_diag on the batch's own rows, k_sweep on every other row of the block)
+int batch_window(efa_ctx* c, const ObsCall& a, long w0, long w1) {
+  for (long b0 = w0; b0 < w1; b0 += a.B) {
+    const int nb = (int)((w1 - b0 < a.B) ? (w1 - b0) : a.B);
+    DiagArgs d{};
+    d.Yp = a.Yw;
+    d.ym = a.ymw;
+    d.M = a.M;
+    d.b0 = b0;
+    d.nb = nb;
+    d.ob_value = c->ob_val.as<double>();
+    d.ob_error = c->ob_err.as<double>();
+    d.ob_assim = c->ob_asm.as<uint8_t>();
+    d.loc_mode = a.loc_mode;
+    d.ob_lat = c->ob_lat.as<double>();
+    d.ob_lon = c->ob_lon.as<double>();
+    d.ob_hw = c->ob_hw.as<double>();
+    d.Ye_rec = c->Ye_rec.as<double>();
+    d.coef = c->coef.as<double>();
+    d.prior_mean = c->d_prior_mean.as<double>();
+    d.prior_var = c->d_prior_var.as<double>();
+    d.post_mean = c->d_post_mean.as<double>();
+    d.post_var = c->d_post_var.as<double>();
+    d.assimilated = c->d_assimilated.as<uint8_t>();
+    EFA_HIP(launch_diag(d, c->stream));
+    if (active_in(a, b0, nb) == 0 || a.R == nb) continue;
+    EFA_TRY(sweep_rows(c, a, b0, nb, c->Ye_rec.as<double>() + (size_t)b0 * a.M, a.M, b0, b0 + nb, a.R));
+  }
+  return EFA_OK;
+}
+
+// ... and for a window inside a call whose records are laid out already: the dense ye rows into that layout, zero-filled first
+int batch_window_into_records(efa_ctx* c, const ObsCall& a, const Window& win, Records layout) {
+  EFA_TRY(batch_window(c, a, win.w0, win.w1));
+  const long TSk = record_stride(a, layout);
+  double* rec = reinterpret_cast<double*>(c->traj.p) + (size_t)win.w0 * TSk;
+  EFA_HIP(hipMemsetAsync(rec, 0, (size_t)win.Pw * TSk * sizeof(double), c->stream));
+  EFA_HIP(hipMemcpy2DAsync(rec, (size_t)TSk * sizeof(double), c->Ye_rec.as<double>() + (size_t)win.w0 * a.M, (size_t)a.M * sizeof(double),
+                           (size_t)a.M * sizeof(double), (size_t)win.Pw, hipMemcpyDeviceToDevice, c->stream));
+  return EFA_OK;
+}
+
+// A windowed launch's rows, [window rows | transform rows | the window's own identity rows], copied out of the block.  Also the
+// restore after a failed attempt: the block keeps the pre-launch rows.
+int stage_window(efa_ctx* c, const ObsCall& a, const Window& win) {
+  if (win.direct) return EFA_OK;
+  hipStream_t s = c->stream;
+  const int M = a.M;
+  EFA_HIP(hipMemcpyAsync(win.Wy, a.Yw + (size_t)win.w0 * M, (size_t)win.Pw * M * sizeof(double), hipMemcpyDeviceToDevice, s));
+  EFA_HIP(hipMemcpyAsync(win.Wm, a.ymw + win.w0, (size_t)win.Pw * sizeof(double), hipMemcpyDeviceToDevice, s));
+  if (a.extra) {
+    EFA_HIP(hipMemcpyAsync(win.Wy + (size_t)win.Pw * M, a.Yw + (size_t)a.P * M, (size_t)a.extra * M * sizeof(double),
+                           hipMemcpyDeviceToDevice, s));
+    EFA_HIP(hipMemcpyAsync(win.Wm + win.Pw, a.ymw + a.P, (size_t)a.extra * sizeof(double), hipMemcpyDeviceToDevice, s));
+    EFA_HIP(launch_set_identity(M, win.Wy + (size_t)(win.Pw + a.extra) * M, win.Wm + win.Pw + a.extra, s));  // the window's own transform
+  }
+  return EFA_OK;
+}
+
+// the rows of a failed attempt as they were before it: a direct launch from the caller's block and the identity rows
+int restore_window(efa_ctx* c, const ObsCall& a, const Window& win) {
+  if (!win.direct) return stage_window(c, a, win);
+  hipStream_t s = c->stream;
+  EFA_HIP(hipMemcpyAsync(a.Yw, a.Yp_dev, (size_t)a.P * a.M * sizeof(double), hipMemcpyDeviceToDevice, s));
+  EFA_HIP(hipMemcpyAsync(a.ymw, a.ym_dev, (size_t)a.P * sizeof(double), hipMemcpyDeviceToDevice, s));
+  if (a.carry_T) EFA_HIP(launch_set_identity(a.M, a.Yw + (size_t)a.P * a.M, a.ymw + a.P, s));
+  return EFA_OK;
+}
+
+// The persistent launch's arguments but the records; with localisation the window's obs-obs taper table, which a direct
+// window reuses while the geometry, its shape and its allocation are unchanged.
+int window_pipe_args(efa_ctx* c, const ObsCall& a, const Window& win, PipeArgs* out) {
+  hipStream_t s = c->stream;
+  const long w0 = win.w0, Pw = win.Pw, Rw = win.Rw;
+  PipeArgs pa{};
+  pa.Yp = win.Wy;
+  pa.ym = win.Wm;
+  pa.R = Rw;
+  pa.P = Pw;
+  pa.M = a.M;
+  pa.ob_value = c->ob_val.as<double>() + w0;
+  pa.ob_error = c->ob_err.as<double>() + w0;
+  pa.ob_assim = c->ob_asm.as<uint8_t>() + w0;
+  pa.ob_errsq = c->ob_errsq.as<double>() + 4 * w0;
+  pa.loc_mode = a.loc_mode;
+  pa.tw = nullptr;
+  if (a.loc_mode == EFA_LOC_GC) {
+    EFA_TRY(c->tw_mat.reserve((size_t)Pw * Rw * sizeof(double)));
+    EFA_TRY(c->gc_obtrig.reserve((size_t)Pw * 6 * sizeof(double)));
+    const bool tw_ok = c->geometry_reuse && win.direct && c->tw_serial == c->geo_serial && c->tw_Pw == Pw && c->tw_Rw == Rw &&
+                       c->tw_ptr == c->tw_mat.p;
+    if (!tw_ok) {
+      EFA_HIP(launch_obs_taper_matrix(Pw, Rw, c->ob_lat.as<double>() + w0, c->ob_lon.as<double>() + w0, c->ob_hw.as<double>() + w0,
+                                      c->gc_obtrig.as<double>(), c->tw_mat.as<double>(), s));
+      c->tw_serial = win.direct ? c->geo_serial : -1;  // (a window's table is not the whole block's)
+      c->tw_Pw = Pw;
+      c->tw_Rw = Rw;
+      c->tw_ptr = c->tw_mat.p;
     }
+    pa.tw = c->tw_mat.as<double>();
+  }
+  pa.coef = c->coef.as<double>() + (size_t)w0 * kCoefStride;
+  pa.prior_mean = c->d_prior_mean.as<double>() + w0;
+  pa.prior_var = c->d_prior_var.as<double>() + w0;
+  pa.post_mean = c->d_post_mean.as<double>() + w0;
+  pa.post_var = c->d_post_var.as<double>() + w0;
+  pa.assimilated = c->d_assimilated.as<uint8_t>() + w0;
+  pa.status = c->status.as<int>();
+  pa.spin_limit = c->spin_limit;
+  pa.spin_ticks = (c->spin_ms >= 0 ? c->spin_ms : 100 + Pw / 100) * 100000L;  // s_memrealtime runs at 100 MHz
+  pa.cu_count = c->cu_count;
+  pa.debug = (int)c->pipe_debug;
+  pa.dbg = nullptr;
+  if (c->pipe_debug & 4) {
+    EFA_TRY(c->dbg.reserve((size_t)a.P * 8 * sizeof(unsigned long long)));
+    if (win.w == 0) EFA_HIP(hipMemsetAsync(c->dbg.p, 0, (size_t)a.P * 8 * sizeof(unsigned long long), s));
+    pa.dbg = c->dbg.as<unsigned long long>() + (size_t)w0 * 8;
+  }
+  *out = pa;
+  return EFA_OK;
+}
+
+// The persistent kinds to try for a window, in order: 4 band leader (option "gram" 2), 3 Gram leader (1), 1 vector chain, the
+// first whose kernel supports the window, then kind 1 if that was not it.  All windows of a call must leave records of ONE layout:
+// after standard records a later window does not start with the band leader, and after band records it tries nothing but the band
+// leader (it goes to the per-batch kernels instead).  A 0 ends the list.
+std::array<int, 2> window_kinds(const efa_ctx* c, const ObsCall& a, long Rw, Records layout) {
+  const bool band = c->use_gram >= 2 && pipeline_band_supported(a.M, Rw, a.loc_mode);
+  const bool gram = c->use_gram >= 1 && pipeline_gram_supported(a.M, Rw, a.loc_mode);
+  const int first = (band && layout != Records::kStandard) ? 4 : gram ? 3 : 1;
+  if (layout == Records::kBand) return {first == 4 ? 4 : 0, 0};
+  return {first, first == 1 ? 0 : 1};
+}
+
+// efa_ensrf_cycle_dev: the state transform goes into the stream behind the launch whose status is not known yet -- it reads
+// [T | w] from the launch's working rows and writes only the caller's posterior; a launch that reports a fallback is redone
+// and the transform enqueued again (by the caller), so a wrong guess costs time, never a result.  The device then runs
+// Phase A -> Phase B with no host round trip in between.
+int speculative_transform(efa_ctx* c, const ObsCall& a, const Window& win, bool* placed) {
+  *placed = false;
+  if (!(c->spec.armed && c->spec.rows > 0 && win.direct && a.carry_T && c->n_active > 0 &&
+        (c->path == EFA_PATH_TRANSFORM || (c->path == EFA_PATH_AUTO && auto_transform(a.M, c->n_active, true)))))
     return EFA_OK;
-  };
-  const long nwin = pipe_ok ? (P + Wmax - 1) / Wmax : 1;
-  for (long w = 0; w < nwin; ++w) {
-    const long w0 = pipe_ok ? w * Wmax : 0, w1 = pipe_ok ? ((w0 + Wmax < P) ? w0 + Wmax : P) : P;
-    const long Pw = w1 - w0, Rw = Pw + ((nwin == 1) ? extra : 2 * extra);
-    bool done = false;
-    const bool tw_fits = (loc_mode != EFA_LOC_GC) || ((size_t)Pw * (size_t)Rw * sizeof(double) <= ((size_t)3 << 30));
-    if (pipe_ok && tw_fits) {
-      // the launch's rows: the block itself when one window covers it, else a workspace [window rows | transform rows]
-      const bool direct = (nwin == 1);
-      double* Wy = Yw;
-      double* Wm = ymw;
-      if (!direct) {
-        EFA_TRY(c->win_Y.reserve((size_t)Rw * M * sizeof(double)));
-        EFA_TRY(c->win_m.reserve((size_t)Rw * sizeof(double)));
-        Wy = c->win_Y.as<double>();
-        Wm = c->win_m.as<double>();
-      }
-      auto stage_in = [&]() -> int {  // (also the restore after a failed attempt: the block keeps the pre-launch rows)
-        if (direct) return EFA_OK;
-        EFA_HIP(hipMemcpyAsync(Wy, Yw + (size_t)w0 * M, (size_t)Pw * M * sizeof(double), hipMemcpyDeviceToDevice, s));
-        EFA_HIP(hipMemcpyAsync(Wm, ymw + w0, (size_t)Pw * sizeof(double), hipMemcpyDeviceToDevice, s));
-        if (extra) {
-          EFA_HIP(hipMemcpyAsync(Wy + (size_t)Pw * M, Yw + (size_t)P * M, (size_t)extra * M * sizeof(double), hipMemcpyDeviceToDevice, s));
-          EFA_HIP(hipMemcpyAsync(Wm + Pw, ymw + P, (size_t)extra * sizeof(double), hipMemcpyDeviceToDevice, s));
-          EFA_HIP(launch_set_identity(M, Wy + (size_t)(Pw + extra) * M, Wm + Pw + extra, s));  // the window's own transform
-        }
-        return EFA_OK;
-      };
-      EFA_TRY(stage_in());
-      if (!status_clear) EFA_HIP(hipMemsetAsync(c->status.p, 0, 3 * sizeof(int), s));
-      status_clear = false;
-      PipeArgs pa{};
-      pa.Yp = Wy;
-      pa.ym = Wm;
-      pa.R = Rw;
-      pa.P = Pw;
-      pa.M = M;
-      pa.ob_value = c->ob_val.as<double>() + w0;
-      pa.ob_error = c->ob_err.as<double>() + w0;
-      pa.ob_assim = c->ob_asm.as<uint8_t>() + w0;
-      pa.ob_errsq = c->ob_errsq.as<double>() + 4 * w0;
-      pa.loc_mode = loc_mode;
-      pa.tw = nullptr;
-      if (loc_mode == EFA_LOC_GC) {
-        EFA_TRY(c->tw_mat.reserve((size_t)Pw * Rw * sizeof(double)));
-        EFA_TRY(c->gc_obtrig.reserve((size_t)Pw * 6 * sizeof(double)));
-        const bool tw_ok = c->geometry_reuse && direct && c->tw_serial == c->geo_serial && c->tw_Pw == Pw && c->tw_Rw == Rw &&
-                           c->tw_ptr == c->tw_mat.p;
-        if (!tw_ok) {
-          EFA_HIP(launch_obs_taper_matrix(Pw, Rw, c->ob_lat.as<double>() + w0, c->ob_lon.as<double>() + w0, c->ob_hw.as<double>() + w0,
-                                          c->gc_obtrig.as<double>(), c->tw_mat.as<double>(), s));
-          c->tw_serial = direct ? c->geo_serial : -1;  // (a window's table is not the whole block's)
-          c->tw_Pw = Pw;
-          c->tw_Rw = Rw;
-          c->tw_ptr = c->tw_mat.p;
-        }
-        pa.tw = c->tw_mat.as<double>();
-      }
-      pa.coef = c->coef.as<double>() + (size_t)w0 * kCoefStride;
-      pa.prior_mean = c->d_prior_mean.as<double>() + w0;
-      pa.prior_var = c->d_prior_var.as<double>() + w0;
-      pa.post_mean = c->d_post_mean.as<double>() + w0;
-      pa.post_var = c->d_post_var.as<double>() + w0;
-      pa.assimilated = c->d_assimilated.as<uint8_t>() + w0;
-      pa.status = c->status.as<int>();
-      pa.spin_limit = c->spin_limit;
-      pa.spin_ticks = (c->spin_ms >= 0 ? c->spin_ms : 100 + Pw / 100) * 100000L;  // s_memrealtime runs at 100 MHz
-      pa.cu_count = c->cu_count;
-      pa.debug = (int)c->pipe_debug;
-      pa.dbg = nullptr;
-      if (c->pipe_debug & 4) {
-        EFA_TRY(c->dbg.reserve((size_t)P * 8 * sizeof(unsigned long long)));
-        if (w == 0) EFA_HIP(hipMemsetAsync(c->dbg.p, 0, (size_t)P * 8 * sizeof(unsigned long long), s));
-        pa.dbg = c->dbg.as<unsigned long long>() + (size_t)w0 * 8;
-      }
-      // attempt 0: Gram-space leader (option "gram"); attempt 1: vector-chain pipeline.  A failed
-      // attempt (bounded spin expired, or the Gram downdate's cancellation guard) may have let
-      // finished workgroups write their rows back, so the launch's rows are restored before the next.
-      // An attempt is skipped when its grid cannot be co-resident (occupancy query in the launcher), and after an
-      // attempt whose bounded spins EXPIRED (status 1: some workgroups never became resident, e.g. another
-      // kernel holds CUs) the other persistent kernel is not tried either: it has the same residency need.
-      // All windows of a call must leave records of ONE layout (Phase B reads them with one stride): once a window
-      // has run as the band leader, later windows do not fall back to the vector chain (they go to the per-batch kernels).
-      int first_kind = (c->use_gram >= 2 && pipeline_band_supported(M, Rw, loc_mode)) ? 4
-                       : (c->use_gram >= 1 && pipeline_gram_supported(M, Rw, loc_mode)) ? 3 : 1;
-      if (any_pipeline && !traj_kind_band && first_kind == 4) first_kind = (c->use_gram >= 1 && pipeline_gram_supported(M, Rw, loc_mode)) ? 3 : 1;
-      for (int attempt = (first_kind == 1) ? 1 : 0; attempt < 2 && !done; ++attempt) {
-        const int kind = (attempt == 0) ? first_kind : 1;
-        if (any_pipeline && traj_kind_band != (kind == 4)) break;
-        const long TSk = (kind == 4) ? TS_band : TS_std;
-        pa.traj = c->traj.as<unsigned long long>() + (size_t)w0 * TSk;
-        const hipError_t le = kind == 4 ? launch_pipeline_band(pa, s) : kind == 3 ? launch_pipeline_gram(pa, s) : launch_pipeline(pa, s);
-        if (le == hipErrorCooperativeLaunchTooLarge) {
-          (void)hipGetLastError();
-          continue;
-        }
-        EFA_HIP(le);
-        // ONE host round trip per launch: the status words and -- when this launch is the whole Phase A -- the diagnostics
-        // it wrote come back together, into pinned memory (a second copy + synchronise after the status was known left the
-        // device idle for ~40 us before Phase B; a pageable destination made the status copy itself a staged one)
-        int* st = reinterpret_cast<int*>(static_cast<char*>(c->pin_out.p) + 5 * oslot - 64);
-        if (direct) EFA_HIP(launch_results_to_host(c->out_pack.p, c->pin_out.p, 4 * oslot + (size_t)P, c->status.as<int>(), st, s));
-        else EFA_HIP(hipMemcpyAsync(st, c->status.p, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
-        // efa_ensrf_cycle_dev: the state transform goes into the stream HERE, behind the launch whose status is not known
-        // yet -- it reads [T | w] from the launch's working rows and writes only the caller's posterior; a launch that
-        // reports a fallback is redone below and the transform enqueued again (by the caller), so a wrong guess costs time, never
-        // a result.  The device then runs Phase A -> Phase B with no host round trip in between.
-        bool spec_now = false;
-        if (c->spec.armed && c->spec.rows > 0 && direct && carry_T && c->n_active > 0 &&
-            (c->path == EFA_PATH_TRANSFORM || (c->path == EFA_PATH_AUTO && auto_transform(M, c->n_active, true)))) {
-          const int pr = c->state_ms_pending ? 1 : 0;
-          if (c->timing) harvest_state_pair(c, pr);  // (both pairs unread cannot happen across the wait below; kept correct anyway)
-          // ONE event between Phase A and the transform (each record idles the stream ~6 us): the status words and diagnostics are on
-          // the host -- what the host waits for below --, the obs interval ends and the state interval of this pair begins
-          EFA_HIP(hipEventRecord(c->ev[2 + 2 * pr], s));
-          c->obs_end_ev = 2 + 2 * pr;
-          EFA_TRY(member_transform(c, c->spec.rows, M, c->spec.X, c->spec.post, Yw + (size_t)P * M, ymw + P, &c->spec.launches));
-          if (c->timing) EFA_HIP(hipEventRecord(c->ev[3 + 2 * pr], s));
-          c->spec.pair = pr;
-          spec_now = true;
-        }
-        if (spec_now) EFA_HIP(hipEventSynchronize(c->ev[2 + 2 * c->spec.pair]));  // (not the stream: the transform behind it is to run while the host goes on)
-        else EFA_HIP(hipStreamSynchronize(s));
-        c->spec.launched = false;
-        if (spec_now && c->timing) harvest_state_pair(c, 1 - c->spec.pair);  // the previous cycle's interval: complete by now
-        if (st[0] == 0 && st[1] == 0) {
-          done = true;
-          any_pipeline = true;
-          traj_kind_band = (kind == 4);
-          c->phase_a_kind = kind;
-          diag_on_host = direct;
-          c->spec.launched = spec_now;
-        } else {
-          if (direct) {
-            EFA_HIP(hipMemcpyAsync(Yw, Yp_dev, (size_t)P * M * sizeof(double), hipMemcpyDeviceToDevice, s));
-            EFA_HIP(hipMemcpyAsync(ymw, ym_dev, dP, hipMemcpyDeviceToDevice, s));
-            if (carry_T) EFA_HIP(launch_set_identity(M, Yw + (size_t)P * M, ymw + P, s));
-          } else {
-            EFA_TRY(stage_in());
-          }
-          if (st[2] == 0) break;  // not the Gram guard, so a spin expired: straight to the per-batch kernels
-          if (attempt == 0) {
-            EFA_HIP(launch_fill_u64(c->traj.as<unsigned long long>() + (size_t)w0 * TS, (size_t)Pw * TS, kTrajSentinel, s));
-            EFA_HIP(hipMemsetAsync(c->status.p, 0, 3 * sizeof(int), s));
-          }
-        }
-      }
-      if (done && !direct) {
-        // window rows and transform rows back into the block, then every other row of the block takes the window's records
-        EFA_HIP(hipMemcpyAsync(Yw + (size_t)w0 * M, Wy, (size_t)Pw * M * sizeof(double), hipMemcpyDeviceToDevice, s));
-        EFA_HIP(hipMemcpyAsync(ymw + w0, Wm, (size_t)Pw * sizeof(double), hipMemcpyDeviceToDevice, s));
-        if (extra) {
-          EFA_HIP(hipMemcpyAsync(Yw + (size_t)P * M, Wy + (size_t)Pw * M, (size_t)extra * M * sizeof(double), hipMemcpyDeviceToDevice, s));
-          EFA_HIP(hipMemcpyAsync(ymw + P, Wm + Pw, (size_t)extra * sizeof(double), hipMemcpyDeviceToDevice, s));
-        }
-        const long TSk = traj_kind_band ? TS_band : TS_std;
-        const double* yebase = reinterpret_cast<const double*>(c->traj.p);
-        if (extra) {  // unlocalised: rows [0, w0) and [w1, P) through the window's transform, in place
-          for (int part = 0; part < 2; ++part) {
-            const long lo = part ? w1 : 0, hi = part ? P : w0;
-            if (hi <= lo) continue;
-            TransformArgs t{};
-            t.Xin = Yw + (size_t)lo * M;
-            t.xin = ymw + lo;
-            t.Xout = Yw + (size_t)lo * M;
-            t.xout = ymw + lo;
-            t.nrows = hi - lo;
-            t.M = M;
-            t.T = Wy + (size_t)(Pw + extra) * M;
-            t.w = Wm + Pw + extra;
-            t.fused_members = 0;
-            EFA_HIP(launch_transform(t, s));
-          }
-        }
-        for (long b0 = w0; !extra && b0 < w1; b0 += B) {
-          const int nb = (int)((w1 - b0 < B) ? (w1 - b0) : B);
-          long act = 0;
-          for (int k = 0; k < nb; ++k) act += ob_assim[b0 + k] ? 1 : 0;
-          if (act == 0) continue;
-          EFA_TRY(sweep_rows(b0, nb, yebase + (size_t)b0 * TSk, TSk, w0, w1, P));  // rows [0, P) but the window's own
-        }
-      }
+  hipStream_t s = c->stream;
+  const int pr = c->state_ms_pending ? 1 : 0;
+  if (c->timing) harvest_state_pair(c, pr);  // (both pairs unread cannot happen across the wait below; kept correct anyway)
+  // ONE event between Phase A and the transform (each record idles the stream ~6 us): the status words and diagnostics are on
+  // the host -- what the host waits for -- the obs interval ends and the state interval of this pair begins
+  EFA_HIP(hipEventRecord(c->ev[2 + 2 * pr], s));
+  c->obs_end_ev = 2 + 2 * pr;
+  EFA_TRY(transform_with_relaxation(c, carried_transform(c, c->spec.X, nullptr, c->spec.post, nullptr, c->spec.rows, 1),
+                                    &c->spec.launches));
+  if (c->timing) EFA_HIP(hipEventRecord(c->ev[3 + 2 * pr], s));
+  c->spec.pair = pr;
+  *placed = true;
+  return EFA_OK;
+}
+
+// ONE host round trip per launch: the status words and -- when this launch is the whole Phase A -- the diagnostics it wrote come
+// back together, into pinned memory (a second copy + synchronise after the status was known left the device idle for ~40 us
+// before Phase B; a pageable destination made the status copy itself a staged one).  *st: the status words on the host.
+int launch_round_trip(efa_ctx* c, const ObsCall& a, const Window& win, const int** st_out, bool* spec_now) {
+  hipStream_t s = c->stream;
+  int* st = reinterpret_cast<int*>(static_cast<char*>(c->pin_out.p) + 5 * a.oslot - 64);
+  if (win.direct) EFA_HIP(launch_results_to_host(c->out_pack.p, c->pin_out.p, 4 * a.oslot + (size_t)a.P, c->status.as<int>(), st, s));
+  else EFA_HIP(hipMemcpyAsync(st, c->status.p, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+  EFA_TRY(speculative_transform(c, a, win, spec_now));
+  if (*spec_now) EFA_HIP(hipEventSynchronize(c->ev[2 + 2 * c->spec.pair]));  // (not the stream: the transform behind it is to run while the host goes on)
+  else EFA_HIP(hipStreamSynchronize(s));
+  c->spec.launched = false;
+  if (*spec_now && c->timing) harvest_state_pair(c, 1 - c->spec.pair);  // the previous cycle's interval: complete by now
+  *st_out = st;
+  return EFA_OK;
+}
+
+// One window through the persistent kernels.  *kind_out: the kind that did it, or 0 -- fall back to the per-batch kernels.
+// A failed attempt (bounded spin expired, or the Gram downdate's cancellation guard) may have let finished workgroups write
+// their rows back, so the launch's rows are restored before anything else runs on them.  An attempt is skipped when its grid
+// cannot be co-resident (occupancy query in the launcher), and after an attempt whose bounded spins EXPIRED (some workgroups
+// never became resident, e.g. another kernel holds CUs) no other persistent kernel is tried: they have the same residency need.
+int try_persistent_window(efa_ctx* c, const ObsCall& a, Window& win, Records layout, bool& status_clear, int* kind_out) {
+  hipStream_t s = c->stream;
+  *kind_out = 0;
+  if (!win.direct) {
+    EFA_TRY(c->win_Y.reserve((size_t)win.Rw * a.M * sizeof(double)));
+    EFA_TRY(c->win_m.reserve((size_t)win.Rw * sizeof(double)));
+    win.Wy = c->win_Y.as<double>();
+    win.Wm = c->win_m.as<double>();
+  }
+  EFA_TRY(stage_window(c, a, win));
+  if (!status_clear) EFA_HIP(hipMemsetAsync(c->status.p, 0, 3 * sizeof(int), s));  // (the prep launch cleared it for the first)
+  status_clear = false;
+  PipeArgs pa;
+  EFA_TRY(window_pipe_args(c, a, win, &pa));
+  for (const int kind : window_kinds(c, a, win.Rw, layout)) {
+    if (kind == 0) break;
+    pa.traj = c->traj.as<unsigned long long>() + (size_t)win.w0 * (kind == 4 ? a.TS_band : a.TS_std);
+    const hipError_t le = kind == 4 ? launch_pipeline_band(pa, s) : kind == 3 ? launch_pipeline_gram(pa, s) : launch_pipeline(pa, s);
+    if (le == hipErrorCooperativeLaunchTooLarge) {
+      (void)hipGetLastError();
+      continue;
     }
-    if (!done) {
-      if (any_pipeline) {
-        // records of this window must look like the pipeline's (one stride for Phase B): the per-batch kernels write
-        // dense ye rows, which are copied into the records' layout afterwards
-        EFA_TRY(batch_window(w0, w1));
-        const long TSk = traj_kind_band ? TS_band : TS_std;
-        EFA_HIP(hipMemsetAsync(reinterpret_cast<double*>(c->traj.p) + (size_t)w0 * TSk, 0, (size_t)Pw * TSk * sizeof(double), s));
-        EFA_HIP(hipMemcpy2DAsync(reinterpret_cast<double*>(c->traj.p) + (size_t)w0 * TSk, (size_t)TSk * sizeof(double),
-                                 c->Ye_rec.as<double>() + (size_t)w0 * M, (size_t)M * sizeof(double), (size_t)M * sizeof(double),
-                                 (size_t)Pw, hipMemcpyDeviceToDevice, s));
-      } else if (w == 0) {
-        // nothing has run as a pipeline: the whole call goes to the per-batch kernels
-        EFA_TRY(batch_window(0, P));
-        any_batch = true;
-        break;
-      } else {
-        return fail(EFA_ERR_UNSUPPORTED, "internal: mixed Phase-A layouts");
-      }
+    EFA_HIP(le);
+    const int* st = nullptr;
+    bool spec_now = false;
+    EFA_TRY(launch_round_trip(c, a, win, &st, &spec_now));
+    if (st[0] == 0 && st[1] == 0) {
+      *kind_out = kind;
+      c->spec.launched = spec_now;
+      return EFA_OK;
+    }
+    EFA_TRY(restore_window(c, a, win));
+    if (st[2] == 0) break;  // not the Gram guard, so a spin expired: straight to the per-batch kernels
+    if (kind != 1) {        // a failed first attempt (kind 1 only ever comes last): fresh records and status for the next
+      EFA_HIP(launch_fill_u64(c->traj.as<unsigned long long>() + (size_t)win.w0 * a.TS, (size_t)win.Pw * a.TS, kTrajSentinel, s));
+      EFA_HIP(hipMemsetAsync(c->status.p, 0, 3 * sizeof(int), s));
     }
   }
-  if (any_batch || !any_pipeline) {
+  return EFA_OK;
+}
+
+// A windowed launch that succeeded: window rows and transform rows back into the block, then every other row of the block takes
+// the window's records -- through the window's own transform without localisation, else the per-batch sweep
+int merge_window_into_block(efa_ctx* c, const ObsCall& a, const Window& win, Records layout) {
+  hipStream_t s = c->stream;
+  const int M = a.M;
+  const long P = a.P, w0 = win.w0, w1 = win.w1, Pw = win.Pw, extra = a.extra;
+  EFA_HIP(hipMemcpyAsync(a.Yw + (size_t)w0 * M, win.Wy, (size_t)Pw * M * sizeof(double), hipMemcpyDeviceToDevice, s));
+  EFA_HIP(hipMemcpyAsync(a.ymw + w0, win.Wm, (size_t)Pw * sizeof(double), hipMemcpyDeviceToDevice, s));
+  if (extra) {
+    EFA_HIP(hipMemcpyAsync(a.Yw + (size_t)P * M, win.Wy + (size_t)Pw * M, (size_t)extra * M * sizeof(double), hipMemcpyDeviceToDevice, s));
+    EFA_HIP(hipMemcpyAsync(a.ymw + P, win.Wm + Pw, (size_t)extra * sizeof(double), hipMemcpyDeviceToDevice, s));
+    for (int part = 0; part < 2; ++part) {  // unlocalised: rows [0, w0) and [w1, P) through the window's transform, in place
+      const long lo = part ? w1 : 0, hi = part ? P : w0;
+      if (hi <= lo) continue;
+      const TransformArgs t{a.Yw + (size_t)lo * M, a.ymw + lo, a.Yw + (size_t)lo * M, a.ymw + lo, hi - lo, M,
+                            win.Wy + (size_t)(Pw + extra) * M, win.Wm + Pw + extra, 0};
+      EFA_HIP(launch_transform(t, s));
+    }
+    return EFA_OK;
+  }
+  const long TSk = record_stride(a, layout);
+  const double* yebase = reinterpret_cast<const double*>(c->traj.p);
+  for (long b0 = w0; b0 < w1; b0 += a.B) {
+    const int nb = (int)((w1 - b0 < a.B) ? (w1 - b0) : a.B);
+    if (active_in(a, b0, nb) == 0) continue;
+    EFA_TRY(sweep_rows(c, a, b0, nb, yebase + (size_t)b0 * TSk, TSk, w0, w1, P));  // rows [0, P) but the window's own
+  }
+  return EFA_OK;
+}
+
+// Where Phase B finds the records, the obs block and the diagnostics back to the caller (ensrf.py:66,70,75,146-149)
+int finish_obs_phase(efa_ctx* c, const ObsCall& a, Records layout, bool diag_on_host, double* prior_mean, double* prior_var,
+                     double* post_mean, double* post_var, uint8_t* assimilated) {
+  hipStream_t s = c->stream;
+  const long P = a.P;
+  const size_t dP = (size_t)P * sizeof(double), oslot = a.oslot;
+  if (layout == Records::kNone) {
     c->ye_ptr = c->Ye_rec.as<double>();
-    c->ye_stride = M;
+    c->ye_stride = a.M;
     c->phase_a_kind = 2;
   } else {
     c->ye_ptr = reinterpret_cast<const double*>(c->traj.p);
-    c->ye_stride = traj_kind_band ? TS_band : TS_std;
+    c->ye_stride = record_stride(a, layout);
   }
   if (!c->spec.armed || c->spec.obs_out) {
-    EFA_HIP(hipMemcpyAsync(Yp_dev, Yw, (size_t)P * M * sizeof(double), hipMemcpyDeviceToDevice, s));
-    EFA_HIP(hipMemcpyAsync(ym_dev, ymw, dP, hipMemcpyDeviceToDevice, s));
+    EFA_HIP(hipMemcpyAsync(a.Yp_dev, a.Yw, (size_t)P * a.M * sizeof(double), hipMemcpyDeviceToDevice, s));
+    EFA_HIP(hipMemcpyAsync(a.ym_dev, a.ymw, dP, hipMemcpyDeviceToDevice, s));
   }
   if (c->timing && !c->spec.launched) {  // (behind a speculative transform the interval ended at the event in front of it)
     EFA_HIP(hipEventRecord(c->ev[1], s));
     c->obs_end_ev = 1;
   }
-
-  // diagnostics back to the caller (ensrf.py:66,70,75,146-149)
   if (!diag_on_host) {
     EFA_HIP(hipMemcpyAsync(c->pin_out.p, c->out_pack.p, 4 * oslot + (size_t)P, hipMemcpyDeviceToHost, s));
     EFA_HIP(hipStreamSynchronize(s));
   }
-  {
-    const char* hb = static_cast<const char*>(c->pin_out.p);
-    if (prior_mean) std::memcpy(prior_mean, hb, dP);
-    if (prior_var) std::memcpy(prior_var, hb + oslot, dP);
-    const double* pm = reinterpret_cast<const double*>(hb + 2 * oslot);
-    const double* pv = reinterpret_cast<const double*>(hb + 3 * oslot);
-    const uint8_t* as = reinterpret_cast<const uint8_t*>(hb + 4 * oslot);
-    for (long k = 0; k < P; ++k) {
-      if (assimilated) assimilated[k] = as[k];
-      if (as[k]) {
-        if (post_mean) post_mean[k] = pm[k];
-        if (post_var) post_var[k] = pv[k];
-      }
+  const char* hb = static_cast<const char*>(c->pin_out.p);
+  if (prior_mean) std::memcpy(prior_mean, hb, dP);
+  if (prior_var) std::memcpy(prior_var, hb + oslot, dP);
+  const double* pm = reinterpret_cast<const double*>(hb + 2 * oslot);
+  const double* pv = reinterpret_cast<const double*>(hb + 3 * oslot);
+  const uint8_t* as = reinterpret_cast<const uint8_t*>(hb + 4 * oslot);
+  for (long k = 0; k < P; ++k) {
+    if (assimilated) assimilated[k] = as[k];
+    if (as[k]) {
+      if (post_mean) post_mean[k] = pm[k];
+      if (post_var) post_var[k] = pv[k];
     }
   }
   if (c->timing) c->obs_ms_pending = true;  // read in efa_last_timing: the copies back to the caller's block may still be in flight
-  c->have_transform = carry_T;
+  c->have_transform = a.carry_T;
   c->have_traj = true;
   return EFA_OK;
+}
+
+int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const double* ob_value,
+              const double* ob_error, const uint8_t* ob_assim, int loc_mode, const double* ob_lat,
+              const double* ob_lon, const double* ob_hw, double* prior_mean, double* prior_var,
+              double* post_mean, double* post_var, uint8_t* assimilated) {
+  EFA_TRY(check_common(M, P));
+  if (loc_mode != EFA_LOC_NONE && loc_mode != EFA_LOC_GC) return fail(EFA_ERR_INVALID, "loc_mode %d", loc_mode);
+  c->have_traj = false;
+  c->M = M;
+  c->P = P;
+  c->loc_mode = loc_mode;
+  c->n_active = 0;
+  c->have_transform = false;
+  c->spec.launched = false;
+  harvest_obs_ms(c);
+  c->obs_ms = 0.0;
+  if (P == 0) {
+    c->have_traj = true;
+    c->h_assim.clear();
+    return EFA_OK;
+  }
+  ObsCall a;
+  a.M = M;
+  a.P = P;
+  a.loc_mode = loc_mode;
+  a.ym_dev = ym_dev;
+  a.Yp_dev = Yp_dev;
+  a.ob_assim = ob_assim;
+  EFA_TRY(stage_obs_inputs(c, a, ob_value, ob_error, ob_lat, ob_lon, ob_hw));
+  EFA_TRY(start_phase_a(c, a));
+  Records layout = Records::kNone;
+  bool diag_on_host = false;    // the diagnostics are already in pin_out (copied with the status words of the one launch that did it all)
+  bool status_clear = a.pipe_ok;  // (cleared by the prep launch: the first window's launch needs no memset of its own)
+  for (long w = 0; w < a.nwin; ++w) {
+    Window win = make_window(a, w);
+    const bool tw_fits = (loc_mode != EFA_LOC_GC) || ((size_t)win.Pw * (size_t)win.Rw * sizeof(double) <= ((size_t)3 << 30));
+    int kind = 0;
+    if (a.pipe_ok && tw_fits) EFA_TRY(try_persistent_window(c, a, win, layout, status_clear, &kind));
+    if (kind != 0) {
+      layout = (kind == 4) ? Records::kBand : Records::kStandard;
+      c->phase_a_kind = kind;
+      diag_on_host = win.direct;
+      if (!win.direct) EFA_TRY(merge_window_into_block(c, a, win, layout));
+    } else if (layout != Records::kNone) {
+      EFA_TRY(batch_window_into_records(c, a, win, layout));
+    } else if (w == 0) {
+      EFA_TRY(batch_window(c, a, 0, P));  // nothing has run as a pipeline: the whole call goes to the per-batch kernels
+      break;
+    } else {
+      return fail(EFA_ERR_UNSUPPORTED, "internal: mixed Phase-A layouts");
+    }
+  }
+  return finish_obs_phase(c, a, layout, diag_on_host, prior_mean, prior_var, post_mean, post_var, assimilated);
 }
 
 // path "auto": one transform pass or sweep passes?  By FLOPS one transform pass is M/2 observations of sweep arithmetic (the rule of
@@ -885,6 +1004,13 @@ int prepare_grid_early(efa_ctx* c, int loc_mode, const double* grid_lat, const d
   return EFA_OK;
 }
 
+// ... and once it has work to do: the grid of a localised call on the device, the state interval begins
+int begin_state_work(efa_ctx* c, const double* grid_lat, const double* grid_lon, long ncol, long n_lead, long rows) {
+  EFA_TRY(prepare_grid(c, grid_lat, grid_lon, ncol, n_lead, rows));
+  if (c->timing) EFA_HIP(hipEventRecord(c->ev[2], c->stream));
+  return EFA_OK;
+}
+
 int read_gc_pairs(efa_ctx* c) {
   if (!c->gc_pairs_pending) return EFA_OK;
   c->gc_pairs_pending = false;
@@ -896,8 +1022,8 @@ int read_gc_pairs(efa_ctx* c) {
 }
 
 // ---- Phase B, localised, one pass (efa_gcsweep.hip) --------------------------------------
-int state_gc_onepass(efa_ctx* c, long rows, const double* xm_in, const double* Xp_in, double* xm_out, double* Xp_out,
-                     long ncol, long n_lead, int fused_members) {
+int state_gc_onepass(efa_ctx* c, const double* xm_in, const double* Xp_in, double* xm_out, double* Xp_out, long ncol, long n_lead,
+                     int fused_members) {
   const int M = c->M;
   const long P = c->P;
   hipStream_t s = c->stream;
@@ -958,7 +1084,6 @@ int state_gc_onepass(efa_ctx* c, long rows, const double* xm_in, const double* X
   g.fused_members = fused_members;
   EFA_HIP(launch_sweep_gc(g, s));
   c->state_launches++;
-  (void)rows;
   return EFA_OK;
 }
 
@@ -969,7 +1094,7 @@ int state_sweeps(efa_ctx* c, long rows, const double* xm_in, const double* Xp_in
   const long P = c->P;
   hipStream_t s = c->stream;
   if (c->loc_mode == EFA_LOC_GC && c->gc_onepass && c->n_active > 0)  // every ensemble size the library accepts (2..256)
-    return state_gc_onepass(c, rows, xm_in, Xp_in, xm_out, Xp_out, ncol, rows / ncol, 0);
+    return state_gc_onepass(c, xm_in, Xp_in, xm_out, Xp_out, ncol, rows / ncol, 0);
   const long B = effective_batch(c, M);
   bool first = true;
   for (long b0 = 0; b0 < P; b0 += B) {
@@ -1016,47 +1141,18 @@ int state_phase(efa_ctx* c, long rows, int M, const double* xm_in, const double*
   if (!c->have_traj) return fail(EFA_ERR_INVALID, "efa_state_phase_dev called before efa_obs_phase_dev");
   if (M != c->M) return fail(EFA_ERR_INVALID, "M=%d differs from the obs phase's M=%d", M, c->M);
   if (rows < 0) return fail(EFA_ERR_INVALID, "negative row count");
-  harvest_state_ms(c);
-  c->state_ms = 0.0;
-  c->state_launches = 0;
-  c->path_taken = EFA_PATH_SWEEP;
+  reset_state_phase(c);
   if (rows == 0) return EFA_OK;
   if (!xm_in || !Xp_in || !xm_out || !Xp_out) return fail(EFA_ERR_INVALID, "null state pointer");
-  EFA_TRY(prepare_grid(c, grid_lat, grid_lon, ncol, n_lead, rows));
-  hipStream_t s = c->stream;
-  if (c->timing) EFA_HIP(hipEventRecord(c->ev[2], s));
-  const bool relax = relax_on(c);
-  const double* prior = nullptr;
+  EFA_TRY(begin_state_work(c, grid_lat, grid_lon, ncol, n_lead, rows));
   if (c->P > 0 && c->n_active > 0 && want_transform(c, false)) {
-    TransformArgs t{};
-    t.Xin = Xp_in;
-    t.xin = xm_in;
-    t.Xout = Xp_out;
-    t.xout = xm_out;
-    t.nrows = rows;
-    t.M = M;
-    t.T = c->Yw.as<double>() + (size_t)c->P * M;
-    t.w = c->ymw.as<double>() + c->P;
-    t.fused_members = 0;
-    c->state_launches = 1;
-    if (relax && c->relax_kind == EFA_RELAX_RTPP) {  // Xap = Xbp ((1-alpha) T + alpha I); xam as without it
-      EFA_TRY(c->relax_T.reserve((size_t)M * M * sizeof(double)));
-      EFA_HIP(launch_relax_fold(M, c->relax_alpha, t.T, c->relax_T.as<double>(), s));
-      t.T = c->relax_T.as<double>();
-      c->state_launches++;
-    } else if (relax) {  // RTPS in perturbation form: the standalone passes
-      EFA_TRY(relax_prepare(c, rows, M, Xp_in, Xp_out, &prior, &c->state_launches));
-    }
-    EFA_HIP(launch_transform(t, s));
-    if (relax && c->relax_kind == EFA_RELAX_RTPS) EFA_TRY(relax_apply(c, rows, M, Xp_out, prior, &c->state_launches));
+    EFA_TRY(transform_with_relaxation(c, carried_transform(c, Xp_in, xm_in, Xp_out, xm_out, rows, 0), &c->state_launches));
     c->path_taken = EFA_PATH_TRANSFORM;
   } else {
-    if (relax) EFA_TRY(relax_prepare(c, rows, M, Xp_in, Xp_out, &prior, &c->state_launches));
-    EFA_TRY(state_sweeps(c, rows, xm_in, Xp_in, xm_out, Xp_out, ncol));
-    if (relax) EFA_TRY(relax_apply(c, rows, M, Xp_out, prior, &c->state_launches));
+    EFA_TRY(with_relaxation(c, rows, M, Xp_in, Xp_out, &c->state_launches,
+                            [&] { return state_sweeps(c, rows, xm_in, Xp_in, xm_out, Xp_out, ncol); }));
   }
-  EFA_TRY(finish_state_timing(c, s));
-  return EFA_OK;
+  return finish_state_timing(c, c->stream);
 }
 
 }  // namespace
@@ -1474,37 +1570,29 @@ int efa_state_cycle_dev(efa_ctx* c, long rows, int M, const double* X_dev, doubl
   EFA_TRY(use(c));
   if (!c->have_traj) return fail(EFA_ERR_INVALID, "efa_state_cycle_dev called before efa_obs_phase_dev");
   if (M != c->M) return fail(EFA_ERR_INVALID, "M=%d differs from the obs phase's M=%d", M, c->M);
-  harvest_state_ms(c);
-  c->state_ms = 0.0;
-  c->state_launches = 0;
-  c->path_taken = EFA_PATH_SWEEP;
+  reset_state_phase(c);
   if (rows <= 0) return rows == 0 ? EFA_OK : fail(EFA_ERR_INVALID, "negative row count");
   if (!X_dev || !post_dev) return fail(EFA_ERR_INVALID, "null state pointer");
-  EFA_TRY(prepare_grid(c, grid_lat, grid_lon, ncol, n_lead, rows));
+  EFA_TRY(begin_state_work(c, grid_lat, grid_lon, ncol, n_lead, rows));
   hipStream_t s = c->stream;
-  if (c->timing) EFA_HIP(hipEventRecord(c->ev[2], s));
-  const bool relax = relax_on(c);
-  const double* prior = nullptr;
   if (c->P > 0 && c->n_active > 0 && want_transform(c, true)) {
-    EFA_TRY(member_transform(c, rows, M, X_dev, post_dev, c->Yw.as<double>() + (size_t)c->P * M, c->ymw.as<double>() + c->P,
-                             &c->state_launches));
+    EFA_TRY(transform_with_relaxation(c, carried_transform(c, X_dev, nullptr, post_dev, nullptr, rows, 1), &c->state_launches));
     c->path_taken = EFA_PATH_TRANSFORM;
   } else if (c->loc_mode == EFA_LOC_GC && c->gc_onepass && c->n_active > 0) {
     // localised: prior members -> posterior members in one read + one write of the state
-    if (relax) EFA_TRY(relax_prepare(c, rows, M, X_dev, post_dev, &prior, &c->state_launches));
-    EFA_TRY(state_gc_onepass(c, rows, nullptr, X_dev, nullptr, post_dev, ncol, n_lead, 1));
-    if (relax) EFA_TRY(relax_apply(c, rows, M, post_dev, prior, &c->state_launches));
+    EFA_TRY(with_relaxation(c, rows, M, X_dev, post_dev, &c->state_launches,
+                            [&] { return state_gc_onepass(c, nullptr, X_dev, nullptr, post_dev, ncol, n_lead, 1); }));
   } else {
-    if (relax) EFA_TRY(relax_prepare(c, rows, M, X_dev, post_dev, &prior, &c->state_launches));
-    EFA_TRY(c->xm_ws.reserve((size_t)rows * sizeof(double)));
-    double* xm = c->xm_ws.as<double>();
-    EFA_HIP(efa::launch_form_perts(rows, M, X_dev, 1.0, xm, post_dev, s));
-    EFA_TRY(state_sweeps(c, rows, xm, post_dev, xm, post_dev, ncol));
-    EFA_HIP(efa::launch_posterior(rows, M, xm, post_dev, post_dev, s));
-    if (relax) EFA_TRY(relax_apply(c, rows, M, post_dev, prior, &c->state_launches));
+    EFA_TRY(with_relaxation(c, rows, M, X_dev, post_dev, &c->state_launches, [&]() -> int {
+      EFA_TRY(c->xm_ws.reserve((size_t)rows * sizeof(double)));
+      double* xm = c->xm_ws.as<double>();
+      EFA_HIP(efa::launch_form_perts(rows, M, X_dev, 1.0, xm, post_dev, s));
+      EFA_TRY(state_sweeps(c, rows, xm, post_dev, xm, post_dev, ncol));
+      EFA_HIP(efa::launch_posterior(rows, M, xm, post_dev, post_dev, s));
+      return EFA_OK;
+    }));
   }
-  EFA_TRY(finish_state_timing(c, s));
-  return EFA_OK;
+  return finish_state_timing(c, s);
 }
 
 int efa_ensrf_update_dev(efa_ctx* c, long rows, int M, long P, double* xm_dev, double* Xp_dev, double* ym_dev,

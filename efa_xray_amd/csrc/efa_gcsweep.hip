@@ -628,14 +628,18 @@ hipError_t gc_lane_launch_one(const GcSweepArgs& a, hipStream_t s) {
   else hipLaunchKernelGGL((k_sweep_gc_lane<MP, false>), dim3((unsigned)(a.nblk * a.lead_split)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
-template <int... Q>
-hipError_t gc_lane_dispatch(int q, const GcSweepArgs& a, hipStream_t s, std::integer_sequence<int, Q...>) {
-  hipError_t r = hipErrorInvalidValue;
-  (void)((q == Q + 1 ? (r = gc_lane_launch_one<4 * (Q + 1)>(a, s), true) : false) || ...);
-  return r;
-}
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+int device_cus() {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus = n;
+  }
+  return cus;
+}
 
 template <int NC>
 hipError_t gc_launch(const GcSweepArgs& a0, hipStream_t s) {
@@ -644,12 +648,7 @@ hipError_t gc_launch(const GcSweepArgs& a0, hipStream_t s) {
   constexpr int RPL = (NC <= 8) ? EFA_GC_RPL : (NC <= 10) ? EFA_GC_RPL_MID : (NC <= 13) ? EFA_GC_RPL_WIDE : (NC <= 16) ? EFA_GC_RPL_XWIDE : 1;  // rows per quad while they fit the register file
   // groups of slabs per column block: whole iterations of the slab loop (4 RPL slabs), as many as it takes to give
   // every CU a dozen workgroups, at most one group per iteration
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus = n;
-  }
+  const int cus = device_cus();
   const long iters = (a.n_lead + 4 * RPL - 1) / (4 * RPL);
   long split = (12L * cus + a.nblk - 1) / a.nblk;
   if (split > iters) split = iters;
@@ -706,16 +705,6 @@ hipError_t launch_gc_count(long ncol, long P, const double* glat, const double* 
   return hipGetLastError();
 }
 
-static int device_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus = n;
-  }
-  return cus;
-}
-
 hipError_t launch_sweep_gc(const GcSweepArgs& a0, hipStream_t s) {
   const GcSweepArgs& a = a0;
   if (a.M < 2 || a.M > kMaxMembers) return hipErrorInvalidValue;
@@ -726,32 +715,9 @@ hipError_t launch_sweep_gc(const GcSweepArgs& a0, hipStream_t s) {
     GcSweepArgs l = a;
     l.lead_split = (int)((l.n_lead + 15) / 16);  // groups of 16 slabs: one workgroup each
     l.lead_chunk = 16;
-    return gc_lane_dispatch((l.M + 3) / 4, l, s, std::make_integer_sequence<int, kLaneMaxMembers / 4>{});
+    return dispatch_width((l.M + 3) / 4, WidthRange<1, kLaneMaxMembers / 4>{}, [&](auto q) { return gc_lane_launch_one<4 * q>(l, s); });
   }
-  int nch = (a.M + 7) / 8;
-  if (nch > 16) nch = (nch <= 20) ? 20 : (nch <= 24) ? 24 : 32;
-  switch (nch) {
-    case 1: return gc_launch<1>(a, s);
-    case 2: return gc_launch<2>(a, s);
-    case 3: return gc_launch<3>(a, s);
-    case 4: return gc_launch<4>(a, s);
-    case 5: return gc_launch<5>(a, s);
-    case 6: return gc_launch<6>(a, s);
-    case 7: return gc_launch<7>(a, s);
-    case 8: return gc_launch<8>(a, s);
-    case 9: return gc_launch<9>(a, s);
-    case 10: return gc_launch<10>(a, s);
-    case 11: return gc_launch<11>(a, s);
-    case 12: return gc_launch<12>(a, s);
-    case 13: return gc_launch<13>(a, s);
-    case 14: return gc_launch<14>(a, s);
-    case 15: return gc_launch<15>(a, s);
-    case 16: return gc_launch<16>(a, s);
-    case 20: return gc_launch<20>(a, s);
-    case 24: return gc_launch<24>(a, s);
-    case 32: return gc_launch<32>(a, s);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_width(sweep_slots(a.M) / 8, SweepChunks{}, [&](auto nc) { return gc_launch<nc>(a, s); });
 }
 
 }  // namespace efa

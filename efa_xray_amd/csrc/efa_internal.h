@@ -4,7 +4,28 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+#include <utility>
+
 namespace efa {
+
+// ---- runtime width -> template argument ------------------------------------------------
+// dispatch_width(w, Widths{}, f) returns f(std::integral_constant<int, W>{}) for the W of Widths equal to w, and
+// hipErrorInvalidValue when there is none.  Only the listed widths are instantiated.
+template <class F>
+hipError_t dispatch_width(int, std::integer_sequence<int>, F&&) { return hipErrorInvalidValue; }
+template <int W0, int... W, class F>
+hipError_t dispatch_width(int w, std::integer_sequence<int, W0, W...>, F&& f) {
+  if (w == W0) return f(std::integral_constant<int, W0>{});
+  return dispatch_width(w, std::integer_sequence<int, W...>{}, f);
+}
+template <int Lo, int... I>
+constexpr std::integer_sequence<int, (Lo + I)...> offset_widths(std::integer_sequence<int, I...>) { return {}; }
+// Lo, Lo+1, ..., Hi
+template <int Lo, int Hi>
+using WidthRange = decltype(offset_widths<Lo>(std::make_integer_sequence<int, Hi - Lo + 1>{}));
+// chunks of 8 members the quad-layout sweeps are instantiated for (sweep_slots(M) / 8)
+using SweepChunks = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 20, 24, 32>;
 
 // Largest ensemble the register-resident kernels are instantiated for.
 constexpr int kMaxMembers = 256;

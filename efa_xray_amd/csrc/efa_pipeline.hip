@@ -41,6 +41,7 @@
 // back and the host re-runs Phase A with the per-batch kernels.
 #include "efa_device.h"
 #include "efa_internal.h"
+#include "efa_pipe.h"
 #include "efa_rows.h"
 
 namespace efa {
@@ -53,47 +54,12 @@ constexpr int kRing = 32;              // LDS ring slots
 constexpr int kGuardEvery = 8;         // the slot-recycling guard is evaluated once per this many records
 constexpr int kPoll = 4;               // records fetched per loader round trip
 
-typedef unsigned long long u64;
-
-__device__ __forceinline__ u64 traj_load(const u64* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void traj_store(u64* p, double v) {
-  __hip_atomic_store(p, (u64)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// LDS control words: plain in-order LDS accesses + a compiler barrier (see header comment)
-__device__ __forceinline__ int ctl_load_lane(const int* p) {  // per-lane address
-  const int v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  asm volatile("" ::: "memory");
-  return v;
-}
-// every lane reads the same word: hand the compiler a wave-uniform (SGPR) value so that the
-// spin / bail logic compiles to scalar branches instead of exec-mask bookkeeping
-__device__ __forceinline__ int ctl_load(const int* p) { return __builtin_amdgcn_readfirstlane(ctl_load_lane(p)); }
 // minimum over the 8 lanes of a row group (DPP, no LDS round trip), same value in all 8 lanes
 __device__ __forceinline__ int group8_min(int v) {  // over the PL lanes of a row group
   v = min(v, __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true));
   v = min(v, __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true));
   if (PL >= 8) v = min(v, __builtin_amdgcn_mov_dpp(v, 0x141, 0xF, 0xF, true));
   return v;
-}
-__device__ __forceinline__ void ctl_store(int* p, int v) {
-  asm volatile("" ::: "memory");
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-// v_rsq_f64 / v_rcp_f64 are accurate to 2e-8 relative on gfx950 (measured, tools/latency_probe.hip):
-// one Newton step squares that (rsq: 1.5 e^2, rcp: e^2) -- below double rounding; the second-order
-// term of the rsq step is added so that both land within ~1 ulp.
-__device__ __forceinline__ double fast_rsq(double a) {  // 1/sqrt(a)
-  const double q = __builtin_amdgcn_rsq(a);
-  const double e = __builtin_fma(-a * q, q, 1.0);           // 1 - a q^2
-  const double p = __builtin_fma(0.375, e, 0.5);            // 1/2 + 3/8 e
-  return __builtin_fma(q * e, p, q);                        // q (1 + e/2 + 3 e^2/8)
-}
-__device__ __forceinline__ double fast_rcp(double b) {  // 1/b
-  const double r = __builtin_amdgcn_rcp(b);
-  const double e = __builtin_fma(-b, r, 1.0);
-  return __builtin_fma(r, __builtin_fma(e, e, e), r);        // r (1 + e + e^2)
 }
 
 enum { kReadyYe = 0, kBail = 1, kReadySc = 2, kFwd = 3, kProg = 4 };  // ctl[] indices; prog[w] = ctl[kProg+w]
@@ -573,25 +539,7 @@ bool pipeline_supported(int M, long R) {
 
 hipError_t launch_pipeline(const PipeArgs& a, hipStream_t s) {
   if (!pipeline_supported(a.M, a.R) || a.P <= 0) return hipErrorInvalidValue;
-  switch ((a.M + 2 * PL - 1) / (2 * PL)) {
-    case 1: return pipe_launch<1>(a, s);
-    case 2: return pipe_launch<2>(a, s);
-    case 3: return pipe_launch<3>(a, s);
-    case 4: return pipe_launch<4>(a, s);
-    case 5: return pipe_launch<5>(a, s);
-    case 6: return pipe_launch<6>(a, s);
-    case 7: return pipe_launch<7>(a, s);
-    case 8: return pipe_launch<8>(a, s);
-    case 9: return pipe_launch<9>(a, s);
-    case 10: return pipe_launch<10>(a, s);
-    case 11: return pipe_launch<11>(a, s);
-    case 12: return pipe_launch<12>(a, s);
-    case 13: return pipe_launch<13>(a, s);
-    case 14: return pipe_launch<14>(a, s);
-    case 15: return pipe_launch<15>(a, s);
-    case 16: return pipe_launch<16>(a, s);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_width((a.M + 2 * PL - 1) / (2 * PL), WidthRange<1, 16>{}, [&](auto nc) { return pipe_launch<nc>(a, s); });
 }
 
 hipError_t launch_fill_u64(unsigned long long* p, size_t n, unsigned long long v, hipStream_t s) {

@@ -42,13 +42,11 @@
 
 #include "efa_device.h"
 #include "efa_internal.h"
+#include "efa_pipe.h"
 #include "efa_rows.h"
 
 namespace efa {
 namespace {
-
-typedef unsigned long long u64;
-typedef double v4f64 __attribute__((ext_vector_type(4)));
 
 constexpr int kVW = 4;        // vector waves (quad per row, one per SIMD)
 constexpr int kGT = 512;      // threads: 4 vector + pivot + 2 G waves + loader
@@ -90,33 +88,6 @@ constexpr int kEarlyNone = EFA_EARLY, kEarlyGC = EFA_EARLY_GC;
 static_assert(kEarlyNone >= 0 && kEarlyNone < kBand && kEarlyGC >= 0 && kEarlyGC < kBand, "early hand-over");
 constexpr int kScStride = 4;  // doubles per ob: rden, beta (latched by the pivot wave), innov, active (added by the forwarder): the record's scalars
 
-__device__ __forceinline__ u64 g_traj_load(const u64* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void g_traj_store(u64* p, double v) {
-  __hip_atomic_store(p, (u64)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ int g_ctl_lane(const int* p) {
-  const int v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  asm volatile("" ::: "memory");
-  return v;
-}
-__device__ __forceinline__ int g_ctl(const int* p) { return __builtin_amdgcn_readfirstlane(g_ctl_lane(p)); }
-__device__ __forceinline__ void g_ctl_set(int* p, int v) {
-  asm volatile("" ::: "memory");
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ double g_rsq(double a) {  // see efa_pipeline.hip: one Newton step suffices
-  const double q = __builtin_amdgcn_rsq(a);
-  const double e = __builtin_fma(-a * q, q, 1.0);
-  const double p = __builtin_fma(0.375, e, 0.5);
-  return __builtin_fma(q * e, p, q);
-}
-__device__ __forceinline__ double g_rcp(double b) {
-  const double r = __builtin_amdgcn_rcp(b);
-  const double e = __builtin_fma(-b, r, 1.0);
-  return __builtin_fma(r, __builtin_fma(e, e, e), r);
-}
 // The gain chain of one observation from its obs-space variance G_kk / M and error variance (ensrf.py:91, :119, :135):
 //   kdenom -> q0 = rsq(kdenom) -> { Newton step of q  ||  beta0 = 1/(1 + sqrt(err) q0) } -> rden = 1/kdenom, beta.
 // The pivot wave (on the serial chain) and the forwarder wave (for the records and diagnostics) both call it on the same
@@ -151,12 +122,6 @@ __device__ __forceinline__ double gain_c(double Gkk, double invM, double errk, d
   const double eu = __builtin_fma(-u, c0, 1.0);
   return __builtin_fma(c0, __builtin_fma(eu, eu, eu), c0) * rM1;
 }
-__device__ __forceinline__ double rl(double v, int lane) {  // value held by `lane` (wave-uniform index)
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-  return __hiloint2double(hi, lo);
-}
-
 
 #ifndef EFA_DEFER_GRAM
 #define EFA_DEFER_GRAM 1
@@ -264,16 +229,16 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
   auto give_up = [&]() {
     __hip_atomic_store(a.status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(a.status + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    g_ctl_set(&ctl[cBail], 1);
+    ctl_store(&ctl[cBail], 1);
   };
   // wait until *word > thr; false if the kernel is being abandoned
   auto wait_gt = [&](const int* word, int thr, bool doze) {
-    while (g_ctl(word) <= thr) {
+    while (ctl_load(word) <= thr) {
       if ((++polls & 15) == 0) {
-        if (g_ctl(&ctl[cBail]) != 0) return false;
+        if (ctl_load(&ctl[cBail]) != 0) return false;
         budget -= 16;
         if (budget <= 0 || EFA_TIMED_OUT()) {
-          EFA_PS(if (a.dbg != nullptr && lane == 0) { u64* d = a.dbg + (size_t)(32 + wave) * 8; d[0] = 1000 + (u64)(word - ctl); d[1] = (u64)thr; d[2] = (u64)g_ctl(word); d[3] = (u64)own0; })
+          EFA_PS(if (a.dbg != nullptr && lane == 0) { u64* d = a.dbg + (size_t)(32 + wave) * 8; d[0] = 1000 + (u64)(word - ctl); d[1] = (u64)thr; d[2] = (u64)ctl_load(word); d[3] = (u64)own0; })
           give_up();
           return false;
         }
@@ -291,7 +256,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
       const int lo = __builtin_amdgcn_readfirstlane((int)(v & 0xffffffffull)), hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
       if (lo > thr && hi > thr) return true;
       if ((++polls & 15) == 0) {
-        if (g_ctl(&ctl[cBail]) != 0) return false;
+        if (ctl_load(&ctl[cBail]) != 0) return false;
         budget -= 16;
         if (budget <= 0 || EFA_TIMED_OUT()) {
           give_up();
@@ -302,7 +267,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
   };
   // least-advanced consumer of the ye ring: the 4 vector waves and the forwarder
   auto min_prog = [&]() {
-    int mn = g_ctl_lane(&ctl[cProg + (lane & 3)]);  // (the forwarder reads the ring no more: the four vector waves are its only consumers)
+    int mn = ctl_load_lane(&ctl[cProg + (lane & 3)]);  // (the forwarder reads the ring no more: the four vector waves are its only consumers)
     mn = min(mn, __builtin_amdgcn_mov_dpp(mn, 0xB1, 0xF, 0xF, true));
     mn = min(mn, __builtin_amdgcn_mov_dpp(mn, 0x4E, 0xF, 0xF, true));
     return __builtin_amdgcn_readfirstlane(mn);
@@ -378,7 +343,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
 #pragma unroll
           for (int e = 0; e < EPL; ++e) {
             const int idx = lane + 64 * e;
-            v[d][e] = g_traj_load(rec + (idx < TS ? idx : TS - 1));
+            v[d][e] = traj_load(rec + (idx < TS ? idx : TS - 1));
           }
         }
         int cnt = 0;
@@ -401,7 +366,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
               failed = true;
               break;
             }
-            const u64 w = g_traj_load(probe);
+            const u64 w = traj_load(probe);
             const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(w & 0xffffffffull));
             const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(w >> 32));
             if ((((u64)hi << 32) | lo) != kTrajSentinel) break;
@@ -413,11 +378,11 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
         const long need = next + cnt - 1 - kRingG;  // slots are recycled only once every vector wave consumed them
         if (need >= 0) {
           for (;;) {
-            int mn = g_ctl_lane(&ctl[cProg + (lane & 3)]);
+            int mn = ctl_load_lane(&ctl[cProg + (lane & 3)]);
             mn = min(mn, __builtin_amdgcn_mov_dpp(mn, 0xB1, 0xF, 0xF, true));
             mn = min(mn, __builtin_amdgcn_mov_dpp(mn, 0x4E, 0xF, 0xF, true));
             if (__builtin_amdgcn_readfirstlane(mn) >= (int)need) break;
-            if (--budget <= 0 || g_ctl(&ctl[cBail]) != 0 || ((budget & 15) == 0 && EFA_TIMED_OUT())) {
+            if (--budget <= 0 || ctl_load(&ctl[cBail]) != 0 || ((budget & 15) == 0 && EFA_TIMED_OUT())) {
               failed = true;
               break;
             }
@@ -437,7 +402,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
           }
         }
         next += cnt;
-        if (lane == 0) g_ctl_set(&ctl[cReady], (int)next);
+        if (lane == 0) ctl_store(&ctl[cReady], (int)next);
       }
     };
     follow(0, (own0 < P) ? own0 : P);
@@ -515,8 +480,8 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
           if (s >= s1) break;  // wave-uniform
           const int st = kBand * b + s;
           const double dv = val_l - xmv;                                       // :85 in the ob's own lane
-          const double innov = rl(dv, st);
-          const double rden_a = rl(rd_a, st);
+          const double innov = readlane_f64(dv, st);
+          const double rden_a = readlane_f64(rd_a, st);
           double kc = gk4[s].x * rM1;                                          // :95
           if (GC) kc = tw4[s] * kc;                                            // :115
           const double km = kc * rden_a;                                       // :119
@@ -529,16 +494,16 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
         // (:95, :115, :119, :130, :136 folded once per ob); then innov and the assimilate flag
         if (mine && f_ob) {
           const double cf = my_asm ? (l_be * l_rd) * rM1 : 0.0, mf = (l_rd * rM1) * l_innov;
-          g_traj_store(rec_l + 0, cf);
-          g_traj_store(rec_l + 1, mf);
-          g_traj_store(rec_l + 2, l_innov);
+          traj_store(rec_l + 0, cf);
+          traj_store(rec_l + 1, mf);
+          traj_store(rec_l + 2, l_innov);
           const double actv = my_asm ? 1.0 : 0.0;
 #pragma unroll
-          for (int sj = 3; sj < TS - PAD; ++sj) g_traj_store(rec_l + sj, actv);  // (the followers wait for every word of a record)
+          for (int sj = 3; sj < TS - PAD; ++sj) traj_store(rec_l + sj, actv);  // (the followers wait for every word of a record)
         }
       }
       // (not when the launch is being abandoned anyway: then this block may have run on rows that were never parked)
-      if (!failed && __ballot(bad) != 0ull && g_ctl(&ctl[cBail]) == 0 &&
+      if (!failed && __ballot(bad) != 0ull && ctl_load(&ctl[cBail]) == 0 &&
           __hip_atomic_load(a.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {  // abandon the launch (status[2]: the host re-runs
         if (lane == 0) {                                                                  // Phase A with the vector-chain kernel)
           give_up();
@@ -669,8 +634,8 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
             double gi[kBand], kbi[kBand];
 #pragma unroll
             for (int s2 = 0; s2 < kBand; ++s2) {
-              gi[s2] = rl(gprev[o], r0 + s2);
-              kbi[s2] = GC ? rl(kbprev[o], r0 + s2) : 0.0;
+              gi[s2] = readlane_f64(gprev[o], r0 + s2);
+              kbi[s2] = GC ? readlane_f64(kbprev[o], r0 + s2) : 0.0;
             }
 #pragma unroll
             for (int s2 = 0; s2 < kBand; ++s2) {
@@ -707,7 +672,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
             if (FULL || s < s1) {  // wave-uniform
               const int kk = r0 + s;
               const double g = band[s];
-              const double Gkk = rl(g, kk);
+              const double Gkk = readlane_f64(g, kk);
               double cc = gain_c(Gkk, invM, ec[s][0], ec[s][1], rM1);       // beta / ((M-1) kdenom)  (:95, :119, :135, :136)
               cc = (ec[s][2] != 0.0) ? cc : 0.0;                            // :74: an ob that is not assimilated changes nothing
               double kb = cc * g;                                           // the rows' gains (:136)
@@ -720,8 +685,8 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
               double gi[kBand], kbi[kBand];                                  // (all the scalars first: see the note on wait states above)
 #pragma unroll
               for (int s2 = s + 1; s2 < kBand; ++s2) {
-                gi[s2] = rl(g, r0 + s2);                                    // G_k,i of row i = r0 + s2
-                kbi[s2] = GC ? rl(kb, r0 + s2) : 0.0;                       // GC: kb_j = w_kj c G_kj is no longer a multiple of G_kj
+                gi[s2] = readlane_f64(g, r0 + s2);                                    // G_k,i of row i = r0 + s2
+                kbi[s2] = GC ? readlane_f64(kb, r0 + s2) : 0.0;                       // GC: kb_j = w_kj c G_kj is no longer a multiple of G_kj
               }
 #pragma unroll
               for (int s2 = s + 1; s2 < kBand; ++s2) {
@@ -735,7 +700,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
                 }
               }
               recb[s * kRowsWG] = make_double2(g, kb);         // the step's record: {G_kj, kb_j} per row
-              if (s == kEarly - 1 && lane == 0) g_ctl_set(&ctl[cHalf], 2 * b + 1);  // the G waves may start on the next band's rows
+              if (s == kEarly - 1 && lane == 0) ctl_store(&ctl[cHalf], 2 * b + 1);  // the G waves may start on the next band's rows
               EFA_PS(if (s == kEarly - 1 && a.dbg != nullptr && lane == 0 && own0 + 64 + b < P) a.dbg[(size_t)(own0 + 64 + b) * 8 + 0] = EFA_PS_NOW();)
               if (s >= kEarly) {
                 gprev[s - kEarly] = g;
@@ -758,8 +723,8 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
         else run_steps(std::false_type());
         EFA_PS(EFA_PIN_BAND(band); const u64 ps_s1 = EFA_PS_NOW(); ps_st += ps_s1 - ps_s0;)
         if (lane == 0) {
-          g_ctl_set(&ctl[cSReady], r0 + s1);
-          g_ctl_set(&ctl[cLinv], b + 1);
+          ctl_store(&ctl[cSReady], r0 + s1);
+          ctl_store(&ctl[cLinv], b + 1);
         }
         EFA_HO_IF((b & 3) == 3, 14, b >> 2);  // the pivot is through with bands 3, 7, 11, 15
         EFA_PS(ps_en += EFA_PS_NOW() - ps_s1;)
@@ -815,7 +780,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
         const double Gkk = dg.x;
         double gam = 0.0;
         if (!GC) {
-          const double cc = (Gkk > 0.0) ? dg.y * g_rcp(Gkk) : 0.0;  // kb_k = 0 for an ob that is not assimilated
+          const double cc = (Gkk > 0.0) ? dg.y * fast_rcp(Gkk) : 0.0;  // kb_k = 0 for an ob that is not assimilated
           gam = cc * __builtin_fma(-cc, Gkk, 2.0);
         }
 #pragma unroll
@@ -876,7 +841,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
         const int r0 = kBand * b;
         const int I2 = (r0 + 2 * kBand) >> 4;  // tile row of band b + 2
         if (!wait_gt(&ctl[cSReady], r0 + kBand - 1, false)) break;
-        if (DEFER && !rows_ready && (I2 > 0 || g_ctl(&ctl[cDef]) >= 12)) {
+        if (DEFER && !rows_ready && (I2 > 0 || ctl_load(&ctl[cDef]) >= 12)) {
           // tile rows 1..3 of G have arrived (or are needed now): take them, and give them the bands they owe
           if (!wait_gt(&ctl[cDef], 11, false)) break;
           load_acc(1, 4);
@@ -896,7 +861,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
           case 2: update_row(std::integral_constant<int, 2>(), r0, 0, kBand); hand_over(std::integral_constant<int, 2>(), r0 + 2 * kBand); break;
           default: update_row(std::integral_constant<int, 3>(), r0, 0, kBand); hand_over(std::integral_constant<int, 3>(), r0 + 2 * kBand); break;
         }
-        if (lane == 0) g_ctl_set(&ctl[cBandH + h], b + 2);
+        if (lane == 0) ctl_store(&ctl[cBandH + h], b + 2);
         if (rows_ready) {  // (else: owed, see above)
           if (I2 < 1) update_row(std::integral_constant<int, 1>(), r0, 0, kBand);
           if (I2 < 2) update_row(std::integral_constant<int, 2>(), r0, 0, kBand);
@@ -930,7 +895,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
         case 2: update_row(std::integral_constant<int, 2>(), r0, 0, kEarly); hand_over(std::integral_constant<int, 2>(), r0 + kBand); break;
         default: update_row(std::integral_constant<int, 3>(), r0, 0, kEarly); hand_over(std::integral_constant<int, 3>(), r0 + kBand); break;
       }
-      if (lane == 0) g_ctl_set(&ctl[cBandH + h], b + 1);
+      if (lane == 0) ctl_store(&ctl[cBandH + h], b + 1);
       EFA_PS(const u64 ps_c = EFA_PS_NOW(); ps_p1 += ps_c - ps_b;
              if (a.dbg != nullptr && lane == 0 && h == 0 && own0 + 64 + b < P) a.dbg[(size_t)(own0 + 64 + b) * 8 + 4] = ps_c;)
       // while the pivot runs the band's other steps: the trailing update owed from the previous band
@@ -1052,11 +1017,11 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
             {
               const int need = (b >= kRingG / kBand) ? (int)(own0 + kBand * (b - kRingG / kBand) + kBand - 1) : -0x7fffffff;
               for (;;) {
-                const int fl = g_ctl_lane(&ctl[cLinv]);
+                const int fl = ctl_load_lane(&ctl[cLinv]);
                 const int mp = min_prog();
                 if (__builtin_amdgcn_readfirstlane(fl) > b && mp >= need) break;
                 if ((++polls & 15) == 0) {
-                  if (g_ctl(&ctl[cBail]) != 0) {
+                  if (ctl_load(&ctl[cBail]) != 0) {
                     bailed = true;
                     break;
                   }
@@ -1087,14 +1052,14 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
               if (lr < s1) {
 #pragma unroll
                 for (int J = 0; J < NJ; ++J)
-                  if (16 * J + lc < PAD) g_traj_store(grec + 16 * J + lc, ye0[J]);
+                  if (16 * J + lc < PAD) traj_store(grec + 16 * J + lc, ye0[J]);
               }
             }
             EFA_HO_IF(b == nbands - 1, 8, 6);  // T1b: the ye rows of the block's last band are on their way to global memory
 #pragma unroll
             for (int J = 0; J < NJ; ++J)
               if (16 * J + lc < PAD) ring[(size_t)((own0 + r0 + lr) % kRingG) * TSR + 16 * J + lc] = ye0[J];
-            if (lane == 0) g_ctl_set(&ctl[cYe], 4 * (b + 1));  // the other vector waves may read the band
+            if (lane == 0) ctl_store(&ctl[cYe], 4 * (b + 1));  // the other vector waves may read the band
           } else {
             if (!wait_gt(&ctl[cYe], 4 * (b + 1) - 1, true)) {
               bailed = true;
@@ -1115,7 +1080,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
               xt[J] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, xt[J], 0, 0, 0);
             }
           }
-          if (lane == 0) g_ctl_set(&ctl[cProg + wave], (int)(own0 + r0 + s1 - 1));  // ring slots up to here consumed
+          if (lane == 0) ctl_store(&ctl[cProg + wave], (int)(own0 + r0 + s1 - 1));  // ring slots up to here consumed
           EFA_HO_IF((b & 3) == 3, 10 + wave, b >> 2);  // this vector wave is through with bands 3, 7, 11, 15
         }
       }
@@ -1154,7 +1119,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
       bailed = true;
       break;
     }
-    long avail = g_ctl(&ctl[cReady]);  // (read again: reusing the value the wait saw measured slower -- more has usually arrived by now)
+    long avail = ctl_load(&ctl[cReady]);  // (read again: reusing the value the wait saw measured slower -- more has usually arrived by now)
     const long lim = (leads && k < own0) ? own0 : P;
     if (avail > lim) avail = lim;
     if (avail > k + kRingG / 2) avail = k + kRingG / 2;  // progress is reported at least every half ring (slot recycling)
@@ -1192,10 +1157,10 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
       apply(yb2, b01, wb);
       ++k;
     }
-    if (lane == 0) g_ctl_set(&ctl[cProg + wave], (int)(k - 1));
+    if (lane == 0) ctl_store(&ctl[cProg + wave], (int)(k - 1));
   }
   for (; barriers_left > 0; --barriers_left) __syncthreads();
-  if (bailed || g_ctl(&ctl[cBail]) != 0) return;  // nothing written back: the host re-runs Phase A
+  if (bailed || ctl_load(&ctl[cBail]) != 0) return;  // nothing written back: the host re-runs Phase A
   if (live) {
     if (vec) store_row<PLg, NC, true>(a.Yp + (size_t)row * M, M, j, x);
     else store_row<PLg, NC, false>(a.Yp + (size_t)row * M, M, j, x);
@@ -1242,25 +1207,7 @@ bool pipeline_band_supported(int M, long R, int loc_mode) {
 
 hipError_t launch_pipeline_band(const PipeArgs& a, hipStream_t s) {
   if (!pipeline_band_supported(a.M, a.R, a.loc_mode) || a.P <= 0) return hipErrorInvalidValue;
-  switch ((a.M + 2 * PLg - 1) / (2 * PLg)) {
-    case 1: return band_launch<1>(a, s);
-    case 2: return band_launch<2>(a, s);
-    case 3: return band_launch<3>(a, s);
-    case 4: return band_launch<4>(a, s);
-    case 5: return band_launch<5>(a, s);
-    case 6: return band_launch<6>(a, s);
-    case 7: return band_launch<7>(a, s);
-    case 8: return band_launch<8>(a, s);
-    case 9: return band_launch<9>(a, s);
-    case 10: return band_launch<10>(a, s);
-    case 11: return band_launch<11>(a, s);
-    case 12: return band_launch<12>(a, s);
-    case 13: return band_launch<13>(a, s);
-    case 14: return band_launch<14>(a, s);
-    case 15: return band_launch<15>(a, s);
-    case 16: return band_launch<16>(a, s);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_width((a.M + 2 * PLg - 1) / (2 * PLg), WidthRange<1, 16>{}, [&](auto nc) { return band_launch<nc>(a, s); });
 }
 
 }  // namespace efa

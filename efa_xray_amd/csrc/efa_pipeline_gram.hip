@@ -31,13 +31,11 @@
 
 #include "efa_device.h"
 #include "efa_internal.h"
+#include "efa_pipe.h"
 #include "efa_rows.h"
 
 namespace efa {
 namespace {
-
-typedef unsigned long long u64;
-typedef double v4f64 __attribute__((ext_vector_type(4)));
 
 constexpr int kVW = 4;        // vector waves (quad per row, one per SIMD)
 constexpr int kGT = 512;      // threads: 4 vector + pivot + 2 helpers + loader
@@ -49,39 +47,6 @@ static_assert(PLg == 4 && kRowsWG == 64, "layout assumptions of the Gram kernel"
 
 enum { cReady = 0, cBail = 1, cSReady = 2, cFwd = 3, cProg = 4, cHProg = 8 };
 constexpr int kScStride = 8;  // doubles per step in the pivot's scalar records
-
-__device__ __forceinline__ u64 g_traj_load(const u64* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void g_traj_store(u64* p, double v) {
-  __hip_atomic_store(p, (u64)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ int g_ctl_lane(const int* p) {
-  const int v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  asm volatile("" ::: "memory");
-  return v;
-}
-__device__ __forceinline__ int g_ctl(const int* p) { return __builtin_amdgcn_readfirstlane(g_ctl_lane(p)); }
-__device__ __forceinline__ void g_ctl_set(int* p, int v) {
-  asm volatile("" ::: "memory");
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ double g_rsq(double a) {  // see efa_pipeline.hip: one Newton step suffices
-  const double q = __builtin_amdgcn_rsq(a);
-  const double e = __builtin_fma(-a * q, q, 1.0);
-  const double p = __builtin_fma(0.375, e, 0.5);
-  return __builtin_fma(q * e, p, q);
-}
-__device__ __forceinline__ double g_rcp(double b) {
-  const double r = __builtin_amdgcn_rcp(b);
-  const double e = __builtin_fma(-b, r, 1.0);
-  return __builtin_fma(r, __builtin_fma(e, e, e), r);
-}
-__device__ __forceinline__ double rl(double v, int lane) {  // value held by `lane` (wave-uniform index)
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-  return __hiloint2double(hi, lo);
-}
 
 template <int NC>
 struct GramShape {
@@ -169,13 +134,13 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
   auto give_up = [&]() {
     __hip_atomic_store(a.status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(a.status + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    g_ctl_set(&ctl[cBail], 1);
+    ctl_store(&ctl[cBail], 1);
   };
   // wait until *word > thr; false if the kernel is being abandoned
   auto wait_gt = [&](const int* word, int thr, bool doze) {
-    while (g_ctl(word) <= thr) {
+    while (ctl_load(word) <= thr) {
       if ((++polls & 15) == 0) {
-        if (g_ctl(&ctl[cBail]) != 0) return false;
+        if (ctl_load(&ctl[cBail]) != 0) return false;
         budget -= 16;
         if (budget <= 0 || EFA_TIMED_OUT()) {
           give_up();
@@ -190,10 +155,10 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
 
   auto wait2_gt = [&](const int* wa, int ta, const int* wb, int tb, bool doze) {  // both words in one LDS round trip
     for (;;) {
-      const int va = g_ctl_lane(wa), vb = g_ctl_lane(wb);
+      const int va = ctl_load_lane(wa), vb = ctl_load_lane(wb);
       if (__builtin_amdgcn_readfirstlane(va) > ta && __builtin_amdgcn_readfirstlane(vb) > tb) return true;
       if ((++polls & 15) == 0) {
-        if (g_ctl(&ctl[cBail]) != 0) return false;
+        if (ctl_load(&ctl[cBail]) != 0) return false;
         budget -= 16;
         if (budget <= 0 || EFA_TIMED_OUT()) {
           give_up();
@@ -249,7 +214,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
 #pragma unroll
           for (int e = 0; e < EPL; ++e) {
             const int idx = lane + 64 * e;
-            v[d][e] = g_traj_load(rec + (idx < TS ? idx : TS - 1));
+            v[d][e] = traj_load(rec + (idx < TS ? idx : TS - 1));
           }
         }
         int cnt = 0;
@@ -270,11 +235,11 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
         const long need = next + cnt - 1 - kRingG;  // slots are recycled only once every vector wave consumed them
         if (need >= 0) {
           for (;;) {
-            int mn = g_ctl_lane(&ctl[cProg + (lane & 3)]);
+            int mn = ctl_load_lane(&ctl[cProg + (lane & 3)]);
             mn = min(mn, __builtin_amdgcn_mov_dpp(mn, 0xB1, 0xF, 0xF, true));
             mn = min(mn, __builtin_amdgcn_mov_dpp(mn, 0x4E, 0xF, 0xF, true));
             if (__builtin_amdgcn_readfirstlane(mn) >= (int)need) break;
-            if (--budget <= 0 || g_ctl(&ctl[cBail]) != 0 || ((budget & 15) == 0 && EFA_TIMED_OUT())) {
+            if (--budget <= 0 || ctl_load(&ctl[cBail]) != 0 || ((budget & 15) == 0 && EFA_TIMED_OUT())) {
               failed = true;
               break;
             }
@@ -293,7 +258,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
           }
         }
         next += cnt;
-        if (lane == 0) g_ctl_set(&ctl[cReady], (int)next);
+        if (lane == 0) ctl_store(&ctl[cReady], (int)next);
       }
     };
     follow(0, (own0 < P) ? own0 : P);
@@ -323,9 +288,9 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
         for (int e = 0; e < EPL; ++e) {
           const int idx = lane + 64 * e;  // record = ye, then 8 scalars of which the followers read [2..5]
           const int si = idx - PAD - 2;
-          if (idx < TS) g_traj_store(rec + idx, idx < PAD ? slot[idx] : ((si >= 0 && si < 4) ? sc[si] : 0.0));
+          if (idx < TS) traj_store(rec + idx, idx < PAD ? slot[idx] : ((si >= 0 && si < 4) ? sc[si] : 0.0));
         }
-        if (lane == 0) g_ctl_set(&ctl[cFwd], (int)f);
+        if (lane == 0) ctl_store(&ctl[cFwd], (int)f);
         // the ob's diagnostics and sweep coefficients, derived from the pivot's record (the pivot wave itself
         // keeps nothing per ob: every instruction there is on the chain).  The same operations in the same
         // order as the pivot's own lane k: km = kc rden with kc = G_kk/(M-1) (x the taper of an ob with itself,
@@ -413,12 +378,12 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
       auto wait_row = [&](int kk, double& r2) {
         const int* flag = &ctl[cHProg + (kk & 1)];
         for (;;) {
-          const int f = g_ctl_lane(flag);
+          const int f = ctl_load_lane(flag);
           r2 = G_s[(kk + 2) * kRowsWG + lane];
           if (__builtin_amdgcn_readfirstlane(f) >= kk + 2) return true;
           if ((++polls & 15) == 0) {
             budget -= 16;
-            if (g_ctl(&ctl[cBail]) != 0) return false;
+            if (ctl_load(&ctl[cBail]) != 0) return false;
             if (budget <= 0 || EFA_TIMED_OUT()) {
               if (lane == 0) give_up();
               return false;
@@ -443,14 +408,14 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
         int f_early = 0;
         double r2 = 0.0;
         if (has2) {
-          f_early = poll ? g_ctl_lane(&ctl[cHProg + (kk & 1)]) : 0;
+          f_early = poll ? ctl_load_lane(&ctl[cHProg + (kk & 1)]) : 0;
           r2 = G_s[(kk + 2) * kRowsWG + lane];
         }
         const double twk = GC ? tw_s[kk * kRowsWG + lane] : 1.0;       // consumed after the gain chain
         const bool act = ((asm_mask >> kk) & 1) != 0;
         if (!EFA_EXP(0x70)) bad |= __ballot(!(g > thr)) & (1ull << kk);
-        const double Gkk = rl(g, kk), muk = rl(mu, kk), xmk = rl(xmv, kk);
-        const double errk = rl(err_l, kk), sqk = rl(sq_l, kk), valk = rl(val_l, kk);
+        const double Gkk = readlane_f64(g, kk), muk = readlane_f64(mu, kk), xmk = readlane_f64(xmv, kk);
+        const double errk = readlane_f64(err_l, kk), sqk = readlane_f64(sq_l, kk), valk = readlane_f64(val_l, kk);
         const double mu2 = muk * muk;
         const double kdenom = __builtin_fma(Gkk, invM, errk - mu2);   // var + err  (:69, :91)
         const double q0 = __builtin_amdgcn_rsq(kdenom);
@@ -477,7 +442,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
           // g1 = row kk+1 through step kk-1; row kk+2 through step kk-1 comes from its helper (handed
           // over through G_s during the helper's step kk-1)
           const double t = __builtin_fma(-kb, Gkk, g);
-          const double gi = rl(g, kk + 1), ai = rl(kb, kk + 1);
+          const double gi = readlane_f64(g, kk + 1), ai = readlane_f64(kb, kk + 1);
           const double gnew = __builtin_fma(-ai, t, __builtin_fma(-kb, gi, g1));
           if (has2) {
             if (__builtin_expect(poll && !EFA_EXP(2048) && __builtin_amdgcn_readfirstlane(f_early) < kk + 2, 0)) {
@@ -486,7 +451,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
 #endif
               ok = wait_row(kk, r2);
             }
-            const double gi2 = rl(g, kk + 2), ai2 = rl(kb, kk + 2);
+            const double gi2 = readlane_f64(g, kk + 2), ai2 = readlane_f64(kb, kk + 2);
             g1 = __builtin_fma(-ai2, t, __builtin_fma(-kb, gi2, r2));
           }
           g = gnew;
@@ -500,7 +465,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
           sc[0] = make_double2(innov, rden);
           sc[1] = make_double2(beta, act ? 1.0 : 0.0);
           sc[2] = make_double2(xmk, __builtin_fma(Gkk, invM, -mu2));   // prior mean (:66), np.var ddof = 0 (:69, :70)
-          g_ctl_set(&ctl[cSReady], kk + 1);
+          ctl_store(&ctl[cSReady], kk + 1);
         }
         EFA_GSTAMP(lane == 0, own0 + kk, 1);
         return ok;
@@ -583,7 +548,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
 #endif
       const double2* rec = s_gk + kk * kRowsWG;
       const double2 own = rec[lane];
-      const double Gkk = rl(own.x, kk);
+      const double Gkk = readlane_f64(own.x, kk);
       const double kb = own.y;
       const double t = own.x - kb * Gkk;
       EFA_GSTAMP(lane == 0 && h == ((kk + 1) & 1) && !(a.debug & 8), own0 + kk, 5);
@@ -611,7 +576,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
         cur = __builtin_fma(-kb, gu.x, cur);
         cur = __builtin_fma(-gu.y, t, cur);
         G_s[hr * kRowsWG + lane] = cur;
-        if (lane == 0) g_ctl_set(&ctl[cHProg + h], hr);
+        if (lane == 0) ctl_store(&ctl[cHProg + h], hr);
         EFA_GSTAMP(lane == 0 && !(a.debug & 8), own0 + kk, 6);
       }
       // rows behind the pivot may be updated too (their registers are dead)
@@ -656,7 +621,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
   int barriers_left = leads ? 3 : 0;
   bool bailed = false;
   auto min_prog = [&]() {  // least-advanced consumer of the ring: the 4 vector waves and the forwarder
-    int mn = min(g_ctl_lane(&ctl[cProg + j]), g_ctl_lane(&ctl[cFwd]));
+    int mn = min(ctl_load_lane(&ctl[cProg + j]), ctl_load_lane(&ctl[cFwd]));
     mn = min(mn, __builtin_amdgcn_mov_dpp(mn, 0xB1, 0xF, 0xF, true));
     mn = min(mn, __builtin_amdgcn_mov_dpp(mn, 0x4E, 0xF, 0xF, true));
     return __builtin_amdgcn_readfirstlane(mn);
@@ -711,7 +676,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
 #undef EFA_PUB_CASE
           }
         }
-        if (lane == 0) g_ctl_set(&ctl[cReady], (int)(own0 + r + 1));
+        if (lane == 0) ctl_store(&ctl[cReady], (int)(own0 + r + 1));
       };
       if (wave == 0) publish_row(0);
       for (int st = 0; st < nb; ++st) {
@@ -747,7 +712,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
           if (mine) {  // the chain: publish the next ye
             if ((nu & 3) == 0) {  // recycling guard, amortised over four records
               while (min_prog() < (int)(kg + 1 + 3 - kRingG)) {
-                if (g_ctl(&ctl[cBail]) != 0 || --budget <= 0 || ((budget & 15) == 0 && EFA_TIMED_OUT())) {
+                if (ctl_load(&ctl[cBail]) != 0 || --budget <= 0 || ((budget & 15) == 0 && EFA_TIMED_OUT())) {
                   bailed = true;
                   break;
                 }
@@ -759,7 +724,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
           }
         }
         if (batch && EFA_EXP(32)) {
-          if (lane == 0) g_ctl_set(&ctl[cProg + wave], (int)kg);
+          if (lane == 0) ctl_store(&ctl[cProg + wave], (int)kg);
         } else if (batch) {
           // rank-4 update with the steps 4 tp - 1 .. 4 tp + 2 (those that exist), minus what the window did
           const int tp = (st + 1) >> 2;
@@ -773,7 +738,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
           const double* bs = ring + (size_t)((own0 + sc) % kRingG) * TS;
 #pragma unroll
           for (int J = 0; J < NJ; ++J) xt[J] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bs[16 * J + lc], xt[J], 0, 0, 0);
-          if (lane == 0) g_ctl_set(&ctl[cProg + wave], (int)kg);       // ring slots up to kg consumed
+          if (lane == 0) ctl_store(&ctl[cProg + wave], (int)kg);       // ring slots up to kg consumed
         }
       }
       __syncthreads();  // B3: every wave is done with the pivot's records; the tile region is free again
@@ -806,7 +771,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
     lds_read_row<PLg, NC>(slot, j, y);
     const double2 s23 = *reinterpret_cast<const double2*>(slot + PAD + 2);  // innov, rden
     const double2 s45 = *reinterpret_cast<const double2*>(slot + PAD + 4);  // beta, active
-    if (lane == 0) g_ctl_set(&ctl[cProg + wave], (int)k);
+    if (lane == 0) ctl_store(&ctl[cProg + wave], (int)k);
     const double w = wq0;
     wq0 = wq1;
     if (use_tw) wq1 = a.tw[(size_t)((k + 2 < P) ? k + 2 : P - 1) * R + row];
@@ -827,7 +792,7 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
     ++k;
   }
   for (; barriers_left > 0; --barriers_left) __syncthreads();
-  if (bailed || g_ctl(&ctl[cBail]) != 0) return;  // nothing written back: the host re-runs Phase A
+  if (bailed || ctl_load(&ctl[cBail]) != 0) return;  // nothing written back: the host re-runs Phase A
   if (live) {
     if (vec) store_row<PLg, NC, true>(a.Yp + (size_t)row * M, M, j, x);
     else store_row<PLg, NC, false>(a.Yp + (size_t)row * M, M, j, x);
@@ -865,25 +830,7 @@ bool pipeline_gram_supported(int M, long R, int loc_mode) {
 
 hipError_t launch_pipeline_gram(const PipeArgs& a, hipStream_t s) {
   if (!pipeline_gram_supported(a.M, a.R, a.loc_mode) || a.P <= 0) return hipErrorInvalidValue;
-  switch ((a.M + 2 * PLg - 1) / (2 * PLg)) {
-    case 1: return gram_launch<1>(a, s);
-    case 2: return gram_launch<2>(a, s);
-    case 3: return gram_launch<3>(a, s);
-    case 4: return gram_launch<4>(a, s);
-    case 5: return gram_launch<5>(a, s);
-    case 6: return gram_launch<6>(a, s);
-    case 7: return gram_launch<7>(a, s);
-    case 8: return gram_launch<8>(a, s);
-    case 9: return gram_launch<9>(a, s);
-    case 10: return gram_launch<10>(a, s);
-    case 11: return gram_launch<11>(a, s);
-    case 12: return gram_launch<12>(a, s);
-    case 13: return gram_launch<13>(a, s);
-    case 14: return gram_launch<14>(a, s);
-    case 15: return gram_launch<15>(a, s);
-    case 16: return gram_launch<16>(a, s);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_width((a.M + 2 * PLg - 1) / (2 * PLg), WidthRange<1, 16>{}, [&](auto nc) { return gram_launch<nc>(a, s); });
 }
 
 }  // namespace efa

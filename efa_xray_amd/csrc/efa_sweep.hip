@@ -333,9 +333,6 @@ hipError_t sweep_launch(const SweepArgs& a, bool vec, hipStream_t s) {
 }
 
 template <int NC>
-hipError_t sweep4(const SweepArgs& a, bool vec, hipStream_t s) { return sweep_launch<4, NC>(a, vec, s); }
-
-template <int NC>
 hipError_t diag_nc(const DiagArgs& a, bool vec, hipStream_t s) {
   const size_t lds = diag_lds_bytes(8 * NC, a.nb, a.loc_mode);
   if (lds > 64 * 1024) {
@@ -357,30 +354,6 @@ hipError_t diag_nc(const DiagArgs& a, bool vec, hipStream_t s) {
 
 }  // namespace
 
-#define EFA_NCH_SWITCH(FN, ...)                                  \
-  switch (nch) {                                                 \
-    case 1: return FN<1>(__VA_ARGS__);                           \
-    case 2: return FN<2>(__VA_ARGS__);                           \
-    case 3: return FN<3>(__VA_ARGS__);                           \
-    case 4: return FN<4>(__VA_ARGS__);                           \
-    case 5: return FN<5>(__VA_ARGS__);                           \
-    case 6: return FN<6>(__VA_ARGS__);                           \
-    case 7: return FN<7>(__VA_ARGS__);                           \
-    case 8: return FN<8>(__VA_ARGS__);                           \
-    case 9: return FN<9>(__VA_ARGS__);                           \
-    case 10: return FN<10>(__VA_ARGS__);                         \
-    case 11: return FN<11>(__VA_ARGS__);                         \
-    case 12: return FN<12>(__VA_ARGS__);                         \
-    case 13: return FN<13>(__VA_ARGS__);                         \
-    case 14: return FN<14>(__VA_ARGS__);                         \
-    case 15: return FN<15>(__VA_ARGS__);                         \
-    case 16: return FN<16>(__VA_ARGS__);                         \
-    case 20: return FN<20>(__VA_ARGS__);                         \
-    case 24: return FN<24>(__VA_ARGS__);                         \
-    case 32: return FN<32>(__VA_ARGS__);                         \
-    default: return hipErrorInvalidValue;                        \
-  }
-
 int sweep_slots(int M) {  // padded row length (doubles) of the quad layout's LDS image
   int nch = (M + 7) / 8;
   if (nch > 16) nch = (nch <= 20) ? 20 : (nch <= 24) ? 24 : 32;
@@ -395,15 +368,13 @@ hipError_t launch_sweep(const SweepArgs& a, hipStream_t s) {
   if (a.M < 2 || a.M > kMaxMembers || a.nb < 1 || a.nb > kMaxBatch) return hipErrorInvalidValue;
   if (a.nrows <= 0) return hipSuccess;
   const bool vec = (a.M % 2 == 0) && (a.ye_stride % 2 == 0) && aligned16(a.Xin) && aligned16(a.Xout) && aligned16(a.Ye);
-  const int nch = sweep_slots(a.M) / 8;
-  EFA_NCH_SWITCH(sweep4, a, vec, s)
+  return dispatch_width(sweep_slots(a.M) / 8, SweepChunks{}, [&](auto nc) { return sweep_launch<4, nc>(a, vec, s); });
 }
 
 hipError_t launch_diag(const DiagArgs& a, hipStream_t s) {
   if (a.M < 2 || a.M > kMaxMembers || a.nb < 1 || a.nb > kMaxBatch) return hipErrorInvalidValue;
   const bool vec = (a.M % 2 == 0) && aligned16(a.Yp) && aligned16(a.Ye_rec);
-  const int nch = sweep_slots(a.M) / 8;
-  EFA_NCH_SWITCH(diag_nc, a, vec, s)
+  return dispatch_width(sweep_slots(a.M) / 8, SweepChunks{}, [&](auto nc) { return diag_nc<nc>(a, vec, s); });
 }
 
 }  // namespace efa

@@ -676,26 +676,7 @@ hipError_t launch_transform_rtps(const TransformArgs& a, double alpha, hipStream
   if (!transform_rtps_supported(a.M) || !a.fused_members) return hipErrorInvalidValue;
   if ((reinterpret_cast<uintptr_t>(a.Xin) & 7u) != 0) return hipErrorInvalidValue;
   if (a.nrows <= 0) return hipSuccess;
-  switch ((a.M + 7) / 8) {
-    case 1: return transform_rtps_nu<1>(a, alpha, s);
-    case 2: return transform_rtps_nu<2>(a, alpha, s);
-    case 3: return transform_rtps_nu<3>(a, alpha, s);
-    case 4: return transform_rtps_nu<4>(a, alpha, s);
-    case 5: return transform_rtps_nu<5>(a, alpha, s);
-    case 6: return transform_rtps_nu<6>(a, alpha, s);
-    case 7: return transform_rtps_nu<7>(a, alpha, s);
-    case 8: return transform_rtps_nu<8>(a, alpha, s);
-    case 9: return transform_rtps_nu<9>(a, alpha, s);
-    case 10: return transform_rtps_nu<10>(a, alpha, s);
-    case 11: return transform_rtps_nu<11>(a, alpha, s);
-    case 12: return transform_rtps_nu<12>(a, alpha, s);
-    case 13: return transform_rtps_nu<13>(a, alpha, s);
-    case 14: return transform_rtps_nu<14>(a, alpha, s);
-    case 15: return transform_rtps_nu<15>(a, alpha, s);
-    case 16: return transform_rtps_nu<16>(a, alpha, s);
-    case 17: return transform_rtps_nu<17>(a, alpha, s);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_width((a.M + 7) / 8, WidthRange<1, 17>{}, [&](auto nu) { return transform_rtps_nu<nu>(a, alpha, s); });
 }
 
 hipError_t launch_transform(const TransformArgs& a, hipStream_t s) {
@@ -703,41 +684,8 @@ hipError_t launch_transform(const TransformArgs& a, hipStream_t s) {
   if ((reinterpret_cast<uintptr_t>(a.Xin) & 7u) != 0) return hipErrorInvalidValue;
   if (a.nrows <= 0) return hipSuccess;
   const int nu = (a.M + 7) / 8;
-  switch (nu) {
-    case 1: return transform_nu<1>(a, s);
-    case 2: return transform_nu<2>(a, s);
-    case 3: return transform_nu<3>(a, s);
-    case 4: return transform_nu<4>(a, s);
-    case 5: return transform_nu<5>(a, s);
-    case 6: return transform_nu<6>(a, s);
-    case 7: return transform_nu<7>(a, s);
-    case 8: return transform_nu<8>(a, s);
-    case 9: return transform_nu<9>(a, s);
-    case 10: return transform_nu<10>(a, s);
-    case 11: return transform_nu<11>(a, s);
-    case 12: return transform_nu<12>(a, s);
-    case 13: return transform_nu<13>(a, s);
-    case 14: return transform_nu<14>(a, s);
-    case 15: return transform_nu<15>(a, s);
-    case 16: return transform_nu<16>(a, s);
-    case 17: return transform_nu<17>(a, s);
-    case 18: return transform_wide_nu<18>(a, s);
-    case 19: return transform_wide_nu<19>(a, s);
-    case 20: return transform_wide_nu<20>(a, s);
-    case 21: return transform_wide_nu<21>(a, s);
-    case 22: return transform_wide_nu<22>(a, s);
-    case 23: return transform_wide_nu<23>(a, s);
-    case 24: return transform_wide_nu<24>(a, s);
-    case 25: return transform_wide_nu<25>(a, s);
-    case 26: return transform_wide_nu<26>(a, s);
-    case 27: return transform_wide_nu<27>(a, s);
-    case 28: return transform_wide_nu<28>(a, s);
-    case 29: return transform_wide_nu<29>(a, s);
-    case 30: return transform_wide_nu<30>(a, s);
-    case 31: return transform_wide_nu<31>(a, s);
-    case 32: return transform_wide_nu<32>(a, s);
-    default: return hipErrorInvalidValue;
-  }
+  if (nu <= 17) return dispatch_width(nu, WidthRange<1, 17>{}, [&](auto n) { return transform_nu<n>(a, s); });
+  return dispatch_width(nu, WidthRange<18, 32>{}, [&](auto n) { return transform_wide_nu<n>(a, s); });
 }
 
 }  // namespace efa
