@@ -9,6 +9,7 @@ from efa_xray_amd.state.ensemble import EnsembleState
 from efa_xray_amd.observation.observation import Observation, gaspari_cohn, haversine
 from efa_xray_amd.assimilation.assimilation import Assimilation
 from efa_xray_amd.assimilation.ensrf import EnSRF
+from efa_xray_amd.assimilation.adaptive_inflation import AdaptiveInflation
 
-__all__ = ["EnsembleState", "Observation", "gaspari_cohn", "haversine", "Assimilation", "EnSRF"]
+__all__ = ["EnsembleState", "Observation", "gaspari_cohn", "haversine", "Assimilation", "EnSRF", "AdaptiveInflation"]
 __version__ = "0.1.0"

@@ -46,6 +46,9 @@ SIGNATURES = {
     "efa_ctx_set_option": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_long]),
     "efa_ctx_get_option": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_long)]),
     "efa_ctx_set_relaxation": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double]),
+    "efa_inflate_rows_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "efa_ctx_set_adaptive_inflation": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_double,
+                                                      ctypes.c_double, ctypes.c_double]),
     "efa_ctx_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
     "efa_malloc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, c_void_pp]),
     "efa_free": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
@@ -287,6 +290,16 @@ class Context(object):
     def set_relaxation(self, kind, alpha=0.0):
         """Posterior relaxation of every later state phase on this context (RELAX_NONE / RELAX_RTPP / RELAX_RTPS)."""
         _check(self.lib, self.lib.efa_ctx_set_relaxation(self.handle, int(kind), float(alpha)))
+
+    def set_adaptive_inflation(self, field, rows=0, lower=1.0, upper=1e6, sd_lower=0.0):
+        """Adaptive inflation (Anderson 2009) of every later GC state phase on this context: `field` a device [rows][2]
+        (mean, sd) array updated in place, or None to turn it off."""
+        _check(self.lib, self.lib.efa_ctx_set_adaptive_inflation(self.handle, self._addr(field), int(rows), float(lower),
+                                                                 float(upper), float(sd_lower)))
+
+    def inflate_rows(self, rows, M, X, field):
+        """X[row] <- mean + sqrt(field[row][0]) (X[row] - mean), in place on the device."""
+        _check(self.lib, self.lib.efa_inflate_rows_dev(self.handle, rows, M, self._addr(X), self._addr(field)))
 
     def set_stream(self, hip_stream):
         _check(self.lib, self.lib.efa_ctx_set_stream(self.handle, ctypes.c_void_p(hip_stream or 0)))

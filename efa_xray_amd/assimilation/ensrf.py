@@ -15,6 +15,7 @@ library or a gfx950 GPU is missing the call raises -- there is no NumPy path.
 import numpy as np
 
 from efa_xray_amd import _lib
+from efa_xray_amd.assimilation.adaptive_inflation import AdaptiveInflation
 from efa_xray_amd.assimilation.assimilation import Assimilation
 
 
@@ -44,15 +45,29 @@ class EnSRF(Assimilation):
         rtps     -- posterior relaxation to prior spread, factor >= 0 (Whitaker & Hamill 2012)
         rtpp     -- posterior relaxation to prior perturbations, factor in [0, 1]
                     (at most one of the two; None: no relaxation)
+        adaptive_inflation -- an AdaptiveInflation: its field inflates the prior and is updated
+                    from the innovations by every update() (Anderson 2009); needs
+                    loc='GC' and excludes inflation=
         """
         device = kw.pop("device", 0)
         self.obs_batch = kw.pop("obs_batch", None)
         self.path = kw.pop("path", None)
         rtps = kw.pop("rtps", None)
         rtpp = kw.pop("rtpp", None)
+        adaptive = kw.pop("adaptive_inflation", None)
         if kw:
             raise TypeError("unexpected keyword arguments %r" % sorted(kw))
         self.relaxation = relaxation_setting(rtps, rtpp)
+        if adaptive is not None:
+            if not isinstance(adaptive, AdaptiveInflation):
+                raise ValueError("adaptive_inflation must be an AdaptiveInflation, got %r" % type(adaptive).__name__)
+            if loc != 'GC':
+                raise ValueError("adaptive_inflation needs loc='GC' (Anderson 2009 is defined per state element, "
+                                 "weighted by localisation); got loc=%r" % (loc,))
+            if inflation is not None:
+                raise ValueError("adaptive_inflation and inflation= are exclusive: the adaptive field is the prior inflation")
+            adaptive.check_state(state)
+        self.adaptive_inflation = adaptive
         Assimilation.__init__(self, state, obs, nproc, inflation, verbose, device=device)
         self.loc = loc
         self.last_timing = None
@@ -97,6 +112,7 @@ class EnSRF(Assimilation):
                 "transform": _lib.PATH_TRANSFORM}[self.path]
         ctx.set_option("path", path)
         ctx.set_relaxation(*self.relaxation)   # every call: the context is shared per device
+        ctx.set_adaptive_inflation(None)        # set by update() around its own cycle only
 
     # ------------------------------------------------------------------
     def update(self):
@@ -114,19 +130,43 @@ class EnSRF(Assimilation):
         N = prior.nstate()
         M = prior.nmems()
 
+        ai = self.adaptive_inflation
+        if ai is not None:
+            ai.check_state(prior)
         ctx = self._context()
         self._configure(ctx)
         ctx.set_option("timing", 1)
         if self.verbose:
             print("Converting state to vector")
-        X = self._upload_prior(ctx)                            # slab by slab from the variables: no stacked host copy
+        device_fo = P and self._default_forward_operator()
+        field = None
+        HX = None
+        if ai is not None:
+            # the prior inflation comes before the forward operator: on the device for the reference's
+            # point interpolation, on the host for user-defined operators (they read the state object), which is then the
+            # state that is uploaded
+            field = ctx.to_device(ai.inflation.to_vect())
+            if not device_fo and P:
+                self.prior = ai.inflate_state(prior)           # for the operators and the upload only
+                try:
+                    X = self._upload_prior(ctx)
+                    HX = self.compute_ob_estimates()
+                finally:
+                    self.prior = prior
+            else:
+                X = self._upload_prior(ctx)
+                ctx.inflate_rows(N, M, X, field)
+        else:
+            X = self._upload_prior(ctx)                        # slab by slab from the variables: no stacked host copy
         # forward operator, once per ob from the prior (assimilation.py:45-48): on the device for the
         # reference's point interpolation, through ob.estimate() for user-defined operators
         if self.verbose:
             print("Computing observation priors")
         ym = ctx.empty((max(P, 1),))
-        if P and self._default_forward_operator():
+        if device_fo:
             Yp = self.device_ob_estimates(ctx, X)
+        elif HX is not None:
+            Yp = ctx.to_device(HX)
         else:
             Yp = ctx.to_device(self.compute_ob_estimates()) if P else ctx.empty((1, M))
         if P:
@@ -142,7 +182,16 @@ class EnSRF(Assimilation):
             print("Beginning observation loop")
         # Phase A (ensrf.py:50-149 on the obs block) and the state phase in one library call; in place, so nothing is
         # enqueued ahead of Phase A's status (efa_ensrf_cycle_dev speculates only into a separate posterior buffer)
-        diag = ctx.ensrf_cycle(N, M, P, X, X, ym, Yp, value, error, assim, loc_mode, lat, lon, hw, grid_lat, grid_lon, n_lead)
+        if ai is None:
+            diag = ctx.ensrf_cycle(N, M, P, X, X, ym, Yp, value, error, assim, loc_mode, lat, lon, hw, grid_lat, grid_lon, n_lead)
+        else:
+            ctx.set_adaptive_inflation(field, N, ai.lower, ai.upper, ai.sd_lower)
+            try:
+                diag = ctx.ensrf_cycle(N, M, P, X, X, ym, Yp, value, error, assim, loc_mode, lat, lon, hw, grid_lat, grid_lon,
+                                       n_lead)
+            finally:
+                ctx.set_adaptive_inflation(None)
+            ai.inflation.from_vect(field.download())           # next cycle's prior inflation
         self.last_timing = ctx.last_timing()
 
         # diagnostics onto the observations, as ensrf.py:66,70,75,146-149
@@ -169,6 +218,9 @@ class EnSRF(Assimilation):
         `format_prior_state`) and return `(xam, Xap)` as handed to
         `format_posterior_state` (ensrf.py:44,151).  Diagnostics are written
         onto the observations."""
+        if self.adaptive_inflation is not None:
+            raise ValueError("update_arrays does not support adaptive_inflation (out of scope: it runs on the augmented "
+                             "arrays without the prior inflation step); use update()")
         loc_mode = self._loc_mode()
         P, value, error, assim, lat, lon, hw = self._ob_arrays(loc_mode)
         N = self.prior.nstate()

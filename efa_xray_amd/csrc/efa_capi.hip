@@ -185,6 +185,11 @@ struct efa_ctx {
   DevBuf relax_T;      // RTPP: (1-alpha) T + alpha I [M][M]
   DevBuf relax_ss;     // standalone passes: sum of squared prior deviations per row [rows]
   DevBuf relax_prior;  // standalone RTPP with the posterior written over the prior: a copy of the prior [rows][M]
+  // --- adaptive inflation (efa_ctx_set_adaptive_inflation) -------------------------------------
+  double* ai_field = nullptr;  // the caller's [ai_rows][2] (mean, sd), updated by every GC state phase; null: off
+  long ai_rows = 0;
+  double ai_lower = 1.0, ai_upper = 1e6, ai_sd_lower = 0.0;
+  DevBuf ai_ob;               // [P][4] what the sweep's update reads of each ob (launch_adapt_obs)
   // --- f1: interpolation stencils -------------------------------------------------
   DevBuf fs_idx, fs_wts;  // efa_forward_stencil_dev staging
   DevBuf f_glat, f_glon, f_sl, f_cl, f_valids, f_var, f_time, f_lat, f_lon, f_near, f_idx, f_wts, f_status;
@@ -378,6 +383,18 @@ TransformArgs carried_transform(const efa_ctx* c, const double* Xin, const doubl
                                 int fused_members) {
   return TransformArgs{Xin, xin, Xout, xout, rows, c->M, c->Yw.as<double>() + (size_t)c->P * c->M, c->ymw.as<double>() + c->P,
                        fused_members};
+}
+
+// ---- adaptive inflation (efa_adapt.hip, the update fused into the one-pass GC sweep) ----------------------------------------
+// While a field is set, only the one-pass GC state sweep may run the state phase: it is the one that updates the field.
+int check_adaptive(const efa_ctx* c, int loc_mode, long rows) {
+  if (!c->ai_field) return EFA_OK;
+  if (loc_mode != EFA_LOC_GC)
+    return fail(EFA_ERR_INVALID, "adaptive inflation is set: it needs GC localisation (loc_mode %d is not EFA_LOC_GC)", loc_mode);
+  if (!c->gc_onepass) return fail(EFA_ERR_INVALID, "adaptive inflation is set: it needs the one-pass GC sweep (option gc_onepass is 0)");
+  if (rows != c->ai_rows)
+    return fail(EFA_ERR_INVALID, "adaptive inflation field has %ld rows but the state phase has %ld", c->ai_rows, rows);
+  return EFA_OK;
 }
 
 // ---- Phase A ---------------------------------------------------------------
@@ -1082,6 +1099,17 @@ int state_gc_onepass(efa_ctx* c, const double* xm_in, const double* Xp_in, doubl
   g.Xout = Xp_out;
   g.xout = xm_out;
   g.fused_members = fused_members;
+  if (c->ai_field) {  // the per-ob scalars of the inflation update, from Phase A's records and diagnostics
+    EFA_TRY(c->ai_ob.reserve((size_t)(P ? P : 1) * 4 * sizeof(double)));
+    EFA_HIP(launch_adapt_obs(P, M, c->coef.as<double>(), c->d_prior_var.as<double>(), c->ob_err.as<double>(), c->ye_ptr, c->ye_stride,
+                             c->ai_ob.as<double>(), s));
+    c->state_launches++;
+    g.infl = c->ai_field;
+    g.adapt_ob = c->ai_ob.as<double>();
+    g.infl_lower = c->ai_lower;
+    g.infl_upper = c->ai_upper;
+    g.infl_sd_lower = c->ai_sd_lower;
+  }
   EFA_HIP(launch_sweep_gc(g, s));
   c->state_launches++;
   return EFA_OK;
@@ -1141,6 +1169,7 @@ int state_phase(efa_ctx* c, long rows, int M, const double* xm_in, const double*
   if (!c->have_traj) return fail(EFA_ERR_INVALID, "efa_state_phase_dev called before efa_obs_phase_dev");
   if (M != c->M) return fail(EFA_ERR_INVALID, "M=%d differs from the obs phase's M=%d", M, c->M);
   if (rows < 0) return fail(EFA_ERR_INVALID, "negative row count");
+  EFA_TRY(check_adaptive(c, c->loc_mode, rows));
   reset_state_phase(c);
   if (rows == 0) return EFA_OK;
   if (!xm_in || !Xp_in || !xm_out || !Xp_out) return fail(EFA_ERR_INVALID, "null state pointer");
@@ -1271,7 +1300,7 @@ int efa_ctx_destroy(efa_ctx* c) {
   DevBuf* bufs[] = {&c->ob_pack, &c->out_pack, &c->Ye_rec, &c->coef, &c->ob_val, &c->ob_err, &c->ob_asm, &c->ob_lat, &c->ob_lon, &c->ob_hw, &c->ob_errsq,
                     &c->d_prior_mean, &c->d_prior_var, &c->d_post_mean, &c->d_post_var, &c->d_assimilated,
                     &c->Yw, &c->ymw, &c->win_Y, &c->win_m, &c->traj, &c->tw_mat, &c->status, &c->dbg, &c->W, &c->gc_cnt, &c->gc_ub, &c->gc_order, &c->gc_obtrig, &c->gc_off, &c->gc_idx, &c->gc_wts, &c->gc_pairs, &c->glat, &c->glon, &c->xm_ws, &c->fs_idx, &c->fs_wts, &c->f_glat, &c->f_glon, &c->f_sl, &c->f_cl, &c->f_valids, &c->f_var, &c->f_time, &c->f_lat, &c->f_lon, &c->f_near, &c->f_idx, &c->f_wts, &c->f_status, &c->h_xm, &c->h_Xp, &c->h_ym, &c->h_Yp,
-                    &c->gcc_lat, &c->gcc_lon, &c->gcc_oblat, &c->gcc_oblon, &c->gcc_obhw, &c->gcc_coef, &c->gcc_trig, &c->gcc_cnt, &c->gcc_pairs};
+                    &c->gcc_lat, &c->gcc_lon, &c->gcc_oblat, &c->gcc_oblon, &c->gcc_obhw, &c->gcc_coef, &c->gcc_trig, &c->gcc_cnt, &c->gcc_pairs, &c->ai_ob};
   for (DevBuf* b : bufs) b->release();
   for (int i = 0; i < 7; ++i)
     if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -1351,6 +1380,36 @@ int efa_ctx_set_relaxation(efa_ctx* c, int kind, double alpha) {
   }
   c->relax_kind = kind;
   c->relax_alpha = kind == EFA_RELAX_NONE ? 0.0 : alpha;
+  return EFA_OK;
+}
+
+int efa_ctx_set_adaptive_inflation(efa_ctx* c, double* field_dev, long rows, double lower, double upper, double sd_lower) {
+  EFA_TRY(use(c));
+  if (!field_dev) {
+    c->ai_field = nullptr;
+    c->ai_rows = 0;
+    return EFA_OK;
+  }
+  if (rows < 0) return fail(EFA_ERR_INVALID, "adaptive inflation: negative row count");
+  if ((reinterpret_cast<uintptr_t>(field_dev) & 7u) != 0) return fail(EFA_ERR_INVALID, "adaptive inflation: field must be 8-byte aligned");
+  if (!std::isfinite(lower) || !(lower > 0.0)) return fail(EFA_ERR_INVALID, "adaptive inflation: lower bound %g must be finite and > 0", lower);
+  if (!std::isfinite(upper) || upper < lower)
+    return fail(EFA_ERR_INVALID, "adaptive inflation: upper bound %g must be finite and >= the lower bound %g", upper, lower);
+  if (!std::isfinite(sd_lower) || sd_lower < 0.0)
+    return fail(EFA_ERR_INVALID, "adaptive inflation: sd lower bound %g must be finite and >= 0", sd_lower);
+  c->ai_field = field_dev;
+  c->ai_rows = rows;
+  c->ai_lower = lower;
+  c->ai_upper = upper;
+  c->ai_sd_lower = sd_lower;
+  return EFA_OK;
+}
+
+int efa_inflate_rows_dev(efa_ctx* c, long rows, int M, double* X_dev, const double* field_dev) {
+  EFA_TRY(use(c));
+  if (rows < 0 || M < 1 || M > efa::kMaxMembers) return fail(EFA_ERR_INVALID, "efa_inflate_rows_dev: bad shape rows=%ld M=%d", rows, M);
+  if (rows && (!X_dev || !field_dev)) return fail(EFA_ERR_INVALID, "null pointer");
+  EFA_HIP(efa::launch_inflate_rows(rows, M, X_dev, field_dev, c->stream));
   return EFA_OK;
 }
 
@@ -1570,6 +1629,7 @@ int efa_state_cycle_dev(efa_ctx* c, long rows, int M, const double* X_dev, doubl
   EFA_TRY(use(c));
   if (!c->have_traj) return fail(EFA_ERR_INVALID, "efa_state_cycle_dev called before efa_obs_phase_dev");
   if (M != c->M) return fail(EFA_ERR_INVALID, "M=%d differs from the obs phase's M=%d", M, c->M);
+  EFA_TRY(check_adaptive(c, c->loc_mode, rows));
   reset_state_phase(c);
   if (rows <= 0) return rows == 0 ? EFA_OK : fail(EFA_ERR_INVALID, "negative row count");
   if (!X_dev || !post_dev) return fail(EFA_ERR_INVALID, "null state pointer");
@@ -1601,6 +1661,7 @@ int efa_ensrf_update_dev(efa_ctx* c, long rows, int M, long P, double* xm_dev, d
                          const double* grid_lat, const double* grid_lon, long ncol, long n_lead, double* prior_mean,
                          double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated) {
   EFA_TRY(use(c));
+  EFA_TRY(check_adaptive(c, loc_mode, rows));
   EFA_TRY(obs_phase(c, M, P, ym_dev, Yp_dev, ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon,
                     ob_halfwidth_km, prior_mean, prior_var, post_mean, post_var, assimilated));
   EFA_TRY(state_phase(c, rows, M, xm_dev, Xp_dev, xm_dev, Xp_dev, grid_lat, grid_lon, ncol, n_lead));
@@ -1616,6 +1677,7 @@ int efa_ensrf_cycle_dev(efa_ctx* c, long rows, int M, long P, const double* X_de
   EFA_TRY(use(c));
   if (rows < 0) return fail(EFA_ERR_INVALID, "negative row count");
   if (rows > 0 && (!X_dev || !post_dev)) return fail(EFA_ERR_INVALID, "null state pointer");
+  EFA_TRY(check_adaptive(c, loc_mode, rows));
   // Phase B may go into the stream before Phase A's status is known only if a wrong guess cannot cost the prior:
   // separate prior and posterior buffers (a redone Phase A needs the transform run again on the untouched prior)
   const char* xb = reinterpret_cast<const char*>(X_dev);

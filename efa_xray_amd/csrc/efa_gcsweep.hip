@@ -271,7 +271,7 @@ __global__ __launch_bounds__(64 * kBuildWaves) void k_gc_build(long ncol, long n
 
 constexpr int kChunk = 32;  // active observations staged in LDS at a time
 
-// Workgroup = one column block.  Wave w owns columns 4w .. 4w+3 of the block; its 16 quads are 4 columns x 4
+// k_sweep_gc (efa_gcsweep_kernels.h).  Workgroup = one column block.  Wave w owns columns 4w .. 4w+3 of the block; its 16 quads are 4 columns x 4
 // variable x time slabs, RPL rows (slabs) per quad, so the four waves walk the same 4 RPL slabs of different
 // columns in lock step.  The block's active observations are staged chunk by chunk into LDS ONCE per group
 // of slabs (ye rows, tapers, coefficients), so the per-lane traffic of the inner loop is LDS only; a wave
@@ -320,124 +320,47 @@ __device__ __forceinline__ double gc_dot(const double (&x)[2 * NC], const double
   return group_sum<4>(s0 + s1);
 }
 
+// ---- adaptive inflation (Anderson 2009), fused into both sweep forms.  One state row's (lam, sd) is updated by
+// one observation from what the sweep holds for the (row, ob) pair BEFORE the ob moves the row: w the taper on the row's column
+// (0 for an ob not assimilated), dot = x'.y', ss = x'.x', and the ob's staged record o01 = {D^2, sigma_p^2}, o23 = {sigma_o^2,
+// y'.y'}.  The formulas of §7c in forms that take fewer fp64 square roots and divides (each a multi-instruction sequence):
+//   gamma = min(1, w |dot| rsqrt(ss y'.y')), tested for 0 before any of it;
+//   g = (dtheta/theta)(D^2/theta^2 - 1) = sp2 gamma q (D^2 - theta^2) / (2 sqrt(lam) theta^4)   (theta itself is not needed);
+//   lam_n = lam + 2 s^2 g / (1 + sqrt(1 + 4 s^2 g^2)), the root of DART's linear_bayes nearer lam, without cancellation;
+//   l = E(lam_n + s) - E(lam_n) + log(theta(lam_n)/theta(lam_n + s))
+//     = -(2 a0 + s) / (2 s) + D^2 (t1 - t0) / (2 t0 t1) + log(t0 / t1) / 2,   a0 = lam_n - lam, t = theta^2 at lam_n, lam_n + s.
+__device__ __forceinline__ void anderson_update(double& lam, double& sd, double w, double dot, double ss, double2 o01, double2 o23,
+                                                double lower, double upper, double sd_lower) {
+  const double nn = ss * o23.y;
+  const double wd = w * fabs(dot);
+  if (!(wd > 0.0) || !(nn > 0.0) || !(sd > 0.0)) return;  // gamma = 0 (or no spread): nothing changes
+  const double gamma = fmin(1.0, wd * rsqrt(nn));
+  const double d2 = o01.x, sp2 = o01.y, so2 = o23.x;
+  const double rl = sqrt(lam);
+  const double q = 1.0 + gamma * (rl - 1.0);
+  const double th2 = q * q * sp2 + so2;
+  const double g = (sp2 * gamma * q * (d2 - th2)) / (2.0 * rl * (th2 * th2));
+  const double s2 = sd * sd;
+  double ln = lam + 2.0 * s2 * g / (1.0 + sqrt(1.0 + 4.0 * s2 * (g * g)));
+  ln = fmin(fmax(ln, lower), upper);
+  if (sd > sd_lower) {
+    const double q0 = 1.0 + gamma * (sqrt(ln) - 1.0), q1 = 1.0 + gamma * (sqrt(ln + sd) - 1.0);
+    const double t0 = q0 * q0 * sp2 + so2, t1 = q1 * q1 * sp2 + so2;  // theta^2 at lam_new and lam_new + sd
+    const double ell = -(2.0 * (ln - lam) + sd) / (2.0 * sd) + d2 * (t1 - t0) / (2.0 * (t0 * t1)) + 0.5 * log(t0 / t1);
+    if (ell < -0.010050335853501441) sd = fmin(fmax(sqrt(-s2 / (2.0 * ell)), sd_lower), sd);  // log(0.99)
+  }
+  lam = ln;
+}
+// x'.x' of the row after the ob: x' - kb y' (kb = the member gain), by the exact recursion
+__device__ __forceinline__ double adapt_ss_after(double ss, double kb, double dot, double yy) {
+  return fmax(ss - kb * (2.0 * dot - kb * yy), 0.0);
+}
+
 // waves per SIMD the register budget allows: RPL rows and one ye row of 2 NC doubles per lane, ~36 registers of everything else
 constexpr int gc_min_waves(int NC, int RPL) {
   return (4 * NC * (RPL + 1) + 36 <= 168) ? EFA_GC_MINWAVES : (4 * NC * (RPL + 1) + 36 <= 256 || NC * (RPL + 1) <= 52) ? 2 : 1;
 }
 
-template <int NC, bool VEC, bool FUSED, int RPL>
-__global__ __launch_bounds__(256, gc_min_waves(NC, RPL)) void k_sweep_gc(const GcSweepArgs a) {
-  constexpr int L = 4;
-  constexpr int S = 2 * L * NC;  // padded ye row (doubles)
-  __shared__ __align__(16) double ye_s[kChunk * S];
-  __shared__ __align__(16) double2 ab_s[kChunk * kBlkCols];  // per (staged ob, column): what scales (x . ye) in the row / in its mean
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6, lane = tid & 63;
-  const int j = lane & 3, r = lane >> 2;
-  // blockIdx.x = (position in the longest-first order) * lead_split + (group of slabs): a shard with few, long
-  // column blocks (the polar ranks of a cost-balanced split) still fills the device and has no tail of whole blocks
-  const long b = a.order[blockIdx.x / a.lead_split];
-  const int lead_lo = (int)(blockIdx.x % a.lead_split) * (int)a.lead_chunk;
-  const int lead_hi = (lead_lo + (int)a.lead_chunk < (int)a.n_lead) ? lead_lo + (int)a.lead_chunk : (int)a.n_lead;
-  // quad r of wave w: column cq of the block, slab slot sq of the group of slabs
-  const int cq = EFA_GC_COLSPLIT ? 4 * wave + (r & 3) : r;
-  const int sq = EFA_GC_COLSPLIT ? (r >> 2) : wave;
-  const long col = b * kBlkCols + cq;
-  const bool col_ok = col < a.ncol;
-  const int M = a.M;
-  const double rM1 = 1.0 / (double)(M - 1);
-  const long e0 = a.off[b], e1 = e0 + a.cnt[b];
-
-  // A quad holds RPL rows of the SAME column (slabs lead, lead + 4, ...): they share the taper and
-  // every ye row read from LDS (the quad layout delivers each ye row once per quad), and a staged
-  // chunk serves 4 RPL slabs instead of 4.
-  for (int lead0 = lead_lo; lead0 < lead_hi; lead0 += 4 * RPL) {
-    double x[RPL][2 * NC];
-    double xm[RPL];
-    bool live[RPL];
-    long row[RPL];
-    bool any_live = false;
-#pragma unroll
-    for (int q = 0; q < RPL; ++q) {
-      const int lead = lead0 + sq + 4 * q;
-      live[q] = col_ok && lead < lead_hi;
-      any_live = any_live || live[q];
-      row[q] = (long)lead * a.ncol + col;
-      xm[q] = 0.0;
-      if (live[q]) {
-        load_row<L, NC, VEC>(a.Xin + (size_t)row[q] * M, M, j, x[q]);
-        if (!FUSED) xm[q] = a.xin[row[q]];
-      } else {
-#pragma unroll
-        for (int c = 0; c < 2 * NC; ++c) x[q][c] = 0.0;
-      }
-      if (FUSED) {  // prior members in: remove the ensemble mean (assimilation.py:146-147)
-        xm[q] = group_rowsum<L, NC>(x[q]) / (double)M;
-#pragma unroll
-        for (int c = 0; c < 2 * NC; ++c) x[q][c] -= xm[q];  // padding slots never reach the output or the dot
-      }
-    }
-    for (long c0 = e0; c0 < e1; c0 += kChunk) {
-      const int ne = (int)((e1 - c0 < kChunk) ? (e1 - c0) : kChunk);
-      __syncthreads();  // previous chunk fully consumed
-      // ---- cooperative staging of ne entries
-      if (VEC) {
-        constexpr int S2 = S / 2;
-        const int M2 = M / 2;
-        for (int i = tid; i < ne * S2; i += 256) {
-          const int ee = i / S2, m2 = i - ee * S2;
-          const int k = a.idx[c0 + ee];
-          reinterpret_cast<double2*>(ye_s)[i] =
-              (m2 < M2) ? reinterpret_cast<const double2*>(a.Ye + (size_t)k * a.ye_stride)[m2] : make_double2(0.0, 0.0);
-        }
-      } else {
-        for (int i = tid; i < ne * S; i += 256) {
-          const int ee = i / S, m = i - ee * S;
-          const int k = a.idx[c0 + ee];
-          ye_s[i] = (m < M) ? a.Ye[(size_t)k * a.ye_stride + m] : 0.0;
-        }
-      }
-      // The gain scalars of ensrf.py:95-136 -- kcov = (x . ye)/(M-1), times the taper, /kdenom, times innov for the mean
-      // and times beta for the members -- do not depend on the state row: they are folded ONCE per (ob, column) here,
-      // A = w (1/(M-1)) (1/kdenom) beta and B = w (1/(M-1)) (1/kdenom) innov, instead of six dependent multiplications
-      // per row and observation in a loop that is bound by the number of fp64 instructions it issues.
-      for (int i = tid; i < ne * kBlkCols; i += 256) {
-        const double w = a.wts[(size_t)c0 * kBlkCols + i];
-        const double* ck = a.coef + (size_t)a.idx[c0 + i / kBlkCols] * kCoefStride;  // innov, 1/kdenom, beta, active
-        const double g = (w * rM1) * ck[1];
-        ab_s[i] = make_double2(g * ck[2], g * ck[0]);  // w == 0 (or an ob that is not assimilated): both exactly 0
-      }
-      __syncthreads();
-      // ---- apply the chunk to this wave's 16 RPL rows
-      for (int ee = 0; ee < ne; ++ee) {
-        const double2 ab = ab_s[ee * kBlkCols + cq];
-        if (!any_live || __ballot(ab.x != 0.0) == 0ull) continue;  // none of this wave's rows (dead slabs / zero taper)
-        double y[2 * NC];
-        lds_read_row<L, NC>(ye_s + ee * S, j, y);
-#pragma unroll
-        for (int q = 0; q < RPL; ++q) {
-          if (RPL > 2 && lead0 + 4 * q >= lead_hi) continue;  // wave-uniform: this slot is beyond the last slab in every quad
-          const double dot = gc_dot<NC>(x[q], y);        // :95 (a dead row holds zeros: its dot, and so its update, is exactly 0)
-          xm[q] = __builtin_fma(ab.y, dot, xm[q]);       // :115, :119, :130
-          const double kb = ab.x * dot;                  // :115, :119, :136
-#pragma unroll
-          for (int c = 0; c < 2 * NC; ++c) x[q][c] = __builtin_fma(-kb, y[c], x[q][c]);  // :141
-        }
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < RPL; ++q) {
-      if (live[q]) {
-        if (FUSED) {  // posterior members out (assimilation.py:168)
-#pragma unroll
-          for (int c = 0; c < 2 * NC; ++c) x[q][c] += xm[q];
-        }
-        store_row<L, NC, VEC>(a.Xout + (size_t)row[q] * M, M, j, x[q]);
-        if (!FUSED && j == 0) a.xout[row[q]] = xm[q];
-      }
-    }
-  }
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Row-per-lane form of the same sweep (round 3).  A lane holds one WHOLE state row (up to 104 members in registers), so the
@@ -481,151 +404,63 @@ __device__ __forceinline__ void lane_update_prefetch(double (&x)[MP], double (&y
   }
 }
 
+// ADAPT: the same update without the prefetch -- the inflation update then runs while no ye register is live (at 100 members the
+// row, the ye registers and the update's temporaries do not fit 256 registers together), and the next ye row is read after it
+template <int MP, int C = 0>
+__device__ __forceinline__ void lane_update(double (&x)[MP], const double (&y)[(MP + 15) / 16], double nkb) {
+  constexpr int NG = (MP + 15) / 16;
+  if constexpr (C < NG) {
+    constexpr int n = (MP - 16 * C < 16) ? MP - 16 * C : 16;
+    lane_update_group<MP, C>(x, y[C], nkb, std::make_integer_sequence<int, n>{});
+    lane_update<MP, C + 1>(x, y, nkb);
+  }
+}
+
 constexpr int kLaneMaxMembers = 104;
 #ifndef EFA_GC_LANE_CHUNK
 #define EFA_GC_LANE_CHUNK 32
 #endif
 constexpr int kChunkL = EFA_GC_LANE_CHUNK;  // observations staged at a time by the row-per-lane kernel (a 64-bit mask of them per wave)
-template <int MP, bool FUSED>  // members padded to a multiple of 4; FUSED: prior members in, posterior members out
-__global__ __launch_bounds__(256, 2) void k_sweep_gc_lane(const GcSweepArgs a) {
-  constexpr int NG = (MP + 15) / 16;  // ye registers per lane
-  constexpr int YS = 16 * NG;         // padded ye row in LDS (doubles)
-  __shared__ __align__(16) double ye_s[kChunkL * YS];
-  __shared__ __align__(16) double2 ab_s[kChunkL * kBlkCols];
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6, lane = tid & 63;
-  // One workgroup per (column block, group of 16 slabs), blocks longest list first, a block's groups next to each other (its
-  // list stays in L2) but starting at a different group from block to block.  (The list is staged once per group of slabs
-  // whichever workgroup takes it, so the fine split costs nothing.  The hardware deals consecutive workgroups to the eight
-  // XCDs in turn: with several groups per workgroup and unequal parts, the larger parts of every block landed on the same
-  // XCDs -- measured as up to 25 % imbalance on a polar shard; all blocks' first groups, then all second groups, ... is even
-  // but 2.5 % slower on the whole grid, the lists leaving L2 between a block's groups.)
-  const long pos = blockIdx.x / a.lead_split;
-  const long b = a.order[pos];
-  const int lead_lo = 16 * (int)((blockIdx.x % a.lead_split + pos) % a.lead_split);
-  const int lead_hi = (lead_lo + 16 < (int)a.n_lead) ? lead_lo + 16 : (int)a.n_lead;
-  const int M = a.M, M2 = M / 2;
-  const double rM1 = 1.0 / (double)(M - 1);
-  const long e0 = a.off[b], e1 = e0 + a.cnt[b];
-  const auto seq = std::make_integer_sequence<int, MP>{};
+// The kernels k_sweep_gc (quad form) and k_sweep_gc_lane (row-per-lane form), defined twice: as they are, and with the
+// adaptive-inflation update fused in as k_sweep_gc_adapt / k_sweep_gc_lane_adapt
+#define EFA_GCK_ADAPT false
+#define EFA_GCK_QUAD k_sweep_gc
+#define EFA_GCK_LANE k_sweep_gc_lane
+#define EFA_GCK_LANE_WAVES(MP) 2
+#define EFA_GCK_QUAD_WAVES(NC, RPL) gc_min_waves(NC, RPL)
+#include "efa_gcsweep_kernels.h"
+#undef EFA_GCK_ADAPT
+#undef EFA_GCK_QUAD
+#undef EFA_GCK_LANE
+#undef EFA_GCK_LANE_WAVES
+#undef EFA_GCK_QUAD_WAVES
+// the quad form with the update: one row per quad (gc_launch), and waves per SIMD for that row, one ye row and ~100 registers of
+// everything else (the update's temporaries included)
+constexpr int gc_adapt_min_waves(int NC) { return (4 * NC * 2 + 100 <= 168) ? 3 : (4 * NC * 2 + 100 <= 256) ? 2 : 1; }
+// with the update, above 80 members at one wave per SIMD: the row, the ye registers and the update's temporaries spill at two
+#define EFA_GCK_ADAPT true
+#define EFA_GCK_QUAD k_sweep_gc_adapt
+#define EFA_GCK_LANE k_sweep_gc_lane_adapt
+#define EFA_GCK_LANE_WAVES(MP) ((MP) > 80 ? 1 : 2)
+#define EFA_GCK_QUAD_WAVES(NC, RPL) gc_adapt_min_waves(NC)
+#include "efa_gcsweep_kernels.h"
+#undef EFA_GCK_ADAPT
+#undef EFA_GCK_QUAD
+#undef EFA_GCK_LANE
+#undef EFA_GCK_LANE_WAVES
+#undef EFA_GCK_QUAD_WAVES
 
-  for (int lead0 = lead_lo; lead0 < lead_hi; lead0 += 16) {
-    // 16 slabs x 4 columns per wave; the last group of a block: the next power of two of what is left, more columns per wave
-    const int rem = lead_hi - lead0;
-    const int lg_cols = (rem > 8) ? 2 : (rem > 4) ? 3 : (rem > 2) ? 4 : (rem > 1) ? 5 : 6;
-    const int ncw = 1 << lg_cols;                 // columns per wave
-    const int cq = (lane & (ncw - 1)) + ncw * wave;
-    const int lead = lead0 + (lane >> lg_cols);
-    const long col = b * kBlkCols + cq;
-    const bool live = cq < kBlkCols && col < a.ncol && lead < lead_hi;
-    const bool any_live = __ballot(live) != 0ull;
-    const long row = (long)lead * a.ncol + col;
-    double x[MP];
-    double xm = 0.0;
-    if (live) {
-      const double2* p = reinterpret_cast<const double2*>(a.Xin + (size_t)row * M);
-      if (M == MP) {
-#pragma unroll
-        for (int i = 0; i < MP / 2; ++i) {
-          const double2 v = p[i];
-          x[2 * i] = v.x;
-          x[2 * i + 1] = v.y;
-        }
-      } else {
-#pragma unroll
-        for (int i = 0; i < MP / 2; ++i) {
-          const double2 v = (i < M2) ? p[i] : make_double2(0.0, 0.0);
-          x[2 * i] = v.x;
-          x[2 * i + 1] = v.y;
-        }
-      }
-      if (FUSED) {  // prior members in: remove the ensemble mean (assimilation.py:146-147)
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-#pragma unroll
-        for (int i = 0; i < MP; i += 4) {
-          s0 += x[i];
-          s1 += x[i + 1];
-          s2 += x[i + 2];
-          s3 += x[i + 3];
-        }
-        xm = ((s0 + s1) + (s2 + s3)) / (double)M;
-#pragma unroll
-        for (int i = 0; i < MP; ++i) x[i] = (i < M) ? x[i] - xm : 0.0;
-      } else {
-        xm = a.xin[row];
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < MP; ++i) x[i] = 0.0;
-    }
-    for (long c0 = e0; c0 < e1; c0 += kChunkL) {
-      const int ne = (int)((e1 - c0 < kChunkL) ? (e1 - c0) : kChunkL);
-      __syncthreads();  // previous chunk fully consumed
-      {
-        constexpr int S2 = YS / 2;
-        for (int i = tid; i < ne * S2; i += 256) {
-          const int ee = i / S2, m2 = i - ee * S2;
-          const int k = a.idx[c0 + ee];
-          reinterpret_cast<double2*>(ye_s)[i] =
-              (m2 < M2) ? reinterpret_cast<const double2*>(a.Ye + (size_t)k * a.ye_stride)[m2] : make_double2(0.0, 0.0);
-        }
-      }
-      for (int i = tid; i < ne * kBlkCols; i += 256) {  // the folded gain scalars, as in k_sweep_gc
-        const double w = a.wts[(size_t)c0 * kBlkCols + i];
-        const double* ck = a.coef + (size_t)a.idx[c0 + i / kBlkCols] * kCoefStride;
-        const double g = (w * rM1) * ck[1];
-        ab_s[i] = make_double2(g * ck[2], g * ck[0]);
-      }
-      __syncthreads();
-      // the staged observations with a non-zero taper on any of this wave's columns, as a bit mask (wave-uniform)
-      bool mine = false;
-      if (lane < ne && any_live) {
-        const int c_lo = ncw * wave, c_hi = (c_lo + ncw < kBlkCols) ? c_lo + ncw : kBlkCols;
-        for (int c = c_lo; c < c_hi; ++c) mine = mine || (ab_s[lane * kBlkCols + c].x != 0.0);
-      }
-      unsigned long long todo = __ballot(mine);
-      if (todo == 0ull) continue;
-      const double2* abq = ab_s + (cq & (kBlkCols - 1));  // (a lane beyond the block's 16 columns holds a zero row: whatever it reads is multiplied by 0)
-      const double* yq = ye_s + (lane & 15);
-      int ee = __builtin_ctzll(todo);
-      todo &= todo - 1;
-      double2 ab = abq[ee * kBlkCols];
-      double y[NG];
-#pragma unroll
-      for (int c = 0; c < NG; ++c) y[c] = yq[ee * YS + 16 * c];
-      while (true) {
-        const int en = (todo != 0ull) ? __builtin_ctzll(todo) : ee;  // the next one (after the last: itself again, harmlessly)
-        const double dot = lane_dot<MP>(x, y, seq);      // :95
-        const double2 abn = abq[en * kBlkCols];
-        xm = __builtin_fma(ab.y, dot, xm);               // :115, :119, :130
-        const double nkb = -(ab.x * dot);                // :115, :119, :136
-        lane_update_prefetch<MP>(x, y, nkb, yq + en * YS);  // :141
-        if (todo == 0ull) break;
-        todo &= todo - 1;
-        ee = en;
-        ab = abn;
-      }
-    }
-    if (live) {  // posterior members out (assimilation.py:168), or perturbations and mean
-      double2* p = reinterpret_cast<double2*>(a.Xout + (size_t)row * M);
-      const double add = FUSED ? xm : 0.0;
-      if (M == MP) {
-#pragma unroll
-        for (int i = 0; i < MP / 2; ++i) p[i] = make_double2(x[2 * i] + add, x[2 * i + 1] + add);
-      } else {
-#pragma unroll
-        for (int i = 0; i < MP / 2; ++i)
-          if (i < M2) p[i] = make_double2(x[2 * i] + add, x[2 * i + 1] + add);
-      }
-      if (!FUSED) a.xout[row] = xm;
-    }
-  }
+
+template <int MP, bool FUSED, bool ADAPT>
+void gc_lane_launch_kernel(const GcSweepArgs& a, hipStream_t s) {
+  const dim3 grid((unsigned)(a.nblk * a.lead_split)), block(256);
+  if constexpr (ADAPT) hipLaunchKernelGGL((k_sweep_gc_lane_adapt<MP, FUSED>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((k_sweep_gc_lane<MP, FUSED>), grid, block, 0, s, a);
 }
-
-template <int MP>
+template <int MP, bool ADAPT>
 hipError_t gc_lane_launch_one(const GcSweepArgs& a, hipStream_t s) {
-  if (a.fused_members) hipLaunchKernelGGL((k_sweep_gc_lane<MP, true>), dim3((unsigned)(a.nblk * a.lead_split)), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((k_sweep_gc_lane<MP, false>), dim3((unsigned)(a.nblk * a.lead_split)), dim3(256), 0, s, a);
+  if (a.fused_members) gc_lane_launch_kernel<MP, true, ADAPT>(a, s);
+  else gc_lane_launch_kernel<MP, false, ADAPT>(a, s);
   return hipGetLastError();
 }
 
@@ -641,11 +476,17 @@ int device_cus() {
   return cus;
 }
 
-template <int NC>
+template <int NC, bool VEC, bool FUSED, int RPL, bool ADAPT>
+void gc_launch_kernel(dim3 grid, dim3 block, hipStream_t s, const GcSweepArgs& a) {
+  if constexpr (ADAPT) hipLaunchKernelGGL((k_sweep_gc_adapt<NC, VEC, FUSED, RPL>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((k_sweep_gc<NC, VEC, FUSED, RPL>), grid, block, 0, s, a);
+}
+template <int NC, bool ADAPT>
 hipError_t gc_launch(const GcSweepArgs& a0, hipStream_t s) {
   GcSweepArgs a = a0;
   const bool vec = (a.M % 2 == 0) && (a.ye_stride % 2 == 0) && aligned16(a.Xin) && aligned16(a.Xout) && aligned16(a.Ye);
-  constexpr int RPL = (NC <= 8) ? EFA_GC_RPL : (NC <= 10) ? EFA_GC_RPL_MID : (NC <= 13) ? EFA_GC_RPL_WIDE : (NC <= 16) ? EFA_GC_RPL_XWIDE : 1;  // rows per quad while they fit the register file
+  // rows per quad while they fit the register file; with the inflation update one (its per-row state and temporaries spill at more)
+  constexpr int RPL = ADAPT ? 1 : (NC <= 8) ? EFA_GC_RPL : (NC <= 10) ? EFA_GC_RPL_MID : (NC <= 13) ? EFA_GC_RPL_WIDE : (NC <= 16) ? EFA_GC_RPL_XWIDE : 1;
   // groups of slabs per column block: whole iterations of the slab loop (4 RPL slabs), as many as it takes to give
   // every CU a dozen workgroups, at most one group per iteration
   const int cus = device_cus();
@@ -657,11 +498,11 @@ hipError_t gc_launch(const GcSweepArgs& a0, hipStream_t s) {
   a.lead_split = (int)((a.n_lead + a.lead_chunk - 1) / a.lead_chunk);
   const dim3 grid((unsigned)(a.nblk * a.lead_split)), block(256);
   if (a.fused_members) {
-    if (vec) hipLaunchKernelGGL((k_sweep_gc<NC, true, true, RPL>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_sweep_gc<NC, false, true, RPL>), grid, block, 0, s, a);
+    if (vec) gc_launch_kernel<NC, true, true, RPL, ADAPT>(grid, block, s, a);
+    else gc_launch_kernel<NC, false, true, RPL, ADAPT>(grid, block, s, a);
   } else {
-    if (vec) hipLaunchKernelGGL((k_sweep_gc<NC, true, false, RPL>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_sweep_gc<NC, false, false, RPL>), grid, block, 0, s, a);
+    if (vec) gc_launch_kernel<NC, true, false, RPL, ADAPT>(grid, block, s, a);
+    else gc_launch_kernel<NC, false, false, RPL, ADAPT>(grid, block, s, a);
   }
   return hipGetLastError();
 }
@@ -715,9 +556,12 @@ hipError_t launch_sweep_gc(const GcSweepArgs& a0, hipStream_t s) {
     GcSweepArgs l = a;
     l.lead_split = (int)((l.n_lead + 15) / 16);  // groups of 16 slabs: one workgroup each
     l.lead_chunk = 16;
-    return dispatch_width((l.M + 3) / 4, WidthRange<1, kLaneMaxMembers / 4>{}, [&](auto q) { return gc_lane_launch_one<4 * q>(l, s); });
+    return dispatch_width((l.M + 3) / 4, WidthRange<1, kLaneMaxMembers / 4>{}, [&](auto q) {
+      return a.infl ? gc_lane_launch_one<4 * q, true>(l, s) : gc_lane_launch_one<4 * q, false>(l, s);
+    });
   }
-  return dispatch_width(sweep_slots(a.M) / 8, SweepChunks{}, [&](auto nc) { return gc_launch<nc>(a, s); });
+  return dispatch_width(sweep_slots(a.M) / 8, SweepChunks{},
+                        [&](auto nc) { return a.infl ? gc_launch<nc, true>(a, s) : gc_launch<nc, false>(a, s); });
 }
 
 }  // namespace efa

@@ -1,0 +1,317 @@
+// The two one-pass GC sweep kernels, included twice by efa_gcsweep.hip (inside namespace efa::<anonymous>, after the helpers they
+// use): EFA_GCK_QUAD / EFA_GCK_LANE name them and EFA_GCK_ADAPT says whether the adaptive-inflation update (Anderson 2009,
+// DESIGN.md §7c) is fused in.  Two kernel names rather than a template flag keep the plain kernels' names and code as they were.
+// No include guard: this file is meant to be included more than once.
+
+template <int NC, bool VEC, bool FUSED, int RPL>
+__global__ __launch_bounds__(256, EFA_GCK_QUAD_WAVES(NC, RPL)) void EFA_GCK_QUAD(const GcSweepArgs a) {
+  constexpr bool ADAPT = EFA_GCK_ADAPT;
+  constexpr int L = 4;
+  constexpr int S = 2 * L * NC;  // padded ye row (doubles)
+  __shared__ __align__(16) double ye_s[kChunk * S];
+  __shared__ __align__(16) double2 ab_s[kChunk * kBlkCols];  // per (staged ob, column): what scales (x . ye) in the row / in its mean
+  __shared__ __align__(16) double aw_s[ADAPT ? kChunk * kBlkCols : 1];  // ADAPT: the taper per (staged ob, column), 0 if not assimilated
+  __shared__ __align__(16) double2 ao_s[ADAPT ? 2 * kChunk : 1];         // ADAPT: the staged obs' records (adapt_ob)
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int j = lane & 3, r = lane >> 2;
+  // blockIdx.x = (position in the longest-first order) * lead_split + (group of slabs): a shard with few, long
+  // column blocks (the polar ranks of a cost-balanced split) still fills the device and has no tail of whole blocks
+  const long b = a.order[blockIdx.x / a.lead_split];
+  const int lead_lo = (int)(blockIdx.x % a.lead_split) * (int)a.lead_chunk;
+  const int lead_hi = (lead_lo + (int)a.lead_chunk < (int)a.n_lead) ? lead_lo + (int)a.lead_chunk : (int)a.n_lead;
+  // quad r of wave w: column cq of the block, slab slot sq of the group of slabs
+  const int cq = EFA_GC_COLSPLIT ? 4 * wave + (r & 3) : r;
+  const int sq = EFA_GC_COLSPLIT ? (r >> 2) : wave;
+  const long col = b * kBlkCols + cq;
+  const bool col_ok = col < a.ncol;
+  const int M = a.M;
+  const double rM1 = 1.0 / (double)(M - 1);
+  const long e0 = a.off[b], e1 = e0 + a.cnt[b];
+
+  // A quad holds RPL rows of the SAME column (slabs lead, lead + 4, ...): they share the taper and
+  // every ye row read from LDS (the quad layout delivers each ye row once per quad), and a staged
+  // chunk serves 4 RPL slabs instead of 4.
+  for (int lead0 = lead_lo; lead0 < lead_hi; lead0 += 4 * RPL) {
+    double x[RPL][2 * NC];
+    double xm[RPL];
+    double lam[RPL], sd[RPL], ss[RPL];  // ADAPT: the row's inflation and x'.x'
+    bool live[RPL];
+    long row[RPL];
+    bool any_live = false;
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+      const int lead = lead0 + sq + 4 * q;
+      live[q] = col_ok && lead < lead_hi;
+      any_live = any_live || live[q];
+      row[q] = (long)lead * a.ncol + col;
+      xm[q] = 0.0;
+      if (live[q]) {
+        load_row<L, NC, VEC>(a.Xin + (size_t)row[q] * M, M, j, x[q]);
+        if (!FUSED) xm[q] = a.xin[row[q]];
+      } else {
+#pragma unroll
+        for (int c = 0; c < 2 * NC; ++c) x[q][c] = 0.0;
+      }
+      if (FUSED) {  // prior members in: remove the ensemble mean (assimilation.py:146-147)
+        xm[q] = group_rowsum<L, NC>(x[q]) / (double)M;
+        if (ADAPT) ss[q] = group_centered_sumsq<L, NC>(x[q], xm[q], M, j);
+#pragma unroll
+        for (int c = 0; c < 2 * NC; ++c) x[q][c] -= xm[q];  // padding slots never reach the output or the dot
+      } else if (ADAPT) {
+        ss[q] = group_centered_sumsq<L, NC>(x[q], 0.0, M, j);
+      }
+      if (ADAPT) {
+        lam[q] = live[q] ? a.infl[2 * row[q]] : 1.0;
+        sd[q] = live[q] ? a.infl[2 * row[q] + 1] : 0.0;
+      }
+    }
+    for (long c0 = e0; c0 < e1; c0 += kChunk) {
+      const int ne = (int)((e1 - c0 < kChunk) ? (e1 - c0) : kChunk);
+      __syncthreads();  // previous chunk fully consumed
+      // ---- cooperative staging of ne entries
+      if (VEC) {
+        constexpr int S2 = S / 2;
+        const int M2 = M / 2;
+        for (int i = tid; i < ne * S2; i += 256) {
+          const int ee = i / S2, m2 = i - ee * S2;
+          const int k = a.idx[c0 + ee];
+          reinterpret_cast<double2*>(ye_s)[i] =
+              (m2 < M2) ? reinterpret_cast<const double2*>(a.Ye + (size_t)k * a.ye_stride)[m2] : make_double2(0.0, 0.0);
+        }
+      } else {
+        for (int i = tid; i < ne * S; i += 256) {
+          const int ee = i / S, m = i - ee * S;
+          const int k = a.idx[c0 + ee];
+          ye_s[i] = (m < M) ? a.Ye[(size_t)k * a.ye_stride + m] : 0.0;
+        }
+      }
+      // The gain scalars of ensrf.py:95-136 -- kcov = (x . ye)/(M-1), times the taper, /kdenom, times innov for the mean
+      // and times beta for the members -- do not depend on the state row: they are folded ONCE per (ob, column) here,
+      // A = w (1/(M-1)) (1/kdenom) beta and B = w (1/(M-1)) (1/kdenom) innov, instead of six dependent multiplications
+      // per row and observation in a loop that is bound by the number of fp64 instructions it issues.
+      for (int i = tid; i < ne * kBlkCols; i += 256) {
+        const double w = a.wts[(size_t)c0 * kBlkCols + i];
+        const double* ck = a.coef + (size_t)a.idx[c0 + i / kBlkCols] * kCoefStride;  // innov, 1/kdenom, beta, active
+        const double g = (w * rM1) * ck[1];
+        ab_s[i] = make_double2(g * ck[2], g * ck[0]);  // w == 0 (or an ob that is not assimilated): both exactly 0
+        if (ADAPT) aw_s[i] = (ck[3] != 0.0) ? w : 0.0;
+      }
+      if (ADAPT)
+        for (int i = tid; i < 2 * ne; i += 256) ao_s[i] = reinterpret_cast<const double2*>(a.adapt_ob + (size_t)a.idx[c0 + (i >> 1)] * 4)[i & 1];
+      __syncthreads();
+      // ---- apply the chunk to this wave's 16 RPL rows
+      for (int ee = 0; ee < ne; ++ee) {
+        const double2 ab = ab_s[ee * kBlkCols + cq];
+        if (!any_live || __ballot(ab.x != 0.0) == 0ull) continue;  // none of this wave's rows (dead slabs / zero taper)
+        double y[2 * NC];
+        lds_read_row<L, NC>(ye_s + ee * S, j, y);
+        double aw = 0.0;
+        double2 o01, o23;
+        if (ADAPT) {
+          aw = aw_s[ee * kBlkCols + cq];
+          o01 = ao_s[2 * ee];
+          o23 = ao_s[2 * ee + 1];
+        }
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+          if (RPL > 2 && lead0 + 4 * q >= lead_hi) continue;  // wave-uniform: this slot is beyond the last slab in every quad
+          const double dot = gc_dot<NC>(x[q], y);        // :95 (a dead row holds zeros: its dot, and so its update, is exactly 0)
+          xm[q] = __builtin_fma(ab.y, dot, xm[q]);       // :115, :119, :130
+          const double kb = ab.x * dot;                  // :115, :119, :136
+          if (ADAPT) {  // (each lane of the quad holds the quad's dot and x'.x': the four do the update alike)
+            anderson_update(lam[q], sd[q], aw, dot, ss[q], o01, o23, a.infl_lower, a.infl_upper, a.infl_sd_lower);
+            ss[q] = adapt_ss_after(ss[q], kb, dot, o23.y);
+          }
+#pragma unroll
+          for (int c = 0; c < 2 * NC; ++c) x[q][c] = __builtin_fma(-kb, y[c], x[q][c]);  // :141
+        }
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < RPL; ++q) {
+      if (live[q]) {
+        if (FUSED) {  // posterior members out (assimilation.py:168)
+#pragma unroll
+          for (int c = 0; c < 2 * NC; ++c) x[q][c] += xm[q];
+        }
+        store_row<L, NC, VEC>(a.Xout + (size_t)row[q] * M, M, j, x[q]);
+        if (!FUSED && j == 0) a.xout[row[q]] = xm[q];
+        if (ADAPT && j == 0) {
+          a.infl[2 * row[q]] = lam[q];
+          a.infl[2 * row[q] + 1] = sd[q];
+        }
+      }
+    }
+  }
+}
+
+template <int MP, bool FUSED>  // members padded to a multiple of 4; FUSED: prior members in, posterior members out
+__global__ __launch_bounds__(256, EFA_GCK_LANE_WAVES(MP)) void EFA_GCK_LANE(const GcSweepArgs a) {
+  constexpr bool ADAPT = EFA_GCK_ADAPT;
+  constexpr int NG = (MP + 15) / 16;  // ye registers per lane
+  constexpr int YS = 16 * NG;         // padded ye row in LDS (doubles)
+  __shared__ __align__(16) double ye_s[kChunkL * YS];
+  __shared__ __align__(16) double2 ab_s[kChunkL * kBlkCols];
+  __shared__ __align__(16) double aw_s[ADAPT ? kChunkL * kBlkCols : 1];  // ADAPT: as in k_sweep_gc
+  __shared__ __align__(16) double2 ao_s[ADAPT ? 2 * kChunkL : 1];
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  // One workgroup per (column block, group of 16 slabs), blocks longest list first, a block's groups next to each other (its
+  // list stays in L2) but starting at a different group from block to block.  (The list is staged once per group of slabs
+  // whichever workgroup takes it, so the fine split costs nothing.  The hardware deals consecutive workgroups to the eight
+  // XCDs in turn: with several groups per workgroup and unequal parts, the larger parts of every block landed on the same
+  // XCDs -- measured as up to 25 % imbalance on a polar shard; all blocks' first groups, then all second groups, ... is even
+  // but 2.5 % slower on the whole grid, the lists leaving L2 between a block's groups.)
+  const long pos = blockIdx.x / a.lead_split;
+  const long b = a.order[pos];
+  const int lead_lo = 16 * (int)((blockIdx.x % a.lead_split + pos) % a.lead_split);
+  const int lead_hi = (lead_lo + 16 < (int)a.n_lead) ? lead_lo + 16 : (int)a.n_lead;
+  const int M = a.M, M2 = M / 2;
+  const double rM1 = 1.0 / (double)(M - 1);
+  const long e0 = a.off[b], e1 = e0 + a.cnt[b];
+  const auto seq = std::make_integer_sequence<int, MP>{};
+
+  for (int lead0 = lead_lo; lead0 < lead_hi; lead0 += 16) {
+    // 16 slabs x 4 columns per wave; the last group of a block: the next power of two of what is left, more columns per wave
+    const int rem = lead_hi - lead0;
+    const int lg_cols = (rem > 8) ? 2 : (rem > 4) ? 3 : (rem > 2) ? 4 : (rem > 1) ? 5 : 6;
+    const int ncw = 1 << lg_cols;                 // columns per wave
+    const int cq = (lane & (ncw - 1)) + ncw * wave;
+    const int lead = lead0 + (lane >> lg_cols);
+    const long col = b * kBlkCols + cq;
+    const bool live = cq < kBlkCols && col < a.ncol && lead < lead_hi;
+    const bool any_live = __ballot(live) != 0ull;
+    const long row = (long)lead * a.ncol + col;
+    double x[MP];
+    double xm = 0.0;
+    double lam = 1.0, sd = 0.0, ss = 0.0;  // ADAPT: the row's inflation and x'.x'
+    if (live) {
+      const double2* p = reinterpret_cast<const double2*>(a.Xin + (size_t)row * M);
+      if (M == MP) {
+#pragma unroll
+        for (int i = 0; i < MP / 2; ++i) {
+          const double2 v = p[i];
+          x[2 * i] = v.x;
+          x[2 * i + 1] = v.y;
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < MP / 2; ++i) {
+          const double2 v = (i < M2) ? p[i] : make_double2(0.0, 0.0);
+          x[2 * i] = v.x;
+          x[2 * i + 1] = v.y;
+        }
+      }
+      if (FUSED) {  // prior members in: remove the ensemble mean (assimilation.py:146-147)
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+#pragma unroll
+        for (int i = 0; i < MP; i += 4) {
+          s0 += x[i];
+          s1 += x[i + 1];
+          s2 += x[i + 2];
+          s3 += x[i + 3];
+        }
+        xm = ((s0 + s1) + (s2 + s3)) / (double)M;
+#pragma unroll
+        for (int i = 0; i < MP; ++i) x[i] = (i < M) ? x[i] - xm : 0.0;
+      } else {
+        xm = a.xin[row];
+      }
+      if (ADAPT) {
+        lam = a.infl[2 * row];
+        sd = a.infl[2 * row + 1];
+        double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
+#pragma unroll
+        for (int i = 0; i < MP; i += 4) {  // (padding slots hold 0)
+          q0 = __builtin_fma(x[i], x[i], q0);
+          q1 = __builtin_fma(x[i + 1], x[i + 1], q1);
+          q2 = __builtin_fma(x[i + 2], x[i + 2], q2);
+          q3 = __builtin_fma(x[i + 3], x[i + 3], q3);
+        }
+        ss = (q0 + q1) + (q2 + q3);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < MP; ++i) x[i] = 0.0;
+    }
+    for (long c0 = e0; c0 < e1; c0 += kChunkL) {
+      const int ne = (int)((e1 - c0 < kChunkL) ? (e1 - c0) : kChunkL);
+      __syncthreads();  // previous chunk fully consumed
+      {
+        constexpr int S2 = YS / 2;
+        for (int i = tid; i < ne * S2; i += 256) {
+          const int ee = i / S2, m2 = i - ee * S2;
+          const int k = a.idx[c0 + ee];
+          reinterpret_cast<double2*>(ye_s)[i] =
+              (m2 < M2) ? reinterpret_cast<const double2*>(a.Ye + (size_t)k * a.ye_stride)[m2] : make_double2(0.0, 0.0);
+        }
+      }
+      for (int i = tid; i < ne * kBlkCols; i += 256) {  // the folded gain scalars, as in k_sweep_gc
+        const double w = a.wts[(size_t)c0 * kBlkCols + i];
+        const double* ck = a.coef + (size_t)a.idx[c0 + i / kBlkCols] * kCoefStride;
+        const double g = (w * rM1) * ck[1];
+        ab_s[i] = make_double2(g * ck[2], g * ck[0]);
+        if (ADAPT) aw_s[i] = (ck[3] != 0.0) ? w : 0.0;
+      }
+      if (ADAPT)
+        for (int i = tid; i < 2 * ne; i += 256) ao_s[i] = reinterpret_cast<const double2*>(a.adapt_ob + (size_t)a.idx[c0 + (i >> 1)] * 4)[i & 1];
+      __syncthreads();
+      // the staged observations with a non-zero taper on any of this wave's columns, as a bit mask (wave-uniform)
+      bool mine = false;
+      if (lane < ne && any_live) {
+        const int c_lo = ncw * wave, c_hi = (c_lo + ncw < kBlkCols) ? c_lo + ncw : kBlkCols;
+        for (int c = c_lo; c < c_hi; ++c) mine = mine || (ab_s[lane * kBlkCols + c].x != 0.0);
+      }
+      unsigned long long todo = __ballot(mine);
+      if (todo == 0ull) continue;
+      const double2* abq = ab_s + (cq & (kBlkCols - 1));  // (a lane beyond the block's 16 columns holds a zero row: whatever it reads is multiplied by 0)
+      const double* yq = ye_s + (lane & 15);
+      int ee = __builtin_ctzll(todo);
+      todo &= todo - 1;
+      double2 ab = abq[ee * kBlkCols];
+      double y[NG];
+#pragma unroll
+      for (int c = 0; c < NG; ++c) y[c] = yq[ee * YS + 16 * c];
+      while (true) {
+        const int en = (todo != 0ull) ? __builtin_ctzll(todo) : ee;  // the next one (after the last: itself again, harmlessly)
+        const double dot = lane_dot<MP>(x, y, seq);      // :95
+        const double2 abn = abq[en * kBlkCols];
+        xm = __builtin_fma(ab.y, dot, xm);               // :115, :119, :130
+        const double nkb = -(ab.x * dot);                // :115, :119, :136
+        if (ADAPT) {
+          lane_update<MP>(x, y, nkb);  // :141
+          const double2 o23 = ao_s[2 * ee + 1];
+          anderson_update(lam, sd, aw_s[ee * kBlkCols + (cq & (kBlkCols - 1))], dot, ss, ao_s[2 * ee], o23, a.infl_lower, a.infl_upper,
+                          a.infl_sd_lower);
+          ss = adapt_ss_after(ss, ab.x * dot, dot, o23.y);
+#pragma unroll
+          for (int c = 0; c < NG; ++c) y[c] = yq[en * YS + 16 * c];
+        } else {
+          lane_update_prefetch<MP>(x, y, nkb, yq + en * YS);  // :141
+        }
+        if (todo == 0ull) break;
+        todo &= todo - 1;
+        ee = en;
+        ab = abn;
+      }
+    }
+    if (live) {  // posterior members out (assimilation.py:168), or perturbations and mean
+      double2* p = reinterpret_cast<double2*>(a.Xout + (size_t)row * M);
+      const double add = FUSED ? xm : 0.0;
+      if (M == MP) {
+#pragma unroll
+        for (int i = 0; i < MP / 2; ++i) p[i] = make_double2(x[2 * i] + add, x[2 * i + 1] + add);
+      } else {
+#pragma unroll
+        for (int i = 0; i < MP / 2; ++i)
+          if (i < M2) p[i] = make_double2(x[2 * i] + add, x[2 * i + 1] + add);
+      }
+      if (!FUSED) a.xout[row] = xm;
+      if (ADAPT) {
+        a.infl[2 * row] = lam;
+        a.infl[2 * row + 1] = sd;
+      }
+    }
+  }
+}

@@ -161,6 +161,10 @@ struct GcSweepArgs {
   int fused_members;
   int lead_split;       // set by the launcher: groups of slabs a column block is cut into (one workgroup each)
   long lead_chunk;      // slabs per group
+  // adaptive inflation (Anderson 2009); infl == null: off
+  double* infl;             // [n_lead*ncol][2] (mean, sd) of every state row, updated in place
+  const double* adapt_ob;   // [P][4] {D^2, prior var, ob error variance, y'.y'} (launch_adapt_obs)
+  double infl_lower, infl_upper, infl_sd_lower;
 };
 long gc_num_blocks(long ncol);
 // list build in one pass: upper bounds + device prefix sum (off[nblk] = capacity needed), then the entries
@@ -205,6 +209,12 @@ hipError_t launch_relax_fold(int M, double alpha, const double* T, double* Tout,
 hipError_t launch_row_spread(long rows, int M, const double* X, double* ss, hipStream_t s);
 hipError_t launch_relax_rows(long rows, int M, int rtpp, double alpha, double* X, const double* ss, const double* prior,
                              hipStream_t s);
+
+// adaptive inflation (efa_adapt.hip): X[row] <- mean + sqrt(field[row][0]) (X[row] - mean) (rows with field 1 untouched);
+// the per-ob scalars the sweep's update reads, from Phase A's records and diagnostics
+hipError_t launch_inflate_rows(long rows, int M, double* X, const double* field, hipStream_t s);
+hipError_t launch_adapt_obs(long P, int M, const double* coef, const double* prior_var, const double* ob_error, const double* Ye,
+                            long ye_stride, double* out /* [P][4] */, hipStream_t s);
 
 hipError_t launch_form_perts(long rows, int M, const double* X, double scale, double* xm,
                              double* Xp, hipStream_t s);

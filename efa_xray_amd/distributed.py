@@ -228,10 +228,13 @@ class ShardedEnSRF(object):
         eng.forward_stencil(self.rows_local, M, X_local, lidx, lwts, HX)
         return HX
 
-    def assimilate(self, X_local, post_local, HX, ob, grid_lat=None, grid_lon=None, rtps=None, rtpp=None):
+    def assimilate(self, X_local, post_local, HX, ob, grid_lat=None, grid_lon=None, rtps=None, rtpp=None,
+                   adaptive_inflation=None):
         """Stage 2, after HX has been summed over the shards: obs-space priors, Phase A
         (replicated: identical on every rank) and the sweep of this shard's rows.  `rtps` / `rtpp`:
         posterior relaxation of the shard's rows as in `EnSRF` (row-local: no communication)."""
+        if adaptive_inflation is not None:
+            raise ValueError("ShardedEnSRF does not support adaptive_inflation (out of scope: use EnSRF on one GPU)")
         eng, M = self.engine, self.M
         relax = relaxation_setting(rtps, rtpp)
         if hasattr(eng, "set_relaxation"):
@@ -252,7 +255,9 @@ class ShardedEnSRF(object):
         return diag
 
     def update(self, X_local, post_local, sten_idx, sten_wts, ob, grid_lat=None, grid_lon=None, inflation=None,
-               rtps=None, rtpp=None):
+               rtps=None, rtpp=None, adaptive_inflation=None):
+        if adaptive_inflation is not None:
+            raise ValueError("ShardedEnSRF does not support adaptive_inflation (out of scope: use EnSRF on one GPU)")
         HX = self.partial_estimates(X_local, sten_idx, sten_wts, inflation)
         self.all_reduce_sum(HX)                                            # the one exchange step
         return self.assimilate(X_local, post_local, HX, ob, grid_lat, grid_lon, rtps=rtps, rtpp=rtpp)

@@ -116,6 +116,25 @@ int efa_ctx_get_option(efa_ctx *ctx, const char *key, long *value);
 #define EFA_RELAX_RTPP 1
 #define EFA_RELAX_RTPS 2
 int efa_ctx_set_relaxation(efa_ctx *ctx, int kind, double alpha);
+
+/* ---- spatially varying adaptive inflation (Anderson 2009) --
+ * field_dev: [rows][2] doubles on the device, (mean lambda, sd s) of each
+ * state row's VARIANCE inflation factor, in the state's row order.
+ * efa_inflate_rows_dev inflates the prior in place, before the forward
+ * operator: x_im <- mean_i + sqrt(lambda_i) (x_im - mean_i); rows with
+ * lambda == 1 are left bit for bit as they are.
+ * efa_ctx_set_adaptive_inflation is context state like the relaxation: while
+ * a field is set, every later state phase (efa_state_phase_dev,
+ * efa_state_cycle_dev, efa_ensrf_cycle_dev, efa_ensrf_update_dev,
+ * efa_ensrf_update) updates it in place, ob by ob in serial order, from the
+ * innovations, fused into the one-pass GC sweep; the posterior is the one of
+ * the prior it is given.  The call fails (EFA_ERR_INVALID) unless the cycle is
+ * GC-localised, option "gc_onepass" is 1 and the state phase has `rows` rows.
+ * Bounds: 0 < lower <= upper (finite), sd_lower >= 0 (DART: 1, 1e6, 0).
+ * field_dev NULL turns it off.  The field must stay allocated while set. */
+int efa_inflate_rows_dev(efa_ctx *ctx, long rows, int M, double *X_dev, const double *field_dev);
+int efa_ctx_set_adaptive_inflation(efa_ctx *ctx, double *field_dev, long rows, double lower, double upper,
+                                   double sd_lower);
 int efa_ctx_synchronize(efa_ctx *ctx);
 
 /* ---- device memory for callers without their own allocator -------------*/
