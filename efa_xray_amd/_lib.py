@@ -49,6 +49,8 @@ SIGNATURES = {
     "efa_inflate_rows_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "efa_ctx_set_adaptive_inflation": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_double,
                                                       ctypes.c_double, ctypes.c_double]),
+    "efa_ctx_set_vertical_localization": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, c_double_p, ctypes.c_long,
+                                                         c_double_p, c_double_p]),
     "efa_ctx_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
     "efa_malloc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, c_void_pp]),
     "efa_free": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
@@ -296,6 +298,20 @@ class Context(object):
         (mean, sd) array updated in place, or None to turn it off."""
         _check(self.lib, self.lib.efa_ctx_set_adaptive_inflation(self.handle, self._addr(field), int(rows), float(lower),
                                                                  float(upper), float(sd_lower)))
+
+    def set_vertical_localization(self, lead_vert=None, ob_vert=None, ob_vert_halfwidth=None):
+        """Vertical localisation of every later GC cycle on this context: host arrays lead_vert [n_lead] and
+        ob_vert / ob_vert_halfwidth [P], NaN meaning no vertical taper; lead_vert None turns it off."""
+        if lead_vert is None:
+            _check(self.lib, self.lib.efa_ctx_set_vertical_localization(self.handle, 0, None, 0, None, None))
+            return
+        lv = np.ascontiguousarray(lead_vert, dtype=np.float64).reshape(-1)
+        ov = np.ascontiguousarray(ob_vert, dtype=np.float64).reshape(-1)
+        oh = np.ascontiguousarray(ob_vert_halfwidth, dtype=np.float64).reshape(-1)
+        if ov.shape != oh.shape:
+            raise ValueError("ob_vert and ob_vert_halfwidth differ in length: %d and %d" % (ov.size, oh.size))
+        _check(self.lib, self.lib.efa_ctx_set_vertical_localization(self.handle, lv.size, _dp(lv), ov.size,
+                                                                    _dp(ov) if ov.size else None, _dp(oh) if oh.size else None))
 
     def inflate_rows(self, rows, M, X, field):
         """X[row] <- mean + sqrt(field[row][0]) (X[row] - mean), in place on the device."""

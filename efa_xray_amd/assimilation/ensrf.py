@@ -17,6 +17,7 @@ import numpy as np
 from efa_xray_amd import _lib
 from efa_xray_amd.assimilation.adaptive_inflation import AdaptiveInflation
 from efa_xray_amd.assimilation.assimilation import Assimilation
+from efa_xray_amd.observation.observation import check_vert_halfwidth
 
 
 def relaxation_setting(rtps=None, rtpp=None):
@@ -36,6 +37,43 @@ def relaxation_setting(rtps=None, rtpp=None):
     return _lib.RELAX_NONE, 0.0
 
 
+def vertical_setting(state, vert_coord, loc, adaptive=None):
+    """vert_coord as a float64 (nvars, ntimes) array, or None; ValueError on a setting that is not supported."""
+    if vert_coord is None:
+        return None
+    if loc != 'GC':
+        raise ValueError("vert_coord needs loc='GC' (the vertical factor multiplies the Gaspari-Cohn taper); got loc=%r" % (loc,))
+    if adaptive is not None:
+        raise ValueError("vert_coord cannot be combined with adaptive_inflation (not supported, DESIGN.md 7d)")
+    try:
+        z = np.array(vert_coord, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("vert_coord must be a float array of shape (nvars, ntimes)")
+    want = (state.nvars(), state.ntimes())
+    if z.shape != want:
+        raise ValueError("vert_coord has shape %r but the state has (nvars, ntimes) = %r" % (z.shape, want))
+    if np.isinf(z).any():
+        raise ValueError("vert_coord holds an infinite value (NaN marks a slab that is not localised vertically)")
+    return z
+
+
+def ob_vertical(obs):
+    """(vert, vert half-width) of every ob as float64 arrays, NaN where missing; ValueError on a bad half-width."""
+    ov = np.full(len(obs), np.nan)
+    oh = np.full(len(obs), np.nan)
+    for k, ob in enumerate(obs):
+        c = getattr(ob, "vert_localize_radius", None)
+        if c is not None:
+            oh[k] = check_vert_halfwidth(c, "observation %d: vert_localize_radius" % k)
+        z = getattr(ob, "vert", None)
+        if z is not None:
+            z = float(z)
+            if np.isinf(z):
+                raise ValueError("observation %d: vert=%r is infinite" % (k, ob.vert))
+            ov[k] = z
+    return ov, oh
+
+
 class EnSRF(Assimilation):
     def __init__(self, state, obs, nproc=1, inflation=None, verbose=True, loc=False, **kw):
         """Extra keyword-only options (all default to reference behaviour):
@@ -48,6 +86,10 @@ class EnSRF(Assimilation):
         adaptive_inflation -- an AdaptiveInflation: its field inflates the prior and is updated
                     from the innovations by every update() (Anderson 2009); needs
                     loc='GC' and excludes inflation=
+        vert_coord -- vertical localisation: float array (nvars, ntimes) in
+                    state.vars() order, the vertical coordinate of each 2-D slab (NaN: not
+                    localised vertically); obs taper with their `vert` and `vert_localize_radius`.
+                    Needs loc='GC'; excludes adaptive_inflation.  None: off
         """
         device = kw.pop("device", 0)
         self.obs_batch = kw.pop("obs_batch", None)
@@ -55,6 +97,7 @@ class EnSRF(Assimilation):
         rtps = kw.pop("rtps", None)
         rtpp = kw.pop("rtpp", None)
         adaptive = kw.pop("adaptive_inflation", None)
+        vert_coord = kw.pop("vert_coord", None)
         if kw:
             raise TypeError("unexpected keyword arguments %r" % sorted(kw))
         self.relaxation = relaxation_setting(rtps, rtpp)
@@ -68,6 +111,9 @@ class EnSRF(Assimilation):
                 raise ValueError("adaptive_inflation and inflation= are exclusive: the adaptive field is the prior inflation")
             adaptive.check_state(state)
         self.adaptive_inflation = adaptive
+        self.vert_coord = vertical_setting(state, vert_coord, loc, adaptive)
+        if self.vert_coord is not None:
+            ob_vertical(obs)
         Assimilation.__init__(self, state, obs, nproc, inflation, verbose, device=device)
         self.loc = loc
         self.last_timing = None
@@ -113,6 +159,14 @@ class EnSRF(Assimilation):
         ctx.set_option("path", path)
         ctx.set_relaxation(*self.relaxation)   # every call: the context is shared per device
         ctx.set_adaptive_inflation(None)        # set by update() around its own cycle only
+        if self.vert_coord is None:             # every call as well, "off" included
+            ctx.set_vertical_localization(None)
+        else:
+            if self.vert_coord.shape != (self.prior.nvars(), self.prior.ntimes()):
+                raise ValueError("vert_coord has shape %r but the state has (nvars, ntimes) = %r"
+                                 % (self.vert_coord.shape, (self.prior.nvars(), self.prior.ntimes())))
+            ov, oh = ob_vertical(self.obs)
+            ctx.set_vertical_localization(self.vert_coord.reshape(-1), ov, oh)
 
     # ------------------------------------------------------------------
     def update(self):

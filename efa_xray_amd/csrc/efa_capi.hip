@@ -190,6 +190,15 @@ struct efa_ctx {
   long ai_rows = 0;
   double ai_lower = 1.0, ai_upper = 1e6, ai_sd_lower = 0.0;
   DevBuf ai_ob;               // [P][4] what the sweep's update reads of each ob (launch_adapt_obs)
+  // --- vertical localisation (efa_ctx_set_vertical_localization) -----------------------------------
+  bool vl_on = false;
+  bool vl_any = false;          // some ob carries vertical information (else every factor is 1 and the plain kernels run)
+  long vl_nlead = 0, vl_P = 0;
+  std::vector<double> vl_host;  // [n_lead slab coordinates | P ob coordinates | P half-widths] as on the device (NaN: 1 as half-width)
+  long vl_serial = 0;           // bumped whenever the setting changes: part of the obs geometry (geo_serial)
+  long geo_vl_serial = 0;       // ... the value the current geometry was compared with
+  DevBuf vl_dev;                // device copy of vl_host
+  DevBuf vl_W;                  // the per-batch sweep's taper table [nb][R] (launch_obs_taper_rows)
   // --- f1: interpolation stencils -------------------------------------------------
   DevBuf fs_idx, fs_wts;  // efa_forward_stencil_dev staging
   DevBuf f_glat, f_glon, f_sl, f_cl, f_valids, f_var, f_time, f_lat, f_lon, f_near, f_idx, f_wts, f_status;
@@ -397,6 +406,26 @@ int check_adaptive(const efa_ctx* c, int loc_mode, long rows) {
   return EFA_OK;
 }
 
+// ---- vertical localisation (efa_vloc.hip and the _vloc sweep kernels) -------------------------------------------------------
+// While it is set, every call must be a GC cycle of the P obs and n_lead slabs it was set for, on the one-pass state sweep (the
+// per-batch state sweep has no vertical factor) and without adaptive inflation (no combined kernel).  n_lead < 0: not checked.
+int check_vloc(const efa_ctx* c, int loc_mode, long P, long n_lead) {
+  if (!c->vl_on) return EFA_OK;
+  if (loc_mode != EFA_LOC_GC)
+    return fail(EFA_ERR_INVALID, "vertical localisation is set: it needs GC localisation (loc_mode %d is not EFA_LOC_GC)", loc_mode);
+  if (!c->gc_onepass)
+    return fail(EFA_ERR_INVALID, "vertical localisation is set: it needs the one-pass GC sweep (option gc_onepass is 0)");
+  if (c->ai_field) return fail(EFA_ERR_INVALID, "vertical localisation is set: adaptive inflation cannot be combined with it");
+  if (P != c->vl_P) return fail(EFA_ERR_INVALID, "vertical localisation was set for %ld observations, the call has %ld", c->vl_P, P);
+  if (n_lead >= 0 && n_lead != c->vl_nlead)
+    return fail(EFA_ERR_INVALID, "vertical localisation was set for %ld slabs, the call has n_lead=%ld", c->vl_nlead, n_lead);
+  return EFA_OK;
+}
+bool vl_active(const efa_ctx* c) { return c->vl_on && c->vl_any; }
+const double* vl_lead(const efa_ctx* c) { return c->vl_dev.as<double>(); }
+const double* vl_obvert(const efa_ctx* c) { return c->vl_dev.as<double>() + c->vl_nlead; }
+const double* vl_obvhw(const efa_ctx* c) { return c->vl_dev.as<double>() + c->vl_nlead + c->vl_P; }
+
 // ---- Phase A ---------------------------------------------------------------
 // One obs_phase call: its arguments and the workspace layout that the steps below share.
 struct ObsCall {
@@ -461,8 +490,9 @@ int stage_obs_inputs(efa_ctx* c, ObsCall& a, const double* ob_value, const doubl
     const size_t nb8 = (size_t)P * sizeof(double);
     const bool same = (long)c->geo_lat.size() == P && std::memcmp(c->geo_lat.data(), ob_lat, nb8) == 0 &&
                       std::memcmp(c->geo_lon.data(), ob_lon, nb8) == 0 && std::memcmp(c->geo_hw.data(), ob_hw, nb8) == 0 &&
-                      std::memcmp(c->geo_assim.data(), ob_assim, (size_t)P) == 0;
+                      std::memcmp(c->geo_assim.data(), ob_assim, (size_t)P) == 0 && c->geo_vl_serial == c->vl_serial;
     if (!same) {
+      c->geo_vl_serial = c->vl_serial;  // (the vertical setting is part of the geometry: the obs-obs table carries its factor)
       c->geo_lat.assign(ob_lat, ob_lat + P);
       c->geo_lon.assign(ob_lon, ob_lon + P);
       c->geo_hw.assign(ob_hw, ob_hw + P);     // (sanitised above)
@@ -586,6 +616,14 @@ int sweep_rows(efa_ctx* c, const ObsCall& a, long b0, int nb, const double* Ye, 
   sw.coef = c->coef.as<double>() + (size_t)b0 * kCoefStride;
   sw.nb = nb;
   sw.taper_mode = (a.loc_mode == EFA_LOC_GC) ? kTaperObs : kTaperNone;
+  if (a.loc_mode == EFA_LOC_GC && vl_active(c)) {  // horizontal x vertical taper of the batch against every row, in table mode
+    EFA_TRY(c->vl_W.reserve((size_t)nb * a.R * sizeof(double)));
+    EFA_HIP(launch_obs_taper_rows(b0, nb, a.R, a.P, c->ob_lat.as<double>(), c->ob_lon.as<double>(), c->ob_hw.as<double>(),
+                                  vl_obvert(c), vl_obvhw(c), c->vl_W.as<double>(), c->stream));
+    sw.taper_mode = kTaperTable;
+    sw.W = c->vl_W.as<double>();
+    sw.ncol = a.R;  // (row j of the block reads column j of the table)
+  }
   sw.row_lat = c->ob_lat.as<double>();
   sw.row_lon = c->ob_lon.as<double>();
   sw.ob_lat = c->ob_lat.as<double>() + b0;
@@ -605,9 +643,11 @@ long active_in(const ObsCall& a, long b0, int nb) {
 }
 
 // obs [w0, w1) by the per-batch kernels (k_diag on the batch's own rows, k_sweep on every other row of the block)
+// (With vertical localisation one ob per batch: k_diag's in-batch taper is horizontal only, and an ob's taper against itself is 1.)
 int batch_window(efa_ctx* c, const ObsCall& a, long w0, long w1) {
-  for (long b0 = w0; b0 < w1; b0 += a.B) {
-    const int nb = (int)((w1 - b0 < a.B) ? (w1 - b0) : a.B);
+  const long B = (a.loc_mode == EFA_LOC_GC && vl_active(c)) ? 1 : a.B;
+  for (long b0 = w0; b0 < w1; b0 += B) {
+    const int nb = (int)((w1 - b0 < B) ? (w1 - b0) : B);
     DiagArgs d{};
     d.Yp = a.Yw;
     d.ym = a.ymw;
@@ -698,6 +738,7 @@ int window_pipe_args(efa_ctx* c, const ObsCall& a, const Window& win, PipeArgs* 
     if (!tw_ok) {
       EFA_HIP(launch_obs_taper_matrix(Pw, Rw, c->ob_lat.as<double>() + w0, c->ob_lon.as<double>() + w0, c->ob_hw.as<double>() + w0,
                                       c->gc_obtrig.as<double>(), c->tw_mat.as<double>(), s));
+      if (vl_active(c)) EFA_HIP(launch_obs_taper_vert(Pw, Rw, vl_obvert(c) + w0, vl_obvhw(c) + w0, c->tw_mat.as<double>(), s));
       c->tw_serial = win.direct ? c->geo_serial : -1;  // (a window's table is not the whole block's)
       c->tw_Pw = Pw;
       c->tw_Rw = Rw;
@@ -906,6 +947,7 @@ int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const d
               double* post_mean, double* post_var, uint8_t* assimilated) {
   EFA_TRY(check_common(M, P));
   if (loc_mode != EFA_LOC_NONE && loc_mode != EFA_LOC_GC) return fail(EFA_ERR_INVALID, "loc_mode %d", loc_mode);
+  EFA_TRY(check_vloc(c, loc_mode, P, -1));
   c->have_traj = false;
   c->M = M;
   c->P = P;
@@ -1110,6 +1152,11 @@ int state_gc_onepass(efa_ctx* c, const double* xm_in, const double* Xp_in, doubl
     g.infl_upper = c->ai_upper;
     g.infl_sd_lower = c->ai_sd_lower;
   }
+  if (vl_active(c)) {
+    g.lead_vert = vl_lead(c);
+    g.ob_vert = vl_obvert(c);
+    g.ob_vhw = vl_obvhw(c);
+  }
   EFA_HIP(launch_sweep_gc(g, s));
   c->state_launches++;
   return EFA_OK;
@@ -1170,6 +1217,7 @@ int state_phase(efa_ctx* c, long rows, int M, const double* xm_in, const double*
   if (M != c->M) return fail(EFA_ERR_INVALID, "M=%d differs from the obs phase's M=%d", M, c->M);
   if (rows < 0) return fail(EFA_ERR_INVALID, "negative row count");
   EFA_TRY(check_adaptive(c, c->loc_mode, rows));
+  EFA_TRY(check_vloc(c, c->loc_mode, c->P, n_lead));
   reset_state_phase(c);
   if (rows == 0) return EFA_OK;
   if (!xm_in || !Xp_in || !xm_out || !Xp_out) return fail(EFA_ERR_INVALID, "null state pointer");
@@ -1300,7 +1348,7 @@ int efa_ctx_destroy(efa_ctx* c) {
   DevBuf* bufs[] = {&c->ob_pack, &c->out_pack, &c->Ye_rec, &c->coef, &c->ob_val, &c->ob_err, &c->ob_asm, &c->ob_lat, &c->ob_lon, &c->ob_hw, &c->ob_errsq,
                     &c->d_prior_mean, &c->d_prior_var, &c->d_post_mean, &c->d_post_var, &c->d_assimilated,
                     &c->Yw, &c->ymw, &c->win_Y, &c->win_m, &c->traj, &c->tw_mat, &c->status, &c->dbg, &c->W, &c->gc_cnt, &c->gc_ub, &c->gc_order, &c->gc_obtrig, &c->gc_off, &c->gc_idx, &c->gc_wts, &c->gc_pairs, &c->glat, &c->glon, &c->xm_ws, &c->fs_idx, &c->fs_wts, &c->f_glat, &c->f_glon, &c->f_sl, &c->f_cl, &c->f_valids, &c->f_var, &c->f_time, &c->f_lat, &c->f_lon, &c->f_near, &c->f_idx, &c->f_wts, &c->f_status, &c->h_xm, &c->h_Xp, &c->h_ym, &c->h_Yp,
-                    &c->gcc_lat, &c->gcc_lon, &c->gcc_oblat, &c->gcc_oblon, &c->gcc_obhw, &c->gcc_coef, &c->gcc_trig, &c->gcc_cnt, &c->gcc_pairs, &c->ai_ob};
+                    &c->gcc_lat, &c->gcc_lon, &c->gcc_oblat, &c->gcc_oblon, &c->gcc_obhw, &c->gcc_coef, &c->gcc_trig, &c->gcc_cnt, &c->gcc_pairs, &c->ai_ob, &c->vl_dev, &c->vl_W};
   for (DevBuf* b : bufs) b->release();
   for (int i = 0; i < 7; ++i)
     if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -1402,6 +1450,46 @@ int efa_ctx_set_adaptive_inflation(efa_ctx* c, double* field_dev, long rows, dou
   c->ai_lower = lower;
   c->ai_upper = upper;
   c->ai_sd_lower = sd_lower;
+  return EFA_OK;
+}
+
+int efa_ctx_set_vertical_localization(efa_ctx* c, long n_lead, const double* lead_vert, long P, const double* ob_vert,
+                                      const double* ob_vert_halfwidth) {
+  EFA_TRY(use(c));
+  if (!lead_vert) {
+    if (c->vl_on) c->vl_serial++;
+    c->vl_on = false;
+    return EFA_OK;
+  }
+  if (n_lead <= 0) return fail(EFA_ERR_INVALID, "vertical localisation: n_lead=%ld must be > 0", n_lead);
+  if (P < 0) return fail(EFA_ERR_INVALID, "vertical localisation: negative observation count");
+  if (P > 0 && (!ob_vert || !ob_vert_halfwidth)) return fail(EFA_ERR_INVALID, "vertical localisation: null ob_vert/ob_vert_halfwidth");
+  std::vector<double> v((size_t)(n_lead + 2 * P));
+  bool any = false;
+  for (long i = 0; i < n_lead; ++i) {
+    if (std::isinf(lead_vert[i])) return fail(EFA_ERR_INVALID, "vertical localisation: slab %ld has an infinite coordinate", i);
+    v[i] = lead_vert[i];
+  }
+  for (long k = 0; k < P; ++k) {
+    const double z = ob_vert[k], h = ob_vert_halfwidth[k];
+    if (std::isinf(z)) return fail(EFA_ERR_INVALID, "vertical localisation: observation %ld has an infinite coordinate", k);
+    const bool none = std::isnan(z) || std::isnan(h);  // either missing: no vertical taper for this ob
+    if (!none && !(std::isfinite(h) && h > 0.0))
+      return fail(EFA_ERR_INVALID, "vertical localisation: observation %ld has half-width %g (must be finite and > 0, or NaN)", k, h);
+    any = any || !none;
+    v[n_lead + k] = none ? std::nan("") : z;
+    v[n_lead + P + k] = none ? 1.0 : h;
+  }
+  if (c->vl_on && c->vl_nlead == n_lead && c->vl_P == P && std::memcmp(c->vl_host.data(), v.data(), v.size() * sizeof(double)) == 0)
+    return EFA_OK;  // unchanged: nothing to copy, the geometry cache stays valid
+  EFA_TRY(h2d(c, c->vl_dev, v.data(), v.size() * sizeof(double)));
+  EFA_HIP(hipStreamSynchronize(c->stream));  // (v is gone on return)
+  c->vl_host.swap(v);
+  c->vl_nlead = n_lead;
+  c->vl_P = P;
+  c->vl_on = true;
+  c->vl_any = any;
+  c->vl_serial++;
   return EFA_OK;
 }
 
@@ -1630,6 +1718,7 @@ int efa_state_cycle_dev(efa_ctx* c, long rows, int M, const double* X_dev, doubl
   if (!c->have_traj) return fail(EFA_ERR_INVALID, "efa_state_cycle_dev called before efa_obs_phase_dev");
   if (M != c->M) return fail(EFA_ERR_INVALID, "M=%d differs from the obs phase's M=%d", M, c->M);
   EFA_TRY(check_adaptive(c, c->loc_mode, rows));
+  EFA_TRY(check_vloc(c, c->loc_mode, c->P, n_lead));
   reset_state_phase(c);
   if (rows <= 0) return rows == 0 ? EFA_OK : fail(EFA_ERR_INVALID, "negative row count");
   if (!X_dev || !post_dev) return fail(EFA_ERR_INVALID, "null state pointer");
@@ -1662,6 +1751,7 @@ int efa_ensrf_update_dev(efa_ctx* c, long rows, int M, long P, double* xm_dev, d
                          double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated) {
   EFA_TRY(use(c));
   EFA_TRY(check_adaptive(c, loc_mode, rows));
+  EFA_TRY(check_vloc(c, loc_mode, P, n_lead));
   EFA_TRY(obs_phase(c, M, P, ym_dev, Yp_dev, ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon,
                     ob_halfwidth_km, prior_mean, prior_var, post_mean, post_var, assimilated));
   EFA_TRY(state_phase(c, rows, M, xm_dev, Xp_dev, xm_dev, Xp_dev, grid_lat, grid_lon, ncol, n_lead));
@@ -1678,6 +1768,7 @@ int efa_ensrf_cycle_dev(efa_ctx* c, long rows, int M, long P, const double* X_de
   if (rows < 0) return fail(EFA_ERR_INVALID, "negative row count");
   if (rows > 0 && (!X_dev || !post_dev)) return fail(EFA_ERR_INVALID, "null state pointer");
   EFA_TRY(check_adaptive(c, loc_mode, rows));
+  EFA_TRY(check_vloc(c, loc_mode, P, n_lead));
   // Phase B may go into the stream before Phase A's status is known only if a wrong guess cannot cost the prior:
   // separate prior and posterior buffers (a redone Phase A needs the transform run again on the untouched prior)
   const char* xb = reinterpret_cast<const char*>(X_dev);

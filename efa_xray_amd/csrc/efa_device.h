@@ -52,6 +52,12 @@ __device__ __forceinline__ double gaspari_cohn(double dist_km, double halfwidth_
   return 0.0;  // r >= 2 or NaN
 }
 
+// Vertical factor of a (row, ob) pair: the same taper of |z_row - z_k| with ob k's vertical half-width, and 1
+// when either coordinate is NaN (no vertical information).  The host hands NaN coordinates a half-width of 1.
+__device__ __forceinline__ double vert_factor(double z_row, double z_ob, double halfwidth) {
+  return (z_row == z_row && z_ob == z_ob) ? gaspari_cohn(fabs(z_row - z_ob), halfwidth) : 1.0;
+}
+
 // Sum over the 4 lanes of a quad (lanes 4q..4q+3); every lane gets the total.
 // DPP quad_perm butterflies on the two 32-bit halves of the double.
 __device__ __forceinline__ double quad_sum(double v) {

@@ -421,8 +421,10 @@ constexpr int kLaneMaxMembers = 104;
 #define EFA_GC_LANE_CHUNK 32
 #endif
 constexpr int kChunkL = EFA_GC_LANE_CHUNK;  // observations staged at a time by the row-per-lane kernel (a 64-bit mask of them per wave)
-// The kernels k_sweep_gc (quad form) and k_sweep_gc_lane (row-per-lane form), defined twice: as they are, and with the
-// adaptive-inflation update fused in as k_sweep_gc_adapt / k_sweep_gc_lane_adapt
+// The kernels k_sweep_gc (quad form) and k_sweep_gc_lane (row-per-lane form), defined three times: as they are, with the
+// adaptive-inflation update fused in as k_sweep_gc_adapt / k_sweep_gc_lane_adapt, and with the vertical factor of
+// each (slab, ob) pair as k_sweep_gc_vloc / k_sweep_gc_lane_vloc
+#define EFA_GCK_VLOC false
 #define EFA_GCK_ADAPT false
 #define EFA_GCK_QUAD k_sweep_gc
 #define EFA_GCK_LANE k_sweep_gc_lane
@@ -449,18 +451,38 @@ constexpr int gc_adapt_min_waves(int NC) { return (4 * NC * 2 + 100 <= 168) ? 3 
 #undef EFA_GCK_LANE
 #undef EFA_GCK_LANE_WAVES
 #undef EFA_GCK_QUAD_WAVES
+#undef EFA_GCK_VLOC
+// with the vertical factor: the launch shapes and rows per quad of the plain kernels (a few registers more per row for the factor)
+#define EFA_GCK_VLOC true
+#define EFA_GCK_ADAPT false
+#define EFA_GCK_QUAD k_sweep_gc_vloc
+#define EFA_GCK_LANE k_sweep_gc_lane_vloc
+#define EFA_GCK_LANE_WAVES(MP) 2
+#define EFA_GCK_QUAD_WAVES(NC, RPL) gc_min_waves(NC, RPL)
+#include "efa_gcsweep_kernels.h"
+#undef EFA_GCK_ADAPT
+#undef EFA_GCK_QUAD
+#undef EFA_GCK_LANE
+#undef EFA_GCK_LANE_WAVES
+#undef EFA_GCK_QUAD_WAVES
+#undef EFA_GCK_VLOC
 
 
-template <int MP, bool FUSED, bool ADAPT>
+// the kernel family of a launch: plain, adaptive inflation fused in, vertical factor
+enum GcFamily : int { kGcPlain = 0, kGcAdapt = 1, kGcVloc = 2 };
+inline int gc_family(const GcSweepArgs& a) { return a.infl ? kGcAdapt : a.lead_vert ? kGcVloc : kGcPlain; }
+
+template <int MP, bool FUSED, int FAM>
 void gc_lane_launch_kernel(const GcSweepArgs& a, hipStream_t s) {
   const dim3 grid((unsigned)(a.nblk * a.lead_split)), block(256);
-  if constexpr (ADAPT) hipLaunchKernelGGL((k_sweep_gc_lane_adapt<MP, FUSED>), grid, block, 0, s, a);
+  if constexpr (FAM == kGcAdapt) hipLaunchKernelGGL((k_sweep_gc_lane_adapt<MP, FUSED>), grid, block, 0, s, a);
+  else if constexpr (FAM == kGcVloc) hipLaunchKernelGGL((k_sweep_gc_lane_vloc<MP, FUSED>), grid, block, 0, s, a);
   else hipLaunchKernelGGL((k_sweep_gc_lane<MP, FUSED>), grid, block, 0, s, a);
 }
-template <int MP, bool ADAPT>
+template <int MP, int FAM>
 hipError_t gc_lane_launch_one(const GcSweepArgs& a, hipStream_t s) {
-  if (a.fused_members) gc_lane_launch_kernel<MP, true, ADAPT>(a, s);
-  else gc_lane_launch_kernel<MP, false, ADAPT>(a, s);
+  if (a.fused_members) gc_lane_launch_kernel<MP, true, FAM>(a, s);
+  else gc_lane_launch_kernel<MP, false, FAM>(a, s);
   return hipGetLastError();
 }
 
@@ -476,13 +498,15 @@ int device_cus() {
   return cus;
 }
 
-template <int NC, bool VEC, bool FUSED, int RPL, bool ADAPT>
+template <int NC, bool VEC, bool FUSED, int RPL, int FAM>
 void gc_launch_kernel(dim3 grid, dim3 block, hipStream_t s, const GcSweepArgs& a) {
-  if constexpr (ADAPT) hipLaunchKernelGGL((k_sweep_gc_adapt<NC, VEC, FUSED, RPL>), grid, block, 0, s, a);
+  if constexpr (FAM == kGcAdapt) hipLaunchKernelGGL((k_sweep_gc_adapt<NC, VEC, FUSED, RPL>), grid, block, 0, s, a);
+  else if constexpr (FAM == kGcVloc) hipLaunchKernelGGL((k_sweep_gc_vloc<NC, VEC, FUSED, RPL>), grid, block, 0, s, a);
   else hipLaunchKernelGGL((k_sweep_gc<NC, VEC, FUSED, RPL>), grid, block, 0, s, a);
 }
-template <int NC, bool ADAPT>
+template <int NC, int FAM>
 hipError_t gc_launch(const GcSweepArgs& a0, hipStream_t s) {
+  constexpr bool ADAPT = FAM == kGcAdapt;
   GcSweepArgs a = a0;
   const bool vec = (a.M % 2 == 0) && (a.ye_stride % 2 == 0) && aligned16(a.Xin) && aligned16(a.Xout) && aligned16(a.Ye);
   // rows per quad while they fit the register file; with the inflation update one (its per-row state and temporaries spill at more)
@@ -498,11 +522,11 @@ hipError_t gc_launch(const GcSweepArgs& a0, hipStream_t s) {
   a.lead_split = (int)((a.n_lead + a.lead_chunk - 1) / a.lead_chunk);
   const dim3 grid((unsigned)(a.nblk * a.lead_split)), block(256);
   if (a.fused_members) {
-    if (vec) gc_launch_kernel<NC, true, true, RPL, ADAPT>(grid, block, s, a);
-    else gc_launch_kernel<NC, false, true, RPL, ADAPT>(grid, block, s, a);
+    if (vec) gc_launch_kernel<NC, true, true, RPL, FAM>(grid, block, s, a);
+    else gc_launch_kernel<NC, false, true, RPL, FAM>(grid, block, s, a);
   } else {
-    if (vec) gc_launch_kernel<NC, true, false, RPL, ADAPT>(grid, block, s, a);
-    else gc_launch_kernel<NC, false, false, RPL, ADAPT>(grid, block, s, a);
+    if (vec) gc_launch_kernel<NC, true, false, RPL, FAM>(grid, block, s, a);
+    else gc_launch_kernel<NC, false, false, RPL, FAM>(grid, block, s, a);
   }
   return hipGetLastError();
 }
@@ -557,11 +581,20 @@ hipError_t launch_sweep_gc(const GcSweepArgs& a0, hipStream_t s) {
     l.lead_split = (int)((l.n_lead + 15) / 16);  // groups of 16 slabs: one workgroup each
     l.lead_chunk = 16;
     return dispatch_width((l.M + 3) / 4, WidthRange<1, kLaneMaxMembers / 4>{}, [&](auto q) {
-      return a.infl ? gc_lane_launch_one<4 * q, true>(l, s) : gc_lane_launch_one<4 * q, false>(l, s);
+      switch (gc_family(a)) {
+        case kGcAdapt: return gc_lane_launch_one<4 * q, kGcAdapt>(l, s);
+        case kGcVloc: return gc_lane_launch_one<4 * q, kGcVloc>(l, s);
+        default: return gc_lane_launch_one<4 * q, kGcPlain>(l, s);
+      }
     });
   }
-  return dispatch_width(sweep_slots(a.M) / 8, SweepChunks{},
-                        [&](auto nc) { return a.infl ? gc_launch<nc, true>(a, s) : gc_launch<nc, false>(a, s); });
+  return dispatch_width(sweep_slots(a.M) / 8, SweepChunks{}, [&](auto nc) {
+    switch (gc_family(a)) {
+      case kGcAdapt: return gc_launch<nc, kGcAdapt>(a, s);
+      case kGcVloc: return gc_launch<nc, kGcVloc>(a, s);
+      default: return gc_launch<nc, kGcPlain>(a, s);
+    }
+  });
 }
 
 }  // namespace efa

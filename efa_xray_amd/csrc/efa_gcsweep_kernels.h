@@ -1,17 +1,22 @@
-// The two one-pass GC sweep kernels, included twice by efa_gcsweep.hip (inside namespace efa::<anonymous>, after the helpers they
-// use): EFA_GCK_QUAD / EFA_GCK_LANE name them and EFA_GCK_ADAPT says whether the adaptive-inflation update (Anderson 2009,
-// DESIGN.md §7c) is fused in.  Two kernel names rather than a template flag keep the plain kernels' names and code as they were.
+// The two one-pass GC sweep kernels, included three times by efa_gcsweep.hip (inside namespace efa::<anonymous>, after the helpers
+// they use): EFA_GCK_QUAD / EFA_GCK_LANE name them, EFA_GCK_ADAPT says whether the adaptive-inflation update (Anderson 2009,
+// DESIGN.md §7c) is fused in and EFA_GCK_VLOC whether the taper carries the vertical factor of each (slab, ob) pair (DESIGN.md
+// §7d).  Separate kernel names rather than a template flag keep the plain kernels' names and code as they were.
 // No include guard: this file is meant to be included more than once.
 
 template <int NC, bool VEC, bool FUSED, int RPL>
 __global__ __launch_bounds__(256, EFA_GCK_QUAD_WAVES(NC, RPL)) void EFA_GCK_QUAD(const GcSweepArgs a) {
   constexpr bool ADAPT = EFA_GCK_ADAPT;
+  constexpr bool VLOC = EFA_GCK_VLOC;
+  static_assert(!(ADAPT && VLOC), "adaptive inflation with vertical localisation is not built");
   constexpr int L = 4;
   constexpr int S = 2 * L * NC;  // padded ye row (doubles)
+  constexpr int NS = 4 * RPL;    // slabs of one iteration of the slab loop
   __shared__ __align__(16) double ye_s[kChunk * S];
   __shared__ __align__(16) double2 ab_s[kChunk * kBlkCols];  // per (staged ob, column): what scales (x . ye) in the row / in its mean
   __shared__ __align__(16) double aw_s[ADAPT ? kChunk * kBlkCols : 1];  // ADAPT: the taper per (staged ob, column), 0 if not assimilated
   __shared__ __align__(16) double2 ao_s[ADAPT ? 2 * kChunk : 1];         // ADAPT: the staged obs' records (adapt_ob)
+  __shared__ __align__(16) double vf_s[VLOC ? kChunk * NS : 1];           // VLOC: the vertical factor per (staged ob, slab slot), 0 beyond the last slab
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   const int j = lane & 3, r = lane >> 2;
@@ -99,11 +104,24 @@ __global__ __launch_bounds__(256, EFA_GCK_QUAD_WAVES(NC, RPL)) void EFA_GCK_QUAD
       }
       if (ADAPT)
         for (int i = tid; i < 2 * ne; i += 256) ao_s[i] = reinterpret_cast<const double2*>(a.adapt_ob + (size_t)a.idx[c0 + (i >> 1)] * 4)[i & 1];
+      if (VLOC)
+        for (int i = tid; i < ne * NS; i += 256) {
+          const int ee = i / NS, lead = lead0 + (i - ee * NS);
+          const int k = a.idx[c0 + ee];
+          vf_s[i] = (lead < lead_hi) ? vert_factor(a.lead_vert[lead], a.ob_vert[k], a.ob_vhw[k]) : 0.0;
+        }
       __syncthreads();
       // ---- apply the chunk to this wave's 16 RPL rows
       for (int ee = 0; ee < ne; ++ee) {
         const double2 ab = ab_s[ee * kBlkCols + cq];
-        if (!any_live || __ballot(ab.x != 0.0) == 0ull) continue;  // none of this wave's rows (dead slabs / zero taper)
+        if (VLOC) {  // skipped unless the horizontal taper AND the vertical factor of one of the quad's slabs are non-zero somewhere
+          bool vz = false;
+#pragma unroll
+          for (int q = 0; q < RPL; ++q) vz = vz || (vf_s[ee * NS + sq + 4 * q] != 0.0);
+          if (!any_live || __ballot(ab.x != 0.0 && vz) == 0ull) continue;
+        } else {
+          if (!any_live || __ballot(ab.x != 0.0) == 0ull) continue;  // none of this wave's rows (dead slabs / zero taper)
+        }
         double y[2 * NC];
         lds_read_row<L, NC>(ye_s + ee * S, j, y);
         double aw = 0.0;
@@ -117,8 +135,14 @@ __global__ __launch_bounds__(256, EFA_GCK_QUAD_WAVES(NC, RPL)) void EFA_GCK_QUAD
         for (int q = 0; q < RPL; ++q) {
           if (RPL > 2 && lead0 + 4 * q >= lead_hi) continue;  // wave-uniform: this slot is beyond the last slab in every quad
           const double dot = gc_dot<NC>(x[q], y);        // :95 (a dead row holds zeros: its dot, and so its update, is exactly 0)
-          xm[q] = __builtin_fma(ab.y, dot, xm[q]);       // :115, :119, :130
-          const double kb = ab.x * dot;                  // :115, :119, :136
+          double2 abr = ab;
+          if (VLOC) {  // the row's slab: both gain scalars times its vertical factor (1: unchanged bit for bit)
+            const double v = vf_s[ee * NS + sq + 4 * q];
+            abr.x = ab.x * v;
+            abr.y = ab.y * v;
+          }
+          xm[q] = __builtin_fma(abr.y, dot, xm[q]);      // :115, :119, :130
+          const double kb = abr.x * dot;                 // :115, :119, :136
           if (ADAPT) {  // (each lane of the quad holds the quad's dot and x'.x': the four do the update alike)
             anderson_update(lam[q], sd[q], aw, dot, ss[q], o01, o23, a.infl_lower, a.infl_upper, a.infl_sd_lower);
             ss[q] = adapt_ss_after(ss[q], kb, dot, o23.y);
@@ -149,12 +173,15 @@ __global__ __launch_bounds__(256, EFA_GCK_QUAD_WAVES(NC, RPL)) void EFA_GCK_QUAD
 template <int MP, bool FUSED>  // members padded to a multiple of 4; FUSED: prior members in, posterior members out
 __global__ __launch_bounds__(256, EFA_GCK_LANE_WAVES(MP)) void EFA_GCK_LANE(const GcSweepArgs a) {
   constexpr bool ADAPT = EFA_GCK_ADAPT;
+  constexpr bool VLOC = EFA_GCK_VLOC;
+  static_assert(!(ADAPT && VLOC), "adaptive inflation with vertical localisation is not built");
   constexpr int NG = (MP + 15) / 16;  // ye registers per lane
   constexpr int YS = 16 * NG;         // padded ye row in LDS (doubles)
   __shared__ __align__(16) double ye_s[kChunkL * YS];
   __shared__ __align__(16) double2 ab_s[kChunkL * kBlkCols];
   __shared__ __align__(16) double aw_s[ADAPT ? kChunkL * kBlkCols : 1];  // ADAPT: as in k_sweep_gc
   __shared__ __align__(16) double2 ao_s[ADAPT ? 2 * kChunkL : 1];
+  __shared__ __align__(16) double vf_s[VLOC ? kChunkL * 16 : 1];  // VLOC: the vertical factor per (staged ob, slab of the group), 0 beyond the last
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   // One workgroup per (column block, group of 16 slabs), blocks longest list first, a block's groups next to each other (its
@@ -256,27 +283,50 @@ __global__ __launch_bounds__(256, EFA_GCK_LANE_WAVES(MP)) void EFA_GCK_LANE(cons
       }
       if (ADAPT)
         for (int i = tid; i < 2 * ne; i += 256) ao_s[i] = reinterpret_cast<const double2*>(a.adapt_ob + (size_t)a.idx[c0 + (i >> 1)] * 4)[i & 1];
+      if (VLOC)
+        for (int i = tid; i < ne * 16; i += 256) {
+          const int lead_i = lead0 + (i & 15);
+          const int k = a.idx[c0 + (i >> 4)];
+          vf_s[i] = (lead_i < lead_hi) ? vert_factor(a.lead_vert[lead_i], a.ob_vert[k], a.ob_vhw[k]) : 0.0;
+        }
       __syncthreads();
-      // the staged observations with a non-zero taper on any of this wave's columns, as a bit mask (wave-uniform)
+      // the staged observations with a non-zero taper on any of this wave's columns, as a bit mask (wave-uniform); with the vertical
+      // factor, on any of its columns AND any of its slabs: a wave skips the obs that none of its rows can reach
       bool mine = false;
       if (lane < ne && any_live) {
         const int c_lo = ncw * wave, c_hi = (c_lo + ncw < kBlkCols) ? c_lo + ncw : kBlkCols;
         for (int c = c_lo; c < c_hi; ++c) mine = mine || (ab_s[lane * kBlkCols + c].x != 0.0);
+        if (VLOC && mine) {
+          bool vz = false;
+          for (int t = 0; t < (64 >> lg_cols) && t < 16; ++t) vz = vz || (vf_s[lane * 16 + t] != 0.0);
+          mine = vz;
+        }
       }
       unsigned long long todo = __ballot(mine);
       if (todo == 0ull) continue;
       const double2* abq = ab_s + (cq & (kBlkCols - 1));  // (a lane beyond the block's 16 columns holds a zero row: whatever it reads is multiplied by 0)
       const double* yq = ye_s + (lane & 15);
+      const double* vq = vf_s + (VLOC ? (lane >> lg_cols) : 0);  // VLOC: the lane's slab slot (< 16 in every layout)
       int ee = __builtin_ctzll(todo);
       todo &= todo - 1;
       double2 ab = abq[ee * kBlkCols];
+      if (VLOC) {  // the row's slab: both gain scalars times its vertical factor (1: unchanged bit for bit)
+        const double v = vq[ee * 16];
+        ab.x *= v;
+        ab.y *= v;
+      }
       double y[NG];
 #pragma unroll
       for (int c = 0; c < NG; ++c) y[c] = yq[ee * YS + 16 * c];
       while (true) {
         const int en = (todo != 0ull) ? __builtin_ctzll(todo) : ee;  // the next one (after the last: itself again, harmlessly)
         const double dot = lane_dot<MP>(x, y, seq);      // :95
-        const double2 abn = abq[en * kBlkCols];
+        double2 abn = abq[en * kBlkCols];
+        if (VLOC) {
+          const double vn = vq[en * 16];
+          abn.x *= vn;
+          abn.y *= vn;
+        }
         xm = __builtin_fma(ab.y, dot, xm);               // :115, :119, :130
         const double nkb = -(ab.x * dot);                // :115, :119, :136
         if (ADAPT) {

@@ -140,6 +140,12 @@ long band_traj_stride(int M);  // doubles per trajectory record as k_pipe_band l
 hipError_t launch_fill_u64(unsigned long long* p, size_t n, unsigned long long v, hipStream_t s);
 hipError_t launch_obs_taper_matrix(long P, long R, const double* ob_lat, const double* ob_lon, const double* ob_hw,
                                    double* trig_scratch /* [P][6] */, double* tw, hipStream_t s);
+// vertical localisation of the obs-obs taper (efa_vloc.hip): tw[k][j] *= the vertical factor of obs (j, k) for
+// j < P (the table launch_obs_taper_matrix wrote); and the per-batch sweep's table W[k][j] = horizontal x vertical taper of
+// ob b0 + k against row j of the obs block (1 for rows j >= P), for the table mode of k_sweep
+hipError_t launch_obs_taper_vert(long P, long R, const double* ob_vert, const double* ob_vhw, double* tw, hipStream_t s);
+hipError_t launch_obs_taper_rows(long b0, int nb, long R, long P, const double* ob_lat, const double* ob_lon, const double* ob_hw,
+                                 const double* ob_vert, const double* ob_vhw, double* W, hipStream_t s);
 
 // ---- one-pass localised sweep (efa_gcsweep.hip) ---------------------------------------
 struct GcSweepArgs {
@@ -165,6 +171,10 @@ struct GcSweepArgs {
   double* infl;             // [n_lead*ncol][2] (mean, sd) of every state row, updated in place
   const double* adapt_ob;   // [P][4] {D^2, prior var, ob error variance, y'.y'} (launch_adapt_obs)
   double infl_lower, infl_upper, infl_sd_lower;
+  // vertical localisation; lead_vert == null: off (exclusive with infl)
+  const double* lead_vert;  // [n_lead] vertical coordinate of each slab, NaN: not localised vertically
+  const double* ob_vert;    // [P] the obs' vertical coordinates, NaN: no vertical taper
+  const double* ob_vhw;     // [P] their vertical half-widths (1 where ob_vert is NaN)
 };
 long gc_num_blocks(long ncol);
 // list build in one pass: upper bounds + device prefix sum (off[nblk] = capacity needed), then the entries

@@ -144,6 +144,10 @@ class HipEngine(object):
         """Posterior relaxation (RTPP / RTPS) of the state phases that follow on this engine's context."""
         self.ctx.set_relaxation(kind, alpha)
 
+    def set_vertical_localization(self, lead_vert, ob_vert=None, ob_vert_halfwidth=None):
+        """Vertical localisation of the cycles that follow on this engine's context; lead_vert None: off."""
+        self.ctx.set_vertical_localization(lead_vert, ob_vert, ob_vert_halfwidth)
+
     def obs_phase(self, M, P, ym, Yp, ob):
         return self.ctx.obs_phase(M, P, ym.data_ptr(), Yp.data_ptr(), ob["value"], ob["error"], ob["assim"],
                                   _lib.LOC_GC if ob.get("loc") == "GC" else _lib.LOC_NONE,
@@ -167,7 +171,8 @@ class ShardedEnSRF(object):
     X_local : engine buffer (rows_local x M), rows_local = n_lead * (hi - lo),
               prior member values of this shard (resident on the rank's device).
     sten_idx/sten_wts : (P, npt) linear forward operator in GLOBAL rows.
-    ob : dict(value, error, assim[, loc='GC', lat, lon, halfwidth]) -- identical on all ranks.
+    ob : dict(value, error, assim[, loc='GC', lat, lon, halfwidth[, vert, vert_halfwidth]]) -- identical on all ranks;
+         vert / vert_halfwidth: (P,) vertical coordinate and half-width of each ob, NaN where missing (with vert_coord).
     grid_lat/grid_lon : (ncol,) per-column lat/lon of the GLOBAL grid (GC only).
     """
 
@@ -229,10 +234,12 @@ class ShardedEnSRF(object):
         return HX
 
     def assimilate(self, X_local, post_local, HX, ob, grid_lat=None, grid_lon=None, rtps=None, rtpp=None,
-                   adaptive_inflation=None):
+                   adaptive_inflation=None, vert_coord=None):
         """Stage 2, after HX has been summed over the shards: obs-space priors, Phase A
         (replicated: identical on every rank) and the sweep of this shard's rows.  `rtps` / `rtpp`:
-        posterior relaxation of the shard's rows as in `EnSRF` (row-local: no communication)."""
+        posterior relaxation of the shard's rows as in `EnSRF` (row-local: no communication).
+        `vert_coord`: vertical localisation as in `EnSRF` -- (nvars, ntimes), n_lead values in slab
+        order -- with the obs' `vert` / `vert_halfwidth` from `ob`."""
         if adaptive_inflation is not None:
             raise ValueError("ShardedEnSRF does not support adaptive_inflation (out of scope: use EnSRF on one GPU)")
         eng, M = self.engine, self.M
@@ -242,6 +249,11 @@ class ShardedEnSRF(object):
         elif relax[0] != _lib.RELAX_NONE:
             raise ValueError("this engine does not support posterior relaxation")
         P = int(HX.shape[0])
+        vert = self._vertical(ob, vert_coord, P)
+        if hasattr(eng, "set_vertical_localization"):
+            eng.set_vertical_localization(*vert)                           # every call: "off" included
+        elif vert[0] is not None:
+            raise ValueError("this engine does not support vertical localisation")
         ym = eng.empty((max(P, 1),))
         eng.form_perts(P, M, HX, ym, HX)                                   # assimilation.py:46-48
         glat = glon = None
@@ -255,9 +267,32 @@ class ShardedEnSRF(object):
         return diag
 
     def update(self, X_local, post_local, sten_idx, sten_wts, ob, grid_lat=None, grid_lon=None, inflation=None,
-               rtps=None, rtpp=None, adaptive_inflation=None):
+               rtps=None, rtpp=None, adaptive_inflation=None, vert_coord=None):
         if adaptive_inflation is not None:
             raise ValueError("ShardedEnSRF does not support adaptive_inflation (out of scope: use EnSRF on one GPU)")
+        self._vertical(ob, vert_coord, int(np.asarray(sten_idx).shape[0]))  # (refused before any work)
         HX = self.partial_estimates(X_local, sten_idx, sten_wts, inflation)
         self.all_reduce_sum(HX)                                            # the one exchange step
-        return self.assimilate(X_local, post_local, HX, ob, grid_lat, grid_lon, rtps=rtps, rtpp=rtpp)
+        return self.assimilate(X_local, post_local, HX, ob, grid_lat, grid_lon, rtps=rtps, rtpp=rtpp, vert_coord=vert_coord)
+
+    def _vertical(self, ob, vert_coord, P):
+        """(lead_vert, ob_vert, ob_vert_halfwidth) for the engine, (None, None, None) when off; ValueError on a bad setting."""
+        if vert_coord is None:
+            return None, None, None
+        if ob.get("loc") != "GC":
+            raise ValueError("vert_coord needs loc='GC' in the ob dict; got loc=%r" % (ob.get("loc"),))
+        z = np.asarray(vert_coord, dtype=np.float64).reshape(-1)
+        if z.size != self.n_lead:
+            raise ValueError("vert_coord has %d values but the shard has n_lead=%d slabs" % (z.size, self.n_lead))
+        if np.isinf(z).any():
+            raise ValueError("vert_coord holds an infinite value (NaN marks a slab that is not localised vertically)")
+        ov = np.full(P, np.nan) if ob.get("vert") is None else np.asarray(ob["vert"], dtype=np.float64).reshape(-1)
+        oh = np.full(P, np.nan) if ob.get("vert_halfwidth") is None else np.asarray(ob["vert_halfwidth"], dtype=np.float64).reshape(-1)
+        if ov.size != P or oh.size != P:
+            raise ValueError("ob['vert'] / ob['vert_halfwidth'] must hold one value per observation (%d)" % P)
+        bad = ~np.isnan(oh) & ~(np.isfinite(oh) & (oh > 0))
+        if bad.any():
+            raise ValueError("ob['vert_halfwidth'][%d]=%r: expected a finite number > 0 or NaN" % (int(np.argmax(bad)), oh[bad][0]))
+        if np.isinf(ov).any():
+            raise ValueError("ob['vert'] holds an infinite value")
+        return z, ov, oh

@@ -17,8 +17,12 @@ class Observation(object):
     def __init__(self, value=None, obtype=None, time=None, error=None, lat=None,
                  lon=None, vert=None,
                  prior_mean=None, post_mean=None, prior_var=None, post_var=None,
-                 assimilate_this=False, description=None, localize_radius=None):
-        # observation.py:18-36 (note: assimilate_this defaults to False there too)
+                 assimilate_this=False, description=None, localize_radius=None,
+                 vert_localize_radius=None):
+        # observation.py:18-36 (note: assimilate_this defaults to False there too).  vert_localize_radius is this
+        # project's own: the vertical half-width that goes with `vert`, in the unit of `vert`
+        if vert_localize_radius is not None:
+            check_vert_halfwidth(vert_localize_radius)
         self.value = value
         self.obtype = obtype
         self.time = time
@@ -34,6 +38,7 @@ class Observation(object):
         self.assimilated = False
         self.description = description
         self.localize_radius = localize_radius
+        self.vert_localize_radius = vert_localize_radius
 
     def estimate(self, state):
         """Ensemble estimate of this ob: interpolate the matching field
@@ -63,6 +68,17 @@ class Observation(object):
         if type == 'GC':
             return gaspari_cohn(distances, halfwidth)
         raise ValueError("unknown localization type %r" % (type,))
+
+
+def check_vert_halfwidth(c, where="vert_localize_radius"):
+    """The vertical half-width as a float; ValueError unless it is a finite number > 0."""
+    try:
+        v = float(c)
+    except (TypeError, ValueError):
+        raise ValueError("%s=%r: expected a number" % (where, c))
+    if not np.isfinite(v) or v <= 0.0:
+        raise ValueError("%s=%r: expected a finite number > 0" % (where, c))
+    return v
 
 
 def gaspari_cohn(distances, halfwidth):

@@ -135,6 +135,24 @@ int efa_ctx_set_relaxation(efa_ctx *ctx, int kind, double alpha);
 int efa_inflate_rows_dev(efa_ctx *ctx, long rows, int M, double *X_dev, const double *field_dev);
 int efa_ctx_set_adaptive_inflation(efa_ctx *ctx, double *field_dev, long rows, double lower, double upper,
                                    double sd_lower);
+
+/* ---- vertical localisation of the GC taper --------------
+ * Host arrays, copied into the context: lead_vert[n_lead] is the vertical
+ * coordinate of each slab (slab s = rows s*ncol .. s*ncol + ncol - 1, the
+ * variable-major, then valid-time order), ob_vert[P] and
+ * ob_vert_halfwidth[P] those of the observations, in any unit as long as it
+ * is the same for all three.  With it every taper weight of a GC cycle --
+ * state rows and the obs-obs taper -- is the horizontal one times
+ * GC(|z_row - z_k|, c_k), the same Gaspari-Cohn polynomial with ob k's
+ * vertical half-width c_k.  A NaN slab coordinate, or an ob whose coordinate
+ * or half-width is NaN, takes factor 1 in every pair it is part of.  A
+ * half-width that is not NaN must be finite and > 0; coordinates may not be
+ * infinite.  lead_vert NULL turns it off.  Context state like the
+ * relaxation: while it is set, a later call fails (EFA_ERR_INVALID) unless
+ * it is a GC cycle of exactly P observations (and n_lead slabs for the state
+ * phase), option "gc_onepass" is 1 and no adaptive-inflation field is set. */
+int efa_ctx_set_vertical_localization(efa_ctx *ctx, long n_lead, const double *lead_vert, long P, const double *ob_vert,
+                                      const double *ob_vert_halfwidth);
 int efa_ctx_synchronize(efa_ctx *ctx);
 
 /* ---- device memory for callers without their own allocator -------------*/
