@@ -51,6 +51,7 @@ SIGNATURES = {
                                                       ctypes.c_double, ctypes.c_double]),
     "efa_ctx_set_vertical_localization": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, c_double_p, ctypes.c_long,
                                                          c_double_p, c_double_p]),
+    "efa_ctx_set_outlier_threshold": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double]),
     "efa_ctx_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
     "efa_malloc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, c_void_pp]),
     "efa_free": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
@@ -312,6 +313,11 @@ class Context(object):
             raise ValueError("ob_vert and ob_vert_halfwidth differ in length: %d and %d" % (ov.size, oh.size))
         _check(self.lib, self.lib.efa_ctx_set_vertical_localization(self.handle, lv.size, _dp(lv), ov.size,
                                                                     _dp(ov) if ov.size else None, _dp(oh) if oh.size else None))
+
+    def set_outlier_threshold(self, threshold=None):
+        """Outlier check of every later obs phase on this context: an ob with
+        (value - ym)^2 > threshold^2 (var(Yp) + error) is not assimilated; None or 0 turns it off."""
+        _check(self.lib, self.lib.efa_ctx_set_outlier_threshold(self.handle, 0.0 if threshold is None else float(threshold)))
 
     def inflate_rows(self, rows, M, X, field):
         """X[row] <- mean + sqrt(field[row][0]) (X[row] - mean), in place on the device."""

@@ -12,6 +12,8 @@ The per-observation loop (ensrf.py:50-149) does not exist in Python here:
 and calls libefa_hip (`efa_obs_phase_dev` + `efa_state_cycle_dev`).  If the
 library or a gfx950 GPU is missing the call raises -- there is no NumPy path.
 """
+import numbers
+
 import numpy as np
 
 from efa_xray_amd import _lib
@@ -74,6 +76,18 @@ def ob_vertical(obs):
     return ov, oh
 
 
+def outlier_setting(threshold):
+    """The outlier threshold as a float, or None when off; ValueError unless a finite number > 0."""
+    if threshold is None:
+        return None
+    if isinstance(threshold, bool) or not isinstance(threshold, numbers.Real):
+        raise ValueError("outlier_threshold must be a number > 0 or None, got %r" % (threshold,))
+    t = float(threshold)
+    if not (np.isfinite(t) and t > 0.0):
+        raise ValueError("outlier_threshold must be a finite number > 0 (None: off), got %r" % (threshold,))
+    return t
+
+
 class EnSRF(Assimilation):
     def __init__(self, state, obs, nproc=1, inflation=None, verbose=True, loc=False, **kw):
         """Extra keyword-only options (all default to reference behaviour):
@@ -90,6 +104,10 @@ class EnSRF(Assimilation):
                     state.vars() order, the vertical coordinate of each 2-D slab (NaN: not
                     localised vertically); obs taper with their `vert` and `vert_localize_radius`.
                     Needs loc='GC'; excludes adaptive_inflation.  None: off
+        outlier_threshold -- gross-error check, a number t > 0: an ob asked to be
+                    assimilated is rejected (assimilated False, nothing updated by it) when
+                    (value - prior mean)^2 > t^2 (prior variance + error), checked once per
+                    update against the prior.  None: off
         """
         device = kw.pop("device", 0)
         self.obs_batch = kw.pop("obs_batch", None)
@@ -98,9 +116,11 @@ class EnSRF(Assimilation):
         rtpp = kw.pop("rtpp", None)
         adaptive = kw.pop("adaptive_inflation", None)
         vert_coord = kw.pop("vert_coord", None)
+        outlier_threshold = kw.pop("outlier_threshold", None)
         if kw:
             raise TypeError("unexpected keyword arguments %r" % sorted(kw))
         self.relaxation = relaxation_setting(rtps, rtpp)
+        self.outlier_threshold = outlier_setting(outlier_threshold)
         if adaptive is not None:
             if not isinstance(adaptive, AdaptiveInflation):
                 raise ValueError("adaptive_inflation must be an AdaptiveInflation, got %r" % type(adaptive).__name__)
@@ -159,6 +179,7 @@ class EnSRF(Assimilation):
         ctx.set_option("path", path)
         ctx.set_relaxation(*self.relaxation)   # every call: the context is shared per device
         ctx.set_adaptive_inflation(None)        # set by update() around its own cycle only
+        ctx.set_outlier_threshold(self.outlier_threshold)  # every call, "off" included
         if self.vert_coord is None:             # every call as well, "off" included
             ctx.set_vertical_localization(None)
         else:

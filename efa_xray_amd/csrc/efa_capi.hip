@@ -199,6 +199,10 @@ struct efa_ctx {
   long geo_vl_serial = 0;       // ... the value the current geometry was compared with
   DevBuf vl_dev;                // device copy of vl_host
   DevBuf vl_W;                  // the per-batch sweep's taper table [nb][R] (launch_obs_taper_rows)
+  // --- outlier check (efa_ctx_set_outlier_threshold) ----------------------------------------------
+  double qc_threshold = 0.0;    // 0: off
+  bool qc_used = false;         // the last obs phase ran it: its flags on the device may be fewer than the caller's
+  DevBuf qc_act;                // [P][kCoefStride], GC: the caller's flags where the one-pass sweep's list builders read coef[3]
   // --- f1: interpolation stencils -------------------------------------------------
   DevBuf fs_idx, fs_wts;  // efa_forward_stencil_dev staging
   DevBuf f_glat, f_glon, f_sl, f_cl, f_valids, f_var, f_time, f_lat, f_lon, f_near, f_idx, f_wts, f_status;
@@ -438,6 +442,7 @@ struct ObsCall {
   double *Yw = nullptr, *ymw = nullptr;  // the working block [R][M], [R]
   size_t oslot = 0;      // bytes of one diagnostics array in out_pack / pin_out
   size_t pack_bytes = 0; // of the input pack, which goes to the device inside the prep launch
+  size_t islot = 0;      // bytes of one slot of that pack
   long B = 0;            // obs per pass of the per-batch kernels
   bool pipe_ok = false;  // the persistent kernels apply
   long Wmax = 0, nwin = 1;  // obs per window, windows
@@ -542,6 +547,7 @@ int stage_obs_inputs(efa_ctx* c, ObsCall& a, const double* ob_value, const doubl
     c->ob_lon.carve(db + 8 * slot, slot);
     c->ob_hw.carve(db + 9 * slot, slot);
     a.pack_bytes = gc ? total : 7 * slot;  // goes to the device inside the prep launch (read from the mapped pinned buffer)
+    a.islot = slot;
   }
   EFA_TRY(c->Ye_rec.reserve((size_t)P * M * sizeof(double)));
   EFA_TRY(c->coef.reserve((size_t)P * kCoefStride * sizeof(double)));
@@ -594,9 +600,22 @@ int start_phase_a(efa_ctx* c, ObsCall& a) {
     EFA_TRY(c->traj.reserve((size_t)P * a.TS * sizeof(unsigned long long)));
     EFA_TRY(c->status.reserve(3 * sizeof(int)));
   }
-  EFA_HIP(launch_phase_a_prep(P, M, a.Yp_dev, a.ym_dev, a.Yw, a.ymw, a.carry_T ? 1 : 0,
-                              a.pipe_ok ? c->traj.as<unsigned long long>() : nullptr, a.pipe_ok ? (size_t)P * a.TS : 0, kTrajSentinel,
-                              a.pipe_ok ? c->status.as<int>() : nullptr, c->pin_in.p, c->ob_pack.p, a.pack_bytes, s));
+  unsigned long long* traj = a.pipe_ok ? c->traj.as<unsigned long long>() : nullptr;
+  int* status = a.pipe_ok ? c->status.as<int>() : nullptr;
+  c->qc_used = c->qc_threshold > 0.0;
+  if (c->qc_used) {  // the outlier check decides every ob's flag here, ONCE, against the caller's block: windows and redone launches
+                     // read the flags it wrote
+    double* host_act = nullptr;
+    if (a.loc_mode == EFA_LOC_GC) {
+      EFA_TRY(c->qc_act.reserve((size_t)P * kCoefStride * sizeof(double)));
+      host_act = c->qc_act.as<double>();
+    }
+    EFA_HIP(launch_phase_a_prep_qc(P, M, a.Yp_dev, a.ym_dev, a.Yw, a.ymw, a.carry_T ? 1 : 0, traj, a.pipe_ok ? (size_t)P * a.TS : 0,
+                                   kTrajSentinel, status, c->pin_in.p, c->ob_pack.p, a.pack_bytes, a.islot, c->qc_threshold, host_act, s));
+  } else {
+    EFA_HIP(launch_phase_a_prep(P, M, a.Yp_dev, a.ym_dev, a.Yw, a.ymw, a.carry_T ? 1 : 0, traj, a.pipe_ok ? (size_t)P * a.TS : 0,
+                                kTrajSentinel, status, c->pin_in.p, c->ob_pack.p, a.pack_bytes, s));
+  }
   a.nwin = a.pipe_ok ? (P + a.Wmax - 1) / a.Wmax : 1;
   return EFA_OK;
 }
@@ -935,6 +954,13 @@ int finish_obs_phase(efa_ctx* c, const ObsCall& a, Records layout, bool diag_on_
       if (post_var) post_var[k] = pv[k];
     }
   }
+  if (c->qc_used) {  // the outlier check may have rejected obs: the state phase goes by the flags Phase A went by
+    c->n_active = 0;
+    for (long k = 0; k < P; ++k) {
+      c->h_assim[k] = as[k] ? 1 : 0;
+      c->n_active += as[k] ? 1 : 0;
+    }
+  }
   if (c->timing) c->obs_ms_pending = true;  // read in efa_last_timing: the copies back to the caller's block may still be in flight
   c->have_transform = a.carry_T;
   c->have_traj = true;
@@ -955,6 +981,7 @@ int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const d
   c->n_active = 0;
   c->have_transform = false;
   c->spec.launched = false;
+  c->qc_used = false;
   harvest_obs_ms(c);
   c->obs_ms = 0.0;
   if (P == 0) {
@@ -1100,15 +1127,18 @@ int state_gc_onepass(efa_ctx* c, const double* xm_in, const double* Xp_in, doubl
   c->gc_list_valid = false;
   EFA_TRY(read_gc_pairs(c));  // (the previous sweep's count, before the counter is cleared: that sweep is long done)
   EFA_HIP(hipMemsetAsync(c->gc_pairs.p, 0, sizeof(unsigned long long), s));
+  // the lists hold the obs the CALLER asked to assimilate, as the geometry they are cached by: an ob the outlier check rejected
+  // stays in them with its inactive record (zero gains), so a later cycle that keeps it finds it there
+  const double* act = c->qc_used ? c->qc_act.as<double>() : c->coef.as<double>();
   EFA_HIP(launch_gc_bound(ncol, P, c->glat.as<double>(), c->ob_lat.as<double>(), c->ob_hw.as<double>(),
-                          c->coef.as<double>(), c->gc_ub.as<int>(), c->gc_off.as<long>(), s));
+                          act, c->gc_ub.as<int>(), c->gc_off.as<long>(), s));
   long cap = 0;  // the only host round trip of the build: 8 bytes, the capacity the lists need
   EFA_HIP(hipMemcpyAsync(&cap, c->gc_off.as<long>() + nblk, sizeof(long), hipMemcpyDeviceToHost, s));
   EFA_HIP(hipStreamSynchronize(s));
   EFA_TRY(c->gc_idx.reserve((size_t)(cap ? cap : 1) * sizeof(int)));
   EFA_TRY(c->gc_wts.reserve((size_t)(cap ? cap : 1) * 16 * sizeof(double)));
   EFA_HIP(launch_gc_fill(ncol, P, c->glat.as<double>(), c->glon.as<double>(), c->ob_lat.as<double>(),
-                         c->ob_lon.as<double>(), c->ob_hw.as<double>(), c->coef.as<double>(), c->gc_obtrig.as<double>(),
+                         c->ob_lon.as<double>(), c->ob_hw.as<double>(), act, c->gc_obtrig.as<double>(),
                          c->gc_off.as<long>(), c->gc_cnt.as<int>(), c->gc_idx.as<int>(), c->gc_wts.as<double>(), c->gc_order.as<int>(),
                          c->gc_pairs.as<unsigned long long>(), s));
   c->gc_list_valid = true;
@@ -1348,7 +1378,7 @@ int efa_ctx_destroy(efa_ctx* c) {
   DevBuf* bufs[] = {&c->ob_pack, &c->out_pack, &c->Ye_rec, &c->coef, &c->ob_val, &c->ob_err, &c->ob_asm, &c->ob_lat, &c->ob_lon, &c->ob_hw, &c->ob_errsq,
                     &c->d_prior_mean, &c->d_prior_var, &c->d_post_mean, &c->d_post_var, &c->d_assimilated,
                     &c->Yw, &c->ymw, &c->win_Y, &c->win_m, &c->traj, &c->tw_mat, &c->status, &c->dbg, &c->W, &c->gc_cnt, &c->gc_ub, &c->gc_order, &c->gc_obtrig, &c->gc_off, &c->gc_idx, &c->gc_wts, &c->gc_pairs, &c->glat, &c->glon, &c->xm_ws, &c->fs_idx, &c->fs_wts, &c->f_glat, &c->f_glon, &c->f_sl, &c->f_cl, &c->f_valids, &c->f_var, &c->f_time, &c->f_lat, &c->f_lon, &c->f_near, &c->f_idx, &c->f_wts, &c->f_status, &c->h_xm, &c->h_Xp, &c->h_ym, &c->h_Yp,
-                    &c->gcc_lat, &c->gcc_lon, &c->gcc_oblat, &c->gcc_oblon, &c->gcc_obhw, &c->gcc_coef, &c->gcc_trig, &c->gcc_cnt, &c->gcc_pairs, &c->ai_ob, &c->vl_dev, &c->vl_W};
+                    &c->gcc_lat, &c->gcc_lon, &c->gcc_oblat, &c->gcc_oblon, &c->gcc_obhw, &c->gcc_coef, &c->gcc_trig, &c->gcc_cnt, &c->gcc_pairs, &c->ai_ob, &c->vl_dev, &c->vl_W, &c->qc_act};
   for (DevBuf* b : bufs) b->release();
   for (int i = 0; i < 7; ++i)
     if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
@@ -1490,6 +1520,14 @@ int efa_ctx_set_vertical_localization(efa_ctx* c, long n_lead, const double* lea
   c->vl_on = true;
   c->vl_any = any;
   c->vl_serial++;
+  return EFA_OK;
+}
+
+int efa_ctx_set_outlier_threshold(efa_ctx* c, double threshold) {
+  EFA_TRY(use(c));
+  if (!std::isfinite(threshold) || threshold < 0.0)
+    return fail(EFA_ERR_INVALID, "outlier threshold %g must be a finite number >= 0 (0: off)", threshold);
+  c->qc_threshold = threshold;
   return EFA_OK;
 }
 
@@ -1798,7 +1836,10 @@ int efa_ensrf_cycle_dev(efa_ctx* c, long rows, int M, long P, const double* X_de
     c->grid_ready = false;
     return rc;
   }
-  if (launched) {  // Phase B is in the stream already, behind the launch that turned out fine
+  // Phase B is in the stream already, behind the launch that turned out fine -- unless the outlier check rejected so many obs
+  // that the state phase would not take the transform (none left, or "auto" with fewer): then it runs as it would have, over the
+  // speculative posterior (the prior is untouched)
+  if (launched && c->n_active > 0 && want_transform(c, true)) {
     c->state_ms = 0.0;
     c->state_launches = spec_launches;
     c->state_launches_sum += spec_launches;

@@ -260,6 +260,12 @@ hipError_t launch_set_identity(int M, double* T, double* w, hipStream_t s);
 hipError_t launch_phase_a_prep(long P, int M, const double* Yp, const double* ym, double* Yw, double* ymw, int carry_T,
                                unsigned long long* traj, size_t traj_words, unsigned long long sentinel, int* status,
                                const void* pack_host, void* pack_dev, size_t pack_bytes, hipStream_t s);
+// ... with the outlier check: `slot` is the pack's slot size (value | error | assim bytes | 4 slots of records ...),
+// `threshold` > 0; host_act [P][kCoefStride] (or null) receives the requested flags for the one-pass sweep's list builders
+hipError_t launch_phase_a_prep_qc(long P, int M, const double* Yp, const double* ym, double* Yw, double* ymw, int carry_T,
+                                  unsigned long long* traj, size_t traj_words, unsigned long long sentinel, int* status,
+                                  const void* pack_host, void* pack_dev, size_t pack_bytes, size_t slot, double threshold,
+                                  double* host_act, hipStream_t s);
 hipError_t launch_results_to_host(const void* src_dev, void* dst_host, size_t bytes, const int* st_dev, int* st_host, hipStream_t s);
 // diagnostic: `blocks` workgroups that hold `lds_bytes` of LDS each and spin for `ms` milliseconds
 hipError_t launch_occupy(int blocks, size_t lds_bytes, double ms, hipStream_t s);

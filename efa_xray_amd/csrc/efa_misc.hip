@@ -227,6 +227,96 @@ hipError_t launch_phase_a_prep(long P, int M, const double* Yp, const double* ym
   return hipGetLastError();
 }
 
+// k_phase_a_prep with the outlier check, still ONE launch.  One wave per observation copies its row of the block
+// into the working rows -- the only read of the row -- and, for an ob the caller asked to assimilate, takes the two-pass variance
+// of the row (ddof 0) and keeps the ob iff d^2 <= t^2 (s2 + error), d = value - ym (a NaN rejects it).  The wave writes the
+// effective flag into BOTH device forms, the assimilate byte and the third double of the ob's {error, sqrt(error), assimilate, 0}
+// record, which the grid-stride pack copy therefore leaves out (pack bytes [skip_lo, skip_hi) -- no thread's 16-byte copy can
+// land on a flag another thread wrote).  `host_act`, when given, gets {0, 0, 0, requested flag} per ob: the coefficient-shaped
+// activity the one-pass sweep's list builders read, so the cached lists follow the caller's flags, not the check's outcome.
+__global__ __launch_bounds__(256) void k_phase_a_prep_qc(long P, int M, const double* __restrict__ Yp, const double* __restrict__ ym,
+                                                         double* __restrict__ Yw, double* __restrict__ ymw, int carry_T,
+                                                         unsigned long long* __restrict__ traj, size_t traj_words,
+                                                         unsigned long long sentinel, int* __restrict__ status,
+                                                         const uint4* __restrict__ pack_host, uint4* __restrict__ pack_dev, size_t pack_n16,
+                                                         size_t slot, size_t skip_lo16, size_t skip_hi16, double t2,
+                                                         double* __restrict__ host_act) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = tid; i < pack_n16; i += nth)
+    if (i < skip_lo16 || i >= skip_hi16) pack_dev[i] = pack_host[i];
+  const char* hb = reinterpret_cast<const char*>(pack_host);
+  char* db = reinterpret_cast<char*>(pack_dev);
+  const double* h_value = reinterpret_cast<const double*>(hb);
+  const double* h_error = reinterpret_cast<const double*>(hb + slot);
+  const uint8_t* h_assim = reinterpret_cast<const uint8_t*>(hb + 2 * slot);
+  const double* h_rec = reinterpret_cast<const double*>(hb + 3 * slot);
+  uint8_t* d_assim = reinterpret_cast<uint8_t*>(db + 2 * slot);
+  double* d_rec = reinterpret_cast<double*>(db + 3 * slot);
+  const int lane = threadIdx.x & 63;
+  const long wave = (long)(tid >> 6), nwaves = (long)(nth >> 6);
+  for (long k = wave; k < P; k += nwaves) {
+    // the ob's scalars from host memory first, all in flight together (one round trip over the link, not four in a row)
+    const uint8_t req = h_assim[k];
+    const double value = h_value[k], error = h_error[k];
+    const double2 rec = (lane < 2) ? reinterpret_cast<const double2*>(h_rec + 4 * k)[lane] : make_double2(0.0, 0.0);
+    const double* src = Yp + (size_t)k * M;
+    double* dst = Yw + (size_t)k * M;
+    double v[4];
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int m = lane + 64 * j;
+      v[j] = (m < M) ? src[m] : 0.0;
+      if (m < M) dst[m] = v[j];
+      s += v[j];
+    }
+    const double y = ym[k];
+    bool keep = false;
+    if (req) {
+      const double mean = wave_sum(s) / (double)M;
+      double q = 0.0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const double e = (lane + 64 * j < M) ? v[j] - mean : 0.0;
+        q += e * e;
+      }
+      const double s2 = wave_sum(q) / (double)M;
+      const double d = value - y;
+      keep = d * d <= t2 * (s2 + error);
+    }
+    if (lane == 0) {
+      ymw[k] = y;
+      d_assim[k] = keep ? req : (uint8_t)0;
+    }
+    if (lane < 2) {  // the record as the host wrote it but its flag
+      reinterpret_cast<double2*>(d_rec + 4 * k)[lane] = lane ? make_double2(keep ? 1.0 : 0.0, rec.y) : rec;
+      if (host_act) reinterpret_cast<double2*>(host_act + 4 * k)[lane] = make_double2(0.0, lane && req ? 1.0 : 0.0);
+    }
+  }
+  if (carry_T) {
+    const size_t n = (size_t)P * M;
+    double* T = Yw + n;
+    for (size_t i = tid; i < (size_t)M * M; i += nth) T[i] = (i / M == i % M) ? 1.0 : 0.0;
+    for (size_t i = tid; i < (size_t)M; i += nth) ymw[P + i] = 0.0;
+  }
+  if (traj != nullptr)
+    for (size_t i = tid; i < traj_words; i += nth) traj[i] = sentinel;
+  if (status != nullptr && tid < 3) status[tid] = 0;
+}
+
+hipError_t launch_phase_a_prep_qc(long P, int M, const double* Yp, const double* ym, double* Yw, double* ymw, int carry_T,
+                                  unsigned long long* traj, size_t traj_words, unsigned long long sentinel, int* status,
+                                  const void* pack_host, void* pack_dev, size_t pack_bytes, size_t slot, double threshold,
+                                  double* host_act, hipStream_t s) {
+  if (M < 1 || M > kMaxMembers || (slot & 15u) != 0 || 7 * slot > pack_bytes) return hipErrorInvalidValue;
+  size_t work = (size_t)P * 256;  // a wave per ob (blocks of four waves take 4 x 256 work items)
+  if (traj && traj_words > work) work = traj_words;
+  hipLaunchKernelGGL(k_phase_a_prep_qc, dim3(grid_for(work, 256 * 4)), dim3(256), 0, s, P, M, Yp, ym, Yw, ymw, carry_T, traj,
+                     traj_words, sentinel, status, static_cast<const uint4*>(pack_host), static_cast<uint4*>(pack_dev), pack_bytes / 16,
+                     slot, 2 * slot / 16, 7 * slot / 16, threshold * threshold, host_act);
+  return hipGetLastError();
+}
+
 // A persistent Phase-A launch's status words and the diagnostics it wrote, stored by a kernel straight into mapped pinned host
 // memory (coalesced 16-byte stores, each byte once): behind it the next kernel starts at once, where two device-to-host copies
 // cost 15 us plus a ~10 us engine switch on either side.  The host reads them after waiting for an event recorded behind this kernel.

@@ -31,7 +31,7 @@ logic on CPU ranks with gloo by passing their own engine.)
 import numpy as np
 
 from efa_xray_amd import _lib
-from efa_xray_amd.assimilation.ensrf import relaxation_setting
+from efa_xray_amd.assimilation.ensrf import outlier_setting, relaxation_setting
 
 
 def column_bounds(ncol, world_size):
@@ -144,6 +144,10 @@ class HipEngine(object):
         """Posterior relaxation (RTPP / RTPS) of the state phases that follow on this engine's context."""
         self.ctx.set_relaxation(kind, alpha)
 
+    def set_outlier_threshold(self, threshold):
+        """Outlier check of the obs phases that follow on this engine's context; None: off."""
+        self.ctx.set_outlier_threshold(threshold)
+
     def set_vertical_localization(self, lead_vert, ob_vert=None, ob_vert_halfwidth=None):
         """Vertical localisation of the cycles that follow on this engine's context; lead_vert None: off."""
         self.ctx.set_vertical_localization(lead_vert, ob_vert, ob_vert_halfwidth)
@@ -234,12 +238,13 @@ class ShardedEnSRF(object):
         return HX
 
     def assimilate(self, X_local, post_local, HX, ob, grid_lat=None, grid_lon=None, rtps=None, rtpp=None,
-                   adaptive_inflation=None, vert_coord=None):
+                   adaptive_inflation=None, vert_coord=None, outlier_threshold=None):
         """Stage 2, after HX has been summed over the shards: obs-space priors, Phase A
         (replicated: identical on every rank) and the sweep of this shard's rows.  `rtps` / `rtpp`:
         posterior relaxation of the shard's rows as in `EnSRF` (row-local: no communication).
         `vert_coord`: vertical localisation as in `EnSRF` -- (nvars, ntimes), n_lead values in slab
-        order -- with the obs' `vert` / `vert_halfwidth` from `ob`."""
+        order -- with the obs' `vert` / `vert_halfwidth` from `ob`.  `outlier_threshold`: the
+        gross-error check as in `EnSRF`; every rank decides alike, from the same summed obs block."""
         if adaptive_inflation is not None:
             raise ValueError("ShardedEnSRF does not support adaptive_inflation (out of scope: use EnSRF on one GPU)")
         eng, M = self.engine, self.M
@@ -248,6 +253,11 @@ class ShardedEnSRF(object):
             eng.set_relaxation(*relax)                                     # every call: "none" included
         elif relax[0] != _lib.RELAX_NONE:
             raise ValueError("this engine does not support posterior relaxation")
+        qc = outlier_setting(outlier_threshold)
+        if hasattr(eng, "set_outlier_threshold"):
+            eng.set_outlier_threshold(qc)                                  # every call: "off" included
+        elif qc is not None:
+            raise ValueError("this engine does not support the outlier check")
         P = int(HX.shape[0])
         vert = self._vertical(ob, vert_coord, P)
         if hasattr(eng, "set_vertical_localization"):
@@ -267,13 +277,15 @@ class ShardedEnSRF(object):
         return diag
 
     def update(self, X_local, post_local, sten_idx, sten_wts, ob, grid_lat=None, grid_lon=None, inflation=None,
-               rtps=None, rtpp=None, adaptive_inflation=None, vert_coord=None):
+               rtps=None, rtpp=None, adaptive_inflation=None, vert_coord=None, outlier_threshold=None):
         if adaptive_inflation is not None:
             raise ValueError("ShardedEnSRF does not support adaptive_inflation (out of scope: use EnSRF on one GPU)")
         self._vertical(ob, vert_coord, int(np.asarray(sten_idx).shape[0]))  # (refused before any work)
+        outlier_setting(outlier_threshold)
         HX = self.partial_estimates(X_local, sten_idx, sten_wts, inflation)
         self.all_reduce_sum(HX)                                            # the one exchange step
-        return self.assimilate(X_local, post_local, HX, ob, grid_lat, grid_lon, rtps=rtps, rtpp=rtpp, vert_coord=vert_coord)
+        return self.assimilate(X_local, post_local, HX, ob, grid_lat, grid_lon, rtps=rtps, rtpp=rtpp, vert_coord=vert_coord,
+                               outlier_threshold=outlier_threshold)
 
     def _vertical(self, ob, vert_coord, P):
         """(lead_vert, ob_vert, ob_vert_halfwidth) for the engine, (None, None, None) when off; ValueError on a bad setting."""

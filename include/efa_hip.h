@@ -153,6 +153,19 @@ int efa_ctx_set_adaptive_inflation(efa_ctx *ctx, double *field_dev, long rows, d
  * phase), option "gc_onepass" is 1 and no adaptive-inflation field is set. */
 int efa_ctx_set_vertical_localization(efa_ctx *ctx, long n_lead, const double *lead_vert, long P, const double *ob_vert,
                                       const double *ob_vert_halfwidth);
+
+/* ---- outlier (gross-error) check ---------------------------
+ * Context state like the relaxation, for every later obs phase
+ * (efa_obs_phase_dev, efa_ensrf_update_dev, efa_ensrf_cycle_dev,
+ * efa_ensrf_update).  With threshold t > 0 each ob the caller asks to
+ * assimilate is checked ONCE per call against the obs block it is handed,
+ * before any ob of the call is assimilated: with d = value - ym[k],
+ * s2 = the variance of Yp[k][0..M-1] (divided by M) and r = error[k], the ob
+ * is kept iff d*d <= t*t*(s2 + r) (a NaN rejects it).  A rejected ob is
+ * treated exactly as one whose assimilate flag is 0; it comes back with
+ * assimilated[k] = 0.  0 turns it off (the default); a negative, NaN or
+ * infinite threshold fails with EFA_ERR_INVALID. */
+int efa_ctx_set_outlier_threshold(efa_ctx *ctx, double threshold);
 int efa_ctx_synchronize(efa_ctx *ctx);
 
 /* ---- device memory for callers without their own allocator -------------*/
