@@ -45,20 +45,18 @@ int fail(int code, const char* fmt, ...) {
     if (_s != EFA_OK) return _s; \
   } while (0)
 
-// grow-only device buffer
+// grow-only device buffer, freed with its owner
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
-  bool view = false;  // p points into another DevBuf (carve): never freed here
-  void carve(void* base, size_t bytes) {
-    if (p && !view) (void)hipFree(p);
-    p = base;
-    cap = bytes;
-    view = true;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
   }
   int reserve(size_t bytes) {
     if (bytes <= cap) return EFA_OK;
-    if (view) return fail(EFA_ERR_INVALID, "internal: reserve() on a carved buffer");
     if (p) {
       hipError_t e = hipFree(p);
       p = nullptr;
@@ -74,12 +72,6 @@ struct DevBuf {
     cap = want;
     return EFA_OK;
   }
-  void release() {
-    if (p && !view) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    view = false;
-  }
   template <typename T>
   T* as() const { return reinterpret_cast<T*>(p); }
 };
@@ -89,6 +81,12 @@ struct DevBuf {
 struct PinBuf {
   void* p = nullptr;
   size_t cap = 0;
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() {
+    if (p) (void)hipHostFree(p);
+  }
   int reserve(size_t bytes) {
     if (bytes <= cap) return EFA_OK;
     if (p) (void)hipHostFree(p);
@@ -103,18 +101,38 @@ struct PinBuf {
     cap = want;
     return EFA_OK;
   }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-  }
 };
+
+// a stream or event the context created, destroyed with it
+template <class H, hipError_t (*Destroy)(H)>
+struct Owned {
+  H h = nullptr;
+  Owned() = default;
+  Owned(const Owned&) = delete;
+  Owned& operator=(const Owned&) = delete;
+  ~Owned() {
+    if (h) (void)Destroy(h);
+  }
+  operator H() const { return h; }
+};
+// a stream finishes its work first (the diagnostic occupier may still hold CUs)
+hipError_t sync_and_destroy(hipStream_t s) {
+  (void)hipStreamSynchronize(s);
+  return hipStreamDestroy(s);
+}
+using OwnedStream = Owned<hipStream_t, sync_and_destroy>;
+using OwnedEvent = Owned<hipEvent_t, hipEventDestroy>;
 
 }  // namespace
 
 struct efa_ctx {
+  // Members are destroyed in reverse order of declaration: the streams and events come first, so every buffer below is
+  // freed before they go away.
+  OwnedStream own_stream;
+  OwnedStream dbg_stream;  // diagnostic occupier (options debug_occupy_*)
+  OwnedEvent ev[7];  // obs phase 0..1; state phase 2..3 and (the fused cycle's second pair) 4..5; 6: Phase A's results on the host (fused cycle)
+  OwnedEvent ev_fs;  // the last host-to-device copy of the forward-operator stencil (pin_fs)
   int device = 0;
-  hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   long obs_batch = 64;
   long path = EFA_PATH_AUTO;
@@ -124,7 +142,6 @@ struct efa_ctx {
   long spin_limit = 4000000;
   long spin_ms = -1;       // wall-time bound of the persistent Phase-A launch; -1: 100 ms + P/100 ms
   int cu_count = 0;
-  hipStream_t dbg_stream = nullptr;  // diagnostic occupier (options debug_occupy_*)
   long dbg_occupy_blocks = 0;
   long pipe_debug = 0;
   long gc_onepass = 1;     // localised state sweep in one pass with per-column-block active lists
@@ -143,15 +160,18 @@ struct efa_ctx {
   const double* ye_ptr = nullptr;  // where Phase B reads the recorded ye rows
   long ye_stride = 0;
   int phase_a_kind = 0;          // 1 vector-chain pipeline, 2 per-batch kernels, 3 Gram leader, 4 band leader
-  DevBuf ob_pack, out_pack;  // the per-ob inputs / diagnostics below are carved out of these two allocations
+  DevBuf ob_pack, out_pack;  // the per-ob inputs / diagnostics below are slices of these two allocations (stage_obs_inputs)
   PinBuf pin_in, pin_out;    // their pinned host images: one H2D and one D2H per call
   PinBuf pin_fs;             // pinned image of the forward-operator stencil
-  hipEvent_t ev_fs = nullptr;  // its last host-to-device copy
   size_t fs_valid_n = 0;       // the device copy fs_idx holds the pinned image's first fs_valid_n stencil entries ...
   const void* fs_valid_dev = nullptr;  // ... if fs_idx and pin_fs are still these allocations
   const void* fs_valid_pin = nullptr;
-  DevBuf ob_val, ob_err, ob_asm, ob_lat, ob_lon, ob_hw, ob_errsq;  // device copies [P] ([P][4] the last)
-  DevBuf d_prior_mean, d_prior_var, d_post_mean, d_post_var, d_assimilated;
+  // in ob_pack: device copies [P] ([P][4] ob_errsq)
+  double *ob_val = nullptr, *ob_err = nullptr, *ob_errsq = nullptr, *ob_lat = nullptr, *ob_lon = nullptr, *ob_hw = nullptr;
+  uint8_t* ob_asm = nullptr;
+  // in out_pack: [P]
+  double *d_prior_mean = nullptr, *d_prior_var = nullptr, *d_post_mean = nullptr, *d_post_var = nullptr;
+  uint8_t* d_assimilated = nullptr;
   DevBuf Yw, ymw;  // obs block workspace [(P+M)][M], [(P+M)]
   DevBuf win_Y, win_m;  // rows of one Phase-A window + the transform rows (only when P exceeds one persistent launch)
   // --- state phase workspaces ---------------------------------------------
@@ -214,7 +234,6 @@ struct efa_ctx {
   int comm_rank = 0, comm_world = 1;
   DevBuf gcc_lat, gcc_lon, gcc_oblat, gcc_oblon, gcc_obhw, gcc_coef, gcc_trig, gcc_cnt, gcc_pairs;  // efa_gc_block_counts
   // --- timing -----------------------------------------------------------------
-  hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // obs phase 0..1; state phase 2..3 and (the fused cycle's second pair) 4..5; 6: Phase A's results on the host (fused cycle)
   double state_ms = 0.0, obs_ms = 0.0;
   bool obs_ms_pending = false;  // ev[0] .. ev[obs_end_ev] of the last obs phase not read yet
   int obs_end_ev = 1;           // 1, or the start event of the state pair a speculative transform was put behind
@@ -539,13 +558,13 @@ int stage_obs_inputs(efa_ctx* c, ObsCall& a, const double* ob_value, const doubl
       std::memcpy(hb + 8 * slot, ob_lon, dP);
       std::memcpy(hb + 9 * slot, ob_hw, dP);
     }
-    c->ob_val.carve(db, slot);
-    c->ob_err.carve(db + slot, slot);
-    c->ob_asm.carve(db + 2 * slot, slot);
-    c->ob_errsq.carve(db + 3 * slot, 4 * slot);
-    c->ob_lat.carve(db + 7 * slot, slot);
-    c->ob_lon.carve(db + 8 * slot, slot);
-    c->ob_hw.carve(db + 9 * slot, slot);
+    c->ob_val = reinterpret_cast<double*>(db);
+    c->ob_err = reinterpret_cast<double*>(db + slot);
+    c->ob_asm = reinterpret_cast<uint8_t*>(db + 2 * slot);
+    c->ob_errsq = reinterpret_cast<double*>(db + 3 * slot);
+    c->ob_lat = reinterpret_cast<double*>(db + 7 * slot);
+    c->ob_lon = reinterpret_cast<double*>(db + 8 * slot);
+    c->ob_hw = reinterpret_cast<double*>(db + 9 * slot);
     a.pack_bytes = gc ? total : 7 * slot;  // goes to the device inside the prep launch (read from the mapped pinned buffer)
     a.islot = slot;
   }
@@ -557,11 +576,11 @@ int stage_obs_inputs(efa_ctx* c, ObsCall& a, const double* ob_value, const doubl
     EFA_TRY(c->out_pack.reserve(5 * a.oslot));
     EFA_TRY(c->pin_out.reserve(5 * a.oslot));
     char* db = static_cast<char*>(c->out_pack.p);
-    c->d_prior_mean.carve(db, a.oslot);
-    c->d_prior_var.carve(db + a.oslot, a.oslot);
-    c->d_post_mean.carve(db + 2 * a.oslot, a.oslot);
-    c->d_post_var.carve(db + 3 * a.oslot, a.oslot);
-    c->d_assimilated.carve(db + 4 * a.oslot, a.oslot);
+    c->d_prior_mean = reinterpret_cast<double*>(db);
+    c->d_prior_var = reinterpret_cast<double*>(db + a.oslot);
+    c->d_post_mean = reinterpret_cast<double*>(db + 2 * a.oslot);
+    c->d_post_var = reinterpret_cast<double*>(db + 3 * a.oslot);
+    c->d_assimilated = reinterpret_cast<uint8_t*>(db + 4 * a.oslot);
   }
   EFA_TRY(c->Yw.reserve((size_t)a.R * M * sizeof(double)));
   EFA_TRY(c->ymw.reserve((size_t)a.R * sizeof(double)));
@@ -637,17 +656,17 @@ int sweep_rows(efa_ctx* c, const ObsCall& a, long b0, int nb, const double* Ye, 
   sw.taper_mode = (a.loc_mode == EFA_LOC_GC) ? kTaperObs : kTaperNone;
   if (a.loc_mode == EFA_LOC_GC && vl_active(c)) {  // horizontal x vertical taper of the batch against every row, in table mode
     EFA_TRY(c->vl_W.reserve((size_t)nb * a.R * sizeof(double)));
-    EFA_HIP(launch_obs_taper_rows(b0, nb, a.R, a.P, c->ob_lat.as<double>(), c->ob_lon.as<double>(), c->ob_hw.as<double>(),
-                                  vl_obvert(c), vl_obvhw(c), c->vl_W.as<double>(), c->stream));
+    EFA_HIP(launch_obs_taper_rows(b0, nb, a.R, a.P, c->ob_lat, c->ob_lon, c->ob_hw, vl_obvert(c), vl_obvhw(c), c->vl_W.as<double>(),
+                                  c->stream));
     sw.taper_mode = kTaperTable;
     sw.W = c->vl_W.as<double>();
     sw.ncol = a.R;  // (row j of the block reads column j of the table)
   }
-  sw.row_lat = c->ob_lat.as<double>();
-  sw.row_lon = c->ob_lon.as<double>();
-  sw.ob_lat = c->ob_lat.as<double>() + b0;
-  sw.ob_lon = c->ob_lon.as<double>() + b0;
-  sw.ob_hw = c->ob_hw.as<double>() + b0;
+  sw.row_lat = c->ob_lat;
+  sw.row_lon = c->ob_lon;
+  sw.ob_lat = c->ob_lat + b0;
+  sw.ob_lon = c->ob_lon + b0;
+  sw.ob_hw = c->ob_hw + b0;
   sw.skip_lo = skip_lo;
   sw.skip_hi = skip_hi;
   sw.taper_rows = a.P;
@@ -673,20 +692,20 @@ int batch_window(efa_ctx* c, const ObsCall& a, long w0, long w1) {
     d.M = a.M;
     d.b0 = b0;
     d.nb = nb;
-    d.ob_value = c->ob_val.as<double>();
-    d.ob_error = c->ob_err.as<double>();
-    d.ob_assim = c->ob_asm.as<uint8_t>();
+    d.ob_value = c->ob_val;
+    d.ob_error = c->ob_err;
+    d.ob_assim = c->ob_asm;
     d.loc_mode = a.loc_mode;
-    d.ob_lat = c->ob_lat.as<double>();
-    d.ob_lon = c->ob_lon.as<double>();
-    d.ob_hw = c->ob_hw.as<double>();
+    d.ob_lat = c->ob_lat;
+    d.ob_lon = c->ob_lon;
+    d.ob_hw = c->ob_hw;
     d.Ye_rec = c->Ye_rec.as<double>();
     d.coef = c->coef.as<double>();
-    d.prior_mean = c->d_prior_mean.as<double>();
-    d.prior_var = c->d_prior_var.as<double>();
-    d.post_mean = c->d_post_mean.as<double>();
-    d.post_var = c->d_post_var.as<double>();
-    d.assimilated = c->d_assimilated.as<uint8_t>();
+    d.prior_mean = c->d_prior_mean;
+    d.prior_var = c->d_prior_var;
+    d.post_mean = c->d_post_mean;
+    d.post_var = c->d_post_var;
+    d.assimilated = c->d_assimilated;
     EFA_HIP(launch_diag(d, c->stream));
     if (active_in(a, b0, nb) == 0 || a.R == nb) continue;
     EFA_TRY(sweep_rows(c, a, b0, nb, c->Ye_rec.as<double>() + (size_t)b0 * a.M, a.M, b0, b0 + nb, a.R));
@@ -743,10 +762,10 @@ int window_pipe_args(efa_ctx* c, const ObsCall& a, const Window& win, PipeArgs* 
   pa.R = Rw;
   pa.P = Pw;
   pa.M = a.M;
-  pa.ob_value = c->ob_val.as<double>() + w0;
-  pa.ob_error = c->ob_err.as<double>() + w0;
-  pa.ob_assim = c->ob_asm.as<uint8_t>() + w0;
-  pa.ob_errsq = c->ob_errsq.as<double>() + 4 * w0;
+  pa.ob_value = c->ob_val + w0;
+  pa.ob_error = c->ob_err + w0;
+  pa.ob_assim = c->ob_asm + w0;
+  pa.ob_errsq = c->ob_errsq + 4 * w0;
   pa.loc_mode = a.loc_mode;
   pa.tw = nullptr;
   if (a.loc_mode == EFA_LOC_GC) {
@@ -755,8 +774,8 @@ int window_pipe_args(efa_ctx* c, const ObsCall& a, const Window& win, PipeArgs* 
     const bool tw_ok = c->geometry_reuse && win.direct && c->tw_serial == c->geo_serial && c->tw_Pw == Pw && c->tw_Rw == Rw &&
                        c->tw_ptr == c->tw_mat.p;
     if (!tw_ok) {
-      EFA_HIP(launch_obs_taper_matrix(Pw, Rw, c->ob_lat.as<double>() + w0, c->ob_lon.as<double>() + w0, c->ob_hw.as<double>() + w0,
-                                      c->gc_obtrig.as<double>(), c->tw_mat.as<double>(), s));
+      EFA_HIP(launch_obs_taper_matrix(Pw, Rw, c->ob_lat + w0, c->ob_lon + w0, c->ob_hw + w0, c->gc_obtrig.as<double>(),
+                                      c->tw_mat.as<double>(), s));
       if (vl_active(c)) EFA_HIP(launch_obs_taper_vert(Pw, Rw, vl_obvert(c) + w0, vl_obvhw(c) + w0, c->tw_mat.as<double>(), s));
       c->tw_serial = win.direct ? c->geo_serial : -1;  // (a window's table is not the whole block's)
       c->tw_Pw = Pw;
@@ -766,11 +785,11 @@ int window_pipe_args(efa_ctx* c, const ObsCall& a, const Window& win, PipeArgs* 
     pa.tw = c->tw_mat.as<double>();
   }
   pa.coef = c->coef.as<double>() + (size_t)w0 * kCoefStride;
-  pa.prior_mean = c->d_prior_mean.as<double>() + w0;
-  pa.prior_var = c->d_prior_var.as<double>() + w0;
-  pa.post_mean = c->d_post_mean.as<double>() + w0;
-  pa.post_var = c->d_post_var.as<double>() + w0;
-  pa.assimilated = c->d_assimilated.as<uint8_t>() + w0;
+  pa.prior_mean = c->d_prior_mean + w0;
+  pa.prior_var = c->d_prior_var + w0;
+  pa.post_mean = c->d_post_mean + w0;
+  pa.post_var = c->d_post_var + w0;
+  pa.assimilated = c->d_assimilated + w0;
   pa.status = c->status.as<int>();
   pa.spin_limit = c->spin_limit;
   pa.spin_ticks = (c->spin_ms >= 0 ? c->spin_ms : 100 + Pw / 100) * 100000L;  // s_memrealtime runs at 100 MHz
@@ -1130,17 +1149,15 @@ int state_gc_onepass(efa_ctx* c, const double* xm_in, const double* Xp_in, doubl
   // the lists hold the obs the CALLER asked to assimilate, as the geometry they are cached by: an ob the outlier check rejected
   // stays in them with its inactive record (zero gains), so a later cycle that keeps it finds it there
   const double* act = c->qc_used ? c->qc_act.as<double>() : c->coef.as<double>();
-  EFA_HIP(launch_gc_bound(ncol, P, c->glat.as<double>(), c->ob_lat.as<double>(), c->ob_hw.as<double>(),
-                          act, c->gc_ub.as<int>(), c->gc_off.as<long>(), s));
+  EFA_HIP(launch_gc_bound(ncol, P, c->glat.as<double>(), c->ob_lat, c->ob_hw, act, c->gc_ub.as<int>(), c->gc_off.as<long>(), s));
   long cap = 0;  // the only host round trip of the build: 8 bytes, the capacity the lists need
   EFA_HIP(hipMemcpyAsync(&cap, c->gc_off.as<long>() + nblk, sizeof(long), hipMemcpyDeviceToHost, s));
   EFA_HIP(hipStreamSynchronize(s));
   EFA_TRY(c->gc_idx.reserve((size_t)(cap ? cap : 1) * sizeof(int)));
   EFA_TRY(c->gc_wts.reserve((size_t)(cap ? cap : 1) * 16 * sizeof(double)));
-  EFA_HIP(launch_gc_fill(ncol, P, c->glat.as<double>(), c->glon.as<double>(), c->ob_lat.as<double>(),
-                         c->ob_lon.as<double>(), c->ob_hw.as<double>(), act, c->gc_obtrig.as<double>(),
-                         c->gc_off.as<long>(), c->gc_cnt.as<int>(), c->gc_idx.as<int>(), c->gc_wts.as<double>(), c->gc_order.as<int>(),
-                         c->gc_pairs.as<unsigned long long>(), s));
+  EFA_HIP(launch_gc_fill(ncol, P, c->glat.as<double>(), c->glon.as<double>(), c->ob_lat, c->ob_lon, c->ob_hw, act,
+                         c->gc_obtrig.as<double>(), c->gc_off.as<long>(), c->gc_cnt.as<int>(), c->gc_idx.as<int>(),
+                         c->gc_wts.as<double>(), c->gc_order.as<int>(), c->gc_pairs.as<unsigned long long>(), s));
   c->gc_list_valid = true;
   c->gc_list_geo = c->geo_serial;
   c->gc_list_grid = c->grid_serial;
@@ -1173,7 +1190,7 @@ int state_gc_onepass(efa_ctx* c, const double* xm_in, const double* Xp_in, doubl
   g.fused_members = fused_members;
   if (c->ai_field) {  // the per-ob scalars of the inflation update, from Phase A's records and diagnostics
     EFA_TRY(c->ai_ob.reserve((size_t)(P ? P : 1) * 4 * sizeof(double)));
-    EFA_HIP(launch_adapt_obs(P, M, c->coef.as<double>(), c->d_prior_var.as<double>(), c->ob_err.as<double>(), c->ye_ptr, c->ye_stride,
+    EFA_HIP(launch_adapt_obs(P, M, c->coef.as<double>(), c->d_prior_var, c->ob_err, c->ye_ptr, c->ye_stride,
                              c->ai_ob.as<double>(), s));
     c->state_launches++;
     g.infl = c->ai_field;
@@ -1221,9 +1238,8 @@ int state_sweeps(efa_ctx* c, long rows, const double* xm_in, const double* Xp_in
     a.skip_lo = a.skip_hi = -1;
     if (c->loc_mode == EFA_LOC_GC) {
       EFA_TRY(c->W.reserve((size_t)B * ncol * sizeof(double)));
-      EFA_HIP(launch_taper_table(ncol, nb, c->glat.as<double>(), c->glon.as<double>(),
-                                 c->ob_lat.as<double>() + b0, c->ob_lon.as<double>() + b0,
-                                 c->ob_hw.as<double>() + b0, c->W.as<double>(), s));
+      EFA_HIP(launch_taper_table(ncol, nb, c->glat.as<double>(), c->glon.as<double>(), c->ob_lat + b0, c->ob_lon + b0, c->ob_hw + b0,
+                                 c->W.as<double>(), s));
       a.taper_mode = kTaperTable;
       a.W = c->W.as<double>();
       a.ncol = ncol;
@@ -1347,16 +1363,16 @@ int efa_ctx_create(int device_id, efa_ctx** out) {
   if (!c) return fail(EFA_ERR_INVALID, "out of host memory");
   c->device = device_id;
   c->cu_count = prop.multiProcessorCount;
-  hipError_t es = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
+  hipError_t es = hipStreamCreateWithFlags(&c->own_stream.h, hipStreamNonBlocking);
   if (es != hipSuccess) {
     delete c;
     return fail(EFA_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(es));
   }
   c->stream = c->own_stream;
   for (int i = 0; i < 7; ++i) {
-    hipError_t ee = hipEventCreate(&c->ev[i]);
+    hipError_t ee = hipEventCreate(&c->ev[i].h);
     if (ee != hipSuccess) {
-      efa_ctx_destroy(c);
+      delete c;
       return fail(EFA_ERR_HIP, "hipEventCreate failed: %s", hipGetErrorString(ee));
     }
   }
@@ -1369,24 +1385,6 @@ int efa_ctx_destroy(efa_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(c->comm);
-  c->comm = nullptr;
-  c->pin_in.release();
-  c->pin_out.release();
-  c->pin_fs.release();
-  c->pin_grid.release();
-  if (c->ev_fs) (void)hipEventDestroy(c->ev_fs);
-  DevBuf* bufs[] = {&c->ob_pack, &c->out_pack, &c->Ye_rec, &c->coef, &c->ob_val, &c->ob_err, &c->ob_asm, &c->ob_lat, &c->ob_lon, &c->ob_hw, &c->ob_errsq,
-                    &c->d_prior_mean, &c->d_prior_var, &c->d_post_mean, &c->d_post_var, &c->d_assimilated,
-                    &c->Yw, &c->ymw, &c->win_Y, &c->win_m, &c->traj, &c->tw_mat, &c->status, &c->dbg, &c->W, &c->gc_cnt, &c->gc_ub, &c->gc_order, &c->gc_obtrig, &c->gc_off, &c->gc_idx, &c->gc_wts, &c->gc_pairs, &c->glat, &c->glon, &c->xm_ws, &c->fs_idx, &c->fs_wts, &c->f_glat, &c->f_glon, &c->f_sl, &c->f_cl, &c->f_valids, &c->f_var, &c->f_time, &c->f_lat, &c->f_lon, &c->f_near, &c->f_idx, &c->f_wts, &c->f_status, &c->h_xm, &c->h_Xp, &c->h_ym, &c->h_Yp,
-                    &c->gcc_lat, &c->gcc_lon, &c->gcc_oblat, &c->gcc_oblon, &c->gcc_obhw, &c->gcc_coef, &c->gcc_trig, &c->gcc_cnt, &c->gcc_pairs, &c->ai_ob, &c->vl_dev, &c->vl_W, &c->qc_act};
-  for (DevBuf* b : bufs) b->release();
-  for (int i = 0; i < 7; ++i)
-    if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-  if (c->dbg_stream) {
-    (void)hipStreamSynchronize(c->dbg_stream);
-    (void)hipStreamDestroy(c->dbg_stream);
-  }
-  if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
   return EFA_OK;
 }
@@ -1437,7 +1435,7 @@ int efa_ctx_set_option(efa_ctx* c, const char* key, long value) {
   } else if (!strcmp(key, "debug_occupy_ms")) {
     // diagnostic: on a stream of its own, debug_occupy_blocks workgroups hold 120 KB of LDS each (one per CU, and no
     // persistent Phase-A workgroup fits beside one) for `value` ms; value 0 waits for them to finish
-    if (!c->dbg_stream) EFA_HIP(hipStreamCreateWithFlags(&c->dbg_stream, hipStreamNonBlocking));
+    if (!c->dbg_stream) EFA_HIP(hipStreamCreateWithFlags(&c->dbg_stream.h, hipStreamNonBlocking));
     if (value > 0) EFA_HIP(efa::launch_occupy((int)c->dbg_occupy_blocks, 120 * 1024, (double)value, c->dbg_stream));
     else EFA_HIP(hipStreamSynchronize(c->dbg_stream));
   } else if (!strcmp(key, "threads_hint")) {
@@ -1639,7 +1637,7 @@ int efa_forward_stencil_dev(efa_ctx* c, long rows, long row_offset, int M, const
   const size_t half = (n * sizeof(int64_t) + 255) & ~(size_t)255;
   EFA_TRY(c->fs_idx.reserve(2 * half));
   EFA_TRY(c->pin_fs.reserve(2 * half));
-  if (!c->ev_fs) EFA_HIP(hipEventCreateWithFlags(&c->ev_fs, hipEventDisableTiming));
+  if (!c->ev_fs) EFA_HIP(hipEventCreateWithFlags(&c->ev_fs.h, hipEventDisableTiming));
   else EFA_HIP(hipEventSynchronize(c->ev_fs));
   // A fixed observing network hands over the same stencil cycle after cycle: when the pinned image still holds exactly these
   // indices and weights, the device copy made from it is current and nothing is copied (the copy itself is 8 us at 1e4 obs, but

@@ -387,3 +387,76 @@ def test_nearest_four_on_a_global_grid_with_mirror_ties():
         if np.all(np.diff(d5) > 1e-9 * d5[1:]):
             assert sorted(got.tolist()) == sorted(ref.tolist())
         assert abs(wts[k].sum() - 1.0) < 1e-14
+
+
+# ---------------------------------------------------------------------------
+# efa_ctx_destroy: a closed context gives back the device memory it took
+# ---------------------------------------------------------------------------
+def test_closed_contexts_give_their_device_memory_back():
+    """Round after round on a fresh context: the cycles that allocate the relaxation's workspaces -- an in-place RTPP sweep
+    (the prior copied before the sweep writes over it, [rows][M]), RTPS on the localised one-pass sweep (row spreads), RTPP
+    folded into the transform -- the stencil's event and the block counts, then close().  The device's free memory comes
+    back: the drift over K rounds stays well under one prior copy (a leak of it would be K copies)."""
+    import torch
+    from efa_xray_amd import _lib
+    dev = torch.device("cuda", 0)
+    N, M, P, K = 500_000, 100, 64, 8
+    prior_bytes = N * M * 8                                  # 400 MB: what one leaked prior copy would cost
+    Xp = torch.empty((N, M), dtype=torch.float64, device=dev)
+    xm = torch.empty(N, dtype=torch.float64, device=dev)
+    Yp = torch.empty((P, M), dtype=torch.float64, device=dev)
+    ym = torch.empty(P, dtype=torch.float64, device=dev)
+    # a small localised problem for the cycles on resident members
+    rng = np.random.default_rng(21)
+    ny, nx, n_lead, m, p = 12, 16, 2, 20, 30
+    lat, lon = np.meshgrid(np.linspace(20, 60, ny), np.linspace(200, 280, nx), indexing="ij")
+    rows = n_lead * ny * nx
+    X = rng.standard_normal((rows, 1)) + 2.0 * rng.standard_normal((rows, m))
+    pick = rng.choice(rows, p, replace=False)
+    HX = X[pick]
+    col = pick % (ny * nx)
+    ob = dict(ob_value=HX.mean(axis=1) + rng.standard_normal(p), ob_error=np.ones(p), ob_assim=np.ones(p, dtype=bool),
+              ob_lat=lat.reshape(-1)[col], ob_lon=lon.reshape(-1)[col], ob_halfwidth=np.full(p, 1500.0))
+    Xs, post, HXs = (torch.from_numpy(a).to(dev) for a in (X, np.zeros_like(X), np.zeros_like(HX)))
+    ys = torch.from_numpy(HX.mean(axis=1)).to(dev)
+    Ys = torch.from_numpy(HX - HX.mean(axis=1, keepdims=True)).to(dev)
+    torch.cuda.synchronize()                                 # (the contexts work on streams of their own)
+
+    def ptr(t):
+        return t.data_ptr()
+
+    def one_round(seed):
+        ctx = _lib.Context(0)
+        try:
+            ctx.fill_synthetic(N, 0, M, seed, 1.0, ptr(Xp))
+            ctx.form_perts(N, M, ptr(Xp), ptr(xm), ptr(Xp))
+            ctx.fill_synthetic(P, 0, M, seed, 1.0, ptr(Yp))
+            ctx.form_perts(P, M, ptr(Yp), ptr(ym), ptr(Yp))
+            # in place on the sweeps: RTPP keeps a copy of the prior rows
+            ctx.set_option("path", _lib.PATH_SWEEP)
+            ctx.set_relaxation(_lib.RELAX_RTPP, 0.5)
+            ctx.ensrf_update_dev(N, M, P, ptr(xm), ptr(Xp), ptr(ym), ptr(Yp), np.zeros(P), np.ones(P), np.ones(P, dtype=bool))
+            # localised, on resident members: RTPS around the one-pass sweep keeps the row spreads
+            ctx.set_option("path", _lib.PATH_AUTO)
+            ctx.set_relaxation(_lib.RELAX_RTPS, 0.9)
+            ctx.ensrf_cycle(rows, m, p, ptr(Xs), ptr(post), ptr(ys), ptr(Ys), loc_mode=_lib.LOC_GC, grid_lat=lat,
+                            grid_lon=lon, n_lead=n_lead, **ob)
+            # unlocalised, through the transform: RTPP folded into T
+            ctx.set_option("path", _lib.PATH_TRANSFORM)
+            ctx.set_relaxation(_lib.RELAX_RTPP, 0.5)
+            ctx.ensrf_cycle(rows, m, p, ptr(Xs), ptr(post), ptr(ys), ptr(Ys), **ob)
+            ctx.forward_stencil(rows, 0, m, ptr(Xs), pick[:, None], np.ones((p, 1)), ptr(HXs))
+            ctx.gc_block_counts(lat, lon, ob["ob_lat"], ob["ob_lon"], ob["ob_halfwidth"], ob["ob_assim"])
+            ctx.synchronize()
+        finally:
+            ctx.close()
+        torch.cuda.empty_cache()
+
+    one_round(0)                                             # first launches and the runtime's own one-time allocations
+    free0 = torch.cuda.mem_get_info(dev)[0]
+    for k in range(1, K + 1):
+        one_round(k)
+    drift = free0 - torch.cuda.mem_get_info(dev)[0]
+    assert drift < prior_bytes // 2, "%d closed contexts kept %.1f MiB of device memory" % (K, drift / 2**20)
+    assert torch.isfinite(Xp).all() and torch.isfinite(post).all()
+    assert_parity(HXs.cpu().numpy(), HX, "the stencil's estimates")
