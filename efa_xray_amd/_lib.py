@@ -326,6 +326,10 @@ class Context(object):
     def set_stream(self, hip_stream):
         _check(self.lib, self.lib.efa_ctx_set_stream(self.handle, ctypes.c_void_p(hip_stream or 0)))
 
+    def use_own_stream(self):
+        """Back to the context's private non-blocking stream (option "own_stream")."""
+        self.set_option("own_stream", 1)
+
     def synchronize(self):
         _check(self.lib, self.lib.efa_ctx_synchronize(self.handle))
 

@@ -132,6 +132,7 @@ struct efa_ctx {
   OwnedStream dbg_stream;  // diagnostic occupier (options debug_occupy_*)
   OwnedEvent ev[7];  // obs phase 0..1; state phase 2..3 and (the fused cycle's second pair) 4..5; 6: Phase A's results on the host (fused cycle)
   OwnedEvent ev_fs;  // the last host-to-device copy of the forward-operator stencil (pin_fs)
+  OwnedEvent ev_order;  // a change of stream: recorded on the stream that is left, waited for by the one that takes over
   int device = 0;
   hipStream_t stream = nullptr;
   long obs_batch = 64;
@@ -1376,6 +1377,13 @@ int efa_ctx_create(int device_id, efa_ctx** out) {
       return fail(EFA_ERR_HIP, "hipEventCreate failed: %s", hipGetErrorString(ee));
     }
   }
+  {
+    hipError_t ee = hipEventCreateWithFlags(&c->ev_order.h, hipEventDisableTiming);
+    if (ee != hipSuccess) {
+      delete c;
+      return fail(EFA_ERR_HIP, "hipEventCreate failed: %s", hipGetErrorString(ee));
+    }
+  }
   *out = c;
   return EFA_OK;
 }
@@ -1389,11 +1397,24 @@ int efa_ctx_destroy(efa_ctx* c) {
   return EFA_OK;
 }
 
+namespace {
+// The calls return with work still in the stream, and that work reads the context's own workspaces (the transform [T | w] behind
+// the obs rows, the recorded trajectory, the active lists, the grid, the pair counter).  What is issued after a change of stream
+// is therefore ordered behind everything issued before it: an event on the stream that is left, waited for on the device by the
+// one that takes over.  No host wait; NULL (the legacy default stream) is a stream like any other here.
+int change_stream(efa_ctx* c, hipStream_t to) {
+  if (to == c->stream) return EFA_OK;
+  EFA_HIP(hipEventRecord(c->ev_order, c->stream));
+  EFA_HIP(hipStreamWaitEvent(to, c->ev_order, 0));
+  c->stream = to;
+  return EFA_OK;
+}
+}  // namespace
+
 int efa_ctx_set_stream(efa_ctx* c, void* hip_stream) {
   EFA_TRY(use(c));
   // NULL is a valid handle: the device's legacy default stream (what torch uses unless told otherwise)
-  c->stream = reinterpret_cast<hipStream_t>(hip_stream);
-  return EFA_OK;
+  return change_stream(c, reinterpret_cast<hipStream_t>(hip_stream));
 }
 
 int efa_ctx_set_option(efa_ctx* c, const char* key, long value) {
@@ -1422,7 +1443,7 @@ int efa_ctx_set_option(efa_ctx* c, const char* key, long value) {
   } else if (!strcmp(key, "geometry_reuse")) {
     c->geometry_reuse = value ? 1 : 0;
   } else if (!strcmp(key, "own_stream")) {
-    c->stream = c->own_stream;  // back to the context's private non-blocking stream
+    EFA_TRY(change_stream(c, c->own_stream));  // back to the context's private non-blocking stream
   } else if (!strcmp(key, "pipe_debug")) {
     c->pipe_debug = value;
   } else if (!strcmp(key, "spin_limit")) {
@@ -1435,7 +1456,14 @@ int efa_ctx_set_option(efa_ctx* c, const char* key, long value) {
   } else if (!strcmp(key, "debug_occupy_ms")) {
     // diagnostic: on a stream of its own, debug_occupy_blocks workgroups hold 120 KB of LDS each (one per CU, and no
     // persistent Phase-A workgroup fits beside one) for `value` ms; value 0 waits for them to finish
-    if (!c->dbg_stream) EFA_HIP(hipStreamCreateWithFlags(&c->dbg_stream.h, hipStreamNonBlocking));
+    if (!c->dbg_stream) {
+      // On a stream of the highest priority: the runtime keeps the hardware queues of each priority apart, so the occupier never
+      // lands in the queue the context's own (default-priority) stream was given -- which, with few hardware queues and many
+      // streams created in the process before, it otherwise can, and then it runs in front of Phase A instead of beside it.
+      int least = 0, greatest = 0;
+      EFA_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+      EFA_HIP(hipStreamCreateWithPriority(&c->dbg_stream.h, hipStreamNonBlocking, greatest));
+    }
     if (value > 0) EFA_HIP(efa::launch_occupy((int)c->dbg_occupy_blocks, 120 * 1024, (double)value, c->dbg_stream));
     else EFA_HIP(hipStreamSynchronize(c->dbg_stream));
   } else if (!strcmp(key, "threads_hint")) {

@@ -72,7 +72,13 @@ int efa_ctx_create(int device_id, efa_ctx **out);
 int efa_ctx_destroy(efa_ctx *ctx);
 /* issue all work on the caller's hipStream_t (e.g. torch's current stream).
  * NULL is the device's legacy default stream.  A new context uses a private
- * non-blocking stream; efa_ctx_set_option(ctx, "own_stream", 1) returns to it. */
+ * non-blocking stream; efa_ctx_set_option(ctx, "own_stream", 1) returns to it.
+ * Several calls return with work still in the stream, and that work reads the
+ * context's own workspaces: work issued after a change of stream is ordered
+ * behind everything the context issued before it (an event on the stream that
+ * is left, waited for on the device by the one that takes over; the host does
+ * not wait; the stream that is left must still exist at that moment).  The
+ * caller's own work on either stream is not ordered by this. */
 int efa_ctx_set_stream(efa_ctx *ctx, void *hip_stream);
 /* options: "obs_batch" (obs fused per sweep launch, 1..64, default 64),
  *          "path" (EFA_PATH_*), "timing" (0/1/2, see efa_last_timing), "pipeline" (1: run Phase A as
