@@ -6,6 +6,7 @@ missing, or no gfx950 device is usable, the calls below raise.
 import ctypes
 import os
 import sys
+import threading
 
 import numpy as np
 
@@ -93,6 +94,13 @@ SIGNATURES = {
                                            c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                            ctypes.c_long, ctypes.c_long,
                                            c_double_p, c_double_p, c_double_p, c_double_p, c_uint8_p]),
+    "efa_ensrf_cycle_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_void_pp, c_void_pp, ctypes.POINTER(ctypes.c_long),
+                                            ctypes.c_long, ctypes.c_int, ctypes.c_long, c_double_p, ctypes.c_long,
+                                            c_double_p, c_double_p, c_uint8_p, ctypes.c_int,
+                                            c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                            c_double_p, c_double_p, c_double_p, c_double_p, c_uint8_p]),
+    "efa_pinned_alloc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, c_void_pp]),
+    "efa_pinned_free": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "efa_ensrf_update": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_int,
                                         ctypes.c_long, c_double_p, c_double_p,
                                         c_double_p, c_double_p, c_uint8_p, ctypes.c_int,
@@ -194,6 +202,56 @@ def _u8p(a):
     return a.ctypes.data_as(c_uint8_p)
 
 
+def plan_chunks(ncol, chunk_cols):
+    """The column chunks [(lo, hi), ...] of a streamed update (efa_ensrf_cycle_host): contiguous, covering [0, ncol), every cut on
+    a multiple of 16 columns (the one-pass sweep's block), the last chunk taking the ragged rest.  A budget below one block gives
+    one block per chunk."""
+    ncol, chunk_cols = int(ncol), int(chunk_cols)
+    if ncol < 0 or chunk_cols < 1:
+        raise ValueError("plan_chunks: need ncol >= 0 and chunk_cols >= 1, got %d and %d" % (ncol, chunk_cols))
+    cc = max(16, chunk_cols // 16 * 16)
+    return [(lo, min(lo + cc, ncol)) for lo in range(0, ncol, cc)]
+
+
+def default_chunk_cols(n_lead, M, target_bytes=64 << 20):
+    """Columns per chunk for a chunk of about `target_bytes` (n_lead slabs of M float64 members per column)."""
+    return max(16, int(target_bytes // max(1, int(n_lead) * int(M) * 8)) // 16 * 16)
+
+
+def compact_stencil(idx):
+    """(rows, cidx) for a stencil `idx` of global state rows (any shape, -1 unused): `rows` the distinct rows it names, ascending,
+    and `cidx` the same stencil with every entry replaced by its position in `rows` (-1 stays -1).  Applying `cidx` to the
+    gathered rows X[rows] is applying `idx` to X, entry by entry in the same order."""
+    idx = np.asarray(idx, dtype=np.int64)
+    used = idx >= 0
+    rows = np.unique(idx[used])
+    cidx = np.full(idx.shape, -1, dtype=np.int64)
+    cidx[used] = np.searchsorted(rows, idx[used])
+    return rows, cidx
+
+
+class PinnedBlock(object):
+    """One block of efa_pinned_alloc, exposed through the array interface: `np.asarray(block)` is a writable float64 view whose
+    base keeps the block alive; the block goes back to its context's pool when the last view is collected."""
+
+    def __init__(self, ctx, nbytes):
+        self.ctx = ctx
+        self.nbytes = int(nbytes)
+        self.ptr = ctx._pinned_take(self.nbytes)
+
+    @property
+    def __array_interface__(self):
+        return {"shape": (self.nbytes // 8,), "typestr": "<f8", "data": (self.ptr, False), "version": 3}
+
+    def __del__(self):
+        try:
+            if self.ptr:
+                self.ctx._pinned_give(self.ptr, self.nbytes)
+            self.ptr = None
+        except Exception:
+            pass
+
+
 class DeviceArray(object):
     """A float64 array in the context GPU's HBM (hipMalloc via efa_malloc)."""
 
@@ -269,11 +327,18 @@ class Context(object):
         _check(self.lib, self.lib.efa_ctx_create(int(device), ctypes.byref(h)))
         self.handle = h
         self.device = int(device)
+        self._pinned_lock = threading.RLock()   # a block may be collected, and given back, on any thread
+        self._pinned_pool = {}       # nbytes -> [host addresses] of blocks no array uses any more
+        self._pinned_pooled = 0      # bytes in the pool
+        self.pinned_live = 0         # bytes of efa_pinned_alloc blocks, pooled ones included
+        self.pinned_pool_limit = 4096 << 20
 
     def close(self):
+        """Destroys the context; blocks of `pinned_empty` still alive are freed with it (their arrays must not be used after)."""
         if self.handle is not None:
             self.lib.efa_ctx_destroy(self.handle)
             self.handle = None
+            self._pinned_pool, self._pinned_pooled, self.pinned_live = {}, 0, 0
 
     def __del__(self):
         try:
@@ -340,6 +405,114 @@ class Context(object):
     def to_device(self, host):
         host = np.ascontiguousarray(host, dtype=np.float64)
         return DeviceArray(self, host.shape).upload(host)
+
+    # -- page-locked host memory the context owns (efa_pinned_alloc) ------------
+    def _pinned_take(self, nbytes):
+        with self._pinned_lock:
+            pool = self._pinned_pool.get(nbytes)
+            if pool:
+                self._pinned_pooled -= nbytes
+                return pool.pop()
+            ptr = ctypes.c_void_p()
+            _check(self.lib, self.lib.efa_pinned_alloc(self.handle, nbytes, ctypes.byref(ptr)))
+            self.pinned_live += nbytes
+            return ptr.value
+
+    def _pinned_give(self, ptr, nbytes):
+        with self._pinned_lock:
+            if self.handle is None:      # the context is gone, and the block with it
+                return
+            if self._pinned_pooled + nbytes <= self.pinned_pool_limit:
+                # kept for the next array of this size: page-locking a block costs more than moving its bytes over the link
+                self._pinned_pool.setdefault(nbytes, []).append(ptr)
+                self._pinned_pooled += nbytes
+                return
+            self.pinned_live -= nbytes
+            self.lib.efa_pinned_free(self.handle, ctypes.c_void_p(ptr))
+
+    def pinned_in_use(self):
+        """Bytes of this context's page-locked blocks that arrays still use."""
+        return self.pinned_live - self._pinned_pooled
+
+    def pinned_trim(self, keep=()):
+        """Free the pooled blocks no array uses, but one block per entry of `keep` (block sizes in bytes) where the pool has it."""
+        with self._pinned_lock:
+            keep = list(keep)
+            pool = {}
+            for nbytes, ptrs in self._pinned_pool.items():
+                for ptr in ptrs:
+                    if nbytes in keep:
+                        keep.remove(nbytes)
+                        pool.setdefault(nbytes, []).append(ptr)
+                        continue
+                    self.pinned_live -= nbytes
+                    self._pinned_pooled -= nbytes
+                    self.lib.efa_pinned_free(self.handle, ctypes.c_void_p(ptr))
+            self._pinned_pool = pool
+
+    def pinned_reserve(self, sizes, limit):
+        """True if arrays of these sizes (bytes) may be taken from `pinned_empty` with at most `limit` bytes of this context's
+        page-locked memory in use afterwards.  Pooled blocks of these sizes are kept for them; other pooled blocks are freed when
+        the new blocks would otherwise take the context's total above the limit."""
+        with self._pinned_lock:
+            sizes = [max(int(n), 8) for n in sizes]
+            if self.pinned_in_use() + sum(sizes) > limit:
+                return False
+            fresh, have = 0, dict((n, len(p)) for n, p in self._pinned_pool.items())
+            for n in sizes:
+                if have.get(n, 0) > 0:
+                    have[n] -= 1
+                else:
+                    fresh += n
+            if self.pinned_live + fresh > limit:
+                self.pinned_trim(keep=sizes)
+            return True
+
+    def pinned_empty(self, shape):
+        """A writable C-contiguous float64 array in page-locked memory of this context: `efa_ensrf_cycle_host` moves it by DMA
+        without staging.  The memory goes back to the context when the array (and every view of it) is collected."""
+        shape = tuple(int(v) for v in np.atleast_1d(shape))
+        n = int(np.prod(shape, dtype=np.int64))
+        return np.asarray(PinnedBlock(self, max(n, 1) * 8))[:n].reshape(shape)
+
+    def ensrf_cycle_host(self, seg_prior, seg_post, ncol, M, HX, chunk_cols, ob_value, ob_error, ob_assim, loc_mode=LOC_NONE,
+                         ob_lat=None, ob_lon=None, ob_halfwidth=None, grid_lat=None, grid_lon=None):
+        """efa_ensrf_cycle_host: one whole cycle on a prior in host memory, streamed through the device in chunks of `chunk_cols`
+        columns.  seg_prior / seg_post: lists of C-contiguous float64 arrays (slabs, ncol, M) -- any leading shape that flattens
+        to it -- one per variable; the posterior is written into seg_post.  Returns the diagnostics."""
+        n_seg = len(seg_prior)
+        assert len(seg_post) == n_seg
+        slabs = (ctypes.c_long * max(n_seg, 1))()
+        pin = (ctypes.c_void_p * max(n_seg, 1))()
+        pout = (ctypes.c_void_p * max(n_seg, 1))()
+        for v, (a, b) in enumerate(zip(seg_prior, seg_post)):
+            for x in (a, b):
+                assert x.dtype == np.float64 and x.flags["C_CONTIGUOUS"]
+            assert a.shape == b.shape and b.flags["WRITEABLE"]
+            assert ncol * M == 0 or a.size % (ncol * M) == 0
+            slabs[v] = a.size // (ncol * M) if ncol * M else 0
+            pin[v] = a.ctypes.data
+            pout[v] = b.ctypes.data
+        P = 0 if HX is None else int(HX.shape[0])
+        if P:
+            HX = np.ascontiguousarray(HX, dtype=np.float64)
+            assert HX.shape == (P, M)
+        val, err, asm, lat, lon, hw = self._ob_arrays(P, ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon, ob_halfwidth)
+        glat, glon, gcol = self._grid(loc_mode, grid_lat, grid_lon)
+        if loc_mode == LOC_GC:
+            assert gcol == ncol
+        d = self._diag_arrays(P)
+        _check(self.lib, self.lib.efa_ensrf_cycle_host(
+            self.handle, n_seg, ctypes.cast(pin, c_void_pp), ctypes.cast(pout, c_void_pp), slabs, int(ncol), int(M), P,
+            _dp(HX) if P else None, int(chunk_cols), _dp(val), _dp(err), _u8p(asm), loc_mode, _dp(lat), _dp(lon), _dp(hw),
+            _dp(glat), _dp(glon), _dp(d["prior_mean"]), _dp(d["prior_var"]), _dp(d["post_mean"]), _dp(d["post_var"]),
+            _u8p(d["assimilated"])))
+        d["assimilated"] = d["assimilated"].astype(bool)
+        return d
+
+    def stream_stats(self):
+        """The read-only options about the last streamed update."""
+        return dict((k, self.get_option("stream_" + k)) for k in ("chunks", "peak_bytes", "h2d_us", "d2h_us", "wall_us"))
 
     # -- kernels --------------------------------------------------------------
     @staticmethod

@@ -219,6 +219,54 @@ class Assimilation(object):
         ctx.forward_interp(ncol, 0, ncol, nvar * nt, M, X_dev, HX)
         return HX
 
+    def _interp_stencils_host(self, ctx):
+        """(idx (P, 8) global state rows, wts (P, 8)) of the reference's default forward operator for every ob, built on the
+        device by `efa_interp_stencils`; ValueError for an ob that cannot be interpolated."""
+        prior = self.prior
+        names = prior.vars()
+        try:
+            ob_var = [names.index(ob.obtype) for ob in self.obs]
+        except ValueError as e:
+            raise KeyError("observation type not in the state: %s" % e)
+        vt, ot = self._time_axis()
+        nvar, nt, ny, nx, M = prior.shape()
+        idx, wts, status = ctx.interp_stencils(nvar, nt, ny, nx, prior.coords["lat"], prior.coords["lon"], vt, ob_var, ot,
+                                               [float(ob.lat) for ob in self.obs], [float(ob.lon) for ob in self.obs],
+                                               want_host=True)
+        if status.any():
+            k = int(np.nonzero(status)[0][0])
+            raise ValueError("observation %d cannot be interpolated (status %d: 1 time outside the state's valid times, "
+                             "2 grid index out of range for 1-D lat/lon, 3 bad variable index)" % (k, status[k]))
+        return idx, wts
+
+    def gather_state_rows(self, rows):
+        """to_vect()[rows] as a new (len(rows), nmems) array, gathered from the variables' own arrays: no stacked copy of the
+        state is made."""
+        prior = self.prior
+        rows = np.asarray(rows, dtype=np.int64)
+        per = prior.ntimes() * prior.ny() * prior.nx()
+        M = prior.nmems()
+        out = np.empty((rows.size, M), dtype=np.float64)
+        iv = rows // per
+        for v, name in enumerate(prior.vars()):
+            sel = iv == v
+            if sel.any():
+                out[sel] = prior.variables[name].reshape(per, M)[rows[sel] - v * per]
+        return out
+
+    def streamed_ob_estimates(self, ctx):
+        """(P, M) host array of the default forward operator's estimates WITHOUT a resident state (the streamed update): the
+        distinct stencil rows (at most 8 per ob) are gathered from the variables into a compact array, uploaded, and the stencil
+        is applied to it with compacted indices by `efa_forward_stencil_dev` -- entry by entry in the order
+        `efa_forward_interp_dev` sums them on the resident state, so the estimates have the same bits."""
+        idx, wts = self._interp_stencils_host(ctx)
+        rows, cidx = _lib.compact_stencil(idx)
+        P, M = len(self.obs), self.prior.nmems()
+        Xc = ctx.to_device(self.gather_state_rows(rows)) if rows.size else ctx.empty((1, M))
+        HX = ctx.empty((P, M))
+        ctx.forward_stencil(rows.size, 0, M, Xc, cidx, wts, HX)
+        return HX.download()
+
     def compute_ob_estimates(self, X_dev=None):
         """(P, M) ensemble estimates HX[k] = ob_k.estimate(prior): the forward operator loop of
         assimilation.py:45-46.  With the reference's own point-interpolation operator the whole loop runs on

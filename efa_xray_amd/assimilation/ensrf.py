@@ -76,6 +76,22 @@ def ob_vertical(obs):
     return ov, oh
 
 
+def stream_setting(streamed, chunk_cols, pinned_limit_mb, adaptive=None):
+    """(streamed, chunk_cols or None, pinned limit in bytes) from the `streamed` / `stream_chunk_cols` /
+    `stream_pinned_limit_mb` keywords; ValueError on a setting that is not supported."""
+    streamed = bool(streamed)
+    if chunk_cols is not None:
+        if isinstance(chunk_cols, bool) or not isinstance(chunk_cols, numbers.Integral) or chunk_cols < 1:
+            raise ValueError("stream_chunk_cols must be a positive integer or None, got %r" % (chunk_cols,))
+        chunk_cols = int(chunk_cols)
+    if isinstance(pinned_limit_mb, bool) or not isinstance(pinned_limit_mb, numbers.Real) or not pinned_limit_mb >= 0:
+        raise ValueError("stream_pinned_limit_mb must be a number >= 0, got %r" % (pinned_limit_mb,))
+    if streamed and adaptive is not None:
+        raise ValueError("streamed=True cannot be combined with adaptive_inflation (its field update needs the whole state "
+                         "resident, DESIGN.md 7f)")
+    return streamed, chunk_cols, int(float(pinned_limit_mb) * (1 << 20))
+
+
 def outlier_setting(threshold):
     """The outlier threshold as a float, or None when off; ValueError unless a finite number > 0."""
     if threshold is None:
@@ -108,6 +124,16 @@ class EnSRF(Assimilation):
                     assimilated is rejected (assimilated False, nothing updated by it) when
                     (value - prior mean)^2 > t^2 (prior variance + error), checked once per
                     update against the prior.  None: off
+        streamed -- True: the prior stays in host memory and crosses the device in chunks of (y, x)
+                    columns, upload, state phase and download overlapping; device
+                    memory for the state is three chunks.  Same results bit for bit.  The posterior's
+                    member arrays then lie in page-locked memory of the context (fed back as the next
+                    prior they move by DMA; `EnsembleState.pinned_copy` makes a first prior like
+                    that).  Excludes adaptive_inflation and update_arrays.  Default False
+        stream_chunk_cols -- columns per chunk, a positive integer (cut to a multiple of 16); None:
+                    about 64 MB per chunk
+        stream_pinned_limit_mb -- page-locked posterior memory allowed in use at once (default 4096);
+                    above it the posterior arrays are ordinary ones and the download is staged
         """
         device = kw.pop("device", 0)
         self.obs_batch = kw.pop("obs_batch", None)
@@ -117,6 +143,9 @@ class EnSRF(Assimilation):
         adaptive = kw.pop("adaptive_inflation", None)
         vert_coord = kw.pop("vert_coord", None)
         outlier_threshold = kw.pop("outlier_threshold", None)
+        streamed = kw.pop("streamed", False)
+        stream_chunk_cols = kw.pop("stream_chunk_cols", None)
+        stream_pinned_limit_mb = kw.pop("stream_pinned_limit_mb", 4096)
         if kw:
             raise TypeError("unexpected keyword arguments %r" % sorted(kw))
         self.relaxation = relaxation_setting(rtps, rtpp)
@@ -131,6 +160,9 @@ class EnSRF(Assimilation):
                 raise ValueError("adaptive_inflation and inflation= are exclusive: the adaptive field is the prior inflation")
             adaptive.check_state(state)
         self.adaptive_inflation = adaptive
+        self.streamed, self.stream_chunk_cols, self.stream_pinned_limit = stream_setting(
+            streamed, stream_chunk_cols, stream_pinned_limit_mb, adaptive)
+        self.last_stream = None
         self.vert_coord = vertical_setting(state, vert_coord, loc, adaptive)
         if self.vert_coord is not None:
             ob_vertical(obs)
@@ -189,12 +221,71 @@ class EnSRF(Assimilation):
             ov, oh = ob_vertical(self.obs)
             ctx.set_vertical_localization(self.vert_coord.reshape(-1), ov, oh)
 
+    def _write_diagnostics(self, diag):
+        """The five diagnostics onto the observations, as ensrf.py:66,70,75,146-149."""
+        for k, ob in enumerate(self.obs):
+            ob.prior_mean = np.float64(diag["prior_mean"][k])
+            ob.prior_var = np.float64(diag["prior_var"][k])
+            if diag["assimilated"][k]:
+                ob.post_mean = np.float64(diag["post_mean"][k])
+                ob.post_var = np.float64(diag["post_var"][k])
+                ob.assimilated = True
+            else:
+                ob.assimilated = False
+
+    def _update_streamed(self, loc_mode, P, value, error, assim, lat, lon, hw):
+        """update() with the prior left in host memory (efa_ensrf_cycle_host)."""
+        from collections import OrderedDict
+        from copy import deepcopy
+        prior = self.prior
+        nvar, nt, ny, nx, M = prior.shape()
+        ncol = ny * nx
+        ctx = self._context()
+        self._configure(ctx)
+        ctx.set_option("timing", 1)
+        if self.verbose:
+            print("Computing observation priors")
+        # forward operator, once per ob from the prior (assimilation.py:45-48), without a resident state
+        HX = None
+        if P:
+            HX = self.streamed_ob_estimates(ctx) if self._default_forward_operator() else self.compute_ob_estimates()
+        grid_lat = grid_lon = None
+        if loc_mode == _lib.LOC_GC:
+            grid_lat, grid_lon = prior.column_latlon()
+        names = prior.vars()
+        seg_prior = [np.ascontiguousarray(prior.variables[n], dtype=np.float64) for n in names]
+        # the posterior is a NEW state: member arrays in page-locked memory of the context while the limit allows
+        if ctx.pinned_reserve([a.nbytes for a in seg_prior], self.stream_pinned_limit):
+            seg_post = [ctx.pinned_empty(a.shape) for a in seg_prior]
+        else:
+            seg_post = [np.empty(a.shape, dtype=np.float64) for a in seg_prior]
+        chunk_cols = self.stream_chunk_cols
+        if chunk_cols is None:
+            chunk_cols = _lib.default_chunk_cols(nvar * nt, M)
+        if self.verbose:
+            print("Beginning observation loop")
+        diag = ctx.ensrf_cycle_host(seg_prior, seg_post, ncol, M, HX, chunk_cols, value, error, assim, loc_mode, lat, lon, hw,
+                                    grid_lat, grid_lon)
+        self.last_timing = ctx.last_timing()
+        self.last_stream = ctx.stream_stats()
+        self._write_diagnostics(diag)
+        if self.verbose:
+            print("Formatting posterior")
+        post_state = type(prior)(OrderedDict(zip(names, seg_post)), deepcopy(prior.coords))
+        return post_state, self.obs
+
     # ------------------------------------------------------------------
     def update(self):
         if self.verbose:
             print("Beginning update sequence")
         loc_mode = self._loc_mode()
         P, value, error, assim, lat, lon, hw = self._ob_arrays(loc_mode)
+        if self.streamed:
+            if self.inflation is not None:      # the inflation hook comes first, as below
+                if self.verbose:
+                    print("Inflating Prior State")
+                self.inflate_state()
+            return self._update_streamed(loc_mode, P, value, error, assim, lat, lon, hw)
         # ensrf.py:44 -> format_prior_state: the inflation hook comes first (assimilation.py:131-134);
         # it may rebind self.prior (per-dimension factors, assimilation.py:96)
         if self.inflation is not None:
@@ -293,6 +384,9 @@ class EnSRF(Assimilation):
         `format_prior_state`) and return `(xam, Xap)` as handed to
         `format_posterior_state` (ensrf.py:44,151).  Diagnostics are written
         onto the observations."""
+        if self.streamed:
+            raise ValueError("update_arrays is not available on a streamed filter (it takes the augmented arrays whole); "
+                             "use update()")
         if self.adaptive_inflation is not None:
             raise ValueError("update_arrays does not support adaptive_inflation (out of scope: it runs on the augmented "
                              "arrays without the prior inflation step); use update()")

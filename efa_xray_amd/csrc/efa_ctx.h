@@ -1,0 +1,281 @@
+// The context behind the C ABI (include/efa_hip.h) and the small owning types it is made of, shared by the translation units that
+// drive it: efa_capi.hip (contexts, options, Phase A / Phase B) and efa_stream.hip (the streamed host-memory update).  Not exported.
+#pragma once
+#include "../../include/efa_hip.h"
+
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>  // types and enums only: librccl is opened with dlopen when a communicator is asked for
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+namespace efa_host {
+
+// sets the thread's efa_last_error() message and returns `code` (efa_capi.hip)
+int fail(int code, const char* fmt, ...);
+
+#define EFA_HIP(expr)                                                                       \
+  do {                                                                                      \
+    hipError_t _e = (expr);                                                                 \
+    if (_e != hipSuccess)                                                                   \
+      return fail(EFA_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, \
+                  __LINE__);                                                                \
+  } while (0)
+
+#define EFA_TRY(expr)          \
+  do {                         \
+    int _s = (expr);           \
+    if (_s != EFA_OK) return _s; \
+  } while (0)
+
+// grow-only device buffer, freed with its owner
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  int reserve(size_t bytes) {
+    if (bytes <= cap) return EFA_OK;
+    if (p) {
+      hipError_t e = hipFree(p);
+      p = nullptr;
+      cap = 0;
+      if (e != hipSuccess) return fail(EFA_ERR_HIP, "hipFree failed: %s", hipGetErrorString(e));
+    }
+    size_t want = bytes + (bytes >> 3) + 256;
+    hipError_t e = hipMalloc(&p, want);
+    if (e != hipSuccess) {
+      p = nullptr;
+      return fail(EFA_ERR_HIP, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
+    }
+    cap = want;
+    return EFA_OK;
+  }
+  template <typename T>
+  T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// grow-only pinned host staging: one asynchronous copy each way instead of one (synchronous, staged by the
+// runtime) copy per pageable caller array
+struct PinBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+  int reserve(size_t bytes) {
+    if (bytes <= cap) return EFA_OK;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+    const size_t want = bytes + (bytes >> 2) + 256;
+    hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
+    if (e != hipSuccess) {
+      p = nullptr;
+      return fail(EFA_ERR_HIP, "hipHostMalloc(%zu) failed: %s", want, hipGetErrorString(e));
+    }
+    cap = want;
+    return EFA_OK;
+  }
+};
+
+// a stream or event the context created, destroyed with it
+template <class H, hipError_t (*Destroy)(H)>
+struct Owned {
+  H h = nullptr;
+  Owned() = default;
+  Owned(const Owned&) = delete;
+  Owned& operator=(const Owned&) = delete;
+  ~Owned() {
+    if (h) (void)Destroy(h);
+  }
+  operator H() const { return h; }
+};
+// a stream finishes its work first (the diagnostic occupier may still hold CUs)
+inline hipError_t sync_and_destroy(hipStream_t s) {
+  (void)hipStreamSynchronize(s);
+  return hipStreamDestroy(s);
+}
+using OwnedStream = Owned<hipStream_t, sync_and_destroy>;
+using OwnedEvent = Owned<hipEvent_t, hipEventDestroy>;
+
+
+// one block of efa_pinned_alloc
+struct PinnedBlock {
+  void* p = nullptr;
+  size_t bytes = 0;
+};
+
+// What the streamed host-memory update (efa_ensrf_cycle_host, efa_stream.hip) keeps from call to call.  Declared last in the
+// context, so it is destroyed first: its events and host blocks go while the device is still set up.
+struct StreamState {
+  static constexpr int kRing = 3;     // device chunk buffers: one uploading, one in the state phase, one downloading
+  static constexpr int kStage = 2;    // pinned staging images each way for caller memory that is not pinned
+  std::vector<hipEvent_t> events;     // six per chunk (upload, state phase, download: start and end), grow-only
+  std::vector<PinnedBlock> blocks;    // registry of efa_pinned_alloc: a host segment inside one of them goes by DMA directly
+  void* ring = nullptr;               // kRing chunk buffers, allocated to the byte
+  size_t ring_bytes = 0;
+  PinBuf stage_up[kStage], stage_dn[kStage];
+  PinBuf pin_obs, pin_grid;           // pinned images of the obs block and of the column grid
+  DevBuf HX, ym, grid;                // obs block [P][M], its means [P], the whole column grid [lat | lon] on the device
+  long chunks = 0, peak_bytes = 0, h2d_us = 0, d2h_us = 0, wall_us = 0;  // read-only options stream_*: the last call
+  StreamState() = default;
+  StreamState(const StreamState&) = delete;
+  StreamState& operator=(const StreamState&) = delete;
+  ~StreamState() {
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    if (ring) (void)hipFree(ring);
+    for (const PinnedBlock& b : blocks) (void)hipHostFree(b.p);
+  }
+};
+
+}  // namespace efa_host
+
+using efa_host::DevBuf;
+using efa_host::fail;
+using efa_host::OwnedEvent;
+using efa_host::OwnedStream;
+using efa_host::PinBuf;
+
+struct efa_ctx {
+  // Members are destroyed in reverse order of declaration: the streams and events come first, so every buffer below is
+  // freed before they go away.
+  OwnedStream own_stream;
+  OwnedStream dbg_stream;  // diagnostic occupier (options debug_occupy_*)
+  OwnedStream up_stream, dn_stream;  // the streamed update's copy streams (efa_stream.hip), created when first used
+  OwnedEvent ev[7];  // obs phase 0..1; state phase 2..3 and (the fused cycle's second pair) 4..5; 6: Phase A's results on the host (fused cycle)
+  OwnedEvent ev_fs;  // the last host-to-device copy of the forward-operator stencil (pin_fs)
+  OwnedEvent ev_order;  // a change of stream: recorded on the stream that is left, waited for by the one that takes over
+  int device = 0;
+  hipStream_t stream = nullptr;
+  long obs_batch = 64;
+  long path = EFA_PATH_AUTO;
+  long timing = 0;
+  long use_gram = 2;       // persistent kernel's leader: 2 band leader (with and without localisation), 1 Gram leader step by step, 0 vector chain
+  long use_pipeline = 1;   // persistent Phase-A kernel when it applies (else per-batch kernels)
+  long spin_limit = 4000000;
+  long spin_ms = -1;       // wall-time bound of the persistent Phase-A launch; -1: 100 ms + P/100 ms
+  int cu_count = 0;
+  long dbg_occupy_blocks = 0;
+  long pipe_debug = 0;
+  long gc_onepass = 1;     // localised state sweep in one pass with per-column-block active lists
+
+  // --- trajectory recorded by the last obs phase --------------------------
+  bool have_traj = false;
+  int M = 0;
+  long P = 0;
+  int loc_mode = EFA_LOC_NONE;
+  long n_active = 0;
+  bool have_transform = false;   // identity rows were carried: (T, w) valid
+  std::vector<uint8_t> h_assim;  // host copy of ob_assim
+  std::vector<double> h_hw;      // host copy of ob_halfwidth_km, sanitised for unassimilated obs
+  DevBuf Ye_rec, coef;           // [P][M], [P][4]
+  DevBuf traj, tw_mat, status, dbg;  // pipeline: trajectory records, GC obs-obs taper, status words, stamps
+  const double* ye_ptr = nullptr;  // where Phase B reads the recorded ye rows
+  long ye_stride = 0;
+  int phase_a_kind = 0;          // 1 vector-chain pipeline, 2 per-batch kernels, 3 Gram leader, 4 band leader
+  DevBuf ob_pack, out_pack;  // the per-ob inputs / diagnostics below are slices of these two allocations (stage_obs_inputs)
+  PinBuf pin_in, pin_out;    // their pinned host images: one H2D and one D2H per call
+  PinBuf pin_fs;             // pinned image of the forward-operator stencil
+  size_t fs_valid_n = 0;       // the device copy fs_idx holds the pinned image's first fs_valid_n stencil entries ...
+  const void* fs_valid_dev = nullptr;  // ... if fs_idx and pin_fs are still these allocations
+  const void* fs_valid_pin = nullptr;
+  // in ob_pack: device copies [P] ([P][4] ob_errsq)
+  double *ob_val = nullptr, *ob_err = nullptr, *ob_errsq = nullptr, *ob_lat = nullptr, *ob_lon = nullptr, *ob_hw = nullptr;
+  uint8_t* ob_asm = nullptr;
+  // in out_pack: [P]
+  double *d_prior_mean = nullptr, *d_prior_var = nullptr, *d_post_mean = nullptr, *d_post_var = nullptr;
+  uint8_t* d_assimilated = nullptr;
+  DevBuf Yw, ymw;  // obs block workspace [(P+M)][M], [(P+M)]
+  DevBuf win_Y, win_m;  // rows of one Phase-A window + the transform rows (only when P exceeds one persistent launch)
+  // --- state phase workspaces ---------------------------------------------
+  DevBuf W;           // taper table [nb][ncol]
+  DevBuf gc_cnt, gc_ub, gc_order, gc_obtrig, gc_off, gc_idx, gc_wts, gc_pairs;  // one-pass GC sweep: CSR active lists
+  long gc_active_pairs = 0;  // (column, ob) pairs with a non-zero taper in the last one-pass sweep
+  // What depends on the GEOMETRY of a localised cycle only -- the obs' positions, radii and assimilate flags, the column grid --
+  // is kept from one cycle to the next while that geometry is unchanged (a fixed observing network on a fixed grid): the obs-obs
+  // taper table of Phase A and the per-block active lists of the one-pass sweep (indices, tapers, hand-out order; the gains are
+  // folded in by the sweep itself, cycle by cycle).  Compared by content on the host, never by pointer.
+  std::vector<double> geo_lat, geo_lon, geo_hw;
+  std::vector<uint8_t> geo_assim;
+  long geo_serial = 0;       // bumped whenever the obs geometry of a call differs from the previous call's
+  long grid_serial = 0;      // bumped whenever the device copy of the column grid is rewritten
+  long tw_serial = -1, tw_Pw = -1, tw_Rw = -1;  // what the obs-obs taper table on the device was built from
+  const void* tw_ptr = nullptr;
+  bool gc_list_valid = false;
+  long gc_list_geo = -1, gc_list_grid = -1, gc_list_ncol = -1, gc_list_P = -1;
+  const void* gc_list_ptrs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  long geometry_reuse = 1;   // option "geometry_reuse" (0: rebuild every cycle)
+  bool gc_pairs_pending = false;  // ... still on the device (read when asked for, or before the counter is cleared again: a read
+                                  // behind the sweep would hold the host until the sweep is done, cycle after cycle)
+  PinBuf pin_grid;           // pinned mirror of the column lat/lon on the device (glat | glon)
+  long grid_ncol = -1;       // columns the mirror and the device copies hold (-1: none)
+  bool grid_ready = false;   // efa_ensrf_cycle_dev brought the grid up to date ahead of Phase A: the state phase must not again
+  DevBuf glat, glon;  // grid lat/lon [ncol]
+  DevBuf xm_ws;       // means for efa_state_cycle_dev
+  // --- posterior relaxation (efa_ctx_set_relaxation) ------------------------------------------------------
+  int relax_kind = EFA_RELAX_NONE;
+  double relax_alpha = 0.0;
+  DevBuf relax_T;      // RTPP: (1-alpha) T + alpha I [M][M]
+  DevBuf relax_ss;     // standalone passes: sum of squared prior deviations per row [rows]
+  DevBuf relax_prior;  // standalone RTPP with the posterior written over the prior: a copy of the prior [rows][M]
+  // --- adaptive inflation (efa_ctx_set_adaptive_inflation) -------------------------------------
+  double* ai_field = nullptr;  // the caller's [ai_rows][2] (mean, sd), updated by every GC state phase; null: off
+  long ai_rows = 0;
+  double ai_lower = 1.0, ai_upper = 1e6, ai_sd_lower = 0.0;
+  DevBuf ai_ob;               // [P][4] what the sweep's update reads of each ob (launch_adapt_obs)
+  // --- vertical localisation (efa_ctx_set_vertical_localization) -----------------------------------
+  bool vl_on = false;
+  bool vl_any = false;          // some ob carries vertical information (else every factor is 1 and the plain kernels run)
+  long vl_nlead = 0, vl_P = 0;
+  std::vector<double> vl_host;  // [n_lead slab coordinates | P ob coordinates | P half-widths] as on the device (NaN: 1 as half-width)
+  long vl_serial = 0;           // bumped whenever the setting changes: part of the obs geometry (geo_serial)
+  long geo_vl_serial = 0;       // ... the value the current geometry was compared with
+  DevBuf vl_dev;                // device copy of vl_host
+  DevBuf vl_W;                  // the per-batch sweep's taper table [nb][R] (launch_obs_taper_rows)
+  // --- outlier check (efa_ctx_set_outlier_threshold) ----------------------------------------------
+  double qc_threshold = 0.0;    // 0: off
+  bool qc_used = false;         // the last obs phase ran it: its flags on the device may be fewer than the caller's
+  DevBuf qc_act;                // [P][kCoefStride], GC: the caller's flags where the one-pass sweep's list builders read coef[3]
+  // --- f1: interpolation stencils -------------------------------------------------
+  DevBuf fs_idx, fs_wts;  // efa_forward_stencil_dev staging
+  DevBuf f_glat, f_glon, f_sl, f_cl, f_valids, f_var, f_time, f_lat, f_lon, f_near, f_idx, f_wts, f_status;
+  long f_P = 0;       // observations of the stencil held in f_idx / f_wts (0: none)
+  // --- host-memory API buffers ----------------------------------------------
+  DevBuf h_xm, h_Xp, h_ym, h_Yp;
+  // --- multi-GPU exchange step: an RCCL communicator owned by the context (efa_comm_init) -------------
+  ncclComm_t comm = nullptr;
+  int comm_rank = 0, comm_world = 1;
+  DevBuf gcc_lat, gcc_lon, gcc_oblat, gcc_oblon, gcc_obhw, gcc_coef, gcc_trig, gcc_cnt, gcc_pairs;  // efa_gc_block_counts
+  // --- timing -----------------------------------------------------------------
+  double state_ms = 0.0, obs_ms = 0.0;
+  bool obs_ms_pending = false;  // ev[0] .. ev[obs_end_ev] of the last obs phase not read yet
+  int obs_end_ev = 1;           // 1, or the start event of the state pair a speculative transform was put behind
+  bool state_ms_pending = false;  // ev[2] .. ev[3] of the last state phase not read yet
+  bool state_ms_pending2 = false; // ev[4] .. ev[5] likewise (efa_ensrf_cycle_dev alternates the pairs: it records a state phase's
+                                  // events BEFORE the stream is synchronised, while the previous cycle's may still be unread)
+  // efa_ensrf_cycle_dev: Phase B enqueued behind Phase A before Phase A's status is known
+  struct Spec {
+    bool armed = false, launched = false;
+    const double* X = nullptr;
+    double* post = nullptr;
+    long rows = 0;
+    int pair = 0;  // event pair of the launched transform
+    long launches = 0;  // state-phase launches it took (the transform, and the relaxation's)
+    bool obs_out = true;
+  } spec;
+  double state_ms_sum = 0.0, obs_ms_sum = 0.0;  // timing 2: sums since the previous efa_last_timing
+  long state_launches_sum = 0;
+  long state_launches = 0;
+  int path_taken = 0;
+  efa_host::StreamState st;  // efa_ensrf_cycle_host, efa_pinned_alloc
+};

@@ -184,6 +184,20 @@ class EnsembleState(object):
         return EnsembleState(OrderedDict((n, v.copy()) for n, v in self.variables.items()),
                              dict((k, np.array(v, copy=True)) for k, v in self.coords.items()))
 
+    def pinned_copy(self, ctx=None):
+        """A copy of this state whose member arrays lie in page-locked memory of `ctx` (an efa_xray_amd._lib.Context; default:
+        device 0's): as a prior of `EnSRF(..., streamed=True)` it is moved by DMA without staging.  The posterior of a streamed
+        update is such a state already."""
+        if ctx is None:
+            from efa_xray_amd import _lib
+            ctx = _lib.get_context(0)
+        variables = OrderedDict()
+        for n, v in self.variables.items():
+            a = ctx.pinned_empty(v.shape)
+            a[...] = v
+            variables[n] = a
+        return type(self)(variables, dict((k, np.array(v, copy=True)) for k, v in self.coords.items()))
+
     def column_latlon(self):
         """Per-(y,x)-column lat/lon, flattened to (ny*nx,): what the HIP library
         takes as grid_lat/grid_lon.  A 1-D lat/lon (ensrf.py:110-111) is

@@ -355,6 +355,64 @@ int efa_ensrf_update(efa_ctx *ctx, long A, long N, int M, long P, double *xbm,
                      double *prior_mean, double *prior_var, double *post_mean,
                      double *post_var, uint8_t *assimilated);
 
+/* ---- one whole cycle on a prior in HOST memory, streamed in column chunks ----
+ * The state never has to fit the device: it crosses it in chunks of (y,x)
+ * columns, upload of chunk i+1, state phase of chunk i and download of chunk
+ * i-1 overlapping on two copy streams beside the context's stream.  Phase A
+ * starts as soon as the obs block is on the device, while the first chunks
+ * upload.  Device memory for the state is a ring of three chunk buffers.
+ *
+ * State: n_seg segments (one per variable); segment v is a C-contiguous
+ *   [seg_slabs[v]][ncol][M] float64 array at seg_prior[v], read only, and its
+ *   posterior goes to seg_post[v] (same shape; must not overlap the prior).
+ *   n_lead = sum of seg_slabs; state row (lead, col) is lead*ncol + col, the
+ *   order of to_vect().  ncol is the number of (y,x) columns, with and without
+ *   localisation.
+ * HX[P*M]: the member estimates of the P observations (host), row k =
+ *   ob_k.estimate(prior); means and perturbations are formed on the device
+ *   (assimilation.py:46-48).  Not written.
+ * chunk_cols (>= 1): columns per chunk, rounded down to a multiple of 16 (the
+ *   one-pass sweep's block; at least 16); the last chunk takes the ragged
+ *   rest.  Chunk [lo, hi) is on the device as the column shard
+ *   row = lead*(hi-lo) + (col-lo).
+ * Per-ob arrays, grid (ncol entries, EFA_LOC_GC only) and diagnostics exactly
+ *   as efa_ensrf_cycle_dev has them.
+ * Relaxation, outlier threshold and vertical localisation are context state
+ * and apply per chunk as they do to a resident state; while an adaptive-
+ * inflation field is set the call fails with EFA_ERR_INVALID.  Results equal
+ * efa_ensrf_cycle_dev on the resident state bit for bit.
+ *
+ * A segment that lies inside a block of efa_pinned_alloc (looked up in the
+ * context's registry; caller memory is never registered) is transferred
+ * directly by DMA, strided pieces as 2-D copies; any other pointer is staged
+ * through a bounded ring of pinned chunk images by the call itself.
+ * The call returns with everything done: the posterior and the diagnostics
+ * are in host memory.  With efa_ctx_set_stream the work is ordered behind
+ * what the context issued on the caller's stream before, like a change of
+ * stream.  The one-pass GC sweep's active lists are rebuilt per chunk (the
+ * 8-byte capacity read-back is the only host wait between chunks besides the
+ * staging ring's).
+ * efa_last_timing keeps its meaning (state_ms: the sum over the chunks).
+ * Read-only options about the last call: "stream_chunks",
+ * "stream_peak_bytes" (device bytes held for state chunks), "stream_h2d_us",
+ * "stream_d2h_us" (sums of the chunks' copy times on the device),
+ * "stream_wall_us" (host wall time of the call). */
+int efa_ensrf_cycle_host(efa_ctx *ctx, int n_seg, const double *const *seg_prior,
+                         double *const *seg_post, const long *seg_slabs, long ncol,
+                         int M, long P, const double *HX, long chunk_cols,
+                         const double *ob_value, const double *ob_error,
+                         const uint8_t *ob_assim, int loc_mode,
+                         const double *ob_lat, const double *ob_lon,
+                         const double *ob_halfwidth_km, const double *grid_lat,
+                         const double *grid_lon, double *prior_mean,
+                         double *prior_var, double *post_mean, double *post_var,
+                         uint8_t *assimilated);
+/* Page-locked host memory owned by the context (hipHostMalloc), for states
+ * that efa_ensrf_cycle_host moves by DMA without staging.  Blocks still
+ * allocated when the context is destroyed are freed with it. */
+int efa_pinned_alloc(efa_ctx *ctx, size_t bytes, void **host_out);
+int efa_pinned_free(efa_ctx *ctx, void *host);
+
 /* ---- configs[4]: batched-obs dense contraction, float32 --------------------
  * C[i*P + k] = sum_m Xbp[i*M + m] * Ye[k*M + m]: the covariance numerators
  * `np.dot(Xbp, ye.T)` of ensrf.py:95 for P recorded obs-space rows at once, as
