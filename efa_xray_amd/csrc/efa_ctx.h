@@ -1,5 +1,5 @@
 // The context behind the C ABI (include/efa_hip.h) and the small owning types it is made of, shared by the translation units that
-// drive it: efa_capi.hip (contexts, options, Phase A / Phase B) and efa_stream.hip (the streamed host-memory update).  Not exported.
+// drive it (efa_driver.h lists them).  Not exported.
 #pragma once
 #include "../../include/efa_hip.h"
 
@@ -108,6 +108,29 @@ inline hipError_t sync_and_destroy(hipStream_t s) {
 using OwnedStream = Owned<hipStream_t, sync_and_destroy>;
 using OwnedEvent = Owned<hipEvent_t, hipEventDestroy>;
 
+// A timed stretch of the context's stream.  "timing" 2 (deferred) leaves it pending: it is read when its events are about to be
+// recorded again, or in efa_last_timing.
+struct Interval {
+  OwnedEvent begin, end;
+  bool pending = false;  // recorded, not read yet
+};
+
+// The column grid (lat | lon) of a localised state phase on the device.  Only its own functions (efa_phase_b.hip) write it: one
+// per way the grid arrives.  Each leaves the device copy current for the state phase that follows.
+struct ColumnGrid {
+  DevBuf lat, lon;        // [ncol]
+  PinBuf mirror;          // pinned image (lat | lon) of what the device holds
+  long mirror_ncol = -1;  // columns the mirror and the device copies hold (-1: the mirror is not current)
+  long serial = 0;        // bumped whenever the device copy is rewritten
+  // from the caller's arrays; waits, so the caller may reuse them on return
+  int upload(hipStream_t s, const double* grid_lat, const double* grid_lon, long ncol);
+  // the same arrays ahead of Phase A: compared with the mirror, copied from it -- asynchronously -- only if they differ
+  int refresh(hipStream_t s, const double* grid_lat, const double* grid_lon, long ncol);
+  // columns [lo, lo + ncol) of a whole grid (lat | lon, `pitch` columns each) already on the device: in stream order, no host wait
+  // (room for the widest slice is reserved first, so that no slice reallocates under work in flight)
+  int reserve(long ncol);
+  int take_slice(hipStream_t s, const double* dev_grid, long pitch, long lo, long ncol);
+};
 
 // one block of efa_pinned_alloc
 struct PinnedBlock {
@@ -140,8 +163,10 @@ struct StreamState {
 
 }  // namespace efa_host
 
+using efa_host::ColumnGrid;
 using efa_host::DevBuf;
 using efa_host::fail;
+using efa_host::Interval;
 using efa_host::OwnedEvent;
 using efa_host::OwnedStream;
 using efa_host::PinBuf;
@@ -152,7 +177,9 @@ struct efa_ctx {
   OwnedStream own_stream;
   OwnedStream dbg_stream;  // diagnostic occupier (options debug_occupy_*)
   OwnedStream up_stream, dn_stream;  // the streamed update's copy streams (efa_stream.hip), created when first used
-  OwnedEvent ev[7];  // obs phase 0..1; state phase 2..3 and (the fused cycle's second pair) 4..5; 6: Phase A's results on the host (fused cycle)
+  Interval obs_iv;       // the obs phase; it ends at obs_ends_at
+  Interval state_iv[2];  // the state phase; efa_ensrf_cycle_dev alternates the two: it records a state phase's events BEFORE the
+                         // stream is synchronised, while the previous cycle's may still be unread
   OwnedEvent ev_fs;  // the last host-to-device copy of the forward-operator stencil (pin_fs)
   OwnedEvent ev_order;  // a change of stream: recorded on the stream that is left, waited for by the one that takes over
   int device = 0;
@@ -208,7 +235,6 @@ struct efa_ctx {
   std::vector<double> geo_lat, geo_lon, geo_hw;
   std::vector<uint8_t> geo_assim;
   long geo_serial = 0;       // bumped whenever the obs geometry of a call differs from the previous call's
-  long grid_serial = 0;      // bumped whenever the device copy of the column grid is rewritten
   long tw_serial = -1, tw_Pw = -1, tw_Rw = -1;  // what the obs-obs taper table on the device was built from
   const void* tw_ptr = nullptr;
   bool gc_list_valid = false;
@@ -217,10 +243,7 @@ struct efa_ctx {
   long geometry_reuse = 1;   // option "geometry_reuse" (0: rebuild every cycle)
   bool gc_pairs_pending = false;  // ... still on the device (read when asked for, or before the counter is cleared again: a read
                                   // behind the sweep would hold the host until the sweep is done, cycle after cycle)
-  PinBuf pin_grid;           // pinned mirror of the column lat/lon on the device (glat | glon)
-  long grid_ncol = -1;       // columns the mirror and the device copies hold (-1: none)
-  bool grid_ready = false;   // efa_ensrf_cycle_dev brought the grid up to date ahead of Phase A: the state phase must not again
-  DevBuf glat, glon;  // grid lat/lon [ncol]
+  ColumnGrid grid;
   DevBuf xm_ws;       // means for efa_state_cycle_dev
   // --- posterior relaxation (efa_ctx_set_relaxation) ------------------------------------------------------
   int relax_kind = EFA_RELAX_NONE;
@@ -247,7 +270,7 @@ struct efa_ctx {
   bool qc_used = false;         // the last obs phase ran it: its flags on the device may be fewer than the caller's
   DevBuf qc_act;                // [P][kCoefStride], GC: the caller's flags where the one-pass sweep's list builders read coef[3]
   // --- f1: interpolation stencils -------------------------------------------------
-  DevBuf fs_idx, fs_wts;  // efa_forward_stencil_dev staging
+  DevBuf fs_idx;  // efa_forward_stencil_dev staging
   DevBuf f_glat, f_glon, f_sl, f_cl, f_valids, f_var, f_time, f_lat, f_lon, f_near, f_idx, f_wts, f_status;
   long f_P = 0;       // observations of the stencil held in f_idx / f_wts (0: none)
   // --- host-memory API buffers ----------------------------------------------
@@ -258,21 +281,7 @@ struct efa_ctx {
   DevBuf gcc_lat, gcc_lon, gcc_oblat, gcc_oblon, gcc_obhw, gcc_coef, gcc_trig, gcc_cnt, gcc_pairs;  // efa_gc_block_counts
   // --- timing -----------------------------------------------------------------
   double state_ms = 0.0, obs_ms = 0.0;
-  bool obs_ms_pending = false;  // ev[0] .. ev[obs_end_ev] of the last obs phase not read yet
-  int obs_end_ev = 1;           // 1, or the start event of the state pair a speculative transform was put behind
-  bool state_ms_pending = false;  // ev[2] .. ev[3] of the last state phase not read yet
-  bool state_ms_pending2 = false; // ev[4] .. ev[5] likewise (efa_ensrf_cycle_dev alternates the pairs: it records a state phase's
-                                  // events BEFORE the stream is synchronised, while the previous cycle's may still be unread)
-  // efa_ensrf_cycle_dev: Phase B enqueued behind Phase A before Phase A's status is known
-  struct Spec {
-    bool armed = false, launched = false;
-    const double* X = nullptr;
-    double* post = nullptr;
-    long rows = 0;
-    int pair = 0;  // event pair of the launched transform
-    long launches = 0;  // state-phase launches it took (the transform, and the relaxation's)
-    bool obs_out = true;
-  } spec;
+  hipEvent_t obs_ends_at = nullptr;  // obs_iv.end, or the begin event of the state interval a speculative transform was put behind
   double state_ms_sum = 0.0, obs_ms_sum = 0.0;  // timing 2: sums since the previous efa_last_timing
   long state_launches_sum = 0;
   long state_launches = 0;

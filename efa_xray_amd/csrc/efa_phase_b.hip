@@ -1,0 +1,414 @@
+// Phase B, the state phase (efa_driver.h): the relaxation glue, the checks of the settings that bind a state phase, the column
+// grid, the sweeps and the two state calls (perturbation form and member form).
+#include "efa_driver.h"
+
+#include <cstring>
+
+namespace efa_host {
+
+using namespace efa;
+
+// ---- posterior relaxation (RTPP / RTPS, efa_relax.hip) ----------------------------------------------------------
+// Applied only where a state phase writes the caller's state rows, and only when an ob was assimilated (otherwise the posterior
+// is returned exactly as without it).
+namespace {
+bool relax_on(const efa_ctx* c) {
+  return c->relax_kind != EFA_RELAX_NONE && c->relax_alpha != 0.0 && c->P > 0 && c->n_active > 0;
+}
+// standalone passes, before the state phase: what the relaxation needs of the prior rows Xin (members or perturbations) -- RTPS
+// their spread, RTPP the rows themselves (copied when the state phase writes over them)
+int relax_prepare(efa_ctx* c, long rows, int M, const double* Xin, const double* Xout, const double** prior, long* nl) {
+  *prior = nullptr;
+  if (c->relax_kind == EFA_RELAX_RTPS) {
+    EFA_TRY(c->relax_ss.reserve((size_t)rows * sizeof(double)));
+    EFA_HIP(launch_row_spread(rows, M, Xin, c->relax_ss.as<double>(), c->stream));
+    ++*nl;
+    return EFA_OK;
+  }
+  const size_t bytes = (size_t)rows * M * sizeof(double);
+  const char *a = reinterpret_cast<const char*>(Xin), *b = reinterpret_cast<const char*>(Xout);
+  if (a + bytes <= b || b + bytes <= a) {
+    *prior = Xin;
+  } else {
+    EFA_TRY(c->relax_prior.reserve(bytes));
+    EFA_HIP(hipMemcpyAsync(c->relax_prior.p, Xin, bytes, hipMemcpyDeviceToDevice, c->stream));
+    *prior = c->relax_prior.as<double>();
+  }
+  return EFA_OK;
+}
+// ... and after it, in place on the posterior rows
+int relax_apply(efa_ctx* c, long rows, int M, double* Xout, const double* prior, long* nl) {
+  EFA_HIP(launch_relax_rows(rows, M, c->relax_kind == EFA_RELAX_RTPP ? 1 : 0, c->relax_alpha, Xout, c->relax_ss.as<double>(), prior,
+                            c->stream));
+  ++*nl;
+  return EFA_OK;
+}
+// core(), the state phase's pass(es) from prior rows Xin to posterior rows Xout, between the standalone relaxation passes
+template <class Core>
+int with_relaxation(efa_ctx* c, long rows, int M, const double* Xin, double* Xout, long* nl, Core&& core) {
+  const bool relax = relax_on(c);
+  const double* prior = nullptr;
+  if (relax) EFA_TRY(relax_prepare(c, rows, M, Xin, Xout, &prior, nl));
+  EFA_TRY(core());
+  if (relax) EFA_TRY(relax_apply(c, rows, M, Xout, prior, nl));
+  return EFA_OK;
+}
+}  // namespace
+// The state transform through [T | w] (member or perturbation form, t.fused_members) with the relaxation: RTPP folded into T
+// (Xb' ((1-alpha) T + alpha I); xam as without it), RTPS fused into the member-form transform up to 136 members, the standalone
+// passes otherwise.  *nl = the launches it took.
+int transform_with_relaxation(efa_ctx* c, TransformArgs t, long* nl) {
+  hipStream_t s = c->stream;
+  const bool relax = relax_on(c);
+  *nl = 1;
+  if (relax && c->relax_kind == EFA_RELAX_RTPP) {
+    EFA_TRY(c->relax_T.reserve((size_t)t.M * t.M * sizeof(double)));
+    EFA_HIP(launch_relax_fold(t.M, c->relax_alpha, t.T, c->relax_T.as<double>(), s));
+    t.T = c->relax_T.as<double>();
+    *nl = 2;
+  } else if (relax && t.fused_members && transform_rtps_supported(t.M)) {
+    EFA_HIP(launch_transform_rtps(t, c->relax_alpha, s));
+    return EFA_OK;
+  } else if (relax) {
+    return with_relaxation(c, t.nrows, t.M, t.Xin, t.Xout, nl, [&]() -> int {
+      EFA_HIP(launch_transform(t, s));
+      return EFA_OK;
+    });
+  }
+  EFA_HIP(launch_transform(t, s));
+  return EFA_OK;
+}
+// [T | w] as Phase A left them: the carried identity rows behind the P obs rows of the working block
+TransformArgs carried_transform(const efa_ctx* c, const double* Xin, const double* xin, double* Xout, double* xout, long rows,
+                                int fused_members) {
+  return TransformArgs{Xin, xin, Xout, xout, rows, c->M, c->Yw.as<double>() + (size_t)c->P * c->M, c->ymw.as<double>() + c->P,
+                       fused_members};
+}
+
+// ---- adaptive inflation (efa_adapt.hip, the update fused into the one-pass GC sweep) ----------------------------------------
+// While a field is set, only the one-pass GC state sweep may run the state phase: it is the one that updates the field.
+int check_adaptive(const efa_ctx* c, int loc_mode, long rows) {
+  if (!c->ai_field) return EFA_OK;
+  if (loc_mode != EFA_LOC_GC)
+    return fail(EFA_ERR_INVALID, "adaptive inflation is set: it needs GC localisation (loc_mode %d is not EFA_LOC_GC)", loc_mode);
+  if (!c->gc_onepass) return fail(EFA_ERR_INVALID, "adaptive inflation is set: it needs the one-pass GC sweep (option gc_onepass is 0)");
+  if (rows != c->ai_rows)
+    return fail(EFA_ERR_INVALID, "adaptive inflation field has %ld rows but the state phase has %ld", c->ai_rows, rows);
+  return EFA_OK;
+}
+
+// ---- vertical localisation (efa_vloc.hip and the _vloc sweep kernels) -------------------------------------------------------
+// While it is set, every call must be a GC cycle of the P obs and n_lead slabs it was set for, on the one-pass state sweep (the
+// per-batch state sweep has no vertical factor) and without adaptive inflation (no combined kernel).  n_lead < 0: not checked.
+int check_vloc(const efa_ctx* c, int loc_mode, long P, long n_lead) {
+  if (!c->vl_on) return EFA_OK;
+  if (loc_mode != EFA_LOC_GC)
+    return fail(EFA_ERR_INVALID, "vertical localisation is set: it needs GC localisation (loc_mode %d is not EFA_LOC_GC)", loc_mode);
+  if (!c->gc_onepass)
+    return fail(EFA_ERR_INVALID, "vertical localisation is set: it needs the one-pass GC sweep (option gc_onepass is 0)");
+  if (c->ai_field) return fail(EFA_ERR_INVALID, "vertical localisation is set: adaptive inflation cannot be combined with it");
+  if (P != c->vl_P) return fail(EFA_ERR_INVALID, "vertical localisation was set for %ld observations, the call has %ld", c->vl_P, P);
+  if (n_lead >= 0 && n_lead != c->vl_nlead)
+    return fail(EFA_ERR_INVALID, "vertical localisation was set for %ld slabs, the call has n_lead=%ld", c->vl_nlead, n_lead);
+  return EFA_OK;
+}
+
+// path "auto": one transform pass or sweep passes?  By FLOPS one transform pass is M/2 observations of sweep arithmetic (the rule of
+// rounds 1-2), but the transform runs on the matrix cores at 49 TFLOP/s and the sweep on the vector ALUs at 10-20, and in MEMBER form
+// (prior members in, posterior members out) the sweep path is three passes over the state -- form the perturbations, sweep, rebuild
+// the members -- where the transform is one.  Measured at 1e7 x 100 (profiles/r03_auto_path.txt): member form 8 obs 10.6 ms by
+// sweeps, 4.1 by the transform (48 obs: 16.9 vs 4.1); perturbation form 8 / 16 obs per sweep launch 3.4 / 4.5 ms vs 4.5.
+// Above 136 members the transform re-reads the state once per group of 64 output columns: the flops rule stays.
+bool auto_transform(int M, long n_active, bool member_form) {
+  if (n_active <= 0) return false;
+  if (M > 136) return n_active > M / 2;
+  if (member_form) return true;
+  return n_active > M / 8;
+}
+bool want_transform(const efa_ctx* c, bool member_form) {
+  if (!c->have_transform) return false;
+  if (c->path == EFA_PATH_TRANSFORM) return true;
+  if (c->path == EFA_PATH_SWEEP) return false;
+  return auto_transform(c->M, c->n_active, member_form);
+}
+
+// ---- the column grid of a localised state phase (ColumnGrid, efa_ctx.h) -------------------------------------------------------
+int check_grid(int loc_mode, const double* grid_lat, const double* grid_lon, long ncol, long n_lead, long rows) {
+  if (loc_mode != EFA_LOC_GC) return EFA_OK;
+  if (!grid_lat || !grid_lon) return fail(EFA_ERR_INVALID, "GC localisation needs grid_lat/grid_lon");
+  if (ncol <= 0 || n_lead <= 0 || ncol * n_lead != rows)
+    return fail(EFA_ERR_INVALID, "rows=%ld must equal n_lead*ncol = %ld*%ld", rows, n_lead, ncol);
+  return EFA_OK;
+}
+
+int ColumnGrid::reserve(long ncol) {
+  EFA_TRY(lat.reserve((size_t)ncol * sizeof(double)));
+  EFA_TRY(lon.reserve((size_t)ncol * sizeof(double)));
+  return EFA_OK;
+}
+
+int ColumnGrid::upload(hipStream_t s, const double* grid_lat, const double* grid_lon, long ncol) {
+  const size_t nb = (size_t)ncol * sizeof(double);
+  EFA_TRY(reserve(ncol));
+  EFA_HIP(hipMemcpyAsync(lat.p, grid_lat, nb, hipMemcpyHostToDevice, s));
+  EFA_HIP(hipMemcpyAsync(lon.p, grid_lon, nb, hipMemcpyHostToDevice, s));
+  mirror_ncol = -1;
+  serial++;
+  EFA_HIP(hipStreamSynchronize(s));  // caller may reuse grid_lat/grid_lon on return
+  return EFA_OK;
+}
+
+// Cycle after cycle on one grid nothing is copied; the comparison (4 MB at configs[3]) is host time spent while the device still
+// works on the previous cycle.
+int ColumnGrid::refresh(hipStream_t s, const double* grid_lat, const double* grid_lon, long ncol) {
+  const size_t nb = (size_t)ncol * sizeof(double);
+  const void* pin_before = mirror.p;
+  EFA_TRY(mirror.reserve(2 * nb));
+  char* pin = static_cast<char*>(mirror.p);
+  const void *dl = lat.p, *dn = lon.p;
+  EFA_TRY(reserve(ncol));
+  const bool same = mirror_ncol == ncol && pin_before == mirror.p && dl == lat.p && dn == lon.p &&
+                    std::memcmp(pin, grid_lat, nb) == 0 && std::memcmp(pin + nb, grid_lon, nb) == 0;
+  if (!same) {
+    EFA_HIP(hipStreamSynchronize(s));  // (an earlier copy out of the mirror may be in flight; a new grid is the rare case)
+    std::memcpy(pin, grid_lat, nb);
+    std::memcpy(pin + nb, grid_lon, nb);
+    EFA_HIP(hipMemcpyAsync(lat.p, pin, nb, hipMemcpyHostToDevice, s));
+    EFA_HIP(hipMemcpyAsync(lon.p, pin + nb, nb, hipMemcpyHostToDevice, s));
+    mirror_ncol = ncol;
+    serial++;
+  }
+  return EFA_OK;
+}
+
+// (the one-pass sweep's lists are rebuilt: the grid changed)
+int ColumnGrid::take_slice(hipStream_t s, const double* dev_grid, long pitch, long lo, long ncol) {
+  EFA_HIP(hipMemcpyAsync(lat.p, dev_grid + lo, (size_t)ncol * sizeof(double), hipMemcpyDeviceToDevice, s));
+  EFA_HIP(hipMemcpyAsync(lon.p, dev_grid + pitch + lo, (size_t)ncol * sizeof(double), hipMemcpyDeviceToDevice, s));
+  mirror_ncol = -1;
+  serial++;
+  return EFA_OK;
+}
+
+int read_gc_pairs(efa_ctx* c) {
+  if (!c->gc_pairs_pending) return EFA_OK;
+  c->gc_pairs_pending = false;
+  unsigned long long h_pairs = 0;
+  EFA_HIP(hipMemcpyAsync(&h_pairs, c->gc_pairs.p, sizeof(h_pairs), hipMemcpyDeviceToHost, c->stream));
+  EFA_HIP(hipStreamSynchronize(c->stream));
+  c->gc_active_pairs = (long)h_pairs;
+  return EFA_OK;
+}
+
+namespace {
+// ---- Phase B, localised, one pass (efa_gcsweep.hip) --------------------------------------
+int state_gc_onepass(efa_ctx* c, const double* xm_in, const double* Xp_in, double* xm_out, double* Xp_out, long ncol, long n_lead,
+                     int fused_members) {
+  const int M = c->M;
+  const long P = c->P;
+  hipStream_t s = c->stream;
+  const long nblk = gc_num_blocks(ncol);
+  EFA_TRY(c->gc_cnt.reserve((size_t)nblk * sizeof(int)));
+  EFA_TRY(c->gc_ub.reserve((size_t)nblk * sizeof(int)));
+  EFA_TRY(c->gc_order.reserve((size_t)nblk * sizeof(int)));
+  EFA_TRY(c->gc_obtrig.reserve((size_t)P * 6 * sizeof(double)));
+  EFA_TRY(c->gc_off.reserve((size_t)(nblk + 1) * sizeof(long)));
+  EFA_TRY(c->gc_pairs.reserve(sizeof(unsigned long long)));
+  const void* ptrs[5] = {c->gc_off.p, c->gc_cnt.p, c->gc_order.p, c->gc_idx.p, c->gc_wts.p};
+  const bool lists_ok = c->geometry_reuse && c->gc_list_valid && c->gc_list_geo == c->geo_serial && c->gc_list_grid == c->grid.serial &&
+                        c->gc_list_ncol == ncol && c->gc_list_P == P && std::memcmp(ptrs, c->gc_list_ptrs, sizeof(ptrs)) == 0;
+  if (!lists_ok) {
+  c->gc_list_valid = false;
+  EFA_TRY(read_gc_pairs(c));  // (the previous sweep's count, before the counter is cleared: that sweep is long done)
+  EFA_HIP(hipMemsetAsync(c->gc_pairs.p, 0, sizeof(unsigned long long), s));
+  // the lists hold the obs the CALLER asked to assimilate, as the geometry they are cached by: an ob the outlier check rejected
+  // stays in them with its inactive record (zero gains), so a later cycle that keeps it finds it there
+  const double* act = c->qc_used ? c->qc_act.as<double>() : c->coef.as<double>();
+  EFA_HIP(launch_gc_bound(ncol, P, c->grid.lat.as<double>(), c->ob_lat, c->ob_hw, act, c->gc_ub.as<int>(), c->gc_off.as<long>(), s));
+  long cap = 0;  // the only host round trip of the build: 8 bytes, the capacity the lists need
+  EFA_HIP(hipMemcpyAsync(&cap, c->gc_off.as<long>() + nblk, sizeof(long), hipMemcpyDeviceToHost, s));
+  EFA_HIP(hipStreamSynchronize(s));
+  EFA_TRY(c->gc_idx.reserve((size_t)(cap ? cap : 1) * sizeof(int)));
+  EFA_TRY(c->gc_wts.reserve((size_t)(cap ? cap : 1) * 16 * sizeof(double)));
+  EFA_HIP(launch_gc_fill(ncol, P, c->grid.lat.as<double>(), c->grid.lon.as<double>(), c->ob_lat, c->ob_lon, c->ob_hw, act,
+                         c->gc_obtrig.as<double>(), c->gc_off.as<long>(), c->gc_cnt.as<int>(), c->gc_idx.as<int>(),
+                         c->gc_wts.as<double>(), c->gc_order.as<int>(), c->gc_pairs.as<unsigned long long>(), s));
+  c->gc_list_valid = true;
+  c->gc_list_geo = c->geo_serial;
+  c->gc_list_grid = c->grid.serial;
+  c->gc_list_ncol = ncol;
+  c->gc_list_P = P;
+  c->gc_list_ptrs[0] = c->gc_off.p;
+  c->gc_list_ptrs[1] = c->gc_cnt.p;
+  c->gc_list_ptrs[2] = c->gc_order.p;
+  c->gc_list_ptrs[3] = c->gc_idx.p;
+  c->gc_list_ptrs[4] = c->gc_wts.p;
+  c->gc_pairs_pending = true;  // read by read_gc_pairs when somebody asks (option "gc_active_pairs") or before the next build
+  }
+  GcSweepArgs g{};
+  g.ncol = ncol;
+  g.n_lead = n_lead;
+  g.M = M;
+  g.nblk = nblk;
+  g.off = c->gc_off.as<long>();
+  g.cnt = c->gc_cnt.as<int>();
+  g.order = c->gc_order.as<int>();
+  g.idx = c->gc_idx.as<int>();
+  g.wts = c->gc_wts.as<double>();
+  g.coef = c->coef.as<double>();
+  g.Ye = c->ye_ptr;
+  g.ye_stride = c->ye_stride;
+  g.Xin = Xp_in;
+  g.xin = xm_in;
+  g.Xout = Xp_out;
+  g.xout = xm_out;
+  g.fused_members = fused_members;
+  if (c->ai_field) {  // the per-ob scalars of the inflation update, from Phase A's records and diagnostics
+    EFA_TRY(c->ai_ob.reserve((size_t)(P ? P : 1) * 4 * sizeof(double)));
+    EFA_HIP(launch_adapt_obs(P, M, c->coef.as<double>(), c->d_prior_var, c->ob_err, c->ye_ptr, c->ye_stride,
+                             c->ai_ob.as<double>(), s));
+    c->state_launches++;
+    g.infl = c->ai_field;
+    g.adapt_ob = c->ai_ob.as<double>();
+    g.infl_lower = c->ai_lower;
+    g.infl_upper = c->ai_upper;
+    g.infl_sd_lower = c->ai_sd_lower;
+  }
+  if (vl_active(c)) {
+    g.lead_vert = vl_lead(c);
+    g.ob_vert = vl_obvert(c);
+    g.ob_vhw = vl_obvhw(c);
+  }
+  EFA_HIP(launch_sweep_gc(g, s));
+  c->state_launches++;
+  return EFA_OK;
+}
+
+// ---- Phase B (perturbation form) ------------------------------------------
+int state_sweeps(efa_ctx* c, long rows, const double* xm_in, const double* Xp_in, double* xm_out, double* Xp_out,
+                 long ncol) {
+  const int M = c->M;
+  const long P = c->P;
+  hipStream_t s = c->stream;
+  if (c->loc_mode == EFA_LOC_GC && c->gc_onepass && c->n_active > 0)  // every ensemble size the library accepts (2..256)
+    return state_gc_onepass(c, xm_in, Xp_in, xm_out, Xp_out, ncol, rows / ncol, 0);
+  const long B = effective_batch(c, M);
+  bool first = true;
+  for (long b0 = 0; b0 < P; b0 += B) {
+    const int nb = (int)((P - b0 < B) ? (P - b0) : B);
+    long act = 0;
+    for (int k = 0; k < nb; ++k) act += c->h_assim[b0 + k] ? 1 : 0;
+    if (act == 0) continue;
+    SweepArgs a{};
+    a.Xin = first ? Xp_in : Xp_out;
+    a.xin = first ? xm_in : xm_out;
+    a.Xout = Xp_out;
+    a.xout = xm_out;
+    a.nrows = rows;
+    a.M = M;
+    a.Ye = c->ye_ptr + (size_t)b0 * c->ye_stride;
+    a.ye_stride = c->ye_stride;
+    a.coef = c->coef.as<double>() + (size_t)b0 * kCoefStride;
+    a.nb = nb;
+    a.skip_lo = a.skip_hi = -1;
+    if (c->loc_mode == EFA_LOC_GC) {
+      EFA_TRY(c->W.reserve((size_t)B * ncol * sizeof(double)));
+      EFA_HIP(launch_taper_table(ncol, nb, c->grid.lat.as<double>(), c->grid.lon.as<double>(), c->ob_lat + b0, c->ob_lon + b0, c->ob_hw + b0,
+                                 c->W.as<double>(), s));
+      a.taper_mode = kTaperTable;
+      a.W = c->W.as<double>();
+      a.ncol = ncol;
+    } else {
+      a.taper_mode = kTaperNone;
+    }
+    EFA_HIP(launch_sweep(a, s));
+    c->state_launches++;
+    first = false;
+  }
+  if (first && Xp_out != Xp_in) {  // nothing assimilated: posterior == prior
+    EFA_HIP(hipMemcpyAsync(Xp_out, Xp_in, (size_t)rows * M * sizeof(double), hipMemcpyDeviceToDevice, s));
+    EFA_HIP(hipMemcpyAsync(xm_out, xm_in, (size_t)rows * sizeof(double), hipMemcpyDeviceToDevice, s));
+  }
+  return EFA_OK;
+}
+
+// ---- the two state calls ------------------------------------------------------------------------------------------------------
+// start of a state-phase call, once its arguments are checked: the previous interval is read, the counters cleared
+void reset_state_phase(efa_ctx* c) {
+  harvest_state_ms(c);
+  c->state_ms = 0.0;
+  c->state_launches = 0;
+  c->path_taken = EFA_PATH_SWEEP;
+}
+
+// What both forms do before their first launch: the checks, the counters, and -- once there is work to do (rows > 0) -- the grid of
+// a localised call on the device and the begin of the state interval.  ptrs_ok: no state pointer of the form is null.
+int begin_state_call(efa_ctx* c, const char* who, long rows, int M, bool ptrs_ok, const double* grid_lat, const double* grid_lon,
+                     long ncol, long n_lead, const StateCall& o) {
+  if (!c->have_traj) return fail(EFA_ERR_INVALID, "%s called before efa_obs_phase_dev", who);
+  if (M != c->M) return fail(EFA_ERR_INVALID, "M=%d differs from the obs phase's M=%d", M, c->M);
+  if (rows < 0) return fail(EFA_ERR_INVALID, "negative row count");
+  EFA_TRY(check_adaptive(c, c->loc_mode, rows));
+  EFA_TRY(check_vloc(c, c->loc_mode, c->P, n_lead));
+  reset_state_phase(c);
+  if (rows == 0) return EFA_OK;
+  if (!ptrs_ok) return fail(EFA_ERR_INVALID, "null state pointer");
+  EFA_TRY(check_grid(c->loc_mode, grid_lat, grid_lon, ncol, n_lead, rows));
+  if (c->loc_mode == EFA_LOC_GC && !o.grid_current) EFA_TRY(c->grid.upload(c->stream, grid_lat, grid_lon, ncol));
+  if (c->timing && o.timed) EFA_HIP(hipEventRecord(c->state_iv[0].begin, c->stream));
+  return EFA_OK;
+}
+
+}  // namespace
+
+int end_state_call(efa_ctx* c, Interval& iv, bool timed, bool end_recorded) {
+  c->state_launches_sum += c->state_launches;
+  if (!c->timing || !timed) return EFA_OK;
+  if (!end_recorded) EFA_HIP(hipEventRecord(iv.end, c->stream));
+  iv.pending = true;
+  if (c->timing == 1) harvest_state_ms(c);
+  return EFA_OK;
+}
+
+// perturbation form (efa_state_phase_dev)
+int state_phase(efa_ctx* c, long rows, int M, const double* xm_in, const double* Xp_in, double* xm_out, double* Xp_out,
+                const double* grid_lat, const double* grid_lon, long ncol, long n_lead, const StateCall& o) {
+  EFA_TRY(begin_state_call(c, "efa_state_phase_dev", rows, M, xm_in && Xp_in && xm_out && Xp_out, grid_lat, grid_lon, ncol, n_lead, o));
+  if (rows == 0) return EFA_OK;
+  if (c->P > 0 && c->n_active > 0 && want_transform(c, false)) {
+    EFA_TRY(transform_with_relaxation(c, carried_transform(c, Xp_in, xm_in, Xp_out, xm_out, rows, 0), &c->state_launches));
+    c->path_taken = EFA_PATH_TRANSFORM;
+  } else {
+    EFA_TRY(with_relaxation(c, rows, M, Xp_in, Xp_out, &c->state_launches,
+                            [&] { return state_sweeps(c, rows, xm_in, Xp_in, xm_out, Xp_out, ncol); }));
+  }
+  return end_state_call(c, c->state_iv[0], o.timed);
+}
+
+// member form (efa_state_cycle_dev)
+int state_cycle(efa_ctx* c, long rows, int M, const double* X_dev, double* post_dev, const double* grid_lat,
+                const double* grid_lon, long ncol, long n_lead, const StateCall& o) {
+  EFA_TRY(begin_state_call(c, "efa_state_cycle_dev", rows, M, X_dev && post_dev, grid_lat, grid_lon, ncol, n_lead, o));
+  if (rows == 0) return EFA_OK;
+  hipStream_t s = c->stream;
+  if (c->P > 0 && c->n_active > 0 && want_transform(c, true)) {
+    EFA_TRY(transform_with_relaxation(c, carried_transform(c, X_dev, nullptr, post_dev, nullptr, rows, 1), &c->state_launches));
+    c->path_taken = EFA_PATH_TRANSFORM;
+  } else if (c->loc_mode == EFA_LOC_GC && c->gc_onepass && c->n_active > 0) {
+    // localised: prior members -> posterior members in one read + one write of the state
+    EFA_TRY(with_relaxation(c, rows, M, X_dev, post_dev, &c->state_launches,
+                            [&] { return state_gc_onepass(c, nullptr, X_dev, nullptr, post_dev, ncol, n_lead, 1); }));
+  } else {
+    EFA_TRY(with_relaxation(c, rows, M, X_dev, post_dev, &c->state_launches, [&]() -> int {
+      EFA_TRY(c->xm_ws.reserve((size_t)rows * sizeof(double)));
+      double* xm = c->xm_ws.as<double>();
+      EFA_HIP(launch_form_perts(rows, M, X_dev, 1.0, xm, post_dev, s));
+      EFA_TRY(state_sweeps(c, rows, xm, post_dev, xm, post_dev, ncol));
+      EFA_HIP(launch_posterior(rows, M, xm, post_dev, post_dev, s));
+      return EFA_OK;
+    }));
+  }
+  return end_state_call(c, c->state_iv[0], o.timed);
+}
+
+}  // namespace efa_host

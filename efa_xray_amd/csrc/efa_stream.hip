@@ -1,8 +1,8 @@
 // The streamed host-memory update (include/efa_hip.h: efa_ensrf_cycle_host, efa_pinned_alloc / efa_pinned_free): the prior stays in
 // host memory and crosses the device in chunks of (y, x) columns.  Upload of chunk i+1, state phase of chunk i and download of
 // chunk i-1 overlap on three streams; Phase A runs on the context's stream while the first chunks upload.  No kernel lives here:
-// a chunk is a column shard (row lead*(hi-lo) + (col-lo)), so efa_obs_phase_dev and efa_state_cycle_dev serve it as they are.
-#include "efa_ctx.h"
+// a chunk is a column shard (row lead*(hi-lo) + (col-lo)), so the obs phase and the member-form state call serve it as they are.
+#include "efa_driver.h"
 
 #include <algorithm>
 #include <chrono>
@@ -11,14 +11,7 @@
 
 namespace {
 
-using efa_host::PinnedBlock;
-using efa_host::StreamState;
-
-int use(efa_ctx* c) {
-  if (!c) return fail(EFA_ERR_INVALID, "null context");
-  EFA_HIP(hipSetDevice(c->device));
-  return EFA_OK;
-}
+using namespace efa_host;
 
 // the block of efa_pinned_alloc that holds [p, p + bytes), or null
 const PinnedBlock* find_block(const StreamState& st, const void* p, size_t bytes) {
@@ -164,21 +157,17 @@ int issue_state_phase(const Pipe& p, long i, int loc_mode, const double* grid_la
   EFA_HIP(hipStreamWaitEvent(s, p.ev(i, kUp1), 0));
   if (loc_mode == EFA_LOC_GC) {
     // the chunk's columns of the grid, from the copy of the whole grid the call put on the device: in stream order, no host wait
-    // (prepare_grid would copy from the caller's arrays and wait).  The one-pass sweep's lists are rebuilt: the grid changed.
-    const double* g = c->st.grid.as<double>();
-    EFA_HIP(hipMemcpyAsync(c->glat.p, g + k.lo(i), (size_t)cw * sizeof(double), hipMemcpyDeviceToDevice, s));
-    EFA_HIP(hipMemcpyAsync(c->glon.p, g + k.ncol + k.lo(i), (size_t)cw * sizeof(double), hipMemcpyDeviceToDevice, s));
-    c->grid_ncol = -1;
-    c->grid_serial++;
-    c->grid_ready = true;
+    // (an upload would copy from the caller's arrays and wait)
+    EFA_TRY(c->grid.take_slice(s, c->st.grid.as<double>(), k.ncol, k.lo(i), cw));
   }
   EFA_HIP(hipEventRecord(p.ev(i, kSt0), s));
   double* X = reinterpret_cast<double*>(p.slot(i));
-  const int rc = (loc_mode == EFA_LOC_GC)
-                     ? efa_state_cycle_dev(c, rows, k.M, X, X, grid_lat + k.lo(i), grid_lon + k.lo(i), cw, k.n_lead)
-                     : efa_state_cycle_dev(c, rows, k.M, X, X, nullptr, nullptr, rows, 1);
-  c->grid_ready = false;
-  EFA_TRY(rc);
+  // the chunk loop keeps its own events: the context's per-call timing would make every state phase wait for its end
+  StateCall sc;
+  sc.grid_current = true;
+  sc.timed = false;
+  if (loc_mode == EFA_LOC_GC) EFA_TRY(state_cycle(c, rows, k.M, X, X, grid_lat + k.lo(i), grid_lon + k.lo(i), cw, k.n_lead, sc));
+  else EFA_TRY(state_cycle(c, rows, k.M, X, X, nullptr, nullptr, rows, 1, sc));
   *launches += c->state_launches;
   EFA_HIP(hipEventRecord(p.ev(i, kSt1), s));
   return EFA_OK;
@@ -214,14 +203,13 @@ int run_pipeline(Pipe& p, long P, const double* HX, const double* ob_value, cons
     EFA_TRY(st.pin_obs.reserve(nb));
     std::memcpy(st.pin_obs.p, HX, nb);
     EFA_HIP(hipMemcpyAsync(st.HX.p, st.pin_obs.p, nb, hipMemcpyHostToDevice, s));
-    EFA_TRY(efa_form_perts_dev(c, P, M, st.HX.as<double>(), 1.0, st.ym.as<double>(), st.HX.as<double>()));  // assimilation.py:46-48
+    EFA_TRY(form_perts(c, P, M, st.HX.as<double>(), 1.0, st.ym.as<double>(), st.HX.as<double>()));  // assimilation.py:46-48
   }
   if (loc_mode == EFA_LOC_GC && k.nchunk > 0) {
     const size_t nb = (size_t)k.ncol * sizeof(double);
     EFA_TRY(st.pin_grid.reserve(2 * nb));
     EFA_TRY(st.grid.reserve(2 * nb));
-    EFA_TRY(c->glat.reserve((size_t)k.cc * sizeof(double)));
-    EFA_TRY(c->glon.reserve((size_t)k.cc * sizeof(double)));
+    EFA_TRY(c->grid.reserve(k.cc));
     std::memcpy(st.pin_grid.p, grid_lat, nb);
     std::memcpy(static_cast<char*>(st.pin_grid.p) + nb, grid_lon, nb);
     EFA_HIP(hipMemcpyAsync(st.grid.p, st.pin_grid.p, 2 * nb, hipMemcpyHostToDevice, s));
@@ -232,11 +220,8 @@ int run_pipeline(Pipe& p, long P, const double* HX, const double* ob_value, cons
   long issued = 0;
   const long ahead = k.in_pinned ? StreamState::kRing - 1 : 1;
   for (; issued < k.nchunk && issued < ahead; ++issued) EFA_TRY(issue_upload(p, issued));
-  EFA_TRY(efa_obs_phase_dev(c, M, P, st.ym.as<double>(), st.HX.as<double>(), ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon,
-                            ob_hw, prior_mean, prior_var, post_mean, post_var, assimilated));
-  // the chunk loop keeps its own events: the context's per-call timing would make every state phase wait for its end
-  const long timing = c->timing;
-  c->timing = 0;
+  EFA_TRY(obs_phase(c, M, P, st.ym.as<double>(), st.HX.as<double>(), ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon, ob_hw,
+                    prior_mean, prior_var, post_mean, post_var, assimilated));
   long launches = 0;
   int rc = EFA_OK;
   for (long i = 0; i < k.nchunk && rc == EFA_OK; ++i) {
@@ -250,7 +235,6 @@ int run_pipeline(Pipe& p, long P, const double* HX, const double* ob_value, cons
     if (rc == EFA_OK && i > 0) rc = drain_download(p, i - 1);
   }
   if (rc == EFA_OK && k.nchunk > 0) rc = drain_download(p, k.nchunk - 1);
-  c->timing = timing;
   EFA_TRY(rc);
   EFA_HIP(hipStreamSynchronize(p.dn));
   EFA_HIP(hipStreamSynchronize(p.up));
@@ -267,7 +251,7 @@ int run_pipeline(Pipe& p, long P, const double* HX, const double* ob_value, cons
   }
   c->state_ms = state_ms;
   c->state_launches = launches;
-  if (timing == 2) c->state_ms_sum += state_ms;
+  if (c->timing == 2) c->state_ms_sum += state_ms;
   return EFA_OK;
 }
 
@@ -398,7 +382,6 @@ int efa_ensrf_cycle_host(efa_ctx* c, int n_seg, const double* const* seg_prior, 
     (void)hipStreamSynchronize(c->stream);
     (void)hipStreamSynchronize(p.dn);
     (void)hipGetLastError();
-    c->grid_ready = false;
     return fail(rc, "%s", msg.c_str());
   }
   st.wall_us = (long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();

@@ -6,7 +6,7 @@ Phase A to the vector-chain kernel (`phase_a_kind` 1) -- when an assimilated ob'
 efa_pipeline_gram.hip, `thr_ld`).  The rows are centred, so `G_kk = M np.var(row)`: the guard's quantity is
 np.var of ob k's row at its step (the oracle's `prior_var[k]`) over np.var of the same row at the step that starts
 its block.  Blocks are 64 launch rows counted from the start of the persistent launch's window; a launch holds at
-most 256 x 64 rows, less the carried transform rows (efa_capi.hip, the Phase-A window loop).
+most 256 x 64 rows, less the carried transform rows (efa_phase_a.hip, the Phase-A window loop).
 
 Use: pass a `GuardProbe` as `step_hook` to `oracle.ensrf_update` (any state rows may ride along: the obs rows do
 not depend on them), then `probe.min_ratio()`; `expected_kind` maps it onto the kernel the library should report.
@@ -24,7 +24,7 @@ FALLS_BACK = 5e-4      # ... and one that expects the fallback at least this far
 
 
 def window_starts(P, extra=0):
-    """First ob of every Phase-A window (efa_capi.hip: Wone / Wmax); `extra` = carried transform rows
+    """First ob of every Phase-A window (efa_phase_a.hip: Wone / Wmax); `extra` = carried transform rows
     (M without localisation on the transform / auto paths, else 0)."""
     wone = MAX_LAUNCH_ROWS - extra
     wmax = wone if P <= wone else wone - extra
