@@ -99,6 +99,14 @@ SIGNATURES = {
                                             c_double_p, c_double_p, c_uint8_p, ctypes.c_int,
                                             c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                             c_double_p, c_double_p, c_double_p, c_double_p, c_uint8_p]),
+    "efa_ensrf_cycle_host_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_void_pp, c_void_pp, ctypes.POINTER(ctypes.c_long),
+                                                ctypes.c_long, ctypes.c_int, ctypes.c_long, c_double_p, ctypes.c_long,
+                                                c_double_p, c_double_p, c_uint8_p, ctypes.c_int,
+                                                c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                c_double_p, c_double_p, c_double_p, c_double_p, c_uint8_p]),
+    "efa_state_cycle_f32_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p,
+                                               ctypes.c_void_p, c_double_p, c_double_p, ctypes.c_long,
+                                               ctypes.c_long]),
     "efa_pinned_alloc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, c_void_pp]),
     "efa_pinned_free": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "efa_ensrf_update": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_int,
@@ -202,10 +210,26 @@ def _u8p(a):
     return a.ctypes.data_as(c_uint8_p)
 
 
-def plan_chunks(ncol, chunk_cols):
-    """The column chunks [(lo, hi), ...] of a streamed update (efa_ensrf_cycle_host): contiguous, covering [0, ncol), every cut on
-    a multiple of 16 columns (the one-pass sweep's block), the last chunk taking the ragged rest.  A budget below one block gives
-    one block per chunk."""
+def state_dtype(dtype):
+    """The storage dtype of a state: None -> float64 (the default everywhere); float64 and float32 as given; anything else raises
+    ValueError.  float32 is storage only: every number is computed in float64."""
+    if dtype is None:
+        return np.dtype(np.float64)
+    try:
+        dt = np.dtype(dtype)
+    except TypeError:
+        raise ValueError("dtype=%r: expected None, numpy.float64 or numpy.float32" % (dtype,))
+    if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError("dtype=%r: a state is stored as float64 (None) or float32" % (dtype,))
+    return dt
+
+
+def plan_chunks(ncol, chunk_cols, itemsize=8):
+    """The column chunks [(lo, hi), ...] of a streamed update (efa_ensrf_cycle_host / _f32): contiguous, covering [0, ncol), every
+    cut on a multiple of 16 columns (the one-pass sweep's block), the last chunk taking the ragged rest.  A budget below one block
+    gives one block per chunk.  The cuts are in columns, so they are the same for either item size (8 or 4 bytes)."""
+    if itemsize not in (4, 8):
+        raise ValueError("plan_chunks: itemsize must be 8 (float64) or 4 (float32), got %r" % (itemsize,))
     ncol, chunk_cols = int(ncol), int(chunk_cols)
     if ncol < 0 or chunk_cols < 1:
         raise ValueError("plan_chunks: need ncol >= 0 and chunk_cols >= 1, got %d and %d" % (ncol, chunk_cols))
@@ -213,9 +237,11 @@ def plan_chunks(ncol, chunk_cols):
     return [(lo, min(lo + cc, ncol)) for lo in range(0, ncol, cc)]
 
 
-def default_chunk_cols(n_lead, M, target_bytes=64 << 20):
-    """Columns per chunk for a chunk of about `target_bytes` (n_lead slabs of M float64 members per column)."""
-    return max(16, int(target_bytes // max(1, int(n_lead) * int(M) * 8)) // 16 * 16)
+def default_chunk_cols(n_lead, M, target_bytes=64 << 20, itemsize=8):
+    """Columns per chunk for a chunk of about `target_bytes` (n_lead slabs of M members of `itemsize` bytes per column)."""
+    if itemsize not in (4, 8):
+        raise ValueError("default_chunk_cols: itemsize must be 8 (float64) or 4 (float32), got %r" % (itemsize,))
+    return max(16, int(target_bytes // max(1, int(n_lead) * int(M) * int(itemsize))) // 16 * 16)
 
 
 def compact_stencil(idx):
@@ -231,17 +257,18 @@ def compact_stencil(idx):
 
 
 class PinnedBlock(object):
-    """One block of efa_pinned_alloc, exposed through the array interface: `np.asarray(block)` is a writable float64 view whose
-    base keeps the block alive; the block goes back to its context's pool when the last view is collected."""
+    """One block of efa_pinned_alloc, exposed through the array interface: `np.asarray(block)` is a writable view (float64, or the
+    block's `dtype`) whose base keeps the block alive; the block goes back to its context's pool when the last view is collected."""
 
-    def __init__(self, ctx, nbytes):
+    def __init__(self, ctx, nbytes, dtype=np.float64):
         self.ctx = ctx
         self.nbytes = int(nbytes)
+        self.dtype = np.dtype(dtype)
         self.ptr = ctx._pinned_take(self.nbytes)
 
     @property
     def __array_interface__(self):
-        return {"shape": (self.nbytes // 8,), "typestr": "<f8", "data": (self.ptr, False), "version": 3}
+        return {"shape": (self.nbytes // self.dtype.itemsize,), "typestr": self.dtype.str, "data": (self.ptr, False), "version": 3}
 
     def __del__(self):
         try:
@@ -253,12 +280,14 @@ class PinnedBlock(object):
 
 
 class DeviceArray(object):
-    """A float64 array in the context GPU's HBM (hipMalloc via efa_malloc)."""
+    """A float64 (or, with dtype=numpy.float32, float32) array in the context GPU's HBM (hipMalloc via efa_malloc)."""
 
-    def __init__(self, ctx, shape):
+    def __init__(self, ctx, shape, dtype=None):
         self.ctx = ctx
         self.shape = tuple(int(s) for s in np.atleast_1d(shape))
-        self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * 8
+        self.dtype = state_dtype(dtype)
+        self.itemsize = self.dtype.itemsize
+        self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.itemsize
         ptr = ctypes.c_void_p()
         _check(ctx.lib, ctx.lib.efa_malloc(ctx.handle, self.nbytes, ctypes.byref(ptr)))
         self.ptr = ptr
@@ -268,40 +297,40 @@ class DeviceArray(object):
         return self.ptr.value
 
     def upload(self, host):
-        host = np.ascontiguousarray(host, dtype=np.float64)
+        host = np.ascontiguousarray(host, dtype=self.dtype)
         assert host.nbytes == self.nbytes, (host.shape, self.shape)
         _check(self.ctx.lib, self.ctx.lib.efa_memcpy_h2d(self.ctx.handle, self.ptr, host.ctypes.data, self.nbytes))
         return self
 
     def download(self, out=None):
         if out is None:
-            out = np.empty(self.shape, dtype=np.float64)
-        assert out.nbytes == self.nbytes and out.flags["C_CONTIGUOUS"]
+            out = np.empty(self.shape, dtype=self.dtype)
+        assert out.dtype == self.dtype and out.nbytes == self.nbytes and out.flags["C_CONTIGUOUS"]
         _check(self.ctx.lib, self.ctx.lib.efa_memcpy_d2h(self.ctx.handle, out.ctypes.data, self.ptr, self.nbytes))
         return out
 
     def upload_rows(self, r0, host):
-        """Rows [r0, r0 + len(host)) from a C-contiguous float64 host array, straight from the caller's memory."""
-        host = np.ascontiguousarray(host, dtype=np.float64)
+        """Rows [r0, r0 + len(host)) from a C-contiguous host array of the array's dtype, straight from the caller's memory."""
+        host = np.ascontiguousarray(host, dtype=self.dtype)
         width = int(np.prod(self.shape[1:], dtype=np.int64)) if len(self.shape) > 1 else 1
-        assert host.size % width == 0 and r0 * width * 8 + host.nbytes <= self.nbytes
-        dst = ctypes.c_void_p(self.ptr.value + r0 * width * 8)
+        assert host.size % width == 0 and r0 * width * self.itemsize + host.nbytes <= self.nbytes
+        dst = ctypes.c_void_p(self.ptr.value + r0 * width * self.itemsize)
         _check(self.ctx.lib, self.ctx.lib.efa_memcpy_h2d(self.ctx.handle, dst, host.ctypes.data, host.nbytes))
 
     def download_rows_into(self, r0, out):
-        """Rows [r0, r0 + out.size / width) into `out` (C-contiguous float64), without an intermediate array."""
-        assert out.dtype == np.float64 and out.flags["C_CONTIGUOUS"]
+        """Rows [r0, r0 + out.size / width) into `out` (C-contiguous, the array's dtype), without an intermediate array."""
+        assert out.dtype == self.dtype and out.flags["C_CONTIGUOUS"]
         width = int(np.prod(self.shape[1:], dtype=np.int64)) if len(self.shape) > 1 else 1
-        assert out.size % width == 0 and r0 * width * 8 + out.nbytes <= self.nbytes
-        src = ctypes.c_void_p(self.ptr.value + r0 * width * 8)
+        assert out.size % width == 0 and r0 * width * self.itemsize + out.nbytes <= self.nbytes
+        src = ctypes.c_void_p(self.ptr.value + r0 * width * self.itemsize)
         _check(self.ctx.lib, self.ctx.lib.efa_memcpy_d2h(self.ctx.handle, out.ctypes.data, src, out.nbytes))
         return out
 
     def download_rows(self, r0, r1):
         """Rows [r0, r1) of a 2-D (or 1-D) array, without copying the rest."""
         width = int(np.prod(self.shape[1:], dtype=np.int64)) if len(self.shape) > 1 else 1
-        out = np.empty((r1 - r0,) + self.shape[1:], dtype=np.float64)
-        src = ctypes.c_void_p(self.ptr.value + r0 * width * 8)
+        out = np.empty((r1 - r0,) + self.shape[1:], dtype=self.dtype)
+        src = ctypes.c_void_p(self.ptr.value + r0 * width * self.itemsize)
         _check(self.ctx.lib, self.ctx.lib.efa_memcpy_d2h(self.ctx.handle, out.ctypes.data, src, out.nbytes))
         return out
 
@@ -399,12 +428,12 @@ class Context(object):
         _check(self.lib, self.lib.efa_ctx_synchronize(self.handle))
 
     # -- memory ---------------------------------------------------------------
-    def empty(self, shape):
-        return DeviceArray(self, shape)
+    def empty(self, shape, dtype=None):
+        return DeviceArray(self, shape, dtype)
 
-    def to_device(self, host):
-        host = np.ascontiguousarray(host, dtype=np.float64)
-        return DeviceArray(self, host.shape).upload(host)
+    def to_device(self, host, dtype=None):
+        host = np.ascontiguousarray(host, dtype=state_dtype(dtype))
+        return DeviceArray(self, host.shape, host.dtype).upload(host)
 
     # -- page-locked host memory the context owns (efa_pinned_alloc) ------------
     def _pinned_take(self, nbytes):
@@ -468,26 +497,34 @@ class Context(object):
                 self.pinned_trim(keep=sizes)
             return True
 
-    def pinned_empty(self, shape):
-        """A writable C-contiguous float64 array in page-locked memory of this context: `efa_ensrf_cycle_host` moves it by DMA
-        without staging.  The memory goes back to the context when the array (and every view of it) is collected."""
+    def pinned_empty(self, shape, dtype=None):
+        """A writable C-contiguous float64 (dtype None) or float32 array in page-locked memory of this context:
+        `efa_ensrf_cycle_host` / `_f32` move it by DMA without staging.  The memory goes back to the context when the array (and
+        every view of it) is collected."""
+        dt = state_dtype(dtype)
         shape = tuple(int(v) for v in np.atleast_1d(shape))
         n = int(np.prod(shape, dtype=np.int64))
-        return np.asarray(PinnedBlock(self, max(n, 1) * 8))[:n].reshape(shape)
+        return np.asarray(PinnedBlock(self, max(max(n, 1) * dt.itemsize, 8), dt))[:n].reshape(shape)
 
     def ensrf_cycle_host(self, seg_prior, seg_post, ncol, M, HX, chunk_cols, ob_value, ob_error, ob_assim, loc_mode=LOC_NONE,
                          ob_lat=None, ob_lon=None, ob_halfwidth=None, grid_lat=None, grid_lon=None):
         """efa_ensrf_cycle_host: one whole cycle on a prior in host memory, streamed through the device in chunks of `chunk_cols`
         columns.  seg_prior / seg_post: lists of C-contiguous float64 arrays (slabs, ncol, M) -- any leading shape that flattens
-        to it -- one per variable; the posterior is written into seg_post.  Returns the diagnostics."""
+        to it -- one per variable; the posterior is written into seg_post.  Arrays that are all float32 go through
+        efa_ensrf_cycle_host_f32 (float32 storage, float64 arithmetic: DESIGN.md 7g).  Returns the diagnostics."""
         n_seg = len(seg_prior)
         assert len(seg_post) == n_seg
+        dts = set(x.dtype for x in list(seg_prior) + list(seg_post))
+        if len(dts) > 1:
+            raise ValueError("ensrf_cycle_host: the segments mix dtypes %r" % sorted(str(d) for d in dts))
+        dt = state_dtype(dts.pop() if dts else None)
+        fn = self.lib.efa_ensrf_cycle_host_f32 if dt == np.float32 else self.lib.efa_ensrf_cycle_host
         slabs = (ctypes.c_long * max(n_seg, 1))()
         pin = (ctypes.c_void_p * max(n_seg, 1))()
         pout = (ctypes.c_void_p * max(n_seg, 1))()
         for v, (a, b) in enumerate(zip(seg_prior, seg_post)):
             for x in (a, b):
-                assert x.dtype == np.float64 and x.flags["C_CONTIGUOUS"]
+                assert x.dtype == dt and x.flags["C_CONTIGUOUS"]
             assert a.shape == b.shape and b.flags["WRITEABLE"]
             assert ncol * M == 0 or a.size % (ncol * M) == 0
             slabs[v] = a.size // (ncol * M) if ncol * M else 0
@@ -502,7 +539,7 @@ class Context(object):
         if loc_mode == LOC_GC:
             assert gcol == ncol
         d = self._diag_arrays(P)
-        _check(self.lib, self.lib.efa_ensrf_cycle_host(
+        _check(self.lib, fn(
             self.handle, n_seg, ctypes.cast(pin, c_void_pp), ctypes.cast(pout, c_void_pp), slabs, int(ncol), int(M), P,
             _dp(HX) if P else None, int(chunk_cols), _dp(val), _dp(err), _u8p(asm), loc_mode, _dp(lat), _dp(lon), _dp(hw),
             _dp(glat), _dp(glon), _dp(d["prior_mean"]), _dp(d["prior_var"]), _dp(d["post_mean"]), _dp(d["post_var"]),
@@ -516,10 +553,15 @@ class Context(object):
 
     # -- kernels --------------------------------------------------------------
     @staticmethod
-    def _addr(x):
+    def _addr(x, dtype=np.float64):
+        """Device address of `x` for a kernel whose elements are `dtype` (None: any).  A DeviceArray of another dtype raises
+        ValueError: a float64 kernel on a float32 allocation would read and write past its end."""
         if x is None:
             return None
         if isinstance(x, DeviceArray):
+            if dtype is not None and x.dtype != np.dtype(dtype):
+                raise ValueError("this call works on %s device memory, but was given a %s DeviceArray (DESIGN.md 7g)"
+                                 % (np.dtype(dtype).name, x.dtype.name))
             return x.ptr
         if isinstance(x, ctypes.c_void_p):
             return x
@@ -626,6 +668,15 @@ class Context(object):
         _check(self.lib, self.lib.efa_state_cycle_dev(
             self.handle, rows, M, self._addr(X), self._addr(post), _dp(glat), _dp(glon), ncol, n_lead))
 
+    def state_cycle_f32(self, rows, M, X, post, grid_lat=None, grid_lon=None, n_lead=1):
+        """efa_state_cycle_f32_dev: `state_cycle` on float32 member rows (posterior = the float64 result rounded once)."""
+        loc_mode = LOC_GC if grid_lat is not None else LOC_NONE
+        glat, glon, ncol = self._grid(loc_mode, grid_lat, grid_lon)
+        if loc_mode == LOC_NONE:
+            ncol, n_lead = rows, 1
+        _check(self.lib, self.lib.efa_state_cycle_f32_dev(
+            self.handle, rows, M, self._addr(X, np.float32), self._addr(post, np.float32), _dp(glat), _dp(glon), ncol, n_lead))
+
     def ensrf_cycle(self, rows, M, P, X, post, ym, Yp, ob_value, ob_error, ob_assim, loc_mode=LOC_NONE,
                     ob_lat=None, ob_lon=None, ob_halfwidth=None, grid_lat=None, grid_lon=None, n_lead=1, obs_block_out=False):
         """Phase A + the state phase on resident prior members in ONE call (efa_ensrf_cycle_dev): Phase B goes into the stream
@@ -684,8 +735,8 @@ class Context(object):
 
     def cov_contract_f32(self, N, M, P, Xbp_f32, Ye_f32, C_f32):
         """C (N x P) = Xbp (N x M) . Ye^T (P x M), float32, device addresses."""
-        _check(self.lib, self.lib.efa_cov_contract_f32_dev(self.handle, N, M, P, self._addr(Xbp_f32),
-                                                           self._addr(Ye_f32), self._addr(C_f32)))
+        _check(self.lib, self.lib.efa_cov_contract_f32_dev(self.handle, N, M, P, self._addr(Xbp_f32, np.float32),
+                                                           self._addr(Ye_f32, np.float32), self._addr(C_f32, np.float32)))
 
     def malloc_bytes(self, nbytes):
         ptr = ctypes.c_void_p()

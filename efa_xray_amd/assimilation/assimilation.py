@@ -79,13 +79,18 @@ class Assimilation(object):
 
         def scale_var(name, factor, inplace=True):
             v = prior.variables[name]
+            store = v.dtype
+            if store != np.float64:     # a float32 state: scaled in float64, rounded once on the way back
+                out, v = v, v.astype(np.float64)
             mean = v.mean(axis=-1, keepdims=True)
             if self.verbose:
                 print(name, "BEFORE stdev:", np.mean(np.std(v, axis=-1), axis=None))
-            if inplace:
+            if inplace and store != np.float64:
+                out[...] = (v - mean) * factor + mean
+            elif inplace:
                 v[...] = (v - mean) * factor + mean          # `variables[v][:] = ...`, assimilation.py:67,113
             else:
-                prior.variables[name] = np.ascontiguousarray((v - mean) * factor + mean)
+                prior.variables[name] = np.ascontiguousarray((v - mean) * factor + mean, dtype=store)
             if self.verbose:
                 print(name, "AFTER stdev:", np.mean(np.std(prior.variables[name], axis=-1), axis=None))
 
@@ -148,12 +153,14 @@ class Assimilation(object):
         self.is_inflated = True
 
     # -- the state between host and device: one pass each way, variable by variable ----------------
-    def _upload_prior(self, ctx):
+    def _upload_prior(self, ctx, dtype=None):
         """The prior as an (nstate, nmems) device array in `to_vect()` order (ensemble.py:110-114), copied slab by slab
-        from each variable's own (nt, ny, nx, nmem) array: no stacked host copy of the state is made."""
+        from each variable's own (nt, ny, nx, nmem) array: no stacked host copy of the state is made.  `dtype` None: the
+        state's own storage dtype (float32 rows for a state stored so); numpy.float64 widens a float32 state slab by slab, for
+        the float64 kernels of the `format_*` / `compute_ob_*` helpers."""
         prior = self.prior
         N, M = prior.nstate(), prior.nmems()
-        X = ctx.empty((max(N, 1), M))
+        X = ctx.empty((max(N, 1), M), prior.dtype if dtype is None else dtype)
         per = prior.ntimes() * prior.ny() * prior.nx()
         for iv, name in enumerate(prior.vars()):
             X.upload_rows(iv * per, prior.variables[name])
@@ -161,13 +168,15 @@ class Assimilation(object):
 
     def _download_posterior(self, X):
         """A NEW state object like the prior (assimilation.py:165 deep-copies it) whose variables are the rows of the device
-        array `X`: coordinates are copied, member arrays are downloaded straight into their own fresh arrays."""
+        array `X`: coordinates are copied, member arrays are downloaded straight into their own fresh arrays.  The new state has
+        the prior's storage dtype: float64 rows of a float32 prior (`format_posterior_state`) are rounded to float32 once."""
         prior = self.prior
         per = prior.ntimes() * prior.ny() * prior.nx()
         shape = prior.shape()[1:]
         variables = OrderedDict()
         for iv, name in enumerate(prior.vars()):
-            variables[name] = X.download_rows_into(iv * per, np.empty(shape, dtype=np.float64))
+            v = X.download_rows_into(iv * per, np.empty(shape, dtype=X.dtype))
+            variables[name] = v if v.dtype == prior.dtype else v.astype(prior.dtype)
         return type(prior)(variables, deepcopy(prior.coords))
 
     def _default_forward_operator(self):
@@ -240,8 +249,8 @@ class Assimilation(object):
         return idx, wts
 
     def gather_state_rows(self, rows):
-        """to_vect()[rows] as a new (len(rows), nmems) array, gathered from the variables' own arrays: no stacked copy of the
-        state is made."""
+        """to_vect()[rows] as a new float64 (len(rows), nmems) array (float32 members widened), gathered from the variables' own
+        arrays: no stacked copy of the state is made."""
         prior = self.prior
         rows = np.asarray(rows, dtype=np.int64)
         per = prior.ntimes() * prior.ny() * prior.nx()
@@ -271,10 +280,14 @@ class Assimilation(object):
         """(P, M) ensemble estimates HX[k] = ob_k.estimate(prior): the forward operator loop of
         assimilation.py:45-46.  With the reference's own point-interpolation operator the whole loop runs on
         the device (`device_ob_estimates`, on the resident copy `X_dev` of the prior if the caller has one);
-        user-defined `estimate` methods are called one by one."""
+        user-defined `estimate` methods are called one by one.  A float32 prior works as well: the forward kernels are float64,
+        so without a float64 `X_dev` the stencil rows are gathered on the host and widened (`streamed_ob_estimates`, the same
+        bits as the resident route on the widened state); a float32 `X_dev` raises ValueError."""
         nobs = len(self.obs)
         if self._default_forward_operator():
             ctx = self._context()
+            if X_dev is None and self.prior.dtype == np.float32:
+                return self.streamed_ob_estimates(ctx)
             X = X_dev if X_dev is not None else self._upload_prior(ctx)
             return self.device_ob_estimates(ctx, X).download()
         HX = np.zeros((nobs, self.prior.nmems()))
@@ -297,13 +310,14 @@ class Assimilation(object):
     def format_prior_state(self):
         """Augmented (xbm, Xbp): state rows then one row per ob
         (assimilation.py:120-154).  Inflates the prior first when `inflation` is set
-        (assimilation.py:131-134)."""
+        (assimilation.py:131-134).  The augmented arrays are float64 whatever the state's storage: a float32 prior is widened
+        on upload (exactly), so they are those of `prior.astype(numpy.float64)`."""
         if self.inflation is not None:
             if self.verbose:
                 print("Inflating Prior State")
             self.inflate_state()
         ctx = self._context()
-        d = self._upload_prior(ctx)                    # ONE upload serves the forward operator and the perturbations
+        d = self._upload_prior(ctx, np.float64)        # ONE upload serves the forward operator and the perturbations
         obmeans, obperts = self.compute_ob_priors(d)
         N, M = self.prior.nstate(), self.prior.nmems()
         m = ctx.empty((N,))
@@ -313,7 +327,8 @@ class Assimilation(object):
         return xbm, Xbp
 
     def format_posterior_state(self, xam, Xap):
-        """(xam, Xap) -> new state object + the obs list (assimilation.py:157-171)."""
+        """(xam, Xap) -> new state object + the obs list (assimilation.py:157-171).  The state has the prior's storage dtype:
+        for a float32 prior the float64 members are rounded to float32 once."""
         N = self.prior.nstate()
         M = self.prior.nmems()
         ctx = self._context()

@@ -134,6 +134,14 @@ class EnSRF(Assimilation):
                     about 64 MB per chunk
         stream_pinned_limit_mb -- page-locked posterior memory allowed in use at once (default 4096);
                     above it the posterior arrays are ordinary ones and the download is staged
+
+        A state stored as float32 (`EnsembleState.from_vardict(..., dtype=numpy.float32)`, `state.astype`)
+        stays float32 from end to end -- upload, device memory, download, posterior -- while every number
+        is computed in float64: the posterior is the float64 result rounded once.  The
+        obs-space estimates come from the host gather of the stencil rows (`streamed_ob_estimates`),
+        user-defined `estimate` operators see the float32 state object, and `inflation=` scales in
+        float64 and rounds once.  With a float32 state `adaptive_inflation` raises ValueError (its
+        field update is float64 only), and so do `update_arrays` and `ShardedEnSRF`.
         """
         device = kw.pop("device", 0)
         self.obs_batch = kw.pop("obs_batch", None)
@@ -159,6 +167,9 @@ class EnSRF(Assimilation):
             if inflation is not None:
                 raise ValueError("adaptive_inflation and inflation= are exclusive: the adaptive field is the prior inflation")
             adaptive.check_state(state)
+        if adaptive is not None and state.dtype == np.float32:
+            raise ValueError("adaptive_inflation does not support a float32 state (its field update is float64 only, "
+                             "DESIGN.md 7g); use state.astype(numpy.float64)")
         self.adaptive_inflation = adaptive
         self.streamed, self.stream_chunk_cols, self.stream_pinned_limit = stream_setting(
             streamed, stream_chunk_cols, stream_pinned_limit_mb, adaptive)
@@ -253,15 +264,16 @@ class EnSRF(Assimilation):
         if loc_mode == _lib.LOC_GC:
             grid_lat, grid_lon = prior.column_latlon()
         names = prior.vars()
-        seg_prior = [np.ascontiguousarray(prior.variables[n], dtype=np.float64) for n in names]
+        dt = prior.dtype                          # float32 states stream as float32 (efa_ensrf_cycle_host_f32)
+        seg_prior = [np.ascontiguousarray(prior.variables[n], dtype=dt) for n in names]
         # the posterior is a NEW state: member arrays in page-locked memory of the context while the limit allows
         if ctx.pinned_reserve([a.nbytes for a in seg_prior], self.stream_pinned_limit):
-            seg_post = [ctx.pinned_empty(a.shape) for a in seg_prior]
+            seg_post = [ctx.pinned_empty(a.shape, dt) for a in seg_prior]
         else:
-            seg_post = [np.empty(a.shape, dtype=np.float64) for a in seg_prior]
+            seg_post = [np.empty(a.shape, dtype=dt) for a in seg_prior]
         chunk_cols = self.stream_chunk_cols
         if chunk_cols is None:
-            chunk_cols = _lib.default_chunk_cols(nvar * nt, M)
+            chunk_cols = _lib.default_chunk_cols(nvar * nt, M, itemsize=dt.itemsize)
         if self.verbose:
             print("Beginning observation loop")
         diag = ctx.ensrf_cycle_host(seg_prior, seg_post, ncol, M, HX, chunk_cols, value, error, assim, loc_mode, lat, lon, hw,
@@ -274,12 +286,57 @@ class EnSRF(Assimilation):
         post_state = type(prior)(OrderedDict(zip(names, seg_post)), deepcopy(prior.coords))
         return post_state, self.obs
 
+    def _update_f32(self, loc_mode, P, value, error, assim, lat, lon, hw):
+        """update() with a resident state stored as float32 (efa_state_cycle_f32_dev): float32 up, the obs-space
+        estimates from the host gather of the stencil rows (widened), Phase A in float64, the state phase in place on the float32
+        rows, float32 down."""
+        prior = self.prior
+        N, M = prior.nstate(), prior.nmems()
+        ctx = self._context()
+        self._configure(ctx)
+        ctx.set_option("timing", 1)
+        if self.verbose:
+            print("Converting state to vector")
+        X = self._upload_prior(ctx)
+        if self.verbose:
+            print("Computing observation priors")
+        ym = ctx.empty((max(P, 1),))
+        if P:
+            HX = self.streamed_ob_estimates(ctx) if self._default_forward_operator() else self.compute_ob_estimates()
+            Yp = ctx.to_device(HX)
+            ctx.form_perts(P, M, Yp, ym, Yp)                   # assimilation.py:46-48
+        else:
+            Yp = ctx.empty((1, M))
+        grid_lat = grid_lon = None
+        n_lead = 1
+        if loc_mode == _lib.LOC_GC:
+            grid_lat, grid_lon = prior.column_latlon()
+            n_lead = prior.nvars() * prior.ntimes()
+        if self.verbose:
+            print("Beginning observation loop")
+        diag = ctx.obs_phase(M, P, ym, Yp, value, error, assim, loc_mode, lat, lon, hw)
+        ctx.state_cycle_f32(N, M, X, X, grid_lat, grid_lon, n_lead)
+        ctx.synchronize()
+        self.last_timing = ctx.last_timing()
+        self._write_diagnostics(diag)
+        if self.verbose:
+            print("Formatting posterior")
+        return self._download_posterior(X), self.obs
+
     # ------------------------------------------------------------------
     def update(self):
         if self.verbose:
             print("Beginning update sequence")
         loc_mode = self._loc_mode()
         P, value, error, assim, lat, lon, hw = self._ob_arrays(loc_mode)
+        if self.prior.dtype == np.float32 and self.adaptive_inflation is not None:
+            raise ValueError("adaptive_inflation does not support a float32 state (DESIGN.md 7g)")
+        if self.prior.dtype == np.float32 and not self.streamed:
+            if self.inflation is not None:      # the inflation hook comes first, as below
+                if self.verbose:
+                    print("Inflating Prior State")
+                self.inflate_state()
+            return self._update_f32(loc_mode, P, value, error, assim, lat, lon, hw)
         if self.streamed:
             if self.inflation is not None:      # the inflation hook comes first, as below
                 if self.verbose:
@@ -386,6 +443,9 @@ class EnSRF(Assimilation):
         onto the observations."""
         if self.streamed:
             raise ValueError("update_arrays is not available on a streamed filter (it takes the augmented arrays whole); "
+                             "use update()")
+        if self.prior.dtype == np.float32:
+            raise ValueError("update_arrays does not support a float32 state (the augmented arrays are float64, DESIGN.md 7g); "
                              "use update()")
         if self.adaptive_inflation is not None:
             raise ValueError("update_arrays does not support adaptive_inflation (out of scope: it runs on the augmented "

@@ -333,6 +333,7 @@ int efa_ctx_get_option(efa_ctx* c, const char* key, long* value) {
   else if (!strcmp(key, "pipe_dbg_addr")) *value = (long)reinterpret_cast<uintptr_t>(c->dbg.p);
   else if (!strcmp(key, "traj_addr")) *value = (long)reinterpret_cast<uintptr_t>(c->traj.p);  // (diagnostic tools only)
   else if (!strcmp(key, "device")) *value = c->device;
+  else if (!strcmp(key, "f32_native")) *value = c->f32_native;  // the last efa_state_cycle_f32_dev / chunk of efa_ensrf_cycle_host_f32
   else if (!strcmp(key, "stream_chunks")) *value = c->st.chunks;  // the last efa_ensrf_cycle_host (efa_stream.hip)
   else if (!strcmp(key, "stream_peak_bytes")) *value = c->st.peak_bytes;
   else if (!strcmp(key, "stream_h2d_us")) *value = c->st.h2d_us;
@@ -529,6 +530,12 @@ int efa_state_cycle_dev(efa_ctx* c, long rows, int M, const double* X_dev, doubl
                         const double* grid_lon, long ncol, long n_lead) {
   EFA_TRY(use(c));
   return state_cycle(c, rows, M, X_dev, post_dev, grid_lat, grid_lon, ncol, n_lead);
+}
+
+int efa_state_cycle_f32_dev(efa_ctx* c, long rows, int M, const float* X_dev, float* post_dev, const double* grid_lat,
+                            const double* grid_lon, long ncol, long n_lead) {
+  EFA_TRY(use(c));
+  return state_cycle_f32(c, rows, M, X_dev, post_dev, grid_lat, grid_lon, ncol, n_lead);
 }
 
 int efa_ensrf_update_dev(efa_ctx* c, long rows, int M, long P, double* xm_dev, double* Xp_dev, double* ym_dev,

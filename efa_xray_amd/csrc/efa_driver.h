@@ -56,7 +56,7 @@ inline const double* vl_obvert(const efa_ctx* c) { return c->vl_dev.as<double>()
 inline const double* vl_obvhw(const efa_ctx* c) { return c->vl_dev.as<double>() + c->vl_nlead + c->vl_P; }
 bool auto_transform(int M, long n_active, bool member_form);
 bool want_transform(const efa_ctx* c, bool member_form);
-int transform_with_relaxation(efa_ctx* c, efa::TransformArgs t, long* nl);
+int transform_with_relaxation(efa_ctx* c, efa::TransformArgs t, long* nl, bool f32 = false);
 efa::TransformArgs carried_transform(const efa_ctx* c, const double* Xin, const double* xin, double* Xout, double* xout, long rows,
                                      int fused_members);
 int read_gc_pairs(efa_ctx* c);
@@ -71,6 +71,9 @@ int state_phase(efa_ctx* c, long rows, int M, const double* xm_in, const double*
                 const double* grid_lat, const double* grid_lon, long ncol, long n_lead, const StateCall& o = StateCall{});
 int state_cycle(efa_ctx* c, long rows, int M, const double* X_dev, double* post_dev, const double* grid_lat,
                 const double* grid_lon, long ncol, long n_lead, const StateCall& o = StateCall{});
+// the member form on float32 rows: natively where a float32 kernel exists, through the float64 workspace otherwise (c->f32_native)
+int state_cycle_f32(efa_ctx* c, long rows, int M, const float* X_dev, float* post_dev, const double* grid_lat,
+                    const double* grid_lon, long ncol, long n_lead, const StateCall& o = StateCall{});
 // end of a state call: the launch count into the sum; "timing" 1 waits and reads the interval, 2 leaves it pending.
 // end_recorded: iv.end is in the stream already (a speculative transform that turned out right)
 int end_state_call(efa_ctx* c, Interval& iv, bool timed = true, bool end_recorded = false);

@@ -424,6 +424,7 @@ constexpr int kChunkL = EFA_GC_LANE_CHUNK;  // observations staged at a time by 
 // The kernels k_sweep_gc (quad form) and k_sweep_gc_lane (row-per-lane form), defined three times: as they are, with the
 // adaptive-inflation update fused in as k_sweep_gc_adapt / k_sweep_gc_lane_adapt, and with the vertical factor of
 // each (slab, ob) pair as k_sweep_gc_vloc / k_sweep_gc_lane_vloc
+#define EFA_GCK_ELEM double
 #define EFA_GCK_VLOC false
 #define EFA_GCK_ADAPT false
 #define EFA_GCK_QUAD k_sweep_gc
@@ -466,6 +467,26 @@ constexpr int gc_adapt_min_waves(int NC) { return (4 * NC * 2 + 100 <= 168) ? 3 
 #undef EFA_GCK_LANE_WAVES
 #undef EFA_GCK_QUAD_WAVES
 #undef EFA_GCK_VLOC
+#undef EFA_GCK_ELEM
+// the row-per-lane kernel on a state stored as float32: plain and with the vertical factor, member form
+#define EFA_GCK_LANE_ONLY 1
+#define EFA_GCK_ELEM float
+#define EFA_GCK_ADAPT false
+#define EFA_GCK_LANE_WAVES(MP) 2
+#define EFA_GCK_VLOC false
+#define EFA_GCK_LANE k_sweep_gc_lane_f32
+#include "efa_gcsweep_kernels.h"
+#undef EFA_GCK_LANE
+#undef EFA_GCK_VLOC
+#define EFA_GCK_VLOC true
+#define EFA_GCK_LANE k_sweep_gc_lane_vloc_f32
+#include "efa_gcsweep_kernels.h"
+#undef EFA_GCK_LANE
+#undef EFA_GCK_VLOC
+#undef EFA_GCK_ADAPT
+#undef EFA_GCK_LANE_WAVES
+#undef EFA_GCK_ELEM
+#undef EFA_GCK_LANE_ONLY
 
 
 // the kernel family of a launch: plain, adaptive inflation fused in, vertical factor
@@ -483,6 +504,15 @@ template <int MP, int FAM>
 hipError_t gc_lane_launch_one(const GcSweepArgs& a, hipStream_t s) {
   if (a.fused_members) gc_lane_launch_kernel<MP, true, FAM>(a, s);
   else gc_lane_launch_kernel<MP, false, FAM>(a, s);
+  return hipGetLastError();
+}
+
+// the row-per-lane kernels on a state stored as float32 (member form; plain and vertical factor)
+template <int MP, int FAM>
+hipError_t gc_lane_launch_f32(const GcSweepArgs& a, hipStream_t s) {
+  const dim3 grid((unsigned)(a.nblk * a.lead_split)), block(256);
+  if constexpr (FAM == kGcVloc) hipLaunchKernelGGL((k_sweep_gc_lane_vloc_f32<MP, true>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((k_sweep_gc_lane_f32<MP, true>), grid, block, 0, s, a);
   return hipGetLastError();
 }
 
@@ -594,6 +624,26 @@ hipError_t launch_sweep_gc(const GcSweepArgs& a0, hipStream_t s) {
       case kGcVloc: return gc_launch<nc, kGcVloc>(a, s);
       default: return gc_launch<nc, kGcPlain>(a, s);
     }
+  });
+}
+
+// ---- a state stored as float32: the row-per-lane kernel, member form --------------------------------------------
+// what the float64 launch asks of a cycle before it takes the row-per-lane kernel, less the 16-byte alignment of the rows
+// (float rows need 4)
+bool sweep_gc_lane_f32_supported(int M, long ye_stride, const double* Ye) {
+  return EFA_GC_LANE && M >= 2 && M <= kLaneMaxMembers && (M % 2 == 0) && (ye_stride % 2 == 0) && aligned16(Ye);
+}
+
+// a.Xin / a.Xout point at float rows (4-byte aligned)
+hipError_t launch_sweep_gc_lane_f32(const GcSweepArgs& a, hipStream_t s) {
+  if (!sweep_gc_lane_f32_supported(a.M, a.ye_stride, a.Ye) || !a.fused_members || a.infl) return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(a.Xin) & 3u) != 0 || (reinterpret_cast<uintptr_t>(a.Xout) & 3u) != 0) return hipErrorInvalidValue;
+  if (a.nblk <= 0 || a.n_lead <= 0) return hipSuccess;
+  GcSweepArgs l = a;
+  l.lead_split = (int)((l.n_lead + 15) / 16);
+  l.lead_chunk = 16;
+  return dispatch_width((l.M + 3) / 4, WidthRange<1, kLaneMaxMembers / 4>{}, [&](auto q) {
+    return l.lead_vert ? gc_lane_launch_f32<4 * q, kGcVloc>(l, s) : gc_lane_launch_f32<4 * q, kGcPlain>(l, s);
   });
 }
 

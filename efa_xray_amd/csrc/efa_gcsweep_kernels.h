@@ -2,7 +2,11 @@
 // they use): EFA_GCK_QUAD / EFA_GCK_LANE name them, EFA_GCK_ADAPT says whether the adaptive-inflation update (Anderson 2009,
 // DESIGN.md §7c) is fused in and EFA_GCK_VLOC whether the taper carries the vertical factor of each (slab, ob) pair (DESIGN.md
 // §7d).  Separate kernel names rather than a template flag keep the plain kernels' names and code as they were.
+// EFA_GCK_ELEM is the element type of the state rows in memory as the row-per-lane kernel sees them: double, or float for a state
+// stored as float32 (member form only, included with EFA_GCK_LANE_ONLY: the quad kernel has no float32 form).
 // No include guard: this file is meant to be included more than once.
+
+#ifndef EFA_GCK_LANE_ONLY
 
 template <int NC, bool VEC, bool FUSED, int RPL>
 __global__ __launch_bounds__(256, EFA_GCK_QUAD_WAVES(NC, RPL)) void EFA_GCK_QUAD(const GcSweepArgs a) {
@@ -170,8 +174,14 @@ __global__ __launch_bounds__(256, EFA_GCK_QUAD_WAVES(NC, RPL)) void EFA_GCK_QUAD
   }
 }
 
+#endif  // EFA_GCK_LANE_ONLY
+
+// EFA_GCK_ELEM float: a lane still owns a whole row, loads it with the widest loads its alignment allows (16 bytes when M % 4 == 0
+// and the base is 16-byte aligned, else 8 bytes, else 4) widened as they arrive, and rounds each posterior member once at its store; everything between is the float64
+// arithmetic of the double kernel, in its order.
 template <int MP, bool FUSED>  // members padded to a multiple of 4; FUSED: prior members in, posterior members out
 __global__ __launch_bounds__(256, EFA_GCK_LANE_WAVES(MP)) void EFA_GCK_LANE(const GcSweepArgs a) {
+  typedef EFA_GCK_ELEM E;
   constexpr bool ADAPT = EFA_GCK_ADAPT;
   constexpr bool VLOC = EFA_GCK_VLOC;
   static_assert(!(ADAPT && VLOC), "adaptive inflation with vertical localisation is not built");
@@ -213,7 +223,29 @@ __global__ __launch_bounds__(256, EFA_GCK_LANE_WAVES(MP)) void EFA_GCK_LANE(cons
     double x[MP];
     double xm = 0.0;
     double lam = 1.0, sd = 0.0, ss = 0.0;  // ADAPT: the row's inflation and x'.x'
-    if (live) {
+    if (live && sizeof(E) != sizeof(double)) {
+      const float* pf = reinterpret_cast<const float*>(a.Xin) + (size_t)row * M;
+      if (M == MP && (reinterpret_cast<uintptr_t>(pf) & 15u) == 0) {  // M % 4 == 0 and a 16-byte aligned base: 16-byte loads
+#pragma unroll
+        for (int i = 0; i < MP / 4; ++i) {
+          const float4 v = reinterpret_cast<const float4*>(pf)[i];
+          x[4 * i] = v.x;
+          x[4 * i + 1] = v.y;
+          x[4 * i + 2] = v.z;
+          x[4 * i + 3] = v.w;
+        }
+      } else if ((reinterpret_cast<uintptr_t>(pf) & 7u) == 0) {  // (M is even: uniform over the launch)
+#pragma unroll
+        for (int i = 0; i < MP / 2; ++i) {
+          const float2 v = (i < M2) ? reinterpret_cast<const float2*>(pf)[i] : make_float2(0.f, 0.f);
+          x[2 * i] = v.x;
+          x[2 * i + 1] = v.y;
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < MP; ++i) x[i] = (i < M) ? (double)pf[i] : 0.0;
+      }
+    } else if (live) {
       const double2* p = reinterpret_cast<const double2*>(a.Xin + (size_t)row * M);
       if (M == MP) {
 #pragma unroll
@@ -230,6 +262,8 @@ __global__ __launch_bounds__(256, EFA_GCK_LANE_WAVES(MP)) void EFA_GCK_LANE(cons
           x[2 * i + 1] = v.y;
         }
       }
+    }
+    if (live) {
       if (FUSED) {  // prior members in: remove the ensemble mean (assimilation.py:146-147)
         double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
 #pragma unroll
@@ -346,7 +380,23 @@ __global__ __launch_bounds__(256, EFA_GCK_LANE_WAVES(MP)) void EFA_GCK_LANE(cons
         ab = abn;
       }
     }
-    if (live) {  // posterior members out (assimilation.py:168), or perturbations and mean
+    if (live && sizeof(E) != sizeof(double)) {  // posterior members out, each rounded to float32 once
+      float* pf = reinterpret_cast<float*>(a.Xout) + (size_t)row * M;
+      if (M == MP && (reinterpret_cast<uintptr_t>(pf) & 15u) == 0) {
+#pragma unroll
+        for (int i = 0; i < MP / 4; ++i)
+          reinterpret_cast<float4*>(pf)[i] = make_float4((float)(x[4 * i] + xm), (float)(x[4 * i + 1] + xm), (float)(x[4 * i + 2] + xm),
+                                                         (float)(x[4 * i + 3] + xm));
+      } else if ((reinterpret_cast<uintptr_t>(pf) & 7u) == 0) {
+#pragma unroll
+        for (int i = 0; i < MP / 2; ++i)
+          if (i < M2) reinterpret_cast<float2*>(pf)[i] = make_float2((float)(x[2 * i] + xm), (float)(x[2 * i + 1] + xm));
+      } else {
+#pragma unroll
+        for (int i = 0; i < MP; ++i)
+          if (i < M) pf[i] = (float)(x[i] + xm);
+      }
+    } else if (live) {  // posterior members out (assimilation.py:168), or perturbations and mean
       double2* p = reinterpret_cast<double2*>(a.Xout + (size_t)row * M);
       const double add = FUSED ? xm : 0.0;
       if (M == MP) {

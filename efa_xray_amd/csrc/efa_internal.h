@@ -190,6 +190,10 @@ hipError_t launch_gc_count(long ncol, long P, const double* glat, const double* 
                            int* cnt, int* blk_pairs /* [nblk] (column, ob) pairs of each block, or null */,
                            unsigned long long* npairs, hipStream_t s);
 hipError_t launch_sweep_gc(const GcSweepArgs& a, hipStream_t s);
+// the row-per-lane kernel on a state stored as float32 (member form, a.Xin / a.Xout point at float rows): the cycles
+// it serves (even M up to 104), whatever the alignment of the rows
+bool sweep_gc_lane_f32_supported(int M, long ye_stride, const double* Ye);
+hipError_t launch_sweep_gc_lane_f32(const GcSweepArgs& a, hipStream_t s);
 
 struct TransformArgs {
   const double* Xin;  // [rows][M] perturbations, or full members when fused_members
@@ -215,6 +219,12 @@ hipError_t launch_transform_rtps(const TransformArgs& a, double alpha, hipStream
 bool transform_rtps_supported(int M);
 // posterior relaxation (efa_relax.hip): Tout = (1-alpha) T + alpha I; per-row sum of squared deviations; in-place relaxation of
 // rows (rtpp 0: RTPS from ss, 1: RTPP against the prior rows)
+// the member-form transforms on rows stored as float32 (efa_transform_f32.hip): Xin / Xout point at float rows
+hipError_t launch_transform_f32(const TransformArgs& a, hipStream_t s);
+hipError_t launch_transform_rtps_f32(const TransformArgs& a, double alpha, hipStream_t s);
+// float32 rows <-> the float64 workspace (efa_misc.hip): an exact widening copy, and posterior members rounded once
+hipError_t launch_widen_f32(size_t n, const float* X, double* out, hipStream_t s);
+hipError_t launch_narrow_f32(size_t n, const double* X, float* out, hipStream_t s);
 hipError_t launch_relax_fold(int M, double alpha, const double* T, double* Tout, hipStream_t s);
 hipError_t launch_row_spread(long rows, int M, const double* X, double* ss, hipStream_t s);
 hipError_t launch_relax_rows(long rows, int M, int rtpp, double alpha, double* X, const double* ss, const double* prior,

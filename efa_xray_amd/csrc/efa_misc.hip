@@ -51,6 +51,17 @@ __global__ __launch_bounds__(kThreads) void k_posterior(long rows, int M, const 
   }
 }
 
+// A state stored as float32 through the float64 kernels: the exact widening copy into the workspace, and the
+// posterior members out of it, each rounded to nearest even once.  Flat, one element per lane and step.
+__global__ __launch_bounds__(kThreads) void k_widen_f32(size_t n, const float* __restrict__ X, double* __restrict__ out) {
+  const size_t stride = (size_t)gridDim.x * kThreads;
+  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) out[i] = (double)X[i];
+}
+__global__ __launch_bounds__(kThreads) void k_narrow_f32(size_t n, const double* __restrict__ X, float* __restrict__ out) {
+  const size_t stride = (size_t)gridDim.x * kThreads;
+  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) out[i] = (float)X[i];
+}
+
 // W[k][col] = GC(distance_to_point(grid[col], ob_k) / halfwidth_k)
 // (observation.py:59-87 on an EnsembleState; the caller broadcasts it over
 // var x time, ensrf.py:108-111 -- here by indexing col = row % ncol).
@@ -149,6 +160,18 @@ hipError_t launch_posterior(long rows, int M, const double* xm, const double* Xp
   if (rows <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_posterior, dim3(grid_for((size_t)rows * M, kThreads)), dim3(kThreads), 0, s, rows, M,
                      xm, Xp, post);
+  return hipGetLastError();
+}
+
+hipError_t launch_widen_f32(size_t n, const float* X, double* out, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_widen_f32, dim3(grid_for(n, kThreads)), dim3(kThreads), 0, s, n, X, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_narrow_f32(size_t n, const double* X, float* out, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_narrow_f32, dim3(grid_for(n, kThreads)), dim3(kThreads), 0, s, n, X, out);
   return hipGetLastError();
 }
 

@@ -57,7 +57,8 @@ int with_relaxation(efa_ctx* c, long rows, int M, const double* Xin, double* Xou
 // The state transform through [T | w] (member or perturbation form, t.fused_members) with the relaxation: RTPP folded into T
 // (Xb' ((1-alpha) T + alpha I); xam as without it), RTPS fused into the member-form transform up to 136 members, the standalone
 // passes otherwise.  *nl = the launches it took.
-int transform_with_relaxation(efa_ctx* c, TransformArgs t, long* nl) {
+// f32: t.Xin / t.Xout point at float32 member rows (member form; the caller has made sure that no standalone pass is needed)
+int transform_with_relaxation(efa_ctx* c, TransformArgs t, long* nl, bool f32) {
   hipStream_t s = c->stream;
   const bool relax = relax_on(c);
   *nl = 1;
@@ -67,15 +68,16 @@ int transform_with_relaxation(efa_ctx* c, TransformArgs t, long* nl) {
     t.T = c->relax_T.as<double>();
     *nl = 2;
   } else if (relax && t.fused_members && transform_rtps_supported(t.M)) {
-    EFA_HIP(launch_transform_rtps(t, c->relax_alpha, s));
+    EFA_HIP(f32 ? launch_transform_rtps_f32(t, c->relax_alpha, s) : launch_transform_rtps(t, c->relax_alpha, s));
     return EFA_OK;
   } else if (relax) {
+    if (f32) return fail(EFA_ERR_INVALID, "the standalone relaxation passes have no float32 form");
     return with_relaxation(c, t.nrows, t.M, t.Xin, t.Xout, nl, [&]() -> int {
       EFA_HIP(launch_transform(t, s));
       return EFA_OK;
     });
   }
-  EFA_HIP(launch_transform(t, s));
+  EFA_HIP(f32 ? launch_transform_f32(t, s) : launch_transform(t, s));
   return EFA_OK;
 }
 // [T | w] as Phase A left them: the carried identity rows behind the P obs rows of the working block
@@ -202,8 +204,9 @@ int read_gc_pairs(efa_ctx* c) {
 
 namespace {
 // ---- Phase B, localised, one pass (efa_gcsweep.hip) --------------------------------------
+// f32: Xp_in / Xp_out point at float32 member rows (member form, the row-per-lane kernel)
 int state_gc_onepass(efa_ctx* c, const double* xm_in, const double* Xp_in, double* xm_out, double* Xp_out, long ncol, long n_lead,
-                     int fused_members) {
+                     int fused_members, bool f32 = false) {
   const int M = c->M;
   const long P = c->P;
   hipStream_t s = c->stream;
@@ -279,7 +282,7 @@ int state_gc_onepass(efa_ctx* c, const double* xm_in, const double* Xp_in, doubl
     g.ob_vert = vl_obvert(c);
     g.ob_vhw = vl_obvhw(c);
   }
-  EFA_HIP(launch_sweep_gc(g, s));
+  EFA_HIP(f32 ? launch_sweep_gc_lane_f32(g, s) : launch_sweep_gc(g, s));
   c->state_launches++;
   return EFA_OK;
 }
@@ -385,11 +388,9 @@ int state_phase(efa_ctx* c, long rows, int M, const double* xm_in, const double*
   return end_state_call(c, c->state_iv[0], o.timed);
 }
 
-// member form (efa_state_cycle_dev)
-int state_cycle(efa_ctx* c, long rows, int M, const double* X_dev, double* post_dev, const double* grid_lat,
-                const double* grid_lon, long ncol, long n_lead, const StateCall& o) {
-  EFA_TRY(begin_state_call(c, "efa_state_cycle_dev", rows, M, X_dev && post_dev, grid_lat, grid_lon, ncol, n_lead, o));
-  if (rows == 0) return EFA_OK;
+namespace {
+// the member form's launches, from prior members X_dev to posterior members post_dev
+int state_cycle_core(efa_ctx* c, long rows, int M, const double* X_dev, double* post_dev, long ncol, long n_lead) {
   hipStream_t s = c->stream;
   if (c->P > 0 && c->n_active > 0 && want_transform(c, true)) {
     EFA_TRY(transform_with_relaxation(c, carried_transform(c, X_dev, nullptr, post_dev, nullptr, rows, 1), &c->state_launches));
@@ -407,6 +408,65 @@ int state_cycle(efa_ctx* c, long rows, int M, const double* X_dev, double* post_
       EFA_HIP(launch_posterior(rows, M, xm, post_dev, post_dev, s));
       return EFA_OK;
     }));
+  }
+  return EFA_OK;
+}
+}  // namespace
+
+// member form (efa_state_cycle_dev)
+int state_cycle(efa_ctx* c, long rows, int M, const double* X_dev, double* post_dev, const double* grid_lat,
+                const double* grid_lon, long ncol, long n_lead, const StateCall& o) {
+  EFA_TRY(begin_state_call(c, "efa_state_cycle_dev", rows, M, X_dev && post_dev, grid_lat, grid_lon, ncol, n_lead, o));
+  if (rows == 0) return EFA_OK;
+  EFA_TRY(state_cycle_core(c, rows, M, X_dev, post_dev, ncol, n_lead));
+  return end_state_call(c, c->state_iv[0], o.timed);
+}
+
+// member form on a state stored as float32 (efa_state_cycle_f32_dev): posterior = fl32(F(widen(prior))), F the
+// float64 member form above.  The transform (plain, RTPP folded, RTPS fused) and the row-per-lane one-pass GC sweep read and write
+// the float rows themselves; every other route widens the rows into a float64 workspace, runs the float64 launches on it as they
+// are and rounds the posterior members once on the way out.
+int state_cycle_f32(efa_ctx* c, long rows, int M, const float* X_dev, float* post_dev, const double* grid_lat,
+                    const double* grid_lon, long ncol, long n_lead, const StateCall& o) {
+  if (c->ai_field)
+    return fail(EFA_ERR_INVALID, "efa_state_cycle_f32_dev: an adaptive-inflation field is set (its update is float64 only)");
+  if (((reinterpret_cast<uintptr_t>(X_dev) | reinterpret_cast<uintptr_t>(post_dev)) & 3u) != 0)
+    return fail(EFA_ERR_INVALID, "efa_state_cycle_f32_dev: state pointers must be 4-byte aligned");
+  EFA_TRY(begin_state_call(c, "efa_state_cycle_f32_dev", rows, M, X_dev && post_dev, grid_lat, grid_lon, ncol, n_lead, o));
+  if (rows == 0) return EFA_OK;
+  hipStream_t s = c->stream;
+  const size_t n = (size_t)rows * M;
+  const bool relax = relax_on(c);
+  const bool transform = c->P > 0 && c->n_active > 0 && want_transform(c, true);
+  const bool wide = M > 136;  // the column groups of k_transform_wide re-read rows that other groups write: never in place
+  const char *a = reinterpret_cast<const char*>(X_dev), *b = reinterpret_cast<const char*>(post_dev);
+  const bool disjoint = a + n * sizeof(float) <= b || b + n * sizeof(float) <= a;
+  // as the float64 shell passes them: the kernels take the element type from the launch, not from the pointer
+  const double* Xd = reinterpret_cast<const double*>(X_dev);
+  double* Pd = reinterpret_cast<double*>(post_dev);
+  c->f32_native = 0;
+  if (transform && (!relax || c->relax_kind == EFA_RELAX_RTPP || transform_rtps_supported(M))) {
+    if (wide && !disjoint) {
+      EFA_TRY(c->f32_prior.reserve(n * sizeof(float)));
+      EFA_HIP(hipMemcpyAsync(c->f32_prior.p, X_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+      Xd = c->f32_prior.as<double>();
+    }
+    EFA_TRY(transform_with_relaxation(c, carried_transform(c, Xd, nullptr, Pd, nullptr, rows, 1), &c->state_launches, true));
+    c->path_taken = EFA_PATH_TRANSFORM;
+    c->f32_native = 1;
+  } else if (!transform && !relax && c->loc_mode == EFA_LOC_GC && c->gc_onepass && c->n_active > 0 &&
+             sweep_gc_lane_f32_supported(M, c->ye_stride, c->ye_ptr)) {
+    EFA_TRY(state_gc_onepass(c, nullptr, Xd, nullptr, Pd, ncol, n_lead, 1, true));
+    c->f32_native = 1;
+  } else {
+    const bool two = transform && wide;
+    EFA_TRY(c->f32_ws.reserve((two ? 2 : 1) * n * sizeof(double)));
+    double* ws = c->f32_ws.as<double>();
+    double* out = two ? ws + n : ws;
+    EFA_HIP(launch_widen_f32(n, X_dev, ws, s));
+    EFA_TRY(state_cycle_core(c, rows, M, ws, out, ncol, n_lead));
+    EFA_HIP(launch_narrow_f32(n, out, post_dev, s));
+    c->state_launches += 2;
   }
   return end_state_call(c, c->state_iv[0], o.timed);
 }

@@ -1,4 +1,4 @@
-// The streamed host-memory update (include/efa_hip.h: efa_ensrf_cycle_host, efa_pinned_alloc / efa_pinned_free): the prior stays in
+// The streamed host-memory update (include/efa_hip.h: efa_ensrf_cycle_host, efa_ensrf_cycle_host_f32, efa_pinned_alloc / efa_pinned_free): the prior stays in
 // host memory and crosses the device in chunks of (y, x) columns.  Upload of chunk i+1, state phase of chunk i and download of
 // chunk i-1 overlap on three streams; Phase A runs on the context's stream while the first chunks upload.  No kernel lives here:
 // a chunk is a column shard (row lead*(hi-lo) + (col-lo)), so the obs phase and the member-form state call serve it as they are.
@@ -23,25 +23,27 @@ const PinnedBlock* find_block(const StreamState& st, const void* p, size_t bytes
   return nullptr;
 }
 
-// One call: the segments as they lie in host memory, the chunk plan and the ring.
+// One call: the segments as they lie in host memory, the chunk plan and the ring.  esz: bytes per stored state element, 8
+// (efa_ensrf_cycle_host) or 4 (efa_ensrf_cycle_host_f32): the images, the ring, the copies and their pitches are in these elements.
 struct Call {
   int n_seg = 0, M = 0;
-  const double* const* in = nullptr;
-  double* const* out = nullptr;
+  size_t esz = sizeof(double);
+  const void* const* in = nullptr;
+  void* const* out = nullptr;
   const long* slabs = nullptr;
   long ncol = 0, n_lead = 0, cc = 0, nchunk = 0;  // columns, slabs of all segments, columns of a full chunk, chunks
   bool in_pinned = false, out_pinned = false;
   size_t slot_bytes = 0;  // one ring buffer: a full chunk
   long lo(long i) const { return i * cc; }
   long hi(long i) const { return std::min(ncol, (i + 1) * cc); }
-  size_t chunk_bytes(long i) const { return (size_t)n_lead * (size_t)(hi(i) - lo(i)) * M * sizeof(double); }
+  size_t chunk_bytes(long i) const { return (size_t)n_lead * (size_t)(hi(i) - lo(i)) * M * esz; }
 };
 
 // Bytes [b0, b1) of chunk i's device image <-> the caller's segments (to_stage: host segments -> image, else image -> segments).
-// The image is slab after slab, each (hi-lo)*M doubles; slab `lead` of the image is slab lead - lead0(v) of its segment v.
+// The image is slab after slab, each (hi-lo)*M elements; slab `lead` of the image is slab lead - lead0(v) of its segment v.
 void copy_image_range(const Call& k, long i, char* image, size_t b0, size_t b1, bool to_stage) {
-  const size_t slab_b = (size_t)(k.hi(i) - k.lo(i)) * k.M * sizeof(double);
-  const size_t pitch_b = (size_t)k.ncol * k.M * sizeof(double), off_b = (size_t)k.lo(i) * k.M * sizeof(double);
+  const size_t slab_b = (size_t)(k.hi(i) - k.lo(i)) * k.M * k.esz;
+  const size_t pitch_b = (size_t)k.ncol * k.M * k.esz, off_b = (size_t)k.lo(i) * k.M * k.esz;
   long lead0 = 0;
   for (int v = 0; v < k.n_seg; ++v) {
     for (long s = 0; s < k.slabs[v]; ++s) {
@@ -76,8 +78,8 @@ void copy_image(const Call& k, long i, char* image, bool to_stage) {
 // chunk i between a pinned caller segment and its ring buffer, by DMA: one strided copy per segment
 int copy_segments_dma(const Call& k, long i, char* dev, bool up, hipStream_t s) {
   const long cw = k.hi(i) - k.lo(i);
-  const size_t slab_b = (size_t)cw * k.M * sizeof(double), pitch_b = (size_t)k.ncol * k.M * sizeof(double);
-  const size_t off_b = (size_t)k.lo(i) * k.M * sizeof(double);
+  const size_t slab_b = (size_t)cw * k.M * k.esz, pitch_b = (size_t)k.ncol * k.M * k.esz;
+  const size_t off_b = (size_t)k.lo(i) * k.M * k.esz;
   long lead0 = 0;
   for (int v = 0; v < k.n_seg; ++v) {
     char* d = dev + (size_t)lead0 * slab_b;
@@ -161,13 +163,17 @@ int issue_state_phase(const Pipe& p, long i, int loc_mode, const double* grid_la
     EFA_TRY(c->grid.take_slice(s, c->st.grid.as<double>(), k.ncol, k.lo(i), cw));
   }
   EFA_HIP(hipEventRecord(p.ev(i, kSt0), s));
+  const bool f32 = k.esz == sizeof(float);
   double* X = reinterpret_cast<double*>(p.slot(i));
+  float* X32 = reinterpret_cast<float*>(p.slot(i));
   // the chunk loop keeps its own events: the context's per-call timing would make every state phase wait for its end
   StateCall sc;
   sc.grid_current = true;
   sc.timed = false;
-  if (loc_mode == EFA_LOC_GC) EFA_TRY(state_cycle(c, rows, k.M, X, X, grid_lat + k.lo(i), grid_lon + k.lo(i), cw, k.n_lead, sc));
-  else EFA_TRY(state_cycle(c, rows, k.M, X, X, nullptr, nullptr, rows, 1, sc));
+  const double *glat = loc_mode == EFA_LOC_GC ? grid_lat + k.lo(i) : nullptr, *glon = loc_mode == EFA_LOC_GC ? grid_lon + k.lo(i) : nullptr;
+  const long ncol = loc_mode == EFA_LOC_GC ? cw : rows, n_lead = loc_mode == EFA_LOC_GC ? k.n_lead : 1;
+  if (f32) EFA_TRY(state_cycle_f32(c, rows, k.M, X32, X32, glat, glon, ncol, n_lead, sc));
+  else EFA_TRY(state_cycle(c, rows, k.M, X, X, glat, glon, ncol, n_lead, sc));
   *launches += c->state_launches;
   EFA_HIP(hipEventRecord(p.ev(i, kSt1), s));
   return EFA_OK;
@@ -255,66 +261,40 @@ int run_pipeline(Pipe& p, long P, const double* HX, const double* ob_value, cons
   return EFA_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int efa_pinned_alloc(efa_ctx* c, size_t bytes, void** host_out) {
-  EFA_TRY(use(c));
-  if (!host_out) return fail(EFA_ERR_INVALID, "null out pointer");
-  *host_out = nullptr;
-  void* p = nullptr;
-  const size_t want = bytes ? bytes : 8;
-  EFA_HIP(hipHostMalloc(&p, want, hipHostMallocDefault));
-  c->st.blocks.push_back(PinnedBlock{p, want});
-  *host_out = p;
-  return EFA_OK;
-}
-
-int efa_pinned_free(efa_ctx* c, void* host) {
-  EFA_TRY(use(c));
-  if (!host) return EFA_OK;
-  std::vector<PinnedBlock>& b = c->st.blocks;
-  for (size_t i = 0; i < b.size(); ++i) {
-    if (b[i].p != host) continue;
-    b.erase(b.begin() + (long)i);
-    EFA_HIP(hipHostFree(host));
-    return EFA_OK;
-  }
-  return fail(EFA_ERR_INVALID, "efa_pinned_free: %p is not a block of efa_pinned_alloc on this context", host);
-}
-
-int efa_ensrf_cycle_host(efa_ctx* c, int n_seg, const double* const* seg_prior, double* const* seg_post, const long* seg_slabs,
-                         long ncol, int M, long P, const double* HX, long chunk_cols, const double* ob_value,
-                         const double* ob_error, const uint8_t* ob_assim, int loc_mode, const double* ob_lat, const double* ob_lon,
-                         const double* ob_halfwidth_km, const double* grid_lat, const double* grid_lon, double* prior_mean,
-                         double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated) {
+// efa_ensrf_cycle_host and efa_ensrf_cycle_host_f32: the state segments hold elements of esz bytes
+int cycle_host(efa_ctx* c, size_t esz, int n_seg, const void* const* seg_prior, void* const* seg_post, const long* seg_slabs,
+               long ncol, int M, long P, const double* HX, long chunk_cols, const double* ob_value, const double* ob_error,
+               const uint8_t* ob_assim, int loc_mode, const double* ob_lat, const double* ob_lon, const double* ob_halfwidth_km,
+               const double* grid_lat, const double* grid_lon, double* prior_mean, double* prior_var, double* post_mean,
+               double* post_var, uint8_t* assimilated) {
+  const char* who = esz == sizeof(float) ? "efa_ensrf_cycle_host_f32" : "efa_ensrf_cycle_host";
   EFA_TRY(use(c));
   const auto t0 = std::chrono::steady_clock::now();
   if (c->ai_field)
-    return fail(EFA_ERR_INVALID, "efa_ensrf_cycle_host: an adaptive-inflation field is set (its update needs the whole state resident)");
-  if (n_seg < 0 || ncol < 0 || P < 0) return fail(EFA_ERR_INVALID, "efa_ensrf_cycle_host: negative n_seg, ncol or P");
+    return fail(EFA_ERR_INVALID, "%s: an adaptive-inflation field is set (its update needs the whole state resident)", who);
+  if (n_seg < 0 || ncol < 0 || P < 0) return fail(EFA_ERR_INVALID, "%s: negative n_seg, ncol or P", who);
   if (M < 2) return fail(EFA_ERR_INVALID, "ensemble size M=%d must be >= 2 (covariance divides by M-1)", M);
-  if (chunk_cols < 1) return fail(EFA_ERR_INVALID, "efa_ensrf_cycle_host: chunk_cols=%ld must be >= 1", chunk_cols);
+  if (chunk_cols < 1) return fail(EFA_ERR_INVALID, "%s: chunk_cols=%ld must be >= 1", who, chunk_cols);
   if (loc_mode != EFA_LOC_NONE && loc_mode != EFA_LOC_GC) return fail(EFA_ERR_INVALID, "loc_mode %d", loc_mode);
-  if (n_seg && (!seg_prior || !seg_post || !seg_slabs)) return fail(EFA_ERR_INVALID, "efa_ensrf_cycle_host: null segment table");
-  if (P && !HX) return fail(EFA_ERR_INVALID, "efa_ensrf_cycle_host: null HX");
+  if (n_seg && (!seg_prior || !seg_post || !seg_slabs)) return fail(EFA_ERR_INVALID, "%s: null segment table", who);
+  if (P && !HX) return fail(EFA_ERR_INVALID, "%s: null HX", who);
   Pipe p{};
   p.c = c;
   Call& k = p.k;
   k.n_seg = n_seg;
   k.M = M;
+  k.esz = esz;
   k.in = seg_prior;
   k.out = seg_post;
   k.slabs = seg_slabs;
   k.ncol = ncol;
-  const size_t col_b = (size_t)M * sizeof(double);
+  const size_t col_b = (size_t)M * esz;
   k.in_pinned = k.out_pinned = true;
   for (int v = 0; v < n_seg; ++v) {
-    if (seg_slabs[v] < 0) return fail(EFA_ERR_INVALID, "efa_ensrf_cycle_host: segment %d has %ld slabs", v, seg_slabs[v]);
+    if (seg_slabs[v] < 0) return fail(EFA_ERR_INVALID, "%s: segment %d has %ld slabs", who, v, seg_slabs[v]);
     k.n_lead += seg_slabs[v];
     if (seg_slabs[v] == 0 || ncol == 0) continue;
-    if (!seg_prior[v] || !seg_post[v]) return fail(EFA_ERR_INVALID, "efa_ensrf_cycle_host: segment %d is null", v);
+    if (!seg_prior[v] || !seg_post[v]) return fail(EFA_ERR_INVALID, "%s: segment %d is null", who, v);
     const size_t seg_b = (size_t)seg_slabs[v] * ncol * col_b;
     k.in_pinned = k.in_pinned && find_block(c->st, seg_prior[v], seg_b);
     k.out_pinned = k.out_pinned && find_block(c->st, seg_post[v], seg_b);
@@ -329,10 +309,10 @@ int efa_ensrf_cycle_host(efa_ctx* c, int n_seg, const double* const* seg_prior, 
       if (!ub) continue;
       const char* a = reinterpret_cast<const char*>(seg_prior[u]);
       if (!(a + ub <= b || b + bb <= a))
-        return fail(EFA_ERR_INVALID, "efa_ensrf_cycle_host: posterior segment %d overlaps prior segment %d (the prior is never written)", v, u);
+        return fail(EFA_ERR_INVALID, "%s: posterior segment %d overlaps prior segment %d (the prior is never written)", who, v, u);
       const char* o = reinterpret_cast<const char*>(seg_post[u]);
       if (u != v && !(o + ub <= b || b + bb <= o))
-        return fail(EFA_ERR_INVALID, "efa_ensrf_cycle_host: posterior segments %d and %d overlap", v, u);
+        return fail(EFA_ERR_INVALID, "%s: posterior segments %d and %d overlap", who, v, u);
     }
   }
   if (loc_mode == EFA_LOC_GC && k.n_lead * ncol > 0 && (!grid_lat || !grid_lon))
@@ -386,6 +366,55 @@ int efa_ensrf_cycle_host(efa_ctx* c, int n_seg, const double* const* seg_prior, 
   }
   st.wall_us = (long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
   return EFA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int efa_pinned_alloc(efa_ctx* c, size_t bytes, void** host_out) {
+  EFA_TRY(use(c));
+  if (!host_out) return fail(EFA_ERR_INVALID, "null out pointer");
+  *host_out = nullptr;
+  void* p = nullptr;
+  const size_t want = bytes ? bytes : 8;
+  EFA_HIP(hipHostMalloc(&p, want, hipHostMallocDefault));
+  c->st.blocks.push_back(PinnedBlock{p, want});
+  *host_out = p;
+  return EFA_OK;
+}
+
+int efa_pinned_free(efa_ctx* c, void* host) {
+  EFA_TRY(use(c));
+  if (!host) return EFA_OK;
+  std::vector<PinnedBlock>& b = c->st.blocks;
+  for (size_t i = 0; i < b.size(); ++i) {
+    if (b[i].p != host) continue;
+    b.erase(b.begin() + (long)i);
+    EFA_HIP(hipHostFree(host));
+    return EFA_OK;
+  }
+  return fail(EFA_ERR_INVALID, "efa_pinned_free: %p is not a block of efa_pinned_alloc on this context", host);
+}
+
+int efa_ensrf_cycle_host(efa_ctx* c, int n_seg, const double* const* seg_prior, double* const* seg_post, const long* seg_slabs,
+                         long ncol, int M, long P, const double* HX, long chunk_cols, const double* ob_value,
+                         const double* ob_error, const uint8_t* ob_assim, int loc_mode, const double* ob_lat, const double* ob_lon,
+                         const double* ob_halfwidth_km, const double* grid_lat, const double* grid_lon, double* prior_mean,
+                         double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated) {
+  return cycle_host(c, sizeof(double), n_seg, reinterpret_cast<const void* const*>(seg_prior), reinterpret_cast<void* const*>(seg_post),
+                    seg_slabs, ncol, M, P, HX, chunk_cols, ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon, ob_halfwidth_km,
+                    grid_lat, grid_lon, prior_mean, prior_var, post_mean, post_var, assimilated);
+}
+
+int efa_ensrf_cycle_host_f32(efa_ctx* c, int n_seg, const float* const* seg_prior, float* const* seg_post, const long* seg_slabs,
+                             long ncol, int M, long P, const double* HX, long chunk_cols, const double* ob_value,
+                             const double* ob_error, const uint8_t* ob_assim, int loc_mode, const double* ob_lat,
+                             const double* ob_lon, const double* ob_halfwidth_km, const double* grid_lat, const double* grid_lon,
+                             double* prior_mean, double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated) {
+  return cycle_host(c, sizeof(float), n_seg, reinterpret_cast<const void* const*>(seg_prior), reinterpret_cast<void* const*>(seg_post),
+                    seg_slabs, ncol, M, P, HX, chunk_cols, ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon, ob_halfwidth_km,
+                    grid_lat, grid_lon, prior_mean, prior_var, post_mean, post_var, assimilated);
 }
 
 }  // extern "C"

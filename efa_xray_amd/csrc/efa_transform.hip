@@ -64,10 +64,19 @@ struct TShape {
 // (M = 100: 25 steps instead of 26).
 // AL: rows are 16-byte aligned (M even and an aligned base): 16-byte loads.  Otherwise (odd M) the two
 // members of a pair are loaded separately -- half the load width, the price of an odd ensemble size only.
-template <int NU, bool HALF, bool AL>
+// E: the element type of the rows in memory.  double as above; float (efa_transform_f32.hip) for a state stored as float32: the
+// same lanes take the same members, an AL pair with one 8-byte load (M even and an 8-byte aligned base), and every value is
+// widened -- exactly -- as it arrives, so everything downstream is the float64 arithmetic unchanged.
+template <typename E>
+struct Pair;
+template <>
+struct Pair<double> { typedef double2 type; };
+template <>
+struct Pair<float> { typedef float2 type; };
+template <int NU, bool HALF, bool AL, typename E = double>
 __device__ __forceinline__ void load_tile(const double* __restrict__ X, long row_clamped, int M, int g,
                                           double (&a)[2 * NU]) {
-  const double* p = X + (size_t)row_clamped * M;
+  const E* p = reinterpret_cast<const E*>(X) + (size_t)row_clamped * M;
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
     if (HALF && u == NU - 1) {
@@ -77,7 +86,7 @@ __device__ __forceinline__ void load_tile(const double* __restrict__ X, long row
     } else if (AL) {
       int m0 = 8 * u + 2 * g;
       if (u == NU - 1) m0 = (m0 < M) ? m0 : M - 2;  // last chunk may be partial: clamp the address
-      const double2 v = *reinterpret_cast<const double2*>(p + m0);
+      const typename Pair<E>::type v = *reinterpret_cast<const typename Pair<E>::type*>(p + m0);
       a[2 * u] = v.x;
       a[2 * u + 1] = v.y;
     } else {
@@ -88,9 +97,10 @@ __device__ __forceinline__ void load_tile(const double* __restrict__ X, long row
   }
 }
 
-template <int NU, bool FUSED, bool HALF, bool AL>
+template <int NU, bool FUSED, bool HALF, bool AL, typename E = double>
 __global__ __launch_bounds__(kThreadsT) void k_transform(const TransformArgs p) {
   using Sh = TShape<NU, FUSED, HALF>;
+  E* const Xout = reinterpret_cast<E*>(p.Xout);  // E float: each posterior value is rounded once, at its store
   constexpr int NT = Sh::NT;
   constexpr bool NARROW = Sh::NARROW;
   extern __shared__ __align__(16) double Bs[];  // [(u*2+h)*NT + t][64], then the narrow tile's [(u*2+h)][64]
@@ -139,7 +149,7 @@ __global__ __launch_bounds__(kThreadsT) void k_transform(const TransformArgs p) 
   long tile = wave;
   if (tile < ntiles) {
     const long r = tile * 16 + n;
-    load_tile<NU, HALF, AL>(p.Xin, r < last_row ? r : last_row, M, g, a);
+    load_tile<NU, HALF, AL, E>(p.Xin, r < last_row ? r : last_row, M, g, a);
   }
   if (kPrefetchT) {  // the first tile has arrived before the loop is entered: its header then needs no vmcnt wait, which on
 #pragma unroll      // the back edge would also wait for the previous tile's stores
@@ -159,7 +169,7 @@ __global__ __launch_bounds__(kThreadsT) void k_transform(const TransformArgs p) 
     }
     if (kPrefetchT) {  // prefetch (the last iteration harmlessly re-reads its own tile)
       const long r = (next < ntiles ? next : tile) * 16 + n;
-      load_tile<NU, HALF, AL>(p.Xin, r < last_row ? r : last_row, M, g, an);
+      load_tile<NU, HALF, AL, E>(p.Xin, r < last_row ? r : last_row, M, g, an);
     }
     if (!last_ok) a[2 * NU - 2] = 0.0;
     if (!last_ok1) a[2 * NU - 1] = 0.0;
@@ -222,6 +232,10 @@ __global__ __launch_bounds__(kThreadsT) void k_transform(const TransformArgs p) 
     const int nrow = 4 * ((lane >> 2) & 3) + g;  // the narrow tile's row and column of this lane
     const int ncol = 16 * NT + (lane & 3);
     const double nval = NARROW ? __shfl(rmean, nrow, 64) + accn : 0.0;
+#ifdef EFA_T_NOSTORE_PROBE  /* make nostore (tools/f32_state_cost.py --unchecked): the kernel with its stores never executed (p.w is never
+                               null), to tell the stores' share of the launch time for either element type */
+    if (p.w == nullptr) {
+#endif
     if (r0 + 16 <= p.nrows) {  // full tile: no row checks (wave-uniform)
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
@@ -229,10 +243,10 @@ __global__ __launch_bounds__(kThreadsT) void k_transform(const TransformArgs p) 
         if (col < M) {
 #pragma unroll
           for (int v = 0; v < 4; ++v)
-            p.Xout[(size_t)(r0 + 4 * v + g) * M + col] = FUSED ? (base[v] + acc[t][v]) : acc[t][v];
+            Xout[(size_t)(r0 + 4 * v + g) * M + col] = (E)(FUSED ? (base[v] + acc[t][v]) : acc[t][v]);
         }
       }
-      if (NARROW && ncol < M) p.Xout[(size_t)(r0 + nrow) * M + ncol] = nval;
+      if (NARROW && ncol < M) Xout[(size_t)(r0 + nrow) * M + ncol] = (E)nval;
       if (!FUSED && n == 0) {
 #pragma unroll
         for (int v = 0; v < 4; ++v) p.xout[r0 + 4 * v + g] = base[v];
@@ -245,10 +259,10 @@ __global__ __launch_bounds__(kThreadsT) void k_transform(const TransformArgs p) 
         for (int v = 0; v < 4; ++v) {
           const long row = r0 + 4 * v + g;
           if (col < M && row < p.nrows)
-            p.Xout[(size_t)row * M + col] = FUSED ? (base[v] + acc[t][v]) : acc[t][v];
+            Xout[(size_t)row * M + col] = (E)(FUSED ? (base[v] + acc[t][v]) : acc[t][v]);
         }
       }
-      if (NARROW && ncol < M && r0 + nrow < p.nrows) p.Xout[(size_t)(r0 + nrow) * M + ncol] = nval;
+      if (NARROW && ncol < M && r0 + nrow < p.nrows) Xout[(size_t)(r0 + nrow) * M + ncol] = (E)nval;
       if (!FUSED && n == 0) {
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
@@ -257,10 +271,13 @@ __global__ __launch_bounds__(kThreadsT) void k_transform(const TransformArgs p) 
         }
       }
     }
+#ifdef EFA_T_NOSTORE_PROBE
+    }
+#endif
 
     if (!kPrefetchT && next < ntiles) {
       const long r = next * 16 + n;
-      load_tile<NU, HALF, AL>(p.Xin, r < last_row ? r : last_row, M, g, a);
+      load_tile<NU, HALF, AL, E>(p.Xin, r < last_row ? r : last_row, M, g, a);
     }
     tile = next;
   }
@@ -272,12 +289,12 @@ __global__ __launch_bounds__(kThreadsT) void k_transform(const TransformArgs p) 
 #endif
 }
 
-template <int NU, bool FUSED, bool HALF, bool AL>
+template <int NU, bool FUSED, bool HALF, bool AL, typename E = double>
 hipError_t transform_launch(const TransformArgs& a, hipStream_t s) {
   using Sh = TShape<NU, FUSED, HALF>;
   const size_t lds = (Sh::lds_doubles ? Sh::lds_doubles : 64) * sizeof(double);
   if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_transform<NU, FUSED, HALF, AL>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_transform<NU, FUSED, HALF, AL, E>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
@@ -286,15 +303,22 @@ hipError_t transform_launch(const TransformArgs& a, hipStream_t s) {
   long grid = (ntiles + EFA_T_WAVES - 1) / EFA_T_WAVES;
   if (grid > 256L * per_cu) grid = 256L * per_cu;
   if (grid < 1) grid = 1;
-  hipLaunchKernelGGL((k_transform<NU, FUSED, HALF, AL>), dim3((unsigned)grid), dim3(kThreadsT), lds, s, a);
+  hipLaunchKernelGGL((k_transform<NU, FUSED, HALF, AL, E>), dim3((unsigned)grid), dim3(kThreadsT), lds, s, a);
   return hipGetLastError();
 }
 
+// the pair loads need M even and a base aligned to a pair of elements
+template <typename E>
+inline bool pair_aligned(const TransformArgs& a) {
+  return (a.M % 2 == 0) && (reinterpret_cast<uintptr_t>(a.Xin) & (2 * sizeof(E) - 1)) == 0;
+}
+
+#ifndef EFA_TRANSFORM_F32
 template <int NU>
 hipError_t transform_nu(const TransformArgs& a, hipStream_t s) {
   const int rem = a.M % 8;
   const bool half = rem != 0 && rem <= 4;
-  const bool al = (a.M % 2 == 0) && (reinterpret_cast<uintptr_t>(a.Xin) & 15u) == 0;
+  const bool al = pair_aligned<double>(a);
   if (al) {
     if (half) return a.fused_members ? transform_launch<NU, true, true, true>(a, s) : transform_launch<NU, false, true, true>(a, s);
     return a.fused_members ? transform_launch<NU, true, false, true>(a, s) : transform_launch<NU, false, false, true>(a, s);
@@ -302,6 +326,16 @@ hipError_t transform_nu(const TransformArgs& a, hipStream_t s) {
   if (half) return a.fused_members ? transform_launch<NU, true, true, false>(a, s) : transform_launch<NU, false, true, false>(a, s);
   return a.fused_members ? transform_launch<NU, true, false, false>(a, s) : transform_launch<NU, false, false, false>(a, s);
 }
+#else
+// member form only: a float32 state has no perturbation form
+template <int NU>
+hipError_t transform_nu_f32(const TransformArgs& a, hipStream_t s) {
+  const int rem = a.M % 8;
+  const bool half = rem != 0 && rem <= 4;
+  if (pair_aligned<float>(a)) return half ? transform_launch<NU, true, true, true, float>(a, s) : transform_launch<NU, true, false, true, float>(a, s);
+  return half ? transform_launch<NU, true, true, false, float>(a, s) : transform_launch<NU, true, false, false, float>(a, s);
+}
+#endif
 
 
 // ---- RTPS fused into the member-form transform (M <= 136) -------------------------------------------------
@@ -313,9 +347,10 @@ hipError_t transform_nu(const TransformArgs& a, hipStream_t s) {
 // of a row group (the narrow tile's over its 4 columns first).  The scale is applied in registers: no extra HBM traffic.
 // Rows with sigma_a == 0 are stored as k_transform stores them.  A kernel of its own -- not a flag of k_transform -- so
 // the shipped transform's code stays as it is.
-template <int NU, bool HALF, bool AL>
+template <int NU, bool HALF, bool AL, typename E = double>
 __global__ __launch_bounds__(kThreadsT) void k_transform_rtps(const TransformArgs p, const double alpha) {
   using Sh = TShape<NU, true, HALF>;
+  E* const Xout = reinterpret_cast<E*>(p.Xout);
   constexpr int NT = Sh::NT;
   constexpr bool NARROW = Sh::NARROW;
   extern __shared__ __align__(16) double Bs[];  // as k_transform (member form: T + w 1^T)
@@ -357,7 +392,7 @@ __global__ __launch_bounds__(kThreadsT) void k_transform_rtps(const TransformArg
   long tile = wave;
   if (tile < ntiles) {
     const long r = tile * 16 + n;
-    load_tile<NU, HALF, AL>(p.Xin, r < last_row ? r : last_row, M, g, a);
+    load_tile<NU, HALF, AL, E>(p.Xin, r < last_row ? r : last_row, M, g, a);
   }
   if (kPrefetchT) {
 #pragma unroll
@@ -369,7 +404,7 @@ __global__ __launch_bounds__(kThreadsT) void k_transform_rtps(const TransformArg
     const long r0 = tile * 16;
     if (kPrefetchT) {
       const long r = (next < ntiles ? next : tile) * 16 + n;
-      load_tile<NU, HALF, AL>(p.Xin, r < last_row ? r : last_row, M, g, an);
+      load_tile<NU, HALF, AL, E>(p.Xin, r < last_row ? r : last_row, M, g, an);
     }
     if (!last_ok) a[2 * NU - 2] = 0.0;
     if (!last_ok1) a[2 * NU - 1] = 0.0;
@@ -478,10 +513,10 @@ __global__ __launch_bounds__(kThreadsT) void k_transform_rtps(const TransformArg
         if (col < M) {
 #pragma unroll
           for (int v = 0; v < 4; ++v)
-            p.Xout[(size_t)(r0 + 4 * v + g) * M + col] = base[v] + sc[v] * (acc[t][v] - mv[v]);
+            Xout[(size_t)(r0 + 4 * v + g) * M + col] = (E)(base[v] + sc[v] * (acc[t][v] - mv[v]));
         }
       }
-      if (nok) p.Xout[(size_t)(r0 + nrow) * M + ncol] = nval;
+      if (nok) Xout[(size_t)(r0 + nrow) * M + ncol] = (E)nval;
     } else {
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
@@ -490,26 +525,26 @@ __global__ __launch_bounds__(kThreadsT) void k_transform_rtps(const TransformArg
         for (int v = 0; v < 4; ++v) {
           const long row = r0 + 4 * v + g;
           if (col < M && row < p.nrows)
-            p.Xout[(size_t)row * M + col] = base[v] + sc[v] * (acc[t][v] - mv[v]);
+            Xout[(size_t)row * M + col] = (E)(base[v] + sc[v] * (acc[t][v] - mv[v]));
         }
       }
-      if (nok && r0 + nrow < p.nrows) p.Xout[(size_t)(r0 + nrow) * M + ncol] = nval;
+      if (nok && r0 + nrow < p.nrows) Xout[(size_t)(r0 + nrow) * M + ncol] = (E)nval;
     }
 
     if (!kPrefetchT && next < ntiles) {
       const long r = next * 16 + n;
-      load_tile<NU, HALF, AL>(p.Xin, r < last_row ? r : last_row, M, g, a);
+      load_tile<NU, HALF, AL, E>(p.Xin, r < last_row ? r : last_row, M, g, a);
     }
     tile = next;
   }
 }
 
-template <int NU, bool HALF, bool AL>
+template <int NU, bool HALF, bool AL, typename E = double>
 hipError_t transform_rtps_launch(const TransformArgs& a, double alpha, hipStream_t s) {
   using Sh = TShape<NU, true, HALF>;
   const size_t lds = (Sh::lds_doubles ? Sh::lds_doubles : 64) * sizeof(double);
   if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_transform_rtps<NU, HALF, AL>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_transform_rtps<NU, HALF, AL, E>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
@@ -518,17 +553,16 @@ hipError_t transform_rtps_launch(const TransformArgs& a, double alpha, hipStream
   long grid = (ntiles + EFA_T_WAVES - 1) / EFA_T_WAVES;
   if (grid > 256L * per_cu) grid = 256L * per_cu;
   if (grid < 1) grid = 1;
-  hipLaunchKernelGGL((k_transform_rtps<NU, HALF, AL>), dim3((unsigned)grid), dim3(kThreadsT), lds, s, a, alpha);
+  hipLaunchKernelGGL((k_transform_rtps<NU, HALF, AL, E>), dim3((unsigned)grid), dim3(kThreadsT), lds, s, a, alpha);
   return hipGetLastError();
 }
 
-template <int NU>
+template <int NU, typename E = double>
 hipError_t transform_rtps_nu(const TransformArgs& a, double alpha, hipStream_t s) {
   const int rem = a.M % 8;
   const bool half = rem != 0 && rem <= 4;
-  const bool al = (a.M % 2 == 0) && (reinterpret_cast<uintptr_t>(a.Xin) & 15u) == 0;
-  if (al) return half ? transform_rtps_launch<NU, true, true>(a, alpha, s) : transform_rtps_launch<NU, false, true>(a, alpha, s);
-  return half ? transform_rtps_launch<NU, true, false>(a, alpha, s) : transform_rtps_launch<NU, false, false>(a, alpha, s);
+  if (pair_aligned<E>(a)) return half ? transform_rtps_launch<NU, true, true, E>(a, alpha, s) : transform_rtps_launch<NU, false, true, E>(a, alpha, s);
+  return half ? transform_rtps_launch<NU, true, false, E>(a, alpha, s) : transform_rtps_launch<NU, false, false, E>(a, alpha, s);
 }
 
 // ---- ensembles of 137 .. 256 members ----------------------------------------------------------------------
@@ -538,9 +572,10 @@ hipError_t transform_rtps_nu(const TransformArgs& a, double alpha, hipStream_t s
 // make one read+write pass per 64 observations).  Same operand layouts as k_transform; no prefetch (the A
 // operand of 256 members is 128 registers), no narrow last tile.
 constexpr int kWideTiles = 4;
-template <int NU, bool FUSED, bool AL>
+template <int NU, bool FUSED, bool AL, typename E = double>
 __global__ __launch_bounds__(kThreadsT) void k_transform_wide(const TransformArgs p) {
   constexpr int NTG = kWideTiles;
+  E* const Xout = reinterpret_cast<E*>(p.Xout);
   constexpr int kSteps = 2 * NU;
   extern __shared__ __align__(16) double Bs[];  // [(u*2+h)*NTG + t][64] for this group's tiles
   const int M = p.M;
@@ -572,7 +607,7 @@ __global__ __launch_bounds__(kThreadsT) void k_transform_wide(const TransformArg
     const long r0 = tile * 16;
     const long r = r0 + n;
     double a[2 * NU];
-    load_tile<NU, false, AL>(p.Xin, r < last_row ? r : last_row, M, g, a);
+    load_tile<NU, false, AL, E>(p.Xin, r < last_row ? r : last_row, M, g, a);
 #pragma unroll
     for (int c = 0; c < 2 * NU; ++c) {  // slots beyond M (only in the last chunk) are zero
       const int m = 8 * (c >> 1) + 2 * g + (c & 1);
@@ -622,7 +657,7 @@ __global__ __launch_bounds__(kThreadsT) void k_transform_wide(const TransformArg
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
         const long row = r0 + 4 * v + g;
-        if (col < M && row < p.nrows) p.Xout[(size_t)row * M + col] = FUSED ? (base[v] + acc[t][v]) : acc[t][v];
+        if (col < M && row < p.nrows) Xout[(size_t)row * M + col] = (E)(FUSED ? (base[v] + acc[t][v]) : acc[t][v]);
       }
     }
     if (!FUSED && n == 0 && tM >= t0 && tM < t0 + NTG) {  // the group that holds column M writes the means
@@ -635,10 +670,10 @@ __global__ __launch_bounds__(kThreadsT) void k_transform_wide(const TransformArg
   }
 }
 
-template <int NU>
+template <int NU, typename E = double>
 hipError_t transform_wide_nu(const TransformArgs& a, hipStream_t s) {
   const size_t lds = (size_t)2 * NU * kWideTiles * 64 * sizeof(double);
-  const bool al = (a.M % 2 == 0) && (reinterpret_cast<uintptr_t>(a.Xin) & 15u) == 0;
+  const bool al = pair_aligned<E>(a);
   const int ncols = a.fused_members ? a.M : a.M + 1;
   const int groups = ((ncols + 15) / 16 + kWideTiles - 1) / kWideTiles;
   const long ntiles = (a.nrows + 15) / 16;
@@ -648,17 +683,19 @@ hipError_t transform_wide_nu(const TransformArgs& a, hipStream_t s) {
   const dim3 grid((unsigned)gx, (unsigned)groups);
 #define EFA_WIDE_LAUNCH(F, A)                                                                                       \
   do {                                                                                                              \
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_transform_wide<NU, F, A>),                  \
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_transform_wide<NU, F, A, E>),                  \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                       \
     if (e != hipSuccess) return e;                                                                                  \
-    hipLaunchKernelGGL((k_transform_wide<NU, F, A>), grid, dim3(kThreadsT), lds, s, a);                              \
+    hipLaunchKernelGGL((k_transform_wide<NU, F, A, E>), grid, dim3(kThreadsT), lds, s, a);                              \
   } while (0)
   if (a.fused_members) {
     if (al) EFA_WIDE_LAUNCH(true, true);
     else EFA_WIDE_LAUNCH(true, false);
-  } else {
+  } else if constexpr (sizeof(E) == sizeof(double)) {
     if (al) EFA_WIDE_LAUNCH(false, true);
     else EFA_WIDE_LAUNCH(false, false);
+  } else {
+    return hipErrorInvalidValue;
   }
 #undef EFA_WIDE_LAUNCH
   return hipGetLastError();
@@ -666,6 +703,7 @@ hipError_t transform_wide_nu(const TransformArgs& a, hipStream_t s) {
 
 }  // namespace
 
+#ifndef EFA_TRANSFORM_F32
 // one launch with the whole [T | w] image in LDS up to M = 136; column groups above (k_transform_wide) up to 256
 bool transform_supported(int M) { return M >= 2 && M <= 256; }
 
@@ -687,5 +725,25 @@ hipError_t launch_transform(const TransformArgs& a, hipStream_t s) {
   if (nu <= 17) return dispatch_width(nu, WidthRange<1, 17>{}, [&](auto n) { return transform_nu<n>(a, s); });
   return dispatch_width(nu, WidthRange<18, 32>{}, [&](auto n) { return transform_wide_nu<n>(a, s); });
 }
+
+#else
+// ---- the same kernels on rows stored as float32 (efa_transform_f32.hip) ---------------------------------------
+// a.Xin / a.Xout point at float rows (4-byte aligned), member form only; T, w and every number computed stay float64.
+hipError_t launch_transform_rtps_f32(const TransformArgs& a, double alpha, hipStream_t s) {
+  if (!transform_rtps_supported(a.M) || !a.fused_members) return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(a.Xin) & 3u) != 0 || (reinterpret_cast<uintptr_t>(a.Xout) & 3u) != 0) return hipErrorInvalidValue;
+  if (a.nrows <= 0) return hipSuccess;
+  return dispatch_width((a.M + 7) / 8, WidthRange<1, 17>{}, [&](auto nu) { return transform_rtps_nu<nu, float>(a, alpha, s); });
+}
+
+hipError_t launch_transform_f32(const TransformArgs& a, hipStream_t s) {
+  if (!transform_supported(a.M) || !a.fused_members) return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(a.Xin) & 3u) != 0 || (reinterpret_cast<uintptr_t>(a.Xout) & 3u) != 0) return hipErrorInvalidValue;
+  if (a.nrows <= 0) return hipSuccess;
+  const int nu = (a.M + 7) / 8;
+  if (nu <= 17) return dispatch_width(nu, WidthRange<1, 17>{}, [&](auto n) { return transform_nu_f32<n>(a, s); });
+  return dispatch_width(nu, WidthRange<18, 32>{}, [&](auto n) { return transform_wide_nu<n, float>(a, s); });
+}
+#endif
 
 }  // namespace efa

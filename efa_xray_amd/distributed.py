@@ -215,12 +215,21 @@ class ShardedEnSRF(object):
                 dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
         return t
 
+    @staticmethod
+    def _reject_float32(*buffers):
+        """ValueError for a float32 shard: the sharded path is float64 only."""
+        for b in buffers:
+            if str(getattr(b, "dtype", "")) in ("float32", "torch.float32"):
+                raise ValueError("ShardedEnSRF does not support a float32 state (float32 storage is EnSRF's, on one GPU: "
+                                 "DESIGN.md 7g)")
+
     def partial_estimates(self, X_local, sten_idx, sten_wts, inflation=None):
         """Stage 1: this shard's contribution to the obs-space prior ensemble HX (P x M): the
         stencil points it owns, zeros elsewhere.  `inflation` (a float) first inflates the
         resident shard in place about its ensemble mean -- the constant form of
         `Assimilation.inflate_state` (assimilation.py:62-69), which the reference applies
         before the obs priors are computed (assimilation.py:131-138)."""
+        self._reject_float32(X_local)
         eng, M = self.engine, self.M
         if inflation is not None:
             eng.inflate(self.rows_local, M, X_local, float(inflation))
@@ -247,6 +256,7 @@ class ShardedEnSRF(object):
         gross-error check as in `EnSRF`; every rank decides alike, from the same summed obs block."""
         if adaptive_inflation is not None:
             raise ValueError("ShardedEnSRF does not support adaptive_inflation (out of scope: use EnSRF on one GPU)")
+        self._reject_float32(X_local, post_local)
         eng, M = self.engine, self.M
         relax = relaxation_setting(rtps, rtpp)
         if hasattr(eng, "set_relaxation"):
@@ -280,6 +290,7 @@ class ShardedEnSRF(object):
                rtps=None, rtpp=None, adaptive_inflation=None, vert_coord=None, outlier_threshold=None):
         if adaptive_inflation is not None:
             raise ValueError("ShardedEnSRF does not support adaptive_inflation (out of scope: use EnSRF on one GPU)")
+        self._reject_float32(X_local, post_local)
         self._vertical(ob, vert_coord, int(np.asarray(sten_idx).shape[0]))  # (refused before any work)
         outlier_setting(outlier_threshold)
         HX = self.partial_estimates(X_local, sten_idx, sten_wts, inflation)

@@ -20,6 +20,8 @@ from copy import deepcopy
 
 import numpy as np
 
+from efa_xray_amd._lib import state_dtype
+
 _DIMS = ("validtime", "y", "x", "mem")
 _COORD_NAMES = ("validtime", "lat", "lon", "mem", "x", "y")
 EARTH_RADIUS_KM = 6371.0
@@ -63,11 +65,15 @@ class EnsembleState(object):
 
     # -- construction (ensemble.py:25-37) -----------------------------------
     @classmethod
-    def from_vardict(cls, vardict, coorddict):
+    def from_vardict(cls, vardict, coorddict, dtype=None):
         """Build from xarray-style dictionaries: `vardict[name] = (dims, data)`
         with dims a permutation of ('validtime','y','x','mem');
         `coorddict` holds validtime, lat, lon (1-D or `(('y','x'), 2-D)`), mem
-        and optionally x, y."""
+        and optionally x, y.  `dtype`: how the members are stored -- None casts
+        to float64, numpy.float32 keeps (or casts to) float32 (storage only:
+        the update computes in float64); anything else raises
+        ValueError."""
+        dt = state_dtype(dtype)
         variables = OrderedDict()
         for name, entry in vardict.items():
             dims, data = _unpack(entry)
@@ -75,7 +81,7 @@ class EnsembleState(object):
                 dims = _DIMS
             if sorted(dims) != sorted(_DIMS):
                 raise ValueError("variable %r must have dims %r, got %r" % (name, _DIMS, dims))
-            data = np.transpose(np.asarray(data, dtype=np.float64), [dims.index(d) for d in _DIMS])
+            data = np.transpose(np.asarray(data, dtype=dt), [dims.index(d) for d in _DIMS])
             variables[name] = np.ascontiguousarray(data)
         shapes = set(v.shape for v in variables.values())
         if len(shapes) > 1:
@@ -93,23 +99,23 @@ class EnsembleState(object):
         return cls(variables, coords)
 
     @classmethod
-    def from_array(cls, arr, lat, lon, varnames=None, validtime=None):
-        """(nvar, nt, ny, nx, nmem) array + lat/lon -> state (convenience)."""
-        arr = np.asarray(arr, dtype=np.float64)
+    def from_array(cls, arr, lat, lon, varnames=None, validtime=None, dtype=None):
+        """(nvar, nt, ny, nx, nmem) array + lat/lon -> state (convenience); `dtype` as in `from_vardict`."""
+        arr = np.asarray(arr, dtype=state_dtype(dtype))
         nvar = arr.shape[0]
         names = varnames or ["var%d" % i for i in range(nvar)]
         vd = OrderedDict((n, (_DIMS, arr[i])) for i, n in enumerate(names))
         cd = dict(lat=np.asarray(lat, dtype=np.float64), lon=np.asarray(lon, dtype=np.float64))
         if validtime is not None:
             cd["validtime"] = np.asarray(validtime)
-        return cls.from_vardict(vd, cd)
+        return cls.from_vardict(vd, cd, dtype=dtype)
 
     @classmethod
-    def from_xarray(cls, ds):
+    def from_xarray(cls, ds, dtype=None):
         names = [v for v in ds.variables.keys() if v not in _COORD_NAMES]
         vd = OrderedDict((n, (tuple(ds[n].dims), ds[n].values)) for n in names)
         cd = dict((c, ds[c].values) for c in _COORD_NAMES if c in ds.variables or c in ds.coords)
-        return cls.from_vardict(vd, cd)
+        return cls.from_vardict(vd, cd, dtype=dtype)
 
     def to_xarray(self):
         import xarray  # optional
@@ -121,6 +127,22 @@ class EnsembleState(object):
             else:
                 cd[k] = v
         return xarray.Dataset(vd, coords=cd)
+
+    # -- storage dtype --------------------------------------------------------------
+    @property
+    def dtype(self):
+        """numpy.float64 or numpy.float32, the dtype every variable is stored in; ValueError when they differ."""
+        dts = set(np.asarray(v).dtype for v in self.variables.values())
+        if len(dts) > 1:
+            raise ValueError("the state's variables mix dtypes %r: store all of them as float64 or all as float32"
+                             % sorted(str(d) for d in dts))
+        return state_dtype(dts.pop() if dts else None)
+
+    def astype(self, dtype):
+        """A copy of this state stored as `dtype` (numpy.float64 / numpy.float32; None: float64)."""
+        dt = state_dtype(dtype)
+        return type(self)(OrderedDict((n, np.ascontiguousarray(v, dtype=dt).copy()) for n, v in self.variables.items()),
+                          dict((k, np.array(v, copy=True)) for k, v in self.coords.items()))
 
     # -- sizes (ensemble.py:40-56) ---------------------------------------------
     def _first(self):
@@ -157,7 +179,7 @@ class EnsembleState(object):
         return np.reshape(np.stack(list(self.variables.values()), axis=0), (self.nstate(), self.nmems()))
 
     def from_vect(self, instate):
-        arr = np.reshape(np.asarray(instate, dtype=np.float64), self.shape())
+        arr = np.reshape(np.asarray(instate, dtype=self.dtype), self.shape())
         for i, name in enumerate(self.variables.keys()):
             self.variables[name] = np.ascontiguousarray(arr[i])
 
@@ -193,7 +215,7 @@ class EnsembleState(object):
             ctx = _lib.get_context(0)
         variables = OrderedDict()
         for n, v in self.variables.items():
-            a = ctx.pinned_empty(v.shape)
+            a = ctx.pinned_empty(v.shape, v.dtype)
             a[...] = v
             variables[n] = a
         return type(self)(variables, dict((k, np.array(v, copy=True)) for k, v in self.coords.items()))
@@ -307,7 +329,7 @@ class EnsembleState(object):
             iv, rem = divmod(int(r), nt * ny * nx)
             it, rem = divmod(rem, ny * nx)
             y, x = divmod(rem, nx)
-            out += w * self.variables[names[iv]][it, y, x, :]
+            out += w * np.asarray(self.variables[names[iv]][it, y, x, :], dtype=np.float64)
         return out
 
     # -- persistence (ensemble.py:269-273) ---------------------------------------
@@ -317,7 +339,7 @@ class EnsembleState(object):
         With xarray importable the file is written by xarray, as in the reference.  Without it (the build image)
         the same content goes out as a classic netCDF-3 file through `scipy.io.netcdf_file` -- which is also the
         format xarray itself falls back to when netCDF4 is absent: dimensions validtime, y, x, mem; one float64
-        variable per state variable; lat / lon on (y, x) or on their own 1-D dimensions; validtime as stored
+        (float32 for a state stored so) variable per state variable; lat / lon on (y, x) or on their own 1-D dimensions; validtime as stored
         (datetime64 values as seconds since 1970-01-01 with a `units` attribute).  `EnsembleState.from_netcdf`
         reads either kind back.  PARITY UNPINNED: the reference's own writer needs xarray."""
         try:
@@ -349,19 +371,20 @@ class EnsembleState(object):
                     f.createVariable(name, "d", (name + "_1d",))[:] = c
             f.createVariable("mem", "d", ("mem",))[:] = np.asarray(self.coords.get("mem", np.arange(1, nm + 1)), dtype=np.float64)
             for name, val in self.variables.items():
-                f.createVariable(name, "d", _DIMS)[:] = val
+                f.createVariable(name, "f" if val.dtype == np.float32 else "d", _DIMS)[:] = val
 
     @classmethod
-    def from_netcdf(cls, filename):
+    def from_netcdf(cls, filename, dtype=None):
         """Read a state written by `save_to_disk` (either writer): the counterpart of the reference's
-        `xarray.open_dataset` + `EnsembleState.from_vardict`."""
+        `xarray.open_dataset` + `EnsembleState.from_vardict`.  `dtype` as in `from_vardict`: None reads every variable as
+        float64 whatever the file holds, numpy.float32 as float32."""
         try:
             import xarray
         except ImportError:
             xarray = None
         if xarray is not None:
             with xarray.open_dataset(filename) as ds:
-                return cls.from_xarray(ds.load())
+                return cls.from_xarray(ds.load(), dtype=dtype)
         from scipy.io import netcdf_file
         with netcdf_file(filename, "r", mmap=False) as f:
             vd = OrderedDict()
@@ -374,4 +397,4 @@ class EnsembleState(object):
                     cd[name] = data
                 elif tuple(var.dimensions) and sorted(var.dimensions) == sorted(_DIMS):
                     vd[name] = (tuple(var.dimensions), data)
-            return cls.from_vardict(vd, cd)
+            return cls.from_vardict(vd, cd, dtype=dtype)

@@ -95,7 +95,8 @@ int efa_ctx_set_stream(efa_ctx *ctx, void *hip_stream);
  *          "own_stream" (see above);
  *          read-only: "phase_a_kind" (1 pipeline / 2 per-batch / 3 Gram pipeline / 4 band pipeline, last call),
  *          "gc_active_pairs"
- *          ((column, ob) pairs with a non-zero taper in the last one-pass sweep) */
+ *          ((column, ob) pairs with a non-zero taper in the last one-pass sweep),
+ *          "f32_native" (see efa_state_cycle_f32_dev) */
 int efa_ctx_set_option(efa_ctx *ctx, const char *key, long value);
 int efa_ctx_get_option(efa_ctx *ctx, const char *key, long *value);
 
@@ -314,6 +315,36 @@ int efa_state_cycle_dev(efa_ctx *ctx, long rows, int M, const double *X_dev,
                         double *post_dev, const double *grid_lat,
                         const double *grid_lon, long ncol, long n_lead);
 
+/* ---- the state stored as float32, every number still computed in float64 ----
+ * efa_state_cycle_dev on float32 member rows X[row*M + mem]: for a float32 prior
+ * X32 the posterior is fl32(F(widen(X32))) -- widen the exact float32 -> float64
+ * conversion, F the float64 state phase of efa_state_cycle_dev (the same kernels'
+ * arithmetic in the same order) and fl32 ONE round-to-nearest-even at the final
+ * store -- on every path and with every option.  Like efa_state_cycle_dev it
+ * follows efa_obs_phase_dev; the obs block, the trajectory and the diagnostics
+ * are float64 as ever.  post_dev may equal X_dev; both need 4-byte alignment
+ * only (rows whose base is 8-byte aligned, M even, are loaded two members at a
+ * time).  Relaxation, vertical localisation and the options "path" and
+ * "gc_onepass" apply as they do to efa_state_cycle_dev; while an adaptive-
+ * inflation field is set the call fails with EFA_ERR_INVALID (that update is
+ * float64 only).
+ * The transform (up to 256 members; RTPP folded in, RTPS fused in up to 136
+ * members) and the one-pass GC sweep for an even number of up to 104 members
+ * without relaxation read and write the float32 rows themselves.  Every other
+ * route -- the per-batch sweeps, "gc_onepass" 0, the one-pass sweep for odd or
+ * more than 104 members, a relaxation that is not folded or fused, a cycle
+ * without an assimilated ob -- widens the rows into a float64 workspace of the
+ * context, runs the float64 kernels there and rounds the posterior members once
+ * on the way out: rows*M*8 bytes more device memory (twice that for the
+ * transform above 136 members, whose column groups cannot run in place; the
+ * float32 transform above 136 members with post_dev == X_dev keeps a copy of the
+ * prior instead, rows*M*4 bytes).  Read-only option "f32_native" says which it
+ * was for the last float32 state call: 1 on the float32 rows, 0 through the
+ * workspace. */
+int efa_state_cycle_f32_dev(efa_ctx *ctx, long rows, int M, const float *X_dev,
+                            float *post_dev, const double *grid_lat,
+                            const double *grid_lon, long ncol, long n_lead);
+
 /* ---- one whole cycle on resident prior members, ONE call ------------------
  * efa_obs_phase_dev followed by efa_state_cycle_dev (ensrf.py:50-149 on the obs
  * block, then on every state row; same arguments, same results bit for bit),
@@ -407,6 +438,24 @@ int efa_ensrf_cycle_host(efa_ctx *ctx, int n_seg, const double *const *seg_prior
                          const double *grid_lon, double *prior_mean,
                          double *prior_var, double *post_mean, double *post_var,
                          uint8_t *assimilated);
+/* efa_ensrf_cycle_host on a state stored as float32: the segments are
+ * [seg_slabs[v]][ncol][M] float32 arrays, every chunk runs
+ * efa_state_cycle_f32_dev (above: posterior = fl32(F(widen(prior)))), and the
+ * ring, the staging images and the copies move 4-byte elements -- half the
+ * bytes over the link and "stream_peak_bytes" three chunks of rows*M*4.  HX,
+ * the per-ob arrays, the grid and the diagnostics are float64 as above, and
+ * bit for bit those of efa_ensrf_cycle_host on the widened prior.  Equal to
+ * efa_state_cycle_f32_dev on the resident float32 state bit for bit. */
+int efa_ensrf_cycle_host_f32(efa_ctx *ctx, int n_seg, const float *const *seg_prior,
+                             float *const *seg_post, const long *seg_slabs, long ncol,
+                             int M, long P, const double *HX, long chunk_cols,
+                             const double *ob_value, const double *ob_error,
+                             const uint8_t *ob_assim, int loc_mode,
+                             const double *ob_lat, const double *ob_lon,
+                             const double *ob_halfwidth_km, const double *grid_lat,
+                             const double *grid_lon, double *prior_mean,
+                             double *prior_var, double *post_mean, double *post_var,
+                             uint8_t *assimilated);
 /* Page-locked host memory owned by the context (hipHostMalloc), for states
  * that efa_ensrf_cycle_host moves by DMA without staging.  Blocks still
  * allocated when the context is destroyed are freed with it. */
