@@ -529,13 +529,13 @@ int efa_state_phase_dev(efa_ctx* c, long rows, int M, const double* xm_in_dev, c
 int efa_state_cycle_dev(efa_ctx* c, long rows, int M, const double* X_dev, double* post_dev, const double* grid_lat,
                         const double* grid_lon, long ncol, long n_lead) {
   EFA_TRY(use(c));
-  return state_cycle(c, rows, M, X_dev, post_dev, grid_lat, grid_lon, ncol, n_lead);
+  return state_cycle(c, StateRows{X_dev, post_dev, Elem::f64, rows, M}, grid_lat, grid_lon, ncol, n_lead);
 }
 
 int efa_state_cycle_f32_dev(efa_ctx* c, long rows, int M, const float* X_dev, float* post_dev, const double* grid_lat,
                             const double* grid_lon, long ncol, long n_lead) {
   EFA_TRY(use(c));
-  return state_cycle_f32(c, rows, M, X_dev, post_dev, grid_lat, grid_lon, ncol, n_lead);
+  return state_cycle(c, StateRows{X_dev, post_dev, Elem::f32, rows, M}, grid_lat, grid_lon, ncol, n_lead);
 }
 
 int efa_ensrf_update_dev(efa_ctx* c, long rows, int M, long P, double* xm_dev, double* Xp_dev, double* ym_dev,
@@ -565,15 +565,8 @@ int efa_ensrf_cycle_dev(efa_ctx* c, long rows, int M, long P, const double* X_de
   EFA_TRY(check_vloc(c, loc_mode, P, n_lead));
   // Phase B may go into the stream before Phase A's status is known only if a wrong guess cannot cost the prior:
   // separate prior and posterior buffers (a redone Phase A needs the transform run again on the untouched prior)
-  const char* xb = reinterpret_cast<const char*>(X_dev);
-  const char* pb = reinterpret_cast<const char*>(post_dev);
-  const size_t bytes = (size_t)rows * (size_t)(M > 0 ? M : 0) * sizeof(double);
-  const bool disjoint = rows > 0 && (xb + bytes <= pb || pb + bytes <= xb);
-  SpecRequest spec;
-  spec.X = X_dev;
-  spec.post = post_dev;
-  spec.rows = (disjoint && loc_mode == EFA_LOC_NONE) ? rows : 0;
-  spec.obs_out = obs_block_out != 0;
+  const StateRows r{X_dev, post_dev, Elem::f64, rows, M};
+  const SpecRequest spec{X_dev, post_dev, (r.disjoint() && loc_mode == EFA_LOC_NONE) ? rows : 0, obs_block_out != 0};
   // the grid ahead of Phase A, while the device is still busy with the previous cycle
   StateCall sc;
   sc.grid_current = loc_mode == EFA_LOC_GC && rows > 0;
@@ -587,13 +580,13 @@ int efa_ensrf_cycle_dev(efa_ctx* c, long rows, int M, long P, const double* X_de
   // Phase B is in the stream already, behind the launch that turned out fine -- unless the outlier check rejected so many obs
   // that the state phase would not take the transform (none left, or "auto" with fewer): then it runs as it would have, over the
   // speculative posterior (the prior is untouched)
-  if (done.launched && c->n_active > 0 && want_transform(c, true)) {
+  const StatePlan plan = plan_state(c, true, r.elem, false, c->have_transform);
+  if (done.launched && plan.route == Route::transform) {
     c->state_ms = 0.0;
-    c->state_launches = done.launches;
-    c->path_taken = EFA_PATH_TRANSFORM;
+    report_state_call(c, plan, r.elem, done.launches);
     return end_state_call(c, *done.interval, true, true);
   }
-  return state_cycle(c, rows, M, X_dev, post_dev, grid_lat, grid_lon, ncol, n_lead, sc);
+  return state_cycle(c, r, grid_lat, grid_lon, ncol, n_lead, sc);
 }
 
 int efa_ensrf_update(efa_ctx* c, long A, long N, int M, long P, double* xbm, double* Xbp, const double* ob_value,

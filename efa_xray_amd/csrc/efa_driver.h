@@ -1,11 +1,12 @@
 // What the host-side translation units of libefa_hip.so share.  Not exported.
 //   efa_capi.hip     the extern "C" shell: contexts, options, memory helpers, the public wrappers, efa_last_timing
 //   efa_phase_a.hip  the obs phase (Phase A): staging, the window driver, the speculative transform
-//   efa_phase_b.hip  the state phase (Phase B): relaxation glue, the column grid, the sweeps and the two state calls
+//   efa_phase_b.hip  the state phase (Phase B): the column grid, the plan of a state call, its executor and the state calls
 //   efa_stream.hip   the streamed host-memory update
 //   efa_comm.hip     RCCL
 // One call's arguments and results travel as arguments and return values; the context (efa_ctx.h) holds settings, caches,
-// workspaces and what the last obs phase left for the state phase.
+// workspaces and what the last obs phase left for the state phase.  A state call's rows travel with their element type (StateRows);
+// its route is decided once, by plan_state, and every caller issues the launches through run_state_plan.
 #pragma once
 #include "efa_ctx.h"
 #include "efa_internal.h"
@@ -54,11 +55,43 @@ inline bool vl_active(const efa_ctx* c) { return c->vl_on && c->vl_any; }
 inline const double* vl_lead(const efa_ctx* c) { return c->vl_dev.as<double>(); }
 inline const double* vl_obvert(const efa_ctx* c) { return c->vl_dev.as<double>() + c->vl_nlead; }
 inline const double* vl_obvhw(const efa_ctx* c) { return c->vl_dev.as<double>() + c->vl_nlead + c->vl_P; }
-bool auto_transform(int M, long n_active, bool member_form);
-bool want_transform(const efa_ctx* c, bool member_form);
-int transform_with_relaxation(efa_ctx* c, efa::TransformArgs t, long* nl, bool f32 = false);
-efa::TransformArgs carried_transform(const efa_ctx* c, const double* Xin, const double* xin, double* Xout, double* xout, long rows,
-                                     int fused_members);
+using efa::Elem;
+// The rows of one state call, prior and posterior: [rows][M] members of type elem, or the perturbation form's float64 perturbations
+struct StateRows {
+  const void* prior = nullptr;
+  void* post = nullptr;
+  Elem elem = Elem::f64;
+  long rows = 0;
+  int M = 0;
+  size_t count() const { return (size_t)(rows > 0 ? rows : 0) * (size_t)(M > 0 ? M : 0); }
+  size_t bytes() const { return count() * efa::elem_size(elem); }
+  bool disjoint() const {  // the posterior is written clear of the prior
+    const char *a = static_cast<const char*>(prior), *b = static_cast<const char*>(post);
+    return a + bytes() <= b || b + bytes() <= a;
+  }
+  bool in_place() const { return !disjoint(); }
+  // As the kernel argument structs carry rows of either type: the launchers that take `elem` (launch_transform, launch_transform_rtps,
+  // launch_sweep_gc) pick the kernels that read them.  Every other pass is float64 only, and no plan sends float32 rows there.
+  const double* in() const { return static_cast<const double*>(prior); }
+  double* out() const { return static_cast<double*>(post); }
+};
+// What a state call will do: plan_state decides it from the context's settings, what the last obs phase left (M, P, n_active,
+// loc_mode, the records) and its arguments -- have_transform: c->have_transform, or ahead of Phase A's end what it will be -- and
+// launches and writes nothing.  run_state_plan issues a plan's launches on the context's stream (xm_in / xm_out: the means of the
+// perturbation form) and counts them; report_state_call sets what the call reports (efa_last_timing, "f32_native") from both.
+enum class Route { transform, gc_onepass, sweeps };      // through [T | w] | the one-pass GC sweep | the per-batch sweeps
+enum class Relax { none, folded, fused, standalone };    // RTPP folded into T | RTPS fused into the transform | passes around the route
+struct StatePlan {
+  Route route = Route::sweeps;
+  Relax relax = Relax::none;
+  bool member_form = true;
+  int ws_copies = 0;        // float32 rows: 0 the kernels read and write the float rows; else copies of the state in the float64 workspace
+  bool copy_prior = false;  // float32 rows, in place, transform above 136 members: it reads a copy of the prior
+};
+StatePlan plan_state(const efa_ctx* c, bool member_form, Elem elem, bool in_place, bool have_transform);
+int run_state_plan(efa_ctx* c, const StatePlan& p, const StateRows& r, const double* xm_in, double* xm_out, long ncol, long n_lead,
+                   long* launches);
+void report_state_call(efa_ctx* c, const StatePlan& p, Elem elem, long launches);
 int read_gc_pairs(efa_ctx* c);
 // the one check of a localised call's grid arguments (no-op without localisation)
 int check_grid(int loc_mode, const double* grid_lat, const double* grid_lon, long ncol, long n_lead, long rows);
@@ -69,11 +102,9 @@ struct StateCall {
 };
 int state_phase(efa_ctx* c, long rows, int M, const double* xm_in, const double* Xp_in, double* xm_out, double* Xp_out,
                 const double* grid_lat, const double* grid_lon, long ncol, long n_lead, const StateCall& o = StateCall{});
-int state_cycle(efa_ctx* c, long rows, int M, const double* X_dev, double* post_dev, const double* grid_lat,
-                const double* grid_lon, long ncol, long n_lead, const StateCall& o = StateCall{});
-// the member form on float32 rows: natively where a float32 kernel exists, through the float64 workspace otherwise (c->f32_native)
-int state_cycle_f32(efa_ctx* c, long rows, int M, const float* X_dev, float* post_dev, const double* grid_lat,
-                    const double* grid_lon, long ncol, long n_lead, const StateCall& o = StateCall{});
+// the member form, on float64 or float32 rows
+int state_cycle(efa_ctx* c, const StateRows& r, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
+                const StateCall& o = StateCall{});
 // end of a state call: the launch count into the sum; "timing" 1 waits and reads the interval, 2 leaves it pending.
 // end_recorded: iv.end is in the stream already (a speculative transform that turned out right)
 int end_state_call(efa_ctx* c, Interval& iv, bool timed = true, bool end_recorded = false);

@@ -600,17 +600,29 @@ hipError_t launch_gc_count(long ncol, long P, const double* glat, const double* 
   return hipGetLastError();
 }
 
-hipError_t launch_sweep_gc(const GcSweepArgs& a0, hipStream_t s) {
-  const GcSweepArgs& a = a0;
-  if (a.M < 2 || a.M > kMaxMembers) return hipErrorInvalidValue;
+// float64 rows serve every cycle; float32 rows the cycles of the row-per-lane kernel: what the float64 launch asks of
+// a cycle before it takes that kernel, less the 16-byte alignment of the rows (float rows need 4)
+bool sweep_gc_serves(Elem elem, int M, long ye_stride, const double* Ye) {
+  if (M < 2 || M > kMaxMembers) return false;
+  return elem == Elem::f64 || (EFA_GC_LANE && M <= kLaneMaxMembers && (M % 2 == 0) && (ye_stride % 2 == 0) && aligned16(Ye));
+}
+
+// The launcher is where a.Xin / a.Xout get their element type: elem picks the kernels that read them as float or as double rows.
+hipError_t launch_sweep_gc(const GcSweepArgs& a, Elem elem, hipStream_t s) {
+  const bool f32 = elem == Elem::f32;
+  if (!sweep_gc_serves(elem, a.M, a.ye_stride, a.Ye)) return hipErrorInvalidValue;
+  // float32 rows: member form, 4-byte aligned, no adaptive inflation (its update is float64 only)
+  if (f32 && (!a.fused_members || a.infl || ((reinterpret_cast<uintptr_t>(a.Xin) | reinterpret_cast<uintptr_t>(a.Xout)) & 3u) != 0))
+    return hipErrorInvalidValue;
   if (a.nblk <= 0 || a.n_lead <= 0) return hipSuccess;
-  // 16-byte aligned rows of up to 104 members (an even number of them): the row-per-lane kernel
-  if (EFA_GC_LANE && a.M <= kLaneMaxMembers && (a.M % 2 == 0) && (a.ye_stride % 2 == 0) && aligned16(a.Xin) &&
-      aligned16(a.Xout) && aligned16(a.Ye)) {
+  // 16-byte aligned float64 rows of up to 104 members (an even number of them), and the float32 rows: the row-per-lane kernel
+  if (f32 || (EFA_GC_LANE && a.M <= kLaneMaxMembers && (a.M % 2 == 0) && (a.ye_stride % 2 == 0) && aligned16(a.Xin) &&
+              aligned16(a.Xout) && aligned16(a.Ye))) {
     GcSweepArgs l = a;
     l.lead_split = (int)((l.n_lead + 15) / 16);  // groups of 16 slabs: one workgroup each
     l.lead_chunk = 16;
     return dispatch_width((l.M + 3) / 4, WidthRange<1, kLaneMaxMembers / 4>{}, [&](auto q) {
+      if (f32) return l.lead_vert ? gc_lane_launch_f32<4 * q, kGcVloc>(l, s) : gc_lane_launch_f32<4 * q, kGcPlain>(l, s);
       switch (gc_family(a)) {
         case kGcAdapt: return gc_lane_launch_one<4 * q, kGcAdapt>(l, s);
         case kGcVloc: return gc_lane_launch_one<4 * q, kGcVloc>(l, s);
@@ -624,26 +636,6 @@ hipError_t launch_sweep_gc(const GcSweepArgs& a0, hipStream_t s) {
       case kGcVloc: return gc_launch<nc, kGcVloc>(a, s);
       default: return gc_launch<nc, kGcPlain>(a, s);
     }
-  });
-}
-
-// ---- a state stored as float32: the row-per-lane kernel, member form --------------------------------------------
-// what the float64 launch asks of a cycle before it takes the row-per-lane kernel, less the 16-byte alignment of the rows
-// (float rows need 4)
-bool sweep_gc_lane_f32_supported(int M, long ye_stride, const double* Ye) {
-  return EFA_GC_LANE && M >= 2 && M <= kLaneMaxMembers && (M % 2 == 0) && (ye_stride % 2 == 0) && aligned16(Ye);
-}
-
-// a.Xin / a.Xout point at float rows (4-byte aligned)
-hipError_t launch_sweep_gc_lane_f32(const GcSweepArgs& a, hipStream_t s) {
-  if (!sweep_gc_lane_f32_supported(a.M, a.ye_stride, a.Ye) || !a.fused_members || a.infl) return hipErrorInvalidValue;
-  if ((reinterpret_cast<uintptr_t>(a.Xin) & 3u) != 0 || (reinterpret_cast<uintptr_t>(a.Xout) & 3u) != 0) return hipErrorInvalidValue;
-  if (a.nblk <= 0 || a.n_lead <= 0) return hipSuccess;
-  GcSweepArgs l = a;
-  l.lead_split = (int)((l.n_lead + 15) / 16);
-  l.lead_chunk = 16;
-  return dispatch_width((l.M + 3) / 4, WidthRange<1, kLaneMaxMembers / 4>{}, [&](auto q) {
-    return l.lead_vert ? gc_lane_launch_f32<4 * q, kGcVloc>(l, s) : gc_lane_launch_f32<4 * q, kGcPlain>(l, s);
   });
 }
 

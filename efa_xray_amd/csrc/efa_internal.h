@@ -27,6 +27,11 @@ using WidthRange = decltype(offset_widths<Lo>(std::make_integer_sequence<int, Hi
 // chunks of 8 members the quad-layout sweeps are instantiated for (sweep_slots(M) / 8)
 using SweepChunks = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 20, 24, 32>;
 
+// The element type of state rows in memory.  The kernel argument structs below carry rows of either type as
+// double pointers: the launch, not the pointer, says which kernels read them.
+enum class Elem { f64, f32 };
+inline size_t elem_size(Elem e) { return e == Elem::f32 ? sizeof(float) : sizeof(double); }
+
 // Largest ensemble the register-resident kernels are instantiated for.
 constexpr int kMaxMembers = 256;
 // Rows (observations) handled by one obs-space diag workgroup == max obs_batch.
@@ -189,11 +194,10 @@ hipError_t launch_gc_count(long ncol, long P, const double* glat, const double* 
                            const double* ob_lon, const double* ob_hw, const double* coef, double* obtrig /* [P][6] scratch */,
                            int* cnt, int* blk_pairs /* [nblk] (column, ob) pairs of each block, or null */,
                            unsigned long long* npairs, hipStream_t s);
-hipError_t launch_sweep_gc(const GcSweepArgs& a, hipStream_t s);
-// the row-per-lane kernel on a state stored as float32 (member form, a.Xin / a.Xout point at float rows): the cycles
-// it serves (even M up to 104), whatever the alignment of the rows
-bool sweep_gc_lane_f32_supported(int M, long ye_stride, const double* Ye);
-hipError_t launch_sweep_gc_lane_f32(const GcSweepArgs& a, hipStream_t s);
+// elem: the element type a.Xin / a.Xout point at.  float32 is the member form on the row-per-lane kernel:
+// sweep_gc_serves says which cycles that is (an even M up to 104), whatever the alignment of the rows; float64 serves every cycle
+bool sweep_gc_serves(Elem elem, int M, long ye_stride, const double* Ye);
+hipError_t launch_sweep_gc(const GcSweepArgs& a, Elem elem, hipStream_t s);
 
 struct TransformArgs {
   const double* Xin;  // [rows][M] perturbations, or full members when fused_members
@@ -212,19 +216,17 @@ size_t diag_lds_bytes(int slots, int nb, int loc_mode);  // dynamic LDS of the d
 
 hipError_t launch_sweep(const SweepArgs& a, hipStream_t s);
 hipError_t launch_diag(const DiagArgs& a, hipStream_t s);
-hipError_t launch_transform(const TransformArgs& a, hipStream_t s);
+// elem: the element type a.Xin / a.Xout point at; float32 rows (the kernels of efa_transform_f32.hip) in member form only
+hipError_t launch_transform(const TransformArgs& a, Elem elem, hipStream_t s);
 bool transform_supported(int M);
 // RTPS fused into the member-form transform (k_transform_rtps): M <= 136, one launch with [T | w] in LDS
-hipError_t launch_transform_rtps(const TransformArgs& a, double alpha, hipStream_t s);
+hipError_t launch_transform_rtps(const TransformArgs& a, double alpha, Elem elem, hipStream_t s);
 bool transform_rtps_supported(int M);
-// posterior relaxation (efa_relax.hip): Tout = (1-alpha) T + alpha I; per-row sum of squared deviations; in-place relaxation of
-// rows (rtpp 0: RTPS from ss, 1: RTPP against the prior rows)
-// the member-form transforms on rows stored as float32 (efa_transform_f32.hip): Xin / Xout point at float rows
-hipError_t launch_transform_f32(const TransformArgs& a, hipStream_t s);
-hipError_t launch_transform_rtps_f32(const TransformArgs& a, double alpha, hipStream_t s);
 // float32 rows <-> the float64 workspace (efa_misc.hip): an exact widening copy, and posterior members rounded once
 hipError_t launch_widen_f32(size_t n, const float* X, double* out, hipStream_t s);
 hipError_t launch_narrow_f32(size_t n, const double* X, float* out, hipStream_t s);
+// posterior relaxation (efa_relax.hip): Tout = (1-alpha) T + alpha I; per-row sum of squared deviations; in-place relaxation of
+// rows (rtpp 0: RTPS from ss, 1: RTPP against the prior rows)
 hipError_t launch_relax_fold(int M, double alpha, const double* T, double* Tout, hipStream_t s);
 hipError_t launch_row_spread(long rows, int M, const double* X, double* ss, hipStream_t s);
 hipError_t launch_relax_rows(long rows, int M, int rtpp, double alpha, double* X, const double* ss, const double* prior,

@@ -406,9 +406,10 @@ std::array<int, 2> window_kinds(const efa_ctx* c, const ObsCall& a, long Rw, Rec
 // Phase A -> Phase B with no host round trip in between.
 int speculative_transform(efa_ctx* c, const ObsCall& a, const Window& win, SpecResult* out) {
   *out = SpecResult{};
-  if (!(a.spec.rows > 0 && win.direct && a.carry_T && c->n_active > 0 &&
-        (c->path == EFA_PATH_TRANSFORM || (c->path == EFA_PATH_AUTO && auto_transform(a.M, c->n_active, true)))))
-    return EFA_OK;
+  // the member form's plan as the state call will make it, with the transform this launch is about to leave
+  const StateRows r{a.spec.X, a.spec.post, Elem::f64, a.spec.rows, a.M};
+  const StatePlan plan = plan_state(c, true, r.elem, false, a.carry_T);
+  if (!(a.spec.rows > 0 && win.direct && plan.route == Route::transform)) return EFA_OK;
   hipStream_t s = c->stream;
   Interval& iv = c->state_iv[c->state_iv[0].pending ? 1 : 0];
   if (c->timing) harvest_state_interval(c, iv);  // (both intervals unread cannot happen across the wait below; kept correct anyway)
@@ -416,7 +417,7 @@ int speculative_transform(efa_ctx* c, const ObsCall& a, const Window& win, SpecR
   // the host -- what the host waits for -- the obs interval ends and this state interval begins
   EFA_HIP(hipEventRecord(iv.begin, s));
   c->obs_ends_at = iv.begin;
-  EFA_TRY(transform_with_relaxation(c, carried_transform(c, a.spec.X, nullptr, a.spec.post, nullptr, a.spec.rows, 1), &out->launches));
+  EFA_TRY(run_state_plan(c, plan, r, nullptr, nullptr, 0, 0, &out->launches));
   if (c->timing) EFA_HIP(hipEventRecord(iv.end, s));
   out->interval = &iv;
   out->launched = true;
@@ -503,7 +504,7 @@ int merge_window_into_block(efa_ctx* c, const ObsCall& a, const Window& win, Rec
       if (hi <= lo) continue;
       const TransformArgs t{a.Yw + (size_t)lo * M, a.ymw + lo, a.Yw + (size_t)lo * M, a.ymw + lo, hi - lo, M,
                             win.Wy + (size_t)(Pw + extra) * M, win.Wm + Pw + extra, 0};
-      EFA_HIP(launch_transform(t, s));
+      EFA_HIP(launch_transform(t, Elem::f64, s));
     }
     return EFA_OK;
   }

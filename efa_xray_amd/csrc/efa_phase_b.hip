@@ -1,5 +1,5 @@
-// Phase B, the state phase (efa_driver.h): the relaxation glue, the checks of the settings that bind a state phase, the column
-// grid, the sweeps and the two state calls (perturbation form and member form).
+// Phase B, the state phase (efa_driver.h): the checks of the settings that bind a state phase, the column grid, the plan of a state
+// call (plan_state), its launches (run_state_plan: relaxation glue, sweeps) and the state calls (perturbation and member form).
 #include "efa_driver.h"
 
 #include <cstring>
@@ -8,84 +8,35 @@ namespace efa_host {
 
 using namespace efa;
 
-// ---- posterior relaxation (RTPP / RTPS, efa_relax.hip) ----------------------------------------------------------
+// ---- posterior relaxation (RTPP / RTPS, efa_relax.hip): the standalone passes -------------------------------------------------
 // Applied only where a state phase writes the caller's state rows, and only when an ob was assimilated (otherwise the posterior
-// is returned exactly as without it).
+// is returned exactly as without it).  Float64 rows only: the plan sends float32 rows that need them through the workspace.
 namespace {
-bool relax_on(const efa_ctx* c) {
-  return c->relax_kind != EFA_RELAX_NONE && c->relax_alpha != 0.0 && c->P > 0 && c->n_active > 0;
-}
-// standalone passes, before the state phase: what the relaxation needs of the prior rows Xin (members or perturbations) -- RTPS
-// their spread, RTPP the rows themselves (copied when the state phase writes over them)
-int relax_prepare(efa_ctx* c, long rows, int M, const double* Xin, const double* Xout, const double** prior, long* nl) {
-  *prior = nullptr;
-  if (c->relax_kind == EFA_RELAX_RTPS) {
-    EFA_TRY(c->relax_ss.reserve((size_t)rows * sizeof(double)));
-    EFA_HIP(launch_row_spread(rows, M, Xin, c->relax_ss.as<double>(), c->stream));
+// core(), the state phase's pass(es) from prior rows to posterior rows, between the plan's standalone passes: before it what the
+// relaxation needs of the prior rows (members or perturbations) -- RTPS their spread, RTPP the rows themselves, copied when the
+// state phase writes over them -- and after it the relaxation, in place on the posterior rows
+template <class Core>
+int with_relaxation(efa_ctx* c, const StatePlan& p, const StateRows& r, long* nl, Core&& core) {
+  if (p.relax != Relax::standalone) return core();
+  const bool rtpp = c->relax_kind == EFA_RELAX_RTPP;
+  const double* prior = nullptr;
+  if (!rtpp) {
+    EFA_TRY(c->relax_ss.reserve((size_t)r.rows * sizeof(double)));
+    EFA_HIP(launch_row_spread(r.rows, r.M, r.in(), c->relax_ss.as<double>(), c->stream));
     ++*nl;
-    return EFA_OK;
-  }
-  const size_t bytes = (size_t)rows * M * sizeof(double);
-  const char *a = reinterpret_cast<const char*>(Xin), *b = reinterpret_cast<const char*>(Xout);
-  if (a + bytes <= b || b + bytes <= a) {
-    *prior = Xin;
+  } else if (r.disjoint()) {
+    prior = r.in();
   } else {
-    EFA_TRY(c->relax_prior.reserve(bytes));
-    EFA_HIP(hipMemcpyAsync(c->relax_prior.p, Xin, bytes, hipMemcpyDeviceToDevice, c->stream));
-    *prior = c->relax_prior.as<double>();
+    EFA_TRY(c->relax_prior.reserve(r.bytes()));
+    EFA_HIP(hipMemcpyAsync(c->relax_prior.p, r.prior, r.bytes(), hipMemcpyDeviceToDevice, c->stream));
+    prior = c->relax_prior.as<double>();
   }
-  return EFA_OK;
-}
-// ... and after it, in place on the posterior rows
-int relax_apply(efa_ctx* c, long rows, int M, double* Xout, const double* prior, long* nl) {
-  EFA_HIP(launch_relax_rows(rows, M, c->relax_kind == EFA_RELAX_RTPP ? 1 : 0, c->relax_alpha, Xout, c->relax_ss.as<double>(), prior,
-                            c->stream));
+  EFA_TRY(core());
+  EFA_HIP(launch_relax_rows(r.rows, r.M, rtpp ? 1 : 0, c->relax_alpha, r.out(), c->relax_ss.as<double>(), prior, c->stream));
   ++*nl;
   return EFA_OK;
 }
-// core(), the state phase's pass(es) from prior rows Xin to posterior rows Xout, between the standalone relaxation passes
-template <class Core>
-int with_relaxation(efa_ctx* c, long rows, int M, const double* Xin, double* Xout, long* nl, Core&& core) {
-  const bool relax = relax_on(c);
-  const double* prior = nullptr;
-  if (relax) EFA_TRY(relax_prepare(c, rows, M, Xin, Xout, &prior, nl));
-  EFA_TRY(core());
-  if (relax) EFA_TRY(relax_apply(c, rows, M, Xout, prior, nl));
-  return EFA_OK;
-}
 }  // namespace
-// The state transform through [T | w] (member or perturbation form, t.fused_members) with the relaxation: RTPP folded into T
-// (Xb' ((1-alpha) T + alpha I); xam as without it), RTPS fused into the member-form transform up to 136 members, the standalone
-// passes otherwise.  *nl = the launches it took.
-// f32: t.Xin / t.Xout point at float32 member rows (member form; the caller has made sure that no standalone pass is needed)
-int transform_with_relaxation(efa_ctx* c, TransformArgs t, long* nl, bool f32) {
-  hipStream_t s = c->stream;
-  const bool relax = relax_on(c);
-  *nl = 1;
-  if (relax && c->relax_kind == EFA_RELAX_RTPP) {
-    EFA_TRY(c->relax_T.reserve((size_t)t.M * t.M * sizeof(double)));
-    EFA_HIP(launch_relax_fold(t.M, c->relax_alpha, t.T, c->relax_T.as<double>(), s));
-    t.T = c->relax_T.as<double>();
-    *nl = 2;
-  } else if (relax && t.fused_members && transform_rtps_supported(t.M)) {
-    EFA_HIP(f32 ? launch_transform_rtps_f32(t, c->relax_alpha, s) : launch_transform_rtps(t, c->relax_alpha, s));
-    return EFA_OK;
-  } else if (relax) {
-    if (f32) return fail(EFA_ERR_INVALID, "the standalone relaxation passes have no float32 form");
-    return with_relaxation(c, t.nrows, t.M, t.Xin, t.Xout, nl, [&]() -> int {
-      EFA_HIP(launch_transform(t, s));
-      return EFA_OK;
-    });
-  }
-  EFA_HIP(f32 ? launch_transform_f32(t, s) : launch_transform(t, s));
-  return EFA_OK;
-}
-// [T | w] as Phase A left them: the carried identity rows behind the P obs rows of the working block
-TransformArgs carried_transform(const efa_ctx* c, const double* Xin, const double* xin, double* Xout, double* xout, long rows,
-                                int fused_members) {
-  return TransformArgs{Xin, xin, Xout, xout, rows, c->M, c->Yw.as<double>() + (size_t)c->P * c->M, c->ymw.as<double>() + c->P,
-                       fused_members};
-}
 
 // ---- adaptive inflation (efa_adapt.hip, the update fused into the one-pass GC sweep) ----------------------------------------
 // While a field is set, only the one-pass GC state sweep may run the state phase: it is the one that updates the field.
@@ -121,17 +72,42 @@ int check_vloc(const efa_ctx* c, int loc_mode, long P, long n_lead) {
 // the members -- where the transform is one.  Measured at 1e7 x 100 (profiles/r03_auto_path.txt): member form 8 obs 10.6 ms by
 // sweeps, 4.1 by the transform (48 obs: 16.9 vs 4.1); perturbation form 8 / 16 obs per sweep launch 3.4 / 4.5 ms vs 4.5.
 // Above 136 members the transform re-reads the state once per group of 64 output columns: the flops rule stays.
-bool auto_transform(int M, long n_active, bool member_form) {
+static bool auto_transform(int M, long n_active, bool member_form) {
   if (n_active <= 0) return false;
   if (M > 136) return n_active > M / 2;
   if (member_form) return true;
   return n_active > M / 8;
 }
-bool want_transform(const efa_ctx* c, bool member_form) {
-  if (!c->have_transform) return false;
-  if (c->path == EFA_PATH_TRANSFORM) return true;
-  if (c->path == EFA_PATH_SWEEP) return false;
-  return auto_transform(c->M, c->n_active, member_form);
+// Do float32 kernels serve the cycle (route and relaxation decided)?  The transform does, but for the standalone relaxation
+// passes; the one-pass GC sweep where its row-per-lane kernel applies and nothing is relaxed.
+static bool f32_kernels_serve(const efa_ctx* c, const StatePlan& p) {
+  if (p.route == Route::transform) return p.relax != Relax::standalone;
+  return p.route == Route::gc_onepass && p.relax == Relax::none && sweep_gc_serves(Elem::f32, c->M, c->ye_stride, c->ye_ptr);
+}
+
+// ---- the plan of a state phase (StatePlan, efa_driver.h) ----------------------------------------------------------------------
+// Every decision of a state call, from the settings and what the obs phase left; nothing is launched or written here.
+StatePlan plan_state(const efa_ctx* c, bool member_form, Elem elem, bool in_place, bool have_transform) {
+  StatePlan p;
+  p.member_form = member_form;
+  const bool any = c->P > 0 && c->n_active > 0;  // an ob was assimilated
+  const bool wide = c->M > 136;                  // the transform runs as column groups (k_transform_wide)
+  if (any && have_transform &&
+      (c->path == EFA_PATH_TRANSFORM || (c->path == EFA_PATH_AUTO && auto_transform(c->M, c->n_active, member_form))))
+    p.route = Route::transform;
+  else if (c->loc_mode == EFA_LOC_GC && c->gc_onepass && c->n_active > 0)  // every ensemble size the library accepts (2..256)
+    p.route = Route::gc_onepass;
+  if (c->relax_kind != EFA_RELAX_NONE && c->relax_alpha != 0.0 && any) {
+    if (p.route != Route::transform) p.relax = Relax::standalone;
+    else if (c->relax_kind == EFA_RELAX_RTPP) p.relax = Relax::folded;
+    else p.relax = (member_form && transform_rtps_supported(c->M)) ? Relax::fused : Relax::standalone;
+  }
+  if (elem == Elem::f32) {
+    if (!f32_kernels_serve(c, p)) p.ws_copies = (p.route == Route::transform && wide) ? 2 : 1;
+    // float32 ONLY reads a copy of the prior (column groups re-read rows other groups write); float64 in place KEEPS that hazard, DESIGN.md 7g
+    p.copy_prior = p.ws_copies == 0 && p.route == Route::transform && wide && in_place;
+  }
+  return p;
 }
 
 // ---- the column grid of a localised state phase (ColumnGrid, efa_ctx.h) -------------------------------------------------------
@@ -204,9 +180,9 @@ int read_gc_pairs(efa_ctx* c) {
 
 namespace {
 // ---- Phase B, localised, one pass (efa_gcsweep.hip) --------------------------------------
-// f32: Xp_in / Xp_out point at float32 member rows (member form, the row-per-lane kernel)
-int state_gc_onepass(efa_ctx* c, const double* xm_in, const double* Xp_in, double* xm_out, double* Xp_out, long ncol, long n_lead,
-                     int fused_members, bool f32 = false) {
+// r: perturbation rows with their means xm_in / xm_out, or member rows (fused_members) of either element type
+int state_gc_onepass(efa_ctx* c, const StateRows& r, const double* xm_in, double* xm_out, long ncol, long n_lead, int fused_members,
+                     long* nl) {
   const int M = c->M;
   const long P = c->P;
   hipStream_t s = c->stream;
@@ -261,16 +237,16 @@ int state_gc_onepass(efa_ctx* c, const double* xm_in, const double* Xp_in, doubl
   g.coef = c->coef.as<double>();
   g.Ye = c->ye_ptr;
   g.ye_stride = c->ye_stride;
-  g.Xin = Xp_in;
+  g.Xin = r.in();
   g.xin = xm_in;
-  g.Xout = Xp_out;
+  g.Xout = r.out();
   g.xout = xm_out;
   g.fused_members = fused_members;
   if (c->ai_field) {  // the per-ob scalars of the inflation update, from Phase A's records and diagnostics
     EFA_TRY(c->ai_ob.reserve((size_t)(P ? P : 1) * 4 * sizeof(double)));
     EFA_HIP(launch_adapt_obs(P, M, c->coef.as<double>(), c->d_prior_var, c->ob_err, c->ye_ptr, c->ye_stride,
                              c->ai_ob.as<double>(), s));
-    c->state_launches++;
+    ++*nl;
     g.infl = c->ai_field;
     g.adapt_ob = c->ai_ob.as<double>();
     g.infl_lower = c->ai_lower;
@@ -282,19 +258,17 @@ int state_gc_onepass(efa_ctx* c, const double* xm_in, const double* Xp_in, doubl
     g.ob_vert = vl_obvert(c);
     g.ob_vhw = vl_obvhw(c);
   }
-  EFA_HIP(f32 ? launch_sweep_gc_lane_f32(g, s) : launch_sweep_gc(g, s));
-  c->state_launches++;
+  EFA_HIP(launch_sweep_gc(g, r.elem, s));
+  ++*nl;
   return EFA_OK;
 }
 
-// ---- Phase B (perturbation form) ------------------------------------------
-int state_sweeps(efa_ctx* c, long rows, const double* xm_in, const double* Xp_in, double* xm_out, double* Xp_out,
-                 long ncol) {
+// ---- Phase B per batch of obs (perturbation form, float64) ------------------------------------------
+int state_sweeps(efa_ctx* c, long rows, const double* xm_in, const double* Xp_in, double* xm_out, double* Xp_out, long ncol,
+                 long* nl) {
   const int M = c->M;
   const long P = c->P;
   hipStream_t s = c->stream;
-  if (c->loc_mode == EFA_LOC_GC && c->gc_onepass && c->n_active > 0)  // every ensemble size the library accepts (2..256)
-    return state_gc_onepass(c, xm_in, Xp_in, xm_out, Xp_out, ncol, rows / ncol, 0);
   const long B = effective_batch(c, M);
   bool first = true;
   for (long b0 = 0; b0 < P; b0 += B) {
@@ -325,7 +299,7 @@ int state_sweeps(efa_ctx* c, long rows, const double* xm_in, const double* Xp_in
       a.taper_mode = kTaperNone;
     }
     EFA_HIP(launch_sweep(a, s));
-    c->state_launches++;
+    ++*nl;
     first = false;
   }
   if (first && Xp_out != Xp_in) {  // nothing assimilated: posterior == prior
@@ -335,15 +309,81 @@ int state_sweeps(efa_ctx* c, long rows, const double* xm_in, const double* Xp_in
   return EFA_OK;
 }
 
-// ---- the two state calls ------------------------------------------------------------------------------------------------------
-// start of a state-phase call, once its arguments are checked: the previous interval is read, the counters cleared
-void reset_state_phase(efa_ctx* c) {
-  harvest_state_ms(c);
-  c->state_ms = 0.0;
-  c->state_launches = 0;
-  c->path_taken = EFA_PATH_SWEEP;
+}  // namespace
+
+// ---- the executor: the launches of a plan ---------------------------------------------------------------------------------------
+// xm_in / xm_out: the means of the perturbation form (null in member form).  *launches: the state-phase launches it issued.
+int run_state_plan(efa_ctx* c, const StatePlan& p, const StateRows& r, const double* xm_in, double* xm_out, long ncol, long n_lead,
+                   long* launches) {
+  hipStream_t s = c->stream;
+  long& nl = *launches;
+  nl = 0;
+  if (p.ws_copies) {  // float32 rows without a float32 kernel: widened, the same plan on the float64 workspace, rounded once
+    const size_t n = r.count();
+    EFA_TRY(c->f32_ws.reserve((size_t)p.ws_copies * n * sizeof(double)));
+    double* ws = c->f32_ws.as<double>();
+    const StateRows w{ws, p.ws_copies == 2 ? ws + n : ws, Elem::f64, r.rows, r.M};
+    StatePlan q = p;
+    q.ws_copies = 0;
+    EFA_HIP(launch_widen_f32(n, static_cast<const float*>(r.prior), ws, s));
+    EFA_TRY(run_state_plan(c, q, w, xm_in, xm_out, ncol, n_lead, launches));
+    EFA_HIP(launch_narrow_f32(n, w.out(), static_cast<float*>(r.post), s));
+    nl += 2;
+    return EFA_OK;
+  }
+  if (p.route == Route::transform) {
+    // through [T | w]; RTPP folded into T: Xb' ((1-alpha) T + alpha I), xam as without it
+    StateRows in = r;
+    if (p.copy_prior) {
+      EFA_TRY(c->f32_prior.reserve(r.bytes()));
+      EFA_HIP(hipMemcpyAsync(c->f32_prior.p, r.prior, r.bytes(), hipMemcpyDeviceToDevice, s));
+      in.prior = c->f32_prior.p;
+    }
+    // [T | w] as Phase A left them: the carried identity rows behind the P obs rows of the working block
+    TransformArgs t{in.in(), xm_in, in.out(), xm_out, in.rows, c->M, c->Yw.as<double>() + (size_t)c->P * c->M,
+                    c->ymw.as<double>() + c->P, p.member_form ? 1 : 0};
+    if (p.relax == Relax::fused) {
+      EFA_HIP(launch_transform_rtps(t, c->relax_alpha, r.elem, s));
+      ++nl;
+    } else {
+      if (p.relax == Relax::folded) {
+        EFA_TRY(c->relax_T.reserve((size_t)t.M * t.M * sizeof(double)));
+        EFA_HIP(launch_relax_fold(t.M, c->relax_alpha, t.T, c->relax_T.as<double>(), s));
+        t.T = c->relax_T.as<double>();
+        ++nl;
+      }
+      EFA_TRY(with_relaxation(c, p, r, &nl, [&]() -> int {  // (r: with the standalone passes no copy of the prior stands in)
+        EFA_HIP(launch_transform(t, r.elem, s));
+        ++nl;
+        return EFA_OK;
+      }));
+    }
+  } else {
+    EFA_TRY(with_relaxation(c, p, r, &nl, [&]() -> int {
+      if (p.route == Route::gc_onepass)  // localised: prior -> posterior in one read + one write of the state
+        return state_gc_onepass(c, r, xm_in, xm_out, ncol, n_lead, p.member_form ? 1 : 0, &nl);
+      if (!p.member_form) return state_sweeps(c, r.rows, xm_in, r.in(), xm_out, r.out(), ncol, &nl);
+      // member form: form the perturbations in the posterior rows, sweep them in place, rebuild the members
+      EFA_TRY(c->xm_ws.reserve((size_t)r.rows * sizeof(double)));
+      double* xm = c->xm_ws.as<double>();
+      EFA_HIP(launch_form_perts(r.rows, r.M, r.in(), 1.0, xm, r.out(), s));
+      EFA_TRY(state_sweeps(c, r.rows, xm, r.out(), xm, r.out(), ncol, &nl));
+      EFA_HIP(launch_posterior(r.rows, r.M, xm, r.out(), r.out(), s));
+      return EFA_OK;
+    }));
+  }
+  return EFA_OK;
 }
 
+// what a state call reports (efa_last_timing, option "f32_native"), from its plan and the launches it took
+void report_state_call(efa_ctx* c, const StatePlan& p, Elem elem, long launches) {
+  c->state_launches = launches;
+  c->path_taken = p.route == Route::transform ? EFA_PATH_TRANSFORM : EFA_PATH_SWEEP;
+  if (elem == Elem::f32) c->f32_native = p.ws_copies == 0 ? 1 : 0;
+}
+
+namespace {
+// ---- the state calls ------------------------------------------------------------------------------------------------------------
 // What both forms do before their first launch: the checks, the counters, and -- once there is work to do (rows > 0) -- the grid of
 // a localised call on the device and the begin of the state interval.  ptrs_ok: no state pointer of the form is null.
 int begin_state_call(efa_ctx* c, const char* who, long rows, int M, bool ptrs_ok, const double* grid_lat, const double* grid_lon,
@@ -353,13 +393,26 @@ int begin_state_call(efa_ctx* c, const char* who, long rows, int M, bool ptrs_ok
   if (rows < 0) return fail(EFA_ERR_INVALID, "negative row count");
   EFA_TRY(check_adaptive(c, c->loc_mode, rows));
   EFA_TRY(check_vloc(c, c->loc_mode, c->P, n_lead));
-  reset_state_phase(c);
+  harvest_state_ms(c);  // the arguments are checked: the previous interval is read, the counters cleared
+  c->state_ms = 0.0;
+  c->state_launches = 0;
+  c->path_taken = EFA_PATH_SWEEP;
   if (rows == 0) return EFA_OK;
   if (!ptrs_ok) return fail(EFA_ERR_INVALID, "null state pointer");
   EFA_TRY(check_grid(c->loc_mode, grid_lat, grid_lon, ncol, n_lead, rows));
   if (c->loc_mode == EFA_LOC_GC && !o.grid_current) EFA_TRY(c->grid.upload(c->stream, grid_lat, grid_lon, ncol));
   if (c->timing && o.timed) EFA_HIP(hipEventRecord(c->state_iv[0].begin, c->stream));
   return EFA_OK;
+}
+
+// ... and after it: plan, launches, report
+int plan_and_run(efa_ctx* c, bool member_form, const StateRows& r, const double* xm_in, double* xm_out, long ncol, long n_lead,
+                 const StateCall& o) {
+  const StatePlan plan = plan_state(c, member_form, r.elem, r.in_place(), c->have_transform);
+  long launches = 0;
+  EFA_TRY(run_state_plan(c, plan, r, xm_in, xm_out, ncol, n_lead, &launches));
+  report_state_call(c, plan, r.elem, launches);
+  return end_state_call(c, c->state_iv[0], o.timed);
 }
 
 }  // namespace
@@ -378,97 +431,22 @@ int state_phase(efa_ctx* c, long rows, int M, const double* xm_in, const double*
                 const double* grid_lat, const double* grid_lon, long ncol, long n_lead, const StateCall& o) {
   EFA_TRY(begin_state_call(c, "efa_state_phase_dev", rows, M, xm_in && Xp_in && xm_out && Xp_out, grid_lat, grid_lon, ncol, n_lead, o));
   if (rows == 0) return EFA_OK;
-  if (c->P > 0 && c->n_active > 0 && want_transform(c, false)) {
-    EFA_TRY(transform_with_relaxation(c, carried_transform(c, Xp_in, xm_in, Xp_out, xm_out, rows, 0), &c->state_launches));
-    c->path_taken = EFA_PATH_TRANSFORM;
-  } else {
-    EFA_TRY(with_relaxation(c, rows, M, Xp_in, Xp_out, &c->state_launches,
-                            [&] { return state_sweeps(c, rows, xm_in, Xp_in, xm_out, Xp_out, ncol); }));
-  }
-  return end_state_call(c, c->state_iv[0], o.timed);
+  return plan_and_run(c, false, StateRows{Xp_in, Xp_out, Elem::f64, rows, M}, xm_in, xm_out, ncol, n_lead, o);
 }
 
-namespace {
-// the member form's launches, from prior members X_dev to posterior members post_dev
-int state_cycle_core(efa_ctx* c, long rows, int M, const double* X_dev, double* post_dev, long ncol, long n_lead) {
-  hipStream_t s = c->stream;
-  if (c->P > 0 && c->n_active > 0 && want_transform(c, true)) {
-    EFA_TRY(transform_with_relaxation(c, carried_transform(c, X_dev, nullptr, post_dev, nullptr, rows, 1), &c->state_launches));
-    c->path_taken = EFA_PATH_TRANSFORM;
-  } else if (c->loc_mode == EFA_LOC_GC && c->gc_onepass && c->n_active > 0) {
-    // localised: prior members -> posterior members in one read + one write of the state
-    EFA_TRY(with_relaxation(c, rows, M, X_dev, post_dev, &c->state_launches,
-                            [&] { return state_gc_onepass(c, nullptr, X_dev, nullptr, post_dev, ncol, n_lead, 1); }));
-  } else {
-    EFA_TRY(with_relaxation(c, rows, M, X_dev, post_dev, &c->state_launches, [&]() -> int {
-      EFA_TRY(c->xm_ws.reserve((size_t)rows * sizeof(double)));
-      double* xm = c->xm_ws.as<double>();
-      EFA_HIP(launch_form_perts(rows, M, X_dev, 1.0, xm, post_dev, s));
-      EFA_TRY(state_sweeps(c, rows, xm, post_dev, xm, post_dev, ncol));
-      EFA_HIP(launch_posterior(rows, M, xm, post_dev, post_dev, s));
-      return EFA_OK;
-    }));
-  }
-  return EFA_OK;
-}
-}  // namespace
-
-// member form (efa_state_cycle_dev)
-int state_cycle(efa_ctx* c, long rows, int M, const double* X_dev, double* post_dev, const double* grid_lat,
-                const double* grid_lon, long ncol, long n_lead, const StateCall& o) {
-  EFA_TRY(begin_state_call(c, "efa_state_cycle_dev", rows, M, X_dev && post_dev, grid_lat, grid_lon, ncol, n_lead, o));
-  if (rows == 0) return EFA_OK;
-  EFA_TRY(state_cycle_core(c, rows, M, X_dev, post_dev, ncol, n_lead));
-  return end_state_call(c, c->state_iv[0], o.timed);
-}
-
-// member form on a state stored as float32 (efa_state_cycle_f32_dev): posterior = fl32(F(widen(prior))), F the
-// float64 member form above.  The transform (plain, RTPP folded, RTPS fused) and the row-per-lane one-pass GC sweep read and write
-// the float rows themselves; every other route widens the rows into a float64 workspace, runs the float64 launches on it as they
-// are and rounds the posterior members once on the way out.
-int state_cycle_f32(efa_ctx* c, long rows, int M, const float* X_dev, float* post_dev, const double* grid_lat,
-                    const double* grid_lon, long ncol, long n_lead, const StateCall& o) {
-  if (c->ai_field)
+// member form (efa_state_cycle_dev, efa_state_cycle_f32_dev).  On a state stored as float32 posterior =
+// fl32(F(widen(prior))), F the float64 member form: by the float32 kernels where the plan finds them, else through the workspace.
+int state_cycle(efa_ctx* c, const StateRows& r, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
+                const StateCall& o) {
+  const bool f32 = r.elem == Elem::f32;
+  if (f32 && c->ai_field)
     return fail(EFA_ERR_INVALID, "efa_state_cycle_f32_dev: an adaptive-inflation field is set (its update is float64 only)");
-  if (((reinterpret_cast<uintptr_t>(X_dev) | reinterpret_cast<uintptr_t>(post_dev)) & 3u) != 0)
+  if (f32 && ((reinterpret_cast<uintptr_t>(r.prior) | reinterpret_cast<uintptr_t>(r.post)) & 3u) != 0)
     return fail(EFA_ERR_INVALID, "efa_state_cycle_f32_dev: state pointers must be 4-byte aligned");
-  EFA_TRY(begin_state_call(c, "efa_state_cycle_f32_dev", rows, M, X_dev && post_dev, grid_lat, grid_lon, ncol, n_lead, o));
-  if (rows == 0) return EFA_OK;
-  hipStream_t s = c->stream;
-  const size_t n = (size_t)rows * M;
-  const bool relax = relax_on(c);
-  const bool transform = c->P > 0 && c->n_active > 0 && want_transform(c, true);
-  const bool wide = M > 136;  // the column groups of k_transform_wide re-read rows that other groups write: never in place
-  const char *a = reinterpret_cast<const char*>(X_dev), *b = reinterpret_cast<const char*>(post_dev);
-  const bool disjoint = a + n * sizeof(float) <= b || b + n * sizeof(float) <= a;
-  // as the float64 shell passes them: the kernels take the element type from the launch, not from the pointer
-  const double* Xd = reinterpret_cast<const double*>(X_dev);
-  double* Pd = reinterpret_cast<double*>(post_dev);
-  c->f32_native = 0;
-  if (transform && (!relax || c->relax_kind == EFA_RELAX_RTPP || transform_rtps_supported(M))) {
-    if (wide && !disjoint) {
-      EFA_TRY(c->f32_prior.reserve(n * sizeof(float)));
-      EFA_HIP(hipMemcpyAsync(c->f32_prior.p, X_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-      Xd = c->f32_prior.as<double>();
-    }
-    EFA_TRY(transform_with_relaxation(c, carried_transform(c, Xd, nullptr, Pd, nullptr, rows, 1), &c->state_launches, true));
-    c->path_taken = EFA_PATH_TRANSFORM;
-    c->f32_native = 1;
-  } else if (!transform && !relax && c->loc_mode == EFA_LOC_GC && c->gc_onepass && c->n_active > 0 &&
-             sweep_gc_lane_f32_supported(M, c->ye_stride, c->ye_ptr)) {
-    EFA_TRY(state_gc_onepass(c, nullptr, Xd, nullptr, Pd, ncol, n_lead, 1, true));
-    c->f32_native = 1;
-  } else {
-    const bool two = transform && wide;
-    EFA_TRY(c->f32_ws.reserve((two ? 2 : 1) * n * sizeof(double)));
-    double* ws = c->f32_ws.as<double>();
-    double* out = two ? ws + n : ws;
-    EFA_HIP(launch_widen_f32(n, X_dev, ws, s));
-    EFA_TRY(state_cycle_core(c, rows, M, ws, out, ncol, n_lead));
-    EFA_HIP(launch_narrow_f32(n, out, post_dev, s));
-    c->state_launches += 2;
-  }
-  return end_state_call(c, c->state_iv[0], o.timed);
+  EFA_TRY(begin_state_call(c, f32 ? "efa_state_cycle_f32_dev" : "efa_state_cycle_dev", r.rows, r.M, r.prior && r.post, grid_lat,
+                           grid_lon, ncol, n_lead, o));
+  if (r.rows == 0) return EFA_OK;
+  return plan_and_run(c, true, r, nullptr, nullptr, ncol, n_lead, o);
 }
 
 }  // namespace efa_host

@@ -163,17 +163,14 @@ int issue_state_phase(const Pipe& p, long i, int loc_mode, const double* grid_la
     EFA_TRY(c->grid.take_slice(s, c->st.grid.as<double>(), k.ncol, k.lo(i), cw));
   }
   EFA_HIP(hipEventRecord(p.ev(i, kSt0), s));
-  const bool f32 = k.esz == sizeof(float);
-  double* X = reinterpret_cast<double*>(p.slot(i));
-  float* X32 = reinterpret_cast<float*>(p.slot(i));
+  const StateRows X{p.slot(i), p.slot(i), k.esz == sizeof(float) ? Elem::f32 : Elem::f64, rows, k.M};
   // the chunk loop keeps its own events: the context's per-call timing would make every state phase wait for its end
   StateCall sc;
   sc.grid_current = true;
   sc.timed = false;
   const double *glat = loc_mode == EFA_LOC_GC ? grid_lat + k.lo(i) : nullptr, *glon = loc_mode == EFA_LOC_GC ? grid_lon + k.lo(i) : nullptr;
   const long ncol = loc_mode == EFA_LOC_GC ? cw : rows, n_lead = loc_mode == EFA_LOC_GC ? k.n_lead : 1;
-  if (f32) EFA_TRY(state_cycle_f32(c, rows, k.M, X32, X32, glat, glon, ncol, n_lead, sc));
-  else EFA_TRY(state_cycle(c, rows, k.M, X, X, glat, glon, ncol, n_lead, sc));
+  EFA_TRY(state_cycle(c, X, glat, glon, ncol, n_lead, sc));
   *launches += c->state_launches;
   EFA_HIP(hipEventRecord(p.ev(i, kSt1), s));
   return EFA_OK;

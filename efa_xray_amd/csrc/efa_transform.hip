@@ -703,43 +703,48 @@ hipError_t transform_wide_nu(const TransformArgs& a, hipStream_t s) {
 
 }  // namespace
 
+// the float32 kernels' dispatch, compiled in efa_transform_f32.hip
+hipError_t transform_rows_f32(const TransformArgs& a, hipStream_t s);
+hipError_t transform_rtps_rows_f32(const TransformArgs& a, double alpha, hipStream_t s);
+
 #ifndef EFA_TRANSFORM_F32
 // one launch with the whole [T | w] image in LDS up to M = 136; column groups above (k_transform_wide) up to 256
 bool transform_supported(int M) { return M >= 2 && M <= 256; }
 
 bool transform_rtps_supported(int M) { return M >= 2 && M <= 136; }
 
-// member form only (Xin prior members, Xout posterior members)
-hipError_t launch_transform_rtps(const TransformArgs& a, double alpha, hipStream_t s) {
-  if (!transform_rtps_supported(a.M) || !a.fused_members) return hipErrorInvalidValue;
-  if ((reinterpret_cast<uintptr_t>(a.Xin) & 7u) != 0) return hipErrorInvalidValue;
+// what a launch asks of its rows: float64 rows 8-byte aligned; float32 rows 4-byte aligned and in member form (a float32 state
+// has no perturbation form)
+static bool rows_ok(const TransformArgs& a, Elem elem) {
+  const uintptr_t in = reinterpret_cast<uintptr_t>(a.Xin), out = reinterpret_cast<uintptr_t>(a.Xout);
+  return elem == Elem::f32 ? (a.fused_members && ((in | out) & 3u) == 0) : (in & 7u) == 0;
+}
+
+// The launchers are where a.Xin / a.Xout get their element type: elem picks the kernels that read them as float or as double rows.
+// T, w and every number computed are float64 either way.  (RTPS: member form only, Xin prior members, Xout posterior members.)
+hipError_t launch_transform_rtps(const TransformArgs& a, double alpha, Elem elem, hipStream_t s) {
+  if (!transform_rtps_supported(a.M) || !a.fused_members || !rows_ok(a, elem)) return hipErrorInvalidValue;
   if (a.nrows <= 0) return hipSuccess;
+  if (elem == Elem::f32) return transform_rtps_rows_f32(a, alpha, s);
   return dispatch_width((a.M + 7) / 8, WidthRange<1, 17>{}, [&](auto nu) { return transform_rtps_nu<nu>(a, alpha, s); });
 }
 
-hipError_t launch_transform(const TransformArgs& a, hipStream_t s) {
-  if (!transform_supported(a.M)) return hipErrorInvalidValue;
-  if ((reinterpret_cast<uintptr_t>(a.Xin) & 7u) != 0) return hipErrorInvalidValue;
+hipError_t launch_transform(const TransformArgs& a, Elem elem, hipStream_t s) {
+  if (!transform_supported(a.M) || !rows_ok(a, elem)) return hipErrorInvalidValue;
   if (a.nrows <= 0) return hipSuccess;
+  if (elem == Elem::f32) return transform_rows_f32(a, s);
   const int nu = (a.M + 7) / 8;
   if (nu <= 17) return dispatch_width(nu, WidthRange<1, 17>{}, [&](auto n) { return transform_nu<n>(a, s); });
   return dispatch_width(nu, WidthRange<18, 32>{}, [&](auto n) { return transform_wide_nu<n>(a, s); });
 }
 
 #else
-// ---- the same kernels on rows stored as float32 (efa_transform_f32.hip) ---------------------------------------
-// a.Xin / a.Xout point at float rows (4-byte aligned), member form only; T, w and every number computed stay float64.
-hipError_t launch_transform_rtps_f32(const TransformArgs& a, double alpha, hipStream_t s) {
-  if (!transform_rtps_supported(a.M) || !a.fused_members) return hipErrorInvalidValue;
-  if ((reinterpret_cast<uintptr_t>(a.Xin) & 3u) != 0 || (reinterpret_cast<uintptr_t>(a.Xout) & 3u) != 0) return hipErrorInvalidValue;
-  if (a.nrows <= 0) return hipSuccess;
+// ---- the same kernels on rows stored as float32 (efa_transform_f32.hip), behind the checks of the launchers -------
+hipError_t transform_rtps_rows_f32(const TransformArgs& a, double alpha, hipStream_t s) {
   return dispatch_width((a.M + 7) / 8, WidthRange<1, 17>{}, [&](auto nu) { return transform_rtps_nu<nu, float>(a, alpha, s); });
 }
 
-hipError_t launch_transform_f32(const TransformArgs& a, hipStream_t s) {
-  if (!transform_supported(a.M) || !a.fused_members) return hipErrorInvalidValue;
-  if ((reinterpret_cast<uintptr_t>(a.Xin) & 3u) != 0 || (reinterpret_cast<uintptr_t>(a.Xout) & 3u) != 0) return hipErrorInvalidValue;
-  if (a.nrows <= 0) return hipSuccess;
+hipError_t transform_rows_f32(const TransformArgs& a, hipStream_t s) {
   const int nu = (a.M + 7) / 8;
   if (nu <= 17) return dispatch_width(nu, WidthRange<1, 17>{}, [&](auto n) { return transform_nu_f32<n>(a, s); });
   return dispatch_width(nu, WidthRange<18, 32>{}, [&](auto n) { return transform_wide_nu<n, float>(a, s); });
