@@ -245,9 +245,9 @@ struct efa_ctx {
                                   // behind the sweep would hold the host until the sweep is done, cycle after cycle)
   ColumnGrid grid;
   DevBuf xm_ws;       // means for efa_state_cycle_dev
+  DevBuf wide_prior;  // a copy of the prior rows for the in-place transform above 136 members [rows][M] of the rows' element type
   // --- float32 state storage (efa_state_cycle_f32_dev) ---------------------------------------
   DevBuf f32_ws;      // the float64 workspace of the routes without a float32 kernel [rows][M] (twice that above 136 members)
-  DevBuf f32_prior;   // a copy of the float32 prior for the in-place transform above 136 members [rows][M] floats
   long f32_native = 0;  // read-only option "f32_native": the last float32 state call ran on the float rows themselves
   // --- posterior relaxation (efa_ctx_set_relaxation) ------------------------------------------------------
   int relax_kind = EFA_RELAX_NONE;

@@ -70,6 +70,8 @@ struct StateRows {
     return a + bytes() <= b || b + bytes() <= a;
   }
   bool in_place() const { return !disjoint(); }
+  // in place means over the prior exactly: a posterior that overlaps the prior without coinciding with it is served by no kernel
+  bool partial_overlap() const { return in_place() && prior != post; }
   // As the kernel argument structs carry rows of either type: the launchers that take `elem` (launch_transform, launch_transform_rtps,
   // launch_sweep_gc) pick the kernels that read them.  Every other pass is float64 only, and no plan sends float32 rows there.
   const double* in() const { return static_cast<const double*>(prior); }
@@ -86,7 +88,7 @@ struct StatePlan {
   Relax relax = Relax::none;
   bool member_form = true;
   int ws_copies = 0;        // float32 rows: 0 the kernels read and write the float rows; else copies of the state in the float64 workspace
-  bool copy_prior = false;  // float32 rows, in place, transform above 136 members: it reads a copy of the prior
+  bool copy_prior = false;  // in place, transform above 136 members, no workspace: it reads a copy of the prior
 };
 StatePlan plan_state(const efa_ctx* c, bool member_form, Elem elem, bool in_place, bool have_transform);
 int run_state_plan(efa_ctx* c, const StatePlan& p, const StateRows& r, const double* xm_in, double* xm_out, long ncol, long n_lead,

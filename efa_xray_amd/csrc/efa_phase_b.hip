@@ -102,11 +102,10 @@ StatePlan plan_state(const efa_ctx* c, bool member_form, Elem elem, bool in_plac
     else if (c->relax_kind == EFA_RELAX_RTPP) p.relax = Relax::folded;
     else p.relax = (member_form && transform_rtps_supported(c->M)) ? Relax::fused : Relax::standalone;
   }
-  if (elem == Elem::f32) {
-    if (!f32_kernels_serve(c, p)) p.ws_copies = (p.route == Route::transform && wide) ? 2 : 1;
-    // float32 ONLY reads a copy of the prior (column groups re-read rows other groups write); float64 in place KEEPS that hazard, DESIGN.md 7g
-    p.copy_prior = p.ws_copies == 0 && p.route == Route::transform && wide && in_place;
-  }
+  if (elem == Elem::f32 && !f32_kernels_serve(c, p)) p.ws_copies = (p.route == Route::transform && wide) ? 2 : 1;
+  // in place the column groups would re-read rows that other groups have written: they read a copy of the prior;
+  // either element type, either form (the workspace never runs that transform in place)
+  p.copy_prior = p.ws_copies == 0 && p.route == Route::transform && wide && in_place;
   return p;
 }
 
@@ -335,9 +334,9 @@ int run_state_plan(efa_ctx* c, const StatePlan& p, const StateRows& r, const dou
     // through [T | w]; RTPP folded into T: Xb' ((1-alpha) T + alpha I), xam as without it
     StateRows in = r;
     if (p.copy_prior) {
-      EFA_TRY(c->f32_prior.reserve(r.bytes()));
-      EFA_HIP(hipMemcpyAsync(c->f32_prior.p, r.prior, r.bytes(), hipMemcpyDeviceToDevice, s));
-      in.prior = c->f32_prior.p;
+      EFA_TRY(c->wide_prior.reserve(r.bytes()));
+      EFA_HIP(hipMemcpyAsync(c->wide_prior.p, r.prior, r.bytes(), hipMemcpyDeviceToDevice, s));
+      in.prior = c->wide_prior.p;
     }
     // [T | w] as Phase A left them: the carried identity rows behind the P obs rows of the working block
     TransformArgs t{in.in(), xm_in, in.out(), xm_out, in.rows, c->M, c->Yw.as<double>() + (size_t)c->P * c->M,
@@ -385,9 +384,10 @@ void report_state_call(efa_ctx* c, const StatePlan& p, Elem elem, long launches)
 namespace {
 // ---- the state calls ------------------------------------------------------------------------------------------------------------
 // What both forms do before their first launch: the checks, the counters, and -- once there is work to do (rows > 0) -- the grid of
-// a localised call on the device and the begin of the state interval.  ptrs_ok: no state pointer of the form is null.
-int begin_state_call(efa_ctx* c, const char* who, long rows, int M, bool ptrs_ok, const double* grid_lat, const double* grid_lon,
-                     long ncol, long n_lead, const StateCall& o) {
+// a localised call on the device and the begin of the state interval.  ptrs_ok: no state pointer of the form is null; partial_overlap:
+// an output range of the form overlaps its input range without coinciding with it.
+int begin_state_call(efa_ctx* c, const char* who, long rows, int M, bool ptrs_ok, bool partial_overlap, const double* grid_lat,
+                     const double* grid_lon, long ncol, long n_lead, const StateCall& o) {
   if (!c->have_traj) return fail(EFA_ERR_INVALID, "%s called before efa_obs_phase_dev", who);
   if (M != c->M) return fail(EFA_ERR_INVALID, "M=%d differs from the obs phase's M=%d", M, c->M);
   if (rows < 0) return fail(EFA_ERR_INVALID, "negative row count");
@@ -399,6 +399,8 @@ int begin_state_call(efa_ctx* c, const char* who, long rows, int M, bool ptrs_ok
   c->path_taken = EFA_PATH_SWEEP;
   if (rows == 0) return EFA_OK;
   if (!ptrs_ok) return fail(EFA_ERR_INVALID, "null state pointer");
+  if (partial_overlap)
+    return fail(EFA_ERR_INVALID, "%s: the posterior rows overlap the prior rows without coinciding with them (in place means the same address)", who);
   EFA_TRY(check_grid(c->loc_mode, grid_lat, grid_lon, ncol, n_lead, rows));
   if (c->loc_mode == EFA_LOC_GC && !o.grid_current) EFA_TRY(c->grid.upload(c->stream, grid_lat, grid_lon, ncol));
   if (c->timing && o.timed) EFA_HIP(hipEventRecord(c->state_iv[0].begin, c->stream));
@@ -429,9 +431,11 @@ int end_state_call(efa_ctx* c, Interval& iv, bool timed, bool end_recorded) {
 // perturbation form (efa_state_phase_dev)
 int state_phase(efa_ctx* c, long rows, int M, const double* xm_in, const double* Xp_in, double* xm_out, double* Xp_out,
                 const double* grid_lat, const double* grid_lon, long ncol, long n_lead, const StateCall& o) {
-  EFA_TRY(begin_state_call(c, "efa_state_phase_dev", rows, M, xm_in && Xp_in && xm_out && Xp_out, grid_lat, grid_lon, ncol, n_lead, o));
+  const StateRows r{Xp_in, Xp_out, Elem::f64, rows, M}, means{xm_in, xm_out, Elem::f64, rows, 1};
+  EFA_TRY(begin_state_call(c, "efa_state_phase_dev", rows, M, xm_in && Xp_in && xm_out && Xp_out,
+                           r.partial_overlap() || means.partial_overlap(), grid_lat, grid_lon, ncol, n_lead, o));
   if (rows == 0) return EFA_OK;
-  return plan_and_run(c, false, StateRows{Xp_in, Xp_out, Elem::f64, rows, M}, xm_in, xm_out, ncol, n_lead, o);
+  return plan_and_run(c, false, r, xm_in, xm_out, ncol, n_lead, o);
 }
 
 // member form (efa_state_cycle_dev, efa_state_cycle_f32_dev).  On a state stored as float32 posterior =
@@ -443,8 +447,8 @@ int state_cycle(efa_ctx* c, const StateRows& r, const double* grid_lat, const do
     return fail(EFA_ERR_INVALID, "efa_state_cycle_f32_dev: an adaptive-inflation field is set (its update is float64 only)");
   if (f32 && ((reinterpret_cast<uintptr_t>(r.prior) | reinterpret_cast<uintptr_t>(r.post)) & 3u) != 0)
     return fail(EFA_ERR_INVALID, "efa_state_cycle_f32_dev: state pointers must be 4-byte aligned");
-  EFA_TRY(begin_state_call(c, f32 ? "efa_state_cycle_f32_dev" : "efa_state_cycle_dev", r.rows, r.M, r.prior && r.post, grid_lat,
-                           grid_lon, ncol, n_lead, o));
+  EFA_TRY(begin_state_call(c, f32 ? "efa_state_cycle_f32_dev" : "efa_state_cycle_dev", r.rows, r.M, r.prior && r.post,
+                           r.partial_overlap(), grid_lat, grid_lon, ncol, n_lead, o));
   if (r.rows == 0) return EFA_OK;
   return plan_and_run(c, true, r, nullptr, nullptr, ncol, n_lead, o);
 }

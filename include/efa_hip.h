@@ -299,7 +299,9 @@ int efa_obs_phase_dev(efa_ctx *ctx, int M, long P, double *ym_dev,
                       double *prior_var, double *post_mean, double *post_var,
                       uint8_t *assimilated);
 /* out-of-place allowed: (xm_in, Xp_in) -> (xm_out, Xp_out); pass the same
- * pointers for in-place. */
+ * pointers for in-place.  An output range that overlaps its input range
+ * without coinciding with it is refused with EFA_ERR_INVALID (here, in
+ * efa_state_cycle_dev and in efa_state_cycle_f32_dev). */
 int efa_state_phase_dev(efa_ctx *ctx, long rows, int M, const double *xm_in_dev,
                         const double *Xp_in_dev, double *xm_out_dev,
                         double *Xp_out_dev, const double *grid_lat,
@@ -310,7 +312,9 @@ int efa_state_phase_dev(efa_ctx *ctx, long rows, int M, const double *xm_in_dev,
  * trajectory recorded by efa_obs_phase_dev.  Equivalent to
  * efa_form_perts_dev + efa_state_phase_dev + efa_posterior_dev with one read
  * and one write of the state when the transform path applies.
- * post_dev may equal X_dev. */
+ * post_dev may equal X_dev (the transform above 136 members then reads a copy
+ * of the prior, rows*M*8 bytes of device memory more: its column groups
+ * re-read whole rows); any other overlap of the two ranges is EFA_ERR_INVALID. */
 int efa_state_cycle_dev(efa_ctx *ctx, long rows, int M, const double *X_dev,
                         double *post_dev, const double *grid_lat,
                         const double *grid_lon, long ncol, long n_lead);
@@ -338,7 +342,7 @@ int efa_state_cycle_dev(efa_ctx *ctx, long rows, int M, const double *X_dev,
  * on the way out: rows*M*8 bytes more device memory (twice that for the
  * transform above 136 members, whose column groups cannot run in place; the
  * float32 transform above 136 members with post_dev == X_dev keeps a copy of the
- * prior instead, rows*M*4 bytes).  Read-only option "f32_native" says which it
+ * prior instead, rows*M*4 bytes, as the float64 one does at 8 bytes a value).  Read-only option "f32_native" says which it
  * was for the last float32 state call: 1 on the float32 rows, 0 through the
  * workspace. */
 int efa_state_cycle_f32_dev(efa_ctx *ctx, long rows, int M, const float *X_dev,

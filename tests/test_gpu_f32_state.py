@@ -66,8 +66,11 @@ class Problem(object):
         self.hw = rng.uniform(600.0, 1500.0, P)
 
 
-def _run(pb, f32, in_place=False, offset=0, ctx=None):
-    """Phase A and the member-form state phase; returns (posterior float32 rows, diagnostics, (ym, Yp), f32_native)."""
+def _run(pb, f32, in_place=False, offset=0, ctx=None, form="member", exact=False):
+    """Phase A and the state phase; returns (posterior, diagnostics, (ym, Yp), f32_native).  The posterior: float32 rows -- those
+    of the float64 call rounded once, or with `exact` that call's float64 rows as they are.  form "perts" (float64 only) is the
+    perturbation form on the means and perturbations that form_perts makes of the prior on the device: the posterior is then the
+    pair (means, perturbations), float64, never rounded.  A float64 call too runs in place when asked to."""
     L = _lib()
     ctx = ctx or _ctx()
     M, P, rows, n = pb.M, pb.P, pb.rows, pb.rows * pb.M
@@ -95,11 +98,18 @@ def _run(pb, f32, in_place=False, offset=0, ctx=None):
         assert np.all(got[guard] == (7.0 if in_place else 9.0)), "written outside the rows"
         if not in_place:
             assert _same(buf.download(), host), "the prior was written"
+    elif form == "perts":
+        Xd = ctx.to_device(pb.X64)
+        xm, Xp = ctx.empty((rows,)), ctx.empty((rows, M))
+        ctx.form_perts(rows, M, Xd, xm, Xp)
+        xo, Xo = (xm, Xp) if in_place else (ctx.empty((rows,)), ctx.empty((rows, M)))
+        ctx.state_phase(rows, M, xm, Xp, xo, Xo, **grid)
+        post = (xo.download(), Xo.download())
     else:
         Xd = ctx.to_device(pb.X64)
-        out = ctx.empty((rows, M))
+        out = Xd if in_place else ctx.empty((rows, M))
         ctx.state_cycle(rows, M, Xd, out, **grid)
-        post = out.download().astype(F32)
+        post = out.download() if exact else out.download().astype(F32)
     obs_block = (ym.download(), Yp.download())
     return post, diag, obs_block, native
 
