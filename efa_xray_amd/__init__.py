@@ -10,6 +10,8 @@ from efa_xray_amd.observation.observation import Observation, gaspari_cohn, have
 from efa_xray_amd.assimilation.assimilation import Assimilation
 from efa_xray_amd.assimilation.ensrf import EnSRF
 from efa_xray_amd.assimilation.adaptive_inflation import AdaptiveInflation
+from efa_xray_amd.postprocess.impact import observation_impact
 
-__all__ = ["EnsembleState", "Observation", "gaspari_cohn", "haversine", "Assimilation", "EnSRF", "AdaptiveInflation"]
+__all__ = ["EnsembleState", "Observation", "gaspari_cohn", "haversine", "Assimilation", "EnSRF", "AdaptiveInflation",
+           "observation_impact"]
 __version__ = "0.1.0"

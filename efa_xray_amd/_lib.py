@@ -117,6 +117,11 @@ SIGNATURES = {
                                         c_double_p, c_double_p, c_double_p, c_double_p, c_uint8_p]),
     "efa_cov_contract_f32_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_long,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "efa_obs_impact_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_long,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          c_double_p, c_double_p, c_uint8_p, ctypes.c_int,
+                                          c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                          ctypes.c_long, ctypes.c_long, c_double_p]),
     "efa_last_timing": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p,
                                        ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_int)]),
     "efa_fill_synthetic_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_int,
@@ -732,6 +737,20 @@ class Context(object):
             _u8p(d["assimilated"])))
         d["assimilated"] = d["assimilated"].astype(bool)
         return d
+
+    def obs_impact(self, rows, M, P, Xf, werr, Ya, innov, ob_error, ob_used, loc_mode=LOC_NONE, ob_lat=None, ob_lon=None,
+                   ob_halfwidth=None, grid_lat=None, grid_lon=None, n_lead=1):
+        """efa_obs_impact_dev: the forecast impact (P,) of every used ob, 0.0 for the others.  Xf (rows, M), werr
+        (rows,) and Ya (P, M) are device arrays and are only read; the per-ob arrays and the grid are host arrays."""
+        d, err, used, lat, lon, hw = self._ob_arrays(P, innov, ob_error, ob_used, loc_mode, ob_lat, ob_lon, ob_halfwidth)
+        glat, glon, ncol = self._grid(loc_mode, grid_lat, grid_lon)
+        if loc_mode == LOC_NONE:
+            ncol, n_lead = rows, 1
+        out = np.zeros(P)
+        _check(self.lib, self.lib.efa_obs_impact_dev(
+            self.handle, rows, M, P, self._addr(Xf), self._addr(werr), self._addr(Ya), _dp(d), _dp(err), _u8p(used), loc_mode,
+            _dp(lat), _dp(lon), _dp(hw), _dp(glat), _dp(glon), ncol, n_lead, _dp(out)))
+        return out
 
     def cov_contract_f32(self, N, M, P, Xbp_f32, Ye_f32, C_f32):
         """C (N x P) = Xbp (N x M) . Ye^T (P x M), float32, device addresses."""

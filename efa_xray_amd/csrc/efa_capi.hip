@@ -339,6 +339,7 @@ int efa_ctx_get_option(efa_ctx* c, const char* key, long* value) {
   else if (!strcmp(key, "stream_h2d_us")) *value = c->st.h2d_us;
   else if (!strcmp(key, "stream_d2h_us")) *value = c->st.d2h_us;
   else if (!strcmp(key, "stream_wall_us")) *value = c->st.wall_us;
+  else if (!strcmp(key, "impact_us")) *value = c->impact_us;  // the last efa_obs_impact_dev (efa_impact.hip)
   else return fail(EFA_ERR_INVALID, "unknown option '%s'", key);
   return EFA_OK;
 }
@@ -639,6 +640,15 @@ int efa_cov_contract_f32_dev(efa_ctx* c, long N, int M, long P, const float* Xbp
     return fail(EFA_ERR_INVALID, "operands must be 16-byte aligned");
   EFA_HIP(efa::launch_contract_f32(N, M, P, Xbp_f32_dev, Ye_f32_dev, C_f32_dev, c->stream));
   return EFA_OK;
+}
+
+int efa_obs_impact_dev(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const double* werr_dev, const double* Ya_dev,
+                       const double* innov, const double* ob_error, const uint8_t* ob_used, int loc_mode, const double* ob_lat,
+                       const double* ob_lon, const double* ob_halfwidth_km, const double* grid_lat, const double* grid_lon,
+                       long ncol, long n_lead, double* impact) {
+  EFA_TRY(use(c));
+  return obs_impact(c, rows, M, P, Xf_dev, werr_dev, Ya_dev, innov, ob_error, ob_used, loc_mode, ob_lat, ob_lon, ob_halfwidth_km,
+                    grid_lat, grid_lon, ncol, n_lead, impact);
 }
 
 int efa_last_timing(efa_ctx* c, double* state_ms, double* obs_ms, long* state_launches, int* path_taken) {

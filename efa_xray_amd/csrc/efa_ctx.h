@@ -180,6 +180,7 @@ struct efa_ctx {
   Interval obs_iv;       // the obs phase; it ends at obs_ends_at
   Interval state_iv[2];  // the state phase; efa_ensrf_cycle_dev alternates the two: it records a state phase's events BEFORE the
                          // stream is synchronised, while the previous cycle's may still be unread
+  Interval imp_iv;       // efa_obs_impact_dev's contraction (its events are created by the first call)
   OwnedEvent ev_fs;  // the last host-to-device copy of the forward-operator stencil (pin_fs)
   OwnedEvent ev_order;  // a change of stream: recorded on the stream that is left, waited for by the one that takes over
   int device = 0;
@@ -273,6 +274,13 @@ struct efa_ctx {
   double qc_threshold = 0.0;    // 0: off
   bool qc_used = false;         // the last obs phase ran it: its flags on the device may be fewer than the caller's
   DevBuf qc_act;                // [P][kCoefStride], GC: the caller's flags where the one-pass sweep's list builders read coef[3]
+  // --- observation impact (efa_obs_impact_dev): buffers of its own, nothing above is touched by it ---------------
+  DevBuf imp_ob;    // per ob: used flags (coefficient-shaped) | scale | lat | lon | half-width | obtrig scratch | impact
+  DevBuf imp_Yp;    // analysis perturbations in observation space [P][M] | their means [P]
+  DevBuf imp_grid;  // the call's column grid (lat | lon)
+  DevBuf imp_blk, imp_idx, imp_wts;  // the call's active lists: off | cnt | ub | order, entries, tapers
+  DevBuf imp_part;  // GC: partial sums [groups of slabs][entries] | per-range sums [ranges][P]; unlocalised: per-wave z | z
+  long impact_us = 0;  // read-only option "impact_us": device time of the last call's contraction and reduction
   // --- f1: interpolation stencils -------------------------------------------------
   DevBuf fs_idx;  // efa_forward_stencil_dev staging
   DevBuf f_glat, f_glon, f_sl, f_cl, f_valids, f_var, f_time, f_lat, f_lon, f_near, f_idx, f_wts, f_status;

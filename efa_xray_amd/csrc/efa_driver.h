@@ -3,6 +3,7 @@
 //   efa_phase_a.hip  the obs phase (Phase A): staging, the window driver, the speculative transform
 //   efa_phase_b.hip  the state phase (Phase B): the column grid, the plan of a state call, its executor and the state calls
 //   efa_stream.hip   the streamed host-memory update
+//   efa_impact.hip   observation impact: its kernels and the driver of efa_obs_impact_dev
 //   efa_comm.hip     RCCL
 // One call's arguments and results travel as arguments and return values; the context (efa_ctx.h) holds settings, caches,
 // workspaces and what the last obs phase left for the state phase.  A state call's rows travel with their element type (StateRows);
@@ -110,5 +111,12 @@ int state_cycle(efa_ctx* c, const StateRows& r, const double* grid_lat, const do
 // end of a state call: the launch count into the sum; "timing" 1 waits and reads the interval, 2 leaves it pending.
 // end_recorded: iv.end is in the stream already (a speculative transform that turned out right)
 int end_state_call(efa_ctx* c, Interval& iv, bool timed = true, bool end_recorded = false);
+
+// ---- efa_impact.hip -----------------------------------------------------------------------------------------------------------
+// efa_obs_impact_dev: checks, the call's own active lists, the contraction and its reduction; waits before it returns impact[P]
+int obs_impact(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const double* werr_dev, const double* Ya_dev,
+               const double* innov, const double* ob_error, const uint8_t* ob_used, int loc_mode, const double* ob_lat,
+               const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
+               double* impact);
 
 }  // namespace efa_host

@@ -15,6 +15,7 @@
 // Work drops from P passes' worth to (active fraction) x P; HBM traffic to one read + one write.
 #include "efa_device.h"
 #include "efa_internal.h"
+#include "efa_lane_dot.h"
 #include "efa_rows.h"
 
 #include <cstdlib>
@@ -375,16 +376,7 @@ constexpr int gc_min_waves(int NC, int RPL) {
 // The DPP instructions are inline assembly (the compiler has no 64-bit DPP intrinsic).  Their DPP operand, ye, is written by
 // LDS reads only, never by a VALU instruction, so the "VALU write -> DPP read" hazard (which the compiler does not track
 // through inline assembly) cannot arise; tests/test_cpu_host.py checks the generated code for exactly that.
-template <int L>
-__device__ __forceinline__ void fmac_bcast(double& acc, double y, double x) {  // acc += (y of lane L of this 16-lane row) * x
-  asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(y), "v"(x), "n"(L));
-}
-template <int MP, int... I>
-__device__ __forceinline__ double lane_dot(const double (&x)[MP], const double (&y)[(MP + 15) / 16], std::integer_sequence<int, I...>) {
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  (fmac_bcast<I % 16>(acc[I & 3], y[I / 16], x[I]), ...);
-  return (acc[0] + acc[1]) + (acc[2] + acc[3]);
-}
+// fmac_bcast and lane_dot: efa_lane_dot.h (shared with the observation-impact contraction, efa_impact.hip).
 // x[16 C + i] += (ye member 16 C + i) * nkb for the members of ye register C
 template <int MP, int C, int... I>
 __device__ __forceinline__ void lane_update_group(double (&x)[MP], double yc, double nkb, std::integer_sequence<int, I...>) {

@@ -199,6 +199,41 @@ hipError_t launch_gc_count(long ncol, long P, const double* glat, const double* 
 bool sweep_gc_serves(Elem elem, int M, long ye_stride, const double* Ye);
 hipError_t launch_sweep_gc(const GcSweepArgs& a, Elem elem, hipStream_t s);
 
+// ---- observation impact (EFSO, efa_impact.hip) ----------------------------------
+// The localised contraction: a sibling of the one-pass sweep's row-per-lane kernel that reads the state once and writes none of
+// it.  It walks the same per-block active lists (built by launch_gc_bound / launch_gc_fill into buffers of the call's own).
+struct ImpactGcArgs {
+  long ncol, n_lead;
+  int M;
+  long nblk;
+  const long* off;      // the active lists, as GcSweepArgs has them
+  const int* cnt;
+  const int* order;
+  const int* idx;
+  const double* wts;
+  const double* Yp;     // [P][M] analysis perturbations in observation space
+  const double* X;      // [n_lead*ncol][M] forecast members
+  const double* v;      // [n_lead*ncol] weighted error sum of every state row
+  const double* lead_vert;  // vertical localisation as in GcSweepArgs; null: off
+  const double* ob_vert;
+  const double* ob_vhw;
+  double* partial;      // [lead_split][cap] out: one sum per (group of 16 slabs, list entry)
+  long cap;             // off[nblk]
+  int lead_split;       // groups of 16 slabs (set by the launcher)
+};
+int impact_lead_split(long n_lead);
+hipError_t launch_impact_gc(const ImpactGcArgs& a, hipStream_t s);
+// partial -> impact[k] = scale[k] * (sum of ob k's partials), in a fixed order: `ranges` workgroups each add the entries of a
+// contiguous range of column blocks into a row of acc [ranges][P], then one thread per ob adds the rows
+int impact_reduce_ranges(long nblk, long P);
+hipError_t launch_impact_reduce(long nblk, long P, const long* off, const int* cnt, const int* idx, const double* partial, long cap,
+                                int lead_split, const double* scale, double* acc, double* impact, hipStream_t s);
+// unlocalised: z[m] = sum_i v[i] X'[i][m] (grid-stride over a capped grid, per-wave partial sums in zpart [impact_z_waves()][256],
+// added in a fixed order), then impact[k] = scale[k] * (Yp[k] . z)
+long impact_z_waves();
+hipError_t launch_impact_none(long rows, int M, long P, const double* X, const double* v, const double* Yp, const double* scale,
+                              double* zpart, double* z /* [256] */, double* impact, hipStream_t s);
+
 struct TransformArgs {
   const double* Xin;  // [rows][M] perturbations, or full members when fused_members
   const double* xin;  // [rows] means (unused when fused_members)

@@ -96,7 +96,7 @@ int efa_ctx_set_stream(efa_ctx *ctx, void *hip_stream);
  *          read-only: "phase_a_kind" (1 pipeline / 2 per-batch / 3 Gram pipeline / 4 band pipeline, last call),
  *          "gc_active_pairs"
  *          ((column, ob) pairs with a non-zero taper in the last one-pass sweep),
- *          "f32_native" (see efa_state_cycle_f32_dev) */
+ *          "f32_native" (see efa_state_cycle_f32_dev), "impact_us" (see efa_obs_impact_dev) */
 int efa_ctx_set_option(efa_ctx *ctx, const char *key, long value);
 int efa_ctx_get_option(efa_ctx *ctx, const char *key, long *value);
 
@@ -475,6 +475,51 @@ int efa_pinned_free(efa_ctx *ctx, void *host);
 int efa_cov_contract_f32_dev(efa_ctx *ctx, long N, int M, long P,
                              const float *Xbp_f32_dev, const float *Ye_f32_dev,
                              float *C_f32_dev);
+
+/* ---- observation impact (EFSO; Kalnay et al. 2012, Ota et al. 2013) ----
+ * How much each assimilated observation changed a forecast error norm, once a
+ * verifying state exists.  For every ob k with ob_used[k] != 0
+ *   impact[k] = (1/(M-1)) (innov[k] / ob_error[k])
+ *               * sum_i rho_ik werr[i] (Xf'_i . Ya'_k)
+ * and impact[k] = 0.0 for every other ob.  Negative: the ob reduced the error.
+ *   Xf_dev   [rows][M] forecast members (Xf' their deviations from the row mean)
+ *   werr_dev [rows]    the weighted error sum c_i (e^a_i + e^b_i) of every row;
+ *                      0 for a row that is not verified
+ *   Ya_dev   [P][M]    analysis members in observation space (Ya' their deviations)
+ *   innov, ob_error, ob_used [P] (host): innovation against the background
+ *                      mean, error variance, and whether the ob was assimilated
+ *   rho_ik: 1 with EFA_LOC_NONE (pass n_lead = 1, ncol = rows).  With
+ *     EFA_LOC_GC the taper the assimilation itself uses for state row
+ *     i = lead*ncol + col and ob k: Gaspari-Cohn of the column's distance to the
+ *     ob with ob_halfwidth_km[k], times -- while vertical localisation is set
+ *     on the context -- the vertical factor of (slab lead, ob k) by the rules of
+ *     efa_ctx_set_vertical_localization.  The taper is not advected.
+ * Xf_dev, werr_dev and Ya_dev are read only.  The call needs no preceding obs
+ * phase and leaves everything a later cycle reads -- cached active lists and
+ * taper tables, the trajectory, options, the sums of efa_last_timing -- as it
+ * found it: a cycle after it returns the bits it returns without it.  It
+ * synchronises the stream before returning impact[P] (host).  The sums are
+ * added in a fixed order without atomics: the same inputs give the same bits.
+ * Relaxation, outlier threshold, adaptive-inflation field and "path" do not
+ * apply and are ignored.
+ * The rows may be a column shard (grid_lat/grid_lon its ncol columns): the
+ * impact arrays of the shards add up to the whole state's, so one
+ * efa_allreduce_sum_dev over a device copy of them finishes a sharded call.
+ * EFA_ERR_INVALID: a NULL pointer, M < 2 or M > 256, rows != n_lead*ncol, a
+ * used ob whose innov is not finite or whose ob_error is not finite and > 0,
+ * a used ob with a NaN half-width under EFA_LOC_GC, or vertical localisation
+ * set while the call is not an EFA_LOC_GC call of exactly its P and n_lead.
+ * Read-only option "impact_us": device time (microseconds, HIP events) of the
+ * last call's contraction and reduction kernels; the build of the call's
+ * active lists and the copies around them are not in it. */
+int efa_obs_impact_dev(efa_ctx *ctx, long rows, int M, long P,
+                       const double *Xf_dev, const double *werr_dev,
+                       const double *Ya_dev, const double *innov,
+                       const double *ob_error, const uint8_t *ob_used,
+                       int loc_mode, const double *ob_lat, const double *ob_lon,
+                       const double *ob_halfwidth_km, const double *grid_lat,
+                       const double *grid_lon, long ncol, long n_lead,
+                       double *impact);
 
 /* ---- measurement support --------------------------------------------------
  * Device time (ms) spent in the state-sweep kernels and in the obs-space
