@@ -46,12 +46,14 @@ __global__ __launch_bounds__(256, EFA_GCK_QUAD_WAVES(NC, RPL)) void EFA_GCK_QUAD
     double xm[RPL];
     double lam[RPL], sd[RPL], ss[RPL];  // ADAPT: the row's inflation and x'.x'
     bool live[RPL];
+    bool touched[RPL];  // FUSED: some ob moved the row (a row no ob reaches goes out as it came in, see the store below)
     long row[RPL];
     bool any_live = false;
 #pragma unroll
     for (int q = 0; q < RPL; ++q) {
       const int lead = lead0 + sq + 4 * q;
       live[q] = col_ok && lead < lead_hi;
+      touched[q] = false;
       any_live = any_live || live[q];
       row[q] = (long)lead * a.ncol + col;
       xm[q] = 0.0;
@@ -147,6 +149,7 @@ __global__ __launch_bounds__(256, EFA_GCK_QUAD_WAVES(NC, RPL)) void EFA_GCK_QUAD
           }
           xm[q] = __builtin_fma(abr.y, dot, xm[q]);      // :115, :119, :130
           const double kb = abr.x * dot;                 // :115, :119, :136
+          if (FUSED) touched[q] = touched[q] || (abr.x != 0.0);
           if (ADAPT) {  // (each lane of the quad holds the quad's dot and x'.x': the four do the update alike)
             anderson_update(lam[q], sd[q], aw, dot, ss[q], o01, o23, a.infl_lower, a.infl_upper, a.infl_sd_lower);
             ss[q] = adapt_ss_after(ss[q], kb, dot, o23.y);
@@ -160,8 +163,12 @@ __global__ __launch_bounds__(256, EFA_GCK_QUAD_WAVES(NC, RPL)) void EFA_GCK_QUAD
     for (int q = 0; q < RPL; ++q) {
       if (live[q]) {
         if (FUSED) {  // posterior members out (assimilation.py:168)
+          if (touched[q]) {
 #pragma unroll
-          for (int c = 0; c < 2 * NC; ++c) x[q][c] += xm[q];
+            for (int c = 0; c < 2 * NC; ++c) x[q][c] += xm[q];
+          } else {  // no ob reaches the row: its prior members bit for bit, which (x - mean) + mean is not
+            load_row<L, NC, VEC>(a.Xin + (size_t)row[q] * M, M, j, x[q]);
+          }
         }
         store_row<L, NC, VEC>(a.Xout + (size_t)row[q] * M, M, j, x[q]);
         if (!FUSED && j == 0) a.xout[row[q]] = xm[q];
@@ -223,6 +230,7 @@ __global__ __launch_bounds__(256, EFA_GCK_LANE_WAVES(MP)) void EFA_GCK_LANE(cons
     double x[MP];
     double xm = 0.0;
     double lam = 1.0, sd = 0.0, ss = 0.0;  // ADAPT: the row's inflation and x'.x'
+    bool touched = false;                  // FUSED: some ob moved the row
     if (live && sizeof(E) != sizeof(double)) {
       const float* pf = reinterpret_cast<const float*>(a.Xin) + (size_t)row * M;
       if (M == MP && (reinterpret_cast<uintptr_t>(pf) & 15u) == 0) {  // M % 4 == 0 and a 16-byte aligned base: 16-byte loads
@@ -363,6 +371,7 @@ __global__ __launch_bounds__(256, EFA_GCK_LANE_WAVES(MP)) void EFA_GCK_LANE(cons
         }
         xm = __builtin_fma(ab.y, dot, xm);               // :115, :119, :130
         const double nkb = -(ab.x * dot);                // :115, :119, :136
+        if (FUSED) touched = touched || (ab.x != 0.0);
         if (ADAPT) {
           lane_update<MP>(x, y, nkb);  // :141
           const double2 o23 = ao_s[2 * ee + 1];
@@ -378,6 +387,25 @@ __global__ __launch_bounds__(256, EFA_GCK_LANE_WAVES(MP)) void EFA_GCK_LANE(cons
         todo &= todo - 1;
         ee = en;
         ab = abn;
+      }
+    }
+    // FUSED, and no ob reaches the row: its prior members go out bit for bit, which (x - mean) + mean is not (-0.0: x + -0.0 is x)
+    if constexpr (FUSED) {
+      if (live && !touched) {
+        if (sizeof(E) != sizeof(double)) {
+          const float* pf = reinterpret_cast<const float*>(a.Xin) + (size_t)row * M;
+#pragma unroll
+          for (int i = 0; i < MP; ++i) x[i] = (i < M) ? (double)pf[i] : 0.0;
+        } else {
+          const double2* p = reinterpret_cast<const double2*>(a.Xin + (size_t)row * M);
+#pragma unroll
+          for (int i = 0; i < MP / 2; ++i) {
+            const double2 v = (i < M2) ? p[i] : make_double2(0.0, 0.0);
+            x[2 * i] = v.x;
+            x[2 * i + 1] = v.y;
+          }
+        }
+        xm = -0.0;
       }
     }
     if (live && sizeof(E) != sizeof(double)) {  // posterior members out, each rounded to float32 once

@@ -314,7 +314,10 @@ int efa_state_phase_dev(efa_ctx *ctx, long rows, int M, const double *xm_in_dev,
  * and one write of the state when the transform path applies.
  * post_dev may equal X_dev (the transform above 136 members then reads a copy
  * of the prior, rows*M*8 bytes of device memory more: its column groups
- * re-read whole rows); any other overlap of the two ranges is EFA_ERR_INVALID. */
+ * re-read whole rows); any other overlap of the two ranges is EFA_ERR_INVALID.
+ * Under EFA_LOC_GC with option "gc_onepass" 1 and no relaxation a row that no assimilated ob
+ * reaches (every taper weight 0) comes back bit for bit as it went in, as its xm
+ * and Xp rows do from efa_state_phase_dev. */
 int efa_state_cycle_dev(efa_ctx *ctx, long rows, int M, const double *X_dev,
                         double *post_dev, const double *grid_lat,
                         const double *grid_lon, long ncol, long n_lead);
