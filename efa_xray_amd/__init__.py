@@ -11,7 +11,8 @@ from efa_xray_amd.assimilation.assimilation import Assimilation
 from efa_xray_amd.assimilation.ensrf import EnSRF
 from efa_xray_amd.assimilation.adaptive_inflation import AdaptiveInflation
 from efa_xray_amd.postprocess.impact import observation_impact
+from efa_xray_amd.postprocess.sensitivity import ensemble_sensitivity, observation_targets
 
 __all__ = ["EnsembleState", "Observation", "gaspari_cohn", "haversine", "Assimilation", "EnSRF", "AdaptiveInflation",
-           "observation_impact"]
+           "observation_impact", "ensemble_sensitivity", "observation_targets"]
 __version__ = "0.1.0"

@@ -122,6 +122,14 @@ SIGNATURES = {
                                           c_double_p, c_double_p, c_uint8_p, ctypes.c_int,
                                           c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                           ctypes.c_long, ctypes.c_long, c_double_p]),
+    "efa_sensitivity_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, c_double_p,
+                                           ctypes.c_long, ctypes.c_long, c_double_p, c_double_p, ctypes.c_void_p, ctypes.c_int,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.POINTER(ctypes.c_long), c_double_p, c_double_p]),
+    "efa_sensitivity_f32_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, c_double_p,
+                                               ctypes.c_long, ctypes.c_long, c_double_p, c_double_p, ctypes.c_void_p, ctypes.c_int,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.POINTER(ctypes.c_long), c_double_p, c_double_p]),
     "efa_last_timing": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p,
                                        ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_int)]),
     "efa_fill_synthetic_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_int,
@@ -751,6 +759,31 @@ class Context(object):
             self.handle, rows, M, P, self._addr(Xf), self._addr(werr), self._addr(Ya), _dp(d), _dp(err), _u8p(used), loc_mode,
             _dp(lat), _dp(lon), _dp(hw), _dp(glat), _dp(glon), ncol, n_lead, _dp(out)))
         return out
+
+    def sensitivity(self, rows, M, X, J, slab_error, ncol=None, n_lead=1, weights=None, cand=None, n_targets=0, var=None, cov=None,
+                    sens=None, corr=None, dvar=None, score=None, f32=None):
+        """efa_sensitivity_dev / efa_sensitivity_f32_dev.  X (rows, M) is a device array of float64 or float32
+        members (`f32` says which for a raw address; None: the DeviceArray's dtype), only read; J (K, M), slab_error (n_lead,)
+        and weights (K,) are host arrays; cand (rows,) uint8 and the fields var (rows,), cov / sens / corr / dvar (K, rows),
+        score (rows,) are float64 device arrays or None (field not wanted).  Returns (picked_row (n_targets,) int64,
+        picked_score (n_targets,), metric_var (n_targets + 1, K))."""
+        J = np.ascontiguousarray(J, dtype=np.float64)
+        K = int(J.shape[0])
+        R = np.ascontiguousarray(slab_error, dtype=np.float64).reshape(-1)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if f32 is None:
+            f32 = isinstance(X, DeviceArray) and X.dtype == np.float32
+        fn = self.lib.efa_sensitivity_f32_dev if f32 else self.lib.efa_sensitivity_dev
+        n = int(n_targets)
+        prow = np.full(max(n, 0), -1, dtype=np.int64)
+        psc = np.zeros(max(n, 0))
+        mv = np.zeros((max(n, 0) + 1, max(K, 1)))
+        _check(self.lib, fn(
+            self.handle, int(rows), int(M), K, self._addr(X, np.float32 if f32 else np.float64), _dp(J),
+            int(rows if ncol is None else ncol), int(n_lead), _dp(R), _dp(w), self._addr(cand, None), n,
+            self._addr(var), self._addr(cov), self._addr(sens), self._addr(corr), self._addr(dvar), self._addr(score),
+            prow.ctypes.data_as(ctypes.POINTER(ctypes.c_long)), _dp(psc), _dp(mv)))
+        return prow, psc, mv
 
     def cov_contract_f32(self, N, M, P, Xbp_f32, Ye_f32, C_f32):
         """C (N x P) = Xbp (N x M) . Ye^T (P x M), float32, device addresses."""

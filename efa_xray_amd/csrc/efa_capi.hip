@@ -340,6 +340,7 @@ int efa_ctx_get_option(efa_ctx* c, const char* key, long* value) {
   else if (!strcmp(key, "stream_d2h_us")) *value = c->st.d2h_us;
   else if (!strcmp(key, "stream_wall_us")) *value = c->st.wall_us;
   else if (!strcmp(key, "impact_us")) *value = c->impact_us;  // the last efa_obs_impact_dev (efa_impact.hip)
+  else if (!strcmp(key, "sens_us")) *value = c->sens_us;  // the last efa_sensitivity_dev (efa_sensitivity.hip)
   else return fail(EFA_ERR_INVALID, "unknown option '%s'", key);
   return EFA_OK;
 }
@@ -649,6 +650,24 @@ int efa_obs_impact_dev(efa_ctx* c, long rows, int M, long P, const double* Xf_de
   EFA_TRY(use(c));
   return obs_impact(c, rows, M, P, Xf_dev, werr_dev, Ya_dev, innov, ob_error, ob_used, loc_mode, ob_lat, ob_lon, ob_halfwidth_km,
                     grid_lat, grid_lon, ncol, n_lead, impact);
+}
+
+int efa_sensitivity_dev(efa_ctx* c, long rows, int M, int K, const double* X_dev, const double* J, long ncol, long n_lead,
+                        const double* slab_error, const double* weights, const uint8_t* cand_dev, int n_targets, double* var_dev,
+                        double* cov_dev, double* sens_dev, double* corr_dev, double* dvar_dev, double* score_dev, long* picked_row,
+                        double* picked_score, double* metric_var) {
+  EFA_TRY(use(c));
+  return sensitivity(c, efa::Elem::f64, rows, M, K, X_dev, J, ncol, n_lead, slab_error, weights, cand_dev, n_targets, var_dev, cov_dev,
+                     sens_dev, corr_dev, dvar_dev, score_dev, picked_row, picked_score, metric_var);
+}
+
+int efa_sensitivity_f32_dev(efa_ctx* c, long rows, int M, int K, const float* X_dev, const double* J, long ncol, long n_lead,
+                            const double* slab_error, const double* weights, const uint8_t* cand_dev, int n_targets, double* var_dev,
+                            double* cov_dev, double* sens_dev, double* corr_dev, double* dvar_dev, double* score_dev,
+                            long* picked_row, double* picked_score, double* metric_var) {
+  EFA_TRY(use(c));
+  return sensitivity(c, efa::Elem::f32, rows, M, K, X_dev, J, ncol, n_lead, slab_error, weights, cand_dev, n_targets, var_dev, cov_dev,
+                     sens_dev, corr_dev, dvar_dev, score_dev, picked_row, picked_score, metric_var);
 }
 
 int efa_last_timing(efa_ctx* c, double* state_ms, double* obs_ms, long* state_launches, int* path_taken) {

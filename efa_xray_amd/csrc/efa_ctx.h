@@ -181,6 +181,7 @@ struct efa_ctx {
   Interval state_iv[2];  // the state phase; efa_ensrf_cycle_dev alternates the two: it records a state phase's events BEFORE the
                          // stream is synchronised, while the previous cycle's may still be unread
   Interval imp_iv;       // efa_obs_impact_dev's contraction (its events are created by the first call)
+  Interval sens_iv;      // one pass of efa_sensitivity_dev (likewise)
   OwnedEvent ev_fs;  // the last host-to-device copy of the forward-operator stencil (pin_fs)
   OwnedEvent ev_order;  // a change of stream: recorded on the stream that is left, waited for by the one that takes over
   int device = 0;
@@ -281,6 +282,10 @@ struct efa_ctx {
   DevBuf imp_blk, imp_idx, imp_wts;  // the call's active lists: off | cnt | ub | order, entries, tapers
   DevBuf imp_part;  // GC: partial sums [groups of slabs][entries] | per-range sums [ranges][P]; unlocalised: per-wave z | z
   long impact_us = 0;  // read-only option "impact_us": device time of the last call's contraction and reduction
+  // --- ensemble sensitivity and targeting (efa_sensitivity_dev): buffers of its own as well -------------------------
+  DevBuf sens_pack;  // what a pass stages in LDS: vectors [K + t][M] | b/d [t][K] | 1/d [t] | weights [K] | varJ [K]; slab errors [n_lead]
+  DevBuf sens_best;  // per workgroup: best score | its row; then the grid's
+  long sens_us = 0;  // read-only option "sens_us": device time of the last call's passes
   // --- f1: interpolation stencils -------------------------------------------------
   DevBuf fs_idx;  // efa_forward_stencil_dev staging
   DevBuf f_glat, f_glon, f_sl, f_cl, f_valids, f_var, f_time, f_lat, f_lon, f_near, f_idx, f_wts, f_status;

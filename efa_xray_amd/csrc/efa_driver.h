@@ -4,6 +4,7 @@
 //   efa_phase_b.hip  the state phase (Phase B): the column grid, the plan of a state call, its executor and the state calls
 //   efa_stream.hip   the streamed host-memory update
 //   efa_impact.hip   observation impact: its kernels and the driver of efa_obs_impact_dev
+//   efa_sensitivity.hip  ensemble sensitivity and observation targeting: its kernels and the driver of efa_sensitivity_dev
 //   efa_comm.hip     RCCL
 // One call's arguments and results travel as arguments and return values; the context (efa_ctx.h) holds settings, caches,
 // workspaces and what the last obs phase left for the state phase.  A state call's rows travel with their element type (StateRows);
@@ -118,5 +119,12 @@ int obs_impact(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const
                const double* innov, const double* ob_error, const uint8_t* ob_used, int loc_mode, const double* ob_lat,
                const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
                double* impact);
+
+// ---- efa_sensitivity.hip ------------------------------------------------------------------------------------------------------
+// efa_sensitivity_dev / _f32_dev: checks, the passes and the host algebra between them; waits before it returns
+int sensitivity(efa_ctx* c, Elem elem, long rows, int M, int K, const void* X_dev, const double* J, long ncol, long n_lead,
+                const double* slab_error, const double* weights, const uint8_t* cand_dev, int n_targets, double* var_dev,
+                double* cov_dev, double* sens_dev, double* corr_dev, double* dvar_dev, double* score_dev, long* picked_row,
+                double* picked_score, double* metric_var);
 
 }  // namespace efa_host

@@ -1,3 +1,4 @@
 from efa_xray_amd.postprocess.impact import observation_impact
+from efa_xray_amd.postprocess.sensitivity import ensemble_sensitivity, observation_targets
 
-__all__ = ["observation_impact"]
+__all__ = ["observation_impact", "ensemble_sensitivity", "observation_targets"]

@@ -96,7 +96,8 @@ int efa_ctx_set_stream(efa_ctx *ctx, void *hip_stream);
  *          read-only: "phase_a_kind" (1 pipeline / 2 per-batch / 3 Gram pipeline / 4 band pipeline, last call),
  *          "gc_active_pairs"
  *          ((column, ob) pairs with a non-zero taper in the last one-pass sweep),
- *          "f32_native" (see efa_state_cycle_f32_dev), "impact_us" (see efa_obs_impact_dev) */
+ *          "f32_native" (see efa_state_cycle_f32_dev), "impact_us" (see efa_obs_impact_dev),
+ *          "sens_us" (see efa_sensitivity_dev) */
 int efa_ctx_set_option(efa_ctx *ctx, const char *key, long value);
 int efa_ctx_get_option(efa_ctx *ctx, const char *key, long *value);
 
@@ -523,6 +524,68 @@ int efa_obs_impact_dev(efa_ctx *ctx, long rows, int M, long P,
                        const double *ob_halfwidth_km, const double *grid_lat,
                        const double *grid_lon, long ncol, long n_lead,
                        double *impact);
+
+/* ---- ensemble sensitivity and greedy observation targeting (Ancell & Hakim 2007, Torn & Hakim 2008) ----
+ * Asked BEFORE observations are taken: which state rows drive K forecast
+ * metrics, and where would the next observation reduce their variance most.
+ *   X_dev [rows][M]  state members (float64; float32 for the _f32 twin, every
+ *                    number computed in float64 as DESIGN.md 7g has it), row
+ *                    i = lead*ncol + col, rows = n_lead*ncol (to_vect() order)
+ *   J [K][M] (host)  the members' values of the K metrics
+ *   slab_error [n_lead] (host) error VARIANCE R of a hypothetical observation
+ *                    of a row of that slab, finite and > 0
+ *   weights [K] (host, NULL: all 1) finite, >= 0
+ *   cand_dev [rows] (NULL: every row) non-zero: the row may be picked
+ * With x'_i, J'_k the deviations from the member means, every statistic with
+ * 1/(M-1) (a product of its own: not ensrf.py's mixed convention):
+ *   var_i = x'_i.x'_i/(M-1)   cov_ik = x'_i.J'_k/(M-1)   varJ_k = J'_k.J'_k/(M-1)
+ * Picks t = 0 .. n_targets-1 are made one after the other, each conditioning
+ * every statistic on the ones before by the exact, unlocalised Kalman update
+ * of observing row i_t with error R_slab(i_t):
+ *   score_i(t) = sum_k w_k cov_ik(t)^2 / (var_i(t) + R_slab(i)),
+ * the expected reduction of sum_k w_k var(J_k); i_t is the candidate with the
+ * largest score, the lowest row among equals, never a NaN; when no candidate
+ * scores > 0 the picks stop (picked_row -1, picked_score 0.0, metric_var
+ * repeats its last row).  A row may be picked twice.
+ * Fields at the final pass (device, each may be NULL = not wanted and not
+ * written; n_targets = 0: the classical ensemble-sensitivity fields):
+ *   var [rows], cov [K][rows], sens = cov/var, corr = cov/sqrt(var varJ_k),
+ *   dvar = -cov^2/(var + R) (each [K][rows]), score [rows] (0.0 for a row that
+ *   is no candidate).  A zero denominator gives exactly 0.0; a row with a
+ *   non-finite member gives NaN fields and is never picked; a constant row
+ *   gives 0.0 everywhere.
+ * Host outputs: picked_row [n_targets], picked_score [n_targets], metric_var
+ * [n_targets+1][K] = varJ after 0 .. n_targets picks (required when
+ * n_targets > 0; metric_var may be given alone with n_targets = 0).
+ * One pass over the state per pick plus one for the fields (skipped when no
+ * field is wanted); between passes the picked row's M members come to the host
+ * for an M x M update.  The best row is found without atomics, in a fixed
+ * order: the same inputs give the same bits and the same picks.  The call
+ * uses workspaces of its own and leaves everything a later cycle reads as it
+ * found it, like efa_obs_impact_dev; it synchronises before returning.
+ * The rows may be a column shard: the fields of the shards are the fields of
+ * the whole state (picks across shards are the caller's business).
+ * EFA_ERR_INVALID, before any launch and with no output written: a NULL
+ * required pointer, M < 2 or M > 256, K < 1, n_targets < 0, K + n_targets >
+ * 32, rows != n_lead*ncol, a non-finite J, a slab_error that is not finite
+ * and > 0, a weight that is not finite and >= 0, n_targets > 0 with a NULL
+ * picked_row / picked_score / metric_var.
+ * Read-only option "sens_us": device time (microseconds, HIP events) of the
+ * last call's passes, summed. */
+int efa_sensitivity_dev(efa_ctx *ctx, long rows, int M, int K, const double *X_dev,
+                        const double *J, long ncol, long n_lead,
+                        const double *slab_error, const double *weights,
+                        const uint8_t *cand_dev, int n_targets, double *var_dev,
+                        double *cov_dev, double *sens_dev, double *corr_dev,
+                        double *dvar_dev, double *score_dev, long *picked_row,
+                        double *picked_score, double *metric_var);
+int efa_sensitivity_f32_dev(efa_ctx *ctx, long rows, int M, int K, const float *X_dev,
+                            const double *J, long ncol, long n_lead,
+                            const double *slab_error, const double *weights,
+                            const uint8_t *cand_dev, int n_targets, double *var_dev,
+                            double *cov_dev, double *sens_dev, double *corr_dev,
+                            double *dvar_dev, double *score_dev, long *picked_row,
+                            double *picked_score, double *metric_var);
 
 /* ---- measurement support --------------------------------------------------
  * Device time (ms) spent in the state-sweep kernels and in the obs-space
