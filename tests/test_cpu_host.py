@@ -76,6 +76,15 @@ def test_baseline_kernels_fit_their_register_budget():
     for mp in (80, 100):
         lane = find("k_sweep_gc_laneILi%dELb1E" % mp)
         assert lane.get(".vgpr_spill_count", 0) == 0 and lane[".vgpr_count"] <= 256, (mp, lane[".vgpr_count"])
+    # configs[4] at every member count: all eight instantiations of k_contract_f32_ra (KH = 8 .. 64; 196 .. 252 VGPRs when this was
+    # written) and the general kernel (196 VGPRs + 64 AGPRs) keep everything in registers: no spill, no scratch
+    contract = [find("k_contract_f32_raILi%dE" % kh) for kh in range(8, 65, 8)] + [find("k_contract_f32E")]
+    assert len(set(k[".name"] for k in contract)) == 9
+    for k in contract:
+        assert k.get(".vgpr_spill_count", 0) == 0 and k.get(".sgpr_spill_count", 0) == 0, (k[".name"], k[".vgpr_count"])
+        assert k[".private_segment_fixed_size"] == 0, (k[".name"], k[".private_segment_fixed_size"])
+    for k in contract[:8]:
+        assert k[".vgpr_count"] <= 256, (k[".name"], k[".vgpr_count"])
 
 
 def test_no_cpu_fallback_without_gpu():
