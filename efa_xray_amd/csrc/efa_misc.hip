@@ -254,8 +254,10 @@ hipError_t launch_phase_a_prep(long P, int M, const double* Yp, const double* ym
 // into the working rows -- the only read of the row -- and, for an ob the caller asked to assimilate, takes the two-pass variance
 // of the row (ddof 0) and keeps the ob iff d^2 <= t^2 (s2 + error), d = value - ym (a NaN rejects it).  The wave writes the
 // effective flag into BOTH device forms, the assimilate byte and the third double of the ob's {error, sqrt(error), assimilate, 0}
-// record, which the grid-stride pack copy therefore leaves out (pack bytes [skip_lo, skip_hi) -- no thread's 16-byte copy can
-// land on a flag another thread wrote).  `host_act`, when given, gets {0, 0, 0, requested flag} per ob: the coefficient-shaped
+// record, and the ob's value and error -- as given for an ob it keeps, the neutral (0, 1) and sqrt = 1 that the host writes for a
+// flag of 0 for an ob it rejects: a rejected ob is an unassimilated one in every word a kernel reads, a NaN value or error included.
+// The grid-stride pack copy therefore leaves all of that out (pack bytes [skip_lo, skip_hi) -- no thread's 16-byte copy can land
+// on a word another thread wrote).  `host_act`, when given, gets {0, 0, 0, requested flag} per ob: the coefficient-shaped
 // activity the one-pass sweep's list builders read, so the cached lists follow the caller's flags, not the check's outcome.
 __global__ __launch_bounds__(256) void k_phase_a_prep_qc(long P, int M, const double* __restrict__ Yp, const double* __restrict__ ym,
                                                          double* __restrict__ Yw, double* __restrict__ ymw, int carry_T,
@@ -273,6 +275,8 @@ __global__ __launch_bounds__(256) void k_phase_a_prep_qc(long P, int M, const do
   const double* h_error = reinterpret_cast<const double*>(hb + slot);
   const uint8_t* h_assim = reinterpret_cast<const uint8_t*>(hb + 2 * slot);
   const double* h_rec = reinterpret_cast<const double*>(hb + 3 * slot);
+  double* d_value = reinterpret_cast<double*>(db);
+  double* d_error = reinterpret_cast<double*>(db + slot);
   uint8_t* d_assim = reinterpret_cast<uint8_t*>(db + 2 * slot);
   double* d_rec = reinterpret_cast<double*>(db + 3 * slot);
   const int lane = threadIdx.x & 63;
@@ -310,9 +314,11 @@ __global__ __launch_bounds__(256) void k_phase_a_prep_qc(long P, int M, const do
     if (lane == 0) {
       ymw[k] = y;
       d_assim[k] = keep ? req : (uint8_t)0;
+      d_value[k] = keep ? value : 0.0;  // a rejected ob leaves what the host leaves for a flag of 0: the neutral pair
+      d_error[k] = keep ? error : 1.0;
     }
-    if (lane < 2) {  // the record as the host wrote it but its flag
-      reinterpret_cast<double2*>(d_rec + 4 * k)[lane] = lane ? make_double2(keep ? 1.0 : 0.0, rec.y) : rec;
+    if (lane < 2) {  // the record as the host wrote it but its flag (and the neutral error of a rejected ob)
+      reinterpret_cast<double2*>(d_rec + 4 * k)[lane] = lane ? make_double2(keep ? 1.0 : 0.0, rec.y) : keep ? rec : make_double2(1.0, 1.0);
       if (host_act) reinterpret_cast<double2*>(host_act + 4 * k)[lane] = make_double2(0.0, lane && req ? 1.0 : 0.0);
     }
   }
@@ -336,7 +342,7 @@ hipError_t launch_phase_a_prep_qc(long P, int M, const double* Yp, const double*
   if (traj && traj_words > work) work = traj_words;
   hipLaunchKernelGGL(k_phase_a_prep_qc, dim3(grid_for(work, 256 * 4)), dim3(256), 0, s, P, M, Yp, ym, Yw, ymw, carry_T, traj,
                      traj_words, sentinel, status, static_cast<const uint4*>(pack_host), static_cast<uint4*>(pack_dev), pack_bytes / 16,
-                     slot, 2 * slot / 16, 7 * slot / 16, threshold * threshold, host_act);
+                     slot, 0, 7 * slot / 16, threshold * threshold, host_act);
   return hipGetLastError();
 }
 

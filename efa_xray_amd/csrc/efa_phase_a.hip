@@ -124,15 +124,21 @@ int stage_obs_inputs(efa_ctx* c, ObsCall& a, const double* ob_value, const doubl
     EFA_TRY(c->pin_in.reserve(total));
     char* hb = static_cast<char*>(c->pin_in.p);
     char* db = static_cast<char*>(c->ob_pack.p);
-    std::memcpy(hb, ob_value, dP);
-    std::memcpy(hb + slot, ob_error, dP);
     std::memcpy(hb + 2 * slot, ob_assim, (size_t)P);
     {
+      // value and error of an ob that is not assimilated are not read (the reference skips it before it reads either,
+      // ensrf.py:74-76; the Python front end passes NaN for a None): the device gets the neutral pair (0, 1) in their place, so
+      // a kernel that gates the ob's gain with a zero factor never multiplies that zero by a NaN or an Inf
+      double* hv = reinterpret_cast<double*>(hb);
+      double* he = reinterpret_cast<double*>(hb + slot);
       double* ec = reinterpret_cast<double*>(hb + 3 * slot);
       for (long k = 0; k < P; ++k) {
-        ec[4 * k] = ob_error[k];
-        ec[4 * k + 1] = std::sqrt(ob_error[k]);
-        ec[4 * k + 2] = ob_assim[k] ? 1.0 : 0.0;
+        const bool on = ob_assim[k] != 0;
+        hv[k] = on ? ob_value[k] : 0.0;
+        he[k] = on ? ob_error[k] : 1.0;
+        ec[4 * k] = he[k];
+        ec[4 * k + 1] = on ? std::sqrt(he[k]) : 1.0;
+        ec[4 * k + 2] = on ? 1.0 : 0.0;
         ec[4 * k + 3] = 0.0;
       }
     }

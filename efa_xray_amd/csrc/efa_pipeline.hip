@@ -365,30 +365,35 @@ __global__ __launch_bounds__(kPT) void k_pipe(const PipeArgs a) {
     const bool active = __builtin_amdgcn_readfirstlane((int)(s45.y != 0.0)) != 0;  // wave-uniform
     const bool own_k = (k >= own0) && (k < own1) && (i_loc == (int)(k - own0));
     if (chain_wave) {
-      // ---- the serial chain of this step: ONE straight-line block so that the scheduler can
-      // interleave the long scalar chain (rsq/rcp + Newton) with the independent row update
-      double kc = dot * rM1;                              // :95
-      if (a.loc_mode != 0) kc = (live ? w : 0.0) * kc;    // :115
-      const double km = active ? kc * s23.y : 0.0;        // :119 (not assimilated: no update)
-      const double kb = s45.x * km;                       // :136
-      const double cov = __builtin_fma(dot, invM, -(rmean * s01.y));
-      const double var_rec = __builtin_fma(kb * kb, var_k, __builtin_fma(-2.0 * kb, cov, vfresh));
-      const double var_next = active ? var_rec : vfresh;  // one-step recurrence (see header)
-      xm = xm + km * s23.x;                               // :130
       Gain g;
-      if (!__any(pub && active && !(var_next > 0.01 * vfresh))) {
-        // fast path, one basic block: the gain chain is issued first and the independent
-        // row update fills its latency
-        g = gain_of(xm, var_next);
-        rmean = __builtin_fma(-kb, s01.y, rmean);
+      if (active) {
+        // ---- the serial chain of this step: ONE straight-line block so that the scheduler can
+        // interleave the long scalar chain (rsq/rcp + Newton) with the independent row update
+        double kc = dot * rM1;                              // :95
+        if (a.loc_mode != 0) kc = (live ? w : 0.0) * kc;    // :115
+        const double km = kc * s23.y;                       // :119
+        const double kb = s45.x * km;                       // :136
+        const double cov = __builtin_fma(dot, invM, -(rmean * s01.y));
+        const double var_next = __builtin_fma(kb * kb, var_k, __builtin_fma(-2.0 * kb, cov, vfresh));  // one-step recurrence (see header)
+        xm = xm + km * s23.x;                               // :130
+        if (!__any(pub && !(var_next > 0.01 * vfresh))) {
+          // fast path, one basic block: the gain chain is issued first and the independent
+          // row update fills its latency
+          g = gain_of(xm, var_next);
+          rmean = __builtin_fma(-kb, s01.y, rmean);
 #pragma unroll
-        for (int c = 0; c < 2 * NC; ++c) x[c] = __builtin_fma(-kb, y[c], x[c]);  // :141
+          for (int c = 0; c < 2 * NC; ++c) x[c] = __builtin_fma(-kb, y[c], x[c]);  // :141
+        } else {
+          // cancellation guard (rare): the recurrence lost digits, take the variance of the updated row
+          rmean = __builtin_fma(-kb, s01.y, rmean);
+#pragma unroll
+          for (int c = 0; c < 2 * NC; ++c) x[c] = __builtin_fma(-kb, y[c], x[c]);
+          g = gain_of(xm, fresh_var());
+        }
       } else {
-        // cancellation guard (rare): the recurrence lost digits, take the variance of the updated row
-        rmean = __builtin_fma(-kb, s01.y, rmean);
-#pragma unroll
-        for (int c = 0; c < 2 * NC; ++c) x[c] = __builtin_fma(-kb, y[c], x[c]);
-        g = gain_of(xm, fresh_var());
+        // :74-76, not assimilated: nothing of the record is applied -- a zero gain times the record's row, mean or
+        // innovation would turn a NaN or an Inf in them (an ob outside the domain) into a NaN in every row of this wave
+        g = gain_of(xm, vfresh);
       }
       EFA_STAMP(4);
       // recycling guard, amortised: once per kGuardEvery records, for that many records ahead

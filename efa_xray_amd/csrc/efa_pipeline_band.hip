@@ -439,7 +439,8 @@ __global__ __launch_bounds__(kGT) void k_pipe_band(const PipeArgs a) {
       // vector-chain kernel, which computes np.var as written.
       const double gjj0 = DEFER ? pm[2 * kRowsWG + lane] : G_s[lane * kRowsWG + lane];  // |y_j|^2 at block start
       const double thr = my_asm ? 1e-3 * gjj0 : -1.0;
-      bool bad = f_ob && !(pm[lane] * pm[lane] <= 1e-22 * fmin(ec_l.x, gjj0 * invM));  // pm[0][j]: the member mean of row j
+      // (the error variance of an ob that is not assimilated is not read: efa_hip.h; its record holds a neutral 1)
+      bool bad = f_ob && !(pm[lane] * pm[lane] <= 1e-22 * fmin(my_asm ? ec_l.x : __builtin_inf(), gjj0 * invM));  // pm[0][j]: the member mean of row j
       double l_xm = 0.0, l_innov = 0.0;
       double l_var = 0.0, l_rd = 0.0, l_be = 0.0;  // this lane's ob: prior variance, 1/kdenom, beta -- from G_kk at its step
       // Round 3: the ye rows of a record go to global memory straight from the vector wave that forms them (below, "owner"), so

@@ -361,7 +361,12 @@ __global__ __launch_bounds__(kGT) void k_pipe_gram(const PipeArgs a) {
       // only ACCUMULATED in the loop (one compare + two scalar ops per step) and acted upon after the block: a
       // tripped guard abandons the whole launch, so the numbers produced meanwhile are never used.
       const double thr_ld = my_asm ? 1e-3 * G_s[lane * kRowsWG + lane] : -1.0;
-      u64 bad = 0ull;
+      // centring guard, as the band leader's (efa_pipeline_band.hip): an ob row of the block, assimilated or not, whose member mean
+      // is not rounding residue (mean^2 above 1e-22 of its variance or, for an ob that is assimilated, of its error variance)
+      // sends the launch to the vector-chain kernel, which computes np.var as written.  A row that is not finite (an ob outside
+      // the domain) fails the comparison too: the downdate multiplies every pivot's row of G by the other rows' kb, and a zero kb
+      // does not stop a NaN.
+      u64 bad = __ballot(pre_ob && !(mu * mu <= 1e-22 * fmin(my_asm ? pre_err : __builtin_inf(), G_s[lane * kRowsWG + lane] * invM)));
       bool bailed = false;
 #ifdef EFA_PIPE_BLOCKTIME
       int slow_rows = 0;  // steps whose hand-over row was late

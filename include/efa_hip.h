@@ -266,6 +266,11 @@ int efa_forward_interp_dev(efa_ctx *ctx, long ncol, long col_lo, long col_hi,
  *   ob_value, ob_error (error VARIANCE, ensrf.py:79,91), ob_assim (0/1:
  *   Observation.assimilate_this, ensrf.py:74), and for EFA_LOC_GC ob_lat,
  *   ob_lon (degrees) and ob_halfwidth_km (Observation.localize_radius).
+ *   ob_value and ob_error of an ob with ob_assim 0 are not read (the
+ *   reference skips it before it reads either, ensrf.py:74-76): they may
+ *   hold anything, NaN and Inf included, and change no bit of any output.
+ *   The same holds in every entry point that takes these three arrays, and
+ *   for an ob the outlier check rejects.
  * Grid (host arrays, length ncol, degrees; EFA_LOC_GC only): lat/lon of each
  *   local column (ensemble.py:254-267 distance_to_point).
  * Diagnostics (host arrays, length P; written for every ob as the reference

@@ -6,7 +6,8 @@ most violations.  Three relations, on every route of tests/test_gpu_state_routes
      homogeneous of degree 0, and a power of two changes no mantissa.  No tolerance, no reference.
   2. State rows of NaN, +Inf, zeros or one constant change no other row's bits, the diagnostics or the obs block: the reads past
      what a lane owns (clamped tile loads, zero-padded MFMA K slots, obs applied with a zero taper) must be dropped, not
-     multiplied by zero.  The obs block stays the clean state's; nothing non-finite goes near Phase A.
+     multiplied by zero.  The obs block stays the clean state's; nothing non-finite goes near Phase A (that is
+     tests/test_gpu_obsprops.py, DESIGN.md 7n: NaN and Inf in the obs' values, errors and rows, through every Phase-A kernel).
   3. With obs and state rows of scales 1e-6..1e6 side by side every row and every ob agrees with the oracle to 1e-10 of ITS OWN
      scale (the generators keep the oracle's own error below 1e-12: tests/test_rowprops_host.py), and scaling ob k's
      (HX, value, error) by (2^j, 2^j, 4^j) leaves the state posterior's bits and scales the diagnostics exactly.
