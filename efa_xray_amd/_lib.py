@@ -130,6 +130,18 @@ SIGNATURES = {
                                                ctypes.c_long, ctypes.c_long, c_double_p, c_double_p, ctypes.c_void_p, ctypes.c_int,
                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.POINTER(ctypes.c_long), c_double_p, c_double_p]),
+    "efa_verify_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long,
+                                      ctypes.POINTER(ctypes.c_int), ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong),
+                                      ctypes.POINTER(ctypes.c_longlong), c_double_p]),
+    "efa_verify_f32_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long,
+                                          ctypes.POINTER(ctypes.c_int), ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong),
+                                          ctypes.POINTER(ctypes.c_longlong), c_double_p]),
     "efa_last_timing": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p,
                                        ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_int)]),
     "efa_fill_synthetic_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_int,
@@ -784,6 +796,34 @@ class Context(object):
             self._addr(var), self._addr(cov), self._addr(sens), self._addr(corr), self._addr(dvar), self._addr(score),
             prow.ctypes.data_as(ctypes.POINTER(ctypes.c_long)), _dp(psc), _dp(mv)))
         return prow, psc, mv
+
+    def verify(self, rows, M, X, verif, slab_group, ncol=None, n_lead=1, col_offset=0, ncol_total=None, col_weight=None,
+               fair=False, seed=0, below=None, equal=None, rank=None, crps=None, err=None, var=None, groups=True, f32=None):
+        """efa_verify_dev / efa_verify_f32_dev.  X (rows, M) is a device array of float64 or float32 members
+        (`f32` says which for a raw address; None: the DeviceArray's dtype) and verif (rows,) a float64 device array, both only
+        read; slab_group (n_lead,) is a host array of group numbers (-1: slab not verified); col_weight (ncol,) a float64
+        device array or None.  The fields below / equal / rank (int32) are raw device addresses (`malloc_bytes`) or None,
+        crps / err / var float64 device arrays or None.  Returns (hist (G, M+1), n (G,), n_bad (G,) int64, sums (G, 5)), or
+        None with groups=False (fields only)."""
+        sg = np.ascontiguousarray(slab_group, dtype=np.int32).reshape(-1)
+        if f32 is None:
+            f32 = isinstance(X, DeviceArray) and X.dtype == np.float32
+        fn = self.lib.efa_verify_f32_dev if f32 else self.lib.efa_verify_dev
+        ncol = int(rows if ncol is None else ncol)
+        G = int(sg.max()) + 1 if sg.size and sg.max() >= 0 else 0
+        hist = np.zeros((G, int(M) + 1), dtype=np.int64)
+        n = np.zeros(G, dtype=np.int64)
+        n_bad = np.zeros(G, dtype=np.int64)
+        sums = np.zeros((G, 5))
+        llp = ctypes.POINTER(ctypes.c_longlong)
+        out = (hist.ctypes.data_as(llp), n.ctypes.data_as(llp), n_bad.ctypes.data_as(llp), _dp(sums)) if groups else (None,) * 4
+        _check(self.lib, fn(
+            self.handle, int(rows), int(M), self._addr(X, np.float32 if f32 else np.float64), self._addr(verif), ncol,
+            int(n_lead), int(col_offset), int(ncol if ncol_total is None else ncol_total),
+            sg.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), self._addr(col_weight), 1 if fair else 0,
+            ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), self._addr(below, None), self._addr(equal, None),
+            self._addr(rank, None), self._addr(crps), self._addr(err), self._addr(var), *out))
+        return (hist, n, n_bad, sums) if groups else None
 
     def cov_contract_f32(self, N, M, P, Xbp_f32, Ye_f32, C_f32):
         """C (N x P) = Xbp (N x M) . Ye^T (P x M), float32, device addresses."""

@@ -213,6 +213,10 @@ int efa_ctx_set_option(efa_ctx* c, const char* key, long value) {
     }
     if (value > 0) EFA_HIP(efa::launch_occupy((int)c->dbg_occupy_blocks, 120 * 1024, (double)value, c->dbg_stream));
     else EFA_HIP(hipStreamSynchronize(c->dbg_stream));
+  } else if (!strcmp(key, "verify_blocks")) {
+    // grid cap of efa_verify_dev's pass (0: the default); the results do not depend on it
+    if (value < 0 || value > 2048) return fail(EFA_ERR_INVALID, "verify_blocks must be in [0,2048]");
+    c->verify_blocks = value;
   } else if (!strcmp(key, "threads_hint")) {
   } else {
     return fail(EFA_ERR_INVALID, "unknown option '%s'", key);
@@ -341,6 +345,8 @@ int efa_ctx_get_option(efa_ctx* c, const char* key, long* value) {
   else if (!strcmp(key, "stream_wall_us")) *value = c->st.wall_us;
   else if (!strcmp(key, "impact_us")) *value = c->impact_us;  // the last efa_obs_impact_dev (efa_impact.hip)
   else if (!strcmp(key, "sens_us")) *value = c->sens_us;  // the last efa_sensitivity_dev (efa_sensitivity.hip)
+  else if (!strcmp(key, "verify_us")) *value = c->verify_us;  // the last efa_verify_dev (efa_verify.hip)
+  else if (!strcmp(key, "verify_blocks")) *value = c->verify_blocks;
   else return fail(EFA_ERR_INVALID, "unknown option '%s'", key);
   return EFA_OK;
 }
@@ -668,6 +674,24 @@ int efa_sensitivity_f32_dev(efa_ctx* c, long rows, int M, int K, const float* X_
   EFA_TRY(use(c));
   return sensitivity(c, efa::Elem::f32, rows, M, K, X_dev, J, ncol, n_lead, slab_error, weights, cand_dev, n_targets, var_dev, cov_dev,
                      sens_dev, corr_dev, dvar_dev, score_dev, picked_row, picked_score, metric_var);
+}
+
+int efa_verify_dev(efa_ctx* c, long rows, int M, const double* X_dev, const double* verif_dev, long ncol, long n_lead,
+                   long col_offset, long ncol_total, const int* slab_group, const double* col_weight_dev, int fair, uint64_t seed,
+                   int* below_dev, int* equal_dev, int* rank_dev, double* crps_dev, double* err_dev, double* var_dev,
+                   long long* hist, long long* n, long long* n_bad, double* sums) {
+  EFA_TRY(use(c));
+  return verify(c, efa::Elem::f64, rows, M, X_dev, verif_dev, ncol, n_lead, col_offset, ncol_total, slab_group, col_weight_dev, fair,
+                seed, below_dev, equal_dev, rank_dev, crps_dev, err_dev, var_dev, hist, n, n_bad, sums);
+}
+
+int efa_verify_f32_dev(efa_ctx* c, long rows, int M, const float* X_dev, const double* verif_dev, long ncol, long n_lead,
+                       long col_offset, long ncol_total, const int* slab_group, const double* col_weight_dev, int fair,
+                       uint64_t seed, int* below_dev, int* equal_dev, int* rank_dev, double* crps_dev, double* err_dev,
+                       double* var_dev, long long* hist, long long* n, long long* n_bad, double* sums) {
+  EFA_TRY(use(c));
+  return verify(c, efa::Elem::f32, rows, M, X_dev, verif_dev, ncol, n_lead, col_offset, ncol_total, slab_group, col_weight_dev, fair,
+                seed, below_dev, equal_dev, rank_dev, crps_dev, err_dev, var_dev, hist, n, n_bad, sums);
 }
 
 int efa_last_timing(efa_ctx* c, double* state_ms, double* obs_ms, long* state_launches, int* path_taken) {

@@ -5,6 +5,7 @@
 //   efa_stream.hip   the streamed host-memory update
 //   efa_impact.hip   observation impact: its kernels and the driver of efa_obs_impact_dev
 //   efa_sensitivity.hip  ensemble sensitivity and observation targeting: its kernels and the driver of efa_sensitivity_dev
+//   efa_verify.hip   ensemble verification: its kernels and the driver of efa_verify_dev
 //   efa_comm.hip     RCCL
 // One call's arguments and results travel as arguments and return values; the context (efa_ctx.h) holds settings, caches,
 // workspaces and what the last obs phase left for the state phase.  A state call's rows travel with their element type (StateRows);
@@ -126,5 +127,12 @@ int sensitivity(efa_ctx* c, Elem elem, long rows, int M, int K, const void* X_de
                 const double* slab_error, const double* weights, const uint8_t* cand_dev, int n_targets, double* var_dev,
                 double* cov_dev, double* sens_dev, double* corr_dev, double* dvar_dev, double* score_dev, long* picked_row,
                 double* picked_score, double* metric_var);
+
+// ---- efa_verify.hip -----------------------------------------------------------------------------------------------------------
+// efa_verify_dev / _f32_dev: checks, the pass and the reduction of its partials; waits before it returns
+int verify(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, const double* verif_dev, long ncol, long n_lead,
+           long col_offset, long ncol_total, const int* slab_group, const double* col_weight_dev, int fair, uint64_t seed,
+           int* below_dev, int* equal_dev, int* rank_dev, double* crps_dev, double* err_dev, double* var_dev, long long* hist,
+           long long* n, long long* n_bad, double* sums);
 
 }  // namespace efa_host

@@ -1,0 +1,520 @@
+// Ensemble verification against a gridded verifying state (Hamill 2001, Hersbach 2000, Ferro 2014).
+//   For every state row i = lead*ncol + col with members x_i1..x_iM and a verifying value y_i: the number of members below and
+//   equal to y, the rank of y among them (ties broken by a counter-based hash of (seed, global row)), the error of the ensemble
+//   mean, the ensemble variance and the CRPS -- every float from the once-rounded d_m = x_im - y_i, in float64 -- and per group of
+//   slabs the rank histogram, the counts and the weighted sums of the three.
+//
+// k_verify reads every row once, in the row layout of k_sens_pass (efa_sensitivity.hip): a wave owns a tile of 16 consecutive rows
+// of one slab; lane l = (g = l>>4, n = l&15) loads members {8u+2g, 8u+2g+1} of row n with one 16-byte load (8-byte for float32
+// rows, widened as they arrive), so slot c = 2u + e of lane g is member 8u + 2g + e and the whole row sits in registers, 2 NU
+// doubles per lane.  below / equal / sum d / sum |d| / sum (d - err)^2 are lane-local plus two __shfl_xor steps.
+//
+// The CRPS needs the sorted d.  NU is a power of two, so a lane's LP = 2 NU slots are a power of two as well; slots beyond M hold
+// +inf.  Every lane sorts its slots with a bitonic network whose comparators all point upwards, and the row's four lanes are
+// merged by two bitonic stages: (g, g^1) exchange slot LP-1-k for slot k, the lower lane keeps the smaller; then (g, 3-g)
+// likewise across the two pairs, a same-slot step inside each pair, and after each stage a lane-local bitonic merge.  Afterwards
+// sorted position j = g LP + k is slot k of lane g, the +inf slots are the positions >= M, and every register index is a
+// compile-time constant.
+//
+// Sums: a chunk is kVerChunkTiles tiles of one slab, whatever the grid; wave w takes its tiles w, w+4, ... in order, lane n adds
+// its rows up, and the 64 lane sums of the chunk are added in index order into the chunk's partial.  k_verify_reduce adds the
+// partials of each group in a fixed order.  So the float sums depend on neither the grid nor the schedule; the histogram is
+// integer adds in LDS and integer atomics in memory, whose result no order can change.  No floating-point atomics.
+#include "efa_device.h"
+#include "efa_driver.h"
+
+#include <cmath>
+#include <vector>
+
+namespace efa {
+namespace {
+
+constexpr int kVerThreads = 256;     // 4 waves, one 16-row tile per wave and trip
+constexpr int kVerBlocks = 2048;     // default grid cap of k_verify (option "verify_blocks" lowers it)
+constexpr int kVerChunkTiles = 64;   // tiles per chunk: 1024 rows give one partial
+constexpr int kVerSums = 5;          // sum w, w crps, w err, w err^2, w var
+constexpr long kVerFlushChunks = 1L << 20;  // the LDS histogram (32-bit) goes to memory at least this often: < 2^31 rows
+
+struct VerArgs {
+  const void* X;
+  const double* verif;   // [rows]
+  const double* colw;    // [ncol] or null
+  const int* sgroup;     // [n_lead], device copy
+  long ncol, n_lead, col_offset, ncol_total;
+  long nchunks, cps;     // chunks in all, chunks per slab
+  int M, fair, al;       // al: the rows are aligned for the paired loads
+  unsigned long long seed;
+  int *below, *equal, *rank;   // [rows] each, or null
+  double *crps, *err, *var;
+  double* part;                // [nchunks][kVerSums]
+  long long* cnt;              // [nchunks][2]: verified good rows, verified bad rows
+  unsigned long long* hist;    // [G][M + 1]
+};
+
+template <typename E>
+struct VerPair;
+template <>
+struct VerPair<double> { typedef double2 type; };
+template <>
+struct VerPair<float> { typedef float2 type; };
+
+__device__ __forceinline__ bool ver_finite(double v) { return __builtin_fabs(v) < __builtin_inf(); }
+
+// the tie-break: splitmix64 of the global row, scaled to [0, equal]
+__device__ __forceinline__ int ver_pick(unsigned long long seed, unsigned long long R, int equal) {
+  unsigned long long z = seed + (R + 1ull) * 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return (int)(((z >> 32) * (unsigned long long)(equal + 1)) >> 32);
+}
+
+#define VER_CMPX(a, b)                     \
+  {                                        \
+    const double lo_ = __builtin_fmin(a, b); \
+    const double hi_ = __builtin_fmax(a, b); \
+    a = lo_;                               \
+    b = hi_;                               \
+  }
+
+// sorts d[0..LP-1] upwards (LP a power of two)
+template <int LP>
+__device__ __forceinline__ void ver_sort_local(double (&d)[LP]) {
+#pragma unroll
+  for (int k = 2; k <= LP; k <<= 1) {
+#pragma unroll
+    for (int i = 0; i < LP; ++i) {
+      const int l = i ^ (k - 1);
+      if (l > i) VER_CMPX(d[i], d[l]);
+    }
+    __builtin_amdgcn_sched_barrier(0);  // (layer by layer: the scheduler otherwise spreads the network over every register)
+#pragma unroll
+    for (int j = k >> 2; j > 0; j >>= 1) {
+#pragma unroll
+      for (int i = 0; i < LP; ++i) {
+        const int l = i ^ j;
+        if (l > i) VER_CMPX(d[i], d[l]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+}
+
+// sorts a bitonic d[0..LP-1] upwards
+template <int LP>
+__device__ __forceinline__ void ver_merge_local(double (&d)[LP]) {
+#pragma unroll
+  for (int j = LP >> 1; j > 0; j >>= 1) {
+#pragma unroll
+    for (int i = 0; i < LP; ++i) {
+      const int l = i ^ j;
+      if (l > i) VER_CMPX(d[i], d[l]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// two sorted lanes (this one and lane ^ mask) -> the lower keeps the LP smaller values, the upper the LP larger, each bitonic
+template <int LP>
+__device__ __forceinline__ void ver_split_rev(double (&d)[LP], int mask, bool upper) {
+#pragma unroll
+  for (int k = 0; k < LP / 2; ++k) {
+    const int kk = LP - 1 - k;
+    const double t1 = __shfl_xor(d[kk], mask, 64);
+    const double t2 = __shfl_xor(d[k], mask, 64);
+    d[k] = ((d[k] < t1) != upper) ? d[k] : t1;
+    d[kk] = ((d[kk] < t2) != upper) ? d[kk] : t2;
+    if ((k & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // (a few exchanges in flight, not all of them)
+  }
+}
+
+// the first step of a bitonic merge over two lanes: same slot
+template <int LP>
+__device__ __forceinline__ void ver_split_same(double (&d)[LP], int mask, bool upper) {
+#pragma unroll
+  for (int k = 0; k < LP; ++k) {
+    const double t = __shfl_xor(d[k], mask, 64);
+    d[k] = ((d[k] < t) != upper) ? d[k] : t;
+    if ((k & 7) == 7) __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// NU: chunks of 8 members the lanes hold, (M + 7) / 8 rounded up to a power of two: the sort network is that of LP = 2 NU slots
+// whatever M is, so the six sizes are the only instantiations; which slots hold members is decided from M as the kernel runs
+template <int NU, typename E>
+__global__ __launch_bounds__(kVerThreads) void k_verify(const VerArgs a) {
+  constexpr int LP = 2 * NU;
+  static_assert((NU & (NU - 1)) == 0, "the bitonic network needs a power of two");
+  __shared__ unsigned int hist_s[kMaxMembers + 1];
+  __shared__ double red_s[4 * 16 * kVerSums];
+  __shared__ int cnt_s[4 * 16 * 2];
+  const int M = a.M;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wv = tid >> 6;
+  const int g = lane >> 4, n = lane & 15;
+  const double inf = __builtin_inf();
+  const double nan = __builtin_nan("");
+  const double dM = (double)M;
+  const double D = a.fair ? dM * (double)(M - 1) : dM * dM;
+  const long tps = (a.ncol + 15) / 16;
+  const bool fields = a.below || a.equal || a.rank || a.crps || a.err || a.var;
+
+  for (int i = tid; i <= M; i += kVerThreads) hist_s[i] = 0u;
+  __syncthreads();
+  int cur_g = -1;  // the group the LDS histogram belongs to
+  long since = 0;
+
+#pragma unroll 1
+  for (long ch = blockIdx.x; ch < a.nchunks; ch += gridDim.x) {
+    const long lead = ch / a.cps, cc = ch % a.cps;
+    const int sg = a.sgroup[lead];
+    if (sg != cur_g || since >= kVerFlushChunks) {  // (uniform)
+      __syncthreads();
+      if (cur_g >= 0)
+        for (int i = tid; i <= M; i += kVerThreads) {
+          const unsigned int v = hist_s[i];
+          if (v) atomicAdd(&a.hist[(size_t)cur_g * (M + 1) + i], (unsigned long long)v);
+          hist_s[i] = 0u;
+        }
+      __syncthreads();
+      cur_g = sg;
+      since = 0;
+    }
+    ++since;
+    const long t0 = cc * kVerChunkTiles;
+    const long t1 = (t0 + kVerChunkTiles < tps) ? t0 + kVerChunkTiles : tps;
+    double acc[kVerSums] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    int n_good = 0, n_bad = 0;
+
+#pragma unroll 1
+    for (long tl = t0 + wv; tl < t1; tl += kVerThreads / 64) {
+      const long col = tl * 16 + n;
+      const bool live = col < a.ncol;
+      const long colc = live ? col : a.ncol - 1;
+      const long r = lead * a.ncol + colc;
+      if (sg < 0) {  // (uniform) a slab that is not verified: only the fields are written
+        if (fields && g == 0 && live) {
+          if (a.below) a.below[r] = -1;
+          if (a.equal) a.equal[r] = -1;
+          if (a.rank) a.rank[r] = -1;
+          if (a.crps) a.crps[r] = nan;
+          if (a.err) a.err[r] = nan;
+          if (a.var) a.var[r] = nan;
+        }
+        continue;
+      }
+      // the lane's quarter of the row again, opaque to the optimiser: what depends only on it and on M (the LP weights 2j - M + 1,
+      // the LP slot predicates) is otherwise hoisted out of this loop and held in registers across it, which sent NU = 32 to scratch
+      int gq = lane >> 4;
+      asm volatile("" : "+v"(gq));
+      const double y = a.verif[r];
+      const double w = a.colw ? a.colw[colc] : 1.0;
+      double d[LP];
+      {  // clamped addresses, no branches: the loads of a tile are issued together
+        const E* p = reinterpret_cast<const E*>(a.X) + (size_t)r * M;
+        if (a.al) {
+#pragma unroll
+          for (int u = 0; u < NU; ++u) {
+            int m0 = 8 * u + 2 * gq;
+            m0 = (m0 < M) ? m0 : M - 2;
+            const typename VerPair<E>::type v = *reinterpret_cast<const typename VerPair<E>::type*>(p + m0);
+            d[2 * u] = v.x;
+            d[2 * u + 1] = v.y;
+          }
+        } else {
+#pragma unroll
+          for (int u = 0; u < NU; ++u) {
+            const int m0 = 8 * u + 2 * gq;
+            d[2 * u] = p[(m0 < M) ? m0 : M - 1];
+            d[2 * u + 1] = p[(m0 + 1 < M) ? m0 + 1 : M - 1];
+          }
+        }
+      }
+      int lb = 0, le = 0;
+      bool badl = false;
+      double s4[4] = {0.0, 0.0, 0.0, 0.0}, a4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int c = 0; c < LP; ++c) {
+        const bool ok = 8 * (c >> 1) + 2 * gq + (c & 1) < M;  // the slot holds a real member
+        const double xv = d[c];
+        lb += (ok && xv < y) ? 1 : 0;
+        le += (ok && xv == y) ? 1 : 0;
+        const double dv = xv - y;
+        badl = badl || (ok && !ver_finite(dv));
+        s4[c & 3] += ok ? dv : 0.0;
+        a4[c & 3] += ok ? __builtin_fabs(dv) : 0.0;
+        d[c] = ok ? dv : inf;
+      }
+      const double d0 = __shfl(d[0], n, 64);  // member 0
+      bool diff = false;
+#pragma unroll
+      for (int c = 0; c < LP; ++c) {
+        const bool ok = 8 * (c >> 1) + 2 * gq + (c & 1) < M;  // the slot holds a real member
+        diff = diff || (ok && d[c] != d0);
+      }
+      double sum = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+      double asum = (a4[0] + a4[1]) + (a4[2] + a4[3]);
+      sum += __shfl_xor(sum, 16, 64);
+      sum += __shfl_xor(sum, 32, 64);
+      asum += __shfl_xor(asum, 16, 64);
+      asum += __shfl_xor(asum, 32, 64);
+      lb += __shfl_xor(lb, 16, 64);
+      lb += __shfl_xor(lb, 32, 64);
+      le += __shfl_xor(le, 16, 64);
+      le += __shfl_xor(le, 32, 64);
+      const unsigned long long quad = 0x0001000100010001ull;
+      const bool varies = ((__ballot(diff) >> n) & quad) != 0ull;
+      const bool bad = ((__ballot(badl) >> n) & quad) != 0ull;
+      // the error of the mean; a row whose members are all equal has deviations of exactly 0 (its sum / M need not give d back)
+      const double err = varies ? sum / dM : d0;
+      double q4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int c = 0; c < LP; ++c) {
+        const bool ok = 8 * (c >> 1) + 2 * gq + (c & 1) < M;  // the slot holds a real member
+        const double e = ok ? d[c] - err : 0.0;
+        q4[c & 3] = __builtin_fma(e, e, q4[c & 3]);
+      }
+      double ss = (q4[0] + q4[1]) + (q4[2] + q4[3]);
+      ss += __shfl_xor(ss, 16, 64);
+      ss += __shfl_xor(ss, 32, 64);
+      const double var = ss / (double)(M - 1);
+
+      __builtin_amdgcn_sched_barrier(0);
+      // the sort: afterwards sorted position g LP + k is slot k of lane g
+      ver_sort_local<LP>(d);
+      ver_split_rev<LP>(d, 16, (gq & 1) != 0);
+      ver_merge_local<LP>(d);
+      ver_split_rev<LP>(d, 48, gq >= 2);
+      ver_split_same<LP>(d, 16, (gq & 1) != 0);
+      ver_merge_local<LP>(d);
+      double t4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int k = 0; k < LP; ++k) {
+        const int j = gq * LP + k;
+        t4[k & 3] = __builtin_fma((double)(2 * j - M + 1), (j < M) ? d[k] : 0.0, t4[k & 3]);
+      }
+      double ts = (t4[0] + t4[1]) + (t4[2] + t4[3]);
+      ts += __shfl_xor(ts, 16, 64);
+      ts += __shfl_xor(ts, 32, 64);
+      const double crps = asum / dM - ts / D;
+
+      if (gq == 0 && live) {
+        const bool verified = ver_finite(y) && w > 0.0;
+        const bool good = verified && !bad;
+        int rank = -1;
+        if (good) {
+          const unsigned long long R =
+              (unsigned long long)lead * (unsigned long long)a.ncol_total + (unsigned long long)(a.col_offset + col);
+          rank = lb + ver_pick(a.seed, R, le);
+          atomicAdd(&hist_s[rank], 1u);
+          acc[0] += w;
+          acc[1] += w * crps;
+          acc[2] += w * err;
+          acc[3] += w * (err * err);
+          acc[4] += w * var;
+          ++n_good;
+        } else if (verified) {
+          ++n_bad;
+        }
+        if (fields) {
+          if (a.below) a.below[r] = good ? lb : -1;
+          if (a.equal) a.equal[r] = good ? le : -1;
+          if (a.rank) a.rank[r] = rank;
+          if (a.crps) a.crps[r] = good ? crps : nan;
+          if (a.err) a.err[r] = good ? err : nan;
+          if (a.var) a.var[r] = good ? var : nan;
+        }
+      }
+    }
+
+    // the chunk's partial: the 64 lane sums in index order
+    if (g == 0) {
+#pragma unroll
+      for (int k = 0; k < kVerSums; ++k) red_s[(wv * 16 + n) * kVerSums + k] = acc[k];
+      cnt_s[(wv * 16 + n) * 2] = n_good;
+      cnt_s[(wv * 16 + n) * 2 + 1] = n_bad;
+    }
+    __syncthreads();
+    if (tid < kVerSums) {
+      double s = 0.0;
+      for (int i = 0; i < 64; ++i) s += red_s[i * kVerSums + tid];
+      a.part[(size_t)ch * kVerSums + tid] = s;
+    } else if (tid < kVerSums + 2) {
+      long long s = 0;
+      for (int i = 0; i < 64; ++i) s += cnt_s[i * 2 + (tid - kVerSums)];
+      a.cnt[(size_t)ch * 2 + (tid - kVerSums)] = s;
+    }
+    __syncthreads();
+  }
+
+  __syncthreads();
+  if (cur_g >= 0)
+    for (int i = tid; i <= M; i += kVerThreads) {
+      const unsigned int v = hist_s[i];
+      if (v) atomicAdd(&a.hist[(size_t)cur_g * (M + 1) + i], (unsigned long long)v);
+    }
+}
+
+// workgroup g: the partials of the chunks of group g, thread by thread in chunk order, then a tree over the threads
+__global__ __launch_bounds__(kVerThreads) void k_verify_reduce(long nchunks, long cps, const int* __restrict__ sgroup,
+                                                               const double* __restrict__ part, const long long* __restrict__ cnt,
+                                                               double* __restrict__ sums, long long* __restrict__ n_out,
+                                                               long long* __restrict__ nbad_out) {
+  __shared__ double s_s[kVerThreads];
+  __shared__ long long c_s[kVerThreads];
+  const int tid = threadIdx.x;
+  const int grp = (int)blockIdx.x;
+  for (int k = 0; k < kVerSums + 2; ++k) {
+    double s = 0.0;
+    long long c = 0;
+    for (long i = tid; i < nchunks; i += kVerThreads) {
+      if (sgroup[i / cps] != grp) continue;
+      if (k < kVerSums) s += part[(size_t)i * kVerSums + k];
+      else c += cnt[(size_t)i * 2 + (k - kVerSums)];
+    }
+    s_s[tid] = s;
+    c_s[tid] = c;
+    __syncthreads();
+    for (int off = kVerThreads / 2; off >= 1; off >>= 1) {
+      if (tid < off) {
+        s_s[tid] += s_s[tid + off];
+        c_s[tid] += c_s[tid + off];
+      }
+      __syncthreads();
+    }
+    if (tid == 0) {
+      if (k < kVerSums) sums[(size_t)grp * kVerSums + k] = s_s[0];
+      else if (k == kVerSums) n_out[grp] = c_s[0];
+      else nbad_out[grp] = c_s[0];
+    }
+    __syncthreads();
+  }
+}
+
+hipError_t launch_verify(const VerArgs& a, Elem elem, int blocks, hipStream_t s) {
+  if (a.M < 2 || a.M > kMaxMembers) return hipErrorInvalidValue;
+  if (a.nchunks <= 0) return hipSuccess;
+  long grid = a.nchunks < blocks ? a.nchunks : blocks;
+  if (grid < 1) grid = 1;
+  int nu_p = 1;
+  while (nu_p * 8 < a.M) nu_p *= 2;
+  return dispatch_width(nu_p, std::integer_sequence<int, 1, 2, 4, 8, 16, 32>{}, [&](auto nu_c) {
+    constexpr int nu = decltype(nu_c)::value;
+    if (elem == Elem::f32) hipLaunchKernelGGL((k_verify<nu, float>), dim3((unsigned)grid), dim3(kVerThreads), 0, s, a);
+    else hipLaunchKernelGGL((k_verify<nu, double>), dim3((unsigned)grid), dim3(kVerThreads), 0, s, a);
+    return hipGetLastError();
+  });
+}
+
+}  // namespace
+}  // namespace efa
+
+// ---- the host side of efa_verify_dev / efa_verify_f32_dev ----------------------------------------------------------------------
+namespace efa_host {
+
+using namespace efa;
+
+// Like efa_obs_impact_dev and efa_sensitivity_dev the call works in a buffer of its own (ver_ws) and neither reads nor writes what
+// a later cycle reads.  Nothing is written to the caller's arrays before every check has passed.
+int verify(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, const double* verif_dev, long ncol, long n_lead,
+           long col_offset, long ncol_total, const int* slab_group, const double* col_weight_dev, int fair, uint64_t seed,
+           int* below_dev, int* equal_dev, int* rank_dev, double* crps_dev, double* err_dev, double* var_dev, long long* hist,
+           long long* n, long long* n_bad, double* sums) {
+  const char* me = elem == Elem::f32 ? "efa_verify_f32_dev" : "efa_verify_dev";
+  if (M < 2 || M > kMaxMembers) return fail(EFA_ERR_INVALID, "%s: M=%d must be in [2,%d]", me, M, kMaxMembers);
+  if (rows < 0 || ncol < 0 || n_lead < 0) return fail(EFA_ERR_INVALID, "%s: negative size", me);
+  if (ncol * n_lead != rows) return fail(EFA_ERR_INVALID, "%s: rows=%ld must equal n_lead*ncol = %ld*%ld", me, rows, n_lead, ncol);
+  if (col_offset < 0 || col_offset + ncol > ncol_total)
+    return fail(EFA_ERR_INVALID, "%s: columns [%ld, %ld) do not lie in [0, ncol_total=%ld)", me, col_offset, col_offset + ncol,
+                ncol_total);
+  if (!X_dev || !verif_dev) return fail(EFA_ERR_INVALID, "%s: null device pointer", me);
+  if (!slab_group) return fail(EFA_ERR_INVALID, "%s: null slab_group", me);
+  int G = 0;
+  for (long s = 0; s < n_lead; ++s) {
+    if (slab_group[s] < -1) return fail(EFA_ERR_INVALID, "%s: slab_group[%ld] = %d must be >= -1", me, s, slab_group[s]);
+    if (slab_group[s] + 1 > G) G = slab_group[s] + 1;
+  }
+  const bool no_groups = !hist && !n && !n_bad && !sums;  // fields only
+  if (G > 0 && !no_groups && (!hist || !n || !n_bad || !sums))
+    return fail(EFA_ERR_INVALID, "%s: hist, n, n_bad and sums go together (all null: fields only)", me);
+
+  c->verify_us = 0;
+  const size_t nh = (size_t)G * (M + 1);
+  std::vector<long long> h_int(nh + 2 * (size_t)G, 0);
+  std::vector<double> h_sums((size_t)G * kVerSums, 0.0);
+  if (rows > 0) {
+    hipStream_t s = c->stream;
+    const long tps = (ncol + 15) / 16;
+    const long cps = (tps + kVerChunkTiles - 1) / kVerChunkTiles;
+    const long nchunks = cps * n_lead;
+    const int Gd = G > 0 ? G : 1;
+    // ver_ws: part [nchunks][5] | sums [Gd][5] | cnt [nchunks][2] | hist [Gd][M+1] | n [Gd] | n_bad [Gd] | slab groups [n_lead]
+    const size_t n_part = (size_t)nchunks * kVerSums, n_sums = (size_t)Gd * kVerSums, n_cnt = (size_t)nchunks * 2,
+                 n_hist = (size_t)Gd * (M + 1);
+    EFA_TRY(c->ver_ws.reserve((n_part + n_sums + n_cnt + n_hist + 2 * (size_t)Gd) * 8 + (size_t)n_lead * sizeof(int)));
+    if (!c->ver_iv.begin.h) EFA_HIP(hipEventCreate(&c->ver_iv.begin.h));
+    if (!c->ver_iv.end.h) EFA_HIP(hipEventCreate(&c->ver_iv.end.h));
+    double* d_part = c->ver_ws.as<double>();
+    double* d_sums = d_part + n_part;
+    long long* d_cnt = reinterpret_cast<long long*>(d_sums + n_sums);
+    long long* d_hist = d_cnt + n_cnt;
+    long long* d_n = d_hist + n_hist;
+    long long* d_nbad = d_n + Gd;
+    int* d_sg = reinterpret_cast<int*>(d_nbad + Gd);
+    EFA_HIP(hipMemcpyAsync(d_sg, slab_group, (size_t)n_lead * sizeof(int), hipMemcpyHostToDevice, s));
+    EFA_HIP(hipMemsetAsync(d_hist, 0, n_hist * sizeof(long long), s));
+    VerArgs a{};
+    a.X = X_dev;
+    a.verif = verif_dev;
+    a.colw = col_weight_dev;
+    a.sgroup = d_sg;
+    a.ncol = ncol;
+    a.n_lead = n_lead;
+    a.col_offset = col_offset;
+    a.ncol_total = ncol_total;
+    a.nchunks = nchunks;
+    a.cps = cps;
+    a.M = M;
+    a.fair = fair ? 1 : 0;
+    a.al = (M % 2 == 0) && (reinterpret_cast<uintptr_t>(X_dev) % (2 * elem_size(elem)) == 0);
+    a.seed = seed;
+    a.below = below_dev;
+    a.equal = equal_dev;
+    a.rank = rank_dev;
+    a.crps = crps_dev;
+    a.err = err_dev;
+    a.var = var_dev;
+    a.part = d_part;
+    a.cnt = d_cnt;
+    a.hist = reinterpret_cast<unsigned long long*>(d_hist);
+    long blocks = c->verify_blocks;
+    if (blocks < 1 || blocks > kVerBlocks) blocks = kVerBlocks;
+    EFA_HIP(hipEventRecord(c->ver_iv.begin, s));
+    EFA_HIP(launch_verify(a, elem, (int)blocks, s));
+    hipLaunchKernelGGL(k_verify_reduce, dim3((unsigned)Gd), dim3(kVerThreads), 0, s, nchunks, cps, d_sg, d_part, d_cnt, d_sums, d_n,
+                       d_nbad);
+    EFA_HIP(hipGetLastError());
+    EFA_HIP(hipEventRecord(c->ver_iv.end, s));
+    if (G > 0) {
+      EFA_HIP(hipMemcpyAsync(h_int.data(), d_hist, nh * sizeof(long long), hipMemcpyDeviceToHost, s));
+      EFA_HIP(hipMemcpyAsync(h_int.data() + nh, d_n, (size_t)G * sizeof(long long), hipMemcpyDeviceToHost, s));
+      EFA_HIP(hipMemcpyAsync(h_int.data() + nh + G, d_nbad, (size_t)G * sizeof(long long), hipMemcpyDeviceToHost, s));
+      EFA_HIP(hipMemcpyAsync(h_sums.data(), d_sums, h_sums.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    EFA_HIP(hipStreamSynchronize(s));
+    float ms = 0.f;
+    EFA_HIP(hipEventElapsedTime(&ms, c->ver_iv.begin, c->ver_iv.end));
+    c->verify_us = (long)std::llround((double)ms * 1000.0);
+  }
+  if (G > 0 && !no_groups) {
+    for (size_t i = 0; i < nh; ++i) hist[i] = h_int[i];
+    for (int g = 0; g < G; ++g) {
+      n[g] = h_int[nh + g];
+      n_bad[g] = h_int[nh + G + g];
+    }
+    for (size_t i = 0; i < h_sums.size(); ++i) sums[i] = h_sums[i];
+  }
+  return EFA_OK;
+}
+
+}  // namespace efa_host

@@ -97,7 +97,8 @@ int efa_ctx_set_stream(efa_ctx *ctx, void *hip_stream);
  *          "gc_active_pairs"
  *          ((column, ob) pairs with a non-zero taper in the last one-pass sweep),
  *          "f32_native" (see efa_state_cycle_f32_dev), "impact_us" (see efa_obs_impact_dev),
- *          "sens_us" (see efa_sensitivity_dev) */
+ *          "sens_us" (see efa_sensitivity_dev), "verify_us" (see efa_verify_dev);
+ *          "verify_blocks" (grid cap of efa_verify_dev's pass, 0 = the default of 2048; results do not depend on it) */
 int efa_ctx_set_option(efa_ctx *ctx, const char *key, long value);
 int efa_ctx_get_option(efa_ctx *ctx, const char *key, long *value);
 
@@ -591,6 +592,65 @@ int efa_sensitivity_f32_dev(efa_ctx *ctx, long rows, int M, int K, const float *
                             double *cov_dev, double *sens_dev, double *corr_dev,
                             double *dvar_dev, double *score_dev, long *picked_row,
                             double *picked_score, double *metric_var);
+
+/* ---- ensemble verification: rank histogram, CRPS, spread and skill per row (Hamill 2001, Hersbach 2000, Ferro 2014) ----
+ * Asked once a verifying state exists: is the ensemble calibrated?
+ *   X_dev [rows][M]   state members (float64; float32 for the _f32 twin, every
+ *                     number computed in float64 as DESIGN.md 7g has it), row
+ *                     i = lead*ncol + col, rows = n_lead*ncol (to_vect() order)
+ *   verif_dev [rows]  the verifying value y_i of every row; not finite: the row
+ *                     is not verified
+ *   slab_group [n_lead] (host) the group g >= 0 whose statistics slab `lead`
+ *                     adds to, or -1: the slab is not verified.  G = 1 + max
+ *   col_weight_dev [ncol] (NULL: all 1) the weight w of every row of a column;
+ *                     a row counts only where w > 0
+ *   col_offset, ncol_total  the columns are columns col_offset .. col_offset +
+ *                     ncol - 1 of a state of ncol_total columns (a whole state:
+ *                     0, ncol): the tie-break below then agrees across shards
+ * A row is VERIFIED when y_i is finite, w > 0 and its slab's group is >= 0.  A
+ * verified row is BAD when a member, or a d_m = x_im - y_i (rounded once, in
+ * float64), is not finite: bad rows are counted, never summed.  For a good row:
+ *   below = #{m: x_im < y_i}, equal = #{m: x_im == y_i} (IEEE: -0.0 == 0.0)
+ *   rank  = below + pick, pick in [0, equal] from (seed, R = lead*ncol_total +
+ *           col_offset + col) alone: z = seed + (R+1) 0x9E3779B97F4A7C15;
+ *           z = (z ^ z>>30) 0xBF58476D1CE4E5B9; z = (z ^ z>>27) 0x94D049BB133111EB;
+ *           z ^= z>>31 (mod 2^64); pick = ((z>>32) (equal+1)) >> 32
+ *   err   = (sum d_m)/M, the error of the ensemble mean
+ *   var   = sum (d_m - err)^2/(M-1); exactly 0.0 when all members are equal
+ *   crps  = (sum |d_m|)/M - (sum_j (2j - M + 1) d_(j))/D with d_(0) <= .. <=
+ *           d_(M-1) the sorted d and D = M^2, or M(M-1) when `fair` is set
+ * Fields (device, [rows], each may be NULL = not wanted; written for EVERY
+ * row): below, equal, rank (int, -1 where the row is not verified or bad),
+ * crps, err, var (double, NaN there).
+ * Group outputs (host): hist [G][M+1] counts of rank, n [G] good rows, n_bad
+ * [G] bad rows, sums [G][5] = sum w, sum w crps, sum w err, sum w err^2,
+ * sum w var over the good rows.  All four NULL: fields only.
+ * One pass reads every row once and sorts it in registers; per-chunk partial
+ * sums are reduced in a fixed order by a second small kernel, and there are no
+ * floating-point atomics: the same inputs give the same bits, whatever the
+ * grid.  The call uses a workspace of its own and leaves everything a later
+ * cycle reads as it found it, like efa_obs_impact_dev; it synchronises before
+ * returning.
+ * EFA_ERR_INVALID, before any launch and with no output written: a NULL ctx,
+ * X_dev, verif_dev or slab_group, M < 2 or M > 256, rows != n_lead*ncol,
+ * col_offset < 0 or col_offset + ncol > ncol_total, a slab_group entry < -1,
+ * some but not all of hist / n / n_bad / sums NULL while a group exists.
+ * Read-only option "verify_us": device time (microseconds, HIP events) of the
+ * last call. */
+int efa_verify_dev(efa_ctx *ctx, long rows, int M, const double *X_dev,
+                   const double *verif_dev, long ncol, long n_lead,
+                   long col_offset, long ncol_total, const int *slab_group,
+                   const double *col_weight_dev, int fair, uint64_t seed,
+                   int *below_dev, int *equal_dev, int *rank_dev,
+                   double *crps_dev, double *err_dev, double *var_dev,
+                   long long *hist, long long *n, long long *n_bad, double *sums);
+int efa_verify_f32_dev(efa_ctx *ctx, long rows, int M, const float *X_dev,
+                       const double *verif_dev, long ncol, long n_lead,
+                       long col_offset, long ncol_total, const int *slab_group,
+                       const double *col_weight_dev, int fair, uint64_t seed,
+                       int *below_dev, int *equal_dev, int *rank_dev,
+                       double *crps_dev, double *err_dev, double *var_dev,
+                       long long *hist, long long *n, long long *n_bad, double *sums);
 
 /* ---- measurement support --------------------------------------------------
  * Device time (ms) spent in the state-sweep kernels and in the obs-space
