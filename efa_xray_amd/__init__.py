@@ -13,8 +13,9 @@ from efa_xray_amd.assimilation.adaptive_inflation import AdaptiveInflation
 from efa_xray_amd.postprocess.impact import observation_impact
 from efa_xray_amd.postprocess.sensitivity import ensemble_sensitivity, observation_targets
 from efa_xray_amd.postprocess.verification import ensemble_verification
+from efa_xray_amd.postprocess.products import ensemble_products, probability_verification
 
 __all__ = ["EnsembleState", "Observation", "gaspari_cohn", "haversine", "Assimilation", "EnSRF", "AdaptiveInflation",
            "observation_impact", "ensemble_sensitivity", "observation_targets",
-           "ensemble_verification"]
+           "ensemble_verification", "ensemble_products", "probability_verification"]
 __version__ = "0.1.0"

@@ -142,6 +142,16 @@ SIGNATURES = {
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong),
                                           ctypes.POINTER(ctypes.c_longlong), c_double_p]),
+    "efa_products_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.c_long,
+                                        ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
+                                        ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong),
+                                        c_double_p]),
+    "efa_products_f32_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_long,
+                                            ctypes.c_long, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.POINTER(ctypes.c_int), ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong),
+                                            ctypes.POINTER(ctypes.c_longlong), c_double_p]),
     "efa_last_timing": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p,
                                        ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_int)]),
     "efa_fill_synthetic_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_int,
@@ -824,6 +834,39 @@ class Context(object):
             ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), self._addr(below, None), self._addr(equal, None),
             self._addr(rank, None), self._addr(crps), self._addr(err), self._addr(var), *out))
         return (hist, n, n_bad, sums) if groups else None
+
+    def products(self, rows, M, X, ncol=None, n_lead=1, quantiles=(), thresholds=None, mean=None, sd=None, quant=None, prob=None,
+                 verif=None, slab_group=None, col_weight=None, f32=None):
+        """efa_products_dev / efa_products_f32_dev.  X (rows, M) is a device array of float64 or float32 members
+        (`f32` says which for a raw address; None: the DeviceArray's dtype), only read; quantiles a host sequence of at most 8
+        levels in [0, 1]; thresholds a host array (n_lead, T), T <= 8, NaN where a slab has no threshold.  The fields mean / sd
+        (rows,), quant (Q, rows) and prob (T, rows) are float64 device arrays or None.  With verif (rows,), a float64 device
+        array, slab_group (n_lead,) is a host array of group numbers (-1: slab not scored) and col_weight (ncol,) a float64
+        device array or None; the call then returns (table (G, T, M+1, 2), n_bad (G, T) int64, sums (G, T, 4)), else None."""
+        if f32 is None:
+            f32 = isinstance(X, DeviceArray) and X.dtype == np.float32
+        fn = self.lib.efa_products_f32_dev if f32 else self.lib.efa_products_dev
+        ncol = int(rows if ncol is None else ncol)
+        q = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+        thr = np.zeros((int(n_lead), 0)) if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float64)
+        thr = thr.reshape(int(n_lead), -1) if thr.size else np.zeros((int(n_lead), 0))
+        T = thr.shape[1]
+        llp = ctypes.POINTER(ctypes.c_longlong)
+        sg_p, out, res = None, (None, None, None), None
+        if verif is not None:
+            sg = np.ascontiguousarray(slab_group, dtype=np.int32).reshape(-1)
+            G = int(sg.max()) + 1 if sg.size and sg.max() >= 0 else 0
+            table = np.zeros((G, T, int(M) + 1, 2), dtype=np.int64)
+            n_bad = np.zeros((G, T), dtype=np.int64)
+            sums = np.zeros((G, T, 4))
+            sg_p = sg.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+            out = (table.ctypes.data_as(llp), n_bad.ctypes.data_as(llp), _dp(sums))
+            res = (table, n_bad, sums)
+        _check(self.lib, fn(
+            self.handle, int(rows), int(M), self._addr(X, np.float32 if f32 else np.float64), ncol, int(n_lead), int(q.size), _dp(q),
+            int(T), _dp(thr), self._addr(mean), self._addr(sd), self._addr(quant), self._addr(prob), self._addr(verif), sg_p,
+            self._addr(col_weight), *out))
+        return res
 
     def cov_contract_f32(self, N, M, P, Xbp_f32, Ye_f32, C_f32):
         """C (N x P) = Xbp (N x M) . Ye^T (P x M), float32, device addresses."""

@@ -217,6 +217,10 @@ int efa_ctx_set_option(efa_ctx* c, const char* key, long value) {
     // grid cap of efa_verify_dev's pass (0: the default); the results do not depend on it
     if (value < 0 || value > 2048) return fail(EFA_ERR_INVALID, "verify_blocks must be in [0,2048]");
     c->verify_blocks = value;
+  } else if (!strcmp(key, "products_blocks")) {
+    // grid cap of efa_products_dev's pass (0: the default); the results do not depend on it
+    if (value < 0 || value > 2048) return fail(EFA_ERR_INVALID, "products_blocks must be in [0,2048]");
+    c->products_blocks = value;
   } else if (!strcmp(key, "threads_hint")) {
   } else {
     return fail(EFA_ERR_INVALID, "unknown option '%s'", key);
@@ -347,6 +351,8 @@ int efa_ctx_get_option(efa_ctx* c, const char* key, long* value) {
   else if (!strcmp(key, "sens_us")) *value = c->sens_us;  // the last efa_sensitivity_dev (efa_sensitivity.hip)
   else if (!strcmp(key, "verify_us")) *value = c->verify_us;  // the last efa_verify_dev (efa_verify.hip)
   else if (!strcmp(key, "verify_blocks")) *value = c->verify_blocks;
+  else if (!strcmp(key, "products_us")) *value = c->products_us;  // the last efa_products_dev (efa_products.hip)
+  else if (!strcmp(key, "products_blocks")) *value = c->products_blocks;
   else return fail(EFA_ERR_INVALID, "unknown option '%s'", key);
   return EFA_OK;
 }
@@ -692,6 +698,24 @@ int efa_verify_f32_dev(efa_ctx* c, long rows, int M, const float* X_dev, const d
   EFA_TRY(use(c));
   return verify(c, efa::Elem::f32, rows, M, X_dev, verif_dev, ncol, n_lead, col_offset, ncol_total, slab_group, col_weight_dev, fair,
                 seed, below_dev, equal_dev, rank_dev, crps_dev, err_dev, var_dev, hist, n, n_bad, sums);
+}
+
+int efa_products_dev(efa_ctx* c, long rows, int M, const double* X_dev, long ncol, long n_lead, int nq, const double* q, int nt,
+                     const double* thr, double* mean_dev, double* sd_dev, double* quant_dev, double* prob_dev,
+                     const double* verif_dev, const int* slab_group, const double* col_weight_dev, long long* table,
+                     long long* n_bad, double* sums) {
+  EFA_TRY(use(c));
+  return products(c, efa::Elem::f64, rows, M, X_dev, ncol, n_lead, nq, q, nt, thr, mean_dev, sd_dev, quant_dev, prob_dev, verif_dev,
+                  slab_group, col_weight_dev, table, n_bad, sums);
+}
+
+int efa_products_f32_dev(efa_ctx* c, long rows, int M, const float* X_dev, long ncol, long n_lead, int nq, const double* q, int nt,
+                         const double* thr, double* mean_dev, double* sd_dev, double* quant_dev, double* prob_dev,
+                         const double* verif_dev, const int* slab_group, const double* col_weight_dev, long long* table,
+                         long long* n_bad, double* sums) {
+  EFA_TRY(use(c));
+  return products(c, efa::Elem::f32, rows, M, X_dev, ncol, n_lead, nq, q, nt, thr, mean_dev, sd_dev, quant_dev, prob_dev, verif_dev,
+                  slab_group, col_weight_dev, table, n_bad, sums);
 }
 
 int efa_last_timing(efa_ctx* c, double* state_ms, double* obs_ms, long* state_launches, int* path_taken) {

@@ -183,6 +183,7 @@ struct efa_ctx {
   Interval imp_iv;       // efa_obs_impact_dev's contraction (its events are created by the first call)
   Interval sens_iv;      // one pass of efa_sensitivity_dev (likewise)
   Interval ver_iv;       // efa_verify_dev's pass and its reduction (likewise)
+  Interval prod_iv;      // efa_products_dev's pass and its reduction (likewise)
   OwnedEvent ev_fs;  // the last host-to-device copy of the forward-operator stencil (pin_fs)
   OwnedEvent ev_order;  // a change of stream: recorded on the stream that is left, waited for by the one that takes over
   int device = 0;
@@ -291,6 +292,10 @@ struct efa_ctx {
   DevBuf ver_ws;     // per chunk: partial sums | counts; per group: sums | histogram | n | n_bad; the slab groups
   long verify_us = 0;      // read-only option "verify_us": device time of the last call
   long verify_blocks = 0;  // option "verify_blocks": grid cap of k_verify (0: the default)
+  // --- ensemble products and probability verification (efa_products_dev): a buffer of its own as well -----------------
+  DevBuf prod_ws;    // per chunk: partial sums | bad counts; per group: sums | n_bad | table; thresholds; the slab groups
+  long products_us = 0;      // read-only option "products_us": device time of the last call
+  long products_blocks = 0;  // option "products_blocks": grid cap of k_products (0: the default)
   // --- f1: interpolation stencils -------------------------------------------------
   DevBuf fs_idx;  // efa_forward_stencil_dev staging
   DevBuf f_glat, f_glon, f_sl, f_cl, f_valids, f_var, f_time, f_lat, f_lon, f_near, f_idx, f_wts, f_status;

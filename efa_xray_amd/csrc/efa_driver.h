@@ -6,6 +6,7 @@
 //   efa_impact.hip   observation impact: its kernels and the driver of efa_obs_impact_dev
 //   efa_sensitivity.hip  ensemble sensitivity and observation targeting: its kernels and the driver of efa_sensitivity_dev
 //   efa_verify.hip   ensemble verification: its kernels and the driver of efa_verify_dev
+//   efa_products.hip ensemble products and probability verification: its kernels and the driver of efa_products_dev
 //   efa_comm.hip     RCCL
 // One call's arguments and results travel as arguments and return values; the context (efa_ctx.h) holds settings, caches,
 // workspaces and what the last obs phase left for the state phase.  A state call's rows travel with their element type (StateRows);
@@ -134,5 +135,11 @@ int verify(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, const dou
            long col_offset, long ncol_total, const int* slab_group, const double* col_weight_dev, int fair, uint64_t seed,
            int* below_dev, int* equal_dev, int* rank_dev, double* crps_dev, double* err_dev, double* var_dev, long long* hist,
            long long* n, long long* n_bad, double* sums);
+
+// ---- efa_products.hip ---------------------------------------------------------------------------------------------------------
+// efa_products_dev / _f32_dev: checks, the pass and the reduction of its partials; waits before it returns
+int products(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, long ncol, long n_lead, int nq, const double* q, int nt,
+             const double* thr, double* mean_dev, double* sd_dev, double* quant_dev, double* prob_dev, const double* verif_dev,
+             const int* slab_group, const double* col_weight_dev, long long* table, long long* n_bad, double* sums);
 
 }  // namespace efa_host

@@ -22,6 +22,7 @@
 // integer adds in LDS and integer atomics in memory, whose result no order can change.  No floating-point atomics.
 #include "efa_device.h"
 #include "efa_driver.h"
+#include "efa_sortnet.h"
 
 #include <cmath>
 #include <vector>
@@ -67,76 +68,6 @@ __device__ __forceinline__ int ver_pick(unsigned long long seed, unsigned long l
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   z ^= z >> 31;
   return (int)(((z >> 32) * (unsigned long long)(equal + 1)) >> 32);
-}
-
-#define VER_CMPX(a, b)                     \
-  {                                        \
-    const double lo_ = __builtin_fmin(a, b); \
-    const double hi_ = __builtin_fmax(a, b); \
-    a = lo_;                               \
-    b = hi_;                               \
-  }
-
-// sorts d[0..LP-1] upwards (LP a power of two)
-template <int LP>
-__device__ __forceinline__ void ver_sort_local(double (&d)[LP]) {
-#pragma unroll
-  for (int k = 2; k <= LP; k <<= 1) {
-#pragma unroll
-    for (int i = 0; i < LP; ++i) {
-      const int l = i ^ (k - 1);
-      if (l > i) VER_CMPX(d[i], d[l]);
-    }
-    __builtin_amdgcn_sched_barrier(0);  // (layer by layer: the scheduler otherwise spreads the network over every register)
-#pragma unroll
-    for (int j = k >> 2; j > 0; j >>= 1) {
-#pragma unroll
-      for (int i = 0; i < LP; ++i) {
-        const int l = i ^ j;
-        if (l > i) VER_CMPX(d[i], d[l]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-}
-
-// sorts a bitonic d[0..LP-1] upwards
-template <int LP>
-__device__ __forceinline__ void ver_merge_local(double (&d)[LP]) {
-#pragma unroll
-  for (int j = LP >> 1; j > 0; j >>= 1) {
-#pragma unroll
-    for (int i = 0; i < LP; ++i) {
-      const int l = i ^ j;
-      if (l > i) VER_CMPX(d[i], d[l]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// two sorted lanes (this one and lane ^ mask) -> the lower keeps the LP smaller values, the upper the LP larger, each bitonic
-template <int LP>
-__device__ __forceinline__ void ver_split_rev(double (&d)[LP], int mask, bool upper) {
-#pragma unroll
-  for (int k = 0; k < LP / 2; ++k) {
-    const int kk = LP - 1 - k;
-    const double t1 = __shfl_xor(d[kk], mask, 64);
-    const double t2 = __shfl_xor(d[k], mask, 64);
-    d[k] = ((d[k] < t1) != upper) ? d[k] : t1;
-    d[kk] = ((d[kk] < t2) != upper) ? d[kk] : t2;
-    if ((k & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // (a few exchanges in flight, not all of them)
-  }
-}
-
-// the first step of a bitonic merge over two lanes: same slot
-template <int LP>
-__device__ __forceinline__ void ver_split_same(double (&d)[LP], int mask, bool upper) {
-#pragma unroll
-  for (int k = 0; k < LP; ++k) {
-    const double t = __shfl_xor(d[k], mask, 64);
-    d[k] = ((d[k] < t) != upper) ? d[k] : t;
-    if ((k & 7) == 7) __builtin_amdgcn_sched_barrier(0);
-  }
 }
 
 // NU: chunks of 8 members the lanes hold, (M + 7) / 8 rounded up to a power of two: the sort network is that of LP = 2 NU slots

@@ -97,8 +97,10 @@ int efa_ctx_set_stream(efa_ctx *ctx, void *hip_stream);
  *          "gc_active_pairs"
  *          ((column, ob) pairs with a non-zero taper in the last one-pass sweep),
  *          "f32_native" (see efa_state_cycle_f32_dev), "impact_us" (see efa_obs_impact_dev),
- *          "sens_us" (see efa_sensitivity_dev), "verify_us" (see efa_verify_dev);
- *          "verify_blocks" (grid cap of efa_verify_dev's pass, 0 = the default of 2048; results do not depend on it) */
+ *          "sens_us" (see efa_sensitivity_dev), "verify_us" (see efa_verify_dev),
+ *          "products_us" (see efa_products_dev);
+ *          "verify_blocks" (grid cap of efa_verify_dev's pass, 0 = the default of 2048; results do not depend on it),
+ *          "products_blocks" (the same for efa_products_dev's pass) */
 int efa_ctx_set_option(efa_ctx *ctx, const char *key, long value);
 int efa_ctx_get_option(efa_ctx *ctx, const char *key, long *value);
 
@@ -651,6 +653,64 @@ int efa_verify_f32_dev(efa_ctx *ctx, long rows, int M, const float *X_dev,
                        int *below_dev, int *equal_dev, int *rank_dev,
                        double *crps_dev, double *err_dev, double *var_dev,
                        long long *hist, long long *n, long long *n_bad, double *sums);
+
+/* ---- ensemble products and probability verification: mean, sd, quantiles, exceedance probabilities, Brier / reliability (Murphy 1973) ----
+ * What is read from an adjusted ensemble, and how good its probabilities are.
+ *   X_dev [rows][M]   state members (float64; float32 for the _f32 twin, every
+ *                     number computed in float64), row i = lead*ncol + col,
+ *                     rows = n_lead*ncol, 2 <= M <= 256
+ *   q [nq] (host)     quantile levels in [0, 1], nq <= 8
+ *   thr [n_lead][nt] (host) thresholds of every slab, nt <= 8; NaN: slab `lead`
+ *                     has no threshold j; an infinite one is refused
+ * A row is BAD when a member is not finite: every float field of it is NaN, it
+ * enters no table and no sum, and it is counted.  Otherwise
+ *   mean  = (sum x_m)/M; exactly the common value when all members are equal
+ *   sd    = sqrt(sum (x_m - mean)^2/(M-1)); exactly 0.0 when all are equal
+ *   quantile at q: numpy's default linear rule on the sorted members x_(0) <=
+ *           .. <= x_(M-1): h = q (M-1), lo = min(floor(h), M-1), hi = min(lo+1,
+ *           M-1), f = h - lo (the host computes them, in float64); the value is
+ *           x_(lo) when f == 0, else min(x_(hi), fma(f, x_(hi) - x_(lo), x_(lo)))
+ *   prob at t: k/M, k = #{m: x_m > t} (strict IEEE comparison, one division);
+ *           NaN where the slab's threshold is NaN
+ * Fields (device, each may be NULL = not wanted; written for EVERY row):
+ * mean_dev [rows], sd_dev [rows], quant_dev [nq][rows], prob_dev [nt][rows].
+ * Probability verification runs when verif_dev [rows] is given: row i is SCORED
+ * at threshold j when y_i is finite, the column weight w > 0 (col_weight_dev
+ * [ncol], NULL: all 1), slab_group[lead] = g >= 0 (host, G = 1 + max), thr[lead][j]
+ * is finite and the row is not bad; the event is o = (y_i > t).  Host outputs:
+ *   table [G][nt][M+1][2]  count of scored rows with forecast count k and
+ *                     outcome o (unweighted: the reliability diagram, exact)
+ *   n_bad [G][nt]     rows that would be scored but are bad
+ *   sums  [G][nt][4]  sum w, sum w (k/M - o)^2, sum w k/M, sum w o
+ * One pass reads every row once; the quantiles come from a sort in registers
+ * that is compiled only into the kernels a call with nq > 0 runs.  Per-chunk
+ * partial sums are reduced in a fixed order by a second small kernel, the
+ * table is integer adds, and there are no floating-point atomics: the same
+ * inputs give the same bits, whatever the grid.  The call uses a workspace of
+ * its own and leaves everything a later cycle reads as it found it; it
+ * synchronises before returning.
+ * EFA_ERR_INVALID, before any launch and with no output written: a NULL ctx or
+ * X_dev, M < 2 or M > 256, rows != n_lead*ncol, nq or nt outside [0, 8], a q
+ * outside [0, 1] or NaN, an infinite threshold, nq > 0 with quant_dev NULL,
+ * nt > 0 with prob_dev and verif_dev both NULL, verif_dev with nt == 0, with
+ * slab_group NULL or with some but not all of table / n_bad / sums NULL, a
+ * slab_group entry < -1.
+ * Read-only option "products_us": device time (microseconds, HIP events) of
+ * the last call. */
+int efa_products_dev(efa_ctx *ctx, long rows, int M, const double *X_dev,
+                     long ncol, long n_lead, int nq, const double *q, int nt,
+                     const double *thr, double *mean_dev, double *sd_dev,
+                     double *quant_dev, double *prob_dev,
+                     const double *verif_dev, const int *slab_group,
+                     const double *col_weight_dev, long long *table,
+                     long long *n_bad, double *sums);
+int efa_products_f32_dev(efa_ctx *ctx, long rows, int M, const float *X_dev,
+                         long ncol, long n_lead, int nq, const double *q, int nt,
+                         const double *thr, double *mean_dev, double *sd_dev,
+                         double *quant_dev, double *prob_dev,
+                         const double *verif_dev, const int *slab_group,
+                         const double *col_weight_dev, long long *table,
+                         long long *n_bad, double *sums);
 
 /* ---- measurement support --------------------------------------------------
  * Device time (ms) spent in the state-sweep kernels and in the obs-space
