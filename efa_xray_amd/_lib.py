@@ -152,6 +152,12 @@ SIGNATURES = {
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.POINTER(ctypes.c_int), ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong),
                                             ctypes.POINTER(ctypes.c_longlong), c_double_p]),
+    "efa_gram_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.c_long,
+                                    c_double_p, ctypes.c_void_p, c_double_p, ctypes.POINTER(ctypes.c_longlong),
+                                    ctypes.POINTER(ctypes.c_longlong), c_double_p]),
+    "efa_gram_f32_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.c_long,
+                                        c_double_p, ctypes.c_void_p, c_double_p, ctypes.POINTER(ctypes.c_longlong),
+                                        ctypes.POINTER(ctypes.c_longlong), c_double_p]),
     "efa_last_timing": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p,
                                        ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_int)]),
     "efa_fill_synthetic_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_int,
@@ -867,6 +873,23 @@ class Context(object):
             int(T), _dp(thr), self._addr(mean), self._addr(sd), self._addr(quant), self._addr(prob), self._addr(verif), sg_p,
             self._addr(col_weight), *out))
         return res
+
+    def gram(self, rows, M, X, slab_scale, ncol=None, n_lead=1, col_weight=None, f32=None):
+        """efa_gram_dev / efa_gram_f32_dev.  X (rows, M) is a device array of float64 or float32 members (`f32`
+        says which for a raw address; None: the DeviceArray's dtype), only read; slab_scale (n_lead,) is a host array of scales
+        >= 0 (0: the slab is not read); col_weight (ncol,) a float64 device array or None.  Returns (gram (M, M), n, n_bad,
+        sums (2,) = sum w, sum w s^2) over the used, good rows."""
+        sc = np.ascontiguousarray(slab_scale, dtype=np.float64).reshape(-1)
+        if f32 is None:
+            f32 = isinstance(X, DeviceArray) and X.dtype == np.float32
+        fn = self.lib.efa_gram_f32_dev if f32 else self.lib.efa_gram_dev
+        G = np.zeros((int(M), int(M)))
+        n, n_bad = ctypes.c_longlong(0), ctypes.c_longlong(0)
+        sums = np.zeros(2)
+        _check(self.lib, fn(
+            self.handle, int(rows), int(M), self._addr(X, np.float32 if f32 else np.float64), int(rows if ncol is None else ncol),
+            int(n_lead), _dp(sc), self._addr(col_weight), _dp(G), ctypes.byref(n), ctypes.byref(n_bad), _dp(sums)))
+        return G, int(n.value), int(n_bad.value), sums
 
     def cov_contract_f32(self, N, M, P, Xbp_f32, Ye_f32, C_f32):
         """C (N x P) = Xbp (N x M) . Ye^T (P x M), float32, device addresses."""

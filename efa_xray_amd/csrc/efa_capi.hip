@@ -221,6 +221,10 @@ int efa_ctx_set_option(efa_ctx* c, const char* key, long value) {
     // grid cap of efa_products_dev's pass (0: the default); the results do not depend on it
     if (value < 0 || value > 2048) return fail(EFA_ERR_INVALID, "products_blocks must be in [0,2048]");
     c->products_blocks = value;
+  } else if (!strcmp(key, "gram_blocks")) {
+    // grid cap of efa_gram_dev's pass (0: the default); the results do not depend on it
+    if (value < 0 || value > 2048) return fail(EFA_ERR_INVALID, "gram_blocks must be in [0,2048]");
+    c->gram_blocks = value;
   } else if (!strcmp(key, "threads_hint")) {
   } else {
     return fail(EFA_ERR_INVALID, "unknown option '%s'", key);
@@ -353,6 +357,8 @@ int efa_ctx_get_option(efa_ctx* c, const char* key, long* value) {
   else if (!strcmp(key, "verify_blocks")) *value = c->verify_blocks;
   else if (!strcmp(key, "products_us")) *value = c->products_us;  // the last efa_products_dev (efa_products.hip)
   else if (!strcmp(key, "products_blocks")) *value = c->products_blocks;
+  else if (!strcmp(key, "gram_us")) *value = c->gram_us;  // the last efa_gram_dev (efa_gram.hip)
+  else if (!strcmp(key, "gram_blocks")) *value = c->gram_blocks;
   else return fail(EFA_ERR_INVALID, "unknown option '%s'", key);
   return EFA_OK;
 }
@@ -716,6 +722,18 @@ int efa_products_f32_dev(efa_ctx* c, long rows, int M, const float* X_dev, long 
   EFA_TRY(use(c));
   return products(c, efa::Elem::f32, rows, M, X_dev, ncol, n_lead, nq, q, nt, thr, mean_dev, sd_dev, quant_dev, prob_dev, verif_dev,
                   slab_group, col_weight_dev, table, n_bad, sums);
+}
+
+int efa_gram_dev(efa_ctx* c, long rows, int M, const double* X_dev, long ncol, long n_lead, const double* slab_scale,
+                 const double* col_weight_dev, double* gram, long long* n, long long* n_bad, double* sums) {
+  EFA_TRY(use(c));
+  return efa_host::gram(c, efa::Elem::f64, rows, M, X_dev, ncol, n_lead, slab_scale, col_weight_dev, gram, n, n_bad, sums);
+}
+
+int efa_gram_f32_dev(efa_ctx* c, long rows, int M, const float* X_dev, long ncol, long n_lead, const double* slab_scale,
+                     const double* col_weight_dev, double* gram, long long* n, long long* n_bad, double* sums) {
+  EFA_TRY(use(c));
+  return efa_host::gram(c, efa::Elem::f32, rows, M, X_dev, ncol, n_lead, slab_scale, col_weight_dev, gram, n, n_bad, sums);
 }
 
 int efa_last_timing(efa_ctx* c, double* state_ms, double* obs_ms, long* state_launches, int* path_taken) {

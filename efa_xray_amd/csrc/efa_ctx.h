@@ -184,6 +184,7 @@ struct efa_ctx {
   Interval sens_iv;      // one pass of efa_sensitivity_dev (likewise)
   Interval ver_iv;       // efa_verify_dev's pass and its reduction (likewise)
   Interval prod_iv;      // efa_products_dev's pass and its reduction (likewise)
+  Interval gram_iv;      // efa_gram_dev's pass and its reduction (likewise)
   OwnedEvent ev_fs;  // the last host-to-device copy of the forward-operator stencil (pin_fs)
   OwnedEvent ev_order;  // a change of stream: recorded on the stream that is left, waited for by the one that takes over
   int device = 0;
@@ -296,6 +297,10 @@ struct efa_ctx {
   DevBuf prod_ws;    // per chunk: partial sums | bad counts; per group: sums | n_bad | table; thresholds; the slab groups
   long products_us = 0;      // read-only option "products_us": device time of the last call
   long products_blocks = 0;  // option "products_blocks": grid cap of k_products (0: the default)
+  // --- ensemble Gram matrix (efa_gram_dev): a buffer of its own as well ------------------------------------------------
+  DevBuf gram_ws;    // per stream: partial tiles | row statistics | counts; G, sums, counts; the slab scales
+  long gram_us = 0;      // read-only option "gram_us": device time of the last call
+  long gram_blocks = 0;  // option "gram_blocks": grid cap of k_gram (0: the default)
   // --- f1: interpolation stencils -------------------------------------------------
   DevBuf fs_idx;  // efa_forward_stencil_dev staging
   DevBuf f_glat, f_glon, f_sl, f_cl, f_valids, f_var, f_time, f_lat, f_lon, f_near, f_idx, f_wts, f_status;

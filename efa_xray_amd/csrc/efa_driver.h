@@ -7,6 +7,7 @@
 //   efa_sensitivity.hip  ensemble sensitivity and observation targeting: its kernels and the driver of efa_sensitivity_dev
 //   efa_verify.hip   ensemble verification: its kernels and the driver of efa_verify_dev
 //   efa_products.hip ensemble products and probability verification: its kernels and the driver of efa_products_dev
+//   efa_gram.hip     the ensemble Gram matrix: its kernels and the driver of efa_gram_dev
 //   efa_comm.hip     RCCL
 // One call's arguments and results travel as arguments and return values; the context (efa_ctx.h) holds settings, caches,
 // workspaces and what the last obs phase left for the state phase.  A state call's rows travel with their element type (StateRows);
@@ -141,5 +142,10 @@ int verify(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, const dou
 int products(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, long ncol, long n_lead, int nq, const double* q, int nt,
              const double* thr, double* mean_dev, double* sd_dev, double* quant_dev, double* prob_dev, const double* verif_dev,
              const int* slab_group, const double* col_weight_dev, long long* table, long long* n_bad, double* sums);
+
+// ---- efa_gram.hip -------------------------------------------------------------------------------------------------------------
+// efa_gram_dev / _f32_dev: checks, the pass and the reduction of its partials; waits before it returns
+int gram(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, long ncol, long n_lead, const double* slab_scale,
+         const double* col_weight_dev, double* gram_out, long long* n, long long* n_bad, double* sums);
 
 }  // namespace efa_host

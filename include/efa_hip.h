@@ -98,9 +98,10 @@ int efa_ctx_set_stream(efa_ctx *ctx, void *hip_stream);
  *          ((column, ob) pairs with a non-zero taper in the last one-pass sweep),
  *          "f32_native" (see efa_state_cycle_f32_dev), "impact_us" (see efa_obs_impact_dev),
  *          "sens_us" (see efa_sensitivity_dev), "verify_us" (see efa_verify_dev),
- *          "products_us" (see efa_products_dev);
+ *          "products_us" (see efa_products_dev), "gram_us" (see efa_gram_dev);
  *          "verify_blocks" (grid cap of efa_verify_dev's pass, 0 = the default of 2048; results do not depend on it),
- *          "products_blocks" (the same for efa_products_dev's pass) */
+ *          "products_blocks" (the same for efa_products_dev's pass),
+ *          "gram_blocks" (the same for efa_gram_dev's pass) */
 int efa_ctx_set_option(efa_ctx *ctx, const char *key, long value);
 int efa_ctx_get_option(efa_ctx *ctx, const char *key, long *value);
 
@@ -711,6 +712,49 @@ int efa_products_f32_dev(efa_ctx *ctx, long rows, int M, const float *X_dev,
                          const double *verif_dev, const int *slab_group,
                          const double *col_weight_dev, long long *table,
                          long long *n_bad, double *sums);
+
+/* ---- ensemble Gram matrix in a weighted norm: member distances, EOFs / principal components, clusters ----
+ * How the members differ from one another over the whole field:
+ *   G = X'^T C X' / (M-1), M x M, X' the rows with their means removed.
+ *   X_dev [rows][M]   state members (float64; float32 for the _f32 twin, each
+ *                     member converted once, every number computed in float64),
+ *                     row i = lead*ncol + col, rows = n_lead*ncol, 2 <= M <= 256
+ *   slab_scale [n_lead] (host) the scale s of every slab, finite and >= 0; a slab
+ *                     of scale 0 is not read
+ *   col_weight_dev [ncol] (NULL: all 1) the weight w of every row of a column
+ * The coefficient of row i is c_i = w_col s_lead^2.  A row is USED when s_lead >
+ * 0 and w_col > 0 (a negative or NaN weight: not used, and not read).  A used
+ * row is BAD when a member or w_col is not finite: bad rows are counted in
+ * n_bad and add nothing.  With mean_i = (sum_m x_im)/M, x'_im = x_im - mean_i
+ * (exactly 0 when all members are equal), over the used, good rows:
+ *   gram [M][M] (host) G_ab = (sum_i c_i x'_ia x'_ib)/(M-1), bit-for-bit symmetric
+ *   n                 their number;  n_bad: the used rows that are bad
+ *   sums [2]          sum w_col, sum c_i
+ * With no used row G is exactly 0.0 everywhere and n = 0.  Scaling the whole
+ * state by 2^k scales G by 4^k exactly.  The rows may be a column shard of a
+ * larger state: the shards' gram, n, n_bad and sums add up to the whole
+ * state's (gram up to rounding).
+ * One pass reads every used row once: chunks of 32 rows are centred in LDS and
+ * contracted on the fp64 matrix cores, upper-triangle tiles only, into a number
+ * of accumulation streams that depends on the sizes alone; a second small
+ * kernel adds the streams in a fixed order, mirrors the matrix and divides by
+ * M-1.  No floating-point atomics: the same inputs give the same bits,
+ * whatever the grid.  The call uses a workspace of its own (at most 134 MB)
+ * and leaves everything a later cycle reads as it found it; it runs on the
+ * context's stream and synchronises before returning.
+ * EFA_ERR_INVALID, before any launch and with no output written: a NULL ctx,
+ * X_dev, slab_scale, gram, n, n_bad or sums, M < 2 or M > 256, rows !=
+ * n_lead*ncol, a slab_scale that is not finite or < 0.
+ * Read-only option "gram_us": device time (microseconds, HIP events) of the
+ * last call; "gram_blocks" caps the grid. */
+int efa_gram_dev(efa_ctx *ctx, long rows, int M, const double *X_dev,
+                 long ncol, long n_lead, const double *slab_scale,
+                 const double *col_weight_dev, double *gram,
+                 long long *n, long long *n_bad, double *sums);
+int efa_gram_f32_dev(efa_ctx *ctx, long rows, int M, const float *X_dev,
+                     long ncol, long n_lead, const double *slab_scale,
+                     const double *col_weight_dev, double *gram,
+                     long long *n, long long *n_bad, double *sums);
 
 /* ---- measurement support --------------------------------------------------
  * Device time (ms) spent in the state-sweep kernels and in the obs-space
