@@ -14,11 +14,13 @@ from efa_xray_amd.postprocess.impact import observation_impact
 from efa_xray_amd.postprocess.sensitivity import ensemble_sensitivity, observation_targets
 from efa_xray_amd.postprocess.verification import ensemble_verification
 from efa_xray_amd.postprocess.products import ensemble_products, probability_verification
+from efa_xray_amd.postprocess.neighbourhood import neighbourhood_probabilities, fractions_skill_score, fss_from_sums
 from efa_xray_amd.postprocess.modes import (ensemble_gram, ensemble_eofs, ensemble_clusters, distances_from_gram,
                                             eofs_from_gram, clusters_from_gram)
 
 __all__ = ["EnsembleState", "Observation", "gaspari_cohn", "haversine", "Assimilation", "EnSRF", "AdaptiveInflation",
            "observation_impact", "ensemble_sensitivity", "observation_targets",
            "ensemble_verification", "ensemble_products", "probability_verification",
-           "ensemble_gram", "ensemble_eofs", "ensemble_clusters", "distances_from_gram", "eofs_from_gram", "clusters_from_gram"]
+           "ensemble_gram", "ensemble_eofs", "ensemble_clusters", "distances_from_gram", "eofs_from_gram", "clusters_from_gram",
+           "neighbourhood_probabilities", "fractions_skill_score", "fss_from_sums"]
 __version__ = "0.1.0"

@@ -158,6 +158,17 @@ SIGNATURES = {
     "efa_gram_f32_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.c_long,
                                         c_double_p, ctypes.c_void_p, c_double_p, ctypes.POINTER(ctypes.c_longlong),
                                         ctypes.POINTER(ctypes.c_longlong), c_double_p]),
+    "efa_neighbourhood_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_long,
+                                             ctypes.c_long, ctypes.c_long, ctypes.c_int, c_double_p, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_void_p,
+                                             c_double_p, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]),
+    "efa_neighbourhood_f32_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_long,
+                                                 ctypes.c_long, ctypes.c_long, ctypes.c_int, c_double_p, ctypes.c_int,
+                                                 ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_void_p,
+                                                 c_double_p, ctypes.POINTER(ctypes.c_longlong),
+                                                 ctypes.POINTER(ctypes.c_longlong)]),
     "efa_last_timing": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p,
                                        ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_int)]),
     "efa_fill_synthetic_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_int,
@@ -872,6 +883,38 @@ class Context(object):
             self.handle, int(rows), int(M), self._addr(X, np.float32 if f32 else np.float64), ncol, int(n_lead), int(q.size), _dp(q),
             int(T), _dp(thr), self._addr(mean), self._addr(sd), self._addr(quant), self._addr(prob), self._addr(verif), sg_p,
             self._addr(col_weight), *out))
+        return res
+
+    def neighbourhood(self, rows, M, X, ny, nx, n_lead, thresholds, radii, shape=0, wrap_x=False, nep=None, nmep=None, verif=None,
+                      slab_group=None, col_weight=None, f32=None):
+        """efa_neighbourhood_dev / efa_neighbourhood_f32_dev.  X (rows, M), rows = n_lead*ny*nx, is a device array of
+        float64 or float32 members (`f32` says which for a raw address; None: the DeviceArray's dtype), only read; thresholds a
+        host array (n_lead, T), 1 <= T <= 8, NaN where a slab has no threshold; radii a host sequence of at most 4 integers in
+        [0, 64]; shape 0 (square) or 1 (disc).  The fields nep / nmep (R, T, rows) are float64 device arrays or None.  With verif
+        (rows,), a float64 device array, slab_group (n_lead,) is a host array of group numbers (-1: slab not scored) and
+        col_weight (ny*nx,) a float64 device array or None; the call then returns (sums (G, R, T, 6), n (G, R, T), n_bad
+        (G, R, T) int64), else None."""
+        if f32 is None:
+            f32 = isinstance(X, DeviceArray) and X.dtype == np.float32
+        fn = self.lib.efa_neighbourhood_f32_dev if f32 else self.lib.efa_neighbourhood_dev
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(int(n_lead), -1)
+        rad = np.ascontiguousarray(radii, dtype=np.int32).reshape(-1)
+        T, R = thr.shape[1], rad.size
+        llp = ctypes.POINTER(ctypes.c_longlong)
+        sg_p, out, res = None, (None, None, None), None
+        if verif is not None:
+            sg = np.ascontiguousarray(slab_group, dtype=np.int32).reshape(-1)
+            G = int(sg.max()) + 1 if sg.size and sg.max() >= 0 else 0
+            sums = np.zeros((G, R, T, 6))
+            n = np.zeros((G, R, T), dtype=np.int64)
+            n_bad = np.zeros((G, R, T), dtype=np.int64)
+            sg_p = sg.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+            out = (_dp(sums), n.ctypes.data_as(llp), n_bad.ctypes.data_as(llp))
+            res = (sums, n, n_bad)
+        _check(self.lib, fn(
+            self.handle, int(rows), int(M), self._addr(X, np.float32 if f32 else np.float64), int(ny), int(nx), int(n_lead), int(T),
+            _dp(thr), int(R), rad.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), int(shape), 1 if wrap_x else 0, self._addr(nep),
+            self._addr(nmep), self._addr(verif), sg_p, self._addr(col_weight), *out))
         return res
 
     def gram(self, rows, M, X, slab_scale, ncol=None, n_lead=1, col_weight=None, f32=None):

@@ -225,6 +225,14 @@ int efa_ctx_set_option(efa_ctx* c, const char* key, long value) {
     // grid cap of efa_gram_dev's pass (0: the default); the results do not depend on it
     if (value < 0 || value > 2048) return fail(EFA_ERR_INVALID, "gram_blocks must be in [0,2048]");
     c->gram_blocks = value;
+  } else if (!strcmp(key, "neighbourhood_blocks")) {
+    // grid cap of efa_neighbourhood_dev's kernels (0: the default); the results do not depend on it
+    if (value < 0 || value > 2048) return fail(EFA_ERR_INVALID, "neighbourhood_blocks must be in [0,2048]");
+    c->neighbourhood_blocks = value;
+  } else if (!strcmp(key, "nbr_ws_bytes")) {
+    // a lower cap of the records efa_neighbourhood_dev holds at a time (0: EFA_NBR_WS_BYTES); the results do not depend on it
+    if (value < 0 || value > EFA_NBR_WS_BYTES) return fail(EFA_ERR_INVALID, "nbr_ws_bytes must be in [0,%ld]", (long)EFA_NBR_WS_BYTES);
+    c->nbr_ws_bytes = value;
   } else if (!strcmp(key, "threads_hint")) {
   } else {
     return fail(EFA_ERR_INVALID, "unknown option '%s'", key);
@@ -359,6 +367,9 @@ int efa_ctx_get_option(efa_ctx* c, const char* key, long* value) {
   else if (!strcmp(key, "products_blocks")) *value = c->products_blocks;
   else if (!strcmp(key, "gram_us")) *value = c->gram_us;  // the last efa_gram_dev (efa_gram.hip)
   else if (!strcmp(key, "gram_blocks")) *value = c->gram_blocks;
+  else if (!strcmp(key, "neighbourhood_us")) *value = c->neighbourhood_us;  // the last efa_neighbourhood_dev (efa_neighbourhood.hip)
+  else if (!strcmp(key, "neighbourhood_blocks")) *value = c->neighbourhood_blocks;
+  else if (!strcmp(key, "nbr_ws_bytes")) *value = c->nbr_ws_bytes;
   else return fail(EFA_ERR_INVALID, "unknown option '%s'", key);
   return EFA_OK;
 }
@@ -734,6 +745,23 @@ int efa_gram_f32_dev(efa_ctx* c, long rows, int M, const float* X_dev, long ncol
                      const double* col_weight_dev, double* gram, long long* n, long long* n_bad, double* sums) {
   EFA_TRY(use(c));
   return efa_host::gram(c, efa::Elem::f32, rows, M, X_dev, ncol, n_lead, slab_scale, col_weight_dev, gram, n, n_bad, sums);
+}
+
+int efa_neighbourhood_dev(efa_ctx* c, long rows, int M, const double* X_dev, long ny, long nx, long n_lead, int nt, const double* thr,
+                          int nr, const int* radius, int shape, int wrap_x, double* nep_dev, double* nmep_dev, const double* verif_dev,
+                          const int* slab_group, const double* col_weight_dev, double* sums, long long* n, long long* n_bad) {
+  EFA_TRY(use(c));
+  return efa_host::neighbourhood(c, efa::Elem::f64, rows, M, X_dev, ny, nx, n_lead, nt, thr, nr, radius, shape, wrap_x, nep_dev,
+                                 nmep_dev, verif_dev, slab_group, col_weight_dev, sums, n, n_bad);
+}
+
+int efa_neighbourhood_f32_dev(efa_ctx* c, long rows, int M, const float* X_dev, long ny, long nx, long n_lead, int nt,
+                              const double* thr, int nr, const int* radius, int shape, int wrap_x, double* nep_dev, double* nmep_dev,
+                              const double* verif_dev, const int* slab_group, const double* col_weight_dev, double* sums,
+                              long long* n, long long* n_bad) {
+  EFA_TRY(use(c));
+  return efa_host::neighbourhood(c, efa::Elem::f32, rows, M, X_dev, ny, nx, n_lead, nt, thr, nr, radius, shape, wrap_x, nep_dev,
+                                 nmep_dev, verif_dev, slab_group, col_weight_dev, sums, n, n_bad);
 }
 
 int efa_last_timing(efa_ctx* c, double* state_ms, double* obs_ms, long* state_launches, int* path_taken) {

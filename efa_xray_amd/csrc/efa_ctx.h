@@ -185,6 +185,7 @@ struct efa_ctx {
   Interval ver_iv;       // efa_verify_dev's pass and its reduction (likewise)
   Interval prod_iv;      // efa_products_dev's pass and its reduction (likewise)
   Interval gram_iv;      // efa_gram_dev's pass and its reduction (likewise)
+  Interval nbr_iv;       // efa_neighbourhood_dev's records, windows and reduction (likewise)
   OwnedEvent ev_fs;  // the last host-to-device copy of the forward-operator stencil (pin_fs)
   OwnedEvent ev_order;  // a change of stream: recorded on the stream that is left, waited for by the one that takes over
   int device = 0;
@@ -301,6 +302,11 @@ struct efa_ctx {
   DevBuf gram_ws;    // per stream: partial tiles | row statistics | counts; G, sums, counts; the slab scales
   long gram_us = 0;      // read-only option "gram_us": device time of the last call
   long gram_blocks = 0;  // option "gram_blocks": grid cap of k_gram (0: the default)
+  // --- neighbourhood probabilities and the fractions skill score (efa_neighbourhood_dev): a buffer of its own as well ---
+  DevBuf nbr_ws;     // per batch of slabs: mask words | counts | flags; per tile: partial sums | counts; per group: sums | n | n_bad; tables
+  long neighbourhood_us = 0;      // read-only option "neighbourhood_us": device time of the last call
+  long neighbourhood_blocks = 0;  // option "neighbourhood_blocks": grid cap of its kernels (0: the default)
+  long nbr_ws_bytes = 0;          // option "nbr_ws_bytes": a lower cap of the records of a batch (0: EFA_NBR_WS_BYTES)
   // --- f1: interpolation stencils -------------------------------------------------
   DevBuf fs_idx;  // efa_forward_stencil_dev staging
   DevBuf f_glat, f_glon, f_sl, f_cl, f_valids, f_var, f_time, f_lat, f_lon, f_near, f_idx, f_wts, f_status;

@@ -7,6 +7,7 @@
 //   efa_sensitivity.hip  ensemble sensitivity and observation targeting: its kernels and the driver of efa_sensitivity_dev
 //   efa_verify.hip   ensemble verification: its kernels and the driver of efa_verify_dev
 //   efa_products.hip ensemble products and probability verification: its kernels and the driver of efa_products_dev
+//   efa_neighbourhood.hip neighbourhood probabilities and the fractions skill score: its kernels and the driver of efa_neighbourhood_dev
 //   efa_gram.hip     the ensemble Gram matrix: its kernels and the driver of efa_gram_dev
 //   efa_comm.hip     RCCL
 // One call's arguments and results travel as arguments and return values; the context (efa_ctx.h) holds settings, caches,
@@ -147,5 +148,11 @@ int products(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, long nc
 // efa_gram_dev / _f32_dev: checks, the pass and the reduction of its partials; waits before it returns
 int gram(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, long ncol, long n_lead, const double* slab_scale,
          const double* col_weight_dev, double* gram_out, long long* n, long long* n_bad, double* sums);
+
+// ---- efa_neighbourhood.hip ----------------------------------------------------------------------------------------------------
+// efa_neighbourhood_dev / _f32_dev: checks, the records and the windows batch by batch, the reduction; waits before it returns
+int neighbourhood(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, long ny, long nx, long n_lead, int nt, const double* thr,
+                  int nr, const int* radius, int shape, int wrap_x, double* nep_dev, double* nmep_dev, const double* verif_dev,
+                  const int* slab_group, const double* col_weight_dev, double* sums, long long* n, long long* n_bad);
 
 }  // namespace efa_host

@@ -101,7 +101,10 @@ int efa_ctx_set_stream(efa_ctx *ctx, void *hip_stream);
  *          "products_us" (see efa_products_dev), "gram_us" (see efa_gram_dev);
  *          "verify_blocks" (grid cap of efa_verify_dev's pass, 0 = the default of 2048; results do not depend on it),
  *          "products_blocks" (the same for efa_products_dev's pass),
- *          "gram_blocks" (the same for efa_gram_dev's pass) */
+ *          "gram_blocks" (the same for efa_gram_dev's pass);
+ *          "neighbourhood_blocks" (the same for efa_neighbourhood_dev's kernels), "nbr_ws_bytes" (a lower cap
+ *          of the records that call holds at a time, 0 = EFA_NBR_WS_BYTES; results do not depend on it),
+ *          read-only "neighbourhood_us" (see efa_neighbourhood_dev) */
 int efa_ctx_set_option(efa_ctx *ctx, const char *key, long value);
 int efa_ctx_get_option(efa_ctx *ctx, const char *key, long *value);
 
@@ -755,6 +758,81 @@ int efa_gram_f32_dev(efa_ctx *ctx, long rows, int M, const float *X_dev,
                      long ncol, long n_lead, const double *slab_scale,
                      const double *col_weight_dev, double *gram,
                      long long *n, long long *n_bad, double *sums);
+
+/* ---- neighbourhood ensemble probabilities and the fractions skill score (Schwartz et al. 2010; Schwartz and Sobash 2017; Roberts and Lean 2008) ----
+ * The products that need the (y, x) structure of the state.
+ *   X_dev [rows][M]   state members (float64; float32 for the _f32 twin, each
+ *                     member converted once, compared in float64), row
+ *                     i = lead*ncol + y*nx + x, ncol = ny*nx, rows = n_lead*ncol,
+ *                     2 <= M <= 256
+ *   thr [n_lead][nt] (host) thresholds of every slab, 1 <= nt <= 8; NaN: slab
+ *                     `lead` has no threshold j; an infinite one is refused
+ *   radius [nr] (host) radii in grid points, 1 <= nr <= EFA_NBR_MAX_RADII,
+ *                     0 <= r <= EFA_NBR_MAX_RADIUS
+ * A row is VALID when every member is finite and, in a call with verif_dev,
+ * its y_i is finite.  An invalid row adds nothing to any window, and every
+ * field is NaN at an invalid centre.  The window W_r(y, x) lies within one
+ * slab: shape 0 (square) |dy| <= r and |dx| <= r; shape 1 (disc) dy*dy + dx*dx
+ * <= r*r, in integers.  Rows outside 0 <= y+dy < ny are left out; columns
+ * outside 0 <= x+dx < nx are left out when wrap_x = 0 and taken modulo nx when
+ * wrap_x = 1 (which needs 2r+1 <= nx for every radius).  With k_i = #{m: x_im >
+ * t} (strict IEEE comparison), over the valid rows i' of the window:
+ *   n    = their number,  S = sum k_i'
+ *   NEP  = (double)S / ((double)M * (double)n), one division; at r = 0 bit for
+ *          bit efa_products_dev's prob
+ *   NMEP = (double)#{m: some i' has x_i'm > t} / (double)M
+ * Fields (device, each may be NULL = not wanted; written for EVERY row; NaN
+ * where the centre is invalid or the slab's threshold is NaN):
+ * nep_dev [nr][nt][rows], nmep_dev [nr][nt][rows].
+ * With verif_dev [rows]: o_i = (y_i > t) on valid rows, O = (double)(sum of o
+ * over the valid rows of the window) / (double)n.  Centre i is SCORED when it is
+ * valid, its column weight w > 0 (col_weight_dev [ncol], NULL: all 1; a centre
+ * of weight 0 still counts in its neighbours' windows), slab_group[lead] = g >=
+ * 0 (host, G = 1 + max) and thr[lead][j] is finite.  Host outputs, with P = NEP:
+ *   sums  [G][nr][nt][6]  sum w, sum w (P-O)^2, sum w P^2, sum w O^2, sum w P,
+ *                     sum w O
+ *   n     [G][nr][nt]     scored centres
+ *   n_bad [G][nr][nt]     centres that would be scored but have a member that
+ *                     is not finite
+ * One pass reads every row of the slabs that are needed once (a slab whose
+ * thresholds are all NaN, or which no field and no group wants, is not read)
+ * and leaves a compact record per row in the call's workspace; a second kernel
+ * forms the windows over the records in LDS.  The records of the slabs held at
+ * a time take at most EFA_NBR_WS_BYTES (option "nbr_ws_bytes" lowers that; a
+ * batch is at least one slab), the slabs are processed in batches, and the
+ * per-tile partial sums (64 nr nt bytes per tile of 1024 rows when scoring) and
+ * small tables come on top.  The partials are added in a fixed order by a third
+ * small kernel; there are no floating-point atomics: the same inputs give the
+ * same bits, whatever the grid and the batches.  The call leaves everything a
+ * later cycle reads as it found it and synchronises before returning.
+ * EFA_ERR_INVALID, before any launch and with no output written: a NULL ctx,
+ * X_dev, thr or radius, M < 2 or M > 256, a negative size or rows !=
+ * n_lead*ny*nx, nt outside [1, 8], nr outside [1, 4], a radius outside [0, 64],
+ * shape or wrap_x not 0 or 1, wrap_x with 2r+1 > nx, an infinite threshold,
+ * some but not all of sums / n / n_bad NULL, no output wanted (nep_dev and
+ * nmep_dev NULL and nothing to score), verif_dev without slab_group, a
+ * slab_group entry < -1.
+ * Read-only option "neighbourhood_us": device time (microseconds, HIP events)
+ * of the last call; "neighbourhood_blocks" caps the grids. */
+#define EFA_NBR_MAX_THRESHOLDS 8
+#define EFA_NBR_MAX_RADII 4
+#define EFA_NBR_MAX_RADIUS 64
+#define EFA_NBR_WS_BYTES (256L << 20) /* cap of the records held at a time */
+int efa_neighbourhood_dev(efa_ctx *ctx, long rows, int M, const double *X_dev,
+                          long ny, long nx, long n_lead, int nt,
+                          const double *thr, int nr, const int *radius,
+                          int shape, int wrap_x, double *nep_dev,
+                          double *nmep_dev, const double *verif_dev,
+                          const int *slab_group, const double *col_weight_dev,
+                          double *sums, long long *n, long long *n_bad);
+int efa_neighbourhood_f32_dev(efa_ctx *ctx, long rows, int M, const float *X_dev,
+                              long ny, long nx, long n_lead, int nt,
+                              const double *thr, int nr, const int *radius,
+                              int shape, int wrap_x, double *nep_dev,
+                              double *nmep_dev, const double *verif_dev,
+                              const int *slab_group,
+                              const double *col_weight_dev, double *sums,
+                              long long *n, long long *n_bad);
 
 /* ---- measurement support --------------------------------------------------
  * Device time (ms) spent in the state-sweep kernels and in the obs-space
