@@ -15,6 +15,7 @@ from efa_xray_amd.postprocess.sensitivity import ensemble_sensitivity, observati
 from efa_xray_amd.postprocess.verification import ensemble_verification
 from efa_xray_amd.postprocess.products import ensemble_products, probability_verification
 from efa_xray_amd.postprocess.neighbourhood import neighbourhood_probabilities, fractions_skill_score, fss_from_sums
+from efa_xray_amd.postprocess.pmmean import probability_matched_mean
 from efa_xray_amd.postprocess.modes import (ensemble_gram, ensemble_eofs, ensemble_clusters, distances_from_gram,
                                             eofs_from_gram, clusters_from_gram)
 
@@ -22,5 +23,6 @@ __all__ = ["EnsembleState", "Observation", "gaspari_cohn", "haversine", "Assimil
            "observation_impact", "ensemble_sensitivity", "observation_targets",
            "ensemble_verification", "ensemble_products", "probability_verification",
            "ensemble_gram", "ensemble_eofs", "ensemble_clusters", "distances_from_gram", "eofs_from_gram", "clusters_from_gram",
-           "neighbourhood_probabilities", "fractions_skill_score", "fss_from_sums"]
+           "neighbourhood_probabilities", "fractions_skill_score", "fss_from_sums",
+           "probability_matched_mean"]
 __version__ = "0.1.0"

@@ -169,6 +169,12 @@ SIGNATURES = {
                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_void_p,
                                                  c_double_p, ctypes.POINTER(ctypes.c_longlong),
                                                  ctypes.POINTER(ctypes.c_longlong)]),
+    "efa_pm_mean_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.c_long,
+                                       ctypes.c_long, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_long, ctypes.c_long,
+                                       ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong)]),
+    "efa_pm_mean_f32_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_long,
+                                           ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_long,
+                                           ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong)]),
     "efa_last_timing": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p,
                                        ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_int)]),
     "efa_fill_synthetic_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_int,
@@ -916,6 +922,29 @@ class Context(object):
             _dp(thr), int(R), rad.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), int(shape), 1 if wrap_x else 0, self._addr(nep),
             self._addr(nmep), self._addr(verif), sg_p, self._addr(col_weight), *out))
         return res
+
+    def pm_mean(self, rows, M, X, ny, nx, n_lead, rank, pm, slab_on=None, patch=None, pick=None, f32=None):
+        """efa_pm_mean_dev / efa_pm_mean_f32_dev.  X (rows, M), rows = n_lead*ny*nx, is a device array of float64 or
+        float32 members (`f32` says which for a raw address; None: the DeviceArray's dtype) and rank (rows,) a float64 device
+        array, both only read; pm (rows,) a float64 device array, written for every row; slab_on (n_lead,) a host array (0: the
+        slab is not read) or None; patch (py, px) or None (the whole slab); pick an int in [0, M) or None (M // 2).  Returns
+        n_bad (n_lead,) int64."""
+        if f32 is None:
+            f32 = isinstance(X, DeviceArray) and X.dtype == np.float32
+        fn = self.lib.efa_pm_mean_f32_dev if f32 else self.lib.efa_pm_mean_dev
+        py, px = (int(ny), int(nx)) if patch is None else (int(patch[0]), int(patch[1]))
+        on_p = None
+        if slab_on is not None:
+            on = np.ascontiguousarray(slab_on, dtype=np.int32).reshape(-1)
+            if on.size != int(n_lead):
+                raise ValueError("slab_on has %d entries, the state %d slabs" % (on.size, int(n_lead)))
+            on_p = on.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        n_bad = np.zeros(int(n_lead), dtype=np.int64)
+        _check(self.lib, fn(
+            self.handle, int(rows), int(M), self._addr(X, np.float32 if f32 else np.float64), int(ny), int(nx), int(n_lead),
+            self._addr(rank), on_p, py, px, int(M) // 2 if pick is None else int(pick), self._addr(pm),
+            n_bad.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+        return n_bad
 
     def gram(self, rows, M, X, slab_scale, ncol=None, n_lead=1, col_weight=None, f32=None):
         """efa_gram_dev / efa_gram_f32_dev.  X (rows, M) is a device array of float64 or float32 members (`f32`

@@ -233,6 +233,14 @@ int efa_ctx_set_option(efa_ctx* c, const char* key, long value) {
     // a lower cap of the records efa_neighbourhood_dev holds at a time (0: EFA_NBR_WS_BYTES); the results do not depend on it
     if (value < 0 || value > EFA_NBR_WS_BYTES) return fail(EFA_ERR_INVALID, "nbr_ws_bytes must be in [0,%ld]", (long)EFA_NBR_WS_BYTES);
     c->nbr_ws_bytes = value;
+  } else if (!strcmp(key, "pm_blocks")) {
+    // grid cap of efa_pm_mean_dev's kernels (0: the default); the results do not depend on it
+    if (value < 0 || value > 2048) return fail(EFA_ERR_INVALID, "pm_blocks must be in [0,2048]");
+    c->pm_blocks = value;
+  } else if (!strcmp(key, "pm_ws_bytes")) {
+    // a lower cap of the pooled buffers efa_pm_mean_dev holds at a time (0: EFA_PM_WS_BYTES); the results do not depend on it
+    if (value < 0 || value > EFA_PM_WS_BYTES) return fail(EFA_ERR_INVALID, "pm_ws_bytes must be in [0,%ld]", (long)EFA_PM_WS_BYTES);
+    c->pm_ws_bytes = value;
   } else if (!strcmp(key, "threads_hint")) {
   } else {
     return fail(EFA_ERR_INVALID, "unknown option '%s'", key);
@@ -370,6 +378,11 @@ int efa_ctx_get_option(efa_ctx* c, const char* key, long* value) {
   else if (!strcmp(key, "neighbourhood_us")) *value = c->neighbourhood_us;  // the last efa_neighbourhood_dev (efa_neighbourhood.hip)
   else if (!strcmp(key, "neighbourhood_blocks")) *value = c->neighbourhood_blocks;
   else if (!strcmp(key, "nbr_ws_bytes")) *value = c->nbr_ws_bytes;
+  else if (!strcmp(key, "pm_us")) *value = c->pm_us;  // the last efa_pm_mean_dev (efa_pmmean.hip)
+  else if (!strcmp(key, "pm_passes")) *value = c->pm_passes;
+  else if (!strcmp(key, "pm_rank_passes")) *value = c->pm_rank_passes;
+  else if (!strcmp(key, "pm_blocks")) *value = c->pm_blocks;
+  else if (!strcmp(key, "pm_ws_bytes")) *value = c->pm_ws_bytes;
   else return fail(EFA_ERR_INVALID, "unknown option '%s'", key);
   return EFA_OK;
 }
@@ -762,6 +775,18 @@ int efa_neighbourhood_f32_dev(efa_ctx* c, long rows, int M, const float* X_dev, 
   EFA_TRY(use(c));
   return efa_host::neighbourhood(c, efa::Elem::f32, rows, M, X_dev, ny, nx, n_lead, nt, thr, nr, radius, shape, wrap_x, nep_dev,
                                  nmep_dev, verif_dev, slab_group, col_weight_dev, sums, n, n_bad);
+}
+
+int efa_pm_mean_dev(efa_ctx* c, long rows, int M, const double* X_dev, long ny, long nx, long n_lead, const double* rank_dev,
+                    const int* slab_on, long py, long px, int pick, double* pm_dev, long long* n_bad) {
+  EFA_TRY(use(c));
+  return efa_host::pm_mean(c, efa::Elem::f64, rows, M, X_dev, ny, nx, n_lead, rank_dev, slab_on, py, px, pick, pm_dev, n_bad);
+}
+
+int efa_pm_mean_f32_dev(efa_ctx* c, long rows, int M, const float* X_dev, long ny, long nx, long n_lead, const double* rank_dev,
+                        const int* slab_on, long py, long px, int pick, double* pm_dev, long long* n_bad) {
+  EFA_TRY(use(c));
+  return efa_host::pm_mean(c, efa::Elem::f32, rows, M, X_dev, ny, nx, n_lead, rank_dev, slab_on, py, px, pick, pm_dev, n_bad);
 }
 
 int efa_last_timing(efa_ctx* c, double* state_ms, double* obs_ms, long* state_launches, int* path_taken) {

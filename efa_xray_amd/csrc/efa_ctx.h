@@ -186,6 +186,7 @@ struct efa_ctx {
   Interval prod_iv;      // efa_products_dev's pass and its reduction (likewise)
   Interval gram_iv;      // efa_gram_dev's pass and its reduction (likewise)
   Interval nbr_iv;       // efa_neighbourhood_dev's records, windows and reduction (likewise)
+  Interval pm_iv;        // efa_pm_mean_dev's keys, sorts and assignment (likewise)
   OwnedEvent ev_fs;  // the last host-to-device copy of the forward-operator stencil (pin_fs)
   OwnedEvent ev_order;  // a change of stream: recorded on the stream that is left, waited for by the one that takes over
   int device = 0;
@@ -307,6 +308,13 @@ struct efa_ctx {
   long neighbourhood_us = 0;      // read-only option "neighbourhood_us": device time of the last call
   long neighbourhood_blocks = 0;  // option "neighbourhood_blocks": grid cap of its kernels (0: the default)
   long nbr_ws_bytes = 0;          // option "nbr_ws_bytes": a lower cap of the records of a batch (0: EFA_NBR_WS_BYTES)
+  // --- probability-matched mean (efa_pm_mean_dev): a buffer of its own as well -------------------------------------------
+  DevBuf pm_ws;      // per batch of slabs: pooled keys a | b, rank keys and payloads a | b; histograms and scans; the tables; n_bad
+  long pm_us = 0;           // read-only option "pm_us": device time of the last call
+  long pm_passes = 0;       // read-only option "pm_passes": radix passes the last call ran on the pool, summed over its batches
+  long pm_rank_passes = 0;  // read-only option "pm_rank_passes": the same on the rank keys
+  long pm_blocks = 0;       // option "pm_blocks": grid cap of its kernels (0: the default)
+  long pm_ws_bytes = 0;     // option "pm_ws_bytes": a lower cap of the pooled buffers of a batch (0: EFA_PM_WS_BYTES)
   // --- f1: interpolation stencils -------------------------------------------------
   DevBuf fs_idx;  // efa_forward_stencil_dev staging
   DevBuf f_glat, f_glon, f_sl, f_cl, f_valids, f_var, f_time, f_lat, f_lon, f_near, f_idx, f_wts, f_status;

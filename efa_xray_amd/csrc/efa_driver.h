@@ -8,6 +8,7 @@
 //   efa_verify.hip   ensemble verification: its kernels and the driver of efa_verify_dev
 //   efa_products.hip ensemble products and probability verification: its kernels and the driver of efa_products_dev
 //   efa_neighbourhood.hip neighbourhood probabilities and the fractions skill score: its kernels and the driver of efa_neighbourhood_dev
+//   efa_pmmean.hip   the probability-matched mean and the segmented radix sort under it: its kernels and the driver of efa_pm_mean_dev
 //   efa_gram.hip     the ensemble Gram matrix: its kernels and the driver of efa_gram_dev
 //   efa_comm.hip     RCCL
 // One call's arguments and results travel as arguments and return values; the context (efa_ctx.h) holds settings, caches,
@@ -154,5 +155,10 @@ int gram(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, long ncol, 
 int neighbourhood(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, long ny, long nx, long n_lead, int nt, const double* thr,
                   int nr, const int* radius, int shape, int wrap_x, double* nep_dev, double* nmep_dev, const double* verif_dev,
                   const int* slab_group, const double* col_weight_dev, double* sums, long long* n, long long* n_bad);
+
+// ---- efa_pmmean.hip -----------------------------------------------------------------------------------------------------------
+// efa_pm_mean_dev / _f32_dev: checks, then batch by batch the keys, the two sorts and the assignment; waits before it returns
+int pm_mean(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, long ny, long nx, long n_lead, const double* rank_dev,
+            const int* slab_on, long py, long px, int pick, double* pm_dev, long long* n_bad);
 
 }  // namespace efa_host

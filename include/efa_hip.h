@@ -104,7 +104,10 @@ int efa_ctx_set_stream(efa_ctx *ctx, void *hip_stream);
  *          "gram_blocks" (the same for efa_gram_dev's pass);
  *          "neighbourhood_blocks" (the same for efa_neighbourhood_dev's kernels), "nbr_ws_bytes" (a lower cap
  *          of the records that call holds at a time, 0 = EFA_NBR_WS_BYTES; results do not depend on it),
- *          read-only "neighbourhood_us" (see efa_neighbourhood_dev) */
+ *          read-only "neighbourhood_us" (see efa_neighbourhood_dev);
+ *          "pm_blocks" (the same grid cap for efa_pm_mean_dev's kernels), "pm_ws_bytes" (a lower cap of the
+ *          pooled key buffers that call holds at a time, 0 = EFA_PM_WS_BYTES; results do not depend on it),
+ *          read-only "pm_us", "pm_passes", "pm_rank_passes" (see efa_pm_mean_dev) */
 int efa_ctx_set_option(efa_ctx *ctx, const char *key, long value);
 int efa_ctx_get_option(efa_ctx *ctx, const char *key, long *value);
 
@@ -833,6 +836,69 @@ int efa_neighbourhood_f32_dev(efa_ctx *ctx, long rows, int M, const float *X_dev
                               const int *slab_group,
                               const double *col_weight_dev, double *sums,
                               long long *n, long long *n_bad);
+
+/* ---- the probability-matched ensemble mean (Ebert 2001) and its patch-wise form (Clark 2017; Snook et al. 2019) ----
+ * The pattern of a rank field with the amplitude distribution of all members
+ * pooled.
+ *   X_dev [rows][M]   state members (float64; float32 for the _f32 twin), row
+ *                     i = lead*ny*nx + y*nx + x, rows = n_lead*ny*nx,
+ *                     2 <= M <= 256
+ *   rank_dev [rows]   the rank field f (float64), usually efa_products_dev's
+ *                     mean or a smoothed form of it
+ *   slab_on [n_lead] (host) 0: the slab is not read, its output is NaN and its
+ *                     n_bad 0; NULL: every slab is on
+ *   py, px            the patch, 1 <= py <= ny and 1 <= px <= nx
+ *   pick              g in [0, M): M/2 is the usual choice, M-1 Ebert's (the PM
+ *                     maximum is the pooled maximum), 0 its mirror image
+ * A SEGMENT is one patch of one slab: patch (Y, X) holds the elements with
+ * y/py == Y and x/px == X; the patches at the upper edges are smaller.
+ * (py, px) = (ny, nx) is one segment per slab, the classic PM mean.
+ * A row is EXCLUDED when f_i is not finite or a member is not finite: its
+ * output is NaN, it enters no pool, and it is counted in n_bad [n_lead] (host).
+ * Within a segment with n included rows:
+ *   order = the included rows by f ascending, ties by row index ascending;
+ *           -0.0 and +0.0 are the same value for this comparison
+ *   pool  = the n*M members of the included rows ascending, -0.0 stored as +0.0
+ *   the row at position r of order gets pool[r*M + g]
+ * pm_dev [rows] (device, float64) is written for EVERY row; for a float32 state
+ * it is the selected member widened, which is exact.  No arithmetic is done on
+ * the values: everything is integer work on order-preserving keys (the bits of
+ * v + 0.0, the sign bit flipped for v >= 0, every bit for v < 0), so the same
+ * inputs give the same bits whatever the grid, the batches and the options.
+ * One kernel reads the rows of a batch of slabs once and writes the keys at the
+ * row's place in its segment (an excluded row writes all-ones keys, which no
+ * finite value has and which sort to the end); a segmented LSD radix sort, 8
+ * bits a pass, stable, sorts the pooled keys and (with the row as payload) the
+ * rank keys; a last kernel assigns.  A pass is four launches (histograms of
+ * tiles of EFA_PM_TILE_KEYS keys, their sums per unit of EFA_PM_UNIT_BLOCKS
+ * tiles, the scan per segment, the stable scatter) ordered by the kernel
+ * boundaries alone; a pass whose byte holds one digit in every segment is
+ * skipped.  No floating-point atomics.  The call owns its workspace: the two
+ * pooled key buffers of the slabs held at a time take at most EFA_PM_WS_BYTES
+ * (option "pm_ws_bytes" lowers that; a batch is at least one slab), the rank
+ * keys, 1 KiB of histograms per tile, 3 KiB of scans per unit and the tables
+ * come on top.  It
+ * runs on the context's stream, leaves everything a later cycle reads as it
+ * found it and synchronises before returning.
+ * EFA_ERR_INVALID, before any launch and with nothing written: a NULL ctx,
+ * X_dev, rank_dev, pm_dev or n_bad, M < 2 or M > 256, a negative size or rows
+ * != n_lead*ny*nx, py outside [1, ny], px outside [1, nx], pick outside [0, M),
+ * a slab of 2^32 rows or more.
+ * Read-only options: "pm_us", device time (microseconds, HIP events) of the
+ * last call; "pm_passes" and "pm_rank_passes", the radix passes it ran on the
+ * pool and on the rank keys, summed over its batches.  "pm_blocks" caps the
+ * grids. */
+#define EFA_PM_WS_BYTES (1L << 30) /* cap of the two pooled key buffers held at a time */
+#define EFA_PM_TILE_KEYS 4096      /* keys of a sort block */
+#define EFA_PM_UNIT_BLOCKS 32      /* sort blocks of a scan unit */
+int efa_pm_mean_dev(efa_ctx *ctx, long rows, int M, const double *X_dev,
+                    long ny, long nx, long n_lead, const double *rank_dev,
+                    const int *slab_on, long py, long px, int pick,
+                    double *pm_dev, long long *n_bad);
+int efa_pm_mean_f32_dev(efa_ctx *ctx, long rows, int M, const float *X_dev,
+                        long ny, long nx, long n_lead, const double *rank_dev,
+                        const int *slab_on, long py, long px, int pick,
+                        double *pm_dev, long long *n_bad);
 
 /* ---- measurement support --------------------------------------------------
  * Device time (ms) spent in the state-sweep kernels and in the obs-space
