@@ -261,6 +261,12 @@ def _dp(a):
     return a.ctypes.data_as(c_double_p)
 
 
+def _llp(a):
+    """long long* view of a C-contiguous int64 ndarray."""
+    assert a.dtype == np.int64 and a.flags["C_CONTIGUOUS"]
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))
+
+
 def _u8p(a):
     if a is None:
         return None
@@ -805,6 +811,19 @@ class Context(object):
             _dp(lat), _dp(lon), _dp(hw), _dp(glat), _dp(glon), ncol, n_lead, _dp(out)))
         return out
 
+    def _elem_entry(self, name, X, f32):
+        """(entry point efa_<name>_dev or efa_<name>_f32_dev, the address of X as that element type); f32 None: X's own dtype"""
+        if f32 is None:
+            f32 = isinstance(X, DeviceArray) and X.dtype == np.float32
+        return getattr(self.lib, "efa_%s%s_dev" % (name, "_f32" if f32 else "")), self._addr(X, np.float32 if f32 else np.float64)
+
+    @staticmethod
+    def _group_outputs(slab_group, *shapes):
+        """slab_group as an int* (which keeps its array alive) and, for G = its largest group + 1, a zeroed int64 array of shape (G,) + s for every s of shapes"""
+        sg = np.ascontiguousarray(slab_group, dtype=np.int32).reshape(-1)
+        G = int(sg.max()) + 1 if sg.size and sg.max() >= 0 else 0
+        return (sg.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), G) + tuple(np.zeros((G,) + s, dtype=np.int64) for s in shapes)
+
     def sensitivity(self, rows, M, X, J, slab_error, ncol=None, n_lead=1, weights=None, cand=None, n_targets=0, var=None, cov=None,
                     sens=None, corr=None, dvar=None, score=None, f32=None):
         """efa_sensitivity_dev / efa_sensitivity_f32_dev.  X (rows, M) is a device array of float64 or float32
@@ -816,15 +835,13 @@ class Context(object):
         K = int(J.shape[0])
         R = np.ascontiguousarray(slab_error, dtype=np.float64).reshape(-1)
         w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
-        if f32 is None:
-            f32 = isinstance(X, DeviceArray) and X.dtype == np.float32
-        fn = self.lib.efa_sensitivity_f32_dev if f32 else self.lib.efa_sensitivity_dev
+        fn, X_p = self._elem_entry("sensitivity", X, f32)
         n = int(n_targets)
         prow = np.full(max(n, 0), -1, dtype=np.int64)
         psc = np.zeros(max(n, 0))
         mv = np.zeros((max(n, 0) + 1, max(K, 1)))
         _check(self.lib, fn(
-            self.handle, int(rows), int(M), K, self._addr(X, np.float32 if f32 else np.float64), _dp(J),
+            self.handle, int(rows), int(M), K, X_p, _dp(J),
             int(rows if ncol is None else ncol), int(n_lead), _dp(R), _dp(w), self._addr(cand, None), n,
             self._addr(var), self._addr(cov), self._addr(sens), self._addr(corr), self._addr(dvar), self._addr(score),
             prow.ctypes.data_as(ctypes.POINTER(ctypes.c_long)), _dp(psc), _dp(mv)))
@@ -838,22 +855,15 @@ class Context(object):
         device array or None.  The fields below / equal / rank (int32) are raw device addresses (`malloc_bytes`) or None,
         crps / err / var float64 device arrays or None.  Returns (hist (G, M+1), n (G,), n_bad (G,) int64, sums (G, 5)), or
         None with groups=False (fields only)."""
-        sg = np.ascontiguousarray(slab_group, dtype=np.int32).reshape(-1)
-        if f32 is None:
-            f32 = isinstance(X, DeviceArray) and X.dtype == np.float32
-        fn = self.lib.efa_verify_f32_dev if f32 else self.lib.efa_verify_dev
+        fn, X_p = self._elem_entry("verify", X, f32)
         ncol = int(rows if ncol is None else ncol)
-        G = int(sg.max()) + 1 if sg.size and sg.max() >= 0 else 0
-        hist = np.zeros((G, int(M) + 1), dtype=np.int64)
-        n = np.zeros(G, dtype=np.int64)
-        n_bad = np.zeros(G, dtype=np.int64)
+        sg_p, G, hist, n, n_bad = self._group_outputs(slab_group, (int(M) + 1,), (), ())
         sums = np.zeros((G, 5))
-        llp = ctypes.POINTER(ctypes.c_longlong)
-        out = (hist.ctypes.data_as(llp), n.ctypes.data_as(llp), n_bad.ctypes.data_as(llp), _dp(sums)) if groups else (None,) * 4
+        out = (_llp(hist), _llp(n), _llp(n_bad), _dp(sums)) if groups else (None,) * 4
         _check(self.lib, fn(
-            self.handle, int(rows), int(M), self._addr(X, np.float32 if f32 else np.float64), self._addr(verif), ncol,
+            self.handle, int(rows), int(M), X_p, self._addr(verif), ncol,
             int(n_lead), int(col_offset), int(ncol if ncol_total is None else ncol_total),
-            sg.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), self._addr(col_weight), 1 if fair else 0,
+            sg_p, self._addr(col_weight), 1 if fair else 0,
             ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), self._addr(below, None), self._addr(equal, None),
             self._addr(rank, None), self._addr(crps), self._addr(err), self._addr(var), *out))
         return (hist, n, n_bad, sums) if groups else None
@@ -866,27 +876,20 @@ class Context(object):
         (rows,), quant (Q, rows) and prob (T, rows) are float64 device arrays or None.  With verif (rows,), a float64 device
         array, slab_group (n_lead,) is a host array of group numbers (-1: slab not scored) and col_weight (ncol,) a float64
         device array or None; the call then returns (table (G, T, M+1, 2), n_bad (G, T) int64, sums (G, T, 4)), else None."""
-        if f32 is None:
-            f32 = isinstance(X, DeviceArray) and X.dtype == np.float32
-        fn = self.lib.efa_products_f32_dev if f32 else self.lib.efa_products_dev
+        fn, X_p = self._elem_entry("products", X, f32)
         ncol = int(rows if ncol is None else ncol)
         q = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
         thr = np.zeros((int(n_lead), 0)) if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float64)
         thr = thr.reshape(int(n_lead), -1) if thr.size else np.zeros((int(n_lead), 0))
         T = thr.shape[1]
-        llp = ctypes.POINTER(ctypes.c_longlong)
         sg_p, out, res = None, (None, None, None), None
         if verif is not None:
-            sg = np.ascontiguousarray(slab_group, dtype=np.int32).reshape(-1)
-            G = int(sg.max()) + 1 if sg.size and sg.max() >= 0 else 0
-            table = np.zeros((G, T, int(M) + 1, 2), dtype=np.int64)
-            n_bad = np.zeros((G, T), dtype=np.int64)
+            sg_p, G, table, n_bad = self._group_outputs(slab_group, (T, int(M) + 1, 2), (T,))
             sums = np.zeros((G, T, 4))
-            sg_p = sg.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-            out = (table.ctypes.data_as(llp), n_bad.ctypes.data_as(llp), _dp(sums))
+            out = (_llp(table), _llp(n_bad), _dp(sums))
             res = (table, n_bad, sums)
         _check(self.lib, fn(
-            self.handle, int(rows), int(M), self._addr(X, np.float32 if f32 else np.float64), ncol, int(n_lead), int(q.size), _dp(q),
+            self.handle, int(rows), int(M), X_p, ncol, int(n_lead), int(q.size), _dp(q),
             int(T), _dp(thr), self._addr(mean), self._addr(sd), self._addr(quant), self._addr(prob), self._addr(verif), sg_p,
             self._addr(col_weight), *out))
         return res
@@ -900,25 +903,18 @@ class Context(object):
         (rows,), a float64 device array, slab_group (n_lead,) is a host array of group numbers (-1: slab not scored) and
         col_weight (ny*nx,) a float64 device array or None; the call then returns (sums (G, R, T, 6), n (G, R, T), n_bad
         (G, R, T) int64), else None."""
-        if f32 is None:
-            f32 = isinstance(X, DeviceArray) and X.dtype == np.float32
-        fn = self.lib.efa_neighbourhood_f32_dev if f32 else self.lib.efa_neighbourhood_dev
+        fn, X_p = self._elem_entry("neighbourhood", X, f32)
         thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(int(n_lead), -1)
         rad = np.ascontiguousarray(radii, dtype=np.int32).reshape(-1)
         T, R = thr.shape[1], rad.size
-        llp = ctypes.POINTER(ctypes.c_longlong)
         sg_p, out, res = None, (None, None, None), None
         if verif is not None:
-            sg = np.ascontiguousarray(slab_group, dtype=np.int32).reshape(-1)
-            G = int(sg.max()) + 1 if sg.size and sg.max() >= 0 else 0
+            sg_p, G, n, n_bad = self._group_outputs(slab_group, (R, T), (R, T))
             sums = np.zeros((G, R, T, 6))
-            n = np.zeros((G, R, T), dtype=np.int64)
-            n_bad = np.zeros((G, R, T), dtype=np.int64)
-            sg_p = sg.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-            out = (_dp(sums), n.ctypes.data_as(llp), n_bad.ctypes.data_as(llp))
+            out = (_dp(sums), _llp(n), _llp(n_bad))
             res = (sums, n, n_bad)
         _check(self.lib, fn(
-            self.handle, int(rows), int(M), self._addr(X, np.float32 if f32 else np.float64), int(ny), int(nx), int(n_lead), int(T),
+            self.handle, int(rows), int(M), X_p, int(ny), int(nx), int(n_lead), int(T),
             _dp(thr), int(R), rad.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), int(shape), 1 if wrap_x else 0, self._addr(nep),
             self._addr(nmep), self._addr(verif), sg_p, self._addr(col_weight), *out))
         return res
@@ -929,9 +925,7 @@ class Context(object):
         array, both only read; pm (rows,) a float64 device array, written for every row; slab_on (n_lead,) a host array (0: the
         slab is not read) or None; patch (py, px) or None (the whole slab); pick an int in [0, M) or None (M // 2).  Returns
         n_bad (n_lead,) int64."""
-        if f32 is None:
-            f32 = isinstance(X, DeviceArray) and X.dtype == np.float32
-        fn = self.lib.efa_pm_mean_f32_dev if f32 else self.lib.efa_pm_mean_dev
+        fn, X_p = self._elem_entry("pm_mean", X, f32)
         py, px = (int(ny), int(nx)) if patch is None else (int(patch[0]), int(patch[1]))
         on_p = None
         if slab_on is not None:
@@ -941,9 +935,9 @@ class Context(object):
             on_p = on.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
         n_bad = np.zeros(int(n_lead), dtype=np.int64)
         _check(self.lib, fn(
-            self.handle, int(rows), int(M), self._addr(X, np.float32 if f32 else np.float64), int(ny), int(nx), int(n_lead),
+            self.handle, int(rows), int(M), X_p, int(ny), int(nx), int(n_lead),
             self._addr(rank), on_p, py, px, int(M) // 2 if pick is None else int(pick), self._addr(pm),
-            n_bad.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+            _llp(n_bad)))
         return n_bad
 
     def gram(self, rows, M, X, slab_scale, ncol=None, n_lead=1, col_weight=None, f32=None):
@@ -952,14 +946,12 @@ class Context(object):
         >= 0 (0: the slab is not read); col_weight (ncol,) a float64 device array or None.  Returns (gram (M, M), n, n_bad,
         sums (2,) = sum w, sum w s^2) over the used, good rows."""
         sc = np.ascontiguousarray(slab_scale, dtype=np.float64).reshape(-1)
-        if f32 is None:
-            f32 = isinstance(X, DeviceArray) and X.dtype == np.float32
-        fn = self.lib.efa_gram_f32_dev if f32 else self.lib.efa_gram_dev
+        fn, X_p = self._elem_entry("gram", X, f32)
         G = np.zeros((int(M), int(M)))
         n, n_bad = ctypes.c_longlong(0), ctypes.c_longlong(0)
         sums = np.zeros(2)
         _check(self.lib, fn(
-            self.handle, int(rows), int(M), self._addr(X, np.float32 if f32 else np.float64), int(rows if ncol is None else ncol),
+            self.handle, int(rows), int(M), X_p, int(rows if ncol is None else ncol),
             int(n_lead), _dp(sc), self._addr(col_weight), _dp(G), ctypes.byref(n), ctypes.byref(n_bad), _dp(sums)))
         return G, int(n.value), int(n_bad.value), sums
 

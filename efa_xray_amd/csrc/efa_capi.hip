@@ -164,10 +164,32 @@ int efa_ctx_set_stream(efa_ctx* c, void* hip_stream) {
   return change_stream(c, reinterpret_cast<hipStream_t>(hip_stream));
 }
 
+namespace {
+// The grid caps of the diagnostics' kernels (0: the default, which is also the bound); the results do not depend on them.
+struct BlocksOption {
+  const char* key;
+  long efa_ctx::*member;
+  long bound;
+};
+const BlocksOption kBlocksOptions[] = {{"verify_blocks", &efa_ctx::verify_blocks, 2048},
+                                       {"products_blocks", &efa_ctx::products_blocks, 2048},
+                                       {"gram_blocks", &efa_ctx::gram_blocks, 2048},
+                                       {"neighbourhood_blocks", &efa_ctx::neighbourhood_blocks, 2048},
+                                       {"pm_blocks", &efa_ctx::pm_blocks, 2048}};
+const BlocksOption* blocks_option(const char* key) {
+  for (const BlocksOption& o : kBlocksOptions)
+    if (!strcmp(key, o.key)) return &o;
+  return nullptr;
+}
+}  // namespace
+
 int efa_ctx_set_option(efa_ctx* c, const char* key, long value) {
   EFA_TRY(use(c));
   if (!key) return fail(EFA_ERR_INVALID, "null option key");
-  if (!strcmp(key, "obs_batch")) {
+  if (const BlocksOption* o = blocks_option(key)) {
+    if (value < 0 || value > o->bound) return fail(EFA_ERR_INVALID, "%s must be in [0,%ld]", o->key, o->bound);
+    c->*(o->member) = value;
+  } else if (!strcmp(key, "obs_batch")) {
     if (value < 1 || value > efa::kMaxBatch) return fail(EFA_ERR_INVALID, "obs_batch must be in [1,%d]", efa::kMaxBatch);
     c->obs_batch = value;
   } else if (!strcmp(key, "path")) {
@@ -213,30 +235,10 @@ int efa_ctx_set_option(efa_ctx* c, const char* key, long value) {
     }
     if (value > 0) EFA_HIP(efa::launch_occupy((int)c->dbg_occupy_blocks, 120 * 1024, (double)value, c->dbg_stream));
     else EFA_HIP(hipStreamSynchronize(c->dbg_stream));
-  } else if (!strcmp(key, "verify_blocks")) {
-    // grid cap of efa_verify_dev's pass (0: the default); the results do not depend on it
-    if (value < 0 || value > 2048) return fail(EFA_ERR_INVALID, "verify_blocks must be in [0,2048]");
-    c->verify_blocks = value;
-  } else if (!strcmp(key, "products_blocks")) {
-    // grid cap of efa_products_dev's pass (0: the default); the results do not depend on it
-    if (value < 0 || value > 2048) return fail(EFA_ERR_INVALID, "products_blocks must be in [0,2048]");
-    c->products_blocks = value;
-  } else if (!strcmp(key, "gram_blocks")) {
-    // grid cap of efa_gram_dev's pass (0: the default); the results do not depend on it
-    if (value < 0 || value > 2048) return fail(EFA_ERR_INVALID, "gram_blocks must be in [0,2048]");
-    c->gram_blocks = value;
-  } else if (!strcmp(key, "neighbourhood_blocks")) {
-    // grid cap of efa_neighbourhood_dev's kernels (0: the default); the results do not depend on it
-    if (value < 0 || value > 2048) return fail(EFA_ERR_INVALID, "neighbourhood_blocks must be in [0,2048]");
-    c->neighbourhood_blocks = value;
   } else if (!strcmp(key, "nbr_ws_bytes")) {
     // a lower cap of the records efa_neighbourhood_dev holds at a time (0: EFA_NBR_WS_BYTES); the results do not depend on it
     if (value < 0 || value > EFA_NBR_WS_BYTES) return fail(EFA_ERR_INVALID, "nbr_ws_bytes must be in [0,%ld]", (long)EFA_NBR_WS_BYTES);
     c->nbr_ws_bytes = value;
-  } else if (!strcmp(key, "pm_blocks")) {
-    // grid cap of efa_pm_mean_dev's kernels (0: the default); the results do not depend on it
-    if (value < 0 || value > 2048) return fail(EFA_ERR_INVALID, "pm_blocks must be in [0,2048]");
-    c->pm_blocks = value;
   } else if (!strcmp(key, "pm_ws_bytes")) {
     // a lower cap of the pooled buffers efa_pm_mean_dev holds at a time (0: EFA_PM_WS_BYTES); the results do not depend on it
     if (value < 0 || value > EFA_PM_WS_BYTES) return fail(EFA_ERR_INVALID, "pm_ws_bytes must be in [0,%ld]", (long)EFA_PM_WS_BYTES);
@@ -343,7 +345,8 @@ int efa_inflate_rows_dev(efa_ctx* c, long rows, int M, double* X_dev, const doub
 int efa_ctx_get_option(efa_ctx* c, const char* key, long* value) {
   EFA_TRY(use(c));
   if (!key || !value) return fail(EFA_ERR_INVALID, "null argument");
-  if (!strcmp(key, "obs_batch")) *value = c->obs_batch;
+  if (const BlocksOption* o = blocks_option(key)) *value = c->*(o->member);
+  else if (!strcmp(key, "obs_batch")) *value = c->obs_batch;
   else if (!strcmp(key, "path")) *value = c->path;
   else if (!strcmp(key, "timing")) *value = c->timing;
   else if (!strcmp(key, "gram")) *value = c->use_gram;
@@ -370,18 +373,13 @@ int efa_ctx_get_option(efa_ctx* c, const char* key, long* value) {
   else if (!strcmp(key, "impact_us")) *value = c->impact_us;  // the last efa_obs_impact_dev (efa_impact.hip)
   else if (!strcmp(key, "sens_us")) *value = c->sens_us;  // the last efa_sensitivity_dev (efa_sensitivity.hip)
   else if (!strcmp(key, "verify_us")) *value = c->verify_us;  // the last efa_verify_dev (efa_verify.hip)
-  else if (!strcmp(key, "verify_blocks")) *value = c->verify_blocks;
   else if (!strcmp(key, "products_us")) *value = c->products_us;  // the last efa_products_dev (efa_products.hip)
-  else if (!strcmp(key, "products_blocks")) *value = c->products_blocks;
   else if (!strcmp(key, "gram_us")) *value = c->gram_us;  // the last efa_gram_dev (efa_gram.hip)
-  else if (!strcmp(key, "gram_blocks")) *value = c->gram_blocks;
   else if (!strcmp(key, "neighbourhood_us")) *value = c->neighbourhood_us;  // the last efa_neighbourhood_dev (efa_neighbourhood.hip)
-  else if (!strcmp(key, "neighbourhood_blocks")) *value = c->neighbourhood_blocks;
   else if (!strcmp(key, "nbr_ws_bytes")) *value = c->nbr_ws_bytes;
   else if (!strcmp(key, "pm_us")) *value = c->pm_us;  // the last efa_pm_mean_dev (efa_pmmean.hip)
   else if (!strcmp(key, "pm_passes")) *value = c->pm_passes;
   else if (!strcmp(key, "pm_rank_passes")) *value = c->pm_rank_passes;
-  else if (!strcmp(key, "pm_blocks")) *value = c->pm_blocks;
   else if (!strcmp(key, "pm_ws_bytes")) *value = c->pm_ws_bytes;
   else return fail(EFA_ERR_INVALID, "unknown option '%s'", key);
   return EFA_OK;

@@ -11,6 +11,9 @@
 //   efa_pmmean.hip   the probability-matched mean and the segmented radix sort under it: its kernels and the driver of efa_pm_mean_dev
 //   efa_gram.hip     the ensemble Gram matrix: its kernels and the driver of efa_gram_dev
 //   efa_comm.hip     RCCL
+// Headers the diagnostics share: efa_quadrow.h (the four-lane row layout of k_sens_pass, k_verify, k_products and k_nbr_records),
+// efa_sortnet.h (the bitonic network on it), efa_quadreduce.h (table flush, chunk partial, k_group_reduce) and efa_diag.h (their
+// drivers' host scaffolding: the interval helper, WsLayout, check_slab_groups, pad_thresholds, pairs_aligned, clamp_blocks, launch_quad).
 // One call's arguments and results travel as arguments and return values; the context (efa_ctx.h) holds settings, caches,
 // workspaces and what the last obs phase left for the state phase.  A state call's rows travel with their element type (StateRows);
 // its route is decided once, by plan_state, and every caller issues the launches through run_state_plan.

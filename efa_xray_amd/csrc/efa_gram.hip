@@ -25,7 +25,8 @@
 //     the 16 sums), for the elements a <= b (from the tile or from its transpose, whichever was computed), mirrors them and divides by
 //     M-1: G[a][b] and G[b][a] are one number.  No floating-point atomics; the same inputs give the same bits for every grid.
 #include "efa_device.h"
-#include "efa_driver.h"
+#include "efa_diag.h"
+#include "efa_quadrow.h"
 
 #include <cmath>
 #include <vector>
@@ -53,15 +54,6 @@ struct GramArgs {
   double* spart;        // [nstreams][2]: sum w, sum c
   long long* cpart;     // [nstreams][2]: good rows, bad rows
 };
-
-template <typename E>
-struct GramPair;
-template <>
-struct GramPair<double> { typedef double2 type; };
-template <>
-struct GramPair<float> { typedef float2 type; };
-
-__device__ __forceinline__ bool gram_finite(double v) { return __builtin_fabs(v) < __builtin_inf(); }
 
 constexpr int gram_waves(int T) { return T > 8 ? 8 : 4; }
 
@@ -115,7 +107,7 @@ __global__ __launch_bounds__(64 * gram_waves(T)) void k_gram(const GramArgs a) {
       // BL paired loads (BL / 2 single ones) in flight per lane and batch: the accumulators leave no room for more at 16 tiles, and
       // eight cost the 80-member instantiation its fourth workgroup per CU (as did asking for the next chunk's weights early)
       if (AL) {
-        typedef typename GramPair<E>::type P2;
+        typedef typename ElemPair<E>::type P2;
         constexpr int NP = kGramRows * MP / 2;
 #pragma unroll 1
         for (int i0 = 0; i0 < NP; i0 += BL * NTH) {
@@ -167,7 +159,7 @@ __global__ __launch_bounds__(64 * gram_waves(T)) void k_gram(const GramArgs a) {
         for (int m = cj; m < M; m += LPR) {
           const double x = xr[m];
           sum += x;
-          flaw |= (gram_finite(x) ? 0 : 1) | ((x != x0) ? 2 : 0);
+          flaw |= (finite64(x) ? 0 : 1) | ((x != x0) ? 2 : 0);
         }
 #pragma unroll
         for (int off = LPR / 2; off >= 1; off >>= 1) {
@@ -175,7 +167,7 @@ __global__ __launch_bounds__(64 * gram_waves(T)) void k_gram(const GramArgs a) {
           flaw |= __shfl_xor(flaw, off, 64);
         }
         const bool used = w > 0.0;
-        const bool good = used && !(flaw & 1) && gram_finite(w);
+        const bool good = used && !(flaw & 1) && finite64(w);
         // a row whose members are all equal has deviations of exactly 0 (its sum / M need not give the member back)
         const double mean = (flaw & 2) ? sum / dM : x0;
         const double c = good ? w * (sc * sc) : 0.0;
@@ -323,7 +315,7 @@ hipError_t launch_gram(const GramArgs& a, Elem elem, int blocks, hipStream_t s) 
   if (a.M < 2 || a.M > kMaxMembers || a.nstreams < 1) return hipErrorInvalidValue;
   int grid = a.nstreams < blocks ? a.nstreams : blocks;
   if (grid < 1) grid = 1;
-  const bool al = (a.M % 2 == 0) && (reinterpret_cast<uintptr_t>(a.X) % (2 * elem_size(elem)) == 0);
+  const bool al = efa_host::pairs_aligned(a.X, a.M, elem);
   return dispatch_width((a.M + 15) / 16, WidthRange<1, kMaxMembers / 16>{}, [&](auto t_c) {
     constexpr int t = decltype(t_c)::value;
     return elem == Elem::f32 ? gram_launch<t, float>(a, al, grid, s) : gram_launch<t, double>(a, al, grid, s);
@@ -368,17 +360,16 @@ int gram(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, long ncol, 
     const int MP = 16 * ((M + 15) / 16);
     const int S = gram_streams(M, nchunks);
     // gram_ws: part [S][MP][MP] | G [M][M] | spart [S][2] | sums [2] | cpart [S][2] | cnt [2] | scales [n_lead]
-    const size_t n_part = (size_t)S * MP * MP, n_G = (size_t)M * M, n_sp = (size_t)S * 2;
-    EFA_TRY(c->gram_ws.reserve((n_part + n_G + n_sp + 2 + n_sp + 2 + (size_t)n_lead) * 8));
-    if (!c->gram_iv.begin.h) EFA_HIP(hipEventCreate(&c->gram_iv.begin.h));
-    if (!c->gram_iv.end.h) EFA_HIP(hipEventCreate(&c->gram_iv.end.h));
-    double* d_part = c->gram_ws.as<double>();
-    double* d_G = d_part + n_part;
-    double* d_sp = d_G + n_G;
-    double* d_sums = d_sp + n_sp;
-    long long* d_cp = reinterpret_cast<long long*>(d_sums + 2);
-    long long* d_cnt = d_cp + n_sp;
-    double* d_scale = reinterpret_cast<double*>(d_cnt + 2);
+    const size_t n_G = (size_t)M * M;
+    WsLayout ws;
+    const auto r_part = ws.add<double>((size_t)S * MP * MP), r_G = ws.add<double>(n_G), r_sp = ws.add<double>((size_t)S * 2),
+               r_sums = ws.add<double>(2);
+    const auto r_cp = ws.add<long long>((size_t)S * 2), r_cnt = ws.add<long long>(2);
+    const auto r_scale = ws.add<double>((size_t)n_lead);
+    EFA_TRY(c->gram_ws.reserve(ws.bytes()));
+    double *d_part = r_part(c->gram_ws), *d_G = r_G(c->gram_ws), *d_sp = r_sp(c->gram_ws), *d_sums = r_sums(c->gram_ws);
+    long long *d_cp = r_cp(c->gram_ws), *d_cnt = r_cnt(c->gram_ws);
+    double* d_scale = r_scale(c->gram_ws);
     EFA_HIP(hipMemcpyAsync(d_scale, slab_scale, (size_t)n_lead * sizeof(double), hipMemcpyHostToDevice, s));
     GramArgs a{};
     a.X = X_dev;
@@ -393,21 +384,17 @@ int gram(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, long ncol, 
     a.part = d_part;
     a.spart = d_sp;
     a.cpart = d_cp;
-    long blocks = c->gram_blocks;
-    if (blocks < 1 || blocks > kGramBlocks) blocks = kGramBlocks;
-    EFA_HIP(hipEventRecord(c->gram_iv.begin, s));
-    EFA_HIP(launch_gram(a, elem, (int)blocks, s));
+    EFA_TRY(interval_begin(c->gram_iv, s));
+    EFA_HIP(launch_gram(a, elem, (int)clamp_blocks(c->gram_blocks, kGramBlocks), s));
     hipLaunchKernelGGL(k_gram_reduce, dim3((unsigned)M, (unsigned)(MP / 16)), dim3(kGramRedThreads), 0, s, M, MP, S, d_part, d_sp, d_cp, d_G, d_sums,
                        d_cnt);
     EFA_HIP(hipGetLastError());
-    EFA_HIP(hipEventRecord(c->gram_iv.end, s));
+    EFA_TRY(interval_end(c->gram_iv, s));
     EFA_HIP(hipMemcpyAsync(h_G.data(), d_G, n_G * sizeof(double), hipMemcpyDeviceToHost, s));
     EFA_HIP(hipMemcpyAsync(h_sums, d_sums, sizeof(h_sums), hipMemcpyDeviceToHost, s));
     EFA_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, s));
     EFA_HIP(hipStreamSynchronize(s));
-    float ms = 0.f;
-    EFA_HIP(hipEventElapsedTime(&ms, c->gram_iv.begin, c->gram_iv.end));
-    c->gram_us = (long)std::llround((double)ms * 1000.0);
+    EFA_TRY(interval_us(c->gram_iv, &c->gram_us));
   }
   for (size_t i = 0; i < h_G.size(); ++i) gram_out[i] = h_G[i];
   *n = h_cnt[0];

@@ -8,9 +8,8 @@
 //   and per group of slabs, radius and threshold the sums of w, w (NEP - O)^2, w NEP^2, w O^2, w NEP, w O over the scored centres.
 //   Everything is integer arithmetic up to the one division of a field.
 //
-// k_nbr_records is the only pass over the state.  It reads the rows in the row layout of k_products (efa_products.hip): a wave owns
-// 16 consecutive rows of a slab, lane (g = l>>4, n = l&15) loads members {8u+2g, 8u+2g+1} of row n with one 16-byte load, so member
-// m = 8u + 2g + e is bit 8(u & 7) + 2g + e of mask word u >> 3.  A lane builds its bits of every word, two __shfl_xor steps OR the
+// k_nbr_records is the only pass over the state.  It reads the rows in the four-lane row layout (efa_quadrow.h): lane g of a row
+// holds members {8u+2g, 8u+2g+1}, so member m = 8u + 2g + e is bit 8(u & 7) + 2g + e of mask word u >> 3.  A lane builds its bits of every word, two __shfl_xor steps OR the
 // four lanes of a row together, and k is the popcount.  Per row and threshold it leaves in the call's workspace a 16-bit k, and the
 // mask words when NMEP is wanted; per row a 16-bit flag word: bit 0 valid, bit 1 "would be scored but has a member that is not
 // finite", bit 8 + j the event o_j = (y > t_j).  An invalid row has k = 0, mask = 0 and no event bit: it adds nothing to a window.
@@ -25,10 +24,11 @@
 // whose span 2h + 1 has floor(log2) = L, the two table entries that cover the span.  Both cost O(2r + 1) per centre.
 //
 // Sums: a thread adds up its kNbrTY*kNbrTX/256 centres in index order, the workgroup adds its threads with a fixed butterfly and
-// writes the tile's partial; k_nbr_reduce adds the partials of each group in a fixed order.  Tiles, not workgroups, own the
+// writes the tile's partial; k_group_reduce (efa_quadreduce.h) adds the partials of each group in a fixed order.  Tiles, not workgroups, own the
 // partials, so the grid and the batching of the slabs change no bit.  No floating-point atomics.
 #include "efa_device.h"
-#include "efa_driver.h"
+#include "efa_diag.h"
+#include "efa_quadreduce.h"
 
 #include <cmath>
 #include <vector>
@@ -36,7 +36,7 @@
 namespace efa {
 namespace {
 
-constexpr int kNbrThreads = 256;       // 4 waves
+constexpr int kNbrThreads = kQuadThreads;
 constexpr int kNbrBlocks = 2048;       // default grid cap of both kernels (option "neighbourhood_blocks" lowers it)
 constexpr int kNbrMaxThr = EFA_NBR_MAX_THRESHOLDS;
 constexpr int kNbrMaxRad = EFA_NBR_MAX_RADII;
@@ -80,15 +80,6 @@ struct NbrWinArgs {
   long long* cnt;        // [tiles of the call][nr][nt][2]: scored centres, bad ones that would be scored
 };
 
-template <typename E>
-struct NbrPair;
-template <>
-struct NbrPair<double> { typedef double2 type; };
-template <>
-struct NbrPair<float> { typedef float2 type; };
-
-__device__ __forceinline__ bool nbr_finite(double v) { return __builtin_fabs(v) < __builtin_inf(); }
-
 // the waves of a workgroup own whole LDS rows: what one lane wrote, another lane of the same wave may read behind this
 __device__ __forceinline__ void nbr_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -116,9 +107,9 @@ __global__ __launch_bounds__(kNbrThreads) void k_nbr_records(const NbrRecArgs a)
     const long colc = live ? col : a.ncol - 1;
     const long r = lead * a.ncol + colc;
     const size_t rec = (size_t)sb * a.ncol + colc;
-    // the lane's quarter of the row, opaque to the optimiser (see k_products)
-    int gq = lane >> 4;
-    asm volatile("" : "+v"(gq));
+    const int gq = quad_lane_quarter(lane);
+    // (the loader and the count's row sum are written out, not taken from efa_quadrow.h: only so is the code the one measured
+    // before the layout was shared, DESIGN.md 7j2.  The text is quad_load_row's and quad_row_sum's.)
     double d[LP];
     {
       const E* p = reinterpret_cast<const E*>(a.X) + (size_t)r * M;
@@ -127,7 +118,7 @@ __global__ __launch_bounds__(kNbrThreads) void k_nbr_records(const NbrRecArgs a)
         for (int u = 0; u < NU; ++u) {
           int m0 = 8 * u + 2 * gq;
           m0 = (m0 < M) ? m0 : M - 2;
-          const typename NbrPair<E>::type v = *reinterpret_cast<const typename NbrPair<E>::type*>(p + m0);
+          const typename ElemPair<E>::type v = *reinterpret_cast<const typename ElemPair<E>::type*>(p + m0);
           d[2 * u] = v.x;
           d[2 * u + 1] = v.y;
         }
@@ -143,12 +134,9 @@ __global__ __launch_bounds__(kNbrThreads) void k_nbr_records(const NbrRecArgs a)
     const double y = ver ? a.verif[r] : 0.0;
     bool badl = false;
 #pragma unroll
-    for (int c = 0; c < LP; ++c) {
-      const bool ok = 8 * (c >> 1) + 2 * gq + (c & 1) < M;  // the slot holds a real member
-      badl = badl || (ok && !nbr_finite(d[c]));
-    }
-    const bool bad = ((__ballot(badl) >> n) & 0x0001000100010001ull) != 0ull;
-    const bool yfin = !ver || nbr_finite(y);
+    for (int c = 0; c < LP; ++c) badl = badl || (quad_slot_ok(c, gq, M) && !finite64(d[c]));
+    const bool bad = quad_row_any(badl, n);
+    const bool yfin = !ver || finite64(y);
     const bool valid = !bad && yfin;
     unsigned int flags = (valid ? 1u : 0u) | ((bad && ver && yfin) ? 2u : 0u);
     const double* thr = a.thr + (size_t)lead * kNbrMaxThr;
@@ -164,8 +152,7 @@ __global__ __launch_bounds__(kNbrThreads) void k_nbr_records(const NbrRecArgs a)
 #pragma unroll
         for (int c = 0; c < LP; ++c) {  // the lane's bits as lane g = 0 would hold them, moved to their place by one shift below
           const int u = c >> 1;
-          const bool ok = 8 * u + 2 * gq + (c & 1) < M;
-          wd[u >> 3] |= (ok && d[c] > t) ? 1ull << (8 * (u & 7) + (c & 1)) : 0ull;
+          wd[u >> 3] |= (quad_slot_ok(c, gq, M) && d[c] > t) ? 1ull << (8 * (u & 7) + (c & 1)) : 0ull;
         }
 #pragma unroll
         for (int w = 0; w < NW; ++w) {
@@ -177,10 +164,7 @@ __global__ __launch_bounds__(kNbrThreads) void k_nbr_records(const NbrRecArgs a)
         }
       } else {
 #pragma unroll
-        for (int c = 0; c < LP; ++c) {
-          const bool ok = 8 * (c >> 1) + 2 * gq + (c & 1) < M;
-          k += (ok && d[c] > t) ? 1 : 0;
-        }
+        for (int c = 0; c < LP; ++c) k += (quad_slot_ok(c, gq, M) && d[c] > t) ? 1 : 0;
         k += __shfl_xor(k, 16, 64);
         k += __shfl_xor(k, 32, 64);
       }
@@ -239,7 +223,7 @@ __global__ __launch_bounds__(kNbrThreads) void k_nbr_windows(const NbrWinArgs a)
 #pragma unroll 1
     for (int j = 0; j < a.nt; ++j) {
       const double t = a.thr[(size_t)lead * kNbrMaxThr + j];
-      if (!nbr_finite(t)) {  // (uniform) no threshold j in this slab: NaN fields, nothing scored
+      if (!finite64(t)) {  // (uniform) no threshold j in this slab: NaN fields, nothing scored
 #pragma unroll 1
         for (int ri = 0; ri < a.nr; ++ri)
 #pragma unroll
@@ -473,48 +457,10 @@ __global__ __launch_bounds__(kNbrThreads) void k_nbr_unread(long rows, long ncol
   }
 }
 
-// workgroup (g, radius and threshold): the partials of the tiles of group g, thread by thread in tile order, then a tree over the threads
-__global__ __launch_bounds__(kNbrThreads) void k_nbr_reduce(long ntiles, long tps, int nrt, const int* __restrict__ slabs,
-                                                          const int* __restrict__ sgroup, const double* __restrict__ part,
-                                                          const long long* __restrict__ cnt, double* __restrict__ sums,
-                                                          long long* __restrict__ n_out, long long* __restrict__ nbad_out) {
-  __shared__ double s_s[kNbrThreads];
-  __shared__ long long c_s[kNbrThreads];
-  const int tid = threadIdx.x;
-  const int grp = (int)blockIdx.x, f = (int)blockIdx.y;
-  for (int k = 0; k < kNbrSums + 2; ++k) {
-    double s = 0.0;
-    long long c = 0;
-    for (long i = tid; i < ntiles; i += kNbrThreads) {
-      if (sgroup[slabs[i / tps]] != grp) continue;
-      if (k < kNbrSums) s += part[((size_t)i * nrt + f) * kNbrSums + k];
-      else c += cnt[((size_t)i * nrt + f) * 2 + (k - kNbrSums)];
-    }
-    s_s[tid] = s;
-    c_s[tid] = c;
-    __syncthreads();
-    for (int off = kNbrThreads / 2; off >= 1; off >>= 1) {
-      if (tid < off) {
-        s_s[tid] += s_s[tid + off];
-        c_s[tid] += c_s[tid + off];
-      }
-      __syncthreads();
-    }
-    if (tid == 0) {
-      if (k < kNbrSums) sums[((size_t)grp * nrt + f) * kNbrSums + k] = s_s[0];
-      else if (k == kNbrSums) n_out[(size_t)grp * nrt + f] = c_s[0];
-      else nbad_out[(size_t)grp * nrt + f] = c_s[0];
-    }
-    __syncthreads();
-  }
-}
-
 template <bool MASK>
-hipError_t launch_records_m(const NbrRecArgs& a, Elem elem, long grid, int nu_p, hipStream_t s) {
-  return dispatch_width(nu_p, std::integer_sequence<int, 1, 2, 4, 8, 16, 32>{}, [&](auto nu_c) {
-    constexpr int nu = decltype(nu_c)::value;
-    if (elem == Elem::f32) hipLaunchKernelGGL((k_nbr_records<nu, float, MASK>), dim3((unsigned)grid), dim3(kNbrThreads), 0, s, a);
-    else hipLaunchKernelGGL((k_nbr_records<nu, double, MASK>), dim3((unsigned)grid), dim3(kNbrThreads), 0, s, a);
+hipError_t launch_records_m(const NbrRecArgs& a, Elem elem, long grid, hipStream_t s) {
+  return efa_host::launch_quad(a.M, elem, [&](auto nu_c, auto e) {
+    hipLaunchKernelGGL((k_nbr_records<decltype(nu_c)::value, decltype(e), MASK>), dim3((unsigned)grid), dim3(kNbrThreads), 0, s, a);
     return hipGetLastError();
   });
 }
@@ -524,9 +470,7 @@ hipError_t launch_records(const NbrRecArgs& a, Elem elem, long blocks, hipStream
   if (a.ntiles <= 0) return hipSuccess;
   long grid = (a.ntiles + kNbrThreads / 64 - 1) / (kNbrThreads / 64);
   if (grid > blocks) grid = blocks;
-  int nu_p = 1;
-  while (nu_p * 8 < a.M) nu_p *= 2;
-  return a.mask ? launch_records_m<true>(a, elem, grid, nu_p, s) : launch_records_m<false>(a, elem, grid, nu_p, s);
+  return a.mask ? launch_records_m<true>(a, elem, grid, s) : launch_records_m<false>(a, elem, grid, s);
 }
 
 hipError_t launch_windows(const NbrWinArgs& a, long blocks, hipStream_t s) {
@@ -577,11 +521,8 @@ int neighbourhood(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, lo
   if (!nep_dev && !nmep_dev && !score) return fail(EFA_ERR_INVALID, "%s: no output wanted (nep_dev, nmep_dev, and sums with verif_dev)", me);
   if (verif_dev && !slab_group) return fail(EFA_ERR_INVALID, "%s: verif_dev needs slab_group", me);
   int G = 0;
-  if (verif_dev)
-    for (long s = 0; s < n_lead; ++s) {
-      if (slab_group[s] < -1) return fail(EFA_ERR_INVALID, "%s: slab_group[%ld] = %d must be >= -1", me, s, slab_group[s]);
-      if (score && slab_group[s] + 1 > G) G = slab_group[s] + 1;
-    }
+  if (verif_dev) EFA_TRY(check_slab_groups(me, slab_group, n_lead, &G));
+  if (!score) G = 0;
 
   c->neighbourhood_us = 0;
   const int nrt = nr * nt;
@@ -594,13 +535,10 @@ int neighbourhood(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, lo
     const bool fields = nep_dev || nmep_dev;
     // the slabs that are read: a finite threshold, and a field or a group that wants them
     std::vector<int> h_sg((size_t)n_lead, -1), h_act((size_t)n_lead, 0), h_slabs;
-    std::vector<double> h_thr((size_t)n_lead * kNbrMaxThr, std::nan(""));
+    const std::vector<double> h_thr = pad_thresholds(thr, n_lead, nt, kNbrMaxThr);
     for (long l = 0; l < n_lead; ++l) {
       bool any = false;
-      for (int j = 0; j < nt; ++j) {
-        h_thr[(size_t)l * kNbrMaxThr + j] = thr[(size_t)l * nt + j];
-        any = any || std::isfinite(thr[(size_t)l * nt + j]);
-      }
+      for (int j = 0; j < nt; ++j) any = any || std::isfinite(thr[(size_t)l * nt + j]);
       if (score) h_sg[l] = slab_group[l];
       if (any && (fields || h_sg[l] >= 0)) {
         h_act[l] = 1;
@@ -622,27 +560,27 @@ int neighbourhood(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, lo
     const size_t Rmax = (size_t)per_batch * ncol;
     // nbr_ws: mask [nt][nw][Rmax] | part [tiles][nrt][6] | cnt [tiles][nrt][2] | sums [G][nrt][6] | n, n_bad [G][nrt] |
     //         thr [n_lead][8] | slab groups, active flags [n_lead], active slabs [nact] | k16 [nt][Rmax] | flag [Rmax]
-    const size_t n_mask = nmep_dev ? (size_t)nt * nw * Rmax : 0;
     const size_t n_part = score ? (size_t)tiles_all * nrt * kNbrSums : 0, n_cnt = score ? (size_t)tiles_all * nrt * 2 : 0;
-    const size_t n_sums = ngf * kNbrSums, n_thr = (size_t)n_lead * kNbrMaxThr;
-    const size_t n_int = (2 * (size_t)n_lead + (size_t)nact + 1) / 2 * 2;
-    const size_t n_k16 = ((size_t)nt * Rmax + 3) / 4 * 4;
-    EFA_TRY(c->nbr_ws.reserve((n_mask + n_part + n_cnt + n_sums + 2 * ngf + n_thr) * 8 + n_int * sizeof(int) + (n_k16 + Rmax) * 2));
-    if (!c->nbr_iv.begin.h) EFA_HIP(hipEventCreate(&c->nbr_iv.begin.h));
-    if (!c->nbr_iv.end.h) EFA_HIP(hipEventCreate(&c->nbr_iv.end.h));
-    unsigned long long* d_mask = c->nbr_ws.as<unsigned long long>();
-    double* d_part = reinterpret_cast<double*>(d_mask + n_mask);
-    long long* d_cnt = reinterpret_cast<long long*>(d_part + n_part);
-    double* d_sums = reinterpret_cast<double*>(d_cnt + n_cnt);
-    long long* d_n = reinterpret_cast<long long*>(d_sums + n_sums);
-    long long* d_nbad = d_n + ngf;
-    double* d_thr = reinterpret_cast<double*>(d_nbad + ngf);
-    int* d_sg = reinterpret_cast<int*>(d_thr + n_thr);
-    int* d_act = d_sg + n_lead;
-    int* d_slabs = d_act + n_lead;
-    unsigned short* d_k16 = reinterpret_cast<unsigned short*>(d_sg + n_int);
-    unsigned short* d_flag = d_k16 + n_k16;
-    EFA_HIP(hipMemcpyAsync(d_thr, h_thr.data(), n_thr * sizeof(double), hipMemcpyHostToDevice, s));
+    const size_t n_sums = ngf * kNbrSums;
+    WsLayout ws;
+    const auto r_mask = ws.add<unsigned long long>(nmep_dev ? (size_t)nt * nw * Rmax : 0);
+    const auto r_part = ws.add<double>(n_part);
+    const auto r_cnt = ws.add<long long>(n_cnt);  // (straight behind part: one memset clears both)
+    const auto r_sums = ws.add<double>(n_sums);
+    const auto r_n = ws.add<long long>(ngf), r_nbad = ws.add<long long>(ngf);  // (n | n_bad come back in one copy)
+    const auto r_thr = ws.add<double>(h_thr.size());
+    const auto r_sg = ws.add<int>((size_t)n_lead), r_act = ws.add<int>((size_t)n_lead), r_slabs = ws.add<int>((size_t)nact);
+    ws.align_to(8);  // (the 16-bit records start on 8-byte boundaries)
+    const auto r_k16 = ws.add<unsigned short>((size_t)nt * Rmax);
+    ws.align_to(8);
+    const auto r_flag = ws.add<unsigned short>(Rmax);
+    EFA_TRY(c->nbr_ws.reserve(ws.bytes()));
+    unsigned long long* d_mask = r_mask(c->nbr_ws);
+    double *d_part = r_part(c->nbr_ws), *d_sums = r_sums(c->nbr_ws), *d_thr = r_thr(c->nbr_ws);
+    long long *d_cnt = r_cnt(c->nbr_ws), *d_n = r_n(c->nbr_ws), *d_nbad = r_nbad(c->nbr_ws);
+    int *d_sg = r_sg(c->nbr_ws), *d_act = r_act(c->nbr_ws), *d_slabs = r_slabs(c->nbr_ws);
+    unsigned short *d_k16 = r_k16(c->nbr_ws), *d_flag = r_flag(c->nbr_ws);
+    EFA_HIP(hipMemcpyAsync(d_thr, h_thr.data(), h_thr.size() * sizeof(double), hipMemcpyHostToDevice, s));
     EFA_HIP(hipMemcpyAsync(d_sg, h_sg.data(), (size_t)n_lead * sizeof(int), hipMemcpyHostToDevice, s));
     EFA_HIP(hipMemcpyAsync(d_act, h_act.data(), (size_t)n_lead * sizeof(int), hipMemcpyHostToDevice, s));
     if (nact > 0) EFA_HIP(hipMemcpyAsync(d_slabs, h_slabs.data(), (size_t)nact * sizeof(int), hipMemcpyHostToDevice, s));
@@ -655,7 +593,7 @@ int neighbourhood(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, lo
     ra.ncol = ncol;
     ra.tps = (ncol + 15) / 16;
     ra.M = M;
-    ra.al = (M % 2 == 0) && (reinterpret_cast<uintptr_t>(X_dev) % (2 * elem_size(elem)) == 0);
+    ra.al = pairs_aligned(X_dev, M, elem);
     ra.nt = nt;
     ra.nw = nw;
     ra.flag = d_flag;
@@ -708,10 +646,9 @@ int neighbourhood(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, lo
     wa.nmep = nmep_dev;
     wa.part = d_part;
     wa.cnt = d_cnt;
-    long blocks = c->neighbourhood_blocks;
-    if (blocks < 1 || blocks > kNbrBlocks) blocks = kNbrBlocks;
+    const long blocks = clamp_blocks(c->neighbourhood_blocks, kNbrBlocks);
 
-    EFA_HIP(hipEventRecord(c->nbr_iv.begin, s));
+    EFA_TRY(interval_begin(c->nbr_iv, s));
     if (fields && nact < n_lead) {
       long grid = (rows + kNbrThreads - 1) / kNbrThreads;
       if (grid > blocks) grid = blocks;
@@ -729,19 +666,16 @@ int neighbourhood(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, lo
       EFA_HIP(launch_windows(wa, blocks, s));
     }
     if (G > 0) {
-      hipLaunchKernelGGL(k_nbr_reduce, dim3((unsigned)G, (unsigned)nrt), dim3(kNbrThreads), 0, s, tiles_all, tps, nrt, d_slabs, d_sg,
-                         d_part, d_cnt, d_sums, d_n, d_nbad);
-      EFA_HIP(hipGetLastError());
+      EFA_HIP((launch_group_reduce<kNbrSums, 2>(G, nrt, s, tiles_all, tps, nrt, d_slabs, d_sg, d_part, d_cnt, d_sums, d_n,
+                                                d_nbad)));
     }
-    EFA_HIP(hipEventRecord(c->nbr_iv.end, s));
+    EFA_TRY(interval_end(c->nbr_iv, s));
     if (G > 0) {
       EFA_HIP(hipMemcpyAsync(h_sums.data(), d_sums, n_sums * sizeof(double), hipMemcpyDeviceToHost, s));
       EFA_HIP(hipMemcpyAsync(h_cnt.data(), d_n, 2 * ngf * sizeof(long long), hipMemcpyDeviceToHost, s));
     }
     EFA_HIP(hipStreamSynchronize(s));
-    float ms = 0.f;
-    EFA_HIP(hipEventElapsedTime(&ms, c->nbr_iv.begin, c->nbr_iv.end));
-    c->neighbourhood_us = (long)std::llround((double)ms * 1000.0);
+    EFA_TRY(interval_us(c->nbr_iv, &c->neighbourhood_us));
   }
   if (G > 0) {
     for (size_t i = 0; i < h_sums.size(); ++i) sums[i] = h_sums[i];

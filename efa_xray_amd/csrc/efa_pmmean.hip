@@ -30,7 +30,8 @@
 // in every segment and its pass is skipped.  The host reads that word once per batch; it is the only wait inside a call.
 // The only atomics are integer: LDS counters whose sum is all that is read, the OR above and the n_bad counts.
 #include "efa_device.h"
-#include "efa_driver.h"
+#include "efa_diag.h"
+#include "efa_quadrow.h"
 
 #include <cmath>
 #include <vector>
@@ -85,8 +86,6 @@ struct PmKey<u32> {
   static __device__ __forceinline__ double dec(u32 k) { return (double)__uint_as_float((k >> 31) ? k ^ 0x80000000u : ~k); }
 };
 
-__device__ __forceinline__ bool pm_finite(double v) { return __builtin_fabs(v) < __builtin_inf(); }
-
 struct PmKeyArgs {
   const void* X;
   const double* f;       // [rows]
@@ -130,13 +129,13 @@ __global__ __launch_bounds__(kPmThreads) void k_pm_keys(const PmKeyArgs a) {
     for (u32 i = tid; i < total; i += kPmThreads) {
       const u32 rl = i / M, m = i - rl * M;
       const E v = p[i];
-      if (!pm_finite((double)v)) bad_s[rl] = 1u;  // (every writer stores the same value)
+      if (!finite64((double)v)) bad_s[rl] = 1u;  // (every writer stores the same value)
       pool[pos_s[rl] * M + m] = PmKey<K>::enc(v);
     }
     __syncthreads();
     if (tid < nrow) {
       const double fv = a.f[(size_t)lead * a.ncol + col];
-      const bool excl = bad_s[tid] != 0u || !pm_finite(fv);
+      const bool excl = bad_s[tid] != 0u || !finite64(fv);
       a.rkey[pos] = excl ? ~0ull : PmKey<u64>::enc(fv);
       a.rpay[pos] = (u32)(sb * a.ncol + col);
       if (excl) {  // rare: the row's pool keys once more, behind the barrier that orders them after the stores above
@@ -390,15 +389,6 @@ hipError_t pm_sort(K* a, K* b, u32* pa, u32* pb, const PmDevTables& t, const PmS
   return hipSuccess;
 }
 
-template <typename T>
-T* pm_carve(char*& p, size_t n) {
-  T* r = reinterpret_cast<T*>(p);
-  p += (n * sizeof(T) + 255) / 256 * 256;
-  return r;
-}
-template <typename T>
-size_t pm_room(size_t n) { return (n * sizeof(T) + 255) / 256 * 256; }
-
 }  // namespace
 }  // namespace efa
 
@@ -482,35 +472,35 @@ int pm_mean(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, long ny,
     const size_t nblk = tp.blk.size() > tr.blk.size() ? tp.blk.size() : tr.blk.size();
     const size_t nunit = tp.unit.size() > tr.unit.size() ? tp.unit.size() : tr.unit.size();
     // pm_ws: pool a | pool b | rank keys a, b | rank payloads a, b | hist | usum | ubase | the two tables | n_bad | masks | slabs, flags
-    size_t need = 2 * pm_room<char>(Rmax * M * ksize) + 2 * pm_room<u64>(Rmax) + 2 * pm_room<u32>(Rmax) + pm_room<u32>(nblk * 256) +
-                  pm_room<u32>(nunit * 256) + pm_room<u64>(nunit * 256) + pm_room<PmBlk>(tp.blk.size()) + pm_room<PmUnit>(tp.unit.size()) +
-                  pm_room<PmSeg>(tp.seg.size()) + pm_room<PmBlk>(tr.blk.size()) + pm_room<PmUnit>(tr.unit.size()) +
-                  pm_room<PmSeg>(tr.seg.size()) + pm_room<u64>((size_t)n_lead) + pm_room<u64>(2) + pm_room<int>((size_t)n_lead) +
-                  pm_room<int>((size_t)nact);
-    EFA_TRY(c->pm_ws.reserve(need));
-    if (!c->pm_iv.begin.h) EFA_HIP(hipEventCreate(&c->pm_iv.begin.h));
-    if (!c->pm_iv.end.h) EFA_HIP(hipEventCreate(&c->pm_iv.end.h));
-    char* p = c->pm_ws.as<char>();
-    char* pool_a = pm_carve<char>(p, Rmax * M * ksize);
-    char* pool_b = pm_carve<char>(p, Rmax * M * ksize);
-    u64* rk_a = pm_carve<u64>(p, Rmax);
-    u64* rk_b = pm_carve<u64>(p, Rmax);
-    u32* rp_a = pm_carve<u32>(p, Rmax);
-    u32* rp_b = pm_carve<u32>(p, Rmax);
+    // (every region starts on a 256-byte boundary)
+    WsLayout ws(256);
+    const auto r_pool_a = ws.add<char>(Rmax * M * ksize), r_pool_b = ws.add<char>(Rmax * M * ksize);
+    const auto r_rk_a = ws.add<u64>(Rmax), r_rk_b = ws.add<u64>(Rmax);
+    const auto r_rp_a = ws.add<u32>(Rmax), r_rp_b = ws.add<u32>(Rmax);
+    const auto r_hist = ws.add<u32>(nblk * 256), r_usum = ws.add<u32>(nunit * 256);
+    const auto r_ubase = ws.add<u64>(nunit * 256);
+    const auto r_pblk = ws.add<PmBlk>(tp.blk.size());
+    const auto r_punit = ws.add<PmUnit>(tp.unit.size());
+    const auto r_pseg = ws.add<PmSeg>(tp.seg.size());
+    const auto r_rblk = ws.add<PmBlk>(tr.blk.size());
+    const auto r_runit = ws.add<PmUnit>(tr.unit.size());
+    const auto r_rseg = ws.add<PmSeg>(tr.seg.size());
+    const auto r_nbad = ws.add<u64>((size_t)n_lead), r_mask = ws.add<u64>(2);
+    const auto r_act = ws.add<int>((size_t)n_lead), r_slabs = ws.add<int>((size_t)nact);
+    EFA_TRY(c->pm_ws.reserve(ws.bytes()));
+    const DevBuf& b = c->pm_ws;
+    char *pool_a = r_pool_a(b), *pool_b = r_pool_b(b);
+    u64 *rk_a = r_rk_a(b), *rk_b = r_rk_b(b);
+    u32 *rp_a = r_rp_a(b), *rp_b = r_rp_b(b);
     PmScratch w;
-    w.hist = pm_carve<u32>(p, nblk * 256);
-    w.usum = pm_carve<u32>(p, nunit * 256);
-    w.ubase = pm_carve<u64>(p, nunit * 256);
-    PmBlk* d_pblk = pm_carve<PmBlk>(p, tp.blk.size());
-    PmUnit* d_punit = pm_carve<PmUnit>(p, tp.unit.size());
-    PmSeg* d_pseg = pm_carve<PmSeg>(p, tp.seg.size());
-    PmBlk* d_rblk = pm_carve<PmBlk>(p, tr.blk.size());
-    PmUnit* d_runit = pm_carve<PmUnit>(p, tr.unit.size());
-    PmSeg* d_rseg = pm_carve<PmSeg>(p, tr.seg.size());
-    u64* d_nbad = pm_carve<u64>(p, (size_t)n_lead);
-    u64* d_mask = pm_carve<u64>(p, 2);
-    int* d_act = pm_carve<int>(p, (size_t)n_lead);
-    int* d_slabs = pm_carve<int>(p, (size_t)nact);
+    w.hist = r_hist(b);
+    w.usum = r_usum(b);
+    w.ubase = r_ubase(b);
+    PmBlk *d_pblk = r_pblk(b), *d_rblk = r_rblk(b);
+    PmUnit *d_punit = r_punit(b), *d_runit = r_runit(b);
+    PmSeg *d_pseg = r_pseg(b), *d_rseg = r_rseg(b);
+    u64 *d_nbad = r_nbad(b), *d_mask = r_mask(b);
+    int *d_act = r_act(b), *d_slabs = r_slabs(b);
     if (nact > 0) {
       EFA_HIP(hipMemcpyAsync(d_pblk, tp.blk.data(), tp.blk.size() * sizeof(PmBlk), hipMemcpyHostToDevice, s));
       EFA_HIP(hipMemcpyAsync(d_punit, tp.unit.data(), tp.unit.size() * sizeof(PmUnit), hipMemcpyHostToDevice, s));
@@ -522,8 +512,7 @@ int pm_mean(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, long ny,
     }
     EFA_HIP(hipMemcpyAsync(d_act, h_act.data(), (size_t)n_lead * sizeof(int), hipMemcpyHostToDevice, s));
     EFA_HIP(hipMemsetAsync(d_nbad, 0, (size_t)n_lead * sizeof(u64), s));
-    long blocks = c->pm_blocks;
-    if (blocks < 1 || blocks > kPmBlocks) blocks = kPmBlocks;
+    const long blocks = clamp_blocks(c->pm_blocks, kPmBlocks);
 
     PmKeyArgs ka{};
     ka.X = X_dev;
@@ -540,7 +529,7 @@ int pm_mean(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, long ny,
     ka.rpay = rp_a;
     ka.nbad = d_nbad;
 
-    EFA_HIP(hipEventRecord(c->pm_iv.begin, s));
+    EFA_TRY(interval_begin(c->pm_iv, s));
     if (nact < n_lead) {
       hipLaunchKernelGGL(k_pm_unread, dim3(pm_grid((rows + kPmThreads - 1) / kPmThreads, blocks)), dim3(kPmThreads), 0, s, rows, ncol,
                          d_act, pm_dev);
@@ -588,12 +577,10 @@ int pm_mean(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, long ny,
                            wr ? rk_b : rk_a, wr ? rp_b : rp_a, d_slabs + s0, R, ncol, M, pick, pm_dev);
       EFA_HIP(hipGetLastError());
     }
-    EFA_HIP(hipEventRecord(c->pm_iv.end, s));
+    EFA_TRY(interval_end(c->pm_iv, s));
     EFA_HIP(hipMemcpyAsync(h_nbad.data(), d_nbad, (size_t)n_lead * sizeof(u64), hipMemcpyDeviceToHost, s));
     EFA_HIP(hipStreamSynchronize(s));
-    float ms = 0.f;
-    EFA_HIP(hipEventElapsedTime(&ms, c->pm_iv.begin, c->pm_iv.end));
-    c->pm_us = (long)std::llround((double)ms * 1000.0);
+    EFA_TRY(interval_us(c->pm_iv, &c->pm_us));
   }
   for (long l = 0; l < n_lead; ++l) n_bad[l] = (long long)h_nbad[l];
   return EFA_OK;

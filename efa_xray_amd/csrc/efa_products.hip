@@ -4,10 +4,8 @@
 //   given a verifying value y_i, per group of slabs and threshold the reliability table table[k][o] of o = (y_i > t), the count of
 //   bad rows and the weighted sums of 1, (k/M - o)^2, k/M and o.  Every number in float64.
 //
-// k_products reads every row once in the row layout of k_verify (efa_verify.hip): a wave owns a tile of 16 consecutive rows of one
-// slab; lane l = (g = l>>4, n = l&15) loads members {8u+2g, 8u+2g+1} of row n with one 16-byte load (8-byte for float32 rows),
-// so slot c = 2u + e of lane g is member 8u + 2g + e and the whole row sits in registers, 2 NU doubles per lane.  Slots beyond M
-// hold +inf.  Sum, sum of squared deviations and the counts are lane-local plus two __shfl_xor steps; the count is taken as
+// k_products reads every row once in the four-lane row layout (efa_quadrow.h): the whole row sits in registers, 2 NU doubles per
+// lane.  Slots beyond M hold +inf.  Sum, sum of squared deviations and the counts are lane-local plus two __shfl_xor steps; the count is taken as
 // M - #{slot <= t}, which the +inf slots never enter and which equals #{x > t} on a row without NaN (a row with one is bad).  The
 // counts of a lane travel as 16-bit fields of two 64-bit words, so the 8 thresholds cost 4 shuffles, and lane g of a row then does
 // the work of thresholds g and g + 4 (the division, the stores, the table, the sums).
@@ -18,11 +16,12 @@
 // instantiates the network.
 //
 // Sums: a chunk is kProdChunkTiles tiles of one slab, whatever the grid; wave w takes its tiles w, w+4, ... in order, every lane
-// adds its rows up, and the 64 lane sums of the chunk are added in index order into the chunk's partial.  k_products_reduce adds
+// adds its rows up, and the 64 lane sums of the chunk are added in index order into the chunk's partial.  k_group_reduce (efa_quadreduce.h) adds
 // the partials of each group in a fixed order.  The table is integer adds in LDS and integer atomics in memory.  No
 // floating-point atomics: the same inputs give the same bits whatever the grid.
 #include "efa_device.h"
-#include "efa_driver.h"
+#include "efa_diag.h"
+#include "efa_quadreduce.h"
 #include "efa_sortnet.h"
 
 #include <cmath>
@@ -31,7 +30,6 @@
 namespace efa {
 namespace {
 
-constexpr int kProdThreads = 256;     // 4 waves, one 16-row tile per wave and trip
 constexpr int kProdBlocks = 2048;     // default grid cap of k_products (option "products_blocks" lowers it)
 constexpr int kProdChunkTiles = 64;   // tiles per chunk: 1024 rows give one partial
 constexpr int kProdMax = 8;           // quantile levels and thresholds per call
@@ -58,15 +56,6 @@ struct ProdArgs {
   unsigned long long* table;  // [G][nt][M + 1][2]
 };
 
-template <typename E>
-struct ProdPair;
-template <>
-struct ProdPair<double> { typedef double2 type; };
-template <>
-struct ProdPair<float> { typedef float2 type; };
-
-__device__ __forceinline__ bool prod_finite(double v) { return __builtin_fabs(v) < __builtin_inf(); }
-
 // slot `slot` (wave-uniform) of d: a chain of selects over compile-time indices, never an indexed register array
 template <int LP>
 __device__ __forceinline__ double prod_pick(const double (&d)[LP], int slot) {
@@ -81,12 +70,12 @@ __device__ __forceinline__ double prod_pick(const double (&d)[LP], int slot) {
 
 // NU: chunks of 8 members the lanes hold, (M + 7) / 8 rounded up to a power of two, as in k_verify
 template <int NU, typename E, bool SORT>
-__global__ __launch_bounds__(kProdThreads) void k_products(const ProdArgs a) {
+__global__ __launch_bounds__(kQuadThreads) void k_products(const ProdArgs a) {
   constexpr int LP = 2 * NU;
   static_assert((NU & (NU - 1)) == 0, "the bitonic network needs a power of two");
   __shared__ unsigned int tab_s[kProdMax * (kMaxMembers + 1) * 2];
-  __shared__ double red_s[kProdThreads * 2 * kProdSums];
-  __shared__ int cnt_s[kProdThreads * 2];
+  __shared__ double red_s[kQuadThreads * 2 * kProdSums];
+  __shared__ int cnt_s[kQuadThreads * 2];
   const int M = a.M;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wv = tid >> 6;
@@ -99,7 +88,7 @@ __global__ __launch_bounds__(kProdThreads) void k_products(const ProdArgs a) {
   const int ntab = a.nt * (M + 1) * 2;
 
   if (ver) {
-    for (int i = tid; i < ntab; i += kProdThreads) tab_s[i] = 0u;
+    for (int i = tid; i < ntab; i += kQuadThreads) tab_s[i] = 0u;
     __syncthreads();
   }
   int cur_g = -1;  // the group the LDS table belongs to
@@ -112,7 +101,7 @@ __global__ __launch_bounds__(kProdThreads) void k_products(const ProdArgs a) {
     if (ver && (sg != cur_g || since >= kProdFlushChunks)) {  // (uniform)
       __syncthreads();
       if (cur_g >= 0)
-        for (int i = tid; i < ntab; i += kProdThreads) {
+        for (int i = tid; i < ntab; i += kQuadThreads) {
           const unsigned int v = tab_s[i];
           if (v) atomicAdd(&a.table[(size_t)cur_g * ntab + i], (unsigned long long)v);
           tab_s[i] = 0u;
@@ -131,15 +120,15 @@ __global__ __launch_bounds__(kProdThreads) void k_products(const ProdArgs a) {
     int n_bad[2] = {0, 0};
 
 #pragma unroll 1
-    for (long tl = t0 + wv; tl < t1; tl += kProdThreads / 64) {
+    for (long tl = t0 + wv; tl < t1; tl += kQuadThreads / 64) {
       const long col = tl * 16 + n;
       const bool live = col < a.ncol;
       const long colc = live ? col : a.ncol - 1;
       const long r = lead * a.ncol + colc;
-      // the lane's quarter of the row again, opaque to the optimiser: what depends only on it and on M (the slot predicates) is
-      // otherwise hoisted out of this loop and held in registers across it
-      int gq = lane >> 4;
-      asm volatile("" : "+v"(gq));
+      const int gq = quad_lane_quarter(lane);
+      // The loader, the slot predicate and the row reductions are written out here, not taken from efa_quadrow.h, and so are the
+      // table flush and the chunk partial of efa_quadreduce.h below: with the former the quantile variants ran 6 % slower, with the
+      // latter the float32 variants up to 0.9 %.  As it stands the kernel is its predecessor's code.
       double d[LP];
       {  // clamped addresses, no branches: the loads of a tile are issued together
         const E* p = reinterpret_cast<const E*>(a.X) + (size_t)r * M;
@@ -148,7 +137,7 @@ __global__ __launch_bounds__(kProdThreads) void k_products(const ProdArgs a) {
           for (int u = 0; u < NU; ++u) {
             int m0 = 8 * u + 2 * gq;
             m0 = (m0 < M) ? m0 : M - 2;
-            const typename ProdPair<E>::type v = *reinterpret_cast<const typename ProdPair<E>::type*>(p + m0);
+            const typename ElemPair<E>::type v = *reinterpret_cast<const typename ElemPair<E>::type*>(p + m0);
             d[2 * u] = v.x;
             d[2 * u + 1] = v.y;
           }
@@ -172,7 +161,7 @@ __global__ __launch_bounds__(kProdThreads) void k_products(const ProdArgs a) {
       for (int c = 0; c < LP; ++c) {
         const bool ok = 8 * (c >> 1) + 2 * gq + (c & 1) < M;  // the slot holds a real member
         const double xv = d[c];
-        badl = badl || (ok && !prod_finite(xv));
+        badl = badl || (ok && !finite64(xv));
         s4[c & 3] += ok ? xv : 0.0;
         d[c] = ok ? xv : inf;
       }
@@ -186,9 +175,8 @@ __global__ __launch_bounds__(kProdThreads) void k_products(const ProdArgs a) {
       double sum = (s4[0] + s4[1]) + (s4[2] + s4[3]);
       sum += __shfl_xor(sum, 16, 64);
       sum += __shfl_xor(sum, 32, 64);
-      const unsigned long long quad = 0x0001000100010001ull;
-      const bool varies = ((__ballot(diff) >> n) & quad) != 0ull;
-      const bool bad = ((__ballot(badl) >> n) & quad) != 0ull;
+      const bool varies = quad_row_any(diff, n);
+      const bool bad = quad_row_any(badl, n);
       // a row whose members are all equal has that value as its mean and deviations of exactly 0 (its sum / M need not give it back)
       const double mean = varies ? sum / dM : x0;
       double q4[4] = {0.0, 0.0, 0.0, 0.0};
@@ -229,10 +217,10 @@ __global__ __launch_bounds__(kProdThreads) void k_products(const ProdArgs a) {
         const double t = s ? tj1 : tj0;
         const int k = M - (int)(((s ? pk1 : pk0) >> (16 * gq)) & 0xFFFFull);
         const double p = (double)k / dM;
-        const bool tfin = prod_finite(t);
+        const bool tfin = finite64(t);
         if (live && j < a.nt) {
           if (a.prob) a.prob[(size_t)j * a.rows + r] = (tfin && !bad) ? p : nan;
-          if (ver && sg >= 0 && tfin && prod_finite(y) && w > 0.0) {
+          if (ver && sg >= 0 && tfin && finite64(y) && w > 0.0) {
             if (bad) {
               ++n_bad[s];
             } else {
@@ -249,14 +237,7 @@ __global__ __launch_bounds__(kProdThreads) void k_products(const ProdArgs a) {
       }
 
       if constexpr (SORT) {
-        __builtin_amdgcn_sched_barrier(0);
-        // the sort: afterwards sorted position g LP + k is slot k of lane g
-        ver_sort_local<LP>(d);
-        ver_split_rev<LP>(d, 16, (gq & 1) != 0);
-        ver_merge_local<LP>(d);
-        ver_split_rev<LP>(d, 48, gq >= 2);
-        ver_split_same<LP>(d, 16, (gq & 1) != 0);
-        ver_merge_local<LP>(d);
+        quad_sort<LP>(d, gq);  // afterwards sorted position g LP + k is slot k of lane g
 #pragma unroll 1
         for (int i = 0; i < a.nq; ++i) {
           const int lo = a.qlo[i], hi = a.qhi[i];  // (uniform)
@@ -278,6 +259,8 @@ __global__ __launch_bounds__(kProdThreads) void k_products(const ProdArgs a) {
         cnt_s[tid * 2 + s] = n_bad[s];
       }
       __syncthreads();
+      // threshold j was finished by lane quarter j & 3 as its s = j >> 2: lane sum i is thread (i >> 4) * 64 + (j & 3) * 16 + (i & 15)
+      // (the text of quad_chunk_partial)
       if (tid < kProdMax * kProdSums) {
         const int j = tid / kProdSums, k = tid % kProdSums;
         double sacc = 0.0;
@@ -296,54 +279,17 @@ __global__ __launch_bounds__(kProdThreads) void k_products(const ProdArgs a) {
   if (ver) {
     __syncthreads();
     if (cur_g >= 0)
-      for (int i = tid; i < ntab; i += kProdThreads) {
+      for (int i = tid; i < ntab; i += kQuadThreads) {
         const unsigned int v = tab_s[i];
         if (v) atomicAdd(&a.table[(size_t)cur_g * ntab + i], (unsigned long long)v);
       }
   }
 }
 
-// workgroup (g, j): the partials of threshold j of the chunks of group g, thread by thread in chunk order, then a tree over the threads
-__global__ __launch_bounds__(kProdThreads) void k_products_reduce(long nchunks, long cps, int nt, const int* __restrict__ sgroup,
-                                                                  const double* __restrict__ part,
-                                                                  const long long* __restrict__ cnt, double* __restrict__ sums,
-                                                                  long long* __restrict__ nbad_out) {
-  __shared__ double s_s[kProdThreads];
-  __shared__ long long c_s[kProdThreads];
-  const int tid = threadIdx.x;
-  const int grp = (int)blockIdx.x, j = (int)blockIdx.y;
-  for (int k = 0; k < kProdSums + 1; ++k) {
-    double s = 0.0;
-    long long c = 0;
-    for (long i = tid; i < nchunks; i += kProdThreads) {
-      if (sgroup[i / cps] != grp) continue;
-      if (k < kProdSums) s += part[((size_t)i * kProdMax + j) * kProdSums + k];
-      else c += cnt[(size_t)i * kProdMax + j];
-    }
-    s_s[tid] = s;
-    c_s[tid] = c;
-    __syncthreads();
-    for (int off = kProdThreads / 2; off >= 1; off >>= 1) {
-      if (tid < off) {
-        s_s[tid] += s_s[tid + off];
-        c_s[tid] += c_s[tid + off];
-      }
-      __syncthreads();
-    }
-    if (tid == 0) {
-      if (k < kProdSums) sums[((size_t)grp * nt + j) * kProdSums + k] = s_s[0];
-      else nbad_out[(size_t)grp * nt + j] = c_s[0];
-    }
-    __syncthreads();
-  }
-}
-
 template <bool SORT>
-hipError_t launch_products_s(const ProdArgs& a, Elem elem, long grid, int nu_p, hipStream_t s) {
-  return dispatch_width(nu_p, std::integer_sequence<int, 1, 2, 4, 8, 16, 32>{}, [&](auto nu_c) {
-    constexpr int nu = decltype(nu_c)::value;
-    if (elem == Elem::f32) hipLaunchKernelGGL((k_products<nu, float, SORT>), dim3((unsigned)grid), dim3(kProdThreads), 0, s, a);
-    else hipLaunchKernelGGL((k_products<nu, double, SORT>), dim3((unsigned)grid), dim3(kProdThreads), 0, s, a);
+hipError_t launch_products_s(const ProdArgs& a, Elem elem, long grid, hipStream_t s) {
+  return efa_host::launch_quad(a.M, elem, [&](auto nu_c, auto e) {
+    hipLaunchKernelGGL((k_products<decltype(nu_c)::value, decltype(e), SORT>), dim3((unsigned)grid), dim3(kQuadThreads), 0, s, a);
     return hipGetLastError();
   });
 }
@@ -353,9 +299,7 @@ hipError_t launch_products(const ProdArgs& a, Elem elem, int blocks, hipStream_t
   if (a.nchunks <= 0) return hipSuccess;
   long grid = a.nchunks < blocks ? a.nchunks : blocks;
   if (grid < 1) grid = 1;
-  int nu_p = 1;
-  while (nu_p * 8 < a.M) nu_p *= 2;
-  return a.nq > 0 ? launch_products_s<true>(a, elem, grid, nu_p, s) : launch_products_s<false>(a, elem, grid, nu_p, s);
+  return a.nq > 0 ? launch_products_s<true>(a, elem, grid, s) : launch_products_s<false>(a, elem, grid, s);
 }
 
 }  // namespace
@@ -392,10 +336,7 @@ int products(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, long nc
     if (!slab_group) return fail(EFA_ERR_INVALID, "%s: null slab_group", me);
     if (!table != !n_bad || !table != !sums)
       return fail(EFA_ERR_INVALID, "%s: table, n_bad and sums go together (all null: no verification)", me);
-    for (long s = 0; s < n_lead; ++s) {
-      if (slab_group[s] < -1) return fail(EFA_ERR_INVALID, "%s: slab_group[%ld] = %d must be >= -1", me, s, slab_group[s]);
-      if (slab_group[s] + 1 > G) G = slab_group[s] + 1;
-    }
+    EFA_TRY(check_slab_groups(me, slab_group, n_lead, &G));
   }
 
   if (!table) {  // nothing to score into
@@ -417,26 +358,22 @@ int products(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, long nc
     const int ntd = nt > 0 ? nt : 1;
     // prod_ws: part [nchunks][8][4] | sums [Gd][ntd][4] | thr [n_lead][8] | cnt [nchunks][8] | n_bad [Gd][ntd] | table [Gd][ntab] |
     //          slab groups [n_lead]
-    const size_t n_part = (size_t)nchunks * kProdMax * kProdSums, n_sums = (size_t)Gd * ntd * kProdSums,
-                 n_thr = (size_t)n_lead * kProdMax, n_cnt = (size_t)nchunks * kProdMax, n_nbad = (size_t)Gd * ntd,
-                 n_tab = (size_t)Gd * (ntab ? ntab : 1);
-    EFA_TRY(c->prod_ws.reserve((n_part + n_sums + n_thr + n_cnt + n_nbad + n_tab) * 8 + (size_t)n_lead * sizeof(int)));
-    if (!c->prod_iv.begin.h) EFA_HIP(hipEventCreate(&c->prod_iv.begin.h));
-    if (!c->prod_iv.end.h) EFA_HIP(hipEventCreate(&c->prod_iv.end.h));
-    double* d_part = c->prod_ws.as<double>();
-    double* d_sums = d_part + n_part;
-    double* d_thr = d_sums + n_sums;
-    long long* d_cnt = reinterpret_cast<long long*>(d_thr + n_thr);
-    long long* d_nbad = d_cnt + n_cnt;
-    long long* d_tab = d_nbad + n_nbad;
-    int* d_sg = reinterpret_cast<int*>(d_tab + n_tab);
-    std::vector<double> h_thr(n_thr, std::nan(""));
-    for (long l = 0; l < n_lead; ++l)
-      for (int j = 0; j < nt; ++j) h_thr[(size_t)l * kProdMax + j] = thr[(size_t)l * nt + j];
+    const size_t n_tab = (size_t)Gd * (ntab ? ntab : 1);
+    WsLayout ws;
+    const auto r_part = ws.add<double>((size_t)nchunks * kProdMax * kProdSums), r_sums = ws.add<double>((size_t)Gd * ntd * kProdSums),
+               r_thr = ws.add<double>((size_t)n_lead * kProdMax);
+    const auto r_cnt = ws.add<long long>((size_t)nchunks * kProdMax), r_nbad = ws.add<long long>((size_t)Gd * ntd),
+               r_tab = ws.add<long long>(n_tab);
+    const auto r_sg = ws.add<int>((size_t)n_lead);
+    EFA_TRY(c->prod_ws.reserve(ws.bytes()));
+    double *d_part = r_part(c->prod_ws), *d_sums = r_sums(c->prod_ws), *d_thr = r_thr(c->prod_ws);
+    long long *d_cnt = r_cnt(c->prod_ws), *d_nbad = r_nbad(c->prod_ws), *d_tab = r_tab(c->prod_ws);
+    int* d_sg = r_sg(c->prod_ws);
+    const std::vector<double> h_thr = pad_thresholds(thr, n_lead, nt, kProdMax);
     std::vector<int> h_sg((size_t)n_lead, -1);
     if (verif_dev)
       for (long l = 0; l < n_lead; ++l) h_sg[l] = slab_group[l];
-    EFA_HIP(hipMemcpyAsync(d_thr, h_thr.data(), n_thr * sizeof(double), hipMemcpyHostToDevice, s));
+    EFA_HIP(hipMemcpyAsync(d_thr, h_thr.data(), h_thr.size() * sizeof(double), hipMemcpyHostToDevice, s));
     EFA_HIP(hipMemcpyAsync(d_sg, h_sg.data(), (size_t)n_lead * sizeof(int), hipMemcpyHostToDevice, s));
     EFA_HIP(hipMemsetAsync(d_tab, 0, n_tab * sizeof(long long), s));
     ProdArgs a{};
@@ -451,7 +388,7 @@ int products(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, long nc
     a.nchunks = nchunks;
     a.cps = cps;
     a.M = M;
-    a.al = (M % 2 == 0) && (reinterpret_cast<uintptr_t>(X_dev) % (2 * elem_size(elem)) == 0);
+    a.al = pairs_aligned(X_dev, M, elem);
     a.nq = nq;
     a.nt = nt;
     for (int i = 0; i < nq; ++i) {  // numpy's linear rule: h = q (M - 1) in float64
@@ -469,25 +406,20 @@ int products(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, long nc
     a.part = d_part;
     a.cnt = d_cnt;
     a.table = reinterpret_cast<unsigned long long*>(d_tab);
-    long blocks = c->products_blocks;
-    if (blocks < 1 || blocks > kProdBlocks) blocks = kProdBlocks;
-    EFA_HIP(hipEventRecord(c->prod_iv.begin, s));
-    EFA_HIP(launch_products(a, elem, (int)blocks, s));
+    EFA_TRY(interval_begin(c->prod_iv, s));
+    EFA_HIP(launch_products(a, elem, (int)clamp_blocks(c->products_blocks, kProdBlocks), s));
     if (G > 0) {
-      hipLaunchKernelGGL(k_products_reduce, dim3((unsigned)G, (unsigned)nt), dim3(kProdThreads), 0, s, nchunks, cps, nt, d_sg, d_part,
-                         d_cnt, d_sums, d_nbad);
-      EFA_HIP(hipGetLastError());
+      EFA_HIP((launch_group_reduce<kProdSums, 1>(G, nt, s, nchunks, cps, kProdMax, nullptr, d_sg, d_part, d_cnt, d_sums, d_nbad,
+                                                 nullptr)));
     }
-    EFA_HIP(hipEventRecord(c->prod_iv.end, s));
+    EFA_TRY(interval_end(c->prod_iv, s));
     if (G > 0) {
       EFA_HIP(hipMemcpyAsync(h_int.data(), d_tab, nh * sizeof(long long), hipMemcpyDeviceToHost, s));
       EFA_HIP(hipMemcpyAsync(h_int.data() + nh, d_nbad, ngt * sizeof(long long), hipMemcpyDeviceToHost, s));
       EFA_HIP(hipMemcpyAsync(h_sums.data(), d_sums, h_sums.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     }
     EFA_HIP(hipStreamSynchronize(s));
-    float ms = 0.f;
-    EFA_HIP(hipEventElapsedTime(&ms, c->prod_iv.begin, c->prod_iv.end));
-    c->products_us = (long)std::llround((double)ms * 1000.0);
+    EFA_TRY(interval_us(c->prod_iv, &c->products_us));
   }
   if (G > 0) {
     for (size_t i = 0; i < nh; ++i) table[i] = h_int[i];

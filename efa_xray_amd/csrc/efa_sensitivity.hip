@@ -6,9 +6,9 @@
 //   squares, and keeps nothing of the size of the state between passes.
 //
 // k_sens_pass is a (rows x M) . (M x (K + t)) float64 contraction on the matrix cores, in the form of k_transform (efa_transform.hip):
-//   - a wave owns a tile of 16 consecutive rows; lane l = (g = l>>4, n = l&15) loads members {8u+2g, 8u+2g+1} of row n with one
-//     16-byte load (8-byte for float32 rows, widened exactly as they arrive): HBM -> VGPR -> MFMA, the whole row in registers up
-//     to 256 members (2 NU doubles per lane), so the mean is removed from the registers and no row is read twice;
+//   - the rows are read in the four-lane row layout (efa_quadrow.h, with its zero padding of the last chunk): HBM -> VGPR -> MFMA,
+//     the whole row in registers up to 256 members (2 NU doubles per lane), so the mean is removed from the registers and no row
+//     is read twice;
 //   - the vectors [J'_1..J'_K, u_0..u_{t-1}]/(M-1) live in LDS, once per workgroup, in MFMA-B order: one or two tiles of 16;
 //   - v_mfma_f64_16x16x4_f64 leaves D[row (lane>>4) + 4 v][vector lane&15] in acc[v]; the wave turns that through LDS so that lane
 //     (n, g) holds row n again and forms the conditioned var, the cov of metrics g, g+4, ... and the score, whose stores
@@ -16,7 +16,8 @@
 //   - the best (score, row) per workgroup is found by comparison only (larger score, then lower row: a total order, so the
 //     result does not depend on how the comparisons are bracketed); k_sens_best reduces the workgroups' bests.  No atomics.
 #include "efa_device.h"
-#include "efa_driver.h"
+#include "efa_diag.h"
+#include "efa_quadrow.h"
 
 #include <cmath>
 #include <vector>
@@ -45,13 +46,6 @@ struct SensArgs {
   double* best_score;   // per workgroup, or null: no pick wanted of this pass
   long* best_row;
 };
-
-template <typename E>
-struct SensPair;
-template <>
-struct SensPair<double> { typedef double2 type; };
-template <>
-struct SensPair<float> { typedef float2 type; };
 
 // (a, ra) is a better pick than (b, rb): the larger score, the lower row among equals; a row of -1 is no pick (its score is 0)
 __device__ __forceinline__ bool sens_better(double a, long ra, double b, long rb) {
@@ -111,7 +105,7 @@ __global__ __launch_bounds__(kSensThreads) void k_sens_pass(const SensArgs a) {
         int m0 = 8 * u + 2 * g;
         if (AL) {
           if (u == NU - 1) m0 = (m0 < M) ? m0 : M - 2;
-          const typename SensPair<E>::type v = *reinterpret_cast<const typename SensPair<E>::type*>(p + m0);
+          const typename ElemPair<E>::type v = *reinterpret_cast<const typename ElemPair<E>::type*>(p + m0);
           x[2 * u] = v.x;
           x[2 * u + 1] = v.y;
         } else {
@@ -132,12 +126,8 @@ __global__ __launch_bounds__(kSensThreads) void k_sens_pass(const SensArgs a) {
       const bool ok = c < 2 * NU - 2 || ((c & 1) ? last_ok1 : last_ok);
       diff = diff || (ok && x[c] != x0);
     }
-    double sum = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-    const unsigned long long db = __ballot(diff);
-    const bool varies = ((db >> n) & 0x0001000100010001ull) != 0ull;
-    const double mean = varies ? sum / (double)M : x0;
+    const double sum = quad_row_sum((s4[0] + s4[1]) + (s4[2] + s4[3]));
+    const double mean = quad_row_any(diff, n) ? sum / (double)M : x0;
     double q4[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int c = 0; c < 2 * NU; ++c) {
@@ -145,9 +135,7 @@ __global__ __launch_bounds__(kSensThreads) void k_sens_pass(const SensArgs a) {
       x[c] = ok ? x[c] - mean : 0.0;
       q4[c & 3] = __builtin_fma(x[c], x[c], q4[c & 3]);
     }
-    double ss = (q4[0] + q4[1]) + (q4[2] + q4[3]);
-    ss += __shfl_xor(ss, 16, 64);
-    ss += __shfl_xor(ss, 32, 64);
+    const double ss = quad_row_sum((q4[0] + q4[1]) + (q4[2] + q4[3]));
 
     sens_v4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -195,8 +183,7 @@ __global__ __launch_bounds__(kSensThreads) void k_sens_pass(const SensArgs a) {
         if (a.dvar) a.dvar[o] = -cc / den;
       }
     }
-    num += __shfl_xor(num, 16, 64);
-    num += __shfl_xor(num, 32, 64);
+    num = quad_row_sum(num);
     if (g == 0 && live) {
       const bool cand = !a.cand || a.cand[r] != 0;
       const double sc = cand ? num / den : 0.0;
@@ -284,8 +271,7 @@ hipError_t sens_launch(const SensArgs& a, hipStream_t s) {
 hipError_t launch_sens_pass(const SensArgs& a, Elem elem, hipStream_t s) {
   if (a.M < 2 || a.M > kMaxMembers || a.K < 1 || a.t < 0 || a.K + a.t > kSensVec) return hipErrorInvalidValue;
   if (a.rows <= 0) return hipSuccess;
-  const size_t esz = elem_size(elem);
-  const bool al = (a.M % 2 == 0) && (reinterpret_cast<uintptr_t>(a.X) % (2 * esz) == 0);
+  const bool al = efa_host::pairs_aligned(a.X, a.M, elem);
   hipError_t e = dispatch_width((a.M + 7) / 8, WidthRange<1, kMaxMembers / 8>{}, [&](auto nu_c) {
     constexpr int nu = decltype(nu_c)::value;
     if (elem == Elem::f32) return al ? sens_launch<nu, true, float>(a, s) : sens_launch<nu, false, float>(a, s);
@@ -366,8 +352,6 @@ int sensitivity(efa_ctx* c, Elem elem, long rows, int M, int K, const void* X_de
     const size_t pack_bytes = pack.size() * sizeof(double);
     EFA_TRY(c->sens_pack.reserve(pack_bytes + (size_t)n_lead * sizeof(double)));
     EFA_TRY(c->sens_best.reserve((size_t)(nblk + 1) * (sizeof(double) + sizeof(long))));
-    if (!c->sens_iv.begin.h) EFA_HIP(hipEventCreate(&c->sens_iv.begin.h));
-    if (!c->sens_iv.end.h) EFA_HIP(hipEventCreate(&c->sens_iv.end.h));
     double* d_pack = c->sens_pack.as<double>();
     double* d_R = d_pack + pack.size();
     double* d_bs = c->sens_best.as<double>();
@@ -386,9 +370,9 @@ int sensitivity(efa_ctx* c, Elem elem, long rows, int M, int K, const void* X_de
     double ms_sum = 0.0;
     auto one_pass = [&]() -> int {  // uploads the pack, runs the pass between the two events, waits and adds its time
       EFA_HIP(hipMemcpyAsync(d_pack, pack.data(), pack_bytes, hipMemcpyHostToDevice, s));
-      EFA_HIP(hipEventRecord(c->sens_iv.begin, s));
+      EFA_TRY(interval_begin(c->sens_iv, s));
       EFA_HIP(launch_sens_pass(a, elem, s));
-      EFA_HIP(hipEventRecord(c->sens_iv.end, s));
+      EFA_TRY(interval_end(c->sens_iv, s));
       return EFA_OK;
     };
     auto pass_time = [&]() -> int {

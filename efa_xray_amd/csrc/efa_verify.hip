@@ -4,10 +4,8 @@
 //   mean, the ensemble variance and the CRPS -- every float from the once-rounded d_m = x_im - y_i, in float64 -- and per group of
 //   slabs the rank histogram, the counts and the weighted sums of the three.
 //
-// k_verify reads every row once, in the row layout of k_sens_pass (efa_sensitivity.hip): a wave owns a tile of 16 consecutive rows
-// of one slab; lane l = (g = l>>4, n = l&15) loads members {8u+2g, 8u+2g+1} of row n with one 16-byte load (8-byte for float32
-// rows, widened as they arrive), so slot c = 2u + e of lane g is member 8u + 2g + e and the whole row sits in registers, 2 NU
-// doubles per lane.  below / equal / sum d / sum |d| / sum (d - err)^2 are lane-local plus two __shfl_xor steps.
+// k_verify reads every row once, in the four-lane row layout (efa_quadrow.h): the whole row sits in registers, 2 NU doubles per
+// lane.  below / equal / sum d / sum |d| / sum (d - err)^2 are lane-local plus two __shfl_xor steps.
 //
 // The CRPS needs the sorted d.  NU is a power of two, so a lane's LP = 2 NU slots are a power of two as well; slots beyond M hold
 // +inf.  Every lane sorts its slots with a bitonic network whose comparators all point upwards, and the row's four lanes are
@@ -17,11 +15,12 @@
 // compile-time constant.
 //
 // Sums: a chunk is kVerChunkTiles tiles of one slab, whatever the grid; wave w takes its tiles w, w+4, ... in order, lane n adds
-// its rows up, and the 64 lane sums of the chunk are added in index order into the chunk's partial.  k_verify_reduce adds the
-// partials of each group in a fixed order.  So the float sums depend on neither the grid nor the schedule; the histogram is
+// its rows up, and the 64 lane sums of the chunk are added in index order into the chunk's partial.  k_group_reduce (efa_quadreduce.h) adds
+// the partials of each group in a fixed order.  So the float sums depend on neither the grid nor the schedule; the histogram is
 // integer adds in LDS and integer atomics in memory, whose result no order can change.  No floating-point atomics.
 #include "efa_device.h"
-#include "efa_driver.h"
+#include "efa_diag.h"
+#include "efa_quadreduce.h"
 #include "efa_sortnet.h"
 
 #include <cmath>
@@ -30,7 +29,6 @@
 namespace efa {
 namespace {
 
-constexpr int kVerThreads = 256;     // 4 waves, one 16-row tile per wave and trip
 constexpr int kVerBlocks = 2048;     // default grid cap of k_verify (option "verify_blocks" lowers it)
 constexpr int kVerChunkTiles = 64;   // tiles per chunk: 1024 rows give one partial
 constexpr int kVerSums = 5;          // sum w, w crps, w err, w err^2, w var
@@ -52,15 +50,6 @@ struct VerArgs {
   unsigned long long* hist;    // [G][M + 1]
 };
 
-template <typename E>
-struct VerPair;
-template <>
-struct VerPair<double> { typedef double2 type; };
-template <>
-struct VerPair<float> { typedef float2 type; };
-
-__device__ __forceinline__ bool ver_finite(double v) { return __builtin_fabs(v) < __builtin_inf(); }
-
 // the tie-break: splitmix64 of the global row, scaled to [0, equal]
 __device__ __forceinline__ int ver_pick(unsigned long long seed, unsigned long long R, int equal) {
   unsigned long long z = seed + (R + 1ull) * 0x9E3779B97F4A7C15ull;
@@ -73,7 +62,7 @@ __device__ __forceinline__ int ver_pick(unsigned long long seed, unsigned long l
 // NU: chunks of 8 members the lanes hold, (M + 7) / 8 rounded up to a power of two: the sort network is that of LP = 2 NU slots
 // whatever M is, so the six sizes are the only instantiations; which slots hold members is decided from M as the kernel runs
 template <int NU, typename E>
-__global__ __launch_bounds__(kVerThreads) void k_verify(const VerArgs a) {
+__global__ __launch_bounds__(kQuadThreads) void k_verify(const VerArgs a) {
   constexpr int LP = 2 * NU;
   static_assert((NU & (NU - 1)) == 0, "the bitonic network needs a power of two");
   __shared__ unsigned int hist_s[kMaxMembers + 1];
@@ -90,7 +79,7 @@ __global__ __launch_bounds__(kVerThreads) void k_verify(const VerArgs a) {
   const long tps = (a.ncol + 15) / 16;
   const bool fields = a.below || a.equal || a.rank || a.crps || a.err || a.var;
 
-  for (int i = tid; i <= M; i += kVerThreads) hist_s[i] = 0u;
+  for (int i = tid; i <= M; i += kQuadThreads) hist_s[i] = 0u;
   __syncthreads();
   int cur_g = -1;  // the group the LDS histogram belongs to
   long since = 0;
@@ -101,12 +90,7 @@ __global__ __launch_bounds__(kVerThreads) void k_verify(const VerArgs a) {
     const int sg = a.sgroup[lead];
     if (sg != cur_g || since >= kVerFlushChunks) {  // (uniform)
       __syncthreads();
-      if (cur_g >= 0)
-        for (int i = tid; i <= M; i += kVerThreads) {
-          const unsigned int v = hist_s[i];
-          if (v) atomicAdd(&a.hist[(size_t)cur_g * (M + 1) + i], (unsigned long long)v);
-          hist_s[i] = 0u;
-        }
+      if (cur_g >= 0) quad_flush_table(hist_s, M + 1, a.hist + (size_t)cur_g * (M + 1), true);
       __syncthreads();
       cur_g = sg;
       since = 0;
@@ -118,7 +102,7 @@ __global__ __launch_bounds__(kVerThreads) void k_verify(const VerArgs a) {
     int n_good = 0, n_bad = 0;
 
 #pragma unroll 1
-    for (long tl = t0 + wv; tl < t1; tl += kVerThreads / 64) {
+    for (long tl = t0 + wv; tl < t1; tl += kQuadThreads / 64) {
       const long col = tl * 16 + n;
       const bool live = col < a.ncol;
       const long colc = live ? col : a.ncol - 1;
@@ -134,103 +118,49 @@ __global__ __launch_bounds__(kVerThreads) void k_verify(const VerArgs a) {
         }
         continue;
       }
-      // the lane's quarter of the row again, opaque to the optimiser: what depends only on it and on M (the LP weights 2j - M + 1,
-      // the LP slot predicates) is otherwise hoisted out of this loop and held in registers across it, which sent NU = 32 to scratch
-      int gq = lane >> 4;
-      asm volatile("" : "+v"(gq));
+      const int gq = quad_lane_quarter(lane);
       const double y = a.verif[r];
       const double w = a.colw ? a.colw[colc] : 1.0;
       double d[LP];
-      {  // clamped addresses, no branches: the loads of a tile are issued together
-        const E* p = reinterpret_cast<const E*>(a.X) + (size_t)r * M;
-        if (a.al) {
-#pragma unroll
-          for (int u = 0; u < NU; ++u) {
-            int m0 = 8 * u + 2 * gq;
-            m0 = (m0 < M) ? m0 : M - 2;
-            const typename VerPair<E>::type v = *reinterpret_cast<const typename VerPair<E>::type*>(p + m0);
-            d[2 * u] = v.x;
-            d[2 * u + 1] = v.y;
-          }
-        } else {
-#pragma unroll
-          for (int u = 0; u < NU; ++u) {
-            const int m0 = 8 * u + 2 * gq;
-            d[2 * u] = p[(m0 < M) ? m0 : M - 1];
-            d[2 * u + 1] = p[(m0 + 1 < M) ? m0 + 1 : M - 1];
-          }
-        }
-      }
+      quad_load_row<NU, E>(a.X, r, M, gq, a.al, d);
       int lb = 0, le = 0;
       bool badl = false;
       double s4[4] = {0.0, 0.0, 0.0, 0.0}, a4[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
       for (int c = 0; c < LP; ++c) {
-        const bool ok = 8 * (c >> 1) + 2 * gq + (c & 1) < M;  // the slot holds a real member
+        const bool ok = quad_slot_ok(c, gq, M);
         const double xv = d[c];
         lb += (ok && xv < y) ? 1 : 0;
         le += (ok && xv == y) ? 1 : 0;
         const double dv = xv - y;
-        badl = badl || (ok && !ver_finite(dv));
+        badl = badl || (ok && !finite64(dv));
         s4[c & 3] += ok ? dv : 0.0;
         a4[c & 3] += ok ? __builtin_fabs(dv) : 0.0;
         d[c] = ok ? dv : inf;
       }
       const double d0 = __shfl(d[0], n, 64);  // member 0
-      bool diff = false;
-#pragma unroll
-      for (int c = 0; c < LP; ++c) {
-        const bool ok = 8 * (c >> 1) + 2 * gq + (c & 1) < M;  // the slot holds a real member
-        diff = diff || (ok && d[c] != d0);
-      }
-      double sum = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-      double asum = (a4[0] + a4[1]) + (a4[2] + a4[3]);
-      sum += __shfl_xor(sum, 16, 64);
-      sum += __shfl_xor(sum, 32, 64);
-      asum += __shfl_xor(asum, 16, 64);
-      asum += __shfl_xor(asum, 32, 64);
-      lb += __shfl_xor(lb, 16, 64);
-      lb += __shfl_xor(lb, 32, 64);
-      le += __shfl_xor(le, 16, 64);
-      le += __shfl_xor(le, 32, 64);
-      const unsigned long long quad = 0x0001000100010001ull;
-      const bool varies = ((__ballot(diff) >> n) & quad) != 0ull;
-      const bool bad = ((__ballot(badl) >> n) & quad) != 0ull;
-      // the error of the mean; a row whose members are all equal has deviations of exactly 0 (its sum / M need not give d back)
-      const double err = varies ? sum / dM : d0;
-      double q4[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int c = 0; c < LP; ++c) {
-        const bool ok = 8 * (c >> 1) + 2 * gq + (c & 1) < M;  // the slot holds a real member
-        const double e = ok ? d[c] - err : 0.0;
-        q4[c & 3] = __builtin_fma(e, e, q4[c & 3]);
-      }
-      double ss = (q4[0] + q4[1]) + (q4[2] + q4[3]);
-      ss += __shfl_xor(ss, 16, 64);
-      ss += __shfl_xor(ss, 32, 64);
-      const double var = ss / (double)(M - 1);
+      const bool diff = quad_differs<LP>(d, d0, gq, M);
+      const double sum = quad_row_sum((s4[0] + s4[1]) + (s4[2] + s4[3]));
+      const double asum = quad_row_sum((a4[0] + a4[1]) + (a4[2] + a4[3]));
+      lb = quad_row_sum(lb);
+      le = quad_row_sum(le);
+      const bool varies = quad_row_any(diff, n);
+      const bool bad = quad_row_any(badl, n);
+      const double err = varies ? sum / dM : d0;  // the error of the mean, by the rule of quad_centred_ss
+      const double var = quad_centred_ss<LP>(d, err, gq, M) / (double)(M - 1);
 
-      __builtin_amdgcn_sched_barrier(0);
-      // the sort: afterwards sorted position g LP + k is slot k of lane g
-      ver_sort_local<LP>(d);
-      ver_split_rev<LP>(d, 16, (gq & 1) != 0);
-      ver_merge_local<LP>(d);
-      ver_split_rev<LP>(d, 48, gq >= 2);
-      ver_split_same<LP>(d, 16, (gq & 1) != 0);
-      ver_merge_local<LP>(d);
+      quad_sort<LP>(d, gq);  // afterwards sorted position g LP + k is slot k of lane g
       double t4[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
       for (int k = 0; k < LP; ++k) {
         const int j = gq * LP + k;
         t4[k & 3] = __builtin_fma((double)(2 * j - M + 1), (j < M) ? d[k] : 0.0, t4[k & 3]);
       }
-      double ts = (t4[0] + t4[1]) + (t4[2] + t4[3]);
-      ts += __shfl_xor(ts, 16, 64);
-      ts += __shfl_xor(ts, 32, 64);
+      const double ts = quad_row_sum((t4[0] + t4[1]) + (t4[2] + t4[3]));
       const double crps = asum / dM - ts / D;
 
       if (gq == 0 && live) {
-        const bool verified = ver_finite(y) && w > 0.0;
+        const bool verified = finite64(y) && w > 0.0;
         const bool good = verified && !bad;
         int rank = -1;
         if (good) {
@@ -266,60 +196,15 @@ __global__ __launch_bounds__(kVerThreads) void k_verify(const VerArgs a) {
       cnt_s[(wv * 16 + n) * 2 + 1] = n_bad;
     }
     __syncthreads();
-    if (tid < kVerSums) {
-      double s = 0.0;
-      for (int i = 0; i < 64; ++i) s += red_s[i * kVerSums + tid];
-      a.part[(size_t)ch * kVerSums + tid] = s;
-    } else if (tid < kVerSums + 2) {
-      long long s = 0;
-      for (int i = 0; i < 64; ++i) s += cnt_s[i * 2 + (tid - kVerSums)];
-      a.cnt[(size_t)ch * 2 + (tid - kVerSums)] = s;
-    }
+    if (tid < kVerSums)
+      a.part[(size_t)ch * kVerSums + tid] = quad_chunk_partial<double>(red_s, [&](int i) { return i * kVerSums + tid; });
+    else if (tid < kVerSums + 2)
+      a.cnt[(size_t)ch * 2 + (tid - kVerSums)] = quad_chunk_partial<long long>(cnt_s, [&](int i) { return i * 2 + (tid - kVerSums); });
     __syncthreads();
   }
 
   __syncthreads();
-  if (cur_g >= 0)
-    for (int i = tid; i <= M; i += kVerThreads) {
-      const unsigned int v = hist_s[i];
-      if (v) atomicAdd(&a.hist[(size_t)cur_g * (M + 1) + i], (unsigned long long)v);
-    }
-}
-
-// workgroup g: the partials of the chunks of group g, thread by thread in chunk order, then a tree over the threads
-__global__ __launch_bounds__(kVerThreads) void k_verify_reduce(long nchunks, long cps, const int* __restrict__ sgroup,
-                                                               const double* __restrict__ part, const long long* __restrict__ cnt,
-                                                               double* __restrict__ sums, long long* __restrict__ n_out,
-                                                               long long* __restrict__ nbad_out) {
-  __shared__ double s_s[kVerThreads];
-  __shared__ long long c_s[kVerThreads];
-  const int tid = threadIdx.x;
-  const int grp = (int)blockIdx.x;
-  for (int k = 0; k < kVerSums + 2; ++k) {
-    double s = 0.0;
-    long long c = 0;
-    for (long i = tid; i < nchunks; i += kVerThreads) {
-      if (sgroup[i / cps] != grp) continue;
-      if (k < kVerSums) s += part[(size_t)i * kVerSums + k];
-      else c += cnt[(size_t)i * 2 + (k - kVerSums)];
-    }
-    s_s[tid] = s;
-    c_s[tid] = c;
-    __syncthreads();
-    for (int off = kVerThreads / 2; off >= 1; off >>= 1) {
-      if (tid < off) {
-        s_s[tid] += s_s[tid + off];
-        c_s[tid] += c_s[tid + off];
-      }
-      __syncthreads();
-    }
-    if (tid == 0) {
-      if (k < kVerSums) sums[(size_t)grp * kVerSums + k] = s_s[0];
-      else if (k == kVerSums) n_out[grp] = c_s[0];
-      else nbad_out[grp] = c_s[0];
-    }
-    __syncthreads();
-  }
+  if (cur_g >= 0) quad_flush_table(hist_s, M + 1, a.hist + (size_t)cur_g * (M + 1), false);
 }
 
 hipError_t launch_verify(const VerArgs& a, Elem elem, int blocks, hipStream_t s) {
@@ -327,12 +212,8 @@ hipError_t launch_verify(const VerArgs& a, Elem elem, int blocks, hipStream_t s)
   if (a.nchunks <= 0) return hipSuccess;
   long grid = a.nchunks < blocks ? a.nchunks : blocks;
   if (grid < 1) grid = 1;
-  int nu_p = 1;
-  while (nu_p * 8 < a.M) nu_p *= 2;
-  return dispatch_width(nu_p, std::integer_sequence<int, 1, 2, 4, 8, 16, 32>{}, [&](auto nu_c) {
-    constexpr int nu = decltype(nu_c)::value;
-    if (elem == Elem::f32) hipLaunchKernelGGL((k_verify<nu, float>), dim3((unsigned)grid), dim3(kVerThreads), 0, s, a);
-    else hipLaunchKernelGGL((k_verify<nu, double>), dim3((unsigned)grid), dim3(kVerThreads), 0, s, a);
+  return efa_host::launch_quad(a.M, elem, [&](auto nu_c, auto e) {
+    hipLaunchKernelGGL((k_verify<decltype(nu_c)::value, decltype(e)>), dim3((unsigned)grid), dim3(kQuadThreads), 0, s, a);
     return hipGetLastError();
   });
 }
@@ -361,10 +242,7 @@ int verify(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, const dou
   if (!X_dev || !verif_dev) return fail(EFA_ERR_INVALID, "%s: null device pointer", me);
   if (!slab_group) return fail(EFA_ERR_INVALID, "%s: null slab_group", me);
   int G = 0;
-  for (long s = 0; s < n_lead; ++s) {
-    if (slab_group[s] < -1) return fail(EFA_ERR_INVALID, "%s: slab_group[%ld] = %d must be >= -1", me, s, slab_group[s]);
-    if (slab_group[s] + 1 > G) G = slab_group[s] + 1;
-  }
+  EFA_TRY(check_slab_groups(me, slab_group, n_lead, &G));
   const bool no_groups = !hist && !n && !n_bad && !sums;  // fields only
   if (G > 0 && !no_groups && (!hist || !n || !n_bad || !sums))
     return fail(EFA_ERR_INVALID, "%s: hist, n, n_bad and sums go together (all null: fields only)", me);
@@ -380,18 +258,16 @@ int verify(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, const dou
     const long nchunks = cps * n_lead;
     const int Gd = G > 0 ? G : 1;
     // ver_ws: part [nchunks][5] | sums [Gd][5] | cnt [nchunks][2] | hist [Gd][M+1] | n [Gd] | n_bad [Gd] | slab groups [n_lead]
-    const size_t n_part = (size_t)nchunks * kVerSums, n_sums = (size_t)Gd * kVerSums, n_cnt = (size_t)nchunks * 2,
-                 n_hist = (size_t)Gd * (M + 1);
-    EFA_TRY(c->ver_ws.reserve((n_part + n_sums + n_cnt + n_hist + 2 * (size_t)Gd) * 8 + (size_t)n_lead * sizeof(int)));
-    if (!c->ver_iv.begin.h) EFA_HIP(hipEventCreate(&c->ver_iv.begin.h));
-    if (!c->ver_iv.end.h) EFA_HIP(hipEventCreate(&c->ver_iv.end.h));
-    double* d_part = c->ver_ws.as<double>();
-    double* d_sums = d_part + n_part;
-    long long* d_cnt = reinterpret_cast<long long*>(d_sums + n_sums);
-    long long* d_hist = d_cnt + n_cnt;
-    long long* d_n = d_hist + n_hist;
-    long long* d_nbad = d_n + Gd;
-    int* d_sg = reinterpret_cast<int*>(d_nbad + Gd);
+    const size_t n_hist = (size_t)Gd * (M + 1);
+    WsLayout ws;
+    const auto r_part = ws.add<double>((size_t)nchunks * kVerSums), r_sums = ws.add<double>((size_t)Gd * kVerSums);
+    const auto r_cnt = ws.add<long long>((size_t)nchunks * 2), r_hist = ws.add<long long>(n_hist), r_n = ws.add<long long>(Gd),
+               r_nbad = ws.add<long long>(Gd);
+    const auto r_sg = ws.add<int>((size_t)n_lead);
+    EFA_TRY(c->ver_ws.reserve(ws.bytes()));
+    double *d_part = r_part(c->ver_ws), *d_sums = r_sums(c->ver_ws);
+    long long *d_cnt = r_cnt(c->ver_ws), *d_hist = r_hist(c->ver_ws), *d_n = r_n(c->ver_ws), *d_nbad = r_nbad(c->ver_ws);
+    int* d_sg = r_sg(c->ver_ws);
     EFA_HIP(hipMemcpyAsync(d_sg, slab_group, (size_t)n_lead * sizeof(int), hipMemcpyHostToDevice, s));
     EFA_HIP(hipMemsetAsync(d_hist, 0, n_hist * sizeof(long long), s));
     VerArgs a{};
@@ -407,7 +283,7 @@ int verify(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, const dou
     a.cps = cps;
     a.M = M;
     a.fair = fair ? 1 : 0;
-    a.al = (M % 2 == 0) && (reinterpret_cast<uintptr_t>(X_dev) % (2 * elem_size(elem)) == 0);
+    a.al = pairs_aligned(X_dev, M, elem);
     a.seed = seed;
     a.below = below_dev;
     a.equal = equal_dev;
@@ -418,14 +294,10 @@ int verify(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, const dou
     a.part = d_part;
     a.cnt = d_cnt;
     a.hist = reinterpret_cast<unsigned long long*>(d_hist);
-    long blocks = c->verify_blocks;
-    if (blocks < 1 || blocks > kVerBlocks) blocks = kVerBlocks;
-    EFA_HIP(hipEventRecord(c->ver_iv.begin, s));
-    EFA_HIP(launch_verify(a, elem, (int)blocks, s));
-    hipLaunchKernelGGL(k_verify_reduce, dim3((unsigned)Gd), dim3(kVerThreads), 0, s, nchunks, cps, d_sg, d_part, d_cnt, d_sums, d_n,
-                       d_nbad);
-    EFA_HIP(hipGetLastError());
-    EFA_HIP(hipEventRecord(c->ver_iv.end, s));
+    EFA_TRY(interval_begin(c->ver_iv, s));
+    EFA_HIP(launch_verify(a, elem, (int)clamp_blocks(c->verify_blocks, kVerBlocks), s));
+    EFA_HIP((launch_group_reduce<kVerSums, 2>(Gd, 1, s, nchunks, cps, 1, nullptr, d_sg, d_part, d_cnt, d_sums, d_n, d_nbad)));
+    EFA_TRY(interval_end(c->ver_iv, s));
     if (G > 0) {
       EFA_HIP(hipMemcpyAsync(h_int.data(), d_hist, nh * sizeof(long long), hipMemcpyDeviceToHost, s));
       EFA_HIP(hipMemcpyAsync(h_int.data() + nh, d_n, (size_t)G * sizeof(long long), hipMemcpyDeviceToHost, s));
@@ -433,9 +305,7 @@ int verify(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, const dou
       EFA_HIP(hipMemcpyAsync(h_sums.data(), d_sums, h_sums.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     }
     EFA_HIP(hipStreamSynchronize(s));
-    float ms = 0.f;
-    EFA_HIP(hipEventElapsedTime(&ms, c->ver_iv.begin, c->ver_iv.end));
-    c->verify_us = (long)std::llround((double)ms * 1000.0);
+    EFA_TRY(interval_us(c->ver_iv, &c->verify_us));
   }
   if (G > 0 && !no_groups) {
     for (size_t i = 0; i < nh; ++i) hist[i] = h_int[i];

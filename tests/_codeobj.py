@@ -48,3 +48,17 @@ def kernels(elf):
 def kernel_table(path):
     """{mangled kernel name: metadata dict} for every gfx950 kernel in the library"""
     return {k[".name"]: k for co in code_objects(path) for k in kernels(co)}
+
+
+def vgpr_step(vgprs):
+    """The occupancy step of a kernel: with 512 VGPRs per SIMD lane, the smallest of 128 / 168 / 256 / 512 (four, three, two
+    waves per SIMD, one) that holds its registers."""
+    return next(s for s in (128, 168, 256, 512) if vgprs <= s)
+
+
+def assert_no_worse_than(k, before_vgprs, before_clean=True):
+    """Kernel k against what the same instantiation had before a change to its source (before_vgprs its .vgpr_count,
+    before_clean: it had no scratch and no VGPR spill): it stays clean, and it does not fall to a lower occupancy step."""
+    if before_clean:
+        assert k[".private_segment_fixed_size"] == 0 and k.get(".vgpr_spill_count", 0) == 0, (k[".name"], k)
+    assert vgpr_step(k[".vgpr_count"]) <= vgpr_step(before_vgprs), (k[".name"], k[".vgpr_count"], before_vgprs)

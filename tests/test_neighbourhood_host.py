@@ -124,6 +124,24 @@ def test_kernels_hold_their_rows_in_registers_and_their_tiles_in_lds():
     assert lds[64] >= (16 + 128) * (64 + 128) * 4                          # the tile and a 64-point halo do sit in LDS
 
 
+# .vgpr_count of k_nbr_records<NU, E, MASK> before the row layout's helpers moved to efa_quadrow.h, (float64, float32) per (NU, MASK);
+# every instantiation was free of scratch and spills
+VGPRS_BEFORE = {(1, 0): (33, 33), (1, 1): (38, 38), (2, 0): (42, 39), (2, 1): (46, 46), (4, 0): (54, 55), (4, 1): (61, 61),
+                (8, 0): (79, 75), (8, 1): (87, 86), (16, 0): (129, 146), (16, 1): (132, 132), (32, 0): (221, 221), (32, 1): (229, 229)}
+
+
+def test_records_kernels_keep_their_occupancy_step():
+    """No k_nbr_records instantiation falls to a lower occupancy step than it had with its private copy of the row layout, and
+    none has scratch or spills."""
+    from efa_xray_amd import _lib
+    from _codeobj import assert_no_worse_than, kernel_table
+    tab = kernel_table(_lib.LIB_PATH)
+    for (nu, msk), before in VGPRS_BEFORE.items():
+        for e, v in zip("df", before):
+            (k,) = [k for n, k in tab.items() if "13k_nbr_recordsILi%dE%sLb%dE" % (nu, e, msk) in n]
+            assert_no_worse_than(k, v)
+
+
 def _state(M=4, dtype=None, nvar=2, nt=2, ny=3, nx=5):
     from efa_xray_amd import EnsembleState
     rng = np.random.default_rng(0)

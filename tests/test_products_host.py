@@ -136,6 +136,30 @@ def test_products_kernels_hold_the_row_in_registers():
     assert seen == 24
 
 
+# .vgpr_count of k_products<NU, E, SORT> before the row layout's helpers moved to efa_quadrow.h / efa_quadreduce.h, (float64, float32)
+# per (NU, SORT); NU = 32 spilled then (8 to 10 registers, no scratch)
+VGPRS_BEFORE = {(1, 0): (105, 105), (1, 1): (111, 111), (2, 0): (111, 111), (2, 1): (115, 113), (4, 0): (133, 133), (4, 1): (135, 135),
+                (8, 0): (164, 164), (8, 1): (176, 175), (16, 0): (250, 250), (16, 1): (256, 256), (32, 0): (394, 394), (32, 1): (451, 451)}
+
+
+def test_products_kernels_keep_their_occupancy_step():
+    """No k_products instantiation needs more registers than its occupancy step before the shared headers allowed, and none that
+    was free of scratch and spills has either now.  k_group_reduce (efa_quadreduce.h) is the only reduce kernel of its shape left,
+    free of scratch and spills as the three it replaces were."""
+    from efa_xray_amd import _lib
+    from _codeobj import assert_no_worse_than, kernel_table
+    tab = kernel_table(_lib.LIB_PATH)
+    for (nu, s), before in VGPRS_BEFORE.items():
+        for e, v in zip("df", before):
+            (k,) = [k for n, k in tab.items() if "10k_productsILi%dE%sLb%dE" % (nu, e, s) in n]
+            assert_no_worse_than(k, v, before_clean=nu <= 16)
+            assert k[".private_segment_fixed_size"] == 0, (k[".name"], k)
+    red = [k for n, k in tab.items() if "k_group_reduce" in n]
+    assert red and not [n for n in tab if "k_products_reduce" in n or "k_verify_reduce" in n or "k_nbr_reduce" in n]
+    for k in red:
+        assert k[".private_segment_fixed_size"] == 0 and k.get(".vgpr_spill_count", 0) == 0, (k[".name"], k)
+
+
 def _state(M=4, dtype=None, nvar=2, nt=2, ny=3, nx=5):
     from efa_xray_amd import EnsembleState
     rng = np.random.default_rng(0)

@@ -69,6 +69,29 @@ def test_exports_and_prototypes():
     assert src.index('"efa_sensitivity_f32_dev"') < src.index("def load_library")
 
 
+# .vgpr_count of k_sens_pass<NU, AL, E> before it took the pair type and the row reductions from efa_quadrow.h, per NU:
+# (unaligned float64, unaligned float32, aligned float64, aligned float32); every instantiation was free of scratch and spills
+VGPRS_BEFORE = {
+    1: (84, 84, 80, 80), 2: (100, 100, 96, 96), 3: (112, 112, 96, 100), 4: (112, 108, 100, 100), 5: (120, 124, 104, 104),
+    6: (128, 128, 108, 108), 7: (136, 136, 112, 112), 8: (144, 148, 116, 116), 9: (164, 160, 132, 128), 10: (176, 176, 140, 136),
+    11: (184, 172, 140, 140), 12: (196, 188, 156, 148), 13: (212, 200, 164, 160), 14: (220, 220, 168, 160), 15: (236, 228, 168, 172),
+    16: (240, 236, 180, 176), 17: (256, 236, 188, 188), 18: (272, 260, 196, 192), 19: (287, 277, 204, 200), 20: (285, 287, 208, 208),
+    21: (305, 295, 220, 212), 22: (312, 304, 228, 220), 23: (300, 296, 232, 228), 24: (310, 308, 240, 244), 25: (326, 317, 244, 244),
+    26: (338, 328, 256, 252), 27: (352, 339, 260, 260), 28: (378, 350, 268, 268), 29: (400, 364, 280, 276), 30: (392, 382, 288, 285),
+    31: (422, 398, 294, 283), 32: (414, 412, 292, 296)}
+
+
+def test_sens_pass_keeps_its_occupancy_step():
+    """All 128 instantiations of k_sens_pass stay free of scratch and spills, none on a lower occupancy step than before."""
+    from efa_xray_amd import _lib
+    from _codeobj import assert_no_worse_than, kernel_table
+    tab = kernel_table(_lib.LIB_PATH)
+    for nu, before in VGPRS_BEFORE.items():
+        for (al, e), v in zip(((0, "d"), (0, "f"), (1, "d"), (1, "f")), before):
+            (k,) = [k for n, k in tab.items() if "11k_sens_passILi%dELb%dE%sE" % (nu, al, e) in n]
+            assert_no_worse_than(k, v)
+
+
 def _state(dtype=None, M=6):
     from efa_xray_amd import EnsembleState
     rng = np.random.default_rng(3)

@@ -95,6 +95,26 @@ def test_exports_and_prototypes():
     assert "efa_verify.hip" in open(os.path.join(ROOT, "efa_xray_amd", "csrc", "Makefile")).read()
 
 
+# .vgpr_count of k_verify<NU, E> before the row layout's helpers moved to efa_quadrow.h / efa_quadreduce.h, (float64, float32) per NU;
+# NU = 32 spilled then (4 registers, no scratch)
+VGPRS_BEFORE = {1: (96, 96), 2: (108, 108), 4: (134, 134), 8: (184, 183), 16: (268, 268), 32: (435, 449)}
+
+
+def test_verify_kernels_hold_the_row_in_registers():
+    """The six sizes of k_verify exist for both element types; none has scratch, up to NU = 16 (128 members) none spills, and none
+    falls to a lower occupancy step than it had with its private copy of the row layout."""
+    from efa_xray_amd import _lib
+    from _codeobj import assert_no_worse_than, kernel_table
+    tab = kernel_table(_lib.LIB_PATH)
+    for nu, before in VGPRS_BEFORE.items():
+        for e, v in zip("df", before):
+            (k,) = [k for n, k in tab.items() if "8k_verifyILi%dE%sE" % (nu, e) in n]
+            assert_no_worse_than(k, v, before_clean=nu <= 16)
+            assert k[".private_segment_fixed_size"] == 0, (k[".name"], k)
+    assert len([n for n in tab if "8k_verifyILi" in n]) == 12
+    assert [n for n in tab if "k_group_reduce" in n] and not [n for n in tab if "k_verify_reduce" in n]
+
+
 def _state(M=4, dtype=None, nvar=2, nt=2, ny=3, nx=5):
     from efa_xray_amd import EnsembleState
     rng = np.random.default_rng(0)
