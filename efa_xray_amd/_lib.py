@@ -33,6 +33,7 @@ RELAX_RTPS = 2
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_uint8_p = ctypes.POINTER(ctypes.c_uint8)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
+c_int32_p = ctypes.POINTER(ctypes.c_int32)
 c_void_pp = ctypes.POINTER(ctypes.c_void_p)
 
 # every exported symbol with its (restype, argtypes); tests check this table
@@ -52,6 +53,10 @@ SIGNATURES = {
                                                       ctypes.c_double, ctypes.c_double]),
     "efa_ctx_set_vertical_localization": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, c_double_p, ctypes.c_long,
                                                          c_double_p, c_double_p]),
+    "efa_ctx_set_slab_localization": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, c_double_p, c_int32_p, ctypes.c_long,
+                                                     ctypes.c_long, c_double_p, c_double_p, c_int32_p, c_int32_p, ctypes.c_long,
+                                                     c_double_p]),
+    "efa_slab_factor_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_double_p]),
     "efa_ctx_set_outlier_threshold": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double]),
     "efa_ctx_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
     "efa_malloc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, c_void_pp]),
@@ -471,6 +476,56 @@ class Context(object):
             raise ValueError("ob_vert and ob_vert_halfwidth differ in length: %d and %d" % (ov.size, oh.size))
         _check(self.lib, self.lib.efa_ctx_set_vertical_localization(self.handle, lv.size, _dp(lv), ov.size,
                                                                     _dp(ov) if ov.size else None, _dp(oh) if oh.size else None))
+
+    def set_slab_localization(self, n_lead=None, P=0, lead_time=None, ob_time=None, ob_time_halfwidth=None, lead_var=None,
+                              ob_group=None, ob_var=None, impact=None):
+        """Temporal and cross-variable localisation of every later GC cycle on this context, host arrays:
+        lead_time [n_lead] with ob_time / ob_time_halfwidth [P] (NaN: no temporal taper) for the temporal part, lead_var [n_lead]
+        with ob_group / ob_var [P] (-1: a row of ones / no target variable) and impact [n_group][n_var] for the variable part;
+        a part left None is absent, both absent (or n_lead None) turns the setting off."""
+        if n_lead is None or (lead_time is None and impact is None):
+            _check(self.lib, self.lib.efa_ctx_set_slab_localization(self.handle, 0, None, None, 0, 0, None, None, None, None, 0, None))
+            return
+        n_lead, P = int(n_lead), int(P)
+
+        def dbl(a, n, what):
+            a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+            if a.size != n:
+                raise ValueError("%s has %d values, expected %d" % (what, a.size, n))
+            return a
+
+        def i32(a, n, what):
+            a = np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+            if a.size != n:
+                raise ValueError("%s has %d values, expected %d" % (what, a.size, n))
+            return a
+
+        lt = ot = oh = lv = og = ov = C = None
+        n_group = n_var = 0
+        if lead_time is not None:
+            lt, ot, oh = dbl(lead_time, n_lead, "lead_time"), dbl(ob_time, P, "ob_time"), dbl(ob_time_halfwidth, P, "ob_time_halfwidth")
+        if impact is not None:
+            C = np.ascontiguousarray(impact, dtype=np.float64)
+            if C.ndim != 2 or C.size == 0:
+                raise ValueError("impact must be a non-empty [n_group][n_var] table, got shape %r" % (C.shape,))
+            n_group, n_var = C.shape
+            lv, og, ov = i32(lead_var, n_lead, "lead_var"), i32(ob_group, P, "ob_group"), i32(ob_var, P, "ob_var")
+
+        def ip(a):
+            return a.ctypes.data_as(c_int32_p) if a is not None and a.size else None
+
+        def dp(a):
+            return _dp(a) if a is not None and a.size else None
+
+        _check(self.lib, self.lib.efa_ctx_set_slab_localization(self.handle, n_lead, _dp(lt), ip(lv), n_var, P, dp(ot), dp(oh), ip(og),
+                                                                ip(ov), n_group, None if C is None else _dp(C.reshape(-1))))
+
+    def slab_factor_table(self, P, n_lead, download=True):
+        """The table S[P][n_lead] of the slab factors (V T) C the one-pass sweep reads while set_slab_localization is on (and
+        with it the vertical factor of set_vertical_localization); download False: only brought up to date on the device."""
+        out = np.empty((int(P), int(n_lead)), dtype=np.float64) if download else None
+        _check(self.lib, self.lib.efa_slab_factor_table(self.handle, int(P), int(n_lead), _dp(out) if out is not None and out.size else None))
+        return out
 
     def set_outlier_threshold(self, threshold=None):
         """Outlier check of every later obs phase on this context: an ob with

@@ -76,6 +76,100 @@ def ob_vertical(obs):
     return ov, oh
 
 
+def time_lags(validtime, times):
+    """float64 lags of `times` relative to validtime[0]: hours when validtime is datetime64 (times are then anything
+    numpy.datetime64 accepts), else in validtime's own unit (times are numbers).  None gives NaN; ValueError on a time that
+    is not finite (NaT included)."""
+    vt = np.asarray(validtime)
+    if vt.size == 0:
+        raise ValueError("the state has no valid times")
+    out = np.full(len(times), np.nan)
+    for i, t in enumerate(times):
+        if t is None:
+            continue
+        try:
+            if vt.dtype.kind == "M":
+                lag = (np.datetime64(t) - vt.reshape(-1)[0]) / np.timedelta64(1, "h")
+            else:
+                lag = float(t) - float(vt.reshape(-1)[0])
+        except (TypeError, ValueError):
+            raise ValueError("time %r cannot be compared with the state's validtime (dtype %s)" % (t, vt.dtype))
+        lag = float(lag)
+        if not np.isfinite(lag):
+            raise ValueError("time %r is not finite" % (t,))
+        out[i] = lag
+    return out
+
+
+def slab_setting(state, loc, time_localize, var_impact, adaptive=None):
+    """(time_localize, impact) from the `time_localize` / `var_impact` keywords, or None when both are off:
+    impact is None or (obtypes, table) with one row of the float64 table [len(obtypes)][nvars] per obtype var_impact names.
+    ValueError on a setting that is not supported."""
+    time_localize = bool(time_localize)
+    if not time_localize and not var_impact:
+        return None
+    what = "time_localize" if time_localize else "var_impact"
+    if loc != 'GC':
+        raise ValueError("%s needs loc='GC' (the factor multiplies the Gaspari-Cohn taper); got loc=%r" % (what, loc))
+    if adaptive is not None:
+        raise ValueError("%s cannot be combined with adaptive_inflation (not supported, DESIGN.md 7t)" % what)
+    if time_localize:
+        time_lags(state.coords["validtime"], list(np.asarray(state.coords["validtime"]).reshape(-1)))
+    impact = None
+    if var_impact:
+        names = state.vars()
+        if not isinstance(var_impact, dict):
+            raise ValueError("var_impact must be a dict {obtype: {state variable: impact in [0, 1]}}, got %r" % type(var_impact).__name__)
+        obtypes = list(var_impact)
+        table = np.ones((len(obtypes), len(names)))
+        for g, obtype in enumerate(obtypes):
+            row = var_impact[obtype]
+            if not isinstance(row, dict):
+                raise ValueError("var_impact[%r] must be a dict {state variable: impact}, got %r" % (obtype, type(row).__name__))
+            for name, val in row.items():
+                if name not in names:
+                    raise ValueError("var_impact[%r] names %r, which is not a state variable (%r)" % (obtype, name, names))
+                try:
+                    c = float(val)
+                except (TypeError, ValueError):
+                    raise ValueError("var_impact[%r][%r]=%r: expected a number" % (obtype, name, val))
+                if not (np.isfinite(c) and 0.0 <= c <= 1.0):
+                    raise ValueError("var_impact[%r][%r]=%r: expected a finite number in [0, 1]" % (obtype, name, val))
+                table[g, names.index(name)] = c
+            if obtype in names and table[g, names.index(obtype)] != 1.0:
+                raise ValueError("var_impact[%r][%r] must be 1: an observation's taper against itself stays 1" % (obtype, obtype))
+        impact = (obtypes, table)
+    return time_localize, impact
+
+
+def ob_slab(state, obs, setting):
+    """The arrays of Context.set_slab_localization for these obs, as a dict of its keywords; ValueError on a bad half-width or time."""
+    time_localize, impact = setting
+    nvar, nt, P = state.nvars(), state.ntimes(), len(obs)
+    kw = dict(n_lead=nvar * nt, P=P)
+    if time_localize:
+        vt = state.coords["validtime"]
+        kw["lead_time"] = np.tile(time_lags(vt, list(np.asarray(vt).reshape(-1))), nvar)
+        oh = np.full(P, np.nan)
+        for k, ob in enumerate(obs):
+            c = getattr(ob, "time_localize_radius", None)
+            if c is not None:
+                oh[k] = check_vert_halfwidth(c, "observation %d: time_localize_radius" % k)
+        try:
+            kw["ob_time"] = time_lags(vt, [getattr(ob, "time", None) for ob in obs])
+        except ValueError as e:
+            raise ValueError("observation times: %s" % e)
+        kw["ob_time_halfwidth"] = oh
+    if impact is not None:
+        names = state.vars()
+        obtypes, table = impact
+        kw["lead_var"] = np.repeat(np.arange(nvar, dtype=np.int32), nt)
+        kw["ob_group"] = np.array([obtypes.index(ob.obtype) if ob.obtype in obtypes else -1 for ob in obs], dtype=np.int32)
+        kw["ob_var"] = np.array([names.index(ob.obtype) if ob.obtype in names else -1 for ob in obs], dtype=np.int32)
+        kw["impact"] = table
+    return kw
+
+
 def stream_setting(streamed, chunk_cols, pinned_limit_mb, adaptive=None):
     """(streamed, chunk_cols or None, pinned limit in bytes) from the `streamed` / `stream_chunk_cols` /
     `stream_pinned_limit_mb` keywords; ValueError on a setting that is not supported."""
@@ -120,6 +214,17 @@ class EnSRF(Assimilation):
                     state.vars() order, the vertical coordinate of each 2-D slab (NaN: not
                     localised vertically); obs taper with their `vert` and `vert_localize_radius`.
                     Needs loc='GC'; excludes adaptive_inflation.  None: off
+        time_localize -- temporal localisation: True multiplies the taper of ob k on a
+                    slab valid at t_s (and on an ob at t_j) by GC(|t_s - t_k|, tau_k), tau_k the ob's
+                    attribute `time_localize_radius` (set it after construction); times are lags from validtime[0], in hours when validtime is
+                    datetime64, else in validtime's unit, and tau is in the same unit.  An ob without
+                    `time` or `time_localize_radius` tapers nothing in time.  Default False
+        var_impact -- cross-variable localisation: {obtype: {state variable: c}} with
+                    0 <= c <= 1, the factor an ob of that obtype takes on that variable's slabs (and
+                    on obs of that variable); pairs left out are 1, and an obtype's impact on the
+                    variable of its own name must be 1.  None or {}: off.
+                    Both need loc='GC', exclude adaptive_inflation and combine freely with vert_coord,
+                    rtps / rtpp, outlier_threshold, streamed and float32 states
         outlier_threshold -- gross-error check, a number t > 0: an ob asked to be
                     assimilated is rejected (assimilated False, nothing updated by it) when
                     (value - prior mean)^2 > t^2 (prior variance + error), checked once per
@@ -151,6 +256,8 @@ class EnSRF(Assimilation):
         adaptive = kw.pop("adaptive_inflation", None)
         vert_coord = kw.pop("vert_coord", None)
         outlier_threshold = kw.pop("outlier_threshold", None)
+        time_localize = kw.pop("time_localize", False)
+        var_impact = kw.pop("var_impact", None)
         streamed = kw.pop("streamed", False)
         stream_chunk_cols = kw.pop("stream_chunk_cols", None)
         stream_pinned_limit_mb = kw.pop("stream_pinned_limit_mb", 4096)
@@ -177,6 +284,9 @@ class EnSRF(Assimilation):
         self.vert_coord = vertical_setting(state, vert_coord, loc, adaptive)
         if self.vert_coord is not None:
             ob_vertical(obs)
+        self.slab = slab_setting(state, loc, time_localize, var_impact, adaptive)
+        if self.slab is not None:
+            ob_slab(state, obs, self.slab)
         Assimilation.__init__(self, state, obs, nproc, inflation, verbose, device=device)
         self.loc = loc
         self.last_timing = None
@@ -231,6 +341,10 @@ class EnSRF(Assimilation):
                                  % (self.vert_coord.shape, (self.prior.nvars(), self.prior.ntimes())))
             ov, oh = ob_vertical(self.obs)
             ctx.set_vertical_localization(self.vert_coord.reshape(-1), ov, oh)
+        if self.slab is None:                   # and the temporal / variable setting, "off" included
+            ctx.set_slab_localization(None)
+        else:
+            ctx.set_slab_localization(**ob_slab(self.prior, self.obs, self.slab))
 
     def _write_diagnostics(self, diag):
         """The five diagnostics onto the observations, as ensrf.py:66,70,75,146-149."""

@@ -326,6 +326,97 @@ int efa_ctx_set_vertical_localization(efa_ctx* c, long n_lead, const double* lea
   return EFA_OK;
 }
 
+int efa_ctx_set_slab_localization(efa_ctx* c, long n_lead, const double* lead_time, const int* lead_var, long n_var, long P,
+                                  const double* ob_time, const double* ob_time_halfwidth, const int* ob_group, const int* ob_var,
+                                  long n_group, const double* impact) {
+  EFA_TRY(use(c));
+  if (!lead_time && !impact) {
+    if (c->sl_on) c->sl_serial++;
+    c->sl_on = false;
+    return EFA_OK;
+  }
+  if (n_lead <= 0) return fail(EFA_ERR_INVALID, "slab localisation: n_lead=%ld must be > 0", n_lead);
+  if (P < 0) return fail(EFA_ERR_INVALID, "slab localisation: negative observation count");
+  if (lead_time && P > 0 && (!ob_time || !ob_time_halfwidth))
+    return fail(EFA_ERR_INVALID, "slab localisation: lead_time without ob_time/ob_time_halfwidth");
+  if (impact) {
+    if (n_var <= 0 || n_group <= 0) return fail(EFA_ERR_INVALID, "slab localisation: n_var=%ld and n_group=%ld must be > 0", n_var, n_group);
+    if (!lead_var || (P > 0 && (!ob_group || !ob_var))) return fail(EFA_ERR_INVALID, "slab localisation: impact without lead_var/ob_group/ob_var");
+  }
+  const long nv = impact ? n_var : 1, ng = impact ? n_group : 0;
+  const size_t nd = (size_t)(n_lead + 2 * P + ng * nv), ni = (size_t)(n_lead + 2 * P);
+  std::vector<double> v(nd + (ni + 1) / 2, 0.0);
+  std::vector<int> iv(ni, -1);
+  const double nan = std::nan("");
+  bool any = false;
+  for (long i = 0; i < n_lead; ++i) {
+    const double t = lead_time ? lead_time[i] : nan;
+    if (std::isinf(t)) return fail(EFA_ERR_INVALID, "slab localisation: slab %ld has an infinite time", i);
+    v[i] = std::isnan(t) ? nan : t;
+  }
+  for (long k = 0; k < P; ++k) {
+    const double t = lead_time ? ob_time[k] : nan, h = lead_time ? ob_time_halfwidth[k] : nan;
+    if (std::isinf(t)) return fail(EFA_ERR_INVALID, "slab localisation: observation %ld has an infinite time", k);
+    if (!std::isnan(h) && !(std::isfinite(h) && h > 0.0))
+      return fail(EFA_ERR_INVALID, "slab localisation: observation %ld has temporal half-width %g (must be finite and > 0, or NaN)", k, h);
+    any = any || (!std::isnan(t) && !std::isnan(h));
+    v[n_lead + k] = std::isnan(t) ? nan : t;
+    v[n_lead + P + k] = std::isnan(h) ? nan : h;
+  }
+  if (impact) {
+    for (long i = 0; i < ng * nv; ++i) {
+      if (!(std::isfinite(impact[i]) && impact[i] >= 0.0 && impact[i] <= 1.0))
+        return fail(EFA_ERR_INVALID, "slab localisation: impact[%ld][%ld] = %g is not in [0, 1]", i / nv, i % nv, impact[i]);
+      v[n_lead + 2 * P + i] = impact[i];
+    }
+    for (long i = 0; i < n_lead; ++i) {
+      if (lead_var[i] < 0 || lead_var[i] >= nv) return fail(EFA_ERR_INVALID, "slab localisation: slab %ld has variable %d (n_var=%ld)", i, lead_var[i], nv);
+      iv[i] = lead_var[i];
+    }
+    for (long k = 0; k < P; ++k) {
+      const int g = ob_group[k], w = ob_var[k];
+      if (g < -1 || g >= ng) return fail(EFA_ERR_INVALID, "slab localisation: observation %ld has impact row %d (n_group=%ld)", k, g, ng);
+      if (w < -1 || w >= nv) return fail(EFA_ERR_INVALID, "slab localisation: observation %ld has target variable %d (n_var=%ld)", k, w, nv);
+      if (g >= 0 && w >= 0 && impact[g * nv + w] != 1.0)  // an ob's taper against itself stays 1 (the per-batch diagnostics, the pivots)
+        return fail(EFA_ERR_INVALID, "slab localisation: observation %ld: the impact of its obtype on its own variable is %g, not 1", k,
+                    impact[g * nv + w]);
+      iv[n_lead + k] = g;
+      iv[n_lead + P + k] = w;
+      if (g >= 0)
+        for (long u = 0; u < nv && !any; ++u) any = impact[g * nv + u] != 1.0;
+    }
+  }
+  if (ni) std::memcpy(v.data() + nd, iv.data(), ni * sizeof(int));
+  if (c->sl_on && c->sl_nlead == n_lead && c->sl_P == P && c->sl_nvar == nv && c->sl_ngroup == ng && c->sl_host.size() == v.size() &&
+      std::memcmp(c->sl_host.data(), v.data(), v.size() * sizeof(double)) == 0)
+    return EFA_OK;  // unchanged: nothing to copy, the geometry cache and the table stay valid
+  EFA_TRY(h2d(c, c->sl_dev, v.data(), v.size() * sizeof(double)));
+  EFA_HIP(hipStreamSynchronize(c->stream));  // (v is gone on return)
+  c->sl_host.swap(v);
+  c->sl_nlead = n_lead;
+  c->sl_P = P;
+  c->sl_nvar = nv;
+  c->sl_ngroup = ng;
+  c->sl_on = true;
+  c->sl_any = any;
+  c->sl_serial++;
+  return EFA_OK;
+}
+
+int efa_slab_factor_table(efa_ctx* c, long P, long n_lead, double* table) {
+  EFA_TRY(use(c));
+  if (!c->sl_on) return fail(EFA_ERR_INVALID, "efa_slab_factor_table: slab localisation is not set");
+  if (P != c->sl_P || n_lead != c->sl_nlead)
+    return fail(EFA_ERR_INVALID, "efa_slab_factor_table: set for %ld observations and %ld slabs, asked for %ld and %ld", c->sl_P, c->sl_nlead, P, n_lead);
+  if (c->vl_on && (c->vl_P != P || c->vl_nlead != n_lead))
+    return fail(EFA_ERR_INVALID, "efa_slab_factor_table: vertical localisation is set for %ld observations and %ld slabs", c->vl_P, c->vl_nlead);
+  EFA_TRY(ensure_slab_table(c));
+  if (table && P * n_lead > 0)
+    EFA_HIP(hipMemcpyAsync(table, c->sl_tab.p, (size_t)(P * n_lead) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  EFA_HIP(hipStreamSynchronize(c->stream));
+  return EFA_OK;
+}
+
 int efa_ctx_set_outlier_threshold(efa_ctx* c, double threshold) {
   EFA_TRY(use(c));
   if (!std::isfinite(threshold) || threshold < 0.0)
@@ -352,6 +443,7 @@ int efa_ctx_get_option(efa_ctx* c, const char* key, long* value) {
   else if (!strcmp(key, "gram")) *value = c->use_gram;
   else if (!strcmp(key, "pipeline")) *value = c->use_pipeline;
   else if (!strcmp(key, "gc_onepass")) *value = c->gc_onepass;
+  else if (!strcmp(key, "gc_family")) *value = c->gc_family_used;  // the last one-pass sweep: 0 plain, 1 adaptive, 2 vertical, 3 slab table
   else if (!strcmp(key, "geometry_reuse")) *value = c->geometry_reuse;
   else if (!strcmp(key, "gc_active_pairs")) {
     EFA_TRY(read_gc_pairs(c));
@@ -588,6 +680,7 @@ int efa_ensrf_update_dev(efa_ctx* c, long rows, int M, long P, double* xm_dev, d
   EFA_TRY(use(c));
   EFA_TRY(check_adaptive(c, loc_mode, rows));
   EFA_TRY(check_vloc(c, loc_mode, P, n_lead));
+  EFA_TRY(check_slab(c, loc_mode, P, n_lead));
   EFA_TRY(obs_phase(c, M, P, ym_dev, Yp_dev, ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon,
                     ob_halfwidth_km, prior_mean, prior_var, post_mean, post_var, assimilated));
   EFA_TRY(state_phase(c, rows, M, xm_dev, Xp_dev, xm_dev, Xp_dev, grid_lat, grid_lon, ncol, n_lead));
@@ -605,6 +698,7 @@ int efa_ensrf_cycle_dev(efa_ctx* c, long rows, int M, long P, const double* X_de
   if (rows > 0 && (!X_dev || !post_dev)) return fail(EFA_ERR_INVALID, "null state pointer");
   EFA_TRY(check_adaptive(c, loc_mode, rows));
   EFA_TRY(check_vloc(c, loc_mode, P, n_lead));
+  EFA_TRY(check_slab(c, loc_mode, P, n_lead));
   // Phase B may go into the stream before Phase A's status is known only if a wrong guess cannot cost the prior:
   // separate prior and posterior buffers (a redone Phase A needs the transform run again on the untouched prior)
   const StateRows r{X_dev, post_dev, Elem::f64, rows, M};

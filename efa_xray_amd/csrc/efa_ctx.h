@@ -276,6 +276,20 @@ struct efa_ctx {
   long geo_vl_serial = 0;       // ... the value the current geometry was compared with
   DevBuf vl_dev;                // device copy of vl_host
   DevBuf vl_W;                  // the per-batch sweep's taper table [nb][R] (launch_obs_taper_rows)
+  // --- temporal and cross-variable localisation (efa_ctx_set_slab_localization) -----------------------
+  bool sl_on = false;
+  bool sl_any = false;          // some ob carries a temporal taper or some impact entry is not 1 (else every factor is 1: today's kernels)
+  long sl_nlead = 0, sl_P = 0, sl_nvar = 0, sl_ngroup = 0;
+  std::vector<double> sl_host;  // as on the device: doubles [lead_time n_lead | ob_time P | ob half-width P | impact n_group*n_var],
+                                // then ints [lead_var n_lead | ob_group P | ob_var P]; NaN / -1 where a part or a value is absent
+  long sl_serial = 0;           // bumped whenever the setting changes: part of the obs geometry (geo_serial), as vl_serial
+  long geo_sl_serial = 0;       // ... the value the current geometry was compared with
+  DevBuf sl_dev;                // device copy of sl_host
+  DevBuf sl_tab;                // S[P][n_lead]: the slab factor (V T) C of every (ob, slab) pair (launch_slab_factor)
+  long sl_tab_serial = -1, sl_tab_vl_serial = -1;  // the settings the table was built from
+  const void* sl_tab_ptr = nullptr;
+  long gc_family_used = -1;     // read-only option "gc_family": the kernel family of the last one-pass sweep (0 plain, 1 adaptive,
+                                // 2 vertical, 3 slab table; -1: none ran)
   // --- outlier check (efa_ctx_set_outlier_threshold) ----------------------------------------------
   double qc_threshold = 0.0;    // 0: off
   bool qc_used = false;         // the last obs phase ran it: its flags on the device may be fewer than the caller's

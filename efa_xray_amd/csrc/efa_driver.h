@@ -65,6 +65,22 @@ inline bool vl_active(const efa_ctx* c) { return c->vl_on && c->vl_any; }
 inline const double* vl_lead(const efa_ctx* c) { return c->vl_dev.as<double>(); }
 inline const double* vl_obvert(const efa_ctx* c) { return c->vl_dev.as<double>() + c->vl_nlead; }
 inline const double* vl_obvhw(const efa_ctx* c) { return c->vl_dev.as<double>() + c->vl_nlead + c->vl_P; }
+// temporal and cross-variable localisation: as check_vloc for that setting, and its arrays on the device
+int check_slab(const efa_ctx* c, int loc_mode, long P, long n_lead);
+inline bool sl_active(const efa_ctx* c) { return c->sl_on && c->sl_any; }
+inline const double* sl_lead_time(const efa_ctx* c) { return c->sl_dev.as<double>(); }
+inline const int* sl_ints(const efa_ctx* c) {
+  return reinterpret_cast<const int*>(c->sl_dev.as<double>() + c->sl_nlead + 2 * c->sl_P + c->sl_ngroup * c->sl_nvar);
+}
+inline const int* sl_lead_var(const efa_ctx* c) { return sl_ints(c); }
+inline efa::SlabObs sl_obs(const efa_ctx* c, long w0) {  // the obs' side from ob w0 on
+  const double* d = c->sl_dev.as<double>();
+  const int* i = sl_ints(c);
+  return efa::SlabObs{d + c->sl_nlead + w0, d + c->sl_nlead + c->sl_P + w0, i + c->sl_nlead + w0, i + c->sl_nlead + c->sl_P + w0,
+                      d + c->sl_nlead + 2 * c->sl_P, c->sl_nvar};
+}
+// the slab table S[P][n_lead] on the device, rebuilt when the slab or the vertical setting changed since it was written
+int ensure_slab_table(efa_ctx* c);
 using efa::Elem;
 // The rows of one state call, prior and posterior: [rows][M] members of type elem, or the perturbation form's float64 perturbations
 struct StateRows {

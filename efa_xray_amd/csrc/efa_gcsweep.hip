@@ -413,10 +413,12 @@ constexpr int kLaneMaxMembers = 104;
 #define EFA_GC_LANE_CHUNK 32
 #endif
 constexpr int kChunkL = EFA_GC_LANE_CHUNK;  // observations staged at a time by the row-per-lane kernel (a 64-bit mask of them per wave)
-// The kernels k_sweep_gc (quad form) and k_sweep_gc_lane (row-per-lane form), defined three times: as they are, with the
-// adaptive-inflation update fused in as k_sweep_gc_adapt / k_sweep_gc_lane_adapt, and with the vertical factor of
-// each (slab, ob) pair as k_sweep_gc_vloc / k_sweep_gc_lane_vloc
+// The kernels k_sweep_gc (quad form) and k_sweep_gc_lane (row-per-lane form), defined four times: as they are, with the
+// adaptive-inflation update fused in as k_sweep_gc_adapt / k_sweep_gc_lane_adapt, with the vertical factor of
+// each (slab, ob) pair as k_sweep_gc_vloc / k_sweep_gc_lane_vloc, and with that factor read from the slab table
+// as k_sweep_gc_slab / k_sweep_gc_lane_slab
 #define EFA_GCK_ELEM double
+#define EFA_GCK_SLAB false
 #define EFA_GCK_VLOC false
 #define EFA_GCK_ADAPT false
 #define EFA_GCK_QUAD k_sweep_gc
@@ -458,13 +460,31 @@ constexpr int gc_adapt_min_waves(int NC) { return (4 * NC * 2 + 100 <= 168) ? 3 
 #undef EFA_GCK_LANE
 #undef EFA_GCK_LANE_WAVES
 #undef EFA_GCK_QUAD_WAVES
+#undef EFA_GCK_SLAB
+// with the slab table: the vertical family's kernels with the factor loaded (one run of consecutive doubles per staged ob)
+// instead of evaluated
+#define EFA_GCK_SLAB true
+#define EFA_GCK_ADAPT false
+#define EFA_GCK_QUAD k_sweep_gc_slab
+#define EFA_GCK_LANE k_sweep_gc_lane_slab
+#define EFA_GCK_LANE_WAVES(MP) 2
+#define EFA_GCK_QUAD_WAVES(NC, RPL) gc_min_waves(NC, RPL)
+#include "efa_gcsweep_kernels.h"
+#undef EFA_GCK_ADAPT
+#undef EFA_GCK_QUAD
+#undef EFA_GCK_LANE
+#undef EFA_GCK_LANE_WAVES
+#undef EFA_GCK_QUAD_WAVES
+#undef EFA_GCK_SLAB
 #undef EFA_GCK_VLOC
 #undef EFA_GCK_ELEM
-// the row-per-lane kernel on a state stored as float32: plain and with the vertical factor, member form
+// the row-per-lane kernel on a state stored as float32: plain, with the vertical factor and with the slab table,
+// member form
 #define EFA_GCK_LANE_ONLY 1
 #define EFA_GCK_ELEM float
 #define EFA_GCK_ADAPT false
 #define EFA_GCK_LANE_WAVES(MP) 2
+#define EFA_GCK_SLAB false
 #define EFA_GCK_VLOC false
 #define EFA_GCK_LANE k_sweep_gc_lane_f32
 #include "efa_gcsweep_kernels.h"
@@ -474,6 +494,12 @@ constexpr int gc_adapt_min_waves(int NC) { return (4 * NC * 2 + 100 <= 168) ? 3 
 #define EFA_GCK_LANE k_sweep_gc_lane_vloc_f32
 #include "efa_gcsweep_kernels.h"
 #undef EFA_GCK_LANE
+#undef EFA_GCK_SLAB
+#define EFA_GCK_SLAB true
+#define EFA_GCK_LANE k_sweep_gc_lane_slab_f32
+#include "efa_gcsweep_kernels.h"
+#undef EFA_GCK_LANE
+#undef EFA_GCK_SLAB
 #undef EFA_GCK_VLOC
 #undef EFA_GCK_ADAPT
 #undef EFA_GCK_LANE_WAVES
@@ -481,15 +507,17 @@ constexpr int gc_adapt_min_waves(int NC) { return (4 * NC * 2 + 100 <= 168) ? 3 
 #undef EFA_GCK_LANE_ONLY
 
 
-// the kernel family of a launch: plain, adaptive inflation fused in, vertical factor
-enum GcFamily : int { kGcPlain = 0, kGcAdapt = 1, kGcVloc = 2 };
-inline int gc_family(const GcSweepArgs& a) { return a.infl ? kGcAdapt : a.lead_vert ? kGcVloc : kGcPlain; }
+// the kernel family of a launch: plain, adaptive inflation fused in, vertical factor, slab table (which carries the vertical factor
+// too: it goes before the vertical family); the values are the option "gc_family"'s
+enum GcFamily : int { kGcPlain = 0, kGcAdapt = 1, kGcVloc = 2, kGcSlab = 3 };
+inline int gc_family(const GcSweepArgs& a) { return a.infl ? kGcAdapt : a.slab_tab ? kGcSlab : a.lead_vert ? kGcVloc : kGcPlain; }
 
 template <int MP, bool FUSED, int FAM>
 void gc_lane_launch_kernel(const GcSweepArgs& a, hipStream_t s) {
   const dim3 grid((unsigned)(a.nblk * a.lead_split)), block(256);
   if constexpr (FAM == kGcAdapt) hipLaunchKernelGGL((k_sweep_gc_lane_adapt<MP, FUSED>), grid, block, 0, s, a);
   else if constexpr (FAM == kGcVloc) hipLaunchKernelGGL((k_sweep_gc_lane_vloc<MP, FUSED>), grid, block, 0, s, a);
+  else if constexpr (FAM == kGcSlab) hipLaunchKernelGGL((k_sweep_gc_lane_slab<MP, FUSED>), grid, block, 0, s, a);
   else hipLaunchKernelGGL((k_sweep_gc_lane<MP, FUSED>), grid, block, 0, s, a);
 }
 template <int MP, int FAM>
@@ -499,11 +527,12 @@ hipError_t gc_lane_launch_one(const GcSweepArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-// the row-per-lane kernels on a state stored as float32 (member form; plain and vertical factor)
+// the row-per-lane kernels on a state stored as float32 (member form; plain, vertical factor and slab table)
 template <int MP, int FAM>
 hipError_t gc_lane_launch_f32(const GcSweepArgs& a, hipStream_t s) {
   const dim3 grid((unsigned)(a.nblk * a.lead_split)), block(256);
   if constexpr (FAM == kGcVloc) hipLaunchKernelGGL((k_sweep_gc_lane_vloc_f32<MP, true>), grid, block, 0, s, a);
+  else if constexpr (FAM == kGcSlab) hipLaunchKernelGGL((k_sweep_gc_lane_slab_f32<MP, true>), grid, block, 0, s, a);
   else hipLaunchKernelGGL((k_sweep_gc_lane_f32<MP, true>), grid, block, 0, s, a);
   return hipGetLastError();
 }
@@ -524,6 +553,7 @@ template <int NC, bool VEC, bool FUSED, int RPL, int FAM>
 void gc_launch_kernel(dim3 grid, dim3 block, hipStream_t s, const GcSweepArgs& a) {
   if constexpr (FAM == kGcAdapt) hipLaunchKernelGGL((k_sweep_gc_adapt<NC, VEC, FUSED, RPL>), grid, block, 0, s, a);
   else if constexpr (FAM == kGcVloc) hipLaunchKernelGGL((k_sweep_gc_vloc<NC, VEC, FUSED, RPL>), grid, block, 0, s, a);
+  else if constexpr (FAM == kGcSlab) hipLaunchKernelGGL((k_sweep_gc_slab<NC, VEC, FUSED, RPL>), grid, block, 0, s, a);
   else hipLaunchKernelGGL((k_sweep_gc<NC, VEC, FUSED, RPL>), grid, block, 0, s, a);
 }
 template <int NC, int FAM>
@@ -614,10 +644,13 @@ hipError_t launch_sweep_gc(const GcSweepArgs& a, Elem elem, hipStream_t s) {
     l.lead_split = (int)((l.n_lead + 15) / 16);  // groups of 16 slabs: one workgroup each
     l.lead_chunk = 16;
     return dispatch_width((l.M + 3) / 4, WidthRange<1, kLaneMaxMembers / 4>{}, [&](auto q) {
-      if (f32) return l.lead_vert ? gc_lane_launch_f32<4 * q, kGcVloc>(l, s) : gc_lane_launch_f32<4 * q, kGcPlain>(l, s);
+      if (f32)
+        return l.slab_tab ? gc_lane_launch_f32<4 * q, kGcSlab>(l, s)
+                          : l.lead_vert ? gc_lane_launch_f32<4 * q, kGcVloc>(l, s) : gc_lane_launch_f32<4 * q, kGcPlain>(l, s);
       switch (gc_family(a)) {
         case kGcAdapt: return gc_lane_launch_one<4 * q, kGcAdapt>(l, s);
         case kGcVloc: return gc_lane_launch_one<4 * q, kGcVloc>(l, s);
+        case kGcSlab: return gc_lane_launch_one<4 * q, kGcSlab>(l, s);
         default: return gc_lane_launch_one<4 * q, kGcPlain>(l, s);
       }
     });
@@ -626,6 +659,7 @@ hipError_t launch_sweep_gc(const GcSweepArgs& a, Elem elem, hipStream_t s) {
     switch (gc_family(a)) {
       case kGcAdapt: return gc_launch<nc, kGcAdapt>(a, s);
       case kGcVloc: return gc_launch<nc, kGcVloc>(a, s);
+      case kGcSlab: return gc_launch<nc, kGcSlab>(a, s);
       default: return gc_launch<nc, kGcPlain>(a, s);
     }
   });

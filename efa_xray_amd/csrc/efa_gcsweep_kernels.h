@@ -1,7 +1,9 @@
-// The two one-pass GC sweep kernels, included three times by efa_gcsweep.hip (inside namespace efa::<anonymous>, after the helpers
+// The two one-pass GC sweep kernels, included four times by efa_gcsweep.hip (inside namespace efa::<anonymous>, after the helpers
 // they use): EFA_GCK_QUAD / EFA_GCK_LANE name them, EFA_GCK_ADAPT says whether the adaptive-inflation update (Anderson 2009,
-// DESIGN.md §7c) is fused in and EFA_GCK_VLOC whether the taper carries the vertical factor of each (slab, ob) pair (DESIGN.md
-// §7d).  Separate kernel names rather than a template flag keep the plain kernels' names and code as they were.
+// DESIGN.md §7c) is fused in and EFA_GCK_VLOC whether the taper carries a factor of each (slab, ob) pair: the vertical factor,
+// evaluated while staging, or with EFA_GCK_SLAB the entry of the slab table S[ob][slab], which holds the product
+// of the vertical, temporal and variable factors.  Separate kernel names rather than a template flag keep the
+// plain kernels' names and code as they were.
 // EFA_GCK_ELEM is the element type of the state rows in memory as the row-per-lane kernel sees them: double, or float for a state
 // stored as float32 (member form only, included with EFA_GCK_LANE_ONLY: the quad kernel has no float32 form).
 // No include guard: this file is meant to be included more than once.
@@ -12,7 +14,9 @@ template <int NC, bool VEC, bool FUSED, int RPL>
 __global__ __launch_bounds__(256, EFA_GCK_QUAD_WAVES(NC, RPL)) void EFA_GCK_QUAD(const GcSweepArgs a) {
   constexpr bool ADAPT = EFA_GCK_ADAPT;
   constexpr bool VLOC = EFA_GCK_VLOC;
+  constexpr bool SLAB = EFA_GCK_SLAB;  // VLOC with the factor read from the slab table
   static_assert(!(ADAPT && VLOC), "adaptive inflation with vertical localisation is not built");
+  static_assert(VLOC || !SLAB, "the slab table is a form of the per-slab factor");
   constexpr int L = 4;
   constexpr int S = 2 * L * NC;  // padded ye row (doubles)
   constexpr int NS = 4 * RPL;    // slabs of one iteration of the slab loop
@@ -114,7 +118,8 @@ __global__ __launch_bounds__(256, EFA_GCK_QUAD_WAVES(NC, RPL)) void EFA_GCK_QUAD
         for (int i = tid; i < ne * NS; i += 256) {
           const int ee = i / NS, lead = lead0 + (i - ee * NS);
           const int k = a.idx[c0 + ee];
-          vf_s[i] = (lead < lead_hi) ? vert_factor(a.lead_vert[lead], a.ob_vert[k], a.ob_vhw[k]) : 0.0;
+          if (SLAB) vf_s[i] = (lead < lead_hi) ? a.slab_tab[(size_t)k * a.n_lead + lead] : 0.0;  // NS consecutive doubles per staged ob
+          else vf_s[i] = (lead < lead_hi) ? vert_factor(a.lead_vert[lead], a.ob_vert[k], a.ob_vhw[k]) : 0.0;
         }
       __syncthreads();
       // ---- apply the chunk to this wave's 16 RPL rows
@@ -191,7 +196,9 @@ __global__ __launch_bounds__(256, EFA_GCK_LANE_WAVES(MP)) void EFA_GCK_LANE(cons
   typedef EFA_GCK_ELEM E;
   constexpr bool ADAPT = EFA_GCK_ADAPT;
   constexpr bool VLOC = EFA_GCK_VLOC;
+  constexpr bool SLAB = EFA_GCK_SLAB;  // VLOC with the factor read from the slab table
   static_assert(!(ADAPT && VLOC), "adaptive inflation with vertical localisation is not built");
+  static_assert(VLOC || !SLAB, "the slab table is a form of the per-slab factor");
   constexpr int NG = (MP + 15) / 16;  // ye registers per lane
   constexpr int YS = 16 * NG;         // padded ye row in LDS (doubles)
   __shared__ __align__(16) double ye_s[kChunkL * YS];
@@ -329,7 +336,8 @@ __global__ __launch_bounds__(256, EFA_GCK_LANE_WAVES(MP)) void EFA_GCK_LANE(cons
         for (int i = tid; i < ne * 16; i += 256) {
           const int lead_i = lead0 + (i & 15);
           const int k = a.idx[c0 + (i >> 4)];
-          vf_s[i] = (lead_i < lead_hi) ? vert_factor(a.lead_vert[lead_i], a.ob_vert[k], a.ob_vhw[k]) : 0.0;
+          if (SLAB) vf_s[i] = (lead_i < lead_hi) ? a.slab_tab[(size_t)k * a.n_lead + lead_i] : 0.0;  // 16 consecutive doubles per staged ob
+          else vf_s[i] = (lead_i < lead_hi) ? vert_factor(a.lead_vert[lead_i], a.ob_vert[k], a.ob_vhw[k]) : 0.0;
         }
       __syncthreads();
       // the staged observations with a non-zero taper on any of this wave's columns, as a bit mask (wave-uniform); with the vertical

@@ -347,7 +347,7 @@ int make_event(OwnedEvent& e) {
 }  // namespace
 
 // Everything the call needs lives in buffers of its own (imp_*): the context's cached lists, obs-obs taper table, geometry serial,
-// trajectory, column grid, options and timing sums are neither read (but for the vertical setting) nor written.
+// trajectory, column grid, options and timing sums are neither read (but for the vertical and the slab setting) nor written.
 int obs_impact(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const double* werr_dev, const double* Ya_dev,
                const double* innov, const double* ob_error, const uint8_t* ob_used, int loc_mode, const double* ob_lat,
                const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
@@ -357,6 +357,8 @@ int obs_impact(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const
   if (M < 2 || M > kMaxMembers) return fail(EFA_ERR_INVALID, "efa_obs_impact_dev: M=%d must be in [2,%d]", M, kMaxMembers);
   if (rows < 0 || P < 0 || ncol < 0 || n_lead < 0) return fail(EFA_ERR_INVALID, "efa_obs_impact_dev: negative size");
   if (ncol * n_lead != rows) return fail(EFA_ERR_INVALID, "efa_obs_impact_dev: rows=%ld must equal n_lead*ncol = %ld*%ld", rows, n_lead, ncol);
+  if (c->sl_on)  // (its kernels have no temporal or variable factor: refused rather than computed under another taper)
+    return fail(EFA_ERR_INVALID, "slab localisation is set: efa_obs_impact_dev does not support the temporal and variable tapers");
   if (c->vl_on) {
     if (!gc) return fail(EFA_ERR_INVALID, "vertical localisation is set: the impact call needs GC localisation (loc_mode %d)", loc_mode);
     if (P != c->vl_P) return fail(EFA_ERR_INVALID, "vertical localisation was set for %ld observations, the impact call has %ld", c->vl_P, P);

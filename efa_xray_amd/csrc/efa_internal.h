@@ -151,6 +151,24 @@ hipError_t launch_obs_taper_matrix(long P, long R, const double* ob_lat, const d
 hipError_t launch_obs_taper_vert(long P, long R, const double* ob_vert, const double* ob_vhw, double* tw, hipStream_t s);
 hipError_t launch_obs_taper_rows(long b0, int nb, long R, long P, const double* ob_lat, const double* ob_lon, const double* ob_hw,
                                  const double* ob_vert, const double* ob_vhw, double* W, hipStream_t s);
+// temporal and cross-variable localisation (efa_slabloc.hip).  The obs' side of the setting on the device, every
+// pointer at the first ob of the block or window it is used for
+struct SlabObs {
+  const double* ob_time;  // [P] lag of each ob, NaN: no time (factor 1 in every pair it is part of)
+  const double* ob_thw;   // [P] temporal half-width, NaN: ob k tapers nothing in time
+  const int* ob_group;    // [P] row of the impact table, -1: a row of ones
+  const int* ob_var;      // [P] the state variable the ob's obtype names, -1: none
+  const double* impact;   // [n_group][n_var]
+  long n_var;
+};
+// S[k][s] = (V T) C of ob k and slab s (lead_vert null: V = 1), the table the slab family of the one-pass sweep stages from
+hipError_t launch_slab_factor(long P, long n_lead, const double* lead_vert, const double* ob_vert, const double* ob_vhw,
+                              const double* lead_time, const int* lead_var, const SlabObs& o, double* S, hipStream_t s);
+// tw[k][j] = (tw[k][j] T(j,k)) C[k, v_j] for j < P, behind launch_obs_taper_matrix (and launch_obs_taper_vert); and
+// launch_obs_taper_rows with both factors (ob_vert null: no vertical factor)
+hipError_t launch_obs_taper_slab(long P, long R, const SlabObs& o, double* tw, hipStream_t s);
+hipError_t launch_obs_taper_rows_slab(long b0, int nb, long R, long P, const double* ob_lat, const double* ob_lon, const double* ob_hw,
+                                      const double* ob_vert, const double* ob_vhw, const SlabObs& o, double* W, hipStream_t s);
 
 // ---- one-pass localised sweep (efa_gcsweep.hip) ---------------------------------------
 struct GcSweepArgs {
@@ -180,6 +198,8 @@ struct GcSweepArgs {
   const double* lead_vert;  // [n_lead] vertical coordinate of each slab, NaN: not localised vertically
   const double* ob_vert;    // [P] the obs' vertical coordinates, NaN: no vertical taper
   const double* ob_vhw;     // [P] their vertical half-widths (1 where ob_vert is NaN)
+  // slab table; null: off.  It carries the vertical factor as well: the slab family serves the call
+  const double* slab_tab;   // [P][n_lead] the factor of every (ob, slab) pair (launch_slab_factor)
 };
 long gc_num_blocks(long ncol);
 // list build in one pass: upper bounds + device prefix sum (off[nblk] = capacity needed), then the entries

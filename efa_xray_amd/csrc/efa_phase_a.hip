@@ -97,9 +97,11 @@ int stage_obs_inputs(efa_ctx* c, ObsCall& a, const double* ob_value, const doubl
     const size_t nb8 = (size_t)P * sizeof(double);
     const bool same = (long)c->geo_lat.size() == P && std::memcmp(c->geo_lat.data(), ob_lat, nb8) == 0 &&
                       std::memcmp(c->geo_lon.data(), ob_lon, nb8) == 0 && std::memcmp(c->geo_hw.data(), ob_hw, nb8) == 0 &&
-                      std::memcmp(c->geo_assim.data(), ob_assim, (size_t)P) == 0 && c->geo_vl_serial == c->vl_serial;
+                      std::memcmp(c->geo_assim.data(), ob_assim, (size_t)P) == 0 && c->geo_vl_serial == c->vl_serial &&
+                      c->geo_sl_serial == c->sl_serial;
     if (!same) {
       c->geo_vl_serial = c->vl_serial;  // (the vertical setting is part of the geometry: the obs-obs table carries its factor)
+      c->geo_sl_serial = c->sl_serial;  // (and so is the slab setting)
       c->geo_lat.assign(ob_lat, ob_lat + P);
       c->geo_lon.assign(ob_lon, ob_lon + P);
       c->geo_hw.assign(ob_hw, ob_hw + P);     // (sanitised above)
@@ -243,7 +245,15 @@ int sweep_rows(efa_ctx* c, const ObsCall& a, long b0, int nb, const double* Ye, 
   sw.coef = c->coef.as<double>() + (size_t)b0 * kCoefStride;
   sw.nb = nb;
   sw.taper_mode = (a.loc_mode == EFA_LOC_GC) ? kTaperObs : kTaperNone;
-  if (a.loc_mode == EFA_LOC_GC && vl_active(c)) {  // horizontal x vertical taper of the batch against every row, in table mode
+  if (a.loc_mode == EFA_LOC_GC && sl_active(c)) {  // ... times the temporal and variable factors, likewise
+    const bool vert = vl_active(c);
+    EFA_TRY(c->vl_W.reserve((size_t)nb * a.R * sizeof(double)));
+    EFA_HIP(launch_obs_taper_rows_slab(b0, nb, a.R, a.P, c->ob_lat, c->ob_lon, c->ob_hw, vert ? vl_obvert(c) : nullptr,
+                                       vert ? vl_obvhw(c) : nullptr, sl_obs(c, 0), c->vl_W.as<double>(), c->stream));
+    sw.taper_mode = kTaperTable;
+    sw.W = c->vl_W.as<double>();
+    sw.ncol = a.R;
+  } else if (a.loc_mode == EFA_LOC_GC && vl_active(c)) {  // horizontal x vertical taper of the batch against every row, in table mode
     EFA_TRY(c->vl_W.reserve((size_t)nb * a.R * sizeof(double)));
     EFA_HIP(launch_obs_taper_rows(b0, nb, a.R, a.P, c->ob_lat, c->ob_lon, c->ob_hw, vl_obvert(c), vl_obvhw(c), c->vl_W.as<double>(),
                                   c->stream));
@@ -270,9 +280,10 @@ long active_in(const ObsCall& a, long b0, int nb) {
 }
 
 // obs [w0, w1) by the per-batch kernels (k_diag on the batch's own rows, k_sweep on every other row of the block)
-// (With vertical localisation one ob per batch: k_diag's in-batch taper is horizontal only, and an ob's taper against itself is 1.)
+// (With vertical or slab localisation one ob per batch: k_diag's in-batch taper is horizontal only, and an ob's taper against itself
+// is 1.)
 int batch_window(efa_ctx* c, const ObsCall& a, long w0, long w1) {
-  const long B = (a.loc_mode == EFA_LOC_GC && vl_active(c)) ? 1 : a.B;
+  const long B = (a.loc_mode == EFA_LOC_GC && (vl_active(c) || sl_active(c))) ? 1 : a.B;
   for (long b0 = w0; b0 < w1; b0 += B) {
     const int nb = (int)((w1 - b0 < B) ? (w1 - b0) : B);
     DiagArgs d{};
@@ -366,6 +377,7 @@ int window_pipe_args(efa_ctx* c, const ObsCall& a, const Window& win, PipeArgs* 
       EFA_HIP(launch_obs_taper_matrix(Pw, Rw, c->ob_lat + w0, c->ob_lon + w0, c->ob_hw + w0, c->gc_obtrig.as<double>(),
                                       c->tw_mat.as<double>(), s));
       if (vl_active(c)) EFA_HIP(launch_obs_taper_vert(Pw, Rw, vl_obvert(c) + w0, vl_obvhw(c) + w0, c->tw_mat.as<double>(), s));
+      if (sl_active(c)) EFA_HIP(launch_obs_taper_slab(Pw, Rw, sl_obs(c, w0), c->tw_mat.as<double>(), s));
       c->tw_serial = win.direct ? c->geo_serial : -1;  // (a window's table is not the whole block's)
       c->tw_Pw = Pw;
       c->tw_Rw = Rw;
@@ -585,6 +597,7 @@ int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const d
   EFA_TRY(check_common(M, P));
   if (loc_mode != EFA_LOC_NONE && loc_mode != EFA_LOC_GC) return fail(EFA_ERR_INVALID, "loc_mode %d", loc_mode);
   EFA_TRY(check_vloc(c, loc_mode, P, -1));
+  EFA_TRY(check_slab(c, loc_mode, P, -1));
   c->have_traj = false;
   c->M = M;
   c->P = P;

@@ -66,6 +66,35 @@ int check_vloc(const efa_ctx* c, int loc_mode, long P, long n_lead) {
   return EFA_OK;
 }
 
+// ---- temporal and cross-variable localisation (efa_slabloc.hip and the _slab sweep kernels) -------------------
+// The same rules as check_vloc, for the same reasons: the factors live in the obs-obs table and in the one-pass sweep only.
+int check_slab(const efa_ctx* c, int loc_mode, long P, long n_lead) {
+  if (!c->sl_on) return EFA_OK;
+  if (loc_mode != EFA_LOC_GC)
+    return fail(EFA_ERR_INVALID, "slab localisation is set: it needs GC localisation (loc_mode %d is not EFA_LOC_GC)", loc_mode);
+  if (!c->gc_onepass) return fail(EFA_ERR_INVALID, "slab localisation is set: it needs the one-pass GC sweep (option gc_onepass is 0)");
+  if (c->ai_field) return fail(EFA_ERR_INVALID, "slab localisation is set: adaptive inflation cannot be combined with it");
+  if (P != c->sl_P) return fail(EFA_ERR_INVALID, "slab localisation was set for %ld observations, the call has %ld", c->sl_P, P);
+  if (n_lead >= 0 && n_lead != c->sl_nlead)
+    return fail(EFA_ERR_INVALID, "slab localisation was set for %ld slabs, the call has n_lead=%ld", c->sl_nlead, n_lead);
+  return EFA_OK;
+}
+
+// The table depends on the two settings alone (not on the obs' positions): it is written once per change of either, on the
+// context's stream, in front of the sweep that reads it.
+int ensure_slab_table(efa_ctx* c) {
+  const long P = c->sl_P, n_lead = c->sl_nlead;
+  EFA_TRY(c->sl_tab.reserve((size_t)(P * n_lead ? P * n_lead : 1) * sizeof(double)));
+  if (c->sl_tab_serial == c->sl_serial && c->sl_tab_vl_serial == c->vl_serial && c->sl_tab_ptr == c->sl_tab.p) return EFA_OK;
+  const bool vert = vl_active(c);  // (check_vloc: set for the same P and n_lead)
+  EFA_HIP(launch_slab_factor(P, n_lead, vert ? vl_lead(c) : nullptr, vert ? vl_obvert(c) : nullptr, vert ? vl_obvhw(c) : nullptr,
+                             sl_lead_time(c), sl_lead_var(c), sl_obs(c, 0), c->sl_tab.as<double>(), c->stream));
+  c->sl_tab_serial = c->sl_serial;
+  c->sl_tab_vl_serial = c->vl_serial;
+  c->sl_tab_ptr = c->sl_tab.p;
+  return EFA_OK;
+}
+
 // path "auto": one transform pass or sweep passes?  By FLOPS one transform pass is M/2 observations of sweep arithmetic (the rule of
 // rounds 1-2), but the transform runs on the matrix cores at 49 TFLOP/s and the sweep on the vector ALUs at 10-20, and in MEMBER form
 // (prior members in, posterior members out) the sweep path is three passes over the state -- form the perturbations, sweep, rebuild
@@ -257,6 +286,11 @@ int state_gc_onepass(efa_ctx* c, const StateRows& r, const double* xm_in, double
     g.ob_vert = vl_obvert(c);
     g.ob_vhw = vl_obvhw(c);
   }
+  if (sl_active(c)) {  // the slab table carries the vertical factor too: its family serves the call
+    EFA_TRY(ensure_slab_table(c));
+    g.slab_tab = c->sl_tab.as<double>();
+  }
+  c->gc_family_used = g.infl ? 1 : g.slab_tab ? 3 : g.lead_vert ? 2 : 0;
   EFA_HIP(launch_sweep_gc(g, r.elem, s));
   ++*nl;
   return EFA_OK;
@@ -393,6 +427,7 @@ int begin_state_call(efa_ctx* c, const char* who, long rows, int M, bool ptrs_ok
   if (rows < 0) return fail(EFA_ERR_INVALID, "negative row count");
   EFA_TRY(check_adaptive(c, c->loc_mode, rows));
   EFA_TRY(check_vloc(c, c->loc_mode, c->P, n_lead));
+  EFA_TRY(check_slab(c, c->loc_mode, c->P, n_lead));
   harvest_state_ms(c);  // the arguments are checked: the previous interval is read, the counters cleared
   c->state_ms = 0.0;
   c->state_launches = 0;

@@ -152,6 +152,11 @@ class HipEngine(object):
         """Vertical localisation of the cycles that follow on this engine's context; lead_vert None: off."""
         self.ctx.set_vertical_localization(lead_vert, ob_vert, ob_vert_halfwidth)
 
+    def clear_slab_localization(self):
+        """Temporal / cross-variable localisation off on this engine's context (an `EnSRF` on the same device may
+        have left it set; the sharded filter does not offer it)."""
+        self.ctx.set_slab_localization(None)
+
     def obs_phase(self, M, P, ym, Yp, ob):
         return self.ctx.obs_phase(M, P, ym.data_ptr(), Yp.data_ptr(), ob["value"], ob["error"], ob["assim"],
                                   _lib.LOC_GC if ob.get("loc") == "GC" else _lib.LOC_NONE,
@@ -274,6 +279,8 @@ class ShardedEnSRF(object):
             eng.set_vertical_localization(*vert)                           # every call: "off" included
         elif vert[0] is not None:
             raise ValueError("this engine does not support vertical localisation")
+        if hasattr(eng, "clear_slab_localization"):
+            eng.clear_slab_localization()                                  # every call (the context is shared per device)
         ym = eng.empty((max(P, 1),))
         eng.form_perts(P, M, HX, ym, HX)                                   # assimilation.py:46-48
         glat = glon = None

@@ -40,6 +40,21 @@ class Observation(object):
         self.localize_radius = localize_radius
         self.vert_localize_radius = vert_localize_radius
 
+    # This project's own as well: the temporal half-width that goes with `time`, in hours when the state's
+    # validtime is datetime64, else in validtime's own unit.  An attribute, not a constructor parameter (the constructor's
+    # parameter list is the reference's plus vert_localize_radius); checked when it is set.  None: no temporal taper.
+    _time_localize_radius = None
+
+    @property
+    def time_localize_radius(self):
+        return self._time_localize_radius
+
+    @time_localize_radius.setter
+    def time_localize_radius(self, c):
+        if c is not None:
+            check_vert_halfwidth(c, "time_localize_radius")
+        self._time_localize_radius = c
+
     def estimate(self, state):
         """Ensemble estimate of this ob: interpolate the matching field
         (observation.py:40-50)."""
@@ -71,7 +86,7 @@ class Observation(object):
 
 
 def check_vert_halfwidth(c, where="vert_localize_radius"):
-    """The vertical half-width as a float; ValueError unless it is a finite number > 0."""
+    """A vertical (or temporal) half-width as a float; ValueError unless it is a finite number > 0."""
     try:
         v = float(c)
     except (TypeError, ValueError):

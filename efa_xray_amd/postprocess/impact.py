@@ -120,6 +120,7 @@ def observation_impact(prior, post, obs, verification, norm=None, loc=False, ver
         grid_lat, grid_lon = post.column_latlon()
         n_lead = nvar * nt
     try:
+        ctx.set_slab_localization(None)                # (an EnSRF on this device may have left it set; no impact under it)
         if z is None:
             ctx.set_vertical_localization(None)
         else:

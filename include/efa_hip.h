@@ -96,6 +96,8 @@ int efa_ctx_set_stream(efa_ctx *ctx, void *hip_stream);
  *          read-only: "phase_a_kind" (1 pipeline / 2 per-batch / 3 Gram pipeline / 4 band pipeline, last call),
  *          "gc_active_pairs"
  *          ((column, ob) pairs with a non-zero taper in the last one-pass sweep),
+ *          "gc_family" (the kernel family of the last one-pass sweep: 0 plain, 1 adaptive inflation, 2 vertical factor,
+ *          3 slab table; -1: none ran yet),
  *          "f32_native" (see efa_state_cycle_f32_dev), "impact_us" (see efa_obs_impact_dev),
  *          "sens_us" (see efa_sensitivity_dev), "verify_us" (see efa_verify_dev),
  *          "products_us" (see efa_products_dev), "gram_us" (see efa_gram_dev);
@@ -171,6 +173,46 @@ int efa_ctx_set_adaptive_inflation(efa_ctx *ctx, double *field_dev, long rows, d
  * phase), option "gc_onepass" is 1 and no adaptive-inflation field is set. */
 int efa_ctx_set_vertical_localization(efa_ctx *ctx, long n_lead, const double *lead_vert, long P, const double *ob_vert,
                                       const double *ob_vert_halfwidth);
+
+/* ---- temporal and cross-variable localisation of the GC taper
+ * Slab s (variable-major, then valid time) has a variable index
+ * lead_var[s] in [0, n_var) and a time lead_time[s]; ob k a time ob_time[k],
+ * a temporal half-width ob_time_halfwidth[k] (same unit as the times), an
+ * impact row ob_group[k] in [0, n_group) (-1: a row of ones) and a target
+ * variable ob_var[k] in [0, n_var), the state variable its obtype names
+ * (-1: none).  With it every taper weight of a GC cycle is
+ *   state row i in slab s:  GC_h(col_i, k) * V(s,k) * T(s,k) * C[k, v_s]
+ *   obs row j:              GC_h(j, k)     * V(j,k) * T(j,k) * C[k, v_j]
+ * with T(x,k) = GC(|t_x - t_k|, tau_k), the same Gaspari-Cohn polynomial (0
+ * from 2 tau_k on) with ob k's half-width, and 1 when t_x, t_k or tau_k is
+ * NaN; C[k,v] = impact[ob_group[k]][v] (1 for ob_group[k] = -1 and for an
+ * obs row j with ob_var[j] = -1); V the vertical factor of
+ * efa_ctx_set_vertical_localization, exactly as without this setting (1 when
+ * that is off).  The factor of a slab is formed as (V T) C, each product
+ * rounded once.
+ * Host arrays, copied into the context.  lead_time NULL: no temporal part
+ * (ob_time and ob_time_halfwidth are not read); impact NULL: no variable part
+ * (lead_var, ob_group, ob_var, n_var and n_group are not read); both NULL
+ * turns the setting off.  Refused (EFA_ERR_INVALID): an impact entry that is
+ * not a finite number in [0, 1]; impact[ob_group[k]][ob_var[k]] != 1 (an
+ * ob's taper against itself stays 1); a half-width that is neither NaN nor
+ * finite and > 0; an infinite time; an index out of range.
+ * Context state like the vertical setting, with the same rules: while it is
+ * set a later call fails (EFA_ERR_INVALID) unless it is a GC cycle of exactly
+ * P observations (and n_lead slabs for the state phase), option "gc_onepass"
+ * is 1 and no adaptive-inflation field is set; efa_obs_impact_dev fails while
+ * it is set (no impact under these tapers).  When no ob has both a time and a
+ * half-width and no impact entry of a row in use differs from 1, every
+ * factor is 1 and the library runs the kernels it runs without the setting.
+ * Setting the same values again is a no-op (cached geometry stays valid).
+ *
+ * efa_slab_factor_table copies the table S[P][n_lead] of the factors (V T) C
+ * the state sweep reads (row k = ob k) to the host array `table` (NULL: the
+ * table is only brought up to date on the device); it waits. */
+int efa_ctx_set_slab_localization(efa_ctx *ctx, long n_lead, const double *lead_time, const int *lead_var, long n_var, long P,
+                                  const double *ob_time, const double *ob_time_halfwidth, const int *ob_group, const int *ob_var,
+                                  long n_group, const double *impact /* [n_group][n_var] */);
+int efa_slab_factor_table(efa_ctx *ctx, long P, long n_lead, double *table);
 
 /* ---- outlier (gross-error) check ---------------------------
  * Context state like the relaxation, for every later obs phase
