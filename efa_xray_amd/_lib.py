@@ -127,6 +127,11 @@ SIGNATURES = {
                                           c_double_p, c_double_p, c_uint8_p, ctypes.c_int,
                                           c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                           ctypes.c_long, ctypes.c_long, c_double_p]),
+    "efa_obs_impact_slab_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_long,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               c_double_p, c_double_p, c_uint8_p, ctypes.c_int,
+                                               c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                               ctypes.c_long, ctypes.c_long, c_double_p]),
     "efa_sensitivity_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, c_double_p,
                                            ctypes.c_long, ctypes.c_long, c_double_p, c_double_p, ctypes.c_void_p, ctypes.c_int,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -856,12 +861,24 @@ class Context(object):
                    ob_halfwidth=None, grid_lat=None, grid_lon=None, n_lead=1):
         """efa_obs_impact_dev: the forecast impact (P,) of every used ob, 0.0 for the others.  Xf (rows, M), werr
         (rows,) and Ya (P, M) are device arrays and are only read; the per-ob arrays and the grid are host arrays."""
+        return self._obs_impact(self.lib.efa_obs_impact_dev, rows, M, P, Xf, werr, Ya, innov, ob_error, ob_used, loc_mode, ob_lat,
+                                ob_lon, ob_halfwidth, grid_lat, grid_lon, n_lead)
+
+    def obs_impact_slab(self, rows, M, P, Xf, werr, Ya, innov, ob_error, ob_used, loc_mode=LOC_NONE, ob_lat=None, ob_lon=None,
+                        ob_halfwidth=None, grid_lat=None, grid_lon=None, n_lead=1):
+        """efa_obs_impact_slab_dev: obs_impact under the temporal and variable tapers of set_slab_localization
+        (times the vertical factor while set_vertical_localization is on); obs_impact itself while that setting is off."""
+        return self._obs_impact(self.lib.efa_obs_impact_slab_dev, rows, M, P, Xf, werr, Ya, innov, ob_error, ob_used, loc_mode,
+                                ob_lat, ob_lon, ob_halfwidth, grid_lat, grid_lon, n_lead)
+
+    def _obs_impact(self, entry, rows, M, P, Xf, werr, Ya, innov, ob_error, ob_used, loc_mode, ob_lat, ob_lon, ob_halfwidth, grid_lat,
+                    grid_lon, n_lead):
         d, err, used, lat, lon, hw = self._ob_arrays(P, innov, ob_error, ob_used, loc_mode, ob_lat, ob_lon, ob_halfwidth)
         glat, glon, ncol = self._grid(loc_mode, grid_lat, grid_lon)
         if loc_mode == LOC_NONE:
             ncol, n_lead = rows, 1
         out = np.zeros(P)
-        _check(self.lib, self.lib.efa_obs_impact_dev(
+        _check(self.lib, entry(
             self.handle, rows, M, P, self._addr(Xf), self._addr(werr), self._addr(Ya), _dp(d), _dp(err), _u8p(used), loc_mode,
             _dp(lat), _dp(lon), _dp(hw), _dp(glat), _dp(glon), ncol, n_lead, _dp(out)))
         return out

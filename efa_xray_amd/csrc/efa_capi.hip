@@ -786,6 +786,15 @@ int efa_obs_impact_dev(efa_ctx* c, long rows, int M, long P, const double* Xf_de
                     grid_lat, grid_lon, ncol, n_lead, impact);
 }
 
+int efa_obs_impact_slab_dev(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const double* werr_dev, const double* Ya_dev,
+                            const double* innov, const double* ob_error, const uint8_t* ob_used, int loc_mode, const double* ob_lat,
+                            const double* ob_lon, const double* ob_halfwidth_km, const double* grid_lat, const double* grid_lon,
+                            long ncol, long n_lead, double* impact) {
+  EFA_TRY(use(c));
+  return obs_impact_slab(c, rows, M, P, Xf_dev, werr_dev, Ya_dev, innov, ob_error, ob_used, loc_mode, ob_lat, ob_lon, ob_halfwidth_km,
+                         grid_lat, grid_lon, ncol, n_lead, impact);
+}
+
 int efa_sensitivity_dev(efa_ctx* c, long rows, int M, int K, const double* X_dev, const double* J, long ncol, long n_lead,
                         const double* slab_error, const double* weights, const uint8_t* cand_dev, int n_targets, double* var_dev,
                         double* cov_dev, double* sens_dev, double* corr_dev, double* dvar_dev, double* score_dev, long* picked_row,

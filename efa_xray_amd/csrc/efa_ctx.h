@@ -295,6 +295,7 @@ struct efa_ctx {
   bool qc_used = false;         // the last obs phase ran it: its flags on the device may be fewer than the caller's
   DevBuf qc_act;                // [P][kCoefStride], GC: the caller's flags where the one-pass sweep's list builders read coef[3]
   // --- observation impact (efa_obs_impact_dev): buffers of its own, nothing above is touched by it ---------------
+  //     (efa_obs_impact_slab_dev, §7u, brings sl_tab up to date as well: the table's cache, keyed by the two settings' serials)
   DevBuf imp_ob;    // per ob: used flags (coefficient-shaped) | scale | lat | lon | half-width | obtrig scratch | impact
   DevBuf imp_Yp;    // analysis perturbations in observation space [P][M] | their means [P]
   DevBuf imp_grid;  // the call's column grid (lat | lon)

@@ -143,6 +143,12 @@ int obs_impact(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const
                const double* innov, const double* ob_error, const uint8_t* ob_used, int loc_mode, const double* ob_lat,
                const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
                double* impact);
+// efa_obs_impact_slab_dev: the same call under the temporal and variable tapers while the slab setting is on (the contraction reads
+// the slab table, brought up to date first); obs_impact itself while it is off
+int obs_impact_slab(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const double* werr_dev, const double* Ya_dev,
+                    const double* innov, const double* ob_error, const uint8_t* ob_used, int loc_mode, const double* ob_lat,
+                    const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
+                    double* impact);
 
 // ---- efa_sensitivity.hip ------------------------------------------------------------------------------------------------------
 // efa_sensitivity_dev / _f32_dev: checks, the passes and the host algebra between them; waits before it returns

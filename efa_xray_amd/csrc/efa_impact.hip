@@ -8,6 +8,8 @@
 // zero tapers -- that writes no state: per staged ob the lanes' contributions are added across the workgroup in a fixed order and
 // one partial sum per (group of slabs, list entry) is written.  k_impact_gather / k_impact_finish add the partials per ob, again in
 // a fixed order: no floating-point atomics anywhere, two calls on the same inputs agree bit for bit.
+// Under the temporal and variable tapers: k_impact_gc_lane_slab, the same statements (efa_impact_lane_body.h) with
+// the factor of every (staged ob, slab) pair loaded from the context's slab table.
 // Unlocalised: z = Xf'^T v by a grid-stride two-stage reduction, then J_k = scale_k (Ya'_k . z).
 #include "efa_device.h"
 #include "efa_driver.h"
@@ -42,164 +44,26 @@ __device__ __forceinline__ void load_piece(const double* __restrict__ p, int M, 
   }
 }
 
+// The factor of a (staged ob, slab of the group) pair on top of the horizontal taper: none, the vertical factor evaluated while
+// staging, or the context's slab table S[P][n_lead] = (V T) C, which carries the vertical factor too
+enum ImpactFactor { kFacNone = 0, kFacVert = 1, kFacTable = 2 };
+#define EFA_IMPACT_LANE_BODY  // (efa_impact_lane_body.h refuses to be included without it)
+
 // MP: members a lane holds at a time, a multiple of 4.  WIDE false: MP is M padded (M <= 104), the row mean comes from the
 // registers as in the sweep's member form.  WIDE true: pieces of MP members, the mean from a first pass over the row.
 // Two waves per SIMD while the row, the two ye register sets and the accumulators fit 256 registers (up to 96 members, no spills); one above.
 template <int MP, bool VLOC, bool WIDE>
 __global__ __launch_bounds__(256, (MP > 96 ? 1 : 2)) void k_sweep_gc_lane_impact(const ImpactGcArgs a) {
-  constexpr int NG = (MP + 15) / 16;  // ye registers per lane
-  constexpr int YS = 16 * NG;         // padded ye row in LDS (doubles)
-  __shared__ __align__(16) double ye_s[kImpChunk * YS];
-  __shared__ __align__(16) double w_s[kImpChunk * kBlkCols];         // the taper per (staged ob, column)
-  __shared__ __align__(16) double vf_s[VLOC ? kImpChunk * 16 : 1];   // VLOC: the vertical factor per (staged ob, slab of the group)
-  __shared__ double cs[kImpChunk * kCS];                             // per (staged ob, wave, quad): the quad's contribution
-  __shared__ unsigned long long todo_s[4];                           // per wave: the staged obs it did not skip
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6, lane = tid & 63;
-  // the hand-out order of k_sweep_gc_lane: blocks longest list first, a block's groups of slabs next to each other
-  const long pos = blockIdx.x / a.lead_split;
-  const long b = a.order[pos];
-  const int grp = (int)((blockIdx.x % a.lead_split + pos) % a.lead_split);
-  const int lead0 = 16 * grp;
-  const int lead_hi = (lead0 + 16 < (int)a.n_lead) ? lead0 + 16 : (int)a.n_lead;
-  const int M = a.M;
-  const long e0 = a.off[b], e1 = e0 + a.cnt[b];
-  const auto seq = std::make_integer_sequence<int, MP>{};
-  // 16 slabs x 4 columns per wave; a group of fewer slabs: the next power of two, more columns per wave (as the sweep folds it)
-  const int rem = lead_hi - lead0;
-  const int lg_cols = (rem > 8) ? 2 : (rem > 4) ? 3 : (rem > 2) ? 4 : (rem > 1) ? 5 : 6;
-  const int ncw = 1 << lg_cols;
-  const int cq = (lane & (ncw - 1)) + ncw * wave;
-  const int lead = lead0 + (lane >> lg_cols);
-  const long col = b * kBlkCols + cq;
-  const bool live = cq < kBlkCols && col < a.ncol && lead < lead_hi;
-  const bool any_live = __ballot(live) != 0ull;
-  const long row = live ? (long)lead * a.ncol + col : 0;
-  const double* xrow = a.X + (size_t)row * M;
-  const bool vec = (M % 2 == 0) && ((reinterpret_cast<uintptr_t>(a.X) & 15u) == 0);
-  const double vi = live ? a.v[row] : 0.0;
-  double xm = 0.0;
-  if (WIDE && live) {  // the row mean, ahead of the pieces
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    int i = 0;
-    for (; i + 4 <= M; i += 4) {
-      s0 += xrow[i];
-      s1 += xrow[i + 1];
-      s2 += xrow[i + 2];
-      s3 += xrow[i + 3];
-    }
-    for (; i < M; ++i) s0 += xrow[i];
-    xm = ((s0 + s1) + (s2 + s3)) / (double)M;
-  }
-  const double* wq = w_s + (cq & (kBlkCols - 1));  // (a lane beyond the block's 16 columns holds a zero row: whatever it reads is multiplied by 0)
-  const double* yq = ye_s + (lane & 15);
-  const double* vq = vf_s + (VLOC ? (lane >> lg_cols) : 0);  // VLOC: the lane's slab slot (< 16 in every layout)
+  constexpr int FAC = VLOC ? kFacVert : kFacNone;
+#include "efa_impact_lane_body.h"
+}
 
-  for (int m0 = 0; m0 < (WIDE ? M : 1); m0 += MP) {
-    double x[MP];
-    if (live) {
-      load_piece<MP>(xrow, M, m0, vec, x);
-      if (!WIDE) {  // remove the ensemble mean as the sweep's member form does
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-#pragma unroll
-        for (int i = 0; i < MP; i += 4) {
-          s0 += x[i];
-          s1 += x[i + 1];
-          s2 += x[i + 2];
-          s3 += x[i + 3];
-        }
-        xm = ((s0 + s1) + (s2 + s3)) / (double)M;
-      }
-#pragma unroll
-      for (int i = 0; i < MP; ++i) x[i] = (m0 + i < M) ? (x[i] - xm) * vi : 0.0;  // v_i Xf'_i
-    } else {
-#pragma unroll
-      for (int i = 0; i < MP; ++i) x[i] = 0.0;
-    }
-    for (long c0 = e0; c0 < e1; c0 += kImpChunk) {
-      const int ne = (int)((e1 - c0 < kImpChunk) ? (e1 - c0) : kImpChunk);
-      __syncthreads();  // previous chunk fully consumed
-      for (int i = tid; i < ne * YS; i += 256) {
-        const int ee = i / YS, m = i - ee * YS;
-        const int k = a.idx[c0 + ee];
-        ye_s[i] = (m < MP && m0 + m < M) ? a.Yp[(size_t)k * M + m0 + m] : 0.0;
-      }
-      for (int i = tid; i < ne * kBlkCols; i += 256) w_s[i] = a.wts[(size_t)c0 * kBlkCols + i];
-      if (VLOC)
-        for (int i = tid; i < ne * 16; i += 256) {
-          const int lead_i = lead0 + (i & 15);
-          const int k = a.idx[c0 + (i >> 4)];
-          vf_s[i] = (lead_i < lead_hi) ? vert_factor(a.lead_vert[lead_i], a.ob_vert[k], a.ob_vhw[k]) : 0.0;
-        }
-      __syncthreads();
-      // the staged obs with a non-zero taper on any of this wave's columns (and, VLOC, any of its slabs): wave-uniform mask
-      bool mine = false;
-      if (lane < ne && any_live) {
-        const int c_lo = ncw * wave, c_hi = (c_lo + ncw < kBlkCols) ? c_lo + ncw : kBlkCols;
-        for (int c = c_lo; c < c_hi; ++c) mine = mine || (w_s[lane * kBlkCols + c] != 0.0);
-        if (VLOC && mine) {
-          bool vz = false;
-          for (int t = 0; t < (64 >> lg_cols) && t < 16; ++t) vz = vz || (vf_s[lane * 16 + t] != 0.0);
-          mine = vz;
-        }
-      }
-      unsigned long long todo = __ballot(mine);
-      if (lane == 0) todo_s[wave] = todo;
-      if (todo != 0ull) {
-        // Two ye register sets taken in turn: the LDS reads of the next ob's members are issued ahead of this ob's dot, and each
-        // set is written by LDS reads only (no register copy between the sets: a VALU write ahead of a DPP read is the hazard
-        // efa_lane_dot.h describes)
-        auto one_ob = [&](int ee, const double (&y)[NG]) {
-          double w = wq[ee * kBlkCols];
-          if (VLOC) w = w * vq[ee * 16];  // horizontal taper times the slab's vertical factor, rounded once as the sweep does
-          const double dot = lane_dot<MP>(x, y, seq);
-          const double q = quad_sum(w * dot);
-          if ((lane & 3) == 0) cs[ee * kCS + 16 * wave + (lane >> 2)] = q;
-        };
-        double ya[NG], yb[NG];
-        int ea = __builtin_ctzll(todo), eb = 0;
-        todo &= todo - 1;
-#pragma unroll
-        for (int c = 0; c < NG; ++c) ya[c] = yq[ea * YS + 16 * c];
-        while (true) {
-          const bool more_b = todo != 0ull;
-          if (more_b) {
-            eb = __builtin_ctzll(todo);
-            todo &= todo - 1;
-#pragma unroll
-            for (int c = 0; c < NG; ++c) yb[c] = yq[eb * YS + 16 * c];
-          }
-          one_ob(ea, ya);
-          if (!more_b) break;
-          const bool more_a = todo != 0ull;
-          if (more_a) {
-            ea = __builtin_ctzll(todo);
-            todo &= todo - 1;
-#pragma unroll
-            for (int c = 0; c < NG; ++c) ya[c] = yq[ea * YS + 16 * c];
-          }
-          one_ob(eb, yb);
-          if (!more_a) break;
-        }
-      }
-      __syncthreads();
-      // per staged ob: its 4 x 16 quad sums in a fixed order (thread 4e + w adds wave w's sixteen, the four are added by quad_sum)
-      {
-        const int e = tid >> 2, wv = tid & 3;
-        double s = 0.0;
-        if (e < ne && ((todo_s[wv] >> e) & 1ull)) {
-          const double* p = cs + e * kCS + 16 * wv;
-#pragma unroll
-          for (int i = 0; i < 16; ++i) s += p[i];
-        }
-        s = quad_sum(s);
-        if (e < ne && wv == 0) {
-          double* out = a.partial + (size_t)grp * a.cap + (c0 + e);
-          *out = (m0 == 0) ? s : *out + s;  // (a later piece: the same thread wrote the earlier ones)
-        }
-      }
-    }
-  }
+// The same kernel under the temporal and variable tapers: the factor of every (staged ob, slab) pair is loaded from
+// a.slab_tab, 16 consecutive doubles per staged ob, where the vertical form evaluates vert_factor
+template <int MP, bool WIDE>
+__global__ __launch_bounds__(256, (MP > 96 ? 1 : 2)) void k_impact_gc_lane_slab(const ImpactGcArgs a) {
+  constexpr int FAC = kFacTable;
+#include "efa_impact_lane_body.h"
 }
 
 // ---- the partials per ob, in a fixed order -----------------------------------------------------------------------------------
@@ -282,7 +146,8 @@ __global__ __launch_bounds__(256) void k_impact_none(long P, int M, const double
 template <int MP, bool WIDE>
 hipError_t impact_launch_one(const ImpactGcArgs& a, hipStream_t s) {
   const dim3 grid((unsigned)(a.nblk * a.lead_split)), block(256);
-  if (a.lead_vert) hipLaunchKernelGGL((k_sweep_gc_lane_impact<MP, true, WIDE>), grid, block, 0, s, a);
+  if (a.slab_tab) hipLaunchKernelGGL((k_impact_gc_lane_slab<MP, WIDE>), grid, block, 0, s, a);
+  else if (a.lead_vert) hipLaunchKernelGGL((k_sweep_gc_lane_impact<MP, true, WIDE>), grid, block, 0, s, a);
   else hipLaunchKernelGGL((k_sweep_gc_lane_impact<MP, false, WIDE>), grid, block, 0, s, a);
   return hipGetLastError();
 }
@@ -348,17 +213,27 @@ int make_event(OwnedEvent& e) {
 
 // Everything the call needs lives in buffers of its own (imp_*): the context's cached lists, obs-obs taper table, geometry serial,
 // trajectory, column grid, options and timing sums are neither read (but for the vertical and the slab setting) nor written.
-int obs_impact(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const double* werr_dev, const double* Ya_dev,
-               const double* innov, const double* ob_error, const uint8_t* ob_used, int loc_mode, const double* ob_lat,
-               const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
-               double* impact) {
+// slab: the call is efa_obs_impact_slab_dev with the slab setting on -- the contraction runs under GC_h(col, k) S(k, slab), S the
+// context's factor table, whose cache (keyed by the two settings' serials) is the one thing of the context it writes.
+static int impact_call(efa_ctx* c, const char* me, bool slab, long rows, int M, long P, const double* Xf_dev, const double* werr_dev,
+                       const double* Ya_dev, const double* innov, const double* ob_error, const uint8_t* ob_used, int loc_mode,
+                       const double* ob_lat, const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon,
+                       long ncol, long n_lead, double* impact) {
   const bool gc = loc_mode == EFA_LOC_GC;
-  if (loc_mode != EFA_LOC_NONE && !gc) return fail(EFA_ERR_INVALID, "efa_obs_impact_dev: loc_mode %d is neither EFA_LOC_NONE nor EFA_LOC_GC", loc_mode);
-  if (M < 2 || M > kMaxMembers) return fail(EFA_ERR_INVALID, "efa_obs_impact_dev: M=%d must be in [2,%d]", M, kMaxMembers);
-  if (rows < 0 || P < 0 || ncol < 0 || n_lead < 0) return fail(EFA_ERR_INVALID, "efa_obs_impact_dev: negative size");
-  if (ncol * n_lead != rows) return fail(EFA_ERR_INVALID, "efa_obs_impact_dev: rows=%ld must equal n_lead*ncol = %ld*%ld", rows, n_lead, ncol);
-  if (c->sl_on)  // (its kernels have no temporal or variable factor: refused rather than computed under another taper)
+  if (loc_mode != EFA_LOC_NONE && !gc) return fail(EFA_ERR_INVALID, "%s: loc_mode %d is neither EFA_LOC_NONE nor EFA_LOC_GC", me, loc_mode);
+  if (M < 2 || M > kMaxMembers) return fail(EFA_ERR_INVALID, "%s: M=%d must be in [2,%d]", me, M, kMaxMembers);
+  if (rows < 0 || P < 0 || ncol < 0 || n_lead < 0) return fail(EFA_ERR_INVALID, "%s: negative size", me);
+  if (ncol * n_lead != rows) return fail(EFA_ERR_INVALID, "%s: rows=%ld must equal n_lead*ncol = %ld*%ld", me, rows, n_lead, ncol);
+  if (c->sl_on && !slab)  // (its kernels have no temporal or variable factor: refused rather than computed under another taper)
     return fail(EFA_ERR_INVALID, "slab localisation is set: efa_obs_impact_dev does not support the temporal and variable tapers");
+  if (slab) {
+    if (!gc) return fail(EFA_ERR_INVALID, "slab localisation is set: the impact call needs GC localisation (loc_mode %d)", loc_mode);
+    if (P != c->sl_P) return fail(EFA_ERR_INVALID, "slab localisation was set for %ld observations, the impact call has %ld", c->sl_P, P);
+    if (n_lead != c->sl_nlead) return fail(EFA_ERR_INVALID, "slab localisation was set for %ld slabs, the impact call has n_lead=%ld", c->sl_nlead, n_lead);
+    if (c->vl_on && (P != c->vl_P || n_lead != c->vl_nlead))  // (the table takes its vertical factors from that setting)
+      return fail(EFA_ERR_INVALID, "slab localisation is set with vertical localisation, which was set for %ld observations and %ld slabs; the impact call has %ld and %ld",
+                  c->vl_P, c->vl_nlead, P, n_lead);
+  }
   if (c->vl_on) {
     if (!gc) return fail(EFA_ERR_INVALID, "vertical localisation is set: the impact call needs GC localisation (loc_mode %d)", loc_mode);
     if (P != c->vl_P) return fail(EFA_ERR_INVALID, "vertical localisation was set for %ld observations, the impact call has %ld", c->vl_P, P);
@@ -368,10 +243,10 @@ int obs_impact(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const
     c->impact_us = 0;
     return EFA_OK;
   }
-  if (!innov || !ob_error || !ob_used || !impact) return fail(EFA_ERR_INVALID, "efa_obs_impact_dev: null per-observation array");
-  if (!Ya_dev || (rows > 0 && (!Xf_dev || !werr_dev))) return fail(EFA_ERR_INVALID, "efa_obs_impact_dev: null device pointer");
+  if (!innov || !ob_error || !ob_used || !impact) return fail(EFA_ERR_INVALID, "%s: null per-observation array", me);
+  if (!Ya_dev || (rows > 0 && (!Xf_dev || !werr_dev))) return fail(EFA_ERR_INVALID, "%s: null device pointer", me);
   if (gc && (!ob_lat || !ob_lon || !ob_hw || (rows > 0 && (!grid_lat || !grid_lon))))
-    return fail(EFA_ERR_INVALID, "efa_obs_impact_dev: GC localisation needs ob_lat/ob_lon/ob_halfwidth_km and grid_lat/grid_lon");
+    return fail(EFA_ERR_INVALID, "%s: GC localisation needs ob_lat/ob_lon/ob_halfwidth_km and grid_lat/grid_lon", me);
   // the per-ob pack: [used (coefficient-shaped: the list builders read [3]) | scale | lat | lon | half-width]
   std::vector<double> pack((size_t)P * (kCoefStride + 4), 0.0);
   double *h_used = pack.data(), *h_scale = h_used + (size_t)P * kCoefStride, *h_lat = h_scale + P, *h_lon = h_lat + P, *h_hw = h_lon + P;
@@ -379,11 +254,11 @@ int obs_impact(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const
   for (long k = 0; k < P; ++k) {
     h_hw[k] = 1.0;  // (an ob that is not used is never looked at; its half-width may be anything)
     if (!ob_used[k]) continue;
-    if (!std::isfinite(innov[k])) return fail(EFA_ERR_INVALID, "efa_obs_impact_dev: observation %ld is used but its innovation is not finite", k);
+    if (!std::isfinite(innov[k])) return fail(EFA_ERR_INVALID, "%s: observation %ld is used but its innovation is not finite", me, k);
     if (!(std::isfinite(ob_error[k]) && ob_error[k] > 0.0))
-      return fail(EFA_ERR_INVALID, "efa_obs_impact_dev: observation %ld is used but its error variance %g is not finite and > 0", k, ob_error[k]);
+      return fail(EFA_ERR_INVALID, "%s: observation %ld is used but its error variance %g is not finite and > 0", me, k, ob_error[k]);
     if (gc) {
-      if (std::isnan(ob_hw[k])) return fail(EFA_ERR_INVALID, "efa_obs_impact_dev: observation %ld is used but its half-width is NaN", k);
+      if (std::isnan(ob_hw[k])) return fail(EFA_ERR_INVALID, "%s: observation %ld is used but its half-width is NaN", me, k);
       h_lat[k] = ob_lat[k];
       h_lon[k] = ob_lon[k];
       h_hw[k] = ob_hw[k];
@@ -454,7 +329,10 @@ int obs_impact(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const
       g.Yp = Yp;
       g.X = Xf_dev;
       g.v = werr_dev;
-      if (vl_active(c)) {
+      if (slab) {  // S = (V T) C: the vertical factor is in the table
+        EFA_TRY(ensure_slab_table(c));
+        g.slab_tab = c->sl_tab.as<double>();
+      } else if (vl_active(c)) {
         g.lead_vert = vl_lead(c);
         g.ob_vert = vl_obvert(c);
         g.ob_vhw = vl_obvhw(c);
@@ -477,6 +355,26 @@ int obs_impact(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const
   EFA_HIP(hipEventElapsedTime(&ms, c->imp_iv.begin, c->imp_iv.end));
   c->impact_us = (long)std::llround((double)ms * 1000.0);
   return EFA_OK;
+}
+
+int obs_impact(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const double* werr_dev, const double* Ya_dev,
+               const double* innov, const double* ob_error, const uint8_t* ob_used, int loc_mode, const double* ob_lat,
+               const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
+               double* impact) {
+  return impact_call(c, "efa_obs_impact_dev", false, rows, M, P, Xf_dev, werr_dev, Ya_dev, innov, ob_error, ob_used, loc_mode, ob_lat,
+                     ob_lon, ob_hw, grid_lat, grid_lon, ncol, n_lead, impact);
+}
+
+// efa_obs_impact_slab_dev: with the slab setting off it IS efa_obs_impact_dev
+int obs_impact_slab(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const double* werr_dev, const double* Ya_dev,
+                    const double* innov, const double* ob_error, const uint8_t* ob_used, int loc_mode, const double* ob_lat,
+                    const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
+                    double* impact) {
+  if (!c->sl_on)
+    return obs_impact(c, rows, M, P, Xf_dev, werr_dev, Ya_dev, innov, ob_error, ob_used, loc_mode, ob_lat, ob_lon, ob_hw, grid_lat,
+                      grid_lon, ncol, n_lead, impact);
+  return impact_call(c, "efa_obs_impact_slab_dev", true, rows, M, P, Xf_dev, werr_dev, Ya_dev, innov, ob_error, ob_used, loc_mode,
+                     ob_lat, ob_lon, ob_hw, grid_lat, grid_lon, ncol, n_lead, impact);
 }
 
 }  // namespace efa_host

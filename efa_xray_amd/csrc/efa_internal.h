@@ -240,6 +240,7 @@ struct ImpactGcArgs {
   double* partial;      // [lead_split][cap] out: one sum per (group of 16 slabs, list entry)
   long cap;             // off[nblk]
   int lead_split;       // groups of 16 slabs (set by the launcher)
+  const double* slab_tab;   // slab table as in GcSweepArgs; null: off.  It carries the vertical factor as well
 };
 int impact_lead_split(long n_lead);
 hipError_t launch_impact_gc(const ImpactGcArgs& a, hipStream_t s);

@@ -6,13 +6,15 @@ Once a verifying state exists, `observation_impact` estimates for every assimila
 
 with e^b / e^a the errors of the prior / posterior ensemble mean against the verification, c the norm's weights, Xf' the posterior
 perturbations, Ya' the posterior perturbations in observation space, d_k the innovation against the prior mean, r_k the ob's error
-variance and rho the taper the update used.  The contraction runs on the device (`efa_obs_impact_dev`); there is no NumPy path.
+variance and rho the taper the update used: Gaspari-Cohn in the horizontal, times the vertical factor (`vert_coord`), times the
+temporal and cross-variable factors (`time_localize`, `var_impact`).  The contraction runs on the device
+(`efa_obs_impact_dev`, `efa_obs_impact_slab_dev` under the last two); there is no NumPy path.
 """
 import numpy as np
 
 from efa_xray_amd import _lib
 from efa_xray_amd.assimilation.assimilation import Assimilation
-from efa_xray_amd.assimilation.ensrf import ob_vertical, vertical_setting
+from efa_xray_amd.assimilation.ensrf import ob_slab, ob_vertical, slab_setting, vertical_setting
 
 
 def _error_terms(prior, post, verification, norm):
@@ -50,7 +52,8 @@ def _error_terms(prior, post, verification, norm):
     return v.reshape(-1), actual
 
 
-def observation_impact(prior, post, obs, verification, norm=None, loc=False, vert_coord=None, device=0):
+def observation_impact(prior, post, obs, verification, norm=None, loc=False, vert_coord=None, device=0, time_localize=False,
+                       var_impact=None):
     """The forecast impact of every assimilated observation.
 
     prior, post  -- the `EnsembleState`s that went into and came out of `EnSRF(...).update()` (float64)
@@ -58,7 +61,7 @@ def observation_impact(prior, post, obs, verification, norm=None, loc=False, ver
     verification -- mapping variable name -> array (ntimes, ny, nx): the verifying state; NaN, or a variable that is missing,
                     means not verified (weight 0)
     norm         -- None (weight 1), or mapping variable name -> non-negative scalar or array broadcastable to (ntimes, ny, nx)
-    loc, vert_coord -- as in `EnSRF`: pass what the update used (the taper is not advected)
+    loc, vert_coord, time_localize, var_impact -- as in `EnSRF`: pass what the update used (the taper is not advected)
     device       -- HIP device ordinal
 
     Returns a dict: `impact` (P,), NaN where the ob was not assimilated, negative where it reduced the error; `total`, the sum
@@ -82,6 +85,8 @@ def observation_impact(prior, post, obs, verification, norm=None, loc=False, ver
     ov = oh = None
     if z is not None:
         ov, oh = ob_vertical(obs)
+    slab = slab_setting(post, loc, time_localize, var_impact)
+    slab_kw = ob_slab(post, obs, slab) if slab is not None else None
     v, actual = _error_terms(prior, post, verification, norm)
     P = len(obs)
     used = np.array([bool(getattr(ob, "assimilated", False)) for ob in obs], dtype=bool)
@@ -120,13 +125,18 @@ def observation_impact(prior, post, obs, verification, norm=None, loc=False, ver
         grid_lat, grid_lon = post.column_latlon()
         n_lead = nvar * nt
     try:
-        ctx.set_slab_localization(None)                # (an EnSRF on this device may have left it set; no impact under it)
+        if slab_kw is None:                            # (an EnSRF on this device may have left it set)
+            ctx.set_slab_localization(None)
+        else:
+            ctx.set_slab_localization(**slab_kw)
         if z is None:
             ctx.set_vertical_localization(None)
         else:
             ctx.set_vertical_localization(z.reshape(-1), ov, oh)
-        J = ctx.obs_impact(N, M, P, X, ctx.to_device(v), Ya, innov, error, used, loc_mode, lat, lon, hw, grid_lat, grid_lon, n_lead)
+        impact = ctx.obs_impact if slab_kw is None else ctx.obs_impact_slab
+        J = impact(N, M, P, X, ctx.to_device(v), Ya, innov, error, used, loc_mode, lat, lon, hw, grid_lat, grid_lon, n_lead)
     finally:
+        ctx.set_slab_localization(None)
         ctx.set_vertical_localization(None)
     out["impact"] = np.where(used, J, np.nan)
     out["total"] = float(np.sum(J[used]))

@@ -201,9 +201,10 @@ int efa_ctx_set_vertical_localization(efa_ctx *ctx, long n_lead, const double *l
  * set a later call fails (EFA_ERR_INVALID) unless it is a GC cycle of exactly
  * P observations (and n_lead slabs for the state phase), option "gc_onepass"
  * is 1 and no adaptive-inflation field is set; efa_obs_impact_dev fails while
- * it is set (no impact under these tapers).  When no ob has both a time and a
- * half-width and no impact entry of a row in use differs from 1, every
- * factor is 1 and the library runs the kernels it runs without the setting.
+ * it is set (efa_obs_impact_slab_dev is the impact under these tapers).
+ * When no ob has both a time and a half-width and no impact entry of a row
+ * in use differs from 1, every factor is 1 and the library runs the kernels
+ * it runs without the setting.
  * Setting the same values again is a no-op (cached geometry stays valid).
  *
  * efa_slab_factor_table copies the table S[P][n_lead] of the factors (V T) C
@@ -581,6 +582,39 @@ int efa_obs_impact_dev(efa_ctx *ctx, long rows, int M, long P,
                        const double *ob_halfwidth_km, const double *grid_lat,
                        const double *grid_lon, long ncol, long n_lead,
                        double *impact);
+
+/* ---- observation impact under the temporal and variable tapers ----
+ * efa_obs_impact_dev for a context on which efa_ctx_set_slab_localization is
+ * set: the same parameters, the same formula, and
+ *   rho_ik = GC(column, ob k; ob_halfwidth_km[k]) * S(k, slab)
+ * for state row i = lead*ncol + col, S = (V T) C the slab factor of
+ * efa_slab_factor_table: the vertical factor (1 unless vertical localisation
+ * is set too), the temporal taper and the impact of ob k's obtype on the
+ * slab's variable -- the taper the one-pass sweep used for that row, each
+ * product rounded once as it rounds it.  The table is brought up to date on
+ * the context's stream ahead of the contraction.
+ * While the slab setting is on, the call must be an EFA_LOC_GC call of exactly
+ * the P and n_lead the setting was made for (and the vertical setting, if on,
+ * for the same P and n_lead); anything else is EFA_ERR_INVALID with a message
+ * that names slab localisation.  While it is off, the call is
+ * efa_obs_impact_dev, bit for bit: it is handed on to that entry, so the
+ * message of an argument error then names efa_obs_impact_dev.
+ * Everything else is as efa_obs_impact_dev has it: no preceding obs phase, a
+ * column shard's rows (the table does not depend on the columns, so the
+ * shards' impacts still add up), "impact_us", the stream synchronised before
+ * returning, exactly 0.0 for an ob that is not used and for a used ob whose
+ * taper or factor is zero on every row, sums in a fixed order without atomics.
+ * Of the context it writes the cached factor table alone (keyed by the two
+ * settings): a cycle after it returns the bits it returns without it.
+ * Sensitivity and targeting stay unlocalised. */
+int efa_obs_impact_slab_dev(efa_ctx *ctx, long rows, int M, long P,
+                            const double *Xf_dev, const double *werr_dev,
+                            const double *Ya_dev, const double *innov,
+                            const double *ob_error, const uint8_t *ob_used,
+                            int loc_mode, const double *ob_lat,
+                            const double *ob_lon, const double *ob_halfwidth_km,
+                            const double *grid_lat, const double *grid_lon,
+                            long ncol, long n_lead, double *impact);
 
 /* ---- ensemble sensitivity and greedy observation targeting (Ancell & Hakim 2007, Torn & Hakim 2008) ----
  * Asked BEFORE observations are taken: which state rows drive K forecast
