@@ -413,127 +413,41 @@ constexpr int kLaneMaxMembers = 104;
 #define EFA_GC_LANE_CHUNK 32
 #endif
 constexpr int kChunkL = EFA_GC_LANE_CHUNK;  // observations staged at a time by the row-per-lane kernel (a 64-bit mask of them per wave)
-// The kernels k_sweep_gc (quad form) and k_sweep_gc_lane (row-per-lane form), defined four times: as they are, with the
-// adaptive-inflation update fused in as k_sweep_gc_adapt / k_sweep_gc_lane_adapt, with the vertical factor of
-// each (slab, ob) pair as k_sweep_gc_vloc / k_sweep_gc_lane_vloc, and with that factor read from the slab table
-// as k_sweep_gc_slab / k_sweep_gc_lane_slab
-#define EFA_GCK_ELEM double
-#define EFA_GCK_SLAB false
-#define EFA_GCK_VLOC false
-#define EFA_GCK_ADAPT false
-#define EFA_GCK_QUAD k_sweep_gc
-#define EFA_GCK_LANE k_sweep_gc_lane
-#define EFA_GCK_LANE_WAVES(MP) 2
-#define EFA_GCK_QUAD_WAVES(NC, RPL) gc_min_waves(NC, RPL)
-#include "efa_gcsweep_kernels.h"
-#undef EFA_GCK_ADAPT
-#undef EFA_GCK_QUAD
-#undef EFA_GCK_LANE
-#undef EFA_GCK_LANE_WAVES
-#undef EFA_GCK_QUAD_WAVES
-// the quad form with the update: one row per quad (gc_launch), and waves per SIMD for that row, one ye row and ~100 registers of
-// everything else (the update's temporaries included)
-constexpr int gc_adapt_min_waves(int NC) { return (4 * NC * 2 + 100 <= 168) ? 3 : (4 * NC * 2 + 100 <= 256) ? 2 : 1; }
-// with the update, above 80 members at one wave per SIMD: the row, the ye registers and the update's temporaries spill at two
-#define EFA_GCK_ADAPT true
-#define EFA_GCK_QUAD k_sweep_gc_adapt
-#define EFA_GCK_LANE k_sweep_gc_lane_adapt
-#define EFA_GCK_LANE_WAVES(MP) ((MP) > 80 ? 1 : 2)
-#define EFA_GCK_QUAD_WAVES(NC, RPL) gc_adapt_min_waves(NC)
-#include "efa_gcsweep_kernels.h"
-#undef EFA_GCK_ADAPT
-#undef EFA_GCK_QUAD
-#undef EFA_GCK_LANE
-#undef EFA_GCK_LANE_WAVES
-#undef EFA_GCK_QUAD_WAVES
-#undef EFA_GCK_VLOC
-// with the vertical factor: the launch shapes and rows per quad of the plain kernels (a few registers more per row for the factor)
-#define EFA_GCK_VLOC true
-#define EFA_GCK_ADAPT false
-#define EFA_GCK_QUAD k_sweep_gc_vloc
-#define EFA_GCK_LANE k_sweep_gc_lane_vloc
-#define EFA_GCK_LANE_WAVES(MP) 2
-#define EFA_GCK_QUAD_WAVES(NC, RPL) gc_min_waves(NC, RPL)
-#include "efa_gcsweep_kernels.h"
-#undef EFA_GCK_ADAPT
-#undef EFA_GCK_QUAD
-#undef EFA_GCK_LANE
-#undef EFA_GCK_LANE_WAVES
-#undef EFA_GCK_QUAD_WAVES
-#undef EFA_GCK_SLAB
-// with the slab table: the vertical family's kernels with the factor loaded (one run of consecutive doubles per staged ob)
-// instead of evaluated
-#define EFA_GCK_SLAB true
-#define EFA_GCK_ADAPT false
-#define EFA_GCK_QUAD k_sweep_gc_slab
-#define EFA_GCK_LANE k_sweep_gc_lane_slab
-#define EFA_GCK_LANE_WAVES(MP) 2
-#define EFA_GCK_QUAD_WAVES(NC, RPL) gc_min_waves(NC, RPL)
-#include "efa_gcsweep_kernels.h"
-#undef EFA_GCK_ADAPT
-#undef EFA_GCK_QUAD
-#undef EFA_GCK_LANE
-#undef EFA_GCK_LANE_WAVES
-#undef EFA_GCK_QUAD_WAVES
-#undef EFA_GCK_SLAB
-#undef EFA_GCK_VLOC
-#undef EFA_GCK_ELEM
-// the row-per-lane kernel on a state stored as float32: plain, with the vertical factor and with the slab table,
-// member form
-#define EFA_GCK_LANE_ONLY 1
-#define EFA_GCK_ELEM float
-#define EFA_GCK_ADAPT false
-#define EFA_GCK_LANE_WAVES(MP) 2
-#define EFA_GCK_SLAB false
-#define EFA_GCK_VLOC false
-#define EFA_GCK_LANE k_sweep_gc_lane_f32
-#include "efa_gcsweep_kernels.h"
-#undef EFA_GCK_LANE
-#undef EFA_GCK_VLOC
-#define EFA_GCK_VLOC true
-#define EFA_GCK_LANE k_sweep_gc_lane_vloc_f32
-#include "efa_gcsweep_kernels.h"
-#undef EFA_GCK_LANE
-#undef EFA_GCK_SLAB
-#define EFA_GCK_SLAB true
-#define EFA_GCK_LANE k_sweep_gc_lane_slab_f32
-#include "efa_gcsweep_kernels.h"
-#undef EFA_GCK_LANE
-#undef EFA_GCK_SLAB
-#undef EFA_GCK_VLOC
-#undef EFA_GCK_ADAPT
-#undef EFA_GCK_LANE_WAVES
-#undef EFA_GCK_ELEM
-#undef EFA_GCK_LANE_ONLY
 
-
-// the kernel family of a launch: plain, adaptive inflation fused in, vertical factor, slab table (which carries the vertical factor
-// too: it goes before the vertical family); the values are the option "gc_family"'s
+// the kernel family of a launch: plain, adaptive inflation fused in, vertical factor (§7d), slab table (§7t; it
+// carries the vertical factor too: it goes before the vertical family); the values are the option "gc_family"'s
 enum GcFamily : int { kGcPlain = 0, kGcAdapt = 1, kGcVloc = 2, kGcSlab = 3 };
 inline int gc_family(const GcSweepArgs& a) { return a.infl ? kGcAdapt : a.slab_tab ? kGcSlab : a.lead_vert ? kGcVloc : kGcPlain; }
-
-template <int MP, bool FUSED, int FAM>
-void gc_lane_launch_kernel(const GcSweepArgs& a, hipStream_t s) {
-  const dim3 grid((unsigned)(a.nblk * a.lead_split)), block(256);
-  if constexpr (FAM == kGcAdapt) hipLaunchKernelGGL((k_sweep_gc_lane_adapt<MP, FUSED>), grid, block, 0, s, a);
-  else if constexpr (FAM == kGcVloc) hipLaunchKernelGGL((k_sweep_gc_lane_vloc<MP, FUSED>), grid, block, 0, s, a);
-  else if constexpr (FAM == kGcSlab) hipLaunchKernelGGL((k_sweep_gc_lane_slab<MP, FUSED>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((k_sweep_gc_lane<MP, FUSED>), grid, block, 0, s, a);
-}
-template <int MP, int FAM>
-hipError_t gc_lane_launch_one(const GcSweepArgs& a, hipStream_t s) {
-  if (a.fused_members) gc_lane_launch_kernel<MP, true, FAM>(a, s);
-  else gc_lane_launch_kernel<MP, false, FAM>(a, s);
-  return hipGetLastError();
+// dispatch_family(fam, f) returns f(std::integral_constant<int, FAM>{}) for the FAM equal to fam
+template <class F>
+hipError_t dispatch_family(int fam, F&& f) {
+  return dispatch_width(fam, std::integer_sequence<int, kGcPlain, kGcAdapt, kGcVloc, kGcSlab>{}, f);
 }
 
-// the row-per-lane kernels on a state stored as float32 (member form; plain, vertical factor and slab table)
-template <int MP, int FAM>
-hipError_t gc_lane_launch_f32(const GcSweepArgs& a, hipStream_t s) {
+// Waves per SIMD of the quad form.  With the update: one row per quad (gc_launch), and waves per SIMD for that row, one ye row and
+// ~100 registers of everything else (the update's temporaries included); the vertical factor and the slab table take the launch
+// shapes and rows per quad of the plain kernels (a few registers more per row for the factor)
+constexpr int gc_adapt_min_waves(int NC) { return (4 * NC * 2 + 100 <= 168) ? 3 : (4 * NC * 2 + 100 <= 256) ? 2 : 1; }
+constexpr int gc_quad_waves(int FAM, int NC, int RPL) { return FAM == kGcAdapt ? gc_adapt_min_waves(NC) : gc_min_waves(NC, RPL); }
+// and of the row-per-lane form.  With the update, above 80 members at one wave per SIMD: the row, the ye registers and the
+// update's temporaries spill at two
+constexpr int gc_lane_waves(int FAM, int MP) { return (FAM == kGcAdapt && MP > 80) ? 1 : 2; }
+
+#include "efa_gcsweep_kernels.h"
+
+// The row-per-lane launch.  float32 rows exist in member form and without adaptive inflation only, which
+// launch_sweep_gc has made sure of.
+template <int FAM, typename E, int MP>
+hipError_t gc_lane_launch(const GcSweepArgs& a, hipStream_t s) {
   const dim3 grid((unsigned)(a.nblk * a.lead_split)), block(256);
-  if constexpr (FAM == kGcVloc) hipLaunchKernelGGL((k_sweep_gc_lane_vloc_f32<MP, true>), grid, block, 0, s, a);
-  else if constexpr (FAM == kGcSlab) hipLaunchKernelGGL((k_sweep_gc_lane_slab_f32<MP, true>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((k_sweep_gc_lane_f32<MP, true>), grid, block, 0, s, a);
+  if constexpr (sizeof(E) != sizeof(double)) {
+    if constexpr (FAM == kGcAdapt) return hipErrorInvalidValue;
+    else hipLaunchKernelGGL((k_sweep_gc_lane<FAM, E, MP, true>), grid, block, 0, s, a);
+  } else if (a.fused_members) {
+    hipLaunchKernelGGL((k_sweep_gc_lane<FAM, E, MP, true>), grid, block, 0, s, a);
+  } else {
+    hipLaunchKernelGGL((k_sweep_gc_lane<FAM, E, MP, false>), grid, block, 0, s, a);
+  }
   return hipGetLastError();
 }
 
@@ -549,14 +463,7 @@ int device_cus() {
   return cus;
 }
 
-template <int NC, bool VEC, bool FUSED, int RPL, int FAM>
-void gc_launch_kernel(dim3 grid, dim3 block, hipStream_t s, const GcSweepArgs& a) {
-  if constexpr (FAM == kGcAdapt) hipLaunchKernelGGL((k_sweep_gc_adapt<NC, VEC, FUSED, RPL>), grid, block, 0, s, a);
-  else if constexpr (FAM == kGcVloc) hipLaunchKernelGGL((k_sweep_gc_vloc<NC, VEC, FUSED, RPL>), grid, block, 0, s, a);
-  else if constexpr (FAM == kGcSlab) hipLaunchKernelGGL((k_sweep_gc_slab<NC, VEC, FUSED, RPL>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((k_sweep_gc<NC, VEC, FUSED, RPL>), grid, block, 0, s, a);
-}
-template <int NC, int FAM>
+template <int FAM, int NC>
 hipError_t gc_launch(const GcSweepArgs& a0, hipStream_t s) {
   constexpr bool ADAPT = FAM == kGcAdapt;
   GcSweepArgs a = a0;
@@ -574,11 +481,11 @@ hipError_t gc_launch(const GcSweepArgs& a0, hipStream_t s) {
   a.lead_split = (int)((a.n_lead + a.lead_chunk - 1) / a.lead_chunk);
   const dim3 grid((unsigned)(a.nblk * a.lead_split)), block(256);
   if (a.fused_members) {
-    if (vec) gc_launch_kernel<NC, true, true, RPL, FAM>(grid, block, s, a);
-    else gc_launch_kernel<NC, false, true, RPL, FAM>(grid, block, s, a);
+    if (vec) hipLaunchKernelGGL((k_sweep_gc<FAM, NC, true, true, RPL>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k_sweep_gc<FAM, NC, false, true, RPL>), grid, block, 0, s, a);
   } else {
-    if (vec) gc_launch_kernel<NC, true, false, RPL, FAM>(grid, block, s, a);
-    else gc_launch_kernel<NC, false, false, RPL, FAM>(grid, block, s, a);
+    if (vec) hipLaunchKernelGGL((k_sweep_gc<FAM, NC, true, false, RPL>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k_sweep_gc<FAM, NC, false, false, RPL>), grid, block, 0, s, a);
   }
   return hipGetLastError();
 }
@@ -643,25 +550,16 @@ hipError_t launch_sweep_gc(const GcSweepArgs& a, Elem elem, hipStream_t s) {
     GcSweepArgs l = a;
     l.lead_split = (int)((l.n_lead + 15) / 16);  // groups of 16 slabs: one workgroup each
     l.lead_chunk = 16;
-    return dispatch_width((l.M + 3) / 4, WidthRange<1, kLaneMaxMembers / 4>{}, [&](auto q) {
-      if (f32)
-        return l.slab_tab ? gc_lane_launch_f32<4 * q, kGcSlab>(l, s)
-                          : l.lead_vert ? gc_lane_launch_f32<4 * q, kGcVloc>(l, s) : gc_lane_launch_f32<4 * q, kGcPlain>(l, s);
-      switch (gc_family(a)) {
-        case kGcAdapt: return gc_lane_launch_one<4 * q, kGcAdapt>(l, s);
-        case kGcVloc: return gc_lane_launch_one<4 * q, kGcVloc>(l, s);
-        case kGcSlab: return gc_lane_launch_one<4 * q, kGcSlab>(l, s);
-        default: return gc_lane_launch_one<4 * q, kGcPlain>(l, s);
-      }
+    return dispatch_family(gc_family(a), [&](auto fam) {
+      constexpr int FAM = fam;
+      return dispatch_width((l.M + 3) / 4, WidthRange<1, kLaneMaxMembers / 4>{}, [&](auto q) {
+        return f32 ? gc_lane_launch<FAM, float, 4 * q>(l, s) : gc_lane_launch<FAM, double, 4 * q>(l, s);
+      });
     });
   }
-  return dispatch_width(sweep_slots(a.M) / 8, SweepChunks{}, [&](auto nc) {
-    switch (gc_family(a)) {
-      case kGcAdapt: return gc_launch<nc, kGcAdapt>(a, s);
-      case kGcVloc: return gc_launch<nc, kGcVloc>(a, s);
-      case kGcSlab: return gc_launch<nc, kGcSlab>(a, s);
-      default: return gc_launch<nc, kGcPlain>(a, s);
-    }
+  return dispatch_family(gc_family(a), [&](auto fam) {
+    constexpr int FAM = fam;
+    return dispatch_width(sweep_slots(a.M) / 8, SweepChunks{}, [&](auto nc) { return gc_launch<FAM, nc>(a, s); });
   });
 }
 

@@ -1,20 +1,22 @@
-// The two one-pass GC sweep kernels, included four times by efa_gcsweep.hip (inside namespace efa::<anonymous>, after the helpers
-// they use): EFA_GCK_QUAD / EFA_GCK_LANE name them, EFA_GCK_ADAPT says whether the adaptive-inflation update (Anderson 2009,
-// DESIGN.md §7c) is fused in and EFA_GCK_VLOC whether the taper carries a factor of each (slab, ob) pair: the vertical factor,
-// evaluated while staging, or with EFA_GCK_SLAB the entry of the slab table S[ob][slab], which holds the product
-// of the vertical, temporal and variable factors.  Separate kernel names rather than a template flag keep the
-// plain kernels' names and code as they were.
-// EFA_GCK_ELEM is the element type of the state rows in memory as the row-per-lane kernel sees them: double, or float for a state
-// stored as float32 (member form only, included with EFA_GCK_LANE_ONLY: the quad kernel has no float32 form).
-// No include guard: this file is meant to be included more than once.
+// The two one-pass GC sweep kernels: k_sweep_gc (quad form) and k_sweep_gc_lane (row-per-lane form).  Included once by
+// efa_gcsweep.hip, inside namespace efa::<anonymous>, after what the kernels use: GcFamily, the launch bounds gc_quad_waves and
+// gc_lane_waves, kBlkCols, kChunk and kChunkL, EFA_GC_COLSPLIT, gc_dot, anderson_update, adapt_ss_after, lane_update and
+// lane_update_prefetch (efa_gcsweep.hip), load_row, store_row, lds_read_row, group_rowsum and group_centered_sumsq (efa_rows.h),
+// lane_dot (efa_lane_dot.h), vert_factor (efa_device.h) and GcSweepArgs (efa_internal.h).
+// FAM is the kernel family (GcFamily): kGcAdapt fuses the adaptive-inflation update in (Anderson 2009); with
+// kGcVloc and kGcSlab the taper carries a factor of each (slab, ob) pair: the vertical factor, evaluated while staging (DESIGN.md
+// §7d), or with kGcSlab the entry of the slab table S[ob][slab], which holds the product of the vertical, temporal and variable
+// factors.
+// E is the element type of the state rows in memory as the row-per-lane kernel sees them: double, or float for a state stored as
+// float32 (member form, no adaptive inflation; the quad kernel has no float32 form).
+#ifndef EFA_GCSWEEP_KERNELS_H
+#define EFA_GCSWEEP_KERNELS_H
 
-#ifndef EFA_GCK_LANE_ONLY
-
-template <int NC, bool VEC, bool FUSED, int RPL>
-__global__ __launch_bounds__(256, EFA_GCK_QUAD_WAVES(NC, RPL)) void EFA_GCK_QUAD(const GcSweepArgs a) {
-  constexpr bool ADAPT = EFA_GCK_ADAPT;
-  constexpr bool VLOC = EFA_GCK_VLOC;
-  constexpr bool SLAB = EFA_GCK_SLAB;  // VLOC with the factor read from the slab table
+template <int FAM, int NC, bool VEC, bool FUSED, int RPL>
+__global__ __launch_bounds__(256, gc_quad_waves(FAM, NC, RPL)) void k_sweep_gc(const GcSweepArgs a) {
+  constexpr bool ADAPT = FAM == kGcAdapt;
+  constexpr bool VLOC = FAM == kGcVloc || FAM == kGcSlab;
+  constexpr bool SLAB = FAM == kGcSlab;  // VLOC with the factor read from the slab table
   static_assert(!(ADAPT && VLOC), "adaptive inflation with vertical localisation is not built");
   static_assert(VLOC || !SLAB, "the slab table is a form of the per-slab factor");
   constexpr int L = 4;
@@ -186,19 +188,17 @@ __global__ __launch_bounds__(256, EFA_GCK_QUAD_WAVES(NC, RPL)) void EFA_GCK_QUAD
   }
 }
 
-#endif  // EFA_GCK_LANE_ONLY
-
-// EFA_GCK_ELEM float: a lane still owns a whole row, loads it with the widest loads its alignment allows (16 bytes when M % 4 == 0
+// E float: a lane still owns a whole row, loads it with the widest loads its alignment allows (16 bytes when M % 4 == 0
 // and the base is 16-byte aligned, else 8 bytes, else 4) widened as they arrive, and rounds each posterior member once at its store; everything between is the float64
 // arithmetic of the double kernel, in its order.
-template <int MP, bool FUSED>  // members padded to a multiple of 4; FUSED: prior members in, posterior members out
-__global__ __launch_bounds__(256, EFA_GCK_LANE_WAVES(MP)) void EFA_GCK_LANE(const GcSweepArgs a) {
-  typedef EFA_GCK_ELEM E;
-  constexpr bool ADAPT = EFA_GCK_ADAPT;
-  constexpr bool VLOC = EFA_GCK_VLOC;
-  constexpr bool SLAB = EFA_GCK_SLAB;  // VLOC with the factor read from the slab table
+template <int FAM, typename E, int MP, bool FUSED>  // members padded to a multiple of 4; FUSED: prior members in, posterior members out
+__global__ __launch_bounds__(256, gc_lane_waves(FAM, MP)) void k_sweep_gc_lane(const GcSweepArgs a) {
+  constexpr bool ADAPT = FAM == kGcAdapt;
+  constexpr bool VLOC = FAM == kGcVloc || FAM == kGcSlab;
+  constexpr bool SLAB = FAM == kGcSlab;  // VLOC with the factor read from the slab table
   static_assert(!(ADAPT && VLOC), "adaptive inflation with vertical localisation is not built");
   static_assert(VLOC || !SLAB, "the slab table is a form of the per-slab factor");
+  static_assert(sizeof(E) == sizeof(double) || (FUSED && !ADAPT), "float32 rows: member form, no adaptive inflation");
   constexpr int NG = (MP + 15) / 16;  // ye registers per lane
   constexpr int YS = 16 * NG;         // padded ye row in LDS (doubles)
   __shared__ __align__(16) double ye_s[kChunkL * YS];
@@ -451,3 +451,5 @@ __global__ __launch_bounds__(256, EFA_GCK_LANE_WAVES(MP)) void EFA_GCK_LANE(cons
     }
   }
 }
+
+#endif  // EFA_GCSWEEP_KERNELS_H

@@ -1,5 +1,5 @@
 // Temporal and cross-variable localisation: the slab-factor table of the one-pass GC sweep's "slab table" family
-// (k_sweep_gc_slab / k_sweep_gc_lane_slab, efa_gcsweep_kernels.h) and the obs-obs taper passes of Phase A.
+// (k_sweep_gc / k_sweep_gc_lane with FAM = kGcSlab, efa_gcsweep_kernels.h) and the obs-obs taper passes of Phase A.
 //
 // k_slab_factor writes S[k][s] = (V(s,k) T(s,k)) C[k, v_s] for every (ob k, slab s): V the vertical factor of §7d (1 when that
 // setting is off), T = GC(|t_s - t_k|, tau_k) (1 when t_s, t_k or tau_k is NaN), C the impact of ob k's obtype on slab s's

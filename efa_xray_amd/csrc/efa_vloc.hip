@@ -1,5 +1,5 @@
 // Vertical localisation: the two obs-obs taper passes of Phase A.  The state rows' factor is fused into the
-// one-pass GC sweep (k_sweep_gc_vloc / k_sweep_gc_lane_vloc, efa_gcsweep_kernels.h).
+// one-pass GC sweep (k_sweep_gc / k_sweep_gc_lane with FAM = kGcVloc, efa_gcsweep_kernels.h).
 //
 // k_obs_taper_vert multiplies the vertical factor into the dense obs-obs table that k_obs_taper_matrix wrote, which the band,
 // Gram and vector-chain Phase-A kernels read: tw[k][j] = GC_h(j, k) * GC(|z_j - z_k|, c_k).  The horizontal value is rounded

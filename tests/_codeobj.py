@@ -50,6 +50,37 @@ def kernel_table(path):
     return {k[".name"]: k for co in code_objects(path) for k in kernels(co)}
 
 
+# The localised kernels' family as their template argument: GcFamily (efa_gcsweep.hip) for the two sweep forms, ImpactFactor
+# (efa_impact.hip) for the impact kernel, which has no adaptive form
+_GC_FAMILY = {"plain": 0, "adapt": 1, "vloc": 2, "slab": 3}
+_IMPACT_FACTOR = {"plain": 0, "vloc": 1, "slab": 2}
+
+
+def gc_kernel_fragment(form, family, elem, *args):
+    """The piece of a mangled name that picks one instantiation of a localised kernel (or, with fewer args, those that begin so):
+      form "quad":   k_sweep_gc<FAM, NC, VEC, FUSED, RPL>          args = NC, VEC, FUSED, RPL   (elem "f64" only)
+      form "lane":   k_sweep_gc_lane<FAM, E, MP, FUSED>            args = MP, FUSED
+      form "impact": k_sweep_gc_lane_impact<MP, FAC, WIDE>         args = MP, WIDE              (elem "f64" only)
+    family is "plain", "adapt", "vloc" or "slab"; elem "f64" or "f32", the rows' element type; bools are given as bools or 0 / 1
+    in the places listed above.  With every arg given the fragment ends with the template list's closing E."""
+    def lit(v, boolean):
+        return "Lb%dE" % int(v) if boolean else "Li%dE" % int(v)
+
+    assert elem in ("f64", "f32") and (form == "lane" or elem == "f64"), (form, elem)
+    if form == "quad":
+        name, full = "k_sweep_gcI", 4
+        parts = [lit(_GC_FAMILY[family], False)] + [lit(v, i in (1, 2)) for i, v in enumerate(args)]
+    elif form == "lane":
+        name, full = "k_sweep_gc_laneI", 2
+        parts = [lit(_GC_FAMILY[family], False), "d" if elem == "f64" else "f"] + [lit(v, i == 1) for i, v in enumerate(args)]
+    else:
+        assert form == "impact" and len(args) >= 1, (form, args)
+        name, full = "k_sweep_gc_lane_impactI", 2
+        parts = [lit(args[0], False), lit(_IMPACT_FACTOR[family], False)] + [lit(v, True) for v in args[1:]]
+    assert len(args) <= full, (form, args)
+    return name + "".join(parts) + ("E" if len(args) == full else "")
+
+
 def vgpr_step(vgprs):
     """The occupancy step of a kernel: with 512 VGPRs per SIMD lane, the smallest of 128 / 168 / 256 / 512 (four, three, two
     waves per SIMD, one) that holds its registers."""

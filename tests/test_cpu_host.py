@@ -40,7 +40,7 @@ def test_baseline_kernels_fit_their_register_budget():
     more waves than two rows of 100 members allow once made configs[3] six times slower without failing any
     parity test), and the persistent Phase-A kernels must fit one workgroup per CU."""
     from efa_xray_amd import _lib
-    from _codeobj import kernel_table
+    from _codeobj import gc_kernel_fragment, kernel_table
     tab = kernel_table(_lib.LIB_PATH)
     assert len(tab) > 100
 
@@ -61,20 +61,20 @@ def test_baseline_kernels_fit_their_register_budget():
         assert k.get(".vgpr_spill_count", 0) == 0, (k[".name"], k[".vgpr_count"], k[".vgpr_spill_count"])
     # configs[2] (80 members, four rows per quad) and configs[3] (100 members, three rows per quad) at two waves per SIMD: only the
     # per-row addresses and means spill, saved and reloaded once per group of slabs (no scratch access in the loop over the obs)
-    assert find("k_sweep_gcILi10ELb1ELb1ELi4E").get(".vgpr_spill_count", 0) <= 32
-    assert find("k_sweep_gcILi13ELb1ELb1ELi3E").get(".vgpr_spill_count", 0) <= 32
+    assert find(gc_kernel_fragment("quad", "plain", "f64", 10, True, True, 4)).get(".vgpr_spill_count", 0) <= 32
+    assert find(gc_kernel_fragment("quad", "plain", "f64", 13, True, True, 3)).get(".vgpr_spill_count", 0) <= 32
     # Phase A: 8 waves of up to 256 registers each; headline (100 members), configs[2] (80, tapered), configs[3] (100, tapered)
     for nm in ("k_pipe_bandILi13ELb0E", "k_pipe_bandILi10ELb1E", "k_pipe_bandILi13ELb1E"):
         band = find(nm)
         assert band.get(".vgpr_spill_count", 0) == 0 and band[".vgpr_count"] <= 256, (nm, band[".vgpr_count"])
     # occupancy the kernels are written for (512 VGPRs per SIMD lane on gfx950)
-    assert find("k_sweep_gcILi8ELb1ELb1ELi2E")[".vgpr_count"] <= 168      # three waves per SIMD
-    assert find("k_sweep_gcILi10ELb1ELb1ELi4E")[".vgpr_count"] <= 256     # two
-    assert find("k_sweep_gcILi13ELb1ELb1ELi3E")[".vgpr_count"] <= 256     # two
+    assert find(gc_kernel_fragment("quad", "plain", "f64", 8, True, True, 2))[".vgpr_count"] <= 168      # three waves per SIMD
+    assert find(gc_kernel_fragment("quad", "plain", "f64", 10, True, True, 4))[".vgpr_count"] <= 256     # two
+    assert find(gc_kernel_fragment("quad", "plain", "f64", 13, True, True, 3))[".vgpr_count"] <= 256     # two
     assert find("k_contract_f32_raILi64E")[".vgpr_count"] <= 256
     # the row-per-lane GC sweep holds a whole row per lane: two waves per SIMD up to 104 members, no spills at configs[2] / configs[3]
     for mp in (80, 100):
-        lane = find("k_sweep_gc_laneILi%dELb1E" % mp)
+        lane = find(gc_kernel_fragment("lane", "plain", "f64", mp, True))
         assert lane.get(".vgpr_spill_count", 0) == 0 and lane[".vgpr_count"] <= 256, (mp, lane[".vgpr_count"])
     # configs[4] at every member count: all eight instantiations of k_contract_f32_ra (KH = 8 .. 64; 196 .. 252 VGPRs when this was
     # written) and the general kernel (196 VGPRs + 64 AGPRs) keep everything in registers: no spill, no scratch

@@ -377,10 +377,9 @@ def test_config2_size_all_obs_on_a_slab():
 def test_adaptive_sweep_fits_its_register_budget():
     """No scratch for the ADAPT lane kernels at configs[2]'s and configs[3]'s member counts (80, 100), both state forms."""
     from efa_xray_amd import _lib
-    from _codeobj import kernel_table
+    from _codeobj import gc_kernel_fragment, kernel_table
     tab = kernel_table(_lib.LIB_PATH)
-    for part in ("k_sweep_gc_lane_adaptILi80ELb1E", "k_sweep_gc_lane_adaptILi80ELb0E",
-                 "k_sweep_gc_lane_adaptILi100ELb1E", "k_sweep_gc_lane_adaptILi100ELb0E"):
+    for part in [gc_kernel_fragment("lane", "adapt", "f64", mp, fused) for mp in (80, 100) for fused in (1, 0)]:
         hits = [k for n, k in tab.items() if part in n]
         assert len(hits) == 1, part
         k = hits[0]

@@ -141,6 +141,31 @@ def test_seeded_both_sweep_forms(M, fused):
     assert not np.array_equal(plain, got)                       # the vertical factor took part
 
 
+@pytest.mark.parametrize("M", [6, 8])
+def test_float32_rows_against_the_helper(M):
+    """The float32 row-per-lane kernel with the vertical factor against the NumPy helper itself (test_gpu_f32_state holds it to the
+    float64 kernels): 20 columns (a full and a partial column block), 3 slabs (one folded group), 40 obs of which a fifth are not
+    assimilated; M = 6 (padded to 8: the masked loads) and M = 8; the rows at a 16-byte aligned base and at one that is only
+    8-byte aligned.  Bound: that of test_gpu_f32_state, half a float32 ulp of the one rounding plus the float64 tolerance."""
+    import test_gpu_f32_state as f32t
+    ctx = _ctx()
+    shape = (1, 3, 4, 5)
+    pb = f32t.Problem(4000 + M, M, 40, n_lead=3, ny=4, nx=5, gc=True)
+    g = dict(ob_value=pb.value, ob_error=pb.error, ob_assim=pb.assim, ob_lat=pb.ob_lat, ob_lon=pb.ob_lon, ob_radius=pb.hw,
+             grid_lat=pb.glat.reshape(4, 5), grid_lon=pb.glon.reshape(4, 5))
+    vert = _vertical(3, pb.P, seed=M, nan_slab=False)
+    ref = _helper(pb.X64, pb.HX, g, shape, *vert)[0]
+    assert np.max(np.abs(ref - _helper(pb.X64, pb.HX, g, shape, None, None, None)[0])) > 1e-3   # the factor matters on this case
+    ctx.set_vertical_localization(*vert)
+    try:
+        for offset in (0, 2):
+            post, _, _, native = f32t._run(pb, True, offset=offset, ctx=ctx)
+            assert native == 1 and ctx.get_option("gc_family") == 2
+            f32t._assert_reference_bound(post, ref, "vertical float32 M=%d offset=%d" % (M, offset))
+    finally:
+        ctx.set_vertical_localization(None)
+
+
 @pytest.mark.parametrize("kind", [("band", 2, 1), ("gram", 1, 1), ("chain", 0, 1), ("batch", 2, 0)])
 def test_every_phase_a_kind(kind):
     name, gram, pipe = kind
@@ -367,11 +392,11 @@ def test_context_refuses_unsupported_combinations():
 def test_vertical_kernels_register_budget():
     """No spills for the lane form at configs[2]'s and configs[3]'s member counts (80, 100), both state forms."""
     from efa_xray_amd import _lib
-    from _codeobj import kernel_table
+    from _codeobj import gc_kernel_fragment, kernel_table
     tab = kernel_table(_lib.LIB_PATH)
     for mp in (80, 100):
         for fused in (0, 1):
-            hits = [k for n, k in tab.items() if "k_sweep_gc_lane_vlocILi%dELb%dE" % (mp, fused) in n]
+            hits = [k for n, k in tab.items() if gc_kernel_fragment("lane", "vloc", "f64", mp, fused) in n]
             assert len(hits) == 1
             k = hits[0]
             assert k.get(".vgpr_spill_count", 0) == 0 and k.get(".private_segment_fixed_size", 0) == 0, (mp, fused, k[".vgpr_count"])

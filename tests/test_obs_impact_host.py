@@ -161,15 +161,21 @@ def test_impact_kernels_fit_their_register_budget():
     """No vector spills in any instantiation of the localised kernel; two waves per SIMD (<= 256 registers) up to 96 members, as
     its launch bounds say, and the configs[2] width (80 members) with room to spare."""
     from efa_xray_amd import _lib
-    from _codeobj import kernel_table
-    tab = dict((n, k) for n, k in kernel_table(_lib.LIB_PATH).items() if "k_sweep_gc_lane_impact" in n)
-    assert len(tab) == 2 * 26 + 2            # 4 .. 104 members, plain and vertical; the pieces of 64 above
-    for n, k in tab.items():
+    from _codeobj import gc_kernel_fragment, kernel_table
+    lib = kernel_table(_lib.LIB_PATH)
+    shapes = [(mp, False) for mp in range(4, 105, 4)] + [(64, True)]   # 4 .. 104 members; the pieces of 64 above
+    tab = {}
+    for fam in ("plain", "vloc"):
+        for mp, wide in shapes:
+            (n,) = [n for n in lib if gc_kernel_fragment("impact", fam, "f64", mp, wide) in n]
+            tab[n] = (mp, lib[n])
+    assert len(tab) == 2 * 26 + 2            # plain and vertical; with the slab table's 26 + 1 that is every instantiation
+    assert len([n for n in lib if "k_sweep_gc_lane_impact" in n]) == 2 * 26 + 2 + 26 + 1
+    for n, (mp, k) in tab.items():
         assert k.get(".vgpr_spill_count", 0) == 0 and k.get(".private_segment_fixed_size", 0) == 0, (n, k[".vgpr_count"])
-        mp = int(n.split("k_sweep_gc_lane_impactILi")[1].split("E")[0])
         if mp <= 96:
             assert k[".vgpr_count"] <= 256, (n, k[".vgpr_count"])
         assert 2 * k[".group_segment_fixed_size"] <= 160 * 1024, (n, k[".group_segment_fixed_size"])
-    for vl in "01":
-        (k,) = [k for n, k in tab.items() if "ILi80ELb%sELb0E" % vl in n]
+    for fam in ("plain", "vloc"):
+        (k,) = [k for n, (mp, k) in tab.items() if gc_kernel_fragment("impact", fam, "f64", 80, False) in n]
         assert k[".vgpr_count"] <= 232

@@ -110,19 +110,21 @@ def test_slab_impact_kernels_fit_their_register_budget():
     256 registers up to 96 members (two waves per SIMD, as the launch bounds say), two workgroups of LDS per CU; the plain and the
     vertical form keep their 54."""
     from efa_xray_amd import _lib
-    from _codeobj import kernel_table
+    from _codeobj import gc_kernel_fragment, kernel_table
     tab = kernel_table(_lib.LIB_PATH)
-    slab = dict((n, k) for n, k in tab.items() if "k_impact_gc_lane_slab" in n)
+    slab = {}
+    for mp, wide in [(mp, False) for mp in range(4, 105, 4)] + [(64, True)]:
+        (n,) = [n for n in tab if gc_kernel_fragment("impact", "slab", "f64", mp, wide) in n]
+        slab[n] = (mp, tab[n])
     assert len(slab) == 26 + 1
-    assert len([n for n in tab if "k_sweep_gc_lane_impact" in n]) == 2 * 26 + 2
+    assert len([n for n in tab if "k_sweep_gc_lane_impact" in n]) == 2 * 26 + 2 + len(slab)
     widths = set()
-    for n, k in slab.items():
+    for n, (mp, k) in slab.items():
         assert k.get(".vgpr_spill_count", 0) == 0 and k.get(".private_segment_fixed_size", 0) == 0, (n, k[".vgpr_count"])
-        mp = int(n.split("k_impact_gc_lane_slabILi")[1].split("E")[0])
         widths.add(mp)
         if mp <= 96:
             assert k[".vgpr_count"] <= 256, (n, k[".vgpr_count"])
         assert 2 * k[".group_segment_fixed_size"] <= 160 * 1024, (n, k[".group_segment_fixed_size"])
     assert widths == set(range(4, 105, 4))
-    (k,) = [k for n, k in slab.items() if "ILi80ELb0E" in n]
+    (k,) = [k for n, (mp, k) in slab.items() if gc_kernel_fragment("impact", "slab", "f64", 80, False) in n]
     assert k[".vgpr_count"] <= 232                                            # the budget 7i gives the configs[2] width

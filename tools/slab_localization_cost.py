@@ -4,9 +4,9 @@ Times efa_ensrf_cycle_dev in ONE process, alternating four variants round by rou
 round), on the configs[2]-like cycle of tools/vertical_localization_cost.py: 4 variables x 37 levels x 361 x 720 rows x 80 members
 x 5 000 obs, GC 1 000 km, the levels on the time slot with ln p as the slabs' vertical coordinate (one scale height as half-width):
 
-  off        no per-slab factor: the plain one-pass sweep (k_sweep_gc_lane)
-  vert       vertical localisation only: the vertical family (k_sweep_gc_lane_vloc), the factor evaluated while staging
-  slab_vert  the slab-table family (k_sweep_gc_lane_slab) fed the same vertical factors and nothing else: a temporal part whose
+  off        no per-slab factor: the plain one-pass sweep (k_sweep_gc_lane, family 0)
+  vert       vertical localisation only: the vertical family (k_sweep_gc_lane, family 2), the factor evaluated while staging
+  slab_vert  the slab-table family (k_sweep_gc_lane, family 3) fed the same vertical factors and nothing else: a temporal part whose
              every factor is exactly 1 (slabs without a time, all obs at one time) keeps the setting active
   slab_all   slab_vert plus a temporal factor (the slab index as time, tau a quarter of the span) and a variable factor (the last
              variable takes impact 0 from every other obtype)

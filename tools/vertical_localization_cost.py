@@ -5,7 +5,7 @@ and on with one scale height in ln p ("tight"), in ONE process, alternating the 
 per variant and round), on a configs[2]-like cycle: 4 variables x 37 levels x 361 x 720 rows x 80 members x 5 000 obs, GC
 1 000 km, the levels on the time slot with ln p (1000 .. 10 hPa) as the slabs' coordinate and every fourth-variable surface
 slab NaN.  The state phase (HIP events, "timing" 2) is reported per variant: off it is the plain one-pass sweep
-(k_sweep_gc_lane), on it is k_sweep_gc_lane_vloc.  "skipped_pairs" is the fraction of (group of 16 slabs, ob) pairs none of whose
+(k_sweep_gc_lane, family 0), on it is family 2 of the same kernel.  "skipped_pairs" is the fraction of (group of 16 slabs, ob) pairs none of whose
 slabs is within an ob's vertical reach: the share of (wave, ob) pairs of the lane form that the vertical factor removes on top of
 the horizontal skipping (from the geometry, on the host).
 
