@@ -184,6 +184,209 @@ def test_coverage_counting_notices_a_missing_transition():
     n = coverage([[s for s in S.make_plan(3, 6, big_p=False) if not s["refusal"]]])
     assert n["P beyond one persistent launch"] == 0 and n["refused after obs_phase began"] == 0
     assert sum(v == 0 for k, v in n.items() if k.startswith("entry ")) >= 44
+    # the second generation: a few steps without refusals and bystanders; then the committed plans without the steps that
+    # change one ob's tau
+    n = coverage2([S.make_plan2(45, 4, 0, refusals=False)])
+    assert n["keeps sl_off_on"] == 0 and n["refusal sl_unloc"] == 0 and n["gram between steps of one geometry"] == 0
+    assert sum(v == 0 for k, v in n.items() if k.startswith("entry ")) >= 70
+    full = S.plans2()
+    cut = [[s for s in plan if s["keep"] != "sl_tau"] for plan in full]
+    assert coverage2(full)["keeps sl_tau"] >= NEED["keeps sl_tau"] > coverage2(cut)["keeps sl_tau"] == 0
+
+
+# ---- the second generation: the slab setting, float32 rows, the streamed cycle, the calls between the steps ------------------
+@pytest.fixture(scope="module")
+def plans2():
+    return S.plans2()
+
+
+PINNED2 = {(45, 41, 0): "ad26392af88c5f2a05f37e0e3cb93cf557a4071accbcd08661a91485cbe5d0f7",
+           (48, 42, 40): "1ac238fdd57325337e30620c293255c2c4ee33276302bd44d47f2a5c77c4d858"}
+
+
+def test_the_second_generation_is_the_same_on_any_machine(plans2):
+    import hashlib
+    assert sorted(PINNED2) == sorted(S.PLANS2)
+    for key, plan in zip(S.PLANS2, plans2):
+        assert hashlib.sha256("\n".join(S.describe(s) for s in plan).encode()).hexdigest() == PINNED2[key], \
+            "plan %r changed: a step number quoted anywhere no longer names the same step" % (key,)
+        assert len(_valid(plan)) == key[1]
+        again = S.make_plan2(*key)
+        assert S.plan_hash([dict(s, after=()) for s in plan]) == S.plan_hash(again)
+
+
+def test_a_first_generation_step_hashes_as_before_the_new_keys():
+    """plan_hash skips a second-generation key at its default: the digest of a plan is that of its steps without those keys."""
+    plan = S.make_plan(5, 8, big_p=False)
+    old = [{k: v for k, v in s.items() if k not in S.NEW_DEFAULTS} for s in plan]
+    assert S.plan_hash(plan) == S.plan_hash(old)
+    assert S.plan_hash([dict(plan[0], elem="f32")]) != S.plan_hash(plan[:1])
+
+
+def test_every_step_of_the_second_generation_is_legal(plans2):
+    for plan in plans2:
+        for i, s in enumerate(plan):
+            assert s["index"] == i
+            S.check_legal(s)
+            assert s["redraws"] <= S.REDRAW_MAX, "%s needed more than %d redraws" % (S.describe(s), S.REDRAW_MAX)
+            assert len(s["after"]) <= 2
+            if s["refusal"]:
+                continue
+            assert S.clear(s), S.describe(s)
+            c = s["case"]
+            assert c["X"].shape == (c["N"], c["M"]) and c["HX"].shape == (c["P"], c["M"]) and c["P"] < S.BIG_P
+            assert np.array_equal(c["X"][c["rows"]], c["HX"])
+            assert all(S.bystander_legal(s, b) for b in s["after"])
+            if c["loc"]:
+                nvar, nt = c["state_shape"][:2]
+                assert 1 <= nvar * nt <= 6 and nvar * nt == c["n_lead"] and 17 <= c["lat"].size <= 400
+            if s["sl"] is not None and "lead_time" in s["sl"]:
+                assert np.array_equal(s["sl"]["lead_time"], np.tile(S.SL_STEP * np.arange(nt), nvar))
+            if s["sl"] is not None and "impact" in s["sl"]:
+                assert np.array_equal(s["sl"]["lead_var"], np.repeat(np.arange(nvar), nt))
+
+
+def test_a_kept_slab_step_changes_exactly_what_it_names(plans2):
+    for plan in plans2:
+        steps = _valid(plan)
+        for p, s in zip(steps, steps[1:]):
+            if s["keep"] not in S.SL_KEEP_KINDS:
+                continue
+            a, b, c, pc = p["sl"], s["sl"], s["case"], p["case"]
+            for key in ("ob_lat", "ob_lon", "hw", "asm", "lat", "lon"):
+                assert np.array_equal(c[key], pc[key]), (S.describe(s), key)
+            differ = [k for k in a if k in b and not np.array_equal(a[k], b[k], equal_nan=True)]
+            want = dict(sl_same=[], sl_off_on=[], vl_under_sl=[], sl_tau=["ob_time_halfwidth"], sl_time=["ob_time"],
+                        sl_impact=["impact"], sl_group=["ob_group"])
+            if s["keep"] == "sl_ones":
+                assert not S.slab_has_factors(b) and np.all(S.slab_table(dict(s, vl=None)) == 1.0)
+                continue
+            assert sorted(a) == sorted(b) and differ == want[s["keep"]], S.describe(s)
+            for k in differ:
+                assert int(np.sum(~((a[k] == b[k]) | (np.isnan(a[k]) & np.isnan(b[k]))))) == 1, S.describe(s)
+            same_vl = all(np.array_equal(x, y, equal_nan=True) for x, y in zip(p["vl"] or (), s["vl"] or ()))
+            assert (p["vl"] is None) == (s["vl"] is None)
+            if s["keep"] == "vl_under_sl":
+                assert not same_vl and np.array_equal(p["vl"][0], s["vl"][0], equal_nan=True) and \
+                    np.array_equal(p["vl"][1], s["vl"][1], equal_nan=True)
+            else:
+                assert same_vl
+
+
+POSITIONS = ("after a slab step", "before a slab step", "between steps of one geometry")
+NEED = {"keeps " + k: 2 for k in S.SL_KEEP_KINDS}      # counts that must reach more than 1
+
+
+def coverage2(plans):
+    """Counts of what the second-generation plans contain, by name."""
+    n = {}
+
+    def hit(key):
+        n[key] = n.get(key, 0) + 1
+    for a, b in itertools.product(S.FEATURES2, S.FEATURES2):
+        if {a, b} != {"ai", "sl"}:
+            n["%s then %s" % (a, b)] = 0
+    for a, b in itertools.product(S.ENTRIES2, S.ENTRIES2):
+        n["entry %s -> %s" % (a, b)] = 0
+    for k in S.SL_KEEP_KINDS:
+        n["keeps " + k] = 0
+    for k in S.KEEP_KINDS[1:]:
+        n["keeps %s under the slab setting" % k] = 0
+    for b in S.BYSTANDERS:
+        for pos in POSITIONS:
+            n["%s %s" % (b, pos)] = 0
+    for k in S.REFUSALS2:
+        n["refusal " + k] = 0
+    for key in ("sl with vl", "sl without vl", "sl time part only", "sl variable part only", "sl both parts", "sl without a factor",
+                "sl switched on", "sl switched off", "sl then plain GC", "sl then unlocalised", "sl after the outlier check rejected",
+                "state_cycle_f32 in place", "state_cycle_f32 out of place", "host_streamed f32", "host_streamed f64",
+                "host_streamed GC", "host_streamed unlocalised", "host_streamed under sl", "f32 under sl", "f32 with relaxation",
+                "f32 above 136 members", "f32 up to 104 members", "f32 then f64 on one geometry", "f64 then f32 on one geometry",
+                "resident GC after host_streamed on one grid"):
+        n[key] = 0
+    for v in S.CHUNK_COLS:
+        n["chunk_cols %s" % v] = 0
+    names = dict(zip(("after sl", "before sl", "same geometry"), POSITIONS))
+    for plan in plans:
+        for s in plan:
+            if s["refusal"]:
+                hit("refusal " + s["refusal"])
+        steps, positions = S._bystander_positions(plan)
+        for i, (s, pos) in enumerate(zip(steps, positions)):
+            c = s["case"]
+            for b in s["after"]:
+                for p in S.bystander_positions_of(b, pos):
+                    hit("%s %s" % (b, names[p]))
+            sl = s["sl"]
+            if sl is not None:
+                hit("sl with vl" if s["vl"] is not None else "sl without vl")
+                hit("sl both parts" if "lead_time" in sl and "impact" in sl else
+                    "sl time part only" if "lead_time" in sl else "sl variable part only")
+                if not S.slab_has_factors(sl):
+                    hit("sl without a factor")
+                if s["entry"] == "host_streamed":
+                    hit("host_streamed under sl")
+                if s["elem"] == "f32":
+                    hit("f32 under sl")
+            if s["entry"] == "state_cycle_f32":
+                hit("state_cycle_f32 in place" if s["in_place"] else "state_cycle_f32 out of place")
+            if s["entry"] == "host_streamed":
+                hit("host_streamed " + s["elem"])
+                hit("host_streamed GC" if c["loc"] else "host_streamed unlocalised")
+                hit("chunk_cols %s" % s["chunk_cols"])
+            if s["elem"] == "f32":
+                if s["relax"]:
+                    hit("f32 with relaxation")
+                hit("f32 above 136 members" if c["M"] > 136 else "f32 up to 104 members" if c["M"] <= 104 else "f32 other")
+            if i == 0:
+                continue
+            p = steps[i - 1]
+            hit("entry %s -> %s" % (p["entry"], s["entry"]))
+            for a, b in itertools.product(S.FEATURES2, S.FEATURES2):
+                if p[a] is not None and s[b] is not None:
+                    hit("%s then %s" % (a, b))
+            if s["keep"] in S.SL_KEEP_KINDS:
+                hit("keeps " + s["keep"])
+            elif s["keep"] != "new" and p["sl"] is not None and sl is not None:
+                hit("keeps %s under the slab setting" % s["keep"])
+            if p["sl"] is None and sl is not None:
+                hit("sl switched on")
+            if p["sl"] is not None and sl is None:
+                hit("sl switched off")
+                if all(s[f] is None for f in S.FEATURES2):
+                    hit("sl then plain GC" if c["loc"] else "sl then unlocalised")
+            if sl is not None and s["keep"] != "new" and p["qc"] is not None and not np.array_equal(S.flags(p), p["case"]["asm"]):
+                hit("sl after the outlier check rejected")
+            if s["keep"] in S.SAME_GEOMETRY and p["elem"] != s["elem"]:
+                hit("%s then %s on one geometry" % (p["elem"], s["elem"]))
+            if p["entry"] == "host_streamed" and s["entry"] != "host_streamed" and c["loc"] and s["keep"] in S.SAME_GEOMETRY + ["flag"]:
+                hit("resident GC after host_streamed on one grid")
+    n.pop("f32 other", None)
+    return n
+
+
+def test_the_second_generation_covers_every_transition(plans2):
+    n = coverage2(plans2)
+    missing = sorted("%s (%d)" % (k, v) for k, v in n.items() if v < NEED.get(k, 1))
+    assert not missing, "the plans %r no longer contain: %s" % (S.PLANS2, "; ".join(missing))
+    # together the two plans walk the Euler circuit of the nine entry points once
+    assert all(v == 1 for k, v in n.items() if k.startswith("entry ")), "an ordered pair of entry points occurs twice"
+
+
+def test_the_slab_factors_take_part_in_the_second_generation(plans2):
+    """At least a third of the steps under the slab setting have a factor different from 1 on an ob that is assimilated (the table
+    of _slabloc.slab_factor_table, the vertical factor left out), and at least one has none."""
+    with_factor, without = 0, 0
+    for plan in plans2:
+        for s in _valid(plan):
+            if s["sl"] is None:
+                continue
+            tab = S.slab_table(dict(s, vl=None))
+            took = bool(np.any(tab[S.flags(s)] != 1.0))
+            with_factor += took
+            without += not took
+            assert took or not S.slab_has_factors(s["sl"]) or not np.any(tab[S.flags(s)] != 1.0)
+    assert without >= 1 and 3 * with_factor >= with_factor + without, (with_factor, without)
 
 
 # ---- the model against the helpers it is made of ---------------------------------------------------------------------------
@@ -291,3 +494,61 @@ def test_model_order_of_the_features():
     m = S.model(s)
     _same(m, relax(Xi, post, rtps=0.5), None, None, diag)
     assert np.array_equal(m["field"], fnew) and not m["diag"]["assimilated"][idx].any()
+
+
+# ---- the model under the slab setting -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("with_vl", [False, True], ids=["plain", "vl"])
+def test_model_with_a_slab_setting_without_factors_is_the_model_without_it(with_vl):
+    import _slabloc
+    g = load_golden("G8")
+    c = S.golden_case(g)
+    nvar, nt = c["state_shape"][:2]
+    vl = S.vertical(np.random.default_rng(3), c["n_lead"], c["P"]) if with_vl else None
+    ones = S.slab_ones(nvar, nt, c["P"])
+    assert not S.slab_has_factors(ones) and S.gc_family(S.make_step(c, vl=vl, sl=ones)) == (2 if with_vl else 0)
+    off = S.model(S.make_step(c, vl=vl))
+    _same(S.model(S.make_step(c, vl=vl, sl=ones)), off["post"], off["xam"], off["Xap"], off["diag"])
+    if with_vl:
+        xbm, Xbp = orc.format_prior_state(c["X"], c["HX"])
+        xam, Xap, diag = _vertloc.ensrf_update_vert(xbm, Xbp, c["N"], c["val"], c["err"], c["asm"], c["ob_lat"], c["ob_lon"], c["hw"],
+                                                    c["lat"], c["lon"], c["state_shape"], lead_vert=vl[0], ob_vert=vl[1],
+                                                    ob_vert_halfwidth=vl[2], obs_taper="loop" if c["P"] <= 128 else "vector")
+        _same(off, orc.format_posterior_state(xam, Xap, c["N"]), xam, Xap, diag)
+    assert np.all(_slabloc.slab_factor_table(c["n_lead"], c["P"], **{k: v for k, v in S.slab_arrays(ones).items() if k != "ob_var"}) == 1.0)
+
+
+@pytest.mark.parametrize("name", ["G5", "G8"])
+def test_model_with_the_slab_setting_only(name):
+    import _slabloc
+    g = load_golden(name)
+    c = S.golden_case(g)
+    nvar, nt = c["state_shape"][:2]
+    sl = S.slab_setting(np.random.default_rng(4), nvar, nt, c["P"])
+    s = S.make_step(c, sl=sl)
+    assert S.slab_has_factors(sl) and S.gc_family(s) == 3
+    xbm, Xbp = orc.format_prior_state(c["X"], c["HX"])
+    xam, Xap, diag = _slabloc.ensrf_update_slab(xbm, Xbp, c["N"], c["val"], c["err"], c["asm"], c["ob_lat"], c["ob_lon"], c["hw"], c["lat"],
+                                                c["lon"], c["state_shape"], obs_taper="loop" if c["P"] <= 128 else "vector",
+                                                **S.slab_arrays(sl))
+    m = S.model(s)
+    _same(m, orc.format_posterior_state(xam, Xap, c["N"]), xam, Xap, diag)
+    assert not np.array_equal(m["post"], S.model(S.make_step(c))["post"])       # the factors took part
+    # the outlier decision and relaxation compose around it as they do without it
+    c2 = dict(c)
+    c2["val"], idx = _outlier.inject(c["HX"], c["val"], c["err"], c["asm"], 3.0, 3, seed=1)
+    s2 = S.make_step(c2, sl=sl, qc=3.0, relax=("rtps", 0.5))
+    assert S.clear(s2)
+    asm = _outlier.masked_flags(c["HX"], c2["val"], c["err"], c["asm"], 3.0)
+    xam, Xap, diag = _slabloc.ensrf_update_slab(xbm, Xbp, c["N"], c2["val"], c["err"], asm, c["ob_lat"], c["ob_lon"], c["hw"], c["lat"],
+                                                c["lon"], c["state_shape"], obs_taper="loop" if c["P"] <= 128 else "vector",
+                                                **S.slab_arrays(sl))
+    _same(S.model(s2), relax(c["X"], orc.format_posterior_state(xam, Xap, c["N"]), rtps=0.5), xam, Xap, diag)
+
+
+def test_a_float32_case_holds_what_the_rows_widen_to():
+    c = S.to_f32(S.new_case(7, 300, 20, 40, False))
+    assert np.array_equal(c["X"], c["X"].astype(np.float32).astype(np.float64)) and np.array_equal(c["X"][c["rows"]], c["HX"])
+    with pytest.raises(AssertionError):
+        S.make_step(S.new_case(7, 300, 20, 40, False), entry="state_cycle_f32", elem="f32")     # not rounded
+    with pytest.raises(AssertionError):
+        S.make_step(c, entry="cycle_out", elem="f32")                                          # no float32 form of this entry

@@ -6,7 +6,15 @@ transform, the per-feature settings -- is exercised by plans of steps (tests/_se
 checked two ways: against `model(step)` to the suite's tolerance (assert_parity, 1e-10 of the array's scale; 1e-10 relative for
 the inflation field), and bit for bit against the same step on a fresh context that is created for it and closed after it.
 
-Replay of a failing step: run_plan(seed, length, only=range(i - 3, i + 1))."""
+The second generation of plans (S.plans2) adds the slab setting, float32 rows, the streamed host cycle and calls of the impact,
+diagnostic and helper entry points between the steps.  A float32 step is held to the model under the bound of
+test_gpu_f32_state (one rounding) and to its fresh context bit for bit; a streamed step also to the resident cycle of the same
+step on the fresh context, bit for bit; after a GC step that ran the one-pass sweep, option "gc_family" must be the
+family the step's arrays imply; the calls between the steps are compared with the fresh context's bit for bit, the impact calls
+and the factor table with their NumPy helpers as well.
+
+Replay of a failing step: run_plan(seed, length, only=range(i - 3, i + 1)); run_steps(S.plans2()[k], only=...) for the second
+generation."""
 import numpy as np
 import pytest
 
@@ -18,7 +26,7 @@ pytestmark = pytest.mark.gpu
 
 FIELD_RTOL = 1e-10            # the inflation field, relative (test_gpu_outlier_qc.py)
 KIND_DIFF_MAX = 0.02          # share of a plan's steps whose used and fresh context may differ in phase_a_kind (spin fall-back)
-DEFAULTS = dict(relax=None, qc=None, ai=None, vl=None, path=0, obs_batch=64, phase_a="band", gc_onepass=1, geometry_reuse=1,
+DEFAULTS = dict(relax=None, qc=None, ai=None, vl=None, sl=None, path=0, obs_batch=64, phase_a="band", gc_onepass=1, geometry_reuse=1,
                 timing=0, stream="own")
 DIAG_KEYS = ("prior_mean", "prior_var", "post_mean", "post_var")
 
@@ -44,10 +52,27 @@ def dev(a):
     return t
 
 
+def dev32(a):
+    """The same for float32 rows."""
+    torch = _torch()
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    t = torch.zeros((max(a.shape[0], 1),) + a.shape[1:], dtype=torch.float32, device="cuda:0")
+    if a.shape[0]:
+        t[:a.shape[0]].copy_(torch.from_numpy(a))
+    torch.cuda.synchronize()
+    return t
+
+
 def host(ctx, t, n):
     """The first n rows of a device tensor, once the context's stream is done."""
     ctx.synchronize()
     return t[:n].cpu().numpy()
+
+
+def ctx_array(made, ctx, a):
+    """A device array of the context holding `a`, added to the list its caller frees."""
+    made.append(ctx.to_device(np.ascontiguousarray(a, dtype=np.float64)))
+    return made[-1]
 
 
 def same_value(a, b):
@@ -64,8 +89,8 @@ def same_value(a, b):
 
 class Runner(object):
     """Drives one context through steps.  Settings are sent to the context only when they differ from what it holds (a setting
-    that leaks into the next cycle then shows), except the vertical arrays and the inflation field, which are handed over again
-    whenever they are on."""
+    that leaks into the next cycle then shows), except the vertical arrays, the slab arrays and the inflation field, which are
+    handed over again whenever they are on (keep "sl_off_on": cleared first)."""
 
     def __init__(self, ctx, caller_stream=None, read_timing=True):
         self.ctx = ctx
@@ -105,6 +130,12 @@ class Runner(object):
             ctx.set_vertical_localization(*s["vl"])
         elif have["vl"] is not None:
             ctx.set_vertical_localization(None)
+        if s["sl"] is not None:
+            if s.get("keep") == "sl_off_on":
+                ctx.set_slab_localization(None)
+            ctx.set_slab_localization(**s["sl"])
+        elif have["sl"] is not None:
+            ctx.set_slab_localization(None)
         for key in DEFAULTS:
             have[key] = s[key]
 
@@ -146,6 +177,19 @@ class Runner(object):
             xbm, Xbp = np.ascontiguousarray(xbm), np.ascontiguousarray(Xbp)
             out["diag"] = ctx.ensrf_update_host(xbm, Xbp, N, c["val"], c["err"], c["asm"], **dict(okw, **gkw))
             out.update(post=orc.format_posterior_state(xbm, Xbp, N), ym=xbm[N:].copy(), Yp=Xbp[N:].copy())
+        elif entry == "host_streamed":
+            out.update(self.streamed(s))
+        elif entry == "state_cycle_f32":
+            X = dev32(c["X"])
+            Yp, ym = dev(c["HX"]), dev(np.zeros(P))
+            if P:
+                ctx.form_perts(P, M, Yp.data_ptr(), ym.data_ptr(), Yp.data_ptr())
+            post = X if s["in_place"] else dev32(np.full((N, M), 9.0))
+            out["diag"] = ctx.obs_phase(M, P, ym.data_ptr(), Yp.data_ptr(), c["val"], c["err"], c["asm"], **okw)
+            ctx.state_cycle_f32(N, M, X.data_ptr(), post.data_ptr(), **gkw)
+            out.update(post=host(ctx, post, N), ym=host(ctx, ym, P), Yp=host(ctx, Yp, P))
+            if not s["in_place"]:
+                assert np.array_equal(host(ctx, X, N), c["X"].astype(np.float32)), "the float32 prior was written"
         else:
             X = dev(c["X"])
             if s["ai"] is not None:              # prior inflation on the device, the forward operator on the inflated prior
@@ -204,7 +248,148 @@ class Runner(object):
             out["path"], out["launches"] = (t["path"], t["state_launches"]) if N and P else (0, 0)
         else:
             out["path"], out["launches"] = None, None
+        if c["loc"] and s["gc_onepass"] == 1 and N and np.any(out["diag"]["assimilated"]):
+            # the state phase ran the one-pass sweep: the kernel family is the one the step's arrays imply
+            fam = int(ctx.get_option("gc_family"))
+            assert fam == S.gc_family(s), "gc_family %d, the step's settings imply %d" % (fam, S.gc_family(s))
+            out["pairs"] = int(ctx.get_option("gc_active_pairs"))
+        out["after"] = dict((b, self.bystander(b, s, out)) for b in s.get("after", ()))
         return out
+
+    def streamed(self, s):
+        """efa_ensrf_cycle_host(_f32): the state in host memory, one segment per variable, pinned and ordinary arrays in turn."""
+        ctx, c = self.ctx, s["case"]
+        N, M, P = c["N"], c["M"], c["P"]
+        dt = np.float32 if s["elem"] == "f32" else np.float64
+        nvar = c["state_shape"][0] if c["loc"] else 1
+        nt = c["n_lead"] // nvar
+        ncol = N // c["n_lead"]
+        X3 = c["X"].astype(dt).reshape(c["n_lead"], ncol, M)
+        prior, post = [], []
+        for v in range(nvar):
+            seg = X3[v * nt:(v + 1) * nt]
+            a, b = (ctx.pinned_empty(seg.shape, dt), ctx.pinned_empty(seg.shape, dt)) if v % 2 == 0 else \
+                (np.empty(seg.shape, dtype=dt), np.empty(seg.shape, dtype=dt))
+            a[...] = seg
+            b[...] = 9.0
+            prior.append(a)
+            post.append(b)
+        chunk = ncol + 5 if s["chunk_cols"] == "all" else s["chunk_cols"]
+        kw = self.ob_kw(c)
+        if c["loc"]:
+            kw.update(grid_lat=c["lat"].reshape(-1), grid_lon=c["lon"].reshape(-1))
+        diag = ctx.ensrf_cycle_host(prior, post, ncol, M, c["HX"] if P else None, chunk, c["val"], c["err"], c["asm"], **kw)
+        for v in range(nvar):
+            assert np.array_equal(prior[v], X3[v * nt:(v + 1) * nt]), "the streamed cycle wrote to its prior"
+        return dict(diag=diag, post=np.concatenate([b.reshape(-1, M) for b in post]).copy())
+
+    def bystander(self, name, s, out):
+        """One call between this step and the next.  The impact calls and the factor table work on the step's posterior and
+        settings and are checked against their NumPy helpers here; the others on a small state of their own.  Returns what the
+        call gave, for the comparison with the fresh context."""
+        import _efso
+        import _efso_slab
+        import _slabloc
+        ctx, c = self.ctx, s["case"]
+        N, M, P = c["N"], c["M"], c["P"]
+        rng = np.random.default_rng([s["index"], (S.BYSTANDERS + S.DIRECTED_BYSTANDERS).index(name)])
+        if name in ("obs_impact", "obs_impact_slab"):
+            Xf = np.asarray(out["post"], dtype=np.float64)
+            Ya = S.forward(c)(Xf)
+            werr = rng.standard_normal(N)
+            werr[::7] = 0.0
+            innov = c["val"] - c["HX"].mean(axis=1)
+            used = np.asarray(out["diag"]["assimilated"], dtype=bool)
+            Xd, wd, Yd = ctx.to_device(Xf), ctx.to_device(werr), ctx.to_device(Ya)
+            try:
+                J = getattr(ctx, name)(N, M, P, Xd, wd, Yd, innov, c["err"], used, **dict(self.ob_kw(c), **self.grid_kw(c)))
+            finally:
+                for d in (Xd, wd, Yd):
+                    d.free()
+            geo = dict(grid_lat=c["lat"], grid_lon=c["lon"], ob_lat=c["ob_lat"], ob_lon=c["ob_lon"], ob_halfwidth=c["hw"],
+                       n_lead=c["n_lead"]) if c["loc"] else {}
+            if s["vl"] is not None:
+                geo.update(lead_vert=s["vl"][0], ob_vert=s["vl"][1], ob_vert_halfwidth=s["vl"][2])
+            if s["sl"] is not None:
+                kw = S.slab_arrays(s["sl"])
+                kw.pop("ob_var", None)
+                ref, A = _efso_slab.efso_slab(Xf, Ya, werr, innov, c["err"], used, **dict(geo, **kw))
+            else:
+                ref, A = _efso.efso(Xf, Ya, werr, innov, c["err"], used, **geo)
+            tol = _efso.tolerance(N, M)
+            assert np.all(np.abs(J - ref) <= tol * A), "%s after the step: worst |J - ref| / A = %.3e (bound %.3e)" % (
+                name, float(np.max(np.abs(J - ref) / np.where(A > 0, A, 1.0))), tol)
+            assert np.all(J[~used] == 0.0)
+            return J
+        if name == "obs_impact_slab_other_vl":
+            # the impact call under other vertical half-widths brings the factor table's cache to THAT pair of settings; the
+            # original half-widths are set again behind it, and the next cycle must rebuild the table
+            lead, ov, oh = s["vl"]
+            other = dict(s, vl=(lead, ov, 0.5 * oh))
+            ctx.set_vertical_localization(*other["vl"])
+            try:
+                return self.bystander("obs_impact_slab", other, out)
+            finally:
+                ctx.set_vertical_localization(*s["vl"])
+        if name == "slab_factor_table":
+            tab = ctx.slab_factor_table(P, c["n_lead"])
+            ref = S.slab_table(s)
+            assert tab.shape == ref.shape and np.array_equal(tab == 0.0, ref == 0.0), "factor table: zeros"
+            nz = ref != 0.0
+            assert not nz.any() or np.max(np.abs(tab[nz] - ref[nz]) / ref[nz]) <= 1e-15, "factor table"
+            return tab
+        if name == "gc_block_counts":
+            o = S.new_case(4200 + s["index"], 2 * 150, 20, 77, True, ncol=150)
+            cnt, bp, pairs = ctx.gc_block_counts(o["lat"], o["lon"], o["ob_lat"], o["ob_lon"], o["hw"], o["asm"])
+            assert pairs == int(bp.sum())
+            return cnt, bp
+        n_lead, ny, nx, Mz = 2, 5, 7, 10
+        rows = n_lead * ny * nx
+        Z = 2.0 * rng.standard_normal((rows, Mz)) + rng.standard_normal((rows, 1))
+        y = rng.standard_normal(rows)
+        Zd = ctx.to_device(Z)
+        made = [Zd]
+
+        def field(*shape):
+            made.append(ctx.to_device(np.full(shape, -7.0)))
+            return made[-1]
+        try:
+            if name == "forward_stencil":
+                idx, wts = rng.integers(0, rows, (30, 3)), rng.random((30, 3))
+                HX = field(30, Mz)
+                ctx.forward_stencil(rows, 0, Mz, Zd, idx, wts, HX)
+                res = HX.download()
+                assert_parity(res, _numpy_stencil(Z, idx, wts), "forward stencil after the step")
+                return res
+            if name == "gram":
+                G, n, n_bad, sums = ctx.gram(rows, Mz, Zd, [1.0, 0.5], ncol=ny * nx, n_lead=n_lead)
+                return G, n, n_bad, sums
+            if name == "products":
+                mean, sd, quant, prob = field(rows), field(rows), field(2, rows), field(1, rows)
+                ctx.products(rows, Mz, Zd, ncol=ny * nx, n_lead=n_lead, quantiles=(0.1, 0.5), thresholds=np.zeros((n_lead, 1)),
+                             mean=mean, sd=sd, quant=quant, prob=prob)
+                return tuple(d.download() for d in (mean, sd, quant, prob))
+            if name == "verify":
+                crps = field(rows)
+                res = ctx.verify(rows, Mz, Zd, ctx_array(made, ctx, y), [0, 1], ncol=ny * nx, n_lead=n_lead, crps=crps)
+                return tuple(res) + (crps.download(),)
+            if name == "neighbourhood":
+                nep = field(1, rows)
+                ctx.neighbourhood(rows, Mz, Zd, ny, nx, n_lead, np.zeros((n_lead, 1)), [1], nep=nep)
+                return nep.download()
+            if name == "pm_mean":
+                pm = field(rows)
+                n_bad = ctx.pm_mean(rows, Mz, Zd, ny, nx, n_lead, ctx_array(made, ctx, y), pm)
+                return n_bad, pm.download()
+            if name == "sensitivity":
+                var, sens = field(rows), field(2, rows)
+                res = ctx.sensitivity(rows, Mz, Zd, rng.standard_normal((2, Mz)), [1.0, 2.0], ncol=ny * nx, n_lead=n_lead, var=var,
+                                      sens=sens)
+                return tuple(res) + (var.download(), sens.download())
+            raise KeyError(name)
+        finally:
+            for d in made:
+                d.free()
 
     def refuse(self, s):
         """A refusal step: the call the header says must fail returns EFA_ERR_INVALID and leaves the caller's buffers alone."""
@@ -238,10 +423,25 @@ class Runner(object):
             must_fail(ctx.state_cycle, N, M, X.data_ptr(), post.data_ptr(), **gkw)  # no trajectory
             xm = dev(np.zeros(N))
             must_fail(ctx.state_phase, N, M, xm.data_ptr(), X.data_ptr(), xm.data_ptr(), post.data_ptr(), **gkw)
+        elif kind == "impact_plain_entry_under_sl":
+            # efa_obs_impact_dev while the slab setting is on (efa_obs_impact_slab_dev is the impact under these tapers)
+            werr = dev(np.ones(N))
+            must_fail(ctx.obs_impact, N, M, P, X.data_ptr(), werr.data_ptr(), Yp.data_ptr(), np.zeros(P), c["err"], c["asm"],
+                      **dict(okw, **gkw))
+        elif kind == "f32_with_ai":
+            # the obs phase is valid under the field; the float32 state cycle is float64 only there
+            X32, post32 = dev32(c["X"]), dev32(np.full((N, M), 7.0))
+            ctx.obs_phase(M, P, ym.data_ptr(), Yp.data_ptr(), *ob, **okw)
+            before[2], before[3] = host(ctx, Yp, P), host(ctx, ym, P)
+            must_fail(ctx.state_cycle_f32, N, M, X32.data_ptr(), post32.data_ptr(), **gkw)
+            assert np.array_equal(host(ctx, X32, N), c["X"].astype(np.float32)) and np.all(host(ctx, post32, N) == 7.0), \
+                "a refused call wrote to the caller's float32 rows"
         else:
             must_fail(ctx.ensrf_cycle, N, M, P, X.data_ptr(), post.data_ptr(), ym.data_ptr(), Yp.data_ptr(), *ob,
                       obs_block_out=True, **dict(okw, **gkw))
-            if s["vl"] is not None:    # (the obs phase alone checks the vertical setting; the adaptive one needs the rows)
+            # (the obs phase alone checks the vertical and the slab setting, but for the number of slabs; the adaptive one needs
+            # the rows)
+            if s["vl"] is not None or (s["sl"] is not None and kind != "sl_other_nlead"):
                 must_fail(ctx.obs_phase, M, P, ym.data_ptr(), Yp.data_ptr(), *ob, **okw)
         after = [host(ctx, t, t.shape[0]) for t in (X, post, Yp, ym)] + ([host(ctx, self.field, self.field.shape[0])]
                                                                          if self.field is not None else [])
@@ -261,8 +461,16 @@ def parity(got, ref, what):
 
 
 def check_against_model(s, got, m, what):
-    """Returns the worst relative error of the step."""
-    worst = assert_parity(got["post"], m["post"], what + " posterior")
+    """Returns the worst relative error of the step.  A float32 step's posterior is held to the bound of test_gpu_f32_state: half
+    a float32 ulp of the one rounding plus the float64 tolerance (its share of the worst error is not in the figure returned)."""
+    if s.get("elem", "f64") == "f32":
+        import test_gpu_f32_state as f32t
+        assert got["post"].dtype == np.float32 and got["post"].shape == m["post"].shape, what + " posterior: float32 rows"
+        if m["post"].size:
+            f32t._assert_reference_bound(got["post"], m["post"], what + " posterior")
+        worst = 0.0
+    else:
+        worst = assert_parity(got["post"], m["post"], what + " posterior")
     for key in DIAG_KEYS:
         worst = max(worst, parity(np.asarray(got["diag"][key], float), m["diag"][key], what + " " + key))
     assert np.array_equal(np.asarray(got["diag"]["assimilated"], bool), m["diag"]["assimilated"]), what + " assimilated"
@@ -277,24 +485,39 @@ def check_against_model(s, got, m, what):
     return worst
 
 
-def check_against_fresh(got, fresh, what):
-    """Bit for bit when both contexts ran the same kernels; returns 1 if they differ in kind (then: parity only)."""
-    if got["kind"] == fresh["kind"] and got["path"] == fresh["path"]:
-        for key in ("post", "ym", "Yp", "field"):
+OWN_ARGUMENTS = ("gram", "products", "verify", "neighbourhood", "pm_mean", "sensitivity", "gc_block_counts", "forward_stencil",
+                 "slab_factor_table")      # bystanders that do not read the step's posterior
+
+
+def check_against_fresh(got, fresh, what, keys=("post", "ym", "Yp", "field")):
+    """Bit for bit when both contexts ran the same kernels; returns 1 if they differ in kind (then: parity only, and none for
+    float32 rows, whose one rounding the model's bound covers).  The calls after the step: bit for bit too."""
+    same_kernels = got["kind"] == fresh["kind"] and got["path"] == fresh["path"]
+    for b, v in got.get("after", {}).items():
+        if same_kernels or b in OWN_ARGUMENTS:
+            assert same_value(v, fresh["after"][b]), "%s: %s after the step differs from a fresh context's" % (what, b)
+    if same_kernels:
+        for key in keys:
             assert same_value(got[key], fresh[key]), "%s: %s differs from a fresh context's" % (what, key)
         for key in DIAG_KEYS + ("assimilated",):
             assert same_value(np.asarray(got["diag"][key]), np.asarray(fresh["diag"][key])), \
                 "%s: %s differs from a fresh context's" % (what, key)
         return 0
-    for key in ("post", "ym", "Yp", "field"):
-        if got[key] is not None:
+    for key in keys:
+        if got[key] is not None and got[key].dtype != np.float32:
             assert_parity(got[key], fresh[key], what + " " + key + " (other Phase-A kind than the fresh context)")
     return 1
 
 
-def run_steps(steps, ctx=None, only=None, stats=None):
+def resident_form(s):
+    """The resident step a streamed step must equal bit for bit: efa_ensrf_cycle_dev on disjoint buffers, or obs
+    phase + efa_state_cycle_f32_dev for float32 rows."""
+    return dict(s, entry="cycle_out" if s["elem"] == "f64" else "state_cycle_f32", in_place=False, chunk_cols=None, after=())
+
+
+def run_steps(steps, ctx=None, only=None, stats=None, results=None):
     """The steps on one context (a new one unless given), each against the model and against a fresh context.
-    only: indices to run (replay); stats: dict the counters are added to."""
+    only: indices to run (replay); stats: dict the counters are added to; results: list the used context's outputs are added to."""
     lib, torch = _lib(), _torch()
     own_ctx = ctx is None
     if own_ctx:
@@ -316,14 +539,20 @@ def run_steps(steps, ctx=None, only=None, stats=None):
                     stats["refusals"] += 1
                     continue
                 got = used.run(s)
+                if results is not None:
+                    results.append(got)
                 stats["worst"] = max(stats["worst"], check_against_model(s, got, S.model(s), what))
                 fctx = lib.Context(0)
                 try:
                     fresh = Runner(fctx, caller).run(s)
+                    resident = Runner(fctx, caller).run(resident_form(s)) if s["entry"] == "host_streamed" else None
                     fctx.synchronize()
                 finally:
                     fctx.close()
-                stats["kind_differs"] += check_against_fresh(got, fresh, what)
+                differs = check_against_fresh(got, fresh, what)
+                if resident is not None:
+                    differs = max(differs, check_against_fresh(dict(got, after={}), resident, what + " (resident)", keys=("post",)))
+                stats["kind_differs"] += differs
                 stats["steps"] += 1
             except lib.EfaError as e:
                 raise AssertionError("%s: the library refused the step: %s" % (what, e))
@@ -376,6 +605,20 @@ def test_random_plan_on_one_context(seed, length):
         stats["kind_differs"], length)
     assert stats["given_back"] >= floor, "close() gave back %.1f MiB, the context held at least %.1f" % (
         stats["given_back"] / 2**20, floor / 2**20)
+
+
+@pytest.mark.parametrize("k", range(len(S.PLANS2)), ids=["%d-%d-%d" % key for key in S.PLANS2])
+def test_second_generation_plan_on_one_context(k):
+    """The plans with the slab setting, float32 rows, the streamed cycle and the calls between the steps (S.plans2)."""
+    plan = S.plans2()[k]
+    seed, length, _ = S.PLANS2[k]
+    stats = run_steps(plan)
+    print("plan %r: %d steps, %d refusals, %d differed in phase_a_kind from the fresh context (at most %d may), worst relative "
+          "error %.3e" % (S.PLANS2[k], stats["steps"], stats["refusals"], stats["kind_differs"], int(KIND_DIFF_MAX * length),
+                          stats["worst"]))
+    assert stats["steps"] == length and stats["refusals"] >= 3
+    assert stats["kind_differs"] <= KIND_DIFF_MAX * length, "%d of %d steps ran another Phase-A kind than a fresh context" % (
+        stats["kind_differs"], length)
 
 
 # ---- b. directed transitions -------------------------------------------------------------------------------------------------
@@ -451,17 +694,147 @@ def _directed_sequences():
     seqs["outlier check on, another rejected set, off, on one geometry"] = _seq(
         [(g1, dict(qc=3.0, keep="values")), (g2, dict(qc=3.0, keep="values", entry="state_cycle")),
          (g2, dict(qc=None, keep="values")), (g1, dict(qc=3.0, keep="values", entry="update_dev")), (g1, dict(keep="values"))])
+    seqs.update(_slab_sequences(rng))
     for steps in seqs.values():
         for s in steps:
             assert S.clear(s), S.describe(s)
     return seqs
 
 
+def _gc_slab(seed=909, nvar=3, nt=2, ncol=600, M=40, P=150):
+    c = S.new_case(seed, nvar * nt * ncol, M, P, True, ncol=ncol)
+    c["state_shape"] = (nvar, nt, c["ny"], c["nx"])
+    return c
+
+
+def _first_ob(c, sl, test):
+    """The first ob of the first third that is assimilated and passes `test`: the obs after it then see what changes with it."""
+    return next(k for k in range(c["P"] // 3) if c["asm"][k] and test(k))
+
+
+def _slab_sequences(rng):
+    """One sequence per key the caches of the slab setting, the streamed cycle and the float32 rows are compared by."""
+    seqs = {}
+    base = _gc_slab()
+    nvar, nt = base["state_shape"][:2]
+    P, n_lead = base["P"], base["n_lead"]
+    sl = S.slab_setting(rng, nvar, nt, P)
+    vl = S.vertical(rng, n_lead, P)
+    # geo_sl_serial (efa_obs_phase: the obs geometry counts as unchanged only under the same slab setting) and with it the tapered
+    # obs-obs table and the active lists: the same case, one ob's tau three times as wide, the first setting again
+    k = _first_ob(base, sl, lambda k: not np.isnan(sl["ob_time"][k]) and not np.isnan(sl["ob_time_halfwidth"][k]))
+    wide = S.slab_copy(sl)
+    wide["ob_time_halfwidth"][k] *= 3.0
+    seqs["slab: one ob's tau changed on one geometry (geo_sl_serial)"] = _seq(
+        [(base, dict(sl=sl)), (base, dict(sl=wide, keep="sl_tau")), (base, dict(sl=S.slab_copy(sl), keep="sl_tau")),
+         (S.revalue(base, rng), dict(sl=wide, keep="sl_tau", entry="state_cycle"))])
+    # the same key through the variable part: the impact of the obtype that names no state variable on variable 0
+    other = S.slab_copy(sl)
+    other["impact"][nvar - 1, 0] = 0.55 if sl["impact"][nvar - 1, 0] != 0.55 else 0.3
+    seqs["slab: one impact entry changed on one geometry (geo_sl_serial)"] = _seq(
+        [(base, dict(sl=sl)), (base, dict(sl=other, keep="sl_impact")), (base, dict(sl=S.slab_copy(sl), keep="sl_impact")),
+         (S.revalue(base, rng), dict(sl=other, keep="sl_impact", entry="update_dev"))])
+    # efa_ctx_set_slab_localization returns early on identical arrays: no serial moves, the lists and the table are reused
+    seqs["slab: identical setting sent again (sl_serial stays)"] = _seq(
+        [(base, dict(sl=sl, vl=vl))] + [(S.revalue(base, rng), dict(sl=S.slab_copy(sl), vl=tuple(a.copy() for a in vl), keep="sl_same",
+                                                                    entry=e)) for e in ("cycle_out", "state_cycle", "cycle_in")])
+    # sl_tab_vl_serial (ensure_slab_table: the table carries the vertical factor and must follow vl_serial)
+    vl2 = (vl[0].copy(), vl[1].copy(), vl[2] * 0.5)
+    seqs["slab: vertical half-widths alone changed (sl_tab_vl_serial)"] = _seq(
+        [(base, dict(sl=sl, vl=vl)), (base, dict(sl=S.slab_copy(sl), vl=vl2, keep="vl_under_sl")),
+         (base, dict(sl=S.slab_copy(sl), vl=tuple(a.copy() for a in vl), keep="vl_under_sl")),
+         (S.revalue(base, rng), dict(sl=S.slab_copy(sl), vl=vl2, keep="vl_under_sl", entry="phases_out"))])
+    # efa_obs_impact_slab_dev writes the table's cache from outside a cycle, here under other half-widths than the cycles'
+    seqs["slab: obs_impact_slab under another vertical setting between two cycles (sl_tab cache)"] = _seq(
+        [(base, dict(sl=sl, vl=vl, after=("obs_impact_slab_other_vl",))), (base, dict(sl=S.slab_copy(sl), vl=vl, keep="sl_same")),
+         (S.revalue(base, rng), dict(sl=S.slab_copy(sl), vl=vl, keep="sl_same", after=("obs_impact_slab", "slab_factor_table"))),
+         (S.revalue(base, rng), dict(sl=S.slab_copy(sl), vl=vl, keep="sl_same", entry="state_cycle"))])
+    # cleared, a plain cycle on the same geometry, the identical setting again: both switches move sl_serial
+    seqs["slab: on, off with a plain cycle, the identical setting on again (sl_serial moves)"] = _seq(
+        [(base, dict(sl=sl)), (base, dict(keep="values")), (base, dict(sl=S.slab_copy(sl), keep="values")),
+         (S.revalue(base, rng), dict(keep="values", entry="state_cycle")),
+         (S.revalue(base, rng), dict(sl=S.slab_copy(sl), keep="sl_off_on", entry="cycle_in"))])
+    # sl_any false between two settings with factors: the plain family serves the step, the table of the first must not
+    sl_b = S.slab_setting(rng, nvar, nt, P)
+    seqs["slab: a setting of ones between two real settings (sl_any)"] = _seq(
+        [(base, dict(sl=sl)), (base, dict(sl=S.slab_ones(nvar, nt, P), keep="sl_ones")), (base, dict(sl=sl_b, keep="values")),
+         (S.revalue(base, rng), dict(sl=S.slab_ones(nvar, nt, P), keep="sl_ones", vl=vl)),
+         (S.revalue(base, rng), dict(sl=S.slab_copy(sl), keep="values", vl=vl))])
+    # qc_used / qc_act feed the list builders: a slab step after a step whose outlier check rejected obs of the same geometry
+    g1 = S.revalue(base, rng)
+    g1["val"], _ = S._outlier.inject(g1["HX"], g1["val"], g1["err"], g1["asm"], 3.0, 3, seed=3)
+    seqs["slab: after an outlier check that rejected three obs of the same geometry (qc_used, qc_act)"] = _seq(
+        [(g1, dict(qc=3.0)), (S.revalue(base, rng), dict(sl=sl, keep="values")), (g1, dict(qc=3.0, sl=S.slab_copy(sl), keep="sl_same")),
+         (S.revalue(base, rng), dict(sl=S.slab_copy(sl), keep="sl_same", entry="state_cycle"))])
+    # ColumnGrid::take_slice: the streamed cycle cuts the grid mirror into chunks (mirror_ncol = -1, grid.serial moves); the
+    # resident cycle on the same grid arrays must upload the whole grid again
+    seqs["streamed in chunks of 16, resident on the same grid, streamed in chunks of 48 (take_slice, grid.serial)"] = _seq(
+        [(base, dict(entry="host_streamed", chunk_cols=16)), (S.revalue(base, rng), dict(entry="cycle_in", keep="values")),
+         (S.revalue(base, rng), dict(entry="host_streamed", chunk_cols=48, keep="values", sl=sl)),
+         (S.revalue(base, rng), dict(entry="state_cycle", keep="values", sl=S.slab_copy(sl)))])
+    # f32_ws, wide_prior, relax_prior, relax_ss only grow: rows of 4 and 8 bytes, above and below 136 members, standalone relaxation
+    u = dict((M, S.new_case(1000 + M, 700, M, 100, False)) for M in (100, 137, 256))
+    seqs["float32 and float64 rows in turn, above and below 136 members (f32_ws, wide_prior, relax_prior, relax_ss)"] = _seq(
+        [(S.to_f32(u[137]), dict(entry="state_cycle_f32", elem="f32", in_place=True, path=2)), (u[137], dict(entry="cycle_in", path=2)),
+         (S.to_f32(u[100]), dict(entry="state_cycle_f32", elem="f32", relax=("rtpp", 0.5), path=1)),
+         (u[256], dict(entry="cycle_in", relax=("rtps", 0.9), path=2)),
+         (S.to_f32(u[137]), dict(entry="state_cycle_f32", elem="f32", relax=("rtps", 0.9), path=2))])
+    # the per-batch rows table against the whole obs-obs table (tw_serial, tw_Pw, tw_Rw, tw_ptr)
+    seqs["slab: Phase A per batch, then the band leader, on one geometry (tw table)"] = _seq(
+        [(S.revalue(base, rng), dict(sl=S.slab_copy(sl), vl=vl, keep="sl_same", phase_a=k, obs_batch=b))
+         for k, b in (("batch", 64), ("band", 64), ("batch", 7), ("gram", 64))])
+    # sl_tab is grow-only: one more ob may or may not move its pointer (sl_tab_ptr); then the first setting again
+    more = _gc_slab(seed=910, P=P + 1)
+    seqs["slab: P obs, P + 1 obs with their own setting, P obs again (sl_tab_ptr)"] = _seq(
+        [(base, dict(sl=sl)), (more, dict(sl=S.slab_setting(rng, nvar, nt, P + 1))), (base, dict(sl=S.slab_copy(sl))),
+         (S.revalue(more, rng), dict(sl=S.slab_setting(rng, nvar, nt, P + 1), keep="values"))])
+    return seqs
+
+
+def _taper_changed(results):
+    """Steps 0..2 run one case under setting A, B, A: the obs block under B differs from A's, and A's comes back bit for bit."""
+    assert not np.array_equal(results[1]["Yp"], results[0]["Yp"]), "the changed setting left the obs block as it was"
+    if results[2]["kind"] == results[0]["kind"]:
+        for key in ("post", "ym", "Yp"):
+            assert np.array_equal(results[2][key], results[0][key]), "the first setting again: %s differs from the first step's" % key
+
+
+def _state_taper_changed(results):
+    """The same where only the state rows' factors change (the obs-obs table has its own key)."""
+    assert not np.array_equal(results[1]["post"], results[0]["post"]), "the changed half-widths left the posterior as it was"
+    if results[2]["kind"] == results[0]["kind"]:
+        assert np.array_equal(results[2]["post"], results[0]["post"]), "the first half-widths again: another posterior"
+
+
+def _lists_reused(results):
+    """What the options show of work that hangs on geo_serial: the same active pairs and as many state launches in every step."""
+    assert len(set(r["pairs"] for r in results)) == 1 and len(set(r["launches"] for r in results)) == 1, \
+        [(r["pairs"], r["launches"]) for r in results]
+
+
+DIRECTED_CHECKS = {"slab: one ob's tau changed on one geometry (geo_sl_serial)": _taper_changed,
+                   "slab: one impact entry changed on one geometry (geo_sl_serial)": _taper_changed,
+                   "slab: vertical half-widths alone changed (sl_tab_vl_serial)": _state_taper_changed,
+                   "slab: identical setting sent again (sl_serial stays)": _lists_reused}
+
+
 DIRECTED = ["grid values changed, cycle_out", "grid values changed, state_cycle",
             "GC, unlocalised with other M and P, the GC cycle again", "gc_onepass 1, 0, 1",
             "obs_batch 64, 7, 64 and each Phase-A kind", "n_lead 4, 6, 1", "small, large, small, large geometry",
             "vertical localisation set, identical, half-widths, off", "adaptive inflation set, other bounds, off",
-            "RTPP in place, more rows, RTPS, none", "outlier check on, another rejected set, off, on one geometry"]
+            "RTPP in place, more rows, RTPS, none", "outlier check on, another rejected set, off, on one geometry",
+            "slab: one ob's tau changed on one geometry (geo_sl_serial)",
+            "slab: one impact entry changed on one geometry (geo_sl_serial)",
+            "slab: identical setting sent again (sl_serial stays)",
+            "slab: vertical half-widths alone changed (sl_tab_vl_serial)",
+            "slab: obs_impact_slab under another vertical setting between two cycles (sl_tab cache)",
+            "slab: on, off with a plain cycle, the identical setting on again (sl_serial moves)",
+            "slab: a setting of ones between two real settings (sl_any)",
+            "slab: after an outlier check that rejected three obs of the same geometry (qc_used, qc_act)",
+            "streamed in chunks of 16, resident on the same grid, streamed in chunks of 48 (take_slice, grid.serial)",
+            "float32 and float64 rows in turn, above and below 136 members (f32_ws, wide_prior, relax_prior, relax_ss)",
+            "slab: Phase A per batch, then the band leader, on one geometry (tw table)",
+            "slab: P obs, P + 1 obs with their own setting, P obs again (sl_tab_ptr)"]
 
 
 def few_kind_differences(stats):
@@ -475,8 +848,11 @@ def few_kind_differences(stats):
 def test_directed_transition(name):
     seqs = directed_sequences()
     assert sorted(seqs) == sorted(DIRECTED)
-    stats = run_steps(seqs[name])
+    results = []
+    stats = run_steps(seqs[name], results=results)
     assert stats["steps"] == len(seqs[name]) and few_kind_differences(stats)
+    if name in DIRECTED_CHECKS:
+        DIRECTED_CHECKS[name](results)
 
 
 def _numpy_stencil(X, idx, wts):
@@ -548,7 +924,9 @@ def test_helper_calls_between_two_cycles_on_one_geometry():
 
 
 def test_deferred_timing_sums_over_the_directed_sequences():
-    """timing 2 across ALL the directed sequences, the helper calls after each of them, with efa_last_timing read only at the end:
+    """timing 2 across ALL the directed sequences, one of the calls of S.BYSTANDERS after every step (the impact, diagnostic and
+    helper entry points: none of them may add to either sum), the helper calls after each sequence, with efa_last_timing read only
+    at the end:
     state_launches equals the sum of the per-step values read with timing 1 on a second pass (the times themselves are not
     asserted).  The per-batch sweeps (obs_batch 7 and 1, gc_onepass 0) are where the count of launches varies most."""
     lib = _lib()
@@ -565,6 +943,9 @@ def test_deferred_timing_sums_over_the_directed_sequences():
                     got = r.run(dict(s, timing=timing))
                     kinds.append(got["kind"])
                     launches += got["launches"] or 0
+                    b = S.BYSTANDERS[len(kinds) % len(S.BYSTANDERS)]     # one call between this step and the next, in turn
+                    if S.bystander_legal(s, b):
+                        r.bystander(b, s, got)
                 helper_calls(ctx, helper_base, np.random.default_rng(4))
             return kinds, launches
 
@@ -650,15 +1031,17 @@ def test_raw_cycles_interleaved_with_the_python_surface_on_the_shared_context():
 
 
 # ---- d. refusals in the middle -----------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("kind", S.REFUSALS)
+@pytest.mark.parametrize("kind", S.REFUSALS + S.REFUSALS2)
 def test_refusal_then_the_next_valid_step(kind):
     rng = np.random.default_rng(12)
     base = _gc(seed=71, n_lead=2, ncol=200, M=20, P=60)
     vl = S.vertical(rng, base["n_lead"], base["P"])
+    refusal = (lambda i: S._refusal_step(rng, kind, None, "refusal", i)) if kind in S.REFUSALS else \
+        (lambda i: S._refusal_step2(rng, kind, "refusal", i))
     steps = [S.make_step(base, seed="refusal", index=0, vl=vl, qc=3.0),
-             S._refusal_step(rng, kind, None, "refusal", 1),
+             refusal(1),
              S.make_step(S.revalue(base, rng), seed="refusal", index=2, keep="values", vl=vl, entry="state_cycle"),
-             S._refusal_step(rng, kind, None, "refusal", 3),
+             refusal(3),
              S.make_step(S.new_case(72, 400, 40, 50, False), seed="refusal", index=4),
              S.make_step(S.revalue(base, rng), seed="refusal", index=5, keep="values", entry="cycle_in")]
     assert all(S.clear(s) for s in steps if not s["refusal"])
