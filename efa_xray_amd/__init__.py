@@ -10,6 +10,7 @@ from efa_xray_amd.observation.observation import Observation, gaspari_cohn, have
 from efa_xray_amd.assimilation.assimilation import Assimilation
 from efa_xray_amd.assimilation.ensrf import EnSRF
 from efa_xray_amd.assimilation.adaptive_inflation import AdaptiveInflation
+from efa_xray_amd.assimilation.sampling_error import sampling_error_table
 from efa_xray_amd.postprocess.impact import observation_impact
 from efa_xray_amd.postprocess.sensitivity import ensemble_sensitivity, observation_targets
 from efa_xray_amd.postprocess.verification import ensemble_verification
@@ -24,5 +25,5 @@ __all__ = ["EnsembleState", "Observation", "gaspari_cohn", "haversine", "Assimil
            "ensemble_verification", "ensemble_products", "probability_verification",
            "ensemble_gram", "ensemble_eofs", "ensemble_clusters", "distances_from_gram", "eofs_from_gram", "clusters_from_gram",
            "neighbourhood_probabilities", "fractions_skill_score", "fss_from_sums",
-           "probability_matched_mean"]
+           "probability_matched_mean", "sampling_error_table"]
 __version__ = "0.1.0"

@@ -58,6 +58,7 @@ SIGNATURES = {
                                                      c_double_p]),
     "efa_slab_factor_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_double_p]),
     "efa_ctx_set_outlier_threshold": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double]),
+    "efa_ctx_set_sampling_error_correction": (ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_int]),
     "efa_ctx_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
     "efa_malloc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, c_void_pp]),
     "efa_free": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
@@ -536,6 +537,17 @@ class Context(object):
         """Outlier check of every later obs phase on this context: an ob with
         (value - ym)^2 > threshold^2 (var(Yp) + error) is not assimilated; None or 0 turns it off."""
         _check(self.lib, self.lib.efa_ctx_set_outlier_threshold(self.handle, 0.0 if threshold is None else float(threshold)))
+
+    def set_sampling_error_correction(self, alpha=None):
+        """Sampling error correction of every later GC cycle on this context: `alpha` a host table of 2..512
+        factors, node j at |r| = j/(T-1), read piecewise linearly; None turns it off."""
+        if alpha is None:
+            _check(self.lib, self.lib.efa_ctx_set_sampling_error_correction(self.handle, None, 0))
+            return
+        a = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
+        if a.size == 0:
+            raise ValueError("the sampling error correction table is empty (None turns the correction off)")
+        _check(self.lib, self.lib.efa_ctx_set_sampling_error_correction(self.handle, _dp(a), a.size))
 
     def inflate_rows(self, rows, M, X, field):
         """X[row] <- mean + sqrt(field[row][0]) (X[row] - mean), in place on the device."""

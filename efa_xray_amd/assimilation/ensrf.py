@@ -19,6 +19,7 @@ import numpy as np
 from efa_xray_amd import _lib
 from efa_xray_amd.assimilation.adaptive_inflation import AdaptiveInflation
 from efa_xray_amd.assimilation.assimilation import Assimilation
+from efa_xray_amd.assimilation.sampling_error import sec_setting
 from efa_xray_amd.observation.observation import check_vert_halfwidth
 
 
@@ -229,6 +230,13 @@ class EnSRF(Assimilation):
                     assimilated is rejected (assimilated False, nothing updated by it) when
                     (value - prior mean)^2 > t^2 (prior variance + error), checked once per
                     update against the prior.  None: off
+        sampling_error_correction -- Anderson's (2012) correction of the gain for sampling error
+                    (DESIGN.md 7w): True damps the gain of every (row, ob) pair by the factor
+                    alpha(|r|; M) of `sampling_error_table(M)` at the pair's sample correlation r; an
+                    array of 2..512 factors >= 0 is used in its place (node j at |r| = j/(T-1), read
+                    piecewise linearly).  Needs loc='GC'; excludes adaptive_inflation, vert_coord,
+                    time_localize / var_impact, streamed and update_arrays; combines with rtps / rtpp,
+                    outlier_threshold, inflation= and float32 states.  None or False: off
         streamed -- True: the prior stays in host memory and crosses the device in chunks of (y, x)
                     columns, upload, state phase and download overlapping; device
                     memory for the state is three chunks.  Same results bit for bit.  The posterior's
@@ -259,6 +267,7 @@ class EnSRF(Assimilation):
         time_localize = kw.pop("time_localize", False)
         var_impact = kw.pop("var_impact", None)
         streamed = kw.pop("streamed", False)
+        sec = kw.pop("sampling_error_correction", None)
         stream_chunk_cols = kw.pop("stream_chunk_cols", None)
         stream_pinned_limit_mb = kw.pop("stream_pinned_limit_mb", 4096)
         if kw:
@@ -287,6 +296,7 @@ class EnSRF(Assimilation):
         self.slab = slab_setting(state, loc, time_localize, var_impact, adaptive)
         if self.slab is not None:
             ob_slab(state, obs, self.slab)
+        self.sec_table = sec_setting(sec, state.nmems(), loc, adaptive, self.vert_coord, self.slab, self.streamed)
         Assimilation.__init__(self, state, obs, nproc, inflation, verbose, device=device)
         self.loc = loc
         self.last_timing = None
@@ -333,6 +343,7 @@ class EnSRF(Assimilation):
         ctx.set_relaxation(*self.relaxation)   # every call: the context is shared per device
         ctx.set_adaptive_inflation(None)        # set by update() around its own cycle only
         ctx.set_outlier_threshold(self.outlier_threshold)  # every call, "off" included
+        ctx.set_sampling_error_correction(self.sec_table)  # likewise
         if self.vert_coord is None:             # every call as well, "off" included
             ctx.set_vertical_localization(None)
         else:
@@ -561,6 +572,8 @@ class EnSRF(Assimilation):
         if self.prior.dtype == np.float32:
             raise ValueError("update_arrays does not support a float32 state (the augmented arrays are float64, DESIGN.md 7g); "
                              "use update()")
+        if self.sec_table is not None:
+            raise ValueError("update_arrays does not support sampling_error_correction (out of scope, DESIGN.md 7w); use update()")
         if self.adaptive_inflation is not None:
             raise ValueError("update_arrays does not support adaptive_inflation (out of scope: it runs on the augmented "
                              "arrays without the prior inflation step); use update()")

@@ -417,6 +417,26 @@ int efa_slab_factor_table(efa_ctx* c, long P, long n_lead, double* table) {
   return EFA_OK;
 }
 
+int efa_ctx_set_sampling_error_correction(efa_ctx* c, const double* alpha, int T) {
+  EFA_TRY(use(c));
+  if (!alpha || T == 0) {
+    c->sec_T = 0;
+    return EFA_OK;
+  }
+  if (T < 2 || T > efa::kSecMaxT)
+    return fail(EFA_ERR_INVALID, "sampling error correction: a table of T=%d nodes (2 .. %d are supported)", T, efa::kSecMaxT);
+  for (int j = 0; j < T; ++j)
+    if (!(std::isfinite(alpha[j]) && alpha[j] >= 0.0))
+      return fail(EFA_ERR_INVALID, "sampling error correction: alpha[%d] = %g is not a finite number >= 0", j, alpha[j]);
+  if (c->sec_T == T && std::memcmp(c->sec_host.data(), alpha, (size_t)T * sizeof(double)) == 0) return EFA_OK;  // unchanged
+  std::vector<double> v(alpha, alpha + T);
+  EFA_TRY(h2d(c, c->sec_dev, v.data(), v.size() * sizeof(double)));
+  EFA_HIP(hipStreamSynchronize(c->stream));  // (v is gone on return)
+  c->sec_host.swap(v);
+  c->sec_T = T;
+  return EFA_OK;
+}
+
 int efa_ctx_set_outlier_threshold(efa_ctx* c, double threshold) {
   EFA_TRY(use(c));
   if (!std::isfinite(threshold) || threshold < 0.0)
@@ -443,7 +463,9 @@ int efa_ctx_get_option(efa_ctx* c, const char* key, long* value) {
   else if (!strcmp(key, "gram")) *value = c->use_gram;
   else if (!strcmp(key, "pipeline")) *value = c->use_pipeline;
   else if (!strcmp(key, "gc_onepass")) *value = c->gc_onepass;
-  else if (!strcmp(key, "gc_family")) *value = c->gc_family_used;  // the last one-pass sweep: 0 plain, 1 adaptive, 2 vertical, 3 slab table
+  else if (!strcmp(key, "gc_family")) *value = c->gc_family_used;  // the last one-pass sweep: 0 plain, 1 adaptive, 2 vertical, 3 slab table, 4 SEC
+  else if (!strcmp(key, "gc_form")) *value = c->gc_form_used;  // the last one-pass sweep: 1 quad kernel, 2 row-per-lane kernel
+  else if (!strcmp(key, "sec_on")) *value = c->sec_T > 0 ? 1 : 0;  // efa_ctx_set_sampling_error_correction
   else if (!strcmp(key, "geometry_reuse")) *value = c->geometry_reuse;
   else if (!strcmp(key, "gc_active_pairs")) {
     EFA_TRY(read_gc_pairs(c));
@@ -681,6 +703,7 @@ int efa_ensrf_update_dev(efa_ctx* c, long rows, int M, long P, double* xm_dev, d
   EFA_TRY(check_adaptive(c, loc_mode, rows));
   EFA_TRY(check_vloc(c, loc_mode, P, n_lead));
   EFA_TRY(check_slab(c, loc_mode, P, n_lead));
+  EFA_TRY(check_sec(c, loc_mode));
   EFA_TRY(obs_phase(c, M, P, ym_dev, Yp_dev, ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon,
                     ob_halfwidth_km, prior_mean, prior_var, post_mean, post_var, assimilated));
   EFA_TRY(state_phase(c, rows, M, xm_dev, Xp_dev, xm_dev, Xp_dev, grid_lat, grid_lon, ncol, n_lead));
@@ -699,6 +722,7 @@ int efa_ensrf_cycle_dev(efa_ctx* c, long rows, int M, long P, const double* X_de
   EFA_TRY(check_adaptive(c, loc_mode, rows));
   EFA_TRY(check_vloc(c, loc_mode, P, n_lead));
   EFA_TRY(check_slab(c, loc_mode, P, n_lead));
+  EFA_TRY(check_sec(c, loc_mode));
   // Phase B may go into the stream before Phase A's status is known only if a wrong guess cannot cost the prior:
   // separate prior and posterior buffers (a redone Phase A needs the transform run again on the untouched prior)
   const StateRows r{X_dev, post_dev, Elem::f64, rows, M};

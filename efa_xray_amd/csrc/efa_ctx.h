@@ -289,7 +289,13 @@ struct efa_ctx {
   long sl_tab_serial = -1, sl_tab_vl_serial = -1;  // the settings the table was built from
   const void* sl_tab_ptr = nullptr;
   long gc_family_used = -1;     // read-only option "gc_family": the kernel family of the last one-pass sweep (0 plain, 1 adaptive,
-                                // 2 vertical, 3 slab table; -1: none ran)
+                                // 2 vertical, 3 slab table, 4 sampling error correction; -1: none ran)
+  long gc_form_used = 0;        // read-only option "gc_form": the form of the last one-pass sweep (1 quad kernel, 2 row-per-lane kernel; 0: none ran)
+  // --- sampling error correction (efa_ctx_set_sampling_error_correction) --------------------------------
+  int sec_T = 0;                // nodes of the table; 0: off
+  std::vector<double> sec_host; // the table as on the device
+  DevBuf sec_dev;               // device copy of sec_host
+  DevBuf sec_ob;                // [P][4] the record the sweep reads y'.y' of each ob from (launch_adapt_obs)
   // --- outlier check (efa_ctx_set_outlier_threshold) ----------------------------------------------
   double qc_threshold = 0.0;    // 0: off
   bool qc_used = false;         // the last obs phase ran it: its flags on the device may be fewer than the caller's

@@ -79,6 +79,10 @@ inline efa::SlabObs sl_obs(const efa_ctx* c, long w0) {  // the obs' side from o
   return efa::SlabObs{d + c->sl_nlead + w0, d + c->sl_nlead + c->sl_P + w0, i + c->sl_nlead + w0, i + c->sl_nlead + c->sl_P + w0,
                       d + c->sl_nlead + 2 * c->sl_P, c->sl_nvar};
 }
+// sampling error correction: while it is set every call must be a GC cycle on the one-pass sweep, without adaptive
+// inflation, vertical or slab localisation (no combined kernel; Phase A then runs its one-ob batches)
+int check_sec(const efa_ctx* c, int loc_mode);
+inline bool sec_active(const efa_ctx* c) { return c->sec_T > 0; }
 // the slab table S[P][n_lead] on the device, rebuilt when the slab or the vertical setting changed since it was written
 int ensure_slab_table(efa_ctx* c);
 using efa::Elem;

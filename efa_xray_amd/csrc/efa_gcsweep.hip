@@ -416,22 +416,51 @@ constexpr int kChunkL = EFA_GC_LANE_CHUNK;  // observations staged at a time by 
 
 // the kernel family of a launch: plain, adaptive inflation fused in, vertical factor (§7d), slab table (§7t; it
 // carries the vertical factor too: it goes before the vertical family); the values are the option "gc_family"'s
-enum GcFamily : int { kGcPlain = 0, kGcAdapt = 1, kGcVloc = 2, kGcSlab = 3 };
-inline int gc_family(const GcSweepArgs& a) { return a.infl ? kGcAdapt : a.slab_tab ? kGcSlab : a.lead_vert ? kGcVloc : kGcPlain; }
+// sampling error correction: the gain of the pair damped by the factor of its sample correlation
+enum GcFamily : int { kGcPlain = 0, kGcAdapt = 1, kGcVloc = 2, kGcSlab = 3, kGcSec = 4 };
+inline int gc_family(const GcSweepArgs& a) {
+  return a.infl ? kGcAdapt : a.sec_tab ? kGcSec : a.slab_tab ? kGcSlab : a.lead_vert ? kGcVloc : kGcPlain;
+}
 // dispatch_family(fam, f) returns f(std::integral_constant<int, FAM>{}) for the FAM equal to fam
 template <class F>
 hipError_t dispatch_family(int fam, F&& f) {
-  return dispatch_width(fam, std::integer_sequence<int, kGcPlain, kGcAdapt, kGcVloc, kGcSlab>{}, f);
+  return dispatch_width(fam, std::integer_sequence<int, kGcPlain, kGcAdapt, kGcVloc, kGcSlab, kGcSec>{}, f);
 }
+
+// ---- sampling error correction (Anderson 2012), fused into both sweep forms.  The factor of one (row, ob) pair from
+// what the sweep holds BEFORE the ob moves the row: dot = x'.y', ss = x'.x', yy = y'.y'.  |r| = |dot| rsqrt(ss yy), 0 when either
+// norm is 0; the table (in LDS, node j at |r| = j / (T - 1)) is read piecewise linearly.  fmin returns its other argument for a
+// NaN, so a poisoned row reads the last interval (its gain is NaN through dot all the same) and no index leaves [0, T - 2].
+struct SecLookup {
+  const double* tab;
+  int T;
+  __device__ __forceinline__ double operator()(double dot, double ss, double yy) const {
+    const double nn = ss * yy;
+    const double r = (nn > 0.0) ? fabs(dot) * rsqrt(nn) : 0.0;
+    const double t = fmin(r, 1.0) * (double)(T - 1);
+    int j = (int)t;
+    j = (j < T - 2) ? j : T - 2;
+    const double a0 = tab[j], a1 = tab[j + 1];
+    return a0 + (t - (double)j) * (a1 - a0);
+  }
+};
 
 // Waves per SIMD of the quad form.  With the update: one row per quad (gc_launch), and waves per SIMD for that row, one ye row and
 // ~100 registers of everything else (the update's temporaries included); the vertical factor and the slab table take the launch
 // shapes and rows per quad of the plain kernels (a few registers more per row for the factor)
 constexpr int gc_adapt_min_waves(int NC) { return (4 * NC * 2 + 100 <= 168) ? 3 : (4 * NC * 2 + 100 <= 256) ? 2 : 1; }
-constexpr int gc_quad_waves(int FAM, int NC, int RPL) { return FAM == kGcAdapt ? gc_adapt_min_waves(NC) : gc_min_waves(NC, RPL); }
+// with the correction: x'.x' of every row and the lookup's temporaries (the reciprocal square root above all) on top of the plain
+// kernel's budget -- measured 16 .. 26 registers; 40 more in the budget keep every instantiation clear of scratch (8 chunks of two
+// rows, 168 + 2 spilled at three waves, go to two)
+constexpr int gc_sec_min_waves(int NC, int RPL) {
+  return (4 * NC * (RPL + 1) + 76 <= 168) ? EFA_GC_MINWAVES : (4 * NC * (RPL + 1) + 76 <= 256 || NC * (RPL + 1) <= 52) ? 2 : 1;
+}
+constexpr int gc_quad_waves(int FAM, int NC, int RPL) {
+  return FAM == kGcAdapt ? gc_adapt_min_waves(NC) : FAM == kGcSec ? gc_sec_min_waves(NC, RPL) : gc_min_waves(NC, RPL);
+}
 // and of the row-per-lane form.  With the update, above 80 members at one wave per SIMD: the row, the ye registers and the
-// update's temporaries spill at two
-constexpr int gc_lane_waves(int FAM, int MP) { return (FAM == kGcAdapt && MP > 80) ? 1 : 2; }
+// update's temporaries spill at two; with the correction above 96 (the plain kernel's last spare registers at 100 and 104)
+constexpr int gc_lane_waves(int FAM, int MP) { return ((FAM == kGcAdapt && MP > 80) || (FAM == kGcSec && MP > 96)) ? 1 : 2; }
 
 #include "efa_gcsweep_kernels.h"
 
@@ -469,7 +498,9 @@ hipError_t gc_launch(const GcSweepArgs& a0, hipStream_t s) {
   GcSweepArgs a = a0;
   const bool vec = (a.M % 2 == 0) && (a.ye_stride % 2 == 0) && aligned16(a.Xin) && aligned16(a.Xout) && aligned16(a.Ye);
   // rows per quad while they fit the register file; with the inflation update one (its per-row state and temporaries spill at more)
-  constexpr int RPL = ADAPT ? 1 : (NC <= 8) ? EFA_GC_RPL : (NC <= 10) ? EFA_GC_RPL_MID : (NC <= 13) ? EFA_GC_RPL_WIDE : (NC <= 16) ? EFA_GC_RPL_XWIDE : 1;
+  // (with the correction one row fewer where the plain kernel holds more than two: its registers go to the lookup)
+  constexpr int RPLP = ADAPT ? 1 : (NC <= 8) ? EFA_GC_RPL : (NC <= 10) ? EFA_GC_RPL_MID : (NC <= 13) ? EFA_GC_RPL_WIDE : (NC <= 16) ? EFA_GC_RPL_XWIDE : 1;
+  constexpr int RPL = (FAM == kGcSec && RPLP > 2) ? RPLP - 1 : RPLP;
   // groups of slabs per column block: whole iterations of the slab loop (4 RPL slabs), as many as it takes to give
   // every CU a dozen workgroups, at most one group per iteration
   const int cus = device_cus();
@@ -536,17 +567,24 @@ bool sweep_gc_serves(Elem elem, int M, long ye_stride, const double* Ye) {
   return elem == Elem::f64 || (EFA_GC_LANE && M <= kLaneMaxMembers && (M % 2 == 0) && (ye_stride % 2 == 0) && aligned16(Ye));
 }
 
+// 16-byte aligned float64 rows of up to 104 members (an even number of them), and the float32 rows: the row-per-lane kernel
+int sweep_gc_form(const GcSweepArgs& a, Elem elem) {
+  return (elem == Elem::f32 || (EFA_GC_LANE && a.M <= kLaneMaxMembers && (a.M % 2 == 0) && (a.ye_stride % 2 == 0) && aligned16(a.Xin) &&
+                                aligned16(a.Xout) && aligned16(a.Ye)))
+             ? 2
+             : 1;
+}
+
 // The launcher is where a.Xin / a.Xout get their element type: elem picks the kernels that read them as float or as double rows.
 hipError_t launch_sweep_gc(const GcSweepArgs& a, Elem elem, hipStream_t s) {
   const bool f32 = elem == Elem::f32;
   if (!sweep_gc_serves(elem, a.M, a.ye_stride, a.Ye)) return hipErrorInvalidValue;
+  if (a.sec_tab && (a.sec_T < 2 || a.sec_T > kSecMaxT || !a.adapt_ob || a.infl || a.slab_tab || a.lead_vert)) return hipErrorInvalidValue;
   // float32 rows: member form, 4-byte aligned, no adaptive inflation (its update is float64 only)
   if (f32 && (!a.fused_members || a.infl || ((reinterpret_cast<uintptr_t>(a.Xin) | reinterpret_cast<uintptr_t>(a.Xout)) & 3u) != 0))
     return hipErrorInvalidValue;
   if (a.nblk <= 0 || a.n_lead <= 0) return hipSuccess;
-  // 16-byte aligned float64 rows of up to 104 members (an even number of them), and the float32 rows: the row-per-lane kernel
-  if (f32 || (EFA_GC_LANE && a.M <= kLaneMaxMembers && (a.M % 2 == 0) && (a.ye_stride % 2 == 0) && aligned16(a.Xin) &&
-              aligned16(a.Xout) && aligned16(a.Ye))) {
+  if (sweep_gc_form(a, elem) == 2) {
     GcSweepArgs l = a;
     l.lead_split = (int)((l.n_lead + 15) / 16);  // groups of 16 slabs: one workgroup each
     l.lead_chunk = 16;

@@ -6,7 +6,9 @@
 // FAM is the kernel family (GcFamily): kGcAdapt fuses the adaptive-inflation update in (Anderson 2009); with
 // kGcVloc and kGcSlab the taper carries a factor of each (slab, ob) pair: the vertical factor, evaluated while staging (DESIGN.md
 // §7d), or with kGcSlab the entry of the slab table S[ob][slab], which holds the product of the vertical, temporal and variable
-// factors.
+// factors.  kGcSec damps the gain of every (row, ob) pair by the sampling-error-correction factor alpha(|r|) of the
+// pair's sample correlation (Anderson 2012): x'.x' of the row is kept as the adaptive family keeps it, y'.y' is the
+// ob's staged record, the table sits in LDS.
 // E is the element type of the state rows in memory as the row-per-lane kernel sees them: double, or float for a state stored as
 // float32 (member form, no adaptive inflation; the quad kernel has no float32 form).
 #ifndef EFA_GCSWEEP_KERNELS_H
@@ -17,6 +19,7 @@ __global__ __launch_bounds__(256, gc_quad_waves(FAM, NC, RPL)) void k_sweep_gc(c
   constexpr bool ADAPT = FAM == kGcAdapt;
   constexpr bool VLOC = FAM == kGcVloc || FAM == kGcSlab;
   constexpr bool SLAB = FAM == kGcSlab;  // VLOC with the factor read from the slab table
+  constexpr bool SEC = FAM == kGcSec;
   static_assert(!(ADAPT && VLOC), "adaptive inflation with vertical localisation is not built");
   static_assert(VLOC || !SLAB, "the slab table is a form of the per-slab factor");
   constexpr int L = 4;
@@ -27,6 +30,8 @@ __global__ __launch_bounds__(256, gc_quad_waves(FAM, NC, RPL)) void k_sweep_gc(c
   __shared__ __align__(16) double aw_s[ADAPT ? kChunk * kBlkCols : 1];  // ADAPT: the taper per (staged ob, column), 0 if not assimilated
   __shared__ __align__(16) double2 ao_s[ADAPT ? 2 * kChunk : 1];         // ADAPT: the staged obs' records (adapt_ob)
   __shared__ __align__(16) double vf_s[VLOC ? kChunk * NS : 1];           // VLOC: the vertical factor per (staged ob, slab slot), 0 beyond the last slab
+  __shared__ __align__(16) double sec_s[SEC ? kSecMaxT : 1];              // SEC: the table, staged once per workgroup
+  __shared__ __align__(16) double yy_s[SEC ? kChunk : 1];                 // SEC: y'.y' of the staged obs
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   const int j = lane & 3, r = lane >> 2;
@@ -43,6 +48,9 @@ __global__ __launch_bounds__(256, gc_quad_waves(FAM, NC, RPL)) void k_sweep_gc(c
   const int M = a.M;
   const double rM1 = 1.0 / (double)(M - 1);
   const long e0 = a.off[b], e1 = e0 + a.cnt[b];
+  const SecLookup sec{sec_s, SEC ? a.sec_T : 2};
+  if (SEC)  // (read behind the barriers of the first chunk's staging)
+    for (int i = tid; i < a.sec_T; i += 256) sec_s[i] = a.sec_tab[i];
 
   // A quad holds RPL rows of the SAME column (slabs lead, lead + 4, ...): they share the taper and
   // every ye row read from LDS (the quad layout delivers each ye row once per quad), and a staged
@@ -50,7 +58,7 @@ __global__ __launch_bounds__(256, gc_quad_waves(FAM, NC, RPL)) void k_sweep_gc(c
   for (int lead0 = lead_lo; lead0 < lead_hi; lead0 += 4 * RPL) {
     double x[RPL][2 * NC];
     double xm[RPL];
-    double lam[RPL], sd[RPL], ss[RPL];  // ADAPT: the row's inflation and x'.x'
+    double lam[RPL], sd[RPL], ss[RPL];  // ADAPT: the row's inflation and x'.x'; SEC: x'.x'
     bool live[RPL];
     bool touched[RPL];  // FUSED: some ob moved the row (a row no ob reaches goes out as it came in, see the store below)
     long row[RPL];
@@ -72,10 +80,10 @@ __global__ __launch_bounds__(256, gc_quad_waves(FAM, NC, RPL)) void k_sweep_gc(c
       }
       if (FUSED) {  // prior members in: remove the ensemble mean (assimilation.py:146-147)
         xm[q] = group_rowsum<L, NC>(x[q]) / (double)M;
-        if (ADAPT) ss[q] = group_centered_sumsq<L, NC>(x[q], xm[q], M, j);
+        if (ADAPT || SEC) ss[q] = group_centered_sumsq<L, NC>(x[q], xm[q], M, j);
 #pragma unroll
         for (int c = 0; c < 2 * NC; ++c) x[q][c] -= xm[q];  // padding slots never reach the output or the dot
-      } else if (ADAPT) {
+      } else if (ADAPT || SEC) {
         ss[q] = group_centered_sumsq<L, NC>(x[q], 0.0, M, j);
       }
       if (ADAPT) {
@@ -116,6 +124,8 @@ __global__ __launch_bounds__(256, gc_quad_waves(FAM, NC, RPL)) void k_sweep_gc(c
       }
       if (ADAPT)
         for (int i = tid; i < 2 * ne; i += 256) ao_s[i] = reinterpret_cast<const double2*>(a.adapt_ob + (size_t)a.idx[c0 + (i >> 1)] * 4)[i & 1];
+      if (SEC)
+        for (int i = tid; i < ne; i += 256) yy_s[i] = a.adapt_ob[(size_t)a.idx[c0 + i] * 4 + 3];
       if (VLOC)
         for (int i = tid; i < ne * NS; i += 256) {
           const int ee = i / NS, lead = lead0 + (i - ee * NS);
@@ -144,6 +154,8 @@ __global__ __launch_bounds__(256, gc_quad_waves(FAM, NC, RPL)) void k_sweep_gc(c
           o01 = ao_s[2 * ee];
           o23 = ao_s[2 * ee + 1];
         }
+        double yy = 0.0;
+        if (SEC) yy = yy_s[ee];
 #pragma unroll
         for (int q = 0; q < RPL; ++q) {
           if (RPL > 2 && lead0 + 4 * q >= lead_hi) continue;  // wave-uniform: this slot is beyond the last slab in every quad
@@ -154,6 +166,11 @@ __global__ __launch_bounds__(256, gc_quad_waves(FAM, NC, RPL)) void k_sweep_gc(c
             abr.x = ab.x * v;
             abr.y = ab.y * v;
           }
+          if (SEC) {  // both gain scalars times the factor of the pair's correlation, row and ob as they are before the ob (1: unchanged bit for bit)
+            const double al = sec(dot, ss[q], yy);
+            abr.x = ab.x * al;
+            abr.y = ab.y * al;
+          }
           xm[q] = __builtin_fma(abr.y, dot, xm[q]);      // :115, :119, :130
           const double kb = abr.x * dot;                 // :115, :119, :136
           if (FUSED) touched[q] = touched[q] || (abr.x != 0.0);
@@ -161,6 +178,7 @@ __global__ __launch_bounds__(256, gc_quad_waves(FAM, NC, RPL)) void k_sweep_gc(c
             anderson_update(lam[q], sd[q], aw, dot, ss[q], o01, o23, a.infl_lower, a.infl_upper, a.infl_sd_lower);
             ss[q] = adapt_ss_after(ss[q], kb, dot, o23.y);
           }
+          if (SEC) ss[q] = adapt_ss_after(ss[q], kb, dot, yy);
 #pragma unroll
           for (int c = 0; c < 2 * NC; ++c) x[q][c] = __builtin_fma(-kb, y[c], x[q][c]);  // :141
         }
@@ -196,6 +214,7 @@ __global__ __launch_bounds__(256, gc_lane_waves(FAM, MP)) void k_sweep_gc_lane(c
   constexpr bool ADAPT = FAM == kGcAdapt;
   constexpr bool VLOC = FAM == kGcVloc || FAM == kGcSlab;
   constexpr bool SLAB = FAM == kGcSlab;  // VLOC with the factor read from the slab table
+  constexpr bool SEC = FAM == kGcSec;
   static_assert(!(ADAPT && VLOC), "adaptive inflation with vertical localisation is not built");
   static_assert(VLOC || !SLAB, "the slab table is a form of the per-slab factor");
   static_assert(sizeof(E) == sizeof(double) || (FUSED && !ADAPT), "float32 rows: member form, no adaptive inflation");
@@ -206,6 +225,8 @@ __global__ __launch_bounds__(256, gc_lane_waves(FAM, MP)) void k_sweep_gc_lane(c
   __shared__ __align__(16) double aw_s[ADAPT ? kChunkL * kBlkCols : 1];  // ADAPT: as in k_sweep_gc
   __shared__ __align__(16) double2 ao_s[ADAPT ? 2 * kChunkL : 1];
   __shared__ __align__(16) double vf_s[VLOC ? kChunkL * 16 : 1];  // VLOC: the vertical factor per (staged ob, slab of the group), 0 beyond the last
+  __shared__ __align__(16) double sec_s[SEC ? kSecMaxT : 1];      // SEC: as in k_sweep_gc
+  __shared__ __align__(16) double yy_s[SEC ? kChunkL : 1];
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   // One workgroup per (column block, group of 16 slabs), blocks longest list first, a block's groups next to each other (its
@@ -222,6 +243,9 @@ __global__ __launch_bounds__(256, gc_lane_waves(FAM, MP)) void k_sweep_gc_lane(c
   const double rM1 = 1.0 / (double)(M - 1);
   const long e0 = a.off[b], e1 = e0 + a.cnt[b];
   const auto seq = std::make_integer_sequence<int, MP>{};
+  const SecLookup sec{sec_s, SEC ? a.sec_T : 2};
+  if (SEC)  // (read behind the barriers of the first chunk's staging)
+    for (int i = tid; i < a.sec_T; i += 256) sec_s[i] = a.sec_tab[i];
 
   for (int lead0 = lead_lo; lead0 < lead_hi; lead0 += 16) {
     // 16 slabs x 4 columns per wave; the last group of a block: the next power of two of what is left, more columns per wave
@@ -236,7 +260,7 @@ __global__ __launch_bounds__(256, gc_lane_waves(FAM, MP)) void k_sweep_gc_lane(c
     const long row = (long)lead * a.ncol + col;
     double x[MP];
     double xm = 0.0;
-    double lam = 1.0, sd = 0.0, ss = 0.0;  // ADAPT: the row's inflation and x'.x'
+    double lam = 1.0, sd = 0.0, ss = 0.0;  // ADAPT: the row's inflation and x'.x'; SEC: x'.x'
     bool touched = false;                  // FUSED: some ob moved the row
     if (live && sizeof(E) != sizeof(double)) {
       const float* pf = reinterpret_cast<const float*>(a.Xin) + (size_t)row * M;
@@ -297,6 +321,8 @@ __global__ __launch_bounds__(256, gc_lane_waves(FAM, MP)) void k_sweep_gc_lane(c
       if (ADAPT) {
         lam = a.infl[2 * row];
         sd = a.infl[2 * row + 1];
+      }
+      if (ADAPT || SEC) {
         double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
 #pragma unroll
         for (int i = 0; i < MP; i += 4) {  // (padding slots hold 0)
@@ -332,6 +358,8 @@ __global__ __launch_bounds__(256, gc_lane_waves(FAM, MP)) void k_sweep_gc_lane(c
       }
       if (ADAPT)
         for (int i = tid; i < 2 * ne; i += 256) ao_s[i] = reinterpret_cast<const double2*>(a.adapt_ob + (size_t)a.idx[c0 + (i >> 1)] * 4)[i & 1];
+      if (SEC)
+        for (int i = tid; i < ne; i += 256) yy_s[i] = a.adapt_ob[(size_t)a.idx[c0 + i] * 4 + 3];
       if (VLOC)
         for (int i = tid; i < ne * 16; i += 256) {
           const int lead_i = lead0 + (i & 15);
@@ -377,6 +405,13 @@ __global__ __launch_bounds__(256, gc_lane_waves(FAM, MP)) void k_sweep_gc_lane(c
           abn.x *= vn;
           abn.y *= vn;
         }
+        double yy = 0.0;
+        if (SEC) {  // both gain scalars times the factor of the pair's correlation, as in k_sweep_gc
+          yy = yy_s[ee];
+          const double al = sec(dot, ss, yy);
+          ab.x *= al;
+          ab.y *= al;
+        }
         xm = __builtin_fma(ab.y, dot, xm);               // :115, :119, :130
         const double nkb = -(ab.x * dot);                // :115, :119, :136
         if (FUSED) touched = touched || (ab.x != 0.0);
@@ -389,6 +424,7 @@ __global__ __launch_bounds__(256, gc_lane_waves(FAM, MP)) void k_sweep_gc_lane(c
 #pragma unroll
           for (int c = 0; c < NG; ++c) y[c] = yq[en * YS + 16 * c];
         } else {
+          if (SEC) ss = adapt_ss_after(ss, ab.x * dot, dot, yy);
           lane_update_prefetch<MP>(x, y, nkb, yq + en * YS);  // :141
         }
         if (todo == 0ull) break;

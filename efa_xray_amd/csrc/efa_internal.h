@@ -36,6 +36,8 @@ inline size_t elem_size(Elem e) { return e == Elem::f32 ? sizeof(float) : sizeof
 constexpr int kMaxMembers = 256;
 // Rows (observations) handled by one obs-space diag workgroup == max obs_batch.
 constexpr int kMaxBatch = 64;
+// Nodes of the largest sampling-error-correction table: the one-pass sweep stages it in 4 KB of LDS.
+constexpr int kSecMaxT = 512;
 
 // Per-observation coefficients recorded by Phase A (4 doubles per ob):
 //   [0] innov   = ob.value - mye                     (ensrf.py:85)
@@ -71,6 +73,9 @@ struct SweepArgs {
   const double* ob_hw;
   long skip_lo, skip_hi;  // rows in [skip_lo, skip_hi) are not touched
   long taper_rows;        // kTaperObs applies to rows < taper_rows (extra rows: weight 1)
+  // sampling error correction; sec_tab == null: off.  Phase A's one-ob batches only (nb == 1)
+  const double* sec_tab;  // [sec_T] the factor at |r| = j / (sec_T - 1), device
+  int sec_T;
 };
 
 struct DiagArgs {
@@ -200,6 +205,10 @@ struct GcSweepArgs {
   const double* ob_vhw;     // [P] their vertical half-widths (1 where ob_vert is NaN)
   // slab table; null: off.  It carries the vertical factor as well: the slab family serves the call
   const double* slab_tab;   // [P][n_lead] the factor of every (ob, slab) pair (launch_slab_factor)
+  // sampling error correction; sec_tab == null: off (exclusive with the three above).  It reads y'.y' of each ob
+  // from adapt_ob, the record of the adaptive-inflation family
+  const double* sec_tab;    // [sec_T] the factor at |r| = j / (sec_T - 1), device
+  int sec_T;                // 2 .. kSecMaxT
 };
 long gc_num_blocks(long ncol);
 // list build in one pass: upper bounds + device prefix sum (off[nblk] = capacity needed), then the entries
@@ -217,6 +226,8 @@ hipError_t launch_gc_count(long ncol, long P, const double* glat, const double* 
 // elem: the element type a.Xin / a.Xout point at.  float32 is the member form on the row-per-lane kernel:
 // sweep_gc_serves says which cycles that is (an even M up to 104), whatever the alignment of the rows; float64 serves every cycle
 bool sweep_gc_serves(Elem elem, int M, long ye_stride, const double* Ye);
+// the form launch_sweep_gc runs the call in: 2 the row-per-lane kernel, 1 the quad kernel (the option "gc_form")
+int sweep_gc_form(const GcSweepArgs& a, Elem elem);
 hipError_t launch_sweep_gc(const GcSweepArgs& a, Elem elem, hipStream_t s);
 
 // ---- observation impact (EFSO, efa_impact.hip) ----------------------------------

@@ -201,7 +201,8 @@ int start_phase_a(efa_ctx* c, ObsCall& a) {
   if (c->timing) EFA_HIP(hipEventRecord(c->obs_iv.begin, s));
   const long Wone = (long)kPipeMaxWGs * kPipeRowsPerWG - a.extra;           // one window covers the block up to here
   a.Wmax = (P <= Wone) ? Wone : Wone - a.extra;                              // else: two sets of extra rows per window
-  a.pipe_ok = c->use_pipeline && a.Wmax > 0 && pipeline_supported(M, (P <= Wone ? P + a.extra : a.Wmax + 2 * a.extra));
+  // (the persistent leaders rest on a gain that is linear in the row, which the sampling error correction's is not: per-batch kernels)
+  a.pipe_ok = c->use_pipeline && !sec_active(c) && a.Wmax > 0 && pipeline_supported(M, (P <= Wone ? P + a.extra : a.Wmax + 2 * a.extra));
   a.TS_std = traj_stride(M);
   a.TS_band = band_traj_stride(M);
   a.TS = a.TS_std > a.TS_band ? a.TS_std : a.TS_band;
@@ -269,6 +270,10 @@ int sweep_rows(efa_ctx* c, const ObsCall& a, long b0, int nb, const double* Ye, 
   sw.skip_lo = skip_lo;
   sw.skip_hi = skip_hi;
   sw.taper_rows = a.P;
+  if (sec_active(c)) {  // (batch_window: one ob per batch)
+    sw.sec_tab = c->sec_dev.as<double>();
+    sw.sec_T = c->sec_T;
+  }
   EFA_HIP(launch_sweep(sw, c->stream));
   return EFA_OK;
 }
@@ -281,9 +286,9 @@ long active_in(const ObsCall& a, long b0, int nb) {
 
 // obs [w0, w1) by the per-batch kernels (k_diag on the batch's own rows, k_sweep on every other row of the block)
 // (With vertical or slab localisation one ob per batch: k_diag's in-batch taper is horizontal only, and an ob's taper against itself
-// is 1.)
+// is 1.  With the sampling error correction likewise: k_diag applies none, and an ob's factor against itself is 1)
 int batch_window(efa_ctx* c, const ObsCall& a, long w0, long w1) {
-  const long B = (a.loc_mode == EFA_LOC_GC && (vl_active(c) || sl_active(c))) ? 1 : a.B;
+  const long B = (a.loc_mode == EFA_LOC_GC && (vl_active(c) || sl_active(c) || sec_active(c))) ? 1 : a.B;
   for (long b0 = w0; b0 < w1; b0 += B) {
     const int nb = (int)((w1 - b0 < B) ? (w1 - b0) : B);
     DiagArgs d{};
@@ -598,6 +603,7 @@ int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const d
   if (loc_mode != EFA_LOC_NONE && loc_mode != EFA_LOC_GC) return fail(EFA_ERR_INVALID, "loc_mode %d", loc_mode);
   EFA_TRY(check_vloc(c, loc_mode, P, -1));
   EFA_TRY(check_slab(c, loc_mode, P, -1));
+  EFA_TRY(check_sec(c, loc_mode));
   c->have_traj = false;
   c->M = M;
   c->P = P;

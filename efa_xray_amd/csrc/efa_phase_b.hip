@@ -80,6 +80,20 @@ int check_slab(const efa_ctx* c, int loc_mode, long P, long n_lead) {
   return EFA_OK;
 }
 
+// ---- sampling error correction (the kGcSec sweep kernels and k_sweep_sec) -----------------------------------
+// The factor depends on the row's current correlation: only the kernels that hold a row while they walk its obs in order apply it.
+int check_sec(const efa_ctx* c, int loc_mode) {
+  if (!sec_active(c)) return EFA_OK;
+  if (loc_mode != EFA_LOC_GC)
+    return fail(EFA_ERR_INVALID, "sampling error correction is set: it needs GC localisation (loc_mode %d is not EFA_LOC_GC)", loc_mode);
+  if (!c->gc_onepass)
+    return fail(EFA_ERR_INVALID, "sampling error correction is set: it needs the one-pass GC sweep (option gc_onepass is 0)");
+  if (c->ai_field) return fail(EFA_ERR_INVALID, "sampling error correction is set: adaptive inflation cannot be combined with it");
+  if (c->vl_on) return fail(EFA_ERR_INVALID, "sampling error correction is set: vertical localisation cannot be combined with it");
+  if (c->sl_on) return fail(EFA_ERR_INVALID, "sampling error correction is set: slab localisation cannot be combined with it");
+  return EFA_OK;
+}
+
 // The table depends on the two settings alone (not on the obs' positions): it is written once per change of either, on the
 // context's stream, in front of the sweep that reads it.
 int ensure_slab_table(efa_ctx* c) {
@@ -290,7 +304,16 @@ int state_gc_onepass(efa_ctx* c, const StateRows& r, const double* xm_in, double
     EFA_TRY(ensure_slab_table(c));
     g.slab_tab = c->sl_tab.as<double>();
   }
-  c->gc_family_used = g.infl ? 1 : g.slab_tab ? 3 : g.lead_vert ? 2 : 0;
+  if (sec_active(c)) {  // y'.y' of every ob, in the record of the inflation update (check_sec: that one is off)
+    EFA_TRY(c->sec_ob.reserve((size_t)(P ? P : 1) * 4 * sizeof(double)));
+    EFA_HIP(launch_adapt_obs(P, M, c->coef.as<double>(), c->d_prior_var, c->ob_err, c->ye_ptr, c->ye_stride, c->sec_ob.as<double>(), s));
+    ++*nl;
+    g.adapt_ob = c->sec_ob.as<double>();
+    g.sec_tab = c->sec_dev.as<double>();
+    g.sec_T = c->sec_T;
+  }
+  c->gc_family_used = g.infl ? 1 : g.sec_tab ? 4 : g.slab_tab ? 3 : g.lead_vert ? 2 : 0;
+  c->gc_form_used = sweep_gc_form(g, r.elem);
   EFA_HIP(launch_sweep_gc(g, r.elem, s));
   ++*nl;
   return EFA_OK;
@@ -428,6 +451,7 @@ int begin_state_call(efa_ctx* c, const char* who, long rows, int M, bool ptrs_ok
   EFA_TRY(check_adaptive(c, c->loc_mode, rows));
   EFA_TRY(check_vloc(c, c->loc_mode, c->P, n_lead));
   EFA_TRY(check_slab(c, c->loc_mode, c->P, n_lead));
+  EFA_TRY(check_sec(c, c->loc_mode));
   harvest_state_ms(c);  // the arguments are checked: the previous interval is read, the counters cleared
   c->state_ms = 0.0;
   c->state_launches = 0;

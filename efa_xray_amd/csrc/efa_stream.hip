@@ -269,6 +269,7 @@ int cycle_host(efa_ctx* c, size_t esz, int n_seg, const void* const* seg_prior, 
   const auto t0 = std::chrono::steady_clock::now();
   if (c->ai_field)
     return fail(EFA_ERR_INVALID, "%s: an adaptive-inflation field is set (its update needs the whole state resident)", who);
+  if (sec_active(c)) return fail(EFA_ERR_INVALID, "%s: sampling error correction is set (the streamed update does not offer it)", who);
   if (n_seg < 0 || ncol < 0 || P < 0) return fail(EFA_ERR_INVALID, "%s: negative n_seg, ncol or P", who);
   if (M < 2) return fail(EFA_ERR_INVALID, "ensemble size M=%d must be >= 2 (covariance divides by M-1)", M);
   if (chunk_cols < 1) return fail(EFA_ERR_INVALID, "%s: chunk_cols=%ld must be >= 1", who, chunk_cols);

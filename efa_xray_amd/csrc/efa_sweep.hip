@@ -32,9 +32,12 @@ constexpr int kThreads = 256;
 // ---------------------------------------------------------------------------
 // Sweep: rows x batch.
 // LDS: ye_s[nb][S] (zero padded, S = 2*L*NC) then coef_s[nb][4].
+// SEC: the gain of every (row, ob) pair times the sampling-error-correction factor of the pair's sample correlation (DESIGN.md
+// §7w), both norms taken from the row and the ye row as they are when the ob is applied (Phase A's one-ob batches: a few
+// thousand rows, the table read from L2).
 // ---------------------------------------------------------------------------
-template <int L, int NC, bool VEC>
-__global__ __launch_bounds__(kThreads) void k_sweep(const SweepArgs a) {
+template <int L, int NC, bool VEC, bool SEC>
+__device__ __forceinline__ void sweep_body(const SweepArgs& a) {
   extern __shared__ __align__(16) double smem[];
   constexpr int S = 2 * L * NC;
   constexpr int kRowsPerBlock = kThreads / L;
@@ -94,6 +97,15 @@ __global__ __launch_bounds__(kThreads) void k_sweep(const SweepArgs a) {
       const double dot = group_dot<L, NC>(x, y);
       double kc = dot * rM1;         // kcov = dot/(Nens-1)
       kc = w * kc;                   // localisation
+      if (SEC) {                     // sampling error correction: |r| = |dot| rsqrt(x'.x' y'.y'), 0 when either norm is 0
+        const double nn = group_dot<L, NC>(x, x) * group_dot<L, NC>(y, y);
+        const double r = (nn > 0.0) ? fabs(dot) * rsqrt(nn) : 0.0;
+        const double t = fmin(r, 1.0) * (double)(a.sec_T - 1);  // (fmin: a NaN reads the last interval, never beyond the table)
+        int jt = (int)t;
+        jt = (jt < a.sec_T - 2) ? jt : a.sec_T - 2;
+        const double a0 = a.sec_tab[jt], a1 = a.sec_tab[jt + 1];
+        kc = (a0 + (t - (double)jt) * (a1 - a0)) * kc;
+      }
       const double km = kc * ck[1];  // kmat = kcov/kdenom
       xm = xm + km * ck[0];          // xam = xbm + kmat*innov
       const double kb = ck[2] * km;  // beta*kmat
@@ -146,6 +158,16 @@ __global__ __launch_bounds__(kThreads) void k_sweep(const SweepArgs a) {
       if (j == 0) a.xout[row] = xm;
     }
   }
+}
+
+// the two kernels of the body: k_sweep, and k_sweep_sec with the correction
+template <int L, int NC, bool VEC>
+__global__ __launch_bounds__(kThreads) void k_sweep(const SweepArgs a) {
+  sweep_body<L, NC, VEC, false>(a);
+}
+template <int L, int NC, bool VEC>
+__global__ __launch_bounds__(kThreads) void k_sweep_sec(const SweepArgs a) {
+  sweep_body<L, NC, VEC, true>(a);
 }
 
 // ---------------------------------------------------------------------------
@@ -310,7 +332,7 @@ __global__ __launch_bounds__(kThreads) void k_diag(const DiagArgs a) {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-template <int L, int NC>
+template <int L, int NC, bool SEC>
 hipError_t sweep_launch(const SweepArgs& a, bool vec, hipStream_t s) {
   constexpr int kRowsPerBlock = kThreads / L;
   const long nblocks = (a.nrows + kRowsPerBlock - 1) / kRowsPerBlock;
@@ -318,17 +340,13 @@ hipError_t sweep_launch(const SweepArgs& a, bool vec, hipStream_t s) {
                       (a.taper_mode == kTaperTable ? (size_t)kRowsPerBlock * kMaxBatch : 0)) * sizeof(double);
   long grid = nblocks < 256L * 8 ? nblocks : 256L * 8;
   if (grid < 1) grid = 1;
+  void (*const kern)(const SweepArgs) = SEC ? (vec ? &k_sweep_sec<L, NC, true> : &k_sweep_sec<L, NC, false>)
+                                            : (vec ? &k_sweep<L, NC, true> : &k_sweep<L, NC, false>);
   if (lds > 64 * 1024) {
-    hipError_t e = vec ? hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sweep<L, NC, true>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                       : hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sweep<L, NC, false>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  if (vec)
-    hipLaunchKernelGGL((k_sweep<L, NC, true>), dim3((unsigned)grid), dim3(kThreads), lds, s, a);
-  else
-    hipLaunchKernelGGL((k_sweep<L, NC, false>), dim3((unsigned)grid), dim3(kThreads), lds, s, a);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), lds, s, a);
   return hipGetLastError();
 }
 
@@ -368,7 +386,11 @@ hipError_t launch_sweep(const SweepArgs& a, hipStream_t s) {
   if (a.M < 2 || a.M > kMaxMembers || a.nb < 1 || a.nb > kMaxBatch) return hipErrorInvalidValue;
   if (a.nrows <= 0) return hipSuccess;
   const bool vec = (a.M % 2 == 0) && (a.ye_stride % 2 == 0) && aligned16(a.Xin) && aligned16(a.Xout) && aligned16(a.Ye);
-  return dispatch_width(sweep_slots(a.M) / 8, SweepChunks{}, [&](auto nc) { return sweep_launch<4, nc>(a, vec, s); });
+  if (a.sec_tab) {  // the correction is built for the one-ob batches Phase A runs it with
+    if (a.nb != 1 || a.sec_T < 2 || a.sec_T > kSecMaxT) return hipErrorInvalidValue;
+    return dispatch_width(sweep_slots(a.M) / 8, SweepChunks{}, [&](auto nc) { return sweep_launch<4, nc, true>(a, vec, s); });
+  }
+  return dispatch_width(sweep_slots(a.M) / 8, SweepChunks{}, [&](auto nc) { return sweep_launch<4, nc, false>(a, vec, s); });
 }
 
 hipError_t launch_diag(const DiagArgs& a, hipStream_t s) {

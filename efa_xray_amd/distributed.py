@@ -152,6 +152,11 @@ class HipEngine(object):
         """Vertical localisation of the cycles that follow on this engine's context; lead_vert None: off."""
         self.ctx.set_vertical_localization(lead_vert, ob_vert, ob_vert_halfwidth)
 
+    def clear_sampling_error_correction(self):
+        """Sampling error correction off on this engine's context (an `EnSRF` on the same device may have left
+        it set; the sharded filter does not offer it)."""
+        self.ctx.set_sampling_error_correction(None)
+
     def clear_slab_localization(self):
         """Temporal / cross-variable localisation off on this engine's context (an `EnSRF` on the same device may
         have left it set; the sharded filter does not offer it)."""
@@ -221,6 +226,12 @@ class ShardedEnSRF(object):
         return t
 
     @staticmethod
+    def _reject_sec(sampling_error_correction):
+        """ValueError when the sampling error correction is asked for: it is EnSRF's, on one GPU."""
+        if sampling_error_correction is not None and sampling_error_correction is not False:
+            raise ValueError("ShardedEnSRF does not support sampling_error_correction (out of scope: use EnSRF on one GPU)")
+
+    @staticmethod
     def _reject_float32(*buffers):
         """ValueError for a float32 shard: the sharded path is float64 only."""
         for b in buffers:
@@ -252,7 +263,7 @@ class ShardedEnSRF(object):
         return HX
 
     def assimilate(self, X_local, post_local, HX, ob, grid_lat=None, grid_lon=None, rtps=None, rtpp=None,
-                   adaptive_inflation=None, vert_coord=None, outlier_threshold=None):
+                   adaptive_inflation=None, vert_coord=None, outlier_threshold=None, sampling_error_correction=None):
         """Stage 2, after HX has been summed over the shards: obs-space priors, Phase A
         (replicated: identical on every rank) and the sweep of this shard's rows.  `rtps` / `rtpp`:
         posterior relaxation of the shard's rows as in `EnSRF` (row-local: no communication).
@@ -261,6 +272,7 @@ class ShardedEnSRF(object):
         gross-error check as in `EnSRF`; every rank decides alike, from the same summed obs block."""
         if adaptive_inflation is not None:
             raise ValueError("ShardedEnSRF does not support adaptive_inflation (out of scope: use EnSRF on one GPU)")
+        self._reject_sec(sampling_error_correction)
         self._reject_float32(X_local, post_local)
         eng, M = self.engine, self.M
         relax = relaxation_setting(rtps, rtpp)
@@ -281,6 +293,8 @@ class ShardedEnSRF(object):
             raise ValueError("this engine does not support vertical localisation")
         if hasattr(eng, "clear_slab_localization"):
             eng.clear_slab_localization()                                  # every call (the context is shared per device)
+        if hasattr(eng, "clear_sampling_error_correction"):
+            eng.clear_sampling_error_correction()                          # likewise
         ym = eng.empty((max(P, 1),))
         eng.form_perts(P, M, HX, ym, HX)                                   # assimilation.py:46-48
         glat = glon = None
@@ -294,9 +308,11 @@ class ShardedEnSRF(object):
         return diag
 
     def update(self, X_local, post_local, sten_idx, sten_wts, ob, grid_lat=None, grid_lon=None, inflation=None,
-               rtps=None, rtpp=None, adaptive_inflation=None, vert_coord=None, outlier_threshold=None):
+               rtps=None, rtpp=None, adaptive_inflation=None, vert_coord=None, outlier_threshold=None,
+               sampling_error_correction=None):
         if adaptive_inflation is not None:
             raise ValueError("ShardedEnSRF does not support adaptive_inflation (out of scope: use EnSRF on one GPU)")
+        self._reject_sec(sampling_error_correction)
         self._reject_float32(X_local, post_local)
         self._vertical(ob, vert_coord, int(np.asarray(sten_idx).shape[0]))  # (refused before any work)
         outlier_setting(outlier_threshold)

@@ -97,7 +97,9 @@ int efa_ctx_set_stream(efa_ctx *ctx, void *hip_stream);
  *          "gc_active_pairs"
  *          ((column, ob) pairs with a non-zero taper in the last one-pass sweep),
  *          "gc_family" (the kernel family of the last one-pass sweep: 0 plain, 1 adaptive inflation, 2 vertical factor,
- *          3 slab table; -1: none ran yet),
+ *          3 slab table, 4 sampling error correction; -1: none ran yet),
+ *          "gc_form" (its kernel form: 1 quad per row, 2 row per lane; 0: none ran yet),
+ *          "sec_on" (see efa_ctx_set_sampling_error_correction),
  *          "f32_native" (see efa_state_cycle_f32_dev), "impact_us" (see efa_obs_impact_dev),
  *          "sens_us" (see efa_sensitivity_dev), "verify_us" (see efa_verify_dev),
  *          "products_us" (see efa_products_dev), "gram_us" (see efa_gram_dev);
@@ -227,6 +229,31 @@ int efa_slab_factor_table(efa_ctx *ctx, long P, long n_lead, double *table);
  * assimilated[k] = 0.  0 turns it off (the default); a negative, NaN or
  * infinite threshold fails with EFA_ERR_INVALID. */
 int efa_ctx_set_outlier_threshold(efa_ctx *ctx, double threshold);
+
+/* ---- sampling error correction (Anderson 2012) --------------
+ * Context state like the relaxation, for every later GC cycle
+ * (efa_obs_phase_dev, efa_state_phase_dev, efa_state_cycle_dev,
+ * efa_state_cycle_f32_dev, efa_ensrf_update_dev, efa_ensrf_cycle_dev,
+ * efa_ensrf_update).  alpha: a host table of T nodes, 2 <= T <= 512, node j
+ * at |r| = j/(T-1), every value finite and >= 0; it is copied.  The gain of
+ * ob k on row i (state rows and the rows of the obs block alike) becomes
+ *   alpha(|r|) * taper * cov(x_i, y_k) / (var(y_k) + error_k),
+ * r the sample correlation of the row and the ob as they are when ob k is
+ * reached in serial order (0 if either has no spread), alpha read from the
+ * table piecewise linearly (|r| > 1 reads the last node); ob k's own row takes
+ * alpha = 1.  A pair with a zero taper leaves the row bit for bit as it is,
+ * and a table of ones gives the results of the call without the setting.
+ * While it is set a call must use EFA_LOC_GC with "gc_onepass" 1 and none of
+ * adaptive inflation, vertical or slab localisation: any other call fails
+ * with EFA_ERR_INVALID before it launches anything.  Phase A then runs its
+ * per-batch kernels one ob at a time ("phase_a_kind" reads 2).  The
+ * relaxation, the outlier check and float32 rows combine with it; the
+ * streamed update (efa_ensrf_cycle_host, _f32) refuses it likewise.
+ * efa_obs_impact_dev is not changed by it: the impact assumes the
+ * uncorrected gain.  NULL or T == 0 turns it off (the default); a bad T or a
+ * negative, NaN or infinite value fails with EFA_ERR_INVALID and leaves the
+ * setting as it was.  Read-only option "sec_on": 1 while a table is set. */
+int efa_ctx_set_sampling_error_correction(efa_ctx *ctx, const double *alpha, int T);
 int efa_ctx_synchronize(efa_ctx *ctx);
 
 /* ---- device memory for callers without their own allocator -------------*/
