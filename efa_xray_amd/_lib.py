@@ -59,6 +59,8 @@ SIGNATURES = {
     "efa_slab_factor_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_double_p]),
     "efa_ctx_set_outlier_threshold": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double]),
     "efa_ctx_set_sampling_error_correction": (ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_int]),
+    "efa_etkf_solution": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p,
+                                         ctypes.POINTER(ctypes.c_long)]),
     "efa_ctx_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
     "efa_malloc": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, c_void_pp]),
     "efa_free": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
@@ -786,6 +788,19 @@ class Context(object):
             _dp(d["post_var"]), _u8p(d["assimilated"])))
         d["assimilated"] = d["assimilated"].astype(bool)
         return d
+
+    def etkf_solution(self, M):
+        """efa_etkf_solution: the batch solve of the last obs phase, which must have run with option "obs_solver" 1,
+        as a dict: T (M, M), w (M,), eigenvalues (M,) of C descending, n_active, q, dfs, chi2, sweeps."""
+        M = int(M)
+        T = np.empty((max(M, 0), max(M, 0)))
+        w = np.empty(max(M, 0))
+        eig = np.empty(max(M, 0))
+        stats = np.zeros(4)
+        sweeps = ctypes.c_long(0)
+        _check(self.lib, self.lib.efa_etkf_solution(self.handle, M, _dp(T), _dp(w), _dp(eig), _dp(stats), ctypes.byref(sweeps)))
+        return dict(T=T, w=w, eigenvalues=eig, n_active=int(stats[0]), q=float(stats[1]), dfs=float(stats[2]),
+                    chi2=float(stats[3]), sweeps=int(sweeps.value))
 
     def state_phase(self, rows, M, xm_in, Xp_in, xm_out, Xp_out, grid_lat=None, grid_lon=None, n_lead=1):
         loc_mode = LOC_GC if grid_lat is not None else LOC_NONE

@@ -340,6 +340,7 @@ class EnSRF(Assimilation):
         path = {None: _lib.PATH_AUTO, "auto": _lib.PATH_AUTO, "sweep": _lib.PATH_SWEEP,
                 "transform": _lib.PATH_TRANSFORM}[self.path]
         ctx.set_option("path", path)
+        ctx.set_option("obs_solver", 0)        # the serial loop (ETKF sets 1 behind this): every call, the context is shared per device
         ctx.set_relaxation(*self.relaxation)   # every call: the context is shared per device
         ctx.set_adaptive_inflation(None)        # set by update() around its own cycle only
         ctx.set_outlier_threshold(self.outlier_threshold)  # every call, "off" included

@@ -3,6 +3,7 @@
 #include "efa_driver.h"
 
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -207,6 +208,9 @@ int efa_ctx_set_option(efa_ctx* c, const char* key, long value) {
     c->use_gram = value;
   } else if (!strcmp(key, "pipeline")) {
     c->use_pipeline = value ? 1 : 0;
+  } else if (!strcmp(key, "obs_solver")) {
+    if (value < 0 || value > 1) return fail(EFA_ERR_INVALID, "obs_solver must be 0 (serial) or 1 (batch)");
+    c->obs_solver = value;
   } else if (!strcmp(key, "gc_onepass")) {
     c->gc_onepass = value ? 1 : 0;
   } else if (!strcmp(key, "geometry_reuse")) {
@@ -462,6 +466,7 @@ int efa_ctx_get_option(efa_ctx* c, const char* key, long* value) {
   else if (!strcmp(key, "timing")) *value = c->timing;
   else if (!strcmp(key, "gram")) *value = c->use_gram;
   else if (!strcmp(key, "pipeline")) *value = c->use_pipeline;
+  else if (!strcmp(key, "obs_solver")) *value = c->obs_solver;
   else if (!strcmp(key, "gc_onepass")) *value = c->gc_onepass;
   else if (!strcmp(key, "gc_family")) *value = c->gc_family_used;  // the last one-pass sweep: 0 plain, 1 adaptive, 2 vertical, 3 slab table, 4 SEC
   else if (!strcmp(key, "gc_form")) *value = c->gc_form_used;  // the last one-pass sweep: 1 quad kernel, 2 row-per-lane kernel
@@ -704,6 +709,7 @@ int efa_ensrf_update_dev(efa_ctx* c, long rows, int M, long P, double* xm_dev, d
   EFA_TRY(check_vloc(c, loc_mode, P, n_lead));
   EFA_TRY(check_slab(c, loc_mode, P, n_lead));
   EFA_TRY(check_sec(c, loc_mode));
+  EFA_TRY(check_batch_solver(c, loc_mode));
   EFA_TRY(obs_phase(c, M, P, ym_dev, Yp_dev, ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon,
                     ob_halfwidth_km, prior_mean, prior_var, post_mean, post_var, assimilated));
   EFA_TRY(state_phase(c, rows, M, xm_dev, Xp_dev, xm_dev, Xp_dev, grid_lat, grid_lon, ncol, n_lead));
@@ -723,6 +729,7 @@ int efa_ensrf_cycle_dev(efa_ctx* c, long rows, int M, long P, const double* X_de
   EFA_TRY(check_vloc(c, loc_mode, P, n_lead));
   EFA_TRY(check_slab(c, loc_mode, P, n_lead));
   EFA_TRY(check_sec(c, loc_mode));
+  EFA_TRY(check_batch_solver(c, loc_mode));
   // Phase B may go into the stream before Phase A's status is known only if a wrong guess cannot cost the prior:
   // separate prior and posterior buffers (a redone Phase A needs the transform run again on the untouched prior)
   const StateRows r{X_dev, post_dev, Elem::f64, rows, M};
@@ -758,6 +765,8 @@ int efa_ensrf_update(efa_ctx* c, long A, long N, int M, long P, double* xbm, dou
   if (N < 0 || P < 0 || A != N + P) return fail(EFA_ERR_INVALID, "A=%ld must equal N+P=%ld+%ld", A, N, P);
   EFA_TRY(check_common(M, P));
   if (A && (!xbm || !Xbp)) return fail(EFA_ERR_INVALID, "null xbm/Xbp");
+  EFA_TRY(check_batch_solver(c, loc_mode));  // (before the first copy)
+  EFA_TRY(check_batch_obs(c, P, ob_error, ob_assim));
   const size_t rowb = (size_t)M * sizeof(double);
   EFA_TRY(c->h_xm.reserve((size_t)(N ? N : 1) * sizeof(double)));
   EFA_TRY(c->h_Xp.reserve((size_t)(N ? N : 1) * rowb));
@@ -912,6 +921,45 @@ int efa_pm_mean_f32_dev(efa_ctx* c, long rows, int M, const float* X_dev, long n
                         const int* slab_on, long py, long px, int pick, double* pm_dev, long long* n_bad) {
   EFA_TRY(use(c));
   return efa_host::pm_mean(c, efa::Elem::f32, rows, M, X_dev, ny, nx, n_lead, rank_dev, slab_on, py, px, pick, pm_dev, n_bad);
+}
+
+int efa_etkf_solution(efa_ctx* c, int M, double* T, double* w, double* eig, double* stats, long* sweeps) {
+  EFA_TRY(use(c));
+  if (!c->have_traj || !c->batch_solved)
+    return fail(EFA_ERR_INVALID, "efa_etkf_solution: the last obs phase did not run the batch solver (option obs_solver 1)");
+  if (M != c->M) return fail(EFA_ERR_INVALID, "efa_etkf_solution: M=%d differs from the obs phase's M=%d", M, c->M);
+  const long P = c->P;
+  const efa::EtkfWs ws = efa::etkf_ws(c->etkf_buf.as<double>(), M, P);
+  hipStream_t s = c->stream;
+  const size_t dM = (size_t)M * sizeof(double);
+  std::vector<double> h_w((size_t)M), h_g((size_t)M), h_mu((size_t)M);
+  double h_qs[2] = {0.0, 0.0};  // q | sweeps
+  EFA_HIP(hipMemcpyAsync(h_w.data(), c->ymw.as<double>() + P, dM, hipMemcpyDeviceToHost, s));
+  EFA_HIP(hipMemcpyAsync(h_g.data(), ws.g, dM, hipMemcpyDeviceToHost, s));
+  EFA_HIP(hipMemcpyAsync(h_mu.data(), ws.mu, dM, hipMemcpyDeviceToHost, s));
+  EFA_HIP(hipMemcpyAsync(h_qs, ws.q, sizeof(h_qs), hipMemcpyDeviceToHost, s));
+  if (T) EFA_HIP(hipMemcpyAsync(T, c->Yw.as<double>() + (size_t)P * M, (size_t)M * dM, hipMemcpyDeviceToHost, s));
+  EFA_HIP(hipStreamSynchronize(s));
+  std::sort(h_mu.begin(), h_mu.end(), [](double a, double b) {  // descending, NaNs last
+    if (std::isnan(b)) return !std::isnan(a);
+    return !std::isnan(a) && a > b;
+  });
+  double dfs = 0.0, gw = 0.0;
+  for (int i = 0; i < M; ++i) {
+    const double lam = h_mu[i] - (double)(M - 1);
+    if (eig) eig[i] = lam;
+    dfs += lam / h_mu[i];
+    gw += h_g[i] * h_w[i];
+  }
+  if (w) std::memcpy(w, h_w.data(), dM);
+  if (stats) {
+    stats[0] = (double)c->n_active;
+    stats[1] = h_qs[0];
+    stats[2] = dfs;
+    stats[3] = h_qs[0] - gw;
+  }
+  if (sweeps) *sweeps = (long)h_qs[1];
+  return EFA_OK;
 }
 
 int efa_last_timing(efa_ctx* c, double* state_ms, double* obs_ms, long* state_launches, int* path_taken) {

@@ -216,7 +216,7 @@ struct efa_ctx {
   DevBuf traj, tw_mat, status, dbg;  // pipeline: trajectory records, GC obs-obs taper, status words, stamps
   const double* ye_ptr = nullptr;  // where Phase B reads the recorded ye rows
   long ye_stride = 0;
-  int phase_a_kind = 0;          // 1 vector-chain pipeline, 2 per-batch kernels, 3 Gram leader, 4 band leader
+  int phase_a_kind = 0;          // 1 vector-chain pipeline, 2 per-batch kernels, 3 Gram leader, 4 band leader, 5 batch solver
   DevBuf ob_pack, out_pack;  // the per-ob inputs / diagnostics below are slices of these two allocations (stage_obs_inputs)
   PinBuf pin_in, pin_out;    // their pinned host images: one H2D and one D2H per call
   PinBuf pin_fs;             // pinned image of the forward-operator stencil
@@ -300,6 +300,10 @@ struct efa_ctx {
   double qc_threshold = 0.0;    // 0: off
   bool qc_used = false;         // the last obs phase ran it: its flags on the device may be fewer than the caller's
   DevBuf qc_act;                // [P][kCoefStride], GC: the caller's flags where the one-pass sweep's list builders read coef[3]
+  // --- batch observation-space solver (option "obs_solver", efa_etkf.hip) ------------------------------------------
+  long obs_solver = 0;          // 0 serial (Phase A's kernels), 1 batch (ETKF)
+  bool batch_solved = false;    // the last obs phase ran the batch solver: the state phase goes through [T | w], there are no records
+  DevBuf etkf_buf;              // its workspace (EtkfWs): scales, A, g, q, sweeps, mu, partial tiles
   // --- observation impact (efa_obs_impact_dev): buffers of its own, nothing above is touched by it ---------------
   //     (efa_obs_impact_slab_dev, §7u, brings sl_tab up to date as well: the table's cache, keyed by the two settings' serials)
   DevBuf imp_ob;    // per ob: used flags (coefficient-shaped) | scale | lat | lon | half-width | obtrig scratch | impact

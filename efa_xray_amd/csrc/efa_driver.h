@@ -10,6 +10,7 @@
 //   efa_neighbourhood.hip neighbourhood probabilities and the fractions skill score: its kernels and the driver of efa_neighbourhood_dev
 //   efa_pmmean.hip   the probability-matched mean and the segmented radix sort under it: its kernels and the driver of efa_pm_mean_dev
 //   efa_gram.hip     the ensemble Gram matrix: its kernels and the driver of efa_gram_dev
+//   efa_etkf.hip     the batch observation-space solver's kernels (option "obs_solver" 1; driven from efa_phase_a.hip)
 //   efa_comm.hip     RCCL
 // Headers the diagnostics share: efa_quadrow.h (the four-lane row layout of k_sens_pass, k_verify, k_products and k_nbr_records),
 // efa_sortnet.h (the bitonic network on it), efa_quadreduce.h (table flush, chunk partial, k_group_reduce) and efa_diag.h (their
@@ -83,6 +84,10 @@ inline efa::SlabObs sl_obs(const efa_ctx* c, long w0) {  // the obs' side from o
 // inflation, vertical or slab localisation (no combined kernel; Phase A then runs its one-ob batches)
 int check_sec(const efa_ctx* c, int loc_mode);
 inline bool sec_active(const efa_ctx* c) { return c->sec_T > 0; }
+// the batch solver (option "obs_solver" 1): refused with GC localisation, an adaptive-inflation field or path sweep;
+// and an assimilated ob's error variance must be finite and > 0 (efa_phase_a.hip; null arrays are left to the obs phase's own check)
+int check_batch_solver(const efa_ctx* c, int loc_mode);
+int check_batch_obs(const efa_ctx* c, long P, const double* ob_error, const uint8_t* ob_assim);
 // the slab table S[P][n_lead] on the device, rebuilt when the slab or the vertical setting changed since it was written
 int ensure_slab_table(efa_ctx* c);
 using efa::Elem;

@@ -345,6 +345,33 @@ hipError_t launch_phase_a_prep_qc(long P, int M, const double* Yp, const double*
                                   unsigned long long* traj, size_t traj_words, unsigned long long sentinel, int* status,
                                   const void* pack_host, void* pack_dev, size_t pack_bytes, size_t slot, double threshold,
                                   double* host_act, hipStream_t s);
+// ---- the batch observation-space solver (ETKF, efa_etkf.hip) ----------------------------------------------------
+constexpr int kEtkfLdsMaxM = 136;   // the eigen-solve keeps its M x M array in LDS up to here (148 KB), in global memory above
+constexpr int kEtkfSweepCap = 30;   // Jacobi sweeps at most (convergence leaves the counted loop early)
+// the solver's workspace, slices of one allocation of etkf_ws_doubles(M, P) doubles
+struct EtkfWs {
+  double* sc;      // [P] 1/sqrt(error) of an assimilated ob, 0 otherwise
+  double* dt;      // [P] the scaled innovation, 0 for an ob that is not assimilated
+  double* A;       // [M][M] (M-1) I + C; the eigen-solve works in it above kEtkfLdsMaxM members
+  double* g;       // [M]
+  double* q;       // [1]
+  double* sweeps;  // [1] Jacobi sweeps taken
+  double* mu;      // [M] eigenvalues of A, in the order of the columns
+  double* part;    // [streams][tiles][256] partial Gram tiles
+};
+size_t etkf_ws_doubles(int M, long P);
+EtkfWs etkf_ws(double* base, int M, long P);
+int etkf_tiles(int M);
+int etkf_streams(int M, long P);
+// prior diagnostics of every ob and the obs' scales, from the caller's block and the effective flags the prep launch wrote
+hipError_t launch_etkf_prior(long P, int M, const double* Yp, const double* ym, const double* ob_value, const double* ob_error,
+                             const uint8_t* ob_assim, double* prior_mean, double* prior_var, uint8_t* assimilated, const EtkfWs& w,
+                             hipStream_t s);
+// Gram contraction, its reduction and the eigen-solve: [T | w] to Tout [M][M], wout [M]; mu, g, q, sweeps stay in the workspace
+hipError_t launch_etkf_solve(long P, int M, const double* Yp, const EtkfWs& w, double* Tout, double* wout, hipStream_t s);
+// posterior diagnostics of the mapped obs rows
+hipError_t launch_etkf_post(long P, int M, const double* Yw, const double* ymw, double* post_mean, double* post_var, hipStream_t s);
+
 hipError_t launch_results_to_host(const void* src_dev, void* dst_host, size_t bytes, const int* st_dev, int* st_host, hipStream_t s);
 // diagnostic: `blocks` workgroups that hold `lds_bytes` of LDS each and spin for `ms` milliseconds
 hipError_t launch_occupy(int blocks, size_t lds_bytes, double ms, hipStream_t s);

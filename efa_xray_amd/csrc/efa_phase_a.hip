@@ -202,7 +202,8 @@ int start_phase_a(efa_ctx* c, ObsCall& a) {
   const long Wone = (long)kPipeMaxWGs * kPipeRowsPerWG - a.extra;           // one window covers the block up to here
   a.Wmax = (P <= Wone) ? Wone : Wone - a.extra;                              // else: two sets of extra rows per window
   // (the persistent leaders rest on a gain that is linear in the row, which the sampling error correction's is not: per-batch kernels)
-  a.pipe_ok = c->use_pipeline && !sec_active(c) && a.Wmax > 0 && pipeline_supported(M, (P <= Wone ? P + a.extra : a.Wmax + 2 * a.extra));
+  // (... and the batch solver walks no chain at all: no records, no status words)
+  a.pipe_ok = c->use_pipeline && !c->obs_solver && !sec_active(c) && a.Wmax > 0 && pipeline_supported(M, (P <= Wone ? P + a.extra : a.Wmax + 2 * a.extra));
   a.TS_std = traj_stride(M);
   a.TS_band = band_traj_stride(M);
   a.TS = a.TS_std > a.TS_band ? a.TS_std : a.TS_band;
@@ -593,7 +594,47 @@ int finish_obs_phase(efa_ctx* c, const ObsCall& a, Records layout, bool diag_on_
   return EFA_OK;
 }
 
+// ---- the batch solver (option "obs_solver" 1, efa_etkf.hip) -------------------------------------------------------
+// Behind the prep launch, which left the effective flags and the neutral (0, 1) of every ob that is not assimilated on the device:
+// the prior diagnostics and the obs' scales, the Gram contraction and the eigen-solve that leave [T | w] where the carried identity
+// rows stand, every obs row through them (perturbation form, from the caller's block into the working rows), the posterior
+// diagnostics, and ONE round trip.  efa_ensrf_cycle_dev's state transform goes into the stream behind all that before the host
+// waits -- nothing is speculated, the solver has no fallback -- unless the outlier check ran: the plan then needs its count.
+int batch_solve(efa_ctx* c, const ObsCall& a, SpecResult* spec) {
+  hipStream_t s = c->stream;
+  const int M = a.M;
+  const long P = a.P;
+  EFA_TRY(c->etkf_buf.reserve(etkf_ws_doubles(M, P) * sizeof(double)));
+  EFA_TRY(c->status.reserve(3 * sizeof(int)));
+  const EtkfWs w = etkf_ws(c->etkf_buf.as<double>(), M, P);
+  double *T = a.Yw + (size_t)P * M, *wv = a.ymw + P;
+  EFA_HIP(launch_etkf_prior(P, M, a.Yp_dev, a.ym_dev, c->ob_val, c->ob_err, c->ob_asm, c->d_prior_mean, c->d_prior_var,
+                            c->d_assimilated, w, s));
+  EFA_HIP(launch_etkf_solve(P, M, a.Yp_dev, w, T, wv, s));
+  const TransformArgs t{a.Yp_dev, a.ym_dev, a.Yw, a.ymw, P, M, T, wv, 0};
+  EFA_HIP(launch_transform(t, Elem::f64, s));
+  EFA_HIP(launch_etkf_post(P, M, a.Yw, a.ymw, c->d_post_mean, c->d_post_var, s));
+  int* st = reinterpret_cast<int*>(static_cast<char*>(c->pin_out.p) + 5 * a.oslot - 64);
+  EFA_HIP(launch_results_to_host(c->out_pack.p, c->pin_out.p, 4 * a.oslot + (size_t)P, c->status.as<int>(), st, s));  // (the status words: not read)
+  *spec = SpecResult{};
+  if (!c->qc_used) EFA_TRY(speculative_transform(c, a, make_window(a, 0), spec));
+  if (spec->launched) EFA_HIP(hipEventSynchronize(spec->interval->begin));
+  else EFA_HIP(hipStreamSynchronize(s));
+  if (spec->launched && c->timing) harvest_state_ms(c);
+  return EFA_OK;
+}
+
 }  // namespace
+
+// option "obs_solver" 1: an assimilated ob's error variance divides (the serial loop only adds it)
+int check_batch_obs(const efa_ctx* c, long P, const double* ob_error, const uint8_t* ob_assim) {
+  if (!c->obs_solver || !ob_error || !ob_assim) return EFA_OK;
+  for (long k = 0; k < P; ++k)
+    if (ob_assim[k] && !(std::isfinite(ob_error[k]) && ob_error[k] > 0.0))
+      return fail(EFA_ERR_INVALID, "observation %ld: error variance %g must be finite and > 0 for the batch solver (option obs_solver 1)", k,
+                  ob_error[k]);
+  return EFA_OK;
+}
 
 int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const double* ob_value,
               const double* ob_error, const uint8_t* ob_assim, int loc_mode, const double* ob_lat,
@@ -604,7 +645,10 @@ int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const d
   EFA_TRY(check_vloc(c, loc_mode, P, -1));
   EFA_TRY(check_slab(c, loc_mode, P, -1));
   EFA_TRY(check_sec(c, loc_mode));
+  EFA_TRY(check_batch_solver(c, loc_mode));
+  EFA_TRY(check_batch_obs(c, P, ob_error, ob_assim));
   c->have_traj = false;
+  c->batch_solved = false;
   c->M = M;
   c->P = P;
   c->loc_mode = loc_mode;
@@ -628,6 +672,15 @@ int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const d
   a.spec = spec;
   EFA_TRY(stage_obs_inputs(c, a, ob_value, ob_error, ob_lat, ob_lon, ob_hw));
   EFA_TRY(start_phase_a(c, a));
+  if (c->obs_solver) {
+    SpecResult done;
+    c->batch_solved = true;  // (the plan of the transform behind the solver reads it)
+    EFA_TRY(batch_solve(c, a, &done));
+    EFA_TRY(finish_obs_phase(c, a, Records::kNone, true, done, prior_mean, prior_var, post_mean, post_var, assimilated));
+    c->phase_a_kind = 5;
+    if (spec_out) *spec_out = done;
+    return EFA_OK;
+  }
   Records layout = Records::kNone;
   SpecResult done;
   bool diag_on_host = false;    // the diagnostics are already in pin_out (copied with the status words of the one launch that did it all)

@@ -94,6 +94,19 @@ int check_sec(const efa_ctx* c, int loc_mode) {
   return EFA_OK;
 }
 
+// ---- the batch observation-space solver (option "obs_solver" 1, efa_etkf.hip) --------------------------------
+// It solves all obs at once in ensemble space, which has no localised form here, leaves no records for a sweep, and no serial
+// order for the inflation update to follow.
+int check_batch_solver(const efa_ctx* c, int loc_mode) {
+  if (!c->obs_solver) return EFA_OK;
+  if (loc_mode == EFA_LOC_GC)
+    return fail(EFA_ERR_INVALID, "option obs_solver is 1: the batch solver is unlocalised (a localised ETKF is out of scope)");
+  if (c->ai_field) return fail(EFA_ERR_INVALID, "option obs_solver is 1: adaptive inflation cannot be combined with the batch solver");
+  if (c->path == EFA_PATH_SWEEP)
+    return fail(EFA_ERR_INVALID, "option obs_solver is 1: the batch solver leaves a transform and no records (option path is sweep)");
+  return EFA_OK;
+}
+
 // The table depends on the two settings alone (not on the obs' positions): it is written once per change of either, on the
 // context's stream, in front of the sweep that reads it.
 int ensure_slab_table(efa_ctx* c) {
@@ -135,8 +148,8 @@ StatePlan plan_state(const efa_ctx* c, bool member_form, Elem elem, bool in_plac
   p.member_form = member_form;
   const bool any = c->P > 0 && c->n_active > 0;  // an ob was assimilated
   const bool wide = c->M > 136;                  // the transform runs as column groups (k_transform_wide)
-  if (any && have_transform &&
-      (c->path == EFA_PATH_TRANSFORM || (c->path == EFA_PATH_AUTO && auto_transform(c->M, c->n_active, member_form))))
+  if (any && have_transform &&  // (behind the batch solver there are no records for any other route)
+      (c->batch_solved || c->path == EFA_PATH_TRANSFORM || (c->path == EFA_PATH_AUTO && auto_transform(c->M, c->n_active, member_form))))
     p.route = Route::transform;
   else if (c->loc_mode == EFA_LOC_GC && c->gc_onepass && c->n_active > 0)  // every ensemble size the library accepts (2..256)
     p.route = Route::gc_onepass;

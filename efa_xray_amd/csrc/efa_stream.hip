@@ -276,6 +276,8 @@ int cycle_host(efa_ctx* c, size_t esz, int n_seg, const void* const* seg_prior, 
   if (loc_mode != EFA_LOC_NONE && loc_mode != EFA_LOC_GC) return fail(EFA_ERR_INVALID, "loc_mode %d", loc_mode);
   if (n_seg && (!seg_prior || !seg_post || !seg_slabs)) return fail(EFA_ERR_INVALID, "%s: null segment table", who);
   if (P && !HX) return fail(EFA_ERR_INVALID, "%s: null HX", who);
+  EFA_TRY(check_batch_solver(c, loc_mode));  // (before the first upload)
+  EFA_TRY(check_batch_obs(c, P, ob_error, ob_assim));
   Pipe p{};
   p.c = c;
   Call& k = p.k;

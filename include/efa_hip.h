@@ -92,8 +92,11 @@ int efa_ctx_set_stream(efa_ctx *ctx, void *hip_stream);
  *          becoming resident; -1 = 100 ms + P/100 ms),
  *          "gc_onepass" (1: localised state sweep in one pass with per-column-block
  *          active lists, 0: per-batch taper tables),
- *          "own_stream" (see above);
- *          read-only: "phase_a_kind" (1 pipeline / 2 per-batch / 3 Gram pipeline / 4 band pipeline, last call),
+ *          "own_stream" (see above),
+ *          "obs_solver" (how the obs phase is solved: 0 (default) the serial EnSRF loop, 1 the batch
+ *          ensemble-space solve, an ETKF -- a different filter, see efa_etkf_solution);
+ *          read-only: "phase_a_kind" (1 pipeline / 2 per-batch / 3 Gram pipeline / 4 band pipeline /
+ *          5 batch solver, last call),
  *          "gc_active_pairs"
  *          ((column, ob) pairs with a non-zero taper in the last one-pass sweep),
  *          "gc_family" (the kernel family of the last one-pass sweep: 0 plain, 1 adaptive inflation, 2 vertical factor,
@@ -255,6 +258,46 @@ int efa_ctx_set_outlier_threshold(efa_ctx *ctx, double threshold);
  * setting as it was.  Read-only option "sec_on": 1 while a table is set. */
 int efa_ctx_set_sampling_error_correction(efa_ctx *ctx, const double *alpha, int T);
 int efa_ctx_synchronize(efa_ctx *ctx);
+
+/* ---- the batch observation-space solver: an ETKF (Bishop et al. 2001; Hunt et al. 2007, global form) ----
+ * Option "obs_solver" 1 is context state like "path": every later obs phase
+ * (efa_obs_phase_dev, efa_ensrf_cycle_dev, efa_ensrf_update_dev,
+ * efa_ensrf_update, efa_ensrf_cycle_host, _f32) solves all observations at
+ * once in ensemble space instead of walking them one after another.  With
+ * a_k the effective flag of ob k (ob_assim[k], and the outlier check's
+ * verdict when a threshold is set), over the obs with a_k = 1:
+ *   s_k = 1/sqrt(ob_error[k]), Y~_k = s_k Yp[k,:], d~_k = s_k (ob_value[k] - ym[k]),
+ *   C = Y~^T Y~, g = Y~^T d~, q = d~^T d~,
+ *   A = (M-1) I + C = V diag(mu) V^T,
+ *   T = V diag(sqrt((M-1)/mu)) V^T (the symmetric square root), w = V diag(1/mu) V^T g,
+ * and every row, of the state and of the obs block alike (all P obs rows,
+ * assimilated or not): xam = xbm + Xbp w, Xap = Xbp T.  The state phase takes
+ * the transform whatever "path" says (there are no records for a sweep);
+ * relaxation, float32 rows, in-place and out-of-place calls work as ever.
+ * Diagnostics: prior_mean = ym and prior_var = the variance (ddof 0) of
+ * Yp[k,:] for every ob, from the prior the call is handed; post_mean and
+ * post_var (ddof 0) from the mapped obs rows where a_k = 1; assimilated = a.
+ * This is the textbook Kalman update.  It is NOT the serial loop: that one
+ * (as the reference does) divides the gain's denominator by M and its
+ * numerator by M-1, so the two filters differ by 1 % to 78 % of the mean
+ * increment, most with many accurate observations.  T 1 = 1 (member means
+ * preserved) holds as far as the rows of Yp sum to zero; it is not enforced.
+ * An ob with a_k = 0 is never read for value or error.  With no ob assimilated
+ * the state calls return what they return under "obs_solver" 0, bit for bit.
+ * The same inputs give the same bits (fixed reduction orders, no atomics).
+ * Refused with EFA_ERR_INVALID before anything is launched (the context stays
+ * usable): EFA_LOC_GC, an adaptive-inflation field, option "path"
+ * EFA_PATH_SWEEP, an assimilated ob whose error variance is not finite and
+ * > 0 (the batch form divides by it).  "phase_a_kind" reads 5.
+ *
+ * efa_etkf_solution returns the solution of the last obs phase, which must
+ * have run with "obs_solver" 1 for M members (else EFA_ERR_INVALID): T, w,
+ * eig = the eigenvalues lambda_i = mu_i - (M-1) of C in descending order,
+ * stats = {n_active, q, dfs = sum lambda_i/(M-1+lambda_i) = trace(HK),
+ * chi2 = q - g^T w = d^T (H P^b H^T + R)^-1 d}, and the Jacobi sweeps the
+ * eigen-solve took (at most 30).  Any output may be NULL; it waits. */
+int efa_etkf_solution(efa_ctx *ctx, int M, double *T /*[M*M]*/, double *w /*[M]*/, double *eig /*[M], descending*/,
+                      double *stats /*[4]: n_active, q, dfs, chi2*/, long *sweeps);
 
 /* ---- device memory for callers without their own allocator -------------*/
 int efa_malloc(efa_ctx *ctx, size_t bytes, void **dev_out);
