@@ -188,6 +188,21 @@ SIGNATURES = {
     "efa_pm_mean_f32_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_long,
                                            ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_long,
                                            ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong)]),
+    "efa_letkf_cycle_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_long,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                           c_double_p, c_double_p, c_uint8_p,
+                                           c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                           ctypes.c_long, ctypes.c_long,
+                                           c_double_p, c_double_p, c_double_p, c_double_p, c_uint8_p, ctypes.c_void_p]),
+    "efa_letkf_cycle_f32_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_long,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                               c_double_p, c_double_p, c_uint8_p,
+                                               c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                               ctypes.c_long, ctypes.c_long,
+                                               c_double_p, c_double_p, c_double_p, c_double_p, c_uint8_p, ctypes.c_void_p]),
+    "efa_letkf_weights_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
+                                             c_double_p, c_double_p, c_uint8_p, c_double_p, c_double_p, c_double_p,
+                                             ctypes.c_long, c_double_p, c_double_p, ctypes.c_void_p, ctypes.c_void_p]),
     "efa_last_timing": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p,
                                        ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_int)]),
     "efa_fill_synthetic_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_int,
@@ -844,6 +859,43 @@ class Context(object):
             _dp(d["prior_mean"]), _dp(d["prior_var"]), _dp(d["post_mean"]), _dp(d["post_var"]), _u8p(d["assimilated"])))
         d["assimilated"] = d["assimilated"].astype(bool)
         return d
+
+    def letkf_cycle(self, rows, M, P, X, post, ym, Yp, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth, grid_lat,
+                    grid_lon, n_lead=1, obs_block_out=False, col_stats=None, f32=None):
+        """efa_letkf_cycle_dev / _f32_dev: the LETKF on resident prior members, one ensemble-space solve per
+        column under the Gaspari-Cohn taper and one per ob position for the obs block.  col_stats: a float64 DeviceArray
+        (ncol, 3) for {n_local, dfs, sweeps} of every column, or None.  f32: the rows' storage (None: X's dtype).  Returns the
+        diagnostics."""
+        val, err, asm, lat, lon, hw = self._ob_arrays(P, ob_value, ob_error, ob_assim, LOC_GC, ob_lat, ob_lon, ob_halfwidth)
+        glat, glon, ncol = self._grid(LOC_GC, grid_lat, grid_lon)
+        if f32 is None:
+            f32 = isinstance(X, DeviceArray) and X.dtype == np.float32
+        entry = self.lib.efa_letkf_cycle_f32_dev if f32 else self.lib.efa_letkf_cycle_dev
+        dt = np.float32 if f32 else np.float64
+        d = self._diag_arrays(P)
+        _check(self.lib, entry(
+            self.handle, rows, M, P, self._addr(X, dt), self._addr(post, dt), self._addr(ym), self._addr(Yp), 1 if obs_block_out else 0,
+            _dp(val), _dp(err), _u8p(asm), _dp(lat), _dp(lon), _dp(hw), _dp(glat), _dp(glon), ncol, n_lead,
+            _dp(d["prior_mean"]), _dp(d["prior_var"]), _dp(d["post_mean"]), _dp(d["post_var"]), _u8p(d["assimilated"]),
+            self._addr(col_stats)))
+        d["assimilated"] = d["assimilated"].astype(bool)
+        return d
+
+    def letkf_weights(self, M, P, ym, Yp, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth, pt_lat, pt_lon):
+        """efa_letkf_weights_dev: the LETKF solve at the given points.  Returns (T (npts, M, M), w (npts, M), stats (npts, 3) =
+        {n_local, dfs, sweeps})."""
+        val, err, asm, lat, lon, hw = self._ob_arrays(P, ob_value, ob_error, ob_assim, LOC_GC, ob_lat, ob_lon, ob_halfwidth)
+        plat = np.ascontiguousarray(pt_lat, dtype=np.float64).reshape(-1)
+        plon = np.ascontiguousarray(pt_lon, dtype=np.float64).reshape(-1)
+        assert plat.shape == plon.shape
+        npts = plat.shape[0]
+        Tw = self.empty((max(npts, 1), M, M + 1))
+        st = self.empty((max(npts, 1), 3))
+        _check(self.lib, self.lib.efa_letkf_weights_dev(
+            self.handle, M, P, self._addr(ym), self._addr(Yp), _dp(val), _dp(err), _u8p(asm), _dp(lat), _dp(lon), _dp(hw),
+            npts, _dp(plat), _dp(plon), self._addr(Tw), self._addr(st)))
+        tw = Tw.download()[:npts]
+        return np.ascontiguousarray(tw[:, :, :M]), np.ascontiguousarray(tw[:, :, M]), st.download()[:npts]
 
     def ensrf_update_dev(self, rows, M, P, xm, Xp, ym, Yp, ob_value, ob_error, ob_assim,
                          loc_mode=LOC_NONE, ob_lat=None, ob_lon=None, ob_halfwidth=None,

@@ -38,7 +38,7 @@ class ETKF(EnSRF):
         sampling_error_correction, path and obs_batch.  `update_arrays` is not offered."""
         loc = kw.pop("loc", False)
         if loc not in (None, False):
-            raise ValueError("ETKF: loc=%r is not supported: a localised ETKF (LETKF) is out of scope; use EnSRF(loc='GC')" % (loc,))
+            raise ValueError("ETKF: loc=%r is not supported: a localised ETKF is out of scope here; use LETKF (or EnSRF(loc='GC'))" % (loc,))
         for name, why in _REFUSED:
             if name in kw:
                 raise ValueError("ETKF does not take %s: %s" % (name, why))

@@ -1,0 +1,110 @@
+"""LETKF: local ensemble transform Kalman filter, computed on an MI355X.
+
+Hunt, Kostelich & Szunyogh (2007): the textbook ensemble-space update of `ETKF`, solved once per (y, x) column with every
+observation's error variance divided by its Gaspari-Cohn taper at that column (R-localisation):
+
+    A_c = (M-1) I + sum_k (rho_k(c)/r_k) Y_k^T Y_k = V diag(mu) V^T,  T_c = V diag(sqrt((M-1)/mu)) V^T,
+    w_c = V diag(1/mu) V^T sum_k (rho_k(c)/r_k) d_k Y_k^T;   every row of column c: mean += X' w_c, X' <- X' T_c
+
+over the observations that are assimilated and within reach of the column, Y_k and d_k the PRIOR observation-space perturbations
+and innovations.  The obs block maps likewise, ob j with the pair solved at its own position.  This is the localised filter for
+the states `ETKF` cannot serve; it is not the reference's serial loop, which `EnSRF(loc='GC')` reproduces.
+
+Same surface as `EnSRF`: `LETKF(state, obs, ...).update() -> (post_state, obs)` with the five diagnostics written onto each
+`Observation` as `ETKF` writes them.  After an update `last_solve` holds three (ny, nx) arrays: `n_local` (the observations
+that reach the column), `dfs` (trace(HK) of the column's solve) and `sweeps` (Jacobi sweeps of its eigen-solve; 0 where no
+observation reaches the column: there is nothing to solve and the column's rows come back bit for bit).
+"""
+import numpy as np
+
+from efa_xray_amd import _lib
+from efa_xray_amd.assimilation.ensrf import EnSRF
+
+MAX_MEMBERS = 136
+
+# keywords of EnSRF that the per-column batch solve does not serve, with the reason given to the caller
+_REFUSED = (
+    ("adaptive_inflation", "adaptive inflation follows the serial order of the observations, which a column's batch solve does not have"),
+    ("vert_coord", "vertical localisation needs a solve per (slab group, column): out of scope (DESIGN.md 7y)"),
+    ("time_localize", "temporal localisation needs a solve per (slab group, column): out of scope (DESIGN.md 7y)"),
+    ("var_impact", "cross-variable localisation needs a solve per (slab group, column): out of scope (DESIGN.md 7y)"),
+    ("sampling_error_correction", "the sampling error correction acts on the serial gain of one observation at a time"),
+    ("streamed", "the streamed host path is out of scope for the LETKF (DESIGN.md 7y): the state must be resident"),
+    ("path", "there is no sweep or transform route to choose: every column runs its own solve and apply in one kernel"),
+    ("obs_batch", "there is no per-batch sweep under the per-column solve"),
+)
+
+
+class LETKF(EnSRF):
+    def __init__(self, state, obs, nproc=1, inflation=None, verbose=True, **kw):
+        """Keyword-only options, as `EnSRF` has them: loc ('GC', the default and the only value), device, rtps / rtpp,
+        outlier_threshold; float32 states work as they do there.  ValueError, before any device work, for loc other than 'GC'
+        (use `ETKF` for the unlocalised filter), adaptive_inflation, vert_coord, time_localize, var_impact,
+        sampling_error_correction, streamed, path, obs_batch, and for more than 136 members (the eigen-solve of a column keeps
+        its M x M array in LDS).  `update_arrays` is not offered."""
+        loc = kw.pop("loc", "GC")
+        if not (isinstance(loc, str) and loc == "GC"):
+            raise ValueError("LETKF: loc=%r is not supported: the LETKF is the localised filter and takes loc='GC' only; "
+                             "use ETKF for the unlocalised ensemble transform filter" % (loc,))
+        for name, why in _REFUSED:
+            if name in kw and kw[name] is not None and kw[name] is not False:
+                raise ValueError("LETKF does not take %s: %s" % (name, why))
+            kw.pop(name, None)
+        if state.nmems() > MAX_MEMBERS:
+            raise ValueError("LETKF: %d members exceed %d, the range in which the eigen-solve's M x M array of a column fits in "
+                             "LDS (DESIGN.md 7y)" % (state.nmems(), MAX_MEMBERS))
+        EnSRF.__init__(self, state, obs, nproc, inflation, verbose, "GC", **kw)
+        self.last_solve = None
+
+    def update(self):
+        self.last_solve = None
+        if self.verbose:
+            print("Beginning update sequence")
+        P, value, error, assim, lat, lon, hw = self._ob_arrays(_lib.LOC_GC)
+        if self.inflation is not None:          # the inflation hook comes first, as in EnSRF.update
+            if self.verbose:
+                print("Inflating Prior State")
+            self.inflate_state()
+        prior = self.prior
+        N, M = prior.nstate(), prior.nmems()
+        if M > MAX_MEMBERS:
+            raise ValueError("LETKF: %d members exceed %d (DESIGN.md 7y)" % (M, MAX_MEMBERS))
+        f32 = prior.dtype == np.float32
+        ctx = self._context()
+        self._configure(ctx)
+        ctx.set_option("timing", 1)
+        if self.verbose:
+            print("Converting state to vector")
+        X = self._upload_prior(ctx)
+        if self.verbose:
+            print("Computing observation priors")
+        ym = ctx.empty((max(P, 1),))
+        if P:
+            if f32:                             # as EnSRF._update_f32: the host gather of the stencil rows, widened
+                HX = self.streamed_ob_estimates(ctx) if self._default_forward_operator() else self.compute_ob_estimates()
+                Yp = ctx.to_device(HX)
+            elif self._default_forward_operator():
+                Yp = self.device_ob_estimates(ctx, X)
+            else:
+                Yp = ctx.to_device(self.compute_ob_estimates())
+            ctx.form_perts(P, M, Yp, ym, Yp)    # assimilation.py:46-48
+        else:
+            Yp = ctx.empty((1, M))
+        grid_lat, grid_lon = prior.column_latlon()
+        ny, nx = prior.shape()[2:4]
+        n_lead = prior.nvars() * prior.ntimes()
+        stats = ctx.empty((ny * nx, 3))
+        if self.verbose:
+            print("Beginning the column solves")
+        diag = ctx.letkf_cycle(N, M, P, X, X, ym, Yp, value, error, assim, lat, lon, hw, grid_lat, grid_lon, n_lead,
+                               col_stats=stats, f32=f32)
+        self.last_timing = ctx.last_timing()
+        self._write_diagnostics(diag)
+        st = stats.download().reshape(ny, nx, 3)
+        self.last_solve = dict(n_local=st[:, :, 0].astype(np.int64), dfs=st[:, :, 1].copy(), sweeps=st[:, :, 2].astype(np.int64))
+        if self.verbose:
+            print("Formatting posterior")
+        return self._download_posterior(X), self.obs
+
+    def update_arrays(self, xbm, Xbp):
+        raise ValueError("LETKF does not offer update_arrays (out of scope, DESIGN.md 7y); use update()")

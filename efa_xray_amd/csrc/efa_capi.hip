@@ -962,6 +962,37 @@ int efa_etkf_solution(efa_ctx* c, int M, double* T, double* w, double* eig, doub
   return EFA_OK;
 }
 
+int efa_letkf_cycle_dev(efa_ctx* c, long rows, int M, long P, const double* X_dev, double* post_dev, double* ym_dev, double* Yp_dev,
+                        int obs_block_out, const double* ob_value, const double* ob_error, const uint8_t* ob_assim,
+                        const double* ob_lat, const double* ob_lon, const double* ob_halfwidth_km, const double* grid_lat,
+                        const double* grid_lon, long ncol, long n_lead, double* prior_mean, double* prior_var, double* post_mean,
+                        double* post_var, uint8_t* assimilated, double* col_stats_dev) {
+  EFA_TRY(use(c));
+  return efa_host::letkf_cycle(c, efa::Elem::f64, rows, M, P, X_dev, post_dev, ym_dev, Yp_dev, obs_block_out, ob_value, ob_error, ob_assim,
+                               ob_lat, ob_lon, ob_halfwidth_km, grid_lat, grid_lon, ncol, n_lead, prior_mean, prior_var, post_mean,
+                               post_var, assimilated, col_stats_dev);
+}
+
+int efa_letkf_cycle_f32_dev(efa_ctx* c, long rows, int M, long P, const float* X_dev, float* post_dev, double* ym_dev, double* Yp_dev,
+                            int obs_block_out, const double* ob_value, const double* ob_error, const uint8_t* ob_assim,
+                            const double* ob_lat, const double* ob_lon, const double* ob_halfwidth_km, const double* grid_lat,
+                            const double* grid_lon, long ncol, long n_lead, double* prior_mean, double* prior_var, double* post_mean,
+                            double* post_var, uint8_t* assimilated, double* col_stats_dev) {
+  EFA_TRY(use(c));
+  return efa_host::letkf_cycle(c, efa::Elem::f32, rows, M, P, X_dev, post_dev, ym_dev, Yp_dev, obs_block_out, ob_value, ob_error, ob_assim,
+                               ob_lat, ob_lon, ob_halfwidth_km, grid_lat, grid_lon, ncol, n_lead, prior_mean, prior_var, post_mean,
+                               post_var, assimilated, col_stats_dev);
+}
+
+int efa_letkf_weights_dev(efa_ctx* c, int M, long P, const double* ym_dev, const double* Yp_dev, const double* ob_value,
+                          const double* ob_error, const uint8_t* ob_assim, const double* ob_lat, const double* ob_lon,
+                          const double* ob_halfwidth_km, long npts, const double* pt_lat, const double* pt_lon, double* Tw_dev,
+                          double* stats_dev) {
+  EFA_TRY(use(c));
+  return efa_host::letkf_weights(c, M, P, ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km, npts, pt_lat,
+                                 pt_lon, Tw_dev, stats_dev);
+}
+
 int efa_last_timing(efa_ctx* c, double* state_ms, double* obs_ms, long* state_launches, int* path_taken) {
   if (!c) return fail(EFA_ERR_INVALID, "null context");
   harvest_obs_ms(c);

@@ -216,7 +216,7 @@ struct efa_ctx {
   DevBuf traj, tw_mat, status, dbg;  // pipeline: trajectory records, GC obs-obs taper, status words, stamps
   const double* ye_ptr = nullptr;  // where Phase B reads the recorded ye rows
   long ye_stride = 0;
-  int phase_a_kind = 0;          // 1 vector-chain pipeline, 2 per-batch kernels, 3 Gram leader, 4 band leader, 5 batch solver
+  int phase_a_kind = 0;          // 1 vector-chain pipeline, 2 per-batch kernels, 3 Gram leader, 4 band leader, 5 batch solver, 6 LETKF (efa_letkf_cycle_dev)
   DevBuf ob_pack, out_pack;  // the per-ob inputs / diagnostics below are slices of these two allocations (stage_obs_inputs)
   PinBuf pin_in, pin_out;    // their pinned host images: one H2D and one D2H per call
   PinBuf pin_fs;             // pinned image of the forward-operator stencil
@@ -304,6 +304,12 @@ struct efa_ctx {
   long obs_solver = 0;          // 0 serial (Phase A's kernels), 1 batch (ETKF)
   bool batch_solved = false;    // the last obs phase ran the batch solver: the state phase goes through [T | w], there are no records
   DevBuf etkf_buf;              // its workspace (EtkfWs): scales, A, g, q, sweeps, mu, partial tiles
+  // --- local ensemble transform Kalman filter (efa_letkf_cycle_dev): buffers of its own as well ------------------------
+  DevBuf letkf_ob;    // per ob: value | error | lat | lon | half-width | requested flag | act [4] | dr [2] | obtrig [6] | diagnostics
+  DevBuf letkf_pts;   // the points of a list build (lat | lon): the grid's columns, or the probe points of efa_letkf_weights_dev
+  DevBuf letkf_blk, letkf_idx, letkf_wts;  // the call's lists: off | cnt | ub | order, entries, tapers (the obs' then the grid's)
+  DevBuf letkf_Yw;    // the mapped obs block [P][M] | its means [P]
+  DevBuf letkf_pairs; // the list builders' pair counter
   // --- observation impact (efa_obs_impact_dev): buffers of its own, nothing above is touched by it ---------------
   //     (efa_obs_impact_slab_dev, §7u, brings sl_tab up to date as well: the table's cache, keyed by the two settings' serials)
   DevBuf imp_ob;    // per ob: used flags (coefficient-shaped) | scale | lat | lon | half-width | obtrig scratch | impact

@@ -11,6 +11,7 @@
 //   efa_pmmean.hip   the probability-matched mean and the segmented radix sort under it: its kernels and the driver of efa_pm_mean_dev
 //   efa_gram.hip     the ensemble Gram matrix: its kernels and the driver of efa_gram_dev
 //   efa_etkf.hip     the batch observation-space solver's kernels (option "obs_solver" 1; driven from efa_phase_a.hip)
+//   efa_letkf.hip    the local ensemble transform Kalman filter: its kernels and the driver of efa_letkf_cycle_dev / efa_letkf_weights_dev
 //   efa_comm.hip     RCCL
 // Headers the diagnostics share: efa_quadrow.h (the four-lane row layout of k_sens_pass, k_verify, k_products and k_nbr_records),
 // efa_sortnet.h (the bitonic network on it), efa_quadreduce.h (table flush, chunk partial, k_group_reduce) and efa_diag.h (their
@@ -145,6 +146,18 @@ int state_cycle(efa_ctx* c, const StateRows& r, const double* grid_lat, const do
 // end of a state call: the launch count into the sum; "timing" 1 waits and reads the interval, 2 leaves it pending.
 // end_recorded: iv.end is in the stream already (a speculative transform that turned out right)
 int end_state_call(efa_ctx* c, Interval& iv, bool timed = true, bool end_recorded = false);
+
+// ---- efa_letkf.hip ------------------------------------------------------------------------------------------------------------
+// efa_letkf_cycle_dev / _f32_dev: checks, the obs' effective flags and prior diagnostics, the lists and the solve at every ob
+// position (the obs block), the lists and the solve of every grid column (the state); waits before it returns the diagnostics
+int letkf_cycle(efa_ctx* c, Elem elem, long rows, int M, long P, const void* X_dev, void* post_dev, double* ym_dev, double* Yp_dev,
+                int obs_block_out, const double* ob_value, const double* ob_error, const uint8_t* ob_assim, const double* ob_lat,
+                const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
+                double* prior_mean, double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated, double* col_stats_dev);
+// efa_letkf_weights_dev: the same solve at caller-given points, [T | w] of each to Tw_dev; waits
+int letkf_weights(efa_ctx* c, int M, long P, const double* ym_dev, const double* Yp_dev, const double* ob_value, const double* ob_error,
+                  const uint8_t* ob_assim, const double* ob_lat, const double* ob_lon, const double* ob_hw, long npts,
+                  const double* pt_lat, const double* pt_lon, double* Tw_dev, double* stats_dev);
 
 // ---- efa_impact.hip -----------------------------------------------------------------------------------------------------------
 // efa_obs_impact_dev: checks, the call's own active lists, the contraction and its reduction; waits before it returns impact[P]

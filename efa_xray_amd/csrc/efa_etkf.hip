@@ -19,6 +19,7 @@
 //                 lives in LDS up to kEtkfLdsMaxM members and in its (L2 resident) global workspace above: the same code.
 // k_etkf_post     a wave per ob: post_mean, post_var (ddof 0) of the mapped obs rows.
 #include "efa_device.h"
+#include "efa_etkf_eig.h"
 #include "efa_internal.h"
 #include "efa_rows.h"
 
@@ -173,9 +174,8 @@ __global__ __launch_bounds__(256) void k_etkf_reduce(int M, int T, int ntiles, i
   }
 }
 
-constexpr double kEtkfRotTol = 8.8817841970012523e-16;  // 2^-50
-
-// G: the array, column j at G + j M.  One workgroup of a multiple of 64 threads; 16 lanes per column pair.
+// G: the array, column j at G + j M.  One workgroup of a multiple of 64 threads; 16 lanes per column pair.  The body is
+// etkf_eig_solve (efa_etkf_eig.h), which k_letkf runs once per column on an array of its own.
 __global__ __launch_bounds__(1024) void k_etkf_eig(int M, int use_lds, double* A, const double* __restrict__ gvec, double* mu_out,
                                                    double* Tout, double* wout, double* sweeps_out) {
   extern __shared__ __align__(16) double etkf_smem[];
@@ -188,97 +188,7 @@ __global__ __launch_bounds__(1024) void k_etkf_eig(int M, int use_lds, double* A
   if (use_lds)
     for (int i = tid; i < M * M; i += nth) G[i] = A[i];
   __syncthreads();
-  const int n = M + (M & 1), npairs = n / 2, nslots = nth >> 4, slot = tid >> 4, sl = tid & 15;
-  int sweeps = 0;
-#pragma unroll 1
-  for (int sw = 0; sw < kEtkfSweepCap; ++sw) {
-    if (tid == 0) rot_s[sw & 1] = 0;
-    // the squared column norms, afresh once per sweep; a rotation then updates its two (alpha - t gamma, beta + t gamma)
-#pragma unroll 1
-    for (int j = slot; j < M; j += nslots) {
-      const double* cj = G + (size_t)j * M;
-      double al = 0.0;
-      for (int i = sl; i < M; i += 16) al = fma(cj[i], cj[i], al);
-      al = group_sum<16>(al);
-      if (sl == 0) n_s[j] = al;
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int r = 0; r < n - 1; ++r) {
-#pragma unroll 1
-      for (int pi = slot; pi < npairs; pi += nslots) {
-        int p = n - 1, q = r;
-        if (pi != 0) {
-          p = r + pi;
-          if (p >= n - 1) p -= n - 1;
-          q = r - pi;
-          if (q < 0) q += n - 1;
-        }
-        if (p >= M || q >= M) continue;  // (an odd M plays against a bye)
-        double* cp = G + (size_t)p * M;
-        double* cq = G + (size_t)q * M;
-        double ga = 0.0;
-        for (int i = sl; i < M; i += 16) ga = fma(cp[i], cq[i], ga);
-        ga = group_sum<16>(ga);  // a butterfly: the 16 lanes hold the same bits
-        const double al = n_s[p], be = n_s[q];
-        if (ga * ga > (kEtkfRotTol * kEtkfRotTol) * (al * be)) {  // |gamma| > 2^-50 sqrt(alpha beta); false for a NaN
-          const double d = be - al;
-          const double t = copysign(2.0, d) * ga / (fabs(d) + sqrt(fma(d, d, 4.0 * (ga * ga))));
-          const double c = rsqrt(fma(t, t, 1.0));
-          const double s = c * t;
-          for (int i = sl; i < M; i += 16) {
-            const double x = cp[i], y = cq[i];
-            cp[i] = c * x - s * y;
-            cq[i] = s * x + c * y;
-          }
-          if (sl == 0) {
-            n_s[p] = al - t * ga;
-            n_s[q] = be + t * ga;
-            rot_s[sw & 1] = 1;
-          }
-        }
-      }
-      __syncthreads();
-    }
-    sweeps = sw + 1;
-    if (rot_s[sw & 1] == 0) break;  // (uniform: read behind the round's barrier; the next sweep clears the other word)
-  }
-  // column norms mu, V in place, the two factor vectors
-#pragma unroll 1
-  for (int j = slot; j < M; j += nslots) {
-    double* cj = G + (size_t)j * M;
-    double al = 0.0, hg = 0.0;
-    for (int i = sl; i < M; i += 16) {
-      const double x = cj[i];
-      al = fma(x, x, al);
-      hg = fma(x, gvec[i], hg);
-    }
-    al = group_sum<16>(al);
-    hg = group_sum<16>(hg);
-    const double mu = sqrt(al);
-    for (int i = sl; i < M; i += 16) cj[i] = cj[i] / mu;
-    if (sl == 0) {
-      mu_out[j] = mu;
-      f_s[j] = sqrt((double)(M - 1) / mu);
-      h_s[j] = (hg / mu) / mu;
-    }
-  }
-  __syncthreads();
-  // T[a][b] = sum_j f_j V[a][j] V[b][j] for a <= b, mirrored; w[a] = sum_j h_j V[a][j]
-#pragma unroll 1
-  for (int e = tid; e < M * M; e += nth) {
-    const int a = e / M, b = e - a * M;
-    if (a > b) continue;
-    double acc = 0.0;
-    for (int j = 0; j < M; ++j) acc = fma(f_s[j] * G[(size_t)j * M + a], G[(size_t)j * M + b], acc);
-    Tout[(size_t)a * M + b] = acc;
-    Tout[(size_t)b * M + a] = acc;
-  }
-  for (int a = tid; a < M; a += nth) {
-    double acc = 0.0;
-    for (int j = 0; j < M; ++j) acc = fma(h_s[j], G[(size_t)j * M + a], acc);
-    wout[a] = acc;
-  }
+  const int sweeps = etkf_eig_solve(M, G, gvec, mu_out, Tout, wout, f_s, h_s, n_s, rot_s, tid, nth);
   if (tid == 0) *sweeps_out = (double)sweeps;
 }
 

@@ -372,6 +372,47 @@ hipError_t launch_etkf_solve(long P, int M, const double* Yp, const EtkfWs& w, d
 // posterior diagnostics of the mapped obs rows
 hipError_t launch_etkf_post(long P, int M, const double* Yw, const double* ymw, double* post_mean, double* post_var, hipStream_t s);
 
+// ---- the local ensemble transform Kalman filter (LETKF, efa_letkf.hip) ------------------------------------------
+constexpr int kLetkfMaxM = kEtkfLdsMaxM;  // the eigen-solve's array of every column lives in LDS: no form above
+enum LetkfMode : int {
+  kLetkfMembers = 0,  // member rows of the state: n_lead rows per column, float64 or float32
+  kLetkfPerts = 1,    // rows in perturbation form (the obs block: one row per point, its mean beside it), not relaxed
+  kLetkfWeights = 2   // no rows: [T | w] of every point to Tw
+};
+struct LetkfArgs {
+  long npts;          // columns of the grid, ob positions, or probe points: one workgroup each
+  long n_lead;        // rows per column (kLetkfMembers), row lead * npts + col
+  int M;
+  // the per-block lists of launch_gc_bound / launch_gc_fill (all null: every list is empty)
+  const long* off;
+  const int* cnt;
+  const int* order;
+  const int* idx;
+  const double* wts;
+  const double* Yp;   // [P][M] the PRIOR obs perturbations
+  const double* dr;   // [P][2] {value - ym, error variance} of every ob with an effective flag of 1
+  const void* Xin;    // kLetkfMembers: [n_lead * npts][M] prior members ...
+  void* Xout;         // ... and posterior members (the same address, or clear of Xin)
+  const double* ym_in;   // kLetkfPerts: [npts] means, [npts][M] perturbations ...
+  const double* Yp_in;
+  double* ym_out;        // ... and where the mapped rows go (clear of the inputs)
+  double* Yp_out;
+  double* Tw;         // kLetkfWeights: [npts][M][M + 1], row a of a point = T[a][0..M) | w[a]
+  double* stats;      // [npts][3] {n_local, dfs, sweeps} or null
+  int relax_kind;     // kLetkfMembers: EFA_RELAX_* and its factor (RTPP folded into f, RTPS fused per row)
+  double relax_alpha;
+};
+int letkf_threads(int M);       // the workgroup size chosen for M members
+size_t letkf_lds_bytes(int M);  // and its dynamic LDS
+// a.Xin / a.Xout are rows of `elem` (kLetkfMembers; the other modes are float64 only)
+hipError_t launch_letkf(const LetkfArgs& a, int mode, Elem elem, hipStream_t s);
+// a wave per ob: prior_mean, prior_var (ddof 0), the effective flag (the requested one, and with t2 > 0 the outlier check's verdict
+// d^2 <= t2 (s2 + error), exactly as the prep launch decides it) as a byte and as the coefficient-shaped act [P][4] the list
+// builders read, and dr [P][2]; an ob with an effective flag of 0 leaves the neutral (0, 1) there, whatever its value and error
+hipError_t launch_letkf_prior(long P, int M, const double* Yp, const double* ym, const double* ob_value, const double* ob_error,
+                              const double* ob_req, double t2, double* prior_mean, double* prior_var, uint8_t* assimilated, double* act,
+                              double* dr, hipStream_t s);
+
 hipError_t launch_results_to_host(const void* src_dev, void* dst_host, size_t bytes, const int* st_dev, int* st_host, hipStream_t s);
 // diagnostic: `blocks` workgroups that hold `lds_bytes` of LDS each and spin for `ms` milliseconds
 hipError_t launch_occupy(int blocks, size_t lds_bytes, double ms, hipStream_t s);

@@ -299,6 +299,67 @@ int efa_ctx_synchronize(efa_ctx *ctx);
 int efa_etkf_solution(efa_ctx *ctx, int M, double *T /*[M*M]*/, double *w /*[M]*/, double *eig /*[M], descending*/,
                       double *stats /*[4]: n_active, q, dfs, chi2*/, long *sweeps);
 
+/* ---- the local ensemble transform Kalman filter (LETKF) -----
+ * Hunt, Kostelich & Szunyogh (2007): one ensemble-space solve per column
+ * under the Gaspari-Cohn taper, the taper multiplying R^-1 (R-localisation).
+ * The inputs are those of efa_ensrf_cycle_dev with EFA_LOC_GC.  With a_k the
+ * effective flag as under "obs_solver" 1 (ob_assim[k], and the outlier
+ * check's verdict when a threshold is set), rho_k(x) = gaspari_cohn(
+ * distance(x, ob k), halfwidth_k) and d_k = value_k - ym_k, for a location x
+ * (a grid column or an ob position), over the obs with a_k = 1, rho_k(x) != 0:
+ *   C_x = sum_k (rho_k/r_k) Yp_k^T Yp_k,  g_x = sum_k (rho_k/r_k) d_k Yp_k^T,
+ *   A_x = (M-1) I + C_x = V diag(mu) V^T,
+ *   T_x = V diag(sqrt((M-1)/mu)) V^T,  w_x = V diag(1/mu) V^T g_x.
+ * State rows: all n_lead rows of column c (row lead*ncol + c) map with that
+ * column's pair, xam = xbm + Xbp w_c, Xap = Xbp T_c.  Obs block: all P rows map,
+ * assimilated or not, ob j with the pair solved at (ob_lat[j], ob_lon[j]).
+ * Every solve reads the PRIOR obs block; the posterior obs block is written
+ * elsewhere and copied into ym_dev / Yp_dev afterwards when obs_block_out is 1
+ * (0: both are left untouched).  Diagnostics as under "obs_solver" 1.
+ * A column no ob reaches keeps its rows bit for bit, with relaxation too.  An
+ * ob with a_k = 0 is never read for value or error.  A NaN value of an
+ * assimilated ob poisons w of exactly the columns it reaches.  The same inputs
+ * give the same bits.  post_dev == X_dev is allowed (a column's rows are read
+ * and written by its own workgroup only); any other overlap is refused.
+ * These are entry points of their own: option "obs_solver" is not read.  They
+ * honour the context's relaxation (state rows only; RTPP folded into the
+ * transform, RTPS per row) and outlier threshold.  Refused with
+ * EFA_ERR_INVALID before anything is launched (the context stays usable):
+ *   M > 136 (the eigen-solve's M x M array of a column must fit in LDS);
+ *   an adaptive-inflation field (its update follows the serial order of the
+ *   obs, which a batch solve does not have); vertical or slab (temporal /
+ *   cross-variable) localisation (each needs a solve per (slab group, column));
+ *   a sampling-error-correction table (it acts on the serial gain of one ob);
+ *   an assimilated ob whose error variance is not finite and > 0, or whose
+ *   half-width is NaN or 0.
+ * col_stats_dev (device, may be NULL) receives per column {n_local = the obs
+ * with a_k = 1 and rho != 0, dfs = sum lambda_i/(M-1+lambda_i), Jacobi sweeps
+ * (at most 30)}; a column no ob reaches runs no solve and reports (0, 0, 0).
+ * Afterwards "phase_a_kind" reads 6, and efa_last_timing gives the list builds
+ * and the obs block as obs_ms, the column launch as state_ms.  They wait.
+ *
+ * efa_letkf_weights_dev solves at npts caller-given points (host arrays
+ * pt_lat / pt_lon) and writes [T | w] of each to Tw_dev (device,
+ * [npts][M][M+1]: row a = T[a][0..M) then w[a]; never relaxed) and the
+ * statistics to stats_dev ([3*npts] or NULL): the probe the tests use, and the
+ * hook for solving on a coarse grid (weight interpolation is out of scope). */
+int efa_letkf_cycle_dev(efa_ctx *ctx, long rows, int M, long P, const double *X_dev, double *post_dev, double *ym_dev,
+                        double *Yp_dev, int obs_block_out, const double *ob_value, const double *ob_error,
+                        const uint8_t *ob_assim, const double *ob_lat, const double *ob_lon, const double *ob_halfwidth_km,
+                        const double *grid_lat, const double *grid_lon, long ncol, long n_lead, double *prior_mean,
+                        double *prior_var, double *post_mean, double *post_var, uint8_t *assimilated,
+                        double *col_stats_dev /* [3*ncol] or NULL */);
+int efa_letkf_cycle_f32_dev(efa_ctx *ctx, long rows, int M, long P, const float *X_dev, float *post_dev, double *ym_dev,
+                            double *Yp_dev, int obs_block_out, const double *ob_value, const double *ob_error,
+                            const uint8_t *ob_assim, const double *ob_lat, const double *ob_lon, const double *ob_halfwidth_km,
+                            const double *grid_lat, const double *grid_lon, long ncol, long n_lead, double *prior_mean,
+                            double *prior_var, double *post_mean, double *post_var, uint8_t *assimilated,
+                            double *col_stats_dev /* [3*ncol] or NULL */);
+int efa_letkf_weights_dev(efa_ctx *ctx, int M, long P, const double *ym_dev, const double *Yp_dev, const double *ob_value,
+                          const double *ob_error, const uint8_t *ob_assim, const double *ob_lat, const double *ob_lon,
+                          const double *ob_halfwidth_km, long npts, const double *pt_lat, const double *pt_lon,
+                          double *Tw_dev /* [npts][M][M+1] */, double *stats_dev /* [3*npts] or NULL */);
+
 /* ---- device memory for callers without their own allocator -------------*/
 int efa_malloc(efa_ctx *ctx, size_t bytes, void **dev_out);
 int efa_free(efa_ctx *ctx, void *dev);
