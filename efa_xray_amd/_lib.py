@@ -203,6 +203,24 @@ SIGNATURES = {
     "efa_letkf_weights_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
                                              c_double_p, c_double_p, c_uint8_p, c_double_p, c_double_p, c_double_p,
                                              ctypes.c_long, c_double_p, c_double_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "efa_letkf_cycle_interp_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_long,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                  c_double_p, c_double_p, c_uint8_p,
+                                                  c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                  ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long,
+                                                  c_double_p, c_double_p, c_double_p, c_double_p, c_uint8_p, ctypes.c_void_p]),
+    "efa_letkf_cycle_interp_f32_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_long,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                      c_double_p, c_double_p, c_uint8_p,
+                                                      c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                      ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long,
+                                                      c_double_p, c_double_p, c_double_p, c_double_p, c_uint8_p, ctypes.c_void_p]),
+    "efa_letkf_interp_apply_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long,
+                                                  ctypes.c_void_p, ctypes.c_void_p]),
+    "efa_letkf_interp_apply_f32_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long,
+                                                      ctypes.c_void_p, ctypes.c_void_p]),
     "efa_last_timing": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p,
                                        ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_int)]),
     "efa_fill_synthetic_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_int,
@@ -436,6 +454,17 @@ class DeviceArray(object):
             self.free()
         except Exception:
             pass
+
+
+def letkf_mesh_nodes(n, stride):
+    """Node indices of the LETKF's weight-interpolation mesh on an axis of n points: 0, s, 2s, .. below n-1,
+    and n-1 itself; one node if n == 1."""
+    n, stride = int(n), int(stride)
+    if n < 1 or stride < 1:
+        raise ValueError("letkf_mesh_nodes: n=%d and stride=%d must be >= 1" % (n, stride))
+    if n == 1:
+        return np.zeros(1, dtype=np.int64)
+    return np.append(np.arange(0, n - 1, stride, dtype=np.int64), n - 1)
 
 
 class Context(object):
@@ -861,25 +890,46 @@ class Context(object):
         return d
 
     def letkf_cycle(self, rows, M, P, X, post, ym, Yp, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth, grid_lat,
-                    grid_lon, n_lead=1, obs_block_out=False, col_stats=None, f32=None):
+                    grid_lon, n_lead=1, obs_block_out=False, col_stats=None, f32=None, shape=None, stride=None):
         """efa_letkf_cycle_dev / _f32_dev: the LETKF on resident prior members, one ensemble-space solve per
         column under the Gaspari-Cohn taper and one per ob position for the obs block.  col_stats: a float64 DeviceArray
         (ncol, 3) for {n_local, dfs, sweeps} of every column, or None.  f32: the rows' storage (None: X's dtype).  Returns the
-        diagnostics."""
+        diagnostics.
+        With shape=(ny, nx) and stride=(s_y, s_x): efa_letkf_cycle_interp_dev / _f32_dev, the solve at the nodes
+        of the mesh only and the pairs interpolated to every column; col_stats then takes the NODE statistics, (nnodes, 3) in the
+        order of `letkf_mesh_nodes`."""
         val, err, asm, lat, lon, hw = self._ob_arrays(P, ob_value, ob_error, ob_assim, LOC_GC, ob_lat, ob_lon, ob_halfwidth)
         glat, glon, ncol = self._grid(LOC_GC, grid_lat, grid_lon)
         if f32 is None:
             f32 = isinstance(X, DeviceArray) and X.dtype == np.float32
-        entry = self.lib.efa_letkf_cycle_f32_dev if f32 else self.lib.efa_letkf_cycle_dev
         dt = np.float32 if f32 else np.float64
         d = self._diag_arrays(P)
-        _check(self.lib, entry(
-            self.handle, rows, M, P, self._addr(X, dt), self._addr(post, dt), self._addr(ym), self._addr(Yp), 1 if obs_block_out else 0,
-            _dp(val), _dp(err), _u8p(asm), _dp(lat), _dp(lon), _dp(hw), _dp(glat), _dp(glon), ncol, n_lead,
-            _dp(d["prior_mean"]), _dp(d["prior_var"]), _dp(d["post_mean"]), _dp(d["post_var"]), _u8p(d["assimilated"]),
-            self._addr(col_stats)))
+        head = (self.handle, rows, M, P, self._addr(X, dt), self._addr(post, dt), self._addr(ym), self._addr(Yp),
+                1 if obs_block_out else 0, _dp(val), _dp(err), _u8p(asm), _dp(lat), _dp(lon), _dp(hw), _dp(glat), _dp(glon))
+        tail = (n_lead, _dp(d["prior_mean"]), _dp(d["prior_var"]), _dp(d["post_mean"]), _dp(d["post_var"]), _u8p(d["assimilated"]),
+                self._addr(col_stats))
+        if stride is None:
+            entry = self.lib.efa_letkf_cycle_f32_dev if f32 else self.lib.efa_letkf_cycle_dev
+            _check(self.lib, entry(*(head + (ncol,) + tail)))
+        else:
+            if shape is None:
+                raise ValueError("letkf_cycle: stride needs the grid's shape=(ny, nx)")
+            entry = self.lib.efa_letkf_cycle_interp_f32_dev if f32 else self.lib.efa_letkf_cycle_interp_dev
+            _check(self.lib, entry(*(head + (int(shape[0]), int(shape[1]), int(stride[0]), int(stride[1])) + tail)))
         d["assimilated"] = d["assimilated"].astype(bool)
         return d
+
+    def letkf_interp_apply(self, rows, M, X, post, shape, stride, n_lead, Tw_nodes, node_stats=None, f32=None):
+        """efa_letkf_interp_apply_dev / _f32_dev: the interpolate-and-apply launch alone.  Tw_nodes: a float64
+        DeviceArray (nnodes, M, M + 1) of node pairs, row a of a node = T[a][0..M) | w[a], nodes in the order of
+        `letkf_mesh_nodes`; node_stats: (nnodes, 3) whose first entry is n_local, or None (every node counts as reached).  The
+        context's relaxation applies."""
+        if f32 is None:
+            f32 = isinstance(X, DeviceArray) and X.dtype == np.float32
+        entry = self.lib.efa_letkf_interp_apply_f32_dev if f32 else self.lib.efa_letkf_interp_apply_dev
+        dt = np.float32 if f32 else np.float64
+        _check(self.lib, entry(self.handle, rows, M, self._addr(X, dt), self._addr(post, dt), int(shape[0]), int(shape[1]),
+                               int(stride[0]), int(stride[1]), n_lead, self._addr(Tw_nodes), self._addr(node_stats)))
 
     def letkf_weights(self, M, P, ym, Yp, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth, pt_lat, pt_lon):
         """efa_letkf_weights_dev: the LETKF solve at the given points.  Returns (T (npts, M, M), w (npts, M), stats (npts, 3) =

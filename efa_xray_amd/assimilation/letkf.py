@@ -14,6 +14,15 @@ Same surface as `EnSRF`: `LETKF(state, obs, ...).update() -> (post_state, obs)` 
 `Observation` as `ETKF` writes them.  After an update `last_solve` holds three (ny, nx) arrays: `n_local` (the observations
 that reach the column), `dfs` (trace(HK) of the column's solve) and `sweeps` (Jacobi sweeps of its eigen-solve; 0 where no
 observation reaches the column: there is nothing to solve and the column's rows come back bit for bit).
+
+`weight_stride=s` or `(s_y, s_x)` turns on weight interpolation (Yang, Kalnay, Hunt & Bowler 2009): the pair
+(T, w) is solved at every s_y x s_x-th column only (and at the last row and column of the grid), interpolated bilinearly in
+grid-index space to the columns in between and applied there, which divides the number of eigen-solves by about s_y s_x.  The
+observation block and the diagnostics are unchanged, bit for bit.  `last_solve` then holds `n_local`, `dfs` and `sweeps` of the
+NODES, of shape (nyn, nxn), and their grid indices `node_y` and `node_x`.  A column all of whose nodes are out of every
+observation's reach keeps its rows bit for bit -- also when an observation of short radius reaches the column itself: that
+observation is lost to it.  Keep the stride, in km, well below the smallest localize_radius.  `None`, `1` and `(1, 1)` are the
+plain filter.
 """
 import numpy as np
 
@@ -35,13 +44,27 @@ _REFUSED = (
 )
 
 
+def _weight_stride(stride):
+    """None for the plain filter (None, 1, (1, 1)), else (s_y, s_x); ValueError for anything but integers >= 1."""
+    if stride is None:
+        return None
+    pair = tuple(stride) if isinstance(stride, (tuple, list)) else (stride, stride)
+    ok = len(pair) == 2 and all(isinstance(s, (int, np.integer)) and not isinstance(s, bool) and s >= 1 for s in pair)
+    if not ok:
+        raise ValueError("LETKF: weight_stride=%r must be an integer >= 1 or a pair (s_y, s_x) of them" % (stride,))
+    pair = (int(pair[0]), int(pair[1]))
+    return None if pair == (1, 1) else pair
+
+
 class LETKF(EnSRF):
     def __init__(self, state, obs, nproc=1, inflation=None, verbose=True, **kw):
         """Keyword-only options, as `EnSRF` has them: loc ('GC', the default and the only value), device, rtps / rtpp,
-        outlier_threshold; float32 states work as they do there.  ValueError, before any device work, for loc other than 'GC'
+        outlier_threshold; float32 states work as they do there; weight_stride (None, an int >= 1 or a pair of them: the module's
+        docstring).  ValueError, before any device work, for loc other than 'GC'
         (use `ETKF` for the unlocalised filter), adaptive_inflation, vert_coord, time_localize, var_impact,
-        sampling_error_correction, streamed, path, obs_batch, and for more than 136 members (the eigen-solve of a column keeps
+        sampling_error_correction, streamed, path, obs_batch, a weight_stride that is not an integer >= 1, and for more than 136 members (the eigen-solve of a column keeps
         its M x M array in LDS).  `update_arrays` is not offered."""
+        stride = _weight_stride(kw.pop("weight_stride", None))
         loc = kw.pop("loc", "GC")
         if not (isinstance(loc, str) and loc == "GC"):
             raise ValueError("LETKF: loc=%r is not supported: the LETKF is the localised filter and takes loc='GC' only; "
@@ -55,6 +78,7 @@ class LETKF(EnSRF):
                              "LDS (DESIGN.md 7y)" % (state.nmems(), MAX_MEMBERS))
         EnSRF.__init__(self, state, obs, nproc, inflation, verbose, "GC", **kw)
         self.last_solve = None
+        self.weight_stride = stride
 
     def update(self):
         self.last_solve = None
@@ -93,15 +117,24 @@ class LETKF(EnSRF):
         grid_lat, grid_lon = prior.column_latlon()
         ny, nx = prior.shape()[2:4]
         n_lead = prior.nvars() * prior.ntimes()
-        stats = ctx.empty((ny * nx, 3))
+        mesh = {}
+        sy, sx = ny, nx                         # the statistics' shape: the grid's, or the node mesh's
+        if self.weight_stride is not None:
+            node_y = _lib.letkf_mesh_nodes(ny, self.weight_stride[0])
+            node_x = _lib.letkf_mesh_nodes(nx, self.weight_stride[1])
+            sy, sx = node_y.size, node_x.size
+            mesh = dict(shape=(ny, nx), stride=self.weight_stride)
+        stats = ctx.empty((sy * sx, 3))
         if self.verbose:
             print("Beginning the column solves")
         diag = ctx.letkf_cycle(N, M, P, X, X, ym, Yp, value, error, assim, lat, lon, hw, grid_lat, grid_lon, n_lead,
-                               col_stats=stats, f32=f32)
+                               col_stats=stats, f32=f32, **mesh)
         self.last_timing = ctx.last_timing()
         self._write_diagnostics(diag)
-        st = stats.download().reshape(ny, nx, 3)
+        st = stats.download().reshape(sy, sx, 3)
         self.last_solve = dict(n_local=st[:, :, 0].astype(np.int64), dfs=st[:, :, 1].copy(), sweeps=st[:, :, 2].astype(np.int64))
+        if mesh:
+            self.last_solve.update(node_y=node_y, node_x=node_x)
         if self.verbose:
             print("Formatting posterior")
         return self._download_posterior(X), self.obs

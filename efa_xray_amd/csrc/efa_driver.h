@@ -12,7 +12,9 @@
 //   efa_gram.hip     the ensemble Gram matrix: its kernels and the driver of efa_gram_dev
 //   efa_etkf.hip     the batch observation-space solver's kernels (option "obs_solver" 1; driven from efa_phase_a.hip)
 //   efa_letkf.hip    the local ensemble transform Kalman filter: its kernels and the driver of efa_letkf_cycle_dev / efa_letkf_weights_dev
-//   efa_comm.hip     RCCL
+//                    and of the weight-interpolation entries (efa_letkf_cycle_interp_dev / efa_letkf_interp_apply_dev)
+//   efa_letkf_interp.hip  the interpolate-and-apply kernel of those entries
+//   efa_comm.hip    RCCL
 // Headers the diagnostics share: efa_quadrow.h (the four-lane row layout of k_sens_pass, k_verify, k_products and k_nbr_records),
 // efa_sortnet.h (the bitonic network on it), efa_quadreduce.h (table flush, chunk partial, k_group_reduce) and efa_diag.h (their
 // drivers' host scaffolding: the interval helper, WsLayout, check_slab_groups, pad_thresholds, pairs_aligned, clamp_blocks, launch_quad).
@@ -153,7 +155,14 @@ int end_state_call(efa_ctx* c, Interval& iv, bool timed = true, bool end_recorde
 int letkf_cycle(efa_ctx* c, Elem elem, long rows, int M, long P, const void* X_dev, void* post_dev, double* ym_dev, double* Yp_dev,
                 int obs_block_out, const double* ob_value, const double* ob_error, const uint8_t* ob_assim, const double* ob_lat,
                 const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
-                double* prior_mean, double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated, double* col_stats_dev);
+                double* prior_mean, double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated, double* col_stats_dev,
+                const efa::LetkfMesh* mesh = nullptr);
+// (mesh: efa_letkf_cycle_interp_dev / _f32_dev, DESIGN.md §7y-2 -- ncol is taken from it, the solve runs at its nodes only into a
+// buffer of the context, col_stats_dev receives the NODE statistics, and efa_letkf_interp.hip's kernel interpolates the pairs to
+// every column and applies them; a unit stride is the call without a mesh)
+// efa_letkf_interp_apply_dev / _f32_dev: that kernel alone on caller-given node pairs, under the context's relaxation; waits
+int letkf_interp_apply(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, void* post_dev, long ny, long nx, long stride_y,
+                       long stride_x, long n_lead, const double* Tw_nodes_dev, const double* node_stats_dev);
 // efa_letkf_weights_dev: the same solve at caller-given points, [T | w] of each to Tw_dev; waits
 int letkf_weights(efa_ctx* c, int M, long P, const double* ym_dev, const double* Yp_dev, const double* ob_value, const double* ob_error,
                   const uint8_t* ob_assim, const double* ob_lat, const double* ob_lon, const double* ob_hw, long npts,

@@ -412,6 +412,34 @@ hipError_t launch_letkf(const LetkfArgs& a, int mode, Elem elem, hipStream_t s);
 hipError_t launch_letkf_prior(long P, int M, const double* Yp, const double* ym, const double* ob_value, const double* ob_error,
                               const double* ob_req, double t2, double* prior_mean, double* prior_var, uint8_t* assimilated, double* act,
                               double* dr, hipStream_t s);
+// ---- weight interpolation (efa_letkf_interp.hip): [T | w] solved at the nodes of a coarse mesh of grid columns,
+// interpolated bilinearly in grid-index space to every column and applied to its rows
+struct LetkfMesh {
+  long ny, nx;        // the grid: column c = iy * nx + ix
+  long sy, sx;        // the node stride on each axis, 1 <= s <= max(n - 1, 1) (a longer stride gives the nodes of n - 1: the two ends)
+  // nodes of an axis: 0, s, 2 s, .. below n - 1, and n - 1 itself (the last cell may be shorter)
+  __host__ __device__ static long axis_nodes(long n, long s) { return n <= 1 ? 1 : (n - 1 + s - 1) / s + 1; }
+  __host__ __device__ static long axis_node(long j, long n, long s) { return j * s < n - 1 ? j * s : n - 1; }
+  __host__ __device__ long nyn() const { return axis_nodes(ny, sy); }
+  __host__ __device__ long nxn() const { return axis_nodes(nx, sx); }
+  __host__ __device__ long nnodes() const { return nyn() * nxn(); }
+  __host__ __device__ long ncol() const { return ny * nx; }
+  bool unit() const { return sy == 1 && sx == 1; }
+};
+struct LetkfInterpArgs {
+  LetkfMesh mesh;
+  long n_lead;         // rows per column, row lead * ncol + col
+  int M;
+  const void* Xin;     // [n_lead * ncol][M] prior members ...
+  void* Xout;          // ... and posterior members (the same address, or clear of Xin)
+  const double* Tw;    // [nnodes][M][M + 1] the node pairs, as kLetkfWeights writes them
+  const double* stats; // [nnodes][3] of the node solves, n_local first; null: every node counts as reached
+  int relax_kind;      // EFA_RELAX_*: RTPP on the interpolated T, RTPS per row
+  double relax_alpha;
+};
+size_t letkf_interp_lds_bytes(int M);
+// one workgroup per column; a.Xin / a.Xout are rows of `elem`
+hipError_t launch_letkf_interp(const LetkfInterpArgs& a, Elem elem, hipStream_t s);
 
 hipError_t launch_results_to_host(const void* src_dev, void* dst_host, size_t bytes, const int* st_dev, int* st_host, hipStream_t s);
 // diagnostic: `blocks` workgroups that hold `lds_bytes` of LDS each and spin for `ms` milliseconds

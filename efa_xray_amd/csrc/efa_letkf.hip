@@ -26,6 +26,8 @@
 //   kLetkfWeights skips 4 and writes T (as k_etkf_eig forms it: upper triangle, mirrored) and w of the point.
 //   A column no ob reaches (n_local = 0) runs no solve: its rows are copied bit for bit, its statistics are (0, 0, 0), its pair (I, 0).
 // Same inputs, same bits: every reduction has a fixed order, there are no floating-point atomics.
+// Weight interpolation: the driver below also runs kLetkfWeights at the nodes of a coarse mesh of grid columns and
+// hands the node pairs to k_letkf_interp (efa_letkf_interp.hip), which interpolates them to every column and applies them.
 #include "efa_driver.h"
 #include "efa_device.h"
 #include "efa_etkf_eig.h"
@@ -621,15 +623,77 @@ LetkfArgs letkf_args(int M, long npts, const LetkfLists& l, const double* Yp, co
   return a;
 }
 
+// the solve at `npts` points whose lists are built: [T | w] of each to Tw, the statistics to stats (or null); does not wait
+int letkf_solve_points(efa_ctx* c, int M, long npts, const LetkfLists& lists, const double* Yp_dev, const LetkfObs& o, double* Tw,
+                       double* stats) {
+  LetkfArgs a = letkf_args(M, npts, lists, Yp_dev, o);
+  a.Tw = Tw;
+  a.stats = stats;
+  EFA_HIP(launch_letkf(a, kLetkfWeights, Elem::f64, c->stream));
+  return EFA_OK;
+}
+
+// the mesh of a weight-interpolation call; *out has the strides cut to the axis (a stride beyond it gives the same nodes: the two ends)
+int letkf_check_mesh(const char* who, const LetkfMesh& m, LetkfMesh* out) {
+  if (m.ny < 1 || m.nx < 1) return fail(EFA_ERR_INVALID, "%s: the grid's shape (%ld, %ld) must be positive", who, m.ny, m.nx);
+  if (m.ny > 0x7FFFFFF0L / m.nx) return fail(EFA_ERR_INVALID, "%s: %ld x %ld columns exceed the launch grid", who, m.ny, m.nx);
+  if (m.sy < 1 || m.sx < 1) return fail(EFA_ERR_INVALID, "%s: the weight stride (%ld, %ld) must be >= 1 on both axes", who, m.sy, m.sx);
+  *out = m;
+  const long cy = m.ny > 2 ? m.ny - 1 : 1, cx = m.nx > 2 ? m.nx - 1 : 1;
+  if (out->sy > cy) out->sy = cy;
+  if (out->sx > cx) out->sx = cx;
+  return EFA_OK;
+}
+
+// the member rows of a state call: pointers, alignment, overlap, and rows == n_lead * ncol
+int letkf_check_rows(const char* who, const StateRows& r, long ncol, long n_lead) {
+  if (r.rows < 0) return fail(EFA_ERR_INVALID, "%s: negative row count", who);
+  if (r.rows == 0) return EFA_OK;
+  if (!r.prior || !r.post) return fail(EFA_ERR_INVALID, "%s: null state pointer", who);
+  if (r.elem == Elem::f32 && ((reinterpret_cast<uintptr_t>(r.prior) | reinterpret_cast<uintptr_t>(r.post)) & 3u) != 0)
+    return fail(EFA_ERR_INVALID, "%s: state pointers must be 4-byte aligned", who);
+  if (r.partial_overlap())
+    return fail(EFA_ERR_INVALID, "%s: the posterior rows overlap the prior rows without coinciding with them (in place means the same "
+                "address: a column's rows are read and written by its own workgroup only)", who);
+  if (n_lead < 1 || ncol < 1 || r.rows != n_lead * ncol)
+    return fail(EFA_ERR_INVALID, "%s: rows=%ld is not n_lead=%ld times the grid's %ld columns", who, r.rows, n_lead, ncol);
+  return EFA_OK;
+}
+
+// the interpolate-and-apply launch of the cycle and of efa_letkf_interp_apply_dev, under the context's relaxation; does not wait
+int letkf_interp_launch(efa_ctx* c, const char* who, Elem elem, int M, const void* X_dev, void* post_dev, const LetkfMesh& nodes,
+                        long n_lead, const double* Tw, const double* stats) {
+  LetkfInterpArgs a{};
+  a.mesh = nodes;
+  a.n_lead = n_lead;
+  a.M = M;
+  a.Xin = X_dev;
+  a.Xout = post_dev;
+  a.Tw = Tw;
+  a.stats = stats;
+  a.relax_kind = c->relax_kind;
+  a.relax_alpha = c->relax_alpha;
+  EFA_HIP(launch_letkf_interp(a, elem, c->stream));
+  return EFA_OK;
+}
+
 }  // namespace
 
 int letkf_cycle(efa_ctx* c, Elem elem, long rows, int M, long P, const void* X_dev, void* post_dev, double* ym_dev, double* Yp_dev,
                 int obs_block_out, const double* ob_value, const double* ob_error, const uint8_t* ob_assim, const double* ob_lat,
                 const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
-                double* prior_mean, double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated, double* col_stats_dev) {
+                double* prior_mean, double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated, double* col_stats_dev,
+                const LetkfMesh* mesh) {
   const bool f32 = elem == Elem::f32;
-  const char* who = f32 ? "efa_letkf_cycle_f32_dev" : "efa_letkf_cycle_dev";
+  const char* who = mesh ? (f32 ? "efa_letkf_cycle_interp_f32_dev" : "efa_letkf_cycle_interp_dev")
+                         : (f32 ? "efa_letkf_cycle_f32_dev" : "efa_letkf_cycle_dev");
   EFA_TRY(letkf_check_settings(c, who, M, P));
+  LetkfMesh nodes{};
+  if (mesh) {
+    EFA_TRY(letkf_check_mesh(who, *mesh, &nodes));
+    ncol = nodes.ncol();
+    if (mesh->unit()) mesh = nullptr;  // every column is a node: the plain call, bit for bit (col_stats_dev: the nodes are the columns)
+  }
   if (rows < 0) return fail(EFA_ERR_INVALID, "%s: negative row count", who);
   const StateRows r{X_dev, post_dev, elem, rows, M};
   if (rows > 0) {
@@ -647,7 +711,7 @@ int letkf_cycle(efa_ctx* c, Elem elem, long rows, int M, long P, const void* X_d
   harvest_state_ms(c);
   c->obs_ms = c->state_ms = 0.0;
   c->state_launches = 0;
-  c->phase_a_kind = 6;
+  c->phase_a_kind = mesh ? 7 : 6;
   c->path_taken = EFA_PATH_TRANSFORM;
   if (c->timing) EFA_HIP(hipEventRecord(c->obs_iv.begin, s));
 
@@ -670,10 +734,34 @@ int letkf_cycle(efa_ctx* c, Elem elem, long rows, int M, long P, const void* X_d
     EFA_HIP(launch_etkf_post(P, M, Yw, ymw, o.post_mean, o.post_var, s));
   }
   // ---- the state: the grid's lists (the obs' are consumed: the stream is in order), then ONE launch -----------------------------
+  //      (with a mesh: the nodes' lists, then the node solve and the interpolate-and-apply launch)
   LetkfLists glists;
+  const long nnodes = mesh ? nodes.nnodes() : 0;
+  double* node_stats = col_stats_dev;
+  if (rows > 0 && mesh) {
+    EFA_TRY(c->letkf_Tw.reserve((size_t)nnodes * M * (M + 1) * sizeof(double)));
+    if (!node_stats) {  // the apply reads n_local of every node
+      EFA_TRY(c->letkf_nst.reserve(3 * (size_t)nnodes * sizeof(double)));
+      node_stats = c->letkf_nst.as<double>();
+    }
+  }
   if (rows > 0 && P > 0) {
-    EFA_TRY(c->grid.upload(s, grid_lat, grid_lon, ncol));
-    EFA_TRY(letkf_build_lists(c, ncol, c->grid.lat.as<double>(), c->grid.lon.as<double>(), o, &glists));
+    if (mesh) {  // a node is a grid column: its position is that column's
+      std::vector<double> h(2 * (size_t)nnodes);
+      const long nyn = nodes.nyn(), nxn = nodes.nxn();
+      for (long jy = 0; jy < nyn; ++jy)
+        for (long jx = 0; jx < nxn; ++jx) {
+          const long col = LetkfMesh::axis_node(jy, nodes.ny, nodes.sy) * nodes.nx + LetkfMesh::axis_node(jx, nodes.nx, nodes.sx);
+          h[jy * nxn + jx] = grid_lat[col];
+          h[nnodes + jy * nxn + jx] = grid_lon[col];
+        }
+      const double *dlat = nullptr, *dlon = nullptr;
+      EFA_TRY(letkf_upload_points(c, nnodes, h.data(), h.data() + nnodes, &dlat, &dlon));
+      EFA_TRY(letkf_build_lists(c, nnodes, dlat, dlon, o, &glists));
+    } else {
+      EFA_TRY(c->grid.upload(s, grid_lat, grid_lon, ncol));
+      EFA_TRY(letkf_build_lists(c, ncol, c->grid.lat.as<double>(), c->grid.lon.as<double>(), o, &glists));
+    }
   }
   if (c->timing) {
     EFA_HIP(hipEventRecord(c->obs_iv.end, s));
@@ -681,7 +769,11 @@ int letkf_cycle(efa_ctx* c, Elem elem, long rows, int M, long P, const void* X_d
     c->obs_iv.pending = true;
     EFA_HIP(hipEventRecord(c->state_iv[0].begin, s));
   }
-  if (rows > 0) {
+  if (rows > 0 && mesh) {  // (P == 0: no lists, every node has the pair (I, 0) and no column changes)
+    EFA_TRY(letkf_solve_points(c, M, nnodes, glists, Yp_dev, o, c->letkf_Tw.as<double>(), node_stats));
+    EFA_TRY(letkf_interp_launch(c, who, elem, M, X_dev, post_dev, nodes, n_lead, c->letkf_Tw.as<double>(), node_stats));
+    c->state_launches = 2;
+  } else if (rows > 0) {
     LetkfArgs a = letkf_args(M, ncol, glists, Yp_dev, o);  // (P == 0: no lists, every column keeps its rows)
     a.n_lead = n_lead;
     a.Xin = X_dev;
@@ -748,11 +840,23 @@ int letkf_weights(efa_ctx* c, int M, long P, const double* ym_dev, const double*
     EFA_TRY(letkf_upload_points(c, npts, pt_lat, pt_lon, &dlat, &dlon));
     EFA_TRY(letkf_build_lists(c, npts, dlat, dlon, o, &lists));
   }
-  LetkfArgs a = letkf_args(M, npts, lists, Yp_dev, o);
-  a.Tw = Tw_dev;
-  a.stats = stats_dev;
-  EFA_HIP(launch_letkf(a, kLetkfWeights, Elem::f64, s));
+  EFA_TRY(letkf_solve_points(c, M, npts, lists, Yp_dev, o, Tw_dev, stats_dev));
   EFA_HIP(hipStreamSynchronize(s));
+  return EFA_OK;
+}
+
+int letkf_interp_apply(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, void* post_dev, long ny, long nx, long stride_y,
+                       long stride_x, long n_lead, const double* Tw_nodes_dev, const double* node_stats_dev) {
+  const bool f32 = elem == Elem::f32;
+  const char* who = f32 ? "efa_letkf_interp_apply_f32_dev" : "efa_letkf_interp_apply_dev";
+  EFA_TRY(letkf_check_settings(c, who, M, 0));
+  LetkfMesh nodes{};
+  EFA_TRY(letkf_check_mesh(who, LetkfMesh{ny, nx, stride_y, stride_x}, &nodes));
+  EFA_TRY(letkf_check_rows(who, StateRows{X_dev, post_dev, elem, rows, M}, nodes.ncol(), n_lead));
+  if (rows == 0) return EFA_OK;
+  if (!Tw_nodes_dev) return fail(EFA_ERR_INVALID, "%s: null node pairs", who);
+  EFA_TRY(letkf_interp_launch(c, who, elem, M, X_dev, post_dev, nodes, n_lead, Tw_nodes_dev, node_stats_dev));
+  EFA_HIP(hipStreamSynchronize(c->stream));
   return EFA_OK;
 }
 

@@ -342,7 +342,7 @@ int efa_etkf_solution(efa_ctx *ctx, int M, double *T /*[M*M]*/, double *w /*[M]*
  * pt_lat / pt_lon) and writes [T | w] of each to Tw_dev (device,
  * [npts][M][M+1]: row a = T[a][0..M) then w[a]; never relaxed) and the
  * statistics to stats_dev ([3*npts] or NULL): the probe the tests use, and the
- * hook for solving on a coarse grid (weight interpolation is out of scope). */
+ * solve the weight-interpolation entries below run at the nodes of their mesh. */
 int efa_letkf_cycle_dev(efa_ctx *ctx, long rows, int M, long P, const double *X_dev, double *post_dev, double *ym_dev,
                         double *Yp_dev, int obs_block_out, const double *ob_value, const double *ob_error,
                         const uint8_t *ob_assim, const double *ob_lat, const double *ob_lon, const double *ob_halfwidth_km,
@@ -359,6 +359,63 @@ int efa_letkf_weights_dev(efa_ctx *ctx, int M, long P, const double *ym_dev, con
                           const double *ob_error, const uint8_t *ob_assim, const double *ob_lat, const double *ob_lon,
                           const double *ob_halfwidth_km, long npts, const double *pt_lat, const double *pt_lon,
                           double *Tw_dev /* [npts][M][M+1] */, double *stats_dev /* [3*npts] or NULL */);
+
+/* ---- LETKF weight interpolation (Yang, Kalnay, Hunt & Bowler 2009)
+ * The pair [T | w] varies smoothly in space (it depends on the taper and the
+ * obs, not on the state rows), so it is solved at every (stride_y, stride_x)-th
+ * column only and interpolated bilinearly, in grid-index space, to the columns
+ * in between.  The grid has shape (ny, nx), column c = iy*nx + ix.  Nodes on an
+ * axis of n points with stride s >= 1: the indices 0, s, 2s, .. below n-1, and
+ * n-1 itself (1 node if n == 1, else ceil((n-1)/s) + 1; the last cell may be
+ * shorter); node (jy, jx) has index jy*nxn + jx and the position of its grid
+ * column.  Node pairs and statistics are exactly what efa_letkf_weights_dev
+ * writes for that position.  Column (iy, ix) lies in the cell [y0,y1] x [x0,x1]
+ * of consecutive nodes (on a node line: the cell with y0 < iy); with
+ * ty = (iy-y0)/(y1-y0), tx likewise (0 on an axis with one node),
+ *   [T_c | w_c] = sum beta_n [T_n | w_n],
+ *   beta = (1-ty)(1-tx), (1-ty)tx, ty(1-tx), ty tx on (y0,x0) (y0,x1) (y1,x0) (y1,x1),
+ * summed in that order over the corners with beta != 0; a corner with beta == 0
+ * is not read (a node column maps with its own pair alone).  Every row of
+ * column c maps as xam = xbm + X' w_c, Xap = X' T_c.  RTPP acts on the
+ * interpolated T_c, RTPS per row.  The obs block and the diagnostics are those
+ * of efa_letkf_cycle_dev bit for bit: ob j is solved at its own position.
+ * If every corner in use has n_local = 0 the column's rows come back bit for
+ * bit -- also when an ob of short radius reaches the column but none of its
+ * nodes: that ob is lost to the column.  Keep the stride (in km) well below
+ * the smallest half-width.  A NaN value of an assimilated ob poisons exactly
+ * the columns that use a node it reaches.  Same inputs, same bits.  Stride
+ * (1, 1) is efa_letkf_cycle_dev itself (node_stats_dev is then col_stats_dev).
+ * Refused with EFA_ERR_INVALID before any launch: all that efa_letkf_cycle_dev
+ * refuses, a stride < 1, rows != ny*nx*n_lead, a partial overlap of post_dev
+ * and X_dev (post_dev == X_dev is allowed).  node_stats_dev ([3*nnodes] or
+ * NULL) receives {n_local, dfs, sweeps} of every node.  Afterwards
+ * "phase_a_kind" reads 7; efa_last_timing: obs_ms as efa_letkf_cycle_dev (the
+ * nodes' lists in the place of the columns'), state_ms the node solve plus the
+ * interpolate-and-apply launch, state_launches 2.  They wait.
+ *
+ * efa_letkf_interp_apply_dev is the second launch alone, on caller-given node
+ * pairs Tw_nodes_dev ([nnodes][M][M+1], rows [T[a][0..M) | w[a]]) and
+ * node_stats_dev ([3*nnodes], only n_local is read; NULL: every node counts as
+ * reached), under the context's relaxation: for pairs solved elsewhere. */
+int efa_letkf_cycle_interp_dev(efa_ctx *ctx, long rows, int M, long P, const double *X_dev, double *post_dev, double *ym_dev,
+                               double *Yp_dev, int obs_block_out, const double *ob_value, const double *ob_error,
+                               const uint8_t *ob_assim, const double *ob_lat, const double *ob_lon, const double *ob_halfwidth_km,
+                               const double *grid_lat, const double *grid_lon, long ny, long nx, long stride_y, long stride_x,
+                               long n_lead, double *prior_mean, double *prior_var, double *post_mean, double *post_var,
+                               uint8_t *assimilated, double *node_stats_dev /* [3*nnodes] or NULL */);
+int efa_letkf_cycle_interp_f32_dev(efa_ctx *ctx, long rows, int M, long P, const float *X_dev, float *post_dev, double *ym_dev,
+                                   double *Yp_dev, int obs_block_out, const double *ob_value, const double *ob_error,
+                                   const uint8_t *ob_assim, const double *ob_lat, const double *ob_lon,
+                                   const double *ob_halfwidth_km, const double *grid_lat, const double *grid_lon, long ny, long nx,
+                                   long stride_y, long stride_x, long n_lead, double *prior_mean, double *prior_var,
+                                   double *post_mean, double *post_var, uint8_t *assimilated,
+                                   double *node_stats_dev /* [3*nnodes] or NULL */);
+int efa_letkf_interp_apply_dev(efa_ctx *ctx, long rows, int M, const double *X_dev, double *post_dev, long ny, long nx,
+                               long stride_y, long stride_x, long n_lead, const double *Tw_nodes_dev,
+                               const double *node_stats_dev /* [3*nnodes] or NULL */);
+int efa_letkf_interp_apply_f32_dev(efa_ctx *ctx, long rows, int M, const float *X_dev, float *post_dev, long ny, long nx,
+                                   long stride_y, long stride_x, long n_lead, const double *Tw_nodes_dev,
+                                   const double *node_stats_dev /* [3*nnodes] or NULL */);
 
 /* ---- device memory for callers without their own allocator -------------*/
 int efa_malloc(efa_ctx *ctx, size_t bytes, void **dev_out);
