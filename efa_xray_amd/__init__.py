@@ -10,7 +10,7 @@ from efa_xray_amd.observation.observation import Observation, gaspari_cohn, have
 from efa_xray_amd.assimilation.assimilation import Assimilation
 from efa_xray_amd.assimilation.ensrf import EnSRF
 from efa_xray_amd.assimilation.etkf import ETKF
-from efa_xray_amd.assimilation.letkf import LETKF
+from efa_xray_amd.assimilation.letkf import LETKF, SlabLETKF
 from efa_xray_amd.assimilation.adaptive_inflation import AdaptiveInflation
 from efa_xray_amd.assimilation.sampling_error import sampling_error_table
 from efa_xray_amd.postprocess.impact import observation_impact
@@ -22,7 +22,7 @@ from efa_xray_amd.postprocess.pmmean import probability_matched_mean
 from efa_xray_amd.postprocess.modes import (ensemble_gram, ensemble_eofs, ensemble_clusters, distances_from_gram,
                                             eofs_from_gram, clusters_from_gram)
 
-__all__ = ["EnsembleState", "Observation", "gaspari_cohn", "haversine", "Assimilation", "EnSRF", "ETKF", "LETKF", "AdaptiveInflation",
+__all__ = ["EnsembleState", "Observation", "gaspari_cohn", "haversine", "Assimilation", "EnSRF", "ETKF", "LETKF", "SlabLETKF", "AdaptiveInflation",
            "observation_impact", "ensemble_sensitivity", "observation_targets",
            "ensemble_verification", "ensemble_products", "probability_verification",
            "ensemble_gram", "ensemble_eofs", "ensemble_clusters", "distances_from_gram", "eofs_from_gram", "clusters_from_gram",

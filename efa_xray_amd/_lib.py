@@ -18,6 +18,7 @@ EFA_ERR_INVALID = -1
 EFA_ERR_NO_DEVICE = -2
 EFA_ERR_HIP = -3
 EFA_ERR_UNSUPPORTED = -4
+EFA_ERR_ALLOC = -5
 
 LOC_NONE = 0
 LOC_GC = 1
@@ -221,6 +222,7 @@ SIGNATURES = {
     "efa_letkf_interp_apply_f32_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                       ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long,
                                                       ctypes.c_void_p, ctypes.c_void_p]),
+    "efa_letkf_slab_groups": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, c_int32_p, ctypes.POINTER(ctypes.c_int)]),
     "efa_last_timing": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p,
                                        ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_int)]),
     "efa_fill_synthetic_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_int,
@@ -454,6 +456,12 @@ class DeviceArray(object):
             self.free()
         except Exception:
             pass
+
+
+# the slab calls of DESIGN.md 7y-3 take the arguments of the calls they stand beside
+for _name in ("cycle_dev", "cycle_f32_dev", "cycle_interp_dev", "cycle_interp_f32_dev", "weights_dev"):
+    SIGNATURES["efa_letkf_slab_" + _name] = SIGNATURES["efa_letkf_" + _name]
+del _name
 
 
 def letkf_mesh_nodes(n, stride):
@@ -890,7 +898,7 @@ class Context(object):
         return d
 
     def letkf_cycle(self, rows, M, P, X, post, ym, Yp, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth, grid_lat,
-                    grid_lon, n_lead=1, obs_block_out=False, col_stats=None, f32=None, shape=None, stride=None):
+                    grid_lon, n_lead=1, obs_block_out=False, col_stats=None, f32=None, shape=None, stride=None, _slab=False):
         """efa_letkf_cycle_dev / _f32_dev: the LETKF on resident prior members, one ensemble-space solve per
         column under the Gaspari-Cohn taper and one per ob position for the obs block.  col_stats: a float64 DeviceArray
         (ncol, 3) for {n_local, dfs, sweeps} of every column, or None.  f32: the rows' storage (None: X's dtype).  Returns the
@@ -908,16 +916,53 @@ class Context(object):
                 1 if obs_block_out else 0, _dp(val), _dp(err), _u8p(asm), _dp(lat), _dp(lon), _dp(hw), _dp(glat), _dp(glon))
         tail = (n_lead, _dp(d["prior_mean"]), _dp(d["prior_var"]), _dp(d["post_mean"]), _dp(d["post_var"]), _u8p(d["assimilated"]),
                 self._addr(col_stats))
+        stem = "efa_letkf_slab_cycle_" if _slab else "efa_letkf_cycle_"
         if stride is None:
-            entry = self.lib.efa_letkf_cycle_f32_dev if f32 else self.lib.efa_letkf_cycle_dev
+            entry = getattr(self.lib, stem + ("f32_dev" if f32 else "dev"))
             _check(self.lib, entry(*(head + (ncol,) + tail)))
         else:
             if shape is None:
                 raise ValueError("letkf_cycle: stride needs the grid's shape=(ny, nx)")
-            entry = self.lib.efa_letkf_cycle_interp_f32_dev if f32 else self.lib.efa_letkf_cycle_interp_dev
+            entry = getattr(self.lib, stem + ("interp_f32_dev" if f32 else "interp_dev"))
             _check(self.lib, entry(*(head + (int(shape[0]), int(shape[1]), int(stride[0]), int(stride[1])) + tail)))
         d["assimilated"] = d["assimilated"].astype(bool)
         return d
+
+    def letkf_slab_cycle(self, rows, M, P, X, post, ym, Yp, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth, grid_lat,
+                         grid_lon, n_lead=1, obs_block_out=False, col_stats=None, f32=None, shape=None, stride=None):
+        """efa_letkf_slab_cycle_dev / _f32_dev / _interp_dev / _interp_f32_dev: `letkf_cycle` with one solve per
+        (slab group, column) under the context's vertical and / or slab setting, which must be on and sized for P and n_lead.
+        col_stats: a float64 DeviceArray (ngroups, ncol, 3), or (ngroups, nnodes, 3) with a stride; ngroups from
+        `letkf_slab_groups`."""
+        return self.letkf_cycle(rows, M, P, X, post, ym, Yp, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth, grid_lat,
+                                grid_lon, n_lead, obs_block_out, col_stats, f32, shape, stride, _slab=True)
+
+    def letkf_slab_groups(self, n_lead):
+        """efa_letkf_slab_groups: (group_of_slab int32 [n_lead], ngroups) under the context's vertical and / or slab setting."""
+        g = np.empty(int(n_lead), dtype=np.int32)
+        n = ctypes.c_int(0)
+        _check(self.lib, self.lib.efa_letkf_slab_groups(self.handle, int(n_lead), g.ctypes.data_as(c_int32_p) if g.size else None,
+                                                        ctypes.byref(n)))
+        return g, n.value
+
+    def letkf_slab_weights(self, M, P, ym, Yp, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth, pt_lat, pt_lon, n_lead):
+        """efa_letkf_slab_weights_dev: the solve of every slab group at the given points.  Returns (T (ngroups, npts, M, M),
+        w (ngroups, npts, M), stats (ngroups, npts, 3))."""
+        val, err, asm, lat, lon, hw = self._ob_arrays(P, ob_value, ob_error, ob_assim, LOC_GC, ob_lat, ob_lon, ob_halfwidth)
+        plat = np.ascontiguousarray(pt_lat, dtype=np.float64).reshape(-1)
+        plon = np.ascontiguousarray(pt_lon, dtype=np.float64).reshape(-1)
+        assert plat.shape == plon.shape
+        npts = plat.shape[0]
+        _, ng = self.letkf_slab_groups(n_lead)
+        Tw = self.empty((ng, max(npts, 1), M, M + 1))
+        st = self.empty((ng, max(npts, 1), 3))
+        _check(self.lib, self.lib.efa_letkf_slab_weights_dev(
+            self.handle, M, P, self._addr(ym), self._addr(Yp), _dp(val), _dp(err), _u8p(asm), _dp(lat), _dp(lon), _dp(hw),
+            npts, _dp(plat), _dp(plon), self._addr(Tw), self._addr(st)))
+        if npts == 0:
+            return np.zeros((ng, 0, M, M)), np.zeros((ng, 0, M)), np.zeros((ng, 0, 3))
+        tw = Tw.download()
+        return np.ascontiguousarray(tw[:, :, :, :M]), np.ascontiguousarray(tw[:, :, :, M]), st.download()
 
     def letkf_interp_apply(self, rows, M, X, post, shape, stride, n_lead, Tw_nodes, node_stats=None, f32=None):
         """efa_letkf_interp_apply_dev / _f32_dev: the interpolate-and-apply launch alone.  Tw_nodes: a float64

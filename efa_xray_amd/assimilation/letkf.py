@@ -23,6 +23,12 @@ NODES, of shape (nyn, nxn), and their grid indices `node_y` and `node_x`.  A col
 observation's reach keeps its rows bit for bit -- also when an observation of short radius reaches the column itself: that
 observation is lost to it.  Keep the stride, in km, well below the smallest localize_radius.  `None`, `1` and `(1, 1)` are the
 plain filter.
+
+`SlabLETKF` is the LETKF with the vertical, temporal and cross-variable factors of `EnSRF(loc='GC')`:
+`vert_coord`, `time_localize` and `var_impact` as documented there.  The (nvars x ntimes) slabs of a column no longer share one
+pair: slabs whose factors agree for every observation form a group, and every (group, column) runs its own solve under the
+product taper.  `last_solve` then holds `n_local`, `dfs` and `sweeps` of shape (ngroups, ny, nx) -- (ngroups, nyn, nxn) with a
+weight_stride -- and `group_of_slab` of shape (nvars, ntimes).  With none of the three options it is `LETKF`, bit for bit.
 """
 import numpy as np
 
@@ -34,9 +40,9 @@ MAX_MEMBERS = 136
 # keywords of EnSRF that the per-column batch solve does not serve, with the reason given to the caller
 _REFUSED = (
     ("adaptive_inflation", "adaptive inflation follows the serial order of the observations, which a column's batch solve does not have"),
-    ("vert_coord", "vertical localisation needs a solve per (slab group, column): out of scope (DESIGN.md 7y)"),
-    ("time_localize", "temporal localisation needs a solve per (slab group, column): out of scope (DESIGN.md 7y)"),
-    ("var_impact", "cross-variable localisation needs a solve per (slab group, column): out of scope (DESIGN.md 7y)"),
+    ("vert_coord", "vertical localisation needs a solve per (slab group, column): use SlabLETKF (DESIGN.md 7y-3)"),
+    ("time_localize", "temporal localisation needs a solve per (slab group, column): use SlabLETKF (DESIGN.md 7y-3)"),
+    ("var_impact", "cross-variable localisation needs a solve per (slab group, column): use SlabLETKF (DESIGN.md 7y-3)"),
     ("sampling_error_correction", "the sampling error correction acts on the serial gain of one observation at a time"),
     ("streamed", "the streamed host path is out of scope for the LETKF (DESIGN.md 7y): the state must be resident"),
     ("path", "there is no sweep or transform route to choose: every column runs its own solve and apply in one kernel"),
@@ -57,6 +63,8 @@ def _weight_stride(stride):
 
 
 class LETKF(EnSRF):
+    _served = ()        # the keywords of _REFUSED a subclass serves: handed on to EnSRF, which validates them
+
     def __init__(self, state, obs, nproc=1, inflation=None, verbose=True, **kw):
         """Keyword-only options, as `EnSRF` has them: loc ('GC', the default and the only value), device, rtps / rtpp,
         outlier_threshold; float32 states work as they do there; weight_stride (None, an int >= 1 or a pair of them: the module's
@@ -70,8 +78,10 @@ class LETKF(EnSRF):
             raise ValueError("LETKF: loc=%r is not supported: the LETKF is the localised filter and takes loc='GC' only; "
                              "use ETKF for the unlocalised ensemble transform filter" % (loc,))
         for name, why in _REFUSED:
+            if name in self._served:
+                continue
             if name in kw and kw[name] is not None and kw[name] is not False:
-                raise ValueError("LETKF does not take %s: %s" % (name, why))
+                raise ValueError("%s does not take %s: %s" % (type(self).__name__, name, why))
             kw.pop(name, None)
         if state.nmems() > MAX_MEMBERS:
             raise ValueError("LETKF: %d members exceed %d, the range in which the eigen-solve's M x M array of a column fits in "
@@ -117,6 +127,7 @@ class LETKF(EnSRF):
         grid_lat, grid_lon = prior.column_latlon()
         ny, nx = prior.shape()[2:4]
         n_lead = prior.nvars() * prior.ntimes()
+        slab = self.vert_coord is not None or self.slab is not None     # (SlabLETKF only: LETKF refuses the three keywords)
         mesh = {}
         sy, sx = ny, nx                         # the statistics' shape: the grid's, or the node mesh's
         if self.weight_stride is not None:
@@ -124,15 +135,30 @@ class LETKF(EnSRF):
             node_x = _lib.letkf_mesh_nodes(nx, self.weight_stride[1])
             sy, sx = node_y.size, node_x.size
             mesh = dict(shape=(ny, nx), stride=self.weight_stride)
-        stats = ctx.empty((sy * sx, 3))
         if self.verbose:
             print("Beginning the column solves")
-        diag = ctx.letkf_cycle(N, M, P, X, X, ym, Yp, value, error, assim, lat, lon, hw, grid_lat, grid_lon, n_lead,
-                               col_stats=stats, f32=f32, **mesh)
+        if slab:
+            try:
+                group_of, ng = ctx.letkf_slab_groups(n_lead)
+                stats = ctx.empty((ng * sy * sx, 3))
+                diag = ctx.letkf_slab_cycle(N, M, P, X, X, ym, Yp, value, error, assim, lat, lon, hw, grid_lat, grid_lon, n_lead,
+                                            col_stats=stats, f32=f32, **mesh)
+            finally:                            # the context is shared per device: the settings do not outlive the update
+                ctx.set_vertical_localization(None)
+                ctx.set_slab_localization(None)
+        else:
+            stats = ctx.empty((sy * sx, 3))
+            diag = ctx.letkf_cycle(N, M, P, X, X, ym, Yp, value, error, assim, lat, lon, hw, grid_lat, grid_lon, n_lead,
+                                   col_stats=stats, f32=f32, **mesh)
         self.last_timing = ctx.last_timing()
         self._write_diagnostics(diag)
-        st = stats.download().reshape(sy, sx, 3)
-        self.last_solve = dict(n_local=st[:, :, 0].astype(np.int64), dfs=st[:, :, 1].copy(), sweeps=st[:, :, 2].astype(np.int64))
+        if slab:
+            st = stats.download().reshape(ng, sy, sx, 3)
+            self.last_solve = dict(n_local=st[..., 0].astype(np.int64), dfs=st[..., 1].copy(), sweeps=st[..., 2].astype(np.int64),
+                                   group_of_slab=group_of.astype(np.int64).reshape(prior.nvars(), prior.ntimes()))
+        else:
+            st = stats.download().reshape(sy, sx, 3)
+            self.last_solve = dict(n_local=st[:, :, 0].astype(np.int64), dfs=st[:, :, 1].copy(), sweeps=st[:, :, 2].astype(np.int64))
         if mesh:
             self.last_solve.update(node_y=node_y, node_x=node_x)
         if self.verbose:
@@ -141,3 +167,11 @@ class LETKF(EnSRF):
 
     def update_arrays(self, xbm, Xbp):
         raise ValueError("LETKF does not offer update_arrays (out of scope, DESIGN.md 7y); use update()")
+
+
+class SlabLETKF(LETKF):
+    """The LETKF under vertical, temporal and cross-variable localisation: `LETKF` plus the keywords
+    vert_coord, time_localize and var_impact of `EnSRF`, validated as there and read from the observations' `vert`,
+    `vert_localize_radius`, `time` and `time_localize_radius`.  One solve per (slab group, column); everything else `LETKF`
+    refuses is refused here.  With none of the three given it is `LETKF` bit for bit (the plain entry point is called)."""
+    _served = ("vert_coord", "time_localize", "var_impact")

@@ -1019,6 +1019,68 @@ int efa_letkf_cycle_interp_f32_dev(efa_ctx* c, long rows, int M, long P, const f
                                post_var, assimilated, node_stats_dev, &mesh);
 }
 
+int efa_letkf_slab_cycle_dev(efa_ctx* c, long rows, int M, long P, const double* X_dev, double* post_dev, double* ym_dev,
+                             double* Yp_dev, int obs_block_out, const double* ob_value, const double* ob_error, const uint8_t* ob_assim,
+                             const double* ob_lat, const double* ob_lon, const double* ob_halfwidth_km, const double* grid_lat,
+                             const double* grid_lon, long ncol, long n_lead, double* prior_mean, double* prior_var, double* post_mean,
+                             double* post_var, uint8_t* assimilated, double* col_stats_dev) {
+  EFA_TRY(use(c));
+  return efa_host::letkf_cycle(c, efa::Elem::f64, rows, M, P, X_dev, post_dev, ym_dev, Yp_dev, obs_block_out, ob_value, ob_error, ob_assim,
+                               ob_lat, ob_lon, ob_halfwidth_km, grid_lat, grid_lon, ncol, n_lead, prior_mean, prior_var, post_mean,
+                               post_var, assimilated, col_stats_dev, nullptr, true);
+}
+
+int efa_letkf_slab_cycle_f32_dev(efa_ctx* c, long rows, int M, long P, const float* X_dev, float* post_dev, double* ym_dev,
+                                 double* Yp_dev, int obs_block_out, const double* ob_value, const double* ob_error,
+                                 const uint8_t* ob_assim, const double* ob_lat, const double* ob_lon, const double* ob_halfwidth_km,
+                                 const double* grid_lat, const double* grid_lon, long ncol, long n_lead, double* prior_mean,
+                                 double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated, double* col_stats_dev) {
+  EFA_TRY(use(c));
+  return efa_host::letkf_cycle(c, efa::Elem::f32, rows, M, P, X_dev, post_dev, ym_dev, Yp_dev, obs_block_out, ob_value, ob_error, ob_assim,
+                               ob_lat, ob_lon, ob_halfwidth_km, grid_lat, grid_lon, ncol, n_lead, prior_mean, prior_var, post_mean,
+                               post_var, assimilated, col_stats_dev, nullptr, true);
+}
+
+int efa_letkf_slab_cycle_interp_dev(efa_ctx* c, long rows, int M, long P, const double* X_dev, double* post_dev, double* ym_dev,
+                                    double* Yp_dev, int obs_block_out, const double* ob_value, const double* ob_error,
+                                    const uint8_t* ob_assim, const double* ob_lat, const double* ob_lon, const double* ob_halfwidth_km,
+                                    const double* grid_lat, const double* grid_lon, long ny, long nx, long stride_y, long stride_x,
+                                    long n_lead, double* prior_mean, double* prior_var, double* post_mean, double* post_var,
+                                    uint8_t* assimilated, double* node_stats_dev) {
+  EFA_TRY(use(c));
+  const efa::LetkfMesh mesh{ny, nx, stride_y, stride_x};
+  return efa_host::letkf_cycle(c, efa::Elem::f64, rows, M, P, X_dev, post_dev, ym_dev, Yp_dev, obs_block_out, ob_value, ob_error, ob_assim,
+                               ob_lat, ob_lon, ob_halfwidth_km, grid_lat, grid_lon, 0, n_lead, prior_mean, prior_var, post_mean,
+                               post_var, assimilated, node_stats_dev, &mesh, true);
+}
+
+int efa_letkf_slab_cycle_interp_f32_dev(efa_ctx* c, long rows, int M, long P, const float* X_dev, float* post_dev, double* ym_dev,
+                                        double* Yp_dev, int obs_block_out, const double* ob_value, const double* ob_error,
+                                        const uint8_t* ob_assim, const double* ob_lat, const double* ob_lon,
+                                        const double* ob_halfwidth_km, const double* grid_lat, const double* grid_lon, long ny, long nx,
+                                        long stride_y, long stride_x, long n_lead, double* prior_mean, double* prior_var,
+                                        double* post_mean, double* post_var, uint8_t* assimilated, double* node_stats_dev) {
+  EFA_TRY(use(c));
+  const efa::LetkfMesh mesh{ny, nx, stride_y, stride_x};
+  return efa_host::letkf_cycle(c, efa::Elem::f32, rows, M, P, X_dev, post_dev, ym_dev, Yp_dev, obs_block_out, ob_value, ob_error, ob_assim,
+                               ob_lat, ob_lon, ob_halfwidth_km, grid_lat, grid_lon, 0, n_lead, prior_mean, prior_var, post_mean,
+                               post_var, assimilated, node_stats_dev, &mesh, true);
+}
+
+int efa_letkf_slab_weights_dev(efa_ctx* c, int M, long P, const double* ym_dev, const double* Yp_dev, const double* ob_value,
+                               const double* ob_error, const uint8_t* ob_assim, const double* ob_lat, const double* ob_lon,
+                               const double* ob_halfwidth_km, long npts, const double* pt_lat, const double* pt_lon, double* Tw_dev,
+                               double* stats_dev) {
+  EFA_TRY(use(c));
+  return efa_host::letkf_weights(c, M, P, ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km, npts, pt_lat,
+                                 pt_lon, Tw_dev, stats_dev, true);
+}
+
+int efa_letkf_slab_groups(efa_ctx* c, long n_lead, int* group_of, int* ngroups) {
+  EFA_TRY(use(c));
+  return efa_host::letkf_slab_group_table(c, n_lead, group_of, ngroups);
+}
+
 int efa_letkf_interp_apply_dev(efa_ctx* c, long rows, int M, const double* X_dev, double* post_dev, long ny, long nx, long stride_y,
                                long stride_x, long n_lead, const double* Tw_nodes_dev, const double* node_stats_dev) {
   EFA_TRY(use(c));

@@ -216,7 +216,7 @@ struct efa_ctx {
   DevBuf traj, tw_mat, status, dbg;  // pipeline: trajectory records, GC obs-obs taper, status words, stamps
   const double* ye_ptr = nullptr;  // where Phase B reads the recorded ye rows
   long ye_stride = 0;
-  int phase_a_kind = 0;          // 1 vector-chain pipeline, 2 per-batch kernels, 3 Gram leader, 4 band leader, 5 batch solver, 6 LETKF (efa_letkf_cycle_dev), 7 LETKF with weight interpolation (efa_letkf_cycle_interp_dev)
+  int phase_a_kind = 0;          // 1 vector-chain pipeline, 2 per-batch kernels, 3 Gram leader, 4 band leader, 5 batch solver, 6 LETKF (efa_letkf_cycle_dev), 7 LETKF with weight interpolation (efa_letkf_cycle_interp_dev), 8 / 9 the two under vertical / slab localisation (efa_letkf_slab_cycle_dev / _interp_dev)
   DevBuf ob_pack, out_pack;  // the per-ob inputs / diagnostics below are slices of these two allocations (stage_obs_inputs)
   PinBuf pin_in, pin_out;    // their pinned host images: one H2D and one D2H per call
   PinBuf pin_fs;             // pinned image of the forward-operator stencil
@@ -312,6 +312,12 @@ struct efa_ctx {
   DevBuf letkf_pairs; // the list builders' pair counter
   DevBuf letkf_Tw;    // weight interpolation (efa_letkf_cycle_interp_dev, §7y-2): the node pairs [nnodes][M][M+1] ...
   DevBuf letkf_nst;   // ... and the node statistics [nnodes][3] when the caller takes none
+  // --- the LETKF's slab groups (efa_letkf_slab_cycle_dev): slabs whose factors agree for every ob share one solve
+  std::vector<int> lg_group_of;                   // [n_lead] the group of every slab, numbered by first appearance
+  int lg_ngroups = 0;
+  long lg_vl_serial = -1, lg_sl_serial = -1;      // the settings the groups were computed from
+  const void* lg_ptr = nullptr;
+  DevBuf lg_dev;      // ints: rep [ngroups] | grp_off [ngroups + 1] | grp_leads [n_lead]
   // --- observation impact (efa_obs_impact_dev): buffers of its own, nothing above is touched by it ---------------
   //     (efa_obs_impact_slab_dev, §7u, brings sl_tab up to date as well: the table's cache, keyed by the two settings' serials)
   DevBuf imp_ob;    // per ob: used flags (coefficient-shaped) | scale | lat | lon | half-width | obtrig scratch | impact

@@ -156,17 +156,22 @@ int letkf_cycle(efa_ctx* c, Elem elem, long rows, int M, long P, const void* X_d
                 int obs_block_out, const double* ob_value, const double* ob_error, const uint8_t* ob_assim, const double* ob_lat,
                 const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
                 double* prior_mean, double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated, double* col_stats_dev,
-                const efa::LetkfMesh* mesh = nullptr);
+                const efa::LetkfMesh* mesh = nullptr, bool slab = false);
 // (mesh: efa_letkf_cycle_interp_dev / _f32_dev, DESIGN.md §7y-2 -- ncol is taken from it, the solve runs at its nodes only into a
 // buffer of the context, col_stats_dev receives the NODE statistics, and efa_letkf_interp.hip's kernel interpolates the pairs to
 // every column and applies them; a unit stride is the call without a mesh)
+// (slab: efa_letkf_slab_cycle_dev and its kin, DESIGN.md §7y-3 -- one solve per (slab group, column) under the vertical and / or slab
+// setting; col_stats_dev is then [ngroups][ncol or nnodes][3])
 // efa_letkf_interp_apply_dev / _f32_dev: that kernel alone on caller-given node pairs, under the context's relaxation; waits
 int letkf_interp_apply(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, void* post_dev, long ny, long nx, long stride_y,
                        long stride_x, long n_lead, const double* Tw_nodes_dev, const double* node_stats_dev);
 // efa_letkf_weights_dev: the same solve at caller-given points, [T | w] of each to Tw_dev; waits
 int letkf_weights(efa_ctx* c, int M, long P, const double* ym_dev, const double* Yp_dev, const double* ob_value, const double* ob_error,
                   const uint8_t* ob_assim, const double* ob_lat, const double* ob_lon, const double* ob_hw, long npts,
-                  const double* pt_lat, const double* pt_lon, double* Tw_dev, double* stats_dev);
+                  const double* pt_lat, const double* pt_lon, double* Tw_dev, double* stats_dev, bool slab = false);
+// (slab: efa_letkf_slab_weights_dev -- Tw_dev [ngroups][npts][M][M + 1], stats_dev [ngroups][npts][3])
+// efa_letkf_slab_groups: the group of every slab under the context's settings, numbered by first appearance
+int letkf_slab_group_table(efa_ctx* c, long n_lead, int* group_of, int* ngroups);
 
 // ---- efa_impact.hip -----------------------------------------------------------------------------------------------------------
 // efa_obs_impact_dev: checks, the call's own active lists, the contraction and its reduction; waits before it returns impact[P]

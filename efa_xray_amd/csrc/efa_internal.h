@@ -441,6 +441,37 @@ size_t letkf_interp_lds_bytes(int M);
 // one workgroup per column; a.Xin / a.Xout are rows of `elem`
 hipError_t launch_letkf_interp(const LetkfInterpArgs& a, Elem elem, hipStream_t s);
 
+// ---- vertical, temporal and variable localisation of the LETKF: one solve per (slab group, column) -------------
+// Slabs whose factors agree for every ob form a group; group g is solved under rho_k(c) * S[k][rep[g]] and maps the rows of its
+// slabs grp_leads[grp_off[g] .. grp_off[g + 1]) only.
+struct LetkfGroups {
+  int ngroups;
+  long s_pitch;          // slabs of the table
+  const double* S;       // [P][s_pitch] the slab factor table (launch_slab_factor)
+  const int* rep;        // [ngroups] the first slab of every group
+  const int* grp_off;    // [ngroups + 1]
+  const int* grp_leads;  // [n_lead] the slabs, group by group, ascending within a group
+};
+// k_letkf with the SLAB switch: npts * ngroups solves, the group the fastest index of the launch; stats [ngroups][npts][3], Tw
+// [ngroups][npts][M][M + 1].  kLetkfMembers and kLetkfWeights only (the obs block runs the plain kLetkfPerts launch on lists that
+// launch_letkf_obs_factor scaled).
+struct LetkfSlabArgs : LetkfArgs {
+  LetkfGroups grp;
+};
+hipError_t launch_letkf_slab(const LetkfSlabArgs& a, int mode, Elem elem, hipStream_t s);
+// the lists built at the P ob positions (blocks of 16 points): wts[e * 16 + cb] *= F(j, idx[e]), j = blk * 16 + cb, with
+// F(j, k) = (V(j,k) T(j,k)) C[k, v_j] of §7t (ob_vert null: V = 1; slab null: T = C = 1); a zero stays zero
+hipError_t launch_letkf_obs_factor(long P, const long* off, const int* cnt, const int* idx, double* wts, const double* ob_vert,
+                                   const double* ob_vhw, const SlabObs* slab, hipStream_t s);
+// k_letkf_interp with the SLAB switch: one workgroup per (column, group), node pairs Tw [ngroups][nnodes][M][M + 1] and node
+// statistics [ngroups][nnodes][3]
+struct LetkfInterpSlabArgs : LetkfInterpArgs {
+  int ngroups;
+  const int* grp_off;
+  const int* grp_leads;
+};
+hipError_t launch_letkf_interp_slab(const LetkfInterpSlabArgs& a, Elem elem, hipStream_t s);
+
 hipError_t launch_results_to_host(const void* src_dev, void* dst_host, size_t bytes, const int* st_dev, int* st_host, hipStream_t s);
 // diagnostic: `blocks` workgroups that hold `lds_bytes` of LDS each and spin for `ms` milliseconds
 hipError_t launch_occupy(int blocks, size_t lds_bytes, double ms, hipStream_t s);

@@ -28,13 +28,21 @@
 // Same inputs, same bits: every reduction has a fixed order, there are no floating-point atomics.
 // Weight interpolation: the driver below also runs kLetkfWeights at the nodes of a coarse mesh of grid columns and
 // hands the node pairs to k_letkf_interp (efa_letkf_interp.hip), which interpolates them to every column and applies them.
+// Vertical, temporal and variable localisation (efa_letkf_slab_cycle_dev and its kin): k_letkf with the SLAB switch
+// solves once per (slab group, column) under rho_k(c) * S[k][rep[g]], S the slab factor table of §7t; k_letkf_obs_factor scales the
+// tapers of the lists built at the ob positions by the obs-obs factor F(j, k), after which the obs block runs as above.  The driver
+// computes the groups from the host copies of the two settings (letkf_groups).
 #include "efa_driver.h"
 #include "efa_device.h"
 #include "efa_etkf_eig.h"
 #include "efa_rows.h"
+#include "efa_slabfactor.h"
 
 #include <cmath>
+#include <cstdint>
 #include <cstring>
+#include <map>
+#include <tuple>
 #include <vector>
 
 namespace efa {
@@ -120,8 +128,16 @@ __device__ __forceinline__ double letkf_round<double>(double v) { return v; }
 template <>
 __device__ __forceinline__ float letkf_round<float>(double v) { return (float)v; }
 
-template <int MODE, typename E, int NTMAX>
-__global__ __launch_bounds__(NTMAX) void k_letkf(const LetkfArgs a) {
+// SLAB: one workgroup per (column, slab group), the group the fastest index of the launch so that the
+// workgroups of a column run together and find its list and Yp rows in L2; the staged weight is fl(fl(rho S[k][rep[g]]) / r), the
+// apply walks the group's slabs, the statistics and the pairs are laid out [group][point].
+template <bool SLAB>
+struct LetkfArgsOf { typedef LetkfArgs type; };
+template <>
+struct LetkfArgsOf<true> { typedef LetkfSlabArgs type; };
+
+template <int MODE, typename E, int NTMAX, bool SLAB = false>
+__global__ __launch_bounds__(NTMAX) void k_letkf(const typename LetkfArgsOf<SLAB>::type a) {
   extern __shared__ __align__(16) double letkf_smem[];
   const int M = a.M;
   const int tid = (int)threadIdx.x, nth = (int)blockDim.x, lane = tid & 63;
@@ -142,8 +158,21 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const LetkfArgs a) {
   int* rot_s = reinterpret_cast<int*>(mean_s + kLetkfSmall);
   int* nloc_s = rot_s + 2;
 
-  const long bi = (long)blockIdx.x >> 4;
-  const int cb = (int)(blockIdx.x & 15);
+  long bid = (long)blockIdx.x, grp = 0, lead0 = 0, nlead_g = a.n_lead;  // the group, its first entry in grp_leads, its slabs
+  const double* Sg = nullptr;                                            // S[.][rep[grp]], pitch sp
+  long sp = 0;
+  const int* leads = nullptr;
+  if constexpr (SLAB) {
+    grp = bid % a.grp.ngroups;
+    bid = bid / a.grp.ngroups;
+    lead0 = a.grp.grp_off[grp];
+    nlead_g = a.grp.grp_off[grp + 1] - lead0;
+    sp = a.grp.s_pitch;
+    Sg = a.grp.S + a.grp.rep[grp];
+    leads = a.grp.grp_leads + lead0;
+  }
+  const long bi = bid >> 4;
+  const int cb = (int)(bid & 15);
   const long blk = a.order ? (long)a.order[bi] : bi;
   const long col = blk * 16 + cb;
   if (col >= a.npts) return;  // (uniform)
@@ -153,7 +182,11 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const LetkfArgs a) {
   // n_local: the listed obs whose taper on THIS column is not zero
   if (wave == 0) {
     int cl = 0;
-    for (int e = lane; e < n; e += 64) cl += (a.wts[(size_t)(off + e) * 16 + cb] != 0.0) ? 1 : 0;
+    for (int e = lane; e < n; e += 64) {
+      double w = a.wts[(size_t)(off + e) * 16 + cb];
+      if constexpr (SLAB) w = w * Sg[(size_t)a.idx[off + e] * sp];
+      cl += (w != 0.0) ? 1 : 0;
+    }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) cl += __shfl_xor(cl, o, 64);
     if (lane == 0) *nloc_s = cl;
@@ -166,7 +199,9 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const LetkfArgs a) {
       const E* in = static_cast<const E*>(a.Xin);
       E* out = static_cast<E*>(a.Xout);
       if (in != out)
-        for (long l = 0; l < a.n_lead; ++l) {
+        for (long li = 0; li < nlead_g; ++li) {
+          long l = li;
+          if constexpr (SLAB) l = leads[li];
           const size_t base = (size_t)(l * a.npts + col) * M;
           for (int m = tid; m < M; m += nth) out[base + m] = in[base + m];
         }
@@ -174,13 +209,13 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const LetkfArgs a) {
       for (int m = tid; m < M; m += nth) a.Yp_out[(size_t)col * M + m] = a.Yp_in[(size_t)col * M + m];
       if (tid == 0) a.ym_out[col] = a.ym_in[col];
     } else {
-      double* tw = a.Tw + (size_t)col * M * (M + 1);
+      double* tw = a.Tw + (size_t)(grp * a.npts + col) * M * (M + 1);
       for (int e = tid; e < M * (M + 1); e += nth) {
         const int r = e / (M + 1), c = e - r * (M + 1);
         tw[e] = (r == c) ? 1.0 : 0.0;
       }
     }
-    if (a.stats && tid < 3) a.stats[3 * col + tid] = 0.0;
+    if (a.stats && tid < 3) a.stats[3 * (grp * a.npts + col) + tid] = 0.0;
     return;
   }
 
@@ -217,7 +252,9 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const LetkfArgs a) {
         double w = 0.0;
         if (en < n) {
           const long k = a.idx[off + en];
-          w = a.wts[(size_t)(off + en) * 16 + cb] / a.dr[2 * k + 1];
+          w = a.wts[(size_t)(off + en) * 16 + cb];
+          if constexpr (SLAB) w = w * Sg[(size_t)k * sp];
+          w = w / a.dr[2 * k + 1];
         }
         wgt[tid] = w;
       }
@@ -271,15 +308,15 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const LetkfArgs a) {
     for (int j = lane; j < M; j += 64) s += (mu_s[j] - (double)(M - 1)) / mu_s[j];
     s = wave_sum(s);
     if (lane == 0) {
-      a.stats[3 * col] = (double)nloc;
-      a.stats[3 * col + 1] = s;
-      a.stats[3 * col + 2] = (double)sweeps;
+      a.stats[3 * (grp * a.npts + col)] = (double)nloc;
+      a.stats[3 * (grp * a.npts + col) + 1] = s;
+      a.stats[3 * (grp * a.npts + col) + 2] = (double)sweeps;
     }
   }
 
   // ---- 3. [T | w], factored ---------------------------------------------------------------------------------------------------
   if (MODE == kLetkfWeights) {
-    double* tw = a.Tw + (size_t)col * M * (M + 1);
+    double* tw = a.Tw + (size_t)(grp * a.npts + col) * M * (M + 1);
     etkf_assemble(M, G, f_s, h_s, tw, (size_t)(M + 1), tw + M, (size_t)(M + 1), tid, nth);
     return;
   }
@@ -291,13 +328,17 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const LetkfArgs a) {
 
   // ---- 4. apply ---------------------------------------------------------------------------------------------------------------
   const int nslots = nth >> 4, slot = tid >> 4, sl = tid & 15;
-  const long nrows = (MODE == kLetkfMembers) ? a.n_lead : 1;
+  const long nrows = (MODE == kLetkfMembers) ? nlead_g : 1;
 #pragma unroll 1
   for (long r0 = 0; r0 < nrows; r0 += kLetkfRows) {
     const int nr = (int)((nrows - r0 < kLetkfRows) ? nrows - r0 : kLetkfRows);
     for (int e = tid; e < nr * M; e += nth) {
       const int r = e / M, m = e - r * M;
-      if (MODE == kLetkfMembers) x_s[e] = (double)static_cast<const E*>(a.Xin)[(size_t)((r0 + r) * a.npts + col) * M + m];
+      if (MODE == kLetkfMembers) {
+        long l = r0 + r;
+        if constexpr (SLAB) l = leads[l];
+        x_s[e] = (double)static_cast<const E*>(a.Xin)[(size_t)(l * a.npts + col) * M + m];
+      }
       else x_s[e] = a.Yp_in[(size_t)col * M + m];
     }
     __syncthreads();
@@ -355,7 +396,9 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const LetkfArgs a) {
       const double* pa = x_s + wave * M;
       const double xam = xam_s[wave];
       if (MODE == kLetkfMembers) {
-        E* out = static_cast<E*>(a.Xout) + (size_t)((r0 + wave) * a.npts + col) * M;
+        long l = r0 + wave;
+        if constexpr (SLAB) l = leads[l];
+        E* out = static_cast<E*>(a.Xout) + (size_t)(l * a.npts + col) * M;
         if (rtps) {  // the posterior members' own mean and spread, as the standalone pass takes them (§7b)
           double s = 0.0;
           for (int m = lane; m < M; m += 64) s += pa[m];
@@ -406,6 +449,54 @@ hipError_t letkf_launch_mode(const LetkfArgs& a, hipStream_t s) {
   return letkf_launch_as<MODE, E, 1024>(a, nth, lds, s);
 }
 
+template <int MODE, typename E, int NTMAX>
+hipError_t letkf_slab_launch_as(const LetkfSlabArgs& a, int nth, size_t lds, hipStream_t s) {
+  auto kern = k_letkf<MODE, E, NTMAX, true>;
+  if (lds > 48 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  const long nblk = (a.npts + 15) / 16;
+  hipLaunchKernelGGL(kern, dim3((unsigned)(nblk * 16 * a.grp.ngroups)), dim3((unsigned)nth), lds, s, a);
+  return hipGetLastError();
+}
+
+template <int MODE, typename E>
+hipError_t letkf_slab_launch_mode(const LetkfSlabArgs& a, hipStream_t s) {
+  const int nth = letkf_threads(a.M);
+  const size_t lds = letkf_lds_bytes(a.M);
+  if (nth <= 256) return letkf_slab_launch_as<MODE, E, 256>(a, nth, lds, s);
+  if (nth <= 512) return letkf_slab_launch_as<MODE, E, 512>(a, nth, lds, s);
+  return letkf_slab_launch_as<MODE, E, 1024>(a, nth, lds, s);
+}
+
+// The obs block under the obs-obs factors: the lists built at the ob positions take F(j, k) of §7t, the factors
+// of k_obs_taper_vert / k_obs_taper_slab by the same device functions, F = (V T) C rounded in that order, then one product with the
+// horizontal taper.  One workgroup per block of 16 ob positions.
+__global__ __launch_bounds__(256) void k_letkf_obs_factor(long P, const long* __restrict__ off, const int* __restrict__ cnt,
+                                                          const int* __restrict__ idx, double* __restrict__ wts,
+                                                          const double* __restrict__ ob_vert, const double* __restrict__ ob_vhw,
+                                                          const bool has_slab, const SlabObs o) {
+  const long blk = (long)blockIdx.x;
+  const long base = off[blk];
+  const int n = cnt[blk];
+  for (int i = (int)threadIdx.x; i < n * 16; i += (int)blockDim.x) {
+    const int e = i >> 4, cb = i & 15;
+    const long j = blk * 16 + cb;
+    if (j >= P) continue;
+    double* p = wts + (size_t)(base + e) * 16 + cb;
+    const double w = *p;
+    if (w == 0.0) continue;  // a zero stays zero, whatever the factors hold
+    const long k = idx[base + e];
+    double f = ob_vert ? vert_factor(ob_vert[j], ob_vert[k], ob_vhw[k]) : 1.0;
+    if (has_slab) {
+      f = f * time_factor(o.ob_time[j], o.ob_time[k], o.ob_thw[k]);
+      f = f * impact_factor(o, k, o.ob_var[j]);
+    }
+    *p = w * f;
+  }
+}
+
 }  // namespace
 
 // The workgroup size, from M: the eigen-solve (where a column spends its time) plays ceil(M/2) column pairs per round on 16 lanes
@@ -449,6 +540,35 @@ hipError_t launch_letkf(const LetkfArgs& a, int mode, Elem elem, hipStream_t s) 
   return hipErrorInvalidValue;
 }
 
+hipError_t launch_letkf_slab(const LetkfSlabArgs& a, int mode, Elem elem, hipStream_t s) {
+  const LetkfGroups& g = a.grp;
+  if (a.M < 2 || a.M > kLetkfMaxM || a.npts < 0) return hipErrorInvalidValue;
+  const int T = letkf_tiles_side(a.M);
+  if (kLetkfTiles * (letkf_threads(a.M) / 64) < T * (T + 1) / 2 || letkf_lds_bytes(a.M) > 160 * 1024) return hipErrorInvalidValue;
+  if (g.ngroups < 1 || !g.rep || !g.grp_off || !g.grp_leads || g.s_pitch < 1) return hipErrorInvalidValue;
+  if (a.idx && !g.S) return hipErrorInvalidValue;  // (no lists: the table is never read)
+  if (a.npts == 0) return hipSuccess;
+  if ((a.npts + 15) / 16 * 16 > 0x7FFFFFF0L / g.ngroups) return hipErrorInvalidValue;
+  if (mode == kLetkfMembers) {
+    if (!a.Xin || !a.Xout || a.n_lead < 1) return hipErrorInvalidValue;
+    return elem == Elem::f32 ? letkf_slab_launch_mode<kLetkfMembers, float>(a, s) : letkf_slab_launch_mode<kLetkfMembers, double>(a, s);
+  }
+  if (elem != Elem::f64 || mode != kLetkfWeights || !a.Tw) return hipErrorInvalidValue;
+  return letkf_slab_launch_mode<kLetkfWeights, double>(a, s);
+}
+
+hipError_t launch_letkf_obs_factor(long P, const long* off, const int* cnt, const int* idx, double* wts, const double* ob_vert,
+                                   const double* ob_vhw, const SlabObs* slab, hipStream_t s) {
+  if (P <= 0) return hipSuccess;
+  if (!off || !cnt || !idx || !wts || (ob_vert && !ob_vhw)) return hipErrorInvalidValue;
+  if (!ob_vert && !slab) return hipSuccess;
+  const long nblk = (P + 15) / 16;
+  if (nblk > 0x7FFFFFF0L) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_letkf_obs_factor, dim3((unsigned)nblk), dim3(256), 0, s, P, off, cnt, idx, wts, ob_vert, ob_vhw, slab != nullptr,
+                     slab ? *slab : SlabObs{});
+  return hipGetLastError();
+}
+
 hipError_t launch_letkf_prior(long P, int M, const double* Yp, const double* ym, const double* ob_value, const double* ob_error,
                               const double* ob_req, double t2, double* prior_mean, double* prior_var, uint8_t* assimilated, double* act,
                               double* dr, hipStream_t s) {
@@ -486,7 +606,8 @@ struct LetkfLists {
 };
 
 // What no LETKF call serves, refused before anything is launched (include/efa_hip.h gives the reasons)
-int letkf_check_settings(const efa_ctx* c, const char* who, int M, long P) {
+// slab: the calls of DESIGN.md §7y-3, which need the vertical and/or the slab setting, sized for this call (n_lead < 0: not checked)
+int letkf_check_settings(const efa_ctx* c, const char* who, int M, long P, bool slab = false, long n_lead = -1) {
   if (M < 2) return fail(EFA_ERR_INVALID, "%s: ensemble size M=%d must be >= 2", who, M);
   if (M > kLetkfMaxM)
     return fail(EFA_ERR_INVALID, "%s: M=%d exceeds %d members, the range in which the eigen-solve's M x M array of a column fits in LDS",
@@ -495,11 +616,23 @@ int letkf_check_settings(const efa_ctx* c, const char* who, int M, long P) {
   if (c->ai_field)
     return fail(EFA_ERR_INVALID, "%s: an adaptive-inflation field is set (its update follows the serial order of the obs, which a "
                 "column's batch solve does not have)", who);
-  if (c->vl_on)
-    return fail(EFA_ERR_INVALID, "%s: vertical localisation is set (it needs a solve per (slab group, column): out of scope)", who);
-  if (c->sl_on)
+  if (!slab && c->vl_on)
+    return fail(EFA_ERR_INVALID, "%s: vertical localisation is set (it needs a solve per (slab group, column): out of scope here, "
+                "use efa_letkf_slab_cycle_dev / SlabLETKF)", who);
+  if (!slab && c->sl_on)
     return fail(EFA_ERR_INVALID, "%s: slab (temporal / cross-variable) localisation is set (it needs a solve per (slab group, column): "
-                "out of scope)", who);
+                "out of scope here, use efa_letkf_slab_cycle_dev / SlabLETKF)", who);
+  if (slab) {
+    if (!c->vl_on && !c->sl_on)
+      return fail(EFA_ERR_INVALID, "%s: neither vertical nor slab (temporal / cross-variable) localisation is set: use the plain call "
+                  "(efa_letkf_cycle_dev and its kin)", who);
+    if (c->vl_on && (c->vl_P != P || (n_lead >= 0 && c->vl_nlead != n_lead)))
+      return fail(EFA_ERR_INVALID, "%s: vertical localisation was set for %ld observations and %ld slabs, the call has %ld and n_lead=%ld",
+                  who, c->vl_P, c->vl_nlead, P, n_lead);
+    if (c->sl_on && (c->sl_P != P || (n_lead >= 0 && c->sl_nlead != n_lead)))
+      return fail(EFA_ERR_INVALID, "%s: slab localisation was set for %ld observations and %ld slabs, the call has %ld and n_lead=%ld", who,
+                  c->sl_P, c->sl_nlead, P, n_lead);
+  }
   if (sec_active(c))
     return fail(EFA_ERR_INVALID, "%s: a sampling-error-correction table is set (it acts on the serial gain of one observation at a time)",
                 who);
@@ -662,8 +795,8 @@ int letkf_check_rows(const char* who, const StateRows& r, long ncol, long n_lead
 
 // the interpolate-and-apply launch of the cycle and of efa_letkf_interp_apply_dev, under the context's relaxation; does not wait
 int letkf_interp_launch(efa_ctx* c, const char* who, Elem elem, int M, const void* X_dev, void* post_dev, const LetkfMesh& nodes,
-                        long n_lead, const double* Tw, const double* stats) {
-  LetkfInterpArgs a{};
+                        long n_lead, const double* Tw, const double* stats, const LetkfGroups* grp = nullptr) {
+  LetkfInterpSlabArgs a{};
   a.mesh = nodes;
   a.n_lead = n_lead;
   a.M = M;
@@ -673,7 +806,106 @@ int letkf_interp_launch(efa_ctx* c, const char* who, Elem elem, int M, const voi
   a.stats = stats;
   a.relax_kind = c->relax_kind;
   a.relax_alpha = c->relax_alpha;
-  EFA_HIP(launch_letkf_interp(a, elem, c->stream));
+  if (grp) {
+    a.ngroups = grp->ngroups;
+    a.grp_off = grp->grp_off;
+    a.grp_leads = grp->grp_leads;
+    EFA_HIP(launch_letkf_interp_slab(a, elem, c->stream));
+    return EFA_OK;
+  }
+  EFA_HIP(launch_letkf_interp(static_cast<const LetkfInterpArgs&>(a), elem, c->stream));
+  return EFA_OK;
+}
+
+// ---- the slab groups --------------------------------------------------------------------------------------------
+// Slabs whose factors agree for every ob share one solve.  Decided here from the host copies of the two settings, without the
+// table: the key of slab s is the bit pattern of lead_vert[s], lead_time[s] and lead_var[s], each only while that part can give a
+// factor other than 1 (some ob carries vertical information; some ob has a time and a temporal half-width; some ob's impact row
+// has an entry other than 1).  Equal keys imply equal columns of S.  Groups are numbered by first appearance; cached on the
+// settings' serials, the device copy uploaded once per change.
+uint64_t letkf_key_bits(double v) {
+  if (v != v) return ~(uint64_t)0;  // every NaN is "no coordinate"
+  uint64_t b;
+  std::memcpy(&b, &v, sizeof b);
+  return b;
+}
+
+int letkf_groups(efa_ctx* c, long n_lead) {
+  if (c->lg_vl_serial == c->vl_serial && c->lg_sl_serial == c->sl_serial && (long)c->lg_group_of.size() == n_lead &&
+      c->lg_ptr == c->lg_dev.p && c->lg_dev.p)
+    return EFA_OK;
+  const bool vert = vl_active(c);
+  bool temporal = false, variable = false;
+  const double* lt = nullptr;
+  const int* lvar = nullptr;
+  if (c->sl_on) {
+    const long P = c->sl_P, nv = c->sl_nvar, ng = c->sl_ngroup;
+    const double* d = c->sl_host.data();
+    const int* iv = reinterpret_cast<const int*>(d + c->sl_nlead + 2 * P + ng * nv);
+    lt = d;
+    lvar = iv;
+    for (long k = 0; k < P && !temporal; ++k) temporal = d[c->sl_nlead + k] == d[c->sl_nlead + k] && d[c->sl_nlead + P + k] == d[c->sl_nlead + P + k];
+    for (long k = 0; k < P && !variable; ++k) {
+      const int g = iv[c->sl_nlead + k];
+      if (g < 0) continue;
+      for (long u = 0; u < nv && !variable; ++u) variable = d[c->sl_nlead + 2 * P + g * nv + u] != 1.0;
+    }
+  }
+  std::map<std::tuple<uint64_t, uint64_t, int>, int> seen;
+  std::vector<int> group_of((size_t)n_lead), rep;
+  for (long sidx = 0; sidx < n_lead; ++sidx) {
+    const auto key = std::make_tuple(vert ? letkf_key_bits(c->vl_host[sidx]) : (uint64_t)0, temporal ? letkf_key_bits(lt[sidx]) : (uint64_t)0,
+                                     variable ? lvar[sidx] : 0);
+    auto it = seen.find(key);
+    if (it == seen.end()) {
+      it = seen.emplace(key, (int)rep.size()).first;
+      rep.push_back((int)sidx);
+    }
+    group_of[sidx] = it->second;
+  }
+  const int ng = (int)rep.size();
+  std::vector<int> h((size_t)(2 * ng + 1 + n_lead));  // rep | grp_off | grp_leads
+  std::vector<int> count((size_t)ng, 0);
+  for (long sidx = 0; sidx < n_lead; ++sidx) count[group_of[sidx]]++;
+  for (int g = 0; g < ng; ++g) {
+    h[g] = rep[g];
+    h[ng + g + 1] = h[ng + g] + count[g];
+  }
+  std::vector<int> fill((size_t)ng, 0);
+  for (long sidx = 0; sidx < n_lead; ++sidx) {
+    const int g = group_of[sidx];
+    h[2 * ng + 1 + h[ng + g] + fill[g]++] = (int)sidx;
+  }
+  EFA_TRY(c->lg_dev.reserve(h.size() * sizeof(int)));
+  EFA_HIP(hipMemcpyAsync(c->lg_dev.p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  EFA_HIP(hipStreamSynchronize(c->stream));  // (h goes out of scope)
+  c->lg_group_of.swap(group_of);
+  c->lg_ngroups = ng;
+  c->lg_vl_serial = c->vl_serial;
+  c->lg_sl_serial = c->sl_serial;
+  c->lg_ptr = c->lg_dev.p;
+  return EFA_OK;
+}
+
+// the table and the groups of a slab call, as the kernels take them (the settings were checked for this P and n_lead)
+int letkf_slab_groups(efa_ctx* c, long n_lead, LetkfGroups* out) {
+  EFA_TRY(ensure_slab_table(c));
+  EFA_TRY(letkf_groups(c, n_lead));
+  const int* d = c->lg_dev.as<int>();
+  const int ng = c->lg_ngroups;
+  *out = LetkfGroups{ng, n_lead, c->sl_tab.as<double>(), d, d + ng, d + 2 * ng + 1};
+  return EFA_OK;
+}
+
+// the node solve of the slab calls: [T | w] of every (group, point) to Tw, the statistics [group][point][3]; does not wait
+int letkf_solve_points_slab(efa_ctx* c, int M, long npts, const LetkfLists& lists, const double* Yp_dev, const LetkfObs& o,
+                            const LetkfGroups& grp, double* Tw, double* stats) {
+  LetkfSlabArgs a{};
+  static_cast<LetkfArgs&>(a) = letkf_args(M, npts, lists, Yp_dev, o);
+  a.grp = grp;
+  a.Tw = Tw;
+  a.stats = stats;
+  EFA_HIP(launch_letkf_slab(a, kLetkfWeights, Elem::f64, c->stream));
   return EFA_OK;
 }
 
@@ -683,11 +915,13 @@ int letkf_cycle(efa_ctx* c, Elem elem, long rows, int M, long P, const void* X_d
                 int obs_block_out, const double* ob_value, const double* ob_error, const uint8_t* ob_assim, const double* ob_lat,
                 const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
                 double* prior_mean, double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated, double* col_stats_dev,
-                const LetkfMesh* mesh) {
+                const LetkfMesh* mesh, bool slab) {
   const bool f32 = elem == Elem::f32;
-  const char* who = mesh ? (f32 ? "efa_letkf_cycle_interp_f32_dev" : "efa_letkf_cycle_interp_dev")
-                         : (f32 ? "efa_letkf_cycle_f32_dev" : "efa_letkf_cycle_dev");
-  EFA_TRY(letkf_check_settings(c, who, M, P));
+  const char* who = slab ? (mesh ? (f32 ? "efa_letkf_slab_cycle_interp_f32_dev" : "efa_letkf_slab_cycle_interp_dev")
+                                 : (f32 ? "efa_letkf_slab_cycle_f32_dev" : "efa_letkf_slab_cycle_dev"))
+                         : (mesh ? (f32 ? "efa_letkf_cycle_interp_f32_dev" : "efa_letkf_cycle_interp_dev")
+                                 : (f32 ? "efa_letkf_cycle_f32_dev" : "efa_letkf_cycle_dev"));
+  EFA_TRY(letkf_check_settings(c, who, M, P, slab, n_lead));
   LetkfMesh nodes{};
   if (mesh) {
     EFA_TRY(letkf_check_mesh(who, *mesh, &nodes));
@@ -711,7 +945,7 @@ int letkf_cycle(efa_ctx* c, Elem elem, long rows, int M, long P, const void* X_d
   harvest_state_ms(c);
   c->obs_ms = c->state_ms = 0.0;
   c->state_launches = 0;
-  c->phase_a_kind = mesh ? 7 : 6;
+  c->phase_a_kind = slab ? (mesh ? 9 : 8) : (mesh ? 7 : 6);
   c->path_taken = EFA_PATH_TRANSFORM;
   if (c->timing) EFA_HIP(hipEventRecord(c->obs_iv.begin, s));
 
@@ -725,6 +959,12 @@ int letkf_cycle(efa_ctx* c, Elem elem, long rows, int M, long P, const void* X_d
     Yw = c->letkf_Yw.as<double>();
     ymw = Yw + (size_t)P * M;
     EFA_TRY(letkf_build_lists(c, P, o.lat, o.lon, o, &lists));
+    if (slab) {  // the obs-obs factors F(j, k) into the lists' tapers; the perturbation-form launch then runs as it is, one group
+      const bool vert = vl_active(c);
+      const SlabObs so = sl_active(c) ? sl_obs(c, 0) : SlabObs{};
+      EFA_HIP(launch_letkf_obs_factor(P, lists.off, lists.cnt, lists.idx, c->letkf_wts.as<double>(), vert ? vl_obvert(c) : nullptr,
+                                      vert ? vl_obvhw(c) : nullptr, sl_active(c) ? &so : nullptr, s));
+    }
     LetkfArgs a = letkf_args(M, P, lists, Yp_dev, o);
     a.ym_in = ym_dev;
     a.Yp_in = Yp_dev;
@@ -738,10 +978,15 @@ int letkf_cycle(efa_ctx* c, Elem elem, long rows, int M, long P, const void* X_d
   LetkfLists glists;
   const long nnodes = mesh ? nodes.nnodes() : 0;
   double* node_stats = col_stats_dev;
+  LetkfGroups grp{};
+  if (rows > 0 && slab) EFA_TRY(letkf_slab_groups(c, n_lead, &grp));
+  const size_t ngr = slab ? (size_t)grp.ngroups : 1;  // solves per column or node
   if (rows > 0 && mesh) {
-    EFA_TRY(c->letkf_Tw.reserve((size_t)nnodes * M * (M + 1) * sizeof(double)));
+    if (c->letkf_Tw.reserve(ngr * (size_t)nnodes * M * (M + 1) * sizeof(double)) != EFA_OK)
+      return fail(EFA_ERR_ALLOC, "%s: the node-pair buffer of %zu groups x %ld nodes x %d x %d doubles could not be allocated", who, ngr,
+                  nnodes, M, M + 1);
     if (!node_stats) {  // the apply reads n_local of every node
-      EFA_TRY(c->letkf_nst.reserve(3 * (size_t)nnodes * sizeof(double)));
+      EFA_TRY(c->letkf_nst.reserve(3 * ngr * (size_t)nnodes * sizeof(double)));
       node_stats = c->letkf_nst.as<double>();
     }
   }
@@ -769,7 +1014,23 @@ int letkf_cycle(efa_ctx* c, Elem elem, long rows, int M, long P, const void* X_d
     c->obs_iv.pending = true;
     EFA_HIP(hipEventRecord(c->state_iv[0].begin, s));
   }
-  if (rows > 0 && mesh) {  // (P == 0: no lists, every node has the pair (I, 0) and no column changes)
+  if (rows > 0 && mesh && slab) {
+    EFA_TRY(letkf_solve_points_slab(c, M, nnodes, glists, Yp_dev, o, grp, c->letkf_Tw.as<double>(), node_stats));
+    EFA_TRY(letkf_interp_launch(c, who, elem, M, X_dev, post_dev, nodes, n_lead, c->letkf_Tw.as<double>(), node_stats, &grp));
+    c->state_launches = 2;
+  } else if (rows > 0 && slab) {
+    LetkfSlabArgs a{};
+    static_cast<LetkfArgs&>(a) = letkf_args(M, ncol, glists, Yp_dev, o);
+    a.grp = grp;
+    a.n_lead = n_lead;
+    a.Xin = X_dev;
+    a.Xout = post_dev;
+    a.stats = col_stats_dev;
+    a.relax_kind = c->relax_kind;
+    a.relax_alpha = c->relax_alpha;
+    EFA_HIP(launch_letkf_slab(a, kLetkfMembers, elem, s));
+    c->state_launches = 1;
+  } else if (rows > 0 && mesh) {  // (P == 0: no lists, every node has the pair (I, 0) and no column changes)
     EFA_TRY(letkf_solve_points(c, M, nnodes, glists, Yp_dev, o, c->letkf_Tw.as<double>(), node_stats));
     EFA_TRY(letkf_interp_launch(c, who, elem, M, X_dev, post_dev, nodes, n_lead, c->letkf_Tw.as<double>(), node_stats));
     c->state_launches = 2;
@@ -824,9 +1085,10 @@ int letkf_cycle(efa_ctx* c, Elem elem, long rows, int M, long P, const void* X_d
 
 int letkf_weights(efa_ctx* c, int M, long P, const double* ym_dev, const double* Yp_dev, const double* ob_value, const double* ob_error,
                   const uint8_t* ob_assim, const double* ob_lat, const double* ob_lon, const double* ob_hw, long npts,
-                  const double* pt_lat, const double* pt_lon, double* Tw_dev, double* stats_dev) {
-  const char* who = "efa_letkf_weights_dev";
-  EFA_TRY(letkf_check_settings(c, who, M, P));
+                  const double* pt_lat, const double* pt_lon, double* Tw_dev, double* stats_dev, bool slab) {
+  const char* who = slab ? "efa_letkf_slab_weights_dev" : "efa_letkf_weights_dev";
+  const long n_lead = c->sl_on ? c->sl_nlead : c->vl_nlead;  // (slab: the slabs are the settings' own)
+  EFA_TRY(letkf_check_settings(c, who, M, P, slab, slab ? n_lead : -1));
   if (npts < 0) return fail(EFA_ERR_INVALID, "%s: negative point count", who);
   if (npts > 0 && (!pt_lat || !pt_lon || !Tw_dev)) return fail(EFA_ERR_INVALID, "%s: null point or output array", who);
   EFA_TRY(letkf_check_obs(who, P, ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_hw));
@@ -840,8 +1102,27 @@ int letkf_weights(efa_ctx* c, int M, long P, const double* ym_dev, const double*
     EFA_TRY(letkf_upload_points(c, npts, pt_lat, pt_lon, &dlat, &dlon));
     EFA_TRY(letkf_build_lists(c, npts, dlat, dlon, o, &lists));
   }
-  EFA_TRY(letkf_solve_points(c, M, npts, lists, Yp_dev, o, Tw_dev, stats_dev));
+  if (slab) {
+    LetkfGroups grp{};
+    EFA_TRY(letkf_slab_groups(c, n_lead, &grp));
+    EFA_TRY(letkf_solve_points_slab(c, M, npts, lists, Yp_dev, o, grp, Tw_dev, stats_dev));
+  } else {
+    EFA_TRY(letkf_solve_points(c, M, npts, lists, Yp_dev, o, Tw_dev, stats_dev));
+  }
   EFA_HIP(hipStreamSynchronize(s));
+  return EFA_OK;
+}
+
+int letkf_slab_group_table(efa_ctx* c, long n_lead, int* group_of, int* ngroups) {
+  const char* who = "efa_letkf_slab_groups";
+  if (!c->vl_on && !c->sl_on) return fail(EFA_ERR_INVALID, "%s: neither vertical nor slab localisation is set", who);
+  if ((c->vl_on && c->vl_nlead != n_lead) || (c->sl_on && c->sl_nlead != n_lead))
+    return fail(EFA_ERR_INVALID, "%s: the settings are not sized for n_lead=%ld", who, n_lead);
+  if (c->vl_on && c->sl_on && c->vl_P != c->sl_P)
+    return fail(EFA_ERR_INVALID, "%s: the vertical and the slab setting are sized for %ld and %ld observations", who, c->vl_P, c->sl_P);
+  EFA_TRY(letkf_groups(c, n_lead));
+  if (group_of) std::memcpy(group_of, c->lg_group_of.data(), (size_t)n_lead * sizeof(int));
+  if (ngroups) *ngroups = c->lg_ngroups;
   return EFA_OK;
 }
 

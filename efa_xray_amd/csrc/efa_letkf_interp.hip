@@ -71,11 +71,13 @@ constexpr int interp_waves(int KMAX) { return KMAX <= 16 ? 3 : 1; }
 
 // 16 rows of a column into registers: lane (g, nn) takes members 8q + 2g, 8q + 2g + 1 of row `first + nn` as k-steps 2q, 2q + 1;
 // exact zeros past M and past the last row
+// (leads: the slab of each of the n_lead rows, the SLAB kernel's group list; null: row i is slab i)
 template <typename E, int KMAX>
 __device__ __forceinline__ void interp_load_rows(const E* in, long first, long n_lead, long ncol, long col, int M, int g, int nn,
-                                                 double (&x)[KMAX]) {
-  const long l = first + nn;
+                                                 double (&x)[KMAX], const int* leads = nullptr) {
+  long l = first + nn;
   const bool rowok = l < n_lead;
+  if (leads && rowok) l = leads[l];
   const E* xin = in + (size_t)((rowok ? l : 0) * ncol + col) * M;
 #pragma unroll
   for (int q = 0; q < KMAX / 2; ++q) {
@@ -88,8 +90,15 @@ __device__ __forceinline__ void interp_load_rows(const E* in, long first, long n
   }
 }
 
-template <typename E, int KMAX, int NT>
-__global__ __launch_bounds__(NT, interp_waves(KMAX)) void k_letkf_interp(const LetkfInterpArgs a) {
+// SLAB: one workgroup per (column, slab group), the group the fastest index; node pairs from Tw[group][node], node
+// statistics from [group][node], a wave's 16 rows gathered from the group's slab list.
+template <bool SLAB>
+struct InterpArgsOf { typedef LetkfInterpArgs type; };
+template <>
+struct InterpArgsOf<true> { typedef LetkfInterpSlabArgs type; };
+
+template <typename E, int KMAX, int NT, bool SLAB = false>
+__global__ __launch_bounds__(NT, interp_waves(KMAX)) void k_letkf_interp(const typename InterpArgsOf<SLAB>::type a) {
   extern __shared__ __align__(16) double interp_smem[];
   static_assert(KMAX % 2 == 0, "k-steps come in pairs");
   constexpr int TMAX = (4 * KMAX + 1 + 15) / 16;
@@ -97,13 +106,28 @@ __global__ __launch_bounds__(NT, interp_waves(KMAX)) void k_letkf_interp(const L
   const int K = 2 * ((M + 7) >> 3), T = (Mp + 15) >> 4;
   const int tid = (int)threadIdx.x, lane = tid & 63, g = lane >> 4, nn = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const long ncol = a.mesh.ncol(), col = (long)blockIdx.x;
+  unsigned bidx = (unsigned)blockIdx.x;
+  long nrows = a.n_lead;             // the rows this workgroup maps: the column's, or the group's
+  const int* leads = nullptr;        // ... and their slabs
+  const double* Tw_g = a.Tw;
+  const double* stats_g = a.stats;
+  if constexpr (SLAB) {
+    const unsigned grp = bidx % (unsigned)a.ngroups;
+    bidx = bidx / (unsigned)a.ngroups;
+    const int o0 = a.grp_off[grp];
+    nrows = a.grp_off[grp + 1] - o0;
+    leads = a.grp_leads + o0;
+    const size_t nn_ = (size_t)a.mesh.nnodes();
+    Tw_g = a.Tw + (size_t)grp * nn_ * (size_t)M * Mp;
+    if (a.stats) stats_g = a.stats + 3 * (size_t)grp * nn_;
+  }
+  const long ncol = a.mesh.ncol(), col = (long)bidx;
   const E* in = static_cast<const E*>(a.Xin);
   E* out = static_cast<E*>(a.Xout);
   double* Tw_s = interp_smem;  // [M][M + 1]
 
   // ---- 1. the cell (every thread computes the same scalars) --------------------------------------------------------------------
-  const unsigned nx = (unsigned)a.mesh.nx, iy = (unsigned)blockIdx.x / nx, ix = (unsigned)blockIdx.x - iy * nx;
+  const unsigned nx = (unsigned)a.mesh.nx, iy = bidx / nx, ix = bidx - iy * nx;
   unsigned jy, jx;
   double ty, tx;
   interp_axis(iy, (unsigned)a.mesh.ny, (unsigned)a.mesh.sy, &jy, &ty);
@@ -119,14 +143,16 @@ __global__ __launch_bounds__(NT, interp_waves(KMAX)) void k_letkf_interp(const L
       if (beta[n] != 0.0) used = node[n];
     double nl[4];
 #pragma unroll
-    for (int n = 0; n < 4; ++n) nl[n] = a.stats[3 * (beta[n] != 0.0 ? node[n] : used)];
+    for (int n = 0; n < 4; ++n) nl[n] = stats_g[3 * (beta[n] != 0.0 ? node[n] : used)];
 #pragma unroll
     for (int n = 0; n < 4; ++n)
       if (nl[n] != 0.0) reached = true;
   }
   if (!reached) {  // (uniform) T_c = I, w_c = 0: the rows keep their bits
     if (in != out)
-      for (long l = 0; l < a.n_lead; ++l) {
+      for (long li = 0; li < nrows; ++li) {
+        long l = li;
+        if constexpr (SLAB) l = leads[li];
         const size_t base = (size_t)(l * ncol + col) * M;
         for (int m = tid; m < M; m += NT) out[base + m] = in[base + m];
       }
@@ -134,9 +160,10 @@ __global__ __launch_bounds__(NT, interp_waves(KMAX)) void k_letkf_interp(const L
   }
 
   // the first 16 rows of every wave are on their way while [T_c | w_c] is formed
-  const long ntiles = (a.n_lead + 15) >> 4;
+  const long ntiles = (nrows + 15) >> 4;
   double x[KMAX];
-  interp_load_rows<E, KMAX>(in, 16 * (long)wave, a.n_lead, ncol, col, M, g, nn, x);
+  if constexpr (SLAB) interp_load_rows<E, KMAX>(in, 16 * (long)wave, nrows, ncol, col, M, g, nn, x, leads);
+  else interp_load_rows<E, KMAX>(in, 16 * (long)wave, a.n_lead, ncol, col, M, g, nn, x);
 
   // ---- 2. [T_c | w_c] in LDS, two elements per lane and step -----------------------------------------------------------------------
   {
@@ -150,7 +177,7 @@ __global__ __launch_bounds__(NT, interp_waves(KMAX)) void k_letkf_interp(const L
 #pragma unroll
       for (int n = 0; n < 4; ++n)
         if (beta[n] != 0.0) {  // (uniform)
-          const interp_v2 v = beta[n] * interp_load2(a.Tw + (size_t)node[n] * pair + 2 * e);
+          const interp_v2 v = beta[n] * interp_load2(Tw_g + (size_t)node[n] * pair + 2 * e);
           acc = first ? v : acc + v;
           first = false;
         }
@@ -252,8 +279,9 @@ __global__ __launch_bounds__(NT, interp_waves(KMAX)) void k_letkf_interp(const L
     }
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
-      const long l = tile * 16 + g + 4 * v;
-      if (l < a.n_lead) {
+      long l = tile * 16 + g + 4 * v;
+      if (l < nrows) {
+        if constexpr (SLAB) l = leads[l];
         E* xo = out + (size_t)(l * ncol + col) * M;
 #pragma unroll
         for (int t = 0; t < TMAX; ++t) {
@@ -265,8 +293,10 @@ __global__ __launch_bounds__(NT, interp_waves(KMAX)) void k_letkf_interp(const L
         }
       }
     }
-    if (tile + NT / 64 < ntiles)  // (uniform) the wave's next 16 rows
-      interp_load_rows<E, KMAX>(in, 16 * (tile + NT / 64), a.n_lead, ncol, col, M, g, nn, x);
+    if (tile + NT / 64 < ntiles) {  // (uniform) the wave's next 16 rows
+      if constexpr (SLAB) interp_load_rows<E, KMAX>(in, 16 * (tile + NT / 64), nrows, ncol, col, M, g, nn, x, leads);
+      else interp_load_rows<E, KMAX>(in, 16 * (tile + NT / 64), a.n_lead, ncol, col, M, g, nn, x);
+    }
   }
 }
 
@@ -289,6 +319,25 @@ hipError_t interp_launch(const LetkfInterpArgs& a, hipStream_t s) {
   return interp_launch_as<E, 34, 256>(a, lds, s);
 }
 
+template <typename E, int KMAX, int NT>
+hipError_t interp_slab_launch_as(const LetkfInterpSlabArgs& a, size_t lds, hipStream_t s) {
+  auto kern = k_letkf_interp<E, KMAX, NT, true>;
+  if (lds > 48 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3((unsigned)(a.mesh.ncol() * a.ngroups)), dim3(NT), lds, s, a);
+  return hipGetLastError();
+}
+
+template <typename E>
+hipError_t interp_slab_launch(const LetkfInterpSlabArgs& a, hipStream_t s) {
+  const size_t lds = letkf_interp_lds_bytes(a.M);
+  if (a.M <= 32) return interp_slab_launch_as<E, 8, 128>(a, lds, s);
+  if (a.M <= 64) return interp_slab_launch_as<E, 16, 128>(a, lds, s);
+  return interp_slab_launch_as<E, 34, 256>(a, lds, s);
+}
+
 }  // namespace
 
 size_t letkf_interp_lds_bytes(int M) { return (size_t)M * (M + 1) * sizeof(double); }
@@ -300,6 +349,17 @@ hipError_t launch_letkf_interp(const LetkfInterpArgs& a, Elem elem, hipStream_t 
   if (m.sy > (m.ny > 2 ? m.ny - 1 : 1) || m.sx > (m.nx > 2 ? m.nx - 1 : 1)) return hipErrorInvalidValue;
   if (!a.Xin || !a.Xout || !a.Tw || a.n_lead < 1) return hipErrorInvalidValue;
   return elem == Elem::f32 ? interp_launch<float>(a, s) : interp_launch<double>(a, s);
+}
+
+hipError_t launch_letkf_interp_slab(const LetkfInterpSlabArgs& a, Elem elem, hipStream_t s) {
+  const LetkfMesh& m = a.mesh;
+  if (a.M < 2 || a.M > kLetkfMaxM || letkf_interp_lds_bytes(a.M) > 160 * 1024) return hipErrorInvalidValue;
+  if (a.ngroups < 1 || !a.grp_off || !a.grp_leads) return hipErrorInvalidValue;
+  if (m.ny < 1 || m.nx < 1 || m.sy < 1 || m.sx < 1 || m.ny > 0x7FFFFFF0L / m.nx || m.ny * m.nx > 0x7FFFFFF0L / a.ngroups)
+    return hipErrorInvalidValue;
+  if (m.sy > (m.ny > 2 ? m.ny - 1 : 1) || m.sx > (m.nx > 2 ? m.nx - 1 : 1)) return hipErrorInvalidValue;
+  if (!a.Xin || !a.Xout || !a.Tw || a.n_lead < 1) return hipErrorInvalidValue;
+  return elem == Elem::f32 ? interp_slab_launch<float>(a, s) : interp_slab_launch<double>(a, s);
 }
 
 }  // namespace efa

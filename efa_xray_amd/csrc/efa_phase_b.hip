@@ -109,13 +109,17 @@ int check_batch_solver(const efa_ctx* c, int loc_mode) {
 
 // The table depends on the two settings alone (not on the obs' positions): it is written once per change of either, on the
 // context's stream, in front of the sweep that reads it.
+// Without the slab setting (the LETKF under the vertical setting alone) the table is sized by the vertical setting
+// and holds its factor alone; the slab setting's serial moves whenever it is turned on or off, so the cache tells the two apart.
 int ensure_slab_table(efa_ctx* c) {
-  const long P = c->sl_P, n_lead = c->sl_nlead;
+  const bool slab = c->sl_on;
+  const long P = slab ? c->sl_P : c->vl_P, n_lead = slab ? c->sl_nlead : c->vl_nlead;
   EFA_TRY(c->sl_tab.reserve((size_t)(P * n_lead ? P * n_lead : 1) * sizeof(double)));
   if (c->sl_tab_serial == c->sl_serial && c->sl_tab_vl_serial == c->vl_serial && c->sl_tab_ptr == c->sl_tab.p) return EFA_OK;
   const bool vert = vl_active(c);  // (check_vloc: set for the same P and n_lead)
   EFA_HIP(launch_slab_factor(P, n_lead, vert ? vl_lead(c) : nullptr, vert ? vl_obvert(c) : nullptr, vert ? vl_obvhw(c) : nullptr,
-                             sl_lead_time(c), sl_lead_var(c), sl_obs(c, 0), c->sl_tab.as<double>(), c->stream));
+                             slab ? sl_lead_time(c) : nullptr, slab ? sl_lead_var(c) : nullptr, slab ? sl_obs(c, 0) : efa::SlabObs{},
+                             c->sl_tab.as<double>(), c->stream));
   c->sl_tab_serial = c->sl_serial;
   c->sl_tab_vl_serial = c->vl_serial;
   c->sl_tab_ptr = c->sl_tab.p;

@@ -9,19 +9,10 @@
 // k_obs_taper_rows_slab is k_obs_taper_rows (efa_vloc.hip) with the two factors: the per-batch sweep's table of one batch.
 #include "efa_device.h"
 #include "efa_internal.h"
+#include "efa_slabfactor.h"
 
 namespace efa {
 namespace {
-
-// GC(|t_x - t_k|, tau_k); 1 when row x has no time, or ob k no time or no temporal half-width (NaN)
-__device__ __forceinline__ double time_factor(double t_x, double t_k, double thw_k) {
-  return (t_x == t_x && t_k == t_k && thw_k == thw_k) ? gaspari_cohn(fabs(t_x - t_k), thw_k) : 1.0;
-}
-// C[obtype of ob k, variable v]; 1 for an ob without an impact row (group -1) and for a row without a variable (v -1)
-__device__ __forceinline__ double impact_factor(const SlabObs& o, long k, int v) {
-  const int g = o.ob_group[k];
-  return (g >= 0 && v >= 0) ? o.impact[(size_t)g * o.n_var + v] : 1.0;
-}
 
 __global__ __launch_bounds__(256) void k_slab_factor(long P, long n_lead, const double* __restrict__ lead_vert,
                                                      const double* __restrict__ ob_vert, const double* __restrict__ ob_vhw,
@@ -34,6 +25,18 @@ __global__ __launch_bounds__(256) void k_slab_factor(long P, long n_lead, const 
   const double v = lead_vert ? vert_factor(lead_vert[lead], ob_vert[k], ob_vhw[k]) : 1.0;
   const double vt = v * time_factor(lead_time[lead], o.ob_time[k], o.ob_thw[k]);
   S[i] = vt * impact_factor(o, k, lead_var[lead]);
+}
+
+// the table without a slab setting (lead_time null: the LETKF under the vertical setting alone): S = V, or 1 when
+// lead_vert is null as well -- what k_slab_factor writes when T and C are 1, (V * 1) * 1
+__global__ __launch_bounds__(256) void k_slab_factor_vert(long P, long n_lead, const double* __restrict__ lead_vert,
+                                                          const double* __restrict__ ob_vert, const double* __restrict__ ob_vhw,
+                                                          double* __restrict__ S) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= P * n_lead) return;
+  const long k = i / n_lead;
+  const long lead = i - k * n_lead;
+  S[i] = lead_vert ? vert_factor(lead_vert[lead], ob_vert[k], ob_vhw[k]) : 1.0;
 }
 
 __global__ __launch_bounds__(256) void k_obs_taper_slab(long P, long R, const SlabObs o, double* __restrict__ tw) {
@@ -75,6 +78,10 @@ hipError_t launch_slab_factor(long P, long n_lead, const double* lead_vert, cons
   if (P <= 0 || n_lead <= 0) return hipSuccess;
   if (lead_vert && (!ob_vert || !ob_vhw)) return hipErrorInvalidValue;
   const long n = P * n_lead;
+  if (!lead_time) {  // no slab setting: the vertical factor alone (lead_var and o are not read)
+    hipLaunchKernelGGL(k_slab_factor_vert, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, P, n_lead, lead_vert, ob_vert, ob_vhw, S);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(k_slab_factor, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, P, n_lead, lead_vert, ob_vert, ob_vhw, lead_time,
                      lead_var, o, S);
   return hipGetLastError();

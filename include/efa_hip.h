@@ -48,7 +48,8 @@ typedef enum efa_status {
   EFA_ERR_INVALID = -1,    /* bad argument (shape, NULL pointer, option) */
   EFA_ERR_NO_DEVICE = -2,  /* no HIP device / wrong architecture */
   EFA_ERR_HIP = -3,        /* a HIP runtime call failed */
-  EFA_ERR_UNSUPPORTED = -4 /* valid request this build cannot serve */
+  EFA_ERR_UNSUPPORTED = -4, /* valid request this build cannot serve */
+  EFA_ERR_ALLOC = -5        /* a device buffer a call sizes itself could not be allocated (the LETKF's node-pair buffer) */
 } efa_status;
 
 /* localisation modes: `loc` of EnSRF (ensrf.py:28,99) */
@@ -416,6 +417,73 @@ int efa_letkf_interp_apply_dev(efa_ctx *ctx, long rows, int M, const double *X_d
 int efa_letkf_interp_apply_f32_dev(efa_ctx *ctx, long rows, int M, const float *X_dev, float *post_dev, long ny, long nx,
                                    long stride_y, long stride_x, long n_lead, const double *Tw_nodes_dev,
                                    const double *node_stats_dev /* [3*nnodes] or NULL */);
+
+/* ---- vertical, temporal and variable localisation of the LETKF
+ * The calls above map all n_lead rows of a column with one pair.  These solve
+ * once per (slab group, column) under the product taper of 7d / 7t.  Inputs:
+ * those of the call of the same name without "_slab", with the context's
+ * vertical setting (efa_ctx_set_vertical_localization) and / or slab setting
+ * (efa_ctx_set_slab_localization) on, sized for this call's P and n_lead.
+ * S(k, s) is the slab factor (V T) C of ob k on slab s, exactly what
+ * efa_slab_factor_table returns (V included while the vertical setting is on;
+ * under the vertical setting alone S = V).  F(j, k) = (V(j,k) T(j,k)) C[k, v_j] is
+ * the factor of ob k on obs row j, each product rounded once in that order.
+ * For column c and slab s, over the obs with a_k = 1 and rho_k(c, s) != 0:
+ *   rho_k(c, s) = fl(GC_h(c, k) * S(k, s)),  weight_k = fl(rho_k(c, s) / r_k),
+ *   A_{c,s} = (M-1) I + sum_k weight_k Yp_k^T Yp_k,  g_{c,s} = sum_k weight_k d_k Yp_k^T,
+ * and T, w follow as above; row s*ncol + c maps with the pair of (c, s).  Obs
+ * row j maps with the pair solved at ob j's position under fl(GC_h(j,k) F(j,k)).
+ * Slabs whose factors agree for every ob form a GROUP and share one solve.  The
+ * key of slab s is the bit pattern (every NaN alike) of lead_vert[s] while some
+ * ob carries vertical information, lead_time[s] while some ob has a time and a
+ * temporal half-width, and lead_var[s] while some ob's impact row has an entry
+ * other than 1.  Groups are numbered by first appearance;
+ * efa_letkf_slab_groups writes the group of every slab (host, [n_lead]) and
+ * their number.  A (column, group) no ob reaches (n_local = 0: every product is
+ * 0) runs no solve, keeps that group's rows bit for bit and reports (0, 0, 0).
+ * Statistics are laid out [ngroups][ncol][3] (col_stats_dev) or
+ * [ngroups][nnodes][3] (node_stats_dev); efa_letkf_slab_weights_dev writes
+ * Tw_dev [ngroups][npts][M][M+1] and stats_dev [ngroups][npts][3].  The interp
+ * call interpolates per group, node pairs in a buffer of the context of
+ * ngroups * nnodes * M * (M+1) doubles (EFA_ERR_ALLOC if it cannot be had); a
+ * unit stride is the plain slab call.  Diagnostics, relaxation, the outlier
+ * check, float32 rows and every other rule are those of the calls above.  With
+ * every S = 1 the results equal the calls above bit for bit.
+ * Refused with EFA_ERR_INVALID before any launch: neither setting on (use the
+ * plain call); a setting sized for another P or n_lead; and all that the plain
+ * call refuses but the two settings.  "phase_a_kind" reads 8 (9 for the interp
+ * call); efa_last_timing as for the plain calls.  They wait. */
+int efa_letkf_slab_cycle_dev(efa_ctx *ctx, long rows, int M, long P, const double *X_dev, double *post_dev, double *ym_dev,
+                             double *Yp_dev, int obs_block_out, const double *ob_value, const double *ob_error,
+                             const uint8_t *ob_assim, const double *ob_lat, const double *ob_lon, const double *ob_halfwidth_km,
+                             const double *grid_lat, const double *grid_lon, long ncol, long n_lead, double *prior_mean,
+                             double *prior_var, double *post_mean, double *post_var, uint8_t *assimilated,
+                             double *col_stats_dev /* [ngroups][ncol][3] or NULL */);
+int efa_letkf_slab_cycle_f32_dev(efa_ctx *ctx, long rows, int M, long P, const float *X_dev, float *post_dev, double *ym_dev,
+                                 double *Yp_dev, int obs_block_out, const double *ob_value, const double *ob_error,
+                                 const uint8_t *ob_assim, const double *ob_lat, const double *ob_lon, const double *ob_halfwidth_km,
+                                 const double *grid_lat, const double *grid_lon, long ncol, long n_lead, double *prior_mean,
+                                 double *prior_var, double *post_mean, double *post_var, uint8_t *assimilated,
+                                 double *col_stats_dev /* [ngroups][ncol][3] or NULL */);
+int efa_letkf_slab_cycle_interp_dev(efa_ctx *ctx, long rows, int M, long P, const double *X_dev, double *post_dev, double *ym_dev,
+                                    double *Yp_dev, int obs_block_out, const double *ob_value, const double *ob_error,
+                                    const uint8_t *ob_assim, const double *ob_lat, const double *ob_lon,
+                                    const double *ob_halfwidth_km, const double *grid_lat, const double *grid_lon, long ny, long nx,
+                                    long stride_y, long stride_x, long n_lead, double *prior_mean, double *prior_var,
+                                    double *post_mean, double *post_var, uint8_t *assimilated,
+                                    double *node_stats_dev /* [ngroups][nnodes][3] or NULL */);
+int efa_letkf_slab_cycle_interp_f32_dev(efa_ctx *ctx, long rows, int M, long P, const float *X_dev, float *post_dev, double *ym_dev,
+                                        double *Yp_dev, int obs_block_out, const double *ob_value, const double *ob_error,
+                                        const uint8_t *ob_assim, const double *ob_lat, const double *ob_lon,
+                                        const double *ob_halfwidth_km, const double *grid_lat, const double *grid_lon, long ny,
+                                        long nx, long stride_y, long stride_x, long n_lead, double *prior_mean, double *prior_var,
+                                        double *post_mean, double *post_var, uint8_t *assimilated,
+                                        double *node_stats_dev /* [ngroups][nnodes][3] or NULL */);
+int efa_letkf_slab_weights_dev(efa_ctx *ctx, int M, long P, const double *ym_dev, const double *Yp_dev, const double *ob_value,
+                               const double *ob_error, const uint8_t *ob_assim, const double *ob_lat, const double *ob_lon,
+                               const double *ob_halfwidth_km, long npts, const double *pt_lat, const double *pt_lon,
+                               double *Tw_dev /* [ngroups][npts][M][M+1] */, double *stats_dev /* [ngroups][npts][3] or NULL */);
+int efa_letkf_slab_groups(efa_ctx *ctx, long n_lead, int *group_of /* [n_lead] or NULL */, int *ngroups);
 
 /* ---- device memory for callers without their own allocator -------------*/
 int efa_malloc(efa_ctx *ctx, size_t bytes, void **dev_out);
