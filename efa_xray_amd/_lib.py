@@ -945,24 +945,28 @@ class Context(object):
                                                         ctypes.byref(n)))
         return g, n.value
 
-    def letkf_slab_weights(self, M, P, ym, Yp, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth, pt_lat, pt_lon, n_lead):
-        """efa_letkf_slab_weights_dev: the solve of every slab group at the given points.  Returns (T (ngroups, npts, M, M),
-        w (ngroups, npts, M), stats (ngroups, npts, 3))."""
+    def _letkf_weights(self, entry, ngroups, M, P, ym, Yp, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth, pt_lat, pt_lon):
+        """The solve at the given points through `entry`.  Returns the downloaded pairs (ngroups, npts, M, M + 1) and statistics
+        (ngroups, npts, 3); ngroups None: the plain entry, one group."""
         val, err, asm, lat, lon, hw = self._ob_arrays(P, ob_value, ob_error, ob_assim, LOC_GC, ob_lat, ob_lon, ob_halfwidth)
         plat = np.ascontiguousarray(pt_lat, dtype=np.float64).reshape(-1)
         plon = np.ascontiguousarray(pt_lon, dtype=np.float64).reshape(-1)
         assert plat.shape == plon.shape
         npts = plat.shape[0]
-        _, ng = self.letkf_slab_groups(n_lead)
+        ng = 1 if ngroups is None else ngroups
         Tw = self.empty((ng, max(npts, 1), M, M + 1))
         st = self.empty((ng, max(npts, 1), 3))
-        _check(self.lib, self.lib.efa_letkf_slab_weights_dev(
-            self.handle, M, P, self._addr(ym), self._addr(Yp), _dp(val), _dp(err), _u8p(asm), _dp(lat), _dp(lon), _dp(hw),
-            npts, _dp(plat), _dp(plon), self._addr(Tw), self._addr(st)))
-        if npts == 0:
-            return np.zeros((ng, 0, M, M)), np.zeros((ng, 0, M)), np.zeros((ng, 0, 3))
-        tw = Tw.download()
-        return np.ascontiguousarray(tw[:, :, :, :M]), np.ascontiguousarray(tw[:, :, :, M]), st.download()
+        _check(self.lib, entry(self.handle, M, P, self._addr(ym), self._addr(Yp), _dp(val), _dp(err), _u8p(asm), _dp(lat), _dp(lon),
+                               _dp(hw), npts, _dp(plat), _dp(plon), self._addr(Tw), self._addr(st)))
+        return Tw.download()[:, :npts], st.download()[:, :npts]
+
+    def letkf_slab_weights(self, M, P, ym, Yp, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth, pt_lat, pt_lon, n_lead):
+        """efa_letkf_slab_weights_dev: the solve of every slab group at the given points.  Returns (T (ngroups, npts, M, M),
+        w (ngroups, npts, M), stats (ngroups, npts, 3))."""
+        _, ng = self.letkf_slab_groups(n_lead)
+        tw, st = self._letkf_weights(self.lib.efa_letkf_slab_weights_dev, ng, M, P, ym, Yp, ob_value, ob_error, ob_assim, ob_lat,
+                                     ob_lon, ob_halfwidth, pt_lat, pt_lon)
+        return np.ascontiguousarray(tw[..., :M]), np.ascontiguousarray(tw[..., M]), st
 
     def letkf_interp_apply(self, rows, M, X, post, shape, stride, n_lead, Tw_nodes, node_stats=None, f32=None):
         """efa_letkf_interp_apply_dev / _f32_dev: the interpolate-and-apply launch alone.  Tw_nodes: a float64
@@ -979,18 +983,9 @@ class Context(object):
     def letkf_weights(self, M, P, ym, Yp, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth, pt_lat, pt_lon):
         """efa_letkf_weights_dev: the LETKF solve at the given points.  Returns (T (npts, M, M), w (npts, M), stats (npts, 3) =
         {n_local, dfs, sweeps})."""
-        val, err, asm, lat, lon, hw = self._ob_arrays(P, ob_value, ob_error, ob_assim, LOC_GC, ob_lat, ob_lon, ob_halfwidth)
-        plat = np.ascontiguousarray(pt_lat, dtype=np.float64).reshape(-1)
-        plon = np.ascontiguousarray(pt_lon, dtype=np.float64).reshape(-1)
-        assert plat.shape == plon.shape
-        npts = plat.shape[0]
-        Tw = self.empty((max(npts, 1), M, M + 1))
-        st = self.empty((max(npts, 1), 3))
-        _check(self.lib, self.lib.efa_letkf_weights_dev(
-            self.handle, M, P, self._addr(ym), self._addr(Yp), _dp(val), _dp(err), _u8p(asm), _dp(lat), _dp(lon), _dp(hw),
-            npts, _dp(plat), _dp(plon), self._addr(Tw), self._addr(st)))
-        tw = Tw.download()[:npts]
-        return np.ascontiguousarray(tw[:, :, :M]), np.ascontiguousarray(tw[:, :, M]), st.download()[:npts]
+        tw, st = self._letkf_weights(self.lib.efa_letkf_weights_dev, None, M, P, ym, Yp, ob_value, ob_error, ob_assim, ob_lat,
+                                     ob_lon, ob_halfwidth, pt_lat, pt_lon)
+        return np.ascontiguousarray(tw[0, :, :, :M]), np.ascontiguousarray(tw[0, :, :, M]), st[0]
 
     def ensrf_update_dev(self, rows, M, P, xm, Xp, ym, Yp, ob_value, ob_error, ob_assim,
                          loc_mode=LOC_NONE, ob_lat=None, ob_lon=None, ob_halfwidth=None,

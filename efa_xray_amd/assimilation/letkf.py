@@ -137,28 +137,25 @@ class LETKF(EnSRF):
             mesh = dict(shape=(ny, nx), stride=self.weight_stride)
         if self.verbose:
             print("Beginning the column solves")
-        if slab:
-            try:
+        ng = 1                                  # solves per column or node
+        try:
+            if slab:
                 group_of, ng = ctx.letkf_slab_groups(n_lead)
-                stats = ctx.empty((ng * sy * sx, 3))
-                diag = ctx.letkf_slab_cycle(N, M, P, X, X, ym, Yp, value, error, assim, lat, lon, hw, grid_lat, grid_lon, n_lead,
-                                            col_stats=stats, f32=f32, **mesh)
-            finally:                            # the context is shared per device: the settings do not outlive the update
+            stats = ctx.empty((ng * sy * sx, 3))
+            diag = ctx.letkf_cycle(N, M, P, X, X, ym, Yp, value, error, assim, lat, lon, hw, grid_lat, grid_lon, n_lead,
+                                   col_stats=stats, f32=f32, _slab=slab, **mesh)
+        finally:
+            if slab:                            # the context is shared per device: the settings do not outlive the update
                 ctx.set_vertical_localization(None)
                 ctx.set_slab_localization(None)
-        else:
-            stats = ctx.empty((sy * sx, 3))
-            diag = ctx.letkf_cycle(N, M, P, X, X, ym, Yp, value, error, assim, lat, lon, hw, grid_lat, grid_lon, n_lead,
-                                   col_stats=stats, f32=f32, **mesh)
         self.last_timing = ctx.last_timing()
         self._write_diagnostics(diag)
+        st = stats.download().reshape(ng, sy, sx, 3)
+        if not slab:                            # the plain filter documents (ny, nx) / (nyn, nxn)
+            st = st[0]
+        self.last_solve = dict(n_local=st[..., 0].astype(np.int64), dfs=st[..., 1].copy(), sweeps=st[..., 2].astype(np.int64))
         if slab:
-            st = stats.download().reshape(ng, sy, sx, 3)
-            self.last_solve = dict(n_local=st[..., 0].astype(np.int64), dfs=st[..., 1].copy(), sweeps=st[..., 2].astype(np.int64),
-                                   group_of_slab=group_of.astype(np.int64).reshape(prior.nvars(), prior.ntimes()))
-        else:
-            st = stats.download().reshape(sy, sx, 3)
-            self.last_solve = dict(n_local=st[:, :, 0].astype(np.int64), dfs=st[:, :, 1].copy(), sweeps=st[:, :, 2].astype(np.int64))
+            self.last_solve.update(group_of_slab=group_of.astype(np.int64).reshape(prior.nvars(), prior.ntimes()))
         if mesh:
             self.last_solve.update(node_y=node_y, node_x=node_x)
         if self.verbose:

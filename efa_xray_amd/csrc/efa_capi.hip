@@ -71,6 +71,35 @@ void harvest_state_ms(efa_ctx* c) {
 
 using namespace efa_host;
 
+namespace {
+
+// the driver's structs from a LETKF entry's values, each assigned to its field by name
+efa_host::LetkfObsIn letkf_obs_in(const double* ym_dev, const double* Yp_dev, const double* ob_value, const double* ob_error,
+                                  const uint8_t* ob_assim, const double* ob_lat, const double* ob_lon, const double* ob_halfwidth_km) {
+  efa_host::LetkfObsIn o;
+  o.ym_dev = ym_dev;
+  o.Yp_dev = Yp_dev;
+  o.ob_value = ob_value;
+  o.ob_error = ob_error;
+  o.ob_assim = ob_assim;
+  o.ob_lat = ob_lat;
+  o.ob_lon = ob_lon;
+  o.ob_hw = ob_halfwidth_km;
+  return o;
+}
+
+efa_host::LetkfDiagOut letkf_diag_out(double* prior_mean, double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated) {
+  efa_host::LetkfDiagOut d;
+  d.prior_mean = prior_mean;
+  d.prior_var = prior_var;
+  d.post_mean = post_mean;
+  d.post_var = post_var;
+  d.assimilated = assimilated;
+  return d;
+}
+
+}  // namespace
+
 extern "C" {
 
 int efa_abi_version(void) { return EFA_ABI_VERSION; }
@@ -968,9 +997,10 @@ int efa_letkf_cycle_dev(efa_ctx* c, long rows, int M, long P, const double* X_de
                         const double* grid_lon, long ncol, long n_lead, double* prior_mean, double* prior_var, double* post_mean,
                         double* post_var, uint8_t* assimilated, double* col_stats_dev) {
   EFA_TRY(use(c));
-  return efa_host::letkf_cycle(c, efa::Elem::f64, rows, M, P, X_dev, post_dev, ym_dev, Yp_dev, obs_block_out, ob_value, ob_error, ob_assim,
-                               ob_lat, ob_lon, ob_halfwidth_km, grid_lat, grid_lon, ncol, n_lead, prior_mean, prior_var, post_mean,
-                               post_var, assimilated, col_stats_dev);
+  return efa_host::letkf_cycle(c, efa_host::StateRows{X_dev, post_dev, efa::Elem::f64, rows, M}, P,
+                               letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+                               obs_block_out ? ym_dev : nullptr, obs_block_out ? Yp_dev : nullptr, grid_lat, grid_lon, ncol, n_lead,
+                               letkf_diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), col_stats_dev, nullptr, false);
 }
 
 int efa_letkf_cycle_f32_dev(efa_ctx* c, long rows, int M, long P, const float* X_dev, float* post_dev, double* ym_dev, double* Yp_dev,
@@ -979,9 +1009,10 @@ int efa_letkf_cycle_f32_dev(efa_ctx* c, long rows, int M, long P, const float* X
                             const double* grid_lon, long ncol, long n_lead, double* prior_mean, double* prior_var, double* post_mean,
                             double* post_var, uint8_t* assimilated, double* col_stats_dev) {
   EFA_TRY(use(c));
-  return efa_host::letkf_cycle(c, efa::Elem::f32, rows, M, P, X_dev, post_dev, ym_dev, Yp_dev, obs_block_out, ob_value, ob_error, ob_assim,
-                               ob_lat, ob_lon, ob_halfwidth_km, grid_lat, grid_lon, ncol, n_lead, prior_mean, prior_var, post_mean,
-                               post_var, assimilated, col_stats_dev);
+  return efa_host::letkf_cycle(c, efa_host::StateRows{X_dev, post_dev, efa::Elem::f32, rows, M}, P,
+                               letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+                               obs_block_out ? ym_dev : nullptr, obs_block_out ? Yp_dev : nullptr, grid_lat, grid_lon, ncol, n_lead,
+                               letkf_diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), col_stats_dev, nullptr, false);
 }
 
 int efa_letkf_weights_dev(efa_ctx* c, int M, long P, const double* ym_dev, const double* Yp_dev, const double* ob_value,
@@ -989,8 +1020,8 @@ int efa_letkf_weights_dev(efa_ctx* c, int M, long P, const double* ym_dev, const
                           const double* ob_halfwidth_km, long npts, const double* pt_lat, const double* pt_lon, double* Tw_dev,
                           double* stats_dev) {
   EFA_TRY(use(c));
-  return efa_host::letkf_weights(c, M, P, ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km, npts, pt_lat,
-                                 pt_lon, Tw_dev, stats_dev);
+  return efa_host::letkf_weights(c, M, P, letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+                                 npts, pt_lat, pt_lon, Tw_dev, stats_dev, false);
 }
 
 int efa_letkf_cycle_interp_dev(efa_ctx* c, long rows, int M, long P, const double* X_dev, double* post_dev, double* ym_dev,
@@ -1001,9 +1032,10 @@ int efa_letkf_cycle_interp_dev(efa_ctx* c, long rows, int M, long P, const doubl
                                uint8_t* assimilated, double* node_stats_dev) {
   EFA_TRY(use(c));
   const efa::LetkfMesh mesh{ny, nx, stride_y, stride_x};
-  return efa_host::letkf_cycle(c, efa::Elem::f64, rows, M, P, X_dev, post_dev, ym_dev, Yp_dev, obs_block_out, ob_value, ob_error, ob_assim,
-                               ob_lat, ob_lon, ob_halfwidth_km, grid_lat, grid_lon, 0, n_lead, prior_mean, prior_var, post_mean,
-                               post_var, assimilated, node_stats_dev, &mesh);
+  return efa_host::letkf_cycle(c, efa_host::StateRows{X_dev, post_dev, efa::Elem::f64, rows, M}, P,
+                               letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+                               obs_block_out ? ym_dev : nullptr, obs_block_out ? Yp_dev : nullptr, grid_lat, grid_lon, 0, n_lead,
+                               letkf_diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), node_stats_dev, &mesh, false);
 }
 
 int efa_letkf_cycle_interp_f32_dev(efa_ctx* c, long rows, int M, long P, const float* X_dev, float* post_dev, double* ym_dev,
@@ -1014,9 +1046,10 @@ int efa_letkf_cycle_interp_f32_dev(efa_ctx* c, long rows, int M, long P, const f
                                    uint8_t* assimilated, double* node_stats_dev) {
   EFA_TRY(use(c));
   const efa::LetkfMesh mesh{ny, nx, stride_y, stride_x};
-  return efa_host::letkf_cycle(c, efa::Elem::f32, rows, M, P, X_dev, post_dev, ym_dev, Yp_dev, obs_block_out, ob_value, ob_error, ob_assim,
-                               ob_lat, ob_lon, ob_halfwidth_km, grid_lat, grid_lon, 0, n_lead, prior_mean, prior_var, post_mean,
-                               post_var, assimilated, node_stats_dev, &mesh);
+  return efa_host::letkf_cycle(c, efa_host::StateRows{X_dev, post_dev, efa::Elem::f32, rows, M}, P,
+                               letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+                               obs_block_out ? ym_dev : nullptr, obs_block_out ? Yp_dev : nullptr, grid_lat, grid_lon, 0, n_lead,
+                               letkf_diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), node_stats_dev, &mesh, false);
 }
 
 int efa_letkf_slab_cycle_dev(efa_ctx* c, long rows, int M, long P, const double* X_dev, double* post_dev, double* ym_dev,
@@ -1025,9 +1058,10 @@ int efa_letkf_slab_cycle_dev(efa_ctx* c, long rows, int M, long P, const double*
                              const double* grid_lon, long ncol, long n_lead, double* prior_mean, double* prior_var, double* post_mean,
                              double* post_var, uint8_t* assimilated, double* col_stats_dev) {
   EFA_TRY(use(c));
-  return efa_host::letkf_cycle(c, efa::Elem::f64, rows, M, P, X_dev, post_dev, ym_dev, Yp_dev, obs_block_out, ob_value, ob_error, ob_assim,
-                               ob_lat, ob_lon, ob_halfwidth_km, grid_lat, grid_lon, ncol, n_lead, prior_mean, prior_var, post_mean,
-                               post_var, assimilated, col_stats_dev, nullptr, true);
+  return efa_host::letkf_cycle(c, efa_host::StateRows{X_dev, post_dev, efa::Elem::f64, rows, M}, P,
+                               letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+                               obs_block_out ? ym_dev : nullptr, obs_block_out ? Yp_dev : nullptr, grid_lat, grid_lon, ncol, n_lead,
+                               letkf_diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), col_stats_dev, nullptr, true);
 }
 
 int efa_letkf_slab_cycle_f32_dev(efa_ctx* c, long rows, int M, long P, const float* X_dev, float* post_dev, double* ym_dev,
@@ -1036,9 +1070,10 @@ int efa_letkf_slab_cycle_f32_dev(efa_ctx* c, long rows, int M, long P, const flo
                                  const double* grid_lat, const double* grid_lon, long ncol, long n_lead, double* prior_mean,
                                  double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated, double* col_stats_dev) {
   EFA_TRY(use(c));
-  return efa_host::letkf_cycle(c, efa::Elem::f32, rows, M, P, X_dev, post_dev, ym_dev, Yp_dev, obs_block_out, ob_value, ob_error, ob_assim,
-                               ob_lat, ob_lon, ob_halfwidth_km, grid_lat, grid_lon, ncol, n_lead, prior_mean, prior_var, post_mean,
-                               post_var, assimilated, col_stats_dev, nullptr, true);
+  return efa_host::letkf_cycle(c, efa_host::StateRows{X_dev, post_dev, efa::Elem::f32, rows, M}, P,
+                               letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+                               obs_block_out ? ym_dev : nullptr, obs_block_out ? Yp_dev : nullptr, grid_lat, grid_lon, ncol, n_lead,
+                               letkf_diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), col_stats_dev, nullptr, true);
 }
 
 int efa_letkf_slab_cycle_interp_dev(efa_ctx* c, long rows, int M, long P, const double* X_dev, double* post_dev, double* ym_dev,
@@ -1049,9 +1084,10 @@ int efa_letkf_slab_cycle_interp_dev(efa_ctx* c, long rows, int M, long P, const 
                                     uint8_t* assimilated, double* node_stats_dev) {
   EFA_TRY(use(c));
   const efa::LetkfMesh mesh{ny, nx, stride_y, stride_x};
-  return efa_host::letkf_cycle(c, efa::Elem::f64, rows, M, P, X_dev, post_dev, ym_dev, Yp_dev, obs_block_out, ob_value, ob_error, ob_assim,
-                               ob_lat, ob_lon, ob_halfwidth_km, grid_lat, grid_lon, 0, n_lead, prior_mean, prior_var, post_mean,
-                               post_var, assimilated, node_stats_dev, &mesh, true);
+  return efa_host::letkf_cycle(c, efa_host::StateRows{X_dev, post_dev, efa::Elem::f64, rows, M}, P,
+                               letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+                               obs_block_out ? ym_dev : nullptr, obs_block_out ? Yp_dev : nullptr, grid_lat, grid_lon, 0, n_lead,
+                               letkf_diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), node_stats_dev, &mesh, true);
 }
 
 int efa_letkf_slab_cycle_interp_f32_dev(efa_ctx* c, long rows, int M, long P, const float* X_dev, float* post_dev, double* ym_dev,
@@ -1062,9 +1098,10 @@ int efa_letkf_slab_cycle_interp_f32_dev(efa_ctx* c, long rows, int M, long P, co
                                         double* post_mean, double* post_var, uint8_t* assimilated, double* node_stats_dev) {
   EFA_TRY(use(c));
   const efa::LetkfMesh mesh{ny, nx, stride_y, stride_x};
-  return efa_host::letkf_cycle(c, efa::Elem::f32, rows, M, P, X_dev, post_dev, ym_dev, Yp_dev, obs_block_out, ob_value, ob_error, ob_assim,
-                               ob_lat, ob_lon, ob_halfwidth_km, grid_lat, grid_lon, 0, n_lead, prior_mean, prior_var, post_mean,
-                               post_var, assimilated, node_stats_dev, &mesh, true);
+  return efa_host::letkf_cycle(c, efa_host::StateRows{X_dev, post_dev, efa::Elem::f32, rows, M}, P,
+                               letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+                               obs_block_out ? ym_dev : nullptr, obs_block_out ? Yp_dev : nullptr, grid_lat, grid_lon, 0, n_lead,
+                               letkf_diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), node_stats_dev, &mesh, true);
 }
 
 int efa_letkf_slab_weights_dev(efa_ctx* c, int M, long P, const double* ym_dev, const double* Yp_dev, const double* ob_value,
@@ -1072,8 +1109,8 @@ int efa_letkf_slab_weights_dev(efa_ctx* c, int M, long P, const double* ym_dev, 
                                const double* ob_halfwidth_km, long npts, const double* pt_lat, const double* pt_lon, double* Tw_dev,
                                double* stats_dev) {
   EFA_TRY(use(c));
-  return efa_host::letkf_weights(c, M, P, ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km, npts, pt_lat,
-                                 pt_lon, Tw_dev, stats_dev, true);
+  return efa_host::letkf_weights(c, M, P, letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+                                 npts, pt_lat, pt_lon, Tw_dev, stats_dev, true);
 }
 
 int efa_letkf_slab_groups(efa_ctx* c, long n_lead, int* group_of, int* ngroups) {
@@ -1084,15 +1121,15 @@ int efa_letkf_slab_groups(efa_ctx* c, long n_lead, int* group_of, int* ngroups) 
 int efa_letkf_interp_apply_dev(efa_ctx* c, long rows, int M, const double* X_dev, double* post_dev, long ny, long nx, long stride_y,
                                long stride_x, long n_lead, const double* Tw_nodes_dev, const double* node_stats_dev) {
   EFA_TRY(use(c));
-  return efa_host::letkf_interp_apply(c, efa::Elem::f64, rows, M, X_dev, post_dev, ny, nx, stride_y, stride_x, n_lead, Tw_nodes_dev,
-                                      node_stats_dev);
+  return efa_host::letkf_interp_apply(c, efa_host::StateRows{X_dev, post_dev, efa::Elem::f64, rows, M},
+                                      efa::LetkfMesh{ny, nx, stride_y, stride_x}, n_lead, Tw_nodes_dev, node_stats_dev);
 }
 
 int efa_letkf_interp_apply_f32_dev(efa_ctx* c, long rows, int M, const float* X_dev, float* post_dev, long ny, long nx, long stride_y,
                                    long stride_x, long n_lead, const double* Tw_nodes_dev, const double* node_stats_dev) {
   EFA_TRY(use(c));
-  return efa_host::letkf_interp_apply(c, efa::Elem::f32, rows, M, X_dev, post_dev, ny, nx, stride_y, stride_x, n_lead, Tw_nodes_dev,
-                                      node_stats_dev);
+  return efa_host::letkf_interp_apply(c, efa_host::StateRows{X_dev, post_dev, efa::Elem::f32, rows, M},
+                                      efa::LetkfMesh{ny, nx, stride_y, stride_x}, n_lead, Tw_nodes_dev, node_stats_dev);
 }
 
 int efa_last_timing(efa_ctx* c, double* state_ms, double* obs_ms, long* state_launches, int* path_taken) {

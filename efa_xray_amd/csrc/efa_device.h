@@ -83,6 +83,14 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
+// A float64 result to the rows' element type, rounded once at the store (k_letkf, k_letkf_interp).
+template <typename E>
+__device__ __forceinline__ E letkf_round(double v);
+template <>
+__device__ __forceinline__ double letkf_round<double>(double v) { return v; }
+template <>
+__device__ __forceinline__ float letkf_round<float>(double v) { return (float)v; }
+
 // Counter-based uniform/normal generator (splitmix64 finaliser) used for the
 // bench's synthetic ensemble: value depends only on (seed, row, member).
 __device__ __host__ __forceinline__ uint64_t mix64(uint64_t z) {

@@ -11,9 +11,9 @@
 //   efa_pmmean.hip   the probability-matched mean and the segmented radix sort under it: its kernels and the driver of efa_pm_mean_dev
 //   efa_gram.hip     the ensemble Gram matrix: its kernels and the driver of efa_gram_dev
 //   efa_etkf.hip     the batch observation-space solver's kernels (option "obs_solver" 1; driven from efa_phase_a.hip)
-//   efa_letkf.hip    the local ensemble transform Kalman filter: its kernels and the driver of efa_letkf_cycle_dev / efa_letkf_weights_dev
-//                    and of the weight-interpolation entries (efa_letkf_cycle_interp_dev / efa_letkf_interp_apply_dev)
-//   efa_letkf_interp.hip  the interpolate-and-apply kernel of those entries
+//   efa_letkf.hip    the local ensemble transform Kalman filter: its kernels and their launcher (plain, or per slab group)
+//   efa_letkf_interp.hip  the interpolate-and-apply kernel of the weight-interpolation entries and its launcher
+//   efa_letkf_driver.hip  the driver of every efa_letkf_* entry: the cycles (plain / interp / slab), the weights, efa_letkf_interp_apply_dev
 //   efa_comm.hip    RCCL
 // Headers the diagnostics share: efa_quadrow.h (the four-lane row layout of k_sens_pass, k_verify, k_products and k_nbr_records),
 // efa_sortnet.h (the bitonic network on it), efa_quadreduce.h (table flush, chunk partial, k_group_reduce) and efa_diag.h (their
@@ -149,26 +149,36 @@ int state_cycle(efa_ctx* c, const StateRows& r, const double* grid_lat, const do
 // end_recorded: iv.end is in the stream already (a speculative transform that turned out right)
 int end_state_call(efa_ctx* c, Interval& iv, bool timed = true, bool end_recorded = false);
 
-// ---- efa_letkf.hip ------------------------------------------------------------------------------------------------------------
+// ---- efa_letkf_driver.hip -----------------------------------------------------------------------------------------------------
+// the observation inputs of a LETKF call: the prior obs block on the device, the per-ob arrays on the host
+struct LetkfObsIn {
+  const double *ym_dev = nullptr, *Yp_dev = nullptr;
+  const double *ob_value = nullptr, *ob_error = nullptr;
+  const uint8_t* ob_assim = nullptr;
+  const double *ob_lat = nullptr, *ob_lon = nullptr, *ob_hw = nullptr;
+};
+// the five host diagnostics of a cycle, [P] each or null
+struct LetkfDiagOut {
+  double *prior_mean = nullptr, *prior_var = nullptr, *post_mean = nullptr, *post_var = nullptr;
+  uint8_t* assimilated = nullptr;
+};
 // efa_letkf_cycle_dev / _f32_dev: checks, the obs' effective flags and prior diagnostics, the lists and the solve at every ob
-// position (the obs block), the lists and the solve of every grid column (the state); waits before it returns the diagnostics
-int letkf_cycle(efa_ctx* c, Elem elem, long rows, int M, long P, const void* X_dev, void* post_dev, double* ym_dev, double* Yp_dev,
-                int obs_block_out, const double* ob_value, const double* ob_error, const uint8_t* ob_assim, const double* ob_lat,
-                const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
-                double* prior_mean, double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated, double* col_stats_dev,
-                const efa::LetkfMesh* mesh = nullptr, bool slab = false);
+// position (the obs block), the lists and the solve of every grid column (the state); waits before it returns the diagnostics.
+// ym_out / Yp_out: where the posterior obs block goes (obs_block_out: the caller's block), both null: nowhere
+int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const LetkfObsIn& obs, double* ym_out, double* Yp_out, const double* grid_lat,
+                const double* grid_lon, long ncol, long n_lead, const LetkfDiagOut& diag, double* col_stats_dev,
+                const efa::LetkfMesh* mesh, bool slab);
 // (mesh: efa_letkf_cycle_interp_dev / _f32_dev, DESIGN.md §7y-2 -- ncol is taken from it, the solve runs at its nodes only into a
 // buffer of the context, col_stats_dev receives the NODE statistics, and efa_letkf_interp.hip's kernel interpolates the pairs to
 // every column and applies them; a unit stride is the call without a mesh)
 // (slab: efa_letkf_slab_cycle_dev and its kin, DESIGN.md §7y-3 -- one solve per (slab group, column) under the vertical and / or slab
 // setting; col_stats_dev is then [ngroups][ncol or nnodes][3])
 // efa_letkf_interp_apply_dev / _f32_dev: that kernel alone on caller-given node pairs, under the context's relaxation; waits
-int letkf_interp_apply(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, void* post_dev, long ny, long nx, long stride_y,
-                       long stride_x, long n_lead, const double* Tw_nodes_dev, const double* node_stats_dev);
+int letkf_interp_apply(efa_ctx* c, const StateRows& r, const efa::LetkfMesh& mesh, long n_lead, const double* Tw_nodes_dev,
+                       const double* node_stats_dev);
 // efa_letkf_weights_dev: the same solve at caller-given points, [T | w] of each to Tw_dev; waits
-int letkf_weights(efa_ctx* c, int M, long P, const double* ym_dev, const double* Yp_dev, const double* ob_value, const double* ob_error,
-                  const uint8_t* ob_assim, const double* ob_lat, const double* ob_lon, const double* ob_hw, long npts,
-                  const double* pt_lat, const double* pt_lon, double* Tw_dev, double* stats_dev, bool slab = false);
+int letkf_weights(efa_ctx* c, int M, long P, const LetkfObsIn& obs, long npts, const double* pt_lat, const double* pt_lon, double* Tw_dev,
+                  double* stats_dev, bool slab);
 // (slab: efa_letkf_slab_weights_dev -- Tw_dev [ngroups][npts][M][M + 1], stats_dev [ngroups][npts][3])
 // efa_letkf_slab_groups: the group of every slab under the context's settings, numbered by first appearance
 int letkf_slab_group_table(efa_ctx* c, long n_lead, int* group_of, int* ngroups);

@@ -26,24 +26,21 @@
 //   kLetkfWeights skips 4 and writes T (as k_etkf_eig forms it: upper triangle, mirrored) and w of the point.
 //   A column no ob reaches (n_local = 0) runs no solve: its rows are copied bit for bit, its statistics are (0, 0, 0), its pair (I, 0).
 // Same inputs, same bits: every reduction has a fixed order, there are no floating-point atomics.
-// Weight interpolation: the driver below also runs kLetkfWeights at the nodes of a coarse mesh of grid columns and
-// hands the node pairs to k_letkf_interp (efa_letkf_interp.hip), which interpolates them to every column and applies them.
+// Weight interpolation: the driver (efa_letkf_driver.hip) also runs kLetkfWeights at the nodes of a coarse mesh of
+// grid columns and hands the node pairs to k_letkf_interp (efa_letkf_interp.hip), which interpolates them to every column and
+// applies them.
 // Vertical, temporal and variable localisation (efa_letkf_slab_cycle_dev and its kin): k_letkf with the SLAB switch
 // solves once per (slab group, column) under rho_k(c) * S[k][rep[g]], S the slab factor table of §7t; k_letkf_obs_factor scales the
 // tapers of the lists built at the ob positions by the obs-obs factor F(j, k), after which the obs block runs as above.  The driver
 // computes the groups from the host copies of the two settings (letkf_groups).
+// This file holds the kernels and their launchers only.
 #include "efa_driver.h"
 #include "efa_device.h"
 #include "efa_etkf_eig.h"
 #include "efa_rows.h"
 #include "efa_slabfactor.h"
 
-#include <cmath>
 #include <cstdint>
-#include <cstring>
-#include <map>
-#include <tuple>
-#include <vector>
 
 namespace efa {
 namespace {
@@ -121,16 +118,12 @@ __device__ __forceinline__ void letkf_tile(int ti, int T, int* ta, int* tb) {
   *tb = a + ti;
 }
 
-template <typename E>
-__device__ __forceinline__ E letkf_round(double v);
-template <>
-__device__ __forceinline__ double letkf_round<double>(double v) { return v; }
-template <>
-__device__ __forceinline__ float letkf_round<float>(double v) { return (float)v; }
-
 // SLAB: one workgroup per (column, slab group), the group the fastest index of the launch so that the
 // workgroups of a column run together and find its list and Yp rows in L2; the staged weight is fl(fl(rho S[k][rep[g]]) / r), the
 // apply walks the group's slabs, the statistics and the pairs are laid out [group][point].
+struct LetkfSlabArgs : LetkfArgs {
+  LetkfGroups grp;
+};
 template <bool SLAB>
 struct LetkfArgsOf { typedef LetkfArgs type; };
 template <>
@@ -428,46 +421,36 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const typename LetkfArgsOf<SLAB
   }
 }
 
-template <int MODE, typename E, int NTMAX>
-hipError_t letkf_launch_as(const LetkfArgs& a, int nth, size_t lds, hipStream_t s) {
-  auto kern = k_letkf<MODE, E, NTMAX>;
+template <int MODE, typename E, int NTMAX, bool SLAB>
+hipError_t letkf_launch_as(const typename LetkfArgsOf<SLAB>::type& a, int nth, size_t lds, hipStream_t s) {
+  auto kern = k_letkf<MODE, E, NTMAX, SLAB>;
   if (lds > 48 * 1024) {
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  const long nblk = (a.npts + 15) / 16;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(nblk * 16)), dim3((unsigned)nth), lds, s, a);
+  long nwg = (a.npts + 15) / 16 * 16;
+  if constexpr (SLAB) nwg *= a.grp.ngroups;
+  hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3((unsigned)nth), lds, s, a);
   return hipGetLastError();
 }
 
-template <int MODE, typename E>
-hipError_t letkf_launch_mode(const LetkfArgs& a, hipStream_t s) {
+template <int MODE, typename E, bool SLAB>
+hipError_t letkf_launch_mode(const typename LetkfArgsOf<SLAB>::type& a, hipStream_t s) {
   const int nth = letkf_threads(a.M);
   const size_t lds = letkf_lds_bytes(a.M);
-  if (nth <= 256) return letkf_launch_as<MODE, E, 256>(a, nth, lds, s);
-  if (nth <= 512) return letkf_launch_as<MODE, E, 512>(a, nth, lds, s);
-  return letkf_launch_as<MODE, E, 1024>(a, nth, lds, s);
+  if (nth <= 256) return letkf_launch_as<MODE, E, 256, SLAB>(a, nth, lds, s);
+  if (nth <= 512) return letkf_launch_as<MODE, E, 512, SLAB>(a, nth, lds, s);
+  return letkf_launch_as<MODE, E, 1024, SLAB>(a, nth, lds, s);
 }
 
-template <int MODE, typename E, int NTMAX>
-hipError_t letkf_slab_launch_as(const LetkfSlabArgs& a, int nth, size_t lds, hipStream_t s) {
-  auto kern = k_letkf<MODE, E, NTMAX, true>;
-  if (lds > 48 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  const long nblk = (a.npts + 15) / 16;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(nblk * 16 * a.grp.ngroups)), dim3((unsigned)nth), lds, s, a);
-  return hipGetLastError();
-}
-
+// the plain launch, or with groups the SLAB one on (a, *grp)
 template <int MODE, typename E>
-hipError_t letkf_slab_launch_mode(const LetkfSlabArgs& a, hipStream_t s) {
-  const int nth = letkf_threads(a.M);
-  const size_t lds = letkf_lds_bytes(a.M);
-  if (nth <= 256) return letkf_slab_launch_as<MODE, E, 256>(a, nth, lds, s);
-  if (nth <= 512) return letkf_slab_launch_as<MODE, E, 512>(a, nth, lds, s);
-  return letkf_slab_launch_as<MODE, E, 1024>(a, nth, lds, s);
+hipError_t letkf_launch(const LetkfArgs& a, const LetkfGroups* grp, hipStream_t s) {
+  if (!grp) return letkf_launch_mode<MODE, E, false>(a, s);
+  LetkfSlabArgs sa{};
+  static_cast<LetkfArgs&>(sa) = a;
+  sa.grp = *grp;
+  return letkf_launch_mode<MODE, E, true>(sa, s);
 }
 
 // The obs block under the obs-obs factors: the lists built at the ob positions take F(j, k) of §7t, the factors
@@ -518,43 +501,30 @@ size_t letkf_lds_bytes(int M) {
   return ((size_t)letkf_region(M) + (size_t)(5 + 2 * kLetkfRows) * M + kLetkfSmall + 2) * sizeof(double);
 }
 
-hipError_t launch_letkf(const LetkfArgs& a, int mode, Elem elem, hipStream_t s) {
+hipError_t launch_letkf(const LetkfArgs& a, const LetkfGroups* grp, int mode, Elem elem, hipStream_t s) {
   if (a.M < 2 || a.M > kLetkfMaxM || a.npts < 0) return hipErrorInvalidValue;
   const int T = letkf_tiles_side(a.M);
   if (kLetkfTiles * (letkf_threads(a.M) / 64) < T * (T + 1) / 2 || letkf_lds_bytes(a.M) > 160 * 1024) return hipErrorInvalidValue;
+  if (grp) {
+    if (grp->ngroups < 1 || !grp->rep || !grp->grp_off || !grp->grp_leads || grp->s_pitch < 1) return hipErrorInvalidValue;
+    if (a.idx && !grp->S) return hipErrorInvalidValue;  // (no lists: the table is never read)
+  }
   if (a.npts == 0) return hipSuccess;
-  if ((a.npts + 15) / 16 * 16 > 0x7FFFFFF0L) return hipErrorInvalidValue;
+  if ((a.npts + 15) / 16 * 16 > 0x7FFFFFF0L / (grp ? grp->ngroups : 1)) return hipErrorInvalidValue;
   if (mode == kLetkfMembers) {
     if (!a.Xin || !a.Xout || a.n_lead < 1) return hipErrorInvalidValue;
-    return elem == Elem::f32 ? letkf_launch_mode<kLetkfMembers, float>(a, s) : letkf_launch_mode<kLetkfMembers, double>(a, s);
+    return elem == Elem::f32 ? letkf_launch<kLetkfMembers, float>(a, grp, s) : letkf_launch<kLetkfMembers, double>(a, grp, s);
   }
   if (elem != Elem::f64) return hipErrorInvalidValue;
-  if (mode == kLetkfPerts) {
-    if (!a.ym_in || !a.Yp_in || !a.ym_out || !a.Yp_out) return hipErrorInvalidValue;
-    return letkf_launch_mode<kLetkfPerts, double>(a, s);
+  if (mode == kLetkfPerts) {  // (no SLAB instantiation: the obs block runs on lists that carry the factors already)
+    if (grp || !a.ym_in || !a.Yp_in || !a.ym_out || !a.Yp_out) return hipErrorInvalidValue;
+    return letkf_launch_mode<kLetkfPerts, double, false>(a, s);
   }
   if (mode == kLetkfWeights) {
     if (!a.Tw) return hipErrorInvalidValue;
-    return letkf_launch_mode<kLetkfWeights, double>(a, s);
+    return letkf_launch<kLetkfWeights, double>(a, grp, s);
   }
   return hipErrorInvalidValue;
-}
-
-hipError_t launch_letkf_slab(const LetkfSlabArgs& a, int mode, Elem elem, hipStream_t s) {
-  const LetkfGroups& g = a.grp;
-  if (a.M < 2 || a.M > kLetkfMaxM || a.npts < 0) return hipErrorInvalidValue;
-  const int T = letkf_tiles_side(a.M);
-  if (kLetkfTiles * (letkf_threads(a.M) / 64) < T * (T + 1) / 2 || letkf_lds_bytes(a.M) > 160 * 1024) return hipErrorInvalidValue;
-  if (g.ngroups < 1 || !g.rep || !g.grp_off || !g.grp_leads || g.s_pitch < 1) return hipErrorInvalidValue;
-  if (a.idx && !g.S) return hipErrorInvalidValue;  // (no lists: the table is never read)
-  if (a.npts == 0) return hipSuccess;
-  if ((a.npts + 15) / 16 * 16 > 0x7FFFFFF0L / g.ngroups) return hipErrorInvalidValue;
-  if (mode == kLetkfMembers) {
-    if (!a.Xin || !a.Xout || a.n_lead < 1) return hipErrorInvalidValue;
-    return elem == Elem::f32 ? letkf_slab_launch_mode<kLetkfMembers, float>(a, s) : letkf_slab_launch_mode<kLetkfMembers, double>(a, s);
-  }
-  if (elem != Elem::f64 || mode != kLetkfWeights || !a.Tw) return hipErrorInvalidValue;
-  return letkf_slab_launch_mode<kLetkfWeights, double>(a, s);
 }
 
 hipError_t launch_letkf_obs_factor(long P, const long* off, const int* cnt, const int* idx, double* wts, const double* ob_vert,
@@ -580,565 +550,3 @@ hipError_t launch_letkf_prior(long P, int M, const double* Yp, const double* ym,
 }
 
 }  // namespace efa
-
-// ---- the driver (efa_letkf_driver) ----------------------------------------------------------------------------------------------
-namespace efa_host {
-
-using namespace efa;
-
-namespace {
-
-// the per-ob arrays of a call on the device, slices of c->letkf_ob
-struct LetkfObs {
-  long P = 0;
-  double *value = nullptr, *error = nullptr, *lat = nullptr, *lon = nullptr, *hw = nullptr, *req = nullptr;
-  double *act = nullptr, *dr = nullptr, *obtrig = nullptr;
-  double *prior_mean = nullptr, *prior_var = nullptr, *post_mean = nullptr, *post_var = nullptr;
-  uint8_t* assimilated = nullptr;
-  size_t diag_bytes() const { return 4 * (size_t)P * sizeof(double) + (size_t)P; }
-};
-
-// the lists of one set of points, slices of c->letkf_blk and the two entry buffers
-struct LetkfLists {
-  const long* off = nullptr;
-  const int *cnt = nullptr, *order = nullptr, *idx = nullptr;
-  const double* wts = nullptr;
-};
-
-// What no LETKF call serves, refused before anything is launched (include/efa_hip.h gives the reasons)
-// slab: the calls of DESIGN.md §7y-3, which need the vertical and/or the slab setting, sized for this call (n_lead < 0: not checked)
-int letkf_check_settings(const efa_ctx* c, const char* who, int M, long P, bool slab = false, long n_lead = -1) {
-  if (M < 2) return fail(EFA_ERR_INVALID, "%s: ensemble size M=%d must be >= 2", who, M);
-  if (M > kLetkfMaxM)
-    return fail(EFA_ERR_INVALID, "%s: M=%d exceeds %d members, the range in which the eigen-solve's M x M array of a column fits in LDS",
-                who, M, kLetkfMaxM);
-  if (P < 0) return fail(EFA_ERR_INVALID, "%s: negative observation count", who);
-  if (c->ai_field)
-    return fail(EFA_ERR_INVALID, "%s: an adaptive-inflation field is set (its update follows the serial order of the obs, which a "
-                "column's batch solve does not have)", who);
-  if (!slab && c->vl_on)
-    return fail(EFA_ERR_INVALID, "%s: vertical localisation is set (it needs a solve per (slab group, column): out of scope here, "
-                "use efa_letkf_slab_cycle_dev / SlabLETKF)", who);
-  if (!slab && c->sl_on)
-    return fail(EFA_ERR_INVALID, "%s: slab (temporal / cross-variable) localisation is set (it needs a solve per (slab group, column): "
-                "out of scope here, use efa_letkf_slab_cycle_dev / SlabLETKF)", who);
-  if (slab) {
-    if (!c->vl_on && !c->sl_on)
-      return fail(EFA_ERR_INVALID, "%s: neither vertical nor slab (temporal / cross-variable) localisation is set: use the plain call "
-                  "(efa_letkf_cycle_dev and its kin)", who);
-    if (c->vl_on && (c->vl_P != P || (n_lead >= 0 && c->vl_nlead != n_lead)))
-      return fail(EFA_ERR_INVALID, "%s: vertical localisation was set for %ld observations and %ld slabs, the call has %ld and n_lead=%ld",
-                  who, c->vl_P, c->vl_nlead, P, n_lead);
-    if (c->sl_on && (c->sl_P != P || (n_lead >= 0 && c->sl_nlead != n_lead)))
-      return fail(EFA_ERR_INVALID, "%s: slab localisation was set for %ld observations and %ld slabs, the call has %ld and n_lead=%ld", who,
-                  c->sl_P, c->sl_nlead, P, n_lead);
-  }
-  if (sec_active(c))
-    return fail(EFA_ERR_INVALID, "%s: a sampling-error-correction table is set (it acts on the serial gain of one observation at a time)",
-                who);
-  return EFA_OK;
-}
-
-int letkf_check_obs(const char* who, long P, const double* ym_dev, const double* Yp_dev, const double* ob_value, const double* ob_error,
-                    const uint8_t* ob_assim, const double* ob_lat, const double* ob_lon, const double* ob_hw) {
-  if (P == 0) return EFA_OK;
-  if (!ym_dev || !Yp_dev || !ob_value || !ob_error || !ob_assim) return fail(EFA_ERR_INVALID, "%s: null observation array", who);
-  if (!ob_lat || !ob_lon || !ob_hw) return fail(EFA_ERR_INVALID, "%s: the taper needs ob_lat/ob_lon/ob_halfwidth_km", who);
-  for (long k = 0; k < P; ++k) {
-    if (!ob_assim[k]) continue;
-    if (!(std::isfinite(ob_error[k]) && ob_error[k] > 0.0))
-      return fail(EFA_ERR_INVALID, "%s: observation %ld: error variance %g must be finite and > 0 (R-localisation divides by it)", who, k,
-                  ob_error[k]);
-    if (!(ob_hw[k] == ob_hw[k]) || ob_hw[k] == 0.0)
-      return fail(EFA_ERR_INVALID, "%s: observation %ld: localize_radius must be a non-zero number", who, k);
-  }
-  return EFA_OK;
-}
-
-// the obs on the device, then their prior diagnostics, effective flags and {d, r}
-int letkf_stage_obs(efa_ctx* c, int M, long P, const double* ym_dev, const double* Yp_dev, const double* ob_value, const double* ob_error,
-                    const uint8_t* ob_assim, const double* ob_lat, const double* ob_lon, const double* ob_hw, LetkfObs* out) {
-  hipStream_t s = c->stream;
-  const size_t n = (size_t)P;
-  // value | error | lat | lon | hw | requested [n each] | act [4n] | dr [2n] | obtrig [6n] | four diagnostics [n each] | assimilated bytes
-  EFA_TRY(c->letkf_ob.reserve((22 * n + 1) * sizeof(double) + n));
-  double* d = c->letkf_ob.as<double>();
-  LetkfObs o;
-  o.P = P;
-  o.value = d;
-  o.error = d + n;
-  o.lat = d + 2 * n;
-  o.lon = d + 3 * n;
-  o.hw = d + 4 * n;
-  o.req = d + 5 * n;
-  o.act = d + 6 * n;
-  o.dr = d + 10 * n;
-  o.obtrig = d + 12 * n;
-  o.prior_mean = d + 18 * n;
-  o.prior_var = d + 19 * n;
-  o.post_mean = d + 20 * n;
-  o.post_var = d + 21 * n;
-  o.assimilated = reinterpret_cast<uint8_t*>(d + 22 * n);
-  // value and error of an ob that is not requested are not read: the device gets the neutral pair (0, 1), its radius a harmless 1
-  std::vector<double> h(6 * n);
-  for (size_t k = 0; k < n; ++k) {
-    const bool on = ob_assim[k] != 0;
-    h[k] = on ? ob_value[k] : 0.0;
-    h[n + k] = on ? ob_error[k] : 1.0;
-    h[2 * n + k] = ob_lat[k];
-    h[3 * n + k] = ob_lon[k];
-    h[4 * n + k] = on ? ob_hw[k] : 1.0;
-    h[5 * n + k] = on ? 1.0 : 0.0;
-  }
-  EFA_HIP(hipMemcpyAsync(d, h.data(), 6 * n * sizeof(double), hipMemcpyHostToDevice, s));
-  EFA_HIP(hipStreamSynchronize(s));  // (h goes out of scope)
-  EFA_HIP(launch_letkf_prior(P, M, Yp_dev, ym_dev, o.value, o.error, o.req, c->qc_threshold * c->qc_threshold, o.prior_mean, o.prior_var,
-                             o.assimilated, o.act, o.dr, s));
-  *out = o;
-  return EFA_OK;
-}
-
-// The lists of `npts` points (device lat / lon) against the obs, by the one-pass sweep's builders as they are; the flag entry of the
-// coefficient table they read is the effective a_k.  One host round trip: the capacity.
-int letkf_build_lists(efa_ctx* c, long npts, const double* plat, const double* plon, const LetkfObs& o, LetkfLists* out) {
-  hipStream_t s = c->stream;
-  const long nblk = gc_num_blocks(npts);
-  const size_t b8 = ((size_t)(nblk + 1) * sizeof(long) + 15) & ~(size_t)15, b4 = ((size_t)nblk * sizeof(int) + 15) & ~(size_t)15;
-  EFA_TRY(c->letkf_blk.reserve(b8 + 3 * b4));
-  EFA_TRY(c->letkf_pairs.reserve(sizeof(unsigned long long)));
-  char* b = static_cast<char*>(c->letkf_blk.p);
-  long* off = reinterpret_cast<long*>(b);
-  int* cnt = reinterpret_cast<int*>(b + b8);
-  int* ub = reinterpret_cast<int*>(b + b8 + b4);
-  int* order = reinterpret_cast<int*>(b + b8 + 2 * b4);
-  EFA_HIP(hipMemsetAsync(c->letkf_pairs.p, 0, sizeof(unsigned long long), s));
-  EFA_HIP(launch_gc_bound(npts, o.P, plat, o.lat, o.hw, o.act, ub, off, s));
-  long cap = 0;
-  EFA_HIP(hipMemcpyAsync(&cap, off + nblk, sizeof(long), hipMemcpyDeviceToHost, s));
-  EFA_HIP(hipStreamSynchronize(s));
-  EFA_TRY(c->letkf_idx.reserve((size_t)(cap ? cap : 1) * sizeof(int)));
-  EFA_TRY(c->letkf_wts.reserve((size_t)(cap ? cap : 1) * 16 * sizeof(double)));
-  EFA_HIP(launch_gc_fill(npts, o.P, plat, plon, o.lat, o.lon, o.hw, o.act, o.obtrig, off, cnt, c->letkf_idx.as<int>(),
-                         c->letkf_wts.as<double>(), order, c->letkf_pairs.as<unsigned long long>(), s));
-  out->off = off;
-  out->cnt = cnt;
-  out->order = order;
-  out->idx = c->letkf_idx.as<int>();
-  out->wts = c->letkf_wts.as<double>();
-  return EFA_OK;
-}
-
-int letkf_upload_points(efa_ctx* c, long npts, const double* lat, const double* lon, const double** dlat, const double** dlon) {
-  const size_t nb = (size_t)npts * sizeof(double);
-  EFA_TRY(c->letkf_pts.reserve(2 * nb));
-  double* d = c->letkf_pts.as<double>();
-  EFA_HIP(hipMemcpyAsync(d, lat, nb, hipMemcpyHostToDevice, c->stream));
-  EFA_HIP(hipMemcpyAsync(d + npts, lon, nb, hipMemcpyHostToDevice, c->stream));
-  EFA_HIP(hipStreamSynchronize(c->stream));  // the caller may reuse its arrays on return
-  *dlat = d;
-  *dlon = d + npts;
-  return EFA_OK;
-}
-
-LetkfArgs letkf_args(int M, long npts, const LetkfLists& l, const double* Yp, const LetkfObs& o) {
-  LetkfArgs a{};
-  a.npts = npts;
-  a.n_lead = 1;
-  a.M = M;
-  a.off = l.off;
-  a.cnt = l.cnt;
-  a.order = l.order;
-  a.idx = l.idx;
-  a.wts = l.wts;
-  a.Yp = Yp;
-  a.dr = o.dr;
-  a.relax_kind = EFA_RELAX_NONE;
-  return a;
-}
-
-// the solve at `npts` points whose lists are built: [T | w] of each to Tw, the statistics to stats (or null); does not wait
-int letkf_solve_points(efa_ctx* c, int M, long npts, const LetkfLists& lists, const double* Yp_dev, const LetkfObs& o, double* Tw,
-                       double* stats) {
-  LetkfArgs a = letkf_args(M, npts, lists, Yp_dev, o);
-  a.Tw = Tw;
-  a.stats = stats;
-  EFA_HIP(launch_letkf(a, kLetkfWeights, Elem::f64, c->stream));
-  return EFA_OK;
-}
-
-// the mesh of a weight-interpolation call; *out has the strides cut to the axis (a stride beyond it gives the same nodes: the two ends)
-int letkf_check_mesh(const char* who, const LetkfMesh& m, LetkfMesh* out) {
-  if (m.ny < 1 || m.nx < 1) return fail(EFA_ERR_INVALID, "%s: the grid's shape (%ld, %ld) must be positive", who, m.ny, m.nx);
-  if (m.ny > 0x7FFFFFF0L / m.nx) return fail(EFA_ERR_INVALID, "%s: %ld x %ld columns exceed the launch grid", who, m.ny, m.nx);
-  if (m.sy < 1 || m.sx < 1) return fail(EFA_ERR_INVALID, "%s: the weight stride (%ld, %ld) must be >= 1 on both axes", who, m.sy, m.sx);
-  *out = m;
-  const long cy = m.ny > 2 ? m.ny - 1 : 1, cx = m.nx > 2 ? m.nx - 1 : 1;
-  if (out->sy > cy) out->sy = cy;
-  if (out->sx > cx) out->sx = cx;
-  return EFA_OK;
-}
-
-// the member rows of a state call: pointers, alignment, overlap, and rows == n_lead * ncol
-int letkf_check_rows(const char* who, const StateRows& r, long ncol, long n_lead) {
-  if (r.rows < 0) return fail(EFA_ERR_INVALID, "%s: negative row count", who);
-  if (r.rows == 0) return EFA_OK;
-  if (!r.prior || !r.post) return fail(EFA_ERR_INVALID, "%s: null state pointer", who);
-  if (r.elem == Elem::f32 && ((reinterpret_cast<uintptr_t>(r.prior) | reinterpret_cast<uintptr_t>(r.post)) & 3u) != 0)
-    return fail(EFA_ERR_INVALID, "%s: state pointers must be 4-byte aligned", who);
-  if (r.partial_overlap())
-    return fail(EFA_ERR_INVALID, "%s: the posterior rows overlap the prior rows without coinciding with them (in place means the same "
-                "address: a column's rows are read and written by its own workgroup only)", who);
-  if (n_lead < 1 || ncol < 1 || r.rows != n_lead * ncol)
-    return fail(EFA_ERR_INVALID, "%s: rows=%ld is not n_lead=%ld times the grid's %ld columns", who, r.rows, n_lead, ncol);
-  return EFA_OK;
-}
-
-// the interpolate-and-apply launch of the cycle and of efa_letkf_interp_apply_dev, under the context's relaxation; does not wait
-int letkf_interp_launch(efa_ctx* c, const char* who, Elem elem, int M, const void* X_dev, void* post_dev, const LetkfMesh& nodes,
-                        long n_lead, const double* Tw, const double* stats, const LetkfGroups* grp = nullptr) {
-  LetkfInterpSlabArgs a{};
-  a.mesh = nodes;
-  a.n_lead = n_lead;
-  a.M = M;
-  a.Xin = X_dev;
-  a.Xout = post_dev;
-  a.Tw = Tw;
-  a.stats = stats;
-  a.relax_kind = c->relax_kind;
-  a.relax_alpha = c->relax_alpha;
-  if (grp) {
-    a.ngroups = grp->ngroups;
-    a.grp_off = grp->grp_off;
-    a.grp_leads = grp->grp_leads;
-    EFA_HIP(launch_letkf_interp_slab(a, elem, c->stream));
-    return EFA_OK;
-  }
-  EFA_HIP(launch_letkf_interp(static_cast<const LetkfInterpArgs&>(a), elem, c->stream));
-  return EFA_OK;
-}
-
-// ---- the slab groups --------------------------------------------------------------------------------------------
-// Slabs whose factors agree for every ob share one solve.  Decided here from the host copies of the two settings, without the
-// table: the key of slab s is the bit pattern of lead_vert[s], lead_time[s] and lead_var[s], each only while that part can give a
-// factor other than 1 (some ob carries vertical information; some ob has a time and a temporal half-width; some ob's impact row
-// has an entry other than 1).  Equal keys imply equal columns of S.  Groups are numbered by first appearance; cached on the
-// settings' serials, the device copy uploaded once per change.
-uint64_t letkf_key_bits(double v) {
-  if (v != v) return ~(uint64_t)0;  // every NaN is "no coordinate"
-  uint64_t b;
-  std::memcpy(&b, &v, sizeof b);
-  return b;
-}
-
-int letkf_groups(efa_ctx* c, long n_lead) {
-  if (c->lg_vl_serial == c->vl_serial && c->lg_sl_serial == c->sl_serial && (long)c->lg_group_of.size() == n_lead &&
-      c->lg_ptr == c->lg_dev.p && c->lg_dev.p)
-    return EFA_OK;
-  const bool vert = vl_active(c);
-  bool temporal = false, variable = false;
-  const double* lt = nullptr;
-  const int* lvar = nullptr;
-  if (c->sl_on) {
-    const long P = c->sl_P, nv = c->sl_nvar, ng = c->sl_ngroup;
-    const double* d = c->sl_host.data();
-    const int* iv = reinterpret_cast<const int*>(d + c->sl_nlead + 2 * P + ng * nv);
-    lt = d;
-    lvar = iv;
-    for (long k = 0; k < P && !temporal; ++k) temporal = d[c->sl_nlead + k] == d[c->sl_nlead + k] && d[c->sl_nlead + P + k] == d[c->sl_nlead + P + k];
-    for (long k = 0; k < P && !variable; ++k) {
-      const int g = iv[c->sl_nlead + k];
-      if (g < 0) continue;
-      for (long u = 0; u < nv && !variable; ++u) variable = d[c->sl_nlead + 2 * P + g * nv + u] != 1.0;
-    }
-  }
-  std::map<std::tuple<uint64_t, uint64_t, int>, int> seen;
-  std::vector<int> group_of((size_t)n_lead), rep;
-  for (long sidx = 0; sidx < n_lead; ++sidx) {
-    const auto key = std::make_tuple(vert ? letkf_key_bits(c->vl_host[sidx]) : (uint64_t)0, temporal ? letkf_key_bits(lt[sidx]) : (uint64_t)0,
-                                     variable ? lvar[sidx] : 0);
-    auto it = seen.find(key);
-    if (it == seen.end()) {
-      it = seen.emplace(key, (int)rep.size()).first;
-      rep.push_back((int)sidx);
-    }
-    group_of[sidx] = it->second;
-  }
-  const int ng = (int)rep.size();
-  std::vector<int> h((size_t)(2 * ng + 1 + n_lead));  // rep | grp_off | grp_leads
-  std::vector<int> count((size_t)ng, 0);
-  for (long sidx = 0; sidx < n_lead; ++sidx) count[group_of[sidx]]++;
-  for (int g = 0; g < ng; ++g) {
-    h[g] = rep[g];
-    h[ng + g + 1] = h[ng + g] + count[g];
-  }
-  std::vector<int> fill((size_t)ng, 0);
-  for (long sidx = 0; sidx < n_lead; ++sidx) {
-    const int g = group_of[sidx];
-    h[2 * ng + 1 + h[ng + g] + fill[g]++] = (int)sidx;
-  }
-  EFA_TRY(c->lg_dev.reserve(h.size() * sizeof(int)));
-  EFA_HIP(hipMemcpyAsync(c->lg_dev.p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  EFA_HIP(hipStreamSynchronize(c->stream));  // (h goes out of scope)
-  c->lg_group_of.swap(group_of);
-  c->lg_ngroups = ng;
-  c->lg_vl_serial = c->vl_serial;
-  c->lg_sl_serial = c->sl_serial;
-  c->lg_ptr = c->lg_dev.p;
-  return EFA_OK;
-}
-
-// the table and the groups of a slab call, as the kernels take them (the settings were checked for this P and n_lead)
-int letkf_slab_groups(efa_ctx* c, long n_lead, LetkfGroups* out) {
-  EFA_TRY(ensure_slab_table(c));
-  EFA_TRY(letkf_groups(c, n_lead));
-  const int* d = c->lg_dev.as<int>();
-  const int ng = c->lg_ngroups;
-  *out = LetkfGroups{ng, n_lead, c->sl_tab.as<double>(), d, d + ng, d + 2 * ng + 1};
-  return EFA_OK;
-}
-
-// the node solve of the slab calls: [T | w] of every (group, point) to Tw, the statistics [group][point][3]; does not wait
-int letkf_solve_points_slab(efa_ctx* c, int M, long npts, const LetkfLists& lists, const double* Yp_dev, const LetkfObs& o,
-                            const LetkfGroups& grp, double* Tw, double* stats) {
-  LetkfSlabArgs a{};
-  static_cast<LetkfArgs&>(a) = letkf_args(M, npts, lists, Yp_dev, o);
-  a.grp = grp;
-  a.Tw = Tw;
-  a.stats = stats;
-  EFA_HIP(launch_letkf_slab(a, kLetkfWeights, Elem::f64, c->stream));
-  return EFA_OK;
-}
-
-}  // namespace
-
-int letkf_cycle(efa_ctx* c, Elem elem, long rows, int M, long P, const void* X_dev, void* post_dev, double* ym_dev, double* Yp_dev,
-                int obs_block_out, const double* ob_value, const double* ob_error, const uint8_t* ob_assim, const double* ob_lat,
-                const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
-                double* prior_mean, double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated, double* col_stats_dev,
-                const LetkfMesh* mesh, bool slab) {
-  const bool f32 = elem == Elem::f32;
-  const char* who = slab ? (mesh ? (f32 ? "efa_letkf_slab_cycle_interp_f32_dev" : "efa_letkf_slab_cycle_interp_dev")
-                                 : (f32 ? "efa_letkf_slab_cycle_f32_dev" : "efa_letkf_slab_cycle_dev"))
-                         : (mesh ? (f32 ? "efa_letkf_cycle_interp_f32_dev" : "efa_letkf_cycle_interp_dev")
-                                 : (f32 ? "efa_letkf_cycle_f32_dev" : "efa_letkf_cycle_dev"));
-  EFA_TRY(letkf_check_settings(c, who, M, P, slab, n_lead));
-  LetkfMesh nodes{};
-  if (mesh) {
-    EFA_TRY(letkf_check_mesh(who, *mesh, &nodes));
-    ncol = nodes.ncol();
-    if (mesh->unit()) mesh = nullptr;  // every column is a node: the plain call, bit for bit (col_stats_dev: the nodes are the columns)
-  }
-  if (rows < 0) return fail(EFA_ERR_INVALID, "%s: negative row count", who);
-  const StateRows r{X_dev, post_dev, elem, rows, M};
-  if (rows > 0) {
-    if (!X_dev || !post_dev) return fail(EFA_ERR_INVALID, "%s: null state pointer", who);
-    if (f32 && ((reinterpret_cast<uintptr_t>(X_dev) | reinterpret_cast<uintptr_t>(post_dev)) & 3u) != 0)
-      return fail(EFA_ERR_INVALID, "%s: state pointers must be 4-byte aligned", who);
-    if (r.partial_overlap())
-      return fail(EFA_ERR_INVALID, "%s: the posterior rows overlap the prior rows without coinciding with them (in place means the same "
-                  "address: a column's rows are read and written by its own workgroup only)", who);
-    EFA_TRY(check_grid(EFA_LOC_GC, grid_lat, grid_lon, ncol, n_lead, rows));
-  }
-  EFA_TRY(letkf_check_obs(who, P, ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_hw));
-  hipStream_t s = c->stream;
-  harvest_obs_ms(c);
-  harvest_state_ms(c);
-  c->obs_ms = c->state_ms = 0.0;
-  c->state_launches = 0;
-  c->phase_a_kind = slab ? (mesh ? 9 : 8) : (mesh ? 7 : 6);
-  c->path_taken = EFA_PATH_TRANSFORM;
-  if (c->timing) EFA_HIP(hipEventRecord(c->obs_iv.begin, s));
-
-  // ---- the obs: flags and prior diagnostics, then the obs block as P more one-row columns, each solved at its own position ------
-  LetkfObs o;
-  LetkfLists lists;
-  double *Yw = nullptr, *ymw = nullptr;
-  if (P > 0) {
-    EFA_TRY(letkf_stage_obs(c, M, P, ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_hw, &o));
-    EFA_TRY(c->letkf_Yw.reserve(((size_t)P * M + (size_t)P) * sizeof(double)));
-    Yw = c->letkf_Yw.as<double>();
-    ymw = Yw + (size_t)P * M;
-    EFA_TRY(letkf_build_lists(c, P, o.lat, o.lon, o, &lists));
-    if (slab) {  // the obs-obs factors F(j, k) into the lists' tapers; the perturbation-form launch then runs as it is, one group
-      const bool vert = vl_active(c);
-      const SlabObs so = sl_active(c) ? sl_obs(c, 0) : SlabObs{};
-      EFA_HIP(launch_letkf_obs_factor(P, lists.off, lists.cnt, lists.idx, c->letkf_wts.as<double>(), vert ? vl_obvert(c) : nullptr,
-                                      vert ? vl_obvhw(c) : nullptr, sl_active(c) ? &so : nullptr, s));
-    }
-    LetkfArgs a = letkf_args(M, P, lists, Yp_dev, o);
-    a.ym_in = ym_dev;
-    a.Yp_in = Yp_dev;
-    a.ym_out = ymw;
-    a.Yp_out = Yw;
-    EFA_HIP(launch_letkf(a, kLetkfPerts, Elem::f64, s));
-    EFA_HIP(launch_etkf_post(P, M, Yw, ymw, o.post_mean, o.post_var, s));
-  }
-  // ---- the state: the grid's lists (the obs' are consumed: the stream is in order), then ONE launch -----------------------------
-  //      (with a mesh: the nodes' lists, then the node solve and the interpolate-and-apply launch)
-  LetkfLists glists;
-  const long nnodes = mesh ? nodes.nnodes() : 0;
-  double* node_stats = col_stats_dev;
-  LetkfGroups grp{};
-  if (rows > 0 && slab) EFA_TRY(letkf_slab_groups(c, n_lead, &grp));
-  const size_t ngr = slab ? (size_t)grp.ngroups : 1;  // solves per column or node
-  if (rows > 0 && mesh) {
-    if (c->letkf_Tw.reserve(ngr * (size_t)nnodes * M * (M + 1) * sizeof(double)) != EFA_OK)
-      return fail(EFA_ERR_ALLOC, "%s: the node-pair buffer of %zu groups x %ld nodes x %d x %d doubles could not be allocated", who, ngr,
-                  nnodes, M, M + 1);
-    if (!node_stats) {  // the apply reads n_local of every node
-      EFA_TRY(c->letkf_nst.reserve(3 * ngr * (size_t)nnodes * sizeof(double)));
-      node_stats = c->letkf_nst.as<double>();
-    }
-  }
-  if (rows > 0 && P > 0) {
-    if (mesh) {  // a node is a grid column: its position is that column's
-      std::vector<double> h(2 * (size_t)nnodes);
-      const long nyn = nodes.nyn(), nxn = nodes.nxn();
-      for (long jy = 0; jy < nyn; ++jy)
-        for (long jx = 0; jx < nxn; ++jx) {
-          const long col = LetkfMesh::axis_node(jy, nodes.ny, nodes.sy) * nodes.nx + LetkfMesh::axis_node(jx, nodes.nx, nodes.sx);
-          h[jy * nxn + jx] = grid_lat[col];
-          h[nnodes + jy * nxn + jx] = grid_lon[col];
-        }
-      const double *dlat = nullptr, *dlon = nullptr;
-      EFA_TRY(letkf_upload_points(c, nnodes, h.data(), h.data() + nnodes, &dlat, &dlon));
-      EFA_TRY(letkf_build_lists(c, nnodes, dlat, dlon, o, &glists));
-    } else {
-      EFA_TRY(c->grid.upload(s, grid_lat, grid_lon, ncol));
-      EFA_TRY(letkf_build_lists(c, ncol, c->grid.lat.as<double>(), c->grid.lon.as<double>(), o, &glists));
-    }
-  }
-  if (c->timing) {
-    EFA_HIP(hipEventRecord(c->obs_iv.end, s));
-    c->obs_ends_at = c->obs_iv.end;
-    c->obs_iv.pending = true;
-    EFA_HIP(hipEventRecord(c->state_iv[0].begin, s));
-  }
-  if (rows > 0 && mesh && slab) {
-    EFA_TRY(letkf_solve_points_slab(c, M, nnodes, glists, Yp_dev, o, grp, c->letkf_Tw.as<double>(), node_stats));
-    EFA_TRY(letkf_interp_launch(c, who, elem, M, X_dev, post_dev, nodes, n_lead, c->letkf_Tw.as<double>(), node_stats, &grp));
-    c->state_launches = 2;
-  } else if (rows > 0 && slab) {
-    LetkfSlabArgs a{};
-    static_cast<LetkfArgs&>(a) = letkf_args(M, ncol, glists, Yp_dev, o);
-    a.grp = grp;
-    a.n_lead = n_lead;
-    a.Xin = X_dev;
-    a.Xout = post_dev;
-    a.stats = col_stats_dev;
-    a.relax_kind = c->relax_kind;
-    a.relax_alpha = c->relax_alpha;
-    EFA_HIP(launch_letkf_slab(a, kLetkfMembers, elem, s));
-    c->state_launches = 1;
-  } else if (rows > 0 && mesh) {  // (P == 0: no lists, every node has the pair (I, 0) and no column changes)
-    EFA_TRY(letkf_solve_points(c, M, nnodes, glists, Yp_dev, o, c->letkf_Tw.as<double>(), node_stats));
-    EFA_TRY(letkf_interp_launch(c, who, elem, M, X_dev, post_dev, nodes, n_lead, c->letkf_Tw.as<double>(), node_stats));
-    c->state_launches = 2;
-  } else if (rows > 0) {
-    LetkfArgs a = letkf_args(M, ncol, glists, Yp_dev, o);  // (P == 0: no lists, every column keeps its rows)
-    a.n_lead = n_lead;
-    a.Xin = X_dev;
-    a.Xout = post_dev;
-    a.stats = col_stats_dev;
-    a.relax_kind = c->relax_kind;
-    a.relax_alpha = c->relax_alpha;
-    EFA_HIP(launch_letkf(a, kLetkfMembers, elem, s));
-    c->state_launches = 1;
-  }
-  if (c->timing) {
-    EFA_HIP(hipEventRecord(c->state_iv[0].end, s));
-    c->state_iv[0].pending = true;
-  }
-  c->state_launches_sum += c->state_launches;
-  // ---- the posterior obs block to the caller, behind every solve that read the prior one; the diagnostics ----------------------
-  std::vector<char> hd;
-  if (P > 0) {
-    if (obs_block_out) {
-      EFA_HIP(hipMemcpyAsync(Yp_dev, Yw, (size_t)P * M * sizeof(double), hipMemcpyDeviceToDevice, s));
-      EFA_HIP(hipMemcpyAsync(ym_dev, ymw, (size_t)P * sizeof(double), hipMemcpyDeviceToDevice, s));
-    }
-    hd.resize(o.diag_bytes());
-    EFA_HIP(hipMemcpyAsync(hd.data(), o.prior_mean, hd.size(), hipMemcpyDeviceToHost, s));
-  }
-  EFA_HIP(hipStreamSynchronize(s));
-  if (P > 0) {
-    const size_t dP = (size_t)P * sizeof(double);
-    const double* pm = reinterpret_cast<const double*>(hd.data() + 2 * dP);
-    const double* pv = reinterpret_cast<const double*>(hd.data() + 3 * dP);
-    const uint8_t* as = reinterpret_cast<const uint8_t*>(hd.data() + 4 * dP);
-    if (prior_mean) std::memcpy(prior_mean, hd.data(), dP);
-    if (prior_var) std::memcpy(prior_var, hd.data() + dP, dP);
-    for (long k = 0; k < P; ++k) {
-      if (assimilated) assimilated[k] = as[k];
-      if (as[k]) {
-        if (post_mean) post_mean[k] = pm[k];
-        if (post_var) post_var[k] = pv[k];
-      }
-    }
-  }
-  if (c->timing == 1) {
-    harvest_obs_ms(c);
-    harvest_state_ms(c);
-  }
-  return EFA_OK;
-}
-
-int letkf_weights(efa_ctx* c, int M, long P, const double* ym_dev, const double* Yp_dev, const double* ob_value, const double* ob_error,
-                  const uint8_t* ob_assim, const double* ob_lat, const double* ob_lon, const double* ob_hw, long npts,
-                  const double* pt_lat, const double* pt_lon, double* Tw_dev, double* stats_dev, bool slab) {
-  const char* who = slab ? "efa_letkf_slab_weights_dev" : "efa_letkf_weights_dev";
-  const long n_lead = c->sl_on ? c->sl_nlead : c->vl_nlead;  // (slab: the slabs are the settings' own)
-  EFA_TRY(letkf_check_settings(c, who, M, P, slab, slab ? n_lead : -1));
-  if (npts < 0) return fail(EFA_ERR_INVALID, "%s: negative point count", who);
-  if (npts > 0 && (!pt_lat || !pt_lon || !Tw_dev)) return fail(EFA_ERR_INVALID, "%s: null point or output array", who);
-  EFA_TRY(letkf_check_obs(who, P, ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_hw));
-  if (npts == 0) return EFA_OK;
-  hipStream_t s = c->stream;
-  LetkfObs o;
-  LetkfLists lists;
-  if (P > 0) {
-    const double *dlat = nullptr, *dlon = nullptr;
-    EFA_TRY(letkf_stage_obs(c, M, P, ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_hw, &o));
-    EFA_TRY(letkf_upload_points(c, npts, pt_lat, pt_lon, &dlat, &dlon));
-    EFA_TRY(letkf_build_lists(c, npts, dlat, dlon, o, &lists));
-  }
-  if (slab) {
-    LetkfGroups grp{};
-    EFA_TRY(letkf_slab_groups(c, n_lead, &grp));
-    EFA_TRY(letkf_solve_points_slab(c, M, npts, lists, Yp_dev, o, grp, Tw_dev, stats_dev));
-  } else {
-    EFA_TRY(letkf_solve_points(c, M, npts, lists, Yp_dev, o, Tw_dev, stats_dev));
-  }
-  EFA_HIP(hipStreamSynchronize(s));
-  return EFA_OK;
-}
-
-int letkf_slab_group_table(efa_ctx* c, long n_lead, int* group_of, int* ngroups) {
-  const char* who = "efa_letkf_slab_groups";
-  if (!c->vl_on && !c->sl_on) return fail(EFA_ERR_INVALID, "%s: neither vertical nor slab localisation is set", who);
-  if ((c->vl_on && c->vl_nlead != n_lead) || (c->sl_on && c->sl_nlead != n_lead))
-    return fail(EFA_ERR_INVALID, "%s: the settings are not sized for n_lead=%ld", who, n_lead);
-  if (c->vl_on && c->sl_on && c->vl_P != c->sl_P)
-    return fail(EFA_ERR_INVALID, "%s: the vertical and the slab setting are sized for %ld and %ld observations", who, c->vl_P, c->sl_P);
-  EFA_TRY(letkf_groups(c, n_lead));
-  if (group_of) std::memcpy(group_of, c->lg_group_of.data(), (size_t)n_lead * sizeof(int));
-  if (ngroups) *ngroups = c->lg_ngroups;
-  return EFA_OK;
-}
-
-int letkf_interp_apply(efa_ctx* c, Elem elem, long rows, int M, const void* X_dev, void* post_dev, long ny, long nx, long stride_y,
-                       long stride_x, long n_lead, const double* Tw_nodes_dev, const double* node_stats_dev) {
-  const bool f32 = elem == Elem::f32;
-  const char* who = f32 ? "efa_letkf_interp_apply_f32_dev" : "efa_letkf_interp_apply_dev";
-  EFA_TRY(letkf_check_settings(c, who, M, 0));
-  LetkfMesh nodes{};
-  EFA_TRY(letkf_check_mesh(who, LetkfMesh{ny, nx, stride_y, stride_x}, &nodes));
-  EFA_TRY(letkf_check_rows(who, StateRows{X_dev, post_dev, elem, rows, M}, nodes.ncol(), n_lead));
-  if (rows == 0) return EFA_OK;
-  if (!Tw_nodes_dev) return fail(EFA_ERR_INVALID, "%s: null node pairs", who);
-  EFA_TRY(letkf_interp_launch(c, who, elem, M, X_dev, post_dev, nodes, n_lead, Tw_nodes_dev, node_stats_dev));
-  EFA_HIP(hipStreamSynchronize(c->stream));
-  return EFA_OK;
-}
-
-}  // namespace efa_host

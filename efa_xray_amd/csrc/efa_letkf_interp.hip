@@ -24,6 +24,8 @@
 //                 row before it stores any of it, and no other wave or workgroup touches its rows: post == X is safe.
 // KMAX is the number of MFMA k-steps a row may take, 2 ceil(M/8) <= KMAX: the register class of the instantiation.
 // Same inputs, same bits: every reduction has a fixed order, there are no atomics.
+// This file holds the kernel and its launcher (plain, or per slab group with LetkfGroups); the driver that runs the node solve and
+// then this launch is efa_letkf_driver.hip.
 #include "efa_driver.h"
 #include "efa_device.h"
 
@@ -36,14 +38,6 @@ typedef float interp_f2 __attribute__((ext_vector_type(2)));
 // pairs at the alignment of their elements (a row of odd M starts on any element; the caller's node pairs on any double)
 typedef interp_v2 interp_v2u __attribute__((aligned(8)));
 typedef interp_f2 interp_f2u __attribute__((aligned(4)));
-
-
-template <typename E>
-__device__ __forceinline__ E interp_round(double v);
-template <>
-__device__ __forceinline__ double interp_round<double>(double v) { return v; }
-template <>
-__device__ __forceinline__ float interp_round<float>(double v) { return (float)v; }
 
 __device__ __forceinline__ interp_v2 interp_load2(const double* p) { return *reinterpret_cast<const interp_v2u*>(p); }
 __device__ __forceinline__ interp_v2 interp_load2(const float* p) {
@@ -92,6 +86,11 @@ __device__ __forceinline__ void interp_load_rows(const E* in, long first, long n
 
 // SLAB: one workgroup per (column, slab group), the group the fastest index; node pairs from Tw[group][node], node
 // statistics from [group][node], a wave's 16 rows gathered from the group's slab list.
+struct LetkfInterpSlabArgs : LetkfInterpArgs {
+  int ngroups;
+  const int* grp_off;
+  const int* grp_leads;
+};
 template <bool SLAB>
 struct InterpArgsOf { typedef LetkfInterpArgs type; };
 template <>
@@ -288,7 +287,7 @@ __global__ __launch_bounds__(NT, interp_waves(KMAX)) void k_letkf_interp(const t
           const int b = 16 * t + nn;
           if (t < T && b < M) {
             const double val = rtps ? base[v] + sc[v] * (acc[t][v] - pm[v]) : xam[v] + acc[t][v];
-            xo[b] = interp_round<E>(val);
+            xo[b] = letkf_round<E>(val);
           }
         }
       }
@@ -300,66 +299,52 @@ __global__ __launch_bounds__(NT, interp_waves(KMAX)) void k_letkf_interp(const t
   }
 }
 
-template <typename E, int KMAX, int NT>
-hipError_t interp_launch_as(const LetkfInterpArgs& a, size_t lds, hipStream_t s) {
-  auto kern = k_letkf_interp<E, KMAX, NT>;
+template <typename E, int KMAX, int NT, bool SLAB>
+hipError_t interp_launch_as(const typename InterpArgsOf<SLAB>::type& a, size_t lds, hipStream_t s) {
+  auto kern = k_letkf_interp<E, KMAX, NT, SLAB>;
   if (lds > 48 * 1024) {
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)a.mesh.ncol()), dim3(NT), lds, s, a);
+  long nwg = a.mesh.ncol();
+  if constexpr (SLAB) nwg *= a.ngroups;
+  hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(NT), lds, s, a);
   return hipGetLastError();
 }
 
-template <typename E>
-hipError_t interp_launch(const LetkfInterpArgs& a, hipStream_t s) {
+template <typename E, bool SLAB>
+hipError_t interp_launch_mode(const typename InterpArgsOf<SLAB>::type& a, hipStream_t s) {
   const size_t lds = letkf_interp_lds_bytes(a.M);
-  if (a.M <= 32) return interp_launch_as<E, 8, 128>(a, lds, s);
-  if (a.M <= 64) return interp_launch_as<E, 16, 128>(a, lds, s);
-  return interp_launch_as<E, 34, 256>(a, lds, s);
+  if (a.M <= 32) return interp_launch_as<E, 8, 128, SLAB>(a, lds, s);
+  if (a.M <= 64) return interp_launch_as<E, 16, 128, SLAB>(a, lds, s);
+  return interp_launch_as<E, 34, 256, SLAB>(a, lds, s);
 }
 
-template <typename E, int KMAX, int NT>
-hipError_t interp_slab_launch_as(const LetkfInterpSlabArgs& a, size_t lds, hipStream_t s) {
-  auto kern = k_letkf_interp<E, KMAX, NT, true>;
-  if (lds > 48 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(a.mesh.ncol() * a.ngroups)), dim3(NT), lds, s, a);
-  return hipGetLastError();
-}
-
+// the plain launch, or with groups the SLAB one on (a, *grp)
 template <typename E>
-hipError_t interp_slab_launch(const LetkfInterpSlabArgs& a, hipStream_t s) {
-  const size_t lds = letkf_interp_lds_bytes(a.M);
-  if (a.M <= 32) return interp_slab_launch_as<E, 8, 128>(a, lds, s);
-  if (a.M <= 64) return interp_slab_launch_as<E, 16, 128>(a, lds, s);
-  return interp_slab_launch_as<E, 34, 256>(a, lds, s);
+hipError_t interp_launch(const LetkfInterpArgs& a, const LetkfGroups* grp, hipStream_t s) {
+  if (!grp) return interp_launch_mode<E, false>(a, s);
+  LetkfInterpSlabArgs sa{};
+  static_cast<LetkfInterpArgs&>(sa) = a;
+  sa.ngroups = grp->ngroups;
+  sa.grp_off = grp->grp_off;
+  sa.grp_leads = grp->grp_leads;
+  return interp_launch_mode<E, true>(sa, s);
 }
 
 }  // namespace
 
 size_t letkf_interp_lds_bytes(int M) { return (size_t)M * (M + 1) * sizeof(double); }
 
-hipError_t launch_letkf_interp(const LetkfInterpArgs& a, Elem elem, hipStream_t s) {
+hipError_t launch_letkf_interp(const LetkfInterpArgs& a, const LetkfGroups* grp, Elem elem, hipStream_t s) {
   const LetkfMesh& m = a.mesh;
   if (a.M < 2 || a.M > kLetkfMaxM || letkf_interp_lds_bytes(a.M) > 160 * 1024) return hipErrorInvalidValue;
+  if (grp && (grp->ngroups < 1 || !grp->grp_off || !grp->grp_leads)) return hipErrorInvalidValue;
   if (m.ny < 1 || m.nx < 1 || m.sy < 1 || m.sx < 1 || m.ny > 0x7FFFFFF0L / m.nx) return hipErrorInvalidValue;
+  if (grp && m.ny * m.nx > 0x7FFFFFF0L / grp->ngroups) return hipErrorInvalidValue;
   if (m.sy > (m.ny > 2 ? m.ny - 1 : 1) || m.sx > (m.nx > 2 ? m.nx - 1 : 1)) return hipErrorInvalidValue;
   if (!a.Xin || !a.Xout || !a.Tw || a.n_lead < 1) return hipErrorInvalidValue;
-  return elem == Elem::f32 ? interp_launch<float>(a, s) : interp_launch<double>(a, s);
-}
-
-hipError_t launch_letkf_interp_slab(const LetkfInterpSlabArgs& a, Elem elem, hipStream_t s) {
-  const LetkfMesh& m = a.mesh;
-  if (a.M < 2 || a.M > kLetkfMaxM || letkf_interp_lds_bytes(a.M) > 160 * 1024) return hipErrorInvalidValue;
-  if (a.ngroups < 1 || !a.grp_off || !a.grp_leads) return hipErrorInvalidValue;
-  if (m.ny < 1 || m.nx < 1 || m.sy < 1 || m.sx < 1 || m.ny > 0x7FFFFFF0L / m.nx || m.ny * m.nx > 0x7FFFFFF0L / a.ngroups)
-    return hipErrorInvalidValue;
-  if (m.sy > (m.ny > 2 ? m.ny - 1 : 1) || m.sx > (m.nx > 2 ? m.nx - 1 : 1)) return hipErrorInvalidValue;
-  if (!a.Xin || !a.Xout || !a.Tw || a.n_lead < 1) return hipErrorInvalidValue;
-  return elem == Elem::f32 ? interp_slab_launch<float>(a, s) : interp_slab_launch<double>(a, s);
+  return elem == Elem::f32 ? interp_launch<float>(a, grp, s) : interp_launch<double>(a, grp, s);
 }
 
 }  // namespace efa

@@ -13,12 +13,11 @@ import _etkf as ek
 import _letkf as lk
 import _letkf_interp as li
 import _outlier as qc
+from _letkf_gpu import TOL, COND_CAP, _reset, _obs_block, _close, _same_bits
 from test_relaxation_host import relax
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-10
-COND_CAP = 1e4
 U = 2.0 ** -53
 # (M, P, ny, nx, n_lead, stride): M below, at and just over a 16-tile and at the cap; ragged last cells; an n_lead that crosses a
 # 16-row tile; a single-node axis; a stride beyond the grid; a unit stride on one axis
@@ -26,19 +25,6 @@ CASES = [(2, 1, 3, 5, 1, (2, 2)), (3, 5, 4, 6, 2, (3, 4)), (16, 64, 5, 7, 3, (2,
          (40, 400, 9, 10, 3, (4, 4)), (80, 300, 5, 6, 2, (2, 5)), (136, 300, 3, 6, 1, (2, 3)), (16, 64, 1, 7, 2, (3, 3)),
          (16, 64, 5, 7, 2, (8, 8)), (16, 64, 5, 7, 2, (1, 3))]
 F32_CASE = (17, 33, 5, 7, 17, (4, 2))
-
-
-def _reset(ctx):
-    from efa_xray_amd import _lib
-    ctx.set_outlier_threshold(None)
-    ctx.set_vertical_localization(None)
-    ctx.set_slab_localization(None)
-    ctx.set_sampling_error_correction(None)
-    ctx.set_adaptive_inflation(None)
-    ctx.set_relaxation(_lib.RELAX_NONE, 0.0)
-    for key, v in (("path", 0), ("gram", 2), ("pipeline", 1), ("gc_onepass", 1), ("obs_solver", 0)):
-        ctx.set_option(key, v)
-    return ctx
 
 
 @pytest.fixture
@@ -73,16 +59,6 @@ def _model(M, P, ny, nx, n_lead, stride, seed=0, hw=(300.0, 3000.0)):
     return _run_model(_case(M, P, ny, nx, n_lead, seed, hw), stride)
 
 
-def _obs_block(ctx, HX, M):
-    P = HX.shape[0]
-    if P == 0:
-        return ctx.empty((1,)), ctx.empty((1, M)), np.zeros(0), np.zeros((0, M))
-    Yp = ctx.to_device(np.ascontiguousarray(HX))
-    ym = ctx.empty((P,))
-    ctx.form_perts(P, M, Yp, ym, Yp)
-    return ym, Yp, ym.download(), Yp.download()
-
-
 def _nnodes(ny, nx, stride):
     return li.axis_nodes(ny, stride[0]).size * li.axis_nodes(nx, stride[1]).size
 
@@ -107,22 +83,6 @@ def _cycle(ctx, c, stride=None, in_place=False, f32=False, X=None, shape=None, *
     diag = ctx.letkf_cycle(N, M, P, Xd, post, ym, Yp, g["value"], g["error"], g["assim"], g["ob_lat"], g["ob_lon"], g["ob_hw"],
                            g["grid_lat"], g["grid_lon"], g["n_lead"], obs_block_out=True, col_stats=stats, f32=f32, **kw)
     return dict(post=post.download(), ym=ym.download()[:P], Yp=Yp.download()[:P], diag=diag, stats=stats.download())
-
-
-def _close(got, want, what, tol=TOL):
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    scale = np.max(np.abs(want)) if want.size else 0.0
-    err = np.max(np.abs(got - want)) if want.size else 0.0
-    print("%s: max abs err %.3e, scale %.3e" % (what, err, scale))
-    assert np.all(np.isfinite(got)), what + ": not finite"
-    assert err <= tol * max(scale, np.finfo(float).tiny), "%s: %.3e > %g * %.3e" % (what, err, tol, scale)
-
-
-def _same_bits(a, b, what, keys=("post", "ym", "Yp", "stats")):
-    for k in keys:
-        assert np.array_equal(a[k], b[k], equal_nan=True), "%s: %s differs" % (what, k)
-    for k in ("prior_mean", "prior_var", "post_mean", "post_var", "assimilated"):
-        assert np.array_equal(np.asarray(a["diag"][k]), np.asarray(b["diag"][k]), equal_nan=True), "%s: %s differs" % (what, k)
 
 
 def _rows(c, cols):

@@ -12,30 +12,15 @@ import pytest
 import _letkf as lk
 import _letkf_slab as ls
 import _outlier as qc
+from _letkf_gpu import TOL, SWEEP_CAP, COND_CAP, _reset, _obs_block, _close, _check_diag, _same_bits
 from test_relaxation_host import relax
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-10
-SWEEP_CAP = 30
-COND_CAP = 1e4
 # (M, P, ny, nx, nvars, ntimes)
 SIZES = [(2, 1, 3, 5, 1, 2), (3, 5, 3, 5, 2, 2), (16, 64, 5, 7, 2, 3), (17, 33, 5, 7, 3, 3), (40, 400, 6, 7, 2, 3), (80, 300, 5, 6, 2, 2),
          (136, 300, 3, 6, 1, 2)]
 MID = (16, 64, 5, 7, 2, 3)
-
-
-def _reset(ctx):
-    from efa_xray_amd import _lib
-    ctx.set_outlier_threshold(None)
-    ctx.set_vertical_localization(None)
-    ctx.set_slab_localization(None)
-    ctx.set_sampling_error_correction(None)
-    ctx.set_adaptive_inflation(None)
-    ctx.set_relaxation(_lib.RELAX_NONE, 0.0)
-    for key, v in (("path", 0), ("gram", 2), ("pipeline", 1), ("gc_onepass", 1), ("obs_solver", 0)):
-        ctx.set_option(key, v)
-    return ctx
 
 
 @pytest.fixture
@@ -82,16 +67,6 @@ def _set(ctx, c, loc=None):
     ctx.set_slab_localization(n_lead, P, **kw)
 
 
-def _obs_block(ctx, HX, M):
-    P = HX.shape[0]
-    if P == 0:
-        return ctx.empty((1,)), ctx.empty((1, M)), np.zeros(0), np.zeros((0, M))
-    Yp = ctx.to_device(np.ascontiguousarray(HX))
-    ym = ctx.empty((P,))
-    ctx.form_perts(P, M, Yp, ym, Yp)
-    return ym, Yp, ym.download(), Yp.download()
-
-
 def _cycle(ctx, c, in_place=False, f32=False, X=None, stride=None, plain=False, ngroups=None, **over):
     """efa_letkf_slab_cycle_dev (or the plain call): dict of posterior, obs block, diagnostics, statistics (ngroups, npts, 3)."""
     g = dict(c, **over)
@@ -125,33 +100,6 @@ def _probe(ctx, c, **over):
     ym, Yp, _, _ = _obs_block(ctx, g["HX"], M)
     return ctx.letkf_slab_weights(M, P, ym, Yp, g["value"], g["error"], g["assim"], g["ob_lat"], g["ob_lon"], g["ob_hw"], g["grid_lat"],
                                   g["grid_lon"], g["n_lead"])
-
-
-def _close(got, want, what, tol=TOL):
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    scale = np.max(np.abs(want)) if want.size else 0.0
-    err = np.max(np.abs(got - want)) if want.size else 0.0
-    print("%s: max abs err %.3e, scale %.3e" % (what, err, scale))
-    assert np.all(np.isfinite(got)), what + ": not finite"
-    assert err <= tol * max(scale, np.finfo(float).tiny), "%s: %.3e > %g * %.3e" % (what, err, tol, scale)
-
-
-def _check_diag(diag, ref, what):
-    a = np.asarray(ref["assimilated"], bool)
-    assert np.array_equal(np.asarray(diag["assimilated"], bool), a), what + ": assimilated"
-    _close(diag["prior_mean"], ref["prior_mean"], what + " prior_mean")
-    _close(diag["prior_var"], ref["prior_var"], what + " prior_var")
-    if a.any():
-        _close(np.asarray(diag["post_mean"])[a], ref["post_mean"][a], what + " post_mean")
-        _close(np.asarray(diag["post_var"])[a], ref["post_var"][a], what + " post_var")
-    assert np.all(np.isnan(np.asarray(diag["post_mean"])[~a])), what + ": post_mean written for an ob that is not assimilated"
-
-
-def _same_bits(a, b, what, keys=("post", "ym", "Yp", "stats")):
-    for k in keys:
-        assert np.array_equal(a[k], b[k], equal_nan=True), "%s: %s differs" % (what, k)
-    for k in ("prior_mean", "prior_var", "post_mean", "post_var", "assimilated"):
-        assert np.array_equal(np.asarray(a["diag"][k]), np.asarray(b["diag"][k]), equal_nan=True), "%s: %s differs" % (what, k)
 
 
 def _check_stats(stats, st, what):
