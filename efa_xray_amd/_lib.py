@@ -728,14 +728,10 @@ class Context(object):
         glat, glon, gcol = self._grid(loc_mode, grid_lat, grid_lon)
         if loc_mode == LOC_GC:
             assert gcol == ncol
-        d = self._diag_arrays(P)
-        _check(self.lib, fn(
-            self.handle, n_seg, ctypes.cast(pin, c_void_pp), ctypes.cast(pout, c_void_pp), slabs, int(ncol), int(M), P,
+        return self._diagnosed(
+            P, fn, self.handle, n_seg, ctypes.cast(pin, c_void_pp), ctypes.cast(pout, c_void_pp), slabs, int(ncol), int(M), P,
             _dp(HX) if P else None, int(chunk_cols), _dp(val), _dp(err), _u8p(asm), loc_mode, _dp(lat), _dp(lon), _dp(hw),
-            _dp(glat), _dp(glon), _dp(d["prior_mean"]), _dp(d["prior_var"]), _dp(d["post_mean"]), _dp(d["post_var"]),
-            _u8p(d["assimilated"])))
-        d["assimilated"] = d["assimilated"].astype(bool)
-        return d
+            _dp(glat), _dp(glon))
 
     def stream_stats(self):
         """The read-only options about the last streamed update."""
@@ -828,18 +824,32 @@ class Context(object):
         assert glat.shape == glon.shape
         return glat, glon, glat.shape[0]
 
+    @classmethod
+    def _columns(cls, loc_mode, grid_lat, grid_lon, rows, n_lead):
+        """(glat, glon, ncol, n_lead) as the library takes them: the flattened grid and the slabs per column under the GC taper;
+        without localisation every row is its own column.  loc_mode None: GC when a grid is given."""
+        if loc_mode is None:
+            loc_mode = LOC_GC if grid_lat is not None else LOC_NONE
+        glat, glon, ncol = cls._grid(loc_mode, grid_lat, grid_lon)
+        if loc_mode == LOC_NONE:
+            ncol, n_lead = rows, 1
+        return glat, glon, ncol, n_lead
+
+    def _diagnosed(self, P, entry, *args, tail=()):
+        """entry(*args, <the five diagnostics>, *tail) on fresh diagnostics [P]; returns them as a dict, `assimilated` as bool."""
+        d = self._diag_arrays(P)
+        _check(self.lib, entry(*(args + (_dp(d["prior_mean"]), _dp(d["prior_var"]), _dp(d["post_mean"]), _dp(d["post_var"]),
+                                         _u8p(d["assimilated"])) + tail)))
+        d["assimilated"] = d["assimilated"].astype(bool)
+        return d
+
     def obs_phase(self, M, P, ym, Yp, ob_value, ob_error, ob_assim, loc_mode=LOC_NONE,
                   ob_lat=None, ob_lon=None, ob_halfwidth=None):
         """Phase A.  Returns the per-ob diagnostics dict."""
         val, err, asm, lat, lon, hw = self._ob_arrays(P, ob_value, ob_error, ob_assim, loc_mode,
                                                       ob_lat, ob_lon, ob_halfwidth)
-        d = self._diag_arrays(P)
-        _check(self.lib, self.lib.efa_obs_phase_dev(
-            self.handle, M, P, self._addr(ym), self._addr(Yp), _dp(val), _dp(err), _u8p(asm), loc_mode,
-            _dp(lat), _dp(lon), _dp(hw), _dp(d["prior_mean"]), _dp(d["prior_var"]), _dp(d["post_mean"]),
-            _dp(d["post_var"]), _u8p(d["assimilated"])))
-        d["assimilated"] = d["assimilated"].astype(bool)
-        return d
+        return self._diagnosed(P, self.lib.efa_obs_phase_dev, self.handle, M, P, self._addr(ym), self._addr(Yp), _dp(val), _dp(err),
+                               _u8p(asm), loc_mode, _dp(lat), _dp(lon), _dp(hw))
 
     def etkf_solution(self, M):
         """efa_etkf_solution: the batch solve of the last obs phase, which must have run with option "obs_solver" 1,
@@ -855,30 +865,21 @@ class Context(object):
                     chi2=float(stats[3]), sweeps=int(sweeps.value))
 
     def state_phase(self, rows, M, xm_in, Xp_in, xm_out, Xp_out, grid_lat=None, grid_lon=None, n_lead=1):
-        loc_mode = LOC_GC if grid_lat is not None else LOC_NONE
-        glat, glon, ncol = self._grid(loc_mode, grid_lat, grid_lon)
-        if loc_mode == LOC_NONE:
-            ncol, n_lead = rows, 1
+        glat, glon, ncol, n_lead = self._columns(None, grid_lat, grid_lon, rows, n_lead)
         _check(self.lib, self.lib.efa_state_phase_dev(
             self.handle, rows, M, self._addr(xm_in), self._addr(Xp_in), self._addr(xm_out),
             self._addr(Xp_out), _dp(glat), _dp(glon), ncol, n_lead))
 
+    def _state_cycle(self, entry, dtype, rows, M, X, post, grid_lat, grid_lon, n_lead):
+        glat, glon, ncol, n_lead = self._columns(None, grid_lat, grid_lon, rows, n_lead)
+        _check(self.lib, entry(self.handle, rows, M, self._addr(X, dtype), self._addr(post, dtype), _dp(glat), _dp(glon), ncol, n_lead))
+
     def state_cycle(self, rows, M, X, post, grid_lat=None, grid_lon=None, n_lead=1):
-        loc_mode = LOC_GC if grid_lat is not None else LOC_NONE
-        glat, glon, ncol = self._grid(loc_mode, grid_lat, grid_lon)
-        if loc_mode == LOC_NONE:
-            ncol, n_lead = rows, 1
-        _check(self.lib, self.lib.efa_state_cycle_dev(
-            self.handle, rows, M, self._addr(X), self._addr(post), _dp(glat), _dp(glon), ncol, n_lead))
+        self._state_cycle(self.lib.efa_state_cycle_dev, np.float64, rows, M, X, post, grid_lat, grid_lon, n_lead)
 
     def state_cycle_f32(self, rows, M, X, post, grid_lat=None, grid_lon=None, n_lead=1):
         """efa_state_cycle_f32_dev: `state_cycle` on float32 member rows (posterior = the float64 result rounded once)."""
-        loc_mode = LOC_GC if grid_lat is not None else LOC_NONE
-        glat, glon, ncol = self._grid(loc_mode, grid_lat, grid_lon)
-        if loc_mode == LOC_NONE:
-            ncol, n_lead = rows, 1
-        _check(self.lib, self.lib.efa_state_cycle_f32_dev(
-            self.handle, rows, M, self._addr(X, np.float32), self._addr(post, np.float32), _dp(glat), _dp(glon), ncol, n_lead))
+        self._state_cycle(self.lib.efa_state_cycle_f32_dev, np.float32, rows, M, X, post, grid_lat, grid_lon, n_lead)
 
     def ensrf_cycle(self, rows, M, P, X, post, ym, Yp, ob_value, ob_error, ob_assim, loc_mode=LOC_NONE,
                     ob_lat=None, ob_lon=None, ob_halfwidth=None, grid_lat=None, grid_lon=None, n_lead=1, obs_block_out=False):
@@ -886,16 +887,11 @@ class Context(object):
         behind Phase A without a host round trip when the cycle is unlocalised and takes the transform.  Returns the diagnostics."""
         val, err, asm, lat, lon, hw = self._ob_arrays(P, ob_value, ob_error, ob_assim, loc_mode,
                                                       ob_lat, ob_lon, ob_halfwidth)
-        glat, glon, ncol = self._grid(loc_mode, grid_lat, grid_lon)
-        if loc_mode == LOC_NONE:
-            ncol, n_lead = rows, 1
-        d = self._diag_arrays(P)
-        _check(self.lib, self.lib.efa_ensrf_cycle_dev(
-            self.handle, rows, M, P, self._addr(X), self._addr(post), self._addr(ym), self._addr(Yp), 1 if obs_block_out else 0,
-            _dp(val), _dp(err), _u8p(asm), loc_mode, _dp(lat), _dp(lon), _dp(hw), _dp(glat), _dp(glon), ncol, n_lead,
-            _dp(d["prior_mean"]), _dp(d["prior_var"]), _dp(d["post_mean"]), _dp(d["post_var"]), _u8p(d["assimilated"])))
-        d["assimilated"] = d["assimilated"].astype(bool)
-        return d
+        glat, glon, ncol, n_lead = self._columns(loc_mode, grid_lat, grid_lon, rows, n_lead)
+        return self._diagnosed(
+            P, self.lib.efa_ensrf_cycle_dev, self.handle, rows, M, P, self._addr(X), self._addr(post), self._addr(ym),
+            self._addr(Yp), 1 if obs_block_out else 0, _dp(val), _dp(err), _u8p(asm), loc_mode, _dp(lat), _dp(lon), _dp(hw),
+            _dp(glat), _dp(glon), ncol, n_lead)
 
     def letkf_cycle(self, rows, M, P, X, post, ym, Yp, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth, grid_lat,
                     grid_lon, n_lead=1, obs_block_out=False, col_stats=None, f32=None, shape=None, stride=None, _slab=False):
@@ -911,22 +907,17 @@ class Context(object):
         if f32 is None:
             f32 = isinstance(X, DeviceArray) and X.dtype == np.float32
         dt = np.float32 if f32 else np.float64
-        d = self._diag_arrays(P)
         head = (self.handle, rows, M, P, self._addr(X, dt), self._addr(post, dt), self._addr(ym), self._addr(Yp),
                 1 if obs_block_out else 0, _dp(val), _dp(err), _u8p(asm), _dp(lat), _dp(lon), _dp(hw), _dp(glat), _dp(glon))
-        tail = (n_lead, _dp(d["prior_mean"]), _dp(d["prior_var"]), _dp(d["post_mean"]), _dp(d["post_var"]), _u8p(d["assimilated"]),
-                self._addr(col_stats))
         stem = "efa_letkf_slab_cycle_" if _slab else "efa_letkf_cycle_"
         if stride is None:
-            entry = getattr(self.lib, stem + ("f32_dev" if f32 else "dev"))
-            _check(self.lib, entry(*(head + (ncol,) + tail)))
+            entry, cols = getattr(self.lib, stem + ("f32_dev" if f32 else "dev")), (ncol,)
         else:
             if shape is None:
                 raise ValueError("letkf_cycle: stride needs the grid's shape=(ny, nx)")
             entry = getattr(self.lib, stem + ("interp_f32_dev" if f32 else "interp_dev"))
-            _check(self.lib, entry(*(head + (int(shape[0]), int(shape[1]), int(stride[0]), int(stride[1])) + tail)))
-        d["assimilated"] = d["assimilated"].astype(bool)
-        return d
+            cols = (int(shape[0]), int(shape[1]), int(stride[0]), int(stride[1]))
+        return self._diagnosed(P, entry, *(head + cols + (n_lead,)), tail=(self._addr(col_stats),))
 
     def letkf_slab_cycle(self, rows, M, P, X, post, ym, Yp, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth, grid_lat,
                          grid_lon, n_lead=1, obs_block_out=False, col_stats=None, f32=None, shape=None, stride=None):
@@ -992,17 +983,10 @@ class Context(object):
                          grid_lat=None, grid_lon=None, n_lead=1):
         val, err, asm, lat, lon, hw = self._ob_arrays(P, ob_value, ob_error, ob_assim, loc_mode,
                                                       ob_lat, ob_lon, ob_halfwidth)
-        glat, glon, ncol = self._grid(loc_mode, grid_lat, grid_lon)
-        if loc_mode == LOC_NONE:
-            ncol, n_lead = rows, 1
-        d = self._diag_arrays(P)
-        _check(self.lib, self.lib.efa_ensrf_update_dev(
-            self.handle, rows, M, P, self._addr(xm), self._addr(Xp), self._addr(ym), self._addr(Yp),
-            _dp(val), _dp(err), _u8p(asm), loc_mode, _dp(lat), _dp(lon), _dp(hw), _dp(glat), _dp(glon),
-            ncol, n_lead, _dp(d["prior_mean"]), _dp(d["prior_var"]), _dp(d["post_mean"]),
-            _dp(d["post_var"]), _u8p(d["assimilated"])))
-        d["assimilated"] = d["assimilated"].astype(bool)
-        return d
+        glat, glon, ncol, n_lead = self._columns(loc_mode, grid_lat, grid_lon, rows, n_lead)
+        return self._diagnosed(
+            P, self.lib.efa_ensrf_update_dev, self.handle, rows, M, P, self._addr(xm), self._addr(Xp), self._addr(ym),
+            self._addr(Yp), _dp(val), _dp(err), _u8p(asm), loc_mode, _dp(lat), _dp(lon), _dp(hw), _dp(glat), _dp(glon), ncol, n_lead)
 
     def ensrf_update_host(self, xbm, Xbp, nstate, ob_value, ob_error, ob_assim, loc_mode=LOC_NONE,
                           ob_lat=None, ob_lon=None, ob_halfwidth=None, grid_lat=None, grid_lon=None,
@@ -1014,17 +998,10 @@ class Context(object):
         P = A - nstate
         val, err, asm, lat, lon, hw = self._ob_arrays(P, ob_value, ob_error, ob_assim, loc_mode,
                                                       ob_lat, ob_lon, ob_halfwidth)
-        glat, glon, ncol = self._grid(loc_mode, grid_lat, grid_lon)
-        if loc_mode == LOC_NONE:
-            ncol, n_lead = nstate, 1
-        d = self._diag_arrays(P)
-        _check(self.lib, self.lib.efa_ensrf_update(
-            self.handle, A, nstate, M, P, _dp(xbm), _dp(Xbp), _dp(val), _dp(err), _u8p(asm), loc_mode,
-            _dp(lat), _dp(lon), _dp(hw), _dp(glat), _dp(glon), ncol, n_lead,
-            _dp(d["prior_mean"]), _dp(d["prior_var"]), _dp(d["post_mean"]), _dp(d["post_var"]),
-            _u8p(d["assimilated"])))
-        d["assimilated"] = d["assimilated"].astype(bool)
-        return d
+        glat, glon, ncol, n_lead = self._columns(loc_mode, grid_lat, grid_lon, nstate, n_lead)
+        return self._diagnosed(
+            P, self.lib.efa_ensrf_update, self.handle, A, nstate, M, P, _dp(xbm), _dp(Xbp), _dp(val), _dp(err), _u8p(asm), loc_mode,
+            _dp(lat), _dp(lon), _dp(hw), _dp(glat), _dp(glon), ncol, n_lead)
 
     def obs_impact(self, rows, M, P, Xf, werr, Ya, innov, ob_error, ob_used, loc_mode=LOC_NONE, ob_lat=None, ob_lon=None,
                    ob_halfwidth=None, grid_lat=None, grid_lon=None, n_lead=1):
@@ -1043,9 +1020,7 @@ class Context(object):
     def _obs_impact(self, entry, rows, M, P, Xf, werr, Ya, innov, ob_error, ob_used, loc_mode, ob_lat, ob_lon, ob_halfwidth, grid_lat,
                     grid_lon, n_lead):
         d, err, used, lat, lon, hw = self._ob_arrays(P, innov, ob_error, ob_used, loc_mode, ob_lat, ob_lon, ob_halfwidth)
-        glat, glon, ncol = self._grid(loc_mode, grid_lat, grid_lon)
-        if loc_mode == LOC_NONE:
-            ncol, n_lead = rows, 1
+        glat, glon, ncol, n_lead = self._columns(loc_mode, grid_lat, grid_lon, rows, n_lead)
         out = np.zeros(P)
         _check(self.lib, entry(
             self.handle, rows, M, P, self._addr(Xf), self._addr(werr), self._addr(Ya), _dp(d), _dp(err), _u8p(used), loc_mode,

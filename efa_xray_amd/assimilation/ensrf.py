@@ -370,25 +370,121 @@ class EnSRF(Assimilation):
             else:
                 ob.assimilated = False
 
-    def _update_streamed(self, loc_mode, P, value, error, assim, lat, lon, hw):
+    def _say(self, line):
+        if self.verbose:
+            print(line)
+
+    def _column_geometry(self, loc_mode):
+        """(grid_lat, grid_lon, n_lead) of a call: the columns' positions and the slabs on each under the 2-D taper
+        (ensrf.py:108-111); (None, None, 1) without localisation."""
+        if loc_mode != _lib.LOC_GC:
+            return None, None, 1
+        grid_lat, grid_lon = self.prior.column_latlon()
+        return grid_lat, grid_lon, self.prior.nvars() * self.prior.ntimes()
+
+    def _host_estimates(self, ctx):
+        """(P, M) estimates without a resident float64 state: the host gather of the stencil rows, or the obs' own `estimate`."""
+        return self.streamed_ob_estimates(ctx) if self._default_forward_operator() else self.compute_ob_estimates()
+
+    def _obs_block(self, ctx, X, P, HX=None):
+        """(ym, Yp) on the device: the forward operator, once per ob from the prior, and its mean and perturbations
+        (assimilation.py:45-48).  On the device from the resident float64 rows X for the reference's point interpolation, from
+        the host for a float32 state and for user-defined operators; HX: estimates the upload step made already."""
+        M = self.prior.nmems()
+        ym = ctx.empty((max(P, 1),))
+        if not P:
+            return ym, ctx.empty((1, M))
+        if HX is not None:
+            Yp = ctx.to_device(HX)
+        elif self.prior.dtype == np.float32:
+            Yp = ctx.to_device(self._host_estimates(ctx))
+        elif self._default_forward_operator():
+            Yp = self.device_ob_estimates(ctx, X)
+        else:
+            Yp = ctx.to_device(self.compute_ob_estimates())
+        ctx.form_perts(P, M, Yp, ym, Yp)
+        return ym, Yp
+
+    def _check_prior(self):
+        """What is checked of the prior the inflation hook left, before any device work."""
+        if self.adaptive_inflation is not None:
+            self.adaptive_inflation.check_state(self.prior)
+
+    def _upload(self, ctx, P):
+        """(X, HX, field): the prior on the device, slab by slab from the variables (no stacked host copy).  Under adaptive
+        inflation the field goes up too and inflates the prior ahead of the forward operator: on the device for
+        the reference's point interpolation, on the host for user-defined operators (they read the state object), which is
+        then the state that is uploaded and whose estimates HX are made here."""
+        ai = self.adaptive_inflation
+        if ai is None:
+            return self._upload_prior(ctx), None, None
+        prior = self.prior
+        field = ctx.to_device(ai.inflation.to_vect())
+        if P and not self._default_forward_operator():
+            self.prior = ai.inflate_state(prior)           # for the operators and the upload only
+            try:
+                return self._upload_prior(ctx), self.compute_ob_estimates(), field
+            finally:
+                self.prior = prior
+        X = self._upload_prior(ctx)
+        ctx.inflate_rows(prior.nstate(), prior.nmems(), X, field)
+        return X, None, field
+
+    _cycle_line = "Beginning observation loop"
+
+    def _run_cycle(self, ctx, X, P, ym, Yp, ob, geometry, field):
+        """Phase A (ensrf.py:50-149 on the obs block) and the state phase, in place on X; returns the diagnostics.  float64: one
+        library call, so nothing is enqueued ahead of Phase A's status (efa_ensrf_cycle_dev speculates only into a separate
+        posterior buffer).  float32: Phase A in float64, the state phase on the float32 rows."""
+        N, M = self.prior.nstate(), self.prior.nmems()
+        if self.prior.dtype == np.float32:
+            diag = ctx.obs_phase(M, P, ym, Yp, *ob)
+            ctx.state_cycle_f32(N, M, X, X, *geometry)
+            ctx.synchronize()
+            return diag
+        ai = self.adaptive_inflation
+        if ai is None:
+            return ctx.ensrf_cycle(N, M, P, X, X, ym, Yp, *(ob + geometry))
+        ctx.set_adaptive_inflation(field, N, ai.lower, ai.upper, ai.sd_lower)
+        try:
+            diag = ctx.ensrf_cycle(N, M, P, X, X, ym, Yp, *(ob + geometry))
+        finally:
+            ctx.set_adaptive_inflation(None)
+        ai.inflation.from_vect(field.download())           # next cycle's prior inflation
+        return diag
+
+    def _update_resident(self, P, ob):
+        """update() on a state that fits the device: up, the obs block, the cycle in place, down."""
+        self._check_prior()
+        ctx = self._context()
+        self._configure(ctx)
+        ctx.set_option("timing", 1)
+        self._say("Converting state to vector")
+        X, HX, field = self._upload(ctx, P)
+        self._say("Computing observation priors")
+        ym, Yp = self._obs_block(ctx, X, P, HX)
+        geometry = self._column_geometry(ob[3])
+        self._say(self._cycle_line)
+        diag = self._run_cycle(ctx, X, P, ym, Yp, ob, geometry, field)
+        self.last_timing = ctx.last_timing()
+        self._write_diagnostics(diag)
+        self._say("Formatting posterior")
+        # a NEW state object (assimilation.py:165 deep-copies the prior): coordinates copied, member arrays downloaded
+        # straight into their own fresh arrays -- the prior's members are not copied only to be overwritten
+        return self._download_posterior(X), self.obs
+
+    def _update_streamed(self, P, ob):
         """update() with the prior left in host memory (efa_ensrf_cycle_host)."""
         from collections import OrderedDict
         from copy import deepcopy
         prior = self.prior
         nvar, nt, ny, nx, M = prior.shape()
-        ncol = ny * nx
         ctx = self._context()
         self._configure(ctx)
         ctx.set_option("timing", 1)
-        if self.verbose:
-            print("Computing observation priors")
-        # forward operator, once per ob from the prior (assimilation.py:45-48), without a resident state
-        HX = None
-        if P:
-            HX = self.streamed_ob_estimates(ctx) if self._default_forward_operator() else self.compute_ob_estimates()
-        grid_lat = grid_lon = None
-        if loc_mode == _lib.LOC_GC:
-            grid_lat, grid_lon = prior.column_latlon()
+        self._say("Computing observation priors")
+        HX = self._host_estimates(ctx) if P else None
+        grid_lat, grid_lon, _ = self._column_geometry(ob[3])
         names = prior.vars()
         dt = prior.dtype                          # float32 states stream as float32 (efa_ensrf_cycle_host_f32)
         seg_prior = [np.ascontiguousarray(prior.variables[n], dtype=dt) for n in names]
@@ -400,166 +496,29 @@ class EnSRF(Assimilation):
         chunk_cols = self.stream_chunk_cols
         if chunk_cols is None:
             chunk_cols = _lib.default_chunk_cols(nvar * nt, M, itemsize=dt.itemsize)
-        if self.verbose:
-            print("Beginning observation loop")
-        diag = ctx.ensrf_cycle_host(seg_prior, seg_post, ncol, M, HX, chunk_cols, value, error, assim, loc_mode, lat, lon, hw,
-                                    grid_lat, grid_lon)
+        self._say("Beginning observation loop")
+        diag = ctx.ensrf_cycle_host(seg_prior, seg_post, ny * nx, M, HX, chunk_cols, *(ob + (grid_lat, grid_lon)))
         self.last_timing = ctx.last_timing()
         self.last_stream = ctx.stream_stats()
         self._write_diagnostics(diag)
-        if self.verbose:
-            print("Formatting posterior")
+        self._say("Formatting posterior")
         post_state = type(prior)(OrderedDict(zip(names, seg_post)), deepcopy(prior.coords))
         return post_state, self.obs
 
-    def _update_f32(self, loc_mode, P, value, error, assim, lat, lon, hw):
-        """update() with a resident state stored as float32 (efa_state_cycle_f32_dev): float32 up, the obs-space
-        estimates from the host gather of the stencil rows (widened), Phase A in float64, the state phase in place on the float32
-        rows, float32 down."""
-        prior = self.prior
-        N, M = prior.nstate(), prior.nmems()
-        ctx = self._context()
-        self._configure(ctx)
-        ctx.set_option("timing", 1)
-        if self.verbose:
-            print("Converting state to vector")
-        X = self._upload_prior(ctx)
-        if self.verbose:
-            print("Computing observation priors")
-        ym = ctx.empty((max(P, 1),))
-        if P:
-            HX = self.streamed_ob_estimates(ctx) if self._default_forward_operator() else self.compute_ob_estimates()
-            Yp = ctx.to_device(HX)
-            ctx.form_perts(P, M, Yp, ym, Yp)                   # assimilation.py:46-48
-        else:
-            Yp = ctx.empty((1, M))
-        grid_lat = grid_lon = None
-        n_lead = 1
-        if loc_mode == _lib.LOC_GC:
-            grid_lat, grid_lon = prior.column_latlon()
-            n_lead = prior.nvars() * prior.ntimes()
-        if self.verbose:
-            print("Beginning observation loop")
-        diag = ctx.obs_phase(M, P, ym, Yp, value, error, assim, loc_mode, lat, lon, hw)
-        ctx.state_cycle_f32(N, M, X, X, grid_lat, grid_lon, n_lead)
-        ctx.synchronize()
-        self.last_timing = ctx.last_timing()
-        self._write_diagnostics(diag)
-        if self.verbose:
-            print("Formatting posterior")
-        return self._download_posterior(X), self.obs
-
     # ------------------------------------------------------------------
     def update(self):
-        if self.verbose:
-            print("Beginning update sequence")
+        self._say("Beginning update sequence")
         loc_mode = self._loc_mode()
         P, value, error, assim, lat, lon, hw = self._ob_arrays(loc_mode)
         if self.prior.dtype == np.float32 and self.adaptive_inflation is not None:
             raise ValueError("adaptive_inflation does not support a float32 state (DESIGN.md 7g)")
-        if self.prior.dtype == np.float32 and not self.streamed:
-            if self.inflation is not None:      # the inflation hook comes first, as below
-                if self.verbose:
-                    print("Inflating Prior State")
-                self.inflate_state()
-            return self._update_f32(loc_mode, P, value, error, assim, lat, lon, hw)
-        if self.streamed:
-            if self.inflation is not None:      # the inflation hook comes first, as below
-                if self.verbose:
-                    print("Inflating Prior State")
-                self.inflate_state()
-            return self._update_streamed(loc_mode, P, value, error, assim, lat, lon, hw)
         # ensrf.py:44 -> format_prior_state: the inflation hook comes first (assimilation.py:131-134);
         # it may rebind self.prior (per-dimension factors, assimilation.py:96)
         if self.inflation is not None:
-            if self.verbose:
-                print("Inflating Prior State")
+            self._say("Inflating Prior State")
             self.inflate_state()
-        prior = self.prior
-        N = prior.nstate()
-        M = prior.nmems()
-
-        ai = self.adaptive_inflation
-        if ai is not None:
-            ai.check_state(prior)
-        ctx = self._context()
-        self._configure(ctx)
-        ctx.set_option("timing", 1)
-        if self.verbose:
-            print("Converting state to vector")
-        device_fo = P and self._default_forward_operator()
-        field = None
-        HX = None
-        if ai is not None:
-            # the prior inflation comes before the forward operator (DESIGN.md 7c): on the device for the reference's
-            # point interpolation, on the host for user-defined operators (they read the state object), which is then the
-            # state that is uploaded
-            field = ctx.to_device(ai.inflation.to_vect())
-            if not device_fo and P:
-                self.prior = ai.inflate_state(prior)           # for the operators and the upload only
-                try:
-                    X = self._upload_prior(ctx)
-                    HX = self.compute_ob_estimates()
-                finally:
-                    self.prior = prior
-            else:
-                X = self._upload_prior(ctx)
-                ctx.inflate_rows(N, M, X, field)
-        else:
-            X = self._upload_prior(ctx)                        # slab by slab from the variables: no stacked host copy
-        # forward operator, once per ob from the prior (assimilation.py:45-48): on the device for the
-        # reference's point interpolation, through ob.estimate() for user-defined operators
-        if self.verbose:
-            print("Computing observation priors")
-        ym = ctx.empty((max(P, 1),))
-        if device_fo:
-            Yp = self.device_ob_estimates(ctx, X)
-        elif HX is not None:
-            Yp = ctx.to_device(HX)
-        else:
-            Yp = ctx.to_device(self.compute_ob_estimates()) if P else ctx.empty((1, M))
-        if P:
-            ctx.form_perts(P, M, Yp, ym, Yp)                   # assimilation.py:46-48
-
-        grid_lat = grid_lon = None
-        n_lead = 1
-        if loc_mode == _lib.LOC_GC:
-            grid_lat, grid_lon = prior.column_latlon()          # 2-D taper, ensrf.py:108-111
-            n_lead = prior.nvars() * prior.ntimes()
-
-        if self.verbose:
-            print("Beginning observation loop")
-        # Phase A (ensrf.py:50-149 on the obs block) and the state phase in one library call; in place, so nothing is
-        # enqueued ahead of Phase A's status (efa_ensrf_cycle_dev speculates only into a separate posterior buffer)
-        if ai is None:
-            diag = ctx.ensrf_cycle(N, M, P, X, X, ym, Yp, value, error, assim, loc_mode, lat, lon, hw, grid_lat, grid_lon, n_lead)
-        else:
-            ctx.set_adaptive_inflation(field, N, ai.lower, ai.upper, ai.sd_lower)
-            try:
-                diag = ctx.ensrf_cycle(N, M, P, X, X, ym, Yp, value, error, assim, loc_mode, lat, lon, hw, grid_lat, grid_lon,
-                                       n_lead)
-            finally:
-                ctx.set_adaptive_inflation(None)
-            ai.inflation.from_vect(field.download())           # next cycle's prior inflation
-        self.last_timing = ctx.last_timing()
-
-        # diagnostics onto the observations, as ensrf.py:66,70,75,146-149
-        for k, ob in enumerate(self.obs):
-            ob.prior_mean = np.float64(diag["prior_mean"][k])
-            ob.prior_var = np.float64(diag["prior_var"][k])
-            if diag["assimilated"][k]:
-                ob.post_mean = np.float64(diag["post_mean"][k])
-                ob.post_var = np.float64(diag["post_var"][k])
-                ob.assimilated = True
-            else:
-                ob.assimilated = False
-
-        if self.verbose:
-            print("Formatting posterior")
-        # a NEW state object (assimilation.py:165 deep-copies the prior): coordinates copied, member arrays downloaded
-        # straight into their own fresh arrays -- the prior's members are not copied only to be overwritten
-        post_state = self._download_posterior(X)
-        return post_state, self.obs
+        ob = (value, error, assim, loc_mode, lat, lon, hw)      # as every Context call takes them
+        return self._update_streamed(P, ob) if self.streamed else self._update_resident(P, ob)
 
     # ------------------------------------------------------------------
     def update_arrays(self, xbm, Xbp):
@@ -583,22 +542,8 @@ class EnSRF(Assimilation):
         N = self.prior.nstate()
         xam = np.array(xbm, dtype=np.float64, order="C")
         Xap = np.array(Xbp, dtype=np.float64, order="C")
-        grid_lat = grid_lon = None
-        n_lead = 1
-        if loc_mode == _lib.LOC_GC:
-            grid_lat, grid_lon = self.prior.column_latlon()
-            n_lead = self.prior.nvars() * self.prior.ntimes()
+        geometry = self._column_geometry(loc_mode)
         ctx = self._context()
         self._configure(ctx)
-        diag = ctx.ensrf_update_host(xam, Xap, N, value, error, assim, loc_mode, lat, lon, hw,
-                                     grid_lat, grid_lon, n_lead)
-        for k, ob in enumerate(self.obs):
-            ob.prior_mean = np.float64(diag["prior_mean"][k])
-            ob.prior_var = np.float64(diag["prior_var"][k])
-            if diag["assimilated"][k]:
-                ob.post_mean = np.float64(diag["post_mean"][k])
-                ob.post_var = np.float64(diag["post_var"][k])
-                ob.assimilated = True
-            else:
-                ob.assimilated = False
+        self._write_diagnostics(ctx.ensrf_update_host(xam, Xap, N, value, error, assim, loc_mode, lat, lon, hw, *geometry))
         return xam, Xap

@@ -90,43 +90,23 @@ class LETKF(EnSRF):
         self.last_solve = None
         self.weight_stride = stride
 
-    def update(self):
-        self.last_solve = None
-        if self.verbose:
-            print("Beginning update sequence")
-        P, value, error, assim, lat, lon, hw = self._ob_arrays(_lib.LOC_GC)
-        if self.inflation is not None:          # the inflation hook comes first, as in EnSRF.update
-            if self.verbose:
-                print("Inflating Prior State")
-            self.inflate_state()
-        prior = self.prior
-        N, M = prior.nstate(), prior.nmems()
+    _cycle_line = "Beginning the column solves"
+
+    def _check_prior(self):
+        M = self.prior.nmems()
         if M > MAX_MEMBERS:
             raise ValueError("LETKF: %d members exceed %d (DESIGN.md 7y)" % (M, MAX_MEMBERS))
-        f32 = prior.dtype == np.float32
-        ctx = self._context()
-        self._configure(ctx)
-        ctx.set_option("timing", 1)
-        if self.verbose:
-            print("Converting state to vector")
-        X = self._upload_prior(ctx)
-        if self.verbose:
-            print("Computing observation priors")
-        ym = ctx.empty((max(P, 1),))
-        if P:
-            if f32:                             # as EnSRF._update_f32: the host gather of the stencil rows, widened
-                HX = self.streamed_ob_estimates(ctx) if self._default_forward_operator() else self.compute_ob_estimates()
-                Yp = ctx.to_device(HX)
-            elif self._default_forward_operator():
-                Yp = self.device_ob_estimates(ctx, X)
-            else:
-                Yp = ctx.to_device(self.compute_ob_estimates())
-            ctx.form_perts(P, M, Yp, ym, Yp)    # assimilation.py:46-48
-        else:
-            Yp = ctx.empty((1, M))
-        grid_lat, grid_lon = prior.column_latlon()
+
+    def update(self):
+        self.last_solve = None
+        return EnSRF.update(self)       # the resident sequence (streamed is refused), with the cycle below
+
+    def _run_cycle(self, ctx, X, P, ym, Yp, ob, geometry, field):
+        """The column solves in place on X (float64 or float32 rows); returns the diagnostics and leaves `last_solve`."""
+        prior = self.prior
+        N, M = prior.nstate(), prior.nmems()
         ny, nx = prior.shape()[2:4]
-        n_lead = prior.nvars() * prior.ntimes()
+        n_lead = geometry[2]
         slab = self.vert_coord is not None or self.slab is not None     # (SlabLETKF only: LETKF refuses the three keywords)
         mesh = {}
         sy, sx = ny, nx                         # the statistics' shape: the grid's, or the node mesh's
@@ -135,21 +115,17 @@ class LETKF(EnSRF):
             node_x = _lib.letkf_mesh_nodes(nx, self.weight_stride[1])
             sy, sx = node_y.size, node_x.size
             mesh = dict(shape=(ny, nx), stride=self.weight_stride)
-        if self.verbose:
-            print("Beginning the column solves")
         ng = 1                                  # solves per column or node
         try:
             if slab:
                 group_of, ng = ctx.letkf_slab_groups(n_lead)
             stats = ctx.empty((ng * sy * sx, 3))
-            diag = ctx.letkf_cycle(N, M, P, X, X, ym, Yp, value, error, assim, lat, lon, hw, grid_lat, grid_lon, n_lead,
-                                   col_stats=stats, f32=f32, _slab=slab, **mesh)
+            diag = ctx.letkf_cycle(N, M, P, X, X, ym, Yp, *(ob[:3] + ob[4:] + geometry), col_stats=stats,
+                                   f32=prior.dtype == np.float32, _slab=slab, **mesh)
         finally:
             if slab:                            # the context is shared per device: the settings do not outlive the update
                 ctx.set_vertical_localization(None)
                 ctx.set_slab_localization(None)
-        self.last_timing = ctx.last_timing()
-        self._write_diagnostics(diag)
         st = stats.download().reshape(ng, sy, sx, 3)
         if not slab:                            # the plain filter documents (ny, nx) / (nyn, nxn)
             st = st[0]
@@ -158,9 +134,7 @@ class LETKF(EnSRF):
             self.last_solve.update(group_of_slab=group_of.astype(np.int64).reshape(prior.nvars(), prior.ntimes()))
         if mesh:
             self.last_solve.update(node_y=node_y, node_x=node_x)
-        if self.verbose:
-            print("Formatting posterior")
-        return self._download_posterior(X), self.obs
+        return diag
 
     def update_arrays(self, xbm, Xbp):
         raise ValueError("LETKF does not offer update_arrays (out of scope, DESIGN.md 7y); use update()")

@@ -73,29 +73,13 @@ using namespace efa_host;
 
 namespace {
 
-// the driver's structs from a LETKF entry's values, each assigned to its field by name
-efa_host::LetkfObsIn letkf_obs_in(const double* ym_dev, const double* Yp_dev, const double* ob_value, const double* ob_error,
-                                  const uint8_t* ob_assim, const double* ob_lat, const double* ob_lon, const double* ob_halfwidth_km) {
-  efa_host::LetkfObsIn o;
-  o.ym_dev = ym_dev;
-  o.Yp_dev = Yp_dev;
-  o.ob_value = ob_value;
-  o.ob_error = ob_error;
-  o.ob_assim = ob_assim;
-  o.ob_lat = ob_lat;
-  o.ob_lon = ob_lon;
-  o.ob_hw = ob_halfwidth_km;
-  return o;
-}
-
-efa_host::LetkfDiagOut letkf_diag_out(double* prior_mean, double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated) {
-  efa_host::LetkfDiagOut d;
-  d.prior_mean = prior_mean;
-  d.prior_var = prior_var;
-  d.post_mean = post_mean;
-  d.post_var = post_var;
-  d.assimilated = assimilated;
-  return d;
+// what efa_ensrf_update_dev and efa_ensrf_cycle_dev check of the context's settings against a cycle's arguments, ahead of both phases
+int check_cycle_settings(const efa_ctx* c, int loc_mode, long rows, long P, long n_lead) {
+  EFA_TRY(check_adaptive(c, loc_mode, rows));
+  EFA_TRY(check_vloc(c, loc_mode, P, n_lead));
+  EFA_TRY(check_slab(c, loc_mode, P, n_lead));
+  EFA_TRY(check_sec(c, loc_mode));
+  return check_batch_solver(c, loc_mode);
 }
 
 }  // namespace
@@ -705,8 +689,8 @@ int efa_obs_phase_dev(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev,
                       const double* ob_lon, const double* ob_halfwidth_km, double* prior_mean, double* prior_var,
                       double* post_mean, double* post_var, uint8_t* assimilated) {
   EFA_TRY(use(c));
-  return obs_phase(c, M, P, ym_dev, Yp_dev, ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon, ob_halfwidth_km,
-                   prior_mean, prior_var, post_mean, post_var, assimilated);
+  return obs_phase(c, M, P, ym_dev, Yp_dev, obs_in(ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon, ob_halfwidth_km),
+                   diag_out(prior_mean, prior_var, post_mean, post_var, assimilated));
 }
 
 int efa_state_phase_dev(efa_ctx* c, long rows, int M, const double* xm_in_dev, const double* Xp_in_dev,
@@ -734,13 +718,9 @@ int efa_ensrf_update_dev(efa_ctx* c, long rows, int M, long P, double* xm_dev, d
                          const double* grid_lat, const double* grid_lon, long ncol, long n_lead, double* prior_mean,
                          double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated) {
   EFA_TRY(use(c));
-  EFA_TRY(check_adaptive(c, loc_mode, rows));
-  EFA_TRY(check_vloc(c, loc_mode, P, n_lead));
-  EFA_TRY(check_slab(c, loc_mode, P, n_lead));
-  EFA_TRY(check_sec(c, loc_mode));
-  EFA_TRY(check_batch_solver(c, loc_mode));
-  EFA_TRY(obs_phase(c, M, P, ym_dev, Yp_dev, ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon,
-                    ob_halfwidth_km, prior_mean, prior_var, post_mean, post_var, assimilated));
+  EFA_TRY(check_cycle_settings(c, loc_mode, rows, P, n_lead));
+  EFA_TRY(obs_phase(c, M, P, ym_dev, Yp_dev, obs_in(ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon, ob_halfwidth_km),
+                    diag_out(prior_mean, prior_var, post_mean, post_var, assimilated)));
   EFA_TRY(state_phase(c, rows, M, xm_dev, Xp_dev, xm_dev, Xp_dev, grid_lat, grid_lon, ncol, n_lead));
   EFA_HIP(hipStreamSynchronize(c->stream));
   return EFA_OK;
@@ -754,11 +734,7 @@ int efa_ensrf_cycle_dev(efa_ctx* c, long rows, int M, long P, const double* X_de
   EFA_TRY(use(c));
   if (rows < 0) return fail(EFA_ERR_INVALID, "negative row count");
   if (rows > 0 && (!X_dev || !post_dev)) return fail(EFA_ERR_INVALID, "null state pointer");
-  EFA_TRY(check_adaptive(c, loc_mode, rows));
-  EFA_TRY(check_vloc(c, loc_mode, P, n_lead));
-  EFA_TRY(check_slab(c, loc_mode, P, n_lead));
-  EFA_TRY(check_sec(c, loc_mode));
-  EFA_TRY(check_batch_solver(c, loc_mode));
+  EFA_TRY(check_cycle_settings(c, loc_mode, rows, P, n_lead));
   // Phase B may go into the stream before Phase A's status is known only if a wrong guess cannot cost the prior:
   // separate prior and posterior buffers (a redone Phase A needs the transform run again on the untouched prior)
   const StateRows r{X_dev, post_dev, Elem::f64, rows, M};
@@ -771,8 +747,8 @@ int efa_ensrf_cycle_dev(efa_ctx* c, long rows, int M, long P, const double* X_de
     EFA_TRY(c->grid.refresh(c->stream, grid_lat, grid_lon, ncol));
   }
   SpecResult done;
-  EFA_TRY(obs_phase(c, M, P, ym_dev, Yp_dev, ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon, ob_halfwidth_km, prior_mean,
-                    prior_var, post_mean, post_var, assimilated, spec, &done));
+  EFA_TRY(obs_phase(c, M, P, ym_dev, Yp_dev, obs_in(ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon, ob_halfwidth_km),
+                    diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), spec, &done));
   // Phase B is in the stream already, behind the launch that turned out fine -- unless the outlier check rejected so many obs
   // that the state phase would not take the transform (none left, or "auto" with fewer): then it runs as it would have, over the
   // speculative posterior (the prior is untouched)
@@ -844,8 +820,8 @@ int efa_obs_impact_dev(efa_ctx* c, long rows, int M, long P, const double* Xf_de
                        const double* ob_lon, const double* ob_halfwidth_km, const double* grid_lat, const double* grid_lon,
                        long ncol, long n_lead, double* impact) {
   EFA_TRY(use(c));
-  return obs_impact(c, rows, M, P, Xf_dev, werr_dev, Ya_dev, innov, ob_error, ob_used, loc_mode, ob_lat, ob_lon, ob_halfwidth_km,
-                    grid_lat, grid_lon, ncol, n_lead, impact);
+  return obs_impact(c, rows, M, P, Xf_dev, werr_dev, Ya_dev, obs_in(innov, ob_error, ob_used, loc_mode, ob_lat, ob_lon, ob_halfwidth_km),
+                    grid_lat, grid_lon, ncol, n_lead, impact, false);
 }
 
 int efa_obs_impact_slab_dev(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const double* werr_dev, const double* Ya_dev,
@@ -853,8 +829,8 @@ int efa_obs_impact_slab_dev(efa_ctx* c, long rows, int M, long P, const double* 
                             const double* ob_lon, const double* ob_halfwidth_km, const double* grid_lat, const double* grid_lon,
                             long ncol, long n_lead, double* impact) {
   EFA_TRY(use(c));
-  return obs_impact_slab(c, rows, M, P, Xf_dev, werr_dev, Ya_dev, innov, ob_error, ob_used, loc_mode, ob_lat, ob_lon, ob_halfwidth_km,
-                         grid_lat, grid_lon, ncol, n_lead, impact);
+  return obs_impact(c, rows, M, P, Xf_dev, werr_dev, Ya_dev, obs_in(innov, ob_error, ob_used, loc_mode, ob_lat, ob_lon, ob_halfwidth_km),
+                    grid_lat, grid_lon, ncol, n_lead, impact, true);
 }
 
 int efa_sensitivity_dev(efa_ctx* c, long rows, int M, int K, const double* X_dev, const double* J, long ncol, long n_lead,
@@ -998,9 +974,9 @@ int efa_letkf_cycle_dev(efa_ctx* c, long rows, int M, long P, const double* X_de
                         double* post_var, uint8_t* assimilated, double* col_stats_dev) {
   EFA_TRY(use(c));
   return efa_host::letkf_cycle(c, efa_host::StateRows{X_dev, post_dev, efa::Elem::f64, rows, M}, P,
-                               letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+                               ym_dev, Yp_dev, obs_in(ob_value, ob_error, ob_assim, EFA_LOC_GC, ob_lat, ob_lon, ob_halfwidth_km),
                                obs_block_out ? ym_dev : nullptr, obs_block_out ? Yp_dev : nullptr, grid_lat, grid_lon, ncol, n_lead,
-                               letkf_diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), col_stats_dev, nullptr, false);
+                               diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), col_stats_dev, nullptr, false);
 }
 
 int efa_letkf_cycle_f32_dev(efa_ctx* c, long rows, int M, long P, const float* X_dev, float* post_dev, double* ym_dev, double* Yp_dev,
@@ -1010,9 +986,9 @@ int efa_letkf_cycle_f32_dev(efa_ctx* c, long rows, int M, long P, const float* X
                             double* post_var, uint8_t* assimilated, double* col_stats_dev) {
   EFA_TRY(use(c));
   return efa_host::letkf_cycle(c, efa_host::StateRows{X_dev, post_dev, efa::Elem::f32, rows, M}, P,
-                               letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+                               ym_dev, Yp_dev, obs_in(ob_value, ob_error, ob_assim, EFA_LOC_GC, ob_lat, ob_lon, ob_halfwidth_km),
                                obs_block_out ? ym_dev : nullptr, obs_block_out ? Yp_dev : nullptr, grid_lat, grid_lon, ncol, n_lead,
-                               letkf_diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), col_stats_dev, nullptr, false);
+                               diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), col_stats_dev, nullptr, false);
 }
 
 int efa_letkf_weights_dev(efa_ctx* c, int M, long P, const double* ym_dev, const double* Yp_dev, const double* ob_value,
@@ -1020,7 +996,7 @@ int efa_letkf_weights_dev(efa_ctx* c, int M, long P, const double* ym_dev, const
                           const double* ob_halfwidth_km, long npts, const double* pt_lat, const double* pt_lon, double* Tw_dev,
                           double* stats_dev) {
   EFA_TRY(use(c));
-  return efa_host::letkf_weights(c, M, P, letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+  return efa_host::letkf_weights(c, M, P, ym_dev, Yp_dev, obs_in(ob_value, ob_error, ob_assim, EFA_LOC_GC, ob_lat, ob_lon, ob_halfwidth_km),
                                  npts, pt_lat, pt_lon, Tw_dev, stats_dev, false);
 }
 
@@ -1033,9 +1009,9 @@ int efa_letkf_cycle_interp_dev(efa_ctx* c, long rows, int M, long P, const doubl
   EFA_TRY(use(c));
   const efa::LetkfMesh mesh{ny, nx, stride_y, stride_x};
   return efa_host::letkf_cycle(c, efa_host::StateRows{X_dev, post_dev, efa::Elem::f64, rows, M}, P,
-                               letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+                               ym_dev, Yp_dev, obs_in(ob_value, ob_error, ob_assim, EFA_LOC_GC, ob_lat, ob_lon, ob_halfwidth_km),
                                obs_block_out ? ym_dev : nullptr, obs_block_out ? Yp_dev : nullptr, grid_lat, grid_lon, 0, n_lead,
-                               letkf_diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), node_stats_dev, &mesh, false);
+                               diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), node_stats_dev, &mesh, false);
 }
 
 int efa_letkf_cycle_interp_f32_dev(efa_ctx* c, long rows, int M, long P, const float* X_dev, float* post_dev, double* ym_dev,
@@ -1047,9 +1023,9 @@ int efa_letkf_cycle_interp_f32_dev(efa_ctx* c, long rows, int M, long P, const f
   EFA_TRY(use(c));
   const efa::LetkfMesh mesh{ny, nx, stride_y, stride_x};
   return efa_host::letkf_cycle(c, efa_host::StateRows{X_dev, post_dev, efa::Elem::f32, rows, M}, P,
-                               letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+                               ym_dev, Yp_dev, obs_in(ob_value, ob_error, ob_assim, EFA_LOC_GC, ob_lat, ob_lon, ob_halfwidth_km),
                                obs_block_out ? ym_dev : nullptr, obs_block_out ? Yp_dev : nullptr, grid_lat, grid_lon, 0, n_lead,
-                               letkf_diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), node_stats_dev, &mesh, false);
+                               diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), node_stats_dev, &mesh, false);
 }
 
 int efa_letkf_slab_cycle_dev(efa_ctx* c, long rows, int M, long P, const double* X_dev, double* post_dev, double* ym_dev,
@@ -1059,9 +1035,9 @@ int efa_letkf_slab_cycle_dev(efa_ctx* c, long rows, int M, long P, const double*
                              double* post_var, uint8_t* assimilated, double* col_stats_dev) {
   EFA_TRY(use(c));
   return efa_host::letkf_cycle(c, efa_host::StateRows{X_dev, post_dev, efa::Elem::f64, rows, M}, P,
-                               letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+                               ym_dev, Yp_dev, obs_in(ob_value, ob_error, ob_assim, EFA_LOC_GC, ob_lat, ob_lon, ob_halfwidth_km),
                                obs_block_out ? ym_dev : nullptr, obs_block_out ? Yp_dev : nullptr, grid_lat, grid_lon, ncol, n_lead,
-                               letkf_diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), col_stats_dev, nullptr, true);
+                               diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), col_stats_dev, nullptr, true);
 }
 
 int efa_letkf_slab_cycle_f32_dev(efa_ctx* c, long rows, int M, long P, const float* X_dev, float* post_dev, double* ym_dev,
@@ -1071,9 +1047,9 @@ int efa_letkf_slab_cycle_f32_dev(efa_ctx* c, long rows, int M, long P, const flo
                                  double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated, double* col_stats_dev) {
   EFA_TRY(use(c));
   return efa_host::letkf_cycle(c, efa_host::StateRows{X_dev, post_dev, efa::Elem::f32, rows, M}, P,
-                               letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+                               ym_dev, Yp_dev, obs_in(ob_value, ob_error, ob_assim, EFA_LOC_GC, ob_lat, ob_lon, ob_halfwidth_km),
                                obs_block_out ? ym_dev : nullptr, obs_block_out ? Yp_dev : nullptr, grid_lat, grid_lon, ncol, n_lead,
-                               letkf_diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), col_stats_dev, nullptr, true);
+                               diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), col_stats_dev, nullptr, true);
 }
 
 int efa_letkf_slab_cycle_interp_dev(efa_ctx* c, long rows, int M, long P, const double* X_dev, double* post_dev, double* ym_dev,
@@ -1085,9 +1061,9 @@ int efa_letkf_slab_cycle_interp_dev(efa_ctx* c, long rows, int M, long P, const 
   EFA_TRY(use(c));
   const efa::LetkfMesh mesh{ny, nx, stride_y, stride_x};
   return efa_host::letkf_cycle(c, efa_host::StateRows{X_dev, post_dev, efa::Elem::f64, rows, M}, P,
-                               letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+                               ym_dev, Yp_dev, obs_in(ob_value, ob_error, ob_assim, EFA_LOC_GC, ob_lat, ob_lon, ob_halfwidth_km),
                                obs_block_out ? ym_dev : nullptr, obs_block_out ? Yp_dev : nullptr, grid_lat, grid_lon, 0, n_lead,
-                               letkf_diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), node_stats_dev, &mesh, true);
+                               diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), node_stats_dev, &mesh, true);
 }
 
 int efa_letkf_slab_cycle_interp_f32_dev(efa_ctx* c, long rows, int M, long P, const float* X_dev, float* post_dev, double* ym_dev,
@@ -1099,9 +1075,9 @@ int efa_letkf_slab_cycle_interp_f32_dev(efa_ctx* c, long rows, int M, long P, co
   EFA_TRY(use(c));
   const efa::LetkfMesh mesh{ny, nx, stride_y, stride_x};
   return efa_host::letkf_cycle(c, efa_host::StateRows{X_dev, post_dev, efa::Elem::f32, rows, M}, P,
-                               letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+                               ym_dev, Yp_dev, obs_in(ob_value, ob_error, ob_assim, EFA_LOC_GC, ob_lat, ob_lon, ob_halfwidth_km),
                                obs_block_out ? ym_dev : nullptr, obs_block_out ? Yp_dev : nullptr, grid_lat, grid_lon, 0, n_lead,
-                               letkf_diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), node_stats_dev, &mesh, true);
+                               diag_out(prior_mean, prior_var, post_mean, post_var, assimilated), node_stats_dev, &mesh, true);
 }
 
 int efa_letkf_slab_weights_dev(efa_ctx* c, int M, long P, const double* ym_dev, const double* Yp_dev, const double* ob_value,
@@ -1109,7 +1085,7 @@ int efa_letkf_slab_weights_dev(efa_ctx* c, int M, long P, const double* ym_dev, 
                                const double* ob_halfwidth_km, long npts, const double* pt_lat, const double* pt_lon, double* Tw_dev,
                                double* stats_dev) {
   EFA_TRY(use(c));
-  return efa_host::letkf_weights(c, M, P, letkf_obs_in(ym_dev, Yp_dev, ob_value, ob_error, ob_assim, ob_lat, ob_lon, ob_halfwidth_km),
+  return efa_host::letkf_weights(c, M, P, ym_dev, Yp_dev, obs_in(ob_value, ob_error, ob_assim, EFA_LOC_GC, ob_lat, ob_lon, ob_halfwidth_km),
                                  npts, pt_lat, pt_lon, Tw_dev, stats_dev, true);
 }
 

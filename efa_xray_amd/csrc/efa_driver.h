@@ -20,7 +20,10 @@
 // drivers' host scaffolding: the interval helper, WsLayout, check_slab_groups, pad_thresholds, pairs_aligned, clamp_blocks, launch_quad).
 // One call's arguments and results travel as arguments and return values; the context (efa_ctx.h) holds settings, caches,
 // workspaces and what the last obs phase left for the state phase.  A state call's rows travel with their element type (StateRows);
-// its route is decided once, by plan_state, and every caller issues the launches through run_state_plan.
+// its route is decided once, by plan_state, and every caller issues the launches through run_state_plan.  The host per-observation
+// arrays of a call travel as one ObsIn and its host diagnostics as one DiagOut, from the extern "C" wrappers (which fill them by
+// name, obs_in / diag_out) down to the obs phase, the streamed update, the impact call and the LETKF; the device obs block
+// (ym_dev, Yp_dev) stays beside them -- the EnSRF writes it in place, the LETKF only reads it.
 #pragma once
 #include "efa_ctx.h"
 #include "efa_internal.h"
@@ -35,6 +38,42 @@ int form_perts(efa_ctx* c, long rows, int M, const double* X_dev, double scale, 
 void harvest_obs_ms(efa_ctx* c);
 void harvest_state_interval(efa_ctx* c, Interval& iv);
 void harvest_state_ms(efa_ctx* c);  // both state intervals
+
+// The per-observation inputs of a call, [P] each on the host: lat / lon / hw (the half-width, km) are read under EFA_LOC_GC only.
+// The impact call carries the innovations in `value` and ob_used in `assim`; the LETKF sets loc_mode EFA_LOC_GC.
+struct ObsIn {
+  const double *value = nullptr, *error = nullptr;
+  const uint8_t* assim = nullptr;
+  int loc_mode = EFA_LOC_NONE;
+  const double *lat = nullptr, *lon = nullptr, *hw = nullptr;
+};
+// the five host diagnostics of a call, [P] each or null
+struct DiagOut {
+  double *prior_mean = nullptr, *prior_var = nullptr, *post_mean = nullptr, *post_var = nullptr;
+  uint8_t* assimilated = nullptr;
+};
+// how the extern "C" wrappers fill them: every field by name, so that no positional list of look-alike pointers is left to swap
+inline ObsIn obs_in(const double* value, const double* error, const uint8_t* assim, int loc_mode, const double* lat, const double* lon,
+                    const double* hw) {
+  ObsIn o;
+  o.value = value;
+  o.error = error;
+  o.assim = assim;
+  o.loc_mode = loc_mode;
+  o.lat = lat;
+  o.lon = lon;
+  o.hw = hw;
+  return o;
+}
+inline DiagOut diag_out(double* prior_mean, double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated) {
+  DiagOut d;
+  d.prior_mean = prior_mean;
+  d.prior_var = prior_var;
+  d.post_mean = post_mean;
+  d.post_var = post_var;
+  d.assimilated = assimilated;
+  return d;
+}
 
 // ---- efa_comm.hip -------------------------------------------------------------------------------------------------------------
 void release_comm(efa_ctx* c);  // efa_ctx_destroy: the communicator goes, errors ignored
@@ -57,9 +96,7 @@ struct SpecResult {
   Interval* interval = nullptr;
   long launches = 0;  // state-phase launches it took (the transform, and the relaxation's)
 };
-int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const double* ob_value, const double* ob_error,
-              const uint8_t* ob_assim, int loc_mode, const double* ob_lat, const double* ob_lon, const double* ob_hw,
-              double* prior_mean, double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated,
+int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const ObsIn& ob, const DiagOut& diag,
               const SpecRequest& spec = SpecRequest{}, SpecResult* spec_out = nullptr);
 
 // ---- efa_phase_b.hip ----------------------------------------------------------------------------------------------------------
@@ -150,24 +187,13 @@ int state_cycle(efa_ctx* c, const StateRows& r, const double* grid_lat, const do
 int end_state_call(efa_ctx* c, Interval& iv, bool timed = true, bool end_recorded = false);
 
 // ---- efa_letkf_driver.hip -----------------------------------------------------------------------------------------------------
-// the observation inputs of a LETKF call: the prior obs block on the device, the per-ob arrays on the host
-struct LetkfObsIn {
-  const double *ym_dev = nullptr, *Yp_dev = nullptr;
-  const double *ob_value = nullptr, *ob_error = nullptr;
-  const uint8_t* ob_assim = nullptr;
-  const double *ob_lat = nullptr, *ob_lon = nullptr, *ob_hw = nullptr;
-};
-// the five host diagnostics of a cycle, [P] each or null
-struct LetkfDiagOut {
-  double *prior_mean = nullptr, *prior_var = nullptr, *post_mean = nullptr, *post_var = nullptr;
-  uint8_t* assimilated = nullptr;
-};
 // efa_letkf_cycle_dev / _f32_dev: checks, the obs' effective flags and prior diagnostics, the lists and the solve at every ob
 // position (the obs block), the lists and the solve of every grid column (the state); waits before it returns the diagnostics.
-// ym_out / Yp_out: where the posterior obs block goes (obs_block_out: the caller's block), both null: nowhere
-int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const LetkfObsIn& obs, double* ym_out, double* Yp_out, const double* grid_lat,
-                const double* grid_lon, long ncol, long n_lead, const LetkfDiagOut& diag, double* col_stats_dev,
-                const efa::LetkfMesh* mesh, bool slab);
+// ym_dev / Yp_dev: the prior obs block, only read; ym_out / Yp_out: where the posterior obs block goes (obs_block_out: the caller's
+// block), both null: nowhere
+int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const double* ym_dev, const double* Yp_dev, const ObsIn& ob, double* ym_out,
+                double* Yp_out, const double* grid_lat, const double* grid_lon, long ncol, long n_lead, const DiagOut& diag,
+                double* col_stats_dev, const efa::LetkfMesh* mesh, bool slab);
 // (mesh: efa_letkf_cycle_interp_dev / _f32_dev, DESIGN.md §7y-2 -- ncol is taken from it, the solve runs at its nodes only into a
 // buffer of the context, col_stats_dev receives the NODE statistics, and efa_letkf_interp.hip's kernel interpolates the pairs to
 // every column and applies them; a unit stride is the call without a mesh)
@@ -177,24 +203,19 @@ int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const LetkfObsIn& obs, d
 int letkf_interp_apply(efa_ctx* c, const StateRows& r, const efa::LetkfMesh& mesh, long n_lead, const double* Tw_nodes_dev,
                        const double* node_stats_dev);
 // efa_letkf_weights_dev: the same solve at caller-given points, [T | w] of each to Tw_dev; waits
-int letkf_weights(efa_ctx* c, int M, long P, const LetkfObsIn& obs, long npts, const double* pt_lat, const double* pt_lon, double* Tw_dev,
-                  double* stats_dev, bool slab);
+int letkf_weights(efa_ctx* c, int M, long P, const double* ym_dev, const double* Yp_dev, const ObsIn& ob, long npts, const double* pt_lat,
+                  const double* pt_lon, double* Tw_dev, double* stats_dev, bool slab);
 // (slab: efa_letkf_slab_weights_dev -- Tw_dev [ngroups][npts][M][M + 1], stats_dev [ngroups][npts][3])
 // efa_letkf_slab_groups: the group of every slab under the context's settings, numbered by first appearance
 int letkf_slab_group_table(efa_ctx* c, long n_lead, int* group_of, int* ngroups);
 
 // ---- efa_impact.hip -----------------------------------------------------------------------------------------------------------
-// efa_obs_impact_dev: checks, the call's own active lists, the contraction and its reduction; waits before it returns impact[P]
-int obs_impact(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const double* werr_dev, const double* Ya_dev,
-               const double* innov, const double* ob_error, const uint8_t* ob_used, int loc_mode, const double* ob_lat,
-               const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
-               double* impact);
-// efa_obs_impact_slab_dev: the same call under the temporal and variable tapers while the slab setting is on (the contraction reads
-// the slab table, brought up to date first); obs_impact itself while it is off
-int obs_impact_slab(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const double* werr_dev, const double* Ya_dev,
-                    const double* innov, const double* ob_error, const uint8_t* ob_used, int loc_mode, const double* ob_lat,
-                    const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
-                    double* impact);
+// efa_obs_impact_dev: checks, the call's own active lists, the contraction and its reduction; waits before it returns impact[P].
+// ob.value: the innovations, ob.assim: ob_used.
+// slab_entry: efa_obs_impact_slab_dev -- the same call under the temporal and variable tapers while the slab setting is on (the
+// contraction reads the slab table, brought up to date first); the plain call while it is off
+int obs_impact(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const double* werr_dev, const double* Ya_dev, const ObsIn& ob,
+               const double* grid_lat, const double* grid_lon, long ncol, long n_lead, double* impact, bool slab_entry);
 
 // ---- efa_sensitivity.hip ------------------------------------------------------------------------------------------------------
 // efa_sensitivity_dev / _f32_dev: checks, the passes and the host algebra between them; waits before it returns

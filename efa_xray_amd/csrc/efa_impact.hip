@@ -367,10 +367,14 @@ int make_event(OwnedEvent& e) {
 // trajectory, column grid, options and timing sums are neither read (but for the vertical and the slab setting) nor written.
 // slab: the call is efa_obs_impact_slab_dev with the slab setting on -- the contraction runs under GC_h(col, k) S(k, slab), S the
 // context's factor table, whose cache (keyed by the two settings' serials) is the one thing of the context it writes.
-static int impact_call(efa_ctx* c, const char* me, bool slab, long rows, int M, long P, const double* Xf_dev, const double* werr_dev,
-                       const double* Ya_dev, const double* innov, const double* ob_error, const uint8_t* ob_used, int loc_mode,
-                       const double* ob_lat, const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon,
-                       long ncol, long n_lead, double* impact) {
+// slab_entry: the call came through efa_obs_impact_slab_dev, which with the slab setting off IS efa_obs_impact_dev.
+int obs_impact(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const double* werr_dev, const double* Ya_dev, const ObsIn& ob,
+               const double* grid_lat, const double* grid_lon, long ncol, long n_lead, double* impact, bool slab_entry) {
+  const bool slab = slab_entry && c->sl_on;
+  const char* me = slab ? "efa_obs_impact_slab_dev" : "efa_obs_impact_dev";
+  const double *innov = ob.value, *ob_error = ob.error, *ob_lat = ob.lat, *ob_lon = ob.lon, *ob_hw = ob.hw;
+  const uint8_t* ob_used = ob.assim;
+  const int loc_mode = ob.loc_mode;
   const bool gc = loc_mode == EFA_LOC_GC;
   if (loc_mode != EFA_LOC_NONE && !gc) return fail(EFA_ERR_INVALID, "%s: loc_mode %d is neither EFA_LOC_NONE nor EFA_LOC_GC", me, loc_mode);
   if (M < 2 || M > kMaxMembers) return fail(EFA_ERR_INVALID, "%s: M=%d must be in [2,%d]", me, M, kMaxMembers);
@@ -507,26 +511,6 @@ static int impact_call(efa_ctx* c, const char* me, bool slab, long rows, int M, 
   EFA_HIP(hipEventElapsedTime(&ms, c->imp_iv.begin, c->imp_iv.end));
   c->impact_us = (long)std::llround((double)ms * 1000.0);
   return EFA_OK;
-}
-
-int obs_impact(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const double* werr_dev, const double* Ya_dev,
-               const double* innov, const double* ob_error, const uint8_t* ob_used, int loc_mode, const double* ob_lat,
-               const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
-               double* impact) {
-  return impact_call(c, "efa_obs_impact_dev", false, rows, M, P, Xf_dev, werr_dev, Ya_dev, innov, ob_error, ob_used, loc_mode, ob_lat,
-                     ob_lon, ob_hw, grid_lat, grid_lon, ncol, n_lead, impact);
-}
-
-// efa_obs_impact_slab_dev: with the slab setting off it IS efa_obs_impact_dev
-int obs_impact_slab(efa_ctx* c, long rows, int M, long P, const double* Xf_dev, const double* werr_dev, const double* Ya_dev,
-                    const double* innov, const double* ob_error, const uint8_t* ob_used, int loc_mode, const double* ob_lat,
-                    const double* ob_lon, const double* ob_hw, const double* grid_lat, const double* grid_lon, long ncol, long n_lead,
-                    double* impact) {
-  if (!c->sl_on)
-    return obs_impact(c, rows, M, P, Xf_dev, werr_dev, Ya_dev, innov, ob_error, ob_used, loc_mode, ob_lat, ob_lon, ob_hw, grid_lat,
-                      grid_lon, ncol, n_lead, impact);
-  return impact_call(c, "efa_obs_impact_slab_dev", true, rows, M, P, Xf_dev, werr_dev, Ya_dev, innov, ob_error, ob_used, loc_mode,
-                     ob_lat, ob_lon, ob_hw, grid_lat, grid_lon, ncol, n_lead, impact);
 }
 
 }  // namespace efa_host

@@ -72,24 +72,24 @@ int letkf_check_settings(const efa_ctx* c, const char* who, int M, long P, bool 
   return EFA_OK;
 }
 
-int letkf_check_obs(const char* who, long P, const LetkfObsIn& in) {
+int letkf_check_obs(const char* who, long P, const double* ym_dev, const double* Yp_dev, const ObsIn& in) {
   if (P == 0) return EFA_OK;
-  if (!in.ym_dev || !in.Yp_dev || !in.ob_value || !in.ob_error || !in.ob_assim)
+  if (!ym_dev || !Yp_dev || !in.value || !in.error || !in.assim)
     return fail(EFA_ERR_INVALID, "%s: null observation array", who);
-  if (!in.ob_lat || !in.ob_lon || !in.ob_hw) return fail(EFA_ERR_INVALID, "%s: the taper needs ob_lat/ob_lon/ob_halfwidth_km", who);
+  if (!in.lat || !in.lon || !in.hw) return fail(EFA_ERR_INVALID, "%s: the taper needs ob_lat/ob_lon/ob_halfwidth_km", who);
   for (long k = 0; k < P; ++k) {
-    if (!in.ob_assim[k]) continue;
-    if (!(std::isfinite(in.ob_error[k]) && in.ob_error[k] > 0.0))
+    if (!in.assim[k]) continue;
+    if (!(std::isfinite(in.error[k]) && in.error[k] > 0.0))
       return fail(EFA_ERR_INVALID, "%s: observation %ld: error variance %g must be finite and > 0 (R-localisation divides by it)", who, k,
-                  in.ob_error[k]);
-    if (!(in.ob_hw[k] == in.ob_hw[k]) || in.ob_hw[k] == 0.0)
+                  in.error[k]);
+    if (!(in.hw[k] == in.hw[k]) || in.hw[k] == 0.0)
       return fail(EFA_ERR_INVALID, "%s: observation %ld: localize_radius must be a non-zero number", who, k);
   }
   return EFA_OK;
 }
 
 // the obs on the device, then their prior diagnostics, effective flags and {d, r}
-int letkf_stage_obs(efa_ctx* c, int M, long P, const LetkfObsIn& in, LetkfObs* out) {
+int letkf_stage_obs(efa_ctx* c, int M, long P, const double* ym_dev, const double* Yp_dev, const ObsIn& in, LetkfObs* out) {
   hipStream_t s = c->stream;
   const size_t n = (size_t)P;
   // value | error | lat | lon | hw | requested [n each] | act [4n] | dr [2n] | obtrig [6n] | four diagnostics [n each] | assimilated bytes
@@ -114,17 +114,17 @@ int letkf_stage_obs(efa_ctx* c, int M, long P, const LetkfObsIn& in, LetkfObs* o
   // value and error of an ob that is not requested are not read: the device gets the neutral pair (0, 1), its radius a harmless 1
   std::vector<double> h(6 * n);
   for (size_t k = 0; k < n; ++k) {
-    const bool on = in.ob_assim[k] != 0;
-    h[k] = on ? in.ob_value[k] : 0.0;
-    h[n + k] = on ? in.ob_error[k] : 1.0;
-    h[2 * n + k] = in.ob_lat[k];
-    h[3 * n + k] = in.ob_lon[k];
-    h[4 * n + k] = on ? in.ob_hw[k] : 1.0;
+    const bool on = in.assim[k] != 0;
+    h[k] = on ? in.value[k] : 0.0;
+    h[n + k] = on ? in.error[k] : 1.0;
+    h[2 * n + k] = in.lat[k];
+    h[3 * n + k] = in.lon[k];
+    h[4 * n + k] = on ? in.hw[k] : 1.0;
     h[5 * n + k] = on ? 1.0 : 0.0;
   }
   EFA_HIP(hipMemcpyAsync(d, h.data(), 6 * n * sizeof(double), hipMemcpyHostToDevice, s));
   EFA_HIP(hipStreamSynchronize(s));  // (h goes out of scope)
-  EFA_HIP(launch_letkf_prior(P, M, in.Yp_dev, in.ym_dev, o.value, o.error, o.req, c->qc_threshold * c->qc_threshold, o.prior_mean,
+  EFA_HIP(launch_letkf_prior(P, M, Yp_dev, ym_dev, o.value, o.error, o.req, c->qc_threshold * c->qc_threshold, o.prior_mean,
                              o.prior_var, o.assimilated, o.act, o.dr, s));
   *out = o;
   return EFA_OK;
@@ -346,9 +346,9 @@ const char* letkf_cycle_name(bool slab, bool mesh, bool f32) {
 
 }  // namespace
 
-int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const LetkfObsIn& obs, double* ym_out, double* Yp_out, const double* grid_lat,
-                const double* grid_lon, long ncol, long n_lead, const LetkfDiagOut& diag, double* col_stats_dev, const LetkfMesh* mesh,
-                bool slab) {
+int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const double* ym_dev, const double* Yp_dev, const ObsIn& ob, double* ym_out,
+                double* Yp_out, const double* grid_lat, const double* grid_lon, long ncol, long n_lead, const DiagOut& diag,
+                double* col_stats_dev, const LetkfMesh* mesh, bool slab) {
   const long rows = r.rows;
   const int M = r.M;
   const char* who = letkf_cycle_name(slab, mesh != nullptr, r.elem == Elem::f32);
@@ -361,8 +361,7 @@ int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const LetkfObsIn& obs, d
   }
   EFA_TRY(letkf_check_rows(who, r));
   if (rows > 0) EFA_TRY(check_grid(EFA_LOC_GC, grid_lat, grid_lon, ncol, n_lead, rows));
-  EFA_TRY(letkf_check_obs(who, P, obs));
-  const double *ym_dev = obs.ym_dev, *Yp_dev = obs.Yp_dev;
+  EFA_TRY(letkf_check_obs(who, P, ym_dev, Yp_dev, ob));
   hipStream_t s = c->stream;
   harvest_obs_ms(c);
   harvest_state_ms(c);
@@ -377,7 +376,7 @@ int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const LetkfObsIn& obs, d
   LetkfLists lists;
   double *Yw = nullptr, *ymw = nullptr;
   if (P > 0) {
-    EFA_TRY(letkf_stage_obs(c, M, P, obs, &o));
+    EFA_TRY(letkf_stage_obs(c, M, P, ym_dev, Yp_dev, ob, &o));
     EFA_TRY(c->letkf_Yw.reserve(((size_t)P * M + (size_t)P) * sizeof(double)));
     Yw = c->letkf_Yw.as<double>();
     ymw = Yw + (size_t)P * M;
@@ -483,27 +482,27 @@ int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const LetkfObsIn& obs, d
   return EFA_OK;
 }
 
-int letkf_weights(efa_ctx* c, int M, long P, const LetkfObsIn& obs, long npts, const double* pt_lat, const double* pt_lon, double* Tw_dev,
-                  double* stats_dev, bool slab) {
+int letkf_weights(efa_ctx* c, int M, long P, const double* ym_dev, const double* Yp_dev, const ObsIn& ob, long npts, const double* pt_lat,
+                  const double* pt_lon, double* Tw_dev, double* stats_dev, bool slab) {
   const char* who = slab ? "efa_letkf_slab_weights_dev" : "efa_letkf_weights_dev";
   const long n_lead = c->sl_on ? c->sl_nlead : c->vl_nlead;  // (slab: the slabs are the settings' own)
   EFA_TRY(letkf_check_settings(c, who, M, P, slab, slab ? n_lead : -1));
   if (npts < 0) return fail(EFA_ERR_INVALID, "%s: negative point count", who);
   if (npts > 0 && (!pt_lat || !pt_lon || !Tw_dev)) return fail(EFA_ERR_INVALID, "%s: null point or output array", who);
-  EFA_TRY(letkf_check_obs(who, P, obs));
+  EFA_TRY(letkf_check_obs(who, P, ym_dev, Yp_dev, ob));
   if (npts == 0) return EFA_OK;
   hipStream_t s = c->stream;
   LetkfObs o;
   LetkfLists lists;
   if (P > 0) {
     const double *dlat = nullptr, *dlon = nullptr;
-    EFA_TRY(letkf_stage_obs(c, M, P, obs, &o));
+    EFA_TRY(letkf_stage_obs(c, M, P, ym_dev, Yp_dev, ob, &o));
     EFA_TRY(letkf_upload_points(c, npts, pt_lat, pt_lon, &dlat, &dlon));
     EFA_TRY(letkf_build_lists(c, npts, dlat, dlon, o, &lists));
   }
   LetkfGroups groups{};
   if (slab) EFA_TRY(letkf_slab_groups(c, n_lead, &groups));
-  EFA_TRY(letkf_solve_points(c, M, npts, lists, obs.Yp_dev, o, slab ? &groups : nullptr, Tw_dev, stats_dev));
+  EFA_TRY(letkf_solve_points(c, M, npts, lists, Yp_dev, o, slab ? &groups : nullptr, Tw_dev, stats_dev));
   EFA_HIP(hipStreamSynchronize(s));
   return EFA_OK;
 }

@@ -34,10 +34,11 @@ namespace {
 // ---- Phase A ---------------------------------------------------------------
 // One obs_phase call: its arguments and the workspace layout that the steps below share.
 struct ObsCall {
-  int M = 0, loc_mode = EFA_LOC_NONE;
+  int M = 0;
   long P = 0;
   double *ym_dev = nullptr, *Yp_dev = nullptr;  // the caller's obs block
-  const uint8_t* ob_assim = nullptr;            // host
+  ObsIn ob;      // the caller's per-ob arrays (host); stage_obs_inputs points ob.hw at the sanitised copy
+  DiagOut diag;  // where the diagnostics go (host)
   SpecRequest spec;      // efa_ensrf_cycle_dev: the transform to put behind the launch (none by default)
   bool carry_T = false;  // M identity rows ride along behind the obs rows: Phase A leaves the transform [T | w] in them
   long extra = 0, R = 0;  // those rows (M or 0); rows of the working block, P + extra
@@ -67,15 +68,16 @@ Window make_window(const ObsCall& a, long w) {
 }
 
 // Argument and radius checks, the host copies of the assimilate flags and the geometry, the per-ob inputs in one pinned pack,
-// the diagnostics pack and the workspaces.  ob_hw comes back sanitised.
-int stage_obs_inputs(efa_ctx* c, ObsCall& a, const double* ob_value, const double* ob_error, const double* ob_lat,
-                     const double* ob_lon, const double*& ob_hw) {
+// the diagnostics pack and the workspaces.  a.ob.hw comes back sanitised.
+int stage_obs_inputs(efa_ctx* c, ObsCall& a) {
   const int M = a.M;
   const long P = a.P;
-  const uint8_t* ob_assim = a.ob_assim;
+  const double *ob_value = a.ob.value, *ob_error = a.ob.error, *ob_lat = a.ob.lat, *ob_lon = a.ob.lon;
+  const double*& ob_hw = a.ob.hw;
+  const uint8_t* ob_assim = a.ob.assim;
   if (!a.ym_dev || !a.Yp_dev || !ob_value || !ob_error || !ob_assim)
     return fail(EFA_ERR_INVALID, "null observation array");
-  if (a.loc_mode == EFA_LOC_GC) {
+  if (a.ob.loc_mode == EFA_LOC_GC) {
     if (!ob_lat || !ob_lon || !ob_hw) return fail(EFA_ERR_INVALID, "GC localisation needs ob_lat/ob_lon/ob_halfwidth_km");
     // the reference reads localize_radius only for obs it assimilates (ensrf.py:74-76 comes before :101):
     // an unassimilated ob may carry any radius; it is replaced by a harmless one before it goes to the device
@@ -93,7 +95,7 @@ int stage_obs_inputs(efa_ctx* c, ObsCall& a, const double* ob_value, const doubl
   }
   c->h_assim.assign(ob_assim, ob_assim + P);
   for (long k = 0; k < P; ++k) c->n_active += ob_assim[k] ? 1 : 0;
-  if (a.loc_mode == EFA_LOC_GC) {
+  if (a.ob.loc_mode == EFA_LOC_GC) {
     const size_t nb8 = (size_t)P * sizeof(double);
     const bool same = (long)c->geo_lat.size() == P && std::memcmp(c->geo_lat.data(), ob_lat, nb8) == 0 &&
                       std::memcmp(c->geo_lon.data(), ob_lon, nb8) == 0 && std::memcmp(c->geo_hw.data(), ob_hw, nb8) == 0 &&
@@ -110,7 +112,7 @@ int stage_obs_inputs(efa_ctx* c, ObsCall& a, const double* ob_value, const doubl
     }
   }
 
-  a.carry_T = (a.loc_mode == EFA_LOC_NONE) && transform_supported(M) && (c->path != EFA_PATH_SWEEP);
+  a.carry_T = (a.ob.loc_mode == EFA_LOC_NONE) && transform_supported(M) && (c->path != EFA_PATH_SWEEP);
   a.extra = a.carry_T ? M : 0;
   a.R = P + a.extra;
   const size_t dP = (size_t)P * sizeof(double);
@@ -119,7 +121,7 @@ int stage_obs_inputs(efa_ctx* c, ObsCall& a, const double* ob_value, const doubl
   // allocation, ONE H2D from pinned memory (the last three slots only with localisation); the four-double records are the band
   // leader's per-ob constants, fetched with wave-uniform loads
   {
-    const bool gc = a.loc_mode == EFA_LOC_GC;
+    const bool gc = a.ob.loc_mode == EFA_LOC_GC;
     const size_t slot = ((size_t)P * sizeof(double) + 255) & ~(size_t)255;
     const size_t total = 10 * slot;
     EFA_TRY(c->ob_pack.reserve(total));
@@ -218,7 +220,7 @@ int start_phase_a(efa_ctx* c, ObsCall& a) {
   if (c->qc_used) {  // the outlier check decides every ob's flag here, ONCE, against the caller's block: windows and redone launches
                      // read the flags it wrote
     double* host_act = nullptr;
-    if (a.loc_mode == EFA_LOC_GC) {
+    if (a.ob.loc_mode == EFA_LOC_GC) {
       EFA_TRY(c->qc_act.reserve((size_t)P * kCoefStride * sizeof(double)));
       host_act = c->qc_act.as<double>();
     }
@@ -246,8 +248,8 @@ int sweep_rows(efa_ctx* c, const ObsCall& a, long b0, int nb, const double* Ye, 
   sw.ye_stride = ye_stride;
   sw.coef = c->coef.as<double>() + (size_t)b0 * kCoefStride;
   sw.nb = nb;
-  sw.taper_mode = (a.loc_mode == EFA_LOC_GC) ? kTaperObs : kTaperNone;
-  if (a.loc_mode == EFA_LOC_GC && sl_active(c)) {  // ... times the temporal and variable factors, likewise
+  sw.taper_mode = (a.ob.loc_mode == EFA_LOC_GC) ? kTaperObs : kTaperNone;
+  if (a.ob.loc_mode == EFA_LOC_GC && sl_active(c)) {  // ... times the temporal and variable factors, likewise
     const bool vert = vl_active(c);
     EFA_TRY(c->vl_W.reserve((size_t)nb * a.R * sizeof(double)));
     EFA_HIP(launch_obs_taper_rows_slab(b0, nb, a.R, a.P, c->ob_lat, c->ob_lon, c->ob_hw, vert ? vl_obvert(c) : nullptr,
@@ -255,7 +257,7 @@ int sweep_rows(efa_ctx* c, const ObsCall& a, long b0, int nb, const double* Ye, 
     sw.taper_mode = kTaperTable;
     sw.W = c->vl_W.as<double>();
     sw.ncol = a.R;
-  } else if (a.loc_mode == EFA_LOC_GC && vl_active(c)) {  // horizontal x vertical taper of the batch against every row, in table mode
+  } else if (a.ob.loc_mode == EFA_LOC_GC && vl_active(c)) {  // horizontal x vertical taper of the batch against every row, in table mode
     EFA_TRY(c->vl_W.reserve((size_t)nb * a.R * sizeof(double)));
     EFA_HIP(launch_obs_taper_rows(b0, nb, a.R, a.P, c->ob_lat, c->ob_lon, c->ob_hw, vl_obvert(c), vl_obvhw(c), c->vl_W.as<double>(),
                                   c->stream));
@@ -281,7 +283,7 @@ int sweep_rows(efa_ctx* c, const ObsCall& a, long b0, int nb, const double* Ye, 
 
 long active_in(const ObsCall& a, long b0, int nb) {
   long act = 0;
-  for (int k = 0; k < nb; ++k) act += a.ob_assim[b0 + k] ? 1 : 0;
+  for (int k = 0; k < nb; ++k) act += a.ob.assim[b0 + k] ? 1 : 0;
   return act;
 }
 
@@ -289,7 +291,7 @@ long active_in(const ObsCall& a, long b0, int nb) {
 // (With vertical or slab localisation one ob per batch: k_diag's in-batch taper is horizontal only, and an ob's taper against itself
 // is 1.  With the sampling error correction likewise: k_diag applies none, and an ob's factor against itself is 1)
 int batch_window(efa_ctx* c, const ObsCall& a, long w0, long w1) {
-  const long B = (a.loc_mode == EFA_LOC_GC && (vl_active(c) || sl_active(c) || sec_active(c))) ? 1 : a.B;
+  const long B = (a.ob.loc_mode == EFA_LOC_GC && (vl_active(c) || sl_active(c) || sec_active(c))) ? 1 : a.B;
   for (long b0 = w0; b0 < w1; b0 += B) {
     const int nb = (int)((w1 - b0 < B) ? (w1 - b0) : B);
     DiagArgs d{};
@@ -301,7 +303,7 @@ int batch_window(efa_ctx* c, const ObsCall& a, long w0, long w1) {
     d.ob_value = c->ob_val;
     d.ob_error = c->ob_err;
     d.ob_assim = c->ob_asm;
-    d.loc_mode = a.loc_mode;
+    d.loc_mode = a.ob.loc_mode;
     d.ob_lat = c->ob_lat;
     d.ob_lon = c->ob_lon;
     d.ob_hw = c->ob_hw;
@@ -372,9 +374,9 @@ int window_pipe_args(efa_ctx* c, const ObsCall& a, const Window& win, PipeArgs* 
   pa.ob_error = c->ob_err + w0;
   pa.ob_assim = c->ob_asm + w0;
   pa.ob_errsq = c->ob_errsq + 4 * w0;
-  pa.loc_mode = a.loc_mode;
+  pa.loc_mode = a.ob.loc_mode;
   pa.tw = nullptr;
-  if (a.loc_mode == EFA_LOC_GC) {
+  if (a.ob.loc_mode == EFA_LOC_GC) {
     EFA_TRY(c->tw_mat.reserve((size_t)Pw * Rw * sizeof(double)));
     EFA_TRY(c->gc_obtrig.reserve((size_t)Pw * 6 * sizeof(double)));
     const bool tw_ok = c->geometry_reuse && win.direct && c->tw_serial == c->geo_serial && c->tw_Pw == Pw && c->tw_Rw == Rw &&
@@ -417,8 +419,8 @@ int window_pipe_args(efa_ctx* c, const ObsCall& a, const Window& win, PipeArgs* 
 // after standard records a later window does not start with the band leader, and after band records it tries nothing but the band
 // leader (it goes to the per-batch kernels instead).  A 0 ends the list.
 std::array<int, 2> window_kinds(const efa_ctx* c, const ObsCall& a, long Rw, Records layout) {
-  const bool band = c->use_gram >= 2 && pipeline_band_supported(a.M, Rw, a.loc_mode);
-  const bool gram = c->use_gram >= 1 && pipeline_gram_supported(a.M, Rw, a.loc_mode);
+  const bool band = c->use_gram >= 2 && pipeline_band_supported(a.M, Rw, a.ob.loc_mode);
+  const bool gram = c->use_gram >= 1 && pipeline_gram_supported(a.M, Rw, a.ob.loc_mode);
   const int first = (band && layout != Records::kStandard) ? 4 : gram ? 3 : 1;
   if (layout == Records::kBand) return {first == 4 ? 4 : 0, 0};
   return {first, first == 1 ? 0 : 1};
@@ -543,9 +545,9 @@ int merge_window_into_block(efa_ctx* c, const ObsCall& a, const Window& win, Rec
 }
 
 // Where Phase B finds the records, the obs block and the diagnostics back to the caller (ensrf.py:66,70,75,146-149)
-int finish_obs_phase(efa_ctx* c, const ObsCall& a, Records layout, bool diag_on_host, const SpecResult& spec, double* prior_mean,
-                     double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated) {
+int finish_obs_phase(efa_ctx* c, const ObsCall& a, Records layout, bool diag_on_host, const SpecResult& spec) {
   hipStream_t s = c->stream;
+  const DiagOut& o = a.diag;
   const long P = a.P;
   const size_t dP = (size_t)P * sizeof(double), oslot = a.oslot;
   if (layout == Records::kNone) {
@@ -569,16 +571,16 @@ int finish_obs_phase(efa_ctx* c, const ObsCall& a, Records layout, bool diag_on_
     EFA_HIP(hipStreamSynchronize(s));
   }
   const char* hb = static_cast<const char*>(c->pin_out.p);
-  if (prior_mean) std::memcpy(prior_mean, hb, dP);
-  if (prior_var) std::memcpy(prior_var, hb + oslot, dP);
+  if (o.prior_mean) std::memcpy(o.prior_mean, hb, dP);
+  if (o.prior_var) std::memcpy(o.prior_var, hb + oslot, dP);
   const double* pm = reinterpret_cast<const double*>(hb + 2 * oslot);
   const double* pv = reinterpret_cast<const double*>(hb + 3 * oslot);
   const uint8_t* as = reinterpret_cast<const uint8_t*>(hb + 4 * oslot);
   for (long k = 0; k < P; ++k) {
-    if (assimilated) assimilated[k] = as[k];
+    if (o.assimilated) o.assimilated[k] = as[k];
     if (as[k]) {
-      if (post_mean) post_mean[k] = pm[k];
-      if (post_var) post_var[k] = pv[k];
+      if (o.post_mean) o.post_mean[k] = pm[k];
+      if (o.post_var) o.post_var[k] = pv[k];
     }
   }
   if (c->qc_used) {  // the outlier check may have rejected obs: the state phase goes by the flags Phase A went by
@@ -636,17 +638,16 @@ int check_batch_obs(const efa_ctx* c, long P, const double* ob_error, const uint
   return EFA_OK;
 }
 
-int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const double* ob_value,
-              const double* ob_error, const uint8_t* ob_assim, int loc_mode, const double* ob_lat,
-              const double* ob_lon, const double* ob_hw, double* prior_mean, double* prior_var,
-              double* post_mean, double* post_var, uint8_t* assimilated, const SpecRequest& spec, SpecResult* spec_out) {
+int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const ObsIn& ob, const DiagOut& diag, const SpecRequest& spec,
+              SpecResult* spec_out) {
+  const int loc_mode = ob.loc_mode;
   EFA_TRY(check_common(M, P));
   if (loc_mode != EFA_LOC_NONE && loc_mode != EFA_LOC_GC) return fail(EFA_ERR_INVALID, "loc_mode %d", loc_mode);
   EFA_TRY(check_vloc(c, loc_mode, P, -1));
   EFA_TRY(check_slab(c, loc_mode, P, -1));
   EFA_TRY(check_sec(c, loc_mode));
   EFA_TRY(check_batch_solver(c, loc_mode));
-  EFA_TRY(check_batch_obs(c, P, ob_error, ob_assim));
+  EFA_TRY(check_batch_obs(c, P, ob.error, ob.assim));
   c->have_traj = false;
   c->batch_solved = false;
   c->M = M;
@@ -665,18 +666,18 @@ int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const d
   ObsCall a;
   a.M = M;
   a.P = P;
-  a.loc_mode = loc_mode;
   a.ym_dev = ym_dev;
   a.Yp_dev = Yp_dev;
-  a.ob_assim = ob_assim;
+  a.ob = ob;
+  a.diag = diag;
   a.spec = spec;
-  EFA_TRY(stage_obs_inputs(c, a, ob_value, ob_error, ob_lat, ob_lon, ob_hw));
+  EFA_TRY(stage_obs_inputs(c, a));
   EFA_TRY(start_phase_a(c, a));
   if (c->obs_solver) {
     SpecResult done;
     c->batch_solved = true;  // (the plan of the transform behind the solver reads it)
     EFA_TRY(batch_solve(c, a, &done));
-    EFA_TRY(finish_obs_phase(c, a, Records::kNone, true, done, prior_mean, prior_var, post_mean, post_var, assimilated));
+    EFA_TRY(finish_obs_phase(c, a, Records::kNone, true, done));
     c->phase_a_kind = 5;
     if (spec_out) *spec_out = done;
     return EFA_OK;
@@ -704,7 +705,7 @@ int obs_phase(efa_ctx* c, int M, long P, double* ym_dev, double* Yp_dev, const d
       return fail(EFA_ERR_UNSUPPORTED, "internal: mixed Phase-A layouts");
     }
   }
-  EFA_TRY(finish_obs_phase(c, a, layout, diag_on_host, done, prior_mean, prior_var, post_mean, post_var, assimilated));
+  EFA_TRY(finish_obs_phase(c, a, layout, diag_on_host, done));
   if (spec_out) *spec_out = done;
   return EFA_OK;
 }

@@ -185,11 +185,9 @@ long elapsed_us(hipEvent_t a, hipEvent_t b) {
   return (long)(ms * 1000.0f + 0.5f);
 }
 
-int run_pipeline(Pipe& p, long P, const double* HX, const double* ob_value, const double* ob_error, const uint8_t* ob_assim,
-                 int loc_mode, const double* ob_lat, const double* ob_lon, const double* ob_hw, const double* grid_lat,
-                 const double* grid_lon, double* prior_mean, double* prior_var, double* post_mean, double* post_var,
-                 uint8_t* assimilated) {
+int run_pipeline(Pipe& p, long P, const double* HX, const ObsIn& ob, const double* grid_lat, const double* grid_lon, const DiagOut& diag) {
   efa_ctx* c = p.c;
+  const int loc_mode = ob.loc_mode;
   StreamState& st = c->st;
   const Call& k = p.k;
   hipStream_t s = c->stream;
@@ -223,8 +221,7 @@ int run_pipeline(Pipe& p, long P, const double* HX, const double* ob_value, cons
   long issued = 0;
   const long ahead = k.in_pinned ? StreamState::kRing - 1 : 1;
   for (; issued < k.nchunk && issued < ahead; ++issued) EFA_TRY(issue_upload(p, issued));
-  EFA_TRY(obs_phase(c, M, P, st.ym.as<double>(), st.HX.as<double>(), ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon, ob_hw,
-                    prior_mean, prior_var, post_mean, post_var, assimilated));
+  EFA_TRY(obs_phase(c, M, P, st.ym.as<double>(), st.HX.as<double>(), ob, diag));
   long launches = 0;
   int rc = EFA_OK;
   for (long i = 0; i < k.nchunk && rc == EFA_OK; ++i) {
@@ -260,10 +257,9 @@ int run_pipeline(Pipe& p, long P, const double* HX, const double* ob_value, cons
 
 // efa_ensrf_cycle_host and efa_ensrf_cycle_host_f32: the state segments hold elements of esz bytes
 int cycle_host(efa_ctx* c, size_t esz, int n_seg, const void* const* seg_prior, void* const* seg_post, const long* seg_slabs,
-               long ncol, int M, long P, const double* HX, long chunk_cols, const double* ob_value, const double* ob_error,
-               const uint8_t* ob_assim, int loc_mode, const double* ob_lat, const double* ob_lon, const double* ob_halfwidth_km,
-               const double* grid_lat, const double* grid_lon, double* prior_mean, double* prior_var, double* post_mean,
-               double* post_var, uint8_t* assimilated) {
+               long ncol, int M, long P, const double* HX, long chunk_cols, const ObsIn& ob, const double* grid_lat, const double* grid_lon,
+               const DiagOut& diag) {
+  const int loc_mode = ob.loc_mode;
   const char* who = esz == sizeof(float) ? "efa_ensrf_cycle_host_f32" : "efa_ensrf_cycle_host";
   EFA_TRY(use(c));
   const auto t0 = std::chrono::steady_clock::now();
@@ -277,7 +273,7 @@ int cycle_host(efa_ctx* c, size_t esz, int n_seg, const void* const* seg_prior, 
   if (n_seg && (!seg_prior || !seg_post || !seg_slabs)) return fail(EFA_ERR_INVALID, "%s: null segment table", who);
   if (P && !HX) return fail(EFA_ERR_INVALID, "%s: null HX", who);
   EFA_TRY(check_batch_solver(c, loc_mode));  // (before the first upload)
-  EFA_TRY(check_batch_obs(c, P, ob_error, ob_assim));
+  EFA_TRY(check_batch_obs(c, P, ob.error, ob.assim));
   Pipe p{};
   p.c = c;
   Call& k = p.k;
@@ -354,8 +350,7 @@ int cycle_host(efa_ctx* c, size_t esz, int n_seg, const void* const* seg_prior, 
   }
   st.chunks = k.nchunk;
   st.peak_bytes = (long)ring_bytes;
-  const int rc = run_pipeline(p, P, HX, ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon, ob_halfwidth_km, grid_lat, grid_lon,
-                              prior_mean, prior_var, post_mean, post_var, assimilated);
+  const int rc = run_pipeline(p, P, HX, ob, grid_lat, grid_lon, diag);
   if (rc != EFA_OK) {  // nothing of the call may still be in flight on the way out: it reads and writes the caller's memory
     const std::string msg = efa_last_error();
     (void)hipStreamSynchronize(p.up);
@@ -403,8 +398,8 @@ int efa_ensrf_cycle_host(efa_ctx* c, int n_seg, const double* const* seg_prior, 
                          const double* ob_halfwidth_km, const double* grid_lat, const double* grid_lon, double* prior_mean,
                          double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated) {
   return cycle_host(c, sizeof(double), n_seg, reinterpret_cast<const void* const*>(seg_prior), reinterpret_cast<void* const*>(seg_post),
-                    seg_slabs, ncol, M, P, HX, chunk_cols, ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon, ob_halfwidth_km,
-                    grid_lat, grid_lon, prior_mean, prior_var, post_mean, post_var, assimilated);
+                    seg_slabs, ncol, M, P, HX, chunk_cols, obs_in(ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon, ob_halfwidth_km),
+                    grid_lat, grid_lon, diag_out(prior_mean, prior_var, post_mean, post_var, assimilated));
 }
 
 int efa_ensrf_cycle_host_f32(efa_ctx* c, int n_seg, const float* const* seg_prior, float* const* seg_post, const long* seg_slabs,
@@ -413,8 +408,8 @@ int efa_ensrf_cycle_host_f32(efa_ctx* c, int n_seg, const float* const* seg_prio
                              const double* ob_lon, const double* ob_halfwidth_km, const double* grid_lat, const double* grid_lon,
                              double* prior_mean, double* prior_var, double* post_mean, double* post_var, uint8_t* assimilated) {
   return cycle_host(c, sizeof(float), n_seg, reinterpret_cast<const void* const*>(seg_prior), reinterpret_cast<void* const*>(seg_post),
-                    seg_slabs, ncol, M, P, HX, chunk_cols, ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon, ob_halfwidth_km,
-                    grid_lat, grid_lon, prior_mean, prior_var, post_mean, post_var, assimilated);
+                    seg_slabs, ncol, M, P, HX, chunk_cols, obs_in(ob_value, ob_error, ob_assim, loc_mode, ob_lat, ob_lon, ob_halfwidth_km),
+                    grid_lat, grid_lon, diag_out(prior_mean, prior_var, post_mean, post_var, assimilated));
 }
 
 }  // extern "C"
