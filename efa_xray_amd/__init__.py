@@ -11,6 +11,7 @@ from efa_xray_amd.assimilation.assimilation import Assimilation
 from efa_xray_amd.assimilation.ensrf import EnSRF
 from efa_xray_amd.assimilation.etkf import ETKF
 from efa_xray_amd.assimilation.letkf import LETKF, SlabLETKF
+from efa_xray_amd.assimilation.letkf_inflation import ColumnInflation
 from efa_xray_amd.assimilation.adaptive_inflation import AdaptiveInflation
 from efa_xray_amd.assimilation.sampling_error import sampling_error_table
 from efa_xray_amd.postprocess.impact import observation_impact
@@ -22,7 +23,7 @@ from efa_xray_amd.postprocess.pmmean import probability_matched_mean
 from efa_xray_amd.postprocess.modes import (ensemble_gram, ensemble_eofs, ensemble_clusters, distances_from_gram,
                                             eofs_from_gram, clusters_from_gram)
 
-__all__ = ["EnsembleState", "Observation", "gaspari_cohn", "haversine", "Assimilation", "EnSRF", "ETKF", "LETKF", "SlabLETKF", "AdaptiveInflation",
+__all__ = ["EnsembleState", "Observation", "gaspari_cohn", "haversine", "Assimilation", "EnSRF", "ETKF", "LETKF", "SlabLETKF", "ColumnInflation", "AdaptiveInflation",
            "observation_impact", "ensemble_sensitivity", "observation_targets",
            "ensemble_verification", "ensemble_products", "probability_verification",
            "ensemble_gram", "ensemble_eofs", "ensemble_clusters", "distances_from_gram", "eofs_from_gram", "clusters_from_gram",

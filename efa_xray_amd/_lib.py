@@ -52,6 +52,8 @@ SIGNATURES = {
     "efa_inflate_rows_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "efa_ctx_set_adaptive_inflation": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_double,
                                                       ctypes.c_double, ctypes.c_double]),
+    "efa_ctx_set_letkf_inflation": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long,
+                                                   ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
     "efa_ctx_set_vertical_localization": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, c_double_p, ctypes.c_long,
                                                          c_double_p, c_double_p]),
     "efa_ctx_set_slab_localization": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, c_double_p, c_int32_p, ctypes.c_long,
@@ -522,6 +524,18 @@ class Context(object):
         (mean, sd) array updated in place, or None to turn it off."""
         _check(self.lib, self.lib.efa_ctx_set_adaptive_inflation(self.handle, self._addr(field), int(rows), float(lower),
                                                                  float(upper), float(sd_lower)))
+
+    def set_letkf_inflation(self, field, ob_infl=None, P=0, sigma_b=0.0, lower=1e-2, upper=1e2, stats=None):
+        """Per-point multiplicative inflation of every later LETKF call on this context (Miyoshi 2011): `field` a
+        float64 DeviceArray of one factor per solve point ([ngroups][columns, nodes or probe points]), updated in place when
+        sigma_b > 0, or None to turn it off; ob_infl: a DeviceArray [P] of the obs' own factors or None (1.0); stats: a
+        DeviceArray [nsolve][4] for {p1, p2, p3, lambda_o} or None."""
+        if field is None:
+            _check(self.lib, self.lib.efa_ctx_set_letkf_inflation(self.handle, None, 0, None, 0, 0.0, 1.0, 1.0, None))
+            return
+        _check(self.lib, self.lib.efa_ctx_set_letkf_inflation(self.handle, self._addr(field), int(np.prod(field.shape, dtype=np.int64)),
+                                                              self._addr(ob_infl),
+                                                              int(P), float(sigma_b), float(lower), float(upper), self._addr(stats)))
 
     def set_vertical_localization(self, lead_vert=None, ob_vert=None, ob_vert_halfwidth=None):
         """Vertical localisation of every later GC cycle on this context: host arrays lead_vert [n_lead] and

@@ -29,11 +29,20 @@ plain filter.
 pair: slabs whose factors agree for every observation form a group, and every (group, column) runs its own solve under the
 product taper.  `last_solve` then holds `n_local`, `dfs` and `sweeps` of shape (ngroups, ny, nx) -- (ngroups, nyn, nxn) with a
 weight_stride -- and `group_of_slab` of shape (nvars, ntimes).  With none of the three options it is `LETKF`, bit for bit.
+
+`column_inflation=ColumnInflation(...)` (letkf_inflation.py) gives every solve point a multiplicative inflation
+factor that enters its solve as Hunt's rho and is re-estimated from the innovations after Miyoshi (2011).  Its `values` have the
+shape of `last_solve`'s arrays -- (ny, nx), (nyn, nxn) with a weight_stride, a leading ngroups axis under `SlabLETKF`'s options --
+and hold the factors for the NEXT update once this one returns; `last_solve` gains `inflation` (the factors this update used),
+`inflation_post` and `inflation_stats` (..., 4) = (p1, p2, p3, lambda_o).  Observations with the default point interpolation are
+solved under that interpolation of the field, observations with a user-defined forward operator under 1.0.  This is the LETKF's
+adaptive inflation; `adaptive_inflation` (Anderson 2009, tied to the serial filter's order) stays refused.
 """
 import numpy as np
 
 from efa_xray_amd import _lib
 from efa_xray_amd.assimilation.ensrf import EnSRF
+from efa_xray_amd.assimilation.letkf_inflation import ColumnInflation, expand_nodes, ob_factors
 
 MAX_MEMBERS = 136
 
@@ -68,11 +77,14 @@ class LETKF(EnSRF):
     def __init__(self, state, obs, nproc=1, inflation=None, verbose=True, **kw):
         """Keyword-only options, as `EnSRF` has them: loc ('GC', the default and the only value), device, rtps / rtpp,
         outlier_threshold; float32 states work as they do there; weight_stride (None, an int >= 1 or a pair of them: the module's
-        docstring).  ValueError, before any device work, for loc other than 'GC'
+        docstring); column_inflation (None or a `ColumnInflation`).  ValueError, before any device work, for loc other than 'GC'
         (use `ETKF` for the unlocalised filter), adaptive_inflation, vert_coord, time_localize, var_impact,
         sampling_error_correction, streamed, path, obs_batch, a weight_stride that is not an integer >= 1, and for more than 136 members (the eigen-solve of a column keeps
         its M x M array in LDS).  `update_arrays` is not offered."""
         stride = _weight_stride(kw.pop("weight_stride", None))
+        ci = kw.pop("column_inflation", None)
+        if ci is not None and not isinstance(ci, ColumnInflation):
+            raise ValueError("column_inflation must be a ColumnInflation, got %r" % type(ci).__name__)
         loc = kw.pop("loc", "GC")
         if not (isinstance(loc, str) and loc == "GC"):
             raise ValueError("LETKF: loc=%r is not supported: the LETKF is the localised filter and takes loc='GC' only; "
@@ -89,6 +101,7 @@ class LETKF(EnSRF):
         EnSRF.__init__(self, state, obs, nproc, inflation, verbose, "GC", **kw)
         self.last_solve = None
         self.weight_stride = stride
+        self.column_inflation = ci
 
     _cycle_line = "Beginning the column solves"
 
@@ -116,16 +129,30 @@ class LETKF(EnSRF):
             sy, sx = node_y.size, node_x.size
             mesh = dict(shape=(ny, nx), stride=self.weight_stride)
         ng = 1                                  # solves per column or node
+        ci = self.column_inflation
         try:
             if slab:
                 group_of, ng = ctx.letkf_slab_groups(n_lead)
             stats = ctx.empty((ng * sy * sx, 3))
+            if ci is not None:                  # one factor per solve point, in the statistics' layout
+                lam_shape = ((ng,) if slab else ()) + (sy, sx)
+                lam_b = ci.field(lam_shape).copy()
+                lam_dev = ctx.to_device(lam_b.reshape(-1))
+                lam_stats = ctx.empty((ng * sy * sx, 4))
+                cols = lam_b.reshape(ng, sy, sx)
+                if mesh:
+                    cols = expand_nodes(cols, node_y, node_x, ny, nx)
+                lam_ob = self._ob_inflation(ctx, P, cols.reshape(ng, ny * nx), group_of if slab else np.zeros(n_lead, dtype=np.int64))
+                lam_ob_dev = None if lam_ob is None else ctx.to_device(np.clip(lam_ob, ci.lower, ci.upper))   # (held: an address)
+                ctx.set_letkf_inflation(lam_dev, lam_ob_dev, P, ci.sigma_b, ci.lower, ci.upper, lam_stats)
             diag = ctx.letkf_cycle(N, M, P, X, X, ym, Yp, *(ob[:3] + ob[4:] + geometry), col_stats=stats,
                                    f32=prior.dtype == np.float32, _slab=slab, **mesh)
         finally:
             if slab:                            # the context is shared per device: the settings do not outlive the update
                 ctx.set_vertical_localization(None)
                 ctx.set_slab_localization(None)
+            if ci is not None:
+                ctx.set_letkf_inflation(None)
         st = stats.download().reshape(ng, sy, sx, 3)
         if not slab:                            # the plain filter documents (ny, nx) / (nyn, nxn)
             st = st[0]
@@ -134,7 +161,19 @@ class LETKF(EnSRF):
             self.last_solve.update(group_of_slab=group_of.astype(np.int64).reshape(prior.nvars(), prior.ntimes()))
         if mesh:
             self.last_solve.update(node_y=node_y, node_x=node_x)
+        if ci is not None:
+            ci.values = lam_dev.download().reshape(lam_shape)       # the next update's prior factors
+            self.last_solve.update(inflation=lam_b, inflation_post=ci.values.copy(),
+                                   inflation_stats=lam_stats.download().reshape(lam_shape + (4,)))
         return diag
+
+    def _ob_inflation(self, ctx, P, field_cols, group_of):
+        """The factor of every ob's own solve: its point interpolation applied to the field (ngroups, ncol); None (1.0 for all)
+        without obs and for user-defined forward operators."""
+        if not P or not self._default_forward_operator():
+            return None
+        idx, wts = self._interp_stencils_host(ctx)
+        return ob_factors(field_cols, group_of, idx, wts)
 
     def update_arrays(self, xbm, Xbp):
         raise ValueError("LETKF does not offer update_arrays (out of scope, DESIGN.md 7y); use update()")

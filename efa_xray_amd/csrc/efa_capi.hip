@@ -303,6 +303,34 @@ int efa_ctx_set_adaptive_inflation(efa_ctx* c, double* field_dev, long rows, dou
   return EFA_OK;
 }
 
+int efa_ctx_set_letkf_inflation(efa_ctx* c, double* field_dev, long nsolve, const double* ob_infl_dev, long P, double sigma_b,
+                                double lower, double upper, double* infl_stats_dev) {
+  EFA_TRY(use(c));
+  if (!field_dev) {
+    c->li_field = nullptr;
+    c->li_ob = nullptr;
+    c->li_stats = nullptr;
+    c->li_nsolve = c->li_P = 0;
+    return EFA_OK;
+  }
+  if (nsolve < 0 || P < 0) return fail(EFA_ERR_INVALID, "LETKF inflation: negative count (nsolve=%ld, P=%ld)", nsolve, P);
+  if (((reinterpret_cast<uintptr_t>(field_dev) | reinterpret_cast<uintptr_t>(ob_infl_dev) | reinterpret_cast<uintptr_t>(infl_stats_dev)) & 7u) != 0)
+    return fail(EFA_ERR_INVALID, "LETKF inflation: the arrays must be 8-byte aligned");
+  if (!std::isfinite(sigma_b) || sigma_b < 0.0) return fail(EFA_ERR_INVALID, "LETKF inflation: sigma_b %g must be finite and >= 0", sigma_b);
+  if (!std::isfinite(lower) || !(lower > 0.0)) return fail(EFA_ERR_INVALID, "LETKF inflation: lower bound %g must be finite and > 0", lower);
+  if (!std::isfinite(upper) || upper < lower)
+    return fail(EFA_ERR_INVALID, "LETKF inflation: upper bound %g must be finite and >= the lower bound %g", upper, lower);
+  c->li_field = field_dev;
+  c->li_nsolve = nsolve;
+  c->li_ob = ob_infl_dev;
+  c->li_P = P;
+  c->li_sigma_b = sigma_b;
+  c->li_lower = lower;
+  c->li_upper = upper;
+  c->li_stats = infl_stats_dev;
+  return EFA_OK;
+}
+
 int efa_ctx_set_vertical_localization(efa_ctx* c, long n_lead, const double* lead_vert, long P, const double* ob_vert,
                                       const double* ob_vert_halfwidth) {
   EFA_TRY(use(c));

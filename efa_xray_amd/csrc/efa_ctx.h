@@ -312,6 +312,12 @@ struct efa_ctx {
   DevBuf letkf_pairs; // the list builders' pair counter
   DevBuf letkf_Tw;    // weight interpolation (efa_letkf_cycle_interp_dev, §7y-2): the node pairs [nnodes][M][M+1] ...
   DevBuf letkf_nst;   // ... and the node statistics [nnodes][3] when the caller takes none
+  // --- the LETKF's per-point multiplicative inflation (efa_ctx_set_letkf_inflation): the caller's device arrays
+  double* li_field = nullptr;        // [nsolve] lambda of every solve point, updated in place when li_sigma_b > 0; null: off
+  long li_nsolve = 0, li_P = 0;
+  const double* li_ob = nullptr;     // [P] the factor of every ob's own solve, or null (1.0)
+  double li_sigma_b = 0.0, li_lower = 0.0, li_upper = 0.0;
+  double* li_stats = nullptr;        // [nsolve][4] {p1, p2, p3, lambda_o}, or null
   // --- the LETKF's slab groups (efa_letkf_slab_cycle_dev): slabs whose factors agree for every ob share one solve
   std::vector<int> lg_group_of;                   // [n_lead] the group of every slab, numbered by first appearance
   int lg_ngroups = 0;

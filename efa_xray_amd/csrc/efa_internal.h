@@ -401,6 +401,11 @@ struct LetkfArgs {
   double* stats;      // [npts][3] {n_local, dfs, sweeps} or null
   int relax_kind;     // kLetkfMembers: EFA_RELAX_* and its factor (RTPP folded into f, RTPS fused per row)
   double relax_alpha;
+  // per-point multiplicative inflation: A = (M-1)/lambda I + C; null: lambda = 1 everywhere, no statistics
+  double* infl;         // [ngroups][npts] lambda_b, indexed as stats; read and (infl_sigma2 > 0) written by the point's own workgroup
+  double infl_sigma2;   // the prior variance sigma_b^2 of Miyoshi's (2011) estimate; 0: the field is fixed and never written
+  double infl_lo, infl_hi;  // lambda_a is clipped to [lo, hi]
+  double* infl_stats;   // [ngroups][npts][4] {p1, p2, p3, lambda_o} or null
 };
 int letkf_threads(int M);       // the workgroup size chosen for M members
 size_t letkf_lds_bytes(int M);  // and its dynamic LDS

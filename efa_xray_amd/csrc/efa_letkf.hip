@@ -33,6 +33,10 @@
 // solves once per (slab group, column) under rho_k(c) * S[k][rep[g]], S the slab factor table of §7t; k_letkf_obs_factor scales the
 // tapers of the lists built at the ob positions by the obs-obs factor F(j, k), after which the obs block runs as above.  The driver
 // computes the groups from the host copies of the two settings (letkf_groups).
+// Per-point multiplicative inflation (efa_ctx_set_letkf_inflation): with a.infl the point's prior factor lambda_b
+// enters the solve as Hunt's rho, A_x = (M-1)/lambda_b I + C_x, and with infl_sigma2 > 0 one lane writes back Miyoshi's (2011)
+// estimate lambda_a from p1 = sum_k w_k d_k^2 (entry (M, M) of the Gram product), p2 = trace(C_x)/(M-1) (its diagonal before the
+// shift) and p3 = sum_k rho_k (the n_local loop).  A uniform run-time branch: a.infl == nullptr is the kernel without it.
 // This file holds the kernels and their launchers only.
 #include "efa_driver.h"
 #include "efa_device.h"
@@ -50,7 +54,7 @@ typedef double letkf_v4 __attribute__((ext_vector_type(4)));
 constexpr int kLetkfChunk = 32;  // obs per stage: 8 MFMA steps of 4
 constexpr int kLetkfRows = 4;    // rows per apply batch (one wave each for the row reductions)
 constexpr int kLetkfTiles = 3;   // tiles a wave may own
-constexpr int kLetkfSmall = 16;  // doubles of per-row scalars: mean [4] | xam [4] | ssb [4] | (unused) [4]
+constexpr int kLetkfSmall = 16;  // doubles of per-row scalars: mean [4] | xam [4] | ssb [4] | inflation scalars [4]
 
 __host__ __device__ inline int letkf_tiles_side(int M) { return (M + 1 + 15) / 16; }
 __host__ __device__ inline int letkf_stage_pitch(int M) { return 16 * (letkf_tiles_side(M) | 1); }
@@ -129,6 +133,33 @@ struct LetkfArgsOf { typedef LetkfArgs type; };
 template <>
 struct LetkfArgsOf<true> { typedef LetkfSlabArgs type; };
 
+// The inflation estimate of a point (Miyoshi 2011), by one lane, from the sums the solve left in sc = lambda_b | p3 |
+// p1 | trace(C): the statistics as computed, and lambda_a over the field unless p2, p3 or the estimate rule it out.  The solve used
+// lambda_b.  Called at the kernel's exits, where nothing else is live.
+__device__ __forceinline__ void letkf_inflation_estimate(size_t pt, int M, const double* sc) {
+  // its four parameters are read HERE from the kernel's argument block, not held in scalar registers from the entry on: the slab
+  // launch has none to spare, and what does not fit goes to vector registers and costs it a wave per SIMD
+  // (k_letkf's only parameter is a LetkfArgs or begins with one, LetkfSlabArgs' base: the kernel's argument block is one)
+  typedef const __attribute__((address_space(4))) LetkfArgs* letkf_kernarg_ptr;
+  const auto& a = *(letkf_kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+  if (!a.infl_stats && !(a.infl_sigma2 > 0.0)) return;
+  const double lb = sc[0], p3 = sc[1], p1 = sc[2], p2 = sc[3] / (double)(M - 1);
+  const double lo = (p1 - p3) / p2;
+  if (a.infl_stats) {
+    double* st = a.infl_stats + 4 * pt;
+    st[0] = p1;
+    st[1] = p2;
+    st[2] = p3;
+    st[3] = lo;
+  }
+  if (a.infl_sigma2 > 0.0 && p2 > 0.0 && p3 > 0.0 && p2 < __builtin_inf() && p3 < __builtin_inf()) {
+    const double q = (lb * p2 + p3) / p2;
+    const double vo = (2.0 / p3) * (q * q);
+    const double la = lb + a.infl_sigma2 / (vo + a.infl_sigma2) * (lo - lb);
+    if (la - la == 0.0) a.infl[pt] = fmin(fmax(la, a.infl_lo), a.infl_hi);  // a non-finite estimate leaves the field as it is
+  }
+}
+
 template <int MODE, typename E, int NTMAX, bool SLAB = false>
 __global__ __launch_bounds__(NTMAX) void k_letkf(const typename LetkfArgsOf<SLAB>::type a) {
   extern __shared__ __align__(16) double letkf_smem[];
@@ -148,6 +179,7 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const typename LetkfArgsOf<SLAB
   double* mean_s = z_s + kLetkfRows * M;
   double* xam_s = mean_s + kLetkfRows;
   double* ssb_s = xam_s + kLetkfRows;
+  double* infl_s = ssb_s + kLetkfRows;         // inflation (§7y-6): lambda_b | p3 | p1 | trace(C)
   int* rot_s = reinterpret_cast<int*>(mean_s + kLetkfSmall);
   int* nloc_s = rot_s + 2;
 
@@ -172,17 +204,26 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const typename LetkfArgsOf<SLAB
   const long off = a.off ? a.off[blk] : 0;
   const int n = a.cnt ? a.cnt[blk] : 0;
 
-  // n_local: the listed obs whose taper on THIS column is not zero
+  // n_local: the listed obs whose taper on THIS column is not zero; under inflation p3, the sum of those tapers (each lane its
+  // entries in list order, then the butterfly)
+  const bool infl = a.infl != nullptr;  // (uniform)
   if (wave == 0) {
     int cl = 0;
+    double p3 = 0.0;
     for (int e = lane; e < n; e += 64) {
       double w = a.wts[(size_t)(off + e) * 16 + cb];
       if constexpr (SLAB) w = w * Sg[(size_t)a.idx[off + e] * sp];
       cl += (w != 0.0) ? 1 : 0;
+      if (infl && w != 0.0) p3 += w;
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) cl += __shfl_xor(cl, o, 64);
-    if (lane == 0) *nloc_s = cl;
+    if (infl) p3 = wave_sum(p3);
+    if (lane == 0) {
+      *nloc_s = cl;
+      infl_s[0] = infl ? a.infl[grp * a.npts + col] : 1.0;
+      infl_s[1] = p3;
+    }
   }
   __syncthreads();
   const int nloc = *nloc_s;
@@ -209,6 +250,7 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const typename LetkfArgsOf<SLAB
       }
     }
     if (a.stats && tid < 3) a.stats[3 * (grp * a.npts + col) + tid] = 0.0;
+    if (infl && a.infl_stats && tid < 4) a.infl_stats[4 * (grp * a.npts + col) + tid] = (tid < 3) ? 0.0 : __builtin_nan("");  // lambda keeps its bits
     return;
   }
 
@@ -268,6 +310,7 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const typename LetkfArgsOf<SLAB
       }
     }
     __syncthreads();  // the stage is consumed: A goes over it
+    const double shift = (double)(M - 1) / infl_s[0];  // the diagonal of A; (M-1)/1.0 is exact: no field, the bits without one
 #pragma unroll
     for (int t = 0; t < kLetkfTiles; ++t) {
       const int ti = wave + t * nW;
@@ -281,24 +324,37 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const typename LetkfArgsOf<SLAB
           if (ta == tb && i > j) continue;  // a diagonal tile holds each pair twice: the upper one is mirrored
           const double s = acc[t][v];
           if (I < M && J < M) {
-            const double val = (I == J) ? s + (double)(M - 1) : s;
+            const double val = (I == J) ? s + shift : s;
             G[I * M + J] = val;
             G[J * M + I] = val;
+            if (infl && I == J) n_s[I] = s;  // the diagonal of C, for its trace (n_s is free until the sweeps)
           } else if (I < M && J == M) {
             g_s[I] = s;
+          } else if (infl && I == M && J == M) {
+            infl_s[2] = s;  // p1 = sum_k w_k d_k^2
           }
         }
       }
     }
     __syncthreads();
+    if (infl) {  // (uniform) trace(C) in a fixed order before the sweeps take n_s
+      if (wave == 0) {
+        double tr = 0.0;
+        for (int j = lane; j < M; j += 64) tr += n_s[j];
+        tr = wave_sum(tr);
+        if (lane == 0) infl_s[3] = tr;
+      }
+      __syncthreads();
+    }
   }
 
   // ---- 2. eigen-solve ---------------------------------------------------------------------------------------------------------
   const int sweeps = etkf_jacobi(M, G, n_s, rot_s, tid, nth);
   etkf_factors(M, G, g_s, mu_s, f_s, h_s, tid, nth);
   if (a.stats && wave == 0) {
+    const double shift = (double)(M - 1) / infl_s[0];
     double s = 0.0;
-    for (int j = lane; j < M; j += 64) s += (mu_s[j] - (double)(M - 1)) / mu_s[j];
+    for (int j = lane; j < M; j += 64) s += (mu_s[j] - shift) / mu_s[j];
     s = wave_sum(s);
     if (lane == 0) {
       a.stats[3 * (grp * a.npts + col)] = (double)nloc;
@@ -311,6 +367,7 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const typename LetkfArgsOf<SLAB
   if (MODE == kLetkfWeights) {
     double* tw = a.Tw + (size_t)(grp * a.npts + col) * M * (M + 1);
     etkf_assemble(M, G, f_s, h_s, tw, (size_t)(M + 1), tw + M, (size_t)(M + 1), tid, nth);
+    if (infl && tid == 0) letkf_inflation_estimate((size_t)(grp * a.npts + col), M, infl_s);
     return;
   }
   const bool rtps = MODE == kLetkfMembers && a.relax_kind == EFA_RELAX_RTPS && a.relax_alpha != 0.0;
@@ -419,6 +476,7 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const typename LetkfArgsOf<SLAB
     }
     __syncthreads();  // the batch's rows are stored: the next batch takes x_s
   }
+  if (infl && tid == 0) letkf_inflation_estimate((size_t)(grp * a.npts + col), M, infl_s);
 }
 
 template <int MODE, typename E, int NTMAX, bool SLAB>

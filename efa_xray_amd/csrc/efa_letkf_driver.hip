@@ -6,6 +6,8 @@
 //   state  the lists of the grid's columns and ONE k_letkf launch (kLetkfMembers); with a mesh the lists of its nodes, the node
 //          solve (kLetkfWeights) and k_letkf_interp.  Under the slab settings both take the groups (letkf_slab_groups) and run one
 //          solve per (group, column or node).
+//   inflation  the context's per-point field (efa_ctx_set_letkf_inflation), checked against the call before any
+//          launch, goes with the launch that solves: the columns' or the nodes'; the obs block takes the fixed ob factors.
 #include "efa_driver.h"
 
 #include <cmath>
@@ -202,6 +204,45 @@ LetkfArgs letkf_args(int M, long npts, const LetkfLists& l, const double* Yp, co
   return a;
 }
 
+// The inflation setting against a call, before any launch: sized for its P and its `nsolve` solve points
+// (nsolve < 0: the call solves at no state point), the field's values, and with `obs_block` the ob factors', finite and within the
+// bounds.  Two small downloads.
+int letkf_check_inflation(efa_ctx* c, const char* who, long P, long nsolve, bool obs_block) {
+  if (!c->li_field) return EFA_OK;
+  if (c->li_P != P) return fail(EFA_ERR_INVALID, "%s: the LETKF inflation was set for %ld observations, the call has %ld", who, c->li_P, P);
+  if (nsolve >= 0 && c->li_nsolve != nsolve)
+    return fail(EFA_ERR_INVALID, "%s: the LETKF inflation field was set for %ld solve points, the call has %ld (groups x columns, nodes or "
+                "probe points)", who, c->li_nsolve, nsolve);
+  std::vector<double> h;
+  const auto check = [&](const double* dev, long n, const char* what) -> int {
+    h.resize((size_t)n);
+    EFA_HIP(hipMemcpyAsync(h.data(), dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    EFA_HIP(hipStreamSynchronize(c->stream));
+    for (long i = 0; i < n; ++i)
+      if (!(std::isfinite(h[i]) && h[i] >= c->li_lower && h[i] <= c->li_upper))
+        return fail(EFA_ERR_INVALID, "%s: LETKF inflation: %s %ld is %g, not a finite value within [%g, %g]", who, what, i, h[i],
+                    c->li_lower, c->li_upper);
+    return EFA_OK;
+  };
+  if (nsolve > 0) EFA_TRY(check(c->li_field, nsolve, "the field's value"));
+  if (obs_block && c->li_ob && P > 0) EFA_TRY(check(c->li_ob, P, "the factor of observation"));
+  return EFA_OK;
+}
+
+// ... into the arguments of a state or node solve (the field, updated when sigma_b > 0) or of the obs block (the fixed ob factors)
+void letkf_args_inflation(const efa_ctx* c, LetkfArgs* a, bool obs_block) {
+  if (!c->li_field) return;
+  a->infl_lo = c->li_lower;
+  a->infl_hi = c->li_upper;
+  if (obs_block) {
+    a->infl = const_cast<double*>(c->li_ob);  // (never written: sigma2 = 0)
+    return;
+  }
+  a->infl = c->li_field;
+  a->infl_sigma2 = c->li_sigma_b * c->li_sigma_b;
+  a->infl_stats = c->li_stats;
+}
+
 // the solve at `npts` points whose lists are built: [T | w] of each to Tw, the statistics to stats (or null); does not wait
 // (grp: [T | w] of every (group, point), the statistics [group][point][3])
 int letkf_solve_points(efa_ctx* c, int M, long npts, const LetkfLists& lists, const double* Yp_dev, const LetkfObs& o,
@@ -209,6 +250,7 @@ int letkf_solve_points(efa_ctx* c, int M, long npts, const LetkfLists& lists, co
   LetkfArgs a = letkf_args(M, npts, lists, Yp_dev, o);
   a.Tw = Tw;
   a.stats = stats;
+  letkf_args_inflation(c, &a, false);
   EFA_HIP(launch_letkf(a, grp, kLetkfWeights, Elem::f64, c->stream));
   return EFA_OK;
 }
@@ -362,6 +404,14 @@ int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const double* ym_dev, co
   EFA_TRY(letkf_check_rows(who, r));
   if (rows > 0) EFA_TRY(check_grid(EFA_LOC_GC, grid_lat, grid_lon, ncol, n_lead, rows));
   EFA_TRY(letkf_check_obs(who, P, ym_dev, Yp_dev, ob));
+  if (c->li_field) {  // one factor per solve: per (group,) column or node
+    long nsolve = -1;
+    if (rows > 0) {
+      if (slab) EFA_TRY(letkf_groups(c, n_lead));
+      nsolve = (slab ? (long)c->lg_ngroups : 1) * (mesh ? nodes.nnodes() : ncol);
+    }
+    EFA_TRY(letkf_check_inflation(c, who, P, nsolve, true));
+  }
   hipStream_t s = c->stream;
   harvest_obs_ms(c);
   harvest_state_ms(c);
@@ -392,6 +442,7 @@ int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const double* ym_dev, co
     a.Yp_in = Yp_dev;
     a.ym_out = ymw;
     a.Yp_out = Yw;
+    letkf_args_inflation(c, &a, true);
     EFA_HIP(launch_letkf(a, nullptr, kLetkfPerts, Elem::f64, s));
     EFA_HIP(launch_etkf_post(P, M, Yw, ymw, o.post_mean, o.post_var, s));
   }
@@ -441,6 +492,7 @@ int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const double* ym_dev, co
     a.stats = col_stats_dev;
     a.relax_kind = c->relax_kind;
     a.relax_alpha = c->relax_alpha;
+    letkf_args_inflation(c, &a, false);
     EFA_HIP(launch_letkf(a, grp, kLetkfMembers, r.elem, s));
     c->state_launches = 1;
   }
@@ -491,6 +543,10 @@ int letkf_weights(efa_ctx* c, int M, long P, const double* ym_dev, const double*
   if (npts > 0 && (!pt_lat || !pt_lon || !Tw_dev)) return fail(EFA_ERR_INVALID, "%s: null point or output array", who);
   EFA_TRY(letkf_check_obs(who, P, ym_dev, Yp_dev, ob));
   if (npts == 0) return EFA_OK;
+  if (c->li_field) {
+    if (slab) EFA_TRY(letkf_groups(c, n_lead));
+    EFA_TRY(letkf_check_inflation(c, who, P, (slab ? (long)c->lg_ngroups : 1) * npts, false));
+  }
   hipStream_t s = c->stream;
   LetkfObs o;
   LetkfLists lists;

@@ -485,6 +485,41 @@ int efa_letkf_slab_weights_dev(efa_ctx *ctx, int M, long P, const double *ym_dev
                                double *Tw_dev /* [ngroups][npts][M][M+1] */, double *stats_dev /* [ngroups][npts][3] or NULL */);
 int efa_letkf_slab_groups(efa_ctx *ctx, long n_lead, int *group_of /* [n_lead] or NULL */, int *ngroups);
 
+/* ---- LETKF: per-point multiplicative inflation, adaptive after Miyoshi
+ * (2011, MWR 139) -------------------------------------------
+ * Context state like the relaxation, read by every LETKF entry above
+ * (cycle, f32, interp, slab and their combinations, efa_letkf_weights_dev,
+ * efa_letkf_slab_weights_dev) and ignored by every other entry.  A solve
+ * point x (a column, a node of the mesh, a probe point; with slab groups a
+ * (group, point) pair, laid out [ngroups][points] as the statistics are) has a
+ * prior factor lambda_b(x) = field_dev[x] > 0 that enters its solve as Hunt's
+ * rho.  With w_k = rho_k(x)/r_k over the listed obs with rho_k(x) != 0, the
+ * taper exactly as the solve uses it (slab factor included):
+ *   A_x = ((M-1)/lambda_b) I + C_x,  T and w from its eigenpairs as above,
+ *   dfs = sum_i (mu_i - (M-1)/lambda_b) / mu_i,
+ *   p1 = sum_k w_k d_k^2,  p2 = trace(C_x)/(M-1),  p3 = sum_k rho_k,
+ *   lambda_o = (p1 - p3)/p2,  v_o = (2/p3) ((lambda_b p2 + p3)/p2)^2,  v_b = sigma_b^2,
+ *   lambda_a = clip(lambda_b + v_b/(v_o + v_b) (lambda_o - lambda_b), lower, upper).
+ * The solve of this call uses lambda_b; lambda_a is written over field_dev[x]
+ * for the next call.  sigma_b == 0: the field is fixed and keeps its bits.  A
+ * point no ob reaches keeps its rows and its factor bit for bit (its pair stays
+ * (I, 0)); so does the factor where p2 or p3 is not finite and positive or the
+ * estimate is not finite (a NaN innovation reaching the point).
+ * infl_stats_dev, [nsolve][4] or NULL, takes {p1, p2, p3, lambda_o} as
+ * computed, NaN included ({0, 0, 0, NaN} for a point no ob reaches).  With a
+ * mesh the nodes are the solve points; k_letkf_interp interpolates pairs that
+ * carry the inflation.  The obs block: ob j is solved under ob_infl_dev[j]
+ * ([P], NULL: 1.0 for all), which is never updated.  A field of 1.0
+ * everywhere gives the bits of the call without the setting.
+ * nsolve must equal ngroups * (columns, nodes or probe points) of the call and
+ * P the call's; before any launch the call downloads the field (and
+ * ob_infl_dev) and refuses values that are not finite or outside
+ * [lower, upper].  The setter refuses sigma_b < 0 or not finite and anything
+ * but 0 < lower <= upper, finite.  Every refusal is EFA_ERR_INVALID, writes
+ * nothing and leaves the context usable.  field_dev == NULL turns it off. */
+int efa_ctx_set_letkf_inflation(efa_ctx *ctx, double *field_dev, long nsolve, const double *ob_infl_dev, long P, double sigma_b,
+                                double lower, double upper, double *infl_stats_dev);
+
 /* ---- device memory for callers without their own allocator -------------*/
 int efa_malloc(efa_ctx *ctx, size_t bytes, void **dev_out);
 int efa_free(efa_ctx *ctx, void *dev);

@@ -9,6 +9,13 @@ The two are different filters: this compares their cost, not their results.  Run
 (a run of its own, --steps 3) for the kernels' own times.
 
     python tools/letkf_cost.py [--steps 10] [--warmup 3] [--members 20,40,80] [--limit 60] [--no-big] [--json profiles/letkf_cost.json]
+
+--inflation measures the per-column inflation instead, on the three 64 x 64 workloads in the same process: the
+LETKF cycle with the setting off (`letkf`), with a fixed field of 1.2 (`letkf_infl_fixed`, sigma_b = 0) and with the adaptive field
+(`letkf_infl_adaptive`, sigma_b = 0.04, the field carried from cycle to cycle); random ob factors in both.  The call's check of the
+field (a download of ncol + P doubles) is inside the timed call.
+
+    python tools/letkf_cost.py --inflation --json profiles/letkf_inflation_cost.json
 """
 import argparse
 import json
@@ -42,10 +49,15 @@ def one_cycle(ctx, s, variant):
     ym = ctx.empty((s["P"],))
     ctx.form_perts(s["P"], s["M"], Yp, ym, Yp)
     ctx.synchronize()
+    if variant in ("letkf_infl_fixed", "letkf_infl_adaptive"):
+        ctx.set_letkf_inflation(s["lam"], s["ob_infl"], s["P"], 0.04 if variant == "letkf_infl_adaptive" else 0.0, 1e-2, 1e2, s["lam_stats"])
     t0 = time.perf_counter()
-    if variant == "letkf":
-        ctx.letkf_cycle(s["rows"], s["M"], s["P"], s["X"], s["X"], ym, Yp, s["value"], s["error"], s["assim"], s["ob_lat"], s["ob_lon"],
-                        s["ob_hw"], s["glat"], s["glon"], s["n_lead"])
+    if variant.startswith("letkf"):
+        try:
+            ctx.letkf_cycle(s["rows"], s["M"], s["P"], s["X"], s["X"], ym, Yp, s["value"], s["error"], s["assim"], s["ob_lat"],
+                            s["ob_lon"], s["ob_hw"], s["glat"], s["glon"], s["n_lead"])
+        finally:
+            ctx.set_letkf_inflation(None)
     else:
         ctx.ensrf_cycle(s["rows"], s["M"], s["P"], s["X"], s["X"], ym, Yp, s["value"], s["error"], s["assim"], _lib.LOC_GC, s["ob_lat"],
                         s["ob_lon"], s["ob_hw"], s["glat"], s["glon"], s["n_lead"])
@@ -72,6 +84,7 @@ def main():
     ap.add_argument("--members", default="20,40,80")
     ap.add_argument("--limit", type=float, default=60.0, help="seconds a configs[2] cycle may be estimated to take")
     ap.add_argument("--no-big", action="store_true")
+    ap.add_argument("--inflation", action="store_true", help="the per-column inflation's three variants (DESIGN.md 7y-6)")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     from efa_xray_amd import _lib
@@ -83,7 +96,10 @@ def main():
         s = setup(ctx, 64, 64, 8, M, 1000, 1000.0)
         rec = dict(workload="64x64x8", M=M, P=1000, halfwidth_km=1000.0, ncol=s["ncol"], n_lead=8, warmup=a.warmup, steps=a.steps,
                    threads=None, variants={})
-        for variant in ("letkf", "ensrf_gc"):
+        if a.inflation:
+            s.update(lam=ctx.to_device(np.full(s["ncol"], 1.2)), lam_stats=ctx.empty((s["ncol"], 4)),
+                     ob_infl=ctx.to_device(np.random.default_rng(M).uniform(0.8, 1.6, s["P"])))
+        for variant in ("letkf", "letkf_infl_fixed", "letkf_infl_adaptive") if a.inflation else ("letkf", "ensrf_gc"):
             ctx.fill_synthetic(s["rows"], 0, M, 1, 3.0, s["X"])      # (the cycles run in place: the same prior for both variants)
             rec["variants"][variant] = measure(ctx, s, variant, a.warmup, a.steps)
             print(json.dumps(dict(workload=rec["workload"], M=M, variant=variant, **rec["variants"][variant])), flush=True)
@@ -91,7 +107,7 @@ def main():
             rate40 = rec["variants"]["letkf"]
         out.append(rec)
         del s
-    if rate40 is not None and not a.no_big:
+    if rate40 is not None and not a.no_big and not a.inflation:
         ny, nx, n_lead, P = 361, 720, 148, 5000
         # per column: the solve (as measured at 8 leads, where it dominates) and 148 / 8 times the rows to apply
         est_s = ny * nx / rate40["columns_per_s_state"] * (148.0 / 8.0)
