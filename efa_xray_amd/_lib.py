@@ -54,6 +54,8 @@ SIGNATURES = {
                                                       ctypes.c_double, ctypes.c_double]),
     "efa_ctx_set_letkf_inflation": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long,
                                                    ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
+    "efa_ctx_set_letkf_control": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_long]),
     "efa_ctx_set_vertical_localization": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, c_double_p, ctypes.c_long,
                                                          c_double_p, c_double_p]),
     "efa_ctx_set_slab_localization": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, c_double_p, c_int32_p, ctypes.c_long,
@@ -536,6 +538,19 @@ class Context(object):
         _check(self.lib, self.lib.efa_ctx_set_letkf_inflation(self.handle, self._addr(field), int(np.prod(field.shape, dtype=np.int64)),
                                                               self._addr(ob_infl),
                                                               int(P), float(sigma_b), float(lower), float(upper), self._addr(stats)))
+
+    def set_letkf_control(self, xc, xc_post=None, yc=None, yc_post=None):
+        """The deterministic control analysis of every later plain or slab LETKF cycle on this context (Schraff et al. 2016;
+        DESIGN.md 7y-7): float64 DeviceArrays xc [rows] (the control, one value per state row) and xc_post [rows] (its analysis;
+        xc itself for in place), yc [P] (the control's observation estimates H(x_c)) and yc_post [P]; yc and yc_post may be None
+        without observations.  xc None turns it off.  The context holds addresses only: keep the arrays alive."""
+        if xc is None:
+            _check(self.lib, self.lib.efa_ctx_set_letkf_control(self.handle, None, None, 0, None, None, 0))
+            return
+        rows = int(np.prod(xc.shape, dtype=np.int64))
+        P = 0 if yc is None else int(np.prod(yc.shape, dtype=np.int64))
+        _check(self.lib, self.lib.efa_ctx_set_letkf_control(self.handle, self._addr(xc), self._addr(xc_post), rows, self._addr(yc),
+                                                            self._addr(yc_post), P))
 
     def set_vertical_localization(self, lead_vert=None, ob_vert=None, ob_vert_halfwidth=None):
         """Vertical localisation of every later GC cycle on this context: host arrays lead_vert [n_lead] and

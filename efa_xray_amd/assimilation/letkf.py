@@ -37,12 +37,29 @@ and hold the factors for the NEXT update once this one returns; `last_solve` gai
 `inflation_post` and `inflation_stats` (..., 4) = (p1, p2, p3, lambda_o).  Observations with the default point interpolation are
 solved under that interpolation of the field, observations with a user-defined forward operator under 1.0.  This is the LETKF's
 adaptive inflation; `adaptive_inflation` (Anderson 2009, tied to the serial filter's order) stays refused.
+
+`control=ctrl` carries a single deterministic forecast beside the ensemble and adjusts it by the same observations
+through the ensemble's covariances (the deterministic analysis of Schraff et al. 2016; the control member of Hunt et al. 2007):
+
+    x_c^a = x_c + X' w^c,   w^c = A_c^-1 sum_k (rho_k(c)/r_k) (value_k - H(x_c)_k) Y_k^T
+
+per column (per (slab group, column) under `SlabLETKF`), and H(x_c)^a likewise at every observation's own position.  `ctrl` is an
+`EnsembleState` with the state's variables, coordinates and grid and exactly ONE member; H(x_c) is the default point interpolation
+applied to it, or `ob.estimate(ctrl)` for user-defined operators.  After `update()`, `last_control` is a dict: `state` (a NEW
+one-member `EnsembleState`, the control analysis), `ob_prior` (P,) = H(x_c) and `ob_post` (P,), NaN where the observation was not
+assimilated.  The ensemble's results -- the return value and the five diagnostics -- do not change by a bit; the outlier check is
+decided on the ensemble mean alone; relaxation and the constant `inflation=` hook act on the ensemble's perturbations only.
+`control` with `weight_stride` raises ValueError: weight interpolation of w^c is the follow-up.
 """
+from collections import OrderedDict
+from copy import deepcopy
+
 import numpy as np
 
 from efa_xray_amd import _lib
 from efa_xray_amd.assimilation.ensrf import EnSRF
 from efa_xray_amd.assimilation.letkf_inflation import ColumnInflation, expand_nodes, ob_factors
+from efa_xray_amd.state.ensemble import EnsembleState
 
 MAX_MEMBERS = 136
 
@@ -71,6 +88,22 @@ def _weight_stride(stride):
     return None if pair == (1, 1) else pair
 
 
+def _check_control(state, ctrl):
+    """ValueError unless `ctrl` is a one-member EnsembleState on the state's variables, coordinates and grid."""
+    if not isinstance(ctrl, EnsembleState):
+        raise ValueError("control must be an EnsembleState with exactly one member, got %r" % type(ctrl).__name__)
+    if ctrl.nvars() == 0 or ctrl.nmems() != 1:
+        raise ValueError("control must have exactly one member, got %d" % (ctrl.nmems() if ctrl.nvars() else 0))
+    if ctrl.vars() != state.vars():
+        raise ValueError("control has the variables %r, the state has %r" % (ctrl.vars(), state.vars()))
+    if ctrl.shape()[:4] != state.shape()[:4]:
+        raise ValueError("control has (nvars, ntimes, ny, nx) = %r, the state has %r" % (ctrl.shape()[:4], state.shape()[:4]))
+    for key in ("validtime", "lat", "lon"):
+        a, b = np.asarray(ctrl.coords.get(key)), np.asarray(state.coords.get(key))
+        if a.shape != b.shape or not np.all(a == b):
+            raise ValueError("control and state differ in the coordinate %r" % key)
+
+
 class LETKF(EnSRF):
     _served = ()        # the keywords of _REFUSED a subclass serves: handed on to EnSRF, which validates them
 
@@ -80,8 +113,17 @@ class LETKF(EnSRF):
         docstring); column_inflation (None or a `ColumnInflation`).  ValueError, before any device work, for loc other than 'GC'
         (use `ETKF` for the unlocalised filter), adaptive_inflation, vert_coord, time_localize, var_impact,
         sampling_error_correction, streamed, path, obs_batch, a weight_stride that is not an integer >= 1, and for more than 136 members (the eigen-solve of a column keeps
-        its M x M array in LDS).  `update_arrays` is not offered."""
+        its M x M array in LDS).  control (None, or a one-member `EnsembleState` on the state's variables, coordinates and grid:
+        the module's docstring): ValueError for anything else and for control with a weight_stride.  `update_arrays` is not
+        offered."""
         stride = _weight_stride(kw.pop("weight_stride", None))
+        ctrl = kw.pop("control", None)
+        if ctrl is not None:
+            _check_control(state, ctrl)
+            if stride is not None:
+                raise ValueError("%s: control and weight_stride do not combine: the interpolated pairs [T | w] have no place for "
+                                 "the control's weight vector (weight interpolation of w^c is the follow-up, DESIGN.md 7y-7)"
+                                 % type(self).__name__)
         ci = kw.pop("column_inflation", None)
         if ci is not None and not isinstance(ci, ColumnInflation):
             raise ValueError("column_inflation must be a ColumnInflation, got %r" % type(ci).__name__)
@@ -102,6 +144,8 @@ class LETKF(EnSRF):
         self.last_solve = None
         self.weight_stride = stride
         self.column_inflation = ci
+        self.control = ctrl
+        self.last_control = None
 
     _cycle_line = "Beginning the column solves"
 
@@ -112,6 +156,7 @@ class LETKF(EnSRF):
 
     def update(self):
         self.last_solve = None
+        self.last_control = None
         return EnSRF.update(self)       # the resident sequence (streamed is refused), with the cycle below
 
     def _run_cycle(self, ctx, X, P, ym, Yp, ob, geometry, field):
@@ -130,7 +175,18 @@ class LETKF(EnSRF):
             mesh = dict(shape=(ny, nx), stride=self.weight_stride)
         ng = 1                                  # solves per column or node
         ci = self.column_inflation
+        ctrl = self.control
+        if ctrl is not None:                    # host work first: the setting goes on only around the cycle
+            _check_control(prior, ctrl)
+            xc = np.ascontiguousarray(ctrl.to_vect()[:, 0], dtype=np.float64)
+            yc = self._control_estimates(ctx, ctrl, xc) if P else None
         try:
+            if ctrl is not None:
+                xc_dev, xc_post = ctx.to_device(xc), ctx.empty((max(N, 1),))
+                yc_dev = yc_post = None
+                if P:
+                    yc_dev, yc_post = ctx.to_device(yc), ctx.empty((P,))
+                ctx.set_letkf_control(xc_dev, xc_post, yc_dev, yc_post)
             if slab:
                 group_of, ng = ctx.letkf_slab_groups(n_lead)
             stats = ctx.empty((ng * sy * sx, 3))
@@ -153,6 +209,8 @@ class LETKF(EnSRF):
                 ctx.set_slab_localization(None)
             if ci is not None:
                 ctx.set_letkf_inflation(None)
+            if ctrl is not None:
+                ctx.set_letkf_control(None)
         st = stats.download().reshape(ng, sy, sx, 3)
         if not slab:                            # the plain filter documents (ny, nx) / (nyn, nxn)
             st = st[0]
@@ -165,7 +223,23 @@ class LETKF(EnSRF):
             ci.values = lam_dev.download().reshape(lam_shape)       # the next update's prior factors
             self.last_solve.update(inflation=lam_b, inflation_post=ci.values.copy(),
                                    inflation_stats=lam_stats.download().reshape(lam_shape + (4,)))
+        if ctrl is not None:
+            post = type(ctrl)(OrderedDict((n, v.copy()) for n, v in ctrl.variables.items()), deepcopy(ctrl.coords))
+            post.from_vect(xc_post.download()[:N].reshape(N, 1))
+            ob_post = np.where(diag["assimilated"], yc_post.download(), np.nan) if P else np.zeros(0)
+            self.last_control = dict(state=post, ob_prior=yc if P else np.zeros(0), ob_post=ob_post)
         return diag
+
+    def _control_estimates(self, ctx, ctrl, xc):
+        """H(x_c) (P,): the default point interpolation's stencils on the control's rows, or the obs' own `estimate`."""
+        if self._default_forward_operator():
+            idx, wts = self._interp_stencils_host(ctx)
+            yc = np.zeros(idx.shape[0])
+            for j in range(idx.shape[1]):           # entry by entry, as the forward kernel sums them
+                on = (idx[:, j] >= 0) & (wts[:, j] != 0.0)
+                yc[on] += wts[on, j] * xc[idx[on, j]]
+            return yc
+        return np.array([np.asarray(ob.estimate(ctrl), dtype=np.float64).reshape(-1)[0] for ob in self.obs], dtype=np.float64)
 
     def _ob_inflation(self, ctx, P, field_cols, group_of):
         """The factor of every ob's own solve: its point interpolation applied to the field (ngroups, ncol); None (1.0 for all)

@@ -331,6 +331,37 @@ int efa_ctx_set_letkf_inflation(efa_ctx* c, double* field_dev, long nsolve, cons
   return EFA_OK;
 }
 
+int efa_ctx_set_letkf_control(efa_ctx* c, const double* xc_dev, double* xc_post_dev, long rows, const double* yc_dev, double* yc_post_dev,
+                              long P) {
+  EFA_TRY(use(c));
+  if (!xc_dev) {
+    c->lc_xc = c->lc_yc = nullptr;
+    c->lc_xc_post = c->lc_yc_post = nullptr;
+    c->lc_rows = c->lc_P = 0;
+    return EFA_OK;
+  }
+  if (rows < 0 || P < 0) return fail(EFA_ERR_INVALID, "LETKF control: negative count (rows=%ld, P=%ld)", rows, P);
+  if (!xc_post_dev || (P > 0 && (!yc_dev || !yc_post_dev))) return fail(EFA_ERR_INVALID, "LETKF control: null array");
+  const uintptr_t x0 = reinterpret_cast<uintptr_t>(xc_dev), x1 = reinterpret_cast<uintptr_t>(xc_post_dev);
+  const uintptr_t y0 = reinterpret_cast<uintptr_t>(yc_dev), y1 = reinterpret_cast<uintptr_t>(yc_post_dev);
+  if (((x0 | x1 | y0 | y1) & 7u) != 0) return fail(EFA_ERR_INVALID, "LETKF control: the arrays must be 8-byte aligned");
+  const auto overlap = [](uintptr_t a, uintptr_t b, long n) {
+    const uintptr_t nb = (uintptr_t)n * sizeof(double);
+    return a < b + nb && b < a + nb;
+  };
+  if (x0 != x1 && overlap(x0, x1, rows))
+    return fail(EFA_ERR_INVALID, "LETKF control: xc_post_dev overlaps xc_dev without coinciding with it (in place means the same address: "
+                "a row's control value is read and written by the wave that owns the row)");
+  if (overlap(y0, y1, P)) return fail(EFA_ERR_INVALID, "LETKF control: yc_post_dev overlaps yc_dev");
+  c->lc_xc = xc_dev;
+  c->lc_xc_post = xc_post_dev;
+  c->lc_rows = rows;
+  c->lc_yc = yc_dev;
+  c->lc_yc_post = yc_post_dev;
+  c->lc_P = P;
+  return EFA_OK;
+}
+
 int efa_ctx_set_vertical_localization(efa_ctx* c, long n_lead, const double* lead_vert, long P, const double* ob_vert,
                                       const double* ob_vert_halfwidth) {
   EFA_TRY(use(c));

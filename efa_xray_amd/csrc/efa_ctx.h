@@ -305,7 +305,7 @@ struct efa_ctx {
   bool batch_solved = false;    // the last obs phase ran the batch solver: the state phase goes through [T | w], there are no records
   DevBuf etkf_buf;              // its workspace (EtkfWs): scales, A, g, q, sweeps, mu, partial tiles
   // --- local ensemble transform Kalman filter (efa_letkf_cycle_dev): buffers of its own as well ------------------------
-  DevBuf letkf_ob;    // per ob: value | error | lat | lon | half-width | requested flag | act [4] | dr [2] | obtrig [6] | diagnostics
+  DevBuf letkf_ob;    // per ob: value | error | lat | lon | half-width | requested flag | act [4] | dr [2] | obtrig [6] | dc | diagnostics
   DevBuf letkf_pts;   // the points of a list build (lat | lon): the grid's columns, or the probe points of efa_letkf_weights_dev
   DevBuf letkf_blk, letkf_idx, letkf_wts;  // the call's lists: off | cnt | ub | order, entries, tapers (the obs' then the grid's)
   DevBuf letkf_Yw;    // the mapped obs block [P][M] | its means [P]
@@ -318,6 +318,12 @@ struct efa_ctx {
   const double* li_ob = nullptr;     // [P] the factor of every ob's own solve, or null (1.0)
   double li_sigma_b = 0.0, li_lower = 0.0, li_upper = 0.0;
   double* li_stats = nullptr;        // [nsolve][4] {p1, p2, p3, lambda_o}, or null
+  // --- the LETKF's deterministic control analysis (efa_ctx_set_letkf_control): the caller's device arrays
+  const double* lc_xc = nullptr;     // [rows] the control, one value per state row; null: off
+  double* lc_xc_post = nullptr;      // [rows] its analysis (lc_xc itself, or clear of it)
+  const double* lc_yc = nullptr;     // [P] H(x_c)
+  double* lc_yc_post = nullptr;      // [P] the analysis' ob estimates (clear of lc_yc)
+  long lc_rows = 0, lc_P = 0;
   // --- the LETKF's slab groups (efa_letkf_slab_cycle_dev): slabs whose factors agree for every ob share one solve
   std::vector<int> lg_group_of;                   // [n_lead] the group of every slab, numbered by first appearance
   int lg_ngroups = 0;

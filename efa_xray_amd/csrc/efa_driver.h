@@ -199,6 +199,8 @@ int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const double* ym_dev, co
 // every column and applies them; a unit stride is the call without a mesh)
 // (slab: efa_letkf_slab_cycle_dev and its kin, DESIGN.md §7y-3 -- one solve per (slab group, column) under the vertical and / or slab
 // setting; col_stats_dev is then [ngroups][ncol or nnodes][3])
+// (the context's control, efa_ctx_set_letkf_control, DESIGN.md §7y-7: served without a mesh, sized for this call's rows and P;
+// with a mesh, and by letkf_weights, the call is refused while it is set; letkf_interp_apply ignores it)
 // efa_letkf_interp_apply_dev / _f32_dev: that kernel alone on caller-given node pairs, under the context's relaxation; waits
 int letkf_interp_apply(efa_ctx* c, const StateRows& r, const efa::LetkfMesh& mesh, long n_lead, const double* Tw_nodes_dev,
                        const double* node_stats_dev);

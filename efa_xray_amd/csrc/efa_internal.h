@@ -406,15 +406,23 @@ struct LetkfArgs {
   double infl_sigma2;   // the prior variance sigma_b^2 of Miyoshi's (2011) estimate; 0: the field is fixed and never written
   double infl_lo, infl_hi;  // lambda_a is clipped to [lo, hi]
   double* infl_stats;   // [ngroups][npts][4] {p1, p2, p3, lambda_o} or null
+  // the deterministic control analysis: a second right-hand side g^c = sum_k (rho_k/r_k) d^c_k Yp_k^T in every solve,
+  // w^c = V diag(1/mu) V^T g^c, and per row ctl_out = ctl_in + x' . w^c; null: off (kLetkfMembers and kLetkfPerts only)
+  const double* dc;     // [P] value - H(x_c) of every ob with an effective flag of 1, 0 for the others
+  const double* ctl_in; // kLetkfMembers: [n_lead * npts] the control's rows; kLetkfPerts: [npts] its ob estimates ...
+  double* ctl_out;      // ... and their analysis (kLetkfMembers: the same address, or clear of ctl_in; read and written by the row's wave)
 };
-int letkf_threads(int M);       // the workgroup size chosen for M members
-size_t letkf_lds_bytes(int M);  // and its dynamic LDS
+int letkf_threads(int M, bool ctl = false);       // the workgroup size chosen for M members (ctl: with the control's column in the Gram)
+size_t letkf_lds_bytes(int M, bool ctl = false);  // and its dynamic LDS (ctl: the stage of M + 2 columns and one more M-vector)
 // a wave per ob: prior_mean, prior_var (ddof 0), the effective flag (the requested one, and with t2 > 0 the outlier check's verdict
 // d^2 <= t2 (s2 + error), exactly as the prep launch decides it) as a byte and as the coefficient-shaped act [P][4] the list
 // builders read, and dr [P][2]; an ob with an effective flag of 0 leaves the neutral (0, 1) there, whatever its value and error
 hipError_t launch_letkf_prior(long P, int M, const double* Yp, const double* ym, const double* ob_value, const double* ob_error,
                               const double* ob_req, double t2, double* prior_mean, double* prior_var, uint8_t* assimilated, double* act,
                               double* dr, hipStream_t s);
+// a thread per ob: dc[k] = value[k] - yc[k] where assimilated[k] (k_letkf_prior's verdict), else the neutral 0 (value and yc not read)
+hipError_t launch_letkf_control_prior(long P, const double* ob_value, const double* yc, const uint8_t* assimilated, double* dc,
+                                      hipStream_t s);
 // ---- weight interpolation (efa_letkf_interp.hip): [T | w] solved at the nodes of a coarse mesh of grid columns,
 // interpolated bilinearly in grid-index space to every column and applied to its rows
 struct LetkfMesh {

@@ -37,6 +37,10 @@
 // enters the solve as Hunt's rho, A_x = (M-1)/lambda_b I + C_x, and with infl_sigma2 > 0 one lane writes back Miyoshi's (2011)
 // estimate lambda_a from p1 = sum_k w_k d_k^2 (entry (M, M) of the Gram product), p2 = trace(C_x)/(M-1) (its diagonal before the
 // shift) and p3 = sum_k rho_k (the n_local loop).  A uniform run-time branch: a.infl == nullptr is the kernel without it.
+// The deterministic control analysis (efa_ctx_set_letkf_control): with a.dc the staged row is [Yp_k | d_k | d^c_k],
+// d^c_k = value_k - H(x_c)_k from k_letkf_control_prior, column M+1 of the (M+2)^2 product is g^c, h^c = (V^T g^c)/mu goes over n_s
+// behind the sweeps, and the wave that owns a row adds h^c . z to the control's value of that row (the obs block: to y_c[j]).  A
+// template switch (CTRL): without a.dc the kernels are the ones without it.
 // This file holds the kernels and their launchers only.
 #include "efa_driver.h"
 #include "efa_device.h"
@@ -56,11 +60,12 @@ constexpr int kLetkfRows = 4;    // rows per apply batch (one wave each for the 
 constexpr int kLetkfTiles = 3;   // tiles a wave may own
 constexpr int kLetkfSmall = 16;  // doubles of per-row scalars: mean [4] | xam [4] | ssb [4] | inflation scalars [4]
 
-__host__ __device__ inline int letkf_tiles_side(int M) { return (M + 1 + 15) / 16; }
-__host__ __device__ inline int letkf_stage_pitch(int M) { return 16 * (letkf_tiles_side(M) | 1); }
+// ctl (the control analysis): the staged row is [Yp_k | d_k | d^c_k], the product (M+2)^2
+__host__ __device__ inline int letkf_tiles_side(int M, bool ctl = false) { return (M + (ctl ? 2 : 1) + 15) / 16; }
+__host__ __device__ inline int letkf_stage_pitch(int M, bool ctl = false) { return 16 * (letkf_tiles_side(M, ctl) | 1); }
 // doubles of the region the stage and the M x M array share
-__host__ __device__ inline int letkf_region(int M) {
-  const int st = kLetkfChunk * letkf_stage_pitch(M) + kLetkfChunk, mm = M * M;
+__host__ __device__ inline int letkf_region(int M, bool ctl = false) {
+  const int st = kLetkfChunk * letkf_stage_pitch(M, ctl) + kLetkfChunk, mm = M * M;
   return st > mm ? st : mm;
 }
 
@@ -111,6 +116,15 @@ __global__ __launch_bounds__(256) void k_letkf_prior(long P, int M, const double
   }
 }
 
+// The control's innovations beside dr, under the flag k_letkf_prior decided on the ENSEMBLE mean: the control never
+// votes, and neither value nor yc of an ob with a flag of 0 is read.
+__global__ __launch_bounds__(256) void k_letkf_control_prior(long P, const double* __restrict__ ob_value, const double* __restrict__ yc,
+                                                             const uint8_t* __restrict__ assimilated, double* __restrict__ dc) {
+  const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= P) return;
+  dc[k] = assimilated[k] ? ob_value[k] - yc[k] : 0.0;
+}
+
 // upper tile ti of a T x T tile grid, row by row: (0,0) (0,1) .. (0,T-1) (1,1) ..
 __device__ __forceinline__ void letkf_tile(int ti, int T, int* ta, int* tb) {
   int a = 0;
@@ -133,15 +147,18 @@ struct LetkfArgsOf { typedef LetkfArgs type; };
 template <>
 struct LetkfArgsOf<true> { typedef LetkfSlabArgs type; };
 
+// k_letkf's argument block where it is needed and not before (k_letkf's only parameter is a LetkfArgs or begins with one,
+// LetkfSlabArgs' base: the kernel's argument block is one).  What is read through it is not held in scalar registers from the entry
+// on: the slab launch has none to spare, and what does not fit goes to vector registers and costs it a wave per SIMD.
+typedef const __attribute__((address_space(4))) LetkfArgs* letkf_kernarg_ptr;
+__device__ __forceinline__ letkf_kernarg_ptr letkf_kernarg() { return (letkf_kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr(); }
+
 // The inflation estimate of a point (Miyoshi 2011), by one lane, from the sums the solve left in sc = lambda_b | p3 |
 // p1 | trace(C): the statistics as computed, and lambda_a over the field unless p2, p3 or the estimate rule it out.  The solve used
 // lambda_b.  Called at the kernel's exits, where nothing else is live.
 __device__ __forceinline__ void letkf_inflation_estimate(size_t pt, int M, const double* sc) {
-  // its four parameters are read HERE from the kernel's argument block, not held in scalar registers from the entry on: the slab
-  // launch has none to spare, and what does not fit goes to vector registers and costs it a wave per SIMD
-  // (k_letkf's only parameter is a LetkfArgs or begins with one, LetkfSlabArgs' base: the kernel's argument block is one)
-  typedef const __attribute__((address_space(4))) LetkfArgs* letkf_kernarg_ptr;
-  const auto& a = *(letkf_kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+  // its four parameters are read HERE from the kernel's argument block (letkf_kernarg)
+  const auto& a = *letkf_kernarg();
   if (!a.infl_stats && !(a.infl_sigma2 > 0.0)) return;
   const double lb = sc[0], p3 = sc[1], p1 = sc[2], p2 = sc[3] / (double)(M - 1);
   const double lo = (p1 - p3) / p2;
@@ -160,16 +177,21 @@ __device__ __forceinline__ void letkf_inflation_estimate(size_t pt, int M, const
   }
 }
 
-template <int MODE, typename E, int NTMAX, bool SLAB = false>
+// CTRL: the deterministic control analysis beside the ensemble's.  A template switch, so that the instantiations
+// without it are today's instruction for instruction; with it the Gram carries one more B-operand column (g^c), h^c = (V_j . g^c)/mu_j
+// goes over n_s behind the sweeps, and the row's wave adds h^c . z to the control's value of its row.  Nothing of the ensemble's
+// arithmetic changes: the tiles are independent accumulators, and every reduction keeps its order whatever the tile side is.
+template <int MODE, typename E, int NTMAX, bool SLAB = false, bool CTRL = false>
 __global__ __launch_bounds__(NTMAX) void k_letkf(const typename LetkfArgsOf<SLAB>::type a) {
+  static_assert(!CTRL || MODE != kLetkfWeights, "the pair layout [M][M+1] has no place for w^c");
   extern __shared__ __align__(16) double letkf_smem[];
   const int M = a.M;
   const int tid = (int)threadIdx.x, nth = (int)blockDim.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nW = nth >> 6;
-  const int T = letkf_tiles_side(M), Sp = letkf_stage_pitch(M), ntiles = T * (T + 1) / 2;
+  const int T = letkf_tiles_side(M, CTRL), Sp = letkf_stage_pitch(M, CTRL), ntiles = T * (T + 1) / 2;
   double* G = letkf_smem;                     // the M x M array; before it the stage [32][Sp] | weights [32]
   double* wgt = G + kLetkfChunk * Sp;
-  double* g_s = G + letkf_region(M);
+  double* g_s = G + letkf_region(M, CTRL);
   double* f_s = g_s + M;
   double* h_s = f_s + M;
   double* n_s = h_s + M;
@@ -182,6 +204,7 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const typename LetkfArgsOf<SLAB
   double* infl_s = ssb_s + kLetkfRows;         // inflation (§7y-6): lambda_b | p3 | p1 | trace(C)
   int* rot_s = reinterpret_cast<int*>(mean_s + kLetkfSmall);
   int* nloc_s = rot_s + 2;
+  double* gc_s = mean_s + kLetkfSmall + 2;    // CTRL: g^c [M] behind the ints (16-byte aligned); h^c takes n_s behind the sweeps
 
   long bid = (long)blockIdx.x, grp = 0, lead0 = 0, nlead_g = a.n_lead;  // the group, its first entry in grp_leads, its slabs
   const double* Sg = nullptr;                                            // S[.][rep[grp]], pitch sp
@@ -239,9 +262,22 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const typename LetkfArgsOf<SLAB
           const size_t base = (size_t)(l * a.npts + col) * M;
           for (int m = tid; m < M; m += nth) out[base + m] = in[base + m];
         }
+      if constexpr (CTRL) {  // the control's rows likewise: copied bit for bit, or left alone in place
+        const double* cin = letkf_kernarg()->ctl_in;
+        double* cout = letkf_kernarg()->ctl_out;
+        if (cin != cout)
+          for (long li = tid; li < nlead_g; li += nth) {
+            long l = li;
+            if constexpr (SLAB) l = leads[li];
+            cout[l * a.npts + col] = cin[l * a.npts + col];
+          }
+      }
     } else if (MODE == kLetkfPerts) {
       for (int m = tid; m < M; m += nth) a.Yp_out[(size_t)col * M + m] = a.Yp_in[(size_t)col * M + m];
       if (tid == 0) a.ym_out[col] = a.ym_in[col];
+      if constexpr (CTRL) {
+        if (tid == 0) letkf_kernarg()->ctl_out[col] = letkf_kernarg()->ctl_in[col];
+      }
     } else {
       double* tw = a.Tw + (size_t)(grp * a.npts + col) * M * (M + 1);
       for (int e = tid; e < M * (M + 1); e += nth) {
@@ -276,9 +312,10 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const typename LetkfArgsOf<SLAB
         const int r = e / Sp, c = e - r * Sp;
         const int en = ch * kLetkfChunk + r;
         double v = 0.0;
-        if (en < n && c <= M) {
+        if (en < n && c <= M + (CTRL ? 1 : 0)) {
           const long k = a.idx[off + en];
-          v = (c < M) ? a.Yp[(size_t)k * M + c] : a.dr[2 * k];
+          if constexpr (CTRL) v = (c < M) ? a.Yp[(size_t)k * M + c] : (c == M) ? a.dr[2 * k] : letkf_kernarg()->dc[k];
+          else v = (c < M) ? a.Yp[(size_t)k * M + c] : a.dr[2 * k];
         }
         G[e] = v;
       }
@@ -330,6 +367,8 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const typename LetkfArgsOf<SLAB
             if (infl && I == J) n_s[I] = s;  // the diagonal of C, for its trace (n_s is free until the sweeps)
           } else if (I < M && J == M) {
             g_s[I] = s;
+          } else if (CTRL && I < M && J == M + 1) {
+            gc_s[I] = s;  // g^c; entries (M, M+1) and (M+1, M+1) are dropped
           } else if (infl && I == M && J == M) {
             infl_s[2] = s;  // p1 = sum_k w_k d_k^2
           }
@@ -351,6 +390,17 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const typename LetkfArgsOf<SLAB
   // ---- 2. eigen-solve ---------------------------------------------------------------------------------------------------------
   const int sweeps = etkf_jacobi(M, G, n_s, rot_s, tid, nth);
   etkf_factors(M, G, g_s, mu_s, f_s, h_s, tid, nth);
+  if constexpr (CTRL) {  // h^c_j = (V_j . g^c) / mu_j over n_s, which the sweeps have left; read behind the apply's first barrier
+    const int nslots_c = nth >> 4, slot_c = tid >> 4, sl_c = tid & 15;
+#pragma unroll 1
+    for (int j = slot_c; j < M; j += nslots_c) {
+      const double* cj = G + (size_t)j * M;
+      double hg = 0.0;
+      for (int i = sl_c; i < M; i += 16) hg = fma(cj[i], gc_s[i], hg);
+      hg = group_sum<16>(hg);
+      if (sl_c == 0) n_s[j] = hg / mu_s[j];
+    }
+  }
   if (a.stats && wave == 0) {
     const double shift = (double)(M - 1) / infl_s[0];
     double s = 0.0;
@@ -429,9 +479,29 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const typename LetkfArgsOf<SLAB
     if (wave < nr) {  // xam = mean + x' w = mean + h . z
       const double* zr = z_s + wave * M;
       double s = 0.0;
-      for (int j = lane; j < M; j += 64) s = fma(h_s[j], zr[j], s);
-      s = wave_sum(s);
-      if (lane == 0) xam_s[wave] = mean_s[wave] + s;
+      if constexpr (CTRL) {  // x_c^a = x_c + x' . w^c = x_c + h^c . z, by the wave that owns the row
+        double sc = 0.0;
+        for (int j = lane; j < M; j += 64) {
+          s = fma(h_s[j], zr[j], s);
+          sc = fma(n_s[j], zr[j], sc);
+        }
+        s = wave_sum(s);
+        sc = wave_sum(sc);
+        if (lane == 0) {
+          xam_s[wave] = mean_s[wave] + s;
+          long row = col;
+          if (MODE == kLetkfMembers) {
+            long l = r0 + wave;
+            if constexpr (SLAB) l = leads[l];
+            row = l * a.npts + col;
+          }
+          letkf_kernarg()->ctl_out[row] = letkf_kernarg()->ctl_in[row] + sc;  // (the pointers from the argument block, here)
+        }
+      } else {
+        for (int j = lane; j < M; j += 64) s = fma(h_s[j], zr[j], s);
+        s = wave_sum(s);
+        if (lane == 0) xam_s[wave] = mean_s[wave] + s;
+      }
     }
     // x'_a[r][b] = sum_j (f_j z[r][j]) V[b][j], over the prior perturbations (z holds all that is needed of them)
     for (int e = tid; e < nr * M; e += nth) {
@@ -479,9 +549,9 @@ __global__ __launch_bounds__(NTMAX) void k_letkf(const typename LetkfArgsOf<SLAB
   if (infl && tid == 0) letkf_inflation_estimate((size_t)(grp * a.npts + col), M, infl_s);
 }
 
-template <int MODE, typename E, int NTMAX, bool SLAB>
+template <int MODE, typename E, int NTMAX, bool SLAB, bool CTRL>
 hipError_t letkf_launch_as(const typename LetkfArgsOf<SLAB>::type& a, int nth, size_t lds, hipStream_t s) {
-  auto kern = k_letkf<MODE, E, NTMAX, SLAB>;
+  auto kern = k_letkf<MODE, E, NTMAX, SLAB, CTRL>;
   if (lds > 48 * 1024) {
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -492,13 +562,22 @@ hipError_t letkf_launch_as(const typename LetkfArgsOf<SLAB>::type& a, int nth, s
   return hipGetLastError();
 }
 
+template <int MODE, typename E, bool SLAB, bool CTRL>
+hipError_t letkf_launch_ctl(const typename LetkfArgsOf<SLAB>::type& a, hipStream_t s) {
+  const int nth = letkf_threads(a.M, CTRL);
+  const size_t lds = letkf_lds_bytes(a.M, CTRL);
+  if (nth <= 256) return letkf_launch_as<MODE, E, 256, SLAB, CTRL>(a, nth, lds, s);
+  if (nth <= 512) return letkf_launch_as<MODE, E, 512, SLAB, CTRL>(a, nth, lds, s);
+  return letkf_launch_as<MODE, E, 1024, SLAB, CTRL>(a, nth, lds, s);
+}
+
+// ... with the control analysis when its innovations are given (launch_letkf refuses them for kLetkfWeights)
 template <int MODE, typename E, bool SLAB>
 hipError_t letkf_launch_mode(const typename LetkfArgsOf<SLAB>::type& a, hipStream_t s) {
-  const int nth = letkf_threads(a.M);
-  const size_t lds = letkf_lds_bytes(a.M);
-  if (nth <= 256) return letkf_launch_as<MODE, E, 256, SLAB>(a, nth, lds, s);
-  if (nth <= 512) return letkf_launch_as<MODE, E, 512, SLAB>(a, nth, lds, s);
-  return letkf_launch_as<MODE, E, 1024, SLAB>(a, nth, lds, s);
+  if constexpr (MODE != kLetkfWeights) {
+    if (a.dc) return letkf_launch_ctl<MODE, E, SLAB, true>(a, s);
+  }
+  return letkf_launch_ctl<MODE, E, SLAB, false>(a, s);
 }
 
 // the plain launch, or with groups the SLAB one on (a, *grp)
@@ -544,25 +623,27 @@ __global__ __launch_bounds__(256) void k_letkf_obs_factor(long P, const long* __
 // each, so 16 ceil(M/2) threads keep every lane of it busy and more would idle there; rounded up to whole waves, at least four (one
 // per row of an apply batch) and at most 1024, and enough waves for the Gram's upper tiles at three per wave.  At 40 members that is
 // 320 threads and 17 KB of LDS: nine workgroups fit a CU's LDS and four its registers, where 1024 threads would leave room for one.
-int letkf_threads(int M) {
+int letkf_threads(int M, bool ctl) {
   const int npairs = (M + 1) / 2;
   int nth = 64 * ((16 * npairs + 63) / 64);
   if (nth < 64 * kLetkfRows) nth = 64 * kLetkfRows;
   if (nth > 1024) nth = 1024;
-  const int T = letkf_tiles_side(M), ntiles = T * (T + 1) / 2;
+  const int T = letkf_tiles_side(M, ctl), ntiles = T * (T + 1) / 2;
   while (nth < 1024 && kLetkfTiles * (nth / 64) < ntiles) nth += 64;
   return nth;
 }
 
-size_t letkf_lds_bytes(int M) {
-  // region | g, f, h, n, mu [M] each | x, z [4][M] each | per-row scalars | rot [2], n_local (ints)
-  return ((size_t)letkf_region(M) + (size_t)(5 + 2 * kLetkfRows) * M + kLetkfSmall + 2) * sizeof(double);
+size_t letkf_lds_bytes(int M, bool ctl) {
+  // region | g, f, h, n, mu [M] each | x, z [4][M] each | per-row scalars | rot [2], n_local (ints) | ctl: g^c [M]
+  return ((size_t)letkf_region(M, ctl) + (size_t)(5 + 2 * kLetkfRows) * M + kLetkfSmall + 2 + (ctl ? (size_t)M : 0)) * sizeof(double);
 }
 
 hipError_t launch_letkf(const LetkfArgs& a, const LetkfGroups* grp, int mode, Elem elem, hipStream_t s) {
   if (a.M < 2 || a.M > kLetkfMaxM || a.npts < 0) return hipErrorInvalidValue;
-  const int T = letkf_tiles_side(a.M);
-  if (kLetkfTiles * (letkf_threads(a.M) / 64) < T * (T + 1) / 2 || letkf_lds_bytes(a.M) > 160 * 1024) return hipErrorInvalidValue;
+  const bool ctl = a.dc != nullptr;
+  if (ctl && (mode == kLetkfWeights || !a.ctl_in || !a.ctl_out)) return hipErrorInvalidValue;
+  const int T = letkf_tiles_side(a.M, ctl);
+  if (kLetkfTiles * (letkf_threads(a.M, ctl) / 64) < T * (T + 1) / 2 || letkf_lds_bytes(a.M, ctl) > 160 * 1024) return hipErrorInvalidValue;
   if (grp) {
     if (grp->ngroups < 1 || !grp->rep || !grp->grp_off || !grp->grp_leads || grp->s_pitch < 1) return hipErrorInvalidValue;
     if (a.idx && !grp->S) return hipErrorInvalidValue;  // (no lists: the table is never read)
@@ -604,6 +685,15 @@ hipError_t launch_letkf_prior(long P, int M, const double* Yp, const double* ym,
   const long b = (P + 3) / 4;
   hipLaunchKernelGGL(k_letkf_prior, dim3((unsigned)(b > 4096 ? 4096 : b)), dim3(256), 0, s, P, M, Yp, ym, ob_value, ob_error, ob_req, t2,
                      prior_mean, prior_var, assimilated, act, dr);
+  return hipGetLastError();
+}
+
+hipError_t launch_letkf_control_prior(long P, const double* ob_value, const double* yc, const uint8_t* assimilated, double* dc,
+                                      hipStream_t s) {
+  if (P < 1 || !ob_value || !yc || !assimilated || !dc) return hipErrorInvalidValue;
+  const long b = (P + 255) / 256;
+  if (b > 0x7FFFFFF0L) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_letkf_control_prior, dim3((unsigned)b), dim3(256), 0, s, P, ob_value, yc, assimilated, dc);
   return hipGetLastError();
 }
 

@@ -8,6 +8,9 @@
 //          solve per (group, column or node).
 //   inflation  the context's per-point field (efa_ctx_set_letkf_inflation), checked against the call before any
 //          launch, goes with the launch that solves: the columns' or the nodes'; the obs block takes the fixed ob factors.
+//   control  the context's deterministic control (efa_ctx_set_letkf_control), checked against the call before any
+//          launch: its innovations d^c beside dr (k_letkf_control_prior), then a second right-hand side in the obs block's and the
+//          columns' launch.  The plain and the slab cycle serve it; the interp cycles and the weights entries refuse it.
 #include "efa_driver.h"
 
 #include <cmath>
@@ -27,7 +30,7 @@ namespace {
 struct LetkfObs {
   long P = 0;
   double *value = nullptr, *error = nullptr, *lat = nullptr, *lon = nullptr, *hw = nullptr, *req = nullptr;
-  double *act = nullptr, *dr = nullptr, *obtrig = nullptr;
+  double *act = nullptr, *dr = nullptr, *obtrig = nullptr, *dc = nullptr;
   double *prior_mean = nullptr, *prior_var = nullptr, *post_mean = nullptr, *post_var = nullptr;
   uint8_t* assimilated = nullptr;
   size_t diag_bytes() const { return 4 * (size_t)P * sizeof(double) + (size_t)P; }
@@ -94,8 +97,9 @@ int letkf_check_obs(const char* who, long P, const double* ym_dev, const double*
 int letkf_stage_obs(efa_ctx* c, int M, long P, const double* ym_dev, const double* Yp_dev, const ObsIn& in, LetkfObs* out) {
   hipStream_t s = c->stream;
   const size_t n = (size_t)P;
-  // value | error | lat | lon | hw | requested [n each] | act [4n] | dr [2n] | obtrig [6n] | four diagnostics [n each] | assimilated bytes
-  EFA_TRY(c->letkf_ob.reserve((22 * n + 1) * sizeof(double) + n));
+  // value | error | lat | lon | hw | requested [n each] | act [4n] | dr [2n] | obtrig [6n] | dc [n] | four diagnostics [n each] |
+  // assimilated bytes
+  EFA_TRY(c->letkf_ob.reserve((23 * n + 1) * sizeof(double) + n));
   double* d = c->letkf_ob.as<double>();
   LetkfObs o;
   o.P = P;
@@ -108,11 +112,12 @@ int letkf_stage_obs(efa_ctx* c, int M, long P, const double* ym_dev, const doubl
   o.act = d + 6 * n;
   o.dr = d + 10 * n;
   o.obtrig = d + 12 * n;
-  o.prior_mean = d + 18 * n;
-  o.prior_var = d + 19 * n;
-  o.post_mean = d + 20 * n;
-  o.post_var = d + 21 * n;
-  o.assimilated = reinterpret_cast<uint8_t*>(d + 22 * n);
+  o.dc = d + 18 * n;
+  o.prior_mean = d + 19 * n;
+  o.prior_var = d + 20 * n;
+  o.post_mean = d + 21 * n;
+  o.post_var = d + 22 * n;
+  o.assimilated = reinterpret_cast<uint8_t*>(d + 23 * n);
   // value and error of an ob that is not requested are not read: the device gets the neutral pair (0, 1), its radius a harmless 1
   std::vector<double> h(6 * n);
   for (size_t k = 0; k < n; ++k) {
@@ -128,6 +133,8 @@ int letkf_stage_obs(efa_ctx* c, int M, long P, const double* ym_dev, const doubl
   EFA_HIP(hipStreamSynchronize(s));  // (h goes out of scope)
   EFA_HIP(launch_letkf_prior(P, M, Yp_dev, ym_dev, o.value, o.error, o.req, c->qc_threshold * c->qc_threshold, o.prior_mean,
                              o.prior_var, o.assimilated, o.act, o.dr, s));
+  // the control's innovations under the same effective flags
+  if (c->lc_xc) EFA_HIP(launch_letkf_control_prior(P, o.value, c->lc_yc, o.assimilated, o.dc, s));
   *out = o;
   return EFA_OK;
 }
@@ -227,6 +234,26 @@ int letkf_check_inflation(efa_ctx* c, const char* who, long P, long nsolve, bool
   if (nsolve > 0) EFA_TRY(check(c->li_field, nsolve, "the field's value"));
   if (obs_block && c->li_ob && P > 0) EFA_TRY(check(c->li_ob, P, "the factor of observation"));
   return EFA_OK;
+}
+
+// The control setting against a call, before any launch.  served: the plain and the slab cycle; every other entry
+// that solves has no place for w^c (the pairs are laid out [M][M + 1]) and refuses the call while the setting is on.
+int letkf_check_control(const efa_ctx* c, const char* who, bool served, long rows, long P) {
+  if (!c->lc_xc) return EFA_OK;
+  if (!served)
+    return fail(EFA_ERR_INVALID, "%s: a LETKF control is set (efa_ctx_set_letkf_control): the pairs [T | w] this call solves or "
+                "interpolates have no place for the control's weight vector w^c; weight interpolation of w^c is a follow-up", who);
+  if (c->lc_rows != rows) return fail(EFA_ERR_INVALID, "%s: the LETKF control was set for %ld rows, the call has %ld", who, c->lc_rows, rows);
+  if (c->lc_P != P) return fail(EFA_ERR_INVALID, "%s: the LETKF control was set for %ld observations, the call has %ld", who, c->lc_P, P);
+  return EFA_OK;
+}
+
+// ... into the arguments of the obs block's launch (y_c) or of the columns' (x_c)
+void letkf_args_control(const efa_ctx* c, LetkfArgs* a, const LetkfObs& o, bool obs_block) {
+  if (!c->lc_xc || !o.dc) return;  // (no obs: no solve, the driver copies the control)
+  a->dc = o.dc;
+  a->ctl_in = obs_block ? c->lc_yc : c->lc_xc;
+  a->ctl_out = obs_block ? c->lc_yc_post : c->lc_xc_post;
 }
 
 // ... into the arguments of a state or node solve (the field, updated when sigma_b > 0) or of the obs block (the fixed ob factors)
@@ -395,6 +422,7 @@ int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const double* ym_dev, co
   const int M = r.M;
   const char* who = letkf_cycle_name(slab, mesh != nullptr, r.elem == Elem::f32);
   EFA_TRY(letkf_check_settings(c, who, M, P, slab, n_lead));
+  EFA_TRY(letkf_check_control(c, who, mesh == nullptr, rows, P));
   LetkfMesh nodes{};
   if (mesh) {
     EFA_TRY(letkf_check_mesh(who, *mesh, &nodes));
@@ -443,6 +471,7 @@ int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const double* ym_dev, co
     a.ym_out = ymw;
     a.Yp_out = Yw;
     letkf_args_inflation(c, &a, true);
+    letkf_args_control(c, &a, o, true);
     EFA_HIP(launch_letkf(a, nullptr, kLetkfPerts, Elem::f64, s));
     EFA_HIP(launch_etkf_post(P, M, Yw, ymw, o.post_mean, o.post_var, s));
   }
@@ -493,7 +522,10 @@ int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const double* ym_dev, co
     a.relax_kind = c->relax_kind;
     a.relax_alpha = c->relax_alpha;
     letkf_args_inflation(c, &a, false);
+    letkf_args_control(c, &a, o, false);
     EFA_HIP(launch_letkf(a, grp, kLetkfMembers, r.elem, s));
+    if (c->lc_xc && !a.dc && c->lc_xc_post != c->lc_xc)  // (P == 0: the control keeps its rows as every column does)
+      EFA_HIP(hipMemcpyAsync(c->lc_xc_post, c->lc_xc, (size_t)rows * sizeof(double), hipMemcpyDeviceToDevice, s));
     c->state_launches = 1;
   }
   if (c->timing) {
@@ -539,6 +571,7 @@ int letkf_weights(efa_ctx* c, int M, long P, const double* ym_dev, const double*
   const char* who = slab ? "efa_letkf_slab_weights_dev" : "efa_letkf_weights_dev";
   const long n_lead = c->sl_on ? c->sl_nlead : c->vl_nlead;  // (slab: the slabs are the settings' own)
   EFA_TRY(letkf_check_settings(c, who, M, P, slab, slab ? n_lead : -1));
+  EFA_TRY(letkf_check_control(c, who, false, 0, P));
   if (npts < 0) return fail(EFA_ERR_INVALID, "%s: negative point count", who);
   if (npts > 0 && (!pt_lat || !pt_lon || !Tw_dev)) return fail(EFA_ERR_INVALID, "%s: null point or output array", who);
   EFA_TRY(letkf_check_obs(who, P, ym_dev, Yp_dev, ob));

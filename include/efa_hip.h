@@ -520,6 +520,46 @@ int efa_letkf_slab_groups(efa_ctx *ctx, long n_lead, int *group_of /* [n_lead] o
 int efa_ctx_set_letkf_inflation(efa_ctx *ctx, double *field_dev, long nsolve, const double *ob_infl_dev, long P, double sigma_b,
                                 double lower, double upper, double *infl_stats_dev);
 
+/* ---- LETKF: the deterministic control analysis (Schraff et al. 2016, QJRMS
+ * 142; the control member of Hunt et al. 2007, section 4) ----
+ * Context state like the inflation.  A single forecast x_c carried beside the
+ * ensemble is adjusted by the same observations through the ensemble's
+ * covariances:
+ *   x_c^a = x_c + X' [ (M-1)/lambda I + Y^T (rho o R^-1) Y ]^-1 Y^T (rho o R^-1) (y - H(x_c)).
+ * xc_dev [rows] is the control, one float64 value per state row in the state's
+ * row order lead*ncol + col (float64 also beside float32 member rows); yc_dev
+ * [P] its observation estimates H(x_c).  At every solve point x (a column, a
+ * (slab group, column), an ob position), over the listed obs with an effective
+ * flag a_k = 1 and rho_k(x) != 0, with V, mu, rho_k, r_k those of the
+ * ensemble's solve at that point (slab factor and inflation shift included):
+ *   d^c_k = value_k - yc[k],  g^c = sum_k (rho_k/r_k) d^c_k Yp_k^T,  w^c = V diag(1/mu) V^T g^c,
+ *   xc_post[row] = xc[row] + X'[row,:] . w^c      for every row the point maps,
+ *   yc_post[j]   = yc[j] + Yp_j . w^c(ob j's position)   for all P obs,
+ * X' the row's PRIOR perturbations in float64.  The effective flag is decided
+ * on the ENSEMBLE mean's innovation: the control never votes in the outlier
+ * check, and value, error and yc of an ob with a_k = 0 are never read.
+ * The ensemble is untouched: with the control set every ensemble output
+ * (posterior members, obs block, diagnostics, col_stats, the inflation field
+ * and its statistics) has the bits it has without it, whatever xc and yc hold.
+ * Relaxation (RTPS, RTPP) acts on perturbations and does not reach the control.
+ * A point no ob reaches copies its control rows bit for bit (leaves them alone
+ * when xc_post_dev == xc_dev), and yc_post[j] = yc[j] bit for bit for an ob
+ * position no ob reaches.  A NaN yc[k] of an assimilated ob makes NaN the
+ * control rows of exactly the columns with rho_k != 0.  Same inputs, same bits:
+ * a row's control value is read and written by the wave that owns the row.
+ * Served by efa_letkf_cycle_dev / _f32_dev and efa_letkf_slab_cycle_dev /
+ * _f32_dev; these refuse, with EFA_ERR_INVALID before any launch, rows or P
+ * that differ from the call's.  While the setting is on the four interp cycles,
+ * efa_letkf_weights_dev and efa_letkf_slab_weights_dev are refused likewise:
+ * their [M][M+1] pair layout has no place for w^c.  efa_letkf_interp_apply_dev
+ * / _f32_dev take no obs and IGNORE the setting; so do the EnSRF and ETKF
+ * entries.  The setter refuses (the setting stays as it was) negative counts,
+ * null or misaligned arrays, xc_post_dev overlapping xc_dev without coinciding
+ * with it, and yc_post_dev overlapping yc_dev; the control's arrays must be
+ * clear of every other array of the call.  xc_dev == NULL turns it off. */
+int efa_ctx_set_letkf_control(efa_ctx *ctx, const double *xc_dev, double *xc_post_dev, long rows, const double *yc_dev,
+                              double *yc_post_dev, long P);
+
 /* ---- device memory for callers without their own allocator -------------*/
 int efa_malloc(efa_ctx *ctx, size_t bytes, void **dev_out);
 int efa_free(efa_ctx *ctx, void *dev);
