@@ -35,6 +35,7 @@ c_double_p = ctypes.POINTER(ctypes.c_double)
 c_uint8_p = ctypes.POINTER(ctypes.c_uint8)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
+c_long_p = ctypes.POINTER(ctypes.c_long)
 c_void_pp = ctypes.POINTER(ctypes.c_void_p)
 
 # every exported symbol with its (restype, argtypes); tests check this table
@@ -56,6 +57,8 @@ SIGNATURES = {
                                                    ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
     "efa_ctx_set_letkf_control": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
                                                  ctypes.c_void_p, ctypes.c_long]),
+    "efa_ctx_set_letkf_obs_cap": (ctypes.c_int, [ctypes.c_void_p, c_int32_p, ctypes.c_long, c_long_p, ctypes.c_int, ctypes.c_void_p,
+                                                 ctypes.c_long]),
     "efa_ctx_set_vertical_localization": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, c_double_p, ctypes.c_long,
                                                          c_double_p, c_double_p]),
     "efa_ctx_set_slab_localization": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, c_double_p, c_int32_p, ctypes.c_long,
@@ -551,6 +554,29 @@ class Context(object):
         P = 0 if yc is None else int(np.prod(yc.shape, dtype=np.int64))
         _check(self.lib, self.lib.efa_ctx_set_letkf_control(self.handle, self._addr(xc), self._addr(xc_post), rows, self._addr(yc),
                                                             self._addr(yc_post), P))
+
+    def set_letkf_obs_cap(self, ob_class, caps, reach=None, P=None):
+        """The cap on the local observations of every later plain or weight-interpolated LETKF cycle and of letkf_weights on this
+        context: ob_class a host int array [P] of classes 0..len(caps)-1 (None: every ob is of class 0, P then
+        gives their number), caps the most obs of each class one local analysis may use, 0 meaning no limit; reach a float64
+        DeviceArray [solve points] that receives the count before the cap (kept alive by the caller), or None.  caps None turns
+        it off."""
+        if caps is None:
+            _check(self.lib, self.lib.efa_ctx_set_letkf_obs_cap(self.handle, None, 0, None, 0, None, 0))
+            return
+        caps_h = np.ascontiguousarray(caps, dtype=np.int64).reshape(-1)
+        cls_h = None
+        if ob_class is not None:
+            cls_h = np.ascontiguousarray(ob_class, dtype=np.int32).reshape(-1)
+            if P is not None and int(P) != cls_h.size:
+                raise ValueError("set_letkf_obs_cap: ob_class has %d entries, P=%d" % (cls_h.size, int(P)))
+            P = cls_h.size
+        elif P is None:
+            raise ValueError("set_letkf_obs_cap: without ob_class the observation count P must be given")
+        nsolve = 0 if reach is None else int(np.prod(reach.shape, dtype=np.int64))
+        _check(self.lib, self.lib.efa_ctx_set_letkf_obs_cap(
+            self.handle, None if cls_h is None else cls_h.ctypes.data_as(c_int32_p), int(P),
+            caps_h.ctypes.data_as(c_long_p), int(caps_h.size), self._addr(reach), nsolve))
 
     def set_vertical_localization(self, lead_vert=None, ob_vert=None, ob_vert_halfwidth=None):
         """Vertical localisation of every later GC cycle on this context: host arrays lead_vert [n_lead] and

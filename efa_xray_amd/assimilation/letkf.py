@@ -50,6 +50,15 @@ one-member `EnsembleState`, the control analysis), `ob_prior` (P,) = H(x_c) and 
 assimilated.  The ensemble's results -- the return value and the five diagnostics -- do not change by a bit; the outlier check is
 decided on the ensemble mean alone; relaxation and the constant `inflation=` hook act on the ensemble's perturbations only.
 `control` with `weight_stride` raises ValueError: weight interpolation of w^c is the follow-up.
+
+`max_local_obs=N` caps the observations one local analysis may use, as Miyoshi's `nobsl`, SCALE-LETKF's
+`MAX_NOBS_PER_GRID` and JEDI's `max nobs` do: at every solve point (a column, a node of the `weight_stride` mesh, an observation's
+own position) only the N assimilated observations with the LARGEST taper keep it, equal tapers ordered by position in `obs`.  An int
+>= 1 caps all observations together; `{obtype: N}` caps each named `obtype` on its own (an obtype that is not named has no limit, a
+named obtype no observation has is ignored, at most 31 may be named), so that a dense network does not swamp the sparse one around
+it.  An observation that is not assimilated (not requested, or rejected by `outlier_threshold`) takes no place.  `last_solve` gains
+`n_reach`, the count before the cap, beside `n_local` = sum over the classes of min(N, reach).  It combines with every other option
+of `LETKF`; `SlabLETKF` takes it only without its three keywords (a cap per slab group is the follow-up).
 """
 from collections import OrderedDict
 from copy import deepcopy
@@ -88,6 +97,43 @@ def _weight_stride(stride):
     return None if pair == (1, 1) else pair
 
 
+MAX_CAP_OBTYPES = 31     # named obtypes of max_local_obs: the library has 32 classes, one is "not named"
+
+
+def _count(n, what):
+    """n as an int >= 1; ValueError for anything else, booleans and floats included."""
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError("%s must be an integer >= 1, got %r" % (what, n))
+    return int(n)
+
+
+def _max_local_obs(cap):
+    """None, or (names, caps): names None and caps (N,) for the int form, else the named obtypes and their caps."""
+    if cap is None:
+        return None
+    if isinstance(cap, dict):
+        if not cap:
+            raise ValueError("max_local_obs: the dict names no obtype; use None for no cap")
+        if len(cap) > MAX_CAP_OBTYPES:
+            raise ValueError("max_local_obs names %d obtypes, more than %d" % (len(cap), MAX_CAP_OBTYPES))
+        names = list(cap)
+        return names, tuple(_count(cap[name], "max_local_obs[%r]" % (name,)) for name in names)
+    return None, (_count(cap, "max_local_obs"),)
+
+
+def _cap_classes(cap, obs):
+    """(ob_class or None, caps) as Context.set_letkf_obs_cap takes them: the named obtypes some ob has are the classes 0.., the
+    class behind them (cap 0: no limit) takes every other ob."""
+    names, caps = cap
+    if names is None:
+        return None, list(caps)
+    have = set(ob.obtype for ob in obs)
+    keep = [i for i, name in enumerate(names) if name in have]
+    cls = {names[i]: j for j, i in enumerate(keep)}
+    ob_class = np.array([cls.get(ob.obtype, len(keep)) for ob in obs], dtype=np.int32)
+    return ob_class, [caps[i] for i in keep] + [0]
+
+
 def _check_control(state, ctrl):
     """ValueError unless `ctrl` is a one-member EnsembleState on the state's variables, coordinates and grid."""
     if not isinstance(ctrl, EnsembleState):
@@ -114,9 +160,18 @@ class LETKF(EnSRF):
         (use `ETKF` for the unlocalised filter), adaptive_inflation, vert_coord, time_localize, var_impact,
         sampling_error_correction, streamed, path, obs_batch, a weight_stride that is not an integer >= 1, and for more than 136 members (the eigen-solve of a column keeps
         its M x M array in LDS).  control (None, or a one-member `EnsembleState` on the state's variables, coordinates and grid:
-        the module's docstring): ValueError for anything else and for control with a weight_stride.  `update_arrays` is not
-        offered."""
+        the module's docstring): ValueError for anything else and for control with a weight_stride.  max_local_obs (None, an
+        int >= 1 or {obtype: int >= 1} with at most 31 names: the module's docstring): ValueError for anything else, and under
+        `SlabLETKF` together with any of its three keywords.  `update_arrays` is not offered."""
         stride = _weight_stride(kw.pop("weight_stride", None))
+        cap = _max_local_obs(kw.pop("max_local_obs", None))
+        if cap is not None:
+            for name in self._served:
+                if kw.get(name) is not None and kw.get(name) is not False:
+                    raise ValueError("%s: max_local_obs and %s do not combine: under the vertical / temporal / variable factors "
+                                     "the taper of a solve is a product per (slab group, column) while the cap ranks the per-column "
+                                     "tapers of the lists (a cap per group is the follow-up, DESIGN.md 7y-8)"
+                                     % (type(self).__name__, name))
         ctrl = kw.pop("control", None)
         if ctrl is not None:
             _check_control(state, ctrl)
@@ -146,6 +201,7 @@ class LETKF(EnSRF):
         self.column_inflation = ci
         self.control = ctrl
         self.last_control = None
+        self.max_local_obs = cap
 
     _cycle_line = "Beginning the column solves"
 
@@ -180,7 +236,16 @@ class LETKF(EnSRF):
             _check_control(prior, ctrl)
             xc = np.ascontiguousarray(ctrl.to_vect()[:, 0], dtype=np.float64)
             yc = self._control_estimates(ctx, ctrl, xc) if P else None
+        cap = self.max_local_obs
+        if cap is not None:
+            if slab:
+                raise ValueError("%s: max_local_obs does not combine with vertical / temporal / variable localisation "
+                                 "(DESIGN.md 7y-8)" % type(self).__name__)
+            ob_class, caps = _cap_classes(cap, self.obs)
         try:
+            if cap is not None:
+                reach = ctx.empty((sy * sx,))
+                ctx.set_letkf_obs_cap(ob_class, caps, reach, P=P)
             if ctrl is not None:
                 xc_dev, xc_post = ctx.to_device(xc), ctx.empty((max(N, 1),))
                 yc_dev = yc_post = None
@@ -211,6 +276,8 @@ class LETKF(EnSRF):
                 ctx.set_letkf_inflation(None)
             if ctrl is not None:
                 ctx.set_letkf_control(None)
+            if cap is not None:
+                ctx.set_letkf_obs_cap(None, None)
         st = stats.download().reshape(ng, sy, sx, 3)
         if not slab:                            # the plain filter documents (ny, nx) / (nyn, nxn)
             st = st[0]
@@ -219,6 +286,8 @@ class LETKF(EnSRF):
             self.last_solve.update(group_of_slab=group_of.astype(np.int64).reshape(prior.nvars(), prior.ntimes()))
         if mesh:
             self.last_solve.update(node_y=node_y, node_x=node_x)
+        if cap is not None:
+            self.last_solve.update(n_reach=reach.download().reshape(sy, sx).astype(np.int64))
         if ci is not None:
             ci.values = lam_dev.download().reshape(lam_shape)       # the next update's prior factors
             self.last_solve.update(inflation=lam_b, inflation_post=ci.values.copy(),

@@ -362,6 +362,38 @@ int efa_ctx_set_letkf_control(efa_ctx* c, const double* xc_dev, double* xc_post_
   return EFA_OK;
 }
 
+int efa_ctx_set_letkf_obs_cap(efa_ctx* c, const int* ob_class, long P, const long* cap, int nclass, double* reach_dev, long nsolve) {
+  EFA_TRY(use(c));
+  if (!cap) {
+    c->oc_on = c->oc_has_class = false;
+    c->oc_nclass = 0;
+    c->oc_P = c->oc_nsolve = 0;
+    c->oc_reach = nullptr;
+    return EFA_OK;
+  }
+  if (nclass < 1 || nclass > 32) return fail(EFA_ERR_INVALID, "LETKF obs cap: nclass=%d must be within 1..32", nclass);
+  if (P < 0 || nsolve < 0) return fail(EFA_ERR_INVALID, "LETKF obs cap: negative count (P=%ld, nsolve=%ld)", P, nsolve);
+  for (int k = 0; k < nclass; ++k)
+    if (cap[k] < 0) return fail(EFA_ERR_INVALID, "LETKF obs cap: the cap of class %d is %ld (must be >= 0, 0 meaning no limit)", k, cap[k]);
+  if (ob_class)
+    for (long k = 0; k < P; ++k)
+      if (ob_class[k] < 0 || ob_class[k] >= nclass)
+        return fail(EFA_ERR_INVALID, "LETKF obs cap: observation %ld has class %d, outside 0..%d", k, ob_class[k], nclass - 1);
+  if ((reinterpret_cast<uintptr_t>(reach_dev) & 7u) != 0) return fail(EFA_ERR_INVALID, "LETKF obs cap: reach_dev must be 8-byte aligned");
+  if (ob_class && P > 0) {
+    EFA_TRY(h2d(c, c->oc_class, ob_class, (size_t)P * sizeof(int)));
+    EFA_HIP(hipStreamSynchronize(c->stream));  // (the caller may reuse its array on return)
+  }
+  c->oc_on = true;
+  c->oc_has_class = ob_class != nullptr && P > 0;
+  c->oc_nclass = nclass;
+  for (int k = 0; k < 32; ++k) c->oc_cap[k] = k < nclass ? (int)(cap[k] > 0x7FFFFFFFL ? 0x7FFFFFFFL : cap[k]) : 0;
+  c->oc_P = P;
+  c->oc_reach = reach_dev;
+  c->oc_nsolve = reach_dev ? nsolve : 0;
+  return EFA_OK;
+}
+
 int efa_ctx_set_vertical_localization(efa_ctx* c, long n_lead, const double* lead_vert, long P, const double* ob_vert,
                                       const double* ob_vert_halfwidth) {
   EFA_TRY(use(c));

@@ -324,6 +324,15 @@ struct efa_ctx {
   const double* lc_yc = nullptr;     // [P] H(x_c)
   double* lc_yc_post = nullptr;      // [P] the analysis' ob estimates (clear of lc_yc)
   long lc_rows = 0, lc_P = 0;
+  // --- the LETKF's cap on the local obs of a solve (efa_ctx_set_letkf_obs_cap)
+  bool oc_on = false;
+  int oc_nclass = 0;
+  int oc_cap[32] = {};               // per class, 0: no limit (a cap beyond INT_MAX is none: a list has fewer entries)
+  long oc_P = 0;
+  bool oc_has_class = false;         // false: every ob is of class 0
+  DevBuf oc_class;                   // [P] ints, the class of every ob
+  double* oc_reach = nullptr;        // [nsolve] the caller's device array, or null
+  long oc_nsolve = 0;
   // --- the LETKF's slab groups (efa_letkf_slab_cycle_dev): slabs whose factors agree for every ob share one solve
   std::vector<int> lg_group_of;                   // [n_lead] the group of every slab, numbered by first appearance
   int lg_ngroups = 0;

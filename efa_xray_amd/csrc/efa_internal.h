@@ -423,6 +423,22 @@ hipError_t launch_letkf_prior(long P, int M, const double* Yp, const double* ym,
 // a thread per ob: dc[k] = value[k] - yc[k] where assimilated[k] (k_letkf_prior's verdict), else the neutral 0 (value and yc not read)
 hipError_t launch_letkf_control_prior(long P, const double* ob_value, const double* yc, const uint8_t* assimilated, double* dc,
                                       hipStream_t s);
+// The cap on the local obs of a solve, between launch_gc_fill and the solve: per point and class, of the listed obs
+// with a non-zero taper the cap[c] with the largest taper keep it (equal bits: list order), the others' tapers become 0.0, which every
+// reader of the lists takes as "not listed".  A point at which no class is over its cap is not written.
+constexpr int kLetkfCapClasses = 32;
+struct LetkfCapArgs {
+  long npts;
+  const long* off;      // the lists of launch_gc_fill over these points
+  const int* cnt;
+  const int* idx;
+  double* wts;
+  const int* ob_class;  // [P] 0..nclass-1, or null: every ob is of class 0
+  int nclass;
+  int cap[kLetkfCapClasses];  // 0: no limit for the class
+  double* reach;        // [npts] the non-zero tapers of the point before the cap, as a double; or null
+};
+hipError_t launch_letkf_cap(const LetkfCapArgs& a, hipStream_t s);
 // ---- weight interpolation (efa_letkf_interp.hip): [T | w] solved at the nodes of a coarse mesh of grid columns,
 // interpolated bilinearly in grid-index space to every column and applied to its rows
 struct LetkfMesh {

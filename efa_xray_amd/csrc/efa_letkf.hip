@@ -41,6 +41,9 @@
 // d^c_k = value_k - H(x_c)_k from k_letkf_control_prior, column M+1 of the (M+2)^2 product is g^c, h^c = (V^T g^c)/mu goes over n_s
 // behind the sweeps, and the wave that owns a row adds h^c . z to the control's value of that row (the obs block: to y_c[j]).  A
 // template switch (CTRL): without a.dc the kernels are the ones without it.
+// The cap on the local obs of a solve (efa_ctx_set_letkf_obs_cap): k_letkf_cap runs between the list build and
+// the solve and zeroes, per point and class, the tapers of all but the cap[c] largest; a zero taper is "not listed" to every kernel
+// above (the select of the Gram, the n_local loop, p3), so none of them changes.
 // This file holds the kernels and their launchers only.
 #include "efa_driver.h"
 #include "efa_device.h"
@@ -617,6 +620,159 @@ __global__ __launch_bounds__(256) void k_letkf_obs_factor(long P, const long* __
   }
 }
 
+// ---- the cap on the local obs of a solve -------------------------------------------------------------------------
+// One workgroup per block of 16 points, between the list build and the solve.  Thread t = (column t & 15, entry slot t >> 4): a wave
+// reads four whole 128-byte entries of wts per step.  Per class that is over its cap at some column of the block, a radix select on
+// the taper's 64-bit pattern, most significant byte first: the counts of the byte's 256 values per column in LDS (integer atomics),
+// then per column the value at which the places run out; a column stops as soon as the candidates that remain equal the places that
+// remain.  The keys are re-read through L2 in every pass (a list is up to P long).  One more pass in list order, each wave a
+// contiguous quarter of the list, zeroes the losers; at a threshold shared by more candidates than places (equal bits) the first in
+// list order win, their ranks from ballots within the wave and, across the waves, from a counting pass that runs only then.
+constexpr int kCapThreads = 256;
+constexpr int kCapBins = 256;
+// the count of byte value d on column c.  Rows of 16 columns: the 16 columns of an entry never share a bank, whatever their bytes are
+// (neighbouring columns have nearly the same taper, so [column][value] would put them on one bank).  One row of padding per 16 values:
+// the runs of 16 values that the four slots of a wave sum start 16 banks apart.
+__device__ __forceinline__ int cap_hist(int d, int c) { return (d + (d >> 4)) * 16 + c; }
+// every double but NaN orders as this key; positive doubles as their bits
+__device__ __forceinline__ unsigned long long cap_key(double w) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(w);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+__global__ __launch_bounds__(kCapThreads) void k_letkf_cap(const LetkfCapArgs a) {
+  __shared__ unsigned hist[(kCapBins + kCapBins / 16) * 16];
+  __shared__ unsigned part[16][16];                  // [slot][column] the sum of values 16 slot .. 16 slot + 15
+  __shared__ int reach_s[kLetkfCapClasses][16];      // the non-zero tapers per (class, column)
+  __shared__ unsigned long long pre_s[16];           // per column: the key's leading bytes decided so far,
+  __shared__ int need_s[16], cand_s[16];             //   the places left for the candidates that have them, and how many those are,
+  __shared__ int sel_s[16], bite_s[16], shift_s[16]; //   still selecting, over the cap at all, the shift at which it stopped
+  __shared__ int tie_s[kCapThreads / 64][16];        // [wave][column] the candidates at the threshold in the wave's part of the list
+  const int tid = (int)threadIdx.x, col = tid & 15, slot = tid >> 4, lane = tid & 63, wv = tid >> 6;
+  const long blk = (long)blockIdx.x;
+  const long off = a.off[blk];
+  const int n = a.cnt[blk];
+  double* wts = a.wts + (size_t)off * 16;
+  const int* idx = a.idx + off;
+
+  for (int i = tid; i < kLetkfCapClasses * 16; i += kCapThreads) (&reach_s[0][0])[i] = 0;
+  __syncthreads();
+  for (int e = slot; e < n; e += 16) {
+    if (wts[(size_t)e * 16 + col] == 0.0) continue;
+    const int cls = a.ob_class ? a.ob_class[idx[e]] : 0;
+    atomicAdd(&reach_s[cls][col], 1);
+  }
+  __syncthreads();
+  if (a.reach && tid < 16 && blk * 16 + tid < a.npts) {
+    int r = 0;
+    for (int c = 0; c < a.nclass; ++c) r += reach_s[c][tid];
+    a.reach[blk * 16 + tid] = (double)r;
+  }
+
+#pragma unroll 1
+  for (int c = 0; c < a.nclass; ++c) {
+    const int cap = a.cap[c];
+    if (cap <= 0) continue;  // (uniform) no limit
+    const int reach = reach_s[c][col];
+    if (!__syncthreads_or(reach > cap)) continue;  // no column of the block is over this class's cap: nothing is written
+    if (tid < 16) {  // (col == tid)
+      pre_s[tid] = 0ull;
+      need_s[tid] = cap;
+      cand_s[tid] = reach;
+      sel_s[tid] = bite_s[tid] = reach > cap ? 1 : 0;
+      shift_s[tid] = 0;
+    }
+    // ---- the select: one byte per pass, most significant first ------------------------------------------------------------------
+#pragma unroll 1
+    for (int shift = 56;; shift -= 8) {
+      for (int i = tid; i < (kCapBins + kCapBins / 16) * 16; i += kCapThreads) hist[i] = 0u;
+      __syncthreads();
+      const bool sel = sel_s[col] != 0;
+      const unsigned long long pre = pre_s[col];
+      if (sel)
+        for (int e = slot; e < n; e += 16) {
+          const double w = wts[(size_t)e * 16 + col];
+          if (w == 0.0) continue;
+          if (a.ob_class && a.ob_class[idx[e]] != c) continue;
+          const unsigned long long key = cap_key(w);
+          if (shift < 56 && (key >> (shift + 8)) != pre) continue;
+          atomicAdd(&hist[cap_hist((int)((key >> shift) & 255ull), col)], 1u);
+        }
+      __syncthreads();
+      {
+        unsigned s = 0u;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) s += hist[cap_hist(16 * slot + j, col)];
+        part[slot][col] = s;
+      }
+      __syncthreads();
+      if (tid < 16 && sel) {  // from the largest value down to the one at which the places run out (the candidates outnumber them)
+        int need = need_s[tid];
+        unsigned acc = 0u;
+        int sl = 15;
+        for (; sl > 0; --sl) {
+          const unsigned p = part[sl][tid];
+          if (acc + p >= (unsigned)need) break;
+          acc += p;
+        }
+        int d = 16 * sl + 15;
+        for (; d > 16 * sl; --d) {
+          const unsigned h = hist[cap_hist(d, tid)];
+          if (acc + h >= (unsigned)need) break;
+          acc += h;
+        }
+        const int h = (int)hist[cap_hist(d, tid)];
+        need -= (int)acc;
+        pre_s[tid] = (pre << 8) | (unsigned long long)d;
+        need_s[tid] = need;
+        cand_s[tid] = h;
+        if (h == need || shift == 0) {  // every candidate left has a place, or the bits are out: equal tapers, list order decides
+          sel_s[tid] = 0;
+          shift_s[tid] = shift;
+        }
+      }
+      if (!__syncthreads_or(tid < 16 && sel_s[tid] != 0)) break;  // (shift == 0 ends every column)
+    }
+    // ---- the losers to zero, in list order ---------------------------------------------------------------------------------------
+    const int ties = __syncthreads_or(tid < 16 && bite_s[tid] != 0 && need_s[tid] < cand_s[tid]);
+    const bool bite = bite_s[col] != 0;
+    const unsigned long long pre = pre_s[col];
+    const int fs = shift_s[col], need = need_s[col];
+    const int sub = lane >> 4;
+    const int nstep = (n + 3) >> 2, per = (nstep + kCapThreads / 64 - 1) / (kCapThreads / 64);
+    const int s0 = wv * per, s1 = (s0 + per < nstep) ? s0 + per : nstep;
+    const unsigned long long colbits = 0x0001000100010001ull << col;  // this column's lanes of the wave
+    int base = 0;
+    if (ties) {  // (uniform)
+      int cnt = 0;
+      for (int st = s0; st < s1; ++st) {
+        const int e = 4 * st + sub;
+        const double w = (e < n) ? wts[(size_t)e * 16 + col] : 0.0;
+        bool eq = bite && w != 0.0;
+        if (eq && a.ob_class) eq = a.ob_class[idx[e]] == c;
+        eq = eq && (cap_key(w) >> fs) == pre;
+        cnt += __builtin_popcountll(__ballot(eq) & colbits);
+      }
+      if (lane < 16) tie_s[wv][lane] = cnt;
+      __syncthreads();
+      for (int v = 0; v < wv; ++v) base += tie_s[v][col];
+    }
+    int run = base;
+    for (int st = s0; st < s1; ++st) {
+      const int e = 4 * st + sub;
+      const double w = (e < n) ? wts[(size_t)e * 16 + col] : 0.0;
+      bool cnd = bite && w != 0.0;
+      if (cnd && a.ob_class) cnd = a.ob_class[idx[e]] == c;
+      const unsigned long long top = cap_key(w) >> fs;
+      const bool eq = cnd && top == pre;
+      const unsigned long long mine = __ballot(eq) & colbits;
+      const int rank = run + __builtin_popcountll(mine & ((1ull << (16 * sub)) - 1ull));
+      if (cnd && (top < pre || (eq && rank >= need))) wts[(size_t)e * 16 + col] = 0.0;
+      run += __builtin_popcountll(mine);
+    }
+  }
+}
+
 }  // namespace
 
 // The workgroup size, from M: the eigen-solve (where a column spends its time) plays ceil(M/2) column pairs per round on 16 lanes
@@ -675,6 +831,21 @@ hipError_t launch_letkf_obs_factor(long P, const long* off, const int* cnt, cons
   if (nblk > 0x7FFFFFF0L) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_letkf_obs_factor, dim3((unsigned)nblk), dim3(256), 0, s, P, off, cnt, idx, wts, ob_vert, ob_vhw, slab != nullptr,
                      slab ? *slab : SlabObs{});
+  return hipGetLastError();
+}
+
+hipError_t launch_letkf_cap(const LetkfCapArgs& a, hipStream_t s) {
+  if (a.npts <= 0) return hipSuccess;
+  if (!a.off || !a.cnt || !a.idx || !a.wts || a.nclass < 1 || a.nclass > kLetkfCapClasses) return hipErrorInvalidValue;
+  bool any = a.reach != nullptr;
+  for (int c = 0; c < a.nclass; ++c) {
+    if (a.cap[c] < 0) return hipErrorInvalidValue;
+    any = any || a.cap[c] > 0;
+  }
+  if (!any) return hipSuccess;
+  const long nblk = (a.npts + 15) / 16;
+  if (nblk > 0x7FFFFFF0L) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_letkf_cap, dim3((unsigned)nblk), dim3(kCapThreads), 0, s, a);
   return hipGetLastError();
 }
 

@@ -11,6 +11,9 @@
 //   control  the context's deterministic control (efa_ctx_set_letkf_control), checked against the call before any
 //          launch: its innovations d^c beside dr (k_letkf_control_prior), then a second right-hand side in the obs block's and the
 //          columns' launch.  The plain and the slab cycle serve it; the interp cycles and the weights entries refuse it.
+//   cap    the context's cap on the local obs of a solve (efa_ctx_set_letkf_obs_cap), checked against the call before
+//          any launch: k_letkf_cap behind every list build (letkf_build_lists), so the obs', the grid's, the nodes' and the probe's
+//          lists are capped in one place.  The plain and the interp cycles and efa_letkf_weights_dev serve it; the slab entries refuse it.
 #include "efa_driver.h"
 
 #include <cmath>
@@ -141,7 +144,9 @@ int letkf_stage_obs(efa_ctx* c, int M, long P, const double* ym_dev, const doubl
 
 // The lists of `npts` points (device lat / lon) against the obs, by the one-pass sweep's builders as they are; the flag entry of the
 // coefficient table they read is the effective a_k.  One host round trip: the capacity.
-int letkf_build_lists(efa_ctx* c, long npts, const double* plat, const double* plon, const LetkfObs& o, LetkfLists* out) {
+// With the cap set k_letkf_cap follows the fill; reach (or null): where it leaves the points' counts before the cap.
+int letkf_build_lists(efa_ctx* c, long npts, const double* plat, const double* plon, const LetkfObs& o, LetkfLists* out,
+                      double* reach = nullptr) {
   hipStream_t s = c->stream;
   const long nblk = gc_num_blocks(npts);
   const size_t b8 = ((size_t)(nblk + 1) * sizeof(long) + 15) & ~(size_t)15, b4 = ((size_t)nblk * sizeof(int) + 15) & ~(size_t)15;
@@ -161,6 +166,19 @@ int letkf_build_lists(efa_ctx* c, long npts, const double* plat, const double* p
   EFA_TRY(c->letkf_wts.reserve((size_t)(cap ? cap : 1) * 16 * sizeof(double)));
   EFA_HIP(launch_gc_fill(npts, o.P, plat, plon, o.lat, o.lon, o.hw, o.act, o.obtrig, off, cnt, c->letkf_idx.as<int>(),
                          c->letkf_wts.as<double>(), order, c->letkf_pairs.as<unsigned long long>(), s));
+  if (c->oc_on) {
+    LetkfCapArgs ca{};
+    ca.npts = npts;
+    ca.off = off;
+    ca.cnt = cnt;
+    ca.idx = c->letkf_idx.as<int>();
+    ca.wts = c->letkf_wts.as<double>();
+    ca.ob_class = c->oc_has_class ? c->oc_class.as<int>() : nullptr;
+    ca.nclass = c->oc_nclass;
+    for (int k = 0; k < kLetkfCapClasses; ++k) ca.cap[k] = c->oc_cap[k];
+    ca.reach = reach;
+    EFA_HIP(launch_letkf_cap(ca, s));
+  }
   out->off = off;
   out->cnt = cnt;
   out->order = order;
@@ -245,6 +263,21 @@ int letkf_check_control(const efa_ctx* c, const char* who, bool served, long row
                 "interpolates have no place for the control's weight vector w^c; weight interpolation of w^c is a follow-up", who);
   if (c->lc_rows != rows) return fail(EFA_ERR_INVALID, "%s: the LETKF control was set for %ld rows, the call has %ld", who, c->lc_rows, rows);
   if (c->lc_P != P) return fail(EFA_ERR_INVALID, "%s: the LETKF control was set for %ld observations, the call has %ld", who, c->lc_P, P);
+  return EFA_OK;
+}
+
+// The cap setting against a call, before any launch.  served: the plain and the interp cycles and
+// efa_letkf_weights_dev; nsolve: the state's solve points of the call (< 0: it solves at none).
+int letkf_check_cap(const efa_ctx* c, const char* who, bool served, long P, long nsolve) {
+  if (!c->oc_on) return EFA_OK;
+  if (!served)
+    return fail(EFA_ERR_INVALID, "%s: a LETKF obs cap is set (efa_ctx_set_letkf_obs_cap): under the vertical / slab settings the taper "
+                "of a solve is a product per (slab group, column) while the lists' tapers, which the cap ranks, are per column; a cap "
+                "per group is a follow-up", who);
+  if (c->oc_P != P) return fail(EFA_ERR_INVALID, "%s: the LETKF obs cap was set for %ld observations, the call has %ld", who, c->oc_P, P);
+  if (c->oc_reach && nsolve >= 0 && c->oc_nsolve != nsolve)
+    return fail(EFA_ERR_INVALID, "%s: the LETKF obs cap's reach array was set for %ld solve points, the call has %ld (columns, nodes or "
+                "probe points)", who, c->oc_nsolve, nsolve);
   return EFA_OK;
 }
 
@@ -432,6 +465,7 @@ int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const double* ym_dev, co
   EFA_TRY(letkf_check_rows(who, r));
   if (rows > 0) EFA_TRY(check_grid(EFA_LOC_GC, grid_lat, grid_lon, ncol, n_lead, rows));
   EFA_TRY(letkf_check_obs(who, P, ym_dev, Yp_dev, ob));
+  EFA_TRY(letkf_check_cap(c, who, !slab, P, rows > 0 ? (mesh ? nodes.nnodes() : ncol) : -1));
   if (c->li_field) {  // one factor per solve: per (group,) column or node
     long nsolve = -1;
     if (rows > 0) {
@@ -497,11 +531,13 @@ int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const double* ym_dev, co
     if (mesh) {
       const double *dlat = nullptr, *dlon = nullptr;
       EFA_TRY(letkf_upload_nodes(c, nodes, grid_lat, grid_lon, &dlat, &dlon));
-      EFA_TRY(letkf_build_lists(c, nnodes, dlat, dlon, o, &glists));
+      EFA_TRY(letkf_build_lists(c, nnodes, dlat, dlon, o, &glists, c->oc_reach));
     } else {
       EFA_TRY(c->grid.upload(s, grid_lat, grid_lon, ncol));
-      EFA_TRY(letkf_build_lists(c, ncol, c->grid.lat.as<double>(), c->grid.lon.as<double>(), o, &glists));
+      EFA_TRY(letkf_build_lists(c, ncol, c->grid.lat.as<double>(), c->grid.lon.as<double>(), o, &glists, c->oc_reach));
     }
+  } else if (rows > 0 && c->oc_on && c->oc_reach) {  // (P == 0: no lists, no ob reaches a point)
+    EFA_HIP(hipMemsetAsync(c->oc_reach, 0, (size_t)c->oc_nsolve * sizeof(double), s));
   }
   if (c->timing) {
     EFA_HIP(hipEventRecord(c->obs_iv.end, s));
@@ -575,6 +611,7 @@ int letkf_weights(efa_ctx* c, int M, long P, const double* ym_dev, const double*
   if (npts < 0) return fail(EFA_ERR_INVALID, "%s: negative point count", who);
   if (npts > 0 && (!pt_lat || !pt_lon || !Tw_dev)) return fail(EFA_ERR_INVALID, "%s: null point or output array", who);
   EFA_TRY(letkf_check_obs(who, P, ym_dev, Yp_dev, ob));
+  EFA_TRY(letkf_check_cap(c, who, !slab, P, npts));
   if (npts == 0) return EFA_OK;
   if (c->li_field) {
     if (slab) EFA_TRY(letkf_groups(c, n_lead));
@@ -587,7 +624,9 @@ int letkf_weights(efa_ctx* c, int M, long P, const double* ym_dev, const double*
     const double *dlat = nullptr, *dlon = nullptr;
     EFA_TRY(letkf_stage_obs(c, M, P, ym_dev, Yp_dev, ob, &o));
     EFA_TRY(letkf_upload_points(c, npts, pt_lat, pt_lon, &dlat, &dlon));
-    EFA_TRY(letkf_build_lists(c, npts, dlat, dlon, o, &lists));
+    EFA_TRY(letkf_build_lists(c, npts, dlat, dlon, o, &lists, c->oc_reach));
+  } else if (c->oc_on && c->oc_reach) {
+    EFA_HIP(hipMemsetAsync(c->oc_reach, 0, (size_t)c->oc_nsolve * sizeof(double), s));
   }
   LetkfGroups groups{};
   if (slab) EFA_TRY(letkf_slab_groups(c, n_lead, &groups));

@@ -560,6 +560,42 @@ int efa_ctx_set_letkf_inflation(efa_ctx *ctx, double *field_dev, long nsolve, co
 int efa_ctx_set_letkf_control(efa_ctx *ctx, const double *xc_dev, double *xc_post_dev, long rows, const double *yc_dev,
                               double *yc_post_dev, long P);
 
+/* ---- LETKF: a cap on the local observations of a solve, by taper rank and
+ * class (Miyoshi's nobsl, SCALE-LETKF's MAX_NOBS_PER_GRID, JEDI's max nobs)
+ *  ----
+ * Context state like the control.  ob_class [P] (host) gives every ob a class
+ * in 0..nclass-1 (NULL: all of class 0), cap [nclass] (host) the most obs of
+ * that class one local analysis may use, 0 meaning no limit.  At a solve point
+ * x (a grid column, a mesh node, an ob position, a probe point), of the obs of
+ * class c with an effective flag a_k = 1 and rho_k(x) != 0: if there are more
+ * than cap[c], exactly the cap[c] with the LARGEST rho_k(x) keep their taper
+ * and the others get rho_k(x) = 0; equal tapers (the same bits) are ordered by
+ * lower ob index first.  Everything downstream is the LETKF's definition on
+ * the tapers that remain: n_local (= sum_c min(cap[c], reach_c) exactly), dfs,
+ * the inflation's p1..p3, the node pairs of a weight stride.  An ob with
+ * a_k = 0 (not requested, or rejected by the outlier check) takes no place.
+ * The obs block is capped at every ob's own position; with a mesh the nodes
+ * are capped.  A point at which no class is over its cap is not touched: caps
+ * >= P give the call without the setting bit for bit.  The NaN value of an ob
+ * that loses at a point does not reach that point.  Same inputs, same bits.
+ * reach_dev [nsolve] (device, or NULL) receives, for the STATE's solve points
+ * (columns, nodes, probe points) only, the count of non-zero tapers before the
+ * cap, as a double; nsolve is read with reach_dev only.
+ * Served by efa_letkf_cycle_dev / _f32_dev, efa_letkf_cycle_interp_dev /
+ * _f32_dev and efa_letkf_weights_dev; these refuse, with EFA_ERR_INVALID before
+ * any launch, a P (and with reach_dev an nsolve) that differs from the call's.
+ * While the setting is on the four slab cycles and efa_letkf_slab_weights_dev
+ * are refused likewise: their taper is a product per (slab group, column), the
+ * lists' tapers are per column, and a cap per group is a follow-up.
+ * efa_letkf_interp_apply_dev / _f32_dev, the EnSRF, ETKF and impact entries
+ * IGNORE it.  The setter refuses (the setting stays as it was) nclass outside
+ * 1..32, a negative cap, a class outside 0..nclass-1, negative counts and a
+ * misaligned reach_dev.  cap == NULL turns it off.  The cap's launch counts
+ * towards obs_ms of efa_last_timing. */
+int efa_ctx_set_letkf_obs_cap(efa_ctx *ctx, const int *ob_class /* host [P], NULL: all class 0 */, long P,
+                              const long *cap /* host [nclass], NULL: off */, int nclass, double *reach_dev /* [nsolve] or NULL */,
+                              long nsolve);
+
 /* ---- device memory for callers without their own allocator -------------*/
 int efa_malloc(efa_ctx *ctx, size_t bytes, void **dev_out);
 int efa_free(efa_ctx *ctx, void *dev);
