@@ -59,6 +59,8 @@ SIGNATURES = {
                                                  ctypes.c_void_p, ctypes.c_long]),
     "efa_ctx_set_letkf_obs_cap": (ctypes.c_int, [ctypes.c_void_p, c_int32_p, ctypes.c_long, c_long_p, ctypes.c_int, ctypes.c_void_p,
                                                  ctypes.c_long]),
+    "efa_ctx_set_letkf_cross_validation": (ctypes.c_int, [ctypes.c_void_p, c_int32_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                          ctypes.c_long]),
     "efa_ctx_set_vertical_localization": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, c_double_p, ctypes.c_long,
                                                          c_double_p, c_double_p]),
     "efa_ctx_set_slab_localization": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, c_double_p, c_int32_p, ctypes.c_long,
@@ -577,6 +579,19 @@ class Context(object):
         _check(self.lib, self.lib.efa_ctx_set_letkf_obs_cap(
             self.handle, None if cls_h is None else cls_h.ctypes.data_as(c_int32_p), int(P),
             caps_h.ctypes.data_as(c_long_p), int(caps_h.size), self._addr(reach), nsolve))
+
+    def set_letkf_cross_validation(self, groups, cv_stats=None):
+        """The cross-validated perturbation update (Buehner 2020) of every later plain or weight-interpolated LETKF
+        cycle and of letkf_weights on this context: groups a host int array [M], the label 0..K-1 of every member (K >= 2, every
+        label used, at least 2 members outside every group); cv_stats a float64 DeviceArray [solve points, 2] that receives the
+        sub-solves' summed sweeps and largest condition number (kept alive by the caller), or None.  groups None turns it off."""
+        if groups is None:
+            _check(self.lib, self.lib.efa_ctx_set_letkf_cross_validation(self.handle, None, 0, 0, None, 0))
+            return
+        g = np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
+        nsolve = 0 if cv_stats is None else int(np.prod(cv_stats.shape, dtype=np.int64)) // 2
+        _check(self.lib, self.lib.efa_ctx_set_letkf_cross_validation(
+            self.handle, g.ctypes.data_as(c_int32_p), int(g.size), int(g.max()) + 1 if g.size else 0, self._addr(cv_stats), nsolve))
 
     def set_vertical_localization(self, lead_vert=None, ob_vert=None, ob_vert_halfwidth=None):
         """Vertical localisation of every later GC cycle on this context: host arrays lead_vert [n_lead] and

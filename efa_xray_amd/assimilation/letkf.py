@@ -59,6 +59,16 @@ named obtype no observation has is ignored, at most 31 may be named), so that a 
 it.  An observation that is not assimilated (not requested, or rejected by `outlier_threshold`) takes no place.  `last_solve` gains
 `n_reach`, the count before the cap, beside `n_local` = sum over the classes of min(N, reach).  It combines with every other option
 of `LETKF`; `SlabLETKF` takes it only without its three keywords (a cap per slab group is the follow-up).
+
+`cross_validation=K` is the LETKF with cross validation of Buehner (2020): the members are split into K groups
+(an int K >= 2: member m has the label m % K; an integer array (M,): the labels 0..K-1 themselves, every label used), and at every
+solve point the perturbations of each group are updated with the perturbation gain of an LETKF formed from the OTHER groups'
+members alone, which takes the inbreeding out of the posterior spread; the mean keeps the full-ensemble gain, and the posterior
+mean is the plain filter's.  Every group must leave at least 2 members outside it (so M >= 4).  K sub-solves of size M - M/K per
+solve point share the point's one Gram matrix.  `last_solve` gains `cv_sweeps` (the sub-solves' Jacobi sweeps, summed) and
+`cv_cond` (their largest condition number), in the shape of `n_local`.  It combines with weight_stride, max_local_obs, rtps /
+rtpp, outlier_threshold and float32 states; with column_inflation or control it raises ValueError, as it does under `SlabLETKF`
+together with any of its three keywords.
 """
 from collections import OrderedDict
 from copy import deepcopy
@@ -134,6 +144,44 @@ def _cap_classes(cap, obs):
     return ob_class, [caps[i] for i in keep] + [0]
 
 
+def _cross_validation(spec, M):
+    """None, or the labels (M,) int32 of cross_validation=spec; ValueError for anything but an int K >= 2 or an integer array (M,) of
+    labels 0..K-1 with K >= 2, every label used and at least 2 members outside every group."""
+    if spec is None:
+        return None
+    what = "cross_validation=%r" % (spec,)
+    if isinstance(spec, (bool, np.bool_)):
+        raise ValueError("%s must be an int K >= 2 or an integer array of M labels" % what)
+    if isinstance(spec, (int, np.integer)):
+        if spec < 2:
+            raise ValueError("%s: the number of groups must be >= 2" % what)
+        if spec > M:
+            raise ValueError("%s: more groups than the ensemble's %d members, a label would be unused" % (what, M))
+        g = np.arange(M, dtype=np.int64) % int(spec)
+    else:
+        try:
+            g = np.asarray(spec)
+        except Exception:
+            g = None
+        if g is None or g.ndim != 1 or g.dtype == np.bool_ or not np.issubdtype(g.dtype, np.integer):
+            raise ValueError("%s must be an int K >= 2 or an integer array of M labels" % what)
+        if g.shape[0] != M:
+            raise ValueError("cross_validation has %d labels, the ensemble %d members" % (g.shape[0], M))
+        g = g.astype(np.int64)
+    if g.size == 0 or g.min() < 0:
+        raise ValueError("cross_validation: the labels must be >= 0")
+    K = int(g.max()) + 1
+    size = np.bincount(g, minlength=K)
+    if K < 2:
+        raise ValueError("cross_validation: at least 2 groups are needed")
+    if np.any(size == 0):
+        raise ValueError("cross_validation: the label %d is unused (every label 0..%d must be)" % (int(np.flatnonzero(size == 0)[0]), K - 1))
+    if M - int(size.max()) < 2:
+        raise ValueError("cross_validation: group %d leaves %d members outside it (at least 2 are needed to form a gain)"
+                         % (int(np.argmax(size)), M - int(size.max())))
+    return g.astype(np.int32)
+
+
 def _check_control(state, ctrl):
     """ValueError unless `ctrl` is a one-member EnsembleState on the state's variables, coordinates and grid."""
     if not isinstance(ctrl, EnsembleState):
@@ -162,7 +210,10 @@ class LETKF(EnSRF):
         its M x M array in LDS).  control (None, or a one-member `EnsembleState` on the state's variables, coordinates and grid:
         the module's docstring): ValueError for anything else and for control with a weight_stride.  max_local_obs (None, an
         int >= 1 or {obtype: int >= 1} with at most 31 names: the module's docstring): ValueError for anything else, and under
-        `SlabLETKF` together with any of its three keywords.  `update_arrays` is not offered."""
+        `SlabLETKF` together with any of its three keywords.  cross_validation (None, an int K >= 2 or an integer array (M,) of
+        labels: the module's docstring): ValueError for anything else, for groups that break its rules, together with
+        column_inflation or control, and under `SlabLETKF` together with any of its three keywords.  `update_arrays` is not
+        offered."""
         stride = _weight_stride(kw.pop("weight_stride", None))
         cap = _max_local_obs(kw.pop("max_local_obs", None))
         if cap is not None:
@@ -182,6 +233,16 @@ class LETKF(EnSRF):
         ci = kw.pop("column_inflation", None)
         if ci is not None and not isinstance(ci, ColumnInflation):
             raise ValueError("column_inflation must be a ColumnInflation, got %r" % type(ci).__name__)
+        cv = _cross_validation(kw.pop("cross_validation", None), state.nmems())
+        if cv is not None:
+            for name, given in (("column_inflation", ci), ("control", ctrl)):
+                if given is not None:
+                    raise ValueError("%s: cross_validation and %s do not combine (out of scope, DESIGN.md 7y-9)"
+                                     % (type(self).__name__, name))
+            for name in self._served:
+                if kw.get(name) is not None and kw.get(name) is not False:
+                    raise ValueError("%s: cross_validation and %s do not combine: the sub-solves per (slab group, column) are out "
+                                     "of scope (DESIGN.md 7y-9)" % (type(self).__name__, name))
         loc = kw.pop("loc", "GC")
         if not (isinstance(loc, str) and loc == "GC"):
             raise ValueError("LETKF: loc=%r is not supported: the LETKF is the localised filter and takes loc='GC' only; "
@@ -202,6 +263,7 @@ class LETKF(EnSRF):
         self.control = ctrl
         self.last_control = None
         self.max_local_obs = cap
+        self.cross_validation = cv
 
     _cycle_line = "Beginning the column solves"
 
@@ -242,7 +304,16 @@ class LETKF(EnSRF):
                 raise ValueError("%s: max_local_obs does not combine with vertical / temporal / variable localisation "
                                  "(DESIGN.md 7y-8)" % type(self).__name__)
             ob_class, caps = _cap_classes(cap, self.obs)
+        cv = self.cross_validation
+        if cv is not None:
+            cv = _cross_validation(cv, M)
+            if slab or ci is not None or ctrl is not None:
+                raise ValueError("%s: cross_validation does not combine with vertical / temporal / variable localisation, "
+                                 "column_inflation or control (DESIGN.md 7y-9)" % type(self).__name__)
         try:
+            if cv is not None:
+                cv_stats = ctx.empty((sy * sx, 2))
+                ctx.set_letkf_cross_validation(cv, cv_stats)
             if cap is not None:
                 reach = ctx.empty((sy * sx,))
                 ctx.set_letkf_obs_cap(ob_class, caps, reach, P=P)
@@ -278,6 +349,8 @@ class LETKF(EnSRF):
                 ctx.set_letkf_control(None)
             if cap is not None:
                 ctx.set_letkf_obs_cap(None, None)
+            if cv is not None:
+                ctx.set_letkf_cross_validation(None)
         st = stats.download().reshape(ng, sy, sx, 3)
         if not slab:                            # the plain filter documents (ny, nx) / (nyn, nxn)
             st = st[0]
@@ -288,6 +361,9 @@ class LETKF(EnSRF):
             self.last_solve.update(node_y=node_y, node_x=node_x)
         if cap is not None:
             self.last_solve.update(n_reach=reach.download().reshape(sy, sx).astype(np.int64))
+        if cv is not None:
+            cvs = cv_stats.download().reshape(sy, sx, 2)
+            self.last_solve.update(cv_sweeps=cvs[..., 0].astype(np.int64), cv_cond=cvs[..., 1].copy())
         if ci is not None:
             ci.values = lam_dev.download().reshape(lam_shape)       # the next update's prior factors
             self.last_solve.update(inflation=lam_b, inflation_post=ci.values.copy(),

@@ -394,6 +394,51 @@ int efa_ctx_set_letkf_obs_cap(efa_ctx* c, const int* ob_class, long P, const lon
   return EFA_OK;
 }
 
+int efa_ctx_set_letkf_cross_validation(efa_ctx* c, const int* group_of_member, int M, int ngroups, double* cv_stats_dev, long nsolve) {
+  EFA_TRY(use(c));
+  if (!group_of_member) {
+    c->cv_on = false;
+    c->cv_M = c->cv_ngroups = 0;
+    c->cv_stats = nullptr;
+    c->cv_nsolve = 0;
+    return EFA_OK;
+  }
+  if (M < 4 || M > efa::kLetkfMaxM)
+    return fail(EFA_ERR_INVALID, "LETKF cross validation: M=%d must be within 4..%d (two groups of two members at least; the LETKF's range)", M,
+                efa::kLetkfMaxM);
+  if (ngroups < 2) return fail(EFA_ERR_INVALID, "LETKF cross validation: ngroups=%d must be >= 2", ngroups);
+  if (nsolve < 0) return fail(EFA_ERR_INVALID, "LETKF cross validation: negative count (nsolve=%ld)", nsolve);
+  std::vector<int> size((size_t)ngroups, 0);
+  for (int m = 0; m < M; ++m) {
+    if (group_of_member[m] < 0 || group_of_member[m] >= ngroups)
+      return fail(EFA_ERR_INVALID, "LETKF cross validation: member %d has the label %d, outside 0..%d", m, group_of_member[m], ngroups - 1);
+    size[group_of_member[m]]++;
+  }
+  for (int k = 0; k < ngroups; ++k) {
+    if (size[k] == 0) return fail(EFA_ERR_INVALID, "LETKF cross validation: the label %d is unused (every label 0..%d must be)", k, ngroups - 1);
+    if (M - size[k] < 2)
+      return fail(EFA_ERR_INVALID, "LETKF cross validation: group %d leaves an independent set of %d members (at least 2 are needed)", k,
+                  M - size[k]);
+  }
+  if ((reinterpret_cast<uintptr_t>(cv_stats_dev) & 7u) != 0)
+    return fail(EFA_ERR_INVALID, "LETKF cross validation: cv_stats_dev must be 8-byte aligned");
+  // per group: the independent members ascending, then its own; and the independent set's size
+  std::vector<int> h((size_t)ngroups * M + ngroups);
+  for (int k = 0; k < ngroups; ++k) {
+    int ni = 0, nh = M - size[k];
+    for (int m = 0; m < M; ++m) h[(size_t)k * M + (group_of_member[m] != k ? ni++ : nh++)] = m;
+    h[(size_t)ngroups * M + k] = M - size[k];
+  }
+  EFA_TRY(h2d(c, c->cv_lists, h.data(), h.size() * sizeof(int)));
+  EFA_HIP(hipStreamSynchronize(c->stream));  // (h goes out of scope)
+  c->cv_on = true;
+  c->cv_M = M;
+  c->cv_ngroups = ngroups;
+  c->cv_stats = cv_stats_dev;
+  c->cv_nsolve = cv_stats_dev ? nsolve : 0;
+  return EFA_OK;
+}
+
 int efa_ctx_set_vertical_localization(efa_ctx* c, long n_lead, const double* lead_vert, long P, const double* ob_vert,
                                       const double* ob_vert_halfwidth) {
   EFA_TRY(use(c));

@@ -333,6 +333,14 @@ struct efa_ctx {
   DevBuf oc_class;                   // [P] ints, the class of every ob
   double* oc_reach = nullptr;        // [nsolve] the caller's device array, or null
   long oc_nsolve = 0;
+  // --- the LETKF's cross validation over member groups (efa_ctx_set_letkf_cross_validation)
+  bool cv_on = false;
+  int cv_M = 0, cv_ngroups = 0;
+  DevBuf cv_lists;                   // ints: perm [ngroups][M] (per group: the other groups' members ascending, then its own) | nind [ngroups]
+  double* cv_stats = nullptr;        // [nsolve][2] the caller's device array, or null
+  long cv_nsolve = 0;
+  DevBuf cv_C;                       // the Gram matrix C of every solve point of a launch [npts][M][M] (the sub-solves re-read it)
+  DevBuf cv_Tw;                      // the obs block's pairs [P][M][M+1]
   // --- the LETKF's slab groups (efa_letkf_slab_cycle_dev): slabs whose factors agree for every ob share one solve
   std::vector<int> lg_group_of;                   // [n_lead] the group of every slab, numbered by first appearance
   int lg_ngroups = 0;

@@ -203,6 +203,10 @@ int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const double* ym_dev, co
 // with a mesh, and by letkf_weights, the call is refused while it is set; letkf_interp_apply ignores it)
 // (the context's obs cap, efa_ctx_set_letkf_obs_cap, DESIGN.md §7y-8: served by the plain and the interp cycle and by letkf_weights,
 // sized for this call's P and solve points; the slab calls are refused while it is set; letkf_interp_apply ignores it)
+// (the context's cross validation, efa_ctx_set_letkf_cross_validation, DESIGN.md §7y-9: served by the plain and the interp cycle and by
+// letkf_weights, sized for this call's M and solve points, without an inflation field and without a control; the state then always
+// goes "solve the points, apply their pairs", without a mesh on the unit mesh; the slab calls are refused while it is set;
+// letkf_interp_apply ignores it)
 // efa_letkf_interp_apply_dev / _f32_dev: that kernel alone on caller-given node pairs, under the context's relaxation; waits
 int letkf_interp_apply(efa_ctx* c, const StateRows& r, const efa::LetkfMesh& mesh, long n_lead, const double* Tw_nodes_dev,
                        const double* node_stats_dev);

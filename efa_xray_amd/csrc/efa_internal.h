@@ -482,6 +482,19 @@ struct LetkfGroups {
 // [ngroups][npts][M][M + 1].  kLetkfMembers and kLetkfWeights only (the obs block runs the plain kLetkfPerts launch on lists that
 // launch_letkf_obs_factor scaled).
 hipError_t launch_letkf(const LetkfArgs& a, const LetkfGroups* grp, int mode, Elem elem, hipStream_t s);
+// ---- cross validation over member groups (Buehner 2020): the perturbations of a group are updated with the gain of the
+// other groups' members; the mean keeps the full solve
+struct LetkfCv {
+  int ngroups;        // K >= 2
+  const int* perm;    // [K][M] per group k: the members with another label ascending (the independent set I), then those with label k (H)
+  const int* nind;    // [K] |I| >= 2 of every group
+  double* C;          // [npts][M][M] scratch: the Gram matrix C of every point, written and re-read by the point's own workgroup
+  double* stats;      // [npts][2] {the sub-solves' sweeps summed, their largest max mu / min mu} or null
+};
+// k_letkf_cv: kLetkfWeights under cross validation, a.Tw [npts][M][M + 1] = the recentred T | w of every point (T is not symmetric:
+// row a holds what member a's prior perturbation contributes to every posterior one); a.stats as launch_letkf writes them.  With
+// a.Yp_in (and ym_in, ym_out, Yp_out, clear of the inputs) point j's row of the obs block is mapped by its own pair as well.
+hipError_t launch_letkf_cv(const LetkfArgs& a, const LetkfCv& cv, hipStream_t s);
 // k_letkf_interp: one workgroup per column; a.Xin / a.Xout are rows of `elem`.  grp (the SLAB switch): one per (column, group), node
 // pairs Tw [ngroups][nnodes][M][M + 1] and node statistics [ngroups][nnodes][3]; the table and rep are not read.
 hipError_t launch_letkf_interp(const LetkfInterpArgs& a, const LetkfGroups* grp, Elem elem, hipStream_t s);

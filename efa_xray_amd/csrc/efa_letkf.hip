@@ -44,6 +44,14 @@
 // The cap on the local obs of a solve (efa_ctx_set_letkf_obs_cap): k_letkf_cap runs between the list build and
 // the solve and zeroes, per point and class, the tapers of all but the cap[c] largest; a zero taper is "not listed" to every kernel
 // above (the select of the Gram, the n_local loop, p3), so none of them changes.
+// Cross validation over member groups (Buehner 2020; efa_ctx_set_letkf_cross_validation): k_letkf_cv is the weights
+// mode with the switch CV.  The Gram also parks C in the point's M x M block of a context-owned global scratch, the mean's solve runs as
+// above and leaves w, and then per group k (I: the members of the other groups, H: its own, m = |I|, a = m - 1, J = I - 11^T/m)
+// J C[I,I] J + a I goes into the LDS array, etkf_jacobi runs on it, and T[I,H] = -J V diag(1/(mu (1 + sqrt(a/mu)))) V^T J C[I,H] and
+// the identity block T[H,H] go to the point's [M][M+1] pair in global memory; one pass takes the row means off T; with Yp_in the
+// point's row of the obs block is mapped by its own pair.  The state is applied by k_letkf_interp (efa_letkf_interp.hip), without a
+// mesh on the unit mesh whose nodes are the columns.  The body of k_letkf and k_letkf_cv is one text, efa_letkf_point.inc: with CV off
+// it is k_letkf as it was, instruction for instruction.
 // This file holds the kernels and their launchers only.
 #include "efa_driver.h"
 #include "efa_device.h"
@@ -184,372 +192,190 @@ __device__ __forceinline__ void letkf_inflation_estimate(size_t pt, int M, const
 // without it are today's instruction for instruction; with it the Gram carries one more B-operand column (g^c), h^c = (V_j . g^c)/mu_j
 // goes over n_s behind the sweeps, and the row's wave adds h^c . z to the control's value of its row.  Nothing of the ensemble's
 // arithmetic changes: the tiles are independent accumulators, and every reduction keeps its order whatever the tile side is.
+//
+// CV: the cross-validated perturbation update (Buehner 2020) of kLetkfWeights, k_letkf_cv's switch.  The body of
+// both kernels is one text, efa_letkf_point.inc: with CV off it is k_letkf instruction for instruction (a kernel of another name,
+// because the instantiations of k_letkf are counted and named by the tests).  With it the Gram also parks C in the point's M x M
+// block of the context's scratch (global, re-read through L2), the mean's solve runs as it is and leaves w, and letkf_cv_transform
+// forms T group by group from C.
+struct LetkfCvArgs : LetkfArgs {
+  LetkfCv cv;
+};
+
+// The cross-validated T of one point, by the whole workgroup, behind the mean's solve: every LDS vector but the
+// M x M array G is free.  Per group k, from the lists the host made (perm[k] = I ascending | H ascending, nind[k] = |I| = m):
+//   B = J C[I,I] J + (m-1) I into G (pitch m) from the row means of C[I,I], etkf_jacobi on it, V and mu, d_j = 1/(mu_j (1 + sqrt(a/mu_j)));
+//   four held-out members at a time, as k_letkf's apply takes four rows: x = J C[I,h], z = d . (V^T x), t = V z, T[I,h] = -(t - mean(t)),
+//   T[H,h] = the identity's column.
+// Then one pass per row of T: its sum over 16 lanes in a fixed order, the mean taken off.  With Yp_in the point's one row of the obs
+// block is mapped by its own [T | w] at the end.  No atomics; C and T are written and re-read by this workgroup only.
+template <typename A>
+__device__ __forceinline__ void letkf_cv_transform(const A& a, int M, long col, double* G, double* il_s, double* rb_s, double* d_s,
+                                                   double* n_s, double* mu_s, double* x_s, double* z_s, double* mean_s, int* rot_s,
+                                                   int tid, int nth) {
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nslots = nth >> 4, slot = tid >> 4, sl = tid & 15;
+  const double* Cg = a.cv.C + (size_t)col * M * M;
+  double* tw = a.Tw + (size_t)col * M * (M + 1);
+  int* il = reinterpret_cast<int*>(il_s);  // [M] the group's I, then its H
+  int swsum = 0;
+  double cmax = 0.0;  // (wave 0)
+#pragma unroll 1
+  for (int k = 0; k < a.cv.ngroups; ++k) {
+    const int m = a.cv.nind[k], nh = M - m;
+    const double am = (double)(m - 1);
+    __syncthreads();  // the previous group's lists, vectors and G are consumed
+    for (int e = tid; e < M; e += nth) il[e] = a.cv.perm[(size_t)k * M + e];
+    __syncthreads();
+    // the row means of C[I,I], then their mean
+#pragma unroll 1
+    for (int i = slot; i < m; i += nslots) {
+      const double* cr = Cg + (size_t)il[i] * M;
+      double s = 0.0;
+      for (int j = sl; j < m; j += 16) s += cr[il[j]];
+      s = group_sum<16>(s);
+      if (sl == 0) rb_s[i] = s / (double)m;
+    }
+    __syncthreads();
+    if (wave == 0) {
+      double s = 0.0;
+      for (int i = lane; i < m; i += 64) s += rb_s[i];
+      s = wave_sum(s);
+      if (lane == 0) mean_s[0] = s / (double)m;
+    }
+    __syncthreads();
+    const double cbar = mean_s[0];
+    for (int e = tid; e < m * m; e += nth) {  // (rb_i + rb_j commutes: B is symmetric to the bit, as C is)
+      const int i = e / m, j = e - i * m;
+      const double v = (Cg[(size_t)il[i] * M + il[j]] - (rb_s[i] + rb_s[j])) + cbar;
+      G[e] = (i == j) ? v + am : v;
+    }
+    __syncthreads();
+    swsum += etkf_jacobi(m, G, n_s, rot_s, tid, nth);
+#pragma unroll 1
+    for (int j = slot; j < m; j += nslots) {  // V in place, mu, d
+      double* cj = G + (size_t)j * m;
+      double al = 0.0;
+      for (int i = sl; i < m; i += 16) al = fma(cj[i], cj[i], al);
+      al = group_sum<16>(al);
+      const double mu = sqrt(al);
+      for (int i = sl; i < m; i += 16) cj[i] = cj[i] / mu;
+      if (sl == 0) {
+        mu_s[j] = mu;
+        d_s[j] = 1.0 / (mu * (1.0 + sqrt(am / mu)));
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {  // the sub-solve's condition number
+      double hi = 0.0, lo = __builtin_inf();
+      for (int j = lane; j < m; j += 64) {
+        hi = fmax(hi, mu_s[j]);
+        lo = fmin(lo, mu_s[j]);
+      }
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) {
+        hi = fmax(hi, __shfl_xor(hi, o, 64));
+        lo = fmin(lo, __shfl_xor(lo, o, 64));
+      }
+      cmax = fmax(cmax, hi / lo);
+    }
+#pragma unroll 1
+    for (int h0 = 0; h0 < nh; h0 += kLetkfRows) {
+      const int nr = (nh - h0 < kLetkfRows) ? nh - h0 : kLetkfRows;
+      for (int e = tid; e < nr * m; e += nth) {
+        const int r = e / m, i = e - r * m;
+        x_s[e] = Cg[(size_t)il[i] * M + il[m + h0 + r]];
+      }
+      __syncthreads();
+      if (wave < nr) {  // x = J C[I,h]
+        double* xr = x_s + wave * m;
+        double s = 0.0;
+        for (int i = lane; i < m; i += 64) s += xr[i];
+        const double mean = wave_sum(s) / (double)m;
+        for (int i = lane; i < m; i += 64) xr[i] -= mean;
+      }
+      __syncthreads();
+#pragma unroll 1
+      for (int pr = slot; pr < nr * m; pr += nslots) {  // z[r][j] = d_j (V_j . x_r)
+        const int r = pr / m, j = pr - r * m;
+        const double* cj = G + (size_t)j * m;
+        const double* xr = x_s + r * m;
+        double d = 0.0;
+        for (int i = sl; i < m; i += 16) d = fma(cj[i], xr[i], d);
+        d = group_sum<16>(d);
+        if (sl == 0) z_s[pr] = d_s[j] * d;
+      }
+      __syncthreads();
+      for (int e = tid; e < nr * m; e += nth) {  // t[r][b] = sum_j z[r][j] V[b][j]
+        const int r = e / m, b = e - r * m;
+        const double* zr = z_s + r * m;
+        double acc = 0.0;
+        for (int j = 0; j < m; ++j) acc = fma(zr[j], G[(size_t)j * m + b], acc);
+        x_s[e] = acc;
+      }
+      __syncthreads();
+      if (wave < nr) {
+        const double* tr = x_s + wave * m;
+        const int hc = il[m + h0 + wave];
+        double s = 0.0;
+        for (int i = lane; i < m; i += 64) s += tr[i];
+        const double mean = wave_sum(s) / (double)m;
+        for (int i = lane; i < m; i += 64) tw[(size_t)il[i] * (M + 1) + hc] = mean - tr[i];
+        for (int q = lane; q < nh; q += 64) tw[(size_t)il[m + q] * (M + 1) + hc] = (il[m + q] == hc) ? 1.0 : 0.0;
+      }
+      __syncthreads();  // the batch is stored: the next one takes x_s
+    }
+  }
+  __syncthreads();  // every column of T is written (by this workgroup: visible behind the barrier)
+#pragma unroll 1
+  for (int r = slot; r < M; r += nslots) {  // recentre: the row's mean off its entries
+    double* row = tw + (size_t)r * (M + 1);
+    double s = 0.0;
+    for (int b = sl; b < M; b += 16) s += row[b];
+    const double mean = group_sum<16>(s) / (double)M;
+    for (int b = sl; b < M; b += 16) row[b] -= mean;
+  }
+  if (a.cv.stats && tid == 0) {
+    a.cv.stats[2 * col] = (double)swsum;
+    a.cv.stats[2 * col + 1] = cmax;
+  }
+  if (a.Yp_in) {  // (uniform) the obs block: the point's own row through its own pair, column M of which is w
+    for (int m2 = tid; m2 < M; m2 += nth) x_s[m2] = a.Yp_in[(size_t)col * M + m2];
+    __syncthreads();
+    for (int b = tid; b <= M; b += nth) {
+      double acc = 0.0;
+      for (int r = 0; r < M; ++r) acc = fma(x_s[r], tw[(size_t)r * (M + 1) + b], acc);
+      if (b < M) a.Yp_out[(size_t)col * M + b] = acc;
+      else a.ym_out[col] = a.ym_in[col] + acc;
+    }
+  }
+}
+
 template <int MODE, typename E, int NTMAX, bool SLAB = false, bool CTRL = false>
 __global__ __launch_bounds__(NTMAX) void k_letkf(const typename LetkfArgsOf<SLAB>::type a) {
-  static_assert(!CTRL || MODE != kLetkfWeights, "the pair layout [M][M+1] has no place for w^c");
-  extern __shared__ __align__(16) double letkf_smem[];
-  const int M = a.M;
-  const int tid = (int)threadIdx.x, nth = (int)blockDim.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nW = nth >> 6;
-  const int T = letkf_tiles_side(M, CTRL), Sp = letkf_stage_pitch(M, CTRL), ntiles = T * (T + 1) / 2;
-  double* G = letkf_smem;                     // the M x M array; before it the stage [32][Sp] | weights [32]
-  double* wgt = G + kLetkfChunk * Sp;
-  double* g_s = G + letkf_region(M, CTRL);
-  double* f_s = g_s + M;
-  double* h_s = f_s + M;
-  double* n_s = h_s + M;
-  double* mu_s = n_s + M;
-  double* x_s = mu_s + M;                     // [4][M] rows of a batch: members, perturbations, then posterior perturbations
-  double* z_s = x_s + kLetkfRows * M;         // [4][M] V^T x'
-  double* mean_s = z_s + kLetkfRows * M;
-  double* xam_s = mean_s + kLetkfRows;
-  double* ssb_s = xam_s + kLetkfRows;
-  double* infl_s = ssb_s + kLetkfRows;         // inflation (§7y-6): lambda_b | p3 | p1 | trace(C)
-  int* rot_s = reinterpret_cast<int*>(mean_s + kLetkfSmall);
-  int* nloc_s = rot_s + 2;
-  double* gc_s = mean_s + kLetkfSmall + 2;    // CTRL: g^c [M] behind the ints (16-byte aligned); h^c takes n_s behind the sweeps
+  constexpr bool CV = false;
+#include "efa_letkf_point.inc"
+}
 
-  long bid = (long)blockIdx.x, grp = 0, lead0 = 0, nlead_g = a.n_lead;  // the group, its first entry in grp_leads, its slabs
-  const double* Sg = nullptr;                                            // S[.][rep[grp]], pitch sp
-  long sp = 0;
-  const int* leads = nullptr;
-  if constexpr (SLAB) {
-    grp = bid % a.grp.ngroups;
-    bid = bid / a.grp.ngroups;
-    lead0 = a.grp.grp_off[grp];
-    nlead_g = a.grp.grp_off[grp + 1] - lead0;
-    sp = a.grp.s_pitch;
-    Sg = a.grp.S + a.grp.rep[grp];
-    leads = a.grp.grp_leads + lead0;
-  }
-  const long bi = bid >> 4;
-  const int cb = (int)(bid & 15);
-  const long blk = a.order ? (long)a.order[bi] : bi;
-  const long col = blk * 16 + cb;
-  if (col >= a.npts) return;  // (uniform)
-  const long off = a.off ? a.off[blk] : 0;
-  const int n = a.cnt ? a.cnt[blk] : 0;
+// the solve points under cross validation: [T | w] of every point to Tw, with Yp_in the obs block's rows as well
+// (A is LetkfCvArgs: a template parameter so that the body's SLAB and CTRL branches, which name members it lacks, stay dependent)
+template <int NTMAX, typename A>
+__global__ __launch_bounds__(NTMAX) void k_letkf_cv(const A a) {
+  constexpr int MODE = kLetkfWeights;
+  constexpr bool SLAB = false, CTRL = false, CV = true;
+  typedef double E;
+#include "efa_letkf_point.inc"
+}
 
-  // n_local: the listed obs whose taper on THIS column is not zero; under inflation p3, the sum of those tapers (each lane its
-  // entries in list order, then the butterfly)
-  const bool infl = a.infl != nullptr;  // (uniform)
-  if (wave == 0) {
-    int cl = 0;
-    double p3 = 0.0;
-    for (int e = lane; e < n; e += 64) {
-      double w = a.wts[(size_t)(off + e) * 16 + cb];
-      if constexpr (SLAB) w = w * Sg[(size_t)a.idx[off + e] * sp];
-      cl += (w != 0.0) ? 1 : 0;
-      if (infl && w != 0.0) p3 += w;
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) cl += __shfl_xor(cl, o, 64);
-    if (infl) p3 = wave_sum(p3);
-    if (lane == 0) {
-      *nloc_s = cl;
-      infl_s[0] = infl ? a.infl[grp * a.npts + col] : 1.0;
-      infl_s[1] = p3;
-    }
+template <int NTMAX>
+hipError_t letkf_cv_launch_as(const LetkfCvArgs& a, int nth, size_t lds, hipStream_t s) {
+  auto kern = k_letkf_cv<NTMAX, LetkfCvArgs>;
+  if (lds > 48 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
   }
-  __syncthreads();
-  const int nloc = *nloc_s;
-
-  if (nloc == 0) {  // (uniform) no ob reaches the column: A = (M-1) I, no rotation, T = I, w = 0 -- the rows keep their bits
-    if (MODE == kLetkfMembers) {
-      const E* in = static_cast<const E*>(a.Xin);
-      E* out = static_cast<E*>(a.Xout);
-      if (in != out)
-        for (long li = 0; li < nlead_g; ++li) {
-          long l = li;
-          if constexpr (SLAB) l = leads[li];
-          const size_t base = (size_t)(l * a.npts + col) * M;
-          for (int m = tid; m < M; m += nth) out[base + m] = in[base + m];
-        }
-      if constexpr (CTRL) {  // the control's rows likewise: copied bit for bit, or left alone in place
-        const double* cin = letkf_kernarg()->ctl_in;
-        double* cout = letkf_kernarg()->ctl_out;
-        if (cin != cout)
-          for (long li = tid; li < nlead_g; li += nth) {
-            long l = li;
-            if constexpr (SLAB) l = leads[li];
-            cout[l * a.npts + col] = cin[l * a.npts + col];
-          }
-      }
-    } else if (MODE == kLetkfPerts) {
-      for (int m = tid; m < M; m += nth) a.Yp_out[(size_t)col * M + m] = a.Yp_in[(size_t)col * M + m];
-      if (tid == 0) a.ym_out[col] = a.ym_in[col];
-      if constexpr (CTRL) {
-        if (tid == 0) letkf_kernarg()->ctl_out[col] = letkf_kernarg()->ctl_in[col];
-      }
-    } else {
-      double* tw = a.Tw + (size_t)(grp * a.npts + col) * M * (M + 1);
-      for (int e = tid; e < M * (M + 1); e += nth) {
-        const int r = e / (M + 1), c = e - r * (M + 1);
-        tw[e] = (r == c) ? 1.0 : 0.0;
-      }
-    }
-    if (a.stats && tid < 3) a.stats[3 * (grp * a.npts + col) + tid] = 0.0;
-    if (infl && a.infl_stats && tid < 4) a.infl_stats[4 * (grp * a.npts + col) + tid] = (tid < 3) ? 0.0 : __builtin_nan("");  // lambda keeps its bits
-    return;
-  }
-
-  // ---- 1. Gram ----------------------------------------------------------------------------------------------------------------
-  {
-    const int g = lane >> 4, nn = lane & 15;
-    int ca[kLetkfTiles], cbt[kLetkfTiles];
-    letkf_v4 acc[kLetkfTiles];
-#pragma unroll
-    for (int t = 0; t < kLetkfTiles; ++t) {
-      const int ti = wave + t * nW;
-      int ta = 0, tb = 0;
-      if (ti < ntiles) letkf_tile(ti, T, &ta, &tb);
-      ca[t] = 16 * ta + nn;
-      cbt[t] = 16 * tb + nn;
-      acc[t] = letkf_v4{0.0, 0.0, 0.0, 0.0};
-    }
-    const int nchunks = (n + kLetkfChunk - 1) / kLetkfChunk;
-#pragma unroll 1
-    for (int ch = 0; ch < nchunks; ++ch) {
-      __syncthreads();  // the previous chunk is consumed
-      for (int e = tid; e < kLetkfChunk * Sp; e += nth) {
-        const int r = e / Sp, c = e - r * Sp;
-        const int en = ch * kLetkfChunk + r;
-        double v = 0.0;
-        if (en < n && c <= M + (CTRL ? 1 : 0)) {
-          const long k = a.idx[off + en];
-          if constexpr (CTRL) v = (c < M) ? a.Yp[(size_t)k * M + c] : (c == M) ? a.dr[2 * k] : letkf_kernarg()->dc[k];
-          else v = (c < M) ? a.Yp[(size_t)k * M + c] : a.dr[2 * k];
-        }
-        G[e] = v;
-      }
-      if (tid < kLetkfChunk) {
-        const int en = ch * kLetkfChunk + tid;
-        double w = 0.0;
-        if (en < n) {
-          const long k = a.idx[off + en];
-          w = a.wts[(size_t)(off + en) * 16 + cb];
-          if constexpr (SLAB) w = w * Sg[(size_t)k * sp];
-          w = w / a.dr[2 * k + 1];
-        }
-        wgt[tid] = w;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int t = 0; t < kLetkfTiles; ++t) {
-        if (wave + t * nW < ntiles) {  // (wave-uniform)
-#pragma unroll
-          for (int k = 0; k < kLetkfChunk / 4; ++k) {
-            const int row = 4 * k + g;
-            const double wv = wgt[row];
-            const double ya = G[row * Sp + ca[t]], yb = G[row * Sp + cbt[t]];
-            const double oa = (wv != 0.0) ? wv * ya : 0.0;  // a zero weight: exact zeros, whatever the row holds
-            const double ob = (wv != 0.0) ? yb : 0.0;
-            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(oa, ob, acc[t], 0, 0, 0);
-          }
-        }
-      }
-    }
-    __syncthreads();  // the stage is consumed: A goes over it
-    const double shift = (double)(M - 1) / infl_s[0];  // the diagonal of A; (M-1)/1.0 is exact: no field, the bits without one
-#pragma unroll
-    for (int t = 0; t < kLetkfTiles; ++t) {
-      const int ti = wave + t * nW;
-      if (ti < ntiles) {
-        int ta, tb;
-        letkf_tile(ti, T, &ta, &tb);
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          const int i = g + 4 * v, j = nn;
-          const int I = 16 * ta + i, J = 16 * tb + j;
-          if (ta == tb && i > j) continue;  // a diagonal tile holds each pair twice: the upper one is mirrored
-          const double s = acc[t][v];
-          if (I < M && J < M) {
-            const double val = (I == J) ? s + shift : s;
-            G[I * M + J] = val;
-            G[J * M + I] = val;
-            if (infl && I == J) n_s[I] = s;  // the diagonal of C, for its trace (n_s is free until the sweeps)
-          } else if (I < M && J == M) {
-            g_s[I] = s;
-          } else if (CTRL && I < M && J == M + 1) {
-            gc_s[I] = s;  // g^c; entries (M, M+1) and (M+1, M+1) are dropped
-          } else if (infl && I == M && J == M) {
-            infl_s[2] = s;  // p1 = sum_k w_k d_k^2
-          }
-        }
-      }
-    }
-    __syncthreads();
-    if (infl) {  // (uniform) trace(C) in a fixed order before the sweeps take n_s
-      if (wave == 0) {
-        double tr = 0.0;
-        for (int j = lane; j < M; j += 64) tr += n_s[j];
-        tr = wave_sum(tr);
-        if (lane == 0) infl_s[3] = tr;
-      }
-      __syncthreads();
-    }
-  }
-
-  // ---- 2. eigen-solve ---------------------------------------------------------------------------------------------------------
-  const int sweeps = etkf_jacobi(M, G, n_s, rot_s, tid, nth);
-  etkf_factors(M, G, g_s, mu_s, f_s, h_s, tid, nth);
-  if constexpr (CTRL) {  // h^c_j = (V_j . g^c) / mu_j over n_s, which the sweeps have left; read behind the apply's first barrier
-    const int nslots_c = nth >> 4, slot_c = tid >> 4, sl_c = tid & 15;
-#pragma unroll 1
-    for (int j = slot_c; j < M; j += nslots_c) {
-      const double* cj = G + (size_t)j * M;
-      double hg = 0.0;
-      for (int i = sl_c; i < M; i += 16) hg = fma(cj[i], gc_s[i], hg);
-      hg = group_sum<16>(hg);
-      if (sl_c == 0) n_s[j] = hg / mu_s[j];
-    }
-  }
-  if (a.stats && wave == 0) {
-    const double shift = (double)(M - 1) / infl_s[0];
-    double s = 0.0;
-    for (int j = lane; j < M; j += 64) s += (mu_s[j] - shift) / mu_s[j];
-    s = wave_sum(s);
-    if (lane == 0) {
-      a.stats[3 * (grp * a.npts + col)] = (double)nloc;
-      a.stats[3 * (grp * a.npts + col) + 1] = s;
-      a.stats[3 * (grp * a.npts + col) + 2] = (double)sweeps;
-    }
-  }
-
-  // ---- 3. [T | w], factored ---------------------------------------------------------------------------------------------------
-  if (MODE == kLetkfWeights) {
-    double* tw = a.Tw + (size_t)(grp * a.npts + col) * M * (M + 1);
-    etkf_assemble(M, G, f_s, h_s, tw, (size_t)(M + 1), tw + M, (size_t)(M + 1), tid, nth);
-    if (infl && tid == 0) letkf_inflation_estimate((size_t)(grp * a.npts + col), M, infl_s);
-    return;
-  }
-  const bool rtps = MODE == kLetkfMembers && a.relax_kind == EFA_RELAX_RTPS && a.relax_alpha != 0.0;
-  if (MODE == kLetkfMembers && a.relax_kind == EFA_RELAX_RTPP && a.relax_alpha != 0.0) {  // (uniform)
-    for (int j = tid; j < M; j += nth) f_s[j] = (1.0 - a.relax_alpha) * f_s[j] + a.relax_alpha;
-    __syncthreads();
-  }
-
-  // ---- 4. apply ---------------------------------------------------------------------------------------------------------------
-  const int nslots = nth >> 4, slot = tid >> 4, sl = tid & 15;
-  const long nrows = (MODE == kLetkfMembers) ? nlead_g : 1;
-#pragma unroll 1
-  for (long r0 = 0; r0 < nrows; r0 += kLetkfRows) {
-    const int nr = (int)((nrows - r0 < kLetkfRows) ? nrows - r0 : kLetkfRows);
-    for (int e = tid; e < nr * M; e += nth) {
-      const int r = e / M, m = e - r * M;
-      if (MODE == kLetkfMembers) {
-        long l = r0 + r;
-        if constexpr (SLAB) l = leads[l];
-        x_s[e] = (double)static_cast<const E*>(a.Xin)[(size_t)(l * a.npts + col) * M + m];
-      }
-      else x_s[e] = a.Yp_in[(size_t)col * M + m];
-    }
-    __syncthreads();
-    if (wave < nr) {  // the row's mean, its perturbations in place, the prior spread
-      double* xr = x_s + wave * M;
-      if (MODE == kLetkfMembers) {
-        double s = 0.0;
-        for (int m = lane; m < M; m += 64) s += xr[m];
-        const double mean = wave_sum(s) / (double)M;
-        double q = 0.0;
-        for (int m = lane; m < M; m += 64) {
-          const double p = xr[m] - mean;
-          xr[m] = p;
-          q = fma(p, p, q);
-        }
-        q = wave_sum(q);
-        if (lane == 0) {
-          mean_s[wave] = mean;
-          ssb_s[wave] = q;
-        }
-      } else if (lane == 0) {
-        mean_s[wave] = a.ym_in[col];
-      }
-    }
-    __syncthreads();
-    // z[r][j] = V_j . x'_r
-#pragma unroll 1
-    for (int pr = slot; pr < nr * M; pr += nslots) {
-      const int r = pr / M, j = pr - r * M;
-      const double* cj = G + (size_t)j * M;
-      const double* xr = x_s + r * M;
-      double d = 0.0;
-      for (int i = sl; i < M; i += 16) d = fma(cj[i], xr[i], d);
-      d = group_sum<16>(d);
-      if (sl == 0) z_s[pr] = d;
-    }
-    __syncthreads();
-    if (wave < nr) {  // xam = mean + x' w = mean + h . z
-      const double* zr = z_s + wave * M;
-      double s = 0.0;
-      if constexpr (CTRL) {  // x_c^a = x_c + x' . w^c = x_c + h^c . z, by the wave that owns the row
-        double sc = 0.0;
-        for (int j = lane; j < M; j += 64) {
-          s = fma(h_s[j], zr[j], s);
-          sc = fma(n_s[j], zr[j], sc);
-        }
-        s = wave_sum(s);
-        sc = wave_sum(sc);
-        if (lane == 0) {
-          xam_s[wave] = mean_s[wave] + s;
-          long row = col;
-          if (MODE == kLetkfMembers) {
-            long l = r0 + wave;
-            if constexpr (SLAB) l = leads[l];
-            row = l * a.npts + col;
-          }
-          letkf_kernarg()->ctl_out[row] = letkf_kernarg()->ctl_in[row] + sc;  // (the pointers from the argument block, here)
-        }
-      } else {
-        for (int j = lane; j < M; j += 64) s = fma(h_s[j], zr[j], s);
-        s = wave_sum(s);
-        if (lane == 0) xam_s[wave] = mean_s[wave] + s;
-      }
-    }
-    // x'_a[r][b] = sum_j (f_j z[r][j]) V[b][j], over the prior perturbations (z holds all that is needed of them)
-    for (int e = tid; e < nr * M; e += nth) {
-      const int r = e / M, b = e - r * M;
-      const double* zr = z_s + r * M;
-      double acc = 0.0;
-      for (int j = 0; j < M; ++j) acc = fma(f_s[j] * zr[j], G[(size_t)j * M + b], acc);
-      x_s[e] = acc;
-    }
-    __syncthreads();
-    if (wave < nr) {
-      const double* pa = x_s + wave * M;
-      const double xam = xam_s[wave];
-      if (MODE == kLetkfMembers) {
-        long l = r0 + wave;
-        if constexpr (SLAB) l = leads[l];
-        E* out = static_cast<E*>(a.Xout) + (size_t)(l * a.npts + col) * M;
-        if (rtps) {  // the posterior members' own mean and spread, as the standalone pass takes them (§7b)
-          double s = 0.0;
-          for (int m = lane; m < M; m += 64) s += pa[m];
-          const double pm = wave_sum(s) / (double)M;
-          double q = 0.0;
-          for (int m = lane; m < M; m += 64) {
-            const double dv = pa[m] - pm;
-            q = fma(dv, dv, q);
-          }
-          q = wave_sum(q);
-          if (q > 0.0) {  // (wave-uniform) sigma_a == 0: the row stays as it is
-            const double sc = (1.0 - a.relax_alpha) + a.relax_alpha * sqrt(ssb_s[wave] / q);
-            const double base = xam + pm;
-            for (int m = lane; m < M; m += 64) out[m] = letkf_round<E>(base + sc * (pa[m] - pm));
-          } else {
-            for (int m = lane; m < M; m += 64) out[m] = letkf_round<E>(xam + pa[m]);
-          }
-        } else {
-          for (int m = lane; m < M; m += 64) out[m] = letkf_round<E>(xam + pa[m]);
-        }
-      } else {
-        for (int m = lane; m < M; m += 64) a.Yp_out[(size_t)col * M + m] = pa[m];
-        if (lane == 0) a.ym_out[col] = xam;
-      }
-    }
-    __syncthreads();  // the batch's rows are stored: the next batch takes x_s
-  }
-  if (infl && tid == 0) letkf_inflation_estimate((size_t)(grp * a.npts + col), M, infl_s);
+  hipLaunchKernelGGL(kern, dim3((unsigned)((a.npts + 15) / 16 * 16)), dim3((unsigned)nth), lds, s, a);
+  return hipGetLastError();
 }
 
 template <int MODE, typename E, int NTMAX, bool SLAB, bool CTRL>
@@ -820,6 +646,23 @@ hipError_t launch_letkf(const LetkfArgs& a, const LetkfGroups* grp, int mode, El
     return letkf_launch<kLetkfWeights, double>(a, grp, s);
   }
   return hipErrorInvalidValue;
+}
+
+hipError_t launch_letkf_cv(const LetkfArgs& a, const LetkfCv& cv, hipStream_t s) {
+  if (a.M < 4 || a.M > kLetkfMaxM || a.npts < 0 || letkf_lds_bytes(a.M) > 160 * 1024) return hipErrorInvalidValue;
+  if (cv.ngroups < 2 || cv.ngroups > a.M || !cv.perm || !cv.nind || !cv.C || !a.Tw) return hipErrorInvalidValue;
+  if (a.infl || a.dc) return hipErrorInvalidValue;  // (out of scope: the driver refuses both before any launch)
+  if (a.Yp_in && (!a.ym_in || !a.ym_out || !a.Yp_out)) return hipErrorInvalidValue;
+  if (a.npts == 0) return hipSuccess;
+  if ((a.npts + 15) / 16 * 16 > 0x7FFFFFF0L) return hipErrorInvalidValue;
+  LetkfCvArgs ca{};
+  static_cast<LetkfArgs&>(ca) = a;
+  ca.cv = cv;
+  const int nth = letkf_threads(a.M);
+  const size_t lds = letkf_lds_bytes(a.M);
+  if (nth <= 256) return letkf_cv_launch_as<256>(ca, nth, lds, s);
+  if (nth <= 512) return letkf_cv_launch_as<512>(ca, nth, lds, s);
+  return letkf_cv_launch_as<1024>(ca, nth, lds, s);
 }
 
 hipError_t launch_letkf_obs_factor(long P, const long* off, const int* cnt, const int* idx, double* wts, const double* ob_vert,

@@ -14,6 +14,11 @@
 //   cap    the context's cap on the local obs of a solve (efa_ctx_set_letkf_obs_cap), checked against the call before
 //          any launch: k_letkf_cap behind every list build (letkf_build_lists), so the obs', the grid's, the nodes' and the probe's
 //          lists are capped in one place.  The plain and the interp cycles and efa_letkf_weights_dev serve it; the slab entries refuse it.
+//   cross validation  the context's member groups (efa_ctx_set_letkf_cross_validation), checked against the call before
+//          any launch: every solve runs k_letkf_cv, which leaves the recentred cross-validated T beside the plain w; the obs block's
+//          rows are mapped in that launch, the state always by k_letkf_interp (without a mesh: on the unit mesh whose nodes are the
+//          columns).  The plain and the interp cycles and efa_letkf_weights_dev serve it; the slab entries, and any call with an
+//          inflation field or a control set, are refused while it is on.
 #include "efa_driver.h"
 
 #include <cmath>
@@ -281,6 +286,35 @@ int letkf_check_cap(const efa_ctx* c, const char* who, bool served, long P, long
   return EFA_OK;
 }
 
+// The cross-validation setting against a call, before any launch.  Served by the plain and the interp cycles and
+// efa_letkf_weights_dev, without an inflation field and without a control; nsolve: the state's solve points of the call (< 0: none).
+int letkf_check_cv(const efa_ctx* c, const char* who, bool slab, int M, long nsolve) {
+  if (!c->cv_on) return EFA_OK;
+  if (slab)
+    return fail(EFA_ERR_INVALID, "%s: a LETKF cross validation is set (efa_ctx_set_letkf_cross_validation): the solves per (slab group, "
+                "column) under it are out of scope", who);
+  if (c->li_field)
+    return fail(EFA_ERR_INVALID, "%s: a LETKF cross validation and a LETKF inflation field are both set: the sub-solves under a per-point "
+                "factor, and its estimate under them, are out of scope", who);
+  if (c->lc_xc)
+    return fail(EFA_ERR_INVALID, "%s: a LETKF cross validation and a LETKF control are both set: the cross-validated cycle applies the "
+                "pairs [T | w], which have no place for the control's weight vector", who);
+  if (c->cv_M != M) return fail(EFA_ERR_INVALID, "%s: the LETKF cross validation was set for %d members, the call has %d", who, c->cv_M, M);
+  if (c->cv_stats && nsolve >= 0 && c->cv_nsolve != nsolve)
+    return fail(EFA_ERR_INVALID, "%s: the LETKF cross validation's statistics were set for %ld solve points, the call has %ld (columns, "
+                "nodes or probe points)", who, c->cv_nsolve, nsolve);
+  return EFA_OK;
+}
+
+// ... as the launch takes it, with the scratch for `npts` points; stats: where the sub-solves' statistics go, or null
+int letkf_cv_args(efa_ctx* c, int M, long npts, double* stats, LetkfCv* out) {
+  if (c->cv_C.reserve((size_t)(npts > 0 ? npts : 1) * M * M * sizeof(double)) != EFA_OK)
+    return fail(EFA_ERR_ALLOC, "LETKF cross validation: the scratch of %ld points x %d x %d doubles could not be allocated", npts, M, M);
+  const int* l = c->cv_lists.as<int>();
+  *out = LetkfCv{c->cv_ngroups, l, l + (size_t)c->cv_ngroups * M, c->cv_C.as<double>(), stats};
+  return EFA_OK;
+}
+
 // ... into the arguments of the obs block's launch (y_c) or of the columns' (x_c)
 void letkf_args_control(const efa_ctx* c, LetkfArgs* a, const LetkfObs& o, bool obs_block) {
   if (!c->lc_xc || !o.dc) return;  // (no obs: no solve, the driver copies the control)
@@ -310,6 +344,12 @@ int letkf_solve_points(efa_ctx* c, int M, long npts, const LetkfLists& lists, co
   LetkfArgs a = letkf_args(M, npts, lists, Yp_dev, o);
   a.Tw = Tw;
   a.stats = stats;
+  if (c->cv_on) {  // (checked: no groups, no inflation field) the recentred cross-validated T beside the same w
+    LetkfCv cv{};
+    EFA_TRY(letkf_cv_args(c, M, npts, c->cv_stats, &cv));
+    EFA_HIP(launch_letkf_cv(a, cv, c->stream));
+    return EFA_OK;
+  }
   letkf_args_inflation(c, &a, false);
   EFA_HIP(launch_letkf(a, grp, kLetkfWeights, Elem::f64, c->stream));
   return EFA_OK;
@@ -466,6 +506,12 @@ int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const double* ym_dev, co
   if (rows > 0) EFA_TRY(check_grid(EFA_LOC_GC, grid_lat, grid_lon, ncol, n_lead, rows));
   EFA_TRY(letkf_check_obs(who, P, ym_dev, Yp_dev, ob));
   EFA_TRY(letkf_check_cap(c, who, !slab, P, rows > 0 ? (mesh ? nodes.nnodes() : ncol) : -1));
+  EFA_TRY(letkf_check_cv(c, who, slab, M, rows > 0 ? (mesh ? nodes.nnodes() : ncol) : -1));
+  // under cross validation the state is always "solve the points, then apply their pairs": without a mesh on the
+  // unit mesh of one row whose nodes are the columns (a column then takes its own node's pair with the weight 1.0)
+  const bool cv = c->cv_on;
+  if (cv && !mesh) nodes = LetkfMesh{1, ncol, 1, 1};
+  const bool paired = mesh != nullptr || cv;
   if (c->li_field) {  // one factor per solve: per (group,) column or node
     long nsolve = -1;
     if (rows > 0) {
@@ -504,21 +550,30 @@ int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const double* ym_dev, co
     a.Yp_in = Yp_dev;
     a.ym_out = ymw;
     a.Yp_out = Yw;
-    letkf_args_inflation(c, &a, true);
-    letkf_args_control(c, &a, o, true);
-    EFA_HIP(launch_letkf(a, nullptr, kLetkfPerts, Elem::f64, s));
+    if (cv) {  // every ob's own recentred [T | w] into the context's buffer, its row mapped behind it by the same workgroup
+      if (c->cv_Tw.reserve((size_t)P * M * (M + 1) * sizeof(double)) != EFA_OK)
+        return fail(EFA_ERR_ALLOC, "%s: the obs block's pair buffer of %ld x %d x %d doubles could not be allocated", who, P, M, M + 1);
+      a.Tw = c->cv_Tw.as<double>();
+      LetkfCv cva{};
+      EFA_TRY(letkf_cv_args(c, M, P, nullptr, &cva));
+      EFA_HIP(launch_letkf_cv(a, cva, s));
+    } else {
+      letkf_args_inflation(c, &a, true);
+      letkf_args_control(c, &a, o, true);
+      EFA_HIP(launch_letkf(a, nullptr, kLetkfPerts, Elem::f64, s));
+    }
     EFA_HIP(launch_etkf_post(P, M, Yw, ymw, o.post_mean, o.post_var, s));
   }
   // ---- the state: the grid's lists (the obs' are consumed: the stream is in order), then ONE launch -----------------------------
   //      (with a mesh: the nodes' lists, then the node solve and the interpolate-and-apply launch)
   LetkfLists glists;
-  const long nnodes = mesh ? nodes.nnodes() : 0;
+  const long nnodes = paired ? nodes.nnodes() : 0;
   double* node_stats = col_stats_dev;
   LetkfGroups groups{};
   if (rows > 0 && slab) EFA_TRY(letkf_slab_groups(c, n_lead, &groups));
   const LetkfGroups* grp = (rows > 0 && slab) ? &groups : nullptr;
   const size_t ngr = slab ? (size_t)groups.ngroups : 1;  // solves per column or node
-  if (rows > 0 && mesh) {
+  if (rows > 0 && paired) {
     if (c->letkf_Tw.reserve(ngr * (size_t)nnodes * M * (M + 1) * sizeof(double)) != EFA_OK)
       return fail(EFA_ERR_ALLOC, "%s: the node-pair buffer of %zu groups x %ld nodes x %d x %d doubles could not be allocated", who, ngr,
                   nnodes, M, M + 1);
@@ -545,7 +600,7 @@ int letkf_cycle(efa_ctx* c, const StateRows& r, long P, const double* ym_dev, co
     c->obs_iv.pending = true;
     EFA_HIP(hipEventRecord(c->state_iv[0].begin, s));
   }
-  if (rows > 0 && mesh) {  // (P == 0: no lists, every node has the pair (I, 0) and no column changes)
+  if (rows > 0 && paired) {  // (P == 0: no lists, every node has the pair (I, 0) and no column changes)
     EFA_TRY(letkf_solve_points(c, M, nnodes, glists, Yp_dev, o, grp, c->letkf_Tw.as<double>(), node_stats));
     EFA_TRY(letkf_interp_launch(c, r, nodes, n_lead, c->letkf_Tw.as<double>(), node_stats, grp));
     c->state_launches = 2;
@@ -612,6 +667,7 @@ int letkf_weights(efa_ctx* c, int M, long P, const double* ym_dev, const double*
   if (npts > 0 && (!pt_lat || !pt_lon || !Tw_dev)) return fail(EFA_ERR_INVALID, "%s: null point or output array", who);
   EFA_TRY(letkf_check_obs(who, P, ym_dev, Yp_dev, ob));
   EFA_TRY(letkf_check_cap(c, who, !slab, P, npts));
+  EFA_TRY(letkf_check_cv(c, who, slab, M, npts));
   if (npts == 0) return EFA_OK;
   if (c->li_field) {
     if (slab) EFA_TRY(letkf_groups(c, n_lead));

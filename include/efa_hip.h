@@ -596,6 +596,45 @@ int efa_ctx_set_letkf_obs_cap(efa_ctx *ctx, const int *ob_class /* host [P], NUL
                               const long *cap /* host [nclass], NULL: off */, int nclass, double *reach_dev /* [nsolve] or NULL */,
                               long nsolve);
 
+/* ---- LETKF: cross-validated perturbation update over member groups -----
+ * (Buehner 2020, Mon. Wea. Rev. 148, 2265-2282)  Context
+ * state in the style of the cap above.  Member m carries the label
+ * group_of_member[m] in 0..ngroups-1.  At every solve point (a column, a node
+ * of a mesh, an ob's own position, a probe point), on exactly the tapers and
+ * flags of the plain solve, with C = sum_k (rho_k/r_k) Yp_k^T Yp_k:
+ *   mean      w = ((M-1) I + C)^-1 g: the full-ensemble solve, unchanged, as
+ *             are n_local, dfs and sweeps of the statistics;
+ *   group k   I = the members with another label (ascending), H = those with
+ *             label k, m = |I|, a = m - 1, J = I_m - 1 1^T / m,
+ *             a I + J C[I,I] J = V diag(mu) V^T (the same Jacobi),
+ *             G = V diag(1 / (mu (1 + sqrt(a / mu)))) V^T,
+ *             T[I,H] = -J G J C[I,H], T[H,H] = identity;
+ *   recentre  T <- T - (T 1 / M) 1^T;
+ *   apply     mean += X' w, X' <- X' T, so that a held-out member's
+ *             perturbation is updated with the gain of the other groups alone
+ *             and the posterior perturbations sum to zero.
+ * T is not symmetric.  The state is always applied by the interpolate-and-
+ * apply launch, without a mesh on a unit mesh whose nodes are the columns: two
+ * state launches, a node-pair buffer of nsolve M (M+1) doubles and a scratch
+ * of nsolve M M doubles (P of each for the obs block), held by the context.
+ * cv_stats_dev [nsolve][2] (device, or NULL) receives for the STATE's solve
+ * points the sum of the ngroups sub-solves' sweeps and their largest
+ * max mu / min mu ((0, 0) where no ob reaches the point); nsolve is read with
+ * cv_stats_dev only.
+ * Served by efa_letkf_cycle_dev / _f32_dev, efa_letkf_cycle_interp_dev /
+ * _f32_dev and efa_letkf_weights_dev (whose T is then the recentred one); these
+ * refuse, with EFA_ERR_INVALID before any launch, an M (and with cv_stats_dev
+ * an nsolve) that differs from the call's.  While the setting is on, the slab
+ * entries, any call with a LETKF inflation field set and any call with a
+ * control set are refused likewise.  efa_letkf_interp_apply_dev / _f32_dev,
+ * the EnSRF, ETKF and impact entries IGNORE it.  The setter refuses (the
+ * setting stays as it was) M outside 4..136, ngroups < 2, a label outside
+ * 0..ngroups-1, an unused label, a group that leaves fewer than 2 members
+ * outside it, a negative nsolve and a misaligned cv_stats_dev.
+ * group_of_member == NULL turns it off. */
+int efa_ctx_set_letkf_cross_validation(efa_ctx *ctx, const int *group_of_member /* host [M], NULL: off */, int M, int ngroups,
+                                       double *cv_stats_dev /* [nsolve][2] or NULL */, long nsolve);
+
 /* ---- device memory for callers without their own allocator -------------*/
 int efa_malloc(efa_ctx *ctx, size_t bytes, void **dev_out);
 int efa_free(efa_ctx *ctx, void *dev);
